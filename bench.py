@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the GECCO CRF hot path on MI355X (contract: see the task statement).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+The timed region is exactly K steps after W untimed ones; `ms_per_step` is its time / K.  `--dump-outputs DIR` writes what
+the last timed step computed (marginals and Viterbi labels of the batch, rank 0) to DIR as .npy files: the inputs are
+generated from fixed seeds, so two builds can be compared output for output.
 
 A "step" is one pass of the hot path over one resident batch: the windowed forward-backward
 marginals of every gene (the reference's `ClusterCRF.predict_probabilities` arithmetic,
@@ -85,7 +89,11 @@ def main() -> None:
                     help="weight law of the synthetic model: SURVEY.md 8d to the letter (default) or 'genome' (weights shifted so that "
                          "most genes lean to label 0, as under GECCO's embedded model: the side point `roofline_genome`)")
     ap.add_argument("--min-region-ms", type=float, default=50.0,
-                    help="the K-step timed region is repeated until this much time has been measured; ms_per_step is the median region")
+                    help="side points only (8-way shard, strong scaling): their K-step region is repeated until this much time has been "
+                         "measured and the median region is reported.  The headline is always exactly --steps timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy: P(label 1) per gene (float64) and "
+                         "the Viterbi labels (float32); a fixed, seeded sample of genes with their indices when that exceeds 64 MB")
     ap.add_argument("--no-levels", action="store_true", help="skip the host-buffer / tables / object API levels (SURVEY.md 8d)")
     ap.add_argument("--no-8d", "--no-genome", dest="no_8d", action="store_true", help="skip the second roofline point on the other weight law")
     ap.add_argument("--no-c4", action="store_true", help="skip the 8-way shard point (profiles: keeps the per-kernel averages on one workload)")
@@ -96,6 +104,8 @@ def main() -> None:
                     help="pipelined: one launch per step = window tiles of batch k + Viterbi workgroups of batch k - 1 "
                          "(gecco_crf_plan_run_decode_pipelined, + one flush); two-launch: gecco_crf_plan_run_decode")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     import torch
 
@@ -235,6 +245,8 @@ def main() -> None:
             for _ in range(steps):
                 self.step(schedule)
             self.issue_s = (time.perf_counter() - t0) / max(steps, 1)  # what the HOST spent per step (enqueue only, nothing waited for)
+            # the lane whose buffers receive the last step's marginals and, with the flush, its labels (batches alternate between lanes)
+            self.last_lane = self.lanes[(self.turn - 1) % len(self.lanes)] if self.turn else self.lanes[0]
             self.flush()
             torch.cuda.synchronize(dev)
             barrier()
@@ -293,14 +305,18 @@ def main() -> None:
 
     for ln in res.lanes:
         ln["plan"].viterbi_stats(reset=True)
-    regions = res.timed_regions(args.steps, args.warmup, args.preroll_ms, args.min_region_ms)
-    elapsed = float(np.median(regions))
+    # the headline: exactly --steps timed steps, one region between barrier + device synchronisation on both sides
+    elapsed = res.timed(args.steps, args.warmup, args.preroll_ms)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (before anything else writes the lane's buffers)
+        ln = res.last_lane
+        dumped = _dump_outputs(args.dump_outputs, ln["d_p"][:n_genes], None if args.windowed_only else ln["d_y"][:n_genes])
     vstats = {}
-    if not args.windowed_only:  # what the Viterbi side met in those regions (crf_vd_short.hpp: the exactness margin)
+    if not args.windowed_only:  # what the Viterbi side met in those steps (crf_vd_short.hpp: the exactness margin)
         for ln in res.lanes:
             for k, v in ln["plan"].viterbi_stats(reset=True).items():
                 vstats[k] = vstats.get(k, 0) + v
-        vstats["batches"] = args.steps * len(regions) + args.warmup
+        vstats["batches"] = args.steps + args.warmup
     total_genes = all_sum(n_genes)
     pipelined = args.schedule == "pipelined" and not args.windowed_only
     # the other schedule next to the headline (a quarter of the steps)
@@ -328,7 +344,7 @@ def main() -> None:
     # behind the same pipelined call, and the window kernel stays the dominant one)
     one_launch = pipelined and int(np.diff(wl["contig_ptr"]).max(initial=0)) <= 2048
     if one_launch:
-        # (pre-rolled like the timed regions -- after short regions with a wait each, the device is not at its clocks: the driver's
+        # (pre-rolled like the timed steps -- after short regions with a wait each, the device is not at its clocks: the driver's
         # --steps 20 run measured 33.7 us here where the default run measures 31.9 -- and the median of three series)
         t_pre = time.perf_counter()
         while (time.perf_counter() - t_pre) * 1e3 < args.preroll_ms:
@@ -414,15 +430,13 @@ def main() -> None:
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3,
-        "ms_per_step_single_region": regions[0] / args.steps * 1e3,
-        # the host's share: wall time of the enqueue loop per step (last region; no wait inside).  A batch whose step is no longer than
+        # the host's share: wall time of the enqueue loop per step (no wait inside).  A batch whose step is no longer than
         # this is bound by the launch path (HIP runtime ~3 us + this library ~1 us + ctypes), not by the GPU
         "host_issue_us_per_step": res.issue_s * 1e6,
-        "timed_regions": {"count": len(regions), "steps_each": args.steps, "min_total_ms": args.min_region_ms,
-                          "ms_per_step_min": min(regions) / args.steps * 1e3, "ms_per_step_max": max(regions) / args.steps * 1e3,
-                          "note": "every region = exactly `steps` steps between barrier + device synchronisation on both sides, "
-                                  "pipelines empty at its start and flushed at its end; ms_per_step / value = the MEDIAN region, "
-                                  "ms_per_step_single_region = the first one"},
+        "timed_region": {"steps": args.steps, "ms": elapsed * 1e3,
+                         "note": "exactly `steps` steps between barrier + device synchronisation on both sides, pipelines empty at "
+                                 "its start and flushed at its end"},
+        "dumped_outputs": dumped,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -793,6 +807,42 @@ def _masked_stream(pattern, k, n):
     if rc:
         raise SystemExit(f"hipExtStreamCreateWithCUMask failed: {rc}")
     return h.value
+
+
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SAMPLE_SEED = 0x6ECC0
+
+
+def _dump_outputs(out_dir, p, y=None, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: the arrays a caller of the timed path receives for one batch -- `p` (P(label 1) per gene, float64) and
+    `y` (Viterbi labels, written as float32; None with --windowed-only) -- as out_dir/marginals.npy and out_dir/labels.npy.
+    When they exceed `max_bytes` in all, the same arrays are written for a fixed, seeded sample of genes (ascending), with the
+    sampled gene indices as out_dir/gene_index.npy (float64: exact).  `p` and `y` are tensors of one length on any device.
+    Returns {file name: bytes written}."""
+    import torch
+
+    n = int(p.shape[0])
+    per_gene = 8 + (4 if y is not None else 0)
+    header = 128  # (an .npy header of a 1-d array)
+    idx = None
+    if n * per_gene + 2 * header > max_bytes:
+        m = (max_bytes - 3 * header) // (per_gene + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=m, replace=False))
+        sel = torch.from_numpy(idx).to(p.device)
+        p = p[sel]
+        y = y[sel] if y is not None else None
+    arrays = {"marginals": p.to(torch.float64).cpu().numpy()}
+    if y is not None:
+        arrays["labels"] = y.to(torch.float32).cpu().numpy()
+    if idx is not None:
+        arrays["gene_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, np.ascontiguousarray(a))
+        written[name + ".npy"] = os.path.getsize(path)
+    return written
 
 
 def _ulp_report(a, b):

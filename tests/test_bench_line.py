@@ -75,3 +75,41 @@ def test_detail_file_roundtrip(tmp_path):
     p = bline.write_detail(str(tmp_path / "d.json"), _canned())
     back = json.load(open(p))
     assert back["levels"]["x"].startswith("y") and back["roofline"]["nan_field"] is None
+
+
+def test_dump_outputs_writes_the_arrays_and_samples_past_the_budget(tmp_path):
+    """bench.py --dump-outputs: the whole batch as float64 marginals + float32 labels; past the byte budget a seeded sample of
+    genes (the same one every run) with its indices, and never more than the budget in all."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    n = 10_000
+    rng = np.random.default_rng(1)
+    p_host, y_host = rng.random(n), (rng.random(n) < 0.3).astype(np.int8)
+    p, y = torch.from_numpy(p_host), torch.from_numpy(y_host)
+
+    full = bench._dump_outputs(str(tmp_path / "full"), p, y)
+    assert set(full) == {"marginals.npy", "labels.npy"}
+    got_p, got_y = np.load(tmp_path / "full" / "marginals.npy"), np.load(tmp_path / "full" / "labels.npy")
+    assert got_p.dtype == np.float64 and got_p.tobytes() == p_host.tobytes()
+    assert got_y.dtype == np.float32 and np.array_equal(got_y, y_host.astype(np.float32))
+
+    only_p = bench._dump_outputs(str(tmp_path / "windowed"), p)
+    assert set(only_p) == {"marginals.npy"}
+
+    budget = 40_000
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"sample{k}"
+        sizes = bench._dump_outputs(str(d), p, y, max_bytes=budget)
+        assert set(sizes) == {"marginals.npy", "labels.npy", "gene_index.npy"} and sum(sizes.values()) <= budget
+        runs.append({name: np.load(d / name) for name in sizes})
+    idx = runs[0]["gene_index.npy"]
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    ii = idx.astype(np.int64)
+    assert runs[0]["marginals.npy"].tobytes() == p_host[ii].tobytes()
+    assert np.array_equal(runs[0]["labels.npy"], y_host[ii].astype(np.float32))
+    for name in runs[0]:
+        assert runs[0][name].tobytes() == runs[1][name].tobytes(), name
