@@ -163,6 +163,13 @@ SIGNATURES = {
          ctypes.POINTER(ctypes.c_int64)],
     ),
     "gecco_crf_buffer_free": (None, [_vp]),
+    "gecco_crf_trainer_create": (
+        ctypes.c_int, [ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32,
+                       ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.POINTER(_vp)]
+    ),
+    "gecco_crf_trainer_eval": (ctypes.c_int, [_vp, _c_f64p, _c_f64p, _c_f64p]),
+    "gecco_crf_trainer_num_windows": (ctypes.c_int64, [_vp]),
+    "gecco_crf_trainer_free": (None, [_vp]),
     "gecco_crf_plan_time_windowed": (
         ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
     ),
@@ -1054,3 +1061,48 @@ class Plan:
             )
         )
         return ms.value
+
+
+class Trainer:
+    """Training set of a 2-label CRF resident on one device (``gecco_crf_trainer_*``): ``eval(w)`` returns the summed
+    negative log-likelihood of every training window and its gradient over the ``num_features`` generated features."""
+
+    def __init__(self, seq_ptr, item_ptr, attr_id, labels, num_attrs: int, window: int, step: int, state_fid, trans_fid,
+                 num_features: int, device: int = 0):
+        self._lib = load_library()
+        self._h = None
+        seq_ptr, item_ptr, attr_id, labels = _i32(seq_ptr), _i32(item_ptr), _i32(attr_id), _i32(labels)
+        state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
+        if int(num_attrs) < 1 or state_fid.size % int(num_attrs) != 0:
+            raise ValueError("state_fid must have num_attrs * L entries")
+        L = state_fid.size // int(num_attrs)  # (the library trains 2-label models only and says so for any other L)
+        if trans_fid.size != L * L:
+            raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
+        keep = [seq_ptr, item_ptr, attr_id, labels, state_fid, trans_fid]
+        keep = [a if a.size else np.zeros(1, dtype=np.int32) for a in keep]
+        h = _vp()
+        _check(self._lib.gecco_crf_trainer_create(
+            int(device), _ptr(keep[0], _c_i32p), len(seq_ptr) - 1, _ptr(keep[1], _c_i32p), _ptr(keep[2], _c_i32p),
+            _ptr(keep[3], _c_i32p), int(num_attrs), L, int(window), int(step), _ptr(keep[4], _c_i32p),
+            _ptr(keep[5], _c_i32p), int(num_features), ctypes.byref(h)))
+        self._h = h
+        self.num_features = int(num_features)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.gecco_crf_trainer_free(h)
+
+    @property
+    def num_windows(self) -> int:
+        return int(self._lib.gecco_crf_trainer_num_windows(self._h))
+
+    def eval(self, w):
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.num_features,):
+            raise ValueError(f"expected {self.num_features} weights, got shape {w.shape}")
+        g = np.empty(max(self.num_features, 1), dtype=np.float64)
+        f = ctypes.c_double(0.0)
+        wb = w if w.size else np.zeros(1)
+        _check(self._lib.gecco_crf_trainer_eval(self._h, _ptr(wb, _c_f64p), ctypes.byref(f), _ptr(g, _c_f64p)))
+        return f.value, g[:self.num_features]

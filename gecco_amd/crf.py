@@ -277,6 +277,36 @@ def _annotate_all(genes: List[Any], probs: List[float], w1: Dict[str, float]) ->
     return out
 
 
+# the state keys of a pickled sklearn_crfsuite.CRF [EXT], in the order the shipped model has them
+_CRF_STATE_KEYS = ("algorithm", "min_freq", "all_possible_states", "all_possible_transitions", "c1", "c2", "max_iterations",
+                   "num_memories", "epsilon", "period", "delta", "linesearch", "max_linesearch", "calibration_eta",
+                   "calibration_rate", "calibration_samples", "calibration_candidates", "calibration_max_trials", "pa_type",
+                   "c", "error_sensitive", "averaging", "variance", "gamma", "modelfile", "verbose", "trainer_cls",
+                   "training_log_", "_tagger", "_info_cached")
+
+
+def _extract_training(sequence: Sequence[Any], feature_type: str) -> Tuple[List[List[str]], List[str]]:
+    """``features.extract_features_*`` / ``extract_labels_*`` with ``empty=True`` (gecco/crf/features.py:13-68): per
+    item the distinct domain names in order, and "1" for a probability above 0.5."""
+    feats: List[List[str]] = []
+    labels: List[str] = []
+    if feature_type == "protein":
+        for gene in sequence:
+            feats.append(list(dict.fromkeys(d.name for d in gene.protein.domains)))
+            labels.append("1" if gene.average_probability > 0.5 else "0")
+    else:
+        for gene in sequence:
+            doms = gene.protein.domains
+            if doms:
+                for d in doms:
+                    feats.append([d.name])
+                    labels.append("1" if d.probability > 0.5 else "0")
+            else:
+                feats.append([])
+                labels.append("1" if gene.average_probability > 0.5 else "0")
+    return feats, labels
+
+
 def _default_devices() -> List[int]:
     env = os.environ.get("GECCO_HIP_DEVICES", "").strip()
     if env:
@@ -303,7 +333,10 @@ class ClusterCRF(object):
         """
         if model_path is None:
             model_path = cls._embedded_model_dir()
-        record = pickle_model.load_model_dir(model_path)
+        return cls._from_record(pickle_model.load_model_dir(model_path))
+
+    @classmethod
+    def _from_record(cls, record: "pickle_model.PickledRecord") -> "ClusterCRF":
         st = record.state
         self = cls.__new__(cls)
         self.feature_type = st.get("feature_type", "protein")
@@ -588,15 +621,39 @@ class ClusterCRF(object):
             c0 = c1
         return out
 
-    # ------------------------------------------------------------------ training (delegated)
-    def fit(self, genes: Iterable[Any], **kwargs: Any) -> None:
-        """Training is outside this engine's scope: delegate to the reference
-        implementation when sklearn-crfsuite is importable (``gecco/crf/__init__.py:275-378``)."""
+    # ------------------------------------------------------------------ training
+    def fit(self, genes: Iterable[Any], *, select: Optional[float] = None, shuffle: bool = True, cpus: Optional[int] = None,
+            correction_method: Optional[str] = None) -> None:
+        """Fit the CRF to labelled genes (``gecco/crf/__init__.py:275-378``).
+
+        Without sklearn-crfsuite, or with ``GECCO_AMD_FIT=native``, training runs here: the instances are built as the
+        reference builds them (genes sorted by sequence, domains by start, sequences grouped and sorted by start and, with
+        ``shuffle``, shuffled with the global ``random``; every sliding window of every sequence, no padding), features
+        are generated as CRFsuite does, and L-BFGS (OWL-QN when ``c1 > 0``) runs on the host around an objective and
+        gradient evaluated on the device (``gecco_amd/train.py``, ``csrc/crf_train.hip``).  ``cpus`` is accepted and
+        ignored.  With sklearn-crfsuite importable and ``GECCO_AMD_FIT`` unset or ``reference``, and whenever ``select``
+        is given (Fisher feature selection needs statsmodels), the call is delegated to the reference class."""
+        mode = os.environ.get("GECCO_AMD_FIT", "").strip().lower()
+        if mode not in ("", "native", "reference"):
+            raise ValueError(f"GECCO_AMD_FIT must be 'native' or 'reference', not {mode!r}")
+        native = mode == "native"
+        if not native and mode == "":
+            try:
+                import sklearn_crfsuite  # noqa: F401
+            except Exception:
+                native = True
+        if native and select is None:
+            self._fit_native(genes, shuffle=shuffle)
+            return
+        self._fit_reference(genes, select=select, shuffle=shuffle, cpus=cpus, correction_method=correction_method)
+
+    def _fit_reference(self, genes: Iterable[Any], **kwargs: Any) -> None:
+        """Delegate to the reference implementation (needs GECCO with sklearn-crfsuite)."""
         try:
             from gecco.crf import ClusterCRF as _Reference  # type: ignore
         except Exception as err:
             raise NotImplementedError(
-                "ClusterCRF.fit needs GECCO with sklearn-crfsuite (L-BFGS training runs in CRFsuite)"
+                "ClusterCRF.fit with feature selection needs GECCO with sklearn-crfsuite and statsmodels"
             ) from err
         ref = _Reference(self.feature_type, self.algorithm, self.window_size, self.window_step,
                          **{k: v for k, v in self._options.items() if k != "algorithm"})
@@ -609,13 +666,112 @@ class ClusterCRF(object):
         self.__dict__.pop("_ses", None)  # bound to the previous model
         self.__dict__.update(fitted.__dict__)
 
+    def training_instances(self, genes: Iterable[Any], *, shuffle: bool = True) -> Tuple[List[List[List[str]]], List[List[str]]]:
+        """The reference's preparation of the training data (``gecco/crf/__init__.py:304-367``), with its warnings and
+        errors: per sequence, the attribute names of every item and the labels."""
+        import random
+
+        if self.feature_type not in ("protein", "domain"):
+            raise ValueError(f"invalid feature type: {self.feature_type!r}")
+        genes = sorted(genes, key=operator.attrgetter("source.id"))
+        for gene in genes:
+            gene.protein.domains.sort(key=operator.attrgetter("start"))
+        groups = itertools.groupby(genes, key=operator.attrgetter("source.id"))
+        sequences = [sorted(group, key=operator.attrgetter("start")) for _, group in groups]
+        if shuffle:
+            random.shuffle(sequences)
+        all_feats: List[List[List[str]]] = []
+        all_labels: List[List[str]] = []
+        for sequence in sequences:
+            feats, labels = _extract_training(sequence, self.feature_type)
+            if all(label == "0" for label in labels):
+                warnings.warn(f"only negative labels found in sequence {sequence[0].source.id!r}", UserWarning)
+            elif all(label == "1" for label in labels):
+                warnings.warn(f"only positive labels found in sequence {sequence[0].source.id!r}", UserWarning)
+            if len(feats) != len(labels):
+                raise ValueError("different number of features and labels found, something is wrong")
+            if len(feats) < self.window_size:
+                raise ValueError(f"{sequence[0].source.id!r} has not enough observations ({len(feats)}) for requested window size ({self.window_size})")
+            all_feats.append(feats)
+            all_labels.append(labels)
+        return all_feats, all_labels
+
+    def _fit_native(self, genes: Iterable[Any], *, shuffle: bool = True) -> None:
+        from . import train
+
+        params = train.trainer_params(self._options)
+        feats, labels = self.training_instances(genes, shuffle=shuffle)
+        ts = train.build_training_set(feats, labels, self.window_size, self.window_step, min_freq=float(params["min_freq"]),
+                                      all_possible_states=bool(params["all_possible_states"]),
+                                      all_possible_transitions=bool(params["all_possible_transitions"]))
+        devices = self.devices or [0]
+        result = train.fit_training_set(ts, params, device=int(devices[0]))
+        self._adopt_model_blob(train.model_blob(ts, result.x))
+        self.training_result_ = result
+
+    def _adopt_model_blob(self, blob: bytes) -> None:
+        """Become the fitted model whose CRFsuite file is `blob`: a new ``sklearn_crfsuite.CRF`` record with the keys of
+        the shipped one (the options given are set, the rest stays None) inside a ``gecco.crf.ClusterCRF`` record, loaded
+        exactly as ``trained()`` loads a model directory."""
+        resource = pickle_model.new_record("sklearn_crfsuite._fileresource", "FileResource", {
+            "name": None, "auto": True, "keep_tempfiles": False, "suffix": ".crfsuite", "prefix": "model", "fd": None,
+            "__FILE_RESOURCE_DATA__": bytes(blob)})
+        crf_state: Dict[str, Any] = {k: None for k in _CRF_STATE_KEYS}
+        crf_state.update({k: v for k, v in self._options.items() if k in crf_state})
+        crf_state.update(algorithm=self.algorithm, modelfile=resource, verbose=bool(self._options.get("verbose", False)))
+        crf = pickle_model.new_record("sklearn_crfsuite.estimator", "CRF", crf_state)
+        record = pickle_model.new_record("gecco.crf", "ClusterCRF", {
+            "feature_type": self.feature_type, "window_size": self.window_size, "window_step": self.window_step,
+            "algorithm": self.algorithm, "significance": None, "significant_features": None, "model": crf,
+            "_options": dict(self._options)})
+        devices, reference_bits = self.devices, self.reference_bits
+        fitted = type(self)._from_record(record)
+        self.__dict__.pop("_ses", None)  # bound to the previous model
+        self.__dict__.update(fitted.__dict__)
+        self.devices, self.reference_bits = devices, reference_bits
+
+    def __reduce_ex__(self, protocol: int):
+        """A fitted object pickles as GECCO's own ``gecco.crf.ClusterCRF`` record -- ``gecco train`` saves its model with a
+        plain ``pickle.dump(crf, f, protocol=4)`` -- with the bytes ``save`` writes.  A plain pickler writes a class path
+        only if it can import it, so every class the record tree names (``gecco.crf.ClusterCRF``,
+        ``sklearn_crfsuite.estimator.CRF``, ``sklearn_crfsuite._fileresource.FileResource``, and
+        ``pycrfsuite._logparser.TrainLogParser`` for a model that carries a training log) has to be importable --
+        as in every GECCO install, which depends on sklearn-crfsuite; stock GECCO could not load the file without them
+        either.  Otherwise ``PicklingError`` names what is missing; ``save`` writes the record without importing them."""
+        if self._record is None:
+            raise pickle_model.pickle.PicklingError("only a fitted ClusterCRF can be pickled")
+        self._sync_record()
+        missing = pickle_model.unresolved_globals(self._record)
+        if missing:
+            raise pickle_model.pickle.PicklingError(
+                f"pickling a ClusterCRF as GECCO's record needs {', '.join(missing)} to be importable; "
+                "use save() instead, which writes the same record without them")
+        return self._record.__reduce_ex__(protocol)
+
+    # (copies stay copies of this class: __reduce_ex__ above is for pickling only)
+    def __copy__(self) -> "ClusterCRF":
+        new = object.__new__(type(self))
+        new.__dict__.update(self.__dict__)
+        return new
+
+    def __deepcopy__(self, memo: Dict[int, Any]) -> "ClusterCRF":
+        import copy
+
+        new = object.__new__(type(self))
+        memo[id(self)] = new
+        new.__dict__.update(copy.deepcopy(self.__dict__, memo))
+        return new
+
+    def _sync_record(self) -> None:
+        st = self._record.state
+        st.update(feature_type=self.feature_type, window_size=self.window_size, window_step=self.window_step,
+                  algorithm=self.algorithm, significance=self.significance,
+                  significant_features=self.significant_features)
+
     def save(self, model_path: Union[str, os.PathLike]) -> None:
         """Write ``model.pkl`` (protocol 4) + ``model.pkl.md5`` loadable by stock GECCO
         (``gecco/crf/__init__.py:380-402``)."""
         if self._record is None:
             raise NotFittedError("This ClusterCRF instance is not fitted yet.")
-        st = self._record.state
-        st.update(feature_type=self.feature_type, window_size=self.window_size, window_step=self.window_step,
-                  algorithm=self.algorithm, significance=self.significance,
-                  significant_features=self.significant_features)
+        self._sync_record()
         pickle_model.dump_model_dir(self._record, model_path)

@@ -13,6 +13,7 @@
 #include "crf_plan.hpp"
 #include "crf_session.hpp"
 #include "crf_tables.hpp"
+#include "crf_train.hpp"
 
 using namespace gecco;
 
@@ -91,7 +92,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 221; }
+GECCO_API int gecco_crf_version(void) { return 230; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -911,3 +912,42 @@ GECCO_API int gecco_crf_tsv_format(int64_t n_rows, int32_t n_cols, const int32_t
     GECCO_GUARD_END
 }
 GECCO_API void gecco_crf_buffer_free(uint8_t *p) { std::free(p); }
+
+// ---- training (ABI 2.3.0) ---------------------------------------------------------------------
+struct gecco_crf_trainer {
+    Trainer *t = nullptr;
+    ~gecco_crf_trainer() { trainer_destroy(t); }
+};
+
+GECCO_API int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr,
+                                       const int32_t *attr_id, const int32_t *labels, int32_t num_attrs, int32_t num_labels,
+                                       int32_t window, int32_t step, const int32_t *state_fid, const int32_t *trans_fid,
+                                       int32_t num_features, gecco_crf_trainer **out) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    auto h = std::make_unique<gecco_crf_trainer>();
+    int rc = trainer_create(device, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step, state_fid,
+                            trans_fid, num_features, &h->t);
+    if (rc) return rc;
+    *out = h.release();
+    return GECCO_CRF_OK;
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_trainer_eval(gecco_crf_trainer *t, const double *w, double *f, double *g) {
+    if (!t) return GECCO_CRF_EINVAL;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    return trainer_eval(t->t, w, f, g);
+    GECCO_GUARD_END
+}
+
+GECCO_API int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t) { return t ? trainer_num_windows(t->t) : -1; }
+
+GECCO_API void gecco_crf_trainer_free(gecco_crf_trainer *t) {
+    if (!t) return;
+    DeviceGuard guard;
+    delete t;
+}

@@ -1,0 +1,19 @@
+// Training objective of the 2-label linear-chain CRF on the device (gecco_crf_trainer_*, include/gecco_crf.h):
+// the negative log-likelihood of every training window ([EXT] CRFsuite crf1d_encode's objective, without the
+// regularisation terms the host optimiser adds) and its gradient with respect to the generated features.
+#pragma once
+#include <cstdint>
+
+namespace gecco {
+
+struct Trainer;
+
+// Arguments as gecco_crf_trainer_create; returns GECCO_CRF_* (message via set_error).
+int trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
+                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
+                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, Trainer **out);
+int trainer_eval(Trainer *t, const double *w, double *f, double *g);
+int64_t trainer_num_windows(const Trainer *t);
+void trainer_destroy(Trainer *t);
+
+}  // namespace gecco

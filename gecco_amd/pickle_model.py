@@ -15,7 +15,7 @@ import hashlib
 import io
 import pathlib
 import pickle
-from typing import Any, BinaryIO, Dict, Tuple, Union
+from typing import Any, BinaryIO, Dict, List, Tuple, Union
 
 MODEL_FILENAME = "model.pkl"
 
@@ -40,7 +40,34 @@ class PickledRecord:
         self.__dict__["state"] = dict(state) if isinstance(state, dict) else {"__state__": state}
 
     def __reduce_ex__(self, protocol: int):  # used by `dump_model`
-        return (_RecordFactory(self._global), (), self.state)
+        # the original class when its module is importable: then any pickler (`pickle.dump` included) writes the
+        # record under its original path, with the bytes `dump_model_dir` writes
+        cls = _original_class(*self._global)
+        return (cls if cls is not None else _RecordFactory(self._global), (), self.state)
+
+
+def _original_class(module: str, name: str):
+    """The class a record stands for, if its module can be imported (None otherwise)."""
+    import importlib
+    import sys
+
+    mod = sys.modules.get(module)
+    if mod is None:
+        try:
+            mod = importlib.import_module(module)
+        except Exception:
+            return None
+    cls = getattr(mod, name, None)
+    return cls if isinstance(cls, type) else None
+
+
+def new_record(module: str, name: str, state: Dict[str, Any]) -> PickledRecord:
+    """A record of the allow-listed class ``module.name`` holding `state`."""
+    if (module, name) not in _ALLOWED_GLOBALS:
+        raise ValueError(f"{module}.{name} is not a GECCO model class")
+    rec = _record_type(module, name)()
+    rec.state = dict(state)
+    return rec
 
 
 _record_types: Dict[Tuple[str, str], type] = {}
@@ -61,6 +88,37 @@ class _RecordFactory:
 
     def __call__(self):  # pragma: no cover - only meaningful inside the reference
         return _record_type(*self.glob)()
+
+    def __reduce__(self):
+        # only `_CompatPickler` may write a record whose class is not importable (it writes the original path); any
+        # other pickler would name this helper instead, and neither GECCO nor `load_model_dir` could load the file
+        module, name = self.glob
+        raise pickle.PicklingError(f"{module}.{name} is not importable here: write GECCO model records with "
+                                   "`dump_model_dir` (ClusterCRF.save)")
+
+
+def unresolved_globals(record: PickledRecord) -> List[str]:
+    """Original class paths of the records in `record`'s tree (itself included) whose module cannot be imported:
+    empty when any pickler writes the tree with the bytes `dump_model_dir` writes."""
+    missing: List[str] = []
+    seen = set()
+    stack: List[Any] = [record]
+    while stack:
+        obj = stack.pop()
+        if id(obj) in seen:
+            continue
+        seen.add(id(obj))
+        if isinstance(obj, PickledRecord):
+            if _original_class(*obj._global) is None:
+                path = ".".join(obj._global)
+                if path not in missing:
+                    missing.append(path)
+            stack.extend(reversed(list(obj.state.values())))
+        elif isinstance(obj, dict):
+            stack.extend(reversed(list(obj.values())))
+        elif isinstance(obj, (list, tuple, set, frozenset)):
+            stack.extend(obj)
+    return missing
 
 
 class RestrictedUnpickler(pickle.Unpickler):

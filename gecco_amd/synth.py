@@ -99,3 +99,16 @@ def workload(name: str, seed: int = SEED, law: str = "8d"):
         gptr = np.concatenate([[0]] + [gptr[1:].astype(np.int64) + r * nnz for r in range(reps)]).astype(np.int32)
         attr = np.tile(attr, reps)
     return dict(name=name, w=w, trans=trans, contig_ptr=cptr, gene_ptr=gptr, attr_id=attr, A=A)
+
+
+def synth_training_set(rng: np.random.Generator, lengths, A: int, stay: float = 0.97):
+    """Labelled training data (seq_ptr, item_ptr, attr_id, labels), int32: the batch of `synth_contigs`, labels from a
+    two-state Markov chain that keeps its label with probability `stay`, and the attributes of label-1 items moved to
+    the upper half of the id range so that the labels can be learned."""
+    seq_ptr, item_ptr, attr = synth_contigs(rng, lengths, A)
+    n = int(seq_ptr[-1])
+    flips = rng.random(n) >= stay
+    labels = (np.cumsum(flips) & 1).astype(np.int32)
+    owner = np.repeat(np.arange(n), np.diff(item_ptr))
+    attr = np.where(labels[owner] == 1, (attr + A // 2) % A, attr).astype(np.int32)
+    return seq_ptr, item_ptr, attr, labels

@@ -1,0 +1,332 @@
+"""Host side of CRF training (``ClusterCRF.fit``): the training set, CRFsuite's feature generation, and the L-BFGS /
+OWL-QN optimiser.  The objective and its gradient are evaluated on the device (``_native.Trainer``,
+``csrc/crf_train.hip``); everything here is cheap bookkeeping around that.
+
+What is reproduced ([EXT] CRFsuite 0.12 ``crf1d`` + ``train_lbfgs`` with libLBFGS, as sklearn-crfsuite drives it):
+
+* instances are the sliding windows of every sequence (``gecco/crf/__init__.py:364-367``); labels and attributes get ids
+  in order of first appearance over the instances, attribute names before the label of every item;
+* a state feature exists for every observed (attribute, label) pair and a transition feature for every observed label
+  bigram inside an instance; ``all_possible_states`` / ``all_possible_transitions`` add the unobserved ones and
+  ``min_freq`` drops features seen fewer times; feature ids follow (type, source, destination) order;
+* ``f(w) = sum of -log p(y | x) over the instances + c2 * |w|^2 + c1 * |w|_1``: OWL-QN when ``c1 > 0``;
+* libLBFGS's defaults as CRFsuite sets them: 6 memories, epsilon 1e-5 (stop when |g| < epsilon * max(1, |w|)), a
+  delta test over a period of 10 iterations (1e-5), no iteration limit, 20 line-search trials.  The line search is
+  backtracking: with the sufficient-decrease test on the orthant-projected step when ``c1 > 0`` (what CRFsuite uses
+  there), and with the Wolfe conditions when ``c1 = 0`` (CRFsuite's default there is More-Thuente; the optimum is
+  the same, the iterates are not).
+"""
+import math
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+__all__ = ["TRAINER_DEFAULTS", "trainer_params", "minimize", "OptimizeResult", "TrainingSet", "build_training_set",
+           "fit_training_set", "model_blob"]
+
+#: libLBFGS parameters as CRFsuite's ``train_lbfgs`` sets them (``max_iterations`` None = unbounded)
+TRAINER_DEFAULTS = {"num_memories": 6, "epsilon": 1e-5, "period": 10, "delta": 1e-5, "max_iterations": None}
+#: options of ``sklearn_crfsuite.CRF`` accepted without effect on the fit
+_SILENT_OPTIONS = ("verbose",)
+
+
+def trainer_params(options: Dict[str, object]) -> Dict[str, object]:
+    """Check ``sklearn_crfsuite.CRF``-style options (what ``ClusterCRF(**kwargs)`` stores) and return the complete set:
+    ``c1``, ``c2``, the feature-generation options and the five libLBFGS parameters, defaults filled in."""
+    out: Dict[str, object] = {"c1": 0.0, "c2": 1.0, "min_freq": 0.0, "all_possible_states": False,
+                              "all_possible_transitions": False, **TRAINER_DEFAULTS}
+    for key, value in options.items():
+        if key == "algorithm":
+            if value != "lbfgs":
+                raise ValueError(f"unsupported training algorithm {value!r} (only 'lbfgs' is implemented)")
+            continue
+        if value is None or key in _SILENT_OPTIONS:
+            continue
+        if key in ("c1", "c2", "epsilon", "delta", "min_freq"):
+            value = float(value)
+            if value < 0 or not math.isfinite(value):
+                raise ValueError(f"invalid value for {key}: {value}")
+        elif key in ("num_memories", "period", "max_iterations"):
+            value = int(value)
+            if value < (1 if key != "period" else 0):
+                raise ValueError(f"invalid value for {key}: {value}")
+        elif key in ("all_possible_states", "all_possible_transitions"):
+            value = bool(value)
+        else:
+            raise ValueError(f"unsupported trainer option {key!r}")
+        out[key] = value
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- optimiser
+class OptimizeResult:
+    def __init__(self, x: np.ndarray, f: float, n_iter: int, n_eval: int, status: str):
+        self.x, self.f, self.n_iter, self.n_eval, self.status = x, f, n_iter, n_eval, status
+
+    def __repr__(self) -> str:
+        return f"OptimizeResult(f={self.f!r}, n_iter={self.n_iter}, n_eval={self.n_eval}, status={self.status!r})"
+
+
+def _pseudo_gradient(x: np.ndarray, g: np.ndarray, c1: float) -> np.ndarray:
+    """OWL-QN's pseudo-gradient of f + c1 |x|_1: the one-sided derivative of steepest descent."""
+    pg = np.where(x < 0, g - c1, np.where(x > 0, g + c1, 0.0))
+    zero = x == 0
+    pg = np.where(zero & (g + c1 < 0), g + c1, pg)
+    pg = np.where(zero & (g - c1 > 0), g - c1, pg)
+    return pg
+
+
+def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarray, c1: float = 0.0,
+             num_memories: int = 6, epsilon: float = 1e-5, period: int = 10, delta: float = 1e-5,
+             max_iterations: Optional[int] = None, max_linesearch: int = 20,
+             callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> OptimizeResult:
+    """Minimise ``fg(x)[0] + c1 * |x|_1`` with L-BFGS (``c1 = 0``) or OWL-QN (``c1 > 0``), libLBFGS's algorithm.
+    ``fg`` returns the smooth part of the objective and its gradient.  Stops on the gradient test, the delta test, the
+    iteration limit, or a failed line search (status "line search failed": the point before that search is returned, as
+    libLBFGS does; near the optimum this is where the objective's rounding hides any further decrease)."""
+    ftol, wolfe, min_step, max_step = 1e-4, 0.9, 1e-20, 1e20
+    x = np.array(x0, dtype=np.float64)
+    n_eval = 0
+
+    def evaluate(xv):
+        nonlocal n_eval
+        n_eval += 1
+        f, g = fg(xv)
+        g = np.asarray(g, dtype=np.float64)
+        if c1 > 0:
+            f = f + c1 * float(np.abs(xv).sum())
+        return float(f), g
+
+    fx, g = evaluate(x)
+    pg = _pseudo_gradient(x, g, c1) if c1 > 0 else g
+    history = [fx] * max(period, 1)
+    d = -pg
+    xnorm, gnorm = max(float(np.linalg.norm(x)), 1.0), float(np.linalg.norm(pg))
+    if gnorm / xnorm <= epsilon:
+        return OptimizeResult(x, fx, 0, n_eval, "converged")
+    step = 1.0 / float(np.linalg.norm(d))
+    mem_s: List[np.ndarray] = []
+    mem_y: List[np.ndarray] = []
+    mem_ys: List[float] = []
+    k = 1
+    while True:
+        xp, gp, pgp, fp = x, g, pg, fx
+        # ---- line search
+        count = 0
+        ok = False
+        if c1 > 0:
+            orthant = np.where(xp == 0, -pgp, xp)
+            while True:
+                x = xp + step * d
+                x = np.where(x * orthant <= 0, 0.0, x)
+                fx, g = evaluate(x)
+                count += 1
+                if fx <= fp + ftol * float(np.dot(x - xp, pgp)):
+                    ok = True
+                    break
+                if step < min_step or step > max_step or count >= max_linesearch:
+                    break
+                step *= 0.5
+        else:
+            dginit = float(np.dot(gp, d))
+            if dginit > 0:
+                x, fx, g = xp, fp, gp
+                return OptimizeResult(x, fx, k - 1, n_eval, "search direction is not a descent direction")
+            while True:
+                x = xp + step * d
+                fx, g = evaluate(x)
+                count += 1
+                if fx > fp + step * ftol * dginit:
+                    width = 0.5
+                elif float(np.dot(g, d)) < wolfe * dginit:
+                    width = 2.1
+                else:
+                    ok = True
+                    break
+                if step < min_step or step > max_step or count >= max_linesearch:
+                    break
+                step *= width
+        if not ok:
+            # libLBFGS returns the point before the failed search
+            return OptimizeResult(xp, fp, k - 1, n_eval, "line search failed")
+        pg = _pseudo_gradient(x, g, c1) if c1 > 0 else g
+        if callback is not None:
+            callback(k, fx, x)
+        # ---- stopping tests
+        xnorm, gnorm = max(float(np.linalg.norm(x)), 1.0), float(np.linalg.norm(pg))
+        if gnorm / xnorm <= epsilon:
+            return OptimizeResult(x, fx, k, n_eval, "converged")
+        if period > 0:
+            if k >= period:
+                rate = (history[k % period] - fx) / fx if fx != 0 else 0.0
+                if rate < delta:
+                    return OptimizeResult(x, fx, k, n_eval, "delta test")
+            history[k % period] = fx
+        if max_iterations is not None and k >= max_iterations:
+            return OptimizeResult(x, fx, k, n_eval, "maximum number of iterations")
+        # ---- L-BFGS direction (two-loop recursion on the smooth gradient's differences)
+        s, y = x - xp, g - gp
+        ys, yy = float(np.dot(y, s)), float(np.dot(y, y))
+        mem_s.append(s)
+        mem_y.append(y)
+        mem_ys.append(ys)
+        if len(mem_s) > num_memories:
+            mem_s.pop(0)
+            mem_y.pop(0)
+            mem_ys.pop(0)
+        d = -pg
+        alphas = []
+        for si, yi, ysi in zip(reversed(mem_s), reversed(mem_y), reversed(mem_ys)):
+            a = float(np.dot(si, d)) / ysi
+            alphas.append(a)
+            d = d - a * yi
+        d = d * (ys / yy)
+        for si, yi, ysi, a in zip(mem_s, mem_y, mem_ys, reversed(alphas)):
+            b = float(np.dot(yi, d)) / ysi
+            d = d + (a - b) * si
+        if c1 > 0:
+            d = np.where(d * pg >= 0, 0.0, d)
+        step = 1.0
+        k += 1
+
+
+# ---------------------------------------------------------------------------------------------- training set
+class TrainingSet:
+    """Encoded training data and the generated features.
+
+    ``seq_ptr`` / ``item_ptr`` / ``attr_id`` / ``labels``: the sequences as CSR over items and attribute ids (ids in order
+    of first appearance over the instances); ``labels_`` / ``attrs_``: the id -> name tables; ``state_attr``,
+    ``state_label``, ``trans_src``, ``trans_dst``: the generated features (state features first, feature id = position);
+    ``state_fid`` [A, L] / ``trans_fid`` [L, L]: feature id of every pair, -1 where there is none."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def num_features(self) -> int:
+        return len(self.state_attr) + len(self.trans_src)
+
+
+def _coverage(n: int, window: int, step: int) -> np.ndarray:
+    """Number of windows (gecco/_meta.py:124-132 ``sliding_window``) covering every position of a sequence of n items."""
+    cov = np.zeros(n + 1, dtype=np.int64)
+    starts = np.arange(0, n + 1 - window, step)
+    np.add.at(cov, starts, 1)
+    np.add.at(cov, starts + window, -1)
+    return np.cumsum(cov)[:n]
+
+
+def _pair_coverage(n: int, window: int, step: int) -> np.ndarray:
+    """Number of windows holding both positions p - 1 and p, for p = 1 .. n - 1."""
+    if n < 2 or window < 2:
+        return np.zeros(max(n - 1, 0), dtype=np.int64)
+    nw = (n - window) // step + 1
+    p = np.arange(1, n)
+    lo = np.maximum(0, -((window - 1 - p) // step))  # ceil((p - W + 1) / step)
+    hi = np.minimum(nw - 1, (p - 1) // step)
+    return np.maximum(hi - lo + 1, 0)
+
+
+def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_labels: Sequence[Sequence[str]],
+                       window: int, step: int, min_freq: float = 0.0, all_possible_states: bool = False,
+                       all_possible_transitions: bool = False) -> TrainingSet:
+    """Encode sequences (per item the attribute names, per item a label) and generate CRFsuite's features over the
+    sliding-window instances.  Every sequence must hold at least `window` items.  Raises ``ValueError`` unless exactly
+    two labels occur."""
+    label_index: Dict[str, int] = {}
+    attr_index: Dict[str, int] = {}
+    covs = []
+    # ids in order of first appearance over the instances: an item no window covers is never seen by CRFsuite
+    for items, labs in zip(sequences, sequence_labels):
+        cov = _coverage(len(items), window, step)
+        covs.append(cov)
+        for names, lab, c in zip(items, labs, cov.tolist()):
+            if c == 0:
+                continue
+            for name in names:
+                if name not in attr_index:
+                    attr_index[name] = len(attr_index)
+            if lab not in label_index:
+                label_index[lab] = len(label_index)
+    if len(label_index) != 2:
+        raise ValueError(f"training needs exactly 2 labels, found {len(label_index)} ({sorted(label_index)}): "
+                         "GECCO's protein and domain modes are binary")
+    L, A = 2, len(attr_index)
+    seq_ptr = [0]
+    item_ptr = [0]
+    attr_id: List[int] = []
+    labels: List[int] = []
+    for items, labs in zip(sequences, sequence_labels):
+        for names, lab in zip(items, labs):
+            # (names outside the dictionary can only sit on items no window covers: they carry no weight)
+            attr_id.extend(attr_index[nm] for nm in names if nm in attr_index)
+            item_ptr.append(len(attr_id))
+            labels.append(label_index.get(lab, 0))
+        seq_ptr.append(len(labels))
+    seq_ptr_a = np.array(seq_ptr, dtype=np.int32)
+    item_ptr_a = np.array(item_ptr, dtype=np.int64)
+    attr_a = np.array(attr_id, dtype=np.int64)
+    lab_a = np.array(labels, dtype=np.int64)
+    cov_a = np.concatenate(covs) if covs else np.zeros(0, dtype=np.int64)
+
+    # observed frequencies: state (a, y) once per window holding the item, transitions once per window holding the pair
+    deg = np.diff(item_ptr_a)
+    occ_item = np.repeat(np.arange(len(lab_a)), deg)
+    state_freq = np.zeros(A * L, dtype=np.float64)
+    np.add.at(state_freq, attr_a * L + lab_a[occ_item], cov_a[occ_item].astype(np.float64))
+    state_seen = np.zeros(A * L, dtype=bool)
+    state_seen[(attr_a * L + lab_a[occ_item])[cov_a[occ_item] > 0]] = True
+    trans_freq = np.zeros(L * L, dtype=np.float64)
+    trans_seen = np.zeros(L * L, dtype=bool)
+    for s in range(len(seq_ptr) - 1):
+        b, e = seq_ptr[s], seq_ptr[s + 1]
+        pc = _pair_coverage(e - b, window, step)
+        pair = lab_a[b:e - 1] * L + lab_a[b + 1:e]
+        np.add.at(trans_freq, pair, pc.astype(np.float64))
+        trans_seen[pair[pc > 0]] = True
+    if all_possible_states:
+        state_seen[:] = True
+    if all_possible_transitions:
+        trans_seen[:] = True
+    state_keep = state_seen & (state_freq >= min_freq)
+    trans_keep = trans_seen & (trans_freq >= min_freq)
+    s_idx = np.flatnonzero(state_keep)  # (attribute, label) order
+    t_idx = np.flatnonzero(trans_keep)  # (source, destination) order
+    state_fid = np.full(A * L, -1, dtype=np.int32)
+    state_fid[s_idx] = np.arange(len(s_idx), dtype=np.int32)
+    trans_fid = np.full(L * L, -1, dtype=np.int32)
+    trans_fid[t_idx] = len(s_idx) + np.arange(len(t_idx), dtype=np.int32)
+    return TrainingSet(
+        seq_ptr=seq_ptr_a, item_ptr=item_ptr_a.astype(np.int32), attr_id=attr_a.astype(np.int32),
+        labels=lab_a.astype(np.int32), labels_=list(label_index), attrs_=list(attr_index),
+        state_attr=s_idx // L, state_label=s_idx % L, trans_src=t_idx // L, trans_dst=t_idx % L,
+        state_fid=state_fid.reshape(A, L), trans_fid=trans_fid.reshape(L, L), window=window, step=step,
+    )
+
+
+def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0,
+                     callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> OptimizeResult:
+    """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0."""
+    from . import _native
+
+    trainer = _native.Trainer(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.window, ts.step,
+                              ts.state_fid, ts.trans_fid, ts.num_features, device=device)
+    c2 = float(params["c2"])
+
+    def fg(w):
+        f, g = trainer.eval(w)
+        if c2 > 0:
+            f += c2 * float(np.dot(w, w))
+            g = g + (2.0 * c2) * w
+        return f, g
+
+    return minimize(fg, np.zeros(ts.num_features), c1=float(params["c1"]), num_memories=int(params["num_memories"]),
+                    epsilon=float(params["epsilon"]), period=int(params["period"]), delta=float(params["delta"]),
+                    max_iterations=params["max_iterations"], callback=callback)
+
+
+def model_blob(ts: TrainingSet, w: np.ndarray) -> bytes:
+    """The CRFsuite model file of trained weights (zero weights and unused attributes dropped, as CRFsuite saves)."""
+    from .crfsuite_model import model_bytes
+
+    return model_bytes(ts.labels_, ts.attrs_, ts.state_attr, ts.state_label, ts.trans_src, ts.trans_dst, w)

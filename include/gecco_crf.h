@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.2.1 = 221). */
+/* ABI version: major*100 + minor*10 + patch (2.3.0 = 230). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -414,6 +414,26 @@ int gecco_crf_packed_order_info(const gecco_crf_packed *p, const int64_t *gene_s
 int gecco_crf_tsv_format(int64_t n_rows, int32_t n_cols, const int32_t *kinds, const void *const *data,
                          const int64_t *const *offsets, const char *header, uint8_t **out, int64_t *out_len);
 void gecco_crf_buffer_free(uint8_t *p);
+
+/* ---- training (ABI 2.3.0): objective and gradient of a 2-label CRF on the device ------------------------------
+ * What `ClusterCRF.fit` (gecco/crf/__init__.py:275-378) hands to CRFsuite's L-BFGS trainer: the training instances are every
+ * sliding window of `window` items, `step` apart, of every sequence (no padding: a sequence shorter than the window is EINVAL).
+ * Sequences are CSR over items (seq_ptr[n_seqs+1], seq_ptr[0] = 0), items CSR over attributes (item_ptr[n_items+1],
+ * attr_id in [0, num_attrs)), labels[n_items] in {0, 1}.  The host generates the features: state_fid[a*L + y] is the id of
+ * the state feature (attribute a, label y) and trans_fid[i*L + j] that of the transition (i, j), -1 where there is none;
+ * ids are in [0, num_features).  The training set is copied to `device` once and stays there; every array may be freed
+ * after the call.  num_labels must be 2 and window at most 32 (GECCO_CRF_EUNSUPPORTED otherwise).
+ * eval: f = sum over windows of (log Z - score of the gold path), g[k] = expected - empirical count of feature k, under
+ * the weights w[num_features] (features absent from both tables weigh 0).  No regularisation terms.  Synchronous; every
+ * sum has a fixed order, so equal weights give equal bits.  One evaluation at a time per trainer. */
+typedef struct gecco_crf_trainer gecco_crf_trainer;
+int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr,
+                             const int32_t *attr_id, const int32_t *labels, int32_t num_attrs, int32_t num_labels,
+                             int32_t window, int32_t step, const int32_t *state_fid, const int32_t *trans_fid,
+                             int32_t num_features, gecco_crf_trainer **out);
+int gecco_crf_trainer_eval(gecco_crf_trainer *t, const double *w, double *f, double *g);
+int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t);
+void gecco_crf_trainer_free(gecco_crf_trainer *t);
 
 #ifdef __cplusplus
 }
