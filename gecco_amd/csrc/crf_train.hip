@@ -10,7 +10,10 @@
 // The training set is uploaded once.  One evaluation is six launches on the trainer's stream:
 //   1. item scores     one thread per item: s[i][y] = sum of the state weights of its attributes (CSR order)
 //   2. windows         one thread per window: scaled fp64 forward-backward; alpha and the normalisers live in LDS;
-//                      writes the window's node marginals [W][2] and one row (log Z - gold score, four pairwise sums)
+//                      writes the window's node marginals [W][2] and one row (log Z - gold score, four pairwise sums).
+//                      Transitions travel max-shifted (exp(t - t_max)).  The scaled form is used while its intermediates
+//                      stay normal fp64 numbers; a window where they do not is redone in log space by the same thread,
+//                      so the results are right for any finite weights (train_windows has the exact conditions)
 //   3. item marginals  one thread per item: the node marginals of the windows covering it, in window order
 //   4. attr counts     one workgroup per attribute: the item marginals over the attribute -> items transpose
 //   5/6. row sums      fixed-geometry two-stage tree over the window rows
@@ -19,6 +22,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cfloat>
 #include <cmath>
 #include <memory>
 #include <string>
@@ -41,7 +45,9 @@ constexpr int kTrainMaxW = 32;           // = kWinMaxW of the inference kernels
 
 struct TransArgs {
     double t00, t01, t10, t11;  // transition weights
-    double e00, e01, e10, e11;  // exp of the same
+    double e00, e01, e10, e11;  // exp(t - tmax)
+    double tmax;                // the largest of the four weights
+    int log_space;              // 1 when an exp(t - tmax) is not a normal number: every window goes to log space
 };
 
 __global__ void __launch_bounds__(kTrainThreads) train_item_scores(const int32_t *__restrict__ item_ptr,
@@ -59,15 +65,70 @@ __global__ void __launch_bounds__(kTrainThreads) train_item_scores(const int32_t
     score[i] = make_double2(s0, s1);
 }
 
+// Natural log of exp(a) + exp(b), fp64, for the log-space recomputation of a flagged window.
+__device__ __forceinline__ double lse2(double a, double b) {
+    const double hi = fmax(a, b), lo = fmin(a, b);
+    return hi + log1p(exp(lo - hi));
+}
+
+// The window at i0 once more in log space (fp64 log-sum-exp), for a window the scaled pass flagged: same outputs as
+// that pass (node marginals, log Z, the four pairwise sums), correct for any finite scores and transition weights.
+// log alpha lives in the LDS slots of alpha; log beta is carried backward in registers.
+__device__ __forceinline__ void train_window_logspace(const double2 *__restrict__ score, int64_t i0, int32_t W,
+                                                   const TransArgs &T, double2 *__restrict__ la_lds, int lane,
+                                                   double2 *__restrict__ mw, double *__restrict__ logz_out,
+                                                   double *__restrict__ x_out) {
+    double2 s = score[i0];
+    double l0 = s.x, l1 = s.y;
+    la_lds[lane] = make_double2(l0, l1);
+    for (int t = 1; t < W; ++t) {
+        s = score[i0 + t];
+        const double n0 = lse2(l0 + T.t00, l1 + T.t10) + s.x;
+        const double n1 = lse2(l0 + T.t01, l1 + T.t11) + s.y;
+        l0 = n0;
+        l1 = n1;
+        la_lds[t * kTrainWinThreads + lane] = make_double2(l0, l1);
+    }
+    const double logz = lse2(l0, l1);
+    mw[W - 1] = make_double2(exp(l0 - logz), exp(l1 - logz));
+    double b0 = 0.0, b1 = 0.0;  // log beta
+    double x00 = 0.0, x01 = 0.0, x10 = 0.0, x11 = 0.0;
+    for (int t = W - 1; t >= 1; --t) {
+        s = score[i0 + t];
+        const double q0 = s.x + b0, q1 = s.y + b1;  // log of exp(s_t) beta_t
+        const double2 ap = la_lds[(t - 1) * kTrainWinThreads + lane];
+        x00 += exp(ap.x + T.t00 + q0 - logz);
+        x01 += exp(ap.x + T.t01 + q1 - logz);
+        x10 += exp(ap.y + T.t10 + q0 - logz);
+        x11 += exp(ap.y + T.t11 + q1 - logz);
+        b0 = lse2(T.t00 + q0, T.t01 + q1);
+        b1 = lse2(T.t10 + q0, T.t11 + q1);
+        mw[t - 1] = make_double2(exp(ap.x + b0 - logz), exp(ap.y + b1 - logz));
+    }
+    *logz_out = logz;
+    x_out[0] = x00;
+    x_out[1] = x01;
+    x_out[2] = x10;
+    x_out[3] = x11;
+}
+
+
 // One window per thread.  Forward: alpha_t = normalised (alpha_{t-1} E) * exp(s_t - m_t), c_t its normaliser,
-// log Z = sum (log c_t + m_t).  Backward with the same normalisers: beta_{W-1} = 1,
+// E = exp(t - t_max), log Z = sum (log c_t + m_t) + (W - 1) t_max.  Backward with the same normalisers: beta_{W-1} = 1,
 // beta_{t-1}[i] = sum_j E[i][j] exp(s_t[j] - m_t) beta_t[j] / c_t; marginal_t = alpha_t * beta_t;
 // pairwise (t-1, t) = alpha_{t-1}[i] E[i][j] exp(s_t[j] - m_t) beta_t[j] / c_t.
-__global__ void __launch_bounds__(kTrainWinThreads) train_windows(const double2 *__restrict__ score,
-                                                                  const int32_t *__restrict__ label,
-                                                                  const int32_t *__restrict__ win_start, int64_t n_win,
-                                                                  int32_t W, const TransArgs T, double2 *__restrict__ marg,
-                                                                  double *__restrict__ rows) {
+// The scaled form is exact up to rounding while every exp(s - m), alpha (before and after normalising), u and beta stays
+// a normal fp64 number.  With E <= 1, exp(s - m) <= 1 and alpha_{t-1} summing to 1, n_j = (alpha E)_j exp(s_j - m) <= 1
+// and c <= 2, so one test per step covers the forward pass: min(n0, n1) >= 2 DBL_MIN implies exp(s - m), n and alpha
+// all normal.  It also bounds the backward pass from above: marginal <= 1 gives beta_j <= c / n_j and
+// u_j <= 1 / (alpha E)_j <= 1 / (2 DBL_MIN), so only underflow of u and beta is tested there.  A window that fails
+// (a state-score gap of some 708 nats or more, a label whose alpha underflows), or every window when a shifted
+// transition E is not normal (T.log_space), is recomputed in log space by the same thread (train_window_logspace);
+// nothing changes for the other windows.
+// (waves_per_eu(6): keeps the VGPR count, and so the occupancy, of the kernel without the log-space branch.)
+__global__ void __launch_bounds__(kTrainWinThreads) __attribute__((amdgpu_waves_per_eu(6)))
+train_windows(const double2 *__restrict__ score, const int32_t *__restrict__ label, const int32_t *__restrict__ win_start,
+              int64_t n_win, int32_t W, const TransArgs T, double2 *__restrict__ marg, double *__restrict__ rows) {
     extern __shared__ double lds[];
     double2 *alpha = reinterpret_cast<double2 *>(lds);                 // [W][kTrainWinThreads]
     double *cnorm = lds + 2 * static_cast<size_t>(W) * kTrainWinThreads;  // [W][kTrainWinThreads]
@@ -82,6 +143,8 @@ __global__ void __launch_bounds__(kTrainWinThreads) train_windows(const double2 
     double c = e0 + e1;
     double a0 = e0 / c, a1 = e1 / c;
     double logz = m + log(c);
+    constexpr double kMinN = 2 * DBL_MIN;
+    bool ok = !T.log_space & (fmin(e0, e1) >= kMinN);  // (c = e0 + e1 >= 1 here)
     int y = label[i0];
     double gold = y ? s.y : s.x;
     alpha[lane] = make_double2(a0, a1);
@@ -96,7 +159,8 @@ __global__ void __launch_bounds__(kTrainWinThreads) train_windows(const double2 
         c = n0 + n1;
         a0 = n0 / c;
         a1 = n1 / c;
-        logz += m + log(c);
+        logz += m + log(c) + T.tmax;
+        ok &= fmin(n0, n1) >= kMinN;
         const int yn = label[i0 + t];
         gold += (yn ? s.y : s.x) + (y ? (yn ? T.t11 : T.t10) : (yn ? T.t01 : T.t00));
         y = yn;
@@ -104,29 +168,36 @@ __global__ void __launch_bounds__(kTrainWinThreads) train_windows(const double2 
         cnorm[t * kTrainWinThreads + lane] = c;
     }
     double2 *mw = marg + w * W;
-    mw[W - 1] = make_double2(a0, a1);
-    double b0 = 1.0, b1 = 1.0;
-    double x00 = 0.0, x01 = 0.0, x10 = 0.0, x11 = 0.0;
-    for (int t = W - 1; t >= 1; --t) {
-        s = score[i0 + t];
-        m = fmax(s.x, s.y);
-        const double ct = cnorm[t * kTrainWinThreads + lane];
-        const double u0 = exp(s.x - m) * b0 / ct, u1 = exp(s.y - m) * b1 / ct;
-        const double2 ap = alpha[(t - 1) * kTrainWinThreads + lane];
-        x00 += ap.x * T.e00 * u0;
-        x01 += ap.x * T.e01 * u1;
-        x10 += ap.y * T.e10 * u0;
-        x11 += ap.y * T.e11 * u1;
-        b0 = T.e00 * u0 + T.e01 * u1;
-        b1 = T.e10 * u0 + T.e11 * u1;
-        mw[t - 1] = make_double2(ap.x * b0, ap.y * b1);
-    }
     double *r = rows + w * kTrainRowCols;
+    if (ok) {
+        mw[W - 1] = make_double2(a0, a1);
+        double b0 = 1.0, b1 = 1.0;
+        double x00 = 0.0, x01 = 0.0, x10 = 0.0, x11 = 0.0;
+        for (int t = W - 1; t >= 1; --t) {
+            s = score[i0 + t];
+            m = fmax(s.x, s.y);
+            const double ct = cnorm[t * kTrainWinThreads + lane];
+            const double u0 = exp(s.x - m) * b0 / ct, u1 = exp(s.y - m) * b1 / ct;
+            const double2 ap = alpha[(t - 1) * kTrainWinThreads + lane];
+            x00 += ap.x * T.e00 * u0;
+            x01 += ap.x * T.e01 * u1;
+            x10 += ap.y * T.e10 * u0;
+            x11 += ap.y * T.e11 * u1;
+            b0 = T.e00 * u0 + T.e01 * u1;
+            b1 = T.e10 * u0 + T.e11 * u1;
+            ok &= fmin(fmin(u0, u1), fmin(b0, b1)) >= DBL_MIN;
+            mw[t - 1] = make_double2(ap.x * b0, ap.y * b1);
+        }
+        r[1] = x00;
+        r[2] = x01;
+        r[3] = x10;
+        r[4] = x11;
+    }
+    if (!ok) {
+        // (overwrites whatever the scaled pass stored for this window: marginals, log Z, pairwise sums)
+        train_window_logspace(score, i0, W, T, alpha, lane, mw, &logz, r + 1);
+    }
     r[0] = logz - gold;
-    r[1] = x00;
-    r[2] = x01;
-    r[3] = x10;
-    r[4] = x11;
 }
 
 // Item i is covered by the windows first .. first + cnt - 1, at position off, off - step, ... in them.
@@ -403,7 +474,12 @@ int trainer_eval(Trainer *t, const double *w, double *f, double *g) {
     double tw[4];
     for (int k = 0; k < 4; ++k) tw[k] = t->trans_fid[k] >= 0 ? w[t->trans_fid[k]] : 0.0;
     T.t00 = tw[0], T.t01 = tw[1], T.t10 = tw[2], T.t11 = tw[3];
-    T.e00 = std::exp(tw[0]), T.e01 = std::exp(tw[1]), T.e10 = std::exp(tw[2]), T.e11 = std::exp(tw[3]);
+    T.tmax = std::max(std::max(tw[0], tw[1]), std::max(tw[2], tw[3]));
+    T.e00 = std::exp(tw[0] - T.tmax), T.e01 = std::exp(tw[1] - T.tmax);
+    T.e10 = std::exp(tw[2] - T.tmax), T.e11 = std::exp(tw[3] - T.tmax);
+    T.log_space = 0;
+    for (double e : {T.e00, T.e01, T.e10, T.e11})
+        if (!(e >= DBL_MIN && e <= DBL_MAX)) T.log_space = 1;
 
     int rc = check_hip(hipSetDevice(t->device), "hipSetDevice");
     if (rc) return rc;

@@ -83,7 +83,9 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
     """Minimise ``fg(x)[0] + c1 * |x|_1`` with L-BFGS (``c1 = 0``) or OWL-QN (``c1 > 0``), libLBFGS's algorithm.
     ``fg`` returns the smooth part of the objective and its gradient.  Stops on the gradient test, the delta test, the
     iteration limit, or a failed line search (status "line search failed": the point before that search is returned, as
-    libLBFGS does; near the optimum this is where the objective's rounding hides any further decrease)."""
+    libLBFGS does; near the optimum this is where the objective's rounding hides any further decrease).  A trial point
+    whose f or g is not finite fails the sufficient-decrease test, so the step is halved: it is never accepted.  A start
+    ``x0`` whose f or g is not finite raises ``ValueError``."""
     ftol, wolfe, min_step, max_step = 1e-4, 0.9, 1e-20, 1e20
     x = np.array(x0, dtype=np.float64)
     n_eval = 0
@@ -97,7 +99,13 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
             f = f + c1 * float(np.abs(xv).sum())
         return float(f), g
 
+    def finite(fv, gv):
+        return math.isfinite(fv) and bool(np.all(np.isfinite(gv)))
+
     fx, g = evaluate(x)
+    if not finite(fx, g):
+        raise ValueError(f"minimize: the objective is not finite at the start point (f = {fx}, "
+                         f"{int(np.count_nonzero(~np.isfinite(g)))} non-finite gradient entries)")
     pg = _pseudo_gradient(x, g, c1) if c1 > 0 else g
     history = [fx] * max(period, 1)
     d = -pg
@@ -121,7 +129,7 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
                 x = np.where(x * orthant <= 0, 0.0, x)
                 fx, g = evaluate(x)
                 count += 1
-                if fx <= fp + ftol * float(np.dot(x - xp, pgp)):
+                if finite(fx, g) and fx <= fp + ftol * float(np.dot(x - xp, pgp)):
                     ok = True
                     break
                 if step < min_step or step > max_step or count >= max_linesearch:
@@ -136,7 +144,7 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
                 x = xp + step * d
                 fx, g = evaluate(x)
                 count += 1
-                if fx > fp + step * ftol * dginit:
+                if not finite(fx, g) or fx > fp + step * ftol * dginit:
                     width = 0.5
                 elif float(np.dot(g, d)) < wolfe * dginit:
                     width = 2.1

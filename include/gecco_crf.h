@@ -425,7 +425,10 @@ void gecco_crf_buffer_free(uint8_t *p);
  * after the call.  num_labels must be 2 and window at most 32 (GECCO_CRF_EUNSUPPORTED otherwise).
  * eval: f = sum over windows of (log Z - score of the gold path), g[k] = expected - empirical count of feature k, under
  * the weights w[num_features] (features absent from both tables weigh 0).  No regularisation terms.  Synchronous; every
- * sum has a fixed order, so equal weights give equal bits.  One evaluation at a time per trainer. */
+ * sum has a fixed order, so equal weights give equal bits.  One evaluation at a time per trainer.
+ * Range: correct for any finite weights.  Each window runs a scaled forward-backward (transitions max-shifted); a window
+ * whose scaled intermediates leave the normal fp64 range (state-score gaps beyond ~708 nats, transition weights more
+ * than ~708 apart) is recomputed in log space.  Non-finite weights give a non-finite f. */
 typedef struct gecco_crf_trainer gecco_crf_trainer;
 int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr,
                              const int32_t *attr_id, const int32_t *labels, int32_t num_attrs, int32_t num_labels,

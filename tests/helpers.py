@@ -143,3 +143,44 @@ def pack_refiner_case(case, markers=None):
         cptr.append(len(ids))
     return (ids, cids, np.array(p, dtype=np.float64), np.array(ann, dtype=np.uint8), np.array(cptr, dtype=np.int32),
             np.array(mptr, dtype=np.int32), np.array(mid, dtype=np.int32))
+
+
+# ---------------------------------------------------------------- training objective: error bounds
+EPS = float(np.finfo(np.float64).eps)
+
+
+def objective_tolerances(seq_ptr, item_ptr, attr_id, W, step, state_fid, trans_fid, w, details):
+    """Bounds (tol_f, tol_g [K]) on |f - f_ref| and |g - g_ref| between two fp64 evaluations of the training objective,
+    derived from the magnitudes of the terms (``details`` = benchkit.train_objective's breakdown).
+
+    Every log-space quantity of a window -- log alpha, log beta, log Z, the gold score, the scaled form's sum of
+    m_t + log c_t + t_max -- is bounded by M_w = sum_t max_y |s_t[y]| + (W - 1) max |t| + W ln 2.  A window's row
+    (log Z - gold) is a sum of at most 2W + 2 such terms, so each side rounds it by at most (2W + 2) eps M_w; the rows
+    are then summed in a tree (device) or pairwise (numpy) of depth log2(n_windows) over |row| <= 2 M_w.  Hence
+        tol_f = 2 eps sum_w (2W + 2 + 2 log2(n_windows + 1)) M_w.
+    A node or pairwise marginal is exp of a sum of about four terms bounded by M = max_w M_w (log space), or a
+    product/quotient chain of at most 4W normalised factors (scaled form): relative error <= eps (4W + 4 M).  An
+    expected count sums at most W window marginals per item and then items in a tree of depth log2(n_items); the
+    empirical count is an exact integer and g = expected - empirical rounds once more by eps (expected + empirical); a
+    marginal below DBL_MIN may be flushed to 0 by either side, DBL_MIN per summand:
+        tol_g = 2 eps ((5W + 4 M + log2(n_items + 1)) expected + empirical) + (n_items + W n_windows) DBL_MIN.
+    Both are the sum of the two sides' worst cases; the measured differences are typically far below them."""
+    seq_ptr, item_ptr = np.asarray(seq_ptr), np.asarray(item_ptr)
+    w = np.asarray(w, dtype=np.float64)
+    sfid, tfid = np.asarray(state_fid).reshape(-1, 2), np.asarray(trans_fid).ravel()
+    S = np.where(sfid >= 0, w[np.maximum(sfid, 0)] if len(w) else 0.0, 0.0)
+    T = np.where(tfid >= 0, w[np.maximum(tfid, 0)] if len(w) else 0.0, 0.0)
+    n = int(seq_ptr[-1])
+    score = np.zeros((n, 2))
+    np.add.at(score, np.repeat(np.arange(n), np.diff(item_ptr)), S[np.asarray(attr_id)])
+    smag = np.abs(score).max(axis=1) if n else np.zeros(0)
+    starts = [np.arange(seq_ptr[s], seq_ptr[s + 1] - W + 1, step) for s in range(len(seq_ptr) - 1)]
+    starts = np.concatenate(starts + [np.zeros(0, dtype=np.int64)]).astype(np.int64)
+    csum = np.concatenate([[0.0], np.cumsum(smag)])
+    Mw = csum[starts + W] - csum[starts] + (W - 1) * float(np.abs(T).max()) + W * np.log(2.0)
+    nw = len(starts)
+    tol_f = 2 * EPS * (2 * W + 2 + 2 * np.log2(nw + 1)) * float(Mw.sum())
+    M = float(Mw.max()) if nw else 0.0
+    tol_g = (2 * EPS * ((5 * W + 4 * M + np.log2(n + 1)) * details["expected"] + details["empirical"])
+             + (n + W * nw) * float(np.finfo(np.float64).tiny))
+    return tol_f, tol_g

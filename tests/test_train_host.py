@@ -310,3 +310,134 @@ def test_pickling_without_the_reference_classes_is_refused_clearly():
     crf._adopt_model_blob(pickle_model.crfsuite_blob(pickle_model.load_model_dir(GOLDEN)))
     with pytest.raises(pickle.PicklingError, match="save"):
         pickle.dumps(crf, protocol=4)
+
+
+# ---------------------------------------------------------------- the yardstick of the device objective
+def _mp_objective(seq_ptr, item_ptr, attr_id, labels, W, step, sfid, tfid, w):
+    """f, g [K], per-window log Z of the training objective by enumerating all 2^W label paths of every window in
+    50-digit arithmetic: no recursion, no scaling, no log-sum-exp."""
+    import itertools
+
+    import mpmath
+
+    with mpmath.workdps(50):
+        return _mp_objective_at_precision(mpmath, seq_ptr, item_ptr, attr_id, labels, W, step, sfid, tfid, w)
+
+
+def _mp_objective_at_precision(mpmath, seq_ptr, item_ptr, attr_id, labels, W, step, sfid, tfid, w):
+    import itertools
+
+    K = len(w)
+    wm = [mpmath.mpf(float(x)) for x in w]
+    sfid, tfid = np.asarray(sfid).reshape(-1, 2), np.asarray(tfid).reshape(2, 2)
+    n = int(seq_ptr[-1])
+    item_feats = [[[int(sfid[a, y]) for a in attr_id[item_ptr[i]:item_ptr[i + 1]] if sfid[a, y] >= 0] for y in (0, 1)]
+                  for i in range(n)]
+    score = [[mpmath.fsum(wm[k] for k in item_feats[i][y]) for y in (0, 1)] for i in range(n)]
+    tw = [[wm[tfid[i, j]] if tfid[i, j] >= 0 else mpmath.mpf(0) for j in (0, 1)] for i in (0, 1)]
+    f = mpmath.mpf(0)
+    g = [mpmath.mpf(0)] * K
+    logzs = []
+    paths = list(itertools.product((0, 1), repeat=W))
+    for s in range(len(seq_ptr) - 1):
+        for i0 in range(int(seq_ptr[s]), int(seq_ptr[s + 1]) - W + 1, step):
+            sc = [mpmath.fsum([score[i0 + t][y[t]] for t in range(W)] + [tw[y[t - 1]][y[t]] for t in range(1, W)])
+                  for y in paths]
+            top = max(sc)
+            ex = [mpmath.exp(v - top) for v in sc]
+            z = mpmath.fsum(ex)
+            logz = top + mpmath.log(z)
+            logzs.append(logz)
+            gold = [int(v) for v in labels[i0:i0 + W]]
+            f += logz - sc[paths.index(tuple(gold))]
+            for y, e in zip(paths, ex):  # expected - empirical counts, feature by feature
+                p = e / z - (1 if list(y) == gold else 0)
+                for t in range(W):
+                    for k in item_feats[i0 + t][y[t]]:
+                        g[k] += p
+                    if t > 0 and tfid[y[t - 1], y[t]] >= 0:
+                        g[tfid[y[t - 1], y[t]]] += p
+    return f, g, logzs
+
+
+@pytest.mark.parametrize("W,step", [(1, 1), (3, 2), (6, 1), (10, 3)])
+@pytest.mark.parametrize("scale", [1.0, 100.0, 1000.0])
+def test_numpy_objective_matches_path_enumeration(W, step, scale):
+    """benchkit.train_objective (log space, vectorised recursions) against the definition of the objective summed over
+    every label path, in 50-digit arithmetic, up to weights far beyond where any fp64 exp would overflow."""
+    from benchkit.train_objective import objective
+    from gecco_amd import synth
+    from tests.helpers import objective_tolerances
+
+    rng = np.random.default_rng(W * 100 + step)
+    A = 6
+    lengths = [W, W + 2 * step] if W >= 6 else [W, W + 1, W + 4]
+    seq_ptr, item_ptr, attr_id, labels = synth.synth_training_set(rng, lengths, A, stay=0.7)
+    fid = np.arange(2 * A + 4, dtype=np.int32)
+    fid[[3, 2 * A + 1]] = -1  # a state and a transition pair without a feature
+    keep = fid >= 0
+    fid[keep] = np.arange(int(keep.sum()))
+    sfid, tfid = fid[:2 * A], fid[2 * A:]
+    w = scale * rng.normal(0, 1.5, size=int(keep.sum()))
+    f, g, nw, d = objective(seq_ptr, item_ptr, attr_id, labels, A, W, step, sfid, tfid, w, details=True)
+    mf, mg, mlogz = _mp_objective(seq_ptr, item_ptr, attr_id, labels, W, step, sfid, tfid, w)
+    assert nw == len(mlogz) > 0
+    tol_f, tol_g = objective_tolerances(seq_ptr, item_ptr, attr_id, W, step, sfid, tfid, w, d)
+    assert np.all(np.abs(d["logz"] - np.array([float(v) for v in mlogz])) <= tol_f)
+    assert abs(f - float(mf)) <= tol_f / 2, (f, float(mf), tol_f)
+    err = np.abs(g - np.array([float(v) for v in mg]))
+    assert np.all(err <= tol_g / 2), (err / np.maximum(tol_g, 1e-300)).max()
+    if scale <= 1:
+        assert abs(f - float(mf)) <= 1e-12 * abs(float(mf)) and np.all(err <= 1e-9 * (1 + np.abs(g)))
+
+
+# ---------------------------------------------------------------- the optimiser at non-finite points
+class _OutOfBudget(Exception):
+    pass
+
+
+def _nan_beyond(limit=3.0, target=10.0, budget=500):
+    """f = |x - target|^2 where every |x_i| <= limit, NaN (f and g) elsewhere; raises after `budget` calls."""
+    calls = [0]
+
+    def fg(x):
+        calls[0] += 1
+        if calls[0] > budget:
+            raise _OutOfBudget(calls[0])
+        if np.any(np.abs(x) > limit):
+            return float("nan"), np.full_like(x, np.nan)
+        return float(np.sum((x - target) ** 2)), 2 * (x - target)
+
+    return fg, calls
+
+
+@pytest.mark.parametrize("c1", [0.0, 0.5])
+def test_minimize_never_accepts_a_non_finite_point(c1):
+    from gecco_amd.train import minimize
+
+    fg, calls = _nan_beyond()
+    seen = []
+    res = minimize(fg, np.zeros(3), c1=c1, max_iterations=None, callback=lambda k, f, x: seen.append((f, x.copy())))
+    assert calls[0] <= 500
+    assert np.all(np.isfinite(res.x)) and np.isfinite(res.f), res
+    assert np.all(np.abs(res.x) <= 3.0)
+    assert res.status in ("line search failed", "converged", "delta test"), res
+    # every accepted iterate is finite, inside the finite region, and f decreases along them
+    fs = [f for f, _ in seen]
+    assert all(np.isfinite(f) for f in fs) and all(np.all(np.abs(x) <= 3.0) for _, x in seen)
+    assert all(b <= a for a, b in zip(fs, fs[1:]))
+    assert res.f < 300.0  # better than f(0)
+
+
+@pytest.mark.parametrize("c1", [0.0, 0.5])
+@pytest.mark.parametrize("bad", ["nan", "inf", "grad"])
+def test_minimize_refuses_a_non_finite_start(c1, bad):
+    from gecco_amd.train import minimize
+
+    def fg(x):
+        if bad == "grad":
+            return 1.0, np.array([0.0, np.nan])
+        return float(bad), np.zeros_like(x)
+
+    with pytest.raises(ValueError, match="not finite at the start point"):
+        minimize(fg, np.zeros(2), c1=c1)
