@@ -32,8 +32,8 @@ struct WinArgs {
     //   mu01 = m01*m10/m00^2, mu11 = m11/m00, kappa = m10/m00, rho = mu11/mu01  with m = exp(trans)
     double mu01, rho, kappa_over_mu01, inv_kappa;
     double expc[12];            // 1/13!, 1/12!, ..., 1/2!: Taylor coefficients of exp (SGPR-resident)
-    double ratio_zmax;          // a window whose forward pass ends on Z >= this (1e250) is repeated in the max-normalised form; -1: every
-                                // window is (GECCO_CRF_RATIO=0: A/B runs, tests)
+    double ratio_zmax;          // a window whose forward pass ends on Z >= this (1e250) is repeated in the max-normalised form (the host
+                                // always sets 1e250; -1 would repeat every window)
     double g00, g01, g10, g11;  // exp(trans - max), (other, label) order: generic kernel
     int32_t generic;            // 1: dispatch to the generic window kernel
     const double *exp_trans;   // [L*L] exp(trans) for the generic kernel
@@ -50,7 +50,7 @@ struct WinArgs {
 constexpr int kWinThreads = 256;  // lanes (= window starts) per workgroup: 4 waves, 8 workgroups per CU at <= 64 VGPRs
 constexpr int kWinMaxW = 32;      // largest window the register-resident kernel handles
 constexpr int kWinTilesPerWg = 2; // default DP phases per workgroup (GECCO_CRF_TILES_PER_WG=1..3 overrides; A/B runs)
-constexpr int kWinTiles1MaxSlots = 350000;  // batches of up to this many slots: one tile per workgroup (tools/tiles_sweep.py: the window kernel wins up to 0.4 M genes, the pipelined launch -- seven workgroups per CU -- up to 0.3 M)
+constexpr int kWinTiles1MaxSlots = 350000;  // batches of up to this many slots: one tile per workgroup (profiles/r05_tiles_sweep.txt: the window kernel wins up to 0.4 M genes, the pipelined launch -- seven workgroups per CU -- up to 0.3 M)
 
 // ---- shared device helpers ----------------------------------------------------------------------
 // exp(-t) for t >= 0: n = rint(t log2 e), r = n ln2 - t in two pieces (|r| <= ln2/2), degree-13
@@ -144,7 +144,7 @@ struct SeqArgs {
     double t00, t01, t10, t11;  // raw transition weights (Viterbi)
     double mx;                  // max(trans)
     double v_lo, v_hi, v_k;     // difference-form Viterbi: t01-t11, t00-t10, t11-t00
-    int32_t v_exact;            // 1: decisions within rounding noise of a threshold are re-derived sequentially (GECCO_CRF_VD_EXACT=0: A/B runs)
+    int32_t v_exact;            // 1: decisions within rounding noise of a threshold are re-derived sequentially (the host always sets 1)
     // What bounds CRFsuite's accumulated scores, for the margin inside which a decision of the difference form is not
     // PROVABLY crf1dc_viterbi's (crf_vd_short.hpp): |delta_t| <= nnz * max|w| + n * max|trans| over a contig of n genes and
     // nnz attribute entries.  v_wmax2 = 2 max_a max_y |w[a][y]| (the factor 2 also covers |s[1] - s[0]|), v_tmax = max |trans|.
@@ -172,7 +172,7 @@ struct SeqArgs {
     VE *vLane, *vBlock;
     uint32_t *vMaps, *vLaneMap, *vBlockMap;
     FE *fLane, *fBlock, *fLaneSuf, *fBlockSuf;
-    double2 *alpha;      // [n_genes] F: alpha_t
+    double2 *alpha;      // [n_genes] workspace: emission maxima of the short marginals path (smax), the exact decoder's backpointers
     double2 *contigTmp;  // [n_genes] sparse: values parked at contig ends
     // outputs
     double *marg;     // [n_genes*2]
@@ -183,7 +183,6 @@ struct SeqArgs {
 
 hipError_t launch_seq_state(const int32_t *gene_ptr, const int32_t *attr_id, const double2 *wtab01, int n_attrs, int n_genes,
                             double2 *state, hipStream_t stream);
-hipError_t launch_seq_marginals(const SeqArgs &a, const int32_t *d_contig_ptr, hipStream_t stream);
 hipError_t launch_seq_marginals_short(const SeqArgs &a, const int32_t *gene_ptr, const int32_t *attr_id, const double2 *wtab01,
                                       int n_attrs, const int32_t *d_contig_ptr, hipStream_t stream);
 hipError_t launch_seq_viterbi(const SeqArgs &a, const int32_t *d_contig_ptr, hipStream_t stream);

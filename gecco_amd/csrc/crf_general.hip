@@ -1489,17 +1489,12 @@ __global__ void __launch_bounds__(kGT) gl_chunk_backtrack(GenArgs a) {
 template <int LP>
 hipError_t launch_chunked(int what, const GenArgs &a, hipStream_t stream) {
     constexpr int G = kGT / LP;
-    // GECCO_CRF_GENERAL_ROWS=groups: the lane-group kernel for every label count (A/B runs, tests)
-    static const bool rows_groups = [] {
-        const char *env = std::getenv("GECCO_CRF_GENERAL_ROWS");
-        return env && env[0] == 'g';
-    }();
     const int rows_period = a.rows_rescale_period;
     auto blocks = [](long long items, int per) { return dim3(unsigned((items + per - 1) / per)); };
     const long long rows = static_cast<long long>(a.n_chunks) * a.L;
     if (a.n_chunks <= 0) return hipSuccess;
     if (what == 2) {
-        if (LP >= 16 && a.L > 8 && !rows_groups) {  // 9 to 32 labels: sixteen rows of a chunk's transfer matrix per wave on the matrix cores
+        if (LP >= 16 && a.L > 8) {  // 9 to 32 labels: sixteen rows of a chunk's transfer matrix per wave on the matrix cores
             const int groups = (a.L + 15) / 16, ns = (a.L + 3) / 4;
             const dim3 grid = blocks(static_cast<long long>(a.n_chunks) * groups, kGT / 64);
             switch (ns) {

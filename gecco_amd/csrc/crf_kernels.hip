@@ -485,7 +485,7 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
             }
             asm volatile("" ::: "memory");
             double z = fma(a1, P.inv_kappa, a0);
-            // (ratio_zmax = 1e250; GECCO_CRF_RATIO=0 sets it to -1: every window takes the max-normalised form -- A/B runs, tests)
+            // (ratio_zmax = 1e250, set by the host; -1 would send every window to the max-normalised form)
             const bool renorm = __builtin_amdgcn_ballot_w64(!(z < P.ratio_zmax)) != 0;
             // max-normalised pair of a slot from its ratio constant: r > mu01 <=> d > 0, where (e0, f) = (exp(-d), mu01)
             // = (mu01 / r, mu01); else (1, mu01 exp(d)) = (1, r).

@@ -120,8 +120,7 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
             c.g10 = G(label, o);
             c.g11 = G(label, label);
             fill_exp_coefficients(c.expc);
-            const char *env = std::getenv("GECCO_CRF_RATIO");
-            c.ratio_zmax = (env && env[0] == '0') ? -1.0 : 1.0e250;
+            c.ratio_zmax = 1.0e250;
         }
         DeviceTables::SeqConsts &q = t->seq;
         q.mx = *std::max_element(m.trans.begin(), m.trans.end());
@@ -134,8 +133,7 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
         q.v_lo = m.trans[1] - m.trans[3];
         q.v_hi = m.trans[0] - m.trans[2];
         q.v_k = m.trans[3] - m.trans[0];
-        const char *env = std::getenv("GECCO_CRF_VD_EXACT");
-        q.v_exact = (env && env[0] == '0') ? 0 : 1;
+        q.v_exact = 1;
         fill_exp_coefficients(q.expc);
         t->consts_ok = true;
     }
@@ -379,12 +377,8 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
         p.tiles_per_wg = (env && env[0] >= '1' && env[0] <= '3' && !env[1]) ? env[0] - '0' : kWinTilesPerWg;
         // A batch that leaves most wave slots of the chip empty runs ONE tile per workgroup: the two tiles of a workgroup are a
         // chain, and with a wave or two per SIMD nothing else hides a tile's latency (C2, 0.2 M genes: window kernel 10.0 -> 7.9 us).
-        // A batch of one workgroup keeps two (crf_windowed_small_l2).  GECCO_CRF_TILES1_MAX_SLOTS moves the limit (tests / A/B).
-        static const int64_t tiles1_max = [] {
-            const char *e = std::getenv("GECCO_CRF_TILES1_MAX_SLOTS");
-            return e ? std::atoll(e) : int64_t(kWinTiles1MaxSlots);
-        }();
-        if (!env && !p.general && W == 20 && p.S > 2 * (kWinThreads - (W - 1)) && p.S <= tiles1_max) p.tiles_per_wg = 1;
+        // A batch of one workgroup keeps two (crf_windowed_small_l2).
+        if (!env && !p.general && W == 20 && p.S > 2 * (kWinThreads - (W - 1)) && p.S <= kWinTiles1MaxSlots) p.tiles_per_wg = 1;
         // windows other than GECCO's 20 take the dynamic-W instantiation, whose two-tile form spills scalar registers: one tile
         // (tools/window_size_sweep.py, 1 M genes, two / one tile: W = 5 19.9 / 17.1 us, W = 10 22.9 / 19.2, W = 32 76 / 69)
         if (!env && !p.general && W != 20) p.tiles_per_wg = 1;
@@ -1120,26 +1114,15 @@ int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d
     }
     a.marg = d_marg;
     a.lognorm = d_lognorm;
-    static const bool general_path = [] {  // GECCO_CRF_MARGINALS=general: the three-pass path on 16-byte states (A/B runs, tests)
-        const char *env = std::getenv("GECCO_CRF_MARGINALS");
-        return env && env[0] == 'g';
-    }();
-    if (p.seq_short || !general_path) {
-        // 8-byte inputs, alpha in registers: one fused kernel when workgroups own whole contigs, the workgroups' products
-        // + the fused kernel (look-back / look-ahead over them) for contigs of any length
-        a.smax = reinterpret_cast<const double *>(a.alpha);
-        // short contigs: log Z is written by the kernel at every contig's last gene; contigs without genes get their 0 here
-        if (p.seq_short && d_lognorm && p.n_empty_contigs &&
-            (rc = check_hip(hipMemsetAsync(d_lognorm, 0, size_t(p.n_contigs) * 8, stream), "memset lognorm")))
-            return rc;
-        return check_hip(launch_seq_marginals_short(a, d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.d_contig_ptr,
-                                                    stream), "marginals launch");
-    }
-    // wtab2[1] holds (w[a][0], w[a][1]) = (other, label) pairs for label 1
-    if ((rc = check_hip(launch_seq_state(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
-                                         const_cast<double2 *>(a.state), stream), "state score launch")))
+    // 8-byte inputs, alpha in registers: one fused kernel when workgroups own whole contigs, the workgroups' products
+    // + the fused kernel (look-back / look-ahead over them) for contigs of any length
+    a.smax = reinterpret_cast<const double *>(a.alpha);
+    // short contigs: log Z is written by the kernel at every contig's last gene; contigs without genes get their 0 here
+    if (p.seq_short && d_lognorm && p.n_empty_contigs &&
+        (rc = check_hip(hipMemsetAsync(d_lognorm, 0, size_t(p.n_contigs) * 8, stream), "memset lognorm")))
         return rc;
-    return check_hip(launch_seq_marginals(a, p.d_contig_ptr, stream), "marginals launch");
+    return check_hip(launch_seq_marginals_short(a, d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.d_contig_ptr,
+                                                stream), "marginals launch");
 }
 
 int plan_run_viterbi(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int8_t *d_y, double *d_score,
@@ -1304,13 +1287,7 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
         PipelinedLaunch fl{};
         fl.seq = &pa;
         fl.took = &took;
-        // A/B switch (wrong labels): the tiles keep their score differences to themselves -- what the WRITE half of the hand-over
-        // between launches (8 B per gene + its five vector instructions) costs the step (profiles/r06_ab.txt)
-        static const bool ab_no_store = [] {
-            const char *env = std::getenv("GECCO_CRF_AB_NO_HANDOVER_STORE");
-            return env && env[0] == '1';
-        }();
-        if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, ab_no_store ? nullptr : d_dstate, stream,
+        if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, d_dstate, stream,
                                     (delta && prev_delta) ? &fl : nullptr)))
             return rc;
         p.pipe.pending = delta;

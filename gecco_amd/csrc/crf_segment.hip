@@ -26,7 +26,6 @@
 //                their gene offsets and -- on request -- the probabilities of their genes (what a cluster table needs of p)
 // Bound: HBM, 2 x 10 B/gene read + 4 B/gene written; four short launches (round 3: six + the gather).
 #include <algorithm>
-#include <cstdlib>
 
 #include "crf_device.hpp"
 #include "crf_scan.hpp"
@@ -447,11 +446,7 @@ hipError_t launch_segment(const double *d_p, const uint8_t *d_ann, const uint8_t
     a.gcap = gather_cap;
     a.row_c0 = params.row_contig0;
     a.row_g0 = params.row_gene0;
-    static const bool fused_small = [] {  // GECCO_CRF_SEGMENT_FUSED=0: the five launches for every batch (tests, A/B)
-        const char *e = std::getenv("GECCO_CRF_SEGMENT_FUSED");
-        return !(e && e[0] == '0');
-    }();
-    if (nb == 1 && fused_small) {
+    if (nb == 1) {
         a.flags = d_flags ? d_flags : own_flags;
         hipLaunchKernelGGL(seg_small, dim3(1), dim3(kT), 0, stream, a, d_flags ? 0 : 1);
         return hipGetLastError();

@@ -355,36 +355,6 @@ __device__ __forceinline__ LaneGenes load_lane(const SeqArgs &A, int slot, LaneS
     return L;
 }
 
-// Per-lane rows of kGPL consecutive 16-byte entries <-> global memory with coalesced accesses: a lane
-// touching its own kGPL entries directly hits 64 different cache lines per instruction.  Same
-// padded LDS transpose as load_lane; `stg` must not be in use (both end with a barrier).
-__device__ __forceinline__ void store_lane_rows(double2 *__restrict__ gmem, int n_genes, int slot, const double2 (&v)[kGPL],
-                                                LaneStage &stg) {
-    const int base = blockIdx.x * kT * kGPL;
-#pragma unroll
-    for (int k = 0; k < kGPL; ++k) stg.st[slot * (kGPL + 1) + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kGPL; ++j) {
-        const int idx = j * kT + slot, g = base + idx;
-        if (g < n_genes) gmem[g] = stg.st[(idx / kGPL) * (kGPL + 1) + idx % kGPL];
-    }
-    __syncthreads();
-}
-__device__ __forceinline__ void load_lane_rows(const double2 *__restrict__ gmem, int n_genes, int slot, double2 (&v)[kGPL],
-                                               LaneStage &stg) {
-    const int base = blockIdx.x * kT * kGPL;
-#pragma unroll
-    for (int j = 0; j < kGPL; ++j) {
-        const int idx = j * kT + slot, g = base + idx;
-        stg.st[(idx / kGPL) * (kGPL + 1) + idx % kGPL] = g < n_genes ? gmem[g] : make_double2(0.0, 0.0);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kGPL; ++k) v[k] = stg.st[slot * (kGPL + 1) + k];
-    __syncthreads();
-}
-
 // =====================================================================================
 // V: max-plus.  delta_0 = s_0; delta_t[j] = max_i(delta_{t-1}[i] + trans[i][j]) + s_t[j]; ties keep
 // the smaller i (CRFsuite updates on strict '<'); the end label is the first argmax.
@@ -719,144 +689,11 @@ __global__ void __launch_bounds__(kT) v_scores(const SeqArgs A, const int32_t *_
 // factors cancel in P_t(y) = alpha_t[y] beta_t[y] / (alpha_t . beta_t); exponents and emission
 // maxima are carried along only for log Z.
 // =====================================================================================
-// exp(s - max s): one of the two is exp(0) = 1 exactly, the other one exp(-|s1 - s0|)
-__device__ __forceinline__ double2 emit_norm(const SeqArgs &A, double2 s, double &m) {
-    const double d = s.y - s.x;
-    const double e = exp_neg(fabs(d), A.expc);
-    m = d > 0.0 ? s.y : s.x;
-    return d > 0.0 ? make_double2(e, 1.0) : make_double2(1.0, e);
-}
-__device__ __forceinline__ FE f_step(const SeqArgs &A, double2 s, bool first) {
-    double m;
-    const double2 e = emit_norm(A, s, m);
-    return FE{(first ? 1.0 : A.m00) * e.x, (first ? 1.0 : A.m01) * e.y, (first ? 1.0 : A.m10) * e.x,
-              (first ? 1.0 : A.m11) * e.y, 0.0, m, first ? 1.0 : 0.0};
-}
-
-__global__ void __launch_bounds__(kT) f_fold(const SeqArgs A) {
-    __shared__ FE lds[kT / 64];
-    __shared__ LaneStage stg;
-    const LaneGenes L = load_lane(A, threadIdx.x, stg);
-    FE P = FOp::identity();
-#pragma unroll
-    for (int k = 0; k < kGPL; ++k)
-        if (k < L.cnt) P = FOp::combine(P, f_step(A, L.s[k], (L.first >> k) & 1u));
-    FE total;
-    const FE excl = block_scan_exclusive<FOp, false>(P, lds, &total);
-    A.fLane[blockIdx.x * kT + threadIdx.x] = excl;
-    if (threadIdx.x == 0) A.fBlock[blockIdx.x] = total;
-}
-
-// forward replay (alpha of every gene, cumulative log-mass at contig ends) + fold of the
-// backward matrices B_t, scanned back to front
-__global__ void __launch_bounds__(kT) f_replay(const SeqArgs A) {
-    __shared__ FE lds[kT / 64];
-    __shared__ FE xch[kT];
-    __shared__ LaneStage stg;
-    const int slot = threadIdx.x;
-    const LaneGenes L = load_lane(A, slot, stg);
-    const FE M = FOp::combine(lookback_prefix(A.fBlock, blockIdx.x), A.fLane[blockIdx.x * kT + slot]);
-    // alpha entering the lane = a row of M (rows are identical once a contig has started), with the
-    // exponent and emission-maximum sums accumulated since that contig's first gene
-    double a0 = M.a00, a1 = M.a01, ex = M.ex, ms = M.ms;
-    const double2 s_next = (L.cnt == kGPL && L.g0 + kGPL < A.n_genes) ? A.state[L.g0 + kGPL] : make_double2(0.0, 0.0);
-    FE Bfold = FOp::identity();
-    double2 al[kGPL];
-#pragma unroll
-    for (int k = 0; k < kGPL; ++k) {
-        al[k] = make_double2(0.0, 0.0);
-        if (k < L.cnt) {
-            double m;
-            const double2 e = emit_norm(A, L.s[k], m);
-            double n0, n1;
-            if ((L.first >> k) & 1u) {  // alpha_0 = exp(s_0): restart exactly
-                n0 = n1 = 1.0;
-                ex = 0.0;
-                ms = 0.0;
-            } else {
-                n0 = fma(a1, A.m10, a0 * A.m00);
-                n1 = fma(a1, A.m11, a0 * A.m01);
-            }
-            a0 = n0 * e.x;
-            a1 = n1 * e.y;
-            int ee;
-            (void)frexp(fmax(a0, a1), &ee);
-            a0 = ldexp(a0, -ee);
-            a1 = ldexp(a1, -ee);
-            ex += double(ee);
-            ms += m;
-            al[k] = make_double2(a0, a1);
-            if ((L.last >> k) & 1u) {
-                // log Z' of the contig (max-normalised emissions / transitions) and its emission maxima
-                A.contigTmp[L.g0 + k] = make_double2(ex * 0.6931471805599453 + log(a0 + a1), ms);
-            }
-            // backward matrix of this gene
-            const bool last = (L.last >> k) & 1u;
-            const double2 sn = k + 1 < kGPL ? L.s[k + 1 < kGPL ? k + 1 : k] : s_next;
-            FE B;
-            if (last) {
-                B = FE{1.0, 1.0, 1.0, 1.0, 0.0, 0.0, 1.0};  // rs: everything after this gene only scales the product
-            } else {
-                B = f_step(A, sn, false);
-            }
-            Bfold = FOpB::combine(Bfold, B);  // B_{g0} B_{g0+1} ... in sequence order
-        }
-    }
-    store_lane_rows(A.alpha, A.n_genes, slot, al, stg);
-    xch[kT - 1 - slot] = Bfold;
-    __syncthreads();
-    const FE mine = xch[slot];
-    FE total;
-    const FE excl = block_scan_exclusive<FOpB, true>(mine, lds, &total);
-    __syncthreads();
-    xch[kT - 1 - slot] = excl;
-    __syncthreads();
-    A.fLaneSuf[blockIdx.x * kT + slot] = xch[slot];
-    if (slot == 0) A.fBlockSuf[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kT) f_marginals(const SeqArgs A) {
-    __shared__ LaneStage stg;
-    const int slot = threadIdx.x;
-    const LaneGenes L = load_lane(A, slot, stg);
-    double2 al[kGPL], out[kGPL];
-    load_lane_rows(A.alpha, A.n_genes, slot, al, stg);
-    // beta entering from the right of the lane: (suffix of the lanes to the right) 1
-    const FE S = FOpB::combine(A.fLaneSuf[blockIdx.x * kT + slot], lookahead_suffix(A.fBlockSuf, blockIdx.x, gridDim.x));
-    double b0 = S.a00 + S.a01, b1 = S.a10 + S.a11;
-    const double2 s_next = (L.cnt == kGPL && L.g0 + kGPL < A.n_genes) ? A.state[L.g0 + kGPL] : make_double2(0.0, 0.0);
-#pragma unroll
-    for (int k = kGPL - 1; k >= 0; --k) {
-        out[k] = make_double2(0.0, 0.0);
-        if (k < L.cnt) {
-            // beta_k = B_k beta_{k+1}
-            if ((L.last >> k) & 1u) {
-                b0 = b1 = 1.0;
-            } else {
-                double m;
-                const double2 e = emit_norm(A, k + 1 < kGPL ? L.s[k + 1 < kGPL ? k + 1 : k] : s_next, m);
-                const double c0 = e.x * b0, c1 = e.y * b1;
-                b0 = fma(A.m01, c1, A.m00 * c0);
-                b1 = fma(A.m11, c1, A.m10 * c0);
-                int ee;
-                (void)frexp(fmax(b0, b1), &ee);
-                b0 = ldexp(b0, -ee);
-                b1 = ldexp(b1, -ee);
-            }
-            const double x0 = al[k].x * b0, x1 = al[k].y * b1, z = x0 + x1;
-            double r = __builtin_amdgcn_rcp(z);  // one reciprocal (+ Newton step) instead of two divisions
-            r = fma(fma(-z, r, 1.0), r, r);
-            out[k] = make_double2(x0 * r, x1 * r);
-        }
-    }
-    store_lane_rows(reinterpret_cast<double2 *>(A.marg), A.n_genes, slot, out, stg);
-}
-
 // ---- short contigs: whole-contig marginals in ONE launch on 8-byte inputs --------------------------------
 // Workgroups own whole contigs (`cblk`), so the forward products, alpha, the backward products and the marginals
 // of a gene all stay in the registers of the lane that owns it: per gene 8 B are read (s[1] - s[0]: every
 // marginal depends on the emissions only through that difference; + 8 B of emission maxima when log Z is
-// wanted) and 16 B written.  The general path above reads 16-byte states three times and parks alpha in HBM.
+// wanted) and 16 B written.
 __device__ __forceinline__ double2 emit_d(const SeqArgs &A, double d) {
     const double e = exp_neg(fabs(d), A.expc);
     return d > 0.0 ? make_double2(e, 1.0) : make_double2(1.0, e);
@@ -1228,18 +1065,6 @@ hipError_t launch_seq_marginals_short(const SeqArgs &a, const int32_t *gene_ptr,
         }
     }
     if (!a.short_contigs && a.lognorm) hipLaunchKernelGGL(f_lognorm, grid_for(a.n_contigs, kT), dim3(kT), 0, stream, a, d_contig_ptr);
-    return hipGetLastError();
-}
-
-hipError_t launch_seq_marginals(const SeqArgs &a, const int32_t *d_contig_ptr, hipStream_t stream) {
-    if (a.n_contigs <= 0) return hipSuccess;
-    if (a.n_genes > 0) {
-        const int nb = (a.n_genes + kBlockGenes - 1) / kBlockGenes;
-        hipLaunchKernelGGL(f_fold, dim3(nb), dim3(kT), 0, stream, a);
-        hipLaunchKernelGGL(f_replay, dim3(nb), dim3(kT), 0, stream, a);
-        hipLaunchKernelGGL(f_marginals, dim3(nb), dim3(kT), 0, stream, a);
-    }
-    if (a.lognorm) hipLaunchKernelGGL(f_lognorm, grid_for(a.n_contigs, kT), dim3(kT), 0, stream, a, d_contig_ptr);
     return hipGetLastError();
 }
 

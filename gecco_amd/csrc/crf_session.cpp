@@ -639,11 +639,8 @@ int submit_direct_arrays(RunCtx &X, Lane &ln, int chunk_index) {
     // An input array of kCopy bytes and more goes to device memory by a copy command on the compute stream (~8 us of engine
     // turnaround + the transfer, against a PCIe round trip for every tile that reads it in place); smaller ones are read from
     // the staging block.  tools/direct_sweep.py, us per windowed call at 20 000 / 40 000 / 65 000 genes: copy from 64 KB on
-    // 47.6 / 53.5 / 61.1, from 256 KB 34.0 / 44.2 / 49.7, from 1 MB 34.6 / 42.0 / 55.5.  (GECCO_CRF_DIRECT_COPY_BYTES: A/B runs)
-    static const size_t kCopy = [] {
-        const char *e = std::getenv("GECCO_CRF_DIRECT_COPY_BYTES");
-        return e ? size_t(std::atoll(e)) : size_t(262144);
-    }();
+    // 47.6 / 53.5 / 61.1, from 256 KB 34.0 / 44.2 / 49.7, from 1 MB 34.6 / 42.0 / 55.5.
+    constexpr size_t kCopy = 262144;
     const bool c_gp = (ng + 1) * 4 >= kCopy, c_at = nnz * 4 >= kCopy && !r.attr_id16;
     if (c_gp) {
         if ((rc = ln.d_gp.reserve((ng + 1) * 4, "hipMalloc gene_ptr"))) return rc;
@@ -743,12 +740,8 @@ int submit_plan(RunCtx &X, Lane &ln, int chunk_index) {
     {
         // marginals (and labels) only: the window kernel reads the plan tables (~0.1 MB per chunk, each word once) from the
         // plan's pinned block itself -- one copy and one ~10 us gap between copies less per chunk.  The refiner and the
-        // whole-contig marginals search the contig table many times: for them it is copied.  GECCO_CRF_TABLES_COPY=1: always copy
-        static const bool always_copy = [] {
-            const char *env = std::getenv("GECCO_CRF_TABLES_COPY");
-            return env && env[0] == '1';
-        }();
-        ln.plan.tables_in_host_memory = !always_copy && !r.want_segments && !X.full && !r.score_out;
+        // whole-contig marginals search the contig table many times: for them it is copied.
+        ln.plan.tables_in_host_memory = !r.want_segments && !X.full && !r.score_out;
         // copied tables are fetched by a small launch at the head of the chunk's kernels, not by the copy engine: the upload
         // stream then carries nothing but the chunks' arrays, back to back (a copy issued behind the next chunk's arrays
         // would hold this chunk's kernels back until those have crossed; every copy also costs ~10 us of engine turnaround)
@@ -867,36 +860,18 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     const int32_t *d_at = reinterpret_cast<const int32_t *>(ln.d_at.p) - a0;
     double *d_p = nullptr, *d_score = nullptr;
     int8_t *d_y = nullptr;
-    // Where the tiles write p: the lane's device buffer, downloaded by a copy.  GECCO_CRF_P_TO_HOST=1 (experiment, round 5): into
-    // the caller's own array when it is pinned and nothing on the device reads p again -- the probabilities then cross PCIe as
-    // the tiles' posted writes and the chunk has no download of 8 bytes per gene.  Not faster: the tiles' stores share the link
-    // with the next chunk's upload less gracefully than the copy engine does (tools/ubench/pcie_bw.hip: 19 MB up + 16 MB down
-    // at once 354 us by copies, 432 us with the download done by a kernel's stores).
-    bool p_to_host = false;
+    // The tiles write p to the lane's device buffer, downloaded by a copy.  (Writing it straight into a pinned caller array was
+    // measured slower: the tiles' stores share the link with the next chunk's upload less gracefully than the copy engine does,
+    // tools/ubench/pcie_bw.hip; C3 with pinned buffers 0.619 ms against 0.609 through a copy.)
     if (X.windowed) {
-        static const bool allowed = [] {  // (off by default: measured on C3, pinned buffers: 0.619 ms against 0.609 through a copy)
-            const char *env = std::getenv("GECCO_CRF_P_TO_HOST");
-            return env && env[0] == '1';
-        }();
-        double *m_p = nullptr;
-        if (allowed && r.p_out && !r.want_segments && !ck.piece && !ln.plan.general && ln.plan.fast_ok) m_p = mapped_or_null(r.p_out + ck.g0);
-        if (m_p) {
-            d_p = m_p;
-            p_to_host = true;
-        } else {
-            if ((rc = ln.d_p.reserve(size_t(ng) * 8, "hipMalloc p"))) return rc;
-            d_p = reinterpret_cast<double *>(ln.d_p.p);
-        }
+        if ((rc = ln.d_p.reserve(size_t(ng) * 8, "hipMalloc p"))) return rc;
+        d_p = reinterpret_cast<double *>(ln.d_p.p);
     }
     if (X.viterbi) {
         // Labels (a byte per gene) go straight into the caller's array when it is pinned: a chunk's 0.5 MB of them cost a copy
         // command and its ~12 us of engine turnaround each -- on the download stream, which is the critical path of a decode
-        // call on the compact wire format -- and nothing as stores of the decoder.  GECCO_CRF_Y_TO_HOST=0: always a copy.
-        static const bool y_allowed = [] {
-            const char *env = std::getenv("GECCO_CRF_Y_TO_HOST");
-            return !(env && env[0] == '0');
-        }();
-        int8_t *m_y = (y_allowed && r.y_out && !ck.piece) ? mapped_or_null(r.y_out + ck.g0) : nullptr;
+        // call on the compact wire format -- and nothing as stores of the decoder.
+        int8_t *m_y = (r.y_out && !ck.piece) ? mapped_or_null(r.y_out + ck.g0) : nullptr;
         ln.y_to_host = m_y != nullptr;
         if (m_y) {
             d_y = m_y;
@@ -920,10 +895,8 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
         if ((rc = check_hip(hipEventRecord(ln.ev_comp, ln.comp), "hipEventRecord"))) return rc;
         if ((rc = check_hip(hipStreamWaitEvent(ln.down, ln.ev_comp, 0), "hipStreamWaitEvent"))) return rc;
         if (prev && (rc = finish_pending(X, D))) return rc;
-        if (!p_to_host) {
-            ln.st->d2h_bytes += int64_t(ng) * 8;
-            if ((rc = check_hip(hipMemcpyAsync(r.p_out + ck.g0, d_p, size_t(ng) * 8, hipMemcpyDeviceToHost, ln.down), "D2H p"))) return rc;
-        }
+        ln.st->d2h_bytes += int64_t(ng) * 8;
+        if ((rc = check_hip(hipMemcpyAsync(r.p_out + ck.g0, d_p, size_t(ng) * 8, hipMemcpyDeviceToHost, ln.down), "D2H p"))) return rc;
         D.pending = &ln;  // (its labels and its `done` come with the device's next launch, or with the flush)
         tm.lap("launch", chunk_index);
         return GECCO_CRF_OK;
@@ -976,7 +949,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
             return rc;
     }
     tm.lap("launch", chunk_index);
-    const bool c_p = r.p_out && !p_to_host, c_y = r.y_out && !ln.y_to_host, c_score = r.score_out, c_marg = r.marg_out, c_ln = r.lognorm_out;
+    const bool c_p = r.p_out, c_y = r.y_out && !ln.y_to_host, c_score = r.score_out, c_marg = r.marg_out, c_ln = r.lognorm_out;
     if (!(c_p || c_y || c_score || c_marg || c_ln)) return check_hip(hipEventRecord(ln.done, ln.comp), "hipEventRecord");
     if ((rc = check_hip(hipEventRecord(ln.ev_comp, ln.comp), "hipEventRecord"))) return rc;
     if ((rc = check_hip(hipStreamWaitEvent(ln.down, ln.ev_comp, 0), "hipStreamWaitEvent"))) return rc;

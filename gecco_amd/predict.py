@@ -47,7 +47,8 @@ def filter_features(feats_t: tables.FeatureTable, e_filter: Optional[float] = No
 def _refiner_order_differs(sid_code: np.ndarray, start: np.ndarray, end: np.ndarray) -> bool:
     """The CRF scores genes in (contig, start) order (crf/__init__.py:199), the refiner walks them in
     (contig, start, end) order (refine.py:190): they differ only if two genes of a contig share a start and
-    their ends come in decreasing order."""
+    their ends come in decreasing order.  predict_tables asks the packed batch's native `order_info`; this numpy form is
+    what tests/test_host_logic.py checks it against."""
     if len(start) < 2:
         return False
     tie = (sid_code[1:] == sid_code[:-1]) & (start[1:] == start[:-1])
@@ -119,17 +120,11 @@ def predict_tables(genes_t: tables.GeneTable, feats_t: tables.FeatureTable, crf:
     in_order, reorder = have_row and n == 0, None
     if have_row and n:
         g_start_all = np.asarray(genes_t.start, dtype=np.int64)
-        if os.environ.get("GECCO_AMD_TABLES_NUMPY_PASSES") == "1":  # A/B switch: the numpy passes of round 5
-            in_order = len(genes_t) == n and rows[0] == 0 and bool(np.all(np.diff(rows) == 1))
-            differs = _refiner_order_differs(np.repeat(np.arange(pk.n_contigs), lengths), g_start_all if in_order else g_start_all[rows],
-                                             g_end_all if in_order else g_end_all[rows])
-        else:
-            in_order, differs = pk.order_info(g_start_all, g_end_all)
+        in_order, differs = pk.order_info(g_start_all, g_end_all)
         if differs:
             g_start_o = g_start_all if in_order else g_start_all[rows]
             g_end_o = g_end_all if in_order else g_end_all[rows]
             code = np.repeat(np.arange(pk.n_contigs), lengths)
-            assert _refiner_order_differs(code, g_start_o, g_end_o)
             reorder = np.lexsort((g_end_o, g_start_o, code))
     if reorder is None:
         seg, seg_p, seg_off, p = session.clusters(cptr, pk.gene_ptr, pk.attr_id, pk.annotated, W, crf.window_step, label, pad,
@@ -166,10 +161,7 @@ def predict_tables(genes_t: tables.GeneTable, feats_t: tables.FeatureTable, crf:
 
     # ---- features table: every domain row carries its gene's probability (features.py:92-96)
     fcols = dict(feats_t.columns)
-    if os.environ.get("GECCO_AMD_TABLES_NUMPY_PASSES") == "1":
-        fcols["cluster_probability"] = p[pk.row_gene] if pk.n_rows else np.zeros(0)
-    else:
-        fcols["cluster_probability"] = _native.gather_f64(p, pk.row_gene) if pk.n_rows else np.zeros(0)
+    fcols["cluster_probability"] = _native.gather_f64(p, pk.row_gene) if pk.n_rows else np.zeros(0)
     feats_out = tables.FeatureTable(fcols)
 
     # ---- clusters table (gecco/model.py:731-760)

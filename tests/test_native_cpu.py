@@ -216,3 +216,25 @@ def test_exp_fast_path_equals_the_slow_routine(tmp_path):
                            os.path.join(ROOT, "tests", "exp_fast_vs_slow.cpp"), "-o", exe])
     out = subprocess.run([exe, "2500000"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "mismatches 0" in out.stdout, out.stdout + out.stderr
+
+
+def test_environment_switches_are_the_ones_design_lists():
+    """Every GECCO_* variable the library (`getenv` under gecco_amd/csrc) or the package (`os.environ` under gecco_amd and in
+    __graft_entry__.py) reads is a row of DESIGN.md section 8, and every row is read somewhere: a switch cannot come back,
+    or go, unnoticed."""
+    read = set()
+    for top, pattern in ((os.path.join(ROOT, "gecco_amd", "csrc"), r'getenv\(\s*"(GECCO_\w+)"'),
+                         (os.path.join(ROOT, "gecco_amd"), r'os\.(?:environ\.get\(|environ\[|getenv\()\s*"(GECCO_\w+)"')):
+        for d, _, files in os.walk(top):
+            for f in files:
+                if f.endswith((".py", ".c", ".cpp", ".hpp", ".hip", ".h")):
+                    read |= set(re.findall(pattern, open(os.path.join(d, f)).read()))
+    read |= set(re.findall(r'os\.(?:environ\.get\(|environ\[|getenv\()\s*"(GECCO_\w+)"',
+                           open(os.path.join(ROOT, "__graft_entry__.py")).read()))
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("\n## 8. "):]
+    section = section[:section.index("\n## 9. ")]
+    listed = re.findall(r"^\| `(GECCO_\w+)` \|", section, re.M)
+    assert len(listed) == len(set(listed)), "a variable is listed twice"
+    assert read, "no reads found: the patterns no longer match the code"
+    assert set(listed) == read, f"read but not listed: {sorted(read - set(listed))}; listed but not read: {sorted(set(listed) - read)}"
