@@ -238,3 +238,23 @@ def test_environment_switches_are_the_ones_design_lists():
     assert len(listed) == len(set(listed)), "a variable is listed twice"
     assert read, "no reads found: the patterns no longer match the code"
     assert set(listed) == read, f"read but not listed: {sorted(read - set(listed))}; listed but not read: {sorted(set(listed) - read)}"
+
+
+def test_named_tools_exist_or_are_marked_removed():
+    """Every `tools/…` script or source (.py .sh .hip .cpp .hpp .c .h) that a document, comment or script names is in the
+    tree, or is followed on the same line by `(removed`: a deleted tool cannot stay referenced unnoticed.  The raw records
+    in profiles/ (everything there but *.md) and the fixtures under tests/golden/ are left as they were written."""
+    named = re.compile(r"(?<![\w/.])tools/[\w/]+\.(?:py|sh|hip|cpp|hpp|c|h)\b")
+    dangling = []
+    for d, dirs, files in os.walk(ROOT):
+        dirs[:] = [x for x in dirs if not x.startswith((".", "_")) and x != "build" and os.path.join(d, x) != GOLDEN]
+        for f in files:
+            path = os.path.join(d, f)
+            if not f.endswith((".md", ".py", ".sh", ".hip", ".cpp", ".hpp", ".c", ".h")) or (
+                    os.path.basename(d) == "profiles" and not f.endswith(".md")):
+                continue
+            for n, line in enumerate(open(path, errors="replace"), 1):
+                for m in named.finditer(line):
+                    if not os.path.exists(os.path.join(ROOT, m.group())) and "(removed" not in line[m.end():]:
+                        dangling.append(f"{os.path.relpath(path, ROOT)}:{n}: {m.group()}")
+    assert not dangling, "named but not in the tree (mark them `(removed; see git history)`):\n" + "\n".join(dangling)
