@@ -295,6 +295,10 @@ struct GenArgs {
     double *chZ;               // [n_chunks]     partial log-partition
     uint8_t *chMap;            // [n_chunks*L]   label of the chunk's last gene -> label of the gene before the chunk
     int8_t *chY;               // [n_chunks]     label of the chunk's last gene
+    // chunked Viterbi: decisions inside the margin (gl_chunk_vit) send their contigs to CRFsuite's recursion (gl_viterbi_seq)
+    uint8_t *fix_flag;            // [n_contigs] 1 = decode this contig again; zero at rest
+    uint32_t *vit_stats;          // [4] as SeqArgs::vd_stats: lanes with a decision inside the margin (x2), contigs, genes re-decoded
+    double v_wmax, v_tmax;        // max |state weight|, max |transition|: the bound M of the margin
     int32_t wave_tmax;            // gl_viterbi_wave: contigs longer than this are left to the chunked kernels (0: none is)
     int32_t rows_rescale_period;  // gl_chunk_rows_mfma: steps between two power-of-two rescalings of a column (1 or 4; host: 4 max|trans| < 600)
     // windowed path: slot space of the plan

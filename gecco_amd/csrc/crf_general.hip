@@ -514,7 +514,9 @@ __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
 // ---- row V: whole-contig Viterbi, one group per contig ------------------------------------------
 constexpr int kBackRows = 32;  // back-pointer rows walked from LDS per global round trip
 
-template <int LP>
+// FIX: only the contigs gl_chunk_vit flagged (a decision inside its margin), whose labels and score this overwrites with
+// CRFsuite's; their flags are cleared again
+template <int LP, bool FIX = false>
 __global__ void __launch_bounds__(kGT) gl_viterbi_seq(GenArgs a) {
     __shared__ double vecs[kGT];
     __shared__ uint8_t rows[kGT * kBackRows];
@@ -524,8 +526,14 @@ __global__ void __launch_bounds__(kGT) gl_viterbi_seq(GenArgs a) {
     uint8_t *row = rows + grp * LP * kBackRows;
     const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
     if (ci >= a.n_contigs) return;
+    if (FIX && !a.fix_flag[ci]) return;  // (group-uniform)
     const int L = a.L;
     const int g0 = a.contig_ptr[ci], T = a.contig_ptr[ci + 1] - g0;
+    if (FIX && j == 0) {
+        a.fix_flag[ci] = 0;  // (every lane of the group has read it: they run in step)
+        atomicAdd(a.vit_stats + 2, 1u);
+        atomicAdd(a.vit_stats + 3, uint32_t(T));
+    }
     if (T <= 0) {
         if (j == 0 && a.score) a.score[ci] = 0.0;
         return;
@@ -1383,6 +1391,14 @@ __global__ void __launch_bounds__(kGT) gl_chunk_vit(GenArgs a) {
     double tcol[LP];
 #pragma unroll
     for (int k = 0; k < LP; ++k) tcol[k] = (k < L && on) ? a.trans[k * L + j] : 0.0;
+    // The margin (crf_sequence.hip, v_margin, argues it for two labels; nothing in it depends on L): the entering vector is
+    // composed from chunk products, so each delta_t[j] here -- and CRFsuite's -- is within t ulp(M) of the exact maximum,
+    // M = nnz max|w| + (n + 2) max|trans| bounding every partial sum of the contig's paths.  Where the best candidate of a
+    // decision leads the second best by at most (4 t + 8) ulp(M), t = the gene's position in its contig, the two sides may
+    // disagree: the contig is flagged and gl_viterbi_seq<FIX> decodes it again, the way CRFsuite does.
+    const double ulpM = (double(a.gene_ptr[cend] - a.gene_ptr[cfirst]) * a.v_wmax + double(cend - cfirst + 2) * a.v_tmax) *
+                        2.220446049250313e-16;
+    bool inside = false;
     double d = on ? a.chV[static_cast<size_t>(ci) * L + j] : -DBL_MAX;
     for (int t = g0; t < g1; ++t) {
         const double s_t = on ? a.state[static_cast<size_t>(t) * L + jj] : 0.0;
@@ -1392,36 +1408,54 @@ __global__ void __launch_bounds__(kGT) gl_chunk_vit(GenArgs a) {
         }
         vec[j] = d;
         __builtin_amdgcn_wave_barrier();
-        double best = -DBL_MAX;
+        double best = -DBL_MAX, second = -DBL_MAX;
         int arg = -1;
 #pragma unroll
         for (int k = 0; k < LP; ++k) {
             if (k < L) {
                 const double sc = vec[k] + tcol[k];
                 if (best < sc) {
+                    second = best;
                     best = sc;
                     arg = k;
+                } else {
+                    second = fmax(second, sc);
                 }
             }
         }
         __builtin_amdgcn_wave_barrier();
         if (on) a.back[static_cast<size_t>(t) * L + j] = static_cast<uint8_t>(arg < 0 ? 0 : arg);
+        inside |= on && L > 1 && best - second <= (4.0 * double(t - cfirst) + 8.0) * ulpM;
         d = best + s_t;
     }
     if (g1 == cend) {  // first arg max of the final scores
         vec[j] = d;
         __builtin_amdgcn_wave_barrier();
         if (j == 0) {
-            double best = -DBL_MAX;
+            double best = -DBL_MAX, second = -DBL_MAX;
             int y = 0;
-            for (int k = 0; k < L; ++k)
+            for (int k = 0; k < L; ++k) {
                 if (best < vec[k]) {
+                    second = best;
                     best = vec[k];
                     y = k;
+                } else {
+                    second = fmax(second, vec[k]);
                 }
+            }
             a.chY[ci] = static_cast<int8_t>(y);
             if (a.score) a.score[ct] = best;
+            inside |= L > 1 && best - second <= (4.0 * double(cend - cfirst) + 8.0) * ulpM;
         }
+    }
+    // one flag and one count per chunk with a decision inside the margin (the first such lane of the group)
+    const unsigned long long bal = __ballot(inside);
+    const int lane = threadIdx.x & 63, gbase = lane & ~(LP - 1);
+    const unsigned long long gm = (bal >> gbase) & ((1ull << LP) - 1ull);
+    if (a.fix_flag && gm && lane == gbase + __builtin_ctzll(gm)) {
+        a.fix_flag[ct] = 1;
+        atomicAdd(a.vit_stats + 0, 1u);
+        atomicAdd(a.vit_stats + 1, 1u);
     }
 }
 
@@ -1518,6 +1552,8 @@ hipError_t launch_chunked(int what, const GenArgs &a, hipStream_t stream) {
         hipLaunchKernelGGL(gl_chunk_maps<LP>, blocks(a.n_chunks, G), dim3(kGT), 0, stream, a);
         hipLaunchKernelGGL(gl_chunk_ends, blocks(a.n_contigs, kGT / 64), dim3(kGT), 0, stream, a);
         hipLaunchKernelGGL(gl_chunk_backtrack, blocks(a.n_chunks, kGT), dim3(kGT), 0, stream, a);
+        // contigs with a decision inside the margin: CRFsuite's recursion, one group of lanes per flagged contig
+        if (a.fix_flag) hipLaunchKernelGGL((gl_viterbi_seq<LP, true>), blocks(a.n_contigs, G), dim3(kGT), 0, stream, a);
     }
     return hipGetLastError();
 }

@@ -495,6 +495,8 @@ inline size_t align256g(size_t x) { return (x + 255) & ~size_t(255); }
 // below it, one group of lanes per contig walking it sequentially is the cheaper arrangement.
 constexpr int32_t kGenLongContig = 2048;
 
+inline size_t gen_fix_bytes(const Plan &p) { return align256g(size_t(p.n_contigs) + 16); }
+
 // chunk_min_len >= 0: only contigs LONGER than that get chunks (the second table set); -1: every contig
 int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, GenArgs &a, bool whole_contig = false,
                   hipStream_t stream = nullptr, int32_t chunk_min_len = -1) {
@@ -556,13 +558,22 @@ int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, 
     }
     const size_t b_chM = align256g(nch * L * L * 8 + 8), b_chv = align256g(nch * L * 8 + 8), b_chs = align256g(nch * 8 + 8);
     const size_t b_chunks = chunked ? b_chM + 3 * b_chv + 2 * b_chs + 2 * align256g(nch * L + 8) : 0;
+    // in front of everything, at a fixed place: the chunked Viterbi's counters (4 x u32) and contig flags, zero at rest (the
+    // re-decode clears the flags it reads); zeroed when the block is allocated
+    const size_t b_fix = gen_fix_bytes(p);
     {
         std::lock_guard<std::mutex> lock(p.ws_mutex);
-        int rc = grow_ws(p.d_gen_ws, p.gen_ws_cap, 3 * b_vec + 2 * b_one + b_back + b_chunks, "hipMalloc general-L workspace");
+        const size_t cap0 = p.gen_ws_cap;
+        int rc = grow_ws(p.d_gen_ws, p.gen_ws_cap, b_fix + 3 * b_vec + 2 * b_one + b_back + b_chunks, "hipMalloc general-L workspace");
         if (rc) return rc;
+        if (p.gen_ws_cap != cap0 && (rc = check_hip(hipMemsetAsync(p.d_gen_ws, 0, b_fix, stream), "memset contig flags"))) return rc;
     }
-    char *w = p.d_gen_ws;
+    char *w = p.d_gen_ws + b_fix;
     a = GenArgs{};
+    a.vit_stats = reinterpret_cast<uint32_t *>(p.d_gen_ws);
+    a.fix_flag = reinterpret_cast<uint8_t *>(p.d_gen_ws + 16);
+    a.v_wmax = p.tables_model->wmax_abs;
+    a.v_tmax = p.tables_model->tmax_abs;
     a.gene_ptr = d_gene_ptr;
     a.attr_id = d_attr_id;
     a.wtab = p.tables_model->wtab;
@@ -1068,12 +1079,14 @@ int fill_seq_args(Plan &p, SeqArgs &a, hipStream_t stream) {
 }
 }  // namespace
 
-// Labels without path scores from a 2-label model whose transitions satisfy lo <= hi take the
-// difference form (8 B/gene, 24-B scan elements); GECCO_CRF_VITERBI=matrix forces the general form.
-static bool viterbi_delta_ok(const SeqArgs &a, const double *d_score) {
+// Labels of a 2-label model whose transitions satisfy lo <= hi come from the difference form (8 B/gene, 24-B scan
+// elements), the one decoder with a margin test and CRFsuite's own recursion behind it.  A path score, where
+// one is requested, comes from the max-plus scan (v_fold -> v_replay -> v_scores) run in front of it without its labels.
+// GECCO_CRF_VITERBI=matrix forces the matrix form for the labels too.
+static bool viterbi_delta_ok(const SeqArgs &a) {
     const char *env = std::getenv("GECCO_CRF_VITERBI");
     if (env && env[0] == 'm') return false;
-    return !d_score && a.v_lo <= a.v_hi && std::isfinite(a.v_lo) && std::isfinite(a.v_hi);
+    return a.v_lo <= a.v_hi && std::isfinite(a.v_lo) && std::isfinite(a.v_hi);
 }
 
 int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, double *d_marg,
@@ -1180,16 +1193,19 @@ int plan_run_viterbi(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_i
     a.csr_attr_id = d_attr_id;
     a.csr_wtab01 = p.tables_model->wtab2[1];
     a.csr_n_attrs = p.model->A;
-    if (viterbi_delta_ok(a, d_score)) {
-        if ((rc = check_hip(launch_seq_state_delta(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
-                                                   const_cast<double *>(a.dstate), stream), "state score launch")))
+    const bool delta = viterbi_delta_ok(a);
+    if (!delta || d_score) {
+        if ((rc = check_hip(launch_seq_state(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
+                                             const_cast<double2 *>(a.state), stream), "state score launch")))
             return rc;
-        return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
+        SeqArgs m = a;
+        if (delta) m.y = nullptr;  // the scores only: the labels are the difference form's, below
+        if ((rc = check_hip(launch_seq_viterbi(m, p.d_contig_ptr, stream), "viterbi launch")) || !delta) return rc;
     }
-    if ((rc = check_hip(launch_seq_state(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
-                                         const_cast<double2 *>(a.state), stream), "state score launch")))
+    if ((rc = check_hip(launch_seq_state_delta(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
+                                               const_cast<double *>(a.dstate), stream), "state score launch")))
         return rc;
-    return check_hip(launch_seq_viterbi(a, p.d_contig_ptr, stream), "viterbi launch");
+    return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
 }
 
 
@@ -1221,14 +1237,21 @@ int plan_run_decode(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id
     a.csr_attr_id = d_attr_id;
     a.csr_wtab01 = p.tables_model->wtab2[1];
     a.csr_n_attrs = p.model->A;
-    if (viterbi_delta_ok(a, d_score)) {
+    const bool delta = viterbi_delta_ok(a);
+    if (delta && !d_score) {
         if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, const_cast<double *>(a.dstate), stream)))
             return rc;
         return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
     }
     if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, const_cast<double2 *>(a.state), nullptr, stream)))
         return rc;
-    return check_hip(launch_seq_viterbi(a, p.d_contig_ptr, stream), "viterbi launch");
+    SeqArgs m = a;
+    if (delta) m.y = nullptr;  // a score requested: the max-plus scan gives it, the difference form the labels (plan_run_viterbi)
+    if ((rc = check_hip(launch_seq_viterbi(m, p.d_contig_ptr, stream), "viterbi launch")) || !delta) return rc;
+    if ((rc = check_hip(launch_seq_state_delta(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
+                                               const_cast<double *>(a.dstate), stream), "state score launch")))
+        return rc;
+    return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
 }
 
 int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
@@ -1279,7 +1302,7 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
             } else if ((rc = fill_seq_args(p, ca, stream))) {
                 return rc;
             }
-            if (viterbi_delta_ok(ca, nullptr)) {
+            if (viterbi_delta_ok(ca)) {
                 delta = true;
                 d_dstate = const_cast<double *>(reinterpret_cast<const double *>(ca.state)) + size_t(parity) * (size_t(p.n_genes) + 8);
             }
@@ -1304,12 +1327,14 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset) {
     for (int i = 0; i < 4; ++i) out[i] = 0;
     std::lock_guard<std::mutex> lock(p.ws_mutex);
-    if (p.device < 0 || !p.d_seq_ws) return GECCO_CRF_OK;  // nothing has been decoded yet
+    // (any-L plans: the counters of the chunked Viterbi, in front of the general-L workspace)
+    char *base = p.general ? p.d_gen_ws : p.d_seq_ws;
+    if (p.device < 0 || !base) return GECCO_CRF_OK;  // nothing has been decoded yet
     int rc = use_device(p.device);
     if (rc) return rc;
     if ((rc = check_hip(hipDeviceSynchronize(), "hipDeviceSynchronize"))) return rc;
     uint32_t v[4] = {0, 0, 0, 0};
-    char *at = p.d_seq_ws + seq_layout(size_t(p.n_genes)).off_stats;
+    char *at = p.general ? base : base + seq_layout(size_t(p.n_genes)).off_stats;
     if ((rc = check_hip(hipMemcpy(v, at, sizeof(v), hipMemcpyDeviceToHost), "read decoder counters"))) return rc;
     for (int i = 0; i < 4; ++i) out[i] = v[i];
     if (reset) rc = check_hip(hipMemset(at, 0, sizeof(v)), "clear decoder counters");

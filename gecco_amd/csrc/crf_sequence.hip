@@ -359,6 +359,19 @@ __device__ __forceinline__ LaneGenes load_lane(const SeqArgs &A, int slot, LaneS
 // V: max-plus.  delta_0 = s_0; delta_t[j] = max_i(delta_{t-1}[i] + trans[i][j]) + s_t[j]; ties keep
 // the smaller i (CRFsuite updates on strict '<'); the end label is the first argmax.
 // =====================================================================================
+// When is a decision of the matrix form provably crf1dc_viterbi's?  Rounding is monotone, so fl(max(x, y) + c) =
+// max(fl(x + c), fl(y + c)): whatever the grouping -- lanes folded, waves scanned, workgroups looked back over --, a
+// computed delta_t[j] is the maximum over the paths ending in (t, j) of each path's sum rounded in that grouping.  Such a
+// path has 2 t + 1 terms, every partial sum of which is bounded by M (vd_bound, crf_vd_short.hpp; the state scores are
+// summed in CSR order on both sides, so they are the same numbers), so it is within t ulp(M) of its exact sum, and the
+// computed delta_t[j] within t ulp(M) of the exact maximum -- CRFsuite's sequential delta as much as this one.  A candidate
+// delta_t[i] + trans[i][j] adds half an ulp.  So both sides decide alike wherever the two candidates (the two final
+// scores at a contig's end) lie more than (4 t + 4) ulp(M) apart -- vd_margin with r = t, the gene's position in its
+// contig; every other decision sends its contig to CRFsuite's own recursion (vd_exact_fix).
+__device__ __forceinline__ double v_margin(const SeqArgs &A, int c, int t) {
+    const int gs = A.contig_ptr[c], ge = A.contig_ptr[c + 1];
+    return vd_margin(double(t), vd_bound(A, double(A.csr_gene_ptr[ge] - A.csr_gene_ptr[gs]), double(ge - gs)) * kVdEps);
+}
 __global__ void __launch_bounds__(kT) v_fold(const SeqArgs A) {
     __shared__ VE lds[kT / 64];
     __shared__ LaneStage stg;
@@ -377,6 +390,16 @@ __global__ void __launch_bounds__(kT) v_fold(const SeqArgs A) {
     const VE excl = block_scan_exclusive<VOp, false>(P, lds, &total);
     A.vLane[blockIdx.x * kT + threadIdx.x] = excl;
     if (threadIdx.x == 0) A.vBlock[blockIdx.x] = total;
+    // the largest margin of any contig (v_margin) over the batch, for the coarse test of v_replay: a contig per lane, one
+    // atomic per wave (non-negative doubles: bit patterns order like values)
+    if (A.fix_flag && A.csr_gene_ptr) {
+        double mx = 0.0;
+        for (int c = blockIdx.x * kT + threadIdx.x; c < A.n_contigs; c += gridDim.x * kT)
+            if (A.contig_ptr[c + 1] > A.contig_ptr[c]) mx = fmax(mx, v_margin(A, c, A.contig_ptr[c + 1] - A.contig_ptr[c]));
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+        if ((threadIdx.x & 63) == 0 && mx > 0.0) atomicMax(A.vBound, static_cast<unsigned long long>(__double_as_longlong(mx)));
+    }
 }
 
 // replay with the exact entering delta; per gene the map label_{t+1} -> label_t (its own end label
@@ -391,6 +414,10 @@ __global__ void __launch_bounds__(kT) v_replay(const SeqArgs A) {
     double d0 = M.a00, d1 = M.a01;  // rows are identical once a contig has started (M.rs)
     uint32_t maps = 0;                                         // 2 bits per gene
     uint32_t lane_map = MapOp::identity();
+    // the coarse test: the largest margin of the batch's contigs (v_fold); genes that fail it are judged again below
+    const bool exact = A.v_exact && A.fix_flag && A.csr_gene_ptr;
+    const double coarse = exact ? __longlong_as_double(static_cast<long long>(A.vBound[0])) : -1.0;
+    double gap[kGPL];
 #pragma unroll
     for (int k = 0; k < kGPL; ++k) {
         if (k < L.cnt) {
@@ -407,10 +434,42 @@ __global__ void __launch_bounds__(kT) v_replay(const SeqArgs A) {
                 const uint32_t end = d0 < d1 ? 1u : 0u;  // first argmax
                 m = end | (end << 1);
                 A.contigTmp[L.g0 + k] = make_double2(fmax(d0, d1), 0.0);
+                gap[k] = fabs(d1 - d0);
             } else {
-                m = ((d0 + A.t00 < d1 + A.t10) ? 1u : 0u) | ((d0 + A.t01 < d1 + A.t11) ? 2u : 0u);
+                const double a0 = d0 + A.t00, b0 = d1 + A.t10, a1 = d0 + A.t01, b1 = d1 + A.t11;
+                m = (a0 < b0 ? 1u : 0u) | (a1 < b1 ? 2u : 0u);
+                gap[k] = fmin(fabs(b0 - a0), fabs(b1 - a1));
             }
             maps |= m << (2 * k);
+        }
+    }
+    if (exact) {
+        bool sensitive = false;
+#pragma unroll
+        for (int k = 0; k < kGPL; ++k) sensitive |= k < L.cnt && gap[k] <= coarse;
+        if (sensitive) {  // rare: the gene's own contig, position and margin (a binary search per gene)
+            bool inside = false;
+#pragma unroll
+            for (int k = 0; k < kGPL; ++k) {  // (unrolled: gap stays in registers)
+                if (!(k < L.cnt && gap[k] <= coarse)) continue;
+                const int g = L.g0 + k;
+                int lo = 0, hi = A.n_contigs - 1;  // largest c with contig_ptr[c] <= g: the contig that holds gene g
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (A.contig_ptr[mid] <= g) lo = mid; else hi = mid - 1;
+                }
+                // (the decision at gene t compares candidates built from delta_t: position t + 1 of the next gene's
+                // back-pointers, t at a contig's end)
+                if (gap[k] <= v_margin(A, lo, g - A.contig_ptr[lo] + 1)) {
+                    A.fix_flag[lo] = 1;
+                    inside = true;
+                }
+            }
+            // counted per lane, like the difference form's candidates and decisions inside the margin
+            if (A.vd_stats) {
+                atomicAdd(A.vd_stats + 0, 1u);
+                if (inside) atomicAdd(A.vd_stats + 1, 1u);
+            }
         }
     }
     // lane map: label entering from the right -> label of the lane's first gene
@@ -989,9 +1048,16 @@ hipError_t launch_seq_viterbi(const SeqArgs &a, const int32_t *d_contig_ptr, hip
     if (a.n_contigs <= 0) return hipSuccess;
     if (a.n_genes > 0) {
         const int nb = (a.n_genes + kBlockGenes - 1) / kBlockGenes;
-        hipLaunchKernelGGL(v_fold, dim3(nb), dim3(kT), 0, stream, a);
-        hipLaunchKernelGGL(v_replay, dim3(nb), dim3(kT), 0, stream, a);
-        hipLaunchKernelGGL(v_labels, dim3(nb), dim3(kT), 0, stream, a);
+        // without labels (the path scores only: plan_run_viterbi takes the labels from the difference form then) there is no
+        // margin test, and the bound stays zero for the decoder after it; with them, contigs that v_replay flagged (a
+        // decision inside the margin) are decoded again with CRFsuite's own recursion
+        const bool exact = a.y && a.v_exact && a.fix_flag && a.csr_gene_ptr;
+        SeqArgs b = a;
+        if (!exact) b.fix_flag = nullptr;
+        hipLaunchKernelGGL(v_fold, dim3(nb), dim3(kT), 0, stream, b);
+        hipLaunchKernelGGL(v_replay, dim3(nb), dim3(kT), 0, stream, b);
+        if (a.y) hipLaunchKernelGGL(v_labels, dim3(nb), dim3(kT), 0, stream, b);
+        if (exact) hipLaunchKernelGGL(vd_exact_fix, dim3(min(a.n_contigs, 1024)), dim3(kT), 0, stream, b);
     }
     if (a.score) hipLaunchKernelGGL(v_scores, grid_for(a.n_contigs, kT), dim3(kT), 0, stream, a, d_contig_ptr);
     return hipGetLastError();

@@ -184,3 +184,241 @@ def objective_tolerances(seq_ptr, item_ptr, attr_id, W, step, state_fid, trans_f
     tol_g = (2 * EPS * ((5 * W + 4 * M + np.log2(n + 1)) * details["expected"] + details["empirical"])
              + (n + W * nw) * float(np.finfo(np.float64).tiny))
     return tol_f, tol_g
+
+
+# ---------------------------------------------------------------- Viterbi: planted near-ties
+ULP_STEPS = (0, 1, -1, 2, -2)
+
+
+def _ulp_step(x, k):
+    """x moved by k units in the last place (k < 0: downwards)."""
+    for _ in range(abs(k)):
+        x = np.nextafter(x, np.inf if k > 0 else -np.inf)
+    return float(x)
+
+
+def _solve_sum(a, b, target):
+    """s with fl(fl(a + s) + b) == target (b = 0.0: fl(a + s) == target), or None: a correction by the residual, then a
+    walk of s by units in the last place (one step of s moves a + s by at most one of ITS units)."""
+    s = target - b - a
+    for _ in range(8):
+        got = (a + s) + b
+        if got == target:
+            return float(s)
+        s = s + (target - got)
+    for _ in range(256):
+        got = (a + s) + b
+        if got == target:
+            return float(s)
+        s = np.nextafter(s, np.inf if got < target else -np.inf)
+    return None
+
+
+def _delta_step(d, trans):
+    """[EXT] crf1dc_viterbi's maximum over predecessors, label by label (strict '<': the first arg max): (m, arg)."""
+    cand = d[:, None] + trans
+    arg = cand.argmax(axis=0)
+    return cand[arg, np.arange(len(d))], arg
+
+
+def viterbi_tie_positions(T, start, boundaries=(8, 64, 2048), phase=0):
+    """Decision genes (contig-relative) right after the boundaries the kernels compose across: the first gene of an 8-gene
+    lane, of a 64-gene chunk (contig-relative) and of a 2048-gene scan block (batch-relative), or the gene after it; in a
+    contig of more than 64 blocks also a block boundary more than 64 blocks in.  Planted decisions keep three genes apart."""
+    want = []
+    for k, B in enumerate(boundaries):
+        off = (phase + k) % 2
+        want.append(B + off)  # contig-relative (the chunks of the any-L kernels start at the contig's first gene)
+        g = ((start + 2 + B - 1) // B) * B + off  # batch-relative (lanes and blocks)
+        want.append(g - start)
+    if T > 65 * 2048:
+        g = ((start + 65 * 2048 + 2047) // 2048) * 2048 + phase % 2
+        want.append(g - start)
+    out = []
+    for t in sorted(set(want)):
+        if 2 <= t <= T - 3 and (not out or t - out[-1] >= 3):
+            out.append(t)
+    return out
+
+
+SEPARATION = 72  # genes a separated tie's two candidate paths run apart: more than a 64-gene chunk
+
+
+def plant_viterbi_ties(rng, lengths, L, trans, big=20.0, boundaries=(8, 64, 2048), separated=True):
+    """A batch of contigs (gene g carries attribute g alone; N(0, 1) weights) with planted near-ties of CRFsuite's delta
+    recursion ([EXT] crf1dc_viterbi; oracle_viterbi_seq), built from that recursion itself.
+
+    * End ties: at a contig's last gene the two best final scores delta[i1], delta[i2] (i1 < i2) lie k ulps apart,
+      k in ULP_STEPS (0: an exact tie, which the first arg max gives to i1).
+    * Interior ties: at a decision gene t (viterbi_tie_positions) the two best candidates delta_{t-1}[i] + trans[i][j]
+      for label j lie k ulps apart; gene t then favours j by `big`, so the planted back-pointer decides label t - 1.
+    * Separated ties (`separated`): interior ties at the genes t = 128 q (+1 for odd q) -- the first gene of a 64-gene
+      chunk whose entering vector is composed from the chunk products before it, of a 32-gene chunk and of an 8-gene lane
+      -- and, in contigs of more than 65 blocks, at a block boundary more than 64 blocks in.  For SEPARATION genes before
+      the tie the two candidate labels each stay their own best predecessor (every other label `big` below), so their
+      paths split before the chunk entry and an entering value off by some ulps moves one candidate and not the other.
+      Their `merge` is the batch index of the last gene the two paths share (contig start - 1: none).
+    Label pairs alternate between adjacent and (for L >= 3) non-adjacent ones; every other label is held `big` below at
+    the planted gene.  Returns (w, contig_ptr, gene_ptr, attr_id, cases); a case is a dict with `kind` ('end', 'interior'
+    or 'separated'), `contig`, `gene` (batch index of the gene whose label the decision sets), `pair` (i1, i2), `j`, `ulps`,
+    `winner`, `loser` and `planted` (the gene whose weight row was solved for)."""
+    trans = np.asarray(trans, dtype=np.float64)
+    lengths = [int(x) for x in lengths]
+    n = sum(lengths)
+    cptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    w = rng.normal(0.0, 1.0, size=(n, L))
+    pairs = [(0, 1)] if L == 2 else [(0, 1), (0, L - 1), (L // 2 - 1, L // 2), (1, L - 1)]
+    cases = []
+    cnt = n_end = 0
+
+    def solve(m, t, g, i1, i2, j, k):
+        """weights of gene g (max over predecessors m; t == 0: a contig's first gene) so that the candidates of i1 and
+        i2 for label j (j < 0: the final scores) lie k ulps apart, above every other label's"""
+        b1 = 0.0 if j < 0 else trans[i1, j]
+        b2 = 0.0 if j < 0 else trans[i2, j]
+        for attempt in range(400):
+            # (a wider draw as attempts fail: the parity of the grid two sums land on can rule out an exact tie; another
+            # binade of delta[i1] changes it)
+            s = rng.normal(0.0, 1.0 + attempt / 50.0, size=L)
+            s[[x for x in range(L) if x not in (i1, i2)]] = -big
+            d1 = (m[i1] + s[i1]) if t else s[i1]
+            target = _ulp_step(d1 + b1, k)
+            s2 = _solve_sum(m[i2] if t else 0.0, b2, target)
+            if s2 is None or abs(s2) >= big:
+                continue
+            s[i2] = s2
+            d = (m + s) if t else s.copy()
+            cand = d + (0.0 if j < 0 else trans[:, j])
+            assert cand[i2] == _ulp_step(cand[i1], k)
+            others = np.delete(cand, [i1, i2])
+            if others.size == 0 or others.max() < cand[i1] - 1.0:
+                w[g] = s
+                return
+        raise AssertionError("could not plant a tie")
+
+    # pairs that can keep paths of their own: both labels their own best predecessor while delta[a] - delta[b] lies in
+    # (trans[b][a] - trans[a][a], trans[b][b] - trans[a][b])
+    sep_pairs = [(a, b) for a in range(L) for b in range(a + 1, L)
+                 if trans[a, a] + trans[b, b] - trans[a, b] - trans[b, a] >= 0.25]
+    sep_pairs = sep_pairs[::max(1, len(sep_pairs) // 4)]
+    n_sep = 0
+    for c, T in enumerate(lengths):
+        if T == 0:
+            continue
+        start = int(cptr[c])
+        plan, stretch, sep_at = {}, {}, []
+        if separated and sep_pairs:
+            want = [128 * q + q % 2 for q in range(1, 13)]
+            if T > 65 * 2048:
+                want.append(((65 * 2048 + 2047) // 2048) * 2048 + c % 2)
+            for t in want:
+                if t > T - 3:
+                    continue
+                a, b = sep_pairs[n_sep % len(sep_pairs)]
+                j = (a, b, L - 1)[n_sep % 3]
+                k = ULP_STEPS[n_sep % len(ULP_STEPS)]
+                n_sep += 1
+                plan[t - 1] = (a, b, j, k)
+                for u in range(t - 1 - SEPARATION, t - 1):
+                    stretch[u] = (a, b)
+                sep_at.append((t - 1 - SEPARATION - 2, t + 2))
+                win = b if k > 0 else a
+                cases.append(dict(kind="separated", contig=c, gene=start + t - 1, pair=(a, b), j=j, ulps=k, winner=win,
+                                  loser=a + b - win, planted=start + t - 1))
+        inner = [t for t in viterbi_tie_positions(T, start, boundaries, phase=c)
+                 if not any(lo <= t - 2 and t - 1 <= hi or lo <= t <= hi for lo, hi in sep_at)]
+        for t in sorted(inner):
+            i1, i2 = pairs[cnt % len(pairs)]
+            j = (i1, i2, L - 1)[cnt % 3]
+            k = ULP_STEPS[cnt % len(ULP_STEPS)]
+            cnt += 1
+            plan[t - 1] = (i1, i2, j, k)
+            win = i2 if k > 0 else i1
+            cases.append(dict(kind="interior", contig=c, gene=start + t - 1, pair=(i1, i2), j=j, ulps=k, winner=win,
+                              loser=i1 + i2 - win, planted=start + t - 1))
+        i1, i2 = pairs[n_end % len(pairs)]
+        k = ULP_STEPS[n_end % len(ULP_STEPS)]
+        n_end += 1
+        win = i2 if k > 0 else i1
+        cases.append(dict(kind="end", contig=c, gene=start + T - 1, pair=(i1, i2), j=-1, ulps=k, winner=win,
+                          loser=i1 + i2 - win, planted=start + T - 1))
+        d = np.zeros(L)
+        m = np.zeros(L)
+        back = np.zeros((T, L), dtype=np.int64)
+        for t in range(T):
+            g = start + t
+            if t:
+                m, back[t] = _delta_step(d, trans)
+            if t in stretch:  # keep a and b apart: delta[a] - delta[b] steered into the middle of its interval
+                a, b = stretch[t]
+                lo, hi = trans[b, a] - trans[a, a], trans[b, b] - trans[a, b]
+                s = np.full(L, -big)
+                s[a] = rng.normal(0.0, 0.5)
+                target = 0.5 * (lo + hi) + 0.3 * (hi - lo) * rng.uniform(-1.0, 1.0)
+                s[b] = m[a] + s[a] - target - m[b]
+                w[g] = s
+            elif t in plan:
+                i1, i2, j, k = plan[t]
+                solve(m, t, g, i1, i2, j, k)
+            elif t - 1 in plan:  # the decision gene: label j by a wide margin
+                j = plan[t - 1][2]
+                w[g] = -big
+                w[g, j] = big
+            elif t == T - 1:
+                ce = cases[-1]
+                solve(m, t, g, ce["pair"][0], ce["pair"][1], -1, ce["ulps"])
+            d = (m + w[g]) if t else w[g].copy()
+        for case in cases:
+            if case["contig"] == c and case["kind"] == "separated":  # where the two candidates' paths last meet
+                u, ya, yb = case["gene"] - start, case["pair"][0], case["pair"][1]
+                while u > 0 and ya != yb:
+                    ya, yb, u = back[u, ya], back[u, yb], u - 1
+                case["merge"] = start + u if ya == yb else start - 1
+    gptr = np.arange(n + 1, dtype=np.int32)
+    attr = np.arange(n, dtype=np.int32)
+    return w, cptr, gptr, attr, cases
+
+
+def viterbi_score_bounds(w, trans, contig_ptr, gene_ptr, attr_id):
+    """Per contig, a bound on |score - score'| between two fp64 evaluations of the best path score, and between either and
+    the exact sum of a best path: S = sum_t max_y |s_t[y]| + (T - 1) max |trans| bounds every partial sum of every path, a
+    path of T genes is 2 T - 1 additions of error <= ulp(S) / 2 each in whatever grouping, and the maximum over paths
+    adds none; the path the labels name may itself be one a rounding away from the best.  Hence 4 (T + 1) ulp(S)."""
+    from oracle import crf_oracle as orc
+
+    st = orc.state_scores(w, gene_ptr, attr_id)
+    cptr = np.asarray(contig_ptr)
+    T = np.diff(cptr).astype(np.float64)
+    smax = np.abs(st).max(axis=1) if len(st) else np.zeros(0)
+    cs = np.concatenate([[0.0], np.cumsum(smax)])
+    S = cs[cptr[1:]] - cs[cptr[:-1]] + np.maximum(T - 1, 0) * float(np.abs(trans).max())
+    return 4.0 * (T + 1) * np.spacing(np.maximum(S, 1.0)), st
+
+
+def exact_path_scores(state, trans, contig_ptr, labels):
+    """math.fsum of the state and transition terms of each contig's path `labels` (correctly rounded)."""
+    import math
+
+    labels = np.asarray(labels).astype(np.int64)
+    out = []
+    for c in range(len(contig_ptr) - 1):
+        g0, g1 = int(contig_ptr[c]), int(contig_ptr[c + 1])
+        if g1 <= g0:
+            out.append(0.0)
+            continue
+        y = labels[g0:g1]
+        terms = state[np.arange(g0, g1), y].tolist() + trans[y[:-1], y[1:]].tolist()
+        out.append(math.fsum(terms))
+    return np.array(out)
+
+
+def check_viterbi_scores(sc, esc, w, trans, contig_ptr, gene_ptr, attr_id, labels, what=""):
+    """Each contig's score within its own bound (viterbi_score_bounds) of the oracle's, and of the exact sum of the path
+    the call returned."""
+    bound, st = viterbi_score_bounds(w, trans, contig_ptr, gene_ptr, attr_id)
+    sc, esc = np.asarray(sc, dtype=np.float64), np.asarray(esc, dtype=np.float64)
+    ex = exact_path_scores(st, np.asarray(trans, dtype=np.float64), contig_ptr, labels)
+    bad = np.nonzero(~(np.abs(sc - esc) <= bound))[0]
+    assert bad.size == 0, f"{what}: contig {bad[:5]} score {sc[bad[:5]]} vs oracle {esc[bad[:5]]} (bound {bound[bad[:5]]})"
+    bad = np.nonzero(~(np.abs(sc - ex) <= bound))[0]
+    assert bad.size == 0, f"{what}: contig {bad[:5]} score {sc[bad[:5]]} vs its path's exact sum {ex[bad[:5]]}"

@@ -6,7 +6,7 @@ enumeration of label paths.  Tolerance: 1e-12 on marginals (north star: 1e-6), l
 import numpy as np
 import pytest
 
-from tests.helpers import golden_csr, synth_contigs, synth_model
+from tests.helpers import check_viterbi_scores, golden_csr, synth_contigs, synth_model
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +68,7 @@ def test_viterbi_any_label_count(nat, L):
     ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
     assert np.array_equal(y.astype(np.int32), ey)
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)  # (per contig: tests/helpers.py)
 
 
 @pytest.mark.parametrize("L", [3, 8, 16])
@@ -93,6 +94,7 @@ def test_empty_contigs_any_label_count(nat, L):
     ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
     assert np.array_equal(y.astype(np.int32), ey)
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)  # (per contig: tests/helpers.py)
     assert all(sc[c] == 0.0 for c in (0, 2, 3, 6, 8))
 
 
@@ -229,6 +231,7 @@ def test_contig_sequential_kernels(nat, L, monkeypatch):
     ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
     assert np.array_equal(y.astype(np.int32), ey)
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)  # (per contig: tests/helpers.py)
 
 
 @pytest.mark.parametrize("L", [9, 13, 16, 17, 24, 32])
@@ -247,6 +250,7 @@ def test_viterbi_wave_per_contig(nat, L, mode, monkeypatch):
     ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
     assert np.array_equal(y.astype(np.int32), ey)
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)  # (per contig: tests/helpers.py)
     # ties: small integer weights (every sum exact), many equal path scores
     rng = np.random.default_rng(800 + L)
     wi = rng.integers(-2, 3, size=(40, L)).astype(np.float64)
@@ -300,6 +304,7 @@ def test_viterbi_wave_is_chosen_for_batches_of_many_contigs(nat, monkeypatch):
         ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
         assert np.array_equal(y.astype(np.int32), ey)
         assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+        check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)
 
 
 def test_three_labels_against_path_enumeration(nat):
@@ -386,6 +391,7 @@ def test_chunked_path_equals_oracle(nat, L, monkeypatch):
     ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
     assert np.array_equal(y.astype(np.int32), ey)
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)  # (per contig: tests/helpers.py)
 
 
 @pytest.mark.parametrize("L", [3, 5])
@@ -448,3 +454,4 @@ def test_viterbi_split_wave_contig_next_to_a_chunked_one(nat, L, monkeypatch):
             ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
             assert np.array_equal(y.astype(np.int32), ey)
             assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+            check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)

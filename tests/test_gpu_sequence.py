@@ -3,7 +3,7 @@ Viterbi decoding vs the CPU oracle ([EXT] CRFsuite semantics)."""
 import numpy as np
 import pytest
 
-from tests.helpers import golden_csr, synth_contigs, synth_model
+from tests.helpers import check_viterbi_scores, golden_csr, synth_contigs, synth_model
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +61,7 @@ def test_viterbi_random(real, oracle_model):
     ey, esc = orc.viterbi(oracle_model["state"], oracle_model["trans"], cptr, gptr, attr)
     assert np.array_equal(y, ey.astype(np.int8))
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, oracle_model["state"], oracle_model["trans"], cptr, gptr, attr, y)  # (per contig)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])
@@ -116,6 +117,7 @@ def test_viterbi_very_long_contigs_walk_back_many_workgroups(nat, real, oracle_m
     ey, esc = orc.viterbi(w, trans, cptr, gptr, attr)
     assert np.array_equal(y, ey.astype(np.int8))
     assert np.abs(sc - esc).max() <= 1e-9 * max(1.0, np.abs(esc).max())
+    check_viterbi_scores(sc, esc, w, trans, cptr, gptr, attr, y)  # (per contig: the 3-gene contig is held to its own bound)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])
