@@ -5,11 +5,7 @@
 // the cluster's domains named all_possible[i], the row divided by `row.sum() or 1`.
 //
 // The only arithmetic is numpy.sum, so bit-identical output means reproducing numpy's pairwise
-// summation ([EXT] numpy/_core/src/umath/loops_utils.h.src `pairwise_sum`): fewer than 8 terms are
-// added left to right; up to 128 terms go through 8 interleaved accumulators combined as
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus a left-to-right tail; longer ranges split at
-// n/2 rounded down to a multiple of 8, left + right; the reduction starts from 0.0 and takes the
-// array in chunks of 8192 elements (numpy's reduction buffer), adding each chunk's pairwise sum.
+// summation order (crf_npsum.hpp).
 //
 // One workgroup per cluster.  Domain rows of a cluster are contiguous (genes of a cluster are
 // consecutive, domain rows are stored per gene), so the cluster is a row range [r0, r1):
@@ -19,88 +15,13 @@
 //      order; the first row of every column sums its terms;
 //   3. the row total: leaves of the pairwise tree in parallel (one lane each), combined by lane 0.
 #include "crf_device.hpp"
+#include "crf_npsum.hpp"
 
 namespace gecco {
 namespace {
 
 constexpr int kCT = 256;
 constexpr int kMaxLeaves = 2048;  // leaves of the row-total tree held in LDS (n_cols <= ~130 k)
-
-// numpy's pairwise_sum for n <= 128 contiguous terms
-__device__ __forceinline__ double np_leaf(const double *a, int n) {
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; ++i) res += a[i];
-        return res;
-    }
-    double r[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) r[k] = a[k];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) r[k] += a[i + k];
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
-
-// Walks numpy's recursion tree over [0, n) without recursion; leaf(off, len, index) supplies the
-// value of the index-th leaf in left-to-right order.  Returns the root value.
-template <class Leaf>
-__device__ double np_pairwise_tree(int n, Leaf leaf) {
-    int off_s[64], len_s[64];  // len < 0: "add the two topmost values"
-    double val[40];
-    int top = 0, vp = 0, idx = 0;
-    off_s[0] = 0;
-    len_s[0] = n;
-    top = 1;
-    while (top > 0) {
-        --top;
-        const int off = off_s[top], len = len_s[top];
-        if (len < 0) {
-            const double b = val[--vp], a = val[--vp];
-            val[vp++] = a + b;
-        } else if (len <= 128) {
-            val[vp++] = leaf(off, len, idx++);
-        } else {
-            int n2 = len / 2;
-            n2 -= n2 % 8;
-            off_s[top] = 0;
-            len_s[top++] = -1;
-            off_s[top] = off + n2;
-            len_s[top++] = len - n2;
-            off_s[top] = off;
-            len_s[top++] = n2;
-        }
-    }
-    return val[0];
-}
-
-constexpr int kNpChunk = 8192;  // numpy.getbufsize()
-
-// numpy.sum of n contiguous doubles; leaf(off, len, index) as above, indices running over all chunks
-template <class Leaf>
-__device__ double np_sum_with(int n, Leaf leaf) {
-    double res = 0.0;
-    int base = 0;
-    for (int lo = 0; lo < n; lo += kNpChunk) {
-        const int len = n - lo < kNpChunk ? n - lo : kNpChunk;
-        int used = 0;
-        res += np_pairwise_tree(len, [&](int off, int l, int idx) {
-            used = idx + 1;
-            return leaf(lo + off, l, base + idx);
-        });
-        base += used;
-    }
-    return res;
-}
-
-__device__ double np_sum(const double *a, int n) {
-    if (n <= 128) return 0.0 + np_leaf(a, n);
-    return np_sum_with(n, [&](int off, int len, int) { return np_leaf(a + off, len); });
-}
 
 __global__ void __launch_bounds__(kCT) composition_kernel(const int32_t *__restrict__ seg, const int32_t *__restrict__ dom_ptr,
                                                           const int32_t *__restrict__ dom_col,

@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "crf_device.hpp"
+#include "crf_npsum.hpp"
 #include "crf_scan.hpp"
 
 namespace gecco {
@@ -215,6 +216,8 @@ __device__ __forceinline__ int upper_bound_i32(const int32_t *__restrict__ a, in
     return lo;
 }
 
+// kAntismash: the criterion, a template argument so that the "gecco" kernels carry none of the antismash walk's registers
+template <bool kAntismash>
 __device__ __forceinline__ void seg_validate_body(const SegArgs &A) {
     const int n_raw = *A.n_raw;
     const int ntile = (n_raw + kT - 1) / kT;
@@ -246,7 +249,7 @@ __device__ __forceinline__ void seg_validate_body(const SegArgs &A) {
                 }
             }
             len = b - a;
-            if (A.criterion == 0) {
+            if (!kAntismash) {
                 const int pa = A.pre[a], ann = A.pre[b] - pa;
                 int edge = 0;
                 if (A.edge > 0) {
@@ -258,13 +261,11 @@ __device__ __forceinline__ void seg_validate_body(const SegArgs &A) {
                 kept = ann >= A.n_cds && len - edge >= A.n_cds;
             } else {
                 // "antismash" (refine.py:157-163): mean probability, distinct marker domains, number of genes.  This
-                // one does walk the run (one lane per run; runs are short where this criterion is used).  The mean
-                // is the plain left-to-right sum over the count: numpy.mean's own last bit depends on the SIMD
-                // width numpy was dispatched to, so the reference does not pin it.
-                double sum = 0.0;
+                // one does walk the run (one lane per run; runs are short where this criterion is used).  The mean is
+                // numpy.mean's: the sum in numpy's order (crf_npsum.hpp), then one division by the count.
+                const double sum = np_sum(A.p + a, len);
                 uint64_t seen[kSegMaxMarkers / 64] = {};
                 for (int g = a; g < b; ++g) {
-                    sum += A.p[g];
                     for (int k = A.bio_ptr[g]; k < A.bio_ptr[g + 1]; ++k) {
                         const uint32_t id = uint32_t(A.bio_id[k]);
                         if (id < uint32_t(kSegMaxMarkers)) seen[id >> 6] |= 1ull << (id & 63u);
@@ -289,7 +290,8 @@ __device__ __forceinline__ void seg_validate_body(const SegArgs &A) {
         __syncthreads();
     }
 }
-__global__ void __launch_bounds__(kT) seg_validate(const SegArgs A) { seg_validate_body(A); }
+template <bool kAntismash>
+__global__ void __launch_bounds__(kT) seg_validate(const SegArgs A) { seg_validate_body<kAntismash>(A); }
 
 // Ordered compaction of the kept rows.  A workgroup takes tiles t, t + G, ...; (rows, genes) kept in the tiles before
 // a tile are summed by every wave for itself (64 tiles per step), carried from the workgroup's previous tile.  Kept rows go
@@ -360,6 +362,7 @@ __global__ void __launch_bounds__(kT) seg_compact(const SegArgs A) { seg_compact
 // "the workgroups before this one" are none, every reduction over workgroups is empty, and what a stage reads of the stage
 // before it was written by lanes of the same workgroup (a barrier and a workgroup-scope fence in between).  The one place
 // where a lane leaves a stage early (seg_replay_body) has no barrier behind it inside the stage.
+template <bool kAntismash>
 __global__ void __launch_bounds__(kT) seg_small(const SegArgs A, const int build_flags) {
     if (build_flags) {
         for (int w = threadIdx.x; w * 8 < A.n_genes + 8; w += kT)
@@ -373,7 +376,7 @@ __global__ void __launch_bounds__(kT) seg_small(const SegArgs A, const int build
     seg_replay_body(A);
     __threadfence_block();
     __syncthreads();
-    seg_validate_body(A);
+    seg_validate_body<kAntismash>(A);
     __threadfence_block();
     __syncthreads();
     seg_compact_body(A);
@@ -448,7 +451,8 @@ hipError_t launch_segment(const double *d_p, const uint8_t *d_ann, const uint8_t
     a.row_g0 = params.row_gene0;
     if (nb == 1) {
         a.flags = d_flags ? d_flags : own_flags;
-        hipLaunchKernelGGL(seg_small, dim3(1), dim3(kT), 0, stream, a, d_flags ? 0 : 1);
+        if (a.criterion) hipLaunchKernelGGL(seg_small<true>, dim3(1), dim3(kT), 0, stream, a, d_flags ? 0 : 1);
+        else hipLaunchKernelGGL(seg_small<false>, dim3(1), dim3(kT), 0, stream, a, d_flags ? 0 : 1);
         return hipGetLastError();
     }
     if (!d_flags) {
@@ -459,7 +463,8 @@ hipError_t launch_segment(const double *d_p, const uint8_t *d_ann, const uint8_t
     const int tiles_cap = int(std::min<size_t>(cap / kT + 1, 2048));
     hipLaunchKernelGGL(seg_fold, dim3(nb), dim3(kT), 0, stream, a);
     hipLaunchKernelGGL(seg_replay, dim3(nb), dim3(kT), 0, stream, a);
-    hipLaunchKernelGGL(seg_validate, dim3(tiles_cap), dim3(kT), 0, stream, a);
+    if (a.criterion) hipLaunchKernelGGL(seg_validate<true>, dim3(tiles_cap), dim3(kT), 0, stream, a);
+    else hipLaunchKernelGGL(seg_validate<false>, dim3(tiles_cap), dim3(kT), 0, stream, a);
     hipLaunchKernelGGL(seg_compact, dim3(tiles_cap), dim3(kT), 0, stream, a);
     return hipGetLastError();
 }

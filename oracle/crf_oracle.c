@@ -445,10 +445,44 @@ ORACLE_API int oracle_segment(const double *p, const uint8_t *annotated,
     return kept;
 }
 
+/* numpy's pairwise_sum ([EXT] numpy/_core/src/umath/loops_utils.h.src): fewer than 8 terms left to right; up to 128
+ * through 8 interleaved accumulators, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then a left-to-right tail; longer ranges
+ * split at n/2 rounded down to a multiple of 8. */
+static double np_pairwise_sum(const double *a, int n)
+{
+    if (n < 8) {
+        double res = 0.0;
+        for (int i = 0; i < n; ++i) res += a[i];
+        return res;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int k = 0; k < 8; ++k) r[k] = a[k];
+        int i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int k = 0; k < 8; ++k) r[k] += a[i + k];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) res += a[i];
+        return res;
+    }
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
+}
+
+/* numpy.sum of a contiguous float64 array: from 0.0, the pairwise sums of 8192-element chunks (numpy's reduction
+ * buffer) added in turn, whatever SIMD width numpy was built for */
+static double np_sum(const double *a, int n)
+{
+    double res = 0.0;
+    for (int lo = 0; lo < n; lo += 8192) res += np_pairwise_sum(a + lo, n - lo < 8192 ? n - lo : 8192);
+    return res;
+}
+
 /* The same walk with the "antismash" validation of refine.py:157-163: mean probability of the (trimmed) run's genes
  * >= average_threshold, distinct marker domains (the reference's BIO_PFAMS) among ALL domains of those genes >=
  * n_biopfams, number of genes >= n_cds.  marker_ptr / marker_id: CSR over genes of marker indices (< 256).  The mean
- * is the left-to-right sum over the count (numpy.mean's last bit depends on numpy's SIMD dispatch: not pinned). */
+ * is numpy.mean's: the sum in numpy's order (np_sum), then one division by the count. */
 ORACLE_API int oracle_segment_antismash(const double *p, const uint8_t *annotated, const int32_t *contig_ptr, int n_contigs,
                                         const int32_t *marker_ptr, const int32_t *marker_id, double threshold, int n_cds,
                                         int n_biopfams, double average_threshold, int trim, int carry_state,
@@ -479,12 +513,11 @@ ORACLE_API int oracle_segment_antismash(const double *p, const uint8_t *annotate
                     while (a < b && !annotated[a]) ++a;
                     while (b > a && !annotated[b - 1]) --b;
                 }
-                double sum = 0.0;
+                const double sum = np_sum(p + a, b - a);
                 uint8_t seen[256];
                 memset(seen, 0, sizeof seen);
                 int markers = 0;
                 for (int k = a; k < b; ++k) {
-                    sum += p[k];
                     for (int q = marker_ptr[k]; q < marker_ptr[k + 1]; ++q) {
                         int id = marker_id[q];
                         if (id >= 0 && id < 256 && !seen[id]) {

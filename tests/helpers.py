@@ -422,3 +422,294 @@ def check_viterbi_scores(sc, esc, w, trans, contig_ptr, gene_ptr, attr_id, label
     assert bad.size == 0, f"{what}: contig {bad[:5]} score {sc[bad[:5]]} vs oracle {esc[bad[:5]]} (bound {bound[bad[:5]]})"
     bad = np.nonzero(~(np.abs(sc - ex) <= bound))[0]
     assert bad.size == 0, f"{what}: contig {bad[:5]} score {sc[bad[:5]]} vs its path's exact sum {ex[bad[:5]]}"
+
+
+# ---------------------------------------------------------------- row R: planted refiner boundaries
+class RefinerReference:
+    """A literal statement of the reference's GeneGrouper and ClusterRefiner (gecco/refine.py:51-64, 118-200) over the
+    packed arrays of a batch: NaN stands for a gene without probability, contig c is the reference's sequence c, genes are
+    already in (start, end) order.  Rows (contig, number, first, last + 1) as `gecco_crf_segment` returns them; a run
+    trimmed to nothing is reported at its end.  The antismash mean is `float(numpy.mean(list_of_floats))`.  The runs and the
+    per-run quantities are kept per (threshold, carry_state, trim), so that many parameter sets over one batch stay cheap."""
+
+    def __init__(self, p, annotated, contig_ptr, marker_ptr=None, marker_id=None):
+        self.p = [float(x) for x in np.asarray(p, dtype=np.float64)]
+        self.ann = [bool(x) for x in np.asarray(annotated)]
+        self.cptr = [int(x) for x in contig_ptr]
+        self.mptr = None if marker_ptr is None else [int(x) for x in marker_ptr]
+        self.mid = None if marker_id is None else [int(x) for x in marker_id]
+        self._runs, self._stats = {}, {}
+
+    def runs(self, threshold, carry_state=False):
+        """(contig, number, start, end) of every "in" group: one grouper per call (carry_state) or per contig (the CLI)"""
+        import itertools
+
+        key = (threshold, carry_state)
+        if key not in self._runs:
+            out, in_cluster = [], False
+            for c in range(len(self.cptr) - 1):
+                g0, g1 = self.cptr[c], self.cptr[c + 1]
+                if not carry_state:
+                    in_cluster = False
+
+                def grouper(g):
+                    nonlocal in_cluster
+                    if self.p[g] == self.p[g]:  # (`average_probability is not None`)
+                        in_cluster = self.p[g] > threshold
+                    return in_cluster
+
+                number = 0
+                for flag, genes in itertools.groupby(range(g0, g1), key=grouper):
+                    if flag:
+                        genes = list(genes)
+                        number += 1
+                        out.append((c, number, genes[0], genes[-1] + 1))
+            self._runs[key] = out
+        return self._runs[key]
+
+    def stats(self, threshold, carry_state, trim):
+        """per run: (contig, number, a, b) after trimming and what the criteria look at"""
+        import warnings
+
+        key = (threshold, carry_state, trim)
+        if key not in self._stats:
+            out = []
+            for c, number, s, e in self.runs(threshold, carry_state):
+                a, b = s, e
+                if trim:
+                    while a < b and not self.ann[a]:
+                        a += 1
+                    while b > a and not self.ann[b - 1]:
+                        b -= 1
+                st = {"row": [c, number, a, b], "annotated": sum(self.ann[a:b])}
+                if self.mptr is not None:
+                    st["markers"] = len({self.mid[k] for g in range(a, b) for k in range(self.mptr[g], self.mptr[g + 1])})
+                    with warnings.catch_warnings():
+                        warnings.simplefilter("ignore")  # (numpy's "mean of empty slice": NaN, as in the reference)
+                        st["mean"] = float(np.mean([self.p[g] for g in range(a, b)]))
+                out.append(st)
+            self._stats[key] = out
+        return self._stats[key]
+
+    def edge_genes(self, c, edge_distance):
+        ids = [g for g in range(self.cptr[c], self.cptr[c + 1]) if self.ann[g]]
+        return set(ids[:edge_distance]).union(ids[-edge_distance:]) if edge_distance > 0 else set()
+
+    def __call__(self, threshold=0.8, criterion="gecco", n_cds=5, n_biopfams=5, average_threshold=0.6, edge_distance=0, trim=True,
+                 carry_state=False):
+        rows = []
+        for st in self.stats(threshold, carry_state, trim):
+            c, _, a, b = st["row"]
+            if criterion == "gecco":
+                inner = len(set(range(a, b)).difference(self.edge_genes(c, edge_distance)))
+                ok = st["annotated"] >= n_cds and inner >= n_cds
+            else:
+                ok = st["mean"] >= average_threshold and st["markers"] >= n_biopfams and b - a >= n_cds
+            if ok:
+                rows.append(list(st["row"]))
+        return rows
+
+
+ANTISMASH_LENGTHS = (1, 7, 8, 9, 16, 127, 128, 129, 136, 1000, 8191, 8192, 8193, 20000)
+
+
+def _markers_for(rng, ann, pool, rate=0.7):
+    """CSR of marker ids per gene, on annotated genes only (a marker is a domain): ids repeated within a gene and across
+    genes"""
+    ptr, ids = [0], []
+    for a in ann:
+        k = int(rng.integers(1, 4)) if a and rng.random() < rate else 0
+        m = [int(x) for x in rng.choice(pool, size=k)]
+        if m and rng.random() < 0.2:
+            m.append(m[0])  # the same marker twice in one gene
+        ids.extend(m)
+        ptr.append(len(ids))
+    return ptr, ids
+
+
+def _batch(name, p, ann, cptr, mptr, mid, params):
+    return {"name": name, "p": np.asarray(p, dtype=np.float64), "ann": np.asarray(ann, dtype=np.uint8),
+            "cptr": np.asarray(cptr, dtype=np.int32), "mptr": np.asarray(mptr, dtype=np.int32),
+            "mid": np.asarray(mid, dtype=np.int32), "params": params}
+
+
+def plant_antismash_params(ref, threshold, trims=(True, False), carry_state=False, runs=None):
+    """Parameter sets that put every run of the batch (or the runs whose index is in `runs`) on the antismash boundary:
+    average_threshold = numpy.mean of the trimmed run and 1, 2 ulps either side (other criteria met exactly); the distinct
+    marker count at n_biopfams and n_biopfams - 1; the gene count at n_cds and n_cds - 1.  Each carries `plant` = (run index,
+    what was planted, ulps) for the messages."""
+    out = []
+    for trim in trims:
+        for i, st in enumerate(ref.stats(threshold, carry_state, trim)):
+            if runs is not None and i not in runs:
+                continue
+            c, _, a, b = st["row"]
+            base = dict(threshold=threshold, criterion="antismash", trim=trim, carry_state=carry_state, edge_distance=0)
+            if b == a:  # trimmed to nothing: numpy.mean([]) is NaN, which no threshold passes
+                out.append(dict(base, n_cds=0, n_biopfams=0, average_threshold=0.0, plant=(i, "empty", 0)))
+                continue
+            m, k_bio, n = st["mean"], st["markers"], b - a
+            for k in ULP_STEPS:
+                out.append(dict(base, n_cds=n, n_biopfams=k_bio, average_threshold=_ulp_step(m, k), plant=(i, "mean", k)))
+            for d in (0, 1):
+                out.append(dict(base, n_cds=n, n_biopfams=k_bio + d, average_threshold=m, plant=(i, "markers", d)))
+                out.append(dict(base, n_cds=n + d, n_biopfams=k_bio, average_threshold=m, plant=(i, "genes", d)))
+    return out
+
+
+def _grouper_batch(rng):
+    """Every grouper decision on a boundary: probabilities drawn from {x, x +- 1 ulp, x +- 2 ulps} and thresholds from the
+    same set; 0.0 / -0.0 / the smallest subnormal against threshold 0.0, 1.0 against 1.0; NaN runs at contig starts,
+    NaN-only contigs, empty contigs between others."""
+    x = float(rng.uniform(0.3, 0.7))
+    near = [_ulp_step(x, k) for k in ULP_STEPS]
+    zero, one = [0.0, -0.0, 5e-324], [1.0, float(np.nextafter(1.0, 0.0))]
+    p, cptr = [], [0]
+    for c in range(36):
+        kind = c % 9
+        n = 0 if kind == 4 else int(rng.integers(1, 30))
+        pool = zero if kind == 6 else one if kind == 7 else near
+        q = [float(rng.choice(pool)) for _ in range(n)]
+        for g in range(n):
+            if rng.random() < 0.12 or kind == 8:  # kind 8: a contig without a single probability
+                q[g] = float("nan")
+        if kind in (1, 3, 5) and n:  # a run of NaN at the contig's start: it inherits the state (carry_state) or "out"
+            k = int(rng.integers(1, min(n, 4) + 1))
+            q[:k] = [float("nan")] * k
+        p.extend(q)
+        cptr.append(len(p))
+    ann = (rng.random(len(p)) < 0.7).astype(np.uint8)
+    params = []
+    for thr in near + [0.0, 1.0]:
+        for carry in (False, True):
+            for trim in (True, False):
+                for n_cds in (0, 1, 2):
+                    params.append(dict(threshold=thr, criterion="gecco", n_cds=n_cds, edge_distance=0, trim=trim, carry_state=carry))
+    return _batch("grouper", p, ann, cptr, [0] * (len(p) + 1), [], params)
+
+
+def _gecco_batch(rng):
+    """Contigs of one or two runs between low genes; n_cds at the annotated count and at the non-edge count of every run,
+    and one either side, for edge_distance 0, 1, n_ann / 2, n_ann / 2 + 1, n_ann, n_ann + 1 and 10**6 of every contig (edge
+    sets that overlap included); a run of unannotated genes that trims to nothing."""
+    p, ann, cptr = [], [], [0]
+    for c in range(7):
+        segs = [("out", int(rng.integers(0, 4))), ("in", int(rng.integers(1, 12))), ("out", int(rng.integers(1, 4)))]
+        if c % 2:
+            segs += [("in", int(rng.integers(1, 9))), ("out", int(rng.integers(0, 3)))]
+        for kind, n in segs:
+            for _ in range(n):
+                p.append(float(rng.uniform(0.85, 1.0)) if kind == "in" else float(rng.uniform(0.0, 0.5)))
+                ann.append(0 if (c == 3 and kind == "in") else int(rng.random() < 0.65))
+        cptr.append(len(p))
+    ref = RefinerReference(p, ann, cptr)
+    params = []
+    n_anns = {sum(ann[cptr[c]:cptr[c + 1]]) for c in range(len(cptr) - 1)}
+    edges = sorted({0, 1, 10 ** 6} | {e for n in n_anns for e in (n // 2, n // 2 + 1, n, n + 1)})
+    for trim in (True, False):
+        for edge in edges:
+            counts = set()
+            for st in ref.stats(0.8, False, trim):
+                c, _, a, b = st["row"]
+                inner = len(set(range(a, b)).difference(ref.edge_genes(c, edge)))
+                counts |= {st["annotated"] + d for d in (-1, 0, 1)} | {inner + d for d in (-1, 0, 1)}
+            for n_cds in sorted(k for k in counts if k >= 0):
+                params.append(dict(threshold=0.8, criterion="gecco", n_cds=n_cds, edge_distance=edge, trim=trim, carry_state=False))
+    return _batch("gecco", p, ann, cptr, [0] * (len(p) + 1), [], params)
+
+
+def _antismash_batch(rng, lengths):
+    """One contig per run length: low genes, a run of `length` genes above the threshold whose ends are unannotated now and
+    then (so trimming moves them), low genes; one more run of unannotated genes that trims to nothing."""
+    p, ann, cptr = [], [], [0]
+    for i, L in enumerate(list(lengths) + [5]):
+        lead, tail = int(rng.integers(0, 3)), int(rng.integers(1, 3))
+        p += [float(rng.uniform(0.0, 0.5)) for _ in range(lead)]
+        ann += [int(rng.random() < 0.5) for _ in range(lead)]
+        p += [float(x) for x in rng.uniform(0.5, 1.0, size=L)]
+        a = (rng.random(L) < 0.8).astype(int)
+        if i == len(lengths):
+            a[:] = 0
+        elif L > 2 and i % 2:
+            a[0] = a[-1] = 0
+        ann += [int(x) for x in a]
+        p += [float(rng.uniform(0.0, 0.5)) for _ in range(tail)]
+        ann += [int(rng.random() < 0.5) for _ in range(tail)]
+        cptr.append(len(p))
+    p = [max(x, float(np.nextafter(0.5, 1.0))) if x > 0.5 else x for x in p]
+    mptr, mid = _markers_for(rng, ann, np.arange(20))
+    ref = RefinerReference(p, ann, cptr, mptr, mid)
+    return _batch("antismash", p, ann, cptr, mptr, mid, plant_antismash_params(ref, 0.5))
+
+
+def _geometry_batch(rng, n):
+    """Run starts and ends, and trim points, on the boundaries of the 8-gene lanes and the 2048-gene workgroups; a contig
+    starting at gene 2048 (when the batch is longer); both criteria, the antismash means planted."""
+    marks = {8, 16, 64, 2040, 2047, 2048, 2049, 2056, 4096, 4104}
+    cuts = sorted(m for m in marks if 0 < m < n) + [n]
+    p, ann = np.empty(n), (rng.random(n) < 0.75).astype(np.uint8)
+    lo, inside = 0, False
+    for hi in cuts:
+        p[lo:hi] = rng.uniform(0.6, 1.0, size=hi - lo) if inside else rng.uniform(0.0, 0.4, size=hi - lo)
+        if inside and hi - lo > 9 and lo % 16 == 0:
+            ann[lo:lo + 8] = 0  # trimmed up to the next lane
+            ann[lo + 8] = 1
+        lo, inside = hi, not inside
+    cptr = sorted({0, n} | ({3, 2048} if n > 2048 else {3, 1000}))
+    mptr, mid = _markers_for(rng, ann, np.arange(40), rate=0.3)
+    ref = RefinerReference(p, ann, cptr, mptr, mid)
+    params = [dict(threshold=0.5, criterion="gecco", n_cds=k, edge_distance=e, trim=t, carry_state=carry)
+              for k in (1, 3, 8) for e in (0, 2) for t in (True, False) for carry in (False, True)]
+    params += plant_antismash_params(ref, 0.5)
+    return _batch(f"geometry{n}", p, ann, cptr, mptr, mid, params)
+
+
+def plant_refiner_boundaries(seed=0, lengths=ANTISMASH_LENGTHS, geometry=(2048, 2049, 6150)):
+    """Packed batches (p, annotated, contig_ptr, marker_ptr, marker_id) with parameter sets that put every refiner decision
+    of row R on its boundary or one or two ulps from it (`RefinerReference` decides them): the grouper's strict `>` and NaN
+    inheritance, the "gecco" counts against n_cds and edge_distance, the "antismash" mean, marker and gene counts, runs on
+    the kernel's lane and workgroup boundaries, batches of exactly one workgroup (2048 genes) and one gene more."""
+    rng = np.random.default_rng(seed)
+    out = [_grouper_batch(rng), _gecco_batch(rng), _antismash_batch(rng, lengths)]
+    out += [_geometry_batch(rng, n) for n in geometry]
+    return out
+
+
+def refiner_params(prm):
+    """the keyword arguments of RefinerReference / ClusterRefiner in a planted parameter set"""
+    return {k: v for k, v in prm.items() if k != "plant"}
+
+
+def genes_from_planted(batch, contigs=None):
+    """`gecco_amd.model` genes of a planted batch (contig c is sequence f"c{c:04d}", in order): an annotated gene carries its
+    markers as domains of sorted(BIO_PFAMS) (repeats kept) or one domain that is no marker; NaN: no probability.  Returns
+    {contig: [genes]} for the contigs asked for (all by default)."""
+    from gecco_amd.model import Domain, Gene, Protein, Source, Strand
+    from gecco_amd.refine import BIO_PFAMS
+
+    bio = sorted(BIO_PFAMS)
+    p, ann, cptr, mptr, mid = batch["p"], batch["ann"], batch["cptr"], batch["mptr"], batch["mid"]
+    out = {}
+    for c in range(len(cptr) - 1) if contigs is None else contigs:
+        src, genes = Source(f"c{c:04d}"), []
+        for g in range(int(cptr[c]), int(cptr[c + 1])):
+            prob = None if p[g] != p[g] else float(p[g])
+            names = [bio[int(k)] for k in mid[mptr[g]:mptr[g + 1]]] or (["PF99999"] if ann[g] else [])
+            doms = [Domain(nm, 1, 51, "Pfam", 1e-5, 1e-7, probability=prob) for nm in names]
+            genes.append(Gene(src, 10 * g, 10 * g + 9, Strand.Coding, Protein(f"g{g}", None, doms), _probability=prob))
+        out[c] = genes
+    return out
+
+
+def rows_from_clusters(clusters):
+    """(contig, number, first, last + 1) of `genes_from_planted` clusters; an empty cluster has no genes to place it by"""
+    rows = []
+    for cl in clusters:
+        seq, num = cl.id.rsplit("_cluster_", 1)
+        c = int(seq[1:])
+        if cl.genes:
+            a = int(cl.genes[0].protein.id[1:])
+            rows.append([c, int(num), a, a + len(cl.genes)])
+        else:
+            rows.append([c, int(num), None, None])
+    return rows

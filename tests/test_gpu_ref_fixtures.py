@@ -194,3 +194,25 @@ def test_predict_tables_equals_the_reference(crf_cases):
             worst = max(worst, float(np.nanmax(np.abs(gp - ep))))
         n += 1
     assert n >= 150 and worst <= 1e-12, (n, worst)
+
+
+def test_device_refiner_ties_equal_the_reference():
+    """csrc/crf_segment.hip on tests/golden/ref_refiner_ties.json.gz: the planted boundary batches (grouper thresholds on and
+    one or two ulps off a gene's p, "gecco" counts at n_cds and edge_distance, "antismash" means on the threshold, runs on
+    lane and workgroup boundaries) decided as the reference's own ClusterRefiner decided them."""
+    from gecco_amd import _native as nat
+    from gecco_amd.refine import BIO_PFAMS
+
+    markers = sorted(BIO_PFAMS)
+    n = 0
+    for case in load_ref("ref_refiner_ties"):
+        ids, cids, p, ann, cptr, mptr, mid = pack_refiner_case(case, markers)
+        for dec in case["decisions"]:
+            prm = dec["params"]
+            seg = nat.segment(p, ann, cptr, prm["threshold"], prm["n_cds"], prm["edge_distance"], prm["trim"],
+                              carry_state=prm["carry_state"], criterion=prm["criterion"], n_biopfams=prm.get("n_biopfams", 5),
+                              average_threshold=prm.get("average_threshold", 0.6), marker_ptr=mptr, marker_id=mid)
+            got = [[f"{cids[c]}_cluster_{k}", ids[a:b]] for c, k, a, b in seg.tolist()]
+            assert got == dec["clusters"], (case["name"], prm)
+            n += len(got)
+    assert n > 1000

@@ -101,7 +101,7 @@ def test_segment_antismash_matches_oracle(n_cds, n_bio, avg, trim):
 
 def test_segment_antismash_equals_the_object_refiner():
     """Packed arrays against gecco_amd.refine.ClusterRefiner(criterion="antismash") on objects (the mirror of
-    refine.py:118-200): the same clusters when no mean lies within rounding of the threshold."""
+    refine.py:118-200): the same clusters (tests/test_gpu_refiner_edges.py plants means on the threshold)."""
     from gecco_amd import _native as nat
     from gecco_amd import refine
     from gecco_amd.model import Cluster, Domain, Gene, Protein, Source, Strand

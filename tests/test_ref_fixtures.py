@@ -126,3 +126,39 @@ def test_oracle_composition_equals_the_reference():
             got = oc.domain_composition(names, weights, case["all_possible"], normalize=normalize)
             assert np.asarray(got, dtype=np.float64).tobytes() == np.asarray(exp, dtype=np.float64).tobytes()
 
+
+
+def test_refiner_ties_equal_the_reference():
+    """tests/golden/ref_refiner_ties.json.gz: the planted boundary batches of tests/helpers.py (every grouper, "gecco" and
+    "antismash" decision on its boundary or one or two ulps from it) as the reference's own ClusterRefiner decided them.
+    The object refiner and the oracle's packed-array restatement decide every one of them alike."""
+    import warnings
+
+    from gecco_amd.model import Cluster
+    from gecco_amd.refine import BIO_PFAMS, ClusterRefiner
+    from oracle import crf_oracle as orc
+
+    markers = sorted(BIO_PFAMS)
+    n = kinds = 0
+    for case in load_ref("ref_refiner_ties"):
+        genes = genes_from_refiner_case(case)
+        ids, cids, p, ann, cptr, mptr, mid = pack_refiner_case(case, markers)
+        by_contig = [list(g) for _, g in itertools.groupby(genes, key=operator.attrgetter("source.id"))]
+        for dec in case["decisions"]:
+            prm = dict(dec["params"])
+            carry = prm.pop("carry_state")
+            refiner = ClusterRefiner(cluster_type=Cluster, **prm)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                calls = [genes] if carry else by_contig
+                got = [[c.id, [g.protein.id for g in c.genes]] for call in calls for c in refiner.iter_clusters(call)]
+            assert got == dec["clusters"], (case["name"], dec["params"])
+            if prm["criterion"] == "gecco":
+                seg = orc.segment(p, ann, cptr, prm["threshold"], prm["n_cds"], prm["edge_distance"], prm["trim"], carry_state=carry)
+            else:
+                seg = orc.segment_antismash(p, ann, cptr, mptr, mid, prm["threshold"], prm["n_cds"], prm["n_biopfams"],
+                                            prm["average_threshold"], prm["trim"], carry_state=carry)
+            assert [[f"{cids[c]}_cluster_{k}", ids[a:b]] for c, k, a, b in seg.tolist()] == dec["clusters"], (case["name"], dec["params"])
+            n += len(got)
+        kinds += 1
+    assert kinds == 4 and n > 1000

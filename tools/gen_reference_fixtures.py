@@ -5,7 +5,8 @@ Imports the REFERENCE'S OWN code from /root/reference (nothing of it is copied o
 
 * `gecco.crf.ClusterCRF.predict_probabilities`   (gecco/crf/__init__.py:148-273: sort, group, pad / skip + warnings, the sliding
   windows of gecco/_meta.py:124-132, max over windows, annotate (gecco/crf/features.py), cluster_weight, progress calls),
-* `gecco.refine.ClusterRefiner.iter_clusters`     (gecco/refine.py:51-64,118-200: grouper, trim, both criteria, edge distance),
+* `gecco.refine.ClusterRefiner.iter_clusters`     (gecco/refine.py:51-64,118-200: grouper, trim, both criteria, edge distance;
+  also on the planted boundary batches of tests/helpers.py -> ref_refiner_ties),
 * `gecco.model.Cluster.domain_composition`        (gecco/model.py:458-503) and `Cluster.average_probability` (:442-447)
 
 on seeded random inputs, writing DATA fixtures (inputs + the reference's outputs) to tests/golden/ref_*.json.
@@ -299,6 +300,46 @@ def gen_refiner_cases(gecco, om, n_cases, rng):
     return cases
 
 
+# ---- refiner cases on planted boundaries ---------------------------------------------------------------------------------------
+def gen_refiner_tie_cases(gecco):
+    """The planted batches of tests/helpers.py (plant_refiner_boundaries: every grouper, "gecco" and "antismash" decision on
+    its boundary or one or two ulps from it), runs up to 1 000 genes, decided by the reference's own ClusterRefiner: one
+    iter_clusters call per contig, or one over all contigs when the grouper state is carried."""
+    import importlib.util
+
+    # (by path: the reference's own `tests` package may be the one `import tests` finds here)
+    spec = importlib.util.spec_from_file_location("_planter_helpers", os.path.join(ROOT, "tests", "helpers.py"))
+    helpers = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(helpers)
+    genes_from_planted, plant_refiner_boundaries, refiner_params = \
+        helpers.genes_from_planted, helpers.plant_refiner_boundaries, helpers.refiner_params
+    model, refine = gecco.model, gecco.refine
+    cases = []
+    for batch in plant_refiner_boundaries(seed=7, lengths=(1, 7, 8, 9, 16, 127, 128, 129, 136, 1000), geometry=(2049,)):
+        rows, contigs = [], []
+        for c, genes in genes_from_planted(batch).items():
+            src = sys.modules["Bio.SeqRecord"].SeqRecord(None, id=f"c{c:04d}")
+            objs = []
+            for g in genes:
+                doms = [model.Domain(d.name, d.start, d.end, "Pfam", 1e-5, 1e-7, probability=g._probability) for d in g.protein.domains]
+                objs.append(model.Gene(src, g.start, g.end, model.Strand.Coding, model.Protein(g.protein.id, None, doms),
+                                       _probability=g._probability))
+                rows.append([src.id, g.protein.id, g.start, g.end, g._probability, [d.name for d in g.protein.domains]])
+            contigs.append(objs)
+        decisions = []
+        for prm in batch["params"]:
+            kw = refiner_params(prm)
+            carry = kw.pop("carry_state")
+            refiner = refine.ClusterRefiner(**kw)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")  # (numpy's "mean of empty slice" for a cluster trimmed to nothing: the reference's own)
+                calls = [[g for genes in contigs for g in genes]] if carry else contigs
+                clusters = [[c.id, [g.protein.id for g in c.genes]] for genes in calls for c in refiner.iter_clusters(genes)]
+            decisions.append({"params": dict(kw, carry_state=carry), "clusters": clusters})
+        cases.append({"name": batch["name"], "genes": rows, "decisions": decisions})
+    return cases
+
+
 # ---- composition cases -------------------------------------------------------------------------------------------------------
 def gen_composition_cases(gecco, om, n_cases, rng):
     model = gecco.model
@@ -351,6 +392,7 @@ def main():
         "ref_predict_probabilities": gen_crf_cases(gecco, om, args.cases, np.random.default_rng(SEED)),
         "ref_refiner": gen_refiner_cases(gecco, om, args.cases, np.random.default_rng(SEED + 1)),
         "ref_composition": gen_composition_cases(gecco, om, max(60, args.cases // 3), np.random.default_rng(SEED + 2)),
+        "ref_refiner_ties": gen_refiner_tie_cases(gecco),
     }
     for name, cases in sets.items():
         doc = dict(header, cases=cases)
