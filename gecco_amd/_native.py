@@ -170,6 +170,7 @@ SIGNATURES = {
     "gecco_crf_trainer_eval": (ctypes.c_int, [_vp, _c_f64p, _c_f64p, _c_f64p]),
     "gecco_crf_trainer_num_windows": (ctypes.c_int64, [_vp]),
     "gecco_crf_trainer_free": (None, [_vp]),
+    "gecco_crf_fisher_exact": (ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
     "gecco_crf_plan_time_windowed": (
         ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
     ),
@@ -1106,3 +1107,14 @@ class Trainer:
         wb = w if w.size else np.zeros(1)
         _check(self._lib.gecco_crf_trainer_eval(self._h, _ptr(wb, _c_f64p), ctypes.byref(f), _ptr(g, _c_f64p)))
         return f.value, g[:self.num_features]
+
+
+def fisher_exact(tables, device: int = 0) -> np.ndarray:
+    """Two-sided Fisher exact p-values of the 2x2 tables ``tables[i] = [[a, b], [c, d]]`` (any shape that reshapes to
+    ``(n, 4)``), computed on ``device`` (``gecco_crf_fisher_exact``): scipy's semantics, in fp64."""
+    lib = load_library()
+    t = np.ascontiguousarray(np.asarray(tables, dtype=np.int64).reshape(-1, 4))
+    out = np.empty(len(t), dtype=np.float64)
+    _check(lib.gecco_crf_fisher_exact(int(device), t.ctypes.data if len(t) else None, len(t),
+                                      out.ctypes.data if len(t) else None))
+    return out

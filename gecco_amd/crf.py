@@ -631,8 +631,15 @@ class ClusterCRF(object):
         ``shuffle``, shuffled with the global ``random``; every sliding window of every sequence, no padding), features
         are generated as CRFsuite does, and L-BFGS (OWL-QN when ``c1 > 0``) runs on the host around an objective and
         gradient evaluated on the device (``gecco_amd/train.py``, ``csrc/crf_train.hip``).  ``cpus`` is accepted and
-        ignored.  With sklearn-crfsuite importable and ``GECCO_AMD_FIT`` unset or ``reference``, and whenever ``select``
-        is given (Fisher feature selection needs statsmodels), the call is delegated to the reference class."""
+        ignored.
+
+        ``select`` (``0 < select <= 1``) runs GECCO's Fisher feature selection first, natively too
+        (``gecco_amd/select.py``, ``csrc/crf_fisher.hip``): ``significance`` becomes the p-value of every domain name
+        (corrected with ``correction_method`` unless it is None), ``significant_features`` the ``int(select * n)`` names
+        with the smallest p-values (ties broken by name; a cut that selects nothing raises ``ValueError``, and one that
+        still takes a p-value of 1 warns), and every other domain is removed from the genes before training.  Both are
+        saved with the model.  With sklearn-crfsuite importable and ``GECCO_AMD_FIT`` unset or ``reference``, the whole
+        call is delegated to the reference class."""
         mode = os.environ.get("GECCO_AMD_FIT", "").strip().lower()
         if mode not in ("", "native", "reference"):
             raise ValueError(f"GECCO_AMD_FIT must be 'native' or 'reference', not {mode!r}")
@@ -642,10 +649,34 @@ class ClusterCRF(object):
                 import sklearn_crfsuite  # noqa: F401
             except Exception:
                 native = True
-        if native and select is None:
+        if native:
+            sig = keep = None
+            if select is not None:
+                genes, sig, keep = self._select_features(genes, select, correction_method)
+            self.significance, self.significant_features = sig, keep  # (written into the fitted model's record)
             self._fit_native(genes, shuffle=shuffle)
             return
         self._fit_reference(genes, select=select, shuffle=shuffle, cpus=cpus, correction_method=correction_method)
+
+    def _select_features(self, genes: Iterable[Any], select: float, correction_method: Optional[str]
+                         ) -> Tuple[List[Any], Dict[str, float], FrozenSet[str]]:
+        """The ``select`` branch of the reference's ``fit`` (``gecco/crf/__init__.py:313-346``): genes sorted by sequence
+        and domains by start, the significance of every domain name and the selected names, and the genes keeping only
+        the selected domains."""
+        from . import select as _select
+
+        if not (0 < select <= 1):
+            raise ValueError(f"invalid value for select: {select}")
+        genes = sorted(genes, key=operator.attrgetter("source.id"))
+        for gene in genes:
+            gene.protein.domains.sort(key=operator.attrgetter("start"))
+        devices = self.devices or [0]
+        sig = _select.fisher_significance((gene.protein for gene in genes), correction_method=correction_method,
+                                          device=int(devices[0]))
+        keep = _select.select_features(sig, select)
+        genes = [gene.with_protein(gene.protein.with_domains([d for d in gene.protein.domains if d.name in keep]))
+                 for gene in genes]
+        return genes, sig, keep
 
     def _fit_reference(self, genes: Iterable[Any], **kwargs: Any) -> None:
         """Delegate to the reference implementation (needs GECCO with sklearn-crfsuite)."""
@@ -722,7 +753,8 @@ class ClusterCRF(object):
         crf = pickle_model.new_record("sklearn_crfsuite.estimator", "CRF", crf_state)
         record = pickle_model.new_record("gecco.crf", "ClusterCRF", {
             "feature_type": self.feature_type, "window_size": self.window_size, "window_step": self.window_step,
-            "algorithm": self.algorithm, "significance": None, "significant_features": None, "model": crf,
+            "algorithm": self.algorithm, "significance": self.significance,
+            "significant_features": self.significant_features, "model": crf,
             "_options": dict(self._options)})
         devices, reference_bits = self.devices, self.reference_bits
         fitted = type(self)._from_record(record)

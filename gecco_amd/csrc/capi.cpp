@@ -9,6 +9,7 @@
 
 #include "../../include/gecco_crf.h"
 #include "crf_exact_exp.hpp"
+#include "crf_fisher.hpp"
 #include "crf_model.hpp"
 #include "crf_plan.hpp"
 #include "crf_session.hpp"
@@ -92,7 +93,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 230; }
+GECCO_API int gecco_crf_version(void) { return 240; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -950,4 +951,15 @@ GECCO_API void gecco_crf_trainer_free(gecco_crf_trainer *t) {
     if (!t) return;
     DeviceGuard guard;
     delete t;
+}
+
+// ---- feature selection (ABI 2.4.0) ------------------------------------------------------------
+GECCO_API int gecco_crf_fisher_exact(int32_t device, const int64_t *tables, int64_t n, double *pvalue) {
+    GECCO_GUARD_BEGIN
+    int rc = fisher_check(tables, n, pvalue);
+    if (rc || n == 0) return rc;
+    if ((rc = check_device(device))) return rc;
+    DeviceGuard guard;
+    return fisher_exact(device, tables, n, pvalue);
+    GECCO_GUARD_END
 }

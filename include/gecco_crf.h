@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.3.0 = 230). */
+/* ABI version: major*100 + minor*10 + patch (2.4.0 = 240). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -437,6 +437,19 @@ int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_s
 int gecco_crf_trainer_eval(gecco_crf_trainer *t, const double *w, double *f, double *g);
 int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t);
 void gecco_crf_trainer_free(gecco_crf_trainer *t);
+
+/* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
+ * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
+ * per domain name.  tables: n rows of {a, b, c, d} (int64, row-major, = [[a, b], [c, d]]); pvalue[n] out.  Synchronous.
+ * Semantics (scipy 1.15): a zero row or column sum gives exactly 1.0; a pmf(a) within a relative 1e-14 of the pmf at the
+ * mode int((a + c + 1) * (a + b + 1) / (N + 2)) gives exactly 1.0; otherwise p is the hypergeometric mass from a outward on
+ * its side of the mode plus the mass of every term on the other side whose pmf is at most pmf(a) * (1 + 1e-14), clamped to
+ * 1.0.  Terms that are mathematically equal to pmf(a) (every symmetric table) are included.
+ * Range and accuracy: cells >= 0 and a total <= 2^31 - 1 (GECCO_CRF_EINVAL otherwise, before any device work; n = 0 is
+ * valid and touches no device).  Relative error <= 1e-10 against scipy wherever scipy's p >= 1e-280; below that both are
+ * < 1e-250 (p underflows to 0 where pmf(a) < e^-720 pmf(mode)); where scipy is itself off (up to ~3e-9 at N ~ 10^7) the
+ * value matches the exact one to 1e-12.  A table's value depends on that table alone. */
+int gecco_crf_fisher_exact(int32_t device, const int64_t *tables, int64_t n, double *pvalue);
 
 #ifdef __cplusplus
 }
