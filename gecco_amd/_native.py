@@ -170,6 +170,15 @@ SIGNATURES = {
     "gecco_crf_trainer_eval": (ctypes.c_int, [_vp, _c_f64p, _c_f64p, _c_f64p]),
     "gecco_crf_trainer_num_windows": (ctypes.c_int64, [_vp]),
     "gecco_crf_trainer_free": (None, [_vp]),
+    "gecco_crf_trainer_batch_create": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32,
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
+    ),
+    "gecco_crf_trainer_batch_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _c_f64p, ctypes.POINTER(_vp)]),
+    "gecco_crf_trainer_batch_num_problems": (ctypes.c_int32, [_vp]),
+    "gecco_crf_trainer_batch_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_batch_free": (None, [_vp]),
     "gecco_crf_fisher_exact": (ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
     "gecco_crf_plan_time_windowed": (
         ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
@@ -1107,6 +1116,89 @@ class Trainer:
         wb = w if w.size else np.zeros(1)
         _check(self._lib.gecco_crf_trainer_eval(self._h, _ptr(wb, _c_f64p), ctypes.byref(f), _ptr(g, _c_f64p)))
         return f.value, g[:self.num_features]
+
+
+class TrainerBatch:
+    """Several training sets of 2-label CRFs resident on one device at once (``gecco_crf_trainer_batch_*``).
+
+    ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)``
+    per problem, as ``Trainer`` takes them; ``window`` and ``step`` are shared.  ``eval(ws, active)`` evaluates the active
+    problems in one batched pass; problem k's f and g are bitwise what a lone ``Trainer`` of it returns for ``ws[k]``."""
+
+    def __init__(self, problems, window: int, step: int, device: int = 0):
+        self._lib = load_library()
+        self._h = None
+        n = len(problems)
+        arrays = {name: [] for name in ("seq_ptr", "item_ptr", "attr_id", "labels", "state_fid", "trans_fid")}
+        n_seqs, num_attrs, num_labels, num_features = [], [], [], []
+        for seq_ptr, item_ptr, attr_id, labels, A, state_fid, trans_fid, K in problems:
+            state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
+            if int(A) < 1 or state_fid.size % int(A) != 0:
+                raise ValueError("state_fid must have num_attrs * L entries")
+            L = state_fid.size // int(A)
+            if trans_fid.size != L * L:
+                raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
+            seq_ptr = _i32(seq_ptr)
+            for name, a in zip(arrays, (seq_ptr, _i32(item_ptr), _i32(attr_id), _i32(labels), state_fid, trans_fid)):
+                arrays[name].append(a if a.size else np.zeros(1, dtype=np.int32))
+            n_seqs.append(len(seq_ptr) - 1)
+            num_attrs.append(int(A))
+            num_labels.append(L)
+            num_features.append(int(K))
+        ptrs = {name: (_vp * max(n, 1))(*[a.ctypes.data for a in arrs]) for name, arrs in arrays.items()}
+        ints = [np.ascontiguousarray(v if v else [0], dtype=np.int32) for v in (n_seqs, num_attrs, num_labels, num_features)]
+        h = _vp()
+        _check(self._lib.gecco_crf_trainer_batch_create(
+            int(device), n, ptrs["seq_ptr"], _ptr(ints[0], _c_i32p), ptrs["item_ptr"], ptrs["attr_id"], ptrs["labels"],
+            _ptr(ints[1], _c_i32p), _ptr(ints[2], _c_i32p), int(window), int(step), ptrs["state_fid"], ptrs["trans_fid"],
+            _ptr(ints[3], _c_i32p), ctypes.byref(h)))
+        self._h = h
+        self.num_features = list(num_features)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.gecco_crf_trainer_batch_free(h)
+
+    def __len__(self) -> int:
+        return int(self._lib.gecco_crf_trainer_batch_num_problems(self._h))
+
+    def num_windows(self, k: int) -> int:
+        return int(self._lib.gecco_crf_trainer_batch_num_windows(self._h, int(k)))
+
+    def eval(self, ws, active=None, f=None, g=None):
+        """f and g of every active problem (all of them when ``active`` is None) under the weights ``ws[k]`` (None for
+        an inactive problem).  Returns ``(f, g)``: an ``(n,)`` float64 array and a list of gradient arrays.  Given ``f``
+        and ``g`` are written in place, and the entries of inactive problems are left as they were."""
+        n = len(self.num_features)
+        act = np.ones(n, dtype=np.uint8) if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        if act.shape != (n,):
+            raise ValueError(f"expected an active mask of {n} entries, got shape {act.shape}")
+        if f is None:
+            f = np.full(n, np.nan)
+        if g is None:
+            g = [np.empty(K) for K in self.num_features]
+        if not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.shape == (n,) and f.flags.c_contiguous):
+            raise ValueError("f must be a contiguous float64 array of one entry per problem")
+        wk, gk = [], []
+        w_ptr, g_ptr = (_vp * max(n, 1))(), (_vp * max(n, 1))()
+        for k in range(n):
+            if not act[k]:
+                continue
+            K = self.num_features[k]
+            w = np.ascontiguousarray(ws[k], dtype=np.float64)
+            if w.shape != (K,):
+                raise ValueError(f"problem {k}: expected {K} weights, got shape {w.shape}")
+            gg = g[k]
+            if not (isinstance(gg, np.ndarray) and gg.dtype == np.float64 and gg.shape == (K,) and gg.flags.c_contiguous):
+                raise ValueError(f"problem {k}: the gradient must be a contiguous float64 array of {K} entries")
+            w = w if w.size else np.zeros(1)
+            gb = gg if gg.size else np.zeros(1)
+            wk.append(w)
+            gk.append(gb)
+            w_ptr[k], g_ptr[k] = w.ctypes.data, gb.ctypes.data
+        _check(self._lib.gecco_crf_trainer_batch_eval(self._h, _ptr(act, _c_u8p), w_ptr, _ptr(f, _c_f64p), g_ptr))
+        return f, g
 
 
 def fisher_exact(tables, device: int = 0) -> np.ndarray:

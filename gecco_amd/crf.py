@@ -730,13 +730,24 @@ class ClusterCRF(object):
     def _fit_native(self, genes: Iterable[Any], *, shuffle: bool = True) -> None:
         from . import train
 
+        ts, params = self._training_set(genes, shuffle=shuffle)
+        devices = self.devices or [0]
+        self._adopt_fit(ts, train.fit_training_set(ts, params, device=int(devices[0])))
+
+    def _training_set(self, genes: Iterable[Any], *, shuffle: bool = True) -> Tuple["train.TrainingSet", Dict[str, Any]]:
+        """The encoded training set ``_fit_native`` optimises, and the trainer parameters."""
+        from . import train
+
         params = train.trainer_params(self._options)
         feats, labels = self.training_instances(genes, shuffle=shuffle)
         ts = train.build_training_set(feats, labels, self.window_size, self.window_step, min_freq=float(params["min_freq"]),
                                       all_possible_states=bool(params["all_possible_states"]),
                                       all_possible_transitions=bool(params["all_possible_transitions"]))
-        devices = self.devices or [0]
-        result = train.fit_training_set(ts, params, device=int(devices[0]))
+        return ts, params
+
+    def _adopt_fit(self, ts: "train.TrainingSet", result: "train.OptimizeResult") -> None:
+        from . import train
+
         self._adopt_model_blob(train.model_blob(ts, result.x))
         self.training_result_ = result
 

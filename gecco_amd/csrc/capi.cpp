@@ -93,7 +93,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 240; }
+GECCO_API int gecco_crf_version(void) { return 250; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -945,9 +945,57 @@ GECCO_API int gecco_crf_trainer_eval(gecco_crf_trainer *t, const double *w, doub
     GECCO_GUARD_END
 }
 
-GECCO_API int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t) { return t ? trainer_num_windows(t->t) : -1; }
+GECCO_API int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t) { return t ? trainer_num_windows(t->t, 0) : -1; }
 
 GECCO_API void gecco_crf_trainer_free(gecco_crf_trainer *t) {
+    if (!t) return;
+    DeviceGuard guard;
+    delete t;
+}
+
+// ---- training, several problems at once (ABI 2.5.0) --------------------------------------------
+struct gecco_crf_trainer_batch {
+    Trainer *t = nullptr;
+    ~gecco_crf_trainer_batch() { trainer_destroy(t); }
+};
+
+GECCO_API int gecco_crf_trainer_batch_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                             const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                             const int32_t *const *attr_id, const int32_t *const *labels,
+                                             const int32_t *num_attrs, const int32_t *num_labels, int32_t window, int32_t step,
+                                             const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                             const int32_t *num_features, gecco_crf_trainer_batch **out) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    auto h = std::make_unique<gecco_crf_trainer_batch>();
+    int rc = trainer_batch_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
+                                  step, state_fid, trans_fid, num_features, &h->t);
+    if (rc) return rc;
+    *out = h.release();
+    return GECCO_CRF_OK;
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_trainer_batch_eval(gecco_crf_trainer_batch *t, const uint8_t *active, const double *const *w, double *f,
+                                           double *const *g) {
+    if (!t) return GECCO_CRF_EINVAL;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    return trainer_batch_eval(t->t, active, w, f, g);
+    GECCO_GUARD_END
+}
+
+GECCO_API int32_t gecco_crf_trainer_batch_num_problems(const gecco_crf_trainer_batch *t) {
+    return t ? trainer_num_problems(t->t) : -1;
+}
+
+GECCO_API int64_t gecco_crf_trainer_batch_num_windows(const gecco_crf_trainer_batch *t, int32_t k) {
+    return t ? trainer_num_windows(t->t, k) : -1;
+}
+
+GECCO_API void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t) {
     if (!t) return;
     DeviceGuard guard;
     delete t;

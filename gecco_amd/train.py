@@ -17,12 +17,12 @@ What is reproduced ([EXT] CRFsuite 0.12 ``crf1d`` + ``train_lbfgs`` with libLBFG
   the same, the iterates are not).
 """
 import math
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["TRAINER_DEFAULTS", "trainer_params", "minimize", "OptimizeResult", "TrainingSet", "build_training_set",
-           "fit_training_set", "model_blob"]
+__all__ = ["TRAINER_DEFAULTS", "trainer_params", "minimize", "minimize_steps", "OptimizeResult", "TrainingSet",
+           "build_training_set", "fit_training_set", "fit_training_sets", "model_blob"]
 
 #: libLBFGS parameters as CRFsuite's ``train_lbfgs`` sets them (``max_iterations`` None = unbounded)
 TRAINER_DEFAULTS = {"num_memories": 6, "epsilon": 1e-5, "period": 10, "delta": 1e-5, "max_iterations": None}
@@ -85,7 +85,24 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
     iteration limit, or a failed line search (status "line search failed": the point before that search is returned, as
     libLBFGS does; near the optimum this is where the objective's rounding hides any further decrease).  A trial point
     whose f or g is not finite fails the sufficient-decrease test, so the step is halved: it is never accepted.  A start
-    ``x0`` whose f or g is not finite raises ``ValueError``."""
+    ``x0`` whose f or g is not finite raises ``ValueError``.  This drives ``minimize_steps`` with ``fg``."""
+    steps = minimize_steps(x0, c1=c1, num_memories=num_memories, epsilon=epsilon, period=period, delta=delta,
+                           max_iterations=max_iterations, max_linesearch=max_linesearch, callback=callback)
+    try:
+        x = next(steps)
+        while True:
+            x = steps.send(fg(x))
+    except StopIteration as stop:
+        return stop.value
+
+
+def minimize_steps(x0: np.ndarray, c1: float = 0.0, num_memories: int = 6, epsilon: float = 1e-5, period: int = 10,
+                   delta: float = 1e-5, max_iterations: Optional[int] = None, max_linesearch: int = 20,
+                   callback: Optional[Callable[[int, float, np.ndarray], None]] = None
+                   ) -> Generator[np.ndarray, Tuple[float, np.ndarray], OptimizeResult]:
+    """``minimize`` in stepping form, for driving several optimisations in lock-step: a generator that yields every
+    point to evaluate, takes ``(f, g)`` of the smooth part there back through ``send``, and returns the
+    ``OptimizeResult`` (``StopIteration.value``).  The same iterates, statuses and evaluation counts as ``minimize``."""
     ftol, wolfe, min_step, max_step = 1e-4, 0.9, 1e-20, 1e20
     x = np.array(x0, dtype=np.float64)
     n_eval = 0
@@ -93,7 +110,7 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
     def evaluate(xv):
         nonlocal n_eval
         n_eval += 1
-        f, g = fg(xv)
+        f, g = yield xv
         g = np.asarray(g, dtype=np.float64)
         if c1 > 0:
             f = f + c1 * float(np.abs(xv).sum())
@@ -102,7 +119,7 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
     def finite(fv, gv):
         return math.isfinite(fv) and bool(np.all(np.isfinite(gv)))
 
-    fx, g = evaluate(x)
+    fx, g = yield from evaluate(x)
     if not finite(fx, g):
         raise ValueError(f"minimize: the objective is not finite at the start point (f = {fx}, "
                          f"{int(np.count_nonzero(~np.isfinite(g)))} non-finite gradient entries)")
@@ -127,7 +144,7 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
             while True:
                 x = xp + step * d
                 x = np.where(x * orthant <= 0, 0.0, x)
-                fx, g = evaluate(x)
+                fx, g = yield from evaluate(x)
                 count += 1
                 if finite(fx, g) and fx <= fp + ftol * float(np.dot(x - xp, pgp)):
                     ok = True
@@ -142,7 +159,7 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
                 return OptimizeResult(x, fx, k - 1, n_eval, "search direction is not a descent direction")
             while True:
                 x = xp + step * d
-                fx, g = evaluate(x)
+                fx, g = yield from evaluate(x)
                 count += 1
                 if not finite(fx, g) or fx > fp + step * ftol * dginit:
                     width = 0.5
@@ -331,6 +348,47 @@ def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0
     return minimize(fg, np.zeros(ts.num_features), c1=float(params["c1"]), num_memories=int(params["num_memories"]),
                     epsilon=float(params["epsilon"]), period=int(params["period"]), delta=float(params["delta"]),
                     max_iterations=params["max_iterations"], callback=callback)
+
+
+def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], device: int = 0) -> List[OptimizeResult]:
+    """``fit_training_set`` of every set at once: all sets are resident on the device together (``_native.TrainerBatch``)
+    and one optimiser per set runs in lock-step, each round evaluating the pending points of the unfinished sets in one
+    batched pass.  Sets drop out as they stop.  Result k is exactly ``fit_training_set(sets[k], params, device)``:
+    the batched objective gives every set the bits a lone trainer gives it, and the host adds the same L2 term.
+    The sets must share ``window`` and ``step``."""
+    from . import _native
+
+    if not sets:
+        return []
+    window, step = sets[0].window, sets[0].step
+    if any(ts.window != window or ts.step != step for ts in sets):
+        raise ValueError("fit_training_sets: every training set must have the same window and step")
+    batch = _native.TrainerBatch([(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.state_fid,
+                                   ts.trans_fid, ts.num_features) for ts in sets], window, step, device=device)
+    c2 = float(params["c2"])
+    n = len(sets)
+    steppers = [minimize_steps(np.zeros(ts.num_features), c1=float(params["c1"]), num_memories=int(params["num_memories"]),
+                               epsilon=float(params["epsilon"]), period=int(params["period"]), delta=float(params["delta"]),
+                               max_iterations=params["max_iterations"]) for ts in sets]
+    pending: List[Optional[np.ndarray]] = [next(st) for st in steppers]
+    results: List[Optional[OptimizeResult]] = [None] * n
+    f = np.zeros(n)
+    g = [np.empty(ts.num_features) for ts in sets]
+    while any(x is not None for x in pending):
+        active = np.array([x is not None for x in pending], dtype=np.uint8)
+        batch.eval(pending, active, f, g)
+        for k in np.flatnonzero(active).tolist():
+            w = pending[k]
+            fk, gk = float(f[k]), g[k].copy()
+            if c2 > 0:
+                fk += c2 * float(np.dot(w, w))
+                gk = gk + (2.0 * c2) * w
+            try:
+                pending[k] = steppers[k].send((fk, gk))
+            except StopIteration as stop:
+                pending[k] = None
+                results[k] = stop.value
+    return results
 
 
 def model_blob(ts: TrainingSet, w: np.ndarray) -> bytes:

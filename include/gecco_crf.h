@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.4.0 = 240). */
+/* ABI version: major*100 + minor*10 + patch (2.5.0 = 250). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -425,7 +425,8 @@ void gecco_crf_buffer_free(uint8_t *p);
  * after the call.  num_labels must be 2 and window at most 32 (GECCO_CRF_EUNSUPPORTED otherwise).
  * eval: f = sum over windows of (log Z - score of the gold path), g[k] = expected - empirical count of feature k, under
  * the weights w[num_features] (features absent from both tables weigh 0).  No regularisation terms.  Synchronous; every
- * sum has a fixed order, so equal weights give equal bits.  One evaluation at a time per trainer.
+ * sum has a fixed order, so equal weights give equal bits.  One evaluation at a time per trainer.  (A lone trainer is the
+ * one-problem case of gecco_crf_trainer_batch_*, below: the same kernels.)
  * Range: correct for any finite weights.  Each window runs a scaled forward-backward (transitions max-shifted); a window
  * whose scaled intermediates leave the normal fp64 range (state-score gaps beyond ~708 nats, transition weights more
  * than ~708 apart) is recomputed in log space.  Non-finite weights give a non-finite f. */
@@ -437,6 +438,31 @@ int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_s
 int gecco_crf_trainer_eval(gecco_crf_trainer *t, const double *w, double *f, double *g);
 int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t);
 void gecco_crf_trainer_free(gecco_crf_trainer *t);
+
+/* ---- training, several problems at once (ABI 2.5.0) --------------------------------------------------------------
+ * K independent training sets resident on one device, evaluated together (cross-validation folds, for example).  Problem k
+ * is exactly what gecco_crf_trainer_create takes: seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k],
+ * num_labels[k], state_fid[k], trans_fid[k], num_features[k]; all problems share `window` and `step`.  The single trainer's
+ * checks apply to every problem, and the first bad problem is reported by its index ("problem k: ..." in the message).
+ * Memory is about the sum of the lone trainers' (GECCO_CRF_ENOMEM, with nothing left allocated, when it does not fit).
+ * eval: for every k with active[k] != 0, f[k] and g[k][num_features[k]] under the weights w[k][num_features[k]]; the
+ * entries of inactive problems are neither read nor written (their w[k] and g[k] may be NULL).  One upload, six launches
+ * whatever K is, one download; synchronous.
+ * Bit contract: f[k] and g[k] are bitwise equal to gecco_crf_trainer_eval on a trainer built from problem k alone, with the
+ * same w[k], whatever the other problems hold and whichever of them are active: every sum stays inside its problem, in the
+ * lone trainer's order (a problem whose transitions force log space, or whose weights are not finite, affects no other).
+ * num_windows(t, k): the windows of problem k (-1 for a bad k); num_problems: K. */
+typedef struct gecco_crf_trainer_batch gecco_crf_trainer_batch;
+int gecco_crf_trainer_batch_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                                   const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                                   const int32_t *num_attrs, const int32_t *num_labels, int32_t window, int32_t step,
+                                   const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                                   gecco_crf_trainer_batch **out);
+int gecco_crf_trainer_batch_eval(gecco_crf_trainer_batch *t, const uint8_t *active, const double *const *w, double *f,
+                                 double *const *g);
+int32_t gecco_crf_trainer_batch_num_problems(const gecco_crf_trainer_batch *t);
+int64_t gecco_crf_trainer_batch_num_windows(const gecco_crf_trainer_batch *t, int32_t k);
+void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
