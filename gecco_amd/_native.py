@@ -180,6 +180,13 @@ SIGNATURES = {
     "gecco_crf_trainer_batch_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_batch_free": (None, [_vp]),
     "gecco_crf_fisher_exact": (ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
+    "gecco_crf_cluster_overlaps": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
+                       ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+    ),
+    "gecco_crf_domain_composition_members": (
+        ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp]
+    ),
     "gecco_crf_plan_time_windowed": (
         ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
     ),
@@ -467,6 +474,65 @@ def domain_composition(seg, dom_ptr, dom_col, dom_weight, n_cols, normalize=True
     _check(lib.gecco_crf_domain_composition(
         device, _ptr(seg_buf, _c_i32p), len(seg), _ptr(dom_ptr, _c_i32p), len(dom_ptr) - 1, _ptr(dom_col, _c_i32p),
         _ptr(dom_weight, _c_f64p), int(n_cols), int(bool(normalize)), _ptr(out_buf, _c_f64p)))
+    return out
+
+
+def _addr(a: np.ndarray):
+    return a.ctypes.data if a.size else None
+
+
+def cluster_overlaps(gene_seq, gene_start, gene_end, cluster_ptr, cluster_start, cluster_end, device=0):
+    """The interval join of genes and clusters (gecco_crf_cluster_overlaps): ``(labels, member_ptr, member_gene)``.
+
+    Genes are grouped by sequence code (codes ``0 <= c < len(cluster_ptr) - 1``, non-decreasing) and sorted by start inside
+    a sequence; the clusters of sequence s are rows ``cluster_ptr[s]:cluster_ptr[s + 1]`` of ``cluster_start`` /
+    ``cluster_end``, sorted by start.  ``labels[g]`` (uint8) is 1 where gene g overlaps any cluster of its sequence, bounds
+    inclusive; ``member_gene[member_ptr[k]:member_ptr[k + 1]]`` are the genes of cluster k in gene order."""
+    lib = load_library()
+    seq = np.ascontiguousarray(gene_seq, dtype=np.int32)
+    start = np.ascontiguousarray(gene_start, dtype=np.int64)
+    end = np.ascontiguousarray(gene_end, dtype=np.int64)
+    cptr = np.ascontiguousarray(cluster_ptr, dtype=np.int32)
+    cs = np.ascontiguousarray(cluster_start, dtype=np.int64)
+    ce = np.ascontiguousarray(cluster_end, dtype=np.int64)
+    n, n_seqs = len(seq), len(cptr) - 1
+    if len(start) != n or len(end) != n:
+        raise ValueError("cluster_overlaps: gene_seq, gene_start and gene_end differ in length")
+    if n_seqs < 0 or int(cptr[-1]) != len(cs) or len(ce) != len(cs):
+        raise ValueError("cluster_overlaps: cluster_ptr[-1] must be the number of clusters")
+    m = len(cs)
+    labels = np.zeros(n, dtype=np.uint8)
+    member_ptr = np.zeros(m + 1, dtype=np.int32)
+    members = np.zeros(n + 64, dtype=np.int32)  # (a gene is usually in one cluster at most: one retry otherwise)
+    count = ctypes.c_int64(0)
+    for _ in range(2):
+        rc = lib.gecco_crf_cluster_overlaps(int(device), n, _addr(seq), _addr(start), _addr(end), n_seqs, cptr.ctypes.data,
+                                            _addr(cs), _addr(ce), _addr(labels), member_ptr.ctypes.data, members.ctypes.data,
+                                            len(members), ctypes.byref(count))
+        if rc == EINVAL and count.value > len(members):
+            members = np.zeros(count.value, dtype=np.int32)
+            continue
+        _check(rc)
+        break
+    return labels, member_ptr, members[:count.value].copy()
+
+
+def domain_composition_members(member_ptr, member_gene, dom_ptr, dom_col, dom_weight, n_cols, normalize=True,
+                               device=0) -> np.ndarray:
+    """Dense (n_clusters, n_cols) weighted domain compositions of clusters given as member lists
+    (gecco_crf_domain_composition_members): cluster k is the genes ``member_gene[member_ptr[k]:member_ptr[k + 1]]`` in
+    that order, gene g the domain rows ``dom_ptr[g]:dom_ptr[g + 1]``; the bits of ``domain_composition`` on the
+    concatenated rows."""
+    lib = load_library()
+    mptr, mgene, dptr, dcol = _i32(member_ptr), _i32(member_gene), _i32(dom_ptr), _i32(dom_col)
+    dw = np.ascontiguousarray(dom_weight, dtype=np.float64)
+    if len(dcol) != int(dptr[-1]) or len(dw) != len(dcol):
+        raise ValueError("domain_composition_members: dom_ptr[-1] must be the number of domain rows")
+    k = len(mptr) - 1
+    out = np.zeros((k, int(n_cols)), dtype=np.float64)
+    _check(lib.gecco_crf_domain_composition_members(int(device), mptr.ctypes.data, k, _addr(mgene), dptr.ctypes.data,
+                                                    len(dptr) - 1, _addr(dcol), _addr(dw), int(n_cols), int(bool(normalize)),
+                                                    _addr(out)))
     return out
 
 

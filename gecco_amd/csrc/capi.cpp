@@ -11,6 +11,7 @@
 #include "crf_exact_exp.hpp"
 #include "crf_fisher.hpp"
 #include "crf_model.hpp"
+#include "crf_overlap.hpp"
 #include "crf_plan.hpp"
 #include "crf_session.hpp"
 #include "crf_tables.hpp"
@@ -93,7 +94,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 250; }
+GECCO_API int gecco_crf_version(void) { return 260; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -1009,5 +1010,38 @@ GECCO_API int gecco_crf_fisher_exact(int32_t device, const int64_t *tables, int6
     if ((rc = check_device(device))) return rc;
     DeviceGuard guard;
     return fisher_exact(device, tables, n, pvalue);
+    GECCO_GUARD_END
+}
+
+// ---- interval join of genes and clusters (ABI 2.6.0) ------------------------------------------
+GECCO_API int gecco_crf_cluster_overlaps(int32_t device, int32_t n_genes, const int32_t *gene_seq, const int64_t *gene_start,
+                                         const int64_t *gene_end, int32_t n_seqs, const int32_t *cluster_ptr,
+                                         const int64_t *cluster_start, const int64_t *cluster_end, uint8_t *label_out,
+                                         int32_t *member_ptr_out, int32_t *member_gene_out, int64_t max_members,
+                                         int64_t *n_members) {
+    GECCO_GUARD_BEGIN
+    int rc = overlaps_check(n_genes, gene_seq, gene_start, gene_end, n_seqs, cluster_ptr, cluster_start, cluster_end, label_out,
+                            member_ptr_out, max_members, n_members);
+    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
+    DeviceGuard guard;
+    return cluster_overlaps(device, n_genes, gene_seq, gene_start, gene_end, n_seqs, cluster_ptr, cluster_start, cluster_end,
+                            label_out, member_ptr_out, member_gene_out, max_members, n_members);
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_domain_composition_members(int32_t device, const int32_t *member_ptr, int32_t n_clusters,
+                                                   const int32_t *member_gene, const int32_t *dom_ptr, int32_t n_genes,
+                                                   const int32_t *dom_col, const double *dom_weight, int32_t n_cols,
+                                                   int32_t normalize, double *comp_out) {
+    GECCO_GUARD_BEGIN
+    int rc = composition_members_check(member_ptr, n_clusters, member_gene, dom_ptr, n_genes, dom_col, dom_weight, n_cols,
+                                       comp_out);
+    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
+    if (n_clusters == 0 || n_cols == 0) return GECCO_CRF_OK;
+    DeviceGuard guard;
+    return composition_members(device, member_ptr, n_clusters, member_gene, dom_ptr, n_genes, dom_col, dom_weight, n_cols,
+                               normalize, comp_out);
     GECCO_GUARD_END
 }

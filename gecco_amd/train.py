@@ -15,8 +15,11 @@ What is reproduced ([EXT] CRFsuite 0.12 ``crf1d`` + ``train_lbfgs`` with libLBFG
   backtracking: with the sufficient-decrease test on the orthant-projected step when ``c1 > 0`` (what CRFsuite uses
   there), and with the Wolfe conditions when ``c1 = 0`` (CRFsuite's default there is More-Thuente; the optimum is
   the same, the iterates are not).
+
+``python -m gecco_amd.train`` is ``gecco train``: labelled tables in, a model directory out (``train_cli``).
 """
 import math
+import sys
 from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -396,3 +399,14 @@ def model_blob(ts: TrainingSet, w: np.ndarray) -> bytes:
     from .crfsuite_model import model_bytes
 
     return model_bytes(ts.labels_, ts.attrs_, ts.state_attr, ts.state_label, ts.trans_src, ts.trans_dst, w)
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    """``gecco train`` (``train_cli.main``)."""
+    from . import train_cli
+
+    return train_cli.main(argv)
+
+
+if __name__ == "__main__":
+    sys.exit(main())

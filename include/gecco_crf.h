@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.5.0 = 250). */
+/* ABI version: major*100 + minor*10 + patch (2.6.0 = 260). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -476,6 +476,31 @@ void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t);
  * < 1e-250 (p underflows to 0 where pmf(a) < e^-720 pmf(mode)); where scipy is itself off (up to ~3e-9 at N ~ 10^7) the
  * value matches the exact one to 1e-12.  A table's value depends on that table alone. */
 int gecco_crf_fisher_exact(int32_t device, const int64_t *tables, int64_t n, double *pvalue);
+
+/* ---- interval join of genes and clusters (ABI 2.6.0) ----------------------------------------------------------------
+ * What GECCO's `label_genes` (gecco/cli/commands/_common.py) and `gecco train`'s `_assign_clusters` ask: which clusters of
+ * its sequence does every gene overlap, bounds inclusive (cluster_start <= gene_end and gene_start <= cluster_end).
+ * Genes: n_genes rows of (gene_seq, gene_start, gene_end), grouped by sequence code (0 <= code < n_seqs, non-decreasing) and
+ * sorted by start inside a sequence (GECCO_CRF_EINVAL otherwise; equal starts may come in any order).  Clusters: those of
+ * sequence s are cluster_start / cluster_end[cluster_ptr[s] .. cluster_ptr[s + 1]), sorted by start; a sequence may have
+ * no genes or no clusters.  Coordinates are below 2^60 in magnitude.
+ * Out: label_out[n_genes] = 1 where the gene overlaps any cluster, else 0; member_ptr_out[n_clusters + 1] /
+ * member_gene_out = the genes of every cluster in gene order (CSR; a gene in several clusters is listed in each).  The
+ * member count is written to *n_members; when it exceeds max_members, labels and member_ptr_out are still written, the
+ * call returns GECCO_CRF_EINVAL, and the caller retries with a larger member_gene_out.  Deterministic; synchronous. */
+int gecco_crf_cluster_overlaps(int32_t device, int32_t n_genes, const int32_t *gene_seq, const int64_t *gene_start,
+                               const int64_t *gene_end, int32_t n_seqs, const int32_t *cluster_ptr,
+                               const int64_t *cluster_start, const int64_t *cluster_end, uint8_t *label_out,
+                               int32_t *member_ptr_out, int32_t *member_gene_out, int64_t max_members, int64_t *n_members);
+
+/* gecco_crf_domain_composition with clusters given as member lists instead of contiguous gene ranges: cluster k is the
+ * genes member_gene[member_ptr[k] .. member_ptr[k + 1]) in that order (any genes, repeats allowed), each contributing its
+ * domain rows dom_ptr[g] .. dom_ptr[g + 1].  comp_out[n_clusters][n_cols]: the same sums, in the same order, as
+ * gecco_crf_domain_composition gives for the concatenated rows.  Synchronous. */
+int gecco_crf_domain_composition_members(int32_t device, const int32_t *member_ptr, int32_t n_clusters,
+                                         const int32_t *member_gene, const int32_t *dom_ptr, int32_t n_genes,
+                                         const int32_t *dom_col, const double *dom_weight, int32_t n_cols,
+                                         int32_t normalize, double *comp_out);
 
 #ifdef __cplusplus
 }
