@@ -187,6 +187,14 @@ SIGNATURES = {
     "gecco_crf_domain_composition_members": (
         ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp]
     ),
+    "gecco_crf_forest_fit": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp,
+                       _vp, ctypes.c_int32, ctypes.POINTER(_vp)]
+    ),
+    "gecco_crf_forest_info": (ctypes.c_int, [_vp, _c_i32p, _c_i32p, _c_i32p, _vp, _vp]),
+    "gecco_crf_forest_export": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gecco_crf_forest_predict": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp]),
+    "gecco_crf_forest_free": (None, [_vp]),
     "gecco_crf_plan_time_windowed": (
         ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
     ),
@@ -1276,3 +1284,66 @@ def fisher_exact(tables, device: int = 0) -> np.ndarray:
     _check(lib.gecco_crf_fisher_exact(int(device), t.ctypes.data if len(t) else None, len(t),
                                       out.ctypes.data if len(t) else None))
     return out
+
+
+class Forest:
+    """A random forest fitted on the device (``gecco_crf_forest_*``): sklearn 1.7's RandomForestClassifier for the
+    configuration GECCO's TypeClassifier uses, tree for tree.  The host draws the random streams (see ``gecco_amd.types``)."""
+
+    def __init__(self, col_ptr, row_idx, values, n_samples: int, y, n_classes, sample_counts, rand_state, max_features: int,
+                 device: int = 0):
+        lib = self._lib = load_library()
+        cp = np.ascontiguousarray(col_ptr, dtype=np.int32)
+        ri = np.ascontiguousarray(row_idx, dtype=np.int32)
+        va = np.ascontiguousarray(values, dtype=np.float32)
+        yy = np.ascontiguousarray(y, dtype=np.uint8)
+        nc = np.ascontiguousarray(n_classes, dtype=np.uint8)
+        sc = np.ascontiguousarray(sample_counts, dtype=np.int32)
+        rs = np.ascontiguousarray(rand_state, dtype=np.uint32)
+        n_features, n_outputs = len(cp) - 1, len(nc)
+        if yy.shape != (int(n_samples), n_outputs) or sc.shape != (len(rs), int(n_samples)):
+            raise ValueError("forest fit: y must be (n_samples, n_outputs) and sample_counts (n_trees, n_samples)")
+        h = _vp()
+        self._h = None
+        _check(lib.gecco_crf_forest_fit(int(device), int(n_samples), n_features, _addr(cp), _addr(ri), _addr(va), n_outputs,
+                                        _addr(nc), _addr(yy), len(rs), _addr(sc), _addr(rs), int(max_features), ctypes.byref(h)))
+        self._h = h
+        n_trees, n_out, mc = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        nodes = np.zeros(len(rs), dtype=np.int32)
+        depth = np.zeros(len(rs), dtype=np.int32)
+        _check(lib.gecco_crf_forest_info(h, ctypes.byref(n_trees), ctypes.byref(n_out), ctypes.byref(mc), nodes.ctypes.data,
+                                         depth.ctypes.data))
+        self.n_trees, self.n_outputs, self.max_n_classes = n_trees.value, n_out.value, mc.value
+        self.n_features = n_features
+        self.node_count, self.max_depth = nodes, depth
+
+    def export(self, tree: int) -> dict:
+        """Tree `tree` as sklearn's ``Tree`` arrays (intp arrays as int64, ``value`` as (nodes, n_outputs, max_n_classes))."""
+        n = int(self.node_count[tree])
+        i32 = {k: np.zeros(n, dtype=np.int32) for k in ("children_left", "children_right", "feature", "n_node_samples")}
+        f64 = {k: np.zeros(n, dtype=np.float64) for k in ("threshold", "impurity", "weighted_n_node_samples")}
+        value = np.zeros((n, self.n_outputs, self.max_n_classes), dtype=np.float64)
+        _check(self._lib.gecco_crf_forest_export(
+            self._h, int(tree), i32["children_left"].ctypes.data, i32["children_right"].ctypes.data, i32["feature"].ctypes.data,
+            f64["threshold"].ctypes.data, f64["impurity"].ctypes.data, i32["n_node_samples"].ctypes.data,
+            f64["weighted_n_node_samples"].ctypes.data, value.ctypes.data))
+        out = {k: v.astype(np.int64) for k, v in i32.items()}
+        out.update(f64)
+        out["value"] = value
+        return out
+
+    def predict(self, x) -> np.ndarray:
+        """``posit[r, k] = 1 - predict_proba(x)[k][r, 0]`` of the dense rows ``x`` (n_rows, n_features)."""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        if xx.ndim != 2 or xx.shape[1] != self.n_features:
+            raise ValueError(f"forest predict: expected rows of {self.n_features} features, got shape {xx.shape}")
+        out = np.zeros((xx.shape[0], self.n_outputs), dtype=np.float64)
+        if len(xx):
+            _check(self._lib.gecco_crf_forest_predict(self._h, len(xx), xx.ctypes.data, out.ctypes.data))
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            self._lib.gecco_crf_forest_free(h)
+            self._h = None

@@ -4,7 +4,8 @@ GECCO threads a CRF *class* through every sub-command (``gecco/cli/commands/__in
 ``main(argv=None, console=None, *, program=..., crf_type=None, classifier_type=None, ...)``); this module is the
 five-line console entry point INTEGRATION.md describes.  ``gecco-hip run --genome X.fna -o out`` then behaves like
 ``gecco run`` with every contig of a call scored in batched HIP launches.  GECCO itself is not a dependency of this
-package (its ORF finder, HMMER wrapper and type classifier are reused, not rebuilt): without it the entry point says so.
+package (its ORF finder and HMMER wrapper are reused, not rebuilt; the type classifier is injected too, as
+``classifier_type=gecco_amd.types.TypeClassifier``): without it the entry point says so.
 """
 import sys
 from typing import List, Optional
@@ -20,8 +21,9 @@ def main(argv: Optional[List[str]] = None) -> int:
             "The table front end works without it: python -m gecco_amd.predict --genes ... --features ... -o OUT\n")
         return 2
     from .crf import ClusterCRF
+    from .types import TypeClassifier
 
-    return int(gecco.cli.main(argv, crf_type=ClusterCRF) or 0)
+    return int(gecco.cli.main(argv, crf_type=ClusterCRF, classifier_type=TypeClassifier) or 0)
 
 
 if __name__ == "__main__":

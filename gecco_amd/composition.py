@@ -7,7 +7,7 @@ Mirrors ``Cluster.domain_composition`` (``/root/reference/gecco/model.py:458-503
 Names, argument meaning and defaults follow the reference; the sums and the normalisation run in
 ``gecco_crf_domain_composition`` (bit-identical to numpy's summation order), the host side only
 turns names into column ids and p-values into weights exactly as the reference does
-(``1 - v`` or ``-log10(v)``).  The random forest itself is out of scope.
+(``1 - v`` or ``-log10(v)``).  The random forest that reads these matrices is ``gecco_amd.types``.
 """
 import math
 from typing import Iterable, List, Optional, Sequence
@@ -95,10 +95,12 @@ def table_compositions(seg: np.ndarray, order: List[str], feature_protein_id: Se
 
 
 def packed_compositions(seg: np.ndarray, packed, feature_domain: Sequence[str], feature_pvalue: Sequence[float],
-                        all_possible: Sequence[str], normalize: bool = True, device: int = 0) -> np.ndarray:
+                        all_possible: Sequence[str], normalize: bool = True, device: int = 0,
+                        order: Optional[np.ndarray] = None) -> np.ndarray:
     """`table_compositions` on the row ordering ``packing.pack_columns`` already computed
     (`packed.row_order` / `packed.row_ptr`: feature rows by gene position and domain start): no
-    per-row Python work."""
+    per-row Python work.  With `order` (the refiner's gene order, when it differs from the scoring order) the `seg`
+    ranges index `order`, and each cluster's genes are gathered in that order (gecco_crf_domain_composition_members)."""
     all_possible = list(all_possible)
     col_of, dups = _columns(all_possible)
     if dups:
@@ -108,5 +110,12 @@ def packed_compositions(seg: np.ndarray, packed, feature_domain: Sequence[str], 
     col_of_name = np.fromiter((col_of.get(str(nm), -1) for nm in names), dtype=np.int32, count=len(names))
     dom_col = col_of_name[inverse] if len(dom) else np.zeros(0, dtype=np.int32)
     dom_w = 1 - np.asarray(feature_pvalue, dtype=np.float64)[packed.row_order]
+    if order is not None:
+        seg = np.asarray(seg, dtype=np.int64).reshape(-1, 4)
+        member_ptr = np.concatenate([[0], np.cumsum(seg[:, 3] - seg[:, 2])]).astype(np.int32)
+        member_gene = (np.concatenate([np.asarray(order)[a:b] for a, b in seg[:, 2:4]]) if len(seg)
+                       else np.zeros(0)).astype(np.int32)
+        return _native.domain_composition_members(member_ptr, member_gene, packed.row_ptr.astype(np.int32), dom_col, dom_w,
+                                                  len(all_possible), normalize=normalize, device=device)
     return _native.domain_composition(seg, packed.row_ptr.astype(np.int32), dom_col, dom_w, len(all_possible),
                                       normalize=normalize, device=device)

@@ -10,6 +10,7 @@
 #include "../../include/gecco_crf.h"
 #include "crf_exact_exp.hpp"
 #include "crf_fisher.hpp"
+#include "crf_forest.hpp"
 #include "crf_model.hpp"
 #include "crf_overlap.hpp"
 #include "crf_plan.hpp"
@@ -94,7 +95,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 260; }
+GECCO_API int gecco_crf_version(void) { return 270; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -1044,4 +1045,86 @@ GECCO_API int gecco_crf_domain_composition_members(int32_t device, const int32_t
     return composition_members(device, member_ptr, n_clusters, member_gene, dom_ptr, n_genes, dom_col, dom_weight, n_cols,
                                normalize, comp_out);
     GECCO_GUARD_END
+}
+
+// ---- cluster type classifier (ABI 2.7.0) ----------------------------------------------------------
+struct gecco_crf_forest {
+    std::unique_ptr<Forest> f;
+};
+
+GECCO_API int gecco_crf_forest_fit(int32_t device, int32_t n_samples, int32_t n_features, const int32_t *col_ptr,
+                                   const int32_t *row_idx, const float *values, int32_t n_outputs, const uint8_t *n_classes,
+                                   const uint8_t *y, int32_t n_trees, const int32_t *sample_counts, const uint32_t *rand_state,
+                                   int32_t max_features, gecco_crf_forest **out) {
+    GECCO_GUARD_BEGIN
+    if (!out) {
+        set_error("gecco_crf_forest_fit: null out");
+        return GECCO_CRF_EINVAL;
+    }
+    *out = nullptr;
+    int rc = forest_fit_check(n_samples, n_features, col_ptr, row_idx, values, n_outputs, n_classes, y, n_trees, sample_counts,
+                              rand_state, max_features);
+    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
+    DeviceGuard guard;
+    Forest *f = nullptr;
+    if ((rc = forest_fit(device, n_samples, n_features, col_ptr, row_idx, values, n_outputs, n_classes, y, n_trees, sample_counts,
+                         rand_state, max_features, &f)))
+        return rc;
+    *out = new gecco_crf_forest{std::unique_ptr<Forest>(f)};
+    return GECCO_CRF_OK;
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_forest_info(const gecco_crf_forest *h, int32_t *n_trees, int32_t *n_outputs, int32_t *max_n_classes,
+                                    int32_t *node_count, int32_t *max_depth) {
+    if (!h || !h->f) {
+        set_error("gecco_crf_forest_info: null forest");
+        return GECCO_CRF_EINVAL;
+    }
+    const Forest &f = *h->f;
+    if (n_trees) *n_trees = f.n_trees;
+    if (n_outputs) *n_outputs = f.n_outputs;
+    if (max_n_classes) *max_n_classes = f.max_n_classes;
+    for (int32_t t = 0; t < f.n_trees; ++t) {
+        if (node_count) node_count[t] = f.node_count[size_t(t)];
+        if (max_depth) max_depth[t] = f.max_depth[size_t(t)];
+    }
+    return GECCO_CRF_OK;
+}
+
+GECCO_API int gecco_crf_forest_export(const gecco_crf_forest *h, int32_t tree, int32_t *children_left, int32_t *children_right,
+                                      int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                                      double *weighted_n_node_samples, double *value) {
+    GECCO_GUARD_BEGIN
+    if (!h || !h->f) {
+        set_error("gecco_crf_forest_export: null forest");
+        return GECCO_CRF_EINVAL;
+    }
+    DeviceGuard guard;
+    return forest_export(h->f.get(), tree, children_left, children_right, feature, threshold, impurity, n_node_samples,
+                         weighted_n_node_samples, value);
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_forest_predict(const gecco_crf_forest *h, int32_t n_rows, const double *x, double *posit) {
+    GECCO_GUARD_BEGIN
+    if (!h || !h->f) {
+        set_error("gecco_crf_forest_predict: null forest");
+        return GECCO_CRF_EINVAL;
+    }
+    if (n_rows < 0) {
+        set_error("gecco_crf_forest_predict: n_rows must be >= 0");
+        return GECCO_CRF_EINVAL;
+    }
+    if (n_rows == 0) return GECCO_CRF_OK;
+    DeviceGuard guard;
+    return forest_predict(h->f.get(), n_rows, x, posit);
+    GECCO_GUARD_END
+}
+
+GECCO_API void gecco_crf_forest_free(gecco_crf_forest *h) {
+    if (!h) return;
+    DeviceGuard guard;
+    delete h;
 }

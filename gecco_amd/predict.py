@@ -5,10 +5,11 @@ SURVEY.md §8f rank 1.  Mirrors the data flow of ``/root/reference/gecco/cli/com
 ``extract_clusters``, then the genes / features / clusters tables are written) but keeps
 everything in columns: FeatureTable/GeneTable columns -> CSR (``packing.pack_columns``) ->
 windowed marginals on the device -> cluster segmentation on the device
-(``gecco_crf_segment``) -> output columns.  Type classification (the ``type`` /
-``*_probability`` columns of clusters.tsv) is out of scope and written as ``Unknown``.
+(``gecco_crf_segment``) -> output columns.  Without ``--classify`` the ``type`` column of clusters.tsv is
+``Unknown``; with it the type classifier (``gecco_amd.types``: the random forest fitted and evaluated on the device) fills
+``type`` and the ``*_probability`` columns, like ``gecco predict`` does (cli/commands/predict.py:125-131).
 
-    python -m gecco_amd.predict --genes X.genes.tsv --features X.features.tsv --model DIR -o OUT
+    python -m gecco_amd.predict --genes X.genes.tsv --features X.features.tsv --model DIR -o OUT [--classify]
 """
 import argparse
 import math
@@ -179,10 +180,9 @@ def predict_tables(genes_t: tables.GeneTable, feats_t: tables.FeatureTable, crf:
         clusters_out = _cluster_table_slow(seg, reorder, p, pk, genes_t, feats_t, rows, contig_id)
     if composition_domains is None:
         return genes_out, feats_out, clusters_out
-    if reorder is not None:
-        raise NotImplementedError("compositions for tables whose refiner order differs from the scoring order")
     # input matrix of the type classifier (types/__init__.py:118), one row per called cluster
-    comps = composition.packed_compositions(seg, pk, feats_t.domain, feats_t.pvalue, composition_domains, device=dev)
+    comps = composition.packed_compositions(seg, pk, feats_t.domain, feats_t.pvalue, composition_domains, device=dev,
+                                            order=reorder)
     return genes_out, feats_out, clusters_out, comps
 
 
@@ -231,6 +231,9 @@ def main(argv: Optional[List[str]] = None) -> int:
                          "files bit for bit (the default whenever the model has 2 labels and a window of <= 32 items)")
     ap.add_argument("--fast-kernels", dest="reference_bits", action="store_false",
                     help="the reorganised arithmetic of the fast kernels: probabilities within a few ulps of the reference's")
+    ap.add_argument("--classify", action="store_true",
+                    help="predict cluster types with the type classifier of --model (domains.tsv, types.tsv, "
+                         "compositions.npz; GECCO's embedded data without --model) and write the type / *_probability columns")
     ap.add_argument("--composition-domains", default=None,
                     help="file with one domain accession per line (the type classifier's domains.tsv): also write "
                          "<base>.compositions.npy, the classifier's input matrix")
@@ -243,10 +246,26 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.composition_domains:
         with open(args.composition_domains) as fh:
             comp_domains = [line.strip() for line in fh if line.strip()]
-    res = predict_tables(
-        genes_t, feats_t, crf, pad=not args.no_pad, threshold=args.threshold, n_cds=args.cds,
-        edge_distance=args.edge_distance, trim=not args.no_trim, composition_domains=comp_domains, criterion=args.postproc)
+    classifier = None
+    if args.classify:
+        from .types import TypeClassifier
+
+        classifier = TypeClassifier.trained(args.model)
+    # (cli/commands/predict.py:130: a classifier with a single class predicts nothing)
+    type_domains = classifier.model.attributes_ if classifier is not None and len(classifier.classes_) > 1 else None
+    kw = dict(pad=not args.no_pad, threshold=args.threshold, n_cds=args.cds, edge_distance=args.edge_distance,
+              trim=not args.no_trim, criterion=args.postproc)
+    res = predict_tables(genes_t, feats_t, crf, composition_domains=comp_domains if comp_domains is not None else type_domains,
+                         **kw)
     genes_out, feats_out, clusters = res[:3]
+    if type_domains is not None:
+        from .types import classified_cluster_table
+
+        if comp_domains is None or list(comp_domains) == list(type_domains):
+            comps = res[3]
+        else:
+            comps = predict_tables(genes_t, feats_t, crf, composition_domains=type_domains, **kw)[3]
+        clusters = classified_cluster_table(clusters, classifier, comps)
     os.makedirs(args.output_dir, exist_ok=True)
     base = os.path.splitext(os.path.basename(args.genes))[0]
     base = base[:-len(".genes")] if base.endswith(".genes") else base

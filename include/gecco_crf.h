@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.6.0 = 260). */
+/* ABI version: major*100 + minor*10 + patch (2.7.0 = 270). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -501,6 +501,36 @@ int gecco_crf_domain_composition_members(int32_t device, const int32_t *member_p
                                          const int32_t *member_gene, const int32_t *dom_ptr, int32_t n_genes,
                                          const int32_t *dom_col, const double *dom_weight, int32_t n_cols,
                                          int32_t normalize, double *comp_out);
+
+/* ---- cluster type classifier (ABI 2.7.0): random forest fit and predict ---------------------------------------------
+ * What GECCO's TypeClassifier (gecco/types/__init__.py) asks sklearn.ensemble.RandomForestClassifier for: fit with
+ * criterion "gini", max_features = max_features, bootstrap, no depth limit, min_samples_split 2, min_samples_leaf 1, no
+ * class weights; every tree equals sklearn 1.7's node for node and bit for bit.  The caller draws the random streams as
+ * sklearn does: rand_state[t] = RandomState(seed_t).randint(0, 2^31 - 1) and sample_counts[t] = bincount of
+ * RandomState(seed_t).randint(0, n, n) for the per-tree seeds seed_t = RandomState(random_state).randint(2^31 - 1, n_trees).
+ * X: n_samples x n_features CSC float32 (col_ptr[n_features + 1], row_idx strictly increasing within a column, finite values;
+ * stored zeros count as zeros).  y[n_samples][n_outputs]: class index per output, n_classes[k] in {1, 2}.
+ * Range: n_samples <= 4096, n_features <= 8192, n_outputs <= 64, n_trees <= 65535 (GECCO_CRF_EINVAL before any device
+ * work otherwise).  Synchronous.  The forest lives on `device` until gecco_crf_forest_free. */
+typedef struct gecco_crf_forest gecco_crf_forest;
+int gecco_crf_forest_fit(int32_t device, int32_t n_samples, int32_t n_features, const int32_t *col_ptr, const int32_t *row_idx,
+                         const float *values, int32_t n_outputs, const uint8_t *n_classes, const uint8_t *y, int32_t n_trees,
+                         const int32_t *sample_counts, const uint32_t *rand_state, int32_t max_features,
+                         gecco_crf_forest **out);
+/* n_trees, n_outputs, max_n_classes (2 if any output has 2 classes, else 1); node_count / max_depth: [n_trees] (may be
+ * NULL). */
+int gecco_crf_forest_info(const gecco_crf_forest *f, int32_t *n_trees, int32_t *n_outputs, int32_t *max_n_classes,
+                          int32_t *node_count, int32_t *max_depth);
+/* Tree `tree` as sklearn's Tree arrays, node_count entries each (value: node_count x n_outputs x max_n_classes); any
+ * pointer may be NULL. */
+int gecco_crf_forest_export(const gecco_crf_forest *f, int32_t tree, int32_t *children_left, int32_t *children_right,
+                            int32_t *feature, double *threshold, double *impurity, int32_t *n_node_samples,
+                            double *weighted_n_node_samples, double *value);
+/* posit[n_rows][n_outputs] = 1 - predict_proba(x)[k][:, 0]: rows rounded to float32, leaf values normalised per tree,
+ * summed in tree order in fp64 and divided by n_trees.  x: n_rows x n_features row-major fp64 (host).  n_rows = 0 is valid
+ * and touches no device.  Synchronous. */
+int gecco_crf_forest_predict(const gecco_crf_forest *f, int32_t n_rows, const double *x, double *posit);
+void gecco_crf_forest_free(gecco_crf_forest *f);
 
 #ifdef __cplusplus
 }
