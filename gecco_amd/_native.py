@@ -179,6 +179,17 @@ SIGNATURES = {
     "gecco_crf_trainer_batch_num_problems": (ctypes.c_int32, [_vp]),
     "gecco_crf_trainer_batch_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_batch_free": (None, [_vp]),
+    "gecco_crf_trainer_grid_create": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, _c_i32p, _c_i32p,
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.c_int32, _c_i32p, ctypes.c_int64,
+                       ctypes.POINTER(_vp)]
+    ),
+    "gecco_crf_trainer_grid_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _c_f64p, ctypes.POINTER(_vp)]),
+    "gecco_crf_trainer_grid_num_problems": (ctypes.c_int32, [_vp]),
+    "gecco_crf_trainer_grid_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_grid_scratch_bytes": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_grid_free": (None, [_vp]),
     "gecco_crf_fisher_exact": (ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
     "gecco_crf_cluster_overlaps": (
         ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1271,8 +1282,74 @@ class TrainerBatch:
             wk.append(w)
             gk.append(gb)
             w_ptr[k], g_ptr[k] = w.ctypes.data, gb.ctypes.data
-        _check(self._lib.gecco_crf_trainer_batch_eval(self._h, _ptr(act, _c_u8p), w_ptr, _ptr(f, _c_f64p), g_ptr))
+        _check(self._eval_native(_ptr(act, _c_u8p), w_ptr, _ptr(f, _c_f64p), g_ptr))
         return f, g
+
+    def _eval_native(self, act, w_ptr, f, g_ptr):
+        return self._lib.gecco_crf_trainer_batch_eval(self._h, act, w_ptr, f, g_ptr)
+
+
+class TrainerGrid(TrainerBatch):
+    """A grid of problems over shared training sets on one device (``gecco_crf_trainer_grid_*``).
+
+    ``sets`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features,
+    window, step)`` per training set, each uploaded once; problem k is set ``problem_set[k]`` with weights of its own.
+    ``scratch_budget_bytes`` caps the work space of one group of problems (0: no cap).  ``eval`` is ``TrainerBatch``'s;
+    problem k's f and g are bitwise what a lone ``Trainer`` of its set returns for ``ws[k]``."""
+
+    def __init__(self, sets, problem_set, scratch_budget_bytes: int = 0, device: int = 0):
+        self._lib = load_library()
+        self._h = None
+        n = len(sets)
+        arrays = {name: [] for name in ("seq_ptr", "item_ptr", "attr_id", "labels", "state_fid", "trans_fid")}
+        n_seqs, num_attrs, num_labels, num_features, windows, steps = [], [], [], [], [], []
+        for seq_ptr, item_ptr, attr_id, labels, A, state_fid, trans_fid, K, window, step in sets:
+            state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
+            if int(A) < 1 or state_fid.size % int(A) != 0:
+                raise ValueError("state_fid must have num_attrs * L entries")
+            L = state_fid.size // int(A)
+            if trans_fid.size != L * L:
+                raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
+            seq_ptr = _i32(seq_ptr)
+            for name, a in zip(arrays, (seq_ptr, _i32(item_ptr), _i32(attr_id), _i32(labels), state_fid, trans_fid)):
+                arrays[name].append(a if a.size else np.zeros(1, dtype=np.int32))
+            n_seqs.append(len(seq_ptr) - 1)
+            num_attrs.append(int(A))
+            num_labels.append(L)
+            num_features.append(int(K))
+            windows.append(int(window))
+            steps.append(int(step))
+        pset = _i32(problem_set).ravel()
+        ptrs = {name: (_vp * max(n, 1))(*[a.ctypes.data for a in arrs]) for name, arrs in arrays.items()}
+        ints = [np.ascontiguousarray(v if v else [0], dtype=np.int32)
+                for v in (n_seqs, num_attrs, num_labels, num_features, windows, steps)]
+        pset_c = pset if pset.size else np.zeros(1, dtype=np.int32)
+        h = _vp()
+        _check(self._lib.gecco_crf_trainer_grid_create(
+            int(device), n, ptrs["seq_ptr"], _ptr(ints[0], _c_i32p), ptrs["item_ptr"], ptrs["attr_id"], ptrs["labels"],
+            _ptr(ints[1], _c_i32p), _ptr(ints[2], _c_i32p), _ptr(ints[4], _c_i32p), _ptr(ints[5], _c_i32p),
+            ptrs["state_fid"], ptrs["trans_fid"], _ptr(ints[3], _c_i32p), int(pset.size), _ptr(pset_c, _c_i32p),
+            int(scratch_budget_bytes), ctypes.byref(h)))
+        self._h = h
+        self.num_features = [num_features[s] for s in pset.tolist()]
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.gecco_crf_trainer_grid_free(h)
+
+    def __len__(self) -> int:
+        return int(self._lib.gecco_crf_trainer_grid_num_problems(self._h))
+
+    def num_windows(self, k: int) -> int:
+        return int(self._lib.gecco_crf_trainer_grid_num_windows(self._h, int(k)))
+
+    def scratch_bytes(self, k: int = -1) -> int:
+        """Scratch bytes of problem k; for k = -1 the work space allocated (the most one group of problems uses)."""
+        return int(self._lib.gecco_crf_trainer_grid_scratch_bytes(self._h, int(k)))
+
+    def _eval_native(self, act, w_ptr, f, g_ptr):
+        return self._lib.gecco_crf_trainer_grid_eval(self._h, act, w_ptr, f, g_ptr)
 
 
 def fisher_exact(tables, device: int = 0) -> np.ndarray:

@@ -95,7 +95,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 270; }
+GECCO_API int gecco_crf_version(void) { return 280; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -998,6 +998,59 @@ GECCO_API int64_t gecco_crf_trainer_batch_num_windows(const gecco_crf_trainer_ba
 }
 
 GECCO_API void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t) {
+    if (!t) return;
+    DeviceGuard guard;
+    delete t;
+}
+
+// ---- training, a grid of problems over shared sets (ABI 2.8.0) ---------------------------------
+struct gecco_crf_trainer_grid {
+    Trainer *t = nullptr;
+    ~gecco_crf_trainer_grid() { trainer_destroy(t); }
+};
+
+GECCO_API int gecco_crf_trainer_grid_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                                            const int32_t *const *item_ptr, const int32_t *const *attr_id,
+                                            const int32_t *const *labels, const int32_t *num_attrs, const int32_t *num_labels,
+                                            const int32_t *window, const int32_t *step, const int32_t *const *state_fid,
+                                            const int32_t *const *trans_fid, const int32_t *num_features, int32_t n_problems,
+                                            const int32_t *problem_set, int64_t scratch_budget_bytes,
+                                            gecco_crf_trainer_grid **out) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    auto h = std::make_unique<gecco_crf_trainer_grid>();
+    int rc = trainer_grid_create(device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
+                                 state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes, &h->t);
+    if (rc) return rc;
+    *out = h.release();
+    return GECCO_CRF_OK;
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_trainer_grid_eval(gecco_crf_trainer_grid *t, const uint8_t *active, const double *const *w, double *f,
+                                          double *const *g) {
+    if (!t) return GECCO_CRF_EINVAL;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    return trainer_batch_eval(t->t, active, w, f, g);
+    GECCO_GUARD_END
+}
+
+GECCO_API int32_t gecco_crf_trainer_grid_num_problems(const gecco_crf_trainer_grid *t) {
+    return t ? trainer_num_problems(t->t) : -1;
+}
+
+GECCO_API int64_t gecco_crf_trainer_grid_num_windows(const gecco_crf_trainer_grid *t, int32_t k) {
+    return t ? trainer_num_windows(t->t, k) : -1;
+}
+
+GECCO_API int64_t gecco_crf_trainer_grid_scratch_bytes(const gecco_crf_trainer_grid *t, int32_t k) {
+    return t ? trainer_scratch_bytes(t->t, k) : -1;
+}
+
+GECCO_API void gecco_crf_trainer_grid_free(gecco_crf_trainer_grid *t) {
     if (!t) return;
     DeviceGuard guard;
     delete t;

@@ -50,30 +50,56 @@ struct TransArgs {
     int log_space;              // 1 when an exp(t - tmax) is not a normal number: every window goes to log space
 };
 
-// Where one problem of the batch lives in the concatenated device arrays (uploaded once).  Every array of a problem is
-// exactly what a lone trainer of it would hold: indices inside it (item_ptr, win_start, iw_first, attr_ptr, attr_items)
-// are local to the problem.
-struct ProbDev {
-    int64_t item0;  // items: score, label, iw_first/cnt/off, item_marg
+constexpr int kTrainSetProbs = 8;        // problems of one set whose item scores one thread forms from one read
+
+// One training set as the device holds it (uploaded once).  Indices inside it (item_ptr, win_start, iw_first, attr_ptr,
+// attr_items) are local to the set: exactly what a lone trainer of it holds.  Every problem on the set reads these.
+struct SetDev {
+    int64_t item0;  // items: label, iw_first/cnt/off
     int64_t iptr0;  // item_ptr (n_items + 1 entries)
     int64_t nnz0;   // attr_id, attr_items
-    int64_t win0;   // windows: win_start, rows; node marginals from win0 * W
+    int64_t win0;   // win_start
     int64_t aptr0;  // attr_ptr (A + 1 entries)
-    int64_t ws0;    // state weights in the upload ([A][2] doubles)
-    int64_t out0;   // outputs in the download: 5 row sums, then the expected state counts [A][2]
     int64_t n_win;
-    int32_t n_items, A;
+    int32_t n_items, A, W, step;
 };
 
-// One problem of one evaluation (uploaded with the weights): its transitions and the first block it owns in the
-// item grid (kernels 1, 3), the window grid (2) and the attribute grid (4).  Kernels 5 and 6 give every slot 256 and 1
-// blocks.  Only active problems with windows get a slot, so every slot owns at least one block of every grid.
+// One problem of one evaluation group (uploaded with the weights): its set, transitions, state weights, scratch and
+// outputs, and the first block it owns in the window grid (kernel 2) and the attribute grid (4).  Kernels 5 and 6 give
+// every slot 256 and 1 blocks.  Only active problems with windows get a slot, so every slot owns at least one block of
+// every grid.
 struct Slot {
     TransArgs T;
-    int32_t prob;
-    int32_t blk[3];
+    int64_t ws0;   // state weights in the upload ([A][2] doubles)
+    int64_t sc0;   // scratch, in bytes (16-aligned): see scratch_bytes
+    int64_t out0;  // outputs in the download: 5 row sums, then the expected state counts [A][2]
+    int32_t set;
+    int32_t blk[2];
 };
-enum { kGridItems = 0, kGridWindows = 1, kGridAttrs = 2 };
+enum { kGridWindows = 0, kGridAttrs = 1 };
+
+// Kernels 1 and 3 cover the items of one set for up to kTrainSetProbs of its problems (slot indices in the group).
+struct ItemGroup {
+    int32_t set, n, blk;
+    int32_t slot[kTrainSetProbs];
+};
+
+// A problem's scratch: item scores [n_items], item marginals [n_items], node marginals [n_win][W], rows [n_win][5].
+__host__ __device__ __forceinline__ int64_t scratch_bytes(int64_t n_items, int64_t n_win, int32_t W) {
+    return (32 * n_items + 16 * n_win * W + 8 * kTrainRowCols * n_win + 15) / 16 * 16;
+}
+__device__ __forceinline__ double2 *scratch_score(unsigned char *sc, const Slot &sl) {
+    return reinterpret_cast<double2 *>(sc + sl.sc0);
+}
+__device__ __forceinline__ double2 *scratch_item_marg(unsigned char *sc, const Slot &sl, const SetDev &S) {
+    return scratch_score(sc, sl) + S.n_items;
+}
+__device__ __forceinline__ double2 *scratch_marg(unsigned char *sc, const Slot &sl, const SetDev &S) {
+    return scratch_score(sc, sl) + 2 * static_cast<int64_t>(S.n_items);
+}
+__device__ __forceinline__ double *scratch_rows(unsigned char *sc, const Slot &sl, const SetDev &S) {
+    return reinterpret_cast<double *>(scratch_marg(sc, sl, S) + S.n_win * S.W);
+}
 
 // The slot that owns this block of grid G: the last slot whose first block is at or before it (slots ascend).
 template <int G>
@@ -88,26 +114,55 @@ __device__ __forceinline__ int slot_of(const Slot *__restrict__ slots, int n_slo
     return lo;
 }
 
-__global__ void __launch_bounds__(kTrainThreads) train_item_scores(const Slot *__restrict__ slots, int n_slots,
-                                                                   const ProbDev *__restrict__ probs,
+// The same for the item grid of kernels 1 and 3.
+__device__ __forceinline__ int item_group_of(const ItemGroup *__restrict__ igs, int n_igs) {
+    const int32_t b = static_cast<int32_t>(blockIdx.x);
+    int lo = 0, hi = n_igs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (igs[mid].blk <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// One thread per item of a set: the item's attribute ids are read once, and each problem of the item group (at most
+// NP) sums its own state weights over them in CSR order, as a lone trainer does.
+template <int NP>
+__global__ void __launch_bounds__(kTrainThreads) train_item_scores(const ItemGroup *__restrict__ igs, int n_igs,
+                                                                   const Slot *__restrict__ slots,
+                                                                   const SetDev *__restrict__ sets,
                                                                    const int32_t *__restrict__ item_ptr_all,
                                                                    const int32_t *__restrict__ attr_id_all,
                                                                    const double *__restrict__ wstate_all,
-                                                                   double2 *__restrict__ score_all) {
-    const Slot &sl = slots[slot_of<kGridItems>(slots, n_slots)];
-    const ProbDev &P = probs[sl.prob];
-    const int32_t i = (static_cast<int32_t>(blockIdx.x) - sl.blk[kGridItems]) * blockDim.x + threadIdx.x;
-    if (i >= P.n_items) return;
-    const int32_t *__restrict__ item_ptr = item_ptr_all + P.iptr0;
-    const int32_t *__restrict__ attr_id = attr_id_all + P.nnz0;
-    const double *__restrict__ wstate = wstate_all + P.ws0;
-    double s0 = 0.0, s1 = 0.0;
+                                                                   unsigned char *__restrict__ scratch) {
+    const ItemGroup &ig = igs[item_group_of(igs, n_igs)];
+    const SetDev &S = sets[ig.set];
+    const int32_t i = (static_cast<int32_t>(blockIdx.x) - ig.blk) * blockDim.x + threadIdx.x;
+    if (i >= S.n_items) return;
+    const int n = ig.n;
+    const int32_t *__restrict__ item_ptr = item_ptr_all + S.iptr0;
+    const int32_t *__restrict__ attr_id = attr_id_all + S.nnz0;
+    const double *wstate[NP];
+    double s0[NP], s1[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        wstate[j] = wstate_all + slots[ig.slot[j < n ? j : 0]].ws0;
+        s0[j] = 0.0;
+        s1[j] = 0.0;
+    }
     for (int32_t k = item_ptr[i]; k < item_ptr[i + 1]; ++k) {
         const int32_t a = attr_id[k];
-        s0 += wstate[2 * a];
-        s1 += wstate[2 * a + 1];
+#pragma unroll
+        for (int j = 0; j < NP; ++j)
+            if (j < n) {
+                s0[j] += wstate[j][2 * a];
+                s1[j] += wstate[j][2 * a + 1];
+            }
     }
-    score_all[P.item0 + i] = make_double2(s0, s1);
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+        if (j < n) scratch_score(scratch, slots[ig.slot[j]])[i] = make_double2(s0[j], s1[j]);
 }
 
 // Natural log of exp(a) + exp(b), fp64, for the log-space recomputation of a flagged window.
@@ -171,26 +226,27 @@ __device__ __forceinline__ void train_window_logspace(const double2 *__restrict_
 // transition E is not normal (T.log_space), is recomputed in log space by the same thread (train_window_logspace);
 // nothing changes for the other windows.
 // (waves_per_eu(6): keeps the VGPR count, and so the occupancy, of the kernel without the log-space branch.)
-// The transitions (and the log-space flag) are the problem's own, read from its slot.
+// The transitions (and the log-space flag) are the problem's own, read from its slot; W is its set's.  The LDS holds
+// lds_w >= W steps (the largest W of the group).
 __global__ void __launch_bounds__(kTrainWinThreads) __attribute__((amdgpu_waves_per_eu(6)))
-train_windows(const Slot *__restrict__ slots, int n_slots, const ProbDev *__restrict__ probs,
-              const double2 *__restrict__ score_all, const int32_t *__restrict__ label_all,
-              const int32_t *__restrict__ win_start_all, int32_t W, double2 *__restrict__ marg_all,
-              double *__restrict__ rows_all) {
+train_windows(const Slot *__restrict__ slots, int n_slots, const SetDev *__restrict__ sets,
+              const int32_t *__restrict__ label_all, const int32_t *__restrict__ win_start_all, int32_t lds_w,
+              unsigned char *__restrict__ scratch) {
     extern __shared__ double lds[];
-    double2 *alpha = reinterpret_cast<double2 *>(lds);                 // [W][kTrainWinThreads]
-    double *cnorm = lds + 2 * static_cast<size_t>(W) * kTrainWinThreads;  // [W][kTrainWinThreads]
+    double2 *alpha = reinterpret_cast<double2 *>(lds);                        // [W][kTrainWinThreads]
+    double *cnorm = lds + 2 * static_cast<size_t>(lds_w) * kTrainWinThreads;  // [W][kTrainWinThreads]
     const Slot &sl = slots[slot_of<kGridWindows>(slots, n_slots)];
-    const ProbDev &P = probs[sl.prob];
+    const SetDev &S = sets[sl.set];
     const int lane = threadIdx.x;
     const int64_t w = static_cast<int64_t>(static_cast<int32_t>(blockIdx.x) - sl.blk[kGridWindows]) * kTrainWinThreads + lane;
-    if (w >= P.n_win) return;
+    if (w >= S.n_win) return;
+    const int32_t W = S.W;
     const TransArgs T = sl.T;
-    const double2 *__restrict__ score = score_all + P.item0;
-    const int32_t *__restrict__ label = label_all + P.item0;
-    const int32_t *__restrict__ win_start = win_start_all + P.win0;
-    double2 *__restrict__ marg = marg_all + P.win0 * W;
-    double *__restrict__ rows = rows_all + P.win0 * kTrainRowCols;
+    const double2 *__restrict__ score = scratch_score(scratch, sl);
+    const int32_t *__restrict__ label = label_all + S.item0;
+    const int32_t *__restrict__ win_start = win_start_all + S.win0;
+    double2 *__restrict__ marg = scratch_marg(scratch, sl, S);
+    double *__restrict__ rows = scratch_rows(scratch, sl, S);
     const int64_t i0 = win_start[w];
 
     double2 s = score[i0];
@@ -256,29 +312,35 @@ train_windows(const Slot *__restrict__ slots, int n_slots, const ProbDev *__rest
     r[0] = logz - gold;
 }
 
-// Item i is covered by the windows first .. first + cnt - 1, at position off, off - step, ... in them.
-__global__ void __launch_bounds__(kTrainThreads) train_item_marginals(const Slot *__restrict__ slots, int n_slots,
-                                                                      const ProbDev *__restrict__ probs,
-                                                                      const double2 *__restrict__ marg_all,
+// Item i is covered by the windows first .. first + cnt - 1, at position off, off - step, ... in them.  The coverage is
+// read once for the item group; each problem sums its own node marginals in window order.
+__global__ void __launch_bounds__(kTrainThreads) train_item_marginals(const ItemGroup *__restrict__ igs, int n_igs,
+                                                                      const Slot *__restrict__ slots,
+                                                                      const SetDev *__restrict__ sets,
                                                                       const int32_t *__restrict__ iw_first_all,
                                                                       const int32_t *__restrict__ iw_cnt_all,
-                                                                      const int32_t *__restrict__ iw_off_all, int32_t W,
-                                                                      int32_t step, double2 *__restrict__ item_marg_all) {
-    const Slot &sl = slots[slot_of<kGridItems>(slots, n_slots)];
-    const ProbDev &P = probs[sl.prob];
-    const int32_t i = (static_cast<int32_t>(blockIdx.x) - sl.blk[kGridItems]) * blockDim.x + threadIdx.x;
-    if (i >= P.n_items) return;
-    const double2 *__restrict__ marg = marg_all + P.win0 * W;
-    const int64_t first = iw_first_all[P.item0 + i];
-    const int32_t cnt = iw_cnt_all[P.item0 + i];
-    int32_t off = iw_off_all[P.item0 + i];
-    double p0 = 0.0, p1 = 0.0;
-    for (int32_t k = 0; k < cnt; ++k, off -= step) {
-        const double2 v = marg[(first + k) * W + off];
-        p0 += v.x;
-        p1 += v.y;
+                                                                      const int32_t *__restrict__ iw_off_all,
+                                                                      unsigned char *__restrict__ scratch) {
+    const ItemGroup &ig = igs[item_group_of(igs, n_igs)];
+    const SetDev &S = sets[ig.set];
+    const int32_t i = (static_cast<int32_t>(blockIdx.x) - ig.blk) * blockDim.x + threadIdx.x;
+    if (i >= S.n_items) return;
+    const int32_t W = S.W, step = S.step;
+    const int64_t first = iw_first_all[S.item0 + i];
+    const int32_t cnt = iw_cnt_all[S.item0 + i];
+    const int32_t off0 = iw_off_all[S.item0 + i];
+    for (int j = 0; j < ig.n; ++j) {
+        const Slot &sl = slots[ig.slot[j]];
+        const double2 *__restrict__ marg = scratch_marg(scratch, sl, S);
+        int32_t off = off0;
+        double p0 = 0.0, p1 = 0.0;
+        for (int32_t k = 0; k < cnt; ++k, off -= step) {
+            const double2 v = marg[(first + k) * W + off];
+            p0 += v.x;
+            p1 += v.y;
+        }
+        scratch_item_marg(scratch, sl, S)[i] = make_double2(p0, p1);
     }
-    item_marg_all[P.item0 + i] = make_double2(p0, p1);
 }
 
 template <int NT>
@@ -297,19 +359,19 @@ __device__ __forceinline__ double2 block_sum2(double2 v, double2 *sh) {
 
 // Expected state counts: one workgroup per attribute, thread j sums the items j, j + NT, ... of its list, then a tree.
 __global__ void __launch_bounds__(kTrainThreads) train_attr_counts(const Slot *__restrict__ slots, int n_slots,
-                                                                   const ProbDev *__restrict__ probs,
+                                                                   const SetDev *__restrict__ sets,
                                                                    const int32_t *__restrict__ attr_ptr_all,
                                                                    const int32_t *__restrict__ attr_items_all,
-                                                                   const double2 *__restrict__ item_marg_all,
+                                                                   unsigned char *__restrict__ scratch,
                                                                    double *__restrict__ out_all) {
     __shared__ double2 sh[kTrainThreads];
     const Slot &sl = slots[slot_of<kGridAttrs>(slots, n_slots)];
-    const ProbDev &P = probs[sl.prob];
+    const SetDev &S = sets[sl.set];
     const int32_t a = static_cast<int32_t>(blockIdx.x) - sl.blk[kGridAttrs];
-    if (a >= P.A) return;
-    const int32_t *__restrict__ attr_ptr = attr_ptr_all + P.aptr0;
-    const int32_t *__restrict__ attr_items = attr_items_all + P.nnz0;
-    const double2 *__restrict__ item_marg = item_marg_all + P.item0;
+    if (a >= S.A) return;
+    const int32_t *__restrict__ attr_ptr = attr_ptr_all + S.aptr0;
+    const int32_t *__restrict__ attr_items = attr_items_all + S.nnz0;
+    const double2 *__restrict__ item_marg = scratch_item_marg(scratch, sl, S);
     double2 acc = make_double2(0.0, 0.0);
     for (int32_t k = attr_ptr[a] + threadIdx.x; k < attr_ptr[a + 1]; k += kTrainThreads) {
         const double2 v = item_marg[attr_items[k]];
@@ -318,7 +380,7 @@ __global__ void __launch_bounds__(kTrainThreads) train_attr_counts(const Slot *_
     }
     const double2 tot = block_sum2<kTrainThreads>(acc, sh);
     if (threadIdx.x == 0) {
-        double *expected = out_all + P.out0 + kTrainRowCols;
+        double *expected = out_all + sl.out0 + kTrainRowCols;
         expected[2 * a] = tot.x;
         expected[2 * a + 1] = tot.y;
     }
@@ -327,14 +389,15 @@ __global__ void __launch_bounds__(kTrainThreads) train_attr_counts(const Slot *_
 // Row sums, stage 1: slot s owns the blocks [s * kTrainReduceBlocks, (s + 1) * kTrainReduceBlocks); its slab b = rows
 // [b * chunk, (b + 1) * chunk) of its problem, chunk = ceil(n_win / kTrainReduceBlocks).
 __global__ void __launch_bounds__(kTrainThreads) train_reduce_rows(const Slot *__restrict__ slots,
-                                                                   const ProbDev *__restrict__ probs,
-                                                                   const double *__restrict__ rows_all,
+                                                                   const SetDev *__restrict__ sets,
+                                                                   unsigned char *__restrict__ scratch,
                                                                    double *__restrict__ partial_all) {
     __shared__ double sh[kTrainRowCols][kTrainThreads];
     const int s = blockIdx.x / kTrainReduceBlocks, b = blockIdx.x % kTrainReduceBlocks;
-    const ProbDev &P = probs[slots[s].prob];
-    const double *__restrict__ rows = rows_all + P.win0 * kTrainRowCols;
-    const int64_t n = P.n_win;
+    const Slot &sl = slots[s];
+    const SetDev &S = sets[sl.set];
+    const double *__restrict__ rows = scratch_rows(scratch, sl, S);
+    const int64_t n = S.n_win;
     const int64_t chunk = (n + kTrainReduceBlocks - 1) / kTrainReduceBlocks;
     const int64_t lo = b * chunk, hi = std::min(n, lo + chunk);
     double acc[kTrainRowCols] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -352,7 +415,6 @@ __global__ void __launch_bounds__(kTrainThreads) train_reduce_rows(const Slot *_
 
 // Stage 2: one workgroup per slot, thread j holds slab j, then a tree.
 __global__ void __launch_bounds__(kTrainReduceBlocks) train_reduce_final(const Slot *__restrict__ slots,
-                                                                         const ProbDev *__restrict__ probs,
                                                                          const double *__restrict__ partial_all,
                                                                          double *__restrict__ out_all) {
     __shared__ double sh[kTrainRowCols][kTrainReduceBlocks];
@@ -364,7 +426,7 @@ __global__ void __launch_bounds__(kTrainReduceBlocks) train_reduce_final(const S
             for (int k = 0; k < kTrainRowCols; ++k) sh[k][threadIdx.x] += sh[k][threadIdx.x + h];
         __syncthreads();
     }
-    if (threadIdx.x < kTrainRowCols) out_all[probs[slots[blockIdx.x].prob].out0 + threadIdx.x] = sh[threadIdx.x][0];
+    if (threadIdx.x < kTrainRowCols) out_all[slots[blockIdx.x].out0 + threadIdx.x] = sh[threadIdx.x][0];
 }
 
 template <class T>
@@ -512,46 +574,54 @@ void append(std::vector<T> &dst, const std::vector<T> &src) {
     dst.insert(dst.end(), src.begin(), src.end());
 }
 
-static_assert(sizeof(Slot) % alignof(double) == 0, "the state weights follow the slots in the upload");
+static_assert(sizeof(Slot) % alignof(double) == 0 && sizeof(ItemGroup) % alignof(int32_t) == 0, "upload layout");
+
+enum Kind { kLone, kBatch, kGrid };
 
 }  // namespace
 
-// K problems resident on one device; a lone trainer is the case K = 1.  Each problem's arrays are concatenated into
-// one device array per kind (ProbDev has the offsets).  Per evaluation, one upload carries the slots of the active
-// problems and the state weights ([Slot][P] then the weights), one download brings back the row sums and expected
-// counts of the span of problems from the first active one to the last.
+// Training sets and problems resident on one device.  A set is a training set, uploaded once (every set's arrays
+// concatenated into one device array per kind, SetDev has the offsets); a problem is a set with its own weights,
+// scratch and outputs.  A lone trainer is one set with one problem, a batch K sets with problem k on set k.
+// Per evaluation, the active problems are cut, in order, into groups whose scratch fits the work space; one upload
+// carries every group's slots and item groups and the active problems' state weights, every group runs the six
+// kernels, and one download brings back the row sums and expected counts of the span of problems from the first active
+// one to the last.
 struct Trainer {
     int device = 0;
-    int32_t W = 0, step = 1;
-    struct Meta {
-        int32_t A, n_items, K;
+    Kind kind = kLone;
+    struct Set {
+        int32_t A, n_items, K, W;
         int64_t n_win;
         std::vector<int32_t> state_fid, trans_fid;
         std::vector<double> empirical;
     };
-    std::vector<Meta> probs;
-    std::vector<ProbDev> layout;
-    size_t slots_bytes = 0;
+    struct Prob {
+        int32_t set;
+        int64_t ws0, out0, scratch;  // state weights in the upload, outputs in the download, scratch bytes
+    };
+    std::vector<Set> sets;
+    std::vector<Prob> probs;
+    size_t igs_off = 0, ws_off = 0;  // upload: [Slot][ItemGroup] (at most one of each per problem), then the weights
+    int64_t scratch_cap = 0;         // bytes of d_scratch: the most one group may use
     std::vector<unsigned char> h_in;  // host staging of the upload
     std::vector<double> h_out;        // host staging of the download
     hipStream_t stream = nullptr;
     // device: training sets (uploaded once) and per-evaluation work space
-    ProbDev *d_probs = nullptr;
+    SetDev *d_sets = nullptr;
     int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr;
     int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr;
     int32_t *d_attr_ptr = nullptr, *d_attr_items = nullptr;
-    unsigned char *d_in = nullptr;
-    double *d_out = nullptr, *d_rows = nullptr, *d_partial = nullptr;
-    double2 *d_score = nullptr, *d_marg = nullptr, *d_item_marg = nullptr;
+    unsigned char *d_in = nullptr, *d_scratch = nullptr;
+    double *d_out = nullptr, *d_partial = nullptr;
 
     ~Trainer() {
         int prev = -1;
         const bool restore = hipGetDevice(&prev) == hipSuccess && prev != device;
         (void)hipSetDevice(device);
-        for (void *p : {(void *)d_probs, (void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start,
+        for (void *p : {(void *)d_sets, (void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start,
                         (void *)d_iw_first, (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items,
-                        (void *)d_in, (void *)d_out, (void *)d_rows, (void *)d_partial, (void *)d_score, (void *)d_marg,
-                        (void *)d_item_marg})
+                        (void *)d_in, (void *)d_scratch, (void *)d_out, (void *)d_partial})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
         if (restore && prev >= 0) (void)hipSetDevice(prev);
@@ -560,42 +630,41 @@ struct Trainer {
 
 namespace {
 
-// `batch`: errors name the problem ("problem k: ..."); a lone trainer keeps its own messages.
-int create_impl(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+int64_t blocks_of(int64_t n, int per) { return (n + per - 1) / per; }
+
+// Sets as build_problem takes them, problem k on set problem_set[k] (NULL: set k).  Errors of a batch name the problem
+// ("problem k: ..."), those of a grid the set or problem; a lone trainer keeps its own messages.  scratch_budget <= 0
+// (and every lone trainer or batch): all problems fit in one group.
+int create_impl(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                 const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
-                const int32_t *num_attrs, const int32_t *num_labels, int32_t window, int32_t step,
-                const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features, bool batch,
-                Trainer **out) {
+                const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget, Kind kind, Trainer **out) {
     auto t = std::make_unique<Trainer>();
     t->device = device;
-    t->W = window;
-    t->step = step;
+    t->kind = kind;
     std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c, attr_items_c;
-    int64_t ws_total = 0, out_total = 0, blocks[3] = {0, 0, 0};
-    for (int32_t k = 0; k < n_problems; ++k) {
+    std::vector<SetDev> layout;
+    for (int32_t k = 0; k < n_sets; ++k) {
         HostProblem hp;
         int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
-                               window, step, state_fid[k], trans_fid[k], num_features[k], &hp);
+                               window[k], step[k], state_fid[k], trans_fid[k], num_features[k], &hp);
         if (rc) {
-            if (batch) set_error("trainer batch: problem " + std::to_string(k) + ": " + last_error());
+            if (kind == kBatch) set_error("trainer batch: problem " + std::to_string(k) + ": " + last_error());
+            if (kind == kGrid) set_error("trainer grid: set " + std::to_string(k) + ": " + last_error());
             return rc;
         }
-        ProbDev d;
+        SetDev d;
         d.item0 = int64_t(label_c.size());
         d.iptr0 = int64_t(item_ptr_c.size());
         d.nnz0 = int64_t(attr_id_c.size());
         d.win0 = int64_t(win_start_c.size());
         d.aptr0 = int64_t(attr_ptr_c.size());
-        d.ws0 = ws_total;
-        d.out0 = out_total;
         d.n_win = hp.n_win;
         d.n_items = hp.n_items;
         d.A = hp.A;
-        ws_total += int64_t(hp.A) * 2;
-        out_total += kTrainRowCols + int64_t(hp.A) * 2;
-        blocks[kGridItems] += (hp.n_items + kTrainThreads - 1) / kTrainThreads;
-        blocks[kGridWindows] += (hp.n_win + kTrainWinThreads - 1) / kTrainWinThreads;
-        blocks[kGridAttrs] += hp.A;
+        d.W = window[k];
+        d.step = step[k];
         append(item_ptr_c, hp.item_ptr);
         append(attr_id_c, hp.attr_id);
         append(label_c, hp.label);
@@ -605,12 +674,32 @@ int create_impl(int32_t device, int32_t n_problems, const int32_t *const *seq_pt
         append(iw_off_c, hp.iw_off);
         append(attr_ptr_c, hp.attr_ptr);
         append(attr_items_c, hp.attr_items);
-        t->layout.push_back(d);
-        t->probs.push_back({hp.A, hp.n_items, hp.K, hp.n_win, std::move(hp.state_fid), std::move(hp.trans_fid),
-                            std::move(hp.empirical)});
+        layout.push_back(d);
+        t->sets.push_back({hp.A, hp.n_items, hp.K, window[k], hp.n_win, std::move(hp.state_fid), std::move(hp.trans_fid),
+                           std::move(hp.empirical)});
     }
-    for (int64_t b : blocks)
-        if (b > INT32_MAX) return fail("trainer batch: the problems need more than 2^31 workgroups in one launch");
+    int64_t ws_total = 0, out_total = 0, scratch_total = 0, scratch_max = 0, blocks[3] = {0, 0, 0};
+    for (int32_t k = 0; k < n_problems; ++k) {
+        const int32_t s = problem_set ? problem_set[k] : k;
+        if (s < 0 || s >= n_sets)
+            return fail("trainer grid: problem " + std::to_string(k) + ": set " + std::to_string(s) + " out of range");
+        const Trainer::Set &S = t->sets[size_t(s)];
+        const int64_t sc = scratch_bytes(S.n_items, S.n_win, S.W);
+        t->probs.push_back({s, ws_total, out_total, sc});
+        ws_total += int64_t(S.A) * 2;
+        out_total += kTrainRowCols + int64_t(S.A) * 2;
+        scratch_total += sc;
+        scratch_max = std::max(scratch_max, sc);
+        blocks[0] += blocks_of(S.n_items, kTrainThreads);
+        blocks[1] += blocks_of(S.n_win, kTrainWinThreads);
+        blocks[2] += S.A;
+    }
+    // (a grid cuts its groups at 2^31 workgroups instead)
+    if (kind != kGrid)
+        for (int64_t b : blocks)
+            if (b > INT32_MAX) return fail("trainer batch: the problems need more than 2^31 workgroups in one launch");
+    t->scratch_cap = scratch_total;
+    if (kind == kGrid && scratch_budget > 0) t->scratch_cap = std::max(scratch_max, std::min(scratch_budget, scratch_total));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available (this library has no CPU fallback)");
@@ -620,15 +709,15 @@ int create_impl(int32_t device, int32_t n_problems, const int32_t *const *seq_pt
         set_error("device index out of range");
         return GECCO_CRF_ENODEV;
     }
-    t->slots_bytes = size_t(n_problems) * sizeof(Slot);
-    t->h_in.assign(t->slots_bytes + size_t(ws_total) * sizeof(double), 0);
+    t->igs_off = size_t(n_problems) * sizeof(Slot);
+    t->ws_off = (t->igs_off + size_t(n_problems) * sizeof(ItemGroup) + 15) / 16 * 16;
+    t->h_in.assign(t->ws_off + size_t(ws_total) * sizeof(double), 0);
     t->h_out.assign(size_t(out_total), 0.0);
-    const size_t n_win = win_start_c.size(), n_items = label_c.size();
 
     int rc = check_hip(hipSetDevice(device), "hipSetDevice");
     if (rc) return rc;
     if ((rc = check_hip(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
-    if ((rc = dev_upload(&t->d_probs, t->layout, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_sets, layout, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_item_ptr, item_ptr_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_attr_id, attr_id_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_label, label_c, "trainer upload"))) return rc;
@@ -640,11 +729,8 @@ int create_impl(int32_t device, int32_t n_problems, const int32_t *const *seq_pt
     if ((rc = dev_upload(&t->d_attr_items, attr_items_c, "trainer upload"))) return rc;
     if ((rc = dev_alloc(&t->d_in, t->h_in.size(), "trainer alloc"))) return rc;
     if ((rc = dev_alloc(&t->d_out, t->h_out.size(), "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_rows, n_win * kTrainRowCols, "trainer alloc"))) return rc;
     if ((rc = dev_alloc(&t->d_partial, size_t(n_problems) * kTrainReduceBlocks * kTrainRowCols, "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_score, n_items, "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_marg, n_win * size_t(window), "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_item_marg, n_items, "trainer alloc"))) return rc;
+    if ((rc = dev_alloc(&t->d_scratch, size_t(t->scratch_cap), "trainer alloc"))) return rc;
     *out = t.release();
     return GECCO_CRF_OK;
 }
@@ -656,8 +742,8 @@ int trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const
                    const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, Trainer **out) {
     if (!out) return fail("trainer: null argument");
     *out = nullptr;
-    return create_impl(device, 1, &seq_ptr, &n_seqs, &item_ptr, &attr_id, &labels, &num_attrs, &num_labels, window, step,
-                       &state_fid, &trans_fid, &num_features, false, out);
+    return create_impl(device, 1, &seq_ptr, &n_seqs, &item_ptr, &attr_id, &labels, &num_attrs, &num_labels, &window, &step,
+                       &state_fid, &trans_fid, &num_features, 1, nullptr, 0, kLone, out);
 }
 
 int trainer_batch_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
@@ -671,62 +757,152 @@ int trainer_batch_create(int32_t device, int32_t n_problems, const int32_t *cons
     if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !state_fid || !trans_fid ||
         !num_features)
         return fail("trainer batch: null argument");
-    return create_impl(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
-                       state_fid, trans_fid, num_features, true, out);
+    const std::vector<int32_t> windows(size_t(n_problems), window), steps(size_t(n_problems), step);
+    return create_impl(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, windows.data(),
+                       steps.data(), state_fid, trans_fid, num_features, n_problems, nullptr, 0, kBatch, out);
 }
 
+int trainer_grid_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                        const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                        const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                        const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                        int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget_bytes, Trainer **out) {
+    if (!out) return fail("trainer grid: null argument");
+    *out = nullptr;
+    if (n_sets < 1) return fail("trainer grid: at least one set is needed");
+    if (n_problems < 1) return fail("trainer grid: at least one problem is needed");
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !window || !step ||
+        !state_fid || !trans_fid || !num_features || !problem_set)
+        return fail("trainer grid: null argument");
+    return create_impl(device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
+                       state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes, kGrid, out);
+}
+
+namespace {
+
+// One group of an evaluation: slots [s0, s1) and item groups [g0, g1) of the upload, its grids, the largest W and the
+// most problems of one item group.
+struct Group {
+    int s0, s1, g0, g1;
+    int64_t blk_items, blk_win, blk_attr;
+    int32_t lds_w, np;
+};
+
+template <int NP>
+void launch_item_scores(const Group &gr, const ItemGroup *igs, const Slot *slots, const Trainer *t, const double *wstate,
+                        hipStream_t st) {
+    train_item_scores<NP><<<dim3(unsigned(gr.blk_items)), kTrainThreads, 0, st>>>(
+        igs, gr.g1 - gr.g0, slots, t->d_sets, t->d_item_ptr, t->d_attr_id, wstate, t->d_scratch);
+}
+
+}  // namespace
+
 int trainer_batch_eval(Trainer *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
-    if (!t || !active || !w || !f || !g) return fail("trainer_batch_eval: null argument");
+    const std::string name = t && t->kind == kGrid ? "trainer_grid_eval" : "trainer_batch_eval";
+    if (!t || !active || !w || !f || !g) return fail(name + ": null argument");
     const int32_t P = int32_t(t->probs.size());
     for (int32_t k = 0; k < P; ++k)
-        if (active[k] && (!g[k] || (t->probs[k].K > 0 && !w[k])))
-            return fail("trainer_batch_eval: null argument for problem " + std::to_string(k));
+        if (active[k] && (!g[k] || (t->sets[size_t(t->probs[k].set)].K > 0 && !w[k])))
+            return fail(name + ": null argument for problem " + std::to_string(k));
     Slot *slots = reinterpret_cast<Slot *>(t->h_in.data());
-    double *wstate = reinterpret_cast<double *>(t->h_in.data() + t->slots_bytes);
-    int n_slots = 0;
-    int32_t blk[3] = {0, 0, 0};
+    ItemGroup *igs = reinterpret_cast<ItemGroup *>(t->h_in.data() + t->igs_off);
+    double *wstate = reinterpret_cast<double *>(t->h_in.data() + t->ws_off);
+    std::vector<Group> groups;
+    int n_slots = 0, n_igs = 0;
     size_t in_hi = 0;
-    int64_t out_lo = INT64_MAX, out_hi = 0;
+    int64_t out_lo = INT64_MAX, out_hi = 0, used = 0, items_bound = 0;
+    // A group's item groups: its slots of one set, up to kTrainSetProbs at a time, in order of their first slot.
+    auto close = [&](Group &gr) {
+        std::vector<std::pair<int32_t, int>> last;  // set -> its latest item group
+        for (int si = gr.s0; si < gr.s1; ++si) {
+            const int32_t set = slots[si].set;
+            int gi = -1;
+            for (const auto &e : last)
+                if (e.first == set) gi = e.second;
+            if (gi < 0 || igs[gi].n == kTrainSetProbs) {
+                gi = n_igs++;
+                igs[gi].set = set;
+                igs[gi].n = 0;
+                igs[gi].blk = int32_t(gr.blk_items);
+                gr.blk_items += blocks_of(t->sets[size_t(set)].n_items, kTrainThreads);
+                bool found = false;
+                for (auto &e : last)
+                    if (e.first == set) e.second = gi, found = true;
+                if (!found) last.emplace_back(set, gi);
+            }
+            igs[gi].slot[igs[gi].n++] = si - gr.s0;
+            gr.np = std::max(gr.np, igs[gi].n);
+        }
+        gr.g1 = n_igs;
+        groups.push_back(gr);
+    };
+    Group cur{};
+    bool open = false;
     for (int32_t k = 0; k < P; ++k) {
         if (!active[k]) continue;
-        const Trainer::Meta &p = t->probs[k];
-        const ProbDev &d = t->layout[k];
-        if (p.n_win == 0) continue;
-        double *ws = wstate + d.ws0;
-        for (size_t j = 0; j < p.state_fid.size(); ++j) ws[j] = p.state_fid[j] >= 0 ? w[k][p.state_fid[j]] : 0.0;
-        in_hi = t->slots_bytes + size_t(d.ws0 + 2 * int64_t(p.A)) * sizeof(double);
+        const Trainer::Prob &p = t->probs[k];
+        const Trainer::Set &S = t->sets[size_t(p.set)];
+        if (S.n_win == 0) continue;
+        const int64_t nb_items = blocks_of(S.n_items, kTrainThreads), nb_win = blocks_of(S.n_win, kTrainWinThreads);
+        if (open && (used + p.scratch > t->scratch_cap || items_bound + nb_items > INT32_MAX ||
+                     cur.blk_win + nb_win > INT32_MAX || cur.blk_attr + S.A > INT32_MAX)) {
+            close(cur);
+            open = false;
+        }
+        if (!open) {
+            cur = Group{n_slots, n_slots, n_igs, n_igs, 0, 0, 0, 0, 1};
+            used = items_bound = 0;
+            open = true;
+        }
+        double *ws = wstate + p.ws0;
+        for (size_t j = 0; j < S.state_fid.size(); ++j) ws[j] = S.state_fid[j] >= 0 ? w[k][S.state_fid[j]] : 0.0;
+        in_hi = std::max(in_hi, t->ws_off + size_t(p.ws0 + 2 * int64_t(S.A)) * sizeof(double));
         Slot &s = slots[n_slots++];
-        s.T = trans_args(p.trans_fid, w[k]);
-        s.prob = k;
-        for (int G = 0; G < 3; ++G) s.blk[G] = blk[G];
-        blk[kGridItems] += (p.n_items + kTrainThreads - 1) / kTrainThreads;
-        blk[kGridWindows] += int32_t((p.n_win + kTrainWinThreads - 1) / kTrainWinThreads);
-        blk[kGridAttrs] += p.A;
-        out_lo = std::min(out_lo, d.out0);
-        out_hi = d.out0 + kTrainRowCols + 2 * int64_t(p.A);
+        s.T = trans_args(S.trans_fid, w[k]);
+        s.ws0 = p.ws0;
+        s.sc0 = used;
+        s.out0 = p.out0;
+        s.set = p.set;
+        s.blk[kGridWindows] = int32_t(cur.blk_win);
+        s.blk[kGridAttrs] = int32_t(cur.blk_attr);
+        cur.s1 = n_slots;
+        cur.blk_win += nb_win;
+        cur.blk_attr += S.A;
+        cur.lds_w = std::max(cur.lds_w, S.W);
+        used += p.scratch;
+        items_bound += nb_items;
+        out_lo = std::min(out_lo, p.out0);
+        out_hi = std::max(out_hi, p.out0 + kTrainRowCols + 2 * int64_t(S.A));
     }
+    if (open) close(cur);
 
     int rc = check_hip(hipSetDevice(t->device), "hipSetDevice");
     if (rc) return rc;
     hipStream_t st = t->stream;
-    if (n_slots > 0) {
-        const Slot *d_slots = reinterpret_cast<const Slot *>(t->d_in);
-        const double *d_wstate = reinterpret_cast<const double *>(t->d_in + t->slots_bytes);
+    if (!groups.empty()) {
+        const double *d_wstate = reinterpret_cast<const double *>(t->d_in + t->ws_off);
         if ((rc = check_hip(hipMemcpyAsync(t->d_in, t->h_in.data(), in_hi, hipMemcpyHostToDevice, st), "trainer weights upload")))
             return rc;
-        train_item_scores<<<blk[kGridItems], kTrainThreads, 0, st>>>(d_slots, n_slots, t->d_probs, t->d_item_ptr,
-                                                                     t->d_attr_id, d_wstate, t->d_score);
-        const size_t lds = size_t(t->W) * kTrainWinThreads * 3 * sizeof(double);
-        train_windows<<<dim3(unsigned(blk[kGridWindows])), kTrainWinThreads, lds, st>>>(
-            d_slots, n_slots, t->d_probs, t->d_score, t->d_label, t->d_win_start, t->W, t->d_marg, t->d_rows);
-        train_item_marginals<<<blk[kGridItems], kTrainThreads, 0, st>>>(d_slots, n_slots, t->d_probs, t->d_marg,
-                                                                        t->d_iw_first, t->d_iw_cnt, t->d_iw_off, t->W,
-                                                                        t->step, t->d_item_marg);
-        train_attr_counts<<<blk[kGridAttrs], kTrainThreads, 0, st>>>(d_slots, n_slots, t->d_probs, t->d_attr_ptr,
-                                                                     t->d_attr_items, t->d_item_marg, t->d_out);
-        train_reduce_rows<<<n_slots * kTrainReduceBlocks, kTrainThreads, 0, st>>>(d_slots, t->d_probs, t->d_rows,
-                                                                                  t->d_partial);
-        train_reduce_final<<<n_slots, kTrainReduceBlocks, 0, st>>>(d_slots, t->d_probs, t->d_partial, t->d_out);
+        // groups run one after another on the stream and share the work space
+        for (const Group &gr : groups) {
+            const Slot *d_slots = reinterpret_cast<const Slot *>(t->d_in) + gr.s0;
+            const ItemGroup *d_igs = reinterpret_cast<const ItemGroup *>(t->d_in + t->igs_off) + gr.g0;
+            const int ns = gr.s1 - gr.s0, ng = gr.g1 - gr.g0;
+            if (gr.np <= 1) launch_item_scores<1>(gr, d_igs, d_slots, t, d_wstate, st);
+            else if (gr.np <= 2) launch_item_scores<2>(gr, d_igs, d_slots, t, d_wstate, st);
+            else if (gr.np <= 4) launch_item_scores<4>(gr, d_igs, d_slots, t, d_wstate, st);
+            else launch_item_scores<kTrainSetProbs>(gr, d_igs, d_slots, t, d_wstate, st);
+            const size_t lds = size_t(gr.lds_w) * kTrainWinThreads * 3 * sizeof(double);
+            train_windows<<<dim3(unsigned(gr.blk_win)), kTrainWinThreads, lds, st>>>(d_slots, ns, t->d_sets, t->d_label,
+                                                                                   t->d_win_start, gr.lds_w, t->d_scratch);
+            train_item_marginals<<<dim3(unsigned(gr.blk_items)), kTrainThreads, 0, st>>>(
+                d_igs, ng, d_slots, t->d_sets, t->d_iw_first, t->d_iw_cnt, t->d_iw_off, t->d_scratch);
+            train_attr_counts<<<dim3(unsigned(gr.blk_attr)), kTrainThreads, 0, st>>>(d_slots, ns, t->d_sets, t->d_attr_ptr,
+                                                                                    t->d_attr_items, t->d_scratch, t->d_out);
+            train_reduce_rows<<<ns * kTrainReduceBlocks, kTrainThreads, 0, st>>>(d_slots, t->d_sets, t->d_scratch,
+                                                                                 t->d_partial);
+            train_reduce_final<<<ns, kTrainReduceBlocks, 0, st>>>(d_slots, t->d_partial, t->d_out);
+        }
         if ((rc = check_hip(hipGetLastError(), "trainer kernels"))) return rc;
         if ((rc = check_hip(hipMemcpyAsync(t->h_out.data() + out_lo, t->d_out + out_lo,
                                            size_t(out_hi - out_lo) * sizeof(double), hipMemcpyDeviceToHost, st),
@@ -737,8 +913,8 @@ int trainer_batch_eval(Trainer *t, const uint8_t *active, const double *const *w
     std::vector<double> zeros;
     for (int32_t k = 0; k < P; ++k) {
         if (!active[k]) continue;
-        const Trainer::Meta &p = t->probs[k];
-        const double *o = t->h_out.data() + t->layout[k].out0;  // row sums, then expected state counts
+        const Trainer::Set &p = t->sets[size_t(t->probs[k].set)];
+        const double *o = t->h_out.data() + t->probs[k].out0;  // row sums, then expected state counts
         if (p.n_win == 0) {
             zeros.assign(kTrainRowCols + 2 * size_t(p.A), 0.0);
             o = zeros.data();
@@ -756,7 +932,7 @@ int trainer_batch_eval(Trainer *t, const uint8_t *active, const double *const *w
 }
 
 int trainer_eval(Trainer *t, const double *w, double *f, double *g) {
-    if (!t || !f || !g || (t->probs[0].K > 0 && !w)) return fail("trainer_eval: null argument");
+    if (!t || !f || !g || (t->sets[0].K > 0 && !w)) return fail("trainer_eval: null argument");
     const uint8_t active = 1;
     return trainer_batch_eval(t, &active, &w, f, &g);
 }
@@ -764,7 +940,12 @@ int trainer_eval(Trainer *t, const double *w, double *f, double *g) {
 int32_t trainer_num_problems(const Trainer *t) { return t ? int32_t(t->probs.size()) : -1; }
 
 int64_t trainer_num_windows(const Trainer *t, int32_t k) {
-    return (t && k >= 0 && k < int32_t(t->probs.size())) ? t->probs[k].n_win : -1;
+    return (t && k >= 0 && k < int32_t(t->probs.size())) ? t->sets[size_t(t->probs[k].set)].n_win : -1;
+}
+
+int64_t trainer_scratch_bytes(const Trainer *t, int32_t k) {
+    if (!t || k < -1 || k >= int32_t(t->probs.size())) return -1;
+    return k < 0 ? t->scratch_cap : t->probs[k].scratch;
 }
 
 void trainer_destroy(Trainer *t) { delete t; }

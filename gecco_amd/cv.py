@@ -19,6 +19,7 @@ import itertools
 import math
 import operator
 import random
+import statistics
 import sys
 import warnings
 from typing import Any, Callable, Dict, Iterable, Iterator, List, Optional, Sequence, Set, Tuple, Union
@@ -28,7 +29,7 @@ import numpy as np
 from . import tables
 
 __all__ = ["LeaveOneGroupOut", "kfold_splits", "roc_auc", "average_precision", "group_genes", "cross_validate",
-           "CrossValidation", "Fold", "cv_table"]
+           "CrossValidation", "Fold", "cv_table", "grid_points", "rank_points", "grid_search", "GridSearch", "GridFold"]
 
 
 # ---------------------------------------------------------------------------------------------- splitters
@@ -244,6 +245,14 @@ def cv_table(folds: Sequence[Fold]) -> bytes:
 SplitSpec = Union[int, Sequence[Tuple[Sequence[int], Sequence[int]]], Callable[[List[List[Any]]], Sequence[Tuple[Any, Any]]]]
 
 
+def _fold_indices(seqs: List[List[Any]], splits: SplitSpec) -> List[Tuple[Any, Any]]:
+    if isinstance(splits, (int, np.integer)) and not isinstance(splits, bool):
+        return kfold_splits(len(seqs), int(splits))
+    if callable(splits):
+        return list(splits(seqs))
+    return list(splits)
+
+
 def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle: bool = True,
                    select: Optional[float] = None, correction_method: Optional[str] = None) -> CrossValidation:
     """Cross-validate the unfitted ``ClusterCRF`` template ``crf`` (its feature type, window, trainer options, ``devices``
@@ -258,12 +267,7 @@ def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle
     from . import train
 
     seqs = group_genes(genes, shuffle=shuffle)
-    if isinstance(splits, (int, np.integer)) and not isinstance(splits, bool):
-        folds_idx = kfold_splits(len(seqs), int(splits))
-    elif callable(splits):
-        folds_idx = list(splits(seqs))
-    else:
-        folds_idx = list(splits)
+    folds_idx = _fold_indices(seqs, splits)
     template_options = {k: v for k, v in crf._options.items() if k != "algorithm"}
     models, sets, params = [], [], None
     for train_idx, _ in folds_idx:
@@ -294,6 +298,266 @@ def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle
         folds.append(Fold(index=k + 1, train=np.asarray(train_idx), test=np.asarray(test_idx), crf=model,
                           predicted=predicted, truth=is_cluster, auroc=auroc, aupr=aupr))
     return CrossValidation(folds)
+
+
+# ---------------------------------------------------------------------------------------------- hyperparameter search
+GRID_KEYS = ("c1", "c2", "window_size")
+METRICS = ("aupr", "auroc")
+
+
+def grid_points(grid: Dict[str, Sequence[Any]], crf: Any = None) -> List[Dict[str, Any]]:
+    """The points of a ``{"c1": [...], "c2": [...], "window_size": [...]}`` grid, in grid order: c1 outermost, then c2,
+    then the window size.  A key left out takes the template ``crf``'s value.  ``ValueError`` for an unknown key, an
+    empty list, a regularisation strength that is negative or not finite, or a window size outside 1 .. 32."""
+    unknown = sorted(set(grid) - set(GRID_KEYS))
+    if unknown:
+        raise ValueError(f"grid: unknown parameter(s) {', '.join(map(repr, unknown))} (expected {', '.join(GRID_KEYS)})")
+    values: Dict[str, List[Any]] = {}
+    for key in GRID_KEYS:
+        if key in grid:
+            vals = list(grid[key])
+        elif crf is None:
+            raise ValueError(f"grid: no values for {key!r}")
+        else:
+            vals = [crf.window_size if key == "window_size" else crf._options.get(key, 0.0 if key == "c1" else 1.0)]
+        if not vals:
+            raise ValueError(f"grid: empty list of values for {key!r}")
+        out = []
+        for v in vals:
+            if key == "window_size":
+                if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= 32:
+                    raise ValueError(f"grid: window_size {v!r} is not an integer in 1 .. 32 (the trainable windows)")
+                out.append(int(v))
+            else:  # (kept as given: the value is stored with the model's options)
+                x = float(v)
+                if isinstance(v, bool) or not math.isfinite(x) or x < 0:
+                    raise ValueError(f"grid: {key} {v!r} is not a finite value >= 0")
+                out.append(v)
+        values[key] = out
+    return [{"c1": c1, "c2": c2, "window_size": w}
+            for c1, c2, w in itertools.product(values["c1"], values["c2"], values["window_size"])]
+
+
+def rank_points(auroc: Sequence[float], aupr: Sequence[float], metric: str = "aupr") -> List[int]:
+    """Point indices best first: by ``metric`` (higher is better, NaN last), then by the other metric, then grid order."""
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {', '.join(METRICS)}, not {metric!r}")
+    first, second = (aupr, auroc) if metric == "aupr" else (auroc, aupr)
+
+    def key(i: int) -> Tuple[float, float, int]:
+        a, b = float(first[i]), float(second[i])
+        return (-a if not math.isnan(a) else math.inf, -b if not math.isnan(b) else math.inf, i)
+
+    return sorted(range(len(first)), key=key)
+
+
+def _nanmean(values: Sequence[float]) -> float:
+    vals = [v for v in values if not math.isnan(v)]
+    return float(np.mean(vals)) if vals else math.nan
+
+
+def _fmt_float(x: float) -> str:
+    return "nan" if math.isnan(x) else repr(float(x))
+
+
+class GridFold:
+    """One fold of one grid point: its 1-based ``index``, the sequence indices it trained and tested on, the fitted
+    ``crf`` (``training_result_``), ``keys`` (sequence id, protein id, start, end) of the test genes in prediction
+    order, their ``probabilities`` (float64, what ``average_probability`` of ``predict_probabilities``' genes gives),
+    ``truth`` (``is_cluster`` joined by gene), ``auroc`` and ``aupr``."""
+
+    def __init__(self, **kw: Any) -> None:
+        self.__dict__.update(kw)
+
+    def __repr__(self) -> str:
+        return f"GridFold({self.index}, n_test={len(self.keys)}, auroc={self.auroc:.3f}, aupr={self.aupr:.3f})"
+
+
+class GridSearch:
+    """The result of ``grid_search``: ``points`` in grid order, ``folds[p]`` the folds of point p, per point the
+    ``mean_auroc`` / ``mean_aupr`` over its folds (NaN folds left out) and the pooled ``auroc`` / ``aupr`` over the
+    predictions of all its folds (what ``CrossValidation`` reports), ``ranking`` (best first, by ``metric``'s mean) and
+    ``best`` (the first of the ranking)."""
+
+    def __init__(self, points: List[Dict[str, Any]], folds: List[List[GridFold]], metric: str = "aupr") -> None:
+        self.points, self.folds, self.metric = points, folds, metric
+        self.mean_auroc = [_nanmean([f.auroc for f in fs]) for fs in folds]
+        self.mean_aupr = [_nanmean([f.aupr for f in fs]) for fs in folds]
+        self.auroc, self.aupr = [], []
+        for fs in folds:
+            labels = [t for f in fs for t in f.truth]
+            probas = [p for f in fs for p in np.asarray(f.probabilities).tolist()]
+            a, b = _metrics(labels, probas) if labels else (math.nan, math.nan)
+            self.auroc.append(a)
+            self.aupr.append(b)
+        self.ranking = rank_points(self.mean_auroc, self.mean_aupr, metric)
+        self.best = self.ranking[0]
+
+    @property
+    def best_point(self) -> Dict[str, Any]:
+        return self.points[self.best]
+
+    def table(self) -> bytes:
+        """One row per (point, fold), points in grid order: ``point`` (1-based), ``c1``, ``c2``, ``window_size``,
+        ``fold``, ``n_train`` / ``n_test`` (sequences), ``auroc``, ``aupr``."""
+        rows = ["point\tc1\tc2\twindow_size\tfold\tn_train\tn_test\tauroc\taupr"]
+        for p, (pt, fs) in enumerate(zip(self.points, self.folds)):
+            for f in fs:
+                rows.append("\t".join([str(p + 1), _fmt_float(pt["c1"]), _fmt_float(pt["c2"]), str(pt["window_size"]),
+                                       str(f.index), str(len(f.train)), str(len(f.test)), _fmt_float(f.auroc),
+                                       _fmt_float(f.aupr)]))
+        return ("\n".join(rows) + "\n").encode("utf-8")
+
+    def summary(self) -> bytes:
+        """One row per point, in grid order: ``point``, ``c1``, ``c2``, ``window_size``, ``mean_auroc``, ``mean_aupr``,
+        the pooled ``auroc`` / ``aupr``, and ``rank`` (1 = best)."""
+        rank = {p: r + 1 for r, p in enumerate(self.ranking)}
+        rows = ["point\tc1\tc2\twindow_size\tmean_auroc\tmean_aupr\tauroc\taupr\trank"]
+        for p, pt in enumerate(self.points):
+            rows.append("\t".join([str(p + 1), _fmt_float(pt["c1"]), _fmt_float(pt["c2"]), str(pt["window_size"]),
+                                   _fmt_float(self.mean_auroc[p]), _fmt_float(self.mean_aupr[p]),
+                                   _fmt_float(self.auroc[p]), _fmt_float(self.aupr[p]), str(rank[p])]))
+        return ("\n".join(rows) + "\n").encode("utf-8")
+
+
+def _encode_test_genes(genes: List[Any], feature_type: str):
+    """The test genes as ``predict_probabilities`` orders and packs them, once per fold: sorted by (sequence, start), their
+    domains by start, grouped by sequence; items CSR over a vocabulary of the fold's domain names (ids in order of first
+    appearance).  Returns the sorted genes, contig_ptr, item_ptr, vocabulary ids and the vocabulary."""
+    genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
+    for gene in genes:
+        gene.protein.domains.sort(key=operator.attrgetter("start"))
+    vocab: Dict[str, int] = {}
+    contig_ptr, item_ptr, attr = [0], [0], []
+    for _, group in itertools.groupby(genes, key=operator.attrgetter("source.id")):
+        n_items = 0
+        for gene in group:
+            doms = gene.protein.domains
+            if feature_type == "protein":
+                for name in dict.fromkeys(d.name for d in doms):  # (a repeated domain is one feature)
+                    attr.append(vocab.setdefault(name, len(vocab)))
+                item_ptr.append(len(attr))
+                n_items += 1
+            elif doms:
+                for d in doms:
+                    attr.append(vocab.setdefault(d.name, len(vocab)))
+                    item_ptr.append(len(attr))
+                    n_items += 1
+            else:
+                item_ptr.append(len(attr))
+                n_items += 1
+        contig_ptr.append(contig_ptr[-1] + n_items)
+    return (genes, np.asarray(contig_ptr, dtype=np.int32), np.asarray(item_ptr, dtype=np.int64),
+            np.asarray(attr, dtype=np.int32), list(vocab))
+
+
+def _score_test_genes(model: Any, encoded) -> np.ndarray:
+    """``average_probability`` of every gene ``model.predict_probabilities`` would return for the encoded genes, scored
+    through ``predict_probabilities_csr``: the fold's vocabulary is mapped to the model's attribute ids and the names the
+    model does not know are dropped, as the object path drops them."""
+    genes, contig_ptr, item_ptr, attr, vocab = encoded
+    index = model.model._attr_index
+    to_model = np.asarray([index.get(name, -1) for name in vocab] or [-1], dtype=np.int32)
+    mapped = to_model[attr] if attr.size else attr
+    known = mapped >= 0
+    kept = np.concatenate([[0], np.cumsum(known, dtype=np.int64)])
+    gene_ptr = kept[item_ptr].astype(np.int32)
+    p_items = model.predict_probabilities_csr(contig_ptr, gene_ptr, mapped[known], pad=True)
+    if model.feature_type == "protein":
+        return np.ascontiguousarray(p_items, dtype=np.float64)
+    out = np.empty(len(genes), dtype=np.float64)
+    k = 0
+    for i, gene in enumerate(genes):
+        n = len(gene.protein.domains)
+        if n:
+            # (_annotate keeps the gene's own probability and sets the domains'; the average is the gene's if it has one)
+            own = getattr(gene, "_probability", None)
+            out[i] = own if own is not None else statistics.mean(float(x) for x in p_items[k:k + n])
+            k += n
+        else:
+            out[i] = float(p_items[k])
+            k += 1
+    return out
+
+
+def grid_search(crf: Any, genes: Iterable[Any], splits: SplitSpec, grid: Dict[str, Sequence[Any]], *,
+                shuffle: bool = True, select: Optional[float] = None, correction_method: Optional[str] = None,
+                metric: str = "aupr") -> GridSearch:
+    """Cross-validate every point of ``grid`` (``grid_points``: ``c1``, ``c2``, ``window_size``) on labelled ``genes``, with
+    the unfitted ``ClusterCRF`` template ``crf`` giving every other option.
+
+    The point's ``cross_validate`` (a template with the point's values, the same ``splits``, ``shuffle``, ``select`` and
+    random state) gives each (point, fold) the same model and test probabilities, bit for bit.  The work shared between
+    points is done once: the groups are shuffled once, Fisher selection runs once per fold, the training set is built
+    once per (fold, window size) from the same random state, all (point, fold) problems are fitted in one
+    ``train.fit_grid``, and each fold's test genes are sorted and encoded once; every model then scores them through
+    ``predict_probabilities_csr``.  The global ``random`` is left as ``cross_validate`` leaves it."""
+    from . import train
+
+    if metric not in METRICS:
+        raise ValueError(f"metric must be one of {', '.join(METRICS)}, not {metric!r}")
+    points = grid_points(grid, crf)
+    seqs = group_genes(genes, shuffle=shuffle)
+    folds_idx = _fold_indices(seqs, splits)
+    template_options = {k: v for k, v in crf._options.items() if k != "algorithm"}
+
+    def model_of(pt: Dict[str, Any]) -> Any:
+        # (the template's options with the point's values, as the point's own template would hold them)
+        options = dict(template_options)
+        options.update({k: pt[k] for k in ("c1", "c2") if k in grid or k in options})
+        model = type(crf)(crf.feature_type, crf.algorithm, pt["window_size"], crf.window_step, **options)
+        model.devices, model.reference_bits = list(crf.devices), crf.reference_bits
+        return model
+
+    windows = list(dict.fromkeys(pt["window_size"] for pt in points))
+    sets: List[Any] = []
+    set_of: Dict[Tuple[int, int], int] = {}
+    selection = []
+    for f, (train_idx, _) in enumerate(folds_idx):
+        template = model_of(points[0])
+        train_genes: List[Any] = [gene for i in train_idx for gene in seqs[i]]
+        sig = keep = None
+        if select is not None:
+            train_genes, sig, keep = template._select_features(train_genes, select, correction_method)
+        selection.append((sig, keep))
+        state = random.getstate()
+        for w in windows:  # (every window size draws the same shuffle: the state before it is restored)
+            random.setstate(state)
+            ts, _ = model_of({**points[0], "window_size": w})._training_set(train_genes, shuffle=shuffle)
+            set_of[(f, w)] = len(sets)
+            sets.append(ts)
+    problems = [(set_of[(f, pt["window_size"])], train.trainer_params(model_of(pt)._options))
+                for pt in points for f in range(len(folds_idx))]
+    devices = crf.devices or [0]
+    results = train.fit_grid(sets, problems, device=int(devices[0]))
+
+    tests = []
+    for train_idx, test_idx in folds_idx:
+        truth_genes = [gene for i in test_idx for gene in seqs[i]]
+        truth: Dict[Tuple[str, str, int, int], bool] = {}
+        for gene in truth_genes:
+            key, label = _gene_key(gene), gene.average_probability > 0.5
+            if truth.setdefault(key, label) != label:
+                raise ValueError(f"two genes {key!r} with different labels")
+        encoded = _encode_test_genes([_test_copy(gene) for gene in truth_genes], crf.feature_type)
+        keys = [_gene_key(gene) for gene in encoded[0]]
+        tests.append((encoded, keys, [truth[k] for k in keys]))
+
+    folds: List[List[GridFold]] = []
+    for p, pt in enumerate(points):
+        row = []
+        for f, (train_idx, test_idx) in enumerate(folds_idx):
+            k = p * len(folds_idx) + f
+            model = model_of(pt)
+            model.significance, model.significant_features = selection[f]
+            model._adopt_fit(sets[problems[k][0]], results[k])
+            encoded, keys, is_cluster = tests[f]
+            probas = _score_test_genes(model, encoded) if keys else np.zeros(0)
+            auroc, aupr = _metrics(is_cluster, probas) if keys else (math.nan, math.nan)
+            row.append(GridFold(index=f + 1, train=np.asarray(train_idx), test=np.asarray(test_idx), crf=model, keys=keys,
+                                probabilities=probas, truth=is_cluster, auroc=auroc, aupr=aupr))
+        folds.append(row)
+    return GridSearch(points, folds, metric)
 
 
 # ---------------------------------------------------------------------------------------------- front end

@@ -25,7 +25,7 @@ from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple
 import numpy as np
 
 __all__ = ["TRAINER_DEFAULTS", "trainer_params", "minimize", "minimize_steps", "OptimizeResult", "TrainingSet",
-           "build_training_set", "fit_training_set", "fit_training_sets", "model_blob"]
+           "build_training_set", "fit_training_set", "fit_training_sets", "fit_grid", "model_blob"]
 
 #: libLBFGS parameters as CRFsuite's ``train_lbfgs`` sets them (``max_iterations`` None = unbounded)
 TRAINER_DEFAULTS = {"num_memories": 6, "epsilon": 1e-5, "period": 10, "delta": 1e-5, "max_iterations": None}
@@ -368,24 +368,55 @@ def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], de
         raise ValueError("fit_training_sets: every training set must have the same window and step")
     batch = _native.TrainerBatch([(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.state_fid,
                                    ts.trans_fid, ts.num_features) for ts in sets], window, step, device=device)
-    c2 = float(params["c2"])
+    return _fit_lockstep(batch, sets, [params] * len(sets))
+
+
+#: default cap of ``fit_grid``'s work space: the scratch of one group of problems evaluated together
+GRID_SCRATCH_BUDGET = 8 << 30
+
+
+def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str, object]]], device: int = 0,
+             scratch_budget_bytes: int = GRID_SCRATCH_BUDGET) -> List[OptimizeResult]:
+    """A grid of fits over shared training sets: problem k is ``(set index, params)``.  Every set is resident on the device
+    once, with its own window and step (``_native.TrainerGrid``); one optimiser per problem, with that problem's
+    ``c1`` / ``c2`` and libLBFGS parameters, runs in lock-step, each round evaluating the pending points of the unfinished
+    problems in one batched pass (in groups whose scratch fits ``scratch_budget_bytes``).  Result k is exactly
+    ``fit_training_set(sets[set_k], params_k, device)``."""
+    from . import _native
+
+    if not problems:
+        return []
+    for k, (s, _) in enumerate(problems):
+        if not 0 <= int(s) < len(sets):
+            raise ValueError(f"fit_grid: problem {k} names set {s}, but there are {len(sets)} sets")
+    grid = _native.TrainerGrid([(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.state_fid, ts.trans_fid,
+                                 ts.num_features, ts.window, ts.step) for ts in sets],
+                               [int(s) for s, _ in problems], scratch_budget_bytes, device=device)
+    return _fit_lockstep(grid, [sets[int(s)] for s, _ in problems], [p for _, p in problems])
+
+
+def _fit_lockstep(trainer, sets: Sequence[TrainingSet], params: Sequence[Dict[str, object]]) -> List[OptimizeResult]:
+    """One optimiser per problem of ``trainer`` (a ``TrainerBatch`` or ``TrainerGrid``; problem k trains ``sets[k]`` with
+    ``params[k]``) in lock-step; problems drop out as they stop.  The host adds each problem's L2 term as
+    ``fit_training_set`` does."""
     n = len(sets)
-    steppers = [minimize_steps(np.zeros(ts.num_features), c1=float(params["c1"]), num_memories=int(params["num_memories"]),
-                               epsilon=float(params["epsilon"]), period=int(params["period"]), delta=float(params["delta"]),
-                               max_iterations=params["max_iterations"]) for ts in sets]
+    steppers = [minimize_steps(np.zeros(ts.num_features), c1=float(p["c1"]), num_memories=int(p["num_memories"]),
+                               epsilon=float(p["epsilon"]), period=int(p["period"]), delta=float(p["delta"]),
+                               max_iterations=p["max_iterations"]) for ts, p in zip(sets, params)]
+    c2 = [float(p["c2"]) for p in params]
     pending: List[Optional[np.ndarray]] = [next(st) for st in steppers]
     results: List[Optional[OptimizeResult]] = [None] * n
     f = np.zeros(n)
     g = [np.empty(ts.num_features) for ts in sets]
     while any(x is not None for x in pending):
         active = np.array([x is not None for x in pending], dtype=np.uint8)
-        batch.eval(pending, active, f, g)
+        trainer.eval(pending, active, f, g)
         for k in np.flatnonzero(active).tolist():
             w = pending[k]
             fk, gk = float(f[k]), g[k].copy()
-            if c2 > 0:
-                fk += c2 * float(np.dot(w, w))
-                gk = gk + (2.0 * c2) * w
+            if c2[k] > 0:
+                fk += c2[k] * float(np.dot(w, w))
+                gk = gk + (2.0 * c2[k]) * w
             try:
                 pending[k] = steppers[k].send((fk, gk))
             except StopIteration as stop:

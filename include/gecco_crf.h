@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.7.0 = 270). */
+/* ABI version: major*100 + minor*10 + patch (2.8.0 = 280). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -463,6 +463,39 @@ int gecco_crf_trainer_batch_eval(gecco_crf_trainer_batch *t, const uint8_t *acti
 int32_t gecco_crf_trainer_batch_num_problems(const gecco_crf_trainer_batch *t);
 int64_t gecco_crf_trainer_batch_num_windows(const gecco_crf_trainer_batch *t, int32_t k);
 void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t);
+
+/* ---- training, a grid of problems over shared training sets (ABI 2.8.0) ------------------------------------------
+ * A hyperparameter search: n_sets training sets, each uploaded once, and n_problems problems, problem k on set
+ * problem_set[k] with its own weights.  Set s is exactly what gecco_crf_trainer_create takes, with its own window[s] and
+ * step[s]: seq_ptr[s], n_seqs[s], item_ptr[s], attr_id[s], labels[s], num_attrs[s], num_labels[s], window[s], step[s],
+ * state_fid[s], trans_fid[s], num_features[s].  The lone trainer's checks apply to every set ("set s: ..." in the
+ * message); a problem_set entry outside [0, n_sets) is EINVAL ("problem k: ...").
+ * eval: as gecco_crf_trainer_batch_eval, w[k] and g[k] of num_features[problem_set[k]] entries.  Problems of one set
+ * read its arrays once per launch (their item scores from one read of its attribute ids).  Each problem has its own
+ * scratch (node marginals [windows][W][2], window rows, item scores and marginals: about 16 W + 40 bytes per window
+ * plus 32 per item; num_windows and scratch_bytes give it).  The active problems are cut, in problem order, into groups
+ * whose scratch together fits scratch_budget_bytes (a problem larger than the budget runs alone; <= 0: no limit), and
+ * the groups run one after another: one upload, six launches per group, one download; synchronous.  Device memory is
+ * the sets once plus the larger of the budget and the largest problem's scratch (at most the sum of all problems').
+ * Bit contract: f[k] and g[k] are bitwise equal to gecco_crf_trainer_eval on a lone trainer built from set
+ * problem_set[k], with the same w[k], whatever the other problems hold, which of them are active and however they are
+ * grouped: every sum stays inside its problem, in the lone trainer's order (a problem whose transitions force log
+ * space, or whose weights are not finite, affects no other).
+ * num_windows(t, k): the windows of problem k's set (-1 for a bad k); scratch_bytes(t, k): problem k's scratch, and for
+ * k = -1 the work space allocated; num_problems: n_problems. */
+typedef struct gecco_crf_trainer_grid gecco_crf_trainer_grid;
+int gecco_crf_trainer_grid_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                                  const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                                  const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                                  const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                                  int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget_bytes,
+                                  gecco_crf_trainer_grid **out);
+int gecco_crf_trainer_grid_eval(gecco_crf_trainer_grid *t, const uint8_t *active, const double *const *w, double *f,
+                                double *const *g);
+int32_t gecco_crf_trainer_grid_num_problems(const gecco_crf_trainer_grid *t);
+int64_t gecco_crf_trainer_grid_num_windows(const gecco_crf_trainer_grid *t, int32_t k);
+int64_t gecco_crf_trainer_grid_scratch_bytes(const gecco_crf_trainer_grid *t, int32_t k);
+void gecco_crf_trainer_grid_free(gecco_crf_trainer_grid *t);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
