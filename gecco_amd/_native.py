@@ -1365,7 +1365,9 @@ def fisher_exact(tables, device: int = 0) -> np.ndarray:
 
 class Forest:
     """A random forest fitted on the device (``gecco_crf_forest_*``): sklearn 1.7's RandomForestClassifier for the
-    configuration GECCO's TypeClassifier uses, tree for tree.  The host draws the random streams (see ``gecco_amd.types``)."""
+    configuration GECCO's TypeClassifier uses, tree for tree.  The host draws the random streams (see ``gecco_amd.types``).
+    Near-equal feature values follow the sklearn 1.7.2 build, not its source: a split position is valid when
+    ``Xf[p] > Xf[p - 1]`` on the float32 values (no 1e-7 margin), so values one ulp apart can be split."""
 
     def __init__(self, col_ptr, row_idx, values, n_samples: int, y, n_classes, sample_counts, rand_state, max_features: int,
                  device: int = 0):

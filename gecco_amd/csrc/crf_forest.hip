@@ -18,10 +18,12 @@
 //   * per output, one workgroup scan gives the class weights left of every position, and each position accumulates its
 //     Gini terms in sklearn's output order; the proxy improvement of every valid position follows, and an argmax that keeps
 //     the first position in scan order among equal values.
-// Which position is "valid" is sklearn's: Xf[p] > Xf[p - 1] + FEATURE_THRESHOLD on float32 values promoted to double,
-// between sorted neighbours (the zero block compares as zeros).  The order of samples within a node, which sklearn's
-// in-place partitioning leaves implementation-defined among equal values, changes no stored number: every quantity of a
-// node is a function of its sample set.
+// Which position is "valid" is the sklearn 1.7.2 build's: Xf[p] > Xf[p - 1] between sorted float32 neighbours (the zero
+// block compares as zeros), and a feature is constant in a node when Xf[end - 1] <= Xf[start].  sklearn's source adds a
+// FEATURE_THRESHOLD of 1e-7 to the right-hand sides, but in the released build that constant acts as 0: two values one
+// ulp apart, or the zero block and the smallest denormal, are split (tests/test_gpu_forest_edges.py pins
+// it).  The order of samples within a node, which sklearn's in-place partitioning leaves implementation-defined among
+// equal values, changes no stored number: every quantity of a node is a function of its sample set.
 //
 // Why the parallel sums give sklearn's bits: bootstrap weights are small integers (counts of a sample in the draw), so every
 // weighted class count, node weight and left / right weight is an integer below 2^24, exact in fp64 whatever the order of
@@ -55,7 +57,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kChunk = kForestMaxSamples / kThreads;  // positions per thread in the scans
 constexpr uint16_t kNone = 0xFFFF;
-constexpr double kFeatureThreshold = 1e-7;        // sklearn/tree/_splitter.pyx FEATURE_THRESHOLD
 constexpr double kEpsilon = 2.220446049250313e-16;  // np.finfo(np.double).eps (_tree.pyx EPSILON)
 constexpr uint32_t kRandRMax = 2147483647u;       // sklearn/utils/_random.pxd RAND_R_MAX
 
@@ -253,8 +254,8 @@ __device__ void evaluate_feature(const FitArgs &A, Shared &s, int f, int a, int 
     const int n_node = b - a;
     const bool zeros = m < n_node;
     const int N = m + (zeros ? 1 : 0);
-    // constant: Xf[end - 1] <= Xf[start] + FEATURE_THRESHOLD
-    if (double(entry_value(s, N - 1, zeros)) <= double(entry_value(s, 0, zeros)) + kFeatureThreshold) {
+    // constant: Xf[end - 1] <= Xf[start] (FEATURE_THRESHOLD acts as 0 in the build this follows)
+    if (entry_value(s, N - 1, zeros) <= entry_value(s, 0, zeros)) {
         if (tid == 0) s.fconst = 1;
         __syncthreads();
         return;
@@ -334,8 +335,7 @@ __device__ void evaluate_feature(const FitArgs &A, Shared &s, int f, int a, int 
     for (int c = 0; c < kChunk; ++c) {
         const int j = c0 + c;
         if (c < cnt && j > 0) {
-            const double vj = double(entry_value(s, j, zeros)), vp = double(entry_value(s, j - 1, zeros));
-            if (vj > vp + kFeatureThreshold) {  // next_p stops here
+            if (entry_value(s, j, zeros) > entry_value(s, j - 1, zeros)) {  // next_p stops here
                 const double il = gl[c] / A.n_out, ir = gr[c] / A.n_out;
                 const double wld = double(wl[c]), wrd = double(Wtot - wl[c]);
                 const double proxy = -wrd * ir - wld * il;
@@ -517,6 +517,7 @@ __global__ __launch_bounds__(kThreads) void forest_fit_kernel(FitArgs A) {
         // ---- partition_samples_final: samples with X[:, f] <= threshold first
         if (split_feature >= 0) {
             const int f = split_feature;
+            // (a threshold of exactly 0 is the midpoint of -a and +a: the node then holds no zeros, and the block is empty)
             const uint8_t zero_left = 0.0 <= split_thr ? 1 : 0;
             for (int p = start + tid; p < end; p += kThreads) s.side[p] = zero_left;
             __syncthreads();

@@ -3,7 +3,8 @@
 Mirrors ``gecco.types.TypeClassifier`` (gecco/types/__init__.py): ``trained()`` reads ``domains.tsv``, ``types.tsv``
 and ``compositions.npz`` from a model directory and fits ``RandomForestClassifier(random_state=0)`` on them;
 ``predict_types`` annotates clusters with ``type`` and ``type_probabilities``.  The forest is sklearn 1.7's, tree for tree
-and bit for bit (``gecco_crf_forest_fit``), without sklearn or scipy: the host only reads the files, draws
+and bit for bit (``gecco_crf_forest_fit``; at near-equal feature values it is the 1.7.2 build's behaviour
+that is followed, which splits any two distinct float32 values), without sklearn or scipy: the host only reads the files, draws
 sklearn's random streams with numpy's ``RandomState`` and lays the matrix out as sklearn does (CSC, float32, sorted
 indices).
 

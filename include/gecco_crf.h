@@ -538,7 +538,9 @@ int gecco_crf_domain_composition_members(int32_t device, const int32_t *member_p
 /* ---- cluster type classifier (ABI 2.7.0): random forest fit and predict ---------------------------------------------
  * What GECCO's TypeClassifier (gecco/types/__init__.py) asks sklearn.ensemble.RandomForestClassifier for: fit with
  * criterion "gini", max_features = max_features, bootstrap, no depth limit, min_samples_split 2, min_samples_leaf 1, no
- * class weights; every tree equals sklearn 1.7's node for node and bit for bit.  The caller draws the random streams as
+ * class weights; every tree equals sklearn 1.7's node for node and bit for bit (the 1.7.2 build's behaviour: two sorted
+ * float32 neighbours are distinct values when the second is greater at all; the 1e-7 FEATURE_THRESHOLD of sklearn's
+ * source acts as 0 in that build).  The caller draws the random streams as
  * sklearn does: rand_state[t] = RandomState(seed_t).randint(0, 2^31 - 1) and sample_counts[t] = bincount of
  * RandomState(seed_t).randint(0, n, n) for the per-tree seeds seed_t = RandomState(random_state).randint(2^31 - 1, n_trees).
  * X: n_samples x n_features CSC float32 (col_ptr[n_features + 1], row_idx strictly increasing within a column, finite values;
