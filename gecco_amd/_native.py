@@ -167,7 +167,8 @@ SIGNATURES = {
         ctypes.c_int, [ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32,
                        ctypes.c_int32, ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.POINTER(_vp)]
     ),
-    "gecco_crf_trainer_eval": (ctypes.c_int, [_vp, _c_f64p, _c_f64p, _c_f64p]),
+    # (the three evals take the double arrays as addresses: `_TrainerHandle._eval_problems` has checked them)
+    "gecco_crf_trainer_eval": (ctypes.c_int, [_vp, _vp, _vp, _vp]),
     "gecco_crf_trainer_num_windows": (ctypes.c_int64, [_vp]),
     "gecco_crf_trainer_free": (None, [_vp]),
     "gecco_crf_trainer_batch_create": (
@@ -175,7 +176,7 @@ SIGNATURES = {
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32,
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
     ),
-    "gecco_crf_trainer_batch_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _c_f64p, ctypes.POINTER(_vp)]),
+    "gecco_crf_trainer_batch_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_batch_num_problems": (ctypes.c_int32, [_vp]),
     "gecco_crf_trainer_batch_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_batch_free": (None, [_vp]),
@@ -185,7 +186,7 @@ SIGNATURES = {
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.c_int32, _c_i32p, ctypes.c_int64,
                        ctypes.POINTER(_vp)]
     ),
-    "gecco_crf_trainer_grid_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _c_f64p, ctypes.POINTER(_vp)]),
+    "gecco_crf_trainer_grid_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_grid_num_problems": (ctypes.c_int32, [_vp]),
     "gecco_crf_trainer_grid_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_grid_scratch_bytes": (ctypes.c_int64, [_vp, ctypes.c_int32]),
@@ -1158,119 +1159,90 @@ class Plan:
         return ms.value
 
 
-class Trainer:
-    """Training set of a 2-label CRF resident on one device (``gecco_crf_trainer_*``): ``eval(w)`` returns the summed
-    negative log-likelihood of every training window and its gradient over the ``num_features`` generated features."""
-
-    def __init__(self, seq_ptr, item_ptr, attr_id, labels, num_attrs: int, window: int, step: int, state_fid, trans_fid,
-                 num_features: int, device: int = 0):
-        self._lib = load_library()
-        self._h = None
-        seq_ptr, item_ptr, attr_id, labels = _i32(seq_ptr), _i32(item_ptr), _i32(attr_id), _i32(labels)
+def _trainer_sets(sets):
+    """The C arguments of training sets ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid,
+    num_features[, window, step])``: per array name the int32 arrays of every set (an empty one replaced by one zero, so
+    that its pointer is valid), and per count name (``n_seqs``, ``num_attrs``, ``num_labels``, ``num_features``,
+    ``window``, ``step``) the list of every set's value."""
+    arrays = {name: [] for name in ("seq_ptr", "item_ptr", "attr_id", "labels", "state_fid", "trans_fid")}
+    counts = {name: [] for name in ("n_seqs", "num_attrs", "num_labels", "num_features", "window", "step")}
+    for seq_ptr, item_ptr, attr_id, labels, A, state_fid, trans_fid, K, *window_step in sets:
         state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
-        if int(num_attrs) < 1 or state_fid.size % int(num_attrs) != 0:
+        if int(A) < 1 or state_fid.size % int(A) != 0:
             raise ValueError("state_fid must have num_attrs * L entries")
-        L = state_fid.size // int(num_attrs)  # (the library trains 2-label models only and says so for any other L)
+        L = state_fid.size // int(A)  # (the library trains 2-label models only and says so for any other L)
         if trans_fid.size != L * L:
             raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
-        keep = [seq_ptr, item_ptr, attr_id, labels, state_fid, trans_fid]
-        keep = [a if a.size else np.zeros(1, dtype=np.int32) for a in keep]
-        h = _vp()
-        _check(self._lib.gecco_crf_trainer_create(
-            int(device), _ptr(keep[0], _c_i32p), len(seq_ptr) - 1, _ptr(keep[1], _c_i32p), _ptr(keep[2], _c_i32p),
-            _ptr(keep[3], _c_i32p), int(num_attrs), L, int(window), int(step), _ptr(keep[4], _c_i32p),
-            _ptr(keep[5], _c_i32p), int(num_features), ctypes.byref(h)))
-        self._h = h
-        self.num_features = int(num_features)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.gecco_crf_trainer_free(h)
-
-    @property
-    def num_windows(self) -> int:
-        return int(self._lib.gecco_crf_trainer_num_windows(self._h))
-
-    def eval(self, w):
-        w = np.ascontiguousarray(w, dtype=np.float64)
-        if w.shape != (self.num_features,):
-            raise ValueError(f"expected {self.num_features} weights, got shape {w.shape}")
-        g = np.empty(max(self.num_features, 1), dtype=np.float64)
-        f = ctypes.c_double(0.0)
-        wb = w if w.size else np.zeros(1)
-        _check(self._lib.gecco_crf_trainer_eval(self._h, _ptr(wb, _c_f64p), ctypes.byref(f), _ptr(g, _c_f64p)))
-        return f.value, g[:self.num_features]
+        seq_ptr = _i32(seq_ptr)
+        for name, a in zip(arrays, (seq_ptr, _i32(item_ptr), _i32(attr_id), _i32(labels), state_fid, trans_fid)):
+            arrays[name].append(a if a.size else np.zeros(1, dtype=np.int32))
+        for name, v in zip(counts, (len(seq_ptr) - 1, A, L, K, *window_step)):
+            counts[name].append(int(v))
+    return arrays, counts
 
 
-class TrainerBatch:
-    """Several training sets of 2-label CRFs resident on one device at once (``gecco_crf_trainer_batch_*``).
+def _ptr_table(arrays):
+    return (_vp * max(len(arrays), 1))(*[a.ctypes.data for a in arrays])
 
-    ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)``
-    per problem, as ``Trainer`` takes them; ``window`` and ``step`` are shared.  ``eval(ws, active)`` evaluates the active
-    problems in one batched pass; problem k's f and g are bitwise what a lone ``Trainer`` of it returns for ``ws[k]``."""
 
-    def __init__(self, problems, window: int, step: int, device: int = 0):
+def _i32_vector(values):
+    return _ptr(np.ascontiguousarray(values if len(values) else [0], dtype=np.int32), _c_i32p)  # (keeps its array alive)
+
+
+def _out_address(a: np.ndarray) -> int:
+    """Address of a non-empty float64 array the library writes to (a read-only one is a ``TypeError``).  This and the
+    plain ctypes mask keep the marshalling of a one-problem ``eval`` at a few microseconds: ``data_as`` costs 2 µs each."""
+    return ctypes.addressof(ctypes.c_double.from_buffer(a))
+
+
+class _TrainerHandle:
+    """What the three trainer families share: the handle, and the evaluation of a list of problems.  A subclass names its
+    C family (``_family``) and marshals that family's ``create`` and ``eval`` arguments."""
+
+    _family = ""
+
+    def _c(self, name):
+        return getattr(self._lib, f"{self._family}_{name}")
+
+    def _create(self, *args):
         self._lib = load_library()
         self._h = None
-        n = len(problems)
-        arrays = {name: [] for name in ("seq_ptr", "item_ptr", "attr_id", "labels", "state_fid", "trans_fid")}
-        n_seqs, num_attrs, num_labels, num_features = [], [], [], []
-        for seq_ptr, item_ptr, attr_id, labels, A, state_fid, trans_fid, K in problems:
-            state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
-            if int(A) < 1 or state_fid.size % int(A) != 0:
-                raise ValueError("state_fid must have num_attrs * L entries")
-            L = state_fid.size // int(A)
-            if trans_fid.size != L * L:
-                raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
-            seq_ptr = _i32(seq_ptr)
-            for name, a in zip(arrays, (seq_ptr, _i32(item_ptr), _i32(attr_id), _i32(labels), state_fid, trans_fid)):
-                arrays[name].append(a if a.size else np.zeros(1, dtype=np.int32))
-            n_seqs.append(len(seq_ptr) - 1)
-            num_attrs.append(int(A))
-            num_labels.append(L)
-            num_features.append(int(K))
-        ptrs = {name: (_vp * max(n, 1))(*[a.ctypes.data for a in arrs]) for name, arrs in arrays.items()}
-        ints = [np.ascontiguousarray(v if v else [0], dtype=np.int32) for v in (n_seqs, num_attrs, num_labels, num_features)]
         h = _vp()
-        _check(self._lib.gecco_crf_trainer_batch_create(
-            int(device), n, ptrs["seq_ptr"], _ptr(ints[0], _c_i32p), ptrs["item_ptr"], ptrs["attr_id"], ptrs["labels"],
-            _ptr(ints[1], _c_i32p), _ptr(ints[2], _c_i32p), int(window), int(step), ptrs["state_fid"], ptrs["trans_fid"],
-            _ptr(ints[3], _c_i32p), ctypes.byref(h)))
+        _check(self._c("create")(*args, ctypes.byref(h)))
         self._h = h
-        self.num_features = list(num_features)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
-            self._lib.gecco_crf_trainer_batch_free(h)
+            self._c("free")(h)
 
     def __len__(self) -> int:
-        return int(self._lib.gecco_crf_trainer_batch_num_problems(self._h))
+        return int(self._c("num_problems")(self._h))
 
     def num_windows(self, k: int) -> int:
-        return int(self._lib.gecco_crf_trainer_batch_num_windows(self._h, int(k)))
+        return int(self._c("num_windows")(self._h, int(k)))
 
-    def eval(self, ws, active=None, f=None, g=None):
+    def _eval_problems(self, ws, active=None, f=None, g=None):
         """f and g of every active problem (all of them when ``active`` is None) under the weights ``ws[k]`` (None for
         an inactive problem).  Returns ``(f, g)``: an ``(n,)`` float64 array and a list of gradient arrays.  Given ``f``
         and ``g`` are written in place, and the entries of inactive problems are left as they were."""
-        n = len(self.num_features)
-        act = np.ones(n, dtype=np.uint8) if active is None else np.ascontiguousarray(active, dtype=np.uint8)
-        if act.shape != (n,):
-            raise ValueError(f"expected an active mask of {n} entries, got shape {act.shape}")
+        features = self._features  # (of every problem)
+        n = len(features)
+        active = [True] * n if active is None else [bool(a) for a in active]
+        if len(active) != n:
+            raise ValueError(f"expected an active mask of {n} entries, got {len(active)}")
         if f is None:
             f = np.full(n, np.nan)
         if g is None:
-            g = [np.empty(K) for K in self.num_features]
+            g = [np.empty(K) for K in features]
         if not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.shape == (n,) and f.flags.c_contiguous):
             raise ValueError("f must be a contiguous float64 array of one entry per problem")
-        wk, gk = [], []
-        w_ptr, g_ptr = (_vp * max(n, 1))(), (_vp * max(n, 1))()
+        keep = []
+        w_ptr, g_ptr = (_vp * n)(), (_vp * n)()
         for k in range(n):
-            if not act[k]:
+            if not active[k]:
                 continue
-            K = self.num_features[k]
+            K = features[k]
             w = np.ascontiguousarray(ws[k], dtype=np.float64)
             if w.shape != (K,):
                 raise ValueError(f"problem {k}: expected {K} weights, got shape {w.shape}")
@@ -1279,14 +1251,64 @@ class TrainerBatch:
                 raise ValueError(f"problem {k}: the gradient must be a contiguous float64 array of {K} entries")
             w = w if w.size else np.zeros(1)
             gb = gg if gg.size else np.zeros(1)
-            wk.append(w)
-            gk.append(gb)
-            w_ptr[k], g_ptr[k] = w.ctypes.data, gb.ctypes.data
-        _check(self._eval_native(_ptr(act, _c_u8p), w_ptr, _ptr(f, _c_f64p), g_ptr))
+            keep += [w, gb]
+            w_ptr[k], g_ptr[k] = w.ctypes.data, _out_address(gb)
+        _check(self._eval_native((ctypes.c_uint8 * n)(*active), w_ptr, _out_address(f), g_ptr))
         return f, g
 
     def _eval_native(self, act, w_ptr, f, g_ptr):
-        return self._lib.gecco_crf_trainer_batch_eval(self._h, act, w_ptr, f, g_ptr)
+        return self._c("eval")(self._h, act, w_ptr, f, g_ptr)
+
+
+class Trainer(_TrainerHandle):
+    """Training set of a 2-label CRF resident on one device (``gecco_crf_trainer_*``): ``eval(w)`` returns the summed
+    negative log-likelihood of every training window and its gradient over the ``num_features`` generated features."""
+
+    _family = "gecco_crf_trainer"
+
+    def __init__(self, seq_ptr, item_ptr, attr_id, labels, num_attrs: int, window: int, step: int, state_fid, trans_fid,
+                 num_features: int, device: int = 0):
+        arrays, counts = _trainer_sets([(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)])
+        a = {name: _ptr(arrs[0], _c_i32p) for name, arrs in arrays.items()}
+        self._create(int(device), a["seq_ptr"], counts["n_seqs"][0], a["item_ptr"], a["attr_id"], a["labels"],
+                     counts["num_attrs"][0], counts["num_labels"][0], int(window), int(step), a["state_fid"], a["trans_fid"],
+                     counts["num_features"][0])
+        self._features = counts["num_features"]
+        self.num_features = self._features[0]
+
+    def __len__(self) -> int:  # (the lone family has no num_problems)
+        return 1
+
+    @property
+    def num_windows(self) -> int:
+        return int(self._c("num_windows")(self._h))
+
+    def eval(self, w):
+        f, g = self._eval_problems([w])
+        return float(f[0]), g[0]
+
+    def _eval_native(self, act, w_ptr, f, g_ptr):
+        return self._c("eval")(self._h, w_ptr[0], f, g_ptr[0])
+
+
+class TrainerBatch(_TrainerHandle):
+    """Several training sets of 2-label CRFs resident on one device at once (``gecco_crf_trainer_batch_*``).
+
+    ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)``
+    per problem, as ``Trainer`` takes them; ``window`` and ``step`` are shared.  ``eval(ws, active)`` evaluates the active
+    problems in one batched pass; problem k's f and g are bitwise what a lone ``Trainer`` of it returns for ``ws[k]``."""
+
+    _family = "gecco_crf_trainer_batch"
+    eval = _TrainerHandle._eval_problems
+
+    def __init__(self, problems, window: int, step: int, device: int = 0):
+        arrays, counts = _trainer_sets(problems)
+        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
+        c = {name: _i32_vector(v) for name, v in counts.items()}
+        self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], t["labels"],
+                     c["num_attrs"], c["num_labels"], int(window), int(step), t["state_fid"], t["trans_fid"],
+                     c["num_features"])
+        self.num_features = self._features = counts["num_features"]
 
 
 class TrainerGrid(TrainerBatch):
@@ -1297,59 +1319,21 @@ class TrainerGrid(TrainerBatch):
     ``scratch_budget_bytes`` caps the work space of one group of problems (0: no cap).  ``eval`` is ``TrainerBatch``'s;
     problem k's f and g are bitwise what a lone ``Trainer`` of its set returns for ``ws[k]``."""
 
+    _family = "gecco_crf_trainer_grid"
+
     def __init__(self, sets, problem_set, scratch_budget_bytes: int = 0, device: int = 0):
-        self._lib = load_library()
-        self._h = None
-        n = len(sets)
-        arrays = {name: [] for name in ("seq_ptr", "item_ptr", "attr_id", "labels", "state_fid", "trans_fid")}
-        n_seqs, num_attrs, num_labels, num_features, windows, steps = [], [], [], [], [], []
-        for seq_ptr, item_ptr, attr_id, labels, A, state_fid, trans_fid, K, window, step in sets:
-            state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
-            if int(A) < 1 or state_fid.size % int(A) != 0:
-                raise ValueError("state_fid must have num_attrs * L entries")
-            L = state_fid.size // int(A)
-            if trans_fid.size != L * L:
-                raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
-            seq_ptr = _i32(seq_ptr)
-            for name, a in zip(arrays, (seq_ptr, _i32(item_ptr), _i32(attr_id), _i32(labels), state_fid, trans_fid)):
-                arrays[name].append(a if a.size else np.zeros(1, dtype=np.int32))
-            n_seqs.append(len(seq_ptr) - 1)
-            num_attrs.append(int(A))
-            num_labels.append(L)
-            num_features.append(int(K))
-            windows.append(int(window))
-            steps.append(int(step))
+        arrays, counts = _trainer_sets(sets)
+        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
+        c = {name: _i32_vector(v) for name, v in counts.items()}
         pset = _i32(problem_set).ravel()
-        ptrs = {name: (_vp * max(n, 1))(*[a.ctypes.data for a in arrs]) for name, arrs in arrays.items()}
-        ints = [np.ascontiguousarray(v if v else [0], dtype=np.int32)
-                for v in (n_seqs, num_attrs, num_labels, num_features, windows, steps)]
-        pset_c = pset if pset.size else np.zeros(1, dtype=np.int32)
-        h = _vp()
-        _check(self._lib.gecco_crf_trainer_grid_create(
-            int(device), n, ptrs["seq_ptr"], _ptr(ints[0], _c_i32p), ptrs["item_ptr"], ptrs["attr_id"], ptrs["labels"],
-            _ptr(ints[1], _c_i32p), _ptr(ints[2], _c_i32p), _ptr(ints[4], _c_i32p), _ptr(ints[5], _c_i32p),
-            ptrs["state_fid"], ptrs["trans_fid"], _ptr(ints[3], _c_i32p), int(pset.size), _ptr(pset_c, _c_i32p),
-            int(scratch_budget_bytes), ctypes.byref(h)))
-        self._h = h
-        self.num_features = [num_features[s] for s in pset.tolist()]
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            self._lib.gecco_crf_trainer_grid_free(h)
-
-    def __len__(self) -> int:
-        return int(self._lib.gecco_crf_trainer_grid_num_problems(self._h))
-
-    def num_windows(self, k: int) -> int:
-        return int(self._lib.gecco_crf_trainer_grid_num_windows(self._h, int(k)))
+        self._create(int(device), len(sets), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], t["labels"],
+                     c["num_attrs"], c["num_labels"], c["window"], c["step"], t["state_fid"], t["trans_fid"],
+                     c["num_features"], int(pset.size), _i32_vector(pset), int(scratch_budget_bytes))
+        self.num_features = self._features = [counts["num_features"][s] for s in pset.tolist()]
 
     def scratch_bytes(self, k: int = -1) -> int:
         """Scratch bytes of problem k; for k = -1 the work space allocated (the most one group of problems uses)."""
-        return int(self._lib.gecco_crf_trainer_grid_scratch_bytes(self._h, int(k)))
-
-    def _eval_native(self, act, w_ptr, f, g_ptr):
-        return self._lib.gecco_crf_trainer_grid_eval(self._h, act, w_ptr, f, g_ptr)
+        return int(self._c("scratch_bytes")(self._h, int(k)))
 
 
 def fisher_exact(tables, device: int = 0) -> np.ndarray:

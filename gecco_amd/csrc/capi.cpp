@@ -6,6 +6,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <vector>
 
 #include "../../include/gecco_crf.h"
 #include "crf_exact_exp.hpp"
@@ -916,11 +917,48 @@ GECCO_API int gecco_crf_tsv_format(int64_t n_rows, int32_t n_cols, const int32_t
 }
 GECCO_API void gecco_crf_buffer_free(uint8_t *p) { std::free(p); }
 
-// ---- training (ABI 2.3.0) ---------------------------------------------------------------------
-struct gecco_crf_trainer {
+// ---- training (ABI 2.3.0 lone, 2.5.0 batch, 2.8.0 grid) ---------------------------------------
+// The three families are argument shapes of one Trainer (crf_train.hpp), and each opaque handle is that Trainer.
+namespace {
+
+int fail(const char *msg) {
+    set_error(msg);
+    return GECCO_CRF_EINVAL;
+}
+
+Trainer *trainer_of(void *h) { return static_cast<Trainer *>(h); }
+const Trainer *trainer_of(const void *h) { return static_cast<const Trainer *>(h); }
+
+// trainer_create's arguments; `out` is not NULL.
+template <class Handle>
+int trainer_open(Handle **out, const char *family, int32_t device, int32_t n_sets, const int32_t *const *seq_ptr,
+                 const int32_t *n_seqs, const int32_t *const *item_ptr, const int32_t *const *attr_id,
+                 const int32_t *const *labels, const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window,
+                 const int32_t *step, const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                 const int32_t *num_features, int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget_bytes) {
+    DeviceGuard guard;
     Trainer *t = nullptr;
-    ~gecco_crf_trainer() { trainer_destroy(t); }
-};
+    int rc = trainer_create(device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
+                            state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes, family, &t);
+    *out = reinterpret_cast<Handle *>(t);
+    return rc;
+}
+
+int trainer_run(Trainer *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
+    if (!t) return GECCO_CRF_EINVAL;
+    GECCO_GUARD_BEGIN
+    DeviceGuard guard;
+    return trainer_eval(t, active, w, f, g);
+    GECCO_GUARD_END
+}
+
+void trainer_close(Trainer *t) {
+    if (!t) return;
+    DeviceGuard guard;
+    trainer_destroy(t);
+}
+
+}  // namespace
 
 GECCO_API int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr,
                                        const int32_t *attr_id, const int32_t *labels, int32_t num_attrs, int32_t num_labels,
@@ -929,37 +967,16 @@ GECCO_API int gecco_crf_trainer_create(int32_t device, const int32_t *seq_ptr, i
     if (!out) return GECCO_CRF_EINVAL;
     *out = nullptr;
     GECCO_GUARD_BEGIN
-    DeviceGuard guard;
-    auto h = std::make_unique<gecco_crf_trainer>();
-    int rc = trainer_create(device, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step, state_fid,
-                            trans_fid, num_features, &h->t);
-    if (rc) return rc;
-    *out = h.release();
-    return GECCO_CRF_OK;
+    return trainer_open(out, nullptr, device, 1, &seq_ptr, &n_seqs, &item_ptr, &attr_id, &labels, &num_attrs, &num_labels,
+                        &window, &step, &state_fid, &trans_fid, &num_features, 1, nullptr, 0);
     GECCO_GUARD_END
 }
-
 GECCO_API int gecco_crf_trainer_eval(gecco_crf_trainer *t, const double *w, double *f, double *g) {
-    if (!t) return GECCO_CRF_EINVAL;
-    GECCO_GUARD_BEGIN
-    DeviceGuard guard;
-    return trainer_eval(t->t, w, f, g);
-    GECCO_GUARD_END
+    const uint8_t active = 1;
+    return trainer_run(trainer_of(t), &active, &w, f, &g);
 }
-
-GECCO_API int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t) { return t ? trainer_num_windows(t->t, 0) : -1; }
-
-GECCO_API void gecco_crf_trainer_free(gecco_crf_trainer *t) {
-    if (!t) return;
-    DeviceGuard guard;
-    delete t;
-}
-
-// ---- training, several problems at once (ABI 2.5.0) --------------------------------------------
-struct gecco_crf_trainer_batch {
-    Trainer *t = nullptr;
-    ~gecco_crf_trainer_batch() { trainer_destroy(t); }
-};
+GECCO_API int64_t gecco_crf_trainer_num_windows(const gecco_crf_trainer *t) { return trainer_num_windows(trainer_of(t), 0); }
+GECCO_API void gecco_crf_trainer_free(gecco_crf_trainer *t) { trainer_close(trainer_of(t)); }
 
 GECCO_API int gecco_crf_trainer_batch_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
                                              const int32_t *n_seqs, const int32_t *const *item_ptr,
@@ -970,44 +987,26 @@ GECCO_API int gecco_crf_trainer_batch_create(int32_t device, int32_t n_problems,
     if (!out) return GECCO_CRF_EINVAL;
     *out = nullptr;
     GECCO_GUARD_BEGIN
-    DeviceGuard guard;
-    auto h = std::make_unique<gecco_crf_trainer_batch>();
-    int rc = trainer_batch_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
-                                  step, state_fid, trans_fid, num_features, &h->t);
-    if (rc) return rc;
-    *out = h.release();
-    return GECCO_CRF_OK;
+    if (n_problems < 1) return fail("trainer batch: at least one problem is needed");
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !state_fid || !trans_fid ||
+        !num_features)
+        return fail("trainer batch: null argument");
+    const std::vector<int32_t> windows(size_t(n_problems), window), steps(size_t(n_problems), step);
+    return trainer_open(out, "batch", device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
+                        windows.data(), steps.data(), state_fid, trans_fid, num_features, n_problems, nullptr, 0);
     GECCO_GUARD_END
 }
-
 GECCO_API int gecco_crf_trainer_batch_eval(gecco_crf_trainer_batch *t, const uint8_t *active, const double *const *w, double *f,
                                            double *const *g) {
-    if (!t) return GECCO_CRF_EINVAL;
-    GECCO_GUARD_BEGIN
-    DeviceGuard guard;
-    return trainer_batch_eval(t->t, active, w, f, g);
-    GECCO_GUARD_END
+    return trainer_run(trainer_of(t), active, w, f, g);
 }
-
 GECCO_API int32_t gecco_crf_trainer_batch_num_problems(const gecco_crf_trainer_batch *t) {
-    return t ? trainer_num_problems(t->t) : -1;
+    return trainer_num_problems(trainer_of(t));
 }
-
 GECCO_API int64_t gecco_crf_trainer_batch_num_windows(const gecco_crf_trainer_batch *t, int32_t k) {
-    return t ? trainer_num_windows(t->t, k) : -1;
+    return trainer_num_windows(trainer_of(t), k);
 }
-
-GECCO_API void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t) {
-    if (!t) return;
-    DeviceGuard guard;
-    delete t;
-}
-
-// ---- training, a grid of problems over shared sets (ABI 2.8.0) ---------------------------------
-struct gecco_crf_trainer_grid {
-    Trainer *t = nullptr;
-    ~gecco_crf_trainer_grid() { trainer_destroy(t); }
-};
+GECCO_API void gecco_crf_trainer_batch_free(gecco_crf_trainer_batch *t) { trainer_close(trainer_of(t)); }
 
 GECCO_API int gecco_crf_trainer_grid_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                                             const int32_t *const *item_ptr, const int32_t *const *attr_id,
@@ -1019,42 +1018,29 @@ GECCO_API int gecco_crf_trainer_grid_create(int32_t device, int32_t n_sets, cons
     if (!out) return GECCO_CRF_EINVAL;
     *out = nullptr;
     GECCO_GUARD_BEGIN
-    DeviceGuard guard;
-    auto h = std::make_unique<gecco_crf_trainer_grid>();
-    int rc = trainer_grid_create(device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
-                                 state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes, &h->t);
-    if (rc) return rc;
-    *out = h.release();
-    return GECCO_CRF_OK;
+    if (n_sets < 1) return fail("trainer grid: at least one set is needed");
+    if (n_problems < 1) return fail("trainer grid: at least one problem is needed");
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !window || !step ||
+        !state_fid || !trans_fid || !num_features || !problem_set)
+        return fail("trainer grid: null argument");
+    return trainer_open(out, "grid", device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
+                        step, state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes);
     GECCO_GUARD_END
 }
-
 GECCO_API int gecco_crf_trainer_grid_eval(gecco_crf_trainer_grid *t, const uint8_t *active, const double *const *w, double *f,
                                           double *const *g) {
-    if (!t) return GECCO_CRF_EINVAL;
-    GECCO_GUARD_BEGIN
-    DeviceGuard guard;
-    return trainer_batch_eval(t->t, active, w, f, g);
-    GECCO_GUARD_END
+    return trainer_run(trainer_of(t), active, w, f, g);
 }
-
 GECCO_API int32_t gecco_crf_trainer_grid_num_problems(const gecco_crf_trainer_grid *t) {
-    return t ? trainer_num_problems(t->t) : -1;
+    return trainer_num_problems(trainer_of(t));
 }
-
 GECCO_API int64_t gecco_crf_trainer_grid_num_windows(const gecco_crf_trainer_grid *t, int32_t k) {
-    return t ? trainer_num_windows(t->t, k) : -1;
+    return trainer_num_windows(trainer_of(t), k);
 }
-
 GECCO_API int64_t gecco_crf_trainer_grid_scratch_bytes(const gecco_crf_trainer_grid *t, int32_t k) {
-    return t ? trainer_scratch_bytes(t->t, k) : -1;
+    return trainer_scratch_bytes(trainer_of(t), k);
 }
-
-GECCO_API void gecco_crf_trainer_grid_free(gecco_crf_trainer_grid *t) {
-    if (!t) return;
-    DeviceGuard guard;
-    delete t;
-}
+GECCO_API void gecco_crf_trainer_grid_free(gecco_crf_trainer_grid *t) { trainer_close(trainer_of(t)); }
 
 // ---- feature selection (ABI 2.4.0) ------------------------------------------------------------
 GECCO_API int gecco_crf_fisher_exact(int32_t device, const int64_t *tables, int64_t n, double *pvalue) {

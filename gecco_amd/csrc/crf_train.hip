@@ -576,8 +576,6 @@ void append(std::vector<T> &dst, const std::vector<T> &src) {
 
 static_assert(sizeof(Slot) % alignof(double) == 0 && sizeof(ItemGroup) % alignof(int32_t) == 0, "upload layout");
 
-enum Kind { kLone, kBatch, kGrid };
-
 }  // namespace
 
 // Training sets and problems resident on one device.  A set is a training set, uploaded once (every set's arrays
@@ -589,7 +587,7 @@ enum Kind { kLone, kBatch, kGrid };
 // one to the last.
 struct Trainer {
     int device = 0;
-    Kind kind = kLone;
+    std::string family;  // "batch" / "grid" in error messages; empty: a lone trainer, which keeps its own messages
     struct Set {
         int32_t A, n_items, K, W;
         int64_t n_win;
@@ -632,17 +630,19 @@ namespace {
 
 int64_t blocks_of(int64_t n, int per) { return (n + per - 1) / per; }
 
-// Sets as build_problem takes them, problem k on set problem_set[k] (NULL: set k).  Errors of a batch name the problem
-// ("problem k: ..."), those of a grid the set or problem; a lone trainer keeps its own messages.  scratch_budget <= 0
-// (and every lone trainer or batch): all problems fit in one group.
-int create_impl(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
-                const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
-                const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
-                const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget, Kind kind, Trainer **out) {
+}  // namespace
+
+// Sets as build_problem takes them.  A set's error names it after what the caller numbers: the set where problems pick
+// their sets (problem_set), the problem where problem k is set k.
+int trainer_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                   const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                   const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                   const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                   int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget, const char *family,
+                   Trainer **out) {
     auto t = std::make_unique<Trainer>();
     t->device = device;
-    t->kind = kind;
+    if (family) t->family = family;
     std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c, attr_items_c;
     std::vector<SetDev> layout;
     for (int32_t k = 0; k < n_sets; ++k) {
@@ -650,8 +650,9 @@ int create_impl(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, c
         int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
                                window[k], step[k], state_fid[k], trans_fid[k], num_features[k], &hp);
         if (rc) {
-            if (kind == kBatch) set_error("trainer batch: problem " + std::to_string(k) + ": " + last_error());
-            if (kind == kGrid) set_error("trainer grid: set " + std::to_string(k) + ": " + last_error());
+            if (family)
+                set_error("trainer " + t->family + (problem_set ? ": set " : ": problem ") + std::to_string(k) + ": " +
+                          last_error());
             return rc;
         }
         SetDev d;
@@ -694,12 +695,12 @@ int create_impl(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, c
         blocks[1] += blocks_of(S.n_win, kTrainWinThreads);
         blocks[2] += S.A;
     }
-    // (a grid cuts its groups at 2^31 workgroups instead)
-    if (kind != kGrid)
+    // (with a scratch budget the evaluation runs in groups, and cuts them at 2^31 workgroups as well)
+    if (!problem_set)
         for (int64_t b : blocks)
             if (b > INT32_MAX) return fail("trainer batch: the problems need more than 2^31 workgroups in one launch");
     t->scratch_cap = scratch_total;
-    if (kind == kGrid && scratch_budget > 0) t->scratch_cap = std::max(scratch_max, std::min(scratch_budget, scratch_total));
+    if (scratch_budget > 0) t->scratch_cap = std::max(scratch_max, std::min(scratch_budget, scratch_total));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         set_error("no HIP device available (this library has no CPU fallback)");
@@ -735,49 +736,6 @@ int create_impl(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, c
     return GECCO_CRF_OK;
 }
 
-}  // namespace
-
-int trainer_create(int32_t device, const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
-                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
-                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, Trainer **out) {
-    if (!out) return fail("trainer: null argument");
-    *out = nullptr;
-    return create_impl(device, 1, &seq_ptr, &n_seqs, &item_ptr, &attr_id, &labels, &num_attrs, &num_labels, &window, &step,
-                       &state_fid, &trans_fid, &num_features, 1, nullptr, 0, kLone, out);
-}
-
-int trainer_batch_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
-                         const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
-                         const int32_t *num_attrs, const int32_t *num_labels, int32_t window, int32_t step,
-                         const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                         Trainer **out) {
-    if (!out) return fail("trainer batch: null argument");
-    *out = nullptr;
-    if (n_problems < 1) return fail("trainer batch: at least one problem is needed");
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !state_fid || !trans_fid ||
-        !num_features)
-        return fail("trainer batch: null argument");
-    const std::vector<int32_t> windows(size_t(n_problems), window), steps(size_t(n_problems), step);
-    return create_impl(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, windows.data(),
-                       steps.data(), state_fid, trans_fid, num_features, n_problems, nullptr, 0, kBatch, out);
-}
-
-int trainer_grid_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr, const int32_t *n_seqs,
-                        const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
-                        const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
-                        const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                        int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget_bytes, Trainer **out) {
-    if (!out) return fail("trainer grid: null argument");
-    *out = nullptr;
-    if (n_sets < 1) return fail("trainer grid: at least one set is needed");
-    if (n_problems < 1) return fail("trainer grid: at least one problem is needed");
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !window || !step ||
-        !state_fid || !trans_fid || !num_features || !problem_set)
-        return fail("trainer grid: null argument");
-    return create_impl(device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
-                       state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes, kGrid, out);
-}
-
 namespace {
 
 // One group of an evaluation: slots [s0, s1) and item groups [g0, g1) of the upload, its grids, the largest W and the
@@ -797,13 +755,14 @@ void launch_item_scores(const Group &gr, const ItemGroup *igs, const Slot *slots
 
 }  // namespace
 
-int trainer_batch_eval(Trainer *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
-    const std::string name = t && t->kind == kGrid ? "trainer_grid_eval" : "trainer_batch_eval";
+int trainer_eval(Trainer *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
+    const bool lone = !t || t->family.empty();
+    const std::string name = lone ? "trainer_eval" : "trainer_" + t->family + "_eval";
     if (!t || !active || !w || !f || !g) return fail(name + ": null argument");
     const int32_t P = int32_t(t->probs.size());
     for (int32_t k = 0; k < P; ++k)
         if (active[k] && (!g[k] || (t->sets[size_t(t->probs[k].set)].K > 0 && !w[k])))
-            return fail(name + ": null argument for problem " + std::to_string(k));
+            return fail(name + ": null argument" + (lone ? "" : " for problem " + std::to_string(k)));
     Slot *slots = reinterpret_cast<Slot *>(t->h_in.data());
     ItemGroup *igs = reinterpret_cast<ItemGroup *>(t->h_in.data() + t->igs_off);
     double *wstate = reinterpret_cast<double *>(t->h_in.data() + t->ws_off);
@@ -929,12 +888,6 @@ int trainer_batch_eval(Trainer *t, const uint8_t *active, const double *const *w
             if (p.trans_fid[j] >= 0) gk[p.trans_fid[j]] += o[1 + j];
     }
     return GECCO_CRF_OK;
-}
-
-int trainer_eval(Trainer *t, const double *w, double *f, double *g) {
-    if (!t || !f || !g || (t->sets[0].K > 0 && !w)) return fail("trainer_eval: null argument");
-    const uint8_t active = 1;
-    return trainer_batch_eval(t, &active, &w, f, &g);
 }
 
 int32_t trainer_num_problems(const Trainer *t) { return t ? int32_t(t->probs.size()) : -1; }

@@ -253,6 +253,34 @@ def _fold_indices(seqs: List[List[Any]], splits: SplitSpec) -> List[Tuple[Any, A
     return list(splits)
 
 
+def _clone(crf: Any, window_size: int, options: Dict[str, Any]) -> Any:
+    """An unfitted model like the template ``crf`` with the given window size and trainer options."""
+    model = type(crf)(crf.feature_type, crf.algorithm, window_size, crf.window_step, **options)
+    model.devices, model.reference_bits = list(crf.devices), crf.reference_bits
+    return model
+
+
+def _fold_selection(model: Any, seqs: List[List[Any]], train_idx: Any, select: Optional[float],
+                    correction_method: Optional[str]) -> Tuple[List[Any], Any, Any]:
+    """A fold's training genes after ``fit``'s Fisher selection, with the significance table and the kept features
+    (both None without ``select``)."""
+    train_genes: List[Any] = [gene for i in train_idx for gene in seqs[i]]
+    if select is None:
+        return train_genes, None, None
+    return model._select_features(train_genes, select, correction_method)
+
+
+def _fold_truth(seqs: List[List[Any]], test_idx: Any) -> Tuple[List[Any], Dict[Tuple[str, str, int, int], bool]]:
+    """A fold's test genes and their labels by gene key."""
+    truth_genes = [gene for i in test_idx for gene in seqs[i]]
+    truth: Dict[Tuple[str, str, int, int], bool] = {}
+    for gene in truth_genes:
+        key, label = _gene_key(gene), gene.average_probability > 0.5
+        if truth.setdefault(key, label) != label:
+            raise ValueError(f"two genes {key!r} with different labels")
+    return truth_genes, truth
+
+
 def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle: bool = True,
                    select: Optional[float] = None, correction_method: Optional[str] = None) -> CrossValidation:
     """Cross-validate the unfitted ``ClusterCRF`` template ``crf`` (its feature type, window, trainer options, ``devices``
@@ -271,13 +299,9 @@ def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle
     template_options = {k: v for k, v in crf._options.items() if k != "algorithm"}
     models, sets, params = [], [], None
     for train_idx, _ in folds_idx:
-        model = type(crf)(crf.feature_type, crf.algorithm, crf.window_size, crf.window_step, **template_options)
-        model.devices, model.reference_bits = list(crf.devices), crf.reference_bits
-        train_genes: List[Any] = [gene for i in train_idx for gene in seqs[i]]
-        sig = keep = None
-        if select is not None:
-            train_genes, sig, keep = model._select_features(train_genes, select, correction_method)
-        model.significance, model.significant_features = sig, keep
+        model = _clone(crf, crf.window_size, template_options)
+        train_genes, model.significance, model.significant_features = _fold_selection(model, seqs, train_idx, select,
+                                                                                      correction_method)
         ts, params = model._training_set(train_genes, shuffle=shuffle)
         models.append(model)
         sets.append(ts)
@@ -286,12 +310,7 @@ def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle
     folds = []
     for k, ((train_idx, test_idx), model, ts, result) in enumerate(zip(folds_idx, models, sets, results)):
         model._adopt_fit(ts, result)
-        truth_genes = [gene for i in test_idx for gene in seqs[i]]
-        truth: Dict[Tuple[str, str, int, int], bool] = {}
-        for gene in truth_genes:
-            key, label = _gene_key(gene), gene.average_probability > 0.5
-            if truth.setdefault(key, label) != label:
-                raise ValueError(f"two genes {key!r} with different labels")
+        truth_genes, truth = _fold_truth(seqs, test_idx)
         predicted = model.predict_probabilities([_test_copy(gene) for gene in truth_genes])
         is_cluster = [truth[_gene_key(gene)] for gene in predicted]
         auroc, aupr = _metrics(is_cluster, [g.average_probability for g in predicted]) if predicted else (math.nan, math.nan)
@@ -505,20 +524,14 @@ def grid_search(crf: Any, genes: Iterable[Any], splits: SplitSpec, grid: Dict[st
         # (the template's options with the point's values, as the point's own template would hold them)
         options = dict(template_options)
         options.update({k: pt[k] for k in ("c1", "c2") if k in grid or k in options})
-        model = type(crf)(crf.feature_type, crf.algorithm, pt["window_size"], crf.window_step, **options)
-        model.devices, model.reference_bits = list(crf.devices), crf.reference_bits
-        return model
+        return _clone(crf, pt["window_size"], options)
 
     windows = list(dict.fromkeys(pt["window_size"] for pt in points))
     sets: List[Any] = []
     set_of: Dict[Tuple[int, int], int] = {}
     selection = []
     for f, (train_idx, _) in enumerate(folds_idx):
-        template = model_of(points[0])
-        train_genes: List[Any] = [gene for i in train_idx for gene in seqs[i]]
-        sig = keep = None
-        if select is not None:
-            train_genes, sig, keep = template._select_features(train_genes, select, correction_method)
+        train_genes, sig, keep = _fold_selection(model_of(points[0]), seqs, train_idx, select, correction_method)
         selection.append((sig, keep))
         state = random.getstate()
         for w in windows:  # (every window size draws the same shuffle: the state before it is restored)
@@ -533,12 +546,7 @@ def grid_search(crf: Any, genes: Iterable[Any], splits: SplitSpec, grid: Dict[st
 
     tests = []
     for train_idx, test_idx in folds_idx:
-        truth_genes = [gene for i in test_idx for gene in seqs[i]]
-        truth: Dict[Tuple[str, str, int, int], bool] = {}
-        for gene in truth_genes:
-            key, label = _gene_key(gene), gene.average_probability > 0.5
-            if truth.setdefault(key, label) != label:
-                raise ValueError(f"two genes {key!r} with different labels")
+        truth_genes, truth = _fold_truth(seqs, test_idx)
         encoded = _encode_test_genes([_test_copy(gene) for gene in truth_genes], crf.feature_type)
         keys = [_gene_key(gene) for gene in encoded[0]]
         tests.append((encoded, keys, [truth[k] for k in keys]))

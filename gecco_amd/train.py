@@ -234,6 +234,11 @@ class TrainingSet:
     def num_features(self) -> int:
         return len(self.state_attr) + len(self.trans_src)
 
+    def native_args(self) -> tuple:
+        """The set as ``_native.TrainerGrid`` takes it (``TrainerBatch``: without the last two, window and step)."""
+        return (self.seq_ptr, self.item_ptr, self.attr_id, self.labels, len(self.attrs_), self.state_fid, self.trans_fid,
+                self.num_features, self.window, self.step)
+
 
 def _coverage(n: int, window: int, step: int) -> np.ndarray:
     """Number of windows (gecco/_meta.py:124-132 ``sliding_window``) covering every position of a sequence of n items."""
@@ -337,27 +342,16 @@ def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0
     """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0."""
     from . import _native
 
-    trainer = _native.Trainer(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.window, ts.step,
-                              ts.state_fid, ts.trans_fid, ts.num_features, device=device)
-    c2 = float(params["c2"])
-
-    def fg(w):
-        f, g = trainer.eval(w)
-        if c2 > 0:
-            f += c2 * float(np.dot(w, w))
-            g = g + (2.0 * c2) * w
-        return f, g
-
-    return minimize(fg, np.zeros(ts.num_features), c1=float(params["c1"]), num_memories=int(params["num_memories"]),
-                    epsilon=float(params["epsilon"]), period=int(params["period"]), delta=float(params["delta"]),
-                    max_iterations=params["max_iterations"], callback=callback)
+    args = ts.native_args()
+    trainer = _native.Trainer(*args[:5], *args[8:], *args[5:8], device=device)  # (it takes window and step in the middle)
+    return _fit_lockstep(trainer, [ts], [params], callback)[0]
 
 
 def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], device: int = 0) -> List[OptimizeResult]:
     """``fit_training_set`` of every set at once: all sets are resident on the device together (``_native.TrainerBatch``)
     and one optimiser per set runs in lock-step, each round evaluating the pending points of the unfinished sets in one
     batched pass.  Sets drop out as they stop.  Result k is exactly ``fit_training_set(sets[k], params, device)``:
-    the batched objective gives every set the bits a lone trainer gives it, and the host adds the same L2 term.
+    the batched objective gives every set the bits a lone trainer gives it, and the optimiser loop is the same one.
     The sets must share ``window`` and ``step``."""
     from . import _native
 
@@ -366,8 +360,7 @@ def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], de
     window, step = sets[0].window, sets[0].step
     if any(ts.window != window or ts.step != step for ts in sets):
         raise ValueError("fit_training_sets: every training set must have the same window and step")
-    batch = _native.TrainerBatch([(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.state_fid,
-                                   ts.trans_fid, ts.num_features) for ts in sets], window, step, device=device)
+    batch = _native.TrainerBatch([ts.native_args()[:-2] for ts in sets], window, step, device=device)
     return _fit_lockstep(batch, sets, [params] * len(sets))
 
 
@@ -389,34 +382,37 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
     for k, (s, _) in enumerate(problems):
         if not 0 <= int(s) < len(sets):
             raise ValueError(f"fit_grid: problem {k} names set {s}, but there are {len(sets)} sets")
-    grid = _native.TrainerGrid([(ts.seq_ptr, ts.item_ptr, ts.attr_id, ts.labels, len(ts.attrs_), ts.state_fid, ts.trans_fid,
-                                 ts.num_features, ts.window, ts.step) for ts in sets],
-                               [int(s) for s, _ in problems], scratch_budget_bytes, device=device)
+    grid = _native.TrainerGrid([ts.native_args() for ts in sets], [int(s) for s, _ in problems], scratch_budget_bytes,
+                               device=device)
     return _fit_lockstep(grid, [sets[int(s)] for s, _ in problems], [p for _, p in problems])
 
 
-def _fit_lockstep(trainer, sets: Sequence[TrainingSet], params: Sequence[Dict[str, object]]) -> List[OptimizeResult]:
-    """One optimiser per problem of ``trainer`` (a ``TrainerBatch`` or ``TrainerGrid``; problem k trains ``sets[k]`` with
-    ``params[k]``) in lock-step; problems drop out as they stop.  The host adds each problem's L2 term as
-    ``fit_training_set`` does."""
+def _fit_lockstep(trainer, sets: Sequence[TrainingSet], params: Sequence[Dict[str, object]],
+                  callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> List[OptimizeResult]:
+    """The optimiser loop of every fit: one ``minimize_steps`` per problem of ``trainer`` (a ``_native`` trainer of any
+    family; problem k trains ``sets[k]`` with ``params[k]``) in lock-step, each round evaluating the pending points of the
+    unfinished problems in one pass; problems drop out as they stop.  The host adds each problem's L2 term.  ``callback``
+    goes to every problem's optimiser (``fit_training_set`` has one problem)."""
     n = len(sets)
     steppers = [minimize_steps(np.zeros(ts.num_features), c1=float(p["c1"]), num_memories=int(p["num_memories"]),
                                epsilon=float(p["epsilon"]), period=int(p["period"]), delta=float(p["delta"]),
-                               max_iterations=p["max_iterations"]) for ts, p in zip(sets, params)]
+                               max_iterations=p["max_iterations"], callback=callback) for ts, p in zip(sets, params)]
     c2 = [float(p["c2"]) for p in params]
     pending: List[Optional[np.ndarray]] = [next(st) for st in steppers]
     results: List[Optional[OptimizeResult]] = [None] * n
     f = np.zeros(n)
     g = [np.empty(ts.num_features) for ts in sets]
     while any(x is not None for x in pending):
-        active = np.array([x is not None for x in pending], dtype=np.uint8)
-        trainer.eval(pending, active, f, g)
-        for k in np.flatnonzero(active).tolist():
-            w = pending[k]
-            fk, gk = float(f[k]), g[k].copy()
+        trainer._eval_problems(pending, [x is not None for x in pending], f, g)
+        for k, w in enumerate(pending):
+            if w is None:
+                continue
+            fk, gk = float(f[k]), g[k]
             if c2[k] > 0:
                 fk += c2[k] * float(np.dot(w, w))
                 gk = gk + (2.0 * c2[k]) * w
+            else:
+                gk = gk.copy()  # (the stepper keeps it, and g[k] is written again next round)
             try:
                 pending[k] = steppers[k].send((fk, gk))
             except StopIteration as stop:

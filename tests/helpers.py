@@ -87,6 +87,38 @@ def synth_contigs(rng, lengths, A, zipf=1.2):
 
 
 # ---- vectors produced by the reference's own Python (tools/gen_reference_fixtures.py -> tests/golden/ref_*.json.gz) ----------
+def training_set(rng, W, step, A, n_seqs, drop=0.1, max_extra=60, fixed=2):
+    """A seeded training set as ``_native.TrainerGrid`` takes it, ``(seq_ptr, item_ptr, attr_id, labels, A, state_fid,
+    trans_fid, K, W, step)`` (``[:8]``: as ``TrainerBatch`` takes it): ``fixed`` sequences of exactly W items and ``n_seqs``
+    of W to W + max_extra - 1; a share ``drop`` of the (attribute, label) and transition pairs has no feature."""
+    from gecco_amd import synth
+
+    lengths = [W] * fixed + list(rng.integers(W, W + max_extra, size=n_seqs))
+    seq_ptr, item_ptr, attr_id, labels = synth.synth_training_set(rng, lengths, A, stay=0.9)
+    fid = np.arange(A * 2 + 4, dtype=np.int32)
+    fid[rng.random(A * 2 + 4) < drop] = -1
+    keep = fid >= 0
+    fid[keep] = np.arange(int(keep.sum()))
+    return (seq_ptr, item_ptr, attr_id, labels, A, fid[:A * 2], fid[A * 2:], int(keep.sum()), W, step)
+
+
+def random_problem(rng, W, step):
+    """``training_set`` of 60 attributes and 3 + 25 sequences without its window and step, and random weights for it."""
+    s = training_set(rng, W, step, 60, 25, fixed=3)[:8]
+    return (*s, rng.normal(0, 1.5, size=s[7]))
+
+
+def lone_trainer(s):
+    """The lone ``_native.Trainer`` of a ``training_set``."""
+    from gecco_amd import _native
+
+    return _native.Trainer(s[0], s[1], s[2], s[3], s[4], s[8], s[9], s[5], s[6], s[7])
+
+
+def same_bits(f_a, g_a, f_b, g_b):
+    return np.float64(f_a).tobytes() == np.float64(f_b).tobytes() and g_a.tobytes() == g_b.tobytes()
+
+
 def load_ref(name):
     import gzip
     import json

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from benchkit.train_objective import objective
-from tests.helpers import GOLDEN, golden_csr, read_tsv
+from tests.helpers import GOLDEN, golden_csr, random_problem, read_tsv
 
 pytestmark = pytest.mark.gpu
 
@@ -17,20 +17,6 @@ pytestmark = pytest.mark.gpu
 def np_objective(seq_ptr, item_ptr, attr_id, labels, A, W, step, state_fid, trans_fid, w):
     f, g, _ = objective(seq_ptr, item_ptr, attr_id, labels, A, W, step, state_fid, trans_fid, w)
     return f, g
-
-
-def random_problem(rng, W, step, A=60, n_seqs=25, drop=0.1):
-    lengths = [W] * 3 + list(rng.integers(W, W + 60, size=n_seqs))
-    from gecco_amd import synth
-
-    seq_ptr, item_ptr, attr_id, labels = synth.synth_training_set(rng, lengths, A, stay=0.9)
-    fid = np.arange(A * 2 + 4, dtype=np.int32)
-    fid[rng.random(A * 2 + 4) < drop] = -1  # some pairs without a feature
-    keep = fid >= 0
-    fid[keep] = np.arange(int(keep.sum()))
-    K = int(keep.sum())
-    w = rng.normal(0, 1.5, size=K)
-    return seq_ptr, item_ptr, attr_id, labels, A, fid[:A * 2], fid[A * 2:], K, w
 
 
 def check_eval(trainer, args, w, W, step):

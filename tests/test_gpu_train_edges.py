@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 from benchkit.train_objective import objective
-from tests.helpers import objective_tolerances
-from tests.test_gpu_train import random_problem
+from tests.helpers import objective_tolerances, random_problem
 
 pytestmark = pytest.mark.gpu
 

@@ -10,6 +10,7 @@ import warnings
 import numpy as np
 import pytest
 
+from tests.helpers import lone_trainer, same_bits, training_set
 from tests.test_gpu_cv import _dataset, _model_bytes
 
 pytestmark = pytest.mark.gpu
@@ -18,40 +19,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRID = {"c1": [0.0, 0.4], "c2": [0.0, 1.0], "window_size": [5, 8]}
 
 
-def _set(rng, W, step, A, n_seqs, drop=0.1, max_extra=60):
-    from gecco_amd import synth
-
-    lengths = [W] * 2 + list(rng.integers(W, W + max_extra, size=n_seqs))
-    seq_ptr, item_ptr, attr_id, labels = synth.synth_training_set(rng, lengths, A, stay=0.9)
-    fid = np.arange(A * 2 + 4, dtype=np.int32)
-    fid[rng.random(A * 2 + 4) < drop] = -1
-    keep = fid >= 0
-    fid[keep] = np.arange(int(keep.sum()))
-    return (seq_ptr, item_ptr, attr_id, labels, A, fid[:A * 2], fid[A * 2:], int(keep.sum()), W, step)
-
-
 def _sets(seed):
     """Mixed windows and steps, one set with more than 256 x 64 windows."""
     rng = np.random.default_rng(seed)
-    return [_set(rng, 5, 1, 90, 300, max_extra=120), _set(rng, 20, 3, 40, 30), _set(rng, 32, 1, 7, 3),
-            _set(rng, 1, 1, 60, 20), _set(rng, 8, 2, 113, 25, drop=0.5)]
-
-
-def _lone(s):
-    from gecco_amd import _native
-
-    return _native.Trainer(s[0], s[1], s[2], s[3], s[4], s[8], s[9], s[5], s[6], s[7])
-
-
-def _same(f_a, g_a, f_b, g_b):
-    return np.float64(f_a).tobytes() == np.float64(f_b).tobytes() and g_a.tobytes() == g_b.tobytes()
+    return [training_set(rng, 5, 1, 90, 300, max_extra=120), training_set(rng, 20, 3, 40, 30), training_set(rng, 32, 1, 7, 3),
+            training_set(rng, 1, 1, 60, 20), training_set(rng, 8, 2, 113, 25, drop=0.5)]
 
 
 def test_grid_trainer_is_bitwise_the_lone_trainers():
     from gecco_amd import _native
 
     sets = _sets(4100)
-    lone = [_lone(s) for s in sets]
+    lone = [lone_trainer(s) for s in sets]
     # 10 problems on set 0 (more than one item group of 8), 3 on set 1, one on each other set, interleaved
     problem_set = [0, 1, 0, 2, 0, 0, 1, 3, 0, 0, 0, 4, 0, 1, 0]
     rng = np.random.default_rng(7)
@@ -76,7 +55,7 @@ def test_grid_trainer_is_bitwise_the_lone_trainers():
             for k, s in enumerate(problem_set):
                 if mask[k]:
                     ef, eg = lone[s].eval(ws[k])
-                    assert _same(f[k], g[k], ef, eg), (budget, k)
+                    assert same_bits(f[k], g[k], ef, eg), (budget, k)
                 else:
                     assert f[k] == 12345.0 and np.all(g[k] == -7.0)
 
@@ -86,7 +65,7 @@ def test_extreme_problems_change_no_other():
 
     sets = _sets(4200)
     problem_set = [0, 0, 0, 1, 1, 4, 0]
-    lone = [_lone(s) for s in sets]
+    lone = [lone_trainer(s) for s in sets]
     rng = np.random.default_rng(3)
     for budget in (0, 1):
         grid = _native.TrainerGrid(sets, problem_set, budget)
@@ -104,7 +83,7 @@ def test_extreme_problems_change_no_other():
             if k in (2, 5):
                 continue
             ef, eg = lone[s].eval(ws[k])
-            assert _same(f[k], g[k], ef, eg), (budget, k)
+            assert same_bits(f[k], g[k], ef, eg), (budget, k)
 
 
 def test_grid_argument_errors_name_the_set_or_problem():
