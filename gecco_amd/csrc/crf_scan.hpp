@@ -149,15 +149,35 @@ __device__ __forceinline__ E block_scan_exclusive(const E &mine, E *lds_totals /
     return comb<Op, REV>(pre, excl);
 }
 
+// Workgroup-wide OR of one flag per lane, in two halves around a barrier the caller has anyway: every wave posts whether
+// any of its lanes holds the flag (a ballot: wave-uniform, one LDS word per wave), and behind the barrier every lane reads
+// the NTH/64 words.  (__syncthreads_or costs a wave reduction, LDS atomics and barriers of its own, and keeps the
+// workgroup's grid coordinates alive in scalar registers for the size of a partial last workgroup.)  The words must not
+// be posted again before a further barrier.
+template <int NTH = kScanThreads>
+__device__ __forceinline__ void block_or_post(bool mine, uint32_t *lds_votes /* NTH/64 */) {
+    const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+    const uint32_t any = __builtin_amdgcn_ballot_w64(mine) != 0 ? 1u : 0u;
+    if ((threadIdx.x & 63) == 63) lds_votes[wave] = any;
+}
+template <int NTH = kScanThreads>
+__device__ __forceinline__ bool block_or_read(const uint32_t *lds_votes /* NTH/64 */) {
+    uint32_t any = 0;
+#pragma unroll
+    for (int w = 0; w < NTH / 64; ++w) any |= lds_votes[w];
+    return __builtin_amdgcn_readfirstlane(int(any)) != 0;
+}
+
 // Workgroup-wide exclusive scan from the BACK for 32-bit elements: lane l receives e[l+1] (x) e[l+2] (x) ... (x) e[NTH-1]
 // with the element closest to the end acting first (Op::combine(a, b) applies b first); *total = e[0] (x) ... (x) e[NTH-1].
 // Every wave mirrors its lanes through the LDS crossbar (ds_bpermute: no memory, no barrier), scans forward and mirrors
 // back; the waves' totals meet in LDS in reverse order -- one barrier instead of the four of a mirrored exchange
 // through LDS around a forward scan.  `lds_totals` must not be reused before the next barrier of the caller.
-// `vote` (may be null): in / out, the workgroup-wide OR of the lanes' values rides on the scan's one barrier.
+// `vote` (may be null): in / out, the workgroup-wide OR of the lanes' values rides on the scan's one barrier, through
+// `lds_votes` (block_or_post / block_or_read).
 template <class Op, int NTH = kScanThreads>
 __device__ __forceinline__ uint32_t block_scan_exclusive_back(uint32_t mine, uint32_t *lds_totals /* NTH/64 */, uint32_t *total,
-                                                              int *vote = nullptr) {
+                                                              int *vote = nullptr, uint32_t *lds_votes /* NTH/64 */ = nullptr) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
     const uint32_t id = Op::identity();
     const int mirror = (63 - lane) << 2;
@@ -165,8 +185,9 @@ __device__ __forceinline__ uint32_t block_scan_exclusive_back(uint32_t mine, uin
     const uint32_t incl = wave_scan_inclusive<Op, true>(m);
     if (lane == 63) lds_totals[wave] = incl;
     const uint32_t excl = wave_shift_up(id, incl);
-    if (vote) *vote = __syncthreads_or(*vote);
-    else __syncthreads();
+    if (vote) block_or_post<NTH>(*vote != 0, lds_votes);
+    __syncthreads();
+    if (vote) *vote = block_or_read<NTH>(lds_votes) ? 1 : 0;
     uint32_t pre = id, all = id;
 #pragma unroll
     for (int w = NTH / 64 - 1; w >= 0; --w) {

@@ -36,6 +36,11 @@ __device__ __forceinline__ double vd_min(double a, double b) {
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+__device__ __forceinline__ double vd_min_abs(double a, double b) {  // min(|a|, |b|)
+    double r;
+    asm("v_min_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 // ... against a wave-uniform bound: the second operand straight from its SGPR pair (a "v" operand would cost a v_mov_b64 per use)
 __device__ __forceinline__ double vd_max_s(double a, double bound) {
     double r;
@@ -283,6 +288,9 @@ struct VdShortSmem {
     int c_end;
     CE tot[kT / 64];
     uint32_t mtot[kT / 64];
+    double pv[kT / 64];      // value propagation: the value leaving every wave's last lane ...
+    uint32_t pbad[kT / 64];  // ... and whether the wave has to ask for the map scan instead (block_or_post)
+    uint32_t vote[kT / 64];  // the workgroup's other votes: a lane has to look back / a contig goes to CRFsuite's recursion
 };
 static_assert(sizeof(VdShortSmem) <= 20480, "eight workgroups per CU");
 // genes [g0, g0 + n) of the workgroup -> the lanes that own kGPL consecutive ones.  A lane loads ITS OWN genes (64
@@ -292,9 +300,19 @@ static_assert(sizeof(VdShortSmem) <= 20480, "eight workgroups per CU");
 __device__ __forceinline__ void load_short(const double *__restrict__ v, int g0, int n, VdShortSmem &stg, double (&x)[kGPL]) {
     const int base = int(threadIdx.x) * kGPL;
     const double *vp = v + g0;
+    double *row = stg.st + threadIdx.x * (kGPL + 1);
+    // a wave all of whose 512 positions are genes (three waves of four in a full workgroup; a wave-uniform test) needs
+    // neither the clamps nor the padding selects: seven vector instructions per gene inside a launch bound by vector issue
+    const int wave_end = (__builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6)) + 1) * 64 * kGPL;
+    if (wave_end <= n) {
+#pragma unroll
+        for (int k = 0; k < kGPL; ++k) x[k] = vp[base + k];
+#pragma unroll
+        for (int k = 0; k < kGPL; ++k) row[k] = x[k];
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < kGPL; ++k) x[k] = vp[max(min(base + k, n - 1), 0)];
-    double *row = stg.st + threadIdx.x * (kGPL + 1);
 #pragma unroll
     for (int k = 0; k < kGPL; ++k) {
         x[k] = base + k < n ? x[k] : kVdPad;
@@ -312,6 +330,25 @@ __device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
     v |= uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x142, 0xA, 0xF, true));  // row_bcast:15 -> rows 1, 3
     v |= uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x143, 0xC, 0xF, true));  // row_bcast:31 -> rows 2, 3
     return uint32_t(__builtin_amdgcn_readlane(int(v), 63));
+}
+
+// Value propagation (vd_short_block): lane l holds the map P of its eight genes and, where bit l of `known` is set, the
+// value v that leaves it.  A lane that is not known but whose left neighbour is takes the neighbour's value, applies its
+// map and becomes known: one lane of every run per step, at most kVdRun steps.  `known` is wave-uniform (a ballot, kept
+// and shifted in scalar registers); a step costs two DPP moves and, in the lanes that take it, three fp64 instructions.
+constexpr int kVdRun = 6;  // (C3: no run longer than 5 lanes under either weight law; longer ones take the map scan)
+__device__ __forceinline__ void vd_apply(const CE &P, double in, double &v) {
+    // (volatile: the caller's branch stays a branch on the execution mask, not three instructions in every lane and two selects)
+    asm volatile("v_add_f64 %0, %1, %2\n\tv_max_f64 %0, %0, %3\n\tv_min_f64 %0, %0, %4" : "+v"(v) : "v"(in), "v"(P.a), "v"(P.L), "v"(P.H));
+}
+__device__ __forceinline__ void vd_propagate(const CE &P, double &v, uint64_t &known) {
+    for (int it = 0; it < kVdRun; ++it) {
+        const uint64_t todo = (known << 1) & ~known;
+        if (!todo) break;
+        const double in = dpp_f64_z<0x138>(v);  // wave_shr:1 (lane 0 is never among `todo`)
+        if (__builtin_amdgcn_inverse_ballot_w64(todo)) vd_apply(P, in, v);
+        known |= todo;
+    }
 }
 
 // workgroup `blk` of the short-contig decoder (kernel vd_short in crf_sequence.hip; the pipelined decode kernel in
@@ -355,10 +392,49 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
             P.H = fst ? dvk : h2;
         }
     }
-    const CE M = block_scan_exclusive<COp, false, CE, kScanThreads, true, true>(P, lds, static_cast<CE *>(nullptr));  // the workgroup starts at a contig start
-    // ---- exact entering values.  M comes from COMPOSED maps: its additions are associated differently from the
-    // sequential recursion, so M.L may differ from the sequential Delta in the last bits, and a decision that
-    // lies within that noise of a threshold would depend on how the scan happens to be cut.  The clamp FORGETS:
+    // ---- the value entering every lane (Delta of the gene before its first).  The workgroup starts at a contig start,
+    // so every exclusive prefix of the lane maps is a CONSTANT map and one number per lane is all that is wanted of it.
+    // A lane whose own map is constant (P.L == P.H: it holds a contig's first gene, a padding position, or a gene at
+    // which the clamp saturates whatever came in -- seven lanes of eight on metagenome batches) knows the value that
+    // leaves it without its neighbours, and that value IS the sequential recursion's, bit for bit: rounding is monotone,
+    // so the recursion started from any entering value runs between the L track and the H track, which have met.  The
+    // others (isolated runs of one to five lanes) apply their map to what their left neighbour hands them, one lane per
+    // step of vd_propagate; lane 63's value crosses to the next wave through LDS on the one barrier this costs, and the
+    // lanes in front of a wave's first constant lane finish behind it.  A workgroup with a run of more than kVdRun such
+    // lanes, or with a wave that holds no constant lane at all, votes (on the same barrier) for the scan of whole maps
+    // that served every workgroup until now: block_scan_exclusive, M.L.
+    double Din;
+    {
+        const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+        double v = P.L;
+        uint64_t known = __builtin_amdgcn_ballot_w64(P.L == P.H);
+        vd_propagate(P, v, known);
+        // (wave-uniform) every lane behind the wave's first constant one is known by now, and at most kVdRun lanes wait in
+        // front of it -- none in wave 0, whose first gene starts a contig
+        const bool wave_bad = (known | (known - 1)) != ~uint64_t(0) || !(known & (wave ? (uint64_t(2) << kVdRun) - 1 : uint64_t(1)));
+        if ((threadIdx.x & 63) == 63) stg.pv[wave] = v;
+        block_or_post(wave_bad, stg.pbad);
+        __syncthreads();
+        if (block_or_read(stg.pbad)) {
+            const CE M = block_scan_exclusive<COp, false, CE, kScanThreads, true, true>(P, lds, static_cast<CE *>(nullptr));
+            Din = M.L;
+        } else {
+            const double carry = stg.pv[wave ? wave - 1 : 0];  // (wave 0: lane 0 starts a contig, what enters it is not used)
+            if (!(known & 1u)) {  // the lanes in front of the wave's first constant one: lane 0 takes the wave before's value
+                if ((threadIdx.x & 63) == 0) vd_apply(P, carry, v);
+                known |= 1u;
+                vd_propagate(P, v, known);
+            }
+            Din = dpp_f64<0x138, 0xF>(carry, v);  // wave_shr:1, lane 0 <- carry
+        }
+    }
+    // ---- exact decisions.  Din is exact behind a constant lane; behind a run of j <= kVdRun other lanes it carries j
+    // additions of a lane's `a` (eight roundings of its own) where the sequential recursion rounds gene by gene: at most
+    // nine half-ulps of a |Delta| <= 2 M per eight genes, 9 / 8 ulp(M) per gene of the run, against the 2 r + 2 ulp(M)
+    // that vd_margin grants the difference form's own roundings -- closer to the sequential recursion than the
+    // tree-ordered composition of up to 256 maps that M.L (the scan's result, still used by the workgroups that vote for
+    // it) is.  Either way the value may differ from the sequential Delta in the last bits, and a decision that
+    // lies within that noise of a threshold would depend on how the lanes happen to be cut.  The clamp FORGETS:
     // wherever Delta_t lies beyond [lo, hi] by more than the noise, Delta_{t+1} = bound + c_{t+1} whatever came
     // before.  So: one approximate pass marks those positions, every lane walks back to the nearest one (or
     // to its contig's first gene) and re-runs the recursion sequentially from there -- a few genes on
@@ -377,7 +453,7 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
     uint32_t maps = 0, lane_map;
     bool sensitive = false;  // some decision of this lane lies within the noise of its threshold
     {
-        double Dq = M.L;
+        double Dq = Din, nearest = __builtin_huge_val();
 #pragma unroll
         for (int k = 0; k < kGPL; ++k) {
             const double dvk = row[k];
@@ -391,16 +467,20 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
             // 2 (kGPL - 1 - k) + {0, 1}
             vd_shift_in_gt(maps, Dq, A.v_lo);
             vd_shift_in_gt(maps, Dq, A.v_hi);
-            bool sens = fabs(Dq - A.v_hi) <= margin || fabs(Dq - A.v_lo) <= margin;
+            // how close the gene's value comes to one of its thresholds: the lane keeps the minimum and tests it once against
+            // the margin (the same predicate as a test per gene, `<=` included; a compare per threshold and gene kept eight
+            // 64-bit masks alive in scalar registers next to 2 x 8 of the wave_bits tests)
+            double dist = vd_min_abs(Dq - A.v_hi, Dq - A.v_lo);
             if ((wave_bits >> (8 + k)) & 1u) {
                 // a contig's last gene decides the end label: both of its "thresholds" are 0 (maps 3 / 0)
                 asm volatile("" ::: "memory");
                 const bool lst = (last >> k) & 1u;
                 maps = lst ? ((maps & ~3u) | (Dq > 0.0 ? 3u : 0u)) : maps;
-                sens = lst ? fabs(Dq) <= margin : sens;
+                dist = lst ? fabs(Dq) : dist;
             }
-            sensitive |= sens;
+            nearest = vd_min(nearest, dist);
         }
+        sensitive = nearest <= margin;
     }
     // the lane's eight genes as ONE label map (label after its last gene -> label before its first): both labels are walked
     // through the genes' maps, back to front -- an or and a bit-field extract per gene and label
@@ -420,11 +500,11 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
     int vote = lane_sensitive ? 1 : 0;
     uint32_t mtotal;
     lane_map = label_map();
-    uint32_t lab = block_scan_exclusive_back<MapOp>(lane_map, ldsm, &mtotal, &vote) & 1u;
+    uint32_t lab = block_scan_exclusive_back<MapOp>(lane_map, ldsm, &mtotal, &vote, stg.vote) & 1u;
     const bool wg_sensitive = vote != 0;
     if (wg_sensitive) {
         // marks for the walk: per gene 1 = beyond hi, 2 = beyond lo (after this gene), 0 = inside or too close to tell
-        double Dq = M.L;
+        double Dq = Din;
         uint64_t sat = 0;
 #pragma unroll
         for (int k = 0; k < kGPL; ++k) {
@@ -497,7 +577,9 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
     // maps: the barrier of the vote also separates the two uses of the scan's LDS words)
     bool wg_flagged = false;
     if (wg_sensitive) {
-        wg_flagged = __syncthreads_or(lane_flagged ? 1 : 0);
+        block_or_post(lane_flagged, stg.vote);  // (a barrier -- the marks' -- lies between the first vote's reads and this)
+        __syncthreads();
+        wg_flagged = block_or_read(stg.vote);
         lane_map = label_map();
         lab = block_scan_exclusive_back<MapOp>(lane_map, ldsm, &mtotal) & 1u;
     }

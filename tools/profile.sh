@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $R
-B="python bench.py --no-cpu-baseline --no-past-l3 --no-c4 --no-8d --no-levels --streams 1 $*"
+B="python bench.py --no-cpu-baseline --no-past-l3 --no-c4 --no-8d --no-levels --no-latency --streams 1 $*"
 # kernel trace of the bench run on ONE decode stream (device pre-roll + 100 warmup + 1000 timed steps + 200 kernel timings):
 # per-kernel averages that are launch durations
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- $B > $O/kt.log 2>&1
