@@ -222,21 +222,17 @@ GECCO_API int gecco_crf_plan_run_windowed(gecco_crf_plan *p, const int32_t *d_ge
     GECCO_GUARD_END
 }
 
-GECCO_API int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
-                                           int32_t label, double *d_p_out, void *stream, int32_t warmup,
-                                           int32_t iters, float *ms_per_launch) {
-    if (!p || !ms_per_launch || iters <= 0) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
-    GECCO_GUARD_BEGIN
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// `call` repeated on stream `s`: `warmup` times untimed, then `iters` times between two events
+template <class Call>
+static int time_calls(hipStream_t s, int32_t warmup, int32_t iters, float *ms_per_launch, Call call) {
     int rc;
     for (int i = 0; i < warmup; ++i)
-        if ((rc = plan_run_windowed(p->p, d_gene_ptr, d_attr_id, label, d_p_out, s))) return rc;
+        if ((rc = call())) return rc;
     hipEvent_t e0, e1;
     if ((rc = check_hip(hipEventCreate(&e0), "hipEventCreate"))) return rc;
     if ((rc = check_hip(hipEventCreate(&e1), "hipEventCreate"))) return rc;
     rc = check_hip(hipEventRecord(e0, s), "hipEventRecord");
-    for (int i = 0; i < iters && !rc; ++i) rc = plan_run_windowed(p->p, d_gene_ptr, d_attr_id, label, d_p_out, s);
+    for (int i = 0; i < iters && !rc; ++i) rc = call();
     if (!rc) rc = check_hip(hipEventRecord(e1, s), "hipEventRecord");
     if (!rc) rc = check_hip(hipEventSynchronize(e1), "hipEventSynchronize");
     float ms = 0.f;
@@ -245,6 +241,16 @@ GECCO_API int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_g
     (void)hipEventDestroy(e1);
     *ms_per_launch = ms / float(iters);
     return rc;
+}
+
+GECCO_API int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
+                                           int32_t label, double *d_p_out, void *stream, int32_t warmup,
+                                           int32_t iters, float *ms_per_launch) {
+    if (!p || !ms_per_launch || iters <= 0) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return time_calls(s, warmup, iters, ms_per_launch, [&] { return plan_run_windowed(p->p, d_gene_ptr, d_attr_id, label, d_p_out, s); });
     GECCO_GUARD_END
 }
 
@@ -258,21 +264,9 @@ GECCO_API int gecco_crf_plan_time_decode_pipelined(gecco_crf_plan *p, const int3
     int rc;
     // the plan follows itself: call 0 primes (tiles only), every later call is one launch of tiles + Viterbi workgroups
     if ((rc = plan_run_decode_pipelined(&p->p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, nullptr, s))) return rc;
-    for (int i = 0; i < warmup; ++i)
-        if ((rc = plan_run_decode_pipelined(&p->p, d_gene_ptr, d_attr_id, label, d_p_out, &p->p, d_y, s))) return rc;
-    hipEvent_t e0, e1;
-    if ((rc = check_hip(hipEventCreate(&e0), "hipEventCreate"))) return rc;
-    if ((rc = check_hip(hipEventCreate(&e1), "hipEventCreate"))) return rc;
-    rc = check_hip(hipEventRecord(e0, s), "hipEventRecord");
-    for (int i = 0; i < iters && !rc; ++i) rc = plan_run_decode_pipelined(&p->p, d_gene_ptr, d_attr_id, label, d_p_out, &p->p, d_y, s);
-    if (!rc) rc = check_hip(hipEventRecord(e1, s), "hipEventRecord");
-    if (!rc) rc = check_hip(hipEventSynchronize(e1), "hipEventSynchronize");
-    float ms = 0.f;
-    if (!rc) rc = check_hip(hipEventElapsedTime(&ms, e0, e1), "hipEventElapsedTime");
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    rc = time_calls(s, warmup, iters, ms_per_launch,
+                    [&] { return plan_run_decode_pipelined(&p->p, d_gene_ptr, d_attr_id, label, d_p_out, &p->p, d_y, s); });
     if (!rc) rc = plan_run_decode_pipelined(nullptr, nullptr, nullptr, label, nullptr, &p->p, d_y, s);  // (flush)
-    *ms_per_launch = ms / float(iters);
     return rc;
     GECCO_GUARD_END
 }

@@ -241,8 +241,6 @@ static inline void set_bit_range(uint64_t *bits, int64_t lo, int64_t hi) {
 }
 
 namespace {
-inline size_t align256p(size_t x) { return (x + 255) & ~size_t(255); }
-
 // grow-only device workspace (hipFree waits for the launches that may still use the old block)
 template <class T>
 int grow_ws(T *&ptr, size_t &cap, size_t bytes, const char *what) {
@@ -443,15 +441,12 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     if (rc) return rc;
     if ((rc = get_device_tables(m, device, &p.tables_model))) return rc;
     // one pinned block -> one device block, one copy
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = off;
-        off += align256p(bytes ? bytes : 1);
-        return r;
-    };
+    Carver blk;
+    auto take = [&](size_t bytes) { return blk.take(bytes ? bytes : 1); };  // (an empty table keeps a place of its own)
     const size_t o_slot = take(p.c_slot.size() * 4), o_gene = take(p.c_gene.size() * 4), o_n = take(p.c_n.size() * 4),
                  o_tile = take(p.tile_desc.size() * sizeof(int4)), o_bits = take(p.start_bits.size() * 8),
                  o_skip = take(p.skipped.size() * sizeof(int2)), o_cptr = take(p.contig_ptr.size() * 4);
+    const size_t off = blk.off;
     if ((rc = p.tables.reserve(off, "plan tables"))) return rc;
     char *h = p.tables.h, *d = p.tables.d;
     if (p.tables_in_host_memory) {
@@ -489,20 +484,15 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
 
 // ---- any number of labels (crf_general.hip) ------------------------------------------------
 namespace {
-inline size_t align256g(size_t x) { return (x + 255) & ~size_t(255); }
-
 // A contig longer than this sends the whole batch through the chunked whole-contig kernels (crf_general.hip):
 // below it, one group of lanes per contig walking it sequentially is the cheaper arrangement.
 constexpr int32_t kGenLongContig = 2048;
-
-inline size_t gen_fix_bytes(const Plan &p) { return align256g(size_t(p.n_contigs) + 16); }
 
 // chunk_min_len >= 0: only contigs LONGER than that get chunks (the second table set); -1: every contig
 int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, GenArgs &a, bool whole_contig = false,
                   hipStream_t stream = nullptr, int32_t chunk_min_len = -1) {
     const Model &m = *p.model;
     const size_t n = size_t(p.n_genes), L = size_t(m.L);
-    const size_t b_vec = align256g(n * L * 8 + 8), b_one = align256g(n * 8 + 8), b_back = align256g(n * L + 8);
     // Whole-contig recursions go through the chunked kernels for EVERY batch (round 3): a contig-sequential group of lanes
     // is a dependent chain as long as the contig, and a batch of 200-gene contigs has three to seven chunks' worth of
     // parallelism inside every contig (1 000 contigs x 200 genes, L = 3: Viterbi 0.40 -> 1.5 G genes/s, marginals 0.17 ->
@@ -537,7 +527,9 @@ int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, 
             }
             ch_g0.push_back(p.n_genes);  // (a chunk ends where the next one starts or where its contig does: gl_chunk_end)
             const size_t n_ch = ch_contig.size();
-            const size_t o1 = align256g(ch_g0.size() * 4), o2 = o1 + align256g(n_ch * 4 + 4), total = o2 + align256g(cc_ptr.size() * 4);
+            Carver img_at;
+            img_at.take(ch_g0.size() * 4);
+            const size_t o1 = img_at.take(n_ch * 4 + 4), o2 = img_at.take(cc_ptr.size() * 4), total = img_at.off;
             if (tab.d) (void)hipFree(tab.d);
             tab.d = nullptr;
             tab.chunk = 0;
@@ -556,22 +548,37 @@ int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, 
         }
         nch = tab.nch;
     }
-    const size_t b_chM = align256g(nch * L * L * 8 + 8), b_chv = align256g(nch * L * 8 + 8), b_chs = align256g(nch * 8 + 8);
-    const size_t b_chunks = chunked ? b_chM + 3 * b_chv + 2 * b_chs + 2 * align256g(nch * L + 8) : 0;
     // in front of everything, at a fixed place: the chunked Viterbi's counters (4 x u32) and contig flags, zero at rest (the
     // re-decode clears the flags it reads); zeroed when the block is allocated
-    const size_t b_fix = gen_fix_bytes(p);
+    Carver ws;
+    ws.take(size_t(p.n_contigs) + 16);
+    const size_t b_fix = ws.off;
+    const size_t b_vec = n * L * 8 + 8, b_one = n * 8 + 8;
+    const size_t o_state = ws.take(b_vec), o_E = ws.take(b_vec), o_alpha = ws.take(b_vec), o_smax = ws.take(b_one), o_scale = ws.take(b_one),
+                 o_back = ws.take(n * L + 8);
+    size_t o_chM = 0, o_chV = 0, o_chB = 0, o_chEx = 0, o_chZ = 0, o_chMap = 0, o_chY = 0;
+    if (chunked) {
+        const size_t b_chv = nch * L * 8 + 8;
+        o_chM = ws.take(nch * L * L * 8 + 8);
+        o_chV = ws.take(b_chv);
+        o_chB = ws.take(b_chv);
+        o_chEx = ws.take(b_chv);
+        o_chZ = ws.take(nch * 8 + 8);
+        ws.take(nch * 8 + 8);  // (chZ is two such arrays)
+        o_chMap = ws.take(nch * L + 8);
+        o_chY = ws.take(nch * L + 8);
+    }
     {
         std::lock_guard<std::mutex> lock(p.ws_mutex);
         const size_t cap0 = p.gen_ws_cap;
-        int rc = grow_ws(p.d_gen_ws, p.gen_ws_cap, b_fix + 3 * b_vec + 2 * b_one + b_back + b_chunks, "hipMalloc general-L workspace");
+        int rc = grow_ws(p.d_gen_ws, p.gen_ws_cap, ws.off, "hipMalloc general-L workspace");
         if (rc) return rc;
         if (p.gen_ws_cap != cap0 && (rc = check_hip(hipMemsetAsync(p.d_gen_ws, 0, b_fix, stream), "memset contig flags"))) return rc;
     }
-    char *w = p.d_gen_ws + b_fix;
+    char *w = p.d_gen_ws;
     a = GenArgs{};
-    a.vit_stats = reinterpret_cast<uint32_t *>(p.d_gen_ws);
-    a.fix_flag = reinterpret_cast<uint8_t *>(p.d_gen_ws + 16);
+    a.vit_stats = reinterpret_cast<uint32_t *>(w);
+    a.fix_flag = reinterpret_cast<uint8_t *>(w + 16);
     a.v_wmax = p.tables_model->wmax_abs;
     a.v_tmax = p.tables_model->tmax_abs;
     a.gene_ptr = d_gene_ptr;
@@ -585,32 +592,25 @@ int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, 
     a.n_genes = p.n_genes;
     a.n_contigs = p.n_contigs;
     a.rows_rescale_period = 4.0 * p.tables_model->tmax_abs < 600.0 ? 4 : 1;
-    a.state = reinterpret_cast<double *>(w);
-    a.E = reinterpret_cast<double *>(w + b_vec);
-    a.alpha = reinterpret_cast<double *>(w + 2 * b_vec);
-    a.smax = reinterpret_cast<double *>(w + 3 * b_vec);
-    a.scale = reinterpret_cast<double *>(w + 3 * b_vec + b_one);
-    a.back = reinterpret_cast<uint8_t *>(w + 3 * b_vec + 2 * b_one);
+    a.state = reinterpret_cast<double *>(w + o_state);
+    a.E = reinterpret_cast<double *>(w + o_E);
+    a.alpha = reinterpret_cast<double *>(w + o_alpha);
+    a.smax = reinterpret_cast<double *>(w + o_smax);
+    a.scale = reinterpret_cast<double *>(w + o_scale);
+    a.back = reinterpret_cast<uint8_t *>(w + o_back);
     if (chunked && nch) {
-        char *q = w + 3 * b_vec + 2 * b_one + b_back;
         const Plan::GenTab &tab = p.gen_tab[chunk_min_len >= 0 ? 1 : 0];
         a.ch_g0 = reinterpret_cast<const int32_t *>(tab.d);
         a.ch_contig = reinterpret_cast<const int32_t *>(tab.d + tab.off1);
         a.cc_ptr = reinterpret_cast<const int32_t *>(tab.d + tab.off2);
         a.n_chunks = int32_t(nch);
-        a.chM = reinterpret_cast<double *>(q);
-        q += b_chM;
-        a.chV = reinterpret_cast<double *>(q);
-        q += b_chv;
-        a.chB = reinterpret_cast<double *>(q);
-        q += b_chv;
-        a.chEx = reinterpret_cast<int32_t *>(q);
-        q += b_chv;
-        a.chZ = reinterpret_cast<double *>(q);
-        q += 2 * b_chs;
-        a.chMap = reinterpret_cast<uint8_t *>(q);
-        q += align256g(nch * L + 8);
-        a.chY = reinterpret_cast<int8_t *>(q);
+        a.chM = reinterpret_cast<double *>(w + o_chM);
+        a.chV = reinterpret_cast<double *>(w + o_chV);
+        a.chB = reinterpret_cast<double *>(w + o_chB);
+        a.chEx = reinterpret_cast<int32_t *>(w + o_chEx);
+        a.chZ = reinterpret_cast<double *>(w + o_chZ);
+        a.chMap = reinterpret_cast<uint8_t *>(w + o_chMap);
+        a.chY = reinterpret_cast<int8_t *>(w + o_chY);
     }
     a.c_slot = p.d_c_slot;
     a.c_gene = p.d_c_gene;
@@ -678,6 +678,132 @@ int join_tail(Plan &p, hipStream_t stream) {
     return check_hip(hipStreamWaitEvent(stream, p.ev_join, 0), "hipStreamWaitEvent");
 }
 
+// One whole-contig recursion of the any-L kernels -- forward-backward marginals or Viterbi -- as run_gen_whole sees it: the
+// switch that forces its arrangement, when the choice is automatic, the cost model of choose_wave_split, its launchers.
+struct GenRecursion {
+    // GECCO_CRF_GENERAL_*=wave|chunked|split for 9 <= L <= 32 (tests, A/B).  A reader, not the variable's name: the getenv call
+    // keeps its literal, which is how tests/test_native_cpu.py finds every switch the library reads
+    const char *(*forced)();
+    int auto_above;                     // the choice is made for models of more labels than this
+    double (*t_step)(int L), (*t_gene)(int L), (*t_walk)(int L), (*t_launches)(int L);  // us; choose_wave_split
+    int32_t Plan::*cache;               // the split chosen for the plan's layout
+    hipError_t (*chunked)(const GenArgs &, hipStream_t), (*wave)(const GenArgs &, hipStream_t);
+    void (*clear)(GenArgs &);           // the workspace fields the recursion does not use
+    const char *what;
+};
+// 17 to 32 labels: the split of the Viterbi recursion for the forward-backward recursion (gl_marginals_wave; a step of it is
+// ~0.5 us; the chunked kernels -- transfer matrices on the matrix cores -- run at 2.6 / 2.2 ns per gene at L = 32 / 24).
+// Measured on 1 000 contigs / 0.22 M genes, longest 1 519 (all chunked -> all waves -> split): L = 32 0.60 -> 0.77 -> 0.44 ms.
+// GECCO_CRF_GENERAL_MARGINALS=wave|chunked|split forces for 9 <= L <= 32 (tests, A/B).
+const GenRecursion kGenMarginals = {
+    [] { return (const char *)std::getenv("GECCO_CRF_GENERAL_MARGINALS"); },
+    16,
+    [](int L) { return L > 16 ? 0.5 : 0.38; },
+    [](int L) { return L >= 28 ? 2.6e-3 : L > 16 ? 2.2e-3 : 1.0e-3; },
+    [](int) { return 0.1; },
+    [](int) { return 200.0; },
+    &Plan::gen_wave_tmax_f,
+    launch_gen_marginals,
+    launch_gen_marginals_wave,
+    [](GenArgs &g) { g.state = nullptr; },
+    "marginals launch",
+};
+// 13 to 32 labels: a wave per contig (gl_viterbi_wave) where the batch has its parallelism in its contigs.  The wave
+// kernel takes as long as the longest contig it is given (~0.36 / 0.25 us per gene above / up to 16 labels: a lone wave
+// issues an instruction every four cycles); the chunked kernels pay L x the arithmetic for every gene they are given
+// plus a chain of six launches and the walk over their longest contig's chunks.  So the batch is SPLIT: the k longest
+// contigs -- the tail of a metagenome's length distribution -- go through the chunked kernels on the plan's side
+// stream, NEXT TO the waves of the others, with k minimising  max(t_wave(longest of the others), t_chunked(the k longest)).
+// Measured on 1 000 contigs / 0.22 M genes, longest 1 519, next 762 (all chunked -> all waves -> split):
+// L = 32 1.42 -> 0.55 -> 0.32 ms, L = 24 0.96 -> 0.55 -> 0.32 ms, L = 16 0.28 -> 0.37 -> 0.22 ms.
+// GECCO_CRF_GENERAL_VITERBI=wave|chunked forces either for 9 <= L <= 32 (tests, A/B); =split forces the split at k = 1.
+const GenRecursion kGenViterbi = {
+    [] { return (const char *)std::getenv("GECCO_CRF_GENERAL_VITERBI"); },
+    12,
+    [](int L) { return L > 16 ? 0.36 : 0.25; },
+    [](int L) { return L >= 28 ? 6.3e-3 : L > 16 ? 4.3e-3 : 1.3e-3; },
+    [](int L) { return L > 16 ? 0.07 : 0.04; },
+    [](int L) { return L > 16 ? 150.0 : 80.0; },
+    &Plan::gen_wave_tmax,
+    launch_gen_viterbi,
+    launch_gen_viterbi_wave,
+    [](GenArgs &g) { g.E = g.smax = nullptr; },
+    "viterbi launch",
+};
+
+// The whole-contig recursion `r` of an any-L plan: state scores, then the chunked kernels, a wave per contig, or both side by
+// side (choose_wave_split).  Outputs the recursion does not write are null.
+int run_gen_whole(Plan &p, const GenRecursion &r, const int32_t *d_gene_ptr, const int32_t *d_attr_id, double *d_marg, double *d_lognorm,
+                  int8_t *d_y, double *d_score, hipStream_t stream) {
+    const int L = p.model->L;
+    int32_t wave_tmax = -1;  // -1: no wave kernel; 0: every contig; > 0: contigs up to this length
+    if (L > 8 && p.n_contigs > 0)
+        wave_tmax = choose_wave_split(p, r.forced(), L > r.auto_above, r.t_step(L), r.t_gene(L), r.t_walk(L), r.t_launches(L), p.*r.cache);
+    const bool wave = wave_tmax >= 0, tail_chunked = wave_tmax > 0;
+    GenArgs g;
+    int rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g, !wave || tail_chunked, stream, tail_chunked ? wave_tmax : -1);
+    if (rc) return rc;
+    g.marg = d_marg;
+    g.lognorm = d_lognorm;
+    g.y = d_y;
+    g.score = d_score;
+    r.clear(g);
+    g.wave_tmax = tail_chunked ? wave_tmax : 0;
+    if ((rc = check_hip(launch_gen_state(g, stream), "state score launch"))) return rc;
+    if (!wave) return check_hip(r.chunked(g, stream), r.what);
+    if (!tail_chunked || g.n_chunks <= 0) return check_hip(r.wave(g, stream), r.what);
+    // the long tail (chunked kernels: short in work, long in dependent launches) NEXT TO the waves of the other contigs:
+    // forked onto the plan's side stream behind the state scores, joined before anything later on the caller's stream.
+    // The two write disjoint genes, contigs and back-pointer regions: a contig's back-pointers, in either kernel's layout, stay
+    // inside its own T * L bytes (gl_viterbi_wave: quads of rows 1 .. T - 1 from the first dword boundary).  (A chunkless
+    // contig's path score is the waves'.)
+    if ((rc = fork_tail(p, stream))) return rc;
+    if ((rc = check_hip(r.chunked(g, p.side_stream), r.what))) return rc;
+    if ((rc = check_hip(r.wave(g, stream), r.what))) return rc;
+    return join_tail(p, stream);
+}
+
+int fill_seq_args(Plan &p, SeqArgs &a, hipStream_t stream);
+
+// What every run entry point checks before it launches, in the order the checks have always had: a device behind the plan and
+// the label (entry points without one pass 0) ...
+int check_plan(const Plan &p, int32_t label) {
+    if (p.device < 0) {
+        set_error("host-only plan: no HIP device bound (there is no CPU fallback)");
+        return GECCO_CRF_ENODEV;
+    }
+    if (label < 0 || label >= p.model->L) {
+        set_error("label out of range");
+        return GECCO_CRF_EINVAL;
+    }
+    return GECCO_CRF_OK;
+}
+// ... for the whole-contig entry points the workspace (what pipelined decode calls left there is lost) ...
+int begin_whole_contig(Plan &p, int32_t label, SeqArgs &a, hipStream_t stream) {
+    p.pipe.pending = false;
+    const int rc = check_plan(p, label);
+    return rc ? rc : fill_seq_args(p, a, stream);
+}
+// ... then a batch with nothing to do, which ends the call without an error, and the caller's buffers.  True: the call ends
+// here, with `rc`.
+bool ends_here(bool empty, bool null_buffer, int &rc) {
+    rc = GECCO_CRF_OK;
+    if (empty) return true;
+    if (!null_buffer) return false;
+    set_error("null device buffer");
+    rc = GECCO_CRF_EINVAL;
+    return true;
+}
+
+// where the window kernels accumulate (atomic maxima: `zero` first, numpy.zeros of crf/__init__.py:251) or store p; the genes of
+// skipped contigs keep "no prediction"
+int start_p_out(const Plan &p, double *d_p_out, bool zero, hipStream_t stream) {
+    int rc;
+    if (zero && (rc = check_hip(hipMemsetAsync(d_p_out, 0, size_t(p.n_genes) * 8, stream), "memset p"))) return rc;
+    if (p.skipped.empty()) return GECCO_CRF_OK;
+    return check_hip(launch_fill_nan(d_p_out, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch");
+}
+
 int run_windowed_general(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
                          hipStream_t stream) {
     if (p.W > kGenMaxW) {
@@ -689,11 +815,7 @@ int run_windowed_general(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_at
     if (rc) return rc;
     a.p_out = d_p_out;
     a.label = label;
-    // atomic-max accumulation starts from 0.0 (numpy.zeros, crf/__init__.py:251)
-    if ((rc = check_hip(hipMemsetAsync(d_p_out, 0, size_t(p.n_genes) * 8, stream), "memset p"))) return rc;
-    if (!p.skipped.empty())
-        if ((rc = check_hip(launch_fill_nan(d_p_out, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch")))
-            return rc;
+    if ((rc = start_p_out(p, d_p_out, true, stream))) return rc;
     double *keep_state = a.state;
     a.state = nullptr;  // marginals only need exp(state - max)
     if ((rc = check_hip(launch_gen_state(a, stream), "state score launch"))) return rc;
@@ -720,21 +842,9 @@ int plan_run_windowed(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_
 
 static int run_windowed_impl(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
                              double2 *d_state_out, double *d_dstate_out, hipStream_t stream, const PipelinedLaunch *piped) {
-    if (p.device < 0) {
-        set_error("host-only plan: no HIP device bound (there is no CPU fallback)");
-        return GECCO_CRF_ENODEV;
-    }
-    if (label < 0 || label >= p.model->L) {
-        set_error("label out of range");
-        return GECCO_CRF_EINVAL;
-    }
-    if (p.n_genes == 0) return GECCO_CRF_OK;
-    if (!d_gene_ptr || !d_p_out) {
-        set_error("null device buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    int rc = use_device(p.device);
-    if (rc) return rc;
+    int rc = check_plan(p, label);
+    if (rc || ends_here(p.n_genes == 0, !d_gene_ptr || !d_p_out, rc)) return rc;
+    if ((rc = use_device(p.device))) return rc;
     const Model &m = *p.model;
     if (p.general) return run_windowed_general(p, d_gene_ptr, d_attr_id, label, d_p_out, stream);
     WinArgs a{};
@@ -779,32 +889,22 @@ static int run_windowed_impl(Plan &p, const int32_t *d_gene_ptr, const int32_t *
     }
     a.csr_begin = int32_t(p.csr_begin);  // (row pointers are 32-bit)
     a.csr_end = int32_t(p.csr_end);
+    a.generic = (p.fast_ok || p.reference_now) ? 0 : 1;
+    if (p.reference_now || !p.fast_ok) {  // (the reference-bits and the generic kernel work in a scratch block)
+        const size_t bytes = p.reference_now ? reference_scratch_bytes(p.n_genes) : size_t(p.S) * size_t(p.W) * 16 + 16;
+        std::lock_guard<std::mutex> lock(p.ws_mutex);
+        if ((rc = grow_ws(p.d_win_scratch, p.win_scratch_cap, bytes, p.reference_now ? "hipMalloc reference scratch" : "hipMalloc window scratch")))
+            return rc;
+    }
+    // (the register-resident and the reference-bits kernel store every gene of slot space once, by the tile that owns its slot:
+    // nothing to zero)
+    if ((rc = start_p_out(p, d_p_out, a.generic, stream))) return rc;
     if (p.reference_now) {
-        {
-            std::lock_guard<std::mutex> lock(p.ws_mutex);
-            if ((rc = grow_ws(p.d_win_scratch, p.win_scratch_cap, reference_scratch_bytes(p.n_genes), "hipMalloc reference scratch"))) return rc;
-        }
-        // (every gene of slot space is stored once by the tile that owns its slot: nothing to zero)
-        if (!p.skipped.empty())
-            if ((rc = check_hip(launch_fill_nan(d_p_out, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch"))) return rc;
         double et[4];
         for (int i = 0; i < 4; ++i) et[i] = std::exp(m.trans[size_t(i)]);  // (the host's libm, as the reference's CRFsuite calls it)
         return check_hip(launch_windowed_reference(a, p.tables_model->wtab2[1], et, p.d_win_scratch, stream), "reference-bits launch");
     }
-    a.generic = p.fast_ok ? 0 : 1;
-    if (a.generic) {
-        {
-            std::lock_guard<std::mutex> lock(p.ws_mutex);
-            if ((rc = grow_ws(p.d_win_scratch, p.win_scratch_cap, size_t(p.S) * size_t(p.W) * 16 + 16, "hipMalloc window scratch")))
-                return rc;
-        }
-        a.scratch = p.d_win_scratch;
-        // atomic-max accumulation starts from 0.0 (numpy.zeros, crf/__init__.py:251)
-        if ((rc = check_hip(hipMemsetAsync(d_p_out, 0, size_t(p.n_genes) * 8, stream), "memset p"))) return rc;
-    }
-    if (!p.skipped.empty())
-        if ((rc = check_hip(launch_fill_nan(d_p_out, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch")))
-            return rc;
+    if (a.generic) a.scratch = p.d_win_scratch;
     if (piped && !a.generic && decode_pipelined_ok(a, *piped->seq)) {
         *piped->took = true;
         return check_hip(launch_decode_pipelined(a, *piped->seq, stream), "pipelined decode launch");
@@ -814,8 +914,6 @@ static int run_windowed_impl(Plan &p, const int32_t *d_gene_ptr, const int32_t *
 
 // ---- whole-contig scans (rows F, V) ------------------------------------------------------
 namespace {
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 struct SeqLayout {
     size_t lanes, blocks, bytes;
     size_t off_state, off_alpha, off_tmp, off_vlane, off_vblock, off_vmaps, off_vlanemap, off_vblockmap, off_flane,
@@ -826,27 +924,22 @@ SeqLayout seq_layout(size_t n) {
     l.lanes = (n + kSeqGenesPerLane - 1) / kSeqGenesPerLane;
     l.blocks = (l.lanes + 255) / 256;
     const size_t lanes_pad = l.blocks * 256;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o += align256(bytes);
-        return r;
-    };
-    l.off_stats = take(64);  // (first: the decoder's counters keep their place when the batch size changes)
-    l.off_state = take((n + kSeqGenesPerLane) * 16);
-    l.off_alpha = take(n * 16);
-    l.off_tmp = take(n * 16);
-    l.off_vlane = take(lanes_pad * sizeof(VE));
-    l.off_vblock = take(l.blocks * sizeof(VE));
-    l.off_vmaps = take(lanes_pad * 4);
-    l.off_vlanemap = take(lanes_pad * 4);
-    l.off_vblockmap = take(l.blocks * 4);
-    l.off_flane = take(lanes_pad * sizeof(FE));
-    l.off_fblock = take(l.blocks * sizeof(FE));
-    l.off_flanesuf = take(lanes_pad * sizeof(FE));
-    l.off_fblocksuf = take(l.blocks * sizeof(FE));
-    l.off_cand = take((lanes_pad + 4 * l.blocks + 16) * sizeof(SeqArgs::VdCand));
-    l.bytes = o + 256;
+    Carver ws;
+    l.off_stats = ws.take(64);  // (first: the decoder's counters keep their place when the batch size changes)
+    l.off_state = ws.take((n + kSeqGenesPerLane) * 16);
+    l.off_alpha = ws.take(n * 16);
+    l.off_tmp = ws.take(n * 16);
+    l.off_vlane = ws.take(lanes_pad * sizeof(VE));
+    l.off_vblock = ws.take(l.blocks * sizeof(VE));
+    l.off_vmaps = ws.take(lanes_pad * 4);
+    l.off_vlanemap = ws.take(lanes_pad * 4);
+    l.off_vblockmap = ws.take(l.blocks * 4);
+    l.off_flane = ws.take(lanes_pad * sizeof(FE));
+    l.off_fblock = ws.take(l.blocks * sizeof(FE));
+    l.off_flanesuf = ws.take(lanes_pad * sizeof(FE));
+    l.off_fblocksuf = ws.take(l.blocks * sizeof(FE));
+    l.off_cand = ws.take((lanes_pad + 4 * l.blocks + 16) * sizeof(SeqArgs::VdCand));
+    l.bytes = ws.off + 256;
     return l;
 }
 // (the per-contig "decode again" flags of the long-contig Viterbi path live behind the scan workspace)
@@ -904,11 +997,11 @@ int plan_ensure_seq(Plan &p, hipStream_t stream, bool sync) {
     // uploaded: the workgroup tables, the lane bits and a copy of the contig table; NOT uploaded: the byte per gene that
     // says "first / last gene of its contig" -- a launch behind the copy derives it from the contig table on the device
     // (two thirds of the block's bytes: 0.5 of 0.77 MB per half-million-gene chunk of the batch driver)
-    const size_t o_blk = 0, o_rank = o_blk + align256p((cblk.size() + 1) * 4),
-                 o_ne = o_rank + align256p((rank.size() + 1) * 4), o_lb = o_ne + align256p((ne.size() + 1) * 4),
-                 o_fb = o_lb + align256p(n_lane_bits * 2 + 2), n_flat_bits = ((n + kSeqBlockGenes - 1) / kSeqBlockGenes) * 256,
-                 o_cp = o_fb + align256p(n_flat_bits * 2 + 2), bytes = o_cp + align256p((size_t(p.n_contigs) + 1) * 4),
-                 o_flags = bytes, all_bytes = o_flags + align256p(n + 16);
+    const size_t n_flat_bits = ((n + kSeqBlockGenes - 1) / kSeqBlockGenes) * 256;
+    Carver blk;
+    const size_t o_blk = blk.take((cblk.size() + 1) * 4), o_rank = blk.take((rank.size() + 1) * 4), o_ne = blk.take((ne.size() + 1) * 4),
+                 o_lb = blk.take(n_lane_bits * 2 + 2), o_fb = blk.take(n_flat_bits * 2 + 2), o_cp = blk.take((size_t(p.n_contigs) + 1) * 4),
+                 bytes = blk.off, o_flags = blk.take(n + 16), all_bytes = blk.off;
     if ((rc = p.seq.reserve(all_bytes, "contig flags"))) return rc;
     if (p.n_contigs) std::memcpy(p.seq.h + o_cp, p.contig_ptr.data(), (size_t(p.n_contigs) + 1) * 4);
     if (n_flat_bits) {
@@ -1015,11 +1108,8 @@ int ensure_seq(Plan &p, hipStream_t stream) {
     return rc;
 }
 
+// (callers have checked that the plan has a device: check_plan, can_hand_over)
 int fill_seq_args(Plan &p, SeqArgs &a, hipStream_t stream) {
-    if (p.device < 0) {
-        set_error("host-only plan: no HIP device bound (there is no CPU fallback)");
-        return GECCO_CRF_ENODEV;
-    }
     int rc = use_device(p.device);
     if (rc) return rc;
     if (p.general) return GECCO_CRF_OK;  // the any-L path has its own workspace
@@ -1089,42 +1179,60 @@ static bool viterbi_delta_ok(const SeqArgs &a) {
     return a.v_lo <= a.v_hi && std::isfinite(a.v_lo) && std::isfinite(a.v_hi);
 }
 
+namespace {
+// what a caller of run_viterbi_l2 has already left in the plan's workspace
+enum class SeqLeft { nothing, state, dstate };  // ... the state scores (a.state), their differences (a.dstate)
+
+inline void bind_seq_io(const Plan &p, SeqArgs &a, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int8_t *d_y, double *d_score) {
+    a.y = d_y;
+    a.score = d_score;
+    a.csr_gene_ptr = d_gene_ptr;
+    a.csr_attr_id = d_attr_id;
+    a.csr_wtab01 = p.tables_model->wtab2[1];
+    a.csr_n_attrs = p.model->A;
+}
+
+// buffer `parity` of the two in which pipelined decode calls hand score differences over (the workspace's state block)
+inline double *parity_buffer(const Plan &p, const SeqArgs &a, int parity) {
+    return const_cast<double *>(reinterpret_cast<const double *>(a.state)) + size_t(parity) * (size_t(p.n_genes) + 8);
+}
+
+// handing the score differences over needs the register-resident 2-label kernel and every gene in slot space
+inline bool can_hand_over(const Plan &p) { return !p.general && p.fast_ok && p.skipped.empty() && p.device >= 0; }
+
+// which of the two the window tiles should leave for run_viterbi_l2 (`delta`: viterbi_delta_ok)
+inline SeqLeft tiles_hand_over(bool delta, const double *d_score) { return delta && !d_score ? SeqLeft::dstate : SeqLeft::state; }
+
+// Whole-contig Viterbi of a 2-label plan; `a` filled and bound (bind_seq_io), `delta`: viterbi_delta_ok(a), read once per call
+// by the caller (score differences left behind imply it).  A path score, or labels under anti-sticky
+// transitions, come from the max-plus scan over the state scores -- with `y` nulled when the difference form gives the labels
+// (viterbi_delta_ok) --; the labels from the decoder over the score differences.
+int run_viterbi_l2(Plan &p, const SeqArgs &a, SeqLeft left, bool delta, hipStream_t stream) {
+    int rc;
+    if (left != SeqLeft::dstate) {
+        if (!delta || a.score) {
+            if (left == SeqLeft::nothing &&
+                (rc = check_hip(launch_seq_state(a.csr_gene_ptr, a.csr_attr_id, a.csr_wtab01, a.csr_n_attrs, p.n_genes,
+                                                 const_cast<double2 *>(a.state), stream), "state score launch")))
+                return rc;
+            SeqArgs m = a;
+            if (delta) m.y = nullptr;  // the scores only: the labels are the difference form's, below
+            if ((rc = check_hip(launch_seq_viterbi(m, p.d_contig_ptr, stream), "viterbi launch")) || !delta) return rc;
+        }
+        if ((rc = check_hip(launch_seq_state_delta(a.csr_gene_ptr, a.csr_attr_id, a.csr_wtab01, a.csr_n_attrs, p.n_genes,
+                                                   const_cast<double *>(a.dstate), stream), "state score launch")))
+            return rc;
+    }
+    return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
+}
+}  // namespace
+
 int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, double *d_marg,
                             double *d_lognorm, hipStream_t stream) {
-    p.pipe.pending = false;  // (the workspace of pipelined decode calls is written below)
     SeqArgs a;
-    int rc = fill_seq_args(p, a, stream);
-    if (rc) return rc;
-    if (p.n_contigs == 0) return GECCO_CRF_OK;
-    if (p.n_genes > 0 && (!d_gene_ptr || !d_marg)) {
-        set_error("null device buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    if (p.general) {
-        // 17 to 32 labels: the split of plan_run_viterbi for the forward-backward recursion (gl_marginals_wave; a step of it is
-        // ~0.5 us; the chunked kernels -- transfer matrices on the matrix cores -- run at 2.6 / 2.2 ns per gene at L = 32 / 24).
-        // Measured on 1 000 contigs / 0.22 M genes, longest 1 519 (all chunked -> all waves -> split): L = 32 0.60 -> 0.77 -> 0.44 ms.
-        // GECCO_CRF_GENERAL_MARGINALS=wave|chunked|split forces for 9 <= L <= 32 (tests, A/B).
-        const int L = p.model->L;
-        int32_t wave_tmax = -1;
-        if (L > 8 && p.n_contigs > 0)
-            wave_tmax = choose_wave_split(p, std::getenv("GECCO_CRF_GENERAL_MARGINALS"), L > 16, L > 16 ? 0.5 : 0.38,
-                                          L >= 28 ? 2.6e-3 : L > 16 ? 2.2e-3 : 1.0e-3, 0.1, 200.0, p.gen_wave_tmax_f);
-        const bool wave = wave_tmax >= 0, tail_chunked = wave_tmax > 0;
-        GenArgs g;
-        if ((rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g, !wave || tail_chunked, stream, tail_chunked ? wave_tmax : -1))) return rc;
-        g.marg = d_marg;
-        g.lognorm = d_lognorm;
-        g.state = nullptr;
-        g.wave_tmax = tail_chunked ? wave_tmax : 0;
-        if ((rc = check_hip(launch_gen_state(g, stream), "state score launch"))) return rc;
-        if (!wave) return check_hip(launch_gen_marginals(g, stream), "marginals launch");
-        if (!tail_chunked || g.n_chunks <= 0) return check_hip(launch_gen_marginals_wave(g, stream), "marginals launch");
-        if ((rc = fork_tail(p, stream))) return rc;
-        if ((rc = check_hip(launch_gen_marginals(g, p.side_stream), "marginals launch"))) return rc;
-        if ((rc = check_hip(launch_gen_marginals_wave(g, stream), "marginals launch"))) return rc;
-        return join_tail(p, stream);
-    }
+    int rc = begin_whole_contig(p, 0, a, stream);
+    if (rc || ends_here(p.n_contigs == 0, p.n_genes > 0 && (!d_gene_ptr || !d_marg), rc)) return rc;
+    if (p.general) return run_gen_whole(p, kGenMarginals, d_gene_ptr, d_attr_id, d_marg, d_lognorm, nullptr, nullptr, stream);
     a.marg = d_marg;
     a.lognorm = d_lognorm;
     // 8-byte inputs, alpha in registers: one fused kernel when workgroups own whole contigs, the workgroups' products
@@ -1140,118 +1248,33 @@ int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d
 
 int plan_run_viterbi(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int8_t *d_y, double *d_score,
                      hipStream_t stream) {
-    p.pipe.pending = false;  // (the workspace of pipelined decode calls is written below)
     SeqArgs a;
-    int rc = fill_seq_args(p, a, stream);
-    if (rc) return rc;
-    if (p.n_contigs == 0) return GECCO_CRF_OK;
-    if (p.n_genes > 0 && (!d_gene_ptr || !d_y)) {
-        set_error("null device buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    if (p.general) {
-        // 13 to 32 labels: a wave per contig (gl_viterbi_wave) where the batch has its parallelism in its contigs.  The wave
-        // kernel takes as long as the longest contig it is given (~0.36 / 0.25 us per gene above / up to 16 labels: a lone wave
-        // issues an instruction every four cycles); the chunked kernels pay L x the arithmetic for every gene they are given
-        // plus a chain of six launches and the walk over their longest contig's chunks.  So the batch is SPLIT: the k longest
-        // contigs -- the tail of a metagenome's length distribution -- go through the chunked kernels on the plan's side
-        // stream, NEXT TO the waves of the others, with k minimising  max(t_wave(longest of the others), t_chunked(the k longest)).
-        // Measured on 1 000 contigs / 0.22 M genes, longest 1 519, next 762 (all chunked -> all waves -> split):
-        // L = 32 1.42 -> 0.55 -> 0.32 ms, L = 24 0.96 -> 0.55 -> 0.32 ms, L = 16 0.28 -> 0.37 -> 0.22 ms.
-        // GECCO_CRF_GENERAL_VITERBI=wave|chunked forces either for 9 <= L <= 32 (tests, A/B); =split forces the split at k = 1.
-        const int L = p.model->L;
-        int32_t wave_tmax = -1;  // -1: no wave kernel; 0: every contig; > 0: contigs up to this length
-        if (L > 8 && p.n_contigs > 0) {
-            const double t_step = L > 16 ? 0.36 : 0.25, t_gene = L >= 28 ? 6.3e-3 : L > 16 ? 4.3e-3 : 1.3e-3;
-            wave_tmax = choose_wave_split(p, std::getenv("GECCO_CRF_GENERAL_VITERBI"), L > 12, t_step, t_gene, L > 16 ? 0.07 : 0.04,
-                                          L > 16 ? 150.0 : 80.0, p.gen_wave_tmax);
-        }
-        GenArgs g;
-        const bool wave = wave_tmax >= 0, tail_chunked = wave_tmax > 0;
-        if ((rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g, !wave || tail_chunked, stream, tail_chunked ? wave_tmax : -1))) return rc;
-        g.y = d_y;
-        g.score = d_score;
-        g.E = nullptr;
-        g.smax = nullptr;
-        g.wave_tmax = tail_chunked ? wave_tmax : 0;
-        if ((rc = check_hip(launch_gen_state(g, stream), "state score launch"))) return rc;
-        if (!wave) return check_hip(launch_gen_viterbi(g, stream), "viterbi launch");
-        if (!tail_chunked || g.n_chunks <= 0) return check_hip(launch_gen_viterbi_wave(g, stream), "viterbi launch");
-        // the long tail (chunked kernels: short in work, long in dependent launches) NEXT TO the waves of the other contigs:
-        // forked onto the plan's side stream behind the state scores, joined before anything later on the caller's stream.
-        // The two write disjoint genes, contigs and back-pointer regions: a contig's back-pointers, in either kernel's layout, stay
-        // inside its own T * L bytes (gl_viterbi_wave: quads of rows 1 .. T - 1 from the first dword boundary).  (A chunkless
-        // contig's path score is the waves'.)
-        if ((rc = fork_tail(p, stream))) return rc;
-        if ((rc = check_hip(launch_gen_viterbi(g, p.side_stream), "viterbi launch"))) return rc;
-        if ((rc = check_hip(launch_gen_viterbi_wave(g, stream), "viterbi launch"))) return rc;
-        return join_tail(p, stream);
-    }
-    a.y = d_y;
-    a.score = d_score;
-    a.csr_gene_ptr = d_gene_ptr;
-    a.csr_attr_id = d_attr_id;
-    a.csr_wtab01 = p.tables_model->wtab2[1];
-    a.csr_n_attrs = p.model->A;
-    const bool delta = viterbi_delta_ok(a);
-    if (!delta || d_score) {
-        if ((rc = check_hip(launch_seq_state(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
-                                             const_cast<double2 *>(a.state), stream), "state score launch")))
-            return rc;
-        SeqArgs m = a;
-        if (delta) m.y = nullptr;  // the scores only: the labels are the difference form's, below
-        if ((rc = check_hip(launch_seq_viterbi(m, p.d_contig_ptr, stream), "viterbi launch")) || !delta) return rc;
-    }
-    if ((rc = check_hip(launch_seq_state_delta(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
-                                               const_cast<double *>(a.dstate), stream), "state score launch")))
-        return rc;
-    return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
+    int rc = begin_whole_contig(p, 0, a, stream);
+    if (rc || ends_here(p.n_contigs == 0, p.n_genes > 0 && (!d_gene_ptr || !d_y), rc)) return rc;
+    if (p.general) return run_gen_whole(p, kGenViterbi, d_gene_ptr, d_attr_id, nullptr, nullptr, d_y, d_score, stream);
+    bind_seq_io(p, a, d_gene_ptr, d_attr_id, d_y, d_score);
+    return run_viterbi_l2(p, a, SeqLeft::nothing, viterbi_delta_ok(a), stream);
 }
-
 
 int plan_run_decode(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
                     int8_t *d_y, double *d_score, hipStream_t stream) {
-    p.pipe.pending = false;  // (the workspace of pipelined decode calls is written below)
-    // handing the score differences over needs the register-resident 2-label kernel and every gene in slot space
-    const bool share = !p.general && p.fast_ok && p.skipped.empty() && p.device >= 0;
-    if (!share) {
+    if (!can_hand_over(p)) {
+        // (pipe.pending is only ever set on a plan that can hand over, so it is clear here; plan_run_viterbi clears it all the same)
         int rc = plan_run_windowed(p, d_gene_ptr, d_attr_id, label, d_p_out, stream);
         if (rc) return rc;
         return plan_run_viterbi(p, d_gene_ptr, d_attr_id, d_y, d_score, stream);
     }
-    if (label < 0 || label >= p.model->L) {
-        set_error("label out of range");
-        return GECCO_CRF_EINVAL;
-    }
     SeqArgs a;
-    int rc = fill_seq_args(p, a, stream);
-    if (rc) return rc;
-    if (p.n_contigs == 0 || p.n_genes == 0) return GECCO_CRF_OK;
-    if (!d_gene_ptr || !d_p_out || !d_y) {
-        set_error("null device buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    a.y = d_y;
-    a.score = d_score;
-    a.csr_gene_ptr = d_gene_ptr;
-    a.csr_attr_id = d_attr_id;
-    a.csr_wtab01 = p.tables_model->wtab2[1];
-    a.csr_n_attrs = p.model->A;
+    int rc = begin_whole_contig(p, label, a, stream);
+    if (rc || ends_here(p.n_contigs == 0 || p.n_genes == 0, !d_gene_ptr || !d_p_out || !d_y, rc)) return rc;
+    bind_seq_io(p, a, d_gene_ptr, d_attr_id, d_y, d_score);
+    // the window tiles leave the state scores, or their differences, where the Viterbi side reads them
     const bool delta = viterbi_delta_ok(a);
-    if (delta && !d_score) {
-        if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, const_cast<double *>(a.dstate), stream)))
-            return rc;
-        return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
-    }
-    if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, const_cast<double2 *>(a.state), nullptr, stream)))
+    const SeqLeft left = tiles_hand_over(delta, d_score);
+    if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, left == SeqLeft::state ? const_cast<double2 *>(a.state) : nullptr,
+                                left == SeqLeft::dstate ? const_cast<double *>(a.dstate) : nullptr, stream)))
         return rc;
-    SeqArgs m = a;
-    if (delta) m.y = nullptr;  // a score requested: the max-plus scan gives it, the difference form the labels (plan_run_viterbi)
-    if ((rc = check_hip(launch_seq_viterbi(m, p.d_contig_ptr, stream), "viterbi launch")) || !delta) return rc;
-    if ((rc = check_hip(launch_seq_state_delta(d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.n_genes,
-                                               const_cast<double *>(a.dstate), stream), "state score launch")))
-        return rc;
-    return check_hip(launch_seq_viterbi_delta(a, stream), "viterbi launch");
+    return run_viterbi_l2(p, a, left, delta, stream);
 }
 
 int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
@@ -1260,23 +1283,19 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
     // ---- the previous batch: labels from the score differences its window tiles left behind (or from its CSR arrays)
     SeqArgs pa{};
     bool prev_delta = false;
-    if (prev && prev->n_genes > 0 && prev->n_contigs > 0) {
+    const bool prev_work = prev && prev->n_genes > 0 && prev->n_contigs > 0;
+    if (prev_work) {
         if (!d_prev_y) {
             set_error("null device buffer");
             return GECCO_CRF_EINVAL;
         }
         if (prev->pipe.pending && !prev->general) {
             if ((rc = fill_seq_args(*prev, pa, stream))) return rc;
-            pa.dstate = reinterpret_cast<const double *>(pa.state) + size_t(prev->pipe.parity) * (size_t(prev->n_genes) + 8);
-            pa.y = d_prev_y;
-            pa.csr_gene_ptr = prev->pipe.gene_ptr;
-            pa.csr_attr_id = prev->pipe.attr_id;
-            pa.csr_wtab01 = prev->tables_model->wtab2[1];
-            pa.csr_n_attrs = prev->model->A;
+            pa.dstate = parity_buffer(*prev, pa, prev->pipe.parity);
+            bind_seq_io(*prev, pa, prev->pipe.gene_ptr, prev->pipe.attr_id, d_prev_y, nullptr);
             prev_delta = true;
         }
     }
-    const bool prev_work = prev && prev->n_genes > 0 && prev->n_contigs > 0;
     if (prev_work && !prev_delta) {
         // no score differences left behind (any-L model, contigs outside slot space, or another call used the workspace since):
         // the state scores are summed again from the CSR arrays -- BEFORE this batch's tiles write into the workspace
@@ -1293,20 +1312,17 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
     if (cur) {
         Plan &p = *cur;
         const int parity = p.pipe.parity ^ 1;  // (cur == prev: the Viterbi side reads the other buffer)
-        bool delta = false;
         double *d_dstate = nullptr;
-        if (!p.general && p.fast_ok && p.skipped.empty() && p.device >= 0 && p.n_genes > 0) {
+        if (can_hand_over(p) && p.n_genes > 0) {
             SeqArgs ca;
             if (prev_delta && prev == cur) {
                 ca = pa;  // (a plan that follows itself: the block has just been filled for the Viterbi side)
             } else if ((rc = fill_seq_args(p, ca, stream))) {
                 return rc;
             }
-            if (viterbi_delta_ok(ca)) {
-                delta = true;
-                d_dstate = const_cast<double *>(reinterpret_cast<const double *>(ca.state)) + size_t(parity) * (size_t(p.n_genes) + 8);
-            }
+            if (viterbi_delta_ok(ca)) d_dstate = parity_buffer(p, ca, parity);
         }
+        const bool delta = d_dstate != nullptr;
         PipelinedLaunch fl{};
         fl.seq = &pa;
         fl.took = &took;
@@ -1318,8 +1334,7 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
         p.pipe.gene_ptr = d_gene_ptr;
         p.pipe.attr_id = d_attr_id;
     }
-    if (prev_work && prev_delta && !took)
-        if ((rc = check_hip(launch_seq_viterbi_delta(pa, stream), "viterbi launch"))) return rc;
+    if (prev_delta && !took && (rc = run_viterbi_l2(*prev, pa, SeqLeft::dstate, true, stream))) return rc;
     if (prev && prev != cur) prev->pipe.pending = false;
     return GECCO_CRF_OK;
 }

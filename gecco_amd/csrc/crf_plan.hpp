@@ -14,6 +14,19 @@
 
 namespace gecco {
 
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// Carves one block into parts that start at multiples of 256 bytes: take() gives the offset of the next part, `off` is the
+// size of the block so far.  Every pinned / device block of the plan and of the batch driver is laid out with it.
+struct Carver {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off += align256(bytes);
+        return at;
+    }
+};
+
 // Per-device copies of a model's tables (owned by the Model, created on first use).
 struct DeviceTables {
     int device = -1;

@@ -150,8 +150,6 @@ struct DeviceCtx {
     Lane *pending = nullptr;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 }  // namespace
 
 // One thread per device entry beyond the first, parked between batches: run(n, job) has the calling thread do job(0) and
@@ -508,6 +506,22 @@ int flush_pending(RunCtx &X, DeviceCtx &D) {
     return finish_pending(X, D);
 }
 
+// Extent [lo, hi) that the genes [g0, g1) of a chunk have in the array behind the caller's row pointers `ptr` (`name`: gene_ptr,
+// marker_ptr), and the degree bytes' agreement with it: the checks of both upload paths.  (A chunk without genes has the extent
+// [0, 0) without a look at `ptr`; nothing is addressed through its offsets.)
+int chunk_extent(const int32_t *ptr, const char *name, int32_t g0, int32_t g1, int64_t &lo, int64_t &hi) {
+    lo = g1 > g0 ? ptr[g0] : 0;
+    hi = g1 > g0 ? ptr[g1] : 0;
+    if (lo >= 0 && hi >= lo) return GECCO_CRF_OK;
+    set_error(std::string(name) + " must be non-decreasing and start at a non-negative offset");
+    return GECCO_CRF_EINVAL;
+}
+int chunk_degrees(const BatchRequest &r, int32_t g0, int32_t g1, int64_t nnz) {
+    if (g1 <= g0 || !r.degree || byte_sum(r.degree + g0, size_t(g1 - g0)) == uint64_t(nnz)) return GECCO_CRF_OK;
+    set_error("degree bytes do not add up to gene_ptr over a chunk (degree must equal diff(gene_ptr))");
+    return GECCO_CRF_EINVAL;
+}
+
 // the bulk uploads of a chunk into an idle lane.  Issued one chunk ahead (session_run): the copy engine then goes from one
 // chunk's arrays to the next one's while the host still lays out and launches the first
 int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
@@ -517,13 +531,9 @@ int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
     if (rc) return rc;
     const int32_t ng = ck.u1 - ck.u0;
     TraceMark tm;
-    const int64_t a0 = ng ? r.gene_ptr[ck.u0] : 0, a1 = ng ? r.gene_ptr[ck.u1] : 0;
-    if (a0 < 0 || a1 < a0) {
-        set_error("gene_ptr must be non-decreasing and start at a non-negative offset");
-        return GECCO_CRF_EINVAL;
-    }
+    int64_t a0, a1, b0 = 0, b1 = 0;  // (b0: first marker offset of the chunk, antismash criterion)
+    if ((rc = chunk_extent(r.gene_ptr, "gene_ptr", ck.u0, ck.u1, a0, a1))) return rc;
     const size_t nnz = size_t(a1 - a0);
-    int64_t b0 = 0;  // first marker offset of the chunk (antismash criterion)
     ln.up_chunk = chunk_index;
     ln.up_a0 = a0;
     ln.up_nnz = int64_t(nnz);
@@ -560,12 +570,7 @@ int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
                 ln.st->h2d_bytes += ng;
             }
             if (r.seg.criterion == 1) {  // the genes' marker domains, offsets kept as the caller's (like gene_ptr)
-                b0 = r.seg.bio_ptr[ck.u0];
-                const int64_t b1 = r.seg.bio_ptr[ck.u1];
-                if (b0 < 0 || b1 < b0) {
-                    set_error("marker_ptr must be non-decreasing and start at a non-negative offset");
-                    return GECCO_CRF_EINVAL;
-                }
+                if ((rc = chunk_extent(r.seg.bio_ptr, "marker_ptr", ck.u0, ck.u1, b0, b1))) return rc;
                 const size_t nb = size_t(b1 - b0);
                 if ((rc = ln.d_bp.reserve((size_t(ng) + 1) * 4, "hipMalloc marker_ptr"))) return rc;
                 if ((rc = ln.d_bi.reserve((nb + 4) * 4, "hipMalloc marker_id"))) return rc;
@@ -580,10 +585,7 @@ int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
     ln.up_b0 = b0;
     // the device derives the rows from the degree bytes, the host takes the chunk's base offset from gene_ptr: they must agree
     // (checked while the copies above are under way)
-    if (ng && r.degree && byte_sum(r.degree + ck.u0, size_t(ng)) != uint64_t(a1 - a0)) {
-        set_error("degree bytes do not add up to gene_ptr over a chunk (degree must equal diff(gene_ptr))");
-        return GECCO_CRF_EINVAL;
-    }
+    if ((rc = chunk_degrees(r, ck.u0, ck.u1, a1 - a0))) return rc;
     tm.lap("h2d csr", chunk_index);
     return GECCO_CRF_OK;
 }
@@ -613,28 +615,13 @@ int submit_direct_arrays(RunCtx &X, Lane &ln, int chunk_index) {
     int rc = check_hip(hipSetDevice(ln.device), "hipSetDevice");
     if (rc) return rc;
     const size_t ng = size_t(ck.g1 - ck.g0);
-    const int64_t a0 = r.gene_ptr[ck.g0], a1 = r.gene_ptr[ck.g1];
-    if (a0 < 0 || a1 < a0) {
-        set_error("gene_ptr must be non-decreasing and start at a non-negative offset");
-        return GECCO_CRF_EINVAL;
-    }
+    int64_t a0, a1, b0 = 0, b1 = 0;
+    if ((rc = chunk_extent(r.gene_ptr, "gene_ptr", ck.g0, ck.g1, a0, a1))) return rc;
     const size_t nnz = size_t(a1 - a0);
-    if (r.degree && byte_sum(r.degree + ck.g0, ng) != uint64_t(nnz)) {
-        set_error("degree bytes do not add up to gene_ptr over a chunk (degree must equal diff(gene_ptr))");
-        return GECCO_CRF_EINVAL;
-    }
-    int64_t b0 = 0;
-    size_t nb = 0;
+    if ((rc = chunk_degrees(r, ck.g0, ck.g1, a1 - a0))) return rc;
     const bool markers = r.want_segments && r.seg.criterion == 1;
-    if (markers) {
-        b0 = r.seg.bio_ptr[ck.g0];
-        const int64_t b1 = r.seg.bio_ptr[ck.g1];
-        if (b0 < 0 || b1 < b0) {
-            set_error("marker_ptr must be non-decreasing and start at a non-negative offset");
-            return GECCO_CRF_EINVAL;
-        }
-        nb = size_t(b1 - b0);
-    }
+    if (markers && (rc = chunk_extent(r.seg.bio_ptr, "marker_ptr", ck.g0, ck.g1, b0, b1))) return rc;
+    const size_t nb = size_t(b1 - b0);
     constexpr size_t kAsk = 32768;  // bytes from which a caller's OUTPUT buffer is asked whether it is pinned
     // An input array of kCopy bytes and more goes to device memory by a copy command on the compute stream (~8 us of engine
     // turnaround + the transfer, against a PCIe round trip for every tile that reads it in place); smaller ones are read from
@@ -668,16 +655,12 @@ int submit_direct_arrays(RunCtx &X, Lane &ln, int chunk_index) {
     // them) and the window kernel stores every gene exactly once (the 2-label register kernel: decided in submit)
     double *m_p = (r.p_out && !r.want_segments && ng * 8 >= kAsk) ? mapped_or_null(r.p_out + ck.g0) : nullptr;
     int8_t *m_y = (r.y_out && ng >= kAsk) ? mapped_or_null(r.y_out + ck.g0) : nullptr;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += align256(bytes + 32);
-        return o;
-    };
+    Carver io;
+    auto take = [&](size_t bytes) { return io.take(bytes + 32); };
     const size_t o_gp = take(m_gp ? 0 : (ng + 1) * 4), o_at = take(m_at ? 0 : (nnz + 8) * 4),
                  o_ann = take(r.want_segments ? ng + 32 : 0), o_bp = take(markers ? (ng + 1) * 4 : 0), o_bi = take(markers ? (nb + 4) * 4 : 0),
                  o_p = take((r.p_out && !r.want_segments && !m_p) ? ng * 8 : 0), o_y = take((r.y_out && !m_y) ? ng + 8 : 0);
-    if ((rc = ln.h_io.reserve(off, "hipHostMalloc staging"))) return rc;
+    if ((rc = ln.h_io.reserve(io.off, "hipHostMalloc staging"))) return rc;
     char *h = ln.h_io.p, *d = ln.h_io.dp;
     ln.x_gp = m_gp;
     if (!m_gp) {
@@ -769,6 +752,54 @@ int submit_plan(RunCtx &X, Lane &ln, int chunk_index) {
     return check_hip(hipEventRecord(ln.ev_up, ln.up), "hipEventRecord");
 }
 
+// The marginals and / or labels of a chunk.  A request for both takes plan_run_decode, or -- `pair`, the direct path -- the
+// pipelined pair on the one batch: marginals, then the labels from the score differences the tiles left behind.
+int run_chunk(RunCtx &X, Lane &ln, const int32_t *d_gp, const int32_t *d_at, double *d_p, int8_t *d_y, double *d_score, bool pair) {
+    const int32_t label = X.r.label;
+    if (X.windowed && X.viterbi && pair) {
+        int rc = plan_run_decode_pipelined(&ln.plan, d_gp, d_at, label, d_p, nullptr, nullptr, ln.comp);
+        if (rc) return rc;
+        return plan_run_decode_pipelined(nullptr, nullptr, nullptr, label, nullptr, &ln.plan, d_y, ln.comp);
+    }
+    if (X.windowed && X.viterbi) return plan_run_decode(ln.plan, d_gp, d_at, label, d_p, d_y, d_score, ln.comp);
+    if (X.windowed) return plan_run_windowed(ln.plan, d_gp, d_at, label, d_p, ln.comp);
+    if (X.viterbi) return plan_run_viterbi(ln.plan, d_gp, d_at, d_y, d_score, ln.comp);
+    return GECCO_CRF_OK;
+}
+
+// The refiner behind a chunk's marginals `d_p`; `d_ann`, `d_bp`, `d_bi`: where the chunk's annotated bytes and (antismash
+// criterion) its marker domains live.  Rows, their offsets and their count are written by the segmenter's last launch straight
+// into the lane's pinned block (written across PCIe, never read back across it); the probabilities of the rows' genes -- under
+// SURVEY.md 8d's weight law nine genes in ten -- are gathered in device memory and downloaded by the copy engine once the host
+// knows how many there are (read back from the pinned block by the host they came at 4 GB/s: 3.5 ms per C3 batch).
+int run_refiner(RunCtx &X, Lane &ln, const Chunk &ck, const double *d_p, const uint8_t *d_ann, const int32_t *d_bp, const int32_t *d_bi) {
+    const BatchRequest &r = X.r;
+    const int32_t nc = ck.c1 - ck.c0, ng = ck.u1 - ck.u0;
+    const size_t cap = std::min<size_t>(size_t(ng), size_t(ng) / 2 + size_t(nc)) + 1;
+    ln.seg_cap = int32_t(cap);
+    Carver blk;  // [total][pad..][seg_off: cap+1][rows: cap*4]
+    blk.take(256);
+    ln.o_off = blk.take((cap + 1) * 4);
+    ln.o_rows = blk.take(cap * 16);
+    ln.o_p = blk.off;
+    int rc = ln.h_seg.reserve(ln.o_p + 256, "hipHostMalloc segments");
+    if (rc) return rc;
+    if (r.seg_p_out && (rc = ln.d_segp.reserve(size_t(ng) * 8 + 8, "hipMalloc cluster probabilities"))) return rc;
+    char *dp = ln.h_seg.dp;
+    SegParams sp = r.seg;
+    sp.carry = 0;
+    sp.row_contig0 = ck.c0;  // (rows arrive in the batch's own indices)
+    sp.row_gene0 = ck.g0;
+    sp.bio_ptr = sp.bio_id = nullptr;
+    if (sp.criterion == 1) {  // (marker_ptr keeps the caller's offsets)
+        sp.bio_ptr = d_bp;
+        sp.bio_id = d_bi - ln.up_b0;
+    }
+    return plan_run_segment(ln.plan, d_p, d_ann, sp, reinterpret_cast<int32_t *>(dp + ln.o_rows), int32_t(cap),
+                            reinterpret_cast<int32_t *>(dp + ln.o_off), reinterpret_cast<int32_t *>(dp), ln.comp,
+                            r.seg_p_out ? reinterpret_cast<double *>(ln.d_segp.p) : nullptr, ng);
+}
+
 // Direct path: every launch of the (one) chunk on the compute stream, on the addresses submit_direct_arrays chose; the host then
 // waits for that stream (retire_begin) -- no copy command, no event, no second stream.  A 50-gene contig: one launch.
 int submit_direct(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
@@ -790,39 +821,8 @@ int submit_direct(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
             d_p = reinterpret_cast<double *>(ln.d_p.p);
         }
     }
-    if (X.windowed && X.viterbi) {
-        // marginals, then the labels from the score differences the tiles left behind (the pipelined pair on one batch)
-        if ((rc = plan_run_decode_pipelined(&ln.plan, d_gp, d_at, r.label, d_p, nullptr, nullptr, ln.comp))) return rc;
-        if ((rc = plan_run_decode_pipelined(nullptr, nullptr, nullptr, r.label, nullptr, &ln.plan, ln.x_y, ln.comp))) return rc;
-    } else if (X.windowed) {
-        if ((rc = plan_run_windowed(ln.plan, d_gp, d_at, r.label, d_p, ln.comp))) return rc;
-    } else if (X.viterbi) {
-        if ((rc = plan_run_viterbi(ln.plan, d_gp, d_at, ln.x_y, nullptr, ln.comp))) return rc;
-    }
-    if (r.want_segments) {
-        const int32_t nc = ck.c1 - ck.c0;
-        const size_t cap = std::min<size_t>(size_t(ng), size_t(ng) / 2 + size_t(nc)) + 1;
-        ln.seg_cap = int32_t(cap);
-        ln.o_off = 256;
-        ln.o_rows = ln.o_off + align256((cap + 1) * 4);
-        ln.o_p = ln.o_rows + align256(cap * 16);
-        if ((rc = ln.h_seg.reserve(ln.o_p + 256, "hipHostMalloc segments"))) return rc;
-        if (r.seg_p_out && (rc = ln.d_segp.reserve(size_t(ng) * 8 + 8, "hipMalloc cluster probabilities"))) return rc;
-        char *dp = ln.h_seg.dp;
-        SegParams sp = r.seg;
-        sp.carry = 0;
-        sp.row_contig0 = ck.c0;
-        sp.row_gene0 = ck.g0;
-        sp.bio_ptr = sp.bio_id = nullptr;
-        if (sp.criterion == 1) {
-            sp.bio_ptr = ln.x_bp;
-            sp.bio_id = ln.x_bi - ln.up_b0;
-        }
-        if ((rc = plan_run_segment(ln.plan, d_p, ln.x_ann, sp, reinterpret_cast<int32_t *>(dp + ln.o_rows), int32_t(cap),
-                                   reinterpret_cast<int32_t *>(dp + ln.o_off), reinterpret_cast<int32_t *>(dp), ln.comp,
-                                   r.seg_p_out ? reinterpret_cast<double *>(ln.d_segp.p) : nullptr, ng)))
-            return rc;
-    }
+    if ((rc = run_chunk(X, ln, d_gp, d_at, d_p, ln.x_y, nullptr, true))) return rc;
+    if (r.want_segments && (rc = run_refiner(X, ln, ck, d_p, ln.x_ann, ln.x_bp, ln.x_bi))) return rc;
     if (r.p_out && !p_to_host) {  // (p lives in device memory: the refiner reads it, or a window kernel with atomic maxima wrote it)
         ln.st->d2h_bytes += int64_t(ng) * 8;
         if ((rc = check_hip(hipMemcpyAsync(r.p_out + ck.g0, d_p, size_t(ng) * 8, hipMemcpyDeviceToHost, ln.comp), "D2H p"))) return rc;
@@ -843,7 +843,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     TraceMark tm;
     ln.chunk = chunk_index;
     ln.up_chunk = -1;
-    const int64_t a0 = ln.up_a0, b0 = ln.up_b0;
+    const int64_t a0 = ln.up_a0;
     const size_t nnz = size_t(ln.up_nnz), L = size_t(m.L);
     if (X.direct) return submit_direct(X, D, ln, chunk_index);
     if ((rc = check_hip(hipStreamWaitEvent(ln.comp, ln.ev_up, 0), "hipStreamWaitEvent"))) return rc;
@@ -901,14 +901,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
         tm.lap("launch", chunk_index);
         return GECCO_CRF_OK;
     }
-    if (X.windowed && X.viterbi) {
-        rc = plan_run_decode(ln.plan, d_gp, d_at, r.label, d_p, d_y, d_score, ln.comp);
-    } else if (X.windowed) {
-        rc = plan_run_windowed(ln.plan, d_gp, d_at, r.label, d_p, ln.comp);
-    } else if (X.viterbi) {
-        rc = plan_run_viterbi(ln.plan, d_gp, d_at, d_y, d_score, ln.comp);
-    }
-    if (rc) return rc;
+    if ((rc = run_chunk(X, ln, d_gp, d_at, d_p, d_y, d_score, false))) return rc;
     double *d_marg = nullptr, *d_lognorm = nullptr;
     if (X.full) {
         if ((rc = ln.d_marg.reserve(size_t(ng) * L * 8, "hipMalloc marginals"))) return rc;
@@ -917,37 +910,11 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
         d_lognorm = reinterpret_cast<double *>(ln.d_lognorm.p);
         if ((rc = plan_run_marginals_full(ln.plan, d_gp, d_at, d_marg, d_lognorm, ln.comp))) return rc;
     }
-    if (r.want_segments) {
-        // rows, their offsets and the probabilities of their genes are written by the kernels into pinned
-        // host memory: nothing but those few bytes crosses PCIe for a cluster call
-        const size_t cap = std::min<size_t>(size_t(ng), size_t(ng) / 2 + size_t(nc)) + 1;
-        ln.seg_cap = int32_t(cap);
-        ln.o_off = 256;
-        ln.o_rows = ln.o_off + align256((cap + 1) * 4);
-        ln.o_p = ln.o_rows + align256(cap * 16);
-        const size_t bytes = ln.o_p + 256;
-        if ((rc = ln.h_seg.reserve(bytes, "hipHostMalloc segments"))) return rc;
-        // the segmenter's last launch writes rows, offsets and count straight into the pinned block (written across PCIe,
-        // never read back across it); the probabilities of the rows' genes -- under SURVEY.md 8d's weight law nine genes in
-        // ten -- are gathered in device memory and downloaded by the copy engine once the host knows how many there are
-        // (read back from the pinned block by the host they came at 4 GB/s: 3.5 ms per C3 batch)
-        if (r.seg_p_out && (rc = ln.d_segp.reserve(size_t(ng) * 8 + 8, "hipMalloc cluster probabilities"))) return rc;
-        char *dp = ln.h_seg.dp;
-        int32_t *d_total = reinterpret_cast<int32_t *>(dp), *d_off = reinterpret_cast<int32_t *>(dp + ln.o_off),
-                *d_rows = reinterpret_cast<int32_t *>(dp + ln.o_rows);
-        SegParams sp = r.seg;
-        sp.carry = 0;
-        sp.row_contig0 = ck.c0;  // (rows arrive in the batch's own indices)
-        sp.row_gene0 = ck.g0;
-        sp.bio_ptr = sp.bio_id = nullptr;
-        if (sp.criterion == 1) {
-            sp.bio_ptr = reinterpret_cast<const int32_t *>(ln.d_bp.p);
-            sp.bio_id = reinterpret_cast<const int32_t *>(ln.d_bi.p) - b0;
-        }
-        if ((rc = plan_run_segment(ln.plan, d_p, reinterpret_cast<const uint8_t *>(r.annotated ? ln.d_ann.p : ln.d_deg.p), sp, d_rows, int32_t(cap), d_off, d_total,
-                                   ln.comp, r.seg_p_out ? reinterpret_cast<double *>(ln.d_segp.p) : nullptr, ng)))
-            return rc;
-    }
+    // (nothing but the rows' few bytes crosses PCIe for a cluster call)
+    if (r.want_segments &&
+        (rc = run_refiner(X, ln, ck, d_p, reinterpret_cast<const uint8_t *>(r.annotated ? ln.d_ann.p : ln.d_deg.p),
+                          reinterpret_cast<const int32_t *>(ln.d_bp.p), reinterpret_cast<const int32_t *>(ln.d_bi.p))))
+        return rc;
     tm.lap("launch", chunk_index);
     const bool c_p = r.p_out, c_y = r.y_out && !ln.y_to_host, c_score = r.score_out, c_marg = r.marg_out, c_ln = r.lognorm_out;
     if (!(c_p || c_y || c_score || c_marg || c_ln)) return check_hip(hipEventRecord(ln.done, ln.comp), "hipEventRecord");
