@@ -207,6 +207,11 @@ SIGNATURES = {
     "gecco_crf_forest_export": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gecco_crf_forest_predict": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp]),
     "gecco_crf_forest_free": (None, [_vp]),
+    "gecco_crf_forest_fit_batch": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                       _vp, _vp, _vp, _vp, _vp, _vp]
+    ),
+    "gecco_crf_forest_predict_batch": (ctypes.c_int, [_vp, ctypes.c_int32, _vp, _vp, _vp]),
     "gecco_crf_plan_time_windowed": (
         ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
     ),
@@ -1353,9 +1358,8 @@ class Forest:
     Near-equal feature values follow the sklearn 1.7.2 build, not its source: a split position is valid when
     ``Xf[p] > Xf[p - 1]`` on the float32 values (no 1e-7 margin), so values one ulp apart can be split."""
 
-    def __init__(self, col_ptr, row_idx, values, n_samples: int, y, n_classes, sample_counts, rand_state, max_features: int,
-                 device: int = 0):
-        lib = self._lib = load_library()
+    @staticmethod
+    def _arrays(col_ptr, row_idx, values, n_samples, y, n_classes, sample_counts, rand_state):
         cp = np.ascontiguousarray(col_ptr, dtype=np.int32)
         ri = np.ascontiguousarray(row_idx, dtype=np.int32)
         va = np.ascontiguousarray(values, dtype=np.float32)
@@ -1363,19 +1367,29 @@ class Forest:
         nc = np.ascontiguousarray(n_classes, dtype=np.uint8)
         sc = np.ascontiguousarray(sample_counts, dtype=np.int32)
         rs = np.ascontiguousarray(rand_state, dtype=np.uint32)
-        n_features, n_outputs = len(cp) - 1, len(nc)
-        if yy.shape != (int(n_samples), n_outputs) or sc.shape != (len(rs), int(n_samples)):
+        if yy.shape != (int(n_samples), len(nc)) or sc.shape != (len(rs), int(n_samples)):
             raise ValueError("forest fit: y must be (n_samples, n_outputs) and sample_counts (n_trees, n_samples)")
+        return cp, ri, va, yy, nc, sc, rs
+
+    def __init__(self, col_ptr, row_idx, values, n_samples: int, y, n_classes, sample_counts, rand_state, max_features: int,
+                 device: int = 0):
+        lib = self._lib = load_library()
+        cp, ri, va, yy, nc, sc, rs = self._arrays(col_ptr, row_idx, values, n_samples, y, n_classes, sample_counts, rand_state)
         h = _vp()
         self._h = None
-        _check(lib.gecco_crf_forest_fit(int(device), int(n_samples), n_features, _addr(cp), _addr(ri), _addr(va), n_outputs,
+        _check(lib.gecco_crf_forest_fit(int(device), int(n_samples), len(cp) - 1, _addr(cp), _addr(ri), _addr(va), len(nc),
                                         _addr(nc), _addr(yy), len(rs), _addr(sc), _addr(rs), int(max_features), ctypes.byref(h)))
+        self._adopt(h, len(cp) - 1)
+
+    def _adopt(self, h, n_features: int) -> None:
+        """Take over the fitted handle `h` and read its sizes."""
+        lib = self._lib
         self._h = h
         n_trees, n_out, mc = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        nodes = np.zeros(len(rs), dtype=np.int32)
-        depth = np.zeros(len(rs), dtype=np.int32)
-        _check(lib.gecco_crf_forest_info(h, ctypes.byref(n_trees), ctypes.byref(n_out), ctypes.byref(mc), nodes.ctypes.data,
-                                         depth.ctypes.data))
+        _check(lib.gecco_crf_forest_info(h, ctypes.byref(n_trees), ctypes.byref(n_out), ctypes.byref(mc), None, None))
+        nodes = np.zeros(n_trees.value, dtype=np.int32)
+        depth = np.zeros(n_trees.value, dtype=np.int32)
+        _check(lib.gecco_crf_forest_info(h, None, None, None, nodes.ctypes.data, depth.ctypes.data))
         self.n_trees, self.n_outputs, self.max_n_classes = n_trees.value, n_out.value, mc.value
         self.n_features = n_features
         self.node_count, self.max_depth = nodes, depth
@@ -1410,3 +1424,53 @@ class Forest:
         if h:
             self._lib.gecco_crf_forest_free(h)
             self._h = None
+
+
+def fit_forests(problems: Sequence[dict], max_features: int, device: int = 0) -> list:
+    """Fit one forest per problem in one launch (``gecco_crf_forest_fit_batch``): each problem is a dict of `Forest`'s
+    per-problem arguments (``col_ptr, row_idx, values, n_samples, y, n_classes, sample_counts, rand_state``); the number of
+    features, outputs and trees is shared.  Every returned `Forest` is bit for bit the one its problem gives alone."""
+    lib = load_library()
+    keys = ("col_ptr", "row_idx", "values", "n_samples", "y", "n_classes", "sample_counts", "rand_state")
+    arrs = [Forest._arrays(*(p[k] for k in keys)) for p in problems]
+    K = len(arrs)
+    if K == 0:
+        return []
+    shared = {(len(a[0]) - 1, len(a[4]), len(a[6])) for a in arrs}
+    if len(shared) != 1:
+        raise ValueError(f"forest fit: the problems of a batch share n_features, n_outputs and n_trees, got {sorted(shared)}")
+    n_features, n_outputs, n_trees = shared.pop()
+    n_samples = np.array([int(p["n_samples"]) for p in problems], dtype=np.int32)
+    ptrs = [(_vp * K)(*(_addr(a[i]) for a in arrs)) for i in range(7)]  # col_ptr, row_idx, values, y, n_classes, counts, states
+    out = (_vp * K)()
+    _check(lib.gecco_crf_forest_fit_batch(int(device), K, n_features, n_outputs, n_trees, int(max_features), _addr(n_samples),
+                                          ptrs[0], ptrs[1], ptrs[2], ptrs[4], ptrs[3], ptrs[5], ptrs[6], out))
+    forests = []
+    for k in range(K):  # (every handle has its owner before anything else can fail)
+        f = Forest.__new__(Forest)
+        f._lib, f._h = lib, _vp(out[k])
+        forests.append(f)
+    for f in forests:
+        f._adopt(f._h, n_features)
+    return forests
+
+
+def predict_forests(forests: Sequence[Forest], xs: Sequence) -> list:
+    """``forests[k].predict(xs[k])`` for every k with one launch and one download
+    (``gecco_crf_forest_predict_batch``); blocks without rows are allowed."""
+    if len(forests) != len(xs):
+        raise ValueError(f"forest predict: {len(forests)} forests but {len(xs)} blocks of rows")
+    K = len(forests)
+    if K == 0:
+        return []
+    xx = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
+    for f, x in zip(forests, xx):
+        if x.ndim != 2 or x.shape[1] != f.n_features:
+            raise ValueError(f"forest predict: expected rows of {f.n_features} features, got shape {x.shape}")
+    outs = [np.zeros((len(x), f.n_outputs), dtype=np.float64) for f, x in zip(forests, xx)]
+    n_rows = np.array([len(x) for x in xx], dtype=np.int32)
+    hs = (_vp * K)(*(f._h for f in forests))
+    xp = (_vp * K)(*(x.ctypes.data for x in xx))
+    op = (_vp * K)(*(o.ctypes.data for o in outs))
+    _check(load_library().gecco_crf_forest_predict_batch(hs, K, _addr(n_rows), xp, op))
+    return outs

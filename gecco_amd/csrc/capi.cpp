@@ -96,7 +96,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 280; }
+GECCO_API int gecco_crf_version(void) { return 290; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -1080,7 +1080,7 @@ GECCO_API int gecco_crf_domain_composition_members(int32_t device, const int32_t
     GECCO_GUARD_END
 }
 
-// ---- cluster type classifier (ABI 2.7.0) ----------------------------------------------------------
+// ---- cluster type classifier (ABI 2.7.0; several forests at once 2.9.0) ----------------------------------------------------------
 struct gecco_crf_forest {
     std::unique_ptr<Forest> f;
 };
@@ -1100,11 +1100,48 @@ GECCO_API int gecco_crf_forest_fit(int32_t device, int32_t n_samples, int32_t n_
     if (rc) return rc;
     if ((rc = check_device(device))) return rc;
     DeviceGuard guard;
-    Forest *f = nullptr;
-    if ((rc = forest_fit(device, n_samples, n_features, col_ptr, row_idx, values, n_outputs, n_classes, y, n_trees, sample_counts,
-                         rand_state, max_features, &f)))
+    const ForestProblem p{n_samples, col_ptr, row_idx, values, n_classes, y, sample_counts, rand_state};
+    std::vector<std::unique_ptr<Forest>> f;
+    if ((rc = forest_fit_batch(device, 1, n_features, n_outputs, n_trees, max_features, &p, /*lone=*/true, &f))) return rc;
+    *out = new gecco_crf_forest{std::move(f[0])};
+    return GECCO_CRF_OK;
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int32_t n_outputs,
+                                         int32_t n_trees, int32_t max_features, const int32_t *n_samples,
+                                         const int32_t *const *col_ptr, const int32_t *const *row_idx,
+                                         const float *const *values, const uint8_t *const *n_classes, const uint8_t *const *y,
+                                         const int32_t *const *sample_counts, const uint32_t *const *rand_state,
+                                         gecco_crf_forest **out) {
+    GECCO_GUARD_BEGIN
+    if (!out) {
+        set_error("gecco_crf_forest_fit_batch: null out");
+        return GECCO_CRF_EINVAL;
+    }
+    // (the range of n_problems is forest_fit_batch_check's to report: nothing is read or written past it here)
+    const bool sized = n_problems >= 1 && n_problems <= kForestMaxProblems;
+    for (int32_t k = 0; sized && k < n_problems; ++k) out[k] = nullptr;
+    if (sized && (!n_samples || !col_ptr || !row_idx || !values || !n_classes || !y || !sample_counts || !rand_state)) {
+        set_error("gecco_crf_forest_fit_batch: null buffer");
+        return GECCO_CRF_EINVAL;
+    }
+    std::vector<ForestProblem> problems;
+    for (int32_t k = 0; sized && k < n_problems; ++k)
+        problems.push_back(ForestProblem{n_samples[k], col_ptr[k], row_idx[k], values[k], n_classes[k], y[k], sample_counts[k],
+                                         rand_state[k]});
+    int rc = forest_fit_batch_check(n_problems, n_features, n_outputs, n_trees, max_features, problems.data());
+    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
+    DeviceGuard guard;
+    std::vector<std::unique_ptr<Forest>> f;
+    if ((rc = forest_fit_batch(device, n_problems, n_features, n_outputs, n_trees, max_features, problems.data(), /*lone=*/false,
+                               &f)))
         return rc;
-    *out = new gecco_crf_forest{std::unique_ptr<Forest>(f)};
+    std::vector<std::unique_ptr<gecco_crf_forest>> handles;  // (all of them, or none: an allocation may fail half way)
+    handles.reserve(f.size());
+    for (auto &forest : f) handles.emplace_back(new gecco_crf_forest{std::move(forest)});
+    for (int32_t k = 0; k < n_problems; ++k) out[k] = handles[size_t(k)].release();
     return GECCO_CRF_OK;
     GECCO_GUARD_END
 }
@@ -1151,8 +1188,26 @@ GECCO_API int gecco_crf_forest_predict(const gecco_crf_forest *h, int32_t n_rows
         return GECCO_CRF_EINVAL;
     }
     if (n_rows == 0) return GECCO_CRF_OK;
+    if (!x || !posit) {
+        set_error("forest_predict: null buffer");
+        return GECCO_CRF_EINVAL;
+    }
     DeviceGuard guard;
-    return forest_predict(h->f.get(), n_rows, x, posit);
+    const Forest *f = h->f.get();
+    return forest_predict_batch(&f, 1, &n_rows, &x, &posit);
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_forest_predict_batch(const gecco_crf_forest *const *h, int32_t n_problems, const int32_t *n_rows,
+                                             const double *const *x, double *const *posit) {
+    GECCO_GUARD_BEGIN
+    std::vector<const Forest *> f;
+    if (h && n_problems >= 1 && n_problems <= kForestMaxProblems)
+        for (int32_t k = 0; k < n_problems; ++k) f.push_back(h[k] ? h[k]->f.get() : nullptr);
+    int rc = forest_predict_batch_check(h ? f.data() : nullptr, n_problems, n_rows, x, posit);
+    if (rc) return rc;
+    DeviceGuard guard;
+    return forest_predict_batch(f.data(), n_problems, n_rows, x, posit);
     GECCO_GUARD_END
 }
 

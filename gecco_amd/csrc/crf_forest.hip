@@ -34,6 +34,12 @@
 // Range (checked on the host): n_samples <= 4096, n_features <= 8192, n_outputs <= 64, 1 or 2 classes per output.  Node
 // and stack storage is sized per tree (2 n - 1 nodes, n + 1 stack records) and every write is bounds-checked on the device;
 // a tree that would overflow stops and reports a status instead.
+//
+// Several forests in one launch (gecco_crf_forest_fit_batch): the grid is n_problems x n_trees workgroups, and
+// workgroup b builds tree b % n_trees of problem b / n_trees.  What the builder knows of its problem is one FitArgs record,
+// read from a table in device memory instead of the kernel arguments; every pointer in it addresses that problem's own
+// arrays, so a tree reads and writes nothing of another problem and its bits are those of the problem fitted alone.  The lone
+// fit is a batch of one.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -82,7 +88,8 @@ struct FitArgs {
     int32_t *stack;                    // [T][stack_cap][6]
     int32_t *left, *right, *feature, *n_node;
     double *threshold, *impurity, *weighted, *value;
-    int32_t *node_count, *max_depth, *status;
+    int32_t *node_count, *max_depth, *status;  // [T]
+    uint8_t *ncls;                              // [n_out], for predict
 };
 
 struct Shared {
@@ -362,9 +369,11 @@ __device__ void evaluate_feature(const FitArgs &A, Shared &s, int f, int a, int 
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kThreads) void forest_fit_kernel(FitArgs A) {
+__global__ __launch_bounds__(kThreads) void forest_fit_kernel(const FitArgs *__restrict__ problems, int32_t n_trees) {
     __shared__ Shared s;
-    const int t = blockIdx.x, tid = threadIdx.x;
+    const int problem = int(blockIdx.x) / n_trees;
+    const int t = int(blockIdx.x) - problem * n_trees, tid = threadIdx.x;
+    const FitArgs &A = problems[problem];  // uniform over the workgroup: scalar loads, like kernel arguments
     const int n = A.n, F = A.F;
     const int32_t *cnt = A.counts + size_t(t) * n;
     for (int i = tid; i < n; i += kThreads) s.w[i] = uint16_t(cnt[i]);
@@ -608,33 +617,45 @@ __global__ __launch_bounds__(kThreads) void forest_fit_kernel(FitArgs A) {
         A.max_depth[t] = depth_seen;
         A.status[t] = s.err;
     }
+    if (t == 0 && tid < A.n_out) A.ncls[tid] = (A.two_class >> tid) & 1u ? 2 : 1;
 }
 
+// One problem of a predict launch: a forest, its rows, and the first of its blocks in the grid.
+struct PredictArgs {
+    const int32_t *left, *right, *feature;
+    const double *threshold, *value;
+    const uint8_t *ncls;
+    int32_t n_trees, cap, n_out, mc, F, block0;
+    const double *x;
+    int64_t n_rows;
+    double *posit;
+};
+
 // One thread per (row, output): walk every tree in order, sum the normalised leaf values in fp64 (forest
-// _accumulate_prediction), divide by the number of trees, posit = 1 - proba[:, k, 0].
-__global__ __launch_bounds__(256) void forest_predict_kernel(const int32_t *left, const int32_t *right, const int32_t *feature,
-                                                             const double *threshold, const double *value, const uint8_t *ncls,
-                                                             int32_t n_trees, int32_t cap, int32_t n_out, int32_t mc, int32_t F,
-                                                             const double *x, int64_t n_rows, double *posit) {
-    const int64_t g = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (g >= n_rows * n_out) return;
-    const int64_t row = g / n_out;
-    const int k = int(g % n_out);
-    const double *xr = x + row * F;
+// _accumulate_prediction), divide by the number of trees, posit = 1 - proba[:, k, 0].  Block b serves problem
+// block_problem[b]; a thread's arithmetic depends on its own forest and row alone.
+__global__ __launch_bounds__(256) void forest_predict_kernel(const PredictArgs *__restrict__ problems,
+                                                             const int32_t *__restrict__ block_problem) {
+    const PredictArgs P = problems[block_problem[blockIdx.x]];
+    const int64_t g = int64_t(int(blockIdx.x) - P.block0) * blockDim.x + threadIdx.x;
+    if (g >= P.n_rows * P.n_out) return;
+    const int64_t row = g / P.n_out;
+    const int k = int(g % P.n_out);
+    const double *xr = P.x + row * P.F;
     double acc = 0.0;
-    for (int t = 0; t < n_trees; ++t) {
-        const size_t nb = size_t(t) * cap;
+    for (int t = 0; t < P.n_trees; ++t) {
+        const size_t nb = size_t(t) * P.cap;
         int node = 0;
-        while (left[nb + node] >= 0) {
-            const float xv = float(xr[feature[nb + node]]);  // predict input is validated to float32 first
-            node = double(xv) <= threshold[nb + node] ? left[nb + node] : right[nb + node];
+        while (P.left[nb + node] >= 0) {
+            const float xv = float(xr[P.feature[nb + node]]);  // predict input is validated to float32 first
+            node = double(xv) <= P.threshold[nb + node] ? P.left[nb + node] : P.right[nb + node];
         }
-        const double *v = value + (nb + node) * size_t(n_out) * mc + size_t(k) * mc;
-        double norm = ncls[k] == 2 ? v[0] + v[1] : v[0];
+        const double *v = P.value + (nb + node) * size_t(P.n_out) * P.mc + size_t(k) * P.mc;
+        double norm = P.ncls[k] == 2 ? v[0] + v[1] : v[0];
         if (norm == 0.0) norm = 1.0;
         acc += v[0] / norm;
     }
-    posit[g] = 1.0 - acc / double(n_trees);
+    P.posit[g] = 1.0 - acc / double(P.n_trees);
 }
 
 int fail(const std::string &msg) {
@@ -642,187 +663,266 @@ int fail(const std::string &msg) {
     return GECCO_CRF_EINVAL;
 }
 
-template <typename T>
-int dalloc(T **p, size_t n, const char *what) {
-    return check_hip(hipMalloc(reinterpret_cast<void **>(p), (n ? n : 1) * sizeof(T)), what);
-}
+// Byte offsets of arrays laid end to end in one allocation, each aligned to 256 bytes.
+struct Layout {
+    size_t bytes = 0;
+    template <typename T>
+    size_t add(size_t n) {
+        const size_t at = bytes;
+        bytes += (n * sizeof(T) + 255) / 256 * 256;
+        return at;
+    }
+};
+
+struct DeviceBuffer {
+    void *p = nullptr;
+    ~DeviceBuffer() {
+        if (p) (void)hipFree(p);
+    }
+    int alloc(size_t bytes, const char *what) { return check_hip(hipMalloc(&p, bytes ? bytes : 1), what); }
+    template <typename T>
+    T *at(size_t off) const {
+        return reinterpret_cast<T *>(static_cast<char *>(p) + off);
+    }
+};
 
 template <typename T>
-int upload(T **p, const T *src, size_t n, const char *what) {
-    int rc = dalloc(p, n, what);
-    if (rc || n == 0) return rc;
-    return check_hip(hipMemcpy(*p, src, n * sizeof(T), hipMemcpyHostToDevice), what);
+void stage(std::vector<unsigned char> &host, size_t off, const T *src, size_t n) {
+    if (n) std::memcpy(host.data() + off, src, n * sizeof(T));
+}
+
+int check_shared(const std::string &pre, int32_t n_features, int32_t n_outputs, int32_t n_trees, int32_t max_features) {
+    if (n_features < 1 || n_features > kForestMaxFeatures)
+        return fail(pre + "n_features must be in [1, " + std::to_string(kForestMaxFeatures) + "]");
+    if (n_outputs < 1 || n_outputs > kForestMaxOutputs)
+        return fail(pre + "n_outputs must be in [1, " + std::to_string(kForestMaxOutputs) + "]");
+    if (n_trees < 1 || n_trees > 65535) return fail(pre + "n_trees must be in [1, 65535]");
+    if (max_features < 1 || max_features > n_features) return fail(pre + "max_features must be in [1, n_features]");
+    return GECCO_CRF_OK;
+}
+
+int check_samples(const std::string &pre, int32_t n_samples) {
+    if (n_samples < 1 || n_samples > kForestMaxSamples)
+        return fail(pre + "n_samples must be in [1, " + std::to_string(kForestMaxSamples) + "]");
+    return GECCO_CRF_OK;
+}
+
+int check_data(const std::string &pre, int32_t n_features, int32_t n_outputs, int32_t n_trees, const ForestProblem &p) {
+    const int32_t n_samples = p.n_samples;
+    const int32_t *col_ptr = p.col_ptr, *row_idx = p.row_idx, *sample_counts = p.sample_counts;
+    if (!col_ptr || !p.n_classes || !p.y || !sample_counts || !p.rand_state) return fail(pre + "null buffer");
+    if (col_ptr[0] != 0) return fail(pre + "col_ptr[0] must be 0");
+    for (int32_t f = 0; f < n_features; ++f)
+        if (col_ptr[f + 1] < col_ptr[f]) return fail(pre + "col_ptr must be non-decreasing");
+    const int64_t nnz = col_ptr[n_features];
+    if (nnz > 0 && (!row_idx || !p.values)) return fail(pre + "null buffer");
+    for (int32_t f = 0; f < n_features; ++f)
+        for (int32_t e = col_ptr[f]; e < col_ptr[f + 1]; ++e) {
+            if (row_idx[e] < 0 || row_idx[e] >= n_samples) return fail(pre + "row index out of range");
+            if (e > col_ptr[f] && row_idx[e] <= row_idx[e - 1])
+                return fail(pre + "row indices must be strictly increasing within a column");
+            if (!std::isfinite(p.values[e])) return fail(pre + "values must be finite");
+        }
+    for (int32_t k = 0; k < n_outputs; ++k)
+        if (p.n_classes[k] < 1 || p.n_classes[k] > 2) return fail(pre + "every output must have 1 or 2 classes");
+    for (int64_t i = 0; i < int64_t(n_samples) * n_outputs; ++i)
+        if (p.y[i] >= p.n_classes[i % n_outputs]) return fail(pre + "class index out of range");
+    for (int64_t i = 0; i < int64_t(n_trees) * n_samples; ++i)
+        if (sample_counts[i] < 0 || sample_counts[i] > n_samples) return fail(pre + "bootstrap counts must be in [0, n_samples]");
+    for (int32_t t = 0; t < n_trees; ++t) {
+        int64_t tot = 0;
+        for (int32_t i = 0; i < n_samples; ++i) tot += sample_counts[int64_t(t) * n_samples + i];
+        if (tot < 1) return fail(pre + "a tree without samples");
+        if (tot >= (int64_t(1) << 24)) return fail(pre + "total weight of a tree must stay below 2^24");
+    }
+    return GECCO_CRF_OK;
+}
+
+std::string fit_prefix(bool lone, int32_t k) {
+    return lone ? std::string("forest_fit: ") : "forest_fit_batch: problem " + std::to_string(k) + ": ";
 }
 
 }  // namespace
 
 Forest::~Forest() {
-    for (void *p : {static_cast<void *>(d_left), static_cast<void *>(d_right), static_cast<void *>(d_feature),
-                    static_cast<void *>(d_n_node), static_cast<void *>(d_threshold), static_cast<void *>(d_impurity),
-                    static_cast<void *>(d_weighted), static_cast<void *>(d_value), static_cast<void *>(d_ncls)})
-        if (p) (void)hipFree(p);
+    if (d_slab) (void)hipFree(d_slab);
 }
 
 int forest_fit_check(int32_t n_samples, int32_t n_features, const int32_t *col_ptr, const int32_t *row_idx, const float *values,
                      int32_t n_outputs, const uint8_t *n_classes, const uint8_t *y, int32_t n_trees, const int32_t *sample_counts,
                      const uint32_t *rand_state, int32_t max_features) {
-    if (n_samples < 1 || n_samples > kForestMaxSamples)
-        return fail("forest_fit: n_samples must be in [1, " + std::to_string(kForestMaxSamples) + "]");
-    if (n_features < 1 || n_features > kForestMaxFeatures)
-        return fail("forest_fit: n_features must be in [1, " + std::to_string(kForestMaxFeatures) + "]");
-    if (n_outputs < 1 || n_outputs > kForestMaxOutputs)
-        return fail("forest_fit: n_outputs must be in [1, " + std::to_string(kForestMaxOutputs) + "]");
-    if (n_trees < 1 || n_trees > 65535) return fail("forest_fit: n_trees must be in [1, 65535]");
-    if (max_features < 1 || max_features > n_features) return fail("forest_fit: max_features must be in [1, n_features]");
-    if (!col_ptr || !n_classes || !y || !sample_counts || !rand_state) return fail("forest_fit: null buffer");
-    if (col_ptr[0] != 0) return fail("forest_fit: col_ptr[0] must be 0");
-    for (int32_t f = 0; f < n_features; ++f)
-        if (col_ptr[f + 1] < col_ptr[f]) return fail("forest_fit: col_ptr must be non-decreasing");
-    const int64_t nnz = col_ptr[n_features];
-    if (nnz > 0 && (!row_idx || !values)) return fail("forest_fit: null buffer");
-    for (int32_t f = 0; f < n_features; ++f)
-        for (int32_t e = col_ptr[f]; e < col_ptr[f + 1]; ++e) {
-            if (row_idx[e] < 0 || row_idx[e] >= n_samples) return fail("forest_fit: row index out of range");
-            if (e > col_ptr[f] && row_idx[e] <= row_idx[e - 1])
-                return fail("forest_fit: row indices must be strictly increasing within a column");
-            if (!std::isfinite(values[e])) return fail("forest_fit: values must be finite");
-        }
-    for (int32_t k = 0; k < n_outputs; ++k)
-        if (n_classes[k] < 1 || n_classes[k] > 2) return fail("forest_fit: every output must have 1 or 2 classes");
-    for (int64_t i = 0; i < int64_t(n_samples) * n_outputs; ++i)
-        if (y[i] >= n_classes[i % n_outputs]) return fail("forest_fit: class index out of range");
-    for (int64_t i = 0; i < int64_t(n_trees) * n_samples; ++i)
-        if (sample_counts[i] < 0 || sample_counts[i] > n_samples) return fail("forest_fit: bootstrap counts must be in [0, n_samples]");
-    for (int32_t t = 0; t < n_trees; ++t) {
-        int64_t tot = 0;
-        for (int32_t i = 0; i < n_samples; ++i) tot += sample_counts[int64_t(t) * n_samples + i];
-        if (tot < 1) return fail("forest_fit: a tree without samples");
-        if (tot >= (int64_t(1) << 24)) return fail("forest_fit: total weight of a tree must stay below 2^24");
-    }
-    return GECCO_CRF_OK;
+    const std::string pre = fit_prefix(true, 0);
+    const ForestProblem p{n_samples, col_ptr, row_idx, values, n_classes, y, sample_counts, rand_state};
+    int rc;
+    if ((rc = check_samples(pre, n_samples)) || (rc = check_shared(pre, n_features, n_outputs, n_trees, max_features))) return rc;
+    return check_data(pre, n_features, n_outputs, n_trees, p);
 }
 
-int forest_fit(int32_t device, int32_t n_samples, int32_t n_features, const int32_t *col_ptr, const int32_t *row_idx,
-               const float *values, int32_t n_outputs, const uint8_t *n_classes, const uint8_t *y, int32_t n_trees,
-               const int32_t *sample_counts, const uint32_t *rand_state, int32_t max_features, Forest **out) {
+int forest_fit_batch_check(int32_t n_problems, int32_t n_features, int32_t n_outputs, int32_t n_trees, int32_t max_features,
+                           const ForestProblem *problems) {
+    if (n_problems < 1 || n_problems > kForestMaxProblems)
+        return fail("forest_fit_batch: n_problems must be in [1, " + std::to_string(kForestMaxProblems) + "]");
+    if (!problems) return fail("forest_fit_batch: null buffer");
+    int rc = check_shared("forest_fit_batch: ", n_features, n_outputs, n_trees, max_features);
+    for (int32_t k = 0; k < n_problems && !rc; ++k) {
+        const std::string pre = fit_prefix(false, k);
+        if (!(rc = check_samples(pre, problems[k].n_samples))) rc = check_data(pre, n_features, n_outputs, n_trees, problems[k]);
+    }
+    return rc;
+}
+
+int forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int32_t n_outputs, int32_t n_trees,
+                     int32_t max_features, const ForestProblem *problems, bool lone, std::vector<std::unique_ptr<Forest>> *out) {
     int rc = check_hip(hipSetDevice(device), "hipSetDevice");
     if (rc) return rc;
-    const int32_t n = n_samples, F = n_features, T = n_trees;
-    // host side: CSR of the nonzero-valued entries, class bits, the output layout
-    const int32_t nnz = col_ptr[F];
-    std::vector<int32_t> row_ptr(size_t(n) + 1, 0), col_idx;
-    for (int32_t e = 0; e < nnz; ++e)
-        if (values[e] != 0.0f) row_ptr[size_t(row_idx[e]) + 1] += 1;
-    for (int32_t i = 0; i < n; ++i) row_ptr[size_t(i) + 1] += row_ptr[i];
-    col_idx.resize(size_t(row_ptr[n]));
-    {
-        std::vector<int32_t> fill(row_ptr.begin(), row_ptr.end() - 1);
-        for (int32_t f = 0; f < F; ++f)
-            for (int32_t e = col_ptr[f]; e < col_ptr[f + 1]; ++e)
-                if (values[e] != 0.0f) col_idx[size_t(fill[row_idx[e]]++)] = f;
+    const int32_t K = n_problems, F = n_features, T = n_trees;
+    // host side, per problem: CSR of the nonzero-valued entries, class bits, the output layout
+    struct Host {
+        std::vector<int32_t> row_ptr, col_idx;
+        std::vector<uint64_t> ybits;
+        uint64_t two = 0;
+        int32_t mc = 1, nnz = 0;
+        size_t col_ptr, row_idx, val, row_ptr_at, col_idx_at, ybits_at, counts, rand_state, stack;  // offsets in the work space
+    };
+    std::vector<Host> host(static_cast<size_t>(K));
+    std::vector<std::unique_ptr<Forest>> own(static_cast<size_t>(K));
+    Layout in;  // uploaded: the descriptor table, then every problem's inputs
+    const size_t table_at = in.add<FitArgs>(size_t(K));
+    for (int32_t k = 0; k < K; ++k) {
+        const ForestProblem &p = problems[k];
+        Host &h = host[size_t(k)];
+        const int32_t n = p.n_samples;
+        h.nnz = p.col_ptr[F];
+        h.row_ptr.assign(size_t(n) + 1, 0);
+        for (int32_t e = 0; e < h.nnz; ++e)
+            if (p.values[e] != 0.0f) h.row_ptr[size_t(p.row_idx[e]) + 1] += 1;
+        for (int32_t i = 0; i < n; ++i) h.row_ptr[size_t(i) + 1] += h.row_ptr[size_t(i)];
+        h.col_idx.resize(size_t(h.row_ptr[size_t(n)]));
+        {
+            std::vector<int32_t> fill(h.row_ptr.begin(), h.row_ptr.end() - 1);
+            for (int32_t f = 0; f < F; ++f)
+                for (int32_t e = p.col_ptr[f]; e < p.col_ptr[f + 1]; ++e)
+                    if (p.values[e] != 0.0f) h.col_idx[size_t(fill[size_t(p.row_idx[e])]++)] = f;
+        }
+        h.ybits.assign(size_t(n), 0);
+        for (int32_t o = 0; o < n_outputs; ++o)
+            if (p.n_classes[o] == 2) {
+                h.two |= uint64_t(1) << o;
+                h.mc = 2;
+            }
+        for (int32_t i = 0; i < n; ++i)
+            for (int32_t o = 0; o < n_outputs; ++o)
+                if (p.y[size_t(i) * n_outputs + o]) h.ybits[size_t(i)] |= uint64_t(1) << o;
+        h.col_ptr = in.add<int32_t>(size_t(F) + 1);
+        h.row_idx = in.add<int32_t>(size_t(h.nnz));
+        h.val = in.add<float>(size_t(h.nnz));
+        h.row_ptr_at = in.add<int32_t>(h.row_ptr.size());
+        h.col_idx_at = in.add<int32_t>(h.col_idx.size());
+        h.ybits_at = in.add<uint64_t>(h.ybits.size());
+        h.counts = in.add<int32_t>(size_t(T) * n);
+        h.rand_state = in.add<uint32_t>(size_t(T));
     }
-    std::vector<uint64_t> ybits(size_t(n), 0);
-    uint64_t two = 0;
-    int32_t mc = 1;
-    for (int32_t k = 0; k < n_outputs; ++k)
-        if (n_classes[k] == 2) {
-            two |= uint64_t(1) << k;
-            mc = 2;
-        }
-    for (int32_t i = 0; i < n; ++i)
-        for (int32_t k = 0; k < n_outputs; ++k)
-            if (y[size_t(i) * n_outputs + k]) ybits[size_t(i)] |= uint64_t(1) << k;
-
-    auto *f = new Forest();
-    std::unique_ptr<Forest> own(f);
-    f->device = device;
-    f->n_trees = T;
-    f->n_features = F;
-    f->n_outputs = n_outputs;
-    f->max_n_classes = mc;
-    f->cap = 2 * n - 1;
-    f->n_classes.assign(n_classes, n_classes + n_outputs);
-    const size_t slots = size_t(T) * f->cap;
-    if ((rc = dalloc(&f->d_left, slots, "forest alloc")) || (rc = dalloc(&f->d_right, slots, "forest alloc")) ||
-        (rc = dalloc(&f->d_feature, slots, "forest alloc")) || (rc = dalloc(&f->d_n_node, slots, "forest alloc")) ||
-        (rc = dalloc(&f->d_threshold, slots, "forest alloc")) || (rc = dalloc(&f->d_impurity, slots, "forest alloc")) ||
-        (rc = dalloc(&f->d_weighted, slots, "forest alloc")) ||
-        (rc = dalloc(&f->d_value, slots * n_outputs * mc, "forest alloc")) ||
-        (rc = upload(&f->d_ncls, n_classes, size_t(n_outputs), "forest upload")))
-        return rc;
-    struct Tmp {
-        int32_t *col_ptr = nullptr, *row_idx = nullptr, *row_ptr = nullptr, *col_idx = nullptr, *counts = nullptr, *stack = nullptr,
-                *node_count = nullptr, *max_depth = nullptr, *status = nullptr;
-        float *val = nullptr;
-        uint64_t *ybits = nullptr;
-        uint32_t *rand_state = nullptr;
-        ~Tmp() {
-            for (void *p : {static_cast<void *>(col_ptr), static_cast<void *>(row_idx), static_cast<void *>(row_ptr),
-                            static_cast<void *>(col_idx), static_cast<void *>(counts), static_cast<void *>(stack),
-                            static_cast<void *>(node_count), static_cast<void *>(max_depth), static_cast<void *>(status),
-                            static_cast<void *>(val), static_cast<void *>(ybits), static_cast<void *>(rand_state)})
-                if (p) (void)hipFree(p);
-        }
-    } d;
-    const int32_t stack_cap = n + 1;
-    if ((rc = upload(&d.col_ptr, col_ptr, size_t(F) + 1, "forest upload")) ||
-        (rc = upload(&d.row_idx, row_idx, size_t(nnz), "forest upload")) || (rc = upload(&d.val, values, size_t(nnz), "forest upload")) ||
-        (rc = upload(&d.row_ptr, row_ptr.data(), row_ptr.size(), "forest upload")) ||
-        (rc = upload(&d.col_idx, col_idx.data(), col_idx.size(), "forest upload")) ||
-        (rc = upload(&d.ybits, ybits.data(), ybits.size(), "forest upload")) ||
-        (rc = upload(&d.counts, sample_counts, size_t(T) * n, "forest upload")) ||
-        (rc = upload(&d.rand_state, rand_state, size_t(T), "forest upload")) ||
-        (rc = dalloc(&d.stack, size_t(T) * stack_cap * 6, "forest alloc")) || (rc = dalloc(&d.node_count, size_t(T), "forest alloc")) ||
-        (rc = dalloc(&d.max_depth, size_t(T), "forest alloc")) || (rc = dalloc(&d.status, size_t(T), "forest alloc")))
-        return rc;
-    FitArgs A{};
-    A.n = n;
-    A.F = F;
-    A.n_out = n_outputs;
-    A.mc = mc;
-    A.max_features = max_features;
-    A.cap = f->cap;
-    A.stack_cap = stack_cap;
-    A.two_class = two;
-    A.col_ptr = d.col_ptr;
-    A.row_idx = d.row_idx;
-    A.val = d.val;
-    A.row_ptr = d.row_ptr;
-    A.col_idx = d.col_idx;
-    A.ybits = d.ybits;
-    A.counts = d.counts;
-    A.rand_state = d.rand_state;
-    A.stack = d.stack;
-    A.left = f->d_left;
-    A.right = f->d_right;
-    A.feature = f->d_feature;
-    A.n_node = f->d_n_node;
-    A.threshold = f->d_threshold;
-    A.impurity = f->d_impurity;
-    A.weighted = f->d_weighted;
-    A.value = f->d_value;
-    A.node_count = d.node_count;
-    A.max_depth = d.max_depth;
-    A.status = d.status;
-    forest_fit_kernel<<<T, kThreads>>>(A);
+    Layout work = in;  // not uploaded: every problem's stacks, then node_count / max_depth / status of all K x T trees
+    for (int32_t k = 0; k < K; ++k) host[size_t(k)].stack = work.add<int32_t>(size_t(T) * (size_t(problems[k].n_samples) + 1) * 6);
+    const size_t result_at = work.add<int32_t>(size_t(3) * K * T);
+    DeviceBuffer d;
+    if ((rc = d.alloc(work.bytes, "forest alloc"))) return rc;
+    std::vector<unsigned char> up(in.bytes);
+    std::vector<FitArgs> table(static_cast<size_t>(K));
+    for (int32_t k = 0; k < K; ++k) {
+        const ForestProblem &p = problems[k];
+        const Host &h = host[size_t(k)];
+        const int32_t n = p.n_samples;
+        auto f = std::make_unique<Forest>();
+        f->device = device;
+        f->n_trees = T;
+        f->n_features = F;
+        f->n_outputs = n_outputs;
+        f->max_n_classes = h.mc;
+        f->cap = 2 * n - 1;
+        f->n_classes.assign(p.n_classes, p.n_classes + n_outputs);
+        const size_t slots = size_t(T) * f->cap;
+        Layout o;  // memory per forest: 40 bytes a node slot, and 8 n_outputs max_n_classes for its value
+        const size_t left = o.add<int32_t>(slots), right = o.add<int32_t>(slots), feature = o.add<int32_t>(slots),
+                     n_node = o.add<int32_t>(slots), threshold = o.add<double>(slots), impurity = o.add<double>(slots),
+                     weighted = o.add<double>(slots), value = o.add<double>(slots * n_outputs * h.mc),
+                     ncls = o.add<uint8_t>(size_t(n_outputs));
+        if ((rc = check_hip(hipMalloc(&f->d_slab, o.bytes), "forest alloc"))) return rc;
+        char *base = static_cast<char *>(f->d_slab);
+        f->d_left = reinterpret_cast<int32_t *>(base + left);
+        f->d_right = reinterpret_cast<int32_t *>(base + right);
+        f->d_feature = reinterpret_cast<int32_t *>(base + feature);
+        f->d_n_node = reinterpret_cast<int32_t *>(base + n_node);
+        f->d_threshold = reinterpret_cast<double *>(base + threshold);
+        f->d_impurity = reinterpret_cast<double *>(base + impurity);
+        f->d_weighted = reinterpret_cast<double *>(base + weighted);
+        f->d_value = reinterpret_cast<double *>(base + value);
+        f->d_ncls = reinterpret_cast<uint8_t *>(base + ncls);
+        stage(up, h.col_ptr, p.col_ptr, size_t(F) + 1);
+        stage(up, h.row_idx, p.row_idx, size_t(h.nnz));
+        stage(up, h.val, p.values, size_t(h.nnz));
+        stage(up, h.row_ptr_at, h.row_ptr.data(), h.row_ptr.size());
+        stage(up, h.col_idx_at, h.col_idx.data(), h.col_idx.size());
+        stage(up, h.ybits_at, h.ybits.data(), h.ybits.size());
+        stage(up, h.counts, p.sample_counts, size_t(T) * n);
+        stage(up, h.rand_state, p.rand_state, size_t(T));
+        FitArgs &A = table[size_t(k)];
+        A = FitArgs{};
+        A.n = n;
+        A.F = F;
+        A.n_out = n_outputs;
+        A.mc = h.mc;
+        A.max_features = max_features;
+        A.cap = f->cap;
+        A.stack_cap = n + 1;
+        A.two_class = h.two;
+        A.col_ptr = d.at<int32_t>(h.col_ptr);
+        A.row_idx = d.at<int32_t>(h.row_idx);
+        A.val = d.at<float>(h.val);
+        A.row_ptr = d.at<int32_t>(h.row_ptr_at);
+        A.col_idx = d.at<int32_t>(h.col_idx_at);
+        A.ybits = d.at<uint64_t>(h.ybits_at);
+        A.counts = d.at<int32_t>(h.counts);
+        A.rand_state = d.at<uint32_t>(h.rand_state);
+        A.stack = d.at<int32_t>(h.stack);
+        A.left = f->d_left;
+        A.right = f->d_right;
+        A.feature = f->d_feature;
+        A.n_node = f->d_n_node;
+        A.threshold = f->d_threshold;
+        A.impurity = f->d_impurity;
+        A.weighted = f->d_weighted;
+        A.value = f->d_value;
+        A.node_count = d.at<int32_t>(result_at) + size_t(k) * T;
+        A.max_depth = A.node_count + size_t(K) * T;
+        A.status = A.max_depth + size_t(K) * T;
+        A.ncls = f->d_ncls;
+        own[size_t(k)] = std::move(f);
+    }
+    stage(up, table_at, table.data(), table.size());
+    if ((rc = check_hip(hipMemcpy(d.p, up.data(), up.size(), hipMemcpyHostToDevice), "forest upload"))) return rc;
+    forest_fit_kernel<<<unsigned(K) * unsigned(T), kThreads>>>(d.at<FitArgs>(table_at), T);
     if ((rc = check_hip(hipGetLastError(), "forest fit kernel"))) return rc;
     if ((rc = check_hip(hipDeviceSynchronize(), "forest fit"))) return rc;
-    std::vector<int32_t> status(static_cast<size_t>(T));
-    f->node_count.resize(size_t(T));
-    f->max_depth.resize(size_t(T));
-    if ((rc = check_hip(hipMemcpy(status.data(), d.status, size_t(T) * 4, hipMemcpyDeviceToHost), "forest download")) ||
-        (rc = check_hip(hipMemcpy(f->node_count.data(), d.node_count, size_t(T) * 4, hipMemcpyDeviceToHost), "forest download")) ||
-        (rc = check_hip(hipMemcpy(f->max_depth.data(), d.max_depth, size_t(T) * 4, hipMemcpyDeviceToHost), "forest download")))
+    const size_t KT = size_t(K) * T;
+    std::vector<int32_t> result(3 * KT);
+    if ((rc = check_hip(hipMemcpy(result.data(), d.at<int32_t>(result_at), result.size() * 4, hipMemcpyDeviceToHost),
+                        "forest download")))
         return rc;
-    for (int32_t t = 0; t < T; ++t)
-        if (status[size_t(t)] != kOk) {
-            static const char *what[] = {"ok", "node capacity exceeded", "stack capacity exceeded",
-                                         "partition disagrees with the chosen split", "gather overflow"};
-            const int s = status[size_t(t)];
-            set_error("forest_fit: tree " + std::to_string(t) + ": " + (s > 0 && s < 5 ? what[s] : "unknown status"));
-            return GECCO_CRF_EUNSUPPORTED;
-        }
-    *out = own.release();
+    for (int32_t k = 0; k < K; ++k) {
+        const int32_t *nc = result.data() + size_t(k) * T, *md = nc + KT, *status = md + KT;
+        own[size_t(k)]->node_count.assign(nc, nc + T);
+        own[size_t(k)]->max_depth.assign(md, md + T);
+        for (int32_t t = 0; t < T; ++t)
+            if (status[t] != kOk) {
+                static const char *what[] = {"ok", "node capacity exceeded", "stack capacity exceeded",
+                                             "partition disagrees with the chosen split", "gather overflow"};
+                const int st = status[t];
+                set_error(fit_prefix(lone, k) + "tree " + std::to_string(t) + ": " + (st > 0 && st < 5 ? what[st] : "unknown status"));
+                return GECCO_CRF_EUNSUPPORTED;
+            }
+    }
+    *out = std::move(own);
     return GECCO_CRF_OK;
 }
 
@@ -847,27 +947,80 @@ int forest_export(const Forest *f, int32_t tree, int32_t *left, int32_t *right, 
     return GECCO_CRF_OK;
 }
 
-int forest_predict(const Forest *f, int32_t n_rows, const double *x, double *posit) {
-    if (!f) return fail("forest_predict: null forest");
-    if (n_rows < 0) return fail("forest_predict: n_rows must be >= 0");
-    if (n_rows == 0) return GECCO_CRF_OK;
-    if (!x || !posit) return fail("forest_predict: null buffer");
-    int rc = check_hip(hipSetDevice(f->device), "hipSetDevice");
+int forest_predict_batch_check(const Forest *const *f, int32_t n_problems, const int32_t *n_rows, const double *const *x,
+                               double *const *posit) {
+    if (n_problems < 1 || n_problems > kForestMaxProblems)
+        return fail("forest_predict_batch: n_problems must be in [1, " + std::to_string(kForestMaxProblems) + "]");
+    if (!f || !n_rows || !x || !posit) return fail("forest_predict_batch: null buffer");
+    for (int32_t k = 0; k < n_problems; ++k)
+        if (n_rows[k] < 0) return fail("forest_predict_batch: problem " + std::to_string(k) + ": n_rows must be >= 0");
+    for (int32_t k = 0; k < n_problems; ++k) {
+        if (!f[k]) return fail("forest_predict_batch: problem " + std::to_string(k) + ": null forest");
+        if (f[k]->device != f[0]->device) return fail("forest_predict_batch: every forest must be on one device");
+        if (n_rows[k] > 0 && (!x[k] || !posit[k])) return fail("forest_predict_batch: problem " + std::to_string(k) + ": null buffer");
+    }
+    return GECCO_CRF_OK;
+}
+
+int forest_predict_batch(const Forest *const *f, int32_t n_problems, const int32_t *n_rows, const double *const *x,
+                         double *const *posit) {
+    const int32_t K = n_problems;
+    std::vector<PredictArgs> table(static_cast<size_t>(K));
+    std::vector<int32_t> block_problem;
+    std::vector<size_t> x_at(static_cast<size_t>(K)), p_at(static_cast<size_t>(K));
+    Layout in, out;
+    for (int32_t k = 0; k < K; ++k) x_at[size_t(k)] = in.add<double>(size_t(n_rows[k]) * f[k]->n_features);
+    for (int32_t k = 0; k < K; ++k) {
+        p_at[size_t(k)] = out.add<double>(size_t(n_rows[k]) * f[k]->n_outputs);
+        const size_t cells = size_t(n_rows[k]) * f[k]->n_outputs;
+        table[size_t(k)].block0 = int32_t(block_problem.size());
+        block_problem.insert(block_problem.end(), (cells + 255) / 256, k);
+    }
+    if (block_problem.empty()) return GECCO_CRF_OK;  // no rows at all: no device is touched
+    // the table and the block map go up in one copy of their own, after the rows
+    const size_t small_at = in.bytes, table_at = in.add<PredictArgs>(size_t(K)), map_at = in.add<int32_t>(block_problem.size());
+    int rc = check_hip(hipSetDevice(f[0]->device), "hipSetDevice");
     if (rc) return rc;
-    struct Tmp {
-        double *x = nullptr, *p = nullptr;
-        ~Tmp() {
-            if (x) (void)hipFree(x);
-            if (p) (void)hipFree(p);
-        }
-    } d;
-    const size_t nx = size_t(n_rows) * f->n_features, np_ = size_t(n_rows) * f->n_outputs;
-    if ((rc = upload(&d.x, x, nx, "forest predict upload")) || (rc = dalloc(&d.p, np_, "forest predict alloc"))) return rc;
-    const unsigned blocks = unsigned((np_ + 255) / 256);
-    forest_predict_kernel<<<blocks, 256>>>(f->d_left, f->d_right, f->d_feature, f->d_threshold, f->d_value, f->d_ncls, f->n_trees,
-                                           f->cap, f->n_outputs, f->max_n_classes, f->n_features, d.x, n_rows, d.p);
+    DeviceBuffer d;
+    if ((rc = d.alloc(in.bytes + out.bytes, "forest predict alloc"))) return rc;
+    std::vector<unsigned char> up(in.bytes - small_at);
+    for (int32_t k = 0; k < K; ++k) {
+        const Forest &fk = *f[k];
+        PredictArgs &P = table[size_t(k)];
+        P.left = fk.d_left;
+        P.right = fk.d_right;
+        P.feature = fk.d_feature;
+        P.threshold = fk.d_threshold;
+        P.value = fk.d_value;
+        P.ncls = fk.d_ncls;
+        P.n_trees = fk.n_trees;
+        P.cap = fk.cap;
+        P.n_out = fk.n_outputs;
+        P.mc = fk.max_n_classes;
+        P.F = fk.n_features;
+        P.x = d.at<double>(x_at[size_t(k)]);
+        P.n_rows = n_rows[k];
+        P.posit = d.at<double>(in.bytes + p_at[size_t(k)]);
+        // rows go up straight from the caller's buffer: staging them would be one more pass over the largest input
+        if (n_rows[k] > 0 && (rc = check_hip(hipMemcpy(d.at<double>(x_at[size_t(k)]), x[k], size_t(n_rows[k]) * fk.n_features * sizeof(double),
+                                                       hipMemcpyHostToDevice),
+                                             "forest predict upload")))
+            return rc;
+    }
+    stage(up, table_at - small_at, table.data(), table.size());
+    stage(up, map_at - small_at, block_problem.data(), block_problem.size());
+    if ((rc = check_hip(hipMemcpy(d.at<unsigned char>(small_at), up.data(), up.size(), hipMemcpyHostToDevice),
+                        "forest predict upload")))
+        return rc;
+    forest_predict_kernel<<<unsigned(block_problem.size()), 256>>>(d.at<PredictArgs>(table_at), d.at<int32_t>(map_at));
     if ((rc = check_hip(hipGetLastError(), "forest predict kernel"))) return rc;
-    return check_hip(hipMemcpy(posit, d.p, np_ * sizeof(double), hipMemcpyDeviceToHost), "forest predict download");
+    std::vector<unsigned char> down(out.bytes);
+    if ((rc = check_hip(hipMemcpy(down.data(), d.at<unsigned char>(in.bytes), down.size(), hipMemcpyDeviceToHost),
+                        "forest predict download")))
+        return rc;
+    for (int32_t k = 0; k < K; ++k)
+        if (n_rows[k] > 0) std::memcpy(posit[k], down.data() + p_at[size_t(k)], size_t(n_rows[k]) * f[k]->n_outputs * sizeof(double));
+    return GECCO_CRF_OK;
 }
 
 }  // namespace gecco

@@ -10,6 +10,10 @@ indices).
 
     clf = TypeClassifier.trained(model_dir)      # or None: GECCO's embedded data / $GECCO_AMD_MODEL_DIR
     posit = clf.predict_probabilities(compositions)   # (n_clusters, n_classes), 1 - P(class absent)
+
+``cross_validate`` gives the held-out predictions of that classifier: k folds, every fold's forest fitted in one launch
+(``gecco_crf_forest_fit_batch``, DESIGN.md 9.3) and each bit for bit the forest its training rows give alone;
+``python -m gecco_amd.types_cv`` is its command line.
 """
 import os
 import pathlib
@@ -17,10 +21,11 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import _native
+from . import _native, cv
 
 __all__ = ["TypeClassifier", "TypeBinarizer", "ClusterType", "type_string", "probability_columns", "classified_cluster_table",
-           "load_npz", "csc_float32", "tree_seeds", "bootstrap_counts", "splitter_state"]
+           "load_npz", "csc_float32", "tree_seeds", "bootstrap_counts", "splitter_state", "cross_validate", "TypeCrossValidation",
+           "type_folds", "type_metrics", "read_training_data"]
 
 MAX_INT = int(np.iinfo(np.int32).max)  # sklearn.ensemble._forest.MAX_INT
 RAND_R_MAX = 2147483647                # sklearn.utils._random.RAND_R_MAX
@@ -187,7 +192,8 @@ class DeviceForest:
             return max(1, int(mf * n_features))
         return int(mf)
 
-    def fit(self, X, y) -> "DeviceForest":
+    def _problem(self, X, y) -> Tuple[Dict[str, Any], int]:
+        """The native fit's arguments for training set (X, y), with this forest's random streams drawn, and max_features."""
         shape, row, col, data = _as_coo(X)
         y = np.asarray(y)
         if y.ndim != 2 or y.shape[0] != shape[0]:
@@ -204,9 +210,32 @@ class DeviceForest:
         self.seeds = tree_seeds(self.random_state, self.n_estimators)
         counts = np.stack([bootstrap_counts(int(s), n) for s in self.seeds]) if n else np.zeros((self.n_estimators, 0), np.int32)
         states = np.array([splitter_state(int(s)) for s in self.seeds], dtype=np.uint32)
-        self.forest = _native.Forest(indptr, indices, values, n, codes, n_classes, counts, states,
-                                     self._max_features(int(shape[1])), device=self.device)
+        problem = dict(col_ptr=indptr, row_idx=indices, values=values, n_samples=n, y=codes, n_classes=n_classes,
+                       sample_counts=counts, rand_state=states)
+        return problem, self._max_features(int(shape[1]))
+
+    def fit(self, X, y) -> "DeviceForest":
+        problem, max_features = self._problem(X, y)
+        self.forest = _native.Forest(**problem, max_features=max_features, device=self.device)
         return self
+
+    @classmethod
+    def fit_many(cls, Xs: Sequence[Any], ys: Sequence[Any], *, n_estimators: int = 100, random_state=None, max_features="sqrt",
+                 device: int = 0) -> List["DeviceForest"]:
+        """One forest per training set ``(Xs[k], ys[k])``, all fitted by one launch (``_native.fit_forests``).  Forest k is
+        what ``DeviceForest(n_estimators, random_state, max_features).fit(Xs[k], ys[k])`` gives: it draws its random streams
+        (``tree_seeds``, ``bootstrap_counts``, ``splitter_state``) for its own number of samples, in the order of `Xs`.  The
+        sets share the number of features and of outputs."""
+        if len(Xs) != len(ys):
+            raise ValueError(f"{len(Xs)} matrices but {len(ys)} label matrices")
+        models = [cls(n_estimators=n_estimators, random_state=random_state, max_features=max_features, device=device) for _ in Xs]
+        prepared = [m._problem(X, y) for m, X, y in zip(models, Xs, ys)]
+        if not prepared:
+            return []
+        forests = _native.fit_forests([p for p, _ in prepared], prepared[0][1], device=device)
+        for m, f in zip(models, forests):
+            m.forest = f
+        return models
 
     def predict_posit(self, X) -> np.ndarray:
         if self.forest is None:
@@ -253,17 +282,8 @@ class TypeClassifier:
     def trained(cls, model_path=None, device: int = 0) -> "TypeClassifier":
         """Fit on ``domains.tsv`` / ``types.tsv`` / ``compositions.npz`` of `model_path` (GECCO's embedded data if None),
         with ``random_state=0``; with fewer than two classes nothing is fitted, like the reference."""
-        path = cls._embedded_dir() if model_path is None else pathlib.Path(model_path)
-        comp = load_npz(path / "compositions.npz")
-        with open(path / "domains.tsv") as fh:
-            domains = [line.strip() for line in fh]
-        types, unique = [], set()
-        with open(path / "types.tsv") as fh:
-            for line in fh:
-                names = frozenset(filter(None, line.split("\t")[1].strip().split(";")))
-                unique |= names
-                types.append(names)
-        clf = cls(classes=sorted(unique), random_state=0, device=device)
+        comp, domains, _, types = read_training_data(cls._embedded_dir() if model_path is None else model_path)
+        clf = cls(classes=sorted(set().union(*types)), random_state=0, device=device)
         if len(clf.classes_) > 1:
             clf.model.fit(comp, clf.binarizer.transform(types))
         clf.model.attributes_ = domains
@@ -296,6 +316,119 @@ class TypeClassifier:
             cluster.type = make(ty)
             cluster.type_probabilities = dict(zip(self.binarizer.classes_, proba))
         return clusters
+
+
+def read_training_data(path) -> Tuple[tuple, List[str], List[str], List[frozenset]]:
+    """The classifier's training files of a model directory, as ``gecco.types.TypeClassifier.trained`` reads them:
+    ``(compositions (a `load_npz` tuple), domains, cluster ids, type name sets)``."""
+    path = pathlib.Path(path)
+    comp = load_npz(path / "compositions.npz")
+    with open(path / "domains.tsv") as fh:
+        domains = [line.strip() for line in fh]
+    ids, types = [], []
+    with open(path / "types.tsv") as fh:
+        for line in fh:
+            cells = line.split("\t")
+            ids.append(cells[0])
+            types.append(frozenset(filter(None, cells[1].strip().split(";"))))
+    return comp, domains, ids, types
+
+
+# ---------------------------------------------------------------------------------------------- cross-validation
+def type_folds(n: int, splits: int = 10, shuffle: bool = True, seed: int = 42) -> List[Tuple[np.ndarray, np.ndarray]]:
+    """``sklearn.model_selection.KFold(splits, shuffle=shuffle, random_state=seed).split(range(n))``: the blocks of
+    ``cv.kfold_splits`` taken from ``RandomState(seed).permutation(n)`` (from ``arange(n)`` without shuffle), the train and
+    the test indices of a fold each sorted ascending."""
+    order = np.random.RandomState(seed).permutation(n) if shuffle else np.arange(n)
+    return [(np.sort(order[train]), np.sort(order[test])) for train, test in cv.kfold_splits(n, splits)]
+
+
+def _or_nan(num: float, den: float) -> float:
+    return float(num) / float(den) if den else float("nan")
+
+
+def type_metrics(truth, posit) -> Dict[str, Any]:
+    """Metrics of probabilities `posit` (rows x classes) against the 0/1 matrix `truth`.  Per class (arrays): ``auroc`` and
+    ``aupr`` (``cv.roc_auc`` / ``cv.average_precision``), ``precision``, ``recall`` and ``f1`` of ``posit > 0.5``.  Over
+    all classes: ``micro_aupr`` (the average precision of the flattened matrices) and ``subset_accuracy`` (the share of rows
+    whose predicted set is the true set).  What is undefined is NaN: AUROC and AUPR of a truth that is all one value,
+    precision when nothing is predicted positive, recall when nothing is truly positive, F1 (``2 tp / (2 tp + fp + fn)``)
+    when either of the two is."""
+    truth = np.asarray(truth) > 0.5
+    posit = np.asarray(posit, dtype=np.float64)
+    if truth.shape != posit.shape or truth.ndim != 2:
+        raise ValueError(f"truth {truth.shape} and posit {posit.shape} must be one rows x classes shape")
+    pred = posit > 0.5
+    nan = float("nan")
+
+    def ranked(t, p):
+        if t.size == 0 or t.all() or not t.any():
+            return nan, nan
+        return cv.roc_auc(t, p), cv.average_precision(t, p)
+
+    per = {name: np.full(truth.shape[1], nan) for name in ("auroc", "aupr", "precision", "recall", "f1")}
+    for k in range(truth.shape[1]):
+        t, p = truth[:, k], pred[:, k]
+        per["auroc"][k], per["aupr"][k] = ranked(t, posit[:, k])
+        tp, fp, fn = int((t & p).sum()), int((~t & p).sum()), int((t & ~p).sum())
+        per["precision"][k] = _or_nan(tp, tp + fp)
+        per["recall"][k] = _or_nan(tp, tp + fn)
+        if tp + fp and tp + fn:
+            per["f1"][k] = 2 * tp / (2 * tp + fp + fn)
+    out: Dict[str, Any] = dict(per)
+    out["n"] = int(truth.shape[0])
+    out["micro_aupr"] = ranked(truth.ravel(), posit.ravel())[1]
+    out["subset_accuracy"] = _or_nan(int((pred == truth).all(axis=1).sum()), truth.shape[0])
+    return out
+
+
+class TypeCrossValidation:
+    """Held-out type predictions.  ``classes``; ``truth`` (n x classes, 0/1); ``posit`` (n x classes: every row scored by
+    the forest of the fold that held it out); ``fold`` (per row); ``folds`` (``(train, test)`` indices); ``predicted``
+    (name sets, ``posit > 0.5``); ``fold_metrics`` (one `type_metrics` dict per fold, on its test rows) and ``pooled`` (on
+    all rows); ``models``: the folds' fitted `DeviceForest` s (they hold device memory while the result lives)."""
+
+    def __init__(self, classes: List[str], truth: np.ndarray, posit: np.ndarray, fold: np.ndarray,
+                 folds: List[Tuple[np.ndarray, np.ndarray]], models: List[DeviceForest]):
+        self.classes, self.truth, self.posit, self.fold, self.folds, self.models = classes, truth, posit, fold, folds, models
+        self.predicted = TypeBinarizer(classes).inverse_transform(posit > 0.5)
+        self.fold_metrics = [type_metrics(truth[test], posit[test]) for _, test in folds]
+        self.pooled = type_metrics(truth, posit)
+
+    def summary(self) -> str:
+        """The per-fold and pooled metrics as text, one block per fold and one line per class."""
+        def fmt(x: float) -> str:
+            return "nan" if np.isnan(x) else f"{x:.4f}"
+
+        lines = []
+        for name, m in [(f"fold {i}", m) for i, m in enumerate(self.fold_metrics)] + [("pooled", self.pooled)]:
+            lines.append(f"{name}: n={m['n']} subset_accuracy={fmt(m['subset_accuracy'])} micro_aupr={fmt(m['micro_aupr'])}")
+            for k, cls in enumerate(self.classes):
+                lines.append(f"  {cls}: " + " ".join(f"{key}={fmt(m[key][k])}" for key in ("auroc", "aupr", "precision", "recall", "f1")))
+        return "\n".join(lines) + "\n"
+
+
+def cross_validate(X, labels, *, classes: Optional[Sequence[str]] = None, splits: int = 10, shuffle: bool = True, seed: int = 42,
+                   random_state=0, n_estimators: int = 100, max_features="sqrt", device: int = 0) -> TypeCrossValidation:
+    """k-fold cross-validation of the type classifier on compositions `X` and type `labels` (strings, name sets or
+    ClusterType objects; a cluster without a type stays in).  The folds are `type_folds`; every fold fits
+    ``RandomForestClassifier(n_estimators, random_state=random_state, max_features=max_features)`` on its training rows,
+    all folds in one launch, and one more launch scores every fold's test rows."""
+    labels = list(labels)
+    dense = _dense(X)
+    if dense.ndim != 2 or dense.shape[0] != len(labels):
+        raise ValueError(f"one label per row of X: X is {dense.shape}, {len(labels)} labels")
+    classes = sorted(set().union(*map(_names, labels))) if classes is None else list(classes)
+    truth = TypeBinarizer(classes).transform(labels)
+    folds = type_folds(len(labels), splits, shuffle, seed)
+    models = DeviceForest.fit_many([dense[train] for train, _ in folds], [truth[train] for train, _ in folds],
+                                   n_estimators=n_estimators, random_state=random_state, max_features=max_features, device=device)
+    blocks = _native.predict_forests([m.forest for m in models], [dense[test] for _, test in folds])
+    posit = np.zeros(truth.shape, dtype=np.float64)
+    fold = np.zeros(len(labels), dtype=np.int64)
+    for i, ((_, test), block) in enumerate(zip(folds, blocks)):
+        posit[test], fold[test] = block, i
+    return TypeCrossValidation(classes, truth, posit, fold, folds, models)
 
 
 def classified_cluster_table(table, classifier: "TypeClassifier", compositions):

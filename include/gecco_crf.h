@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.8.0 = 280). */
+/* ABI version: major*100 + minor*10 + patch (2.9.0 = 290). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -566,6 +566,29 @@ int gecco_crf_forest_export(const gecco_crf_forest *f, int32_t tree, int32_t *ch
  * and touches no device.  Synchronous. */
 int gecco_crf_forest_predict(const gecco_crf_forest *f, int32_t n_rows, const double *x, double *posit);
 void gecco_crf_forest_free(gecco_crf_forest *f);
+
+/* ---- cluster type classifier, several forests at once (ABI 2.9.0) ----------------------------------------------------
+ * n_problems (1 .. 1024) independent fits in one launch of n_problems x n_trees workgroups: the folds of a
+ * cross-validation.  n_features, n_outputs, n_trees and max_features are shared; problem k brings its own n_samples[k], CSC
+ * matrix (col_ptr[k], row_idx[k], values[k]), n_classes[k][n_outputs], y[k], sample_counts[k] and rand_state[k], each as
+ * gecco_crf_forest_fit takes them (n_classes, hence max_n_classes, may differ between problems).  out[k] is an ordinary
+ * forest handle, node for node and bit for bit what gecco_crf_forest_fit returns for problem k alone, whatever the other
+ * problems are and whatever their order; gecco_crf_forest_fit is the batch of one.  Every argument is checked before any
+ * device work, with gecco_crf_forest_fit's ranges per problem; the message names the problem.  On any failure every out[k]
+ * is NULL and nothing stays allocated.  Memory: per problem 2 n - 1 node slots per tree of 40 + 8 n_outputs max_n_classes
+ * bytes each, which stay with the handle, and 24 (n + 1) + 4 n bytes per tree of work space.  Synchronous. */
+int gecco_crf_forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int32_t n_outputs, int32_t n_trees,
+                               int32_t max_features, const int32_t *n_samples, const int32_t *const *col_ptr,
+                               const int32_t *const *row_idx, const float *const *values, const uint8_t *const *n_classes,
+                               const uint8_t *const *y, const int32_t *const *sample_counts,
+                               const uint32_t *const *rand_state, gecco_crf_forest **out /* [n_problems] */);
+/* Forest f[k] scores its own n_rows[k] rows x[k] (n_rows[k] x n_features, row-major fp64) into posit[k]
+ * (n_rows[k] x n_outputs): one launch and one download for all problems (every non-empty block of rows is copied to the
+ * device straight from x[k], the forests' table in one more copy), each posit[k] bit for bit what
+ * gecco_crf_forest_predict gives.  n_rows[k] = 0 is valid (x[k] and posit[k] are then not read).  All forests must be on
+ * one device, otherwise GECCO_CRF_EINVAL.  Synchronous. */
+int gecco_crf_forest_predict_batch(const gecco_crf_forest *const *f, int32_t n_problems, const int32_t *n_rows,
+                                   const double *const *x, double *const *posit);
 
 #ifdef __cplusplus
 }
