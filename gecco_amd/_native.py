@@ -191,6 +191,16 @@ SIGNATURES = {
     "gecco_crf_trainer_grid_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_grid_scratch_bytes": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_grid_free": (None, [_vp]),
+    "gecco_crf_trainer_general_create": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, _c_i32p, _c_i32p,
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
+    ),
+    "gecco_crf_trainer_general_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
+    "gecco_crf_trainer_general_num_problems": (ctypes.c_int32, [_vp]),
+    "gecco_crf_trainer_general_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_general_scratch_bytes": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_general_free": (None, [_vp]),
     "gecco_crf_fisher_exact": (ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
     "gecco_crf_cluster_overlaps": (
         ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1175,7 +1185,7 @@ def _trainer_sets(sets):
         state_fid, trans_fid = _i32(state_fid).ravel(), _i32(trans_fid).ravel()
         if int(A) < 1 or state_fid.size % int(A) != 0:
             raise ValueError("state_fid must have num_attrs * L entries")
-        L = state_fid.size // int(A)  # (the library trains 2-label models only and says so for any other L)
+        L = state_fid.size // int(A)  # (the library says which label counts a family trains)
         if trans_fid.size != L * L:
             raise ValueError(f"trans_fid must have L * L = {L * L} entries, got {trans_fid.size}")
         seq_ptr = _i32(seq_ptr)
@@ -1338,6 +1348,33 @@ class TrainerGrid(TrainerBatch):
 
     def scratch_bytes(self, k: int = -1) -> int:
         """Scratch bytes of problem k; for k = -1 the work space allocated (the most one group of problems uses)."""
+        return int(self._c("scratch_bytes")(self._h, int(k)))
+
+
+class TrainerGeneral(_TrainerHandle):
+    """Training sets of CRFs with 2 to 32 labels resident on one device (``gecco_crf_trainer_general_*``).
+
+    ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features,
+    window, step)`` per problem, as ``TrainerGrid`` takes its sets; the label count of a problem is that of its
+    ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the active problems; problem k's f and g are bitwise what a
+    ``TrainerGeneral`` of problem k alone returns for ``ws[k]``."""
+
+    _family = "gecco_crf_trainer_general"
+    eval = _TrainerHandle._eval_problems
+
+    def __init__(self, problems, device: int = 0):
+        arrays, counts = _trainer_sets(problems)
+        if any(len(v) != len(problems) for v in counts.values()):
+            raise ValueError("every problem needs a window and a step")
+        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
+        c = {name: _i32_vector(v) for name, v in counts.items()}
+        self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], t["labels"],
+                     c["num_attrs"], c["num_labels"], c["window"], c["step"], t["state_fid"], t["trans_fid"],
+                     c["num_features"])
+        self.num_features = self._features = counts["num_features"]
+
+    def scratch_bytes(self, k: int = -1) -> int:
+        """Scratch bytes of problem k; for k = -1 the sum over the problems, which is what is allocated."""
         return int(self._c("scratch_bytes")(self._h, int(k)))
 
 

@@ -447,25 +447,23 @@ int fail(const std::string &msg) {
     return GECCO_CRF_EINVAL;
 }
 
-// One problem's training set as a lone trainer builds it: the host arrays it uploads and what eval needs afterwards.
-struct HostProblem {
-    int32_t A = 0, n_items = 0, K = 0;
-    int64_t n_win = 0;
-    std::vector<int32_t> state_fid, trans_fid;  // [A*2], [4]: feature id of every dense slot, or -1
-    std::vector<double> empirical;              // [K] observed feature counts over all windows
-    std::vector<int32_t> item_ptr, attr_id, label, win_start, iw_first, iw_cnt, iw_off, attr_ptr, attr_items;
-};
+}  // namespace
 
-// Checks one problem (the lone trainer's checks and messages) and builds its windows, coverage, empirical counts and
-// attribute -> items transpose.
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
-                  const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, HostProblem *hp) {
+                  const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
+                  HostProblem *hp) {
     if (!seq_ptr || n_seqs < 0 || !state_fid || !trans_fid) return fail("trainer: null argument");
-    if (num_labels != 2) {
+    if (max_labels == 2 && num_labels != 2) {
         set_error("trainer: only 2-label models can be trained (GECCO's protein and domain modes are binary)");
         return GECCO_CRF_EUNSUPPORTED;
     }
+    if (num_labels < 2 || num_labels > max_labels) {
+        set_error("trainer: " + std::to_string(num_labels) + " labels; models of 2 to " + std::to_string(max_labels) +
+                  " labels can be trained");
+        return GECCO_CRF_EUNSUPPORTED;
+    }
+    const int32_t L = num_labels;
     if (window < 1 || window > kTrainMaxW) {
         set_error("trainer: window of " + std::to_string(window) + " items; windows of 1 to 32 items are supported");
         return GECCO_CRF_EUNSUPPORTED;
@@ -482,22 +480,23 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
     if (n_items > 0 && item_ptr[0] != 0) return fail("trainer: item_ptr[0] must be 0");
     for (int32_t i = 0; i < n_items; ++i) {
         if (item_ptr[i + 1] < item_ptr[i]) return fail("trainer: item_ptr is not monotone");
-        if (labels[i] != 0 && labels[i] != 1) return fail("trainer: labels must be 0 or 1");
+        if (labels[i] < 0 || labels[i] >= L)
+            return fail(max_labels == 2 ? "trainer: labels must be 0 or 1" : "trainer: labels must lie in [0, num_labels)");
     }
     const int32_t nnz = n_items > 0 ? item_ptr[n_items] : 0;
     if (nnz > 0 && !attr_id) return fail("trainer: null argument");
     for (int32_t k = 0; k < nnz; ++k)
         if (attr_id[k] < 0 || attr_id[k] >= num_attrs) return fail("trainer: attribute id out of range");
-    for (int64_t k = 0; k < int64_t(num_attrs) * 2; ++k)
+    for (int64_t k = 0; k < int64_t(num_attrs) * L; ++k)
         if (state_fid[k] < -1 || state_fid[k] >= num_features) return fail("trainer: state feature id out of range");
-    for (int k = 0; k < 4; ++k)
+    for (int k = 0; k < L * L; ++k)
         if (trans_fid[k] < -1 || trans_fid[k] >= num_features) return fail("trainer: transition feature id out of range");
 
     hp->A = num_attrs;
     hp->n_items = n_items;
     hp->K = num_features;
-    hp->state_fid.assign(state_fid, state_fid + int64_t(num_attrs) * 2);
-    hp->trans_fid.assign(trans_fid, trans_fid + 4);
+    hp->state_fid.assign(state_fid, state_fid + int64_t(num_attrs) * L);
+    hp->trans_fid.assign(trans_fid, trans_fid + L * L);
 
     // windows (gecco/_meta.py sliding_window, no padding) and, per item, the windows covering it
     std::vector<int32_t> &win_start = hp->win_start, &iw_first = hp->iw_first, &iw_cnt = hp->iw_cnt, &iw_off = hp->iw_off;
@@ -525,12 +524,12 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
     hp->empirical.assign(size_t(num_features), 0.0);
     for (int32_t i = 0; i < n_items; ++i)
         for (int32_t k = item_ptr[i]; k < item_ptr[i + 1]; ++k) {
-            const int32_t fid = hp->state_fid[size_t(attr_id[k]) * 2 + labels[i]];
+            const int32_t fid = hp->state_fid[size_t(attr_id[k]) * L + labels[i]];
             if (fid >= 0) hp->empirical[fid] += iw_cnt[i];
         }
     for (int32_t i0 : win_start)
         for (int32_t j = 1; j < window; ++j) {
-            const int32_t fid = hp->trans_fid[labels[i0 + j - 1] * 2 + labels[i0 + j]];
+            const int32_t fid = hp->trans_fid[labels[i0 + j - 1] * L + labels[i0 + j]];
             if (fid >= 0) hp->empirical[fid] += 1.0;
         }
 
@@ -553,6 +552,8 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
     }
     return GECCO_CRF_OK;
 }
+
+namespace {
 
 // Transition weights of w as the window kernel takes them.
 TransArgs trans_args(const std::vector<int32_t> &trans_fid, const double *w) {
@@ -648,7 +649,7 @@ int trainer_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr
     for (int32_t k = 0; k < n_sets; ++k) {
         HostProblem hp;
         int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
-                               window[k], step[k], state_fid[k], trans_fid[k], num_features[k], &hp);
+                               window[k], step[k], state_fid[k], trans_fid[k], num_features[k], 2, &hp);
         if (rc) {
             if (family)
                 set_error("trainer " + t->family + (problem_set ? ": set " : ": problem ") + std::to_string(k) + ": " +

@@ -6,10 +6,29 @@
 // one set with one problem, a batch is problem k on set k with one window and step.
 #pragma once
 #include <cstdint>
+#include <vector>
 
 namespace gecco {
 
 struct Trainer;
+struct TrainerGeneral;
+
+// One problem's training set as a trainer builds it on the host: the arrays it uploads and what eval needs afterwards.
+struct HostProblem {
+    int32_t A = 0, n_items = 0, K = 0;
+    int64_t n_win = 0;
+    std::vector<int32_t> state_fid, trans_fid;  // [A*L], [L*L]: feature id of every dense slot, or -1
+    std::vector<double> empirical;              // [K] observed feature counts over all windows
+    std::vector<int32_t> item_ptr, attr_id, label, win_start, iw_first, iw_cnt, iw_off, attr_ptr, attr_items;
+};
+
+// Checks one problem (the lone trainer's checks and messages) and builds its windows, coverage, empirical counts and
+// attribute -> items transpose.  max_labels = 2: the 2-label families (any other num_labels is "only 2-label models");
+// larger: the general family, num_labels in [2, max_labels] and labels in [0, num_labels).
+int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
+                  const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
+                  const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
+                  HostProblem *hp);
 
 // Sets as gecco_crf_trainer_grid_create takes them (one entry per set in the set arrays, each with its own window and
 // step), problem k on set problem_set[k], or on set k where problem_set is NULL (then n_problems == n_sets).
@@ -28,5 +47,18 @@ int64_t trainer_num_windows(const Trainer *t, int32_t k);
 // Scratch bytes of problem k; k = -1: the work space allocated (the most one group may use).  -1 for a bad k.
 int64_t trainer_scratch_bytes(const Trainer *t, int32_t k);
 void trainer_destroy(Trainer *t);
+
+// The general-label family (gecco_crf_trainer_general_*, crf_train_general.hip): the same objective for 2 to 32 labels,
+// problem k with its own label count, window and step.  Errors carry "trainer general: problem k: ".
+int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                           const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                           const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                           const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                           TrainerGeneral **out);
+int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g);
+int32_t trainer_general_num_problems(const TrainerGeneral *t);
+int64_t trainer_general_num_windows(const TrainerGeneral *t, int32_t k);
+int64_t trainer_general_scratch_bytes(const TrainerGeneral *t, int32_t k);  // (k = -1: the sum over the problems)
+void trainer_general_destroy(TrainerGeneral *t);
 
 }  // namespace gecco

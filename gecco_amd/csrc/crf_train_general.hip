@@ -1,0 +1,505 @@
+// Training objective and gradient of a linear-chain CRF with 2 to 32 labels (gecco_crf_trainer_general_*; DESIGN.md
+// §4.9b).  The objective is crf_train.hip's:
+//     f(w) = sum over windows of (log Z(window) - score(gold labels of the window))
+//     g(w) = expected feature counts - empirical feature counts
+// over the sliding windows of every sequence, without the regularisation terms.
+//
+// Every problem has its own label count L, window W and step, and runs its own launches on the trainer's stream (no
+// kernel ever sees two problems, so a problem's bits cannot depend on its neighbours):
+//   1. item scores     one thread per (item, label): s[i][y] = sum of the state weights of its attributes (CSR order)
+//   2. windows         G = the power of two at or above L lanes per window, lane i owning label i; log-space
+//                      forward-backward.  log alpha_t is stored in the window's node-marginal slots and overwritten by
+//                      the marginals on the way back.  A workgroup runs a fixed 128 windows, keeps the pairwise
+//                      expectations xi[i][.] of all of them in registers, and writes one block (f, xi[L][L])
+//   3. item marginals  one thread per (item, label): the node marginals of the windows covering it, in window order
+//   4. attr counts     one workgroup per attribute: the item marginals over the attribute -> items transpose
+//   5/6. block sums    fixed-geometry two-stage sum over the workgroups' blocks
+// Log space throughout: right for any finite weights, no second path.  No float atomics: every sum has one fixed order.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/gecco_crf.h"
+#include "crf_model.hpp"
+#include "crf_plan.hpp"
+#include "crf_train.hpp"
+
+namespace gecco {
+
+namespace {
+
+constexpr int kTrainGenThreads = 256;          // threads per workgroup of every kernel
+constexpr int kTrainGenWindowsPerBlock = 128;  // windows per workgroup of the window kernel, whatever L is
+constexpr int kTrainGenReduceSlabs = 32;       // first stage of the block sums: a fixed number of slabs
+constexpr int kTrainGenMaxL = 32;
+
+// One problem as its kernels take it (by value).  The set arrays are the problem's own slices.
+struct GenProb {
+    const int32_t *item_ptr, *attr_id, *label, *win_start, *iw_first, *iw_cnt, *iw_off, *attr_ptr, *attr_items;
+    const double *wstate;  // [A][L] state weights of this evaluation
+    const double *trans;   // [L][L] transition weights
+    double *score;         // [n_items][L]
+    double *item_marg;     // [n_items][L]
+    double *marg;          // [n_win][W][L]: log alpha on the way forward, node marginals afterwards
+    double *partial;       // [n_blocks][1 + L*L]: per workgroup of the window kernel, f then xi
+    double *slab;          // [kTrainGenReduceSlabs][1 + L*L]
+    double *out;           // [1 + L*L + A*L]: f, xi, expected state counts
+    int64_t n_win;
+    int32_t n_items, A, L, W, step, n_blocks;
+};
+
+__global__ void __launch_bounds__(kTrainGenThreads) gen_item_scores(GenProb P) {
+    const int64_t idx = static_cast<int64_t>(blockIdx.x) * kTrainGenThreads + threadIdx.x;
+    if (idx >= static_cast<int64_t>(P.n_items) * P.L) return;
+    const int32_t i = static_cast<int32_t>(idx / P.L), y = static_cast<int32_t>(idx % P.L);
+    double s = 0.0;
+    for (int32_t k = P.item_ptr[i]; k < P.item_ptr[i + 1]; ++k) s += P.wstate[static_cast<int64_t>(P.attr_id[k]) * P.L + y];
+    P.score[idx] = s;
+}
+
+// G lanes per window (G a power of two, L <= G), lane i owning label i; 256 / G windows run side by side, and a
+// workgroup runs its kTrainGenWindowsPerBlock windows in rounds of that many.  Everything is in log space:
+//     forward   la_t[j] = s_t[j] + lse_i(la_{t-1}[i] + T[i][j])
+//     backward  lb_{t-1}[i] = lse_j(T[i][j] + s_t[j] + lb_t[j]),   marginal_t[i] = exp(la_t[i] + lb_t[i] - log Z)
+//     pairwise  xi_t[i][j] = marginal_{t-1}[i] * e_ij / sum_j e_ij,   e_ij = exp(T[i][j] + s_t[j] + lb_t[j] - max_j),
+// so the pairwise term reuses the exponentials of the backward step (e_ij <= 1 and their sum >= 1: nothing overflows, and
+// what underflows is below 1e-308 of a probability).  A lane reads its neighbours' values by shuffles inside its group
+// of G lanes and the transitions from LDS (both orientations, so that either read is conflict-free).  Lanes at or above
+// L compute on zeros and store nothing.  xi[i][.] accumulates in the registers of lane i over the positions and windows
+// of its slot, in that order; the slots of a wave are then summed by a butterfly, the four waves in wave order.
+template <int G>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_windows(GenProb P) {
+    constexpr int kSlots = kTrainGenThreads / G;  // windows side by side in a workgroup
+    __shared__ double tT[G * G];             // [i][j] = T[i][j]
+    __shared__ double tTt[G * G];            // [j][i] = T[i][j]
+    __shared__ double xi_sh[G * G];          // [j][i]
+    __shared__ double f_sh;
+    const int tid = threadIdx.x;
+    const int L = P.L, W = P.W;
+    const int i = tid % G, slot = tid / G;
+    const bool lab = i < L;
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int a = e / G, b = e % G;
+        const double v = (a < L && b < L) ? P.trans[a * L + b] : 0.0;
+        tT[e] = v;
+        tTt[b * G + a] = v;
+    }
+    __syncthreads();
+
+    double xacc[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) xacc[k] = 0.0;
+    double facc = 0.0;
+    double v[G];
+    const int64_t w_base = static_cast<int64_t>(blockIdx.x) * kTrainGenWindowsPerBlock;
+    for (int r = 0; r < kTrainGenWindowsPerBlock / kSlots; ++r) {
+        const int64_t w = w_base + r * kSlots + slot;
+        if (w >= P.n_win) continue;  // (a whole group of G lanes: the shuffles below stay inside the group)
+        const int64_t i0 = P.win_start[w];
+        const double *sc = P.score + i0 * L;
+        const int32_t *label = P.label + i0;
+        double *mw = P.marg + w * W * L;
+
+        double la = lab ? sc[i] : 0.0;
+        int yprev = label[0];
+        double gold = (lab && yprev == i) ? la : 0.0;  // this label's share of the gold path's score
+        if (lab) mw[i] = la;
+        for (int t = 1; t < W; ++t) {
+            double mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = __shfl(la, k, G) + tT[k * G + i];
+                    mx = fmax(mx, v[k]);
+                }
+            double sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) sum += exp(v[k] - mx);
+            const double s = lab ? sc[t * L + i] : 0.0;
+            la = mx + log(sum) + s;
+            const int y = label[t];
+            if (lab && y == i) gold += s + tT[yprev * G + i];
+            yprev = y;
+            if (lab) mw[t * L + i] = la;
+        }
+        double mx = -INFINITY, gold_all = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            if (k < L) {
+                v[k] = __shfl(la, k, G);
+                mx = fmax(mx, v[k]);
+                gold_all += __shfl(gold, k, G);
+            }
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            if (k < L) sum += exp(v[k] - mx);
+        const double logz = mx + log(sum);
+        if (i == 0) facc += logz - gold_all;
+
+        if (lab) mw[(W - 1) * L + i] = exp(la - logz);
+        double lb = 0.0;
+        for (int t = W - 1; t >= 1; --t) {
+            const double q = (lab ? sc[t * L + i] : 0.0) + lb;  // log of exp(s_t[i]) beta_t[i]
+            const double lap = lab ? mw[(t - 1) * L + i] : 0.0;  // log alpha_{t-1}[i], stored by this lane
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = tTt[k * G + i] + __shfl(q, k, G);
+                    mx = fmax(mx, v[k]);
+                }
+            sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = exp(v[k] - mx);
+                    sum += v[k];
+                }
+            lb = mx + log(sum);
+            const double m = exp(lap + lb - logz);
+            const double c = m / sum;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) xacc[k] += c * v[k];
+            if (lab) mw[(t - 1) * L + i] = m;
+        }
+    }
+
+    // the slots of a wave: a butterfly over the lanes that own the same label (both partners form the same sum)
+    for (int off = 32; off >= G; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
+        facc += __shfl_xor(facc, off);
+    }
+    // the waves, in wave order
+    const int wave = tid / 64, lane = tid % 64;
+    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
+        if (wave == wv && lane < G) {
+#pragma unroll
+            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
+            if (lane == 0) f_sh = (wv ? f_sh : 0.0) + facc;
+        }
+        __syncthreads();
+    }
+    double *part = P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L);
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int k = e / G, a = e % G;
+        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
+    }
+    if (tid == 0) part[0] = f_sh;
+}
+
+__global__ void __launch_bounds__(kTrainGenThreads) gen_item_marginals(GenProb P) {
+    const int64_t idx = static_cast<int64_t>(blockIdx.x) * kTrainGenThreads + threadIdx.x;
+    if (idx >= static_cast<int64_t>(P.n_items) * P.L) return;
+    const int32_t i = static_cast<int32_t>(idx / P.L), y = static_cast<int32_t>(idx % P.L);
+    const int64_t first = P.iw_first[i];
+    const int32_t cnt = P.iw_cnt[i];
+    int32_t off = P.iw_off[i];
+    double p = 0.0;
+    for (int32_t k = 0; k < cnt; ++k, off -= P.step) p += P.marg[((first + k) * P.W + off) * P.L + y];
+    P.item_marg[idx] = p;
+}
+
+// Expected state counts: one workgroup per attribute, as 256 / G rows of G labels.  Row r sums the items r, r + rows, ...
+// of the attribute's list, then the rows are summed by a tree.
+__global__ void __launch_bounds__(kTrainGenThreads) gen_attr_counts(GenProb P, int32_t G) {
+    __shared__ double sh[kTrainGenThreads];
+    const int32_t a = static_cast<int32_t>(blockIdx.x);
+    const int32_t y = threadIdx.x % G, r = threadIdx.x / G, rows = kTrainGenThreads / G;
+    double acc = 0.0;
+    if (y < P.L)
+        for (int32_t k = P.attr_ptr[a] + r; k < P.attr_ptr[a + 1]; k += rows)
+            acc += P.item_marg[static_cast<int64_t>(P.attr_items[k]) * P.L + y];
+    sh[threadIdx.x] = acc;
+    __syncthreads();
+    for (int h = kTrainGenThreads / 2; h >= G; h >>= 1) {
+        if (static_cast<int>(threadIdx.x) < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (static_cast<int>(threadIdx.x) < P.L) P.out[1 + P.L * P.L + static_cast<int64_t>(a) * P.L + threadIdx.x] = sh[threadIdx.x];
+}
+
+// Block sums, stage 1: slab b = the window kernel's blocks [b * chunk, (b + 1) * chunk), chunk = ceil(n_blocks / slabs);
+// a thread owns columns of the (f, xi) block and adds the slab's blocks in order.
+__global__ void __launch_bounds__(kTrainGenThreads) gen_reduce_blocks(GenProb P) {
+    const int cols = 1 + P.L * P.L;
+    const int32_t chunk = (P.n_blocks + kTrainGenReduceSlabs - 1) / kTrainGenReduceSlabs;
+    const int32_t lo = static_cast<int32_t>(blockIdx.x) * chunk, hi = min(P.n_blocks, lo + chunk);
+    for (int e = threadIdx.x; e < cols; e += kTrainGenThreads) {
+        double acc = 0.0;
+        for (int32_t b = lo; b < hi; ++b) acc += P.partial[static_cast<int64_t>(b) * cols + e];
+        P.slab[blockIdx.x * cols + e] = acc;
+    }
+}
+
+// Stage 2: the slabs in order.
+__global__ void __launch_bounds__(kTrainGenThreads) gen_reduce_final(GenProb P) {
+    const int cols = 1 + P.L * P.L;
+    for (int e = threadIdx.x; e < cols; e += kTrainGenThreads) {
+        double acc = 0.0;
+        for (int b = 0; b < kTrainGenReduceSlabs; ++b) acc += P.slab[b * cols + e];
+        P.out[e] = acc;
+    }
+}
+
+template <class T>
+int dev_upload(T **d, const std::vector<T> &h, const char *what) {
+    int rc = check_hip(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(h.size(), 1) * sizeof(T)), what);
+    if (rc) return rc;
+    if (h.empty()) return GECCO_CRF_OK;
+    return check_hip(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), what);
+}
+
+int fail(const std::string &msg) {
+    set_error(msg);
+    return GECCO_CRF_EINVAL;
+}
+
+template <class T>
+void append(std::vector<T> &dst, const std::vector<T> &src) {
+    dst.insert(dst.end(), src.begin(), src.end());
+}
+
+int64_t blocks_of(int64_t n, int per) { return (n + per - 1) / per; }
+
+int group_of(int L) {
+    int G = 2;
+    while (G < L) G *= 2;
+    return G;
+}
+
+}  // namespace
+
+// Problems resident on one device: every problem's arrays concatenated into one device array per kind, and one work
+// space with every problem's scratch (so that the active problems of an evaluation run back to back on the stream).
+struct TrainerGeneral {
+    int device = 0;
+    struct Prob {
+        int32_t A, n_items, K, L, W, step, n_blocks;
+        int64_t n_win;
+        int64_t item0, iptr0, nnz0, win0, aptr0;  // the problem's slices of the set arrays
+        int64_t in0, out0, sc0, scratch;          // weights in the upload, outputs in the download, scratch (doubles)
+        std::vector<int32_t> state_fid, trans_fid;
+        std::vector<double> empirical;
+    };
+    std::vector<Prob> probs;
+    std::vector<double> h_in, h_out;
+    hipStream_t stream = nullptr;
+    int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr;
+    int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr, *d_attr_ptr = nullptr, *d_attr_items = nullptr;
+    double *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+
+    ~TrainerGeneral() {
+        if (!stream) return;  // refused before the device was checked: nothing to free, and no HIP call
+        int prev = -1;
+        const bool restore = hipGetDevice(&prev) == hipSuccess && prev != device;
+        (void)hipSetDevice(device);
+        for (void *p : {(void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start, (void *)d_iw_first,
+                        (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items, (void *)d_in,
+                        (void *)d_out, (void *)d_scratch})
+            if (p) (void)hipFree(p);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (restore && prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                           const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                           const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                           const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                           TrainerGeneral **out) {
+    auto t = std::make_unique<TrainerGeneral>();
+    t->device = device;
+    std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c, attr_items_c;
+    int64_t in_total = 0, out_total = 0, scratch_total = 0;
+    for (int32_t k = 0; k < n_problems; ++k) {
+        HostProblem hp;
+        int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
+                               window[k], step[k], state_fid[k], trans_fid[k], num_features[k], kTrainGenMaxL, &hp);
+        if (rc) {
+            set_error("trainer general: problem " + std::to_string(k) + ": " + last_error());
+            return rc;
+        }
+        TrainerGeneral::Prob p;
+        p.A = hp.A, p.n_items = hp.n_items, p.K = hp.K, p.L = num_labels[k], p.W = window[k], p.step = step[k];
+        p.n_win = hp.n_win;
+        const int64_t nb = blocks_of(hp.n_win, kTrainGenWindowsPerBlock), cols = 1 + int64_t(p.L) * p.L;
+        if (nb > INT32_MAX || blocks_of(int64_t(p.n_items) * p.L, kTrainGenThreads) > INT32_MAX)
+            return fail("trainer general: problem " + std::to_string(k) + ": more than 2^31 workgroups in one launch");
+        p.n_blocks = int32_t(nb);
+        p.item0 = int64_t(label_c.size());
+        p.iptr0 = int64_t(item_ptr_c.size());
+        p.nnz0 = int64_t(attr_id_c.size());
+        p.win0 = int64_t(win_start_c.size());
+        p.aptr0 = int64_t(attr_ptr_c.size());
+        p.in0 = in_total, p.out0 = out_total, p.sc0 = scratch_total;
+        // scratch: item scores and item marginals [n_items][L], node marginals [n_win][W][L], blocks and slabs of (f, xi)
+        p.scratch = 2 * int64_t(p.n_items) * p.L + hp.n_win * p.W * p.L + (nb + kTrainGenReduceSlabs) * cols;
+        in_total += int64_t(p.A) * p.L + int64_t(p.L) * p.L;
+        out_total += cols + int64_t(p.A) * p.L;
+        scratch_total += p.scratch;
+        append(item_ptr_c, hp.item_ptr);
+        append(attr_id_c, hp.attr_id);
+        append(label_c, hp.label);
+        append(win_start_c, hp.win_start);
+        append(iw_first_c, hp.iw_first);
+        append(iw_cnt_c, hp.iw_cnt);
+        append(iw_off_c, hp.iw_off);
+        append(attr_ptr_c, hp.attr_ptr);
+        append(attr_items_c, hp.attr_items);
+        p.state_fid = std::move(hp.state_fid);
+        p.trans_fid = std::move(hp.trans_fid);
+        p.empirical = std::move(hp.empirical);
+        t->probs.push_back(std::move(p));
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        set_error("no HIP device available (this library has no CPU fallback)");
+        return GECCO_CRF_ENODEV;
+    }
+    if (device < 0 || device >= ndev) {
+        set_error("device index out of range");
+        return GECCO_CRF_ENODEV;
+    }
+    t->h_in.assign(size_t(in_total), 0.0);
+    t->h_out.assign(size_t(out_total), 0.0);
+    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    if (rc) return rc;
+    if ((rc = check_hip(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+    if ((rc = dev_upload(&t->d_item_ptr, item_ptr_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_attr_id, attr_id_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_label, label_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_win_start, win_start_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_iw_first, iw_first_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_iw_cnt, iw_cnt_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_iw_off, iw_off_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_attr_ptr, attr_ptr_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_attr_items, attr_items_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_in, t->h_in, "trainer alloc"))) return rc;
+    if ((rc = dev_upload(&t->d_out, t->h_out, "trainer alloc"))) return rc;
+    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&t->d_scratch), std::max<size_t>(size_t(scratch_total), 1) * sizeof(double)),
+                        "trainer alloc")))
+        return rc;
+    *out = t.release();
+    return GECCO_CRF_OK;
+}
+
+int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
+    if (!t || !active || !w || !f || !g) return fail("trainer_general_eval: null argument");
+    const int32_t P = int32_t(t->probs.size());
+    for (int32_t k = 0; k < P; ++k)
+        if (active[k] && (!g[k] || (t->probs[k].K > 0 && !w[k])))
+            return fail("trainer_general_eval: null argument for problem " + std::to_string(k));
+    int64_t in_lo = INT64_MAX, in_hi = 0, out_lo = INT64_MAX, out_hi = 0;
+    for (int32_t k = 0; k < P; ++k) {
+        const TrainerGeneral::Prob &p = t->probs[k];
+        if (!active[k] || p.n_win == 0) continue;
+        double *ws = t->h_in.data() + p.in0, *tr = ws + p.state_fid.size();
+        for (size_t j = 0; j < p.state_fid.size(); ++j) ws[j] = p.state_fid[j] >= 0 ? w[k][p.state_fid[j]] : 0.0;
+        for (size_t j = 0; j < p.trans_fid.size(); ++j) tr[j] = p.trans_fid[j] >= 0 ? w[k][p.trans_fid[j]] : 0.0;
+        const int64_t cols = 1 + int64_t(p.L) * p.L;
+        in_lo = std::min(in_lo, p.in0);
+        in_hi = std::max(in_hi, p.in0 + int64_t(p.state_fid.size() + p.trans_fid.size()));
+        out_lo = std::min(out_lo, p.out0);
+        out_hi = std::max(out_hi, p.out0 + cols + int64_t(p.A) * p.L);
+    }
+    int rc = check_hip(hipSetDevice(t->device), "hipSetDevice");
+    if (rc) return rc;
+    hipStream_t st = t->stream;
+    if (in_hi > 0) {
+        if ((rc = check_hip(hipMemcpyAsync(t->d_in + in_lo, t->h_in.data() + in_lo, size_t(in_hi - in_lo) * sizeof(double),
+                                           hipMemcpyHostToDevice, st),
+                            "trainer weights upload")))
+            return rc;
+        for (int32_t k = 0; k < P; ++k) {
+            const TrainerGeneral::Prob &p = t->probs[k];
+            if (!active[k] || p.n_win == 0) continue;
+            const int64_t cols = 1 + int64_t(p.L) * p.L, nl = int64_t(p.n_items) * p.L;
+            GenProb a;
+            a.item_ptr = t->d_item_ptr + p.iptr0;
+            a.attr_id = t->d_attr_id + p.nnz0;
+            a.label = t->d_label + p.item0;
+            a.win_start = t->d_win_start + p.win0;
+            a.iw_first = t->d_iw_first + p.item0;
+            a.iw_cnt = t->d_iw_cnt + p.item0;
+            a.iw_off = t->d_iw_off + p.item0;
+            a.attr_ptr = t->d_attr_ptr + p.aptr0;
+            a.attr_items = t->d_attr_items + p.nnz0;
+            a.wstate = t->d_in + p.in0;
+            a.trans = a.wstate + int64_t(p.A) * p.L;
+            a.score = t->d_scratch + p.sc0;
+            a.item_marg = a.score + nl;
+            a.marg = a.item_marg + nl;
+            a.partial = a.marg + p.n_win * p.W * p.L;
+            a.slab = a.partial + int64_t(p.n_blocks) * cols;
+            a.out = t->d_out + p.out0;
+            a.n_win = p.n_win;
+            a.n_items = p.n_items, a.A = p.A, a.L = p.L, a.W = p.W, a.step = p.step, a.n_blocks = p.n_blocks;
+            const unsigned nb_items = unsigned(blocks_of(nl, kTrainGenThreads));
+            const int G = group_of(p.L);
+            gen_item_scores<<<nb_items, kTrainGenThreads, 0, st>>>(a);
+            switch (G) {
+                case 2: gen_windows<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                case 4: gen_windows<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                case 8: gen_windows<8><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                case 16: gen_windows<16><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                default: gen_windows<32><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+            }
+            gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
+            gen_attr_counts<<<unsigned(p.A), kTrainGenThreads, 0, st>>>(a, G);
+            gen_reduce_blocks<<<kTrainGenReduceSlabs, kTrainGenThreads, 0, st>>>(a);
+            gen_reduce_final<<<1, kTrainGenThreads, 0, st>>>(a);
+        }
+        if ((rc = check_hip(hipGetLastError(), "trainer kernels"))) return rc;
+        if ((rc = check_hip(hipMemcpyAsync(t->h_out.data() + out_lo, t->d_out + out_lo, size_t(out_hi - out_lo) * sizeof(double),
+                                           hipMemcpyDeviceToHost, st),
+                            "trainer download")))
+            return rc;
+        if ((rc = check_hip(hipStreamSynchronize(st), "trainer synchronize"))) return rc;
+    }
+    for (int32_t k = 0; k < P; ++k) {
+        if (!active[k]) continue;
+        const TrainerGeneral::Prob &p = t->probs[k];
+        double *gk = g[k];
+        if (p.n_win == 0) {  // no windows: nothing ran
+            f[k] = 0.0;
+            for (int32_t j = 0; j < p.K; ++j) gk[j] = 0.0;
+            continue;
+        }
+        const double *o = t->h_out.data() + p.out0;  // f, xi [L][L], expected state counts [A][L]
+        const double *expected = o + 1 + p.trans_fid.size();
+        f[k] = o[0];
+        for (int32_t j = 0; j < p.K; ++j) gk[j] = -p.empirical[j];
+        for (size_t j = 0; j < p.state_fid.size(); ++j)
+            if (p.state_fid[j] >= 0) gk[p.state_fid[j]] += expected[j];
+        for (size_t j = 0; j < p.trans_fid.size(); ++j)
+            if (p.trans_fid[j] >= 0) gk[p.trans_fid[j]] += o[1 + j];
+    }
+    return GECCO_CRF_OK;
+}
+
+int32_t trainer_general_num_problems(const TrainerGeneral *t) { return t ? int32_t(t->probs.size()) : -1; }
+
+int64_t trainer_general_num_windows(const TrainerGeneral *t, int32_t k) {
+    return (t && k >= 0 && k < int32_t(t->probs.size())) ? t->probs[k].n_win : -1;
+}
+
+int64_t trainer_general_scratch_bytes(const TrainerGeneral *t, int32_t k) {
+    if (!t || k < -1 || k >= int32_t(t->probs.size())) return -1;
+    if (k >= 0) return t->probs[k].scratch * int64_t(sizeof(double));
+    int64_t total = 0;
+    for (const TrainerGeneral::Prob &p : t->probs) total += p.scratch;
+    return total * int64_t(sizeof(double));
+}
+
+void trainer_general_destroy(TrainerGeneral *t) { delete t; }
+
+}  // namespace gecco

@@ -1,0 +1,147 @@
+"""A linear-chain CRF over sequences of items with string attributes and 2 to 32 string labels, trained and applied on
+the device: the shape of ``sklearn_crfsuite.CRF`` over this package's training stack (``train``) and inference entry
+points (``_native.Model``).  Training instances are the sliding windows of every sequence, as everywhere in GECCO.
+"""
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import train
+
+__all__ = ["SequenceCRF"]
+
+
+def _items(xseq: Iterable[Iterable[str]]) -> List[List[str]]:
+    """The attribute names of every item, duplicates collapsed (the first occurrence is kept)."""
+    out = []
+    for item in xseq:
+        if isinstance(item, str):
+            raise ValueError("an item is an iterable of attribute names, not a string")
+        out.append(list(dict.fromkeys(str(name) for name in item)))
+    return out
+
+
+class SequenceCRF:
+    """``SequenceCRF(window_size=5, window_step=1, device=0, **options)``: ``options`` are the trainer's
+    (``train.trainer_params``: ``c1``, ``c2``, ``min_freq``, ``all_possible_states``, ``all_possible_transitions`` and the
+    libLBFGS parameters).
+
+    After ``fit(X, y)``: ``classes_`` (labels in order of first appearance), ``attributes_`` (the attributes the model
+    keeps), ``state_features_`` ``{(attribute, label): weight}``, ``transition_features_`` ``{(from, to): weight}`` (the
+    non-zero weights, unrounded) and ``training_result_`` (``train.OptimizeResult``)."""
+
+    def __init__(self, window_size: int = 5, window_step: int = 1, device: int = 0, **options):
+        window_size, window_step = int(window_size), int(window_step)
+        if not 1 <= window_size <= 32:
+            raise ValueError(f"window_size must lie in 1..32, got {window_size}")
+        if not 1 <= window_step <= window_size:
+            raise ValueError("Window step must be strictly positive and under `window_size`")
+        self.window_size, self.window_step, self.device = window_size, window_step, int(device)
+        self.params = train.trainer_params(options)
+        self.training_result_: Optional[train.OptimizeResult] = None
+        self._blob: Optional[bytes] = None
+        self._model = None
+
+    # ---- training
+    def fit(self, X: Sequence[Iterable[Iterable[str]]], y: Sequence[Sequence[str]]) -> "SequenceCRF":
+        seqs = [_items(xseq) for xseq in X]
+        labs = [[str(lab) for lab in yseq] for yseq in y]
+        if len(seqs) != len(labs):
+            raise ValueError(f"X holds {len(seqs)} sequences and y {len(labs)}")
+        for k, (items, ls) in enumerate(zip(seqs, labs)):
+            if len(items) != len(ls):
+                raise ValueError(f"sequence {k}: {len(items)} items but {len(ls)} labels")
+            if len(items) < self.window_size:
+                raise ValueError(f"sequence {k} has {len(items)} items, fewer than the window of {self.window_size}")
+        p = self.params
+        ts = train.build_training_set(seqs, labs, self.window_size, self.window_step, min_freq=p["min_freq"],
+                                      all_possible_states=p["all_possible_states"],
+                                      all_possible_transitions=p["all_possible_transitions"], max_labels=train.MAX_LABELS)
+        self.training_result_ = train.fit_training_set(ts, p, device=self.device)
+        self._set_blob(train.model_blob(ts, self.training_result_.x))
+        return self
+
+    # ---- the model file
+    def _set_blob(self, blob: bytes) -> None:
+        from . import _native
+
+        self._blob = bytes(blob)
+        self._model = m = _native.Model.from_lcrf(self._blob)
+        self.classes_: List[str] = m.labels()
+        self.attributes_: List[str] = m.attrs()
+        self._attr_index = {a: i for i, a in enumerate(self.attributes_)}
+        sw, sp = m.state_weights()
+        tw, tp = m.trans_weights()
+        self.state_features_: Dict[Tuple[str, str], float] = {
+            (self.attributes_[a], self.classes_[l]): float(sw[a, l]) for a, l in zip(*(i.tolist() for i in np.nonzero(sp)))}
+        self.transition_features_: Dict[Tuple[str, str], float] = {
+            (self.classes_[i], self.classes_[j]): float(tw[i, j]) for i, j in zip(*(i.tolist() for i in np.nonzero(tp)))}
+
+    def _fitted(self):
+        if self._model is None:
+            raise ValueError("this SequenceCRF is not fitted: call fit, from_bytes or load first")
+        return self._model
+
+    def to_bytes(self) -> bytes:
+        """The CRFsuite model file."""
+        self._fitted()
+        return self._blob
+
+    def save(self, path) -> None:
+        with open(path, "wb") as fh:
+            fh.write(self.to_bytes())
+
+    @classmethod
+    def from_bytes(cls, blob: bytes, window_size: int = 5, window_step: int = 1, device: int = 0, **options) -> "SequenceCRF":
+        crf = cls(window_size, window_step, device, **options)
+        crf._set_blob(blob)
+        return crf
+
+    @classmethod
+    def load(cls, path, window_size: int = 5, window_step: int = 1, device: int = 0, **options) -> "SequenceCRF":
+        with open(path, "rb") as fh:
+            return cls.from_bytes(fh.read(), window_size, window_step, device, **options)
+
+    # ---- prediction
+    def _pack(self, X) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """X as CSR over the model's attribute ids; names the model does not know are dropped."""
+        self._fitted()
+        seq_ptr, item_ptr, attr = [0], [0], []
+        for xseq in X:
+            for names in _items(xseq):
+                attr.extend(self._attr_index[nm] for nm in names if nm in self._attr_index)
+                item_ptr.append(len(attr))
+            seq_ptr.append(len(item_ptr) - 1)
+        return (np.array(seq_ptr, dtype=np.int32), np.array(item_ptr, dtype=np.int32), np.array(attr, dtype=np.int32))
+
+    @staticmethod
+    def _split(values: np.ndarray, seq_ptr: np.ndarray) -> list:
+        return [values[a:b] for a, b in zip(seq_ptr[:-1].tolist(), seq_ptr[1:].tolist())]
+
+    def predict(self, X) -> List[List[str]]:
+        """Viterbi labels of every sequence."""
+        seq_ptr, item_ptr, attr = self._pack(X)
+        if seq_ptr[-1] == 0:
+            return [[] for _ in X]
+        y, _ = self._model.viterbi(seq_ptr, item_ptr, attr, device=self.device)
+        return [[self.classes_[k] for k in ys.tolist()] for ys in self._split(y, seq_ptr)]
+
+    def predict_marginals(self, X) -> List[np.ndarray]:
+        """Whole-sequence marginals: one ``[n_items, L]`` array per sequence, columns in ``classes_`` order."""
+        seq_ptr, item_ptr, attr = self._pack(X)
+        if seq_ptr[-1] == 0:
+            return [np.zeros((0, len(self.classes_))) for _ in X]
+        marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device)
+        return self._split(marg, seq_ptr)
+
+    def predict_windowed(self, X, label: str, pad: bool = True) -> List[np.ndarray]:
+        """GECCO's windowed probability of ``label``: per item the maximum, over the windows covering it, of the
+        label's marginal inside the window (``pad``: a sequence shorter than the window is one window)."""
+        seq_ptr, item_ptr, attr = self._pack(X)
+        if str(label) not in self.classes_:
+            raise ValueError(f"unknown label {label!r} (classes_: {self.classes_})")
+        if seq_ptr[-1] == 0:
+            return [np.zeros(0) for _ in X]
+        p = self._model.windowed_marginals(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
+                                           label=self.classes_.index(str(label)), pad=pad, device=self.device)
+        return self._split(p, seq_ptr)

@@ -1,6 +1,7 @@
 """Host side of CRF training (``ClusterCRF.fit``): the training set, CRFsuite's feature generation, and the L-BFGS /
 OWL-QN optimiser.  The objective and its gradient are evaluated on the device (``_native.Trainer``,
-``csrc/crf_train.hip``); everything here is cheap bookkeeping around that.
+``csrc/crf_train.hip``; sets of 3 to 32 labels: ``_native.TrainerGeneral``, ``csrc/crf_train_general.hip``);
+everything here is cheap bookkeeping around that.
 
 What is reproduced ([EXT] CRFsuite 0.12 ``crf1d`` + ``train_lbfgs`` with libLBFGS, as sklearn-crfsuite drives it):
 
@@ -24,9 +25,11 @@ from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-__all__ = ["TRAINER_DEFAULTS", "trainer_params", "minimize", "minimize_steps", "OptimizeResult", "TrainingSet",
+__all__ = ["TRAINER_DEFAULTS", "MAX_LABELS", "trainer_params", "minimize", "minimize_steps", "OptimizeResult", "TrainingSet",
            "build_training_set", "fit_training_set", "fit_training_sets", "fit_grid", "model_blob"]
 
+#: the most labels a training set may have (``_native.TrainerGeneral``; the inference kernels' limit)
+MAX_LABELS = 32
 #: libLBFGS parameters as CRFsuite's ``train_lbfgs`` sets them (``max_iterations`` None = unbounded)
 TRAINER_DEFAULTS = {"num_memories": 6, "epsilon": 1e-5, "period": 10, "delta": 1e-5, "max_iterations": None}
 #: options of ``sklearn_crfsuite.CRF`` accepted without effect on the fit
@@ -234,6 +237,10 @@ class TrainingSet:
     def num_features(self) -> int:
         return len(self.state_attr) + len(self.trans_src)
 
+    @property
+    def num_labels(self) -> int:
+        return len(self.labels_)
+
     def native_args(self) -> tuple:
         """The set as ``_native.TrainerGrid`` takes it (``TrainerBatch``: without the last two, window and step)."""
         return (self.seq_ptr, self.item_ptr, self.attr_id, self.labels, len(self.attrs_), self.state_fid, self.trans_fid,
@@ -262,10 +269,12 @@ def _pair_coverage(n: int, window: int, step: int) -> np.ndarray:
 
 def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_labels: Sequence[Sequence[str]],
                        window: int, step: int, min_freq: float = 0.0, all_possible_states: bool = False,
-                       all_possible_transitions: bool = False) -> TrainingSet:
+                       all_possible_transitions: bool = False, max_labels: int = 2) -> TrainingSet:
     """Encode sequences (per item the attribute names, per item a label) and generate CRFsuite's features over the
     sliding-window instances.  Every sequence must hold at least `window` items.  Raises ``ValueError`` unless exactly
-    two labels occur."""
+    two labels occur, or, with ``max_labels`` = m in 2..32, unless 2 to m labels occur."""
+    if not 2 <= int(max_labels) <= MAX_LABELS:
+        raise ValueError(f"max_labels must lie in 2..{MAX_LABELS}, got {max_labels}")
     label_index: Dict[str, int] = {}
     attr_index: Dict[str, int] = {}
     covs = []
@@ -281,10 +290,12 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
                     attr_index[name] = len(attr_index)
             if lab not in label_index:
                 label_index[lab] = len(label_index)
-    if len(label_index) != 2:
+    if max_labels == 2 and len(label_index) != 2:
         raise ValueError(f"training needs exactly 2 labels, found {len(label_index)} ({sorted(label_index)}): "
                          "GECCO's protein and domain modes are binary")
-    L, A = 2, len(attr_index)
+    if not 2 <= len(label_index) <= max_labels:
+        raise ValueError(f"training needs 2 to {max_labels} labels, found {len(label_index)} ({sorted(label_index)})")
+    L, A = len(label_index), len(attr_index)
     seq_ptr = [0]
     item_ptr = [0]
     attr_id: List[int] = []
@@ -339,12 +350,59 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
 
 def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0,
                      callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> OptimizeResult:
-    """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0."""
+    """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0.  A set of two labels
+    takes the 2-label trainer, one of more labels ``_native.TrainerGeneral``."""
     from . import _native
 
     args = ts.native_args()
-    trainer = _native.Trainer(*args[:5], *args[8:], *args[5:8], device=device)  # (it takes window and step in the middle)
+    if ts.num_labels == 2:
+        trainer = _native.Trainer(*args[:5], *args[8:], *args[5:8], device=device)  # (window and step in the middle)
+    else:
+        trainer = _native.TrainerGeneral([args], device=device)
     return _fit_lockstep(trainer, [ts], [params], callback)[0]
+
+
+def _general_scratch_bytes(ts: TrainingSet) -> int:
+    """The scratch ``_native.TrainerGeneral`` allocates for ``ts`` (``scratch_bytes(k)``; the formula of DESIGN.md §4.9b:
+    item scores and marginals, node marginals, and one (f, xi) block per 128 windows plus 32 slabs)."""
+    L, W = ts.num_labels, ts.window
+    n = np.diff(np.asarray(ts.seq_ptr, dtype=np.int64))
+    windows = int(np.sum((n[n >= W] - W) // ts.step + 1))
+    return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L))
+
+
+def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], List[OptimizeResult]],
+                    params: Callable[[int], Dict[str, object]], device: int,
+                    scratch_budget_bytes: Optional[int] = None) -> List[OptimizeResult]:
+    """Results of fits whose sets may mix label counts: ``fit_two(indices)`` fits those of two labels as before, the
+    others run in ``_native.TrainerGeneral``; fit k trains ``sets[k]`` with ``params(k)``.  Without a budget the
+    many-label fits share one trainer; with one they run, in their order, in groups whose scratch fits the budget (a
+    group holds at least one fit), one trainer after another, so that only one group is resident at a time.  A fit's
+    result does not depend on its group: problem k of a trainer has the bits of a lone trainer of it."""
+    from . import _native
+
+    results: List[Optional[OptimizeResult]] = [None] * len(sets)
+    two = [k for k, ts in enumerate(sets) if ts.num_labels == 2]
+    more = [k for k, ts in enumerate(sets) if ts.num_labels != 2]
+    if two:
+        for k, r in zip(two, fit_two(two)):
+            results[k] = r
+    budget = scratch_budget_bytes if scratch_budget_bytes and scratch_budget_bytes > 0 else None  # as TrainerGrid: 0 = none
+    groups: List[List[int]] = []
+    used = 0
+    for k in more:
+        need = _general_scratch_bytes(sets[k]) if budget is not None else 0
+        if not groups or (budget is not None and used + need > budget):
+            groups.append([])
+            used = 0
+        groups[-1].append(k)
+        used += need
+    for group in groups:
+        general = _native.TrainerGeneral([sets[k].native_args() for k in group], device=device)
+        for k, r in zip(group, _fit_lockstep(general, [sets[k] for k in group], [params(k) for k in group])):
+            results[k] = r
+        del general  # frees the group's device memory before the next group is created
+    return results
 
 
 def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], device: int = 0) -> List[OptimizeResult]:
@@ -352,7 +410,8 @@ def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], de
     and one optimiser per set runs in lock-step, each round evaluating the pending points of the unfinished sets in one
     batched pass.  Sets drop out as they stop.  Result k is exactly ``fit_training_set(sets[k], params, device)``:
     the batched objective gives every set the bits a lone trainer gives it, and the optimiser loop is the same one.
-    The sets must share ``window`` and ``step``."""
+    The sets must share ``window`` and ``step``.  Sets of more than two labels run in a ``_native.TrainerGeneral`` of
+    their own, beside the batch of the 2-label sets."""
     from . import _native
 
     if not sets:
@@ -360,8 +419,12 @@ def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], de
     window, step = sets[0].window, sets[0].step
     if any(ts.window != window or ts.step != step for ts in sets):
         raise ValueError("fit_training_sets: every training set must have the same window and step")
-    batch = _native.TrainerBatch([ts.native_args()[:-2] for ts in sets], window, step, device=device)
-    return _fit_lockstep(batch, sets, [params] * len(sets))
+
+    def fit_two(idx):
+        batch = _native.TrainerBatch([sets[k].native_args()[:-2] for k in idx], window, step, device=device)
+        return _fit_lockstep(batch, [sets[k] for k in idx], [params] * len(idx))
+
+    return _by_label_count(sets, fit_two, lambda k: params, device)
 
 
 #: default cap of ``fit_grid``'s work space: the scratch of one group of problems evaluated together
@@ -374,7 +437,9 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
     once, with its own window and step (``_native.TrainerGrid``); one optimiser per problem, with that problem's
     ``c1`` / ``c2`` and libLBFGS parameters, runs in lock-step, each round evaluating the pending points of the unfinished
     problems in one batched pass (in groups whose scratch fits ``scratch_budget_bytes``).  Result k is exactly
-    ``fit_training_set(sets[set_k], params_k, device)``."""
+    ``fit_training_set(sets[set_k], params_k, device)``.  Problems on sets of more than two labels run in
+    ``_native.TrainerGeneral`` (one copy of the set per problem), also in groups whose scratch fits the budget, one
+    group resident at a time."""
     from . import _native
 
     if not problems:
@@ -382,9 +447,15 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
     for k, (s, _) in enumerate(problems):
         if not 0 <= int(s) < len(sets):
             raise ValueError(f"fit_grid: problem {k} names set {s}, but there are {len(sets)} sets")
-    grid = _native.TrainerGrid([ts.native_args() for ts in sets], [int(s) for s, _ in problems], scratch_budget_bytes,
-                               device=device)
-    return _fit_lockstep(grid, [sets[int(s)] for s, _ in problems], [p for _, p in problems])
+
+    def fit_two(idx):
+        used = [s for s, ts in enumerate(sets) if ts.num_labels == 2]
+        grid = _native.TrainerGrid([sets[s].native_args() for s in used], [used.index(int(problems[k][0])) for k in idx],
+                                   scratch_budget_bytes, device=device)
+        return _fit_lockstep(grid, [sets[int(problems[k][0])] for k in idx], [problems[k][1] for k in idx])
+
+    return _by_label_count([sets[int(s)] for s, _ in problems], fit_two, lambda k: problems[k][1], device,
+                           scratch_budget_bytes)
 
 
 def _fit_lockstep(trainer, sets: Sequence[TrainingSet], params: Sequence[Dict[str, object]],

@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.9.0 = 290). */
+/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -496,6 +496,37 @@ int32_t gecco_crf_trainer_grid_num_problems(const gecco_crf_trainer_grid *t);
 int64_t gecco_crf_trainer_grid_num_windows(const gecco_crf_trainer_grid *t, int32_t k);
 int64_t gecco_crf_trainer_grid_scratch_bytes(const gecco_crf_trainer_grid *t, int32_t k);
 void gecco_crf_trainer_grid_free(gecco_crf_trainer_grid *t);
+
+/* ---- training with 2 to 32 labels (ABI 2.10.0) -------------------------------------------------------------------
+ * The same objective for any CRFsuite-style tagging task of 2 to 32 labels: n_problems independent problems resident on
+ * one device, problem k with its own label count num_labels[k], window[k] and step[k]; the other arguments are
+ * gecco_crf_trainer_batch_create's, with labels[k] in [0, num_labels[k]), state_fid[k] of num_attrs[k] * L and
+ * trans_fid[k] of L * L entries (L = num_labels[k]).  The lone trainer's checks apply to every problem ("trainer
+ * general: problem k: ..." in the message); num_labels outside 2..32 and windows outside 1..32 are
+ * GECCO_CRF_EUNSUPPORTED.  The 2-label families above are unchanged and keep their own kernels; at num_labels = 2 this
+ * family agrees with them to rounding, not to the bit.
+ * eval: as gecco_crf_trainer_batch_eval (inactive entries neither read nor written; a problem without windows gives
+ * f = 0, g = 0).  One upload, six launches per active problem, one download; synchronous.
+ * Method: log-space forward-backward throughout (no scaled path, so no range conditions): correct for any finite weights;
+ * non-finite weights give a non-finite f.  No float atomics: every sum has one fixed order that depends on neither the
+ * device nor the other problems, so f[k] and g[k] are bitwise what a trainer built from problem k alone returns for
+ * w[k], whichever problems are active, and two evaluations give the same bits.
+ * Memory: per problem, item scores and item marginals [items][L], node marginals [windows][W][L] and one (1 + L * L)
+ * block per 128 windows (the pairwise expectations are summed inside the workgroup; no L * L block per window);
+ * scratch_bytes(t, k) gives it, k = -1 the sum that is allocated.
+ * num_windows(t, k): the windows of problem k (-1 for a bad k); num_problems: n_problems. */
+typedef struct gecco_crf_trainer_general gecco_crf_trainer_general;
+int gecco_crf_trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                                     const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                                     const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window,
+                                     const int32_t *step, const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                     const int32_t *num_features, gecco_crf_trainer_general **out);
+int gecco_crf_trainer_general_eval(gecco_crf_trainer_general *t, const uint8_t *active, const double *const *w, double *f,
+                                   double *const *g);
+int32_t gecco_crf_trainer_general_num_problems(const gecco_crf_trainer_general *t);
+int64_t gecco_crf_trainer_general_num_windows(const gecco_crf_trainer_general *t, int32_t k);
+int64_t gecco_crf_trainer_general_scratch_bytes(const gecco_crf_trainer_general *t, int32_t k);
+void gecco_crf_trainer_general_free(gecco_crf_trainer_general *t);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
