@@ -45,6 +45,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
          ctypes.c_int32, _c_f64p],
     ),
+    "gecco_crf_windowed_marginals_all": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_marginals_full": (ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_f64p]),
     "gecco_crf_viterbi": (ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_i8p, _c_f64p]),
     "gecco_crf_segment": (
@@ -69,6 +74,11 @@ SIGNATURES = {
     "gecco_crf_plan_tile_out": (ctypes.c_int32, [_vp]),
     "gecco_crf_plan_kernel_name": (ctypes.c_char_p, [_vp]),
     "gecco_crf_plan_run_windowed": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp]),
+    "gecco_crf_plan_run_windowed_all": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    "gecco_crf_plan_all_kernel_name": (ctypes.c_char_p, [_vp]),
+    "gecco_crf_plan_time_windowed_all": (
+        ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]
+    ),
     "gecco_crf_plan_run_decode": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "gecco_crf_plan_run_decode_pipelined": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "gecco_crf_plan_run_marginals_full": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
@@ -461,6 +471,24 @@ class Model:
             )
         )
         return out[:n]
+
+    def windowed_marginals_all(self, contig_ptr, gene_ptr, attr_id, window, step=1, background=None, pad=True, device=0):
+        """Every label's windowed probability in one device pass: ``(p_all [n, L], p_any [n] or None)``; ``p_any`` is the
+        windowed probability of any label but ``background`` (a label id)."""
+        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
+        n, L = (int(contig_ptr[-1]) if len(contig_ptr) else 0), self.num_labels
+        p_all = np.zeros((max(n, 1), L), dtype=np.float64)
+        p_any = None if background is None else np.zeros(max(n, 1), dtype=np.float64)
+        if attr_id.size == 0:
+            attr_id = np.zeros(1, dtype=np.int32)
+        _check(
+            self._lib.gecco_crf_windowed_marginals_all(
+                self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
+                _ptr(attr_id, _c_i32p), int(window), int(step), -1 if background is None else int(background), int(bool(pad)),
+                _ptr(p_all, _c_f64p), None if p_any is None else _ptr(p_any, _c_f64p),
+            )
+        )
+        return p_all[:n], (None if p_any is None else p_any[:n])
 
     def marginals_full(self, contig_ptr, gene_ptr, attr_id, device=0):
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
@@ -1099,6 +1127,24 @@ class Plan:
 
     def run_windowed(self, d_gene_ptr: int, d_attr_id: int, d_p_out: int, label=1, stream: int = 0):
         _check(self._lib.gecco_crf_plan_run_windowed(self._h, d_gene_ptr, d_attr_id, int(label), d_p_out, stream or None))
+
+    @property
+    def all_kernel_name(self) -> str:
+        """The kernel `run_windowed_all` dispatches to."""
+        return self._lib.gecco_crf_plan_all_kernel_name(self._h).decode()
+
+    def run_windowed_all(self, d_gene_ptr: int, d_attr_id: int, d_p_all: int, d_p_any: int = 0, background=None, stream: int = 0):
+        """Every label's windowed probability into ``d_p_all [n, L]``; with ``background`` also ``d_p_any [n]``."""
+        _check(self._lib.gecco_crf_plan_run_windowed_all(self._h, d_gene_ptr, d_attr_id, -1 if background is None else int(background),
+                                                         d_p_all, d_p_any or None, stream or None))
+
+    def time_windowed_all(self, d_gene_ptr: int, d_attr_id: int, d_p_all: int, d_p_any: int = 0, background=None, stream: int = 0,
+                          warmup=2, iters=10) -> float:
+        ms = ctypes.c_float(0)
+        _check(self._lib.gecco_crf_plan_time_windowed_all(self._h, d_gene_ptr, d_attr_id, -1 if background is None else int(background),
+                                                          d_p_all, d_p_any or None, stream or None, int(warmup), int(iters),
+                                                          ctypes.byref(ms)))
+        return ms.value
 
     def run_decode(self, d_gene_ptr: int, d_attr_id: int, d_p_out: int, d_y: int, label: int = 1, d_score: int = 0, stream: int = 0):
         """Windowed marginals + Viterbi labels in one pass over the CSR (shared state scores)."""

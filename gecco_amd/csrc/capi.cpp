@@ -96,7 +96,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 300; }
+GECCO_API int gecco_crf_version(void) { return 310; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -222,6 +222,16 @@ GECCO_API int gecco_crf_plan_run_windowed(gecco_crf_plan *p, const int32_t *d_ge
     GECCO_GUARD_END
 }
 
+GECCO_API int gecco_crf_plan_run_windowed_all(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
+                                              int32_t background, double *d_p_all, double *d_p_any, void *stream) {
+    if (!p) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    return plan_run_windowed_all(p->p, d_gene_ptr, d_attr_id, background, d_p_all, d_p_any, static_cast<hipStream_t>(stream));
+    GECCO_GUARD_END
+}
+GECCO_API const char *gecco_crf_plan_all_kernel_name(const gecco_crf_plan *p) { return p ? plan_all_kernel_name(p->p) : ""; }
+
 // `call` repeated on stream `s`: `warmup` times untimed, then `iters` times between two events
 template <class Call>
 static int time_calls(hipStream_t s, int32_t warmup, int32_t iters, float *ms_per_launch, Call call) {
@@ -251,6 +261,18 @@ GECCO_API int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_g
     GECCO_GUARD_BEGIN
     hipStream_t s = static_cast<hipStream_t>(stream);
     return time_calls(s, warmup, iters, ms_per_launch, [&] { return plan_run_windowed(p->p, d_gene_ptr, d_attr_id, label, d_p_out, s); });
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_plan_time_windowed_all(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
+                                               int32_t background, double *d_p_all, double *d_p_any, void *stream,
+                                               int32_t warmup, int32_t iters, float *ms_per_launch) {
+    if (!p || !ms_per_launch || iters <= 0) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    return time_calls(s, warmup, iters, ms_per_launch,
+                      [&] { return plan_run_windowed_all(p->p, d_gene_ptr, d_attr_id, background, d_p_all, d_p_any, s); });
     GECCO_GUARD_END
 }
 
@@ -600,6 +622,75 @@ GECCO_API int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t dev
     r.pad = pad;
     r.p_out = p_out;
     return session_run(*s, r);
+    GECCO_GUARD_END
+}
+
+// One device, one plan over the whole batch: the arrays go to device memory, the plan runs, the results come back.
+GECCO_API int gecco_crf_windowed_marginals_all(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                               int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                               int32_t window, int32_t step, int32_t background, int32_t pad, double *p_all,
+                                               double *p_any) {
+    if (!m) return GECCO_CRF_EINVAL;
+    // argument errors first, so that they surface even on a box without a GPU
+    if (window <= 0) {
+        set_error("Window size must be strictly positive");
+        return GECCO_CRF_EINVAL;
+    }
+    if (step <= 0 || step > window) {
+        set_error("Window step must be strictly positive and under `window_size`");
+        return GECCO_CRF_EINVAL;
+    }
+    if (background < -1 || background >= m->m.L) {
+        set_error("background label out of range");
+        return GECCO_CRF_EINVAL;
+    }
+    if ((background < 0) != (p_any == nullptr)) {
+        set_error(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
+        return GECCO_CRF_EINVAL;
+    }
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    int rc = check_device(device);
+    if (rc) return rc;
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) {
+        set_error("bad contig_ptr");
+        return GECCO_CRF_EINVAL;
+    }
+    const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
+    if (n > 0 && (!p_all || !gene_ptr)) {
+        set_error("null buffer");
+        return GECCO_CRF_EINVAL;
+    }
+    Plan plan;
+    if ((rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, plan))) return rc;
+    if (plan.n_genes == 0) return GECCO_CRF_OK;
+    const int32_t *gp = gene_ptr + contig_ptr[0];
+    const int64_t a0 = gp[0], nnz = int64_t(gp[n]) - a0;
+    if (nnz < 0 || (nnz > 0 && !attr_id)) {
+        set_error("bad gene_ptr");
+        return GECCO_CRF_EINVAL;
+    }
+    const size_t L = size_t(m->m.L), b_gp = size_t(n + 1) * 4, b_at = size_t(nnz ? nnz : 1) * 4, b_all = size_t(n) * L * 8,
+                 b_any = size_t(n) * 8;
+    Carver blk;
+    const size_t o_gp = blk.take(b_gp), o_at = blk.take(b_at), o_all = blk.take(b_all), o_any = blk.take(b_any);
+    char *d = nullptr;
+    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&d), blk.off), "hipMalloc batch"))) return rc;
+    // (gene_ptr may carry any base offset: the kernels index attr_id with its values, so the attribute array goes up from
+    // that base and the row pointers are rebased on the host)
+    std::vector<int32_t> rows(size_t(n) + 1);
+    for (int64_t i = 0; i <= n; ++i) rows[size_t(i)] = int32_t(gp[i] - a0);
+    rc = check_hip(hipMemcpy(d + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
+    if (!rc && nnz) rc = check_hip(hipMemcpy(d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
+    if (!rc)
+        rc = plan_run_windowed_all(plan, reinterpret_cast<int32_t *>(d + o_gp), reinterpret_cast<int32_t *>(d + o_at), background,
+                                   reinterpret_cast<double *>(d + o_all), p_any ? reinterpret_cast<double *>(d + o_any) : nullptr,
+                                   nullptr);
+    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "windowed marginals");
+    if (!rc) rc = check_hip(hipMemcpy(p_all, d + o_all, b_all, hipMemcpyDeviceToHost), "download p_all");
+    if (!rc && p_any) rc = check_hip(hipMemcpy(p_any, d + o_any, b_any, hipMemcpyDeviceToHost), "download p_any");
+    (void)hipFree(d);
+    return rc;
     GECCO_GUARD_END
 }
 

@@ -310,6 +310,7 @@ struct GenArgs {
 hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_windowed(const GenArgs &a, hipStream_t stream);   // p_out must be zeroed first
 // 3 or 4 labels: one lane per window start (the two-label kernel's design); tile geometry gen_small_tile_out(W)
+constexpr int kGenTileThreads = 256;  // window starts per workgroup of every kernel with that geometry (gen_small_tile_out)
 bool gen_small_ok(int L, int W, const double *trans_host);
 int gen_small_tile_out(int W);
 hipError_t launch_gen_windowed_small(const GenArgs &a, const double *trans_host, const int4 *d_tile_desc, int ntiles,
@@ -320,6 +321,27 @@ hipError_t launch_gen_viterbi(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_viterbi_wave(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_marginals_wave(const GenArgs &a, hipStream_t stream);  // row F likewise (a.E, a.smax, a.alpha, a.scale)
 int gen_chunk_genes();
+
+// ---- every label's windowed marginal in one pass (crf_windowed_all.hip) ------------------------
+// p_all[g][l] = max over the windows covering g of P_w(y_g = l); p_any[g] = max over the same windows of the sum of
+// P_w(y_g = l) over l != background (label-index order, unclipped).  E: gl_state's exp(state - max state).
+struct AllArgs {
+    const double *E;          // [n*L]
+    const double *exp_trans;  // [L*L] exp(trans) (lane-group tier)
+    const int32_t *c_slot, *c_gene, *c_n;
+    const uint64_t *start_bits;
+    double *p_all;            // [n*L]
+    double *p_any;            // [n] or null (background < 0)
+    int32_t L, K, S, W, background;
+};
+// one group of lanes per window start, any L and W <= kGenMaxW: integer atomic maxima, p_all / p_any zeroed first
+hipError_t launch_all_windowed_groups(const AllArgs &a, hipStream_t stream);
+// one lane per window start, 2 to 8 labels under gen_small_ok: tiles of gen_small_tile_out(W) slots, every output stored once
+bool all_small_ok(int L, int W, const double *trans_host);
+hipError_t launch_all_windowed_small(const AllArgs &a, const double *trans_host, const int4 *d_tile_desc, int ntiles,
+                                     hipStream_t stream);
+// NaN ("no prediction") in every column and in p_any for the gene ranges of skipped contigs
+hipError_t launch_all_fill_nan(double *p_all, double *p_any, int L, const int2 *ranges, int n_ranges, hipStream_t stream);
 
 // weighted domain composition of called clusters (crf_composition.hip); d_tmp: one double per domain row
 hipError_t launch_composition(const int32_t *d_seg, int n_seg, const int32_t *d_dom_ptr, const int32_t *d_dom_col,

@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(kGT) gl_windowed(GenArgs a) {
 //     one lane up per step, hand-over between waves through LDS): no atomics, p_out written once.
 //   * a workgroup of 256 window starts owns 256 - (W - 1) output slots; the emissions of its 256 + (W - 1) slots are
 //     staged in LDS once (regular tiles: slots map to genes by a constant shift; others look every slot up).
-constexpr int kSmallNT = 256;
+constexpr int kSmallNT = kGenTileThreads;
 __device__ __forceinline__ double gl_wave_shr1_zero(double v) {  // lane l <- lane l-1, lane 0 <- +0.0
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __builtin_amdgcn_update_dpp(0, lo, 0x138, 0xF, 0xF, true);
@@ -297,7 +297,7 @@ __global__ void __launch_bounds__(kSmallNT) gl_windowed_small(GenArgs a, SmallTr
 //   * a workgroup = 256 window starts (4 waves x 4 batches of 16) owning 256 - (W - 1) output slots, emissions staged once
 //     in LDS, one row per label with a stride that keeps the 16 x 4 lanes of a read on distinct banks.
 typedef double gl_v4d __attribute__((ext_vector_type(4)));
-constexpr int kMfmaNT = 256;
+constexpr int kMfmaNT = kGenTileThreads;
 __host__ __device__ constexpr int gl_mfma_stride(int wmax) { return ((kMfmaNT + wmax - 1 + 15) / 32) * 32 + 16; }  // = 16 mod 32, >= slots
 template <int TILES, int NS, int WMAX>
 __global__ void __launch_bounds__(kMfmaNT) gl_windowed_mfma(GenArgs a, double tmax, const int4 *__restrict__ tile_desc) {

@@ -185,6 +185,7 @@ Plan::~Plan() {
             (void)hipFree(gen_tab[0].d);
             (void)hipFree(gen_tab[1].d);
             (void)hipFree(d_seg_ws);
+            (void)hipFree(d_all_tiles);
             if (side_stream) (void)hipStreamDestroy(side_stream);
             if (ev_fork) (void)hipEventDestroy(ev_fork);
             if (ev_join) (void)hipEventDestroy(ev_join);
@@ -256,6 +257,29 @@ int grow_ws(T *&ptr, size_t &cap, size_t bytes, const char *what) {
 }
 }  // namespace
 
+// The tile table of a window kernel whose workgroups own `tile_out` output slots each: per tile the contigs in reach and
+// whether its slots map to genes by a constant shift.  irr_prefix[k + 1] - irr_prefix[k] = 1 where contig k is padded or a
+// skipped contig lies between it and contig k + 1.
+static void fill_tile_desc(const Plan &p, const std::vector<int32_t> &irr_prefix, int32_t tile_out, int32_t ntiles, int4 *out) {
+    const int32_t W = p.W;
+    // contigs in reach of a workgroup: both ends of the reach only move forward from tile to tile
+    int first = 0, last = 0;
+    for (int32_t b = 0; b < ntiles; ++b) {
+        const int64_t q0 = int64_t(b) * tile_out - (W - 1);
+        const int64_t q_lo = std::max<int64_t>(q0, 0);
+        const int64_t q_hi = std::min<int64_t>(q0 + tile_out + 2 * (W - 1) - 1, p.S - 1);
+        while (first + 1 < p.K && p.c_slot[first + 1] <= q_lo) ++first;  // largest k with c_slot[k] <= q_lo
+        if (last < first) last = first;
+        while (last + 1 < p.K && p.c_slot[last + 1] <= q_hi) ++last;
+        // regular: no padded contig in reach and no skipped contig between the contigs in reach
+        // (a gap after the last contig is harmless)
+        const bool padded_or_gap =
+            (irr_prefix[last] - irr_prefix[first]) != 0 || (p.c_slot[last + 1] - p.c_slot[last] != p.c_n[last]);
+        const int shift = p.c_gene[first] - p.c_slot[first];
+        out[b] = make_int4(shift, first, last, padded_or_gap ? 0 : 1);
+    }
+}
+
 int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_contigs, int32_t W, int32_t step,
                int32_t pad, Plan &p, hipStream_t upload_stream, bool sync) {
     // same checks, same order as gecco/_meta.py:127-130
@@ -276,6 +300,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
         return GECCO_CRF_EINVAL;
     }
     p.gen_small = false;
+    p.all_ntiles = -1;
     p.gen_tab[0].chunk = p.gen_tab[1].chunk = 0;  // (chunk tables of the previous contigs)
     p.gen_wave_tmax = p.gen_wave_tmax_f = INT32_MIN;
     p.pipe = Plan::Pipe{};  // (score differences and CSR pointers of the previous layout)
@@ -417,24 +442,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     }
     p.ntiles = p.S > 0 ? (p.S + p.tile_out - 1) / p.tile_out : 0;
     p.tile_desc.resize(p.ntiles);
-    {
-        // contigs in reach of a workgroup: both ends of the reach only move forward from tile to tile
-        int first = 0, last = 0;
-        for (int32_t b = 0; b < p.ntiles; ++b) {
-            const int64_t q0 = int64_t(b) * p.tile_out - (W - 1);
-            const int64_t q_lo = std::max<int64_t>(q0, 0);
-            const int64_t q_hi = std::min<int64_t>(q0 + p.tile_out + 2 * (W - 1) - 1, p.S - 1);
-            while (first + 1 < p.K && p.c_slot[first + 1] <= q_lo) ++first;  // largest k with c_slot[k] <= q_lo
-            if (last < first) last = first;
-            while (last + 1 < p.K && p.c_slot[last + 1] <= q_hi) ++last;
-            // regular: no padded contig in reach and no skipped contig between the contigs in reach
-            // (a gap after the last contig is harmless)
-            const bool padded_or_gap =
-                (irr_prefix[last] - irr_prefix[first]) != 0 || (p.c_slot[last + 1] - p.c_slot[last] != p.c_n[last]);
-            const int shift = p.c_gene[first] - p.c_slot[first];
-            p.tile_desc[b] = make_int4(shift, first, last, padded_or_gap ? 0 : 1);
-        }
-    }
+    fill_tile_desc(p, irr_prefix, p.tile_out, p.ntiles, p.tile_desc.data());
     if (device < 0) return GECCO_CRF_OK;
 
     int rc = check_hip(hipSetDevice(device), "hipSetDevice");
@@ -910,6 +918,102 @@ static int run_windowed_impl(Plan &p, const int32_t *d_gene_ptr, const int32_t *
         return check_hip(launch_decode_pipelined(a, *piped->seq, stream), "pipelined decode launch");
     }
     return check_hip(launch_windowed(a, stream), "windowed launch");
+}
+
+// ---- every label's windowed marginals (crf_windowed_all.hip) --------------------------------
+namespace {
+// the lane-per-window tier serves this plan (GECCO_CRF_GENERAL_GROUPS=1: the lane-group tier, as for the single-label kernels)
+bool all_small_tier(const Plan &p) {
+    return all_small_ok(p.model->L, p.W, p.model->trans.data()) && !std::getenv("GECCO_CRF_GENERAL_GROUPS");
+}
+// The tile table of the lane-per-window tier: the plan's own when it was laid out for the same geometry (gen_small), else
+// built here by plan_build's own routine (fill_tile_desc).
+int all_tiles(Plan &p, const int4 **d_tiles, int32_t *ntiles) {
+    const int32_t tile_out = gen_small_tile_out(p.W);
+    if (p.gen_small && p.tile_out == tile_out) {
+        *d_tiles = p.d_tile_desc;
+        *ntiles = p.ntiles;
+        return GECCO_CRF_OK;
+    }
+    std::lock_guard<std::mutex> lock(p.ws_mutex);
+    if (p.all_ntiles < 0) {
+        const int32_t nt = p.S > 0 ? (p.S + tile_out - 1) / tile_out : 0;
+        // (the plan's own irr_prefix is scratch that the whole-contig tables reuse: derived again from the layout)
+        std::vector<int32_t> irr(size_t(p.K) + 1, 0);
+        for (int32_t k = 0; k < p.K; ++k) {
+            const bool padded = p.c_slot[k + 1] - p.c_slot[k] != p.c_n[k];
+            const bool gap_after = k + 1 < p.K && p.c_gene[k + 1] != p.c_gene[k] + p.c_n[k];
+            irr[size_t(k) + 1] = irr[size_t(k)] + ((padded || gap_after) ? 1 : 0);
+        }
+        std::vector<int4> td(size_t(nt) + 1);
+        fill_tile_desc(p, irr, tile_out, nt, td.data());
+        int rc = grow_ws(p.d_all_tiles, p.all_tiles_cap, td.size() * sizeof(int4), "hipMalloc tile table");
+        if (rc) return rc;
+        if ((rc = check_hip(hipMemcpy(p.d_all_tiles, td.data(), td.size() * sizeof(int4), hipMemcpyHostToDevice), "upload tile table")))
+            return rc;
+        p.all_ntiles = nt;
+    }
+    *d_tiles = p.d_all_tiles;
+    *ntiles = p.all_ntiles;
+    return GECCO_CRF_OK;
+}
+}  // namespace
+
+const char *plan_all_kernel_name(const Plan &p) { return p.model && all_small_tier(p) ? "gl_all_small" : "gl_all_groups"; }
+
+int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t background, double *d_p_all,
+                          double *d_p_any, hipStream_t stream) {
+    int rc = check_plan(p, 0);
+    if (rc) return rc;
+    if (background < -1 || background >= p.model->L) {
+        set_error("background label out of range");
+        return GECCO_CRF_EINVAL;
+    }
+    if ((background < 0) != (d_p_any == nullptr)) {
+        set_error(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
+        return GECCO_CRF_EINVAL;
+    }
+    if (ends_here(p.n_genes == 0, !d_gene_ptr || !d_p_all, rc)) return rc;
+    if ((rc = use_device(p.device))) return rc;
+    const bool small = all_small_tier(p);
+    if (!small && p.W > kGenMaxW) {
+        set_error("window too long for the any-L kernel (alpha of a whole window is LDS-resident: W <= 48)");
+        return GECCO_CRF_EUNSUPPORTED;
+    }
+    GenArgs g;
+    if ((rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g))) return rc;
+    g.state = nullptr;  // marginals only need exp(state - max)
+    if ((rc = check_hip(launch_gen_state(g, stream), "state score launch"))) return rc;
+    AllArgs a{};
+    a.E = g.E;
+    a.exp_trans = g.exp_trans;
+    a.c_slot = p.d_c_slot;
+    a.c_gene = p.d_c_gene;
+    a.c_n = p.d_c_n;
+    a.start_bits = p.d_start_bits;
+    a.p_all = d_p_all;
+    a.p_any = d_p_any;
+    a.L = p.model->L;
+    a.K = p.K;
+    a.S = p.S;
+    a.W = p.W;
+    a.background = background;
+    // the lane-group tier takes maxima in place: +0.0 everywhere first; then "no prediction" for the genes of skipped contigs,
+    // which lie outside slot space and are written by neither tier
+    if (!small) {
+        if ((rc = check_hip(hipMemsetAsync(d_p_all, 0, size_t(p.n_genes) * size_t(a.L) * 8, stream), "memset p"))) return rc;
+        if (d_p_any && (rc = check_hip(hipMemsetAsync(d_p_any, 0, size_t(p.n_genes) * 8, stream), "memset p"))) return rc;
+    }
+    if (!p.skipped.empty() &&
+        (rc = check_hip(launch_all_fill_nan(d_p_all, d_p_any, a.L, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch")))
+        return rc;
+    if (small) {
+        const int4 *d_tiles = nullptr;
+        int32_t ntiles = 0;
+        if ((rc = all_tiles(p, &d_tiles, &ntiles))) return rc;
+        return check_hip(launch_all_windowed_small(a, p.model->trans.data(), d_tiles, ntiles, stream), "windowed launch");
+    }
+    return check_hip(launch_all_windowed_groups(a, stream), "windowed launch");
 }
 
 // ---- whole-contig scans (rows F, V) ------------------------------------------------------

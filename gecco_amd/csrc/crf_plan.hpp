@@ -139,6 +139,11 @@ struct Plan {
     bool reference_now = false;  // (this layout runs in reference-bits mode: reference_bits, or the environment)
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
+    // every label's windowed marginals (crf_windowed_all.hip): the tile table of the lane-per-window tier when the plan's own
+    // table has another geometry (2-label plans), built on first use
+    int4 *d_all_tiles = nullptr;
+    size_t all_tiles_cap = 0;
+    int32_t all_ntiles = -1;  // (-1: not built for this layout)
     std::mutex ws_mutex;  // guards the lazy workspace / table creation: launches of one plan may come from several threads
     ~Plan();
 };
@@ -157,6 +162,11 @@ int plan_run_segment(Plan &p, const double *d_p, const uint8_t *d_annotated, con
                      int32_t gather_cap = 0);
 int plan_run_windowed(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
                       hipStream_t stream);
+// every label's windowed marginal in one pass: d_p_all [n_genes][L]; d_p_any [n_genes] = the windowed probability of any label
+// but `background`, or null with background == -1 (crf_windowed_all.hip)
+int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t background, double *d_p_all,
+                          double *d_p_any, hipStream_t stream);
+const char *plan_all_kernel_name(const Plan &p);
 // windowed marginals + whole-contig Viterbi of the same batch in one pass over the CSR
 // Decode pipelined over batches: enqueue the windowed marginals of `cur`'s batch (cur may be null: flush) and the Viterbi
 // labels of the batch the previous call scored on `prev` (null on the first call; may be the same plan) -- in ONE launch

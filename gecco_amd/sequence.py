@@ -145,3 +145,22 @@ class SequenceCRF:
         p = self._model.windowed_marginals(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
                                            label=self.classes_.index(str(label)), pad=pad, device=self.device)
         return self._split(p, seq_ptr)
+
+    def predict_windowed_all(self, X, background: Optional[str] = None, pad: bool = True):
+        """GECCO's windowed probability of every label in one device pass: one ``[n_items, L]`` array per sequence, columns
+        in ``classes_`` order (per item and label the maximum, over the windows covering the item, of the label's marginal
+        inside the window).  With ``background`` also, second, one ``[n_items]`` array per sequence: the maximum over the
+        same windows of the probability of any label but ``background``."""
+        seq_ptr, item_ptr, attr = self._pack(X)
+        L = len(self.classes_)
+        if background is not None and str(background) not in self.classes_:
+            raise ValueError(f"unknown label {background!r} (classes_: {self.classes_})")
+        if seq_ptr[-1] == 0:
+            empty = [np.zeros((0, L)) for _ in X]
+            return empty if background is None else (empty, [np.zeros(0) for _ in X])
+        bg = None if background is None else self.classes_.index(str(background))
+        p_all, p_any = self._model.windowed_marginals_all(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
+                                                          background=bg, pad=pad, device=self.device)
+        if background is None:
+            return self._split(p_all, seq_ptr)
+        return self._split(p_all, seq_ptr), self._split(p_any, seq_ptr)

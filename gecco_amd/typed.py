@@ -1,0 +1,429 @@
+"""A type-aware cluster CRF: a gene is labelled ``0`` or with the type of the cluster it lies in.
+
+``TypedClusterCRF`` trains a many-label CRF on GECCO's tables (``train.build_training_set`` with up to 32 labels,
+``train.fit_training_set``), scores genes with ONE device pass that gives every label's windowed probability and the
+probability of lying in any cluster (``_native.Model.windowed_marginals_all``, ``csrc/crf_windowed_all.hip``), calls
+clusters on the latter with the segment kernel, and gives every call a type and per-type probabilities from the former:
+the ``type`` and ``*_probability`` columns of ``clusters.tsv``, which the random forest fills otherwise.
+
+Labels.  A gene outside every cluster is ``"0"`` (the background).  A gene inside a cluster carries the ``";"``-joined
+sorted type names of that cluster, ``"Unknown"`` when it has none.  A gene overlaps a cluster as ``train_cli`` decides it
+for the 2-label model (``join_clusters``: same sequence, bounds inclusive; ``assigned_clusters``: rows without a
+cluster id are skipped, a repeated id is an error); of several clusters the first in ``cluster_id`` order gives the label.  More than 31 cluster labels do not fit the trainer's 32: the
+composite labels (those with a ``";"``) with the fewest clusters are folded into one label ``"Mixed"``, fewest first,
+ties by name, until 31 remain.
+
+Type of a call.  For a type t and a gene g, v[g] = the sum over the labels whose names contain t, in label order, of the
+label's windowed probability; the cluster's probability of t is ``min(1, exact mean of v over its genes)``; its type is
+the set of t with a probability above 0.5 (the rule of ``TypeClassifier.predict_types``), ``Unknown`` when empty.
+``"Mixed"`` and ``"Unknown"`` contain no type.
+
+Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
+``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
+"""
+import argparse
+import gc
+import hashlib
+import itertools
+import json
+import operator
+import os
+import random
+import sys
+import warnings
+from typing import Any, Dict, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import tables
+
+__all__ = ["BACKGROUND", "MIXED", "UNKNOWN", "MAX_CLUSTER_LABELS", "TypedClusterCRF", "cluster_labels", "fold_labels",
+           "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "build_parser", "main"]
+
+BACKGROUND = "0"
+MIXED = "Mixed"
+UNKNOWN = "Unknown"
+MAX_CLUSTER_LABELS = 31  # the trainer's 32 labels less the background
+
+MODEL_FILE = "typed_model.crfsuite"
+META_FILE = "typed_model.json"
+
+
+# ---------------------------------------------------------------------------------------------- labels
+def cluster_labels(clusters: tables.ClusterTable) -> List[str]:
+    """The label of every clusters-table row: its sorted type names joined with ``";"``, ``"Unknown"`` without any."""
+    from .train_cli import type_names
+
+    return [";".join(type_names(cell)) or UNKNOWN for cell in clusters.type]
+
+
+def fold_labels(counts: Dict[str, int], limit: int = MAX_CLUSTER_LABELS) -> Dict[str, str]:
+    """``counts``: clusters per cluster label.  Returns label -> label after folding: while more than ``limit`` labels
+    remain, the composite label with the fewest clusters (ties by name) becomes ``"Mixed"``.  Warns with what was folded;
+    a set that still does not fit raises ``ValueError``."""
+    names = set(counts)
+    folded: List[str] = []
+
+    def remaining() -> int:
+        return len(names) - len(folded) + (1 if folded and MIXED not in names else 0)
+
+    for label in sorted((lab for lab in names if ";" in lab), key=lambda lab: (counts[lab], lab)):
+        if remaining() <= limit:
+            break
+        folded.append(label)
+    if remaining() > limit:
+        raise ValueError(f"{remaining()} cluster labels do not fit the trainer's {limit} (after folding {len(folded)} "
+                         f"composite labels into {MIXED!r})")
+    if folded:
+        warnings.warn(f"more than {limit} cluster labels: folded into {MIXED!r}: " + ", ".join(folded), UserWarning)
+    gone = set(folded)
+    return {label: (MIXED if label in gone else label) for label in names}
+
+
+def gene_labels(n_genes: int, clusters: tables.ClusterTable, join: Any, limit: int = MAX_CLUSTER_LABELS) -> List[str]:
+    """The label of every gene from the overlap join (``train_cli.ClusterJoin``) of the genes with ``clusters``.  The
+    clusters are ``train_cli.assigned_clusters``': those with at least one gene, in sorted ``cluster_id`` order; a row with
+    an empty id labels no gene, and a repeated id is a ``ValueError``."""
+    from .train_cli import assigned_clusters
+
+    row_label = cluster_labels(clusters)
+    rows = [i for _, i, _ in assigned_clusters(clusters, join)]
+    counts: Dict[str, int] = {}
+    for i in rows:
+        counts[row_label[i]] = counts.get(row_label[i], 0) + 1
+    folded = fold_labels(counts, limit)
+    labels = [BACKGROUND] * n_genes
+    for i in rows:
+        label = folded[row_label[i]]
+        for g in np.asarray(join.members(i)).tolist():
+            if labels[g] == BACKGROUND:
+                labels[g] = label
+    return labels
+
+
+def label_type_names(label: str) -> Tuple[str, ...]:
+    """The type names a label contains: none for the background, ``"Mixed"`` and ``"Unknown"``."""
+    if label in (BACKGROUND, MIXED, UNKNOWN):
+        return ()
+    return tuple(label.split(";"))
+
+
+# ---------------------------------------------------------------------------------------------- types of a call
+def type_probabilities(p_all: np.ndarray, label_types: Sequence[Sequence[str]], types: Sequence[str]) -> Dict[str, float]:
+    """``p_all`` [genes of one cluster, L] -> the cluster's probability of every type (module docstring)."""
+    from . import _native
+
+    p_all = np.asarray(p_all, dtype=np.float64)
+    out: Dict[str, float] = {}
+    for t in types:
+        v = np.zeros(p_all.shape[0], dtype=np.float64)
+        for l, names in enumerate(label_types):
+            if t in names:
+                v = v + p_all[:, l]
+        out[t] = min(1.0, _native.exact_mean(v))
+    return out
+
+
+def type_of(probabilities: Dict[str, float]) -> frozenset:
+    """The types with a probability above 0.5."""
+    return frozenset(t for t, p in probabilities.items() if p > 0.5)
+
+
+def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables.ClusterTable:
+    """``ClusterTable.from_clusters`` with one ``{type.lower()}_probability`` column per type between ``type`` and
+    ``proteins``, in ``types.probability_columns`` order."""
+    table = tables.ClusterTable.from_clusters(clusters)
+    extra = []
+    for name in sorted(types, key=str.casefold):
+        col = f"{name.lower()}_probability"
+        table.columns[col] = [float(c.type_probabilities.get(name, float("nan"))) for c in clusters]
+        extra.append((col, float, None))
+    at = [n for n, _, _ in tables.ClusterTable.COLUMNS].index("type") + 1
+    table.COLUMNS = tables.ClusterTable.COLUMNS[:at] + extra + tables.ClusterTable.COLUMNS[at:]
+    return table
+
+
+# ---------------------------------------------------------------------------------------------- the model
+class TypedClusterCRF:
+    """``TypedClusterCRF(window_size=5, window_step=1, device=0, **options)``; ``options`` are the trainer's
+    (``train.trainer_params``: ``c1``, ``c2``, ...).  After ``fit`` or ``trained``: ``classes_`` (labels in id order),
+    ``label_types_`` (per label its type names), ``types_`` (the sorted distinct type names), ``background`` (``"0"``)."""
+
+    feature_type = "protein"
+
+    def __init__(self, window_size: int = 5, window_step: int = 1, device: int = 0, **options: Any) -> None:
+        if options.pop("feature_type", "protein") != "protein":
+            raise ValueError("typed models use protein features")
+        if window_size <= 0:
+            raise ValueError("Window size must be strictly positive")
+        if window_step <= 0 or window_step > window_size:
+            raise ValueError("Window step must be strictly positive and under `window_size`")
+        self.window_size, self.window_step, self.device = int(window_size), int(window_step), int(device)
+        self._options = dict(options)
+        self.background = BACKGROUND
+        self.significance: Optional[Dict[str, float]] = None
+        self.significant_features = None
+        self.training_result_ = None
+        self._blob: Optional[bytes] = None
+        self._model = None
+
+    # ---- training
+    def fit(self, genes: Iterable[Any], clusters: tables.ClusterTable, *, shuffle: bool = True, select: Optional[float] = None,
+            correction_method: Optional[str] = None) -> "TypedClusterCRF":
+        """Label ``genes`` from the ``clusters`` table and fit.  Gene ordering, feature extraction, the warnings and the
+        errors are ``ClusterCRF``'s (``training_instances``), and so is the Fisher selection with ``select``, which sees a
+        gene inside any cluster as positive."""
+        from . import train
+        from .crf import ClusterCRF
+        from .train_cli import join_clusters
+
+        genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
+        join = join_clusters(genes, clusters, device=self.device)
+        labels = gene_labels(len(genes), clusters, join)
+        if BACKGROUND not in labels:
+            raise ValueError("no gene outside every cluster: the background label '0' must be present")
+        helper = ClusterCRF("protein", "lbfgs", self.window_size, self.window_step, **self._options)
+        helper.devices = [self.device]
+        binary = [gene.with_probability(0.0 if label == BACKGROUND else 1.0) for gene, label in zip(genes, labels)]
+        self.significance = self.significant_features = None
+        if select is not None:
+            binary, self.significance, self.significant_features = helper._select_features(binary, select, correction_method)
+        # the instances are the helper's, in its order of sequences; features and labels are then shuffled together, by the
+        # one ``random.shuffle`` over the sequences that ``training_instances`` itself would make
+        feats, binary_labels = helper.training_instances(binary, shuffle=False)
+        order = [[i for i, _ in group] for _, group in
+                 itertools.groupby(enumerate(binary), key=lambda ig: ig[1].source.id)]
+        typed = [[labels[i] for i in seq] for seq in order]
+        if [[lab != BACKGROUND for lab in seq] for seq in typed] != [[lab == "1" for lab in seq] for seq in binary_labels]:
+            raise ValueError("different features and labels found, something is wrong")
+        if shuffle:
+            pairs = list(zip(feats, typed))
+            random.shuffle(pairs)
+            feats, typed = [f for f, _ in pairs], [t for _, t in pairs]
+        params = train.trainer_params(self._options)
+        ts = train.build_training_set(feats, typed, self.window_size, self.window_step, min_freq=float(params["min_freq"]),
+                                      all_possible_states=bool(params["all_possible_states"]),
+                                      all_possible_transitions=bool(params["all_possible_transitions"]),
+                                      max_labels=train.MAX_LABELS)
+        self.training_result_ = train.fit_training_set(ts, params, device=self.device)
+        self._set_blob(train.model_blob(ts, self.training_result_.x))
+        return self
+
+    def _set_blob(self, blob: bytes, types_by_label: Optional[Dict[str, Sequence[str]]] = None) -> None:
+        from . import _native
+
+        self._blob = bytes(blob)
+        self._model = m = _native.Model.from_lcrf(self._blob)
+        self.classes_: List[str] = m.labels()
+        if self.background not in self.classes_:
+            raise ValueError(f"the model has no background label {self.background!r} (labels: {self.classes_})")
+        if types_by_label is not None and set(types_by_label) != set(self.classes_):
+            raise ValueError("the labels of typed_model.json are not the model's")
+        self.label_types_: List[Tuple[str, ...]] = [
+            tuple(types_by_label[label]) if types_by_label is not None else label_type_names(label) for label in self.classes_]
+        self.types_: List[str] = sorted({t for names in self.label_types_ for t in names})
+        self._attr_index = {a: i for i, a in enumerate(m.attrs())}
+
+    def _fitted(self):
+        if self._model is None:
+            raise ValueError("this TypedClusterCRF is not fitted: call fit or trained first")
+        return self._model
+
+    # ---- the model directory
+    def save(self, model_dir) -> None:
+        """``typed_model.crfsuite`` (the CRFsuite model file) and ``typed_model.json`` (window, step, feature type,
+        background label, every label's type names, the md5 of the model file)."""
+        self._fitted()
+        os.makedirs(model_dir, exist_ok=True)
+        with open(os.path.join(model_dir, MODEL_FILE), "wb") as fh:
+            fh.write(self._blob)
+        meta = {"window_size": self.window_size, "window_step": self.window_step, "feature_type": self.feature_type,
+                "background": self.background,
+                "labels": [{"name": label, "types": list(names)} for label, names in zip(self.classes_, self.label_types_)],
+                "md5": hashlib.md5(self._blob).hexdigest()}
+        with open(os.path.join(model_dir, META_FILE), "w") as fh:
+            json.dump(meta, fh, indent=1)
+            fh.write("\n")
+
+    @classmethod
+    def trained(cls, model_dir, device: int = 0) -> "TypedClusterCRF":
+        """Load a directory written by ``save``; a model file whose md5 is not the recorded one is a ``ValueError``."""
+        with open(os.path.join(model_dir, META_FILE)) as fh:
+            meta = json.load(fh)
+        with open(os.path.join(model_dir, MODEL_FILE), "rb") as fh:
+            blob = fh.read()
+        if hashlib.md5(blob).hexdigest() != meta["md5"]:
+            raise ValueError("MD5 hash of model data does not match signature")
+        if meta.get("feature_type", "protein") != "protein":
+            raise ValueError("typed models use protein features")
+        self = cls(int(meta["window_size"]), int(meta["window_step"]), device)
+        self.background = str(meta["background"])
+        self._set_blob(blob, {entry["name"]: tuple(entry["types"]) for entry in meta["labels"]})
+        return self
+
+    # ---- prediction
+    def _score(self, genes: Iterable[Any], pad: bool):
+        """Genes sorted as ``ClusterCRF.predict_probabilities`` sorts them, their contigs, which contigs are scored, and
+        the device pass: ``p_all`` [n, L] and ``p_any`` [n] (NaN on unscored contigs)."""
+        from . import packing
+
+        model = self._fitted()
+        genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
+        for gene in genes:
+            gene.protein.domains.sort(key=operator.attrgetter("start"))
+        contigs = [list(g) for _, g in itertools.groupby(genes, key=operator.attrgetter("source.id"))]
+        batch = packing.pack_contigs(contigs, self._attr_index, "protein")
+        W = self.window_size
+        scored = np.ones(len(contigs), dtype=bool)
+        for ci in np.flatnonzero(np.diff(batch.item_ptr) < W).tolist():
+            contig = contigs[ci]
+            if pad:
+                unit = "protein" if W - len(contig) == 1 else "proteins"
+                warnings.warn(f"Contig {contig[0].source.id!r} does not contain enough proteins ({len(contig)}) for sliding "
+                              f"window of size {W}, padding with {W - len(contig)} {unit}")
+            else:
+                warnings.warn(f"Contig {contig[0].source.id!r} does not contain enough proteins ({len(contig)}) for sliding "
+                              f"window of size {W}")
+                scored[ci] = False
+        L = len(self.classes_)
+        if not genes:
+            return genes, contigs, scored, batch, np.zeros((0, L)), np.zeros(0)
+        p_all, p_any = model.windowed_marginals_all(batch.item_ptr.astype(np.int32), batch.attr_ptr.astype(np.int32),
+                                                    batch.attr_id, W, self.window_step,
+                                                    background=self.classes_.index(self.background), pad=pad, device=self.device)
+        return genes, contigs, scored, batch, p_all, p_any
+
+    def _annotated(self, contigs, scored, batch, p_any) -> List[Any]:
+        """New genes carrying ``p_any``, through ``ClusterCRF``'s annotate path (no label ``'1'``: no cluster weights);
+        the genes of unscored contigs keep their probabilities."""
+        from .crf import _annotate, _annotate_all
+
+        out: List[Any] = []
+        gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            for ci, contig in enumerate(contigs):
+                if not scored[ci]:
+                    out.extend(_annotate(gene, None, None, {}) for gene in contig)
+                    continue
+                i0 = int(batch.item_ptr[ci])
+                probs = p_any[i0:i0 + len(contig)].tolist()
+                fast = _annotate_all(contig, probs, {})
+                out.extend(fast if fast is not None else [_annotate(gene, p, None, {}) for gene, p in zip(contig, probs)])
+        finally:
+            if gc_was_enabled:
+                gc.enable()
+        return out
+
+    def predict_probabilities(self, genes: Iterable[Any], *, pad: bool = True) -> List[Any]:
+        """New genes, sorted by (sequence, start), carrying as their probability the windowed probability of lying in any
+        cluster: ``ClusterRefiner`` and the table writers work on them unchanged."""
+        _, contigs, scored, batch, _, p_any = self._score(genes, pad)
+        return self._annotated(contigs, scored, batch, p_any)
+
+    def predict_label_probabilities(self, genes: Iterable[Any], *, pad: bool = True) -> np.ndarray:
+        """Every label's windowed probability, ``[n, L]`` in the gene order ``predict_probabilities`` returns, columns in
+        ``classes_`` order."""
+        return self._score(genes, pad)[4]
+
+    def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
+                         trim: bool = True, pad: bool = True) -> List[Any]:
+        """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
+        per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities."""
+        return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
+                                               pad=pad)[1]
+
+    def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
+                                   trim: bool = True, pad: bool = True) -> Tuple[List[Any], List[Any]]:
+        """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass."""
+        from . import _native
+        from .refine import _cluster_class
+        from .types import _cluster_type_factory
+
+        _, contigs, scored, batch, p_all, p_any = self._score(genes, pad)
+        annotated = self._annotated(contigs, scored, batch, p_any)
+        if not annotated:
+            return annotated, []
+        has_domains = np.fromiter((1 if g.protein.domains else 0 for g in annotated), dtype=np.uint8, count=len(annotated))
+        rows = _native.segment(p_any, has_domains, batch.item_ptr.astype(np.int32), threshold=threshold, n_cds=n_cds,
+                               edge_distance=edge_distance, trim=trim, device=self.device, carry_state=False)
+        Cluster = _cluster_class()
+        clusters: List[Any] = []
+        for contig, number, first, last in rows.tolist():
+            members = annotated[first:last]
+            cluster = Cluster(f"{members[0].source.id}_cluster_{number}", list(members))
+            proba = type_probabilities(p_all[first:last], self.label_types_, self.types_)
+            cluster.type_probabilities = proba
+            cluster.type = _cluster_type_factory(cluster)(type_of(proba))
+            clusters.append(cluster)
+        return annotated, clusters
+
+
+# ---------------------------------------------------------------------------------------------- command line
+def build_parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="python -m gecco_amd.typed", description=(
+        "Train a type-aware cluster CRF on labelled tables, or call typed clusters with one."))
+    sub = ap.add_subparsers(dest="command", required=True)
+    tr = sub.add_parser("train", help="tables in, a typed model directory out")
+    tr.add_argument("-f", "--features", required=True, nargs="+", action="extend", help="domain annotation table(s) (TSV)")
+    tr.add_argument("-g", "--genes", required=True, help="gene table (TSV)")
+    tr.add_argument("-c", "--clusters", required=True, help="cluster table (TSV): a gene overlapping a cluster takes its type")
+    tr.add_argument("-e", "--e-filter", type=float, default=None, help="e-value cutoff for protein domains to be included")
+    tr.add_argument("-p", "--p-filter", type=float, default=1e-9, help="p-value cutoff for protein domains to be included")
+    tr.add_argument("--no-shuffle", dest="shuffle", action="store_false", help="do not shuffle the data before fitting")
+    tr.add_argument("--seed", type=int, default=42, help="seed of random and numpy.random")
+    tr.add_argument("-W", "--window-size", type=int, default=5)
+    tr.add_argument("--window-step", type=int, default=1)
+    tr.add_argument("--c1", type=float, default=0.15, help="strength of the L1 regularisation")
+    tr.add_argument("--c2", type=float, default=0.15, help="strength of the L2 regularisation")
+    tr.add_argument("--feature-type", choices=("protein", "domain"), default="protein")
+    tr.add_argument("--select", type=float, default=None, help="fraction of domains kept by Fisher selection")
+    tr.add_argument("--correction", type=str, default=None, help="multiple-testing correction of the selection p-values")
+    tr.add_argument("--device", type=int, default=0)
+    tr.add_argument("-o", "--output-dir", default=".", help="the model directory")
+    pr = sub.add_parser("predict", help="tables in; genes.tsv, features.tsv and clusters.tsv out")
+    pr.add_argument("--model", required=True, help="a directory written by train")
+    pr.add_argument("-f", "--features", required=True, nargs="+", action="extend", help="domain annotation table(s) (TSV)")
+    pr.add_argument("-g", "--genes", required=True, help="gene table (TSV)")
+    pr.add_argument("-e", "--e-filter", type=float, default=None, help="e-value cutoff for protein domains to be included")
+    pr.add_argument("-p", "--p-filter", type=float, default=1e-9, help="p-value cutoff for protein domains to be included")
+    pr.add_argument("-m", "--threshold", type=float, default=0.8, help="probability above which a gene is in a cluster")
+    pr.add_argument("-c", "--cds", type=int, default=3, help="minimum number of annotated genes of a cluster")
+    pr.add_argument("-E", "--edge-distance", type=int, default=0, help="annotated genes separating a cluster from the edge")
+    pr.add_argument("--no-trim", dest="trim", action="store_false", help="keep genes without domains on cluster edges")
+    pr.add_argument("--no-pad", dest="pad", action="store_false", help="skip sequences shorter than the window")
+    pr.add_argument("--device", type=int, default=0)
+    pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
+    return ap
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    from .train_cli import load_training_genes
+
+    args = build_parser().parse_args(argv)
+    if args.command == "train":
+        if args.feature_type != "protein":
+            raise ValueError("typed models use protein features")
+        random.seed(args.seed)
+        np.random.seed(args.seed)
+        genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
+        clusters = tables.ClusterTable.load(args.clusters)
+        crf = TypedClusterCRF(args.window_size, args.window_step, args.device, c1=args.c1, c2=args.c2)
+        crf.fit(genes, clusters, shuffle=args.shuffle, select=args.select, correction_method=args.correction)
+        crf.save(args.output_dir)
+        print(f"train: {len(genes)} genes, {len(clusters)} clusters, labels {crf.classes_} -> {args.output_dir}", file=sys.stderr)
+        return 0
+    crf = TypedClusterCRF.trained(args.model, device=args.device)
+    genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
+    annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
+                                                      edge_distance=args.edge_distance, trim=args.trim, pad=args.pad)
+    os.makedirs(args.output_dir, exist_ok=True)
+    tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
+    tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))
+    typed_cluster_table(found, crf.types_).dump(os.path.join(args.output_dir, "clusters.tsv"))
+    print(f"predict: {len(annotated)} genes, {len(found)} clusters -> {args.output_dir}", file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

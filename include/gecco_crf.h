@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300). */
+/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -88,6 +88,24 @@ int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t device,
                                  const int32_t *gene_ptr, const int32_t *attr_id,
                                  int32_t window, int32_t step, int32_t label, int32_t pad,
                                  double *p_out /* n_genes */);
+/* Row W for EVERY label in one pass (ABI 2.11, additive; crf_windowed_all.hip): the windows, padding, centring and
+ * `step` of gecco_crf_windowed_marginals, one forward-backward per window.
+ *   p_all[g][l] = max over the windows covering gene g of P_w(y_g = l)            (row-major [n_genes][L])
+ *   p_any[g]    = max over the same windows of sum_{l != background} P_w(y_g = l)  (label-index order, not clipped)
+ * p_any is what a caller whose label 'background' means "in no cluster" thresholds: the maximum of a sum is not a sum of
+ * maxima, so it cannot be formed from the columns.  With 2 labels and background 0 it is column 1 bit for bit.
+ * background == -1: no p_any, which must then be NULL; a buffer without a background label, a missing buffer with one,
+ * and background >= L are GECCO_CRF_EINVAL.  Genes of skipped contigs hold NaN and genes no window covers 0.0 in every
+ * column and in p_any, as in the single-label entry.  1 <= L <= 32 labels; windows of up to 48 genes (up to 32 at 2 to 4
+ * labels when the lane-per-window kernel serves the model), GECCO_CRF_EUNSUPPORTED beyond -- the single-label entry's
+ * 2-label kernels have no such limit.
+ * A gene's results depend on its own contig only: the same contig alone or inside any batch gives the same bits.
+ * One device per call (there is no batch-driver form of this entry). */
+int gecco_crf_windowed_marginals_all(const gecco_crf_model *m, int32_t device,
+                                     const int32_t *contig_ptr, int32_t n_contigs,
+                                     const int32_t *gene_ptr, const int32_t *attr_id,
+                                     int32_t window, int32_t step, int32_t background /* label id, or -1 */, int32_t pad,
+                                     double *p_all /* [n_genes][L] */, double *p_any /* [n_genes], NULL iff background == -1 */);
 /* Row F (extension; [EXT] CRF.predict_marginals_single on a whole contig): marginals of
  * every label, marg[n_genes][L]; lognorm[n_contigs] may be NULL. */
 int gecco_crf_marginals_full(const gecco_crf_model *m, int32_t device,
@@ -168,6 +186,12 @@ int32_t gecco_crf_plan_tile_out(const gecco_crf_plan *p);    /* output slots per
 const char *gecco_crf_plan_kernel_name(const gecco_crf_plan *p);
 int gecco_crf_plan_run_windowed(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                 int32_t label, double *d_p_out, void *stream);
+/* gecco_crf_windowed_marginals_all on device buffers: d_p_all [n_genes][L], d_p_any [n_genes] or NULL (background == -1).
+ * gecco_crf_plan_all_kernel_name: the kernel that call dispatches to ("gl_all_small": one lane per window, 2 to 8 labels
+ * inside the range guard; "gl_all_groups": one group of lanes per window, everything else). */
+int gecco_crf_plan_run_windowed_all(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
+                                    int32_t background, double *d_p_all, double *d_p_any, void *stream);
+const char *gecco_crf_plan_all_kernel_name(const gecco_crf_plan *p);
 int gecco_crf_plan_run_marginals_full(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                       double *d_marg, double *d_lognorm, void *stream);
 int gecco_crf_plan_run_viterbi(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
@@ -207,6 +231,10 @@ int gecco_crf_plan_run_segment_ex(gecco_crf_plan *p, const double *d_p, const ui
 int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                  int32_t label, double *d_p_out, void *stream,
                                  int32_t warmup, int32_t iters, float *ms_per_launch);
+/* The same for gecco_crf_plan_run_windowed_all. */
+int gecco_crf_plan_time_windowed_all(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
+                                     int32_t background, double *d_p_all, double *d_p_any, void *stream,
+                                     int32_t warmup, int32_t iters, float *ms_per_launch);
 /* The same for the pipelined decode launch (the plan following itself: window tiles of the batch + Viterbi workgroups of
  * the batch before, one launch per iteration); the interval includes the boundaries between the launches. */
 int gecco_crf_plan_time_decode_pipelined(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
