@@ -211,6 +211,16 @@ SIGNATURES = {
     "gecco_crf_trainer_general_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_general_scratch_bytes": (ctypes.c_int64, [_vp, ctypes.c_int32]),
     "gecco_crf_trainer_general_free": (None, [_vp]),
+    "gecco_crf_trainer_sequences_create": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+         ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)],
+    ),
+    "gecco_crf_trainer_sequences_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
+    "gecco_crf_trainer_sequences_num_problems": (ctypes.c_int32, [_vp]),
+    "gecco_crf_trainer_sequences_num_sequences": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_sequences_scratch_bytes": (ctypes.c_int64, [_vp, ctypes.c_int32]),
+    "gecco_crf_trainer_sequences_free": (None, [_vp]),
     "gecco_crf_fisher_exact": (ctypes.c_int, [ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
     "gecco_crf_cluster_overlaps": (
         ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -1418,6 +1428,38 @@ class TrainerGeneral(_TrainerHandle):
                      c["num_attrs"], c["num_labels"], c["window"], c["step"], t["state_fid"], t["trans_fid"],
                      c["num_features"])
         self.num_features = self._features = counts["num_features"]
+
+    def scratch_bytes(self, k: int = -1) -> int:
+        """Scratch bytes of problem k; for k = -1 the sum over the problems, which is what is allocated."""
+        return int(self._c("scratch_bytes")(self._h, int(k)))
+
+
+class TrainerSequences(_TrainerHandle):
+    """Training sets of CRFs with 2 to 32 labels whose instances are the whole sequences, of any length from one item up
+    (``gecco_crf_trainer_sequences_*``): CRFsuite's own training mode.
+
+    ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)``
+    per problem; the label count of a problem is that of its ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the
+    active problems; problem k's f and g are bitwise what a ``TrainerSequences`` of problem k alone returns for
+    ``ws[k]``."""
+
+    _family = "gecco_crf_trainer_sequences"
+    eval = _TrainerHandle._eval_problems
+
+    def __init__(self, problems, device: int = 0):
+        if any(len(p) != 8 for p in problems):
+            raise ValueError("a whole-sequence problem has 8 entries: no window and no step")
+        arrays, counts = _trainer_sets(problems)
+        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
+        c = {name: _i32_vector(v) for name, v in counts.items()}
+        self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], t["labels"],
+                     c["num_attrs"], c["num_labels"], t["state_fid"], t["trans_fid"], c["num_features"])
+        self.num_features = self._features = counts["num_features"]
+
+    def num_sequences(self, k: int) -> int:
+        return int(self._c("num_sequences")(self._h, int(k)))
+
+    num_windows = num_sequences  # (the instances of problem k)
 
     def scratch_bytes(self, k: int = -1) -> int:
         """Scratch bytes of problem k; for k = -1 the sum over the problems, which is what is allocated."""

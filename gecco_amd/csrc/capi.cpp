@@ -96,7 +96,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 310; }
+GECCO_API int gecco_crf_version(void) { return 320; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -1171,6 +1171,45 @@ GECCO_API void gecco_crf_trainer_general_free(gecco_crf_trainer_general *t) {
     if (!t) return;
     DeviceGuard guard;
     trainer_general_destroy(reinterpret_cast<TrainerGeneral *>(t));
+}
+
+// ---- training on whole sequences (ABI 2.12.0): a TrainerGeneral whose problems have no window ---
+GECCO_API int gecco_crf_trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                 const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                 const int32_t *const *attr_id, const int32_t *const *labels,
+                                                 const int32_t *num_attrs, const int32_t *num_labels,
+                                                 const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                                 const int32_t *num_features, gecco_crf_trainer_sequences **out) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    if (n_problems < 1) return fail("trainer sequences: at least one problem is needed");
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !state_fid || !trans_fid ||
+        !num_features)
+        return fail("trainer sequences: null argument");
+    DeviceGuard guard;
+    TrainerGeneral *t = nullptr;
+    int rc = trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
+                                      state_fid, trans_fid, num_features, &t);
+    *out = reinterpret_cast<gecco_crf_trainer_sequences *>(t);
+    return rc;
+    GECCO_GUARD_END
+}
+GECCO_API int gecco_crf_trainer_sequences_eval(gecco_crf_trainer_sequences *t, const uint8_t *active, const double *const *w,
+                                               double *f, double *const *g) {
+    return gecco_crf_trainer_general_eval(reinterpret_cast<gecco_crf_trainer_general *>(t), active, w, f, g);
+}
+GECCO_API int32_t gecco_crf_trainer_sequences_num_problems(const gecco_crf_trainer_sequences *t) {
+    return trainer_general_num_problems(reinterpret_cast<const TrainerGeneral *>(t));
+}
+GECCO_API int64_t gecco_crf_trainer_sequences_num_sequences(const gecco_crf_trainer_sequences *t, int32_t k) {
+    return trainer_general_num_windows(reinterpret_cast<const TrainerGeneral *>(t), k);  // (the instances of problem k)
+}
+GECCO_API int64_t gecco_crf_trainer_sequences_scratch_bytes(const gecco_crf_trainer_sequences *t, int32_t k) {
+    return trainer_general_scratch_bytes(reinterpret_cast<const TrainerGeneral *>(t), k);
+}
+GECCO_API void gecco_crf_trainer_sequences_free(gecco_crf_trainer_sequences *t) {
+    gecco_crf_trainer_general_free(reinterpret_cast<gecco_crf_trainer_general *>(t));
 }
 
 // ---- feature selection (ABI 2.4.0) ------------------------------------------------------------

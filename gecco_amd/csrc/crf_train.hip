@@ -452,7 +452,7 @@ int fail(const std::string &msg) {
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
-                  HostProblem *hp) {
+                  HostProblem *hp, bool whole_sequences) {
     if (!seq_ptr || n_seqs < 0 || !state_fid || !trans_fid) return fail("trainer: null argument");
     if (max_labels == 2 && num_labels != 2) {
         set_error("trainer: only 2-label models can be trained (GECCO's protein and domain modes are binary)");
@@ -464,15 +464,20 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
         return GECCO_CRF_EUNSUPPORTED;
     }
     const int32_t L = num_labels;
-    if (window < 1 || window > kTrainMaxW) {
-        set_error("trainer: window of " + std::to_string(window) + " items; windows of 1 to 32 items are supported");
-        return GECCO_CRF_EUNSUPPORTED;
+    if (!whole_sequences) {
+        if (window < 1 || window > kTrainMaxW) {
+            set_error("trainer: window of " + std::to_string(window) + " items; windows of 1 to 32 items are supported");
+            return GECCO_CRF_EUNSUPPORTED;
+        }
+        if (step < 1 || step > window) return fail("Window step must be strictly positive and under `window_size`");
     }
-    if (step < 1 || step > window) return fail("Window step must be strictly positive and under `window_size`");
     if (num_attrs < 1 || num_features < 0) return fail("trainer: bad attribute or feature count");
     if (seq_ptr[0] != 0) return fail("trainer: seq_ptr[0] must be 0");
     for (int32_t s = 0; s < n_seqs; ++s) {
-        if (seq_ptr[s + 1] - seq_ptr[s] < window)
+        const int64_t n = int64_t(seq_ptr[s + 1]) - seq_ptr[s];
+        if (whole_sequences && n < 0) return fail("trainer: seq_ptr is not monotone");
+        if (whole_sequences && n == 0) return fail("trainer: sequence " + std::to_string(s) + " has no items");
+        if (!whole_sequences && n < window)
             return fail("trainer: sequence " + std::to_string(s) + " has fewer items than the window");
     }
     const int32_t n_items = seq_ptr[n_seqs];
@@ -503,7 +508,21 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
     iw_first.assign(n_items, 0);
     iw_cnt.assign(n_items, 0);
     iw_off.assign(n_items, 0);
-    for (int32_t s = 0; s < n_seqs; ++s) {
+    if (whole_sequences) {
+        // one instance per sequence, in slot order: longest first, ties by index (the sequence kernel runs neighbours of
+        // this order side by side); every item lies in exactly one instance
+        std::vector<int32_t> order(static_cast<size_t>(n_seqs));
+        for (int32_t s = 0; s < n_seqs; ++s) order[s] = s;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+            return seq_ptr[a + 1] - seq_ptr[a] > seq_ptr[b + 1] - seq_ptr[b];
+        });
+        for (int32_t s : order) {
+            win_start.push_back(seq_ptr[s]);
+            hp->win_len.push_back(seq_ptr[s + 1] - seq_ptr[s]);
+        }
+        iw_cnt.assign(n_items, 1);
+    }
+    for (int32_t s = 0; s < n_seqs && !whole_sequences; ++s) {
         const int32_t base = seq_ptr[s], n = seq_ptr[s + 1] - base;
         const int64_t w0 = int64_t(win_start.size());
         const int32_t nw = (n - window) / step + 1;
@@ -527,8 +546,8 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
             const int32_t fid = hp->state_fid[size_t(attr_id[k]) * L + labels[i]];
             if (fid >= 0) hp->empirical[fid] += iw_cnt[i];
         }
-    for (int32_t i0 : win_start)
-        for (int32_t j = 1; j < window; ++j) {
+    for (size_t q = 0; q < win_start.size(); ++q)
+        for (int32_t i0 = win_start[q], j = 1; j < (whole_sequences ? hp->win_len[q] : window); ++j) {
             const int32_t fid = hp->trans_fid[labels[i0 + j - 1] * L + labels[i0 + j]];
             if (fid >= 0) hp->empirical[fid] += 1.0;
         }

@@ -20,15 +20,18 @@ struct HostProblem {
     std::vector<int32_t> state_fid, trans_fid;  // [A*L], [L*L]: feature id of every dense slot, or -1
     std::vector<double> empirical;              // [K] observed feature counts over all windows
     std::vector<int32_t> item_ptr, attr_id, label, win_start, iw_first, iw_cnt, iw_off, attr_ptr, attr_items;
+    std::vector<int32_t> win_len;  // whole-sequence instances only: the items of instance q (win_start[q] is its first)
 };
 
 // Checks one problem (the lone trainer's checks and messages) and builds its windows, coverage, empirical counts and
 // attribute -> items transpose.  max_labels = 2: the 2-label families (any other num_labels is "only 2-label models");
-// larger: the general family, num_labels in [2, max_labels] and labels in [0, num_labels).
+// larger: the general family, num_labels in [2, max_labels] and labels in [0, num_labels).  whole_sequences: the
+// instances are the sequences themselves (window and step are not read; a sequence without items is refused), listed in
+// win_start / win_len longest first, ties by index; iw_first / iw_off are not built.
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
-                  HostProblem *hp);
+                  HostProblem *hp, bool whole_sequences = false);
 
 // Sets as gecco_crf_trainer_grid_create takes them (one entry per set in the set arrays, each with its own window and
 // step), problem k on set problem_set[k], or on set k where problem_set is NULL (then n_problems == n_sets).
@@ -60,5 +63,14 @@ int32_t trainer_general_num_problems(const TrainerGeneral *t);
 int64_t trainer_general_num_windows(const TrainerGeneral *t, int32_t k);
 int64_t trainer_general_scratch_bytes(const TrainerGeneral *t, int32_t k);  // (k = -1: the sum over the problems)
 void trainer_general_destroy(TrainerGeneral *t);
+
+// The whole-sequence family (gecco_crf_trainer_sequences_*, crf_train_general.hip): the general family's objective with one
+// instance per sequence, of that sequence's length (any length >= 1).  The handle is a TrainerGeneral whose problems have
+// no window: eval, num_problems, scratch_bytes and destroy are the general family's, and num_windows counts the
+// sequences.  Errors carry "trainer sequences: problem k: ".
+int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                             const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                             const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
+                             const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out);
 
 }  // namespace gecco

@@ -15,6 +15,10 @@
 //   4. attr counts     one workgroup per attribute: the item marginals over the attribute -> items transpose
 //   5/6. block sums    fixed-geometry two-stage sum over the workgroups' blocks
 // Log space throughout: right for any finite weights, no second path.  No float atomics: every sum has one fixed order.
+//
+// The whole-sequence family (gecco_crf_trainer_sequences_*) is the same objective with one instance per
+// sequence, of that sequence's own length.  It shares kernels 1, 4, 5 and 6 and replaces 2 and 3 by one kernel,
+// gen_sequences: every item lies in exactly one instance, so that kernel's node marginals are the item marginals.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,12 +45,13 @@ constexpr int kTrainGenMaxL = 32;
 // One problem as its kernels take it (by value).  The set arrays are the problem's own slices.
 struct GenProb {
     const int32_t *item_ptr, *attr_id, *label, *win_start, *iw_first, *iw_cnt, *iw_off, *attr_ptr, *attr_items;
+    const int32_t *win_len;  // whole sequences: the items of instance q, which starts at win_start[q]; else not read
     const double *wstate;  // [A][L] state weights of this evaluation
     const double *trans;   // [L][L] transition weights
     double *score;         // [n_items][L]
     double *item_marg;     // [n_items][L]
     double *marg;          // [n_win][W][L]: log alpha on the way forward, node marginals afterwards
-    double *partial;       // [n_blocks][1 + L*L]: per workgroup of the window kernel, f then xi
+    double *partial;       // [n_blocks][1 + L*L]: per workgroup of the window (or sequence) kernel, f then xi
     double *slab;          // [kTrainGenReduceSlabs][1 + L*L]
     double *out;           // [1 + L*L + A*L]: f, xi, expected state counts
     int64_t n_win;
@@ -196,6 +201,136 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_windows(GenProb P) {
     if (tid == 0) part[0] = f_sh;
 }
 
+// Whole sequences: gen_windows with the instance's own length n in place of W, and with the node marginals written
+// straight into item_marg (log alpha on the way forward, the marginal on the way back).  A workgroup owns the 256 / G
+// sequences it runs side by side, one per slot, so that an evaluation is as close to its bound, the longest sequence, as
+// the sequence count allows: instance q of the problem's slot order (longest first, ties by index: computed on the host
+// from the problem alone) runs in workgroup q / kSlots, slot q % kSlots, and the groups running side by side have
+// neighbouring lengths.  The lengths still differ inside a wave, so the loops over t have no workgroup barrier and no
+// shuffle that leaves the group's own G lanes (all of which run the same trip count); the butterfly and the barriers
+// come after every group has left its loops.
+template <int G>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_sequences(GenProb P) {
+    constexpr int kSlots = kTrainGenThreads / G;  // sequences of a workgroup, side by side
+    __shared__ double tT[G * G];             // [i][j] = T[i][j]
+    __shared__ double tTt[G * G];            // [j][i] = T[i][j]
+    __shared__ double xi_sh[G * G];          // [j][i]
+    __shared__ double f_sh;
+    const int tid = threadIdx.x;
+    const int L = P.L;
+    const int i = tid % G, slot = tid / G;
+    const bool lab = i < L;
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int a = e / G, b = e % G;
+        const double v = (a < L && b < L) ? P.trans[a * L + b] : 0.0;
+        tT[e] = v;
+        tTt[b * G + a] = v;
+    }
+    __syncthreads();
+
+    double xacc[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) xacc[k] = 0.0;
+    double facc = 0.0;
+    double v[G];
+    const int64_t q = static_cast<int64_t>(blockIdx.x) * kSlots + slot;
+    if (q < P.n_win) {  // (a whole group of G lanes)
+        const int64_t i0 = P.win_start[q];
+        const int n = P.win_len[q];
+        const double *sc = P.score + i0 * L;
+        const int32_t *label = P.label + i0;
+        double *mw = P.item_marg + i0 * L;
+
+        double la = lab ? sc[i] : 0.0;
+        int yprev = label[0];
+        double gold = (lab && yprev == i) ? la : 0.0;  // this label's share of the gold path's score
+        if (lab) mw[i] = la;
+        for (int t = 1; t < n; ++t) {
+            double mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = __shfl(la, k, G) + tT[k * G + i];
+                    mx = fmax(mx, v[k]);
+                }
+            double sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) sum += exp(v[k] - mx);
+            const double s = lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0;
+            la = mx + log(sum) + s;
+            const int y = label[t];
+            if (lab && y == i) gold += s + tT[yprev * G + i];
+            yprev = y;
+            if (lab) mw[static_cast<int64_t>(t) * L + i] = la;
+        }
+        double mx = -INFINITY, gold_all = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            if (k < L) {
+                v[k] = __shfl(la, k, G);
+                mx = fmax(mx, v[k]);
+                gold_all += __shfl(gold, k, G);
+            }
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            if (k < L) sum += exp(v[k] - mx);
+        const double logz = mx + log(sum);
+        if (i == 0) facc += logz - gold_all;
+
+        if (lab) mw[static_cast<int64_t>(n - 1) * L + i] = exp(la - logz);
+        double lb = 0.0;
+        for (int t = n - 1; t >= 1; --t) {
+            const double q_t = (lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0) + lb;  // log of exp(s_t[i]) beta_t[i]
+            const double lap = lab ? mw[static_cast<int64_t>(t - 1) * L + i] : 0.0;      // log alpha_{t-1}[i], stored by this lane
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = tTt[k * G + i] + __shfl(q_t, k, G);
+                    mx = fmax(mx, v[k]);
+                }
+            sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = exp(v[k] - mx);
+                    sum += v[k];
+                }
+            lb = mx + log(sum);
+            const double m = exp(lap + lb - logz);
+            const double c = m / sum;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) xacc[k] += c * v[k];
+            if (lab) mw[static_cast<int64_t>(t - 1) * L + i] = m;
+        }
+    }
+
+    // every group has left its loops: the slots of a wave by a butterfly, then the waves in wave order (as gen_windows)
+    for (int off = 32; off >= G; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
+        facc += __shfl_xor(facc, off);
+    }
+    const int wave = tid / 64, lane = tid % 64;
+    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
+        if (wave == wv && lane < G) {
+#pragma unroll
+            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
+            if (lane == 0) f_sh = (wv ? f_sh : 0.0) + facc;
+        }
+        __syncthreads();
+    }
+    double *part = P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L);
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int k = e / G, a = e % G;
+        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
+    }
+    if (tid == 0) part[0] = f_sh;
+}
+
 __global__ void __launch_bounds__(kTrainGenThreads) gen_item_marginals(GenProb P) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * kTrainGenThreads + threadIdx.x;
     if (idx >= static_cast<int64_t>(P.n_items) * P.L) return;
@@ -282,6 +417,7 @@ int group_of(int L) {
 // space with every problem's scratch (so that the active problems of an evaluation run back to back on the stream).
 struct TrainerGeneral {
     int device = 0;
+    bool whole = false;  // the whole-sequence family: every problem's instances are its sequences (W = step = 0)
     struct Prob {
         int32_t A, n_items, K, L, W, step, n_blocks;
         int64_t n_win;
@@ -293,7 +429,7 @@ struct TrainerGeneral {
     std::vector<Prob> probs;
     std::vector<double> h_in, h_out;
     hipStream_t stream = nullptr;
-    int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr;
+    int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr, *d_win_len = nullptr;
     int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr, *d_attr_ptr = nullptr, *d_attr_items = nullptr;
     double *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
 
@@ -302,38 +438,47 @@ struct TrainerGeneral {
         int prev = -1;
         const bool restore = hipGetDevice(&prev) == hipSuccess && prev != device;
         (void)hipSetDevice(device);
-        for (void *p : {(void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start, (void *)d_iw_first,
-                        (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items, (void *)d_in,
-                        (void *)d_out, (void *)d_scratch})
+        for (void *p : {(void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start, (void *)d_win_len,
+                        (void *)d_iw_first, (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items,
+                        (void *)d_in, (void *)d_out, (void *)d_scratch})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
         if (restore && prev >= 0) (void)hipSetDevice(prev);
     }
 };
 
-int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
-                           const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
-                           const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
-                           const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                           TrainerGeneral **out) {
+namespace {
+
+// Both families' create: window == nullptr is the whole-sequence family.
+int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                         const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                         const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                         const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                         TrainerGeneral **out) {
     auto t = std::make_unique<TrainerGeneral>();
     t->device = device;
-    std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c, attr_items_c;
+    const bool whole = t->whole = window == nullptr;
+    const std::string family = whole ? "trainer sequences: problem " : "trainer general: problem ";
+    std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, win_len_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c,
+        attr_items_c;
     int64_t in_total = 0, out_total = 0, scratch_total = 0;
     for (int32_t k = 0; k < n_problems; ++k) {
         HostProblem hp;
         int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
-                               window[k], step[k], state_fid[k], trans_fid[k], num_features[k], kTrainGenMaxL, &hp);
+                               whole ? 0 : window[k], whole ? 0 : step[k], state_fid[k], trans_fid[k], num_features[k],
+                               kTrainGenMaxL, &hp, whole);
         if (rc) {
-            set_error("trainer general: problem " + std::to_string(k) + ": " + last_error());
+            set_error(family + std::to_string(k) + ": " + last_error());
             return rc;
         }
         TrainerGeneral::Prob p;
-        p.A = hp.A, p.n_items = hp.n_items, p.K = hp.K, p.L = num_labels[k], p.W = window[k], p.step = step[k];
+        p.A = hp.A, p.n_items = hp.n_items, p.K = hp.K, p.L = num_labels[k];
+        p.W = whole ? 0 : window[k], p.step = whole ? 0 : step[k];
         p.n_win = hp.n_win;
-        const int64_t nb = blocks_of(hp.n_win, kTrainGenWindowsPerBlock), cols = 1 + int64_t(p.L) * p.L;
+        const int64_t nb = blocks_of(hp.n_win, whole ? kTrainGenThreads / group_of(p.L) : kTrainGenWindowsPerBlock);
+        const int64_t cols = 1 + int64_t(p.L) * p.L;
         if (nb > INT32_MAX || blocks_of(int64_t(p.n_items) * p.L, kTrainGenThreads) > INT32_MAX)
-            return fail("trainer general: problem " + std::to_string(k) + ": more than 2^31 workgroups in one launch");
+            return fail(family + std::to_string(k) + ": more than 2^31 workgroups in one launch");
         p.n_blocks = int32_t(nb);
         p.item0 = int64_t(label_c.size());
         p.iptr0 = int64_t(item_ptr_c.size());
@@ -341,7 +486,8 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
         p.win0 = int64_t(win_start_c.size());
         p.aptr0 = int64_t(attr_ptr_c.size());
         p.in0 = in_total, p.out0 = out_total, p.sc0 = scratch_total;
-        // scratch: item scores and item marginals [n_items][L], node marginals [n_win][W][L], blocks and slabs of (f, xi)
+        // scratch: item scores and item marginals [n_items][L], node marginals [n_win][W][L] (none for whole sequences:
+        // W = 0), blocks and slabs of (f, xi)
         p.scratch = 2 * int64_t(p.n_items) * p.L + hp.n_win * p.W * p.L + (nb + kTrainGenReduceSlabs) * cols;
         in_total += int64_t(p.A) * p.L + int64_t(p.L) * p.L;
         out_total += cols + int64_t(p.A) * p.L;
@@ -350,9 +496,12 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
         append(attr_id_c, hp.attr_id);
         append(label_c, hp.label);
         append(win_start_c, hp.win_start);
-        append(iw_first_c, hp.iw_first);
-        append(iw_cnt_c, hp.iw_cnt);
-        append(iw_off_c, hp.iw_off);
+        append(win_len_c, hp.win_len);
+        if (!whole) {  // (the coverage of an item: only the windowed family's kernel 3 reads it)
+            append(iw_first_c, hp.iw_first);
+            append(iw_cnt_c, hp.iw_cnt);
+            append(iw_off_c, hp.iw_off);
+        }
         append(attr_ptr_c, hp.attr_ptr);
         append(attr_items_c, hp.attr_items);
         p.state_fid = std::move(hp.state_fid);
@@ -378,6 +527,7 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
     if ((rc = dev_upload(&t->d_attr_id, attr_id_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_label, label_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_win_start, win_start_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_win_len, win_len_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_iw_first, iw_first_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_iw_cnt, iw_cnt_c, "trainer upload"))) return rc;
     if ((rc = dev_upload(&t->d_iw_off, iw_off_c, "trainer upload"))) return rc;
@@ -392,12 +542,33 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
     return GECCO_CRF_OK;
 }
 
+}  // namespace
+
+int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                           const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                           const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                           const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                           TrainerGeneral **out) {
+    if (!window || !step) return fail("trainer general: null argument");
+    return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
+                                step, state_fid, trans_fid, num_features, out);
+}
+
+int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                             const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
+                             const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
+                             const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out) {
+    return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, nullptr,
+                                nullptr, state_fid, trans_fid, num_features, out);
+}
+
 int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
-    if (!t || !active || !w || !f || !g) return fail("trainer_general_eval: null argument");
+    const std::string name = (t && t->whole) ? "trainer_sequences_eval" : "trainer_general_eval";
+    if (!t || !active || !w || !f || !g) return fail(name + ": null argument");
     const int32_t P = int32_t(t->probs.size());
     for (int32_t k = 0; k < P; ++k)
         if (active[k] && (!g[k] || (t->probs[k].K > 0 && !w[k])))
-            return fail("trainer_general_eval: null argument for problem " + std::to_string(k));
+            return fail(name + ": null argument for problem " + std::to_string(k));
     int64_t in_lo = INT64_MAX, in_hi = 0, out_lo = INT64_MAX, out_hi = 0;
     for (int32_t k = 0; k < P; ++k) {
         const TrainerGeneral::Prob &p = t->probs[k];
@@ -428,9 +599,11 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             a.attr_id = t->d_attr_id + p.nnz0;
             a.label = t->d_label + p.item0;
             a.win_start = t->d_win_start + p.win0;
-            a.iw_first = t->d_iw_first + p.item0;
-            a.iw_cnt = t->d_iw_cnt + p.item0;
-            a.iw_off = t->d_iw_off + p.item0;
+            a.win_len = t->d_win_len + (t->whole ? p.win0 : 0);
+            // (the item coverage is the windowed family's alone: in a whole-sequence trainer the arrays are empty)
+            a.iw_first = t->d_iw_first + (t->whole ? 0 : p.item0);
+            a.iw_cnt = t->d_iw_cnt + (t->whole ? 0 : p.item0);
+            a.iw_off = t->d_iw_off + (t->whole ? 0 : p.item0);
             a.attr_ptr = t->d_attr_ptr + p.aptr0;
             a.attr_items = t->d_attr_items + p.nnz0;
             a.wstate = t->d_in + p.in0;
@@ -446,14 +619,24 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             const unsigned nb_items = unsigned(blocks_of(nl, kTrainGenThreads));
             const int G = group_of(p.L);
             gen_item_scores<<<nb_items, kTrainGenThreads, 0, st>>>(a);
-            switch (G) {
-                case 2: gen_windows<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                case 4: gen_windows<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                case 8: gen_windows<8><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                case 16: gen_windows<16><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                default: gen_windows<32><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+            if (t->whole) {
+                switch (G) {
+                    case 2: gen_sequences<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    case 4: gen_sequences<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    case 8: gen_sequences<8><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    case 16: gen_sequences<16><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    default: gen_sequences<32><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                }
+            } else {
+                switch (G) {
+                    case 2: gen_windows<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    case 4: gen_windows<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    case 8: gen_windows<8><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    case 16: gen_windows<16><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                    default: gen_windows<32><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
+                }
+                gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
             }
-            gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
             gen_attr_counts<<<unsigned(p.A), kTrainGenThreads, 0, st>>>(a, G);
             gen_reduce_blocks<<<kTrainGenReduceSlabs, kTrainGenThreads, 0, st>>>(a);
             gen_reduce_final<<<1, kTrainGenThreads, 0, st>>>(a);

@@ -1,6 +1,8 @@
 """A linear-chain CRF over sequences of items with string attributes and 2 to 32 string labels, trained and applied on
 the device: the shape of ``sklearn_crfsuite.CRF`` over this package's training stack (``train``) and inference entry
-points (``_native.Model``).  Training instances are the sliding windows of every sequence, as everywhere in GECCO.
+points (``_native.Model``).  Training instances are the sliding windows of every sequence, as everywhere in GECCO, or
+with ``window_size=None`` the whole sequences, as CRFsuite trains outside GECCO: the objective ``predict`` and
+``predict_marginals`` decode with.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -24,18 +26,22 @@ def _items(xseq: Iterable[Iterable[str]]) -> List[List[str]]:
 class SequenceCRF:
     """``SequenceCRF(window_size=5, window_step=1, device=0, **options)``: ``options`` are the trainer's
     (``train.trainer_params``: ``c1``, ``c2``, ``min_freq``, ``all_possible_states``, ``all_possible_transitions`` and the
-    libLBFGS parameters).
+    libLBFGS parameters).  ``window_size=None``: the training instances are the whole sequences, of any length from one
+    item up; ``window_step`` is then ignored and stored as 1, and the model has no windowed predictions.
 
     After ``fit(X, y)``: ``classes_`` (labels in order of first appearance), ``attributes_`` (the attributes the model
     keeps), ``state_features_`` ``{(attribute, label): weight}``, ``transition_features_`` ``{(from, to): weight}`` (the
     non-zero weights, unrounded) and ``training_result_`` (``train.OptimizeResult``)."""
 
-    def __init__(self, window_size: int = 5, window_step: int = 1, device: int = 0, **options):
-        window_size, window_step = int(window_size), int(window_step)
-        if not 1 <= window_size <= 32:
-            raise ValueError(f"window_size must lie in 1..32, got {window_size}")
-        if not 1 <= window_step <= window_size:
-            raise ValueError("Window step must be strictly positive and under `window_size`")
+    def __init__(self, window_size: Optional[int] = 5, window_step: int = 1, device: int = 0, **options):
+        if window_size is None:
+            window_step = 1
+        else:
+            window_size, window_step = int(window_size), int(window_step)
+            if not 1 <= window_size <= 32:
+                raise ValueError(f"window_size must lie in 1..32, got {window_size}")
+            if not 1 <= window_step <= window_size:
+                raise ValueError("Window step must be strictly positive and under `window_size`")
         self.window_size, self.window_step, self.device = window_size, window_step, int(device)
         self.params = train.trainer_params(options)
         self.training_result_: Optional[train.OptimizeResult] = None
@@ -51,10 +57,11 @@ class SequenceCRF:
         for k, (items, ls) in enumerate(zip(seqs, labs)):
             if len(items) != len(ls):
                 raise ValueError(f"sequence {k}: {len(items)} items but {len(ls)} labels")
-            if len(items) < self.window_size:
+            if self.window_size is not None and len(items) < self.window_size:
                 raise ValueError(f"sequence {k} has {len(items)} items, fewer than the window of {self.window_size}")
         p = self.params
-        ts = train.build_training_set(seqs, labs, self.window_size, self.window_step, min_freq=p["min_freq"],
+        step = None if self.window_size is None else self.window_step
+        ts = train.build_training_set(seqs, labs, self.window_size, step, min_freq=p["min_freq"],
                                       all_possible_states=p["all_possible_states"],
                                       all_possible_transitions=p["all_possible_transitions"], max_labels=train.MAX_LABELS)
         self.training_result_ = train.fit_training_set(ts, p, device=self.device)
@@ -92,13 +99,13 @@ class SequenceCRF:
             fh.write(self.to_bytes())
 
     @classmethod
-    def from_bytes(cls, blob: bytes, window_size: int = 5, window_step: int = 1, device: int = 0, **options) -> "SequenceCRF":
+    def from_bytes(cls, blob: bytes, window_size: Optional[int] = 5, window_step: int = 1, device: int = 0, **options) -> "SequenceCRF":
         crf = cls(window_size, window_step, device, **options)
         crf._set_blob(blob)
         return crf
 
     @classmethod
-    def load(cls, path, window_size: int = 5, window_step: int = 1, device: int = 0, **options) -> "SequenceCRF":
+    def load(cls, path, window_size: Optional[int] = 5, window_step: int = 1, device: int = 0, **options) -> "SequenceCRF":
         with open(path, "rb") as fh:
             return cls.from_bytes(fh.read(), window_size, window_step, device, **options)
 
@@ -134,9 +141,50 @@ class SequenceCRF:
         marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device)
         return self._split(marg, seq_ptr)
 
+    def log_likelihood(self, X, y: Sequence[Sequence[str]]) -> np.ndarray:
+        """``log p(y | x)`` of every sequence under the model (CRFsuite's ``Tagger.probability`` in logs): the gold path's
+        score, gathered on the host from the weight tables, minus the log partition function of the whole-sequence
+        marginals.  An unknown label raises ``ValueError``; an empty sequence gives 0.0."""
+        seq_ptr, item_ptr, attr = self._pack(X)
+        index = {c: k for k, c in enumerate(self.classes_)}
+        labs = [[str(lab) for lab in yseq] for yseq in y]
+        n_seqs = len(seq_ptr) - 1
+        if len(labs) != n_seqs:
+            raise ValueError(f"X holds {n_seqs} sequences and y {len(labs)}")
+        for k, ls in enumerate(labs):
+            if len(ls) != seq_ptr[k + 1] - seq_ptr[k]:
+                raise ValueError(f"sequence {k}: {seq_ptr[k + 1] - seq_ptr[k]} items but {len(ls)} labels")
+            for lab in ls:
+                if lab not in index:
+                    raise ValueError(f"unknown label {lab!r} (classes_: {self.classes_})")
+        out = np.zeros(n_seqs)
+        if seq_ptr[-1] == 0:
+            return out
+        lengths = np.diff(seq_ptr)
+        full = np.flatnonzero(lengths > 0)  # (an empty sequence stays at 0.0 and never reaches the device)
+        ptr = np.concatenate([[0], np.cumsum(lengths[full])]).astype(np.int32)
+        _, lognorm = self._model.marginals_full(ptr, item_ptr, attr, device=self.device)
+        state, _ = self._model.state_weights()
+        trans, _ = self._model.trans_weights()
+        yy = np.array([index[lab] for ls in labs for lab in ls], dtype=np.int64)
+        owner = np.repeat(np.arange(len(yy)), np.diff(item_ptr))
+        score = np.zeros(len(yy))  # per item: its state score under its label, and the transition into it
+        np.add.at(score, owner, state[attr, yy[owner]])
+        inner = np.ones(len(yy), dtype=bool)
+        inner[ptr[:-1]] = False  # (the first item of a sequence has no predecessor)
+        score[inner] += trans[yy[np.flatnonzero(inner) - 1], yy[inner]]
+        out[full] = np.add.reduceat(score, ptr[:-1]) - lognorm
+        return out
+
+    def _windowed(self) -> None:
+        self._fitted()
+        if self.window_size is None:
+            raise ValueError("this SequenceCRF has no window (window_size=None): it has no windowed predictions")
+
     def predict_windowed(self, X, label: str, pad: bool = True) -> List[np.ndarray]:
         """GECCO's windowed probability of ``label``: per item the maximum, over the windows covering it, of the
         label's marginal inside the window (``pad``: a sequence shorter than the window is one window)."""
+        self._windowed()
         seq_ptr, item_ptr, attr = self._pack(X)
         if str(label) not in self.classes_:
             raise ValueError(f"unknown label {label!r} (classes_: {self.classes_})")
@@ -151,6 +199,7 @@ class SequenceCRF:
         in ``classes_`` order (per item and label the maximum, over the windows covering the item, of the label's marginal
         inside the window).  With ``background`` also, second, one ``[n_items]`` array per sequence: the maximum over the
         same windows of the probability of any label but ``background``."""
+        self._windowed()
         seq_ptr, item_ptr, attr = self._pack(X)
         L = len(self.classes_)
         if background is not None and str(background) not in self.classes_:

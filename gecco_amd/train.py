@@ -1,11 +1,13 @@
 """Host side of CRF training (``ClusterCRF.fit``): the training set, CRFsuite's feature generation, and the L-BFGS /
 OWL-QN optimiser.  The objective and its gradient are evaluated on the device (``_native.Trainer``,
-``csrc/crf_train.hip``; sets of 3 to 32 labels: ``_native.TrainerGeneral``, ``csrc/crf_train_general.hip``);
-everything here is cheap bookkeeping around that.
+``csrc/crf_train.hip``; sets of 3 to 32 labels: ``_native.TrainerGeneral``, ``csrc/crf_train_general.hip``; sets whose
+instances are the whole sequences, ``window=None``: ``_native.TrainerSequences``, same file); everything here is cheap
+bookkeeping around that.
 
 What is reproduced ([EXT] CRFsuite 0.12 ``crf1d`` + ``train_lbfgs`` with libLBFGS, as sklearn-crfsuite drives it):
 
-* instances are the sliding windows of every sequence (``gecco/crf/__init__.py:364-367``); labels and attributes get ids
+* instances are the sliding windows of every sequence (``gecco/crf/__init__.py:364-367``), or with ``window=None`` the
+  sequences themselves, as CRFsuite is driven outside GECCO; labels and attributes get ids
   in order of first appearance over the instances, attribute names before the label of every item;
 * a state feature exists for every observed (attribute, label) pair and a transition feature for every observed label
   bigram inside an instance; ``all_possible_states`` / ``all_possible_transitions`` add the unobserved ones and
@@ -28,7 +30,7 @@ import numpy as np
 __all__ = ["TRAINER_DEFAULTS", "MAX_LABELS", "trainer_params", "minimize", "minimize_steps", "OptimizeResult", "TrainingSet",
            "build_training_set", "fit_training_set", "fit_training_sets", "fit_grid", "model_blob"]
 
-#: the most labels a training set may have (``_native.TrainerGeneral``; the inference kernels' limit)
+#: the most labels a training set may have (``_native.TrainerGeneral`` / ``TrainerSequences``; the inference kernels' limit)
 MAX_LABELS = 32
 #: libLBFGS parameters as CRFsuite's ``train_lbfgs`` sets them (``max_iterations`` None = unbounded)
 TRAINER_DEFAULTS = {"num_memories": 6, "epsilon": 1e-5, "period": 10, "delta": 1e-5, "max_iterations": None}
@@ -242,9 +244,11 @@ class TrainingSet:
         return len(self.labels_)
 
     def native_args(self) -> tuple:
-        """The set as ``_native.TrainerGrid`` takes it (``TrainerBatch``: without the last two, window and step)."""
-        return (self.seq_ptr, self.item_ptr, self.attr_id, self.labels, len(self.attrs_), self.state_fid, self.trans_fid,
-                self.num_features, self.window, self.step)
+        """The set as ``_native.TrainerGrid`` takes it (``TrainerBatch``: without the last two, window and step); a set of
+        whole sequences (``window is None``) as ``_native.TrainerSequences`` takes it, which is without those two."""
+        args = (self.seq_ptr, self.item_ptr, self.attr_id, self.labels, len(self.attrs_), self.state_fid, self.trans_fid,
+                self.num_features)
+        return args if self.window is None else args + (self.window, self.step)
 
 
 def _coverage(n: int, window: int, step: int) -> np.ndarray:
@@ -268,19 +272,30 @@ def _pair_coverage(n: int, window: int, step: int) -> np.ndarray:
 
 
 def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_labels: Sequence[Sequence[str]],
-                       window: int, step: int, min_freq: float = 0.0, all_possible_states: bool = False,
-                       all_possible_transitions: bool = False, max_labels: int = 2) -> TrainingSet:
+                       window: Optional[int] = None, step: Optional[int] = None, min_freq: float = 0.0,
+                       all_possible_states: bool = False, all_possible_transitions: bool = False,
+                       max_labels: int = 2) -> TrainingSet:
     """Encode sequences (per item the attribute names, per item a label) and generate CRFsuite's features over the
     sliding-window instances.  Every sequence must hold at least `window` items.  Raises ``ValueError`` unless exactly
-    two labels occur, or, with ``max_labels`` = m in 2..32, unless 2 to m labels occur."""
+    two labels occur, or, with ``max_labels`` = m in 2..32, unless 2 to m labels occur.
+
+    ``window=None``: the instances are the whole sequences, of any length from one item up (``step`` is not read, and the
+    set's ``window`` and ``step`` are None): a state feature's frequency is its plain count, a transition's its count over
+    adjacent pairs.  An empty sequence raises ``ValueError``."""
     if not 2 <= int(max_labels) <= MAX_LABELS:
         raise ValueError(f"max_labels must lie in 2..{MAX_LABELS}, got {max_labels}")
+    whole = window is None
+    if whole:
+        step = None
+        for k, items in enumerate(sequences):
+            if len(items) == 0:
+                raise ValueError(f"sequence {k} has no items: a whole-sequence instance holds at least one")
     label_index: Dict[str, int] = {}
     attr_index: Dict[str, int] = {}
     covs = []
     # ids in order of first appearance over the instances: an item no window covers is never seen by CRFsuite
     for items, labs in zip(sequences, sequence_labels):
-        cov = _coverage(len(items), window, step)
+        cov = np.ones(len(items), dtype=np.int64) if whole else _coverage(len(items), window, step)
         covs.append(cov)
         for names, lab, c in zip(items, labs, cov.tolist()):
             if c == 0:
@@ -324,7 +339,7 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
     trans_seen = np.zeros(L * L, dtype=bool)
     for s in range(len(seq_ptr) - 1):
         b, e = seq_ptr[s], seq_ptr[s + 1]
-        pc = _pair_coverage(e - b, window, step)
+        pc = np.ones(e - b - 1, dtype=np.int64) if whole else _pair_coverage(e - b, window, step)
         pair = lab_a[b:e - 1] * L + lab_a[b + 1:e]
         np.add.at(trans_freq, pair, pc.astype(np.float64))
         trans_seen[pair[pc > 0]] = True
@@ -350,12 +365,15 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
 
 def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0,
                      callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> OptimizeResult:
-    """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0.  A set of two labels
-    takes the 2-label trainer, one of more labels ``_native.TrainerGeneral``."""
+    """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0.  A set of whole
+    sequences (``window is None``) takes ``_native.TrainerSequences`` at any label count; of the windowed sets, one of two
+    labels takes the 2-label trainer, one of more labels ``_native.TrainerGeneral``."""
     from . import _native
 
     args = ts.native_args()
-    if ts.num_labels == 2:
+    if ts.window is None:
+        trainer = _native.TrainerSequences([args], device=device)
+    elif ts.num_labels == 2:
         trainer = _native.Trainer(*args[:5], *args[8:], *args[5:8], device=device)  # (window and step in the middle)
     else:
         trainer = _native.TrainerGeneral([args], device=device)
@@ -371,37 +389,50 @@ def _general_scratch_bytes(ts: TrainingSet) -> int:
     return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L))
 
 
+def _sequences_scratch_bytes(ts: TrainingSet) -> int:
+    """The scratch ``_native.TrainerSequences`` allocates for ``ts`` (``scratch_bytes(k)``; the formula of DESIGN.md
+    §4.9c: item scores and marginals, and one (f, xi) block per 256 / G sequences, G the power of two at or above L,
+    plus 32 slabs)."""
+    L = ts.num_labels
+    per_block = 256 // max(2, 1 << (L - 1).bit_length())
+    return 8 * (2 * int(ts.seq_ptr[-1]) * L + (-(-(len(ts.seq_ptr) - 1) // per_block) + 32) * (1 + L * L))
+
+
 def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], List[OptimizeResult]],
                     params: Callable[[int], Dict[str, object]], device: int,
                     scratch_budget_bytes: Optional[int] = None) -> List[OptimizeResult]:
-    """Results of fits whose sets may mix label counts: ``fit_two(indices)`` fits those of two labels as before, the
-    others run in ``_native.TrainerGeneral``; fit k trains ``sets[k]`` with ``params(k)``.  Without a budget the
-    many-label fits share one trainer; with one they run, in their order, in groups whose scratch fits the budget (a
-    group holds at least one fit), one trainer after another, so that only one group is resident at a time.  A fit's
-    result does not depend on its group: problem k of a trainer has the bits of a lone trainer of it."""
+    """Results of fits whose sets may mix label counts: ``fit_two(indices)`` fits the windowed sets of two labels as
+    before, the other windowed sets run in ``_native.TrainerGeneral`` and the sets of whole sequences (``window is
+    None``, any label count) in ``_native.TrainerSequences``; fit k trains ``sets[k]`` with ``params(k)``.  Without a
+    budget the fits of such a family share one trainer; with one they run, in their order, in groups whose scratch fits the
+    budget (a group holds at least one fit), one trainer after another, so that only one group is resident at a time.  A
+    fit's result does not depend on its group: problem k of a trainer has the bits of a lone trainer of it."""
     from . import _native
 
     results: List[Optional[OptimizeResult]] = [None] * len(sets)
-    two = [k for k, ts in enumerate(sets) if ts.num_labels == 2]
-    more = [k for k, ts in enumerate(sets) if ts.num_labels != 2]
+    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2]
+    more = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels != 2]
+    whole = [k for k, ts in enumerate(sets) if ts.window is None]
     if two:
         for k, r in zip(two, fit_two(two)):
             results[k] = r
     budget = scratch_budget_bytes if scratch_budget_bytes and scratch_budget_bytes > 0 else None  # as TrainerGrid: 0 = none
-    groups: List[List[int]] = []
-    used = 0
-    for k in more:
-        need = _general_scratch_bytes(sets[k]) if budget is not None else 0
-        if not groups or (budget is not None and used + need > budget):
-            groups.append([])
-            used = 0
-        groups[-1].append(k)
-        used += need
-    for group in groups:
-        general = _native.TrainerGeneral([sets[k].native_args() for k in group], device=device)
-        for k, r in zip(group, _fit_lockstep(general, [sets[k] for k in group], [params(k) for k in group])):
-            results[k] = r
-        del general  # frees the group's device memory before the next group is created
+    for members, scratch, family in ((more, _general_scratch_bytes, "TrainerGeneral"),
+                                     (whole, _sequences_scratch_bytes, "TrainerSequences")):
+        groups: List[List[int]] = []
+        used = 0
+        for k in members:
+            need = scratch(sets[k]) if budget is not None else 0
+            if not groups or (budget is not None and used + need > budget):
+                groups.append([])
+                used = 0
+            groups[-1].append(k)
+            used += need
+        for group in groups:
+            trainer = getattr(_native, family)([sets[k].native_args() for k in group], device=device)
+            for k, r in zip(group, _fit_lockstep(trainer, [sets[k] for k in group], [params(k) for k in group])):
+                results[k] = r
+            del trainer  # frees the group's device memory before the next group is created
     return results
 
 
@@ -410,8 +441,9 @@ def fit_training_sets(sets: Sequence[TrainingSet], params: Dict[str, object], de
     and one optimiser per set runs in lock-step, each round evaluating the pending points of the unfinished sets in one
     batched pass.  Sets drop out as they stop.  Result k is exactly ``fit_training_set(sets[k], params, device)``:
     the batched objective gives every set the bits a lone trainer gives it, and the optimiser loop is the same one.
-    The sets must share ``window`` and ``step``.  Sets of more than two labels run in a ``_native.TrainerGeneral`` of
-    their own, beside the batch of the 2-label sets."""
+    The sets must share ``window`` and ``step`` (sets of whole sequences, ``window is None``, share them).  Sets of more
+    than two labels run in a ``_native.TrainerGeneral`` of their own, beside the batch of the 2-label sets; sets of whole
+    sequences in a ``_native.TrainerSequences``."""
     from . import _native
 
     if not sets:
@@ -439,7 +471,7 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
     problems in one batched pass (in groups whose scratch fits ``scratch_budget_bytes``).  Result k is exactly
     ``fit_training_set(sets[set_k], params_k, device)``.  Problems on sets of more than two labels run in
     ``_native.TrainerGeneral`` (one copy of the set per problem), also in groups whose scratch fits the budget, one
-    group resident at a time."""
+    group resident at a time; so do problems on sets of whole sequences, in ``_native.TrainerSequences``."""
     from . import _native
 
     if not problems:
@@ -449,7 +481,7 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
             raise ValueError(f"fit_grid: problem {k} names set {s}, but there are {len(sets)} sets")
 
     def fit_two(idx):
-        used = [s for s, ts in enumerate(sets) if ts.num_labels == 2]
+        used = [s for s, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2]
         grid = _native.TrainerGrid([sets[s].native_args() for s in used], [used.index(int(problems[k][0])) for k in idx],
                                    scratch_budget_bytes, device=device)
         return _fit_lockstep(grid, [sets[int(problems[k][0])] for k in idx], [problems[k][1] for k in idx])

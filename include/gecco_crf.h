@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310). */
+/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -555,6 +555,37 @@ int32_t gecco_crf_trainer_general_num_problems(const gecco_crf_trainer_general *
 int64_t gecco_crf_trainer_general_num_windows(const gecco_crf_trainer_general *t, int32_t k);
 int64_t gecco_crf_trainer_general_scratch_bytes(const gecco_crf_trainer_general *t, int32_t k);
 void gecco_crf_trainer_general_free(gecco_crf_trainer_general *t);
+
+/* ---- training on whole sequences (ABI 2.12.0) ---------------------------------------------------------------------
+ * CRFsuite's own training mode: one instance per sequence, of that sequence's length, for 2 to 32 labels:
+ *     f(w) = sum over sequences of (log Z(sequence) - score(gold labels)),  g(w) = expected - empirical feature counts.
+ * The arguments are gecco_crf_trainer_general_create's without window and step; a sequence may hold any number of items
+ * from 1 up.  Refused on the host before any device work, with "trainer sequences: problem k: ..." in the message: a null
+ * argument, num_labels outside 2..32 (GECCO_CRF_EUNSUPPORTED), a label outside [0, L), an attribute id outside [0, A), a
+ * sequence of 0 items, a non-monotone seq_ptr or item_ptr, more than 2^31 workgroups in one launch.
+ * eval: as gecco_crf_trainer_general_eval (a problem without sequences gives f = 0, g = 0).  One upload, five launches per
+ * active problem, one download; synchronous.
+ * Method: the general family's log-space forward-backward over each whole sequence, G lanes per sequence (G = the power of
+ * two at or above L); the kernel's node marginals are the item marginals (every item lies in exactly one instance).  A
+ * workgroup owns 256 / G sequences of the problem's slot order (by length, longest first, ties by index: computed on the
+ * host from the problem alone) and runs them side by side.  No float atomics, every sum has one fixed order: f[k] and g[k] are bitwise what a trainer built
+ * from problem k alone returns for w[k], whichever problems are active, and two evaluations give the same bits.
+ * Cost: a sequence is sequential in its length (L exponentials per lane per step, forward and backward), so an evaluation
+ * takes at least the time of the longest sequence; one very long sequence is correct but slow.
+ * Memory: per problem 8 * (2 * items * L + (ceil(sequences / (256 / G)) + 32) * (1 + L * L)) bytes; scratch_bytes(t, k) gives
+ * exactly that, k = -1 the sum that is allocated.  num_sequences(t, k): the sequences of problem k (-1 for a bad k). */
+typedef struct gecco_crf_trainer_sequences gecco_crf_trainer_sequences;
+int gecco_crf_trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
+                                       const int32_t *const *item_ptr, const int32_t *const *attr_id,
+                                       const int32_t *const *labels, const int32_t *num_attrs, const int32_t *num_labels,
+                                       const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                       const int32_t *num_features, gecco_crf_trainer_sequences **out);
+int gecco_crf_trainer_sequences_eval(gecco_crf_trainer_sequences *t, const uint8_t *active, const double *const *w, double *f,
+                                     double *const *g);
+int32_t gecco_crf_trainer_sequences_num_problems(const gecco_crf_trainer_sequences *t);
+int64_t gecco_crf_trainer_sequences_num_sequences(const gecco_crf_trainer_sequences *t, int32_t k);
+int64_t gecco_crf_trainer_sequences_scratch_bytes(const gecco_crf_trainer_sequences *t, int32_t k);
+void gecco_crf_trainer_sequences_free(gecco_crf_trainer_sequences *t);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
