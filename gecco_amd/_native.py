@@ -52,6 +52,20 @@ SIGNATURES = {
     ),
     "gecco_crf_marginals_full": (ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_f64p]),
     "gecco_crf_viterbi": (ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_i8p, _c_f64p]),
+    "gecco_crf_windowed_marginals_valued": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int32, _c_f64p],
+    ),
+    "gecco_crf_windowed_marginals_all_valued": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int32, _c_f64p, _c_f64p],
+    ),
+    "gecco_crf_marginals_full_valued": (
+        ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_f64p, _c_f64p]),
+    "gecco_crf_viterbi_valued": (
+        ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_i8p, _c_f64p]),
     "gecco_crf_segment": (
         ctypes.c_int,
         [ctypes.c_int32, _c_f64p, _c_u8p, _c_i32p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
@@ -206,6 +220,11 @@ SIGNATURES = {
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, _c_i32p, _c_i32p,
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
     ),
+    "gecco_crf_trainer_general_create_valued": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, _c_i32p, _c_i32p,
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
+    ),
     "gecco_crf_trainer_general_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_general_num_problems": (ctypes.c_int32, [_vp]),
     "gecco_crf_trainer_general_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
@@ -215,6 +234,12 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
          ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)],
+    ),
+    "gecco_crf_trainer_sequences_create_valued": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+         ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p,
+         ctypes.POINTER(_vp)],
     ),
     "gecco_crf_trainer_sequences_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_sequences_num_problems": (ctypes.c_int32, [_vp]),
@@ -468,68 +493,89 @@ class Model:
         return w, present.astype(bool)
 
     # ---- one-shot compute (host buffers) ----
-    def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0):
+    # ``values=``: one float64 per attribute entry, parallel to ``attr_id`` (CRFsuite's name:value items): the state score of
+    # a gene is the sum of value * weight, and the call takes the ``*_valued`` entry (the any-L kernels at every label
+    # count).  None: the unvalued entry, as ever.
+    @staticmethod
+    def _values(values, attr_id):
+        values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        if values.size != attr_id.size:
+            raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
+        return values if values.size else np.zeros(1, dtype=np.float64)
+
+    def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0, values=None):
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
         n = int(contig_ptr[-1]) if len(contig_ptr) else 0
         out = np.zeros(max(n, 1), dtype=np.float64)
+        if values is not None:
+            values = self._values(values, attr_id)
         if attr_id.size == 0:
             attr_id = np.zeros(1, dtype=np.int32)
-        _check(
-            self._lib.gecco_crf_windowed_marginals(
-                self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
-                _ptr(attr_id, _c_i32p), int(window), int(step), int(label), int(bool(pad)), _ptr(out, _c_f64p),
-            )
-        )
+        head = (self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
+                _ptr(attr_id, _c_i32p))
+        tail = (int(window), int(step), int(label), int(bool(pad)), _ptr(out, _c_f64p))
+        if values is None:
+            _check(self._lib.gecco_crf_windowed_marginals(*head, *tail))
+        else:
+            _check(self._lib.gecco_crf_windowed_marginals_valued(*head, _ptr(values, _c_f64p), *tail))
         return out[:n]
 
-    def windowed_marginals_all(self, contig_ptr, gene_ptr, attr_id, window, step=1, background=None, pad=True, device=0):
+    def windowed_marginals_all(self, contig_ptr, gene_ptr, attr_id, window, step=1, background=None, pad=True, device=0,
+                               values=None):
         """Every label's windowed probability in one device pass: ``(p_all [n, L], p_any [n] or None)``; ``p_any`` is the
         windowed probability of any label but ``background`` (a label id)."""
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
         n, L = (int(contig_ptr[-1]) if len(contig_ptr) else 0), self.num_labels
         p_all = np.zeros((max(n, 1), L), dtype=np.float64)
         p_any = None if background is None else np.zeros(max(n, 1), dtype=np.float64)
+        if values is not None:
+            values = self._values(values, attr_id)
         if attr_id.size == 0:
             attr_id = np.zeros(1, dtype=np.int32)
-        _check(
-            self._lib.gecco_crf_windowed_marginals_all(
-                self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
-                _ptr(attr_id, _c_i32p), int(window), int(step), -1 if background is None else int(background), int(bool(pad)),
-                _ptr(p_all, _c_f64p), None if p_any is None else _ptr(p_any, _c_f64p),
-            )
-        )
+        head = (self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
+                _ptr(attr_id, _c_i32p))
+        tail = (int(window), int(step), -1 if background is None else int(background), int(bool(pad)),
+                _ptr(p_all, _c_f64p), None if p_any is None else _ptr(p_any, _c_f64p))
+        if values is None:
+            _check(self._lib.gecco_crf_windowed_marginals_all(*head, *tail))
+        else:
+            _check(self._lib.gecco_crf_windowed_marginals_all_valued(*head, _ptr(values, _c_f64p), *tail))
         return p_all[:n], (None if p_any is None else p_any[:n])
 
-    def marginals_full(self, contig_ptr, gene_ptr, attr_id, device=0):
+    def marginals_full(self, contig_ptr, gene_ptr, attr_id, device=0, values=None):
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
         n, nc, L = int(contig_ptr[-1]), len(contig_ptr) - 1, self.num_labels
         marg = np.zeros((max(n, 1), L), dtype=np.float64)
         ln = np.zeros(max(nc, 1), dtype=np.float64)
+        if values is not None:
+            values = self._values(values, attr_id)
         if attr_id.size == 0:
             attr_id = np.zeros(1, dtype=np.int32)
-        _check(
-            self._lib.gecco_crf_marginals_full(
-                self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
-                _ptr(marg, _c_f64p), _ptr(ln, _c_f64p),
-            )
-        )
+        head = (self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p))
+        tail = (_ptr(marg, _c_f64p), _ptr(ln, _c_f64p))
+        if values is None:
+            _check(self._lib.gecco_crf_marginals_full(*head, *tail))
+        else:
+            _check(self._lib.gecco_crf_marginals_full_valued(*head, _ptr(values, _c_f64p), *tail))
         return marg[:n], ln[:nc]
 
-    def viterbi(self, contig_ptr, gene_ptr, attr_id, device=0, want_score=True):
+    def viterbi(self, contig_ptr, gene_ptr, attr_id, device=0, want_score=True, values=None):
         """Best label path per contig; with `want_score=False` returns (labels, None) and 2-label
         models take the cheaper score-difference form of the recursion."""
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
         n, nc = int(contig_ptr[-1]), len(contig_ptr) - 1
         y = np.zeros(max(n, 1), dtype=np.int8)
         sc = np.zeros(max(nc, 1), dtype=np.float64) if want_score else None
+        if values is not None:
+            values = self._values(values, attr_id)
         if attr_id.size == 0:
             attr_id = np.zeros(1, dtype=np.int32)
-        _check(
-            self._lib.gecco_crf_viterbi(
-                self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
-                _ptr(y, _c_i8p), _ptr(sc, _c_f64p) if want_score else None,
-            )
-        )
+        head = (self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p))
+        tail = (_ptr(y, _c_i8p), _ptr(sc, _c_f64p) if want_score else None)
+        if values is None:
+            _check(self._lib.gecco_crf_viterbi(*head, *tail))
+        else:
+            _check(self._lib.gecco_crf_viterbi_valued(*head, _ptr(values, _c_f64p), *tail))
         return y[:n], (sc[:nc] if want_score else None)
 
 
@@ -1275,12 +1321,32 @@ class _TrainerHandle:
     def _c(self, name):
         return getattr(self._lib, f"{self._family}_{name}")
 
-    def _create(self, *args):
+    def _create(self, *args, entry: str = "create"):
         self._lib = load_library()
         self._h = None
         h = _vp()
-        _check(self._c("create")(*args, ctypes.byref(h)))
+        _check(self._c(entry)(*args, ctypes.byref(h)))
         self._h = h
+
+    @staticmethod
+    def _value_table(values, attr_sizes):
+        """``values=`` of the general and whole-sequence families: None, or per problem None (a problem without values)
+        or one float64 per attribute entry.  Returns None when no problem has values (the unvalued ``create`` is called),
+        else the table of pointers (NULL for a problem without) and the arrays it points to."""
+        if values is None or all(v is None for v in values):
+            return None, None
+        if len(values) != len(attr_sizes):
+            raise ValueError(f"values holds {len(values)} entries for {len(attr_sizes)} problems")
+        keep = []
+        for v, attr in zip(values, attr_sizes):
+            if v is None:
+                keep.append(None)
+                continue
+            v = np.ascontiguousarray(v, dtype=np.float64).ravel()
+            if v.size != attr:
+                raise ValueError(f"values of a problem hold {v.size} entries, its attr_id {attr}")
+            keep.append(v if v.size else np.zeros(1, dtype=np.float64))
+        return (_vp * len(keep))(*[None if v is None else v.ctypes.data for v in keep]), keep
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -1413,20 +1479,26 @@ class TrainerGeneral(_TrainerHandle):
     ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features,
     window, step)`` per problem, as ``TrainerGrid`` takes its sets; the label count of a problem is that of its
     ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the active problems; problem k's f and g are bitwise what a
-    ``TrainerGeneral`` of problem k alone returns for ``ws[k]``."""
+    ``TrainerGeneral`` of problem k alone returns for ``ws[k]``.  ``values=``: per problem None or one float64 per
+    attribute entry, parallel to its ``attr_id`` (``gecco_crf_trainer_general_create_valued``)."""
 
     _family = "gecco_crf_trainer_general"
     eval = _TrainerHandle._eval_problems
 
-    def __init__(self, problems, device: int = 0):
+    def __init__(self, problems, device: int = 0, values=None):
         arrays, counts = _trainer_sets(problems)
         if any(len(v) != len(problems) for v in counts.values()):
             raise ValueError("every problem needs a window and a step")
         t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
         c = {name: _i32_vector(v) for name, v in counts.items()}
-        self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], t["labels"],
-                     c["num_attrs"], c["num_labels"], c["window"], c["step"], t["state_fid"], t["trans_fid"],
-                     c["num_features"])
+        vt, _keep = self._value_table(values, [int(np.asarray(p[2]).size) for p in problems])
+        head = (int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"])
+        tail = (t["labels"], c["num_attrs"], c["num_labels"], c["window"], c["step"], t["state_fid"], t["trans_fid"],
+                c["num_features"])
+        if vt is None:
+            self._create(*head, *tail)
+        else:
+            self._create(*head, vt, *tail, entry="create_valued")
         self.num_features = self._features = counts["num_features"]
 
     def scratch_bytes(self, k: int = -1) -> int:
@@ -1441,19 +1513,24 @@ class TrainerSequences(_TrainerHandle):
     ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)``
     per problem; the label count of a problem is that of its ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the
     active problems; problem k's f and g are bitwise what a ``TrainerSequences`` of problem k alone returns for
-    ``ws[k]``."""
+    ``ws[k]``.  ``values=``: as ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_valued``)."""
 
     _family = "gecco_crf_trainer_sequences"
     eval = _TrainerHandle._eval_problems
 
-    def __init__(self, problems, device: int = 0):
+    def __init__(self, problems, device: int = 0, values=None):
         if any(len(p) != 8 for p in problems):
             raise ValueError("a whole-sequence problem has 8 entries: no window and no step")
         arrays, counts = _trainer_sets(problems)
         t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
         c = {name: _i32_vector(v) for name, v in counts.items()}
-        self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], t["labels"],
-                     c["num_attrs"], c["num_labels"], t["state_fid"], t["trans_fid"], c["num_features"])
+        vt, _keep = self._value_table(values, [int(np.asarray(p[2]).size) for p in problems])
+        head = (int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"])
+        tail = (t["labels"], c["num_attrs"], c["num_labels"], t["state_fid"], t["trans_fid"], c["num_features"])
+        if vt is None:
+            self._create(*head, *tail)
+        else:
+            self._create(*head, vt, *tail, entry="create_valued")
         self.num_features = self._features = counts["num_features"]
 
     def num_sequences(self, k: int) -> int:

@@ -96,7 +96,7 @@ int check_device(int32_t device) {
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 320; }
+GECCO_API int gecco_crf_version(void) { return 330; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -733,6 +733,214 @@ GECCO_API int gecco_crf_viterbi(const gecco_crf_model *m, int32_t device, const 
     GECCO_GUARD_END
 }
 
+// ---- real-valued attributes (ABI 2.13.0): the one-shots with a value per attribute entry ---------------------------
+namespace {
+// What a valued one-shot has on the device: one plan over the whole batch, forced onto the any-L kernels, and one block
+// with the rebased row pointers, the attribute ids, their values and the outputs.
+struct ValuedBatch {
+    Plan plan;
+    char *d = nullptr;
+    int64_t n = 0;  // genes
+    const int32_t *d_gene_ptr = nullptr, *d_attr_id = nullptr;
+    ~ValuedBatch() {
+        if (d) (void)hipFree(d);
+    }
+};
+
+// The host checks of every valued one-shot (before any device work), the plan, and the upload.  out_bytes[i] > 0: output i
+// gets a part of the block, at d + out_off[i].  Returns with vb.n == 0 for a batch without genes (nothing to run).
+int valued_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                const int32_t *attr_id, const double *attr_value, int32_t window, int32_t step, int32_t pad, bool windowed,
+                const size_t per_gene[2], size_t per_contig, ValuedBatch &vb, size_t out_off[3]) {
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) {
+        set_error("bad contig_ptr");
+        return GECCO_CRF_EINVAL;
+    }
+    const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
+    if (n > 0 && !gene_ptr) {
+        set_error("null buffer");
+        return GECCO_CRF_EINVAL;
+    }
+    const int32_t *gp = n > 0 ? gene_ptr + contig_ptr[0] : nullptr;
+    const int64_t a0 = n > 0 ? gp[0] : 0, nnz = n > 0 ? int64_t(gp[n]) - a0 : 0;
+    if (nnz < 0 || (nnz > 0 && !attr_id)) {
+        set_error("bad gene_ptr");
+        return GECCO_CRF_EINVAL;
+    }
+    if (nnz > 0 && !attr_value) {
+        set_error("null attr_value with attribute entries (the unvalued entry takes attributes without values)");
+        return GECCO_CRF_EINVAL;
+    }
+    double vmax = 0.0;
+    for (int64_t k = 0; k < nnz; ++k) {
+        const double v = attr_value[a0 + k];
+        if (!std::isfinite(v)) {
+            set_error("attribute value " + std::to_string(a0 + k) + " is not finite (NaN or infinite)");
+            return GECCO_CRF_EINVAL;
+        }
+        vmax = std::max(vmax, std::fabs(v));
+    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    vb.plan.valued = true;
+    vb.plan.windowed_use = windowed;
+    if ((rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, vb.plan))) return rc;
+    if (vb.plan.n_genes == 0) return GECCO_CRF_OK;
+    const size_t b_gp = size_t(n + 1) * 4, b_at = size_t(nnz ? nnz : 1) * 4, b_val = size_t(nnz ? nnz : 1) * 8;
+    Carver blk;
+    const size_t o_gp = blk.take(b_gp), o_at = blk.take(b_at), o_val = blk.take(b_val);
+    out_off[0] = blk.take(per_gene[0] * size_t(n) + 8);
+    out_off[1] = blk.take(per_gene[1] * size_t(n) + 8);
+    out_off[2] = blk.take(per_contig * size_t(n_contigs) + 8);
+    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&vb.d), blk.off), "hipMalloc batch"))) return rc;
+    // (gene_ptr may carry any base offset: the row pointers are rebased on the host, ids and values go up from that base)
+    std::vector<int32_t> rows(size_t(n) + 1);
+    for (int64_t i = 0; i <= n; ++i) rows[size_t(i)] = int32_t(gp[i] - a0);
+    rc = check_hip(hipMemcpy(vb.d + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
+    if (!rc && nnz) rc = check_hip(hipMemcpy(vb.d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
+    if (!rc && nnz) rc = check_hip(hipMemcpy(vb.d + o_val, attr_value + a0, size_t(nnz) * 8, hipMemcpyHostToDevice), "upload attr_value");
+    if (rc) return rc;
+    vb.n = n;
+    vb.d_gene_ptr = reinterpret_cast<const int32_t *>(vb.d + o_gp);
+    vb.d_attr_id = reinterpret_cast<const int32_t *>(vb.d + o_at);
+    vb.plan.d_attr_value = reinterpret_cast<const double *>(vb.d + o_val);
+    vb.plan.vmax_abs = vmax;
+    return GECCO_CRF_OK;
+}
+
+int valued_fetch(int rc, void *dst, const char *src, size_t bytes, const char *what) {
+    if (rc || !dst || !bytes) return rc;
+    return check_hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), what);
+}
+}  // namespace
+
+GECCO_API int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                  int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                  const double *attr_value, int32_t window, int32_t step, int32_t label,
+                                                  int32_t pad, double *p_out) {
+    if (!m) return GECCO_CRF_EINVAL;
+    if (window <= 0) {
+        set_error("Window size must be strictly positive");
+        return GECCO_CRF_EINVAL;
+    }
+    if (step <= 0 || step > window) {
+        set_error("Window step must be strictly positive and under `window_size`");
+        return GECCO_CRF_EINVAL;
+    }
+    if (label < 0 || label >= m->m.L) {
+        set_error("label out of range");
+        return GECCO_CRF_EINVAL;
+    }
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0] && !p_out) {
+        set_error("null buffer");
+        return GECCO_CRF_EINVAL;
+    }
+    ValuedBatch vb;
+    const size_t per_gene[2] = {8, 0};
+    size_t off[3];
+    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, window, step, pad, true, per_gene, 0, vb, off);
+    if (rc || vb.n == 0) return rc;
+    rc = plan_run_windowed(vb.plan, vb.d_gene_ptr, vb.d_attr_id, label, reinterpret_cast<double *>(vb.d + off[0]), nullptr);
+    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "windowed marginals");
+    return valued_fetch(rc, p_out, vb.d + off[0], size_t(vb.n) * 8, "download p");
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_windowed_marginals_all_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                      int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                      const double *attr_value, int32_t window, int32_t step,
+                                                      int32_t background, int32_t pad, double *p_all, double *p_any) {
+    if (!m) return GECCO_CRF_EINVAL;
+    if (window <= 0) {
+        set_error("Window size must be strictly positive");
+        return GECCO_CRF_EINVAL;
+    }
+    if (step <= 0 || step > window) {
+        set_error("Window step must be strictly positive and under `window_size`");
+        return GECCO_CRF_EINVAL;
+    }
+    if (background < -1 || background >= m->m.L) {
+        set_error("background label out of range");
+        return GECCO_CRF_EINVAL;
+    }
+    if ((background < 0) != (p_any == nullptr)) {
+        set_error(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
+        return GECCO_CRF_EINVAL;
+    }
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0] && !p_all) {
+        set_error("null buffer");
+        return GECCO_CRF_EINVAL;
+    }
+    ValuedBatch vb;
+    const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 8};
+    size_t off[3];
+    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, window, step, pad, true, per_gene, 0, vb, off);
+    if (rc || vb.n == 0) return rc;
+    rc = plan_run_windowed_all(vb.plan, vb.d_gene_ptr, vb.d_attr_id, background, reinterpret_cast<double *>(vb.d + off[0]),
+                               p_any ? reinterpret_cast<double *>(vb.d + off[1]) : nullptr, nullptr);
+    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "windowed marginals");
+    rc = valued_fetch(rc, p_all, vb.d + off[0], size_t(vb.n) * L * 8, "download p_all");
+    return valued_fetch(rc, p_any, vb.d + off[1], size_t(vb.n) * 8, "download p_any");
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_marginals_full_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                              int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                              const double *attr_value, double *marg, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    if (!marg && !lognorm) return GECCO_CRF_OK;
+    ValuedBatch vb;
+    const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 0};
+    size_t off[3];
+    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, 1, 1, 1, false, per_gene, 8, vb, off);
+    if (rc || vb.n == 0) {
+        for (int32_t c = 0; !rc && lognorm && c < n_contigs; ++c) lognorm[c] = 0.0;  // (contigs without genes: log Z = 0)
+        return rc;
+    }
+    // (the device always writes both; the caller's missing buffer is simply not fetched)
+    rc = plan_run_marginals_full(vb.plan, vb.d_gene_ptr, vb.d_attr_id, reinterpret_cast<double *>(vb.d + off[0]),
+                                 reinterpret_cast<double *>(vb.d + off[2]), nullptr);
+    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "marginals");
+    rc = valued_fetch(rc, marg, vb.d + off[0], size_t(vb.n) * L * 8, "download marginals");
+    return valued_fetch(rc, lognorm, vb.d + off[2], size_t(n_contigs) * 8, "download lognorm");
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_viterbi_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                       const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                       int8_t *y_out, double *score) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    if (!y_out) {
+        if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0]) {
+            set_error("null buffer");
+            return GECCO_CRF_EINVAL;
+        }
+        return GECCO_CRF_OK;
+    }
+    ValuedBatch vb;
+    const size_t per_gene[2] = {1, 0};
+    size_t off[3];
+    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, 1, 1, 1, false, per_gene, 8, vb, off);
+    if (rc || vb.n == 0) {
+        for (int32_t c = 0; !rc && score && c < n_contigs; ++c) score[c] = 0.0;
+        return rc;
+    }
+    rc = plan_run_viterbi(vb.plan, vb.d_gene_ptr, vb.d_attr_id, reinterpret_cast<int8_t *>(vb.d + off[0]),
+                          reinterpret_cast<double *>(vb.d + off[2]), nullptr);
+    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "viterbi");
+    rc = valued_fetch(rc, y_out, vb.d + off[0], size_t(vb.n), "download labels");
+    return valued_fetch(rc, score, vb.d + off[2], size_t(n_contigs) * 8, "download score");
+    GECCO_GUARD_END
+}
+
 namespace {
 // grow-only scratch of the stand-alone segmenter / composition calls, one set per host thread
 struct Scratch {
@@ -1150,6 +1358,29 @@ GECCO_API int gecco_crf_trainer_general_create(int32_t device, int32_t n_problem
     return rc;
     GECCO_GUARD_END
 }
+// (ABI 2.13.0) attr_value[k]: the values of problem k's attribute entries, or NULL for a problem without
+GECCO_API int gecco_crf_trainer_general_create_valued(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                      const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                      const int32_t *const *attr_id, const double *const *attr_value,
+                                                      const int32_t *const *labels, const int32_t *num_attrs,
+                                                      const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                                                      const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                                      const int32_t *num_features, gecco_crf_trainer_general **out) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    if (n_problems < 1) return fail("trainer general: at least one problem is needed");
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !attr_value || !labels || !num_attrs || !num_labels || !window ||
+        !step || !state_fid || !trans_fid || !num_features)
+        return fail("trainer general: null argument");
+    DeviceGuard guard;
+    TrainerGeneral *t = nullptr;
+    int rc = trainer_general_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
+                                    window, step, state_fid, trans_fid, num_features, &t, attr_value);
+    *out = reinterpret_cast<gecco_crf_trainer_general *>(t);
+    return rc;
+    GECCO_GUARD_END
+}
 GECCO_API int gecco_crf_trainer_general_eval(gecco_crf_trainer_general *t, const uint8_t *active, const double *const *w,
                                              double *f, double *const *g) {
     if (!t) return GECCO_CRF_EINVAL;
@@ -1191,6 +1422,28 @@ GECCO_API int gecco_crf_trainer_sequences_create(int32_t device, int32_t n_probl
     TrainerGeneral *t = nullptr;
     int rc = trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
                                       state_fid, trans_fid, num_features, &t);
+    *out = reinterpret_cast<gecco_crf_trainer_sequences *>(t);
+    return rc;
+    GECCO_GUARD_END
+}
+GECCO_API int gecco_crf_trainer_sequences_create_valued(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                        const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                        const int32_t *const *attr_id, const double *const *attr_value,
+                                                        const int32_t *const *labels, const int32_t *num_attrs,
+                                                        const int32_t *num_labels, const int32_t *const *state_fid,
+                                                        const int32_t *const *trans_fid, const int32_t *num_features,
+                                                        gecco_crf_trainer_sequences **out) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    if (n_problems < 1) return fail("trainer sequences: at least one problem is needed");
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !attr_value || !labels || !num_attrs || !num_labels || !state_fid ||
+        !trans_fid || !num_features)
+        return fail("trainer sequences: null argument");
+    DeviceGuard guard;
+    TrainerGeneral *t = nullptr;
+    int rc = trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
+                                      state_fid, trans_fid, num_features, &t, attr_value);
     *out = reinterpret_cast<gecco_crf_trainer_sequences *>(t);
     return rc;
     GECCO_GUARD_END

@@ -307,7 +307,9 @@ struct GenArgs {
     double *p_out;
     int32_t K, S, W, label;
 };
-hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream);
+// attr_value (the *_valued entries): the value of every attribute entry, parallel to a.attr_id; null = every value is 1, the
+// kernel as it was.  No other kernel reads the values (a.v_wmax then carries max|v| of the batch: crf_plan.cpp)
+hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr);
 hipError_t launch_gen_windowed(const GenArgs &a, hipStream_t stream);   // p_out must be zeroed first
 // 3 or 4 labels: one lane per window start (the two-label kernel's design); tile geometry gen_small_tile_out(W)
 constexpr int kGenTileThreads = 256;  // window starts per workgroup of every kernel with that geometry (gen_small_tile_out)

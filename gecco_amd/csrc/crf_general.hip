@@ -45,11 +45,15 @@ __device__ __forceinline__ int gl_chunk_end(const GenArgs &a, long long ci) {
 
 // ---- row S: state scores of every gene (CSR order, bit-identical to sequential addition) ----
 // state[g][y] = sum_a w[a][y]; E[g][y] = exp(state - max_y); smax[g] = max_y state.
-template <int LP>
+// kValued (the *_valued entries): state[g][y] = sum_a v[a] * w[a][y], attr_value parallel to attr_id, every term
+// added as fma(v, w, acc) in CSR order -- the one multiply-add form of every valued kernel, so that v = 1.0 gives the unvalued
+// sum's bits (fma(1, w, acc) rounds acc + w once).  The unvalued instantiation is the kernel as it was (attr_value, last,
+// is not read there).
+template <int LP, bool kValued>
 __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene_ptr, const int32_t *__restrict__ attr_id,
                                                 const double *__restrict__ wtab, int L, int A, int n_genes,
                                                 double *__restrict__ state, double *__restrict__ E,
-                                                double *__restrict__ smax) {
+                                                double *__restrict__ smax, const double *__restrict__ attr_value) {
     const int j = threadIdx.x & (LP - 1);
     const long long g = (static_cast<long long>(blockIdx.x) * kGT + threadIdx.x) / LP;
     if (g >= n_genes) return;
@@ -57,8 +61,13 @@ __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene
     const int jj = j < L ? j : 0;
     double acc = 0.0;
     for (int a = lo; a < hi; ++a) {
-        const int id = attr_id[a];  // ids outside the model's dictionary are unknown attributes: no weight
-        if (unsigned(id) < unsigned(A)) acc += wtab[static_cast<size_t>(id) * L + jj];
+        const int id = attr_id[a];  // ids outside the model's dictionary are unknown attributes: no weight, whatever their value
+        if (unsigned(id) < unsigned(A)) {
+            if constexpr (kValued)
+                acc = fma(attr_value[a], wtab[static_cast<size_t>(id) * L + jj], acc);
+            else
+                acc += wtab[static_cast<size_t>(id) * L + jj];
+        }
     }
     const double m = group_max<LP>(j < L ? acc : -DBL_MAX);
     if (j < L) {
@@ -1559,14 +1568,19 @@ hipError_t launch_chunked(int what, const GenArgs &a, hipStream_t stream) {
 }
 
 template <int LP>
-hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream) {
+hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr) {
     constexpr int G = kGT / LP;
     auto blocks = [](long long items, int per) { return dim3(unsigned((items + per - 1) / per)); };
     switch (what) {
     case 0:  // state scores
-        if (a.n_genes > 0)
-            hipLaunchKernelGGL(gl_state<LP>, blocks(a.n_genes, G), dim3(kGT), 0, stream, a.gene_ptr, a.attr_id, a.wtab, a.L,
-                               a.A, a.n_genes, a.state, a.E, a.smax);
+        if (a.n_genes > 0) {  // (attr_value: the same for every gene of the launch)
+            if (attr_value)
+                hipLaunchKernelGGL((gl_state<LP, true>), blocks(a.n_genes, G), dim3(kGT), 0, stream, a.gene_ptr, a.attr_id,
+                                   a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value);
+            else
+                hipLaunchKernelGGL((gl_state<LP, false>), blocks(a.n_genes, G), dim3(kGT), 0, stream, a.gene_ptr, a.attr_id,
+                                   a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value);
+        }
         break;
     case 1: {
         const size_t lds = (size_t(G) * a.W * (LP + 1) + kGT) * sizeof(double);
@@ -1588,7 +1602,7 @@ hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream) {
+hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr) {
     if (a.L <= 0 || a.L > kGenMaxL) return hipErrorNotSupported;
     if ((what == 2 || what == 3) && a.n_chunks > 0) {  // long contigs in the batch: chunked recursions
         if (a.L <= 2) return launch_chunked<2>(what, a, stream);
@@ -1597,16 +1611,18 @@ hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream) {
         if (a.L <= 16) return launch_chunked<16>(what, a, stream);
         return launch_chunked<32>(what, a, stream);
     }
-    if (a.L <= 2) return launch_lp<2>(what, a, stream);
-    if (a.L <= 4) return launch_lp<4>(what, a, stream);
-    if (a.L <= 8) return launch_lp<8>(what, a, stream);
-    if (a.L <= 16) return launch_lp<16>(what, a, stream);
-    return launch_lp<32>(what, a, stream);
+    if (a.L <= 2) return launch_lp<2>(what, a, stream, attr_value);
+    if (a.L <= 4) return launch_lp<4>(what, a, stream, attr_value);
+    if (a.L <= 8) return launch_lp<8>(what, a, stream, attr_value);
+    if (a.L <= 16) return launch_lp<16>(what, a, stream, attr_value);
+    return launch_lp<32>(what, a, stream, attr_value);
 }
 
 }  // namespace
 
-hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream) { return launch_any(0, a, stream); }
+hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value) {
+    return launch_any(0, a, stream, attr_value);
+}
 int gen_small_tile_out(int W) { return kSmallNT - (W - 1); }
 
 // the lane-per-window kernel takes 3 to 8 labels (2 too: tests), windows of up to 32 genes (20 beyond 4 labels: W doubles of

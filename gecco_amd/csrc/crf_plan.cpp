@@ -368,7 +368,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     }
     {
         const char *env = std::getenv("GECCO_CRF_FORCE_GENERAL");
-        p.general = m.L != 2 || (env && env[0] == '1');
+        p.general = m.L != 2 || (env && env[0] == '1') || p.valued;  // (valued state scores exist in gl_state alone)
     }
     p.fast_ok = (!p.general && W <= kWinMaxW && rescale_mask_for(m, W, &p.rescale_mask));
     {
@@ -378,7 +378,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
         }();
         // (the environment switch is for windowed marginals of 2-label models: a Viterbi-only or whole-contig layout, or another
         // label count, keeps its kernels; an explicit request -- reference_bits -- for an unsupported shape is an error)
-        p.reference_now = p.reference_bits || (env_reference && p.windowed_use && m.L == 2 && reference_bits_ok(m.L, W));
+        p.reference_now = !p.valued && (p.reference_bits || (env_reference && p.windowed_use && m.L == 2 && reference_bits_ok(m.L, W)));
         if (p.reference_now) {
             if (!reference_bits_ok(m.L, W)) {
                 set_error("reference-bits mode serves 2-label models and windows of at most 32 genes");
@@ -587,7 +587,11 @@ int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, 
     a = GenArgs{};
     a.vit_stats = reinterpret_cast<uint32_t *>(w);
     a.fix_flag = reinterpret_cast<uint8_t *>(w + 16);
-    a.v_wmax = p.tables_model->wmax_abs;
+    // the margin's bound on a partial sum of state scores is nnz * max|v| * max|w| with values.  Nothing else
+    // on this route reads the state weights' size: gen_small_ok / all_small_ok (gl_windowed_small, gl_windowed_mfma, gl_all_small)
+    // and rows_rescale_period below guard the spread of the TRANSITIONS over un-normalised steps, and every sum-product kernel
+    // takes the states as exp(state - max state) in (0, 1], whatever the states' size
+    a.v_wmax = p.valued ? p.tables_model->wmax_abs * p.vmax_abs : p.tables_model->wmax_abs;
     a.v_tmax = p.tables_model->tmax_abs;
     a.gene_ptr = d_gene_ptr;
     a.attr_id = d_attr_id;
@@ -757,7 +761,7 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const int32_t *d_gene_ptr, con
     g.score = d_score;
     r.clear(g);
     g.wave_tmax = tail_chunked ? wave_tmax : 0;
-    if ((rc = check_hip(launch_gen_state(g, stream), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(g, stream, p.valued ? p.d_attr_value : nullptr), "state score launch"))) return rc;
     if (!wave) return check_hip(r.chunked(g, stream), r.what);
     if (!tail_chunked || g.n_chunks <= 0) return check_hip(r.wave(g, stream), r.what);
     // the long tail (chunked kernels: short in work, long in dependent launches) NEXT TO the waves of the other contigs:
@@ -826,7 +830,7 @@ int run_windowed_general(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_at
     if ((rc = start_p_out(p, d_p_out, true, stream))) return rc;
     double *keep_state = a.state;
     a.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(a, stream), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(a, stream, p.valued ? p.d_attr_value : nullptr), "state score launch"))) return rc;
     a.state = keep_state;
     if (p.gen_small)
         return check_hip(launch_gen_windowed_small(a, p.model->trans.data(), p.d_tile_desc, p.ntiles, stream), "windowed launch");
@@ -983,7 +987,7 @@ int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_a
     GenArgs g;
     if ((rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g))) return rc;
     g.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(g, stream), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(g, stream, p.valued ? p.d_attr_value : nullptr), "state score launch"))) return rc;
     AllArgs a{};
     a.E = g.E;
     a.exp_trans = g.exp_trans;

@@ -137,6 +137,13 @@ struct Plan {
     bool windowed_use = true;  // the owner runs windowed marginals on this layout (batch driver: false for Viterbi-only and
                                // whole-contig-marginal requests): the environment switch applies to such layouts only
     bool reference_now = false;  // (this layout runs in reference-bits mode: reference_bits, or the environment)
+    // Real-valued attributes (the *_valued one-shots).  `valued` is set by the owner before plan_build: the layout
+    // takes the any-L kernels at every label count, 2 included, and reference-bits mode does not apply.  d_attr_value (parallel to
+    // the d_attr_id of the run calls) and vmax_abs (max |value| of the batch, which scales the Viterbi margin's bound on a state
+    // score) are set before a run call.
+    bool valued = false;
+    const double *d_attr_value = nullptr;
+    double vmax_abs = 1.0;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_windowed_all.hip): the tile table of the lane-per-window tier when the plan's own

@@ -452,7 +452,7 @@ int fail(const std::string &msg) {
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
-                  HostProblem *hp, bool whole_sequences) {
+                  HostProblem *hp, bool whole_sequences, const double *attr_value) {
     if (!seq_ptr || n_seqs < 0 || !state_fid || !trans_fid) return fail("trainer: null argument");
     if (max_labels == 2 && num_labels != 2) {
         set_error("trainer: only 2-label models can be trained (GECCO's protein and domain modes are binary)");
@@ -492,6 +492,9 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
     if (nnz > 0 && !attr_id) return fail("trainer: null argument");
     for (int32_t k = 0; k < nnz; ++k)
         if (attr_id[k] < 0 || attr_id[k] >= num_attrs) return fail("trainer: attribute id out of range");
+    for (int32_t k = 0; attr_value && k < nnz; ++k)
+        if (!std::isfinite(attr_value[k]))
+            return fail("trainer: attribute value " + std::to_string(k) + " is not finite (NaN or infinite)");
     for (int64_t k = 0; k < int64_t(num_attrs) * L; ++k)
         if (state_fid[k] < -1 || state_fid[k] >= num_features) return fail("trainer: state feature id out of range");
     for (int k = 0; k < L * L; ++k)
@@ -544,7 +547,8 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
     for (int32_t i = 0; i < n_items; ++i)
         for (int32_t k = item_ptr[i]; k < item_ptr[i + 1]; ++k) {
             const int32_t fid = hp->state_fid[size_t(attr_id[k]) * L + labels[i]];
-            if (fid >= 0) hp->empirical[fid] += iw_cnt[i];
+            // (with values: value x coverage, in this one order; a value of 1 adds the integer it always added)
+            if (fid >= 0) hp->empirical[fid] += attr_value ? attr_value[k] * iw_cnt[i] : iw_cnt[i];
         }
     for (size_t q = 0; q < win_start.size(); ++q)
         for (int32_t i0 = win_start[q], j = 1; j < (whole_sequences ? hp->win_len[q] : window); ++j) {
@@ -562,6 +566,12 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
         std::vector<int32_t> fill(attr_ptr.begin(), attr_ptr.end() - 1);
         for (int32_t i = 0; i < n_items; ++i)
             for (int32_t k = item_ptr[i]; k < item_ptr[i + 1]; ++k) attr_items[fill[attr_id[k]]++] = i;
+    }
+    if (attr_value) {  // the transpose carries the value beside the item index
+        hp->attr_value.assign(attr_value, attr_value + nnz);
+        hp->attr_item_value.assign(static_cast<size_t>(nnz), 0.0);
+        std::vector<int32_t> fill(attr_ptr.begin(), attr_ptr.end() - 1);
+        for (int32_t k = 0; k < nnz; ++k) hp->attr_item_value[fill[attr_id[k]]++] = attr_value[k];
     }
     hp->item_ptr.assign(1, 0);
     if (n_items > 0) {

@@ -21,17 +21,21 @@ struct HostProblem {
     std::vector<double> empirical;              // [K] observed feature counts over all windows
     std::vector<int32_t> item_ptr, attr_id, label, win_start, iw_first, iw_cnt, iw_off, attr_ptr, attr_items;
     std::vector<int32_t> win_len;  // whole-sequence instances only: the items of instance q (win_start[q] is its first)
+    // problems with attribute values only: the values parallel to attr_id, and parallel to attr_items
+    std::vector<double> attr_value, attr_item_value;
 };
 
 // Checks one problem (the lone trainer's checks and messages) and builds its windows, coverage, empirical counts and
 // attribute -> items transpose.  max_labels = 2: the 2-label families (any other num_labels is "only 2-label models");
 // larger: the general family, num_labels in [2, max_labels] and labels in [0, num_labels).  whole_sequences: the
 // instances are the sequences themselves (window and step are not read; a sequence without items is refused), listed in
-// win_start / win_len longest first, ties by index; iw_first / iw_off are not built.
+// win_start / win_len longest first, ties by index; iw_first / iw_off are not built.  attr_value: null, or the value of every
+// attribute entry (parallel to attr_id; a NaN or infinite one is refused): the empirical count of a state feature is then the
+// sum of value x coverage over its entries, in item and CSR order, and attr_value / attr_item_value are built.
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
-                  HostProblem *hp, bool whole_sequences = false);
+                  HostProblem *hp, bool whole_sequences = false, const double *attr_value = nullptr);
 
 // Sets as gecco_crf_trainer_grid_create takes them (one entry per set in the set arrays, each with its own window and
 // step), problem k on set problem_set[k], or on set k where problem_set is NULL (then n_problems == n_sets).
@@ -52,12 +56,13 @@ int64_t trainer_scratch_bytes(const Trainer *t, int32_t k);
 void trainer_destroy(Trainer *t);
 
 // The general-label family (gecco_crf_trainer_general_*, crf_train_general.hip): the same objective for 2 to 32 labels,
-// problem k with its own label count, window and step.  Errors carry "trainer general: problem k: ".
+// problem k with its own label count, window and step.  Errors carry "trainer general: problem k: ".  attr_value (the
+// *_create_valued entries): null, or per problem the values of its attribute entries, entry k null for a problem without.
 int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                            const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                            const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                            const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                           TrainerGeneral **out);
+                           TrainerGeneral **out, const double *const *attr_value = nullptr);
 int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g);
 int32_t trainer_general_num_problems(const TrainerGeneral *t);
 int64_t trainer_general_num_windows(const TrainerGeneral *t, int32_t k);
@@ -71,6 +76,7 @@ void trainer_general_destroy(TrainerGeneral *t);
 int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                              const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                              const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
-                             const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out);
+                             const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out,
+                             const double *const *attr_value = nullptr);
 
 }  // namespace gecco

@@ -58,12 +58,22 @@ struct GenProb {
     int32_t n_items, A, L, W, step, n_blocks;
 };
 
-__global__ void __launch_bounds__(kTrainGenThreads) gen_item_scores(GenProb P) {
+// kValued (the *_create_valued problems that carry values): s[i][y] = sum of v * w over the item's attributes,
+// attr_value parallel to attr_id, every term added as fma(v, w, acc) in CSR order.  That is the one multiply-add form of every
+// valued kernel (gl_state and gen_attr_counts too): fma(1, w, acc) rounds acc + w once, so a problem whose values are all 1.0
+// has the unvalued problem's bits.  The unvalued instantiation is the kernel as it was (attr_value, last, is not read there).
+template <bool kValued>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_item_scores(GenProb P, const double *attr_value) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * kTrainGenThreads + threadIdx.x;
     if (idx >= static_cast<int64_t>(P.n_items) * P.L) return;
     const int32_t i = static_cast<int32_t>(idx / P.L), y = static_cast<int32_t>(idx % P.L);
     double s = 0.0;
-    for (int32_t k = P.item_ptr[i]; k < P.item_ptr[i + 1]; ++k) s += P.wstate[static_cast<int64_t>(P.attr_id[k]) * P.L + y];
+    for (int32_t k = P.item_ptr[i]; k < P.item_ptr[i + 1]; ++k) {
+        if constexpr (kValued)
+            s = fma(attr_value[k], P.wstate[static_cast<int64_t>(P.attr_id[k]) * P.L + y], s);
+        else
+            s += P.wstate[static_cast<int64_t>(P.attr_id[k]) * P.L + y];
+    }
     P.score[idx] = s;
 }
 
@@ -344,15 +354,22 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_item_marginals(GenProb P
 }
 
 // Expected state counts: one workgroup per attribute, as 256 / G rows of G labels.  Row r sums the items r, r + rows, ...
-// of the attribute's list, then the rows are summed by a tree.
-__global__ void __launch_bounds__(kTrainGenThreads) gen_attr_counts(GenProb P, int32_t G) {
+// of the attribute's list, then the rows are summed by a tree.  kValued: every item's marginal times the value the attribute has
+// on that item, attr_item_value parallel to attr_items (the transpose carries the value beside the item index), added as
+// fma(v, marginal, acc) in the same order.
+template <bool kValued>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_attr_counts(GenProb P, int32_t G, const double *attr_item_value) {
     __shared__ double sh[kTrainGenThreads];
     const int32_t a = static_cast<int32_t>(blockIdx.x);
     const int32_t y = threadIdx.x % G, r = threadIdx.x / G, rows = kTrainGenThreads / G;
     double acc = 0.0;
     if (y < P.L)
-        for (int32_t k = P.attr_ptr[a] + r; k < P.attr_ptr[a + 1]; k += rows)
-            acc += P.item_marg[static_cast<int64_t>(P.attr_items[k]) * P.L + y];
+        for (int32_t k = P.attr_ptr[a] + r; k < P.attr_ptr[a + 1]; k += rows) {
+            if constexpr (kValued)
+                acc = fma(attr_item_value[k], P.item_marg[static_cast<int64_t>(P.attr_items[k]) * P.L + y], acc);
+            else
+                acc += P.item_marg[static_cast<int64_t>(P.attr_items[k]) * P.L + y];
+        }
     sh[threadIdx.x] = acc;
     __syncthreads();
     for (int h = kTrainGenThreads / 2; h >= G; h >>= 1) {
@@ -423,6 +440,9 @@ struct TrainerGeneral {
         int64_t n_win;
         int64_t item0, iptr0, nnz0, win0, aptr0;  // the problem's slices of the set arrays
         int64_t in0, out0, sc0, scratch;          // weights in the upload, outputs in the download, scratch (doubles)
+        // a problem with values: its slice of d_attr_value (parallel to attr_id); the values in transposed order (parallel to
+        // attr_items) are the last nnz doubles of its scratch, written once by create.  val0 < 0: no values
+        int64_t val0 = -1, nnz = 0;
         std::vector<int32_t> state_fid, trans_fid;
         std::vector<double> empirical;
     };
@@ -431,7 +451,7 @@ struct TrainerGeneral {
     hipStream_t stream = nullptr;
     int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr, *d_win_len = nullptr;
     int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr, *d_attr_ptr = nullptr, *d_attr_items = nullptr;
-    double *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    double *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_attr_value = nullptr;
 
     ~TrainerGeneral() {
         if (!stream) return;  // refused before the device was checked: nothing to free, and no HIP call
@@ -440,7 +460,7 @@ struct TrainerGeneral {
         (void)hipSetDevice(device);
         for (void *p : {(void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start, (void *)d_win_len,
                         (void *)d_iw_first, (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items,
-                        (void *)d_in, (void *)d_out, (void *)d_scratch})
+                        (void *)d_in, (void *)d_out, (void *)d_scratch, (void *)d_attr_value})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
         if (restore && prev >= 0) (void)hipSetDevice(prev);
@@ -449,24 +469,27 @@ struct TrainerGeneral {
 
 namespace {
 
-// Both families' create: window == nullptr is the whole-sequence family.
+// Both families' create: window == nullptr is the whole-sequence family.  attr_value: null, or per problem the values of its
+// attribute entries (entry k null: problem k has none, and runs the unvalued kernels).
 int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                          const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                          const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                          const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                         TrainerGeneral **out) {
+                         const double *const *attr_value, TrainerGeneral **out) {
     auto t = std::make_unique<TrainerGeneral>();
     t->device = device;
     const bool whole = t->whole = window == nullptr;
     const std::string family = whole ? "trainer sequences: problem " : "trainer general: problem ";
     std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, win_len_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c,
         attr_items_c;
+    std::vector<double> attr_value_c;
+    std::vector<std::vector<double>> transposed(static_cast<size_t>(n_problems));  // (attr_item_value of the valued problems)
     int64_t in_total = 0, out_total = 0, scratch_total = 0;
     for (int32_t k = 0; k < n_problems; ++k) {
         HostProblem hp;
         int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
                                whole ? 0 : window[k], whole ? 0 : step[k], state_fid[k], trans_fid[k], num_features[k],
-                               kTrainGenMaxL, &hp, whole);
+                               kTrainGenMaxL, &hp, whole, attr_value ? attr_value[k] : nullptr);
         if (rc) {
             set_error(family + std::to_string(k) + ": " + last_error());
             return rc;
@@ -487,8 +510,15 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
         p.aptr0 = int64_t(attr_ptr_c.size());
         p.in0 = in_total, p.out0 = out_total, p.sc0 = scratch_total;
         // scratch: item scores and item marginals [n_items][L], node marginals [n_win][W][L] (none for whole sequences:
-        // W = 0), blocks and slabs of (f, xi)
+        // W = 0), blocks and slabs of (f, xi); with values, one double per attribute entry (the transposed values)
         p.scratch = 2 * int64_t(p.n_items) * p.L + hp.n_win * p.W * p.L + (nb + kTrainGenReduceSlabs) * cols;
+        if (attr_value && attr_value[k]) {  // a problem with values: the transposed values behind everything else
+            p.val0 = int64_t(attr_value_c.size());
+            p.nnz = int64_t(hp.attr_value.size());
+            p.scratch += p.nnz;
+            append(attr_value_c, hp.attr_value);
+            transposed[size_t(k)] = std::move(hp.attr_item_value);
+        }
         in_total += int64_t(p.A) * p.L + int64_t(p.L) * p.L;
         out_total += cols + int64_t(p.A) * p.L;
         scratch_total += p.scratch;
@@ -538,6 +568,15 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
     if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&t->d_scratch), std::max<size_t>(size_t(scratch_total), 1) * sizeof(double)),
                         "trainer alloc")))
         return rc;
+    if ((rc = dev_upload(&t->d_attr_value, attr_value_c, "trainer upload"))) return rc;
+    for (int32_t k = 0; k < n_problems; ++k) {
+        const TrainerGeneral::Prob &p = t->probs[size_t(k)];
+        if (p.val0 < 0 || p.nnz == 0) continue;
+        if ((rc = check_hip(hipMemcpy(t->d_scratch + p.sc0 + p.scratch - p.nnz, transposed[size_t(k)].data(),
+                                      size_t(p.nnz) * sizeof(double), hipMemcpyHostToDevice),
+                            "trainer upload")))
+            return rc;
+    }
     *out = t.release();
     return GECCO_CRF_OK;
 }
@@ -548,18 +587,19 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
                            const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                            const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                            const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                           TrainerGeneral **out) {
+                           TrainerGeneral **out, const double *const *attr_value) {
     if (!window || !step) return fail("trainer general: null argument");
     return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
-                                step, state_fid, trans_fid, num_features, out);
+                                step, state_fid, trans_fid, num_features, attr_value, out);
 }
 
 int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                              const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                              const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
-                             const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out) {
+                             const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out,
+                             const double *const *attr_value) {
     return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, nullptr,
-                                nullptr, state_fid, trans_fid, num_features, out);
+                                nullptr, state_fid, trans_fid, num_features, attr_value, out);
 }
 
 int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
@@ -618,7 +658,14 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             a.n_items = p.n_items, a.A = p.A, a.L = p.L, a.W = p.W, a.step = p.step, a.n_blocks = p.n_blocks;
             const unsigned nb_items = unsigned(blocks_of(nl, kTrainGenThreads));
             const int G = group_of(p.L);
-            gen_item_scores<<<nb_items, kTrainGenThreads, 0, st>>>(a);
+            // (a problem has values or has none: the branch is the same for every thread of its launches)
+            const bool valued = p.val0 >= 0;
+            const double *attr_value = valued ? t->d_attr_value + p.val0 : nullptr;
+            const double *attr_item_value = valued ? t->d_scratch + p.sc0 + p.scratch - p.nnz : nullptr;
+            if (valued)
+                gen_item_scores<true><<<nb_items, kTrainGenThreads, 0, st>>>(a, attr_value);
+            else
+                gen_item_scores<false><<<nb_items, kTrainGenThreads, 0, st>>>(a, nullptr);
             if (t->whole) {
                 switch (G) {
                     case 2: gen_sequences<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
@@ -637,7 +684,10 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
                 }
                 gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
             }
-            gen_attr_counts<<<unsigned(p.A), kTrainGenThreads, 0, st>>>(a, G);
+            if (valued)
+                gen_attr_counts<true><<<unsigned(p.A), kTrainGenThreads, 0, st>>>(a, G, attr_item_value);
+            else
+                gen_attr_counts<false><<<unsigned(p.A), kTrainGenThreads, 0, st>>>(a, G, nullptr);
             gen_reduce_blocks<<<kTrainGenReduceSlabs, kTrainGenThreads, 0, st>>>(a);
             gen_reduce_final<<<1, kTrainGenThreads, 0, st>>>(a);
         }

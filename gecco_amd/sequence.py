@@ -1,9 +1,11 @@
-"""A linear-chain CRF over sequences of items with string attributes and 2 to 32 string labels, trained and applied on
+"""A linear-chain CRF over sequences of items with string attributes, plain or with a real value each (CRFsuite's
+name:value items, given as dicts as ``sklearn_crfsuite`` takes them), and 2 to 32 string labels, trained and applied on
 the device: the shape of ``sklearn_crfsuite.CRF`` over this package's training stack (``train``) and inference entry
 points (``_native.Model``).  Training instances are the sliding windows of every sequence, as everywhere in GECCO, or
 with ``window_size=None`` the whole sequences, as CRFsuite trains outside GECCO: the objective ``predict`` and
 ``predict_marginals`` decode with.
 """
+from collections.abc import Mapping
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -13,14 +15,25 @@ from . import train
 __all__ = ["SequenceCRF"]
 
 
-def _items(xseq: Iterable[Iterable[str]]) -> List[List[str]]:
-    """The attribute names of every item, duplicates collapsed (the first occurrence is kept)."""
-    out = []
+def _items(xseq) -> Tuple[List[List[str]], Optional[List[List[float]]]]:
+    """The attributes of every item of a sequence as ``(names, values)``: ``values`` is None when every item is a plain
+    iterable of names, whose duplicates are collapsed (the first occurrence is kept) -- the unvalued path.  An item that is
+    a dict (python-crfsuite's conversion, ``train.item_attributes``) or a list of ``(name, value)`` pairs gives every item
+    of the sequence values, 1.0 for the attributes of its plain items."""
+    names, values = [], []
     for item in xseq:
         if isinstance(item, str):
             raise ValueError("an item is an iterable of attribute names, not a string")
-        out.append(list(dict.fromkeys(str(name) for name in item)))
-    return out
+        if not isinstance(item, Mapping):
+            item = list(item)
+            if not any(isinstance(e, tuple) for e in item):
+                item = list(dict.fromkeys(str(name) for name in item))  # (plain names, as ever)
+        nm, vals = train.item_attributes(item)
+        names.append(nm)
+        values.append(vals)
+    if all(v is None for v in values):
+        return names, None
+    return names, [[1.0] * len(nm) if v is None else v for nm, v in zip(names, values)]
 
 
 class SequenceCRF:
@@ -50,7 +63,12 @@ class SequenceCRF:
 
     # ---- training
     def fit(self, X: Sequence[Iterable[Iterable[str]]], y: Sequence[Sequence[str]]) -> "SequenceCRF":
-        seqs = [_items(xseq) for xseq in X]
+        """``X``: sequences of items; an item is an iterable of attribute names, or a dict / a list of ``(name, value)``
+        pairs (``train.item_attributes``), as in every prediction method."""
+        seqs = []
+        for xseq in X:  # (a sequence with values goes to the training set as (name, value) pairs, one without as names)
+            names, values = _items(xseq)
+            seqs.append(names if values is None else [list(zip(nm, v)) for nm, v in zip(names, values)])
         labs = [[str(lab) for lab in yseq] for yseq in y]
         if len(seqs) != len(labs):
             raise ValueError(f"X holds {len(seqs)} sequences and y {len(labs)}")
@@ -110,16 +128,23 @@ class SequenceCRF:
             return cls.from_bytes(fh.read(), window_size, window_step, device, **options)
 
     # ---- prediction
-    def _pack(self, X) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """X as CSR over the model's attribute ids; names the model does not know are dropped."""
+    def _pack(self, X) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray]]:
+        """X as CSR over the model's attribute ids, and the value of every entry or None when every item of X is plain
+        names (the unvalued entries are then called); names the model does not know are dropped, with their values."""
         self._fitted()
-        seq_ptr, item_ptr, attr = [0], [0], []
-        for xseq in X:
-            for names in _items(xseq):
-                attr.extend(self._attr_index[nm] for nm in names if nm in self._attr_index)
+        seq_ptr, item_ptr, attr, vals = [0], [0], [], []
+        packed = [_items(xseq) for xseq in X]
+        valued = any(values is not None for _, values in packed)
+        for names_seq, values_seq in packed:
+            for k, names in enumerate(names_seq):
+                known = [j for j, nm in enumerate(names) if nm in self._attr_index]
+                attr.extend(self._attr_index[names[j]] for j in known)
+                if valued:
+                    vals.extend(1.0 if values_seq is None else values_seq[k][j] for j in known)
                 item_ptr.append(len(attr))
             seq_ptr.append(len(item_ptr) - 1)
-        return (np.array(seq_ptr, dtype=np.int32), np.array(item_ptr, dtype=np.int32), np.array(attr, dtype=np.int32))
+        return (np.array(seq_ptr, dtype=np.int32), np.array(item_ptr, dtype=np.int32), np.array(attr, dtype=np.int32),
+                np.array(vals, dtype=np.float64) if valued else None)
 
     @staticmethod
     def _split(values: np.ndarray, seq_ptr: np.ndarray) -> list:
@@ -127,25 +152,25 @@ class SequenceCRF:
 
     def predict(self, X) -> List[List[str]]:
         """Viterbi labels of every sequence."""
-        seq_ptr, item_ptr, attr = self._pack(X)
+        seq_ptr, item_ptr, attr, values = self._pack(X)
         if seq_ptr[-1] == 0:
             return [[] for _ in X]
-        y, _ = self._model.viterbi(seq_ptr, item_ptr, attr, device=self.device)
+        y, _ = self._model.viterbi(seq_ptr, item_ptr, attr, device=self.device, values=values)
         return [[self.classes_[k] for k in ys.tolist()] for ys in self._split(y, seq_ptr)]
 
     def predict_marginals(self, X) -> List[np.ndarray]:
         """Whole-sequence marginals: one ``[n_items, L]`` array per sequence, columns in ``classes_`` order."""
-        seq_ptr, item_ptr, attr = self._pack(X)
+        seq_ptr, item_ptr, attr, values = self._pack(X)
         if seq_ptr[-1] == 0:
             return [np.zeros((0, len(self.classes_))) for _ in X]
-        marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device)
+        marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device, values=values)
         return self._split(marg, seq_ptr)
 
     def log_likelihood(self, X, y: Sequence[Sequence[str]]) -> np.ndarray:
         """``log p(y | x)`` of every sequence under the model (CRFsuite's ``Tagger.probability`` in logs): the gold path's
-        score, gathered on the host from the weight tables, minus the log partition function of the whole-sequence
+        score, gathered on the host from the weight tables (value x weight for items with values), minus the log partition function of the whole-sequence
         marginals.  An unknown label raises ``ValueError``; an empty sequence gives 0.0."""
-        seq_ptr, item_ptr, attr = self._pack(X)
+        seq_ptr, item_ptr, attr, values = self._pack(X)
         index = {c: k for k, c in enumerate(self.classes_)}
         labs = [[str(lab) for lab in yseq] for yseq in y]
         n_seqs = len(seq_ptr) - 1
@@ -163,13 +188,13 @@ class SequenceCRF:
         lengths = np.diff(seq_ptr)
         full = np.flatnonzero(lengths > 0)  # (an empty sequence stays at 0.0 and never reaches the device)
         ptr = np.concatenate([[0], np.cumsum(lengths[full])]).astype(np.int32)
-        _, lognorm = self._model.marginals_full(ptr, item_ptr, attr, device=self.device)
+        _, lognorm = self._model.marginals_full(ptr, item_ptr, attr, device=self.device, values=values)
         state, _ = self._model.state_weights()
         trans, _ = self._model.trans_weights()
         yy = np.array([index[lab] for ls in labs for lab in ls], dtype=np.int64)
         owner = np.repeat(np.arange(len(yy)), np.diff(item_ptr))
         score = np.zeros(len(yy))  # per item: its state score under its label, and the transition into it
-        np.add.at(score, owner, state[attr, yy[owner]])
+        np.add.at(score, owner, state[attr, yy[owner]] if values is None else values * state[attr, yy[owner]])
         inner = np.ones(len(yy), dtype=bool)
         inner[ptr[:-1]] = False  # (the first item of a sequence has no predecessor)
         score[inner] += trans[yy[np.flatnonzero(inner) - 1], yy[inner]]
@@ -185,13 +210,14 @@ class SequenceCRF:
         """GECCO's windowed probability of ``label``: per item the maximum, over the windows covering it, of the
         label's marginal inside the window (``pad``: a sequence shorter than the window is one window)."""
         self._windowed()
-        seq_ptr, item_ptr, attr = self._pack(X)
+        seq_ptr, item_ptr, attr, values = self._pack(X)
         if str(label) not in self.classes_:
             raise ValueError(f"unknown label {label!r} (classes_: {self.classes_})")
         if seq_ptr[-1] == 0:
             return [np.zeros(0) for _ in X]
         p = self._model.windowed_marginals(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
-                                           label=self.classes_.index(str(label)), pad=pad, device=self.device)
+                                           label=self.classes_.index(str(label)), pad=pad, device=self.device,
+                                           values=values)
         return self._split(p, seq_ptr)
 
     def predict_windowed_all(self, X, background: Optional[str] = None, pad: bool = True):
@@ -200,7 +226,7 @@ class SequenceCRF:
         inside the window).  With ``background`` also, second, one ``[n_items]`` array per sequence: the maximum over the
         same windows of the probability of any label but ``background``."""
         self._windowed()
-        seq_ptr, item_ptr, attr = self._pack(X)
+        seq_ptr, item_ptr, attr, values = self._pack(X)
         L = len(self.classes_)
         if background is not None and str(background) not in self.classes_:
             raise ValueError(f"unknown label {background!r} (classes_: {self.classes_})")
@@ -209,7 +235,8 @@ class SequenceCRF:
             return empty if background is None else (empty, [np.zeros(0) for _ in X])
         bg = None if background is None else self.classes_.index(str(background))
         p_all, p_any = self._model.windowed_marginals_all(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
-                                                          background=bg, pad=pad, device=self.device)
+                                                          background=bg, pad=pad, device=self.device,
+                                                          values=values)
         if background is None:
             return self._split(p_all, seq_ptr)
         return self._split(p_all, seq_ptr), self._split(p_any, seq_ptr)

@@ -23,12 +23,13 @@ What is reproduced ([EXT] CRFsuite 0.12 ``crf1d`` + ``train_lbfgs`` with libLBFG
 """
 import math
 import sys
+from collections.abc import Mapping
 from typing import Callable, Dict, Generator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 __all__ = ["TRAINER_DEFAULTS", "MAX_LABELS", "trainer_params", "minimize", "minimize_steps", "OptimizeResult", "TrainingSet",
-           "build_training_set", "fit_training_set", "fit_training_sets", "fit_grid", "model_blob"]
+           "item_attributes", "build_training_set", "fit_training_set", "fit_training_sets", "fit_grid", "model_blob"]
 
 #: the most labels a training set may have (``_native.TrainerGeneral`` / ``TrainerSequences``; the inference kernels' limit)
 MAX_LABELS = 32
@@ -230,7 +231,11 @@ class TrainingSet:
     ``seq_ptr`` / ``item_ptr`` / ``attr_id`` / ``labels``: the sequences as CSR over items and attribute ids (ids in order
     of first appearance over the instances); ``labels_`` / ``attrs_``: the id -> name tables; ``state_attr``,
     ``state_label``, ``trans_src``, ``trans_dst``: the generated features (state features first, feature id = position);
-    ``state_fid`` [A, L] / ``trans_fid`` [L, L]: feature id of every pair, -1 where there is none."""
+    ``state_fid`` [A, L] / ``trans_fid`` [L, L]: feature id of every pair, -1 where there is none.  ``attr_value``: the value
+    of every attribute entry (float64, parallel to ``attr_id``), or None when every item was plain names (each entry then
+    weighs 1, and the set trains on the unvalued kernels)."""
+
+    attr_value = None  # (a set built without the field has no values)
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -271,12 +276,68 @@ def _pair_coverage(n: int, window: int, step: int) -> np.ndarray:
     return np.maximum(hi - lo + 1, 0)
 
 
+def _mapping_pairs(item: Mapping, prefix: str, out: List[Tuple[str, float]]) -> None:
+    for key, value in item.items():
+        key = prefix + str(key)
+        if isinstance(value, Mapping):
+            _mapping_pairs(value, key + ":", out)
+        elif isinstance(value, (bool, np.bool_)):
+            out.append((key, 1.0 if value else 0.0))
+        elif isinstance(value, (int, float, np.integer, np.floating)):
+            out.append((key, float(value)))
+        elif isinstance(value, (str, bytes)):
+            out.append((f"{key}:{value.decode() if isinstance(value, bytes) else value}", 1.0))
+        elif isinstance(value, (list, tuple, set, frozenset)):
+            out.extend((f"{key}:{s}", 1.0) for s in value)
+        else:
+            raise ValueError(f"attribute {key!r}: a value is a number, a bool, a string, a list or set of strings, or a dict; "
+                             f"got {type(value).__name__}")
+
+
+def item_attributes(item) -> Tuple[List[str], Optional[List[float]]]:
+    """One item as ``(names, values)``; ``values`` is None for an item of plain names (every attribute weighs 1).
+
+    * an iterable of names: the names, duplicates kept as they are given (``values`` None);
+    * an iterable of ``(name, value)`` pairs (a bare name among them weighs 1);
+    * a mapping, by python-crfsuite's ``ItemSequence`` conversion: ``{k: number}`` -> (k, value); ``{k: bool}`` -> (k, 1.0 /
+      0.0); ``{k: str}`` -> ("k:str", 1.0); ``{k: [s1, s2]}`` or a set -> ("k:s1", 1.0), ...; ``{k: {...}}`` -> the inner
+      mapping's attributes with the prefix "k:".
+
+    A value that is NaN or infinite raises ``ValueError``; so does an item that is a string."""
+    if isinstance(item, (str, bytes)):
+        raise ValueError("an item is an iterable of attribute names, of (name, value) pairs, or a mapping, not a string")
+    if isinstance(item, Mapping):
+        pairs: List[Tuple[str, float]] = []
+        _mapping_pairs(item, "", pairs)
+    else:
+        entries = list(item)
+        if all(isinstance(e, str) for e in entries):
+            return entries, None
+        pairs = []
+        for e in entries:
+            if isinstance(e, str):
+                pairs.append((e, 1.0))
+                continue
+            try:
+                name, value = e
+            except (TypeError, ValueError):
+                raise ValueError(f"an attribute is a name or a (name, value) pair, got {e!r}") from None
+            pairs.append((str(name), float(value)))
+    for name, value in pairs:
+        if not math.isfinite(value):
+            raise ValueError(f"attribute {name!r} has the value {value}: values must be finite")
+    return [name for name, _ in pairs], [value for _, value in pairs]
+
+
 def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_labels: Sequence[Sequence[str]],
                        window: Optional[int] = None, step: Optional[int] = None, min_freq: float = 0.0,
                        all_possible_states: bool = False, all_possible_transitions: bool = False,
                        max_labels: int = 2) -> TrainingSet:
     """Encode sequences (per item the attribute names, per item a label) and generate CRFsuite's features over the
-    sliding-window instances.  Every sequence must hold at least `window` items.  Raises ``ValueError`` unless exactly
+    sliding-window instances.  An item may also be a list of ``(name, value)`` pairs or a mapping (``item_attributes``):
+    the set then has ``attr_value``, a state feature (a, y) exists if the pair is observed on a covered item whatever the
+    value (0 included), and its frequency, which ``min_freq`` compares, is the sum of value x coverage.  A NaN or infinite
+    value raises ``ValueError``.  A set of plain names is what it always was, with ``attr_value`` None.  Every sequence must hold at least `window` items.  Raises ``ValueError`` unless exactly
     two labels occur, or, with ``max_labels`` = m in 2..32, unless 2 to m labels occur.
 
     ``window=None``: the instances are the whole sequences, of any length from one item up (``step`` is not read, and the
@@ -290,6 +351,9 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
         for k, items in enumerate(sequences):
             if len(items) == 0:
                 raise ValueError(f"sequence {k} has no items: a whole-sequence instance holds at least one")
+    converted = [[item_attributes(item) for item in items] for items in sequences]
+    valued = any(vals is not None for items in converted for _, vals in items)
+    sequences = [[names for names, _ in items] for items in converted]
     label_index: Dict[str, int] = {}
     attr_index: Dict[str, int] = {}
     covs = []
@@ -315,10 +379,14 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
     item_ptr = [0]
     attr_id: List[int] = []
     labels: List[int] = []
-    for items, labs in zip(sequences, sequence_labels):
-        for names, lab in zip(items, labs):
+    attr_value: List[float] = []
+    for items, labs, conv in zip(sequences, sequence_labels, converted):
+        for names, lab, (_, vals) in zip(items, labs, conv):
             # (names outside the dictionary can only sit on items no window covers: they carry no weight)
             attr_id.extend(attr_index[nm] for nm in names if nm in attr_index)
+            if valued:  # (an item of plain names inside a valued set: every value is 1)
+                vals = vals if vals is not None else [1.0] * len(names)
+                attr_value.extend(v for nm, v in zip(names, vals) if nm in attr_index)
             item_ptr.append(len(attr_id))
             labels.append(label_index.get(lab, 0))
         seq_ptr.append(len(labels))
@@ -332,7 +400,11 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
     deg = np.diff(item_ptr_a)
     occ_item = np.repeat(np.arange(len(lab_a)), deg)
     state_freq = np.zeros(A * L, dtype=np.float64)
-    np.add.at(state_freq, attr_a * L + lab_a[occ_item], cov_a[occ_item].astype(np.float64))
+    val_a = np.array(attr_value, dtype=np.float64) if valued else None
+    occ_freq = cov_a[occ_item].astype(np.float64)
+    if valued:  # frequency = value x coverage (a pair seen with value 0 alone is still seen, below)
+        occ_freq = val_a * occ_freq
+    np.add.at(state_freq, attr_a * L + lab_a[occ_item], occ_freq)
     state_seen = np.zeros(A * L, dtype=bool)
     state_seen[(attr_a * L + lab_a[occ_item])[cov_a[occ_item] > 0]] = True
     trans_freq = np.zeros(L * L, dtype=np.float64)
@@ -360,6 +432,7 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
         labels=lab_a.astype(np.int32), labels_=list(label_index), attrs_=list(attr_index),
         state_attr=s_idx // L, state_label=s_idx % L, trans_src=t_idx // L, trans_dst=t_idx % L,
         state_fid=state_fid.reshape(A, L), trans_fid=trans_fid.reshape(L, L), window=window, step=step,
+        attr_value=val_a,
     )
 
 
@@ -367,17 +440,25 @@ def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0
                      callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> OptimizeResult:
     """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0.  A set of whole
     sequences (``window is None``) takes ``_native.TrainerSequences`` at any label count; of the windowed sets, one of two
-    labels takes the 2-label trainer, one of more labels ``_native.TrainerGeneral``."""
+    labels takes the 2-label trainer, one of more labels ``_native.TrainerGeneral``.  A set with values (``attr_value``)
+    takes ``TrainerGeneral`` at any label count, 2 included, or ``TrainerSequences``, with its values."""
     from . import _native
 
     args = ts.native_args()
+    # (a set with values: the general kernels at any label count; one without: the calls they always were)
+    valued = {} if ts.attr_value is None else {"values": [ts.attr_value]}
     if ts.window is None:
-        trainer = _native.TrainerSequences([args], device=device)
-    elif ts.num_labels == 2:
+        trainer = _native.TrainerSequences([args], device=device, **valued)
+    elif ts.num_labels == 2 and not valued:
         trainer = _native.Trainer(*args[:5], *args[8:], *args[5:8], device=device)  # (window and step in the middle)
     else:
-        trainer = _native.TrainerGeneral([args], device=device)
+        trainer = _native.TrainerGeneral([args], device=device, **valued)
     return _fit_lockstep(trainer, [ts], [params], callback)[0]
+
+
+def _valued_entries(ts: TrainingSet) -> int:
+    """What a set with values adds to its scratch, in doubles: the values in attribute -> items order, one per entry."""
+    return 0 if ts.attr_value is None else int(len(ts.attr_value))
 
 
 def _general_scratch_bytes(ts: TrainingSet) -> int:
@@ -386,7 +467,7 @@ def _general_scratch_bytes(ts: TrainingSet) -> int:
     L, W = ts.num_labels, ts.window
     n = np.diff(np.asarray(ts.seq_ptr, dtype=np.int64))
     windows = int(np.sum((n[n >= W] - W) // ts.step + 1))
-    return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L))
+    return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L) + _valued_entries(ts))
 
 
 def _sequences_scratch_bytes(ts: TrainingSet) -> int:
@@ -395,7 +476,8 @@ def _sequences_scratch_bytes(ts: TrainingSet) -> int:
     plus 32 slabs)."""
     L = ts.num_labels
     per_block = 256 // max(2, 1 << (L - 1).bit_length())
-    return 8 * (2 * int(ts.seq_ptr[-1]) * L + (-(-(len(ts.seq_ptr) - 1) // per_block) + 32) * (1 + L * L))
+    return 8 * (2 * int(ts.seq_ptr[-1]) * L + (-(-(len(ts.seq_ptr) - 1) // per_block) + 32) * (1 + L * L)
+                + _valued_entries(ts))
 
 
 def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], List[OptimizeResult]],
@@ -410,8 +492,9 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
     from . import _native
 
     results: List[Optional[OptimizeResult]] = [None] * len(sets)
-    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2]
-    more = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels != 2]
+    # (a windowed set with values goes with the sets of more labels, at any label count)
+    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and ts.attr_value is None]
+    more = [k for k, ts in enumerate(sets) if ts.window is not None and (ts.num_labels != 2 or ts.attr_value is not None)]
     whole = [k for k, ts in enumerate(sets) if ts.window is None]
     if two:
         for k, r in zip(two, fit_two(two)):
@@ -429,7 +512,9 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
             groups[-1].append(k)
             used += need
         for group in groups:
-            trainer = getattr(_native, family)([sets[k].native_args() for k in group], device=device)
+            values = [sets[k].attr_value for k in group]
+            valued = {} if all(v is None for v in values) else {"values": values}  # (no values: the call it always was)
+            trainer = getattr(_native, family)([sets[k].native_args() for k in group], device=device, **valued)
             for k, r in zip(group, _fit_lockstep(trainer, [sets[k] for k in group], [params(k) for k in group])):
                 results[k] = r
             del trainer  # frees the group's device memory before the next group is created
@@ -481,7 +566,7 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
             raise ValueError(f"fit_grid: problem {k} names set {s}, but there are {len(sets)} sets")
 
     def fit_two(idx):
-        used = [s for s, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2]
+        used = [s for s, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and ts.attr_value is None]
         grid = _native.TrainerGrid([sets[s].native_args() for s in used], [used.index(int(problems[k][0])) for k in idx],
                                    scratch_budget_bytes, device=device)
         return _fit_lockstep(grid, [sets[int(problems[k][0])] for k in idx], [problems[k][1] for k in idx])

@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320). */
+/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -586,6 +586,62 @@ int32_t gecco_crf_trainer_sequences_num_problems(const gecco_crf_trainer_sequenc
 int64_t gecco_crf_trainer_sequences_num_sequences(const gecco_crf_trainer_sequences *t, int32_t k);
 int64_t gecco_crf_trainer_sequences_scratch_bytes(const gecco_crf_trainer_sequences *t, int32_t k);
 void gecco_crf_trainer_sequences_free(gecco_crf_trainer_sequences *t);
+
+/* ---- real-valued attributes (ABI 2.13.0, additive) ------------------------------------------------------------------
+ * CRFsuite's name:value items: every attribute entry carries a value, attr_value parallel to attr_id (same CSR positions),
+ * a finite fp64 that may be negative or zero.  The state score of an item is s[y] = sum over its entries of v * w[a][y],
+ * every term added as fma(v, w, acc) in CSR order; everything downstream of the state scores is the unvalued code.  The
+ * model file stores no values, so models load and save as before.  Every entry above keeps its behaviour and its bits.
+ *
+ * Inference one-shots: the sibling's arguments plus attr_value (length nnz) after attr_id; one device per call, one plan
+ * over the whole batch (no session, batch-driver or multi-device form).
+ *   * A valued call always takes the any-L kernels (crf_general.hip), at 2 labels too; reference-bits mode and the
+ *     GECCO_CRF_REFERENCE_BITS switch do not apply.  With every value 1.0 a model of 3 or more labels gives the bytes of the
+ *     unvalued sibling; a 2-label model agrees with its specialised kernels to rounding.
+ *   * Limits: 1 <= L <= 32.  gecco_crf_windowed_marginals_valued: windows of up to 48 genes at 2 labels and wherever the
+ *     lane-group kernel serves the model, up to 32 / 20 / 32 genes at 3-4 / 5-8 / 9-32 labels under the lane-per-window
+ *     kernels' transition guard (as the unvalued entry at 3 or more labels) -- so at 2 labels a window of more than 48
+ *     genes, which the unvalued entry serves, is GECCO_CRF_EUNSUPPORTED here.  gecco_crf_windowed_marginals_all_valued:
+ *     the limits of gecco_crf_windowed_marginals_all.
+ *   * Viterbi: the chunked kernels' exactness margin bounds a partial sum of state scores by nnz * max|v| * max|w|, max|v|
+ *     taken over the batch on the host; decisions inside the margin are decoded again by CRFsuite's sequential recursion.
+ *   * Attribute ids outside [0, A) carry no weight, whatever their value.
+ *   * Refused on the host before any device work, GECCO_CRF_EINVAL: a NaN or infinite value ("attribute value k is not
+ *     finite"), a NULL attr_value with nnz > 0.
+ * Trainers: gecco_crf_trainer_general_create / gecco_crf_trainer_sequences_create plus attr_value after attr_id; entry k
+ * may be NULL, which makes problem k unvalued with the bits it has from the unvalued create.  eval, num_*, scratch_bytes
+ * and free are the family's.  The objective keeps its form; the gradient of state feature (a, y) is the sum over instances
+ * and items holding a of v * P(y_t = y) minus the sum of v * [y_t = y], the second summed on the host in one fixed order
+ * (a double, no longer an integer).  A problem whose values are all 1.0 has the bytes of the unvalued problem.  A NaN or
+ * infinite value is GECCO_CRF_EINVAL ("trainer general: problem k: trainer: attribute value j is not finite").
+ * Memory: a valued problem's scratch_bytes grows by 8 * nnz (the values in attribute -> items order). */
+int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                        const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                        int32_t window, int32_t step, int32_t label, int32_t pad, double *p_out /* n_genes */);
+int gecco_crf_windowed_marginals_all_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                            int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                            const double *attr_value, int32_t window, int32_t step,
+                                            int32_t background /* label id, or -1 */, int32_t pad, double *p_all /* [n_genes][L] */,
+                                            double *p_any /* [n_genes], NULL iff background == -1 */);
+int gecco_crf_marginals_full_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                    const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value, double *marg,
+                                    double *lognorm);
+int gecco_crf_viterbi_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                             const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                             int8_t *y_out /* n_genes */, double *score);
+int gecco_crf_trainer_general_create_valued(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                            const int32_t *n_seqs, const int32_t *const *item_ptr, const int32_t *const *attr_id,
+                                            const double *const *attr_value, const int32_t *const *labels,
+                                            const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window,
+                                            const int32_t *step, const int32_t *const *state_fid,
+                                            const int32_t *const *trans_fid, const int32_t *num_features,
+                                            gecco_crf_trainer_general **out);
+int gecco_crf_trainer_sequences_create_valued(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                              const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                              const int32_t *const *attr_id, const double *const *attr_value,
+                                              const int32_t *const *labels, const int32_t *num_attrs, const int32_t *num_labels,
+                                              const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                              const int32_t *num_features, gecco_crf_trainer_sequences **out);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
