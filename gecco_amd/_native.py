@@ -496,86 +496,56 @@ class Model:
     # ``values=``: one float64 per attribute entry, parallel to ``attr_id`` (CRFsuite's name:value items): the state score of
     # a gene is the sum of value * weight, and the call takes the ``*_valued`` entry (the any-L kernels at every label
     # count).  None: the unvalued entry, as ever.
-    @staticmethod
-    def _values(values, attr_id):
-        values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-        if values.size != attr_id.size:
-            raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
-        return values if values.size else np.zeros(1, dtype=np.float64)
-
-    def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0, values=None):
+    def _oneshot(self, name, contig_ptr, gene_ptr, attr_id, values, device):
+        """The CSR arguments of the one-shot entry ``name``, or of ``name + "_valued"`` when ``values`` are given (their
+        pointer goes in behind ``attr_id``'s).  Returns ``(n_genes, n_contigs, run)``; ``run(*tail)`` calls the entry with
+        the arguments that follow the CSR arrays."""
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n = int(contig_ptr[-1]) if len(contig_ptr) else 0
-        out = np.zeros(max(n, 1), dtype=np.float64)
+        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
         if values is not None:
-            values = self._values(values, attr_id)
+            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+            if values.size != attr_id.size:
+                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
+            values = values if values.size else np.zeros(1, dtype=np.float64)
         if attr_id.size == 0:
             attr_id = np.zeros(1, dtype=np.int32)
-        head = (self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
-                _ptr(attr_id, _c_i32p))
-        tail = (int(window), int(step), int(label), int(bool(pad)), _ptr(out, _c_f64p))
-        if values is None:
-            _check(self._lib.gecco_crf_windowed_marginals(*head, *tail))
-        else:
-            _check(self._lib.gecco_crf_windowed_marginals_valued(*head, _ptr(values, _c_f64p), *tail))
+        head = [self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p)]
+        if values is not None:
+            head.append(_ptr(values, _c_f64p))
+        entry = getattr(self._lib, name if values is None else name + "_valued")
+        return n, nc, lambda *tail: _check(entry(*head, *tail))  # (`head` keeps the arrays alive)
+
+    def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0, values=None):
+        n, _, run = self._oneshot("gecco_crf_windowed_marginals", contig_ptr, gene_ptr, attr_id, values, device)
+        out = np.zeros(max(n, 1), dtype=np.float64)
+        run(int(window), int(step), int(label), int(bool(pad)), _ptr(out, _c_f64p))
         return out[:n]
 
     def windowed_marginals_all(self, contig_ptr, gene_ptr, attr_id, window, step=1, background=None, pad=True, device=0,
                                values=None):
         """Every label's windowed probability in one device pass: ``(p_all [n, L], p_any [n] or None)``; ``p_any`` is the
         windowed probability of any label but ``background`` (a label id)."""
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, L = (int(contig_ptr[-1]) if len(contig_ptr) else 0), self.num_labels
-        p_all = np.zeros((max(n, 1), L), dtype=np.float64)
+        n, _, run = self._oneshot("gecco_crf_windowed_marginals_all", contig_ptr, gene_ptr, attr_id, values, device)
+        p_all = np.zeros((max(n, 1), self.num_labels), dtype=np.float64)
         p_any = None if background is None else np.zeros(max(n, 1), dtype=np.float64)
-        if values is not None:
-            values = self._values(values, attr_id)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        head = (self._h, device, _ptr(contig_ptr, _c_i32p), max(len(contig_ptr) - 1, 0), _ptr(gene_ptr, _c_i32p),
-                _ptr(attr_id, _c_i32p))
-        tail = (int(window), int(step), -1 if background is None else int(background), int(bool(pad)),
-                _ptr(p_all, _c_f64p), None if p_any is None else _ptr(p_any, _c_f64p))
-        if values is None:
-            _check(self._lib.gecco_crf_windowed_marginals_all(*head, *tail))
-        else:
-            _check(self._lib.gecco_crf_windowed_marginals_all_valued(*head, _ptr(values, _c_f64p), *tail))
+        run(int(window), int(step), -1 if background is None else int(background), int(bool(pad)), _ptr(p_all, _c_f64p),
+            None if p_any is None else _ptr(p_any, _c_f64p))
         return p_all[:n], (None if p_any is None else p_any[:n])
 
     def marginals_full(self, contig_ptr, gene_ptr, attr_id, device=0, values=None):
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, nc, L = int(contig_ptr[-1]), len(contig_ptr) - 1, self.num_labels
-        marg = np.zeros((max(n, 1), L), dtype=np.float64)
+        n, nc, run = self._oneshot("gecco_crf_marginals_full", contig_ptr, gene_ptr, attr_id, values, device)
+        marg = np.zeros((max(n, 1), self.num_labels), dtype=np.float64)
         ln = np.zeros(max(nc, 1), dtype=np.float64)
-        if values is not None:
-            values = self._values(values, attr_id)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        head = (self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p))
-        tail = (_ptr(marg, _c_f64p), _ptr(ln, _c_f64p))
-        if values is None:
-            _check(self._lib.gecco_crf_marginals_full(*head, *tail))
-        else:
-            _check(self._lib.gecco_crf_marginals_full_valued(*head, _ptr(values, _c_f64p), *tail))
+        run(_ptr(marg, _c_f64p), _ptr(ln, _c_f64p))
         return marg[:n], ln[:nc]
 
     def viterbi(self, contig_ptr, gene_ptr, attr_id, device=0, want_score=True, values=None):
         """Best label path per contig; with `want_score=False` returns (labels, None) and 2-label
         models take the cheaper score-difference form of the recursion."""
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, nc = int(contig_ptr[-1]), len(contig_ptr) - 1
+        n, nc, run = self._oneshot("gecco_crf_viterbi", contig_ptr, gene_ptr, attr_id, values, device)
         y = np.zeros(max(n, 1), dtype=np.int8)
         sc = np.zeros(max(nc, 1), dtype=np.float64) if want_score else None
-        if values is not None:
-            values = self._values(values, attr_id)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        head = (self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p))
-        tail = (_ptr(y, _c_i8p), _ptr(sc, _c_f64p) if want_score else None)
-        if values is None:
-            _check(self._lib.gecco_crf_viterbi(*head, *tail))
-        else:
-            _check(self._lib.gecco_crf_viterbi_valued(*head, _ptr(values, _c_f64p), *tail))
+        run(_ptr(y, _c_i8p), _ptr(sc, _c_f64p) if want_score else None)
         return y[:n], (sc[:nc] if want_score else None)
 
 
@@ -1348,6 +1318,24 @@ class _TrainerHandle:
             keep.append(v if v.size else np.zeros(1, dtype=np.float64))
         return (_vp * len(keep))(*[None if v is None else v.ctypes.data for v in keep]), keep
 
+    def _create_general(self, problems, device, values, whole: bool):
+        """The constructor of the general (``whole=False``: every problem with a window and a step) and the whole-sequence
+        family, on ``create`` or, when a problem has values, on ``create_valued``."""
+        if whole and any(len(p) != 8 for p in problems):
+            raise ValueError("a whole-sequence problem has 8 entries: no window and no step")
+        arrays, counts = _trainer_sets(problems)
+        if not whole and any(len(v) != len(problems) for v in counts.values()):
+            raise ValueError("every problem needs a window and a step")
+        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
+        c = {name: _i32_vector(v) for name, v in counts.items()}
+        vt, _keep = self._value_table(values, [int(np.asarray(p[2]).size) for p in problems])
+        value_table = () if vt is None else (vt,)
+        window_step = () if whole else (c["window"], c["step"])
+        self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], *value_table,
+                     t["labels"], c["num_attrs"], c["num_labels"], *window_step, t["state_fid"], t["trans_fid"],
+                     c["num_features"], entry="create" if vt is None else "create_valued")
+        self.num_features = self._features = counts["num_features"]
+
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
         if h:
@@ -1486,20 +1474,7 @@ class TrainerGeneral(_TrainerHandle):
     eval = _TrainerHandle._eval_problems
 
     def __init__(self, problems, device: int = 0, values=None):
-        arrays, counts = _trainer_sets(problems)
-        if any(len(v) != len(problems) for v in counts.values()):
-            raise ValueError("every problem needs a window and a step")
-        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
-        c = {name: _i32_vector(v) for name, v in counts.items()}
-        vt, _keep = self._value_table(values, [int(np.asarray(p[2]).size) for p in problems])
-        head = (int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"])
-        tail = (t["labels"], c["num_attrs"], c["num_labels"], c["window"], c["step"], t["state_fid"], t["trans_fid"],
-                c["num_features"])
-        if vt is None:
-            self._create(*head, *tail)
-        else:
-            self._create(*head, vt, *tail, entry="create_valued")
-        self.num_features = self._features = counts["num_features"]
+        self._create_general(problems, device, values, whole=False)
 
     def scratch_bytes(self, k: int = -1) -> int:
         """Scratch bytes of problem k; for k = -1 the sum over the problems, which is what is allocated."""
@@ -1519,19 +1494,7 @@ class TrainerSequences(_TrainerHandle):
     eval = _TrainerHandle._eval_problems
 
     def __init__(self, problems, device: int = 0, values=None):
-        if any(len(p) != 8 for p in problems):
-            raise ValueError("a whole-sequence problem has 8 entries: no window and no step")
-        arrays, counts = _trainer_sets(problems)
-        t = {name: _ptr_table(arrs) for name, arrs in arrays.items()}
-        c = {name: _i32_vector(v) for name, v in counts.items()}
-        vt, _keep = self._value_table(values, [int(np.asarray(p[2]).size) for p in problems])
-        head = (int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"])
-        tail = (t["labels"], c["num_attrs"], c["num_labels"], t["state_fid"], t["trans_fid"], c["num_features"])
-        if vt is None:
-            self._create(*head, *tail)
-        else:
-            self._create(*head, vt, *tail, entry="create_valued")
-        self.num_features = self._features = counts["num_features"]
+        self._create_general(problems, device, values, whole=True)
 
     def num_sequences(self, k: int) -> int:
         return int(self._c("num_sequences")(self._h, int(k)))

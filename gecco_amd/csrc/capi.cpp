@@ -93,6 +93,28 @@ int check_device(int32_t device) {
     }
     return GECCO_CRF_OK;
 }
+
+int fail(const char *msg) {
+    set_error(msg);
+    return GECCO_CRF_EINVAL;
+}
+
+// The argument checks that the one-shots share, each message written once.  They come before any device work, so that an
+// argument error surfaces even on a box without a GPU.
+int check_window(int32_t window, int32_t step) {
+    if (window <= 0) return fail("Window size must be strictly positive");
+    if (step <= 0 || step > window) return fail("Window step must be strictly positive and under `window_size`");
+    return GECCO_CRF_OK;
+}
+int check_label(const gecco_crf_model *m, int32_t label) {
+    return label < 0 || label >= m->m.L ? fail("label out of range") : GECCO_CRF_OK;
+}
+int check_background(const gecco_crf_model *m, int32_t background, const double *p_any) {
+    if (background < -1 || background >= m->m.L) return fail("background label out of range");
+    if ((background < 0) != (p_any == nullptr))
+        return fail(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
+    return GECCO_CRF_OK;
+}
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
@@ -218,7 +240,7 @@ GECCO_API int gecco_crf_plan_run_windowed(gecco_crf_plan *p, const int32_t *d_ge
     if (!p) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    return plan_run_windowed(p->p, d_gene_ptr, d_attr_id, label, d_p_out, static_cast<hipStream_t>(stream));
+    return plan_run_windowed(p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
 }
 
@@ -227,7 +249,7 @@ GECCO_API int gecco_crf_plan_run_windowed_all(gecco_crf_plan *p, const int32_t *
     if (!p) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    return plan_run_windowed_all(p->p, d_gene_ptr, d_attr_id, background, d_p_all, d_p_any, static_cast<hipStream_t>(stream));
+    return plan_run_windowed_all(p->p, {d_gene_ptr, d_attr_id}, background, d_p_all, d_p_any, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
 }
 GECCO_API const char *gecco_crf_plan_all_kernel_name(const gecco_crf_plan *p) { return p ? plan_all_kernel_name(p->p) : ""; }
@@ -260,7 +282,7 @@ GECCO_API int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_g
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return time_calls(s, warmup, iters, ms_per_launch, [&] { return plan_run_windowed(p->p, d_gene_ptr, d_attr_id, label, d_p_out, s); });
+    return time_calls(s, warmup, iters, ms_per_launch, [&] { return plan_run_windowed(p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, s); });
     GECCO_GUARD_END
 }
 
@@ -272,7 +294,7 @@ GECCO_API int gecco_crf_plan_time_windowed_all(gecco_crf_plan *p, const int32_t 
     GECCO_GUARD_BEGIN
     hipStream_t s = static_cast<hipStream_t>(stream);
     return time_calls(s, warmup, iters, ms_per_launch,
-                      [&] { return plan_run_windowed_all(p->p, d_gene_ptr, d_attr_id, background, d_p_all, d_p_any, s); });
+                      [&] { return plan_run_windowed_all(p->p, {d_gene_ptr, d_attr_id}, background, d_p_all, d_p_any, s); });
     GECCO_GUARD_END
 }
 
@@ -285,10 +307,10 @@ GECCO_API int gecco_crf_plan_time_decode_pipelined(gecco_crf_plan *p, const int3
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
     // the plan follows itself: call 0 primes (tiles only), every later call is one launch of tiles + Viterbi workgroups
-    if ((rc = plan_run_decode_pipelined(&p->p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, nullptr, s))) return rc;
+    if ((rc = plan_run_decode_pipelined(&p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, nullptr, nullptr, s))) return rc;
     rc = time_calls(s, warmup, iters, ms_per_launch,
-                    [&] { return plan_run_decode_pipelined(&p->p, d_gene_ptr, d_attr_id, label, d_p_out, &p->p, d_y, s); });
-    if (!rc) rc = plan_run_decode_pipelined(nullptr, nullptr, nullptr, label, nullptr, &p->p, d_y, s);  // (flush)
+                    [&] { return plan_run_decode_pipelined(&p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, &p->p, d_y, s); });
+    if (!rc) rc = plan_run_decode_pipelined(nullptr, {}, label, nullptr, &p->p, d_y, s);  // (flush)
     return rc;
     GECCO_GUARD_END
 }
@@ -306,7 +328,7 @@ GECCO_API int gecco_crf_plan_run_decode(gecco_crf_plan *p, const int32_t *d_gene
     if (!p) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    return plan_run_decode(p->p, d_gene_ptr, d_attr_id, label, d_p_out, d_y, d_score, static_cast<hipStream_t>(stream));
+    return plan_run_decode(p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, d_y, d_score, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
 }
 GECCO_API int gecco_crf_plan_run_decode_pipelined(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label,
@@ -314,7 +336,7 @@ GECCO_API int gecco_crf_plan_run_decode_pipelined(gecco_crf_plan *p, const int32
     if (!p && !prev) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    return plan_run_decode_pipelined(p ? &p->p : nullptr, d_gene_ptr, d_attr_id, label, d_p_out, prev ? &prev->p : nullptr, d_prev_y,
+    return plan_run_decode_pipelined(p ? &p->p : nullptr, {d_gene_ptr, d_attr_id}, label, d_p_out, prev ? &prev->p : nullptr, d_prev_y,
                                      static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
 }
@@ -323,7 +345,7 @@ GECCO_API int gecco_crf_plan_run_marginals_full(gecco_crf_plan *p, const int32_t
     if (!p) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    return plan_run_marginals_full(p->p, d_gene_ptr, d_attr_id, d_marg, d_lognorm, static_cast<hipStream_t>(stream));
+    return plan_run_marginals_full(p->p, {d_gene_ptr, d_attr_id}, d_marg, d_lognorm, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
 }
 GECCO_API int gecco_crf_plan_run_viterbi(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
@@ -331,7 +353,7 @@ GECCO_API int gecco_crf_plan_run_viterbi(gecco_crf_plan *p, const int32_t *d_gen
     if (!p) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    return plan_run_viterbi(p->p, d_gene_ptr, d_attr_id, d_y, d_score, static_cast<hipStream_t>(stream));
+    return plan_run_viterbi(p->p, {d_gene_ptr, d_attr_id}, d_y, d_score, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
 }
 
@@ -593,24 +615,12 @@ GECCO_API int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t dev
                                            int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
                                            int32_t window, int32_t step, int32_t label, int32_t pad, double *p_out) {
     if (!m) return GECCO_CRF_EINVAL;
-    // argument errors first, so that they surface even on a box without a GPU
-    if (window <= 0) {
-        set_error("Window size must be strictly positive");
-        return GECCO_CRF_EINVAL;
-    }
-    if (step <= 0 || step > window) {
-        set_error("Window step must be strictly positive and under `window_size`");
-        return GECCO_CRF_EINVAL;
-    }
-    if (label < 0 || label >= m->m.L) {
-        set_error("label out of range");
-        return GECCO_CRF_EINVAL;
-    }
+    int rc;
+    if ((rc = check_window(window, step)) || (rc = check_label(m, label))) return rc;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
     Session *s = nullptr;
-    int rc = default_session(m, device, &s);
-    if (rc) return rc;
+    if ((rc = default_session(m, device, &s))) return rc;
     if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > 0 && !p_out) {
         set_error("null buffer");
         return GECCO_CRF_EINVAL;
@@ -622,75 +632,6 @@ GECCO_API int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t dev
     r.pad = pad;
     r.p_out = p_out;
     return session_run(*s, r);
-    GECCO_GUARD_END
-}
-
-// One device, one plan over the whole batch: the arrays go to device memory, the plan runs, the results come back.
-GECCO_API int gecco_crf_windowed_marginals_all(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
-                                               int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
-                                               int32_t window, int32_t step, int32_t background, int32_t pad, double *p_all,
-                                               double *p_any) {
-    if (!m) return GECCO_CRF_EINVAL;
-    // argument errors first, so that they surface even on a box without a GPU
-    if (window <= 0) {
-        set_error("Window size must be strictly positive");
-        return GECCO_CRF_EINVAL;
-    }
-    if (step <= 0 || step > window) {
-        set_error("Window step must be strictly positive and under `window_size`");
-        return GECCO_CRF_EINVAL;
-    }
-    if (background < -1 || background >= m->m.L) {
-        set_error("background label out of range");
-        return GECCO_CRF_EINVAL;
-    }
-    if ((background < 0) != (p_any == nullptr)) {
-        set_error(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
-        return GECCO_CRF_EINVAL;
-    }
-    DeviceGuard guard;
-    GECCO_GUARD_BEGIN
-    int rc = check_device(device);
-    if (rc) return rc;
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) {
-        set_error("bad contig_ptr");
-        return GECCO_CRF_EINVAL;
-    }
-    const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
-    if (n > 0 && (!p_all || !gene_ptr)) {
-        set_error("null buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    Plan plan;
-    if ((rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, plan))) return rc;
-    if (plan.n_genes == 0) return GECCO_CRF_OK;
-    const int32_t *gp = gene_ptr + contig_ptr[0];
-    const int64_t a0 = gp[0], nnz = int64_t(gp[n]) - a0;
-    if (nnz < 0 || (nnz > 0 && !attr_id)) {
-        set_error("bad gene_ptr");
-        return GECCO_CRF_EINVAL;
-    }
-    const size_t L = size_t(m->m.L), b_gp = size_t(n + 1) * 4, b_at = size_t(nnz ? nnz : 1) * 4, b_all = size_t(n) * L * 8,
-                 b_any = size_t(n) * 8;
-    Carver blk;
-    const size_t o_gp = blk.take(b_gp), o_at = blk.take(b_at), o_all = blk.take(b_all), o_any = blk.take(b_any);
-    char *d = nullptr;
-    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&d), blk.off), "hipMalloc batch"))) return rc;
-    // (gene_ptr may carry any base offset: the kernels index attr_id with its values, so the attribute array goes up from
-    // that base and the row pointers are rebased on the host)
-    std::vector<int32_t> rows(size_t(n) + 1);
-    for (int64_t i = 0; i <= n; ++i) rows[size_t(i)] = int32_t(gp[i] - a0);
-    rc = check_hip(hipMemcpy(d + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
-    if (!rc && nnz) rc = check_hip(hipMemcpy(d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
-    if (!rc)
-        rc = plan_run_windowed_all(plan, reinterpret_cast<int32_t *>(d + o_gp), reinterpret_cast<int32_t *>(d + o_at), background,
-                                   reinterpret_cast<double *>(d + o_all), p_any ? reinterpret_cast<double *>(d + o_any) : nullptr,
-                                   nullptr);
-    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "windowed marginals");
-    if (!rc) rc = check_hip(hipMemcpy(p_all, d + o_all, b_all, hipMemcpyDeviceToHost), "download p_all");
-    if (!rc && p_any) rc = check_hip(hipMemcpy(p_any, d + o_any, b_any, hipMemcpyDeviceToHost), "download p_any");
-    (void)hipFree(d);
-    return rc;
     GECCO_GUARD_END
 }
 
@@ -733,46 +674,48 @@ GECCO_API int gecco_crf_viterbi(const gecco_crf_model *m, int32_t device, const 
     GECCO_GUARD_END
 }
 
-// ---- real-valued attributes (ABI 2.13.0): the one-shots with a value per attribute entry ---------------------------
+// ---- one-shots on one plan over the whole batch: every label's windowed marginals (ABI 2.11.0) and the entries with a value
+// per attribute entry (ABI 2.13.0) ---------------------------------------------------------------------------------------
 namespace {
-// What a valued one-shot has on the device: one plan over the whole batch, forced onto the any-L kernels, and one block
-// with the rebased row pointers, the attribute ids, their values and the outputs.
-struct ValuedBatch {
+// A batch resident on the device for one call: one plan over all of it, and one block with the rebased row pointers, the
+// attribute ids, their values (a valued batch: csr.attr_value; null means unvalued) and the outputs.
+struct ResidentBatch {
     Plan plan;
     char *d = nullptr;
     int64_t n = 0;  // genes
-    const int32_t *d_gene_ptr = nullptr, *d_attr_id = nullptr;
-    ~ValuedBatch() {
+    DeviceCsr csr;
+    size_t out_off[3] = {0, 0, 0};
+    template <class T>
+    T *out(int i) const {
+        return reinterpret_cast<T *>(d + out_off[i]);
+    }
+    ~ResidentBatch() {
         if (d) (void)hipFree(d);
     }
 };
 
-// The host checks of every valued one-shot (before any device work), the plan, and the upload.  out_bytes[i] > 0: output i
-// gets a part of the block, at d + out_off[i].  Returns with vb.n == 0 for a batch without genes (nothing to run).
-int valued_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
-                const int32_t *attr_id, const double *attr_value, int32_t window, int32_t step, int32_t pad, bool windowed,
-                const size_t per_gene[2], size_t per_contig, ValuedBatch &vb, size_t out_off[3]) {
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) {
-        set_error("bad contig_ptr");
-        return GECCO_CRF_EINVAL;
-    }
+// the caller's buffer for a per-gene output: needed as soon as the batch has a gene
+int check_output(const int32_t *contig_ptr, int32_t n_contigs, const void *out) {
+    return n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0] && !out ? fail("null buffer") : GECCO_CRF_OK;
+}
+
+// The host checks of the CSR arrays (before any device work), the plan, and the upload.  `valued`: the plan takes the any-L
+// kernels at every label count and attr_value holds a finite value per attribute entry; otherwise attr_value is not read.
+// Output i gets a part of the block, at b.out(i): per_gene[i] bytes for every gene (i = 0, 1), per_contig for every contig
+// (i = 2).  Returns with b.n == 0 for a batch without genes (nothing to run).
+int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+               const int32_t *attr_id, const double *attr_value, bool valued, int32_t window, int32_t step, int32_t pad,
+               bool windowed, const size_t per_gene[2], size_t per_contig, ResidentBatch &b) {
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
     const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
-    if (n > 0 && !gene_ptr) {
-        set_error("null buffer");
-        return GECCO_CRF_EINVAL;
-    }
+    if (n > 0 && !gene_ptr) return fail("null buffer");
     const int32_t *gp = n > 0 ? gene_ptr + contig_ptr[0] : nullptr;
     const int64_t a0 = n > 0 ? gp[0] : 0, nnz = n > 0 ? int64_t(gp[n]) - a0 : 0;
-    if (nnz < 0 || (nnz > 0 && !attr_id)) {
-        set_error("bad gene_ptr");
-        return GECCO_CRF_EINVAL;
-    }
-    if (nnz > 0 && !attr_value) {
-        set_error("null attr_value with attribute entries (the unvalued entry takes attributes without values)");
-        return GECCO_CRF_EINVAL;
-    }
+    if (nnz < 0 || (nnz > 0 && !attr_id)) return fail("bad gene_ptr");
+    if (valued && nnz > 0 && !attr_value)
+        return fail("null attr_value with attribute entries (the unvalued entry takes attributes without values)");
     double vmax = 0.0;
-    for (int64_t k = 0; k < nnz; ++k) {
+    for (int64_t k = 0; valued && k < nnz; ++k) {
         const double v = attr_value[a0 + k];
         if (!std::isfinite(v)) {
             set_error("attribute value " + std::to_string(a0 + k) + " is not finite (NaN or infinite)");
@@ -782,109 +725,97 @@ int valued_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_
     }
     int rc = check_device(device);
     if (rc) return rc;
-    vb.plan.valued = true;
-    vb.plan.windowed_use = windowed;
-    if ((rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, vb.plan))) return rc;
-    if (vb.plan.n_genes == 0) return GECCO_CRF_OK;
-    const size_t b_gp = size_t(n + 1) * 4, b_at = size_t(nnz ? nnz : 1) * 4, b_val = size_t(nnz ? nnz : 1) * 8;
+    b.plan.valued = valued;
+    b.plan.windowed_use = windowed;
+    if ((rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, b.plan))) return rc;
+    if (b.plan.n_genes == 0) return GECCO_CRF_OK;
+    const size_t b_gp = size_t(n + 1) * 4, n_at = size_t(nnz ? nnz : 1);
     Carver blk;
-    const size_t o_gp = blk.take(b_gp), o_at = blk.take(b_at), o_val = blk.take(b_val);
-    out_off[0] = blk.take(per_gene[0] * size_t(n) + 8);
-    out_off[1] = blk.take(per_gene[1] * size_t(n) + 8);
-    out_off[2] = blk.take(per_contig * size_t(n_contigs) + 8);
-    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&vb.d), blk.off), "hipMalloc batch"))) return rc;
-    // (gene_ptr may carry any base offset: the row pointers are rebased on the host, ids and values go up from that base)
+    const size_t o_gp = blk.take(b_gp), o_at = blk.take(n_at * 4), o_val = valued ? blk.take(n_at * 8) : 0;
+    b.out_off[0] = blk.take(per_gene[0] * size_t(n) + 8);
+    b.out_off[1] = blk.take(per_gene[1] * size_t(n) + 8);
+    b.out_off[2] = blk.take(per_contig * size_t(n_contigs) + 8);
+    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&b.d), blk.off), "hipMalloc batch"))) return rc;
+    // (gene_ptr may carry any base offset: the kernels index attr_id with its values, so the row pointers are rebased on the
+    // host, and ids and values go up from that base)
     std::vector<int32_t> rows(size_t(n) + 1);
     for (int64_t i = 0; i <= n; ++i) rows[size_t(i)] = int32_t(gp[i] - a0);
-    rc = check_hip(hipMemcpy(vb.d + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
-    if (!rc && nnz) rc = check_hip(hipMemcpy(vb.d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
-    if (!rc && nnz) rc = check_hip(hipMemcpy(vb.d + o_val, attr_value + a0, size_t(nnz) * 8, hipMemcpyHostToDevice), "upload attr_value");
+    rc = check_hip(hipMemcpy(b.d + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
+    if (!rc && nnz) rc = check_hip(hipMemcpy(b.d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
+    if (!rc && nnz && valued)
+        rc = check_hip(hipMemcpy(b.d + o_val, attr_value + a0, size_t(nnz) * 8, hipMemcpyHostToDevice), "upload attr_value");
     if (rc) return rc;
-    vb.n = n;
-    vb.d_gene_ptr = reinterpret_cast<const int32_t *>(vb.d + o_gp);
-    vb.d_attr_id = reinterpret_cast<const int32_t *>(vb.d + o_at);
-    vb.plan.d_attr_value = reinterpret_cast<const double *>(vb.d + o_val);
-    vb.plan.vmax_abs = vmax;
+    b.n = n;
+    b.csr.gene_ptr = reinterpret_cast<const int32_t *>(b.d + o_gp);
+    b.csr.attr_id = reinterpret_cast<const int32_t *>(b.d + o_at);
+    if (valued) {
+        b.csr.attr_value = reinterpret_cast<const double *>(b.d + o_val);
+        b.csr.vmax_abs = vmax;
+    }
     return GECCO_CRF_OK;
 }
 
-int valued_fetch(int rc, void *dst, const char *src, size_t bytes, const char *what) {
+// after the run call: waits for the device ...
+int batch_wait(int rc, const char *what) { return rc ? rc : check_hip(hipStreamSynchronize(nullptr), what); }
+// ... and brings an output back (one the caller did not ask for is skipped)
+int batch_fetch(int rc, void *dst, const void *src, size_t bytes, const char *what) {
     if (rc || !dst || !bytes) return rc;
     return check_hip(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost), what);
 }
-}  // namespace
 
-GECCO_API int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
-                                                  int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
-                                                  const double *attr_value, int32_t window, int32_t step, int32_t label,
-                                                  int32_t pad, double *p_out) {
+int windowed_all(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                 const int32_t *attr_id, const double *attr_value, bool valued, int32_t window, int32_t step, int32_t background,
+                 int32_t pad, double *p_all, double *p_any) {
     if (!m) return GECCO_CRF_EINVAL;
-    if (window <= 0) {
-        set_error("Window size must be strictly positive");
-        return GECCO_CRF_EINVAL;
-    }
-    if (step <= 0 || step > window) {
-        set_error("Window step must be strictly positive and under `window_size`");
-        return GECCO_CRF_EINVAL;
-    }
-    if (label < 0 || label >= m->m.L) {
-        set_error("label out of range");
-        return GECCO_CRF_EINVAL;
-    }
+    int rc;
+    if ((rc = check_window(window, step)) || (rc = check_background(m, background, p_any))) return rc;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0] && !p_out) {
-        set_error("null buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    ValuedBatch vb;
-    const size_t per_gene[2] = {8, 0};
-    size_t off[3];
-    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, window, step, pad, true, per_gene, 0, vb, off);
-    if (rc || vb.n == 0) return rc;
-    rc = plan_run_windowed(vb.plan, vb.d_gene_ptr, vb.d_attr_id, label, reinterpret_cast<double *>(vb.d + off[0]), nullptr);
-    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "windowed marginals");
-    return valued_fetch(rc, p_out, vb.d + off[0], size_t(vb.n) * 8, "download p");
+    if ((rc = check_output(contig_ptr, n_contigs, p_all))) return rc;
+    ResidentBatch b;
+    const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 8};
+    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, window, step, pad, true, per_gene, 0, b);
+    if (rc || b.n == 0) return rc;
+    rc = plan_run_windowed_all(b.plan, b.csr, background, b.out<double>(0), p_any ? b.out<double>(1) : nullptr, nullptr);
+    rc = batch_wait(rc, "windowed marginals");
+    rc = batch_fetch(rc, p_all, b.out<double>(0), size_t(b.n) * L * 8, "download p_all");
+    return batch_fetch(rc, p_any, b.out<double>(1), size_t(b.n) * 8, "download p_any");
     GECCO_GUARD_END
+}
+}  // namespace
+
+GECCO_API int gecco_crf_windowed_marginals_all(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                               int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                               int32_t window, int32_t step, int32_t background, int32_t pad, double *p_all,
+                                               double *p_any) {
+    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, nullptr, false, window, step, background, pad, p_all,
+                        p_any);
 }
 
 GECCO_API int gecco_crf_windowed_marginals_all_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
                                                       int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
                                                       const double *attr_value, int32_t window, int32_t step,
                                                       int32_t background, int32_t pad, double *p_all, double *p_any) {
+    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, window, step, background, pad, p_all,
+                        p_any);
+}
+
+GECCO_API int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                  int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                  const double *attr_value, int32_t window, int32_t step, int32_t label,
+                                                  int32_t pad, double *p_out) {
     if (!m) return GECCO_CRF_EINVAL;
-    if (window <= 0) {
-        set_error("Window size must be strictly positive");
-        return GECCO_CRF_EINVAL;
-    }
-    if (step <= 0 || step > window) {
-        set_error("Window step must be strictly positive and under `window_size`");
-        return GECCO_CRF_EINVAL;
-    }
-    if (background < -1 || background >= m->m.L) {
-        set_error("background label out of range");
-        return GECCO_CRF_EINVAL;
-    }
-    if ((background < 0) != (p_any == nullptr)) {
-        set_error(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
-        return GECCO_CRF_EINVAL;
-    }
+    int rc;
+    if ((rc = check_window(window, step)) || (rc = check_label(m, label))) return rc;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0] && !p_all) {
-        set_error("null buffer");
-        return GECCO_CRF_EINVAL;
-    }
-    ValuedBatch vb;
-    const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 8};
-    size_t off[3];
-    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, window, step, pad, true, per_gene, 0, vb, off);
-    if (rc || vb.n == 0) return rc;
-    rc = plan_run_windowed_all(vb.plan, vb.d_gene_ptr, vb.d_attr_id, background, reinterpret_cast<double *>(vb.d + off[0]),
-                               p_any ? reinterpret_cast<double *>(vb.d + off[1]) : nullptr, nullptr);
-    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "windowed marginals");
-    rc = valued_fetch(rc, p_all, vb.d + off[0], size_t(vb.n) * L * 8, "download p_all");
-    return valued_fetch(rc, p_any, vb.d + off[1], size_t(vb.n) * 8, "download p_any");
+    if ((rc = check_output(contig_ptr, n_contigs, p_out))) return rc;
+    ResidentBatch b;
+    const size_t per_gene[2] = {8, 0};
+    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, window, step, pad, true, per_gene, 0, b);
+    if (rc || b.n == 0) return rc;
+    rc = batch_wait(plan_run_windowed(b.plan, b.csr, label, b.out<double>(0), nullptr), "windowed marginals");
+    return batch_fetch(rc, p_out, b.out<double>(0), size_t(b.n) * 8, "download p");
     GECCO_GUARD_END
 }
 
@@ -895,20 +826,17 @@ GECCO_API int gecco_crf_marginals_full_valued(const gecco_crf_model *m, int32_t 
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
     if (!marg && !lognorm) return GECCO_CRF_OK;
-    ValuedBatch vb;
+    ResidentBatch b;
     const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 0};
-    size_t off[3];
-    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, 1, 1, 1, false, per_gene, 8, vb, off);
-    if (rc || vb.n == 0) {
+    int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, 1, 1, 1, false, per_gene, 8, b);
+    if (rc || b.n == 0) {
         for (int32_t c = 0; !rc && lognorm && c < n_contigs; ++c) lognorm[c] = 0.0;  // (contigs without genes: log Z = 0)
         return rc;
     }
     // (the device always writes both; the caller's missing buffer is simply not fetched)
-    rc = plan_run_marginals_full(vb.plan, vb.d_gene_ptr, vb.d_attr_id, reinterpret_cast<double *>(vb.d + off[0]),
-                                 reinterpret_cast<double *>(vb.d + off[2]), nullptr);
-    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "marginals");
-    rc = valued_fetch(rc, marg, vb.d + off[0], size_t(vb.n) * L * 8, "download marginals");
-    return valued_fetch(rc, lognorm, vb.d + off[2], size_t(n_contigs) * 8, "download lognorm");
+    rc = batch_wait(plan_run_marginals_full(b.plan, b.csr, b.out<double>(0), b.out<double>(2), nullptr), "marginals");
+    rc = batch_fetch(rc, marg, b.out<double>(0), size_t(b.n) * L * 8, "download marginals");
+    return batch_fetch(rc, lognorm, b.out<double>(2), size_t(n_contigs) * 8, "download lognorm");
     GECCO_GUARD_END
 }
 
@@ -918,26 +846,17 @@ GECCO_API int gecco_crf_viterbi_valued(const gecco_crf_model *m, int32_t device,
     if (!m) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    if (!y_out) {
-        if (n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0]) {
-            set_error("null buffer");
-            return GECCO_CRF_EINVAL;
-        }
-        return GECCO_CRF_OK;
-    }
-    ValuedBatch vb;
+    if (!y_out) return check_output(contig_ptr, n_contigs, y_out);  // (no genes: nothing to label)
+    ResidentBatch b;
     const size_t per_gene[2] = {1, 0};
-    size_t off[3];
-    int rc = valued_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, 1, 1, 1, false, per_gene, 8, vb, off);
-    if (rc || vb.n == 0) {
+    int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, 1, 1, 1, false, per_gene, 8, b);
+    if (rc || b.n == 0) {
         for (int32_t c = 0; !rc && score && c < n_contigs; ++c) score[c] = 0.0;
         return rc;
     }
-    rc = plan_run_viterbi(vb.plan, vb.d_gene_ptr, vb.d_attr_id, reinterpret_cast<int8_t *>(vb.d + off[0]),
-                          reinterpret_cast<double *>(vb.d + off[2]), nullptr);
-    if (!rc) rc = check_hip(hipStreamSynchronize(nullptr), "viterbi");
-    rc = valued_fetch(rc, y_out, vb.d + off[0], size_t(vb.n), "download labels");
-    return valued_fetch(rc, score, vb.d + off[2], size_t(n_contigs) * 8, "download score");
+    rc = batch_wait(plan_run_viterbi(b.plan, b.csr, b.out<int8_t>(0), b.out<double>(2), nullptr), "viterbi");
+    rc = batch_fetch(rc, y_out, b.out<int8_t>(0), size_t(b.n), "download labels");
+    return batch_fetch(rc, score, b.out<double>(2), size_t(n_contigs) * 8, "download score");
     GECCO_GUARD_END
 }
 
@@ -1214,11 +1133,6 @@ GECCO_API void gecco_crf_buffer_free(uint8_t *p) { std::free(p); }
 // The three families are argument shapes of one Trainer (crf_train.hpp), and each opaque handle is that Trainer.
 namespace {
 
-int fail(const char *msg) {
-    set_error(msg);
-    return GECCO_CRF_EINVAL;
-}
-
 Trainer *trainer_of(void *h) { return static_cast<Trainer *>(h); }
 const Trainer *trainer_of(const void *h) { return static_cast<const Trainer *>(h); }
 
@@ -1335,7 +1249,44 @@ GECCO_API int64_t gecco_crf_trainer_grid_scratch_bytes(const gecco_crf_trainer_g
 }
 GECCO_API void gecco_crf_trainer_grid_free(gecco_crf_trainer_grid *t) { trainer_close(trainer_of(t)); }
 
-// ---- training with 2 to 32 labels (ABI 2.10.0) -------------------------------------------------
+// ---- training with 2 to 32 labels (ABI 2.10.0), on windows or on whole sequences (2.12.0) ----
+namespace {
+// The two families of TrainerGeneral: `whole` has the sequences themselves as instances (no window, no step).
+struct GeneralFamily {
+    bool whole;
+    const char *no_problem, *null_argument;
+};
+constexpr GeneralFamily kGeneralFamily{false, "trainer general: at least one problem is needed", "trainer general: null argument"};
+constexpr GeneralFamily kSequencesFamily{true, "trainer sequences: at least one problem is needed",
+                                         "trainer sequences: null argument"};
+
+// The create of both families, with and without attribute values (`valued`: attr_value is required, ABI 2.13.0; its entry k
+// holds the values of problem k's attribute entries, or NULL for a problem without).
+template <class Handle>
+int general_open(Handle **out, const GeneralFamily &family, bool valued, int32_t device, int32_t n_problems,
+                 const int32_t *const *seq_ptr, const int32_t *n_seqs, const int32_t *const *item_ptr,
+                 const int32_t *const *attr_id, const double *const *attr_value, const int32_t *const *labels,
+                 const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                 const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features) {
+    if (!out) return GECCO_CRF_EINVAL;
+    *out = nullptr;
+    GECCO_GUARD_BEGIN
+    if (n_problems < 1) return fail(family.no_problem);
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || (valued && !attr_value) || !labels || !num_attrs || !num_labels ||
+        (!family.whole && (!window || !step)) || !state_fid || !trans_fid || !num_features)
+        return fail(family.null_argument);
+    DeviceGuard guard;
+    TrainerGeneral *t = nullptr;
+    const int rc = family.whole ? trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
+                                                           num_labels, state_fid, trans_fid, num_features, &t, attr_value)
+                                : trainer_general_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
+                                                         num_labels, window, step, state_fid, trans_fid, num_features, &t, attr_value);
+    *out = reinterpret_cast<Handle *>(t);
+    return rc;
+    GECCO_GUARD_END
+}
+}  // namespace
+
 GECCO_API int gecco_crf_trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
                                                const int32_t *n_seqs, const int32_t *const *item_ptr,
                                                const int32_t *const *attr_id, const int32_t *const *labels,
@@ -1343,22 +1294,9 @@ GECCO_API int gecco_crf_trainer_general_create(int32_t device, int32_t n_problem
                                                const int32_t *step, const int32_t *const *state_fid,
                                                const int32_t *const *trans_fid, const int32_t *num_features,
                                                gecco_crf_trainer_general **out) {
-    if (!out) return GECCO_CRF_EINVAL;
-    *out = nullptr;
-    GECCO_GUARD_BEGIN
-    if (n_problems < 1) return fail("trainer general: at least one problem is needed");
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !window || !step ||
-        !state_fid || !trans_fid || !num_features)
-        return fail("trainer general: null argument");
-    DeviceGuard guard;
-    TrainerGeneral *t = nullptr;
-    int rc = trainer_general_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
-                                    window, step, state_fid, trans_fid, num_features, &t);
-    *out = reinterpret_cast<gecco_crf_trainer_general *>(t);
-    return rc;
-    GECCO_GUARD_END
+    return general_open(out, kGeneralFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, nullptr, labels, num_attrs,
+                        num_labels, window, step, state_fid, trans_fid, num_features);
 }
-// (ABI 2.13.0) attr_value[k]: the values of problem k's attribute entries, or NULL for a problem without
 GECCO_API int gecco_crf_trainer_general_create_valued(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
                                                       const int32_t *n_seqs, const int32_t *const *item_ptr,
                                                       const int32_t *const *attr_id, const double *const *attr_value,
@@ -1366,20 +1304,8 @@ GECCO_API int gecco_crf_trainer_general_create_valued(int32_t device, int32_t n_
                                                       const int32_t *num_labels, const int32_t *window, const int32_t *step,
                                                       const int32_t *const *state_fid, const int32_t *const *trans_fid,
                                                       const int32_t *num_features, gecco_crf_trainer_general **out) {
-    if (!out) return GECCO_CRF_EINVAL;
-    *out = nullptr;
-    GECCO_GUARD_BEGIN
-    if (n_problems < 1) return fail("trainer general: at least one problem is needed");
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !attr_value || !labels || !num_attrs || !num_labels || !window ||
-        !step || !state_fid || !trans_fid || !num_features)
-        return fail("trainer general: null argument");
-    DeviceGuard guard;
-    TrainerGeneral *t = nullptr;
-    int rc = trainer_general_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
-                                    window, step, state_fid, trans_fid, num_features, &t, attr_value);
-    *out = reinterpret_cast<gecco_crf_trainer_general *>(t);
-    return rc;
-    GECCO_GUARD_END
+    return general_open(out, kGeneralFamily, true, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
+                        num_attrs, num_labels, window, step, state_fid, trans_fid, num_features);
 }
 GECCO_API int gecco_crf_trainer_general_eval(gecco_crf_trainer_general *t, const uint8_t *active, const double *const *w,
                                              double *f, double *const *g) {
@@ -1404,27 +1330,15 @@ GECCO_API void gecco_crf_trainer_general_free(gecco_crf_trainer_general *t) {
     trainer_general_destroy(reinterpret_cast<TrainerGeneral *>(t));
 }
 
-// ---- training on whole sequences (ABI 2.12.0): a TrainerGeneral whose problems have no window ---
+// ---- the whole-sequence family's handle is a TrainerGeneral whose problems have no window ---
 GECCO_API int gecco_crf_trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
                                                  const int32_t *n_seqs, const int32_t *const *item_ptr,
                                                  const int32_t *const *attr_id, const int32_t *const *labels,
                                                  const int32_t *num_attrs, const int32_t *num_labels,
                                                  const int32_t *const *state_fid, const int32_t *const *trans_fid,
                                                  const int32_t *num_features, gecco_crf_trainer_sequences **out) {
-    if (!out) return GECCO_CRF_EINVAL;
-    *out = nullptr;
-    GECCO_GUARD_BEGIN
-    if (n_problems < 1) return fail("trainer sequences: at least one problem is needed");
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !labels || !num_attrs || !num_labels || !state_fid || !trans_fid ||
-        !num_features)
-        return fail("trainer sequences: null argument");
-    DeviceGuard guard;
-    TrainerGeneral *t = nullptr;
-    int rc = trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
-                                      state_fid, trans_fid, num_features, &t);
-    *out = reinterpret_cast<gecco_crf_trainer_sequences *>(t);
-    return rc;
-    GECCO_GUARD_END
+    return general_open(out, kSequencesFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, nullptr, labels,
+                        num_attrs, num_labels, nullptr, nullptr, state_fid, trans_fid, num_features);
 }
 GECCO_API int gecco_crf_trainer_sequences_create_valued(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
                                                         const int32_t *n_seqs, const int32_t *const *item_ptr,
@@ -1433,20 +1347,8 @@ GECCO_API int gecco_crf_trainer_sequences_create_valued(int32_t device, int32_t 
                                                         const int32_t *num_labels, const int32_t *const *state_fid,
                                                         const int32_t *const *trans_fid, const int32_t *num_features,
                                                         gecco_crf_trainer_sequences **out) {
-    if (!out) return GECCO_CRF_EINVAL;
-    *out = nullptr;
-    GECCO_GUARD_BEGIN
-    if (n_problems < 1) return fail("trainer sequences: at least one problem is needed");
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || !attr_value || !labels || !num_attrs || !num_labels || !state_fid ||
-        !trans_fid || !num_features)
-        return fail("trainer sequences: null argument");
-    DeviceGuard guard;
-    TrainerGeneral *t = nullptr;
-    int rc = trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels,
-                                      state_fid, trans_fid, num_features, &t, attr_value);
-    *out = reinterpret_cast<gecco_crf_trainer_sequences *>(t);
-    return rc;
-    GECCO_GUARD_END
+    return general_open(out, kSequencesFamily, true, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
+                        num_attrs, num_labels, nullptr, nullptr, state_fid, trans_fid, num_features);
 }
 GECCO_API int gecco_crf_trainer_sequences_eval(gecco_crf_trainer_sequences *t, const uint8_t *active, const double *const *w,
                                                double *f, double *const *g) {

@@ -497,7 +497,7 @@ namespace {
 constexpr int32_t kGenLongContig = 2048;
 
 // chunk_min_len >= 0: only contigs LONGER than that get chunks (the second table set); -1: every contig
-int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, GenArgs &a, bool whole_contig = false,
+int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig = false,
                   hipStream_t stream = nullptr, int32_t chunk_min_len = -1) {
     const Model &m = *p.model;
     const size_t n = size_t(p.n_genes), L = size_t(m.L);
@@ -591,10 +591,10 @@ int fill_gen_args(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, 
     // on this route reads the state weights' size: gen_small_ok / all_small_ok (gl_windowed_small, gl_windowed_mfma, gl_all_small)
     // and rows_rescale_period below guard the spread of the TRANSITIONS over un-normalised steps, and every sum-product kernel
     // takes the states as exp(state - max state) in (0, 1], whatever the states' size
-    a.v_wmax = p.valued ? p.tables_model->wmax_abs * p.vmax_abs : p.tables_model->wmax_abs;
+    a.v_wmax = csr.attr_value ? p.tables_model->wmax_abs * csr.vmax_abs : p.tables_model->wmax_abs;
     a.v_tmax = p.tables_model->tmax_abs;
-    a.gene_ptr = d_gene_ptr;
-    a.attr_id = d_attr_id;
+    a.gene_ptr = csr.gene_ptr;
+    a.attr_id = csr.attr_id;
     a.wtab = p.tables_model->wtab;
     a.exp_trans = p.tables_model->exp_trans;
     a.trans = p.tables_model->trans;
@@ -745,7 +745,7 @@ const GenRecursion kGenViterbi = {
 
 // The whole-contig recursion `r` of an any-L plan: state scores, then the chunked kernels, a wave per contig, or both side by
 // side (choose_wave_split).  Outputs the recursion does not write are null.
-int run_gen_whole(Plan &p, const GenRecursion &r, const int32_t *d_gene_ptr, const int32_t *d_attr_id, double *d_marg, double *d_lognorm,
+int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *d_marg, double *d_lognorm,
                   int8_t *d_y, double *d_score, hipStream_t stream) {
     const int L = p.model->L;
     int32_t wave_tmax = -1;  // -1: no wave kernel; 0: every contig; > 0: contigs up to this length
@@ -753,7 +753,7 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const int32_t *d_gene_ptr, con
         wave_tmax = choose_wave_split(p, r.forced(), L > r.auto_above, r.t_step(L), r.t_gene(L), r.t_walk(L), r.t_launches(L), p.*r.cache);
     const bool wave = wave_tmax >= 0, tail_chunked = wave_tmax > 0;
     GenArgs g;
-    int rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g, !wave || tail_chunked, stream, tail_chunked ? wave_tmax : -1);
+    int rc = fill_gen_args(p, csr, g, !wave || tail_chunked, stream, tail_chunked ? wave_tmax : -1);
     if (rc) return rc;
     g.marg = d_marg;
     g.lognorm = d_lognorm;
@@ -761,7 +761,7 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const int32_t *d_gene_ptr, con
     g.score = d_score;
     r.clear(g);
     g.wave_tmax = tail_chunked ? wave_tmax : 0;
-    if ((rc = check_hip(launch_gen_state(g, stream, p.valued ? p.d_attr_value : nullptr), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value), "state score launch"))) return rc;
     if (!wave) return check_hip(r.chunked(g, stream), r.what);
     if (!tail_chunked || g.n_chunks <= 0) return check_hip(r.wave(g, stream), r.what);
     // the long tail (chunked kernels: short in work, long in dependent launches) NEXT TO the waves of the other contigs:
@@ -778,8 +778,8 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const int32_t *d_gene_ptr, con
 int fill_seq_args(Plan &p, SeqArgs &a, hipStream_t stream);
 
 // What every run entry point checks before it launches, in the order the checks have always had: a device behind the plan and
-// the label (entry points without one pass 0) ...
-int check_plan(const Plan &p, int32_t label) {
+// the label (entry points without one pass 0), and a batch that brings values exactly when the layout was built for them ...
+int check_plan(const Plan &p, const DeviceCsr &csr, int32_t label) {
     if (p.device < 0) {
         set_error("host-only plan: no HIP device bound (there is no CPU fallback)");
         return GECCO_CRF_ENODEV;
@@ -788,12 +788,17 @@ int check_plan(const Plan &p, int32_t label) {
         set_error("label out of range");
         return GECCO_CRF_EINVAL;
     }
+    if ((csr.attr_value != nullptr) != p.valued) {
+        set_error(p.valued ? "the plan was built for attribute values: the batch has none"
+                           : "attribute values given to a plan that was not built for them");
+        return GECCO_CRF_EINVAL;
+    }
     return GECCO_CRF_OK;
 }
 // ... for the whole-contig entry points the workspace (what pipelined decode calls left there is lost) ...
-int begin_whole_contig(Plan &p, int32_t label, SeqArgs &a, hipStream_t stream) {
+int begin_whole_contig(Plan &p, const DeviceCsr &csr, int32_t label, SeqArgs &a, hipStream_t stream) {
     p.pipe.pending = false;
-    const int rc = check_plan(p, label);
+    const int rc = check_plan(p, csr, label);
     return rc ? rc : fill_seq_args(p, a, stream);
 }
 // ... then a batch with nothing to do, which ends the call without an error, and the caller's buffers.  True: the call ends
@@ -816,21 +821,21 @@ int start_p_out(const Plan &p, double *d_p_out, bool zero, hipStream_t stream) {
     return check_hip(launch_fill_nan(d_p_out, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch");
 }
 
-int run_windowed_general(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int run_windowed_general(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                          hipStream_t stream) {
     if (p.W > kGenMaxW) {
         set_error("window too long for the any-L kernel (alpha of a whole window is LDS-resident: W <= 48)");
         return GECCO_CRF_EUNSUPPORTED;
     }
     GenArgs a;
-    int rc = fill_gen_args(p, d_gene_ptr, d_attr_id, a);
+    int rc = fill_gen_args(p, csr, a);
     if (rc) return rc;
     a.p_out = d_p_out;
     a.label = label;
     if ((rc = start_p_out(p, d_p_out, true, stream))) return rc;
     double *keep_state = a.state;
     a.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(a, stream, p.valued ? p.d_attr_value : nullptr), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(a, stream, csr.attr_value), "state score launch"))) return rc;
     a.state = keep_state;
     if (p.gen_small)
         return check_hip(launch_gen_windowed_small(a, p.model->trans.data(), p.d_tile_desc, p.ntiles, stream), "windowed launch");
@@ -844,24 +849,24 @@ struct PipelinedLaunch {
     const SeqArgs *seq;
     bool *took = nullptr;  // set when the one launch was made (otherwise the caller launches the Viterbi side itself)
 };
-static int run_windowed_impl(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                              double2 *d_state_out, double *d_dstate_out, hipStream_t stream, const PipelinedLaunch *piped = nullptr);
 
-int plan_run_windowed(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int plan_run_windowed(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                       hipStream_t stream) {
-    return run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, nullptr, stream);
+    return run_windowed_impl(p, csr, label, d_p_out, nullptr, nullptr, stream);
 }
 
-static int run_windowed_impl(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                              double2 *d_state_out, double *d_dstate_out, hipStream_t stream, const PipelinedLaunch *piped) {
-    int rc = check_plan(p, label);
-    if (rc || ends_here(p.n_genes == 0, !d_gene_ptr || !d_p_out, rc)) return rc;
+    int rc = check_plan(p, csr, label);
+    if (rc || ends_here(p.n_genes == 0, !csr.gene_ptr || !d_p_out, rc)) return rc;
     if ((rc = use_device(p.device))) return rc;
     const Model &m = *p.model;
-    if (p.general) return run_windowed_general(p, d_gene_ptr, d_attr_id, label, d_p_out, stream);
+    if (p.general) return run_windowed_general(p, csr, label, d_p_out, stream);
     WinArgs a{};
-    a.gene_ptr = d_gene_ptr;
-    a.attr_id = d_attr_id;
+    a.gene_ptr = csr.gene_ptr;
+    a.attr_id = csr.attr_id;
     a.wtab = p.tables_model->wtab;
     a.wtab2 = p.tables_model->wtab2[label];
     a.exp_trans = p.tables_model->exp_trans;
@@ -965,9 +970,9 @@ int all_tiles(Plan &p, const int4 **d_tiles, int32_t *ntiles) {
 
 const char *plan_all_kernel_name(const Plan &p) { return p.model && all_small_tier(p) ? "gl_all_small" : "gl_all_groups"; }
 
-int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t background, double *d_p_all,
+int plan_run_windowed_all(Plan &p, const DeviceCsr &csr, int32_t background, double *d_p_all,
                           double *d_p_any, hipStream_t stream) {
-    int rc = check_plan(p, 0);
+    int rc = check_plan(p, csr, 0);
     if (rc) return rc;
     if (background < -1 || background >= p.model->L) {
         set_error("background label out of range");
@@ -977,7 +982,7 @@ int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_a
         set_error(background < 0 ? "p_any needs a background label" : "null p_any buffer with a background label");
         return GECCO_CRF_EINVAL;
     }
-    if (ends_here(p.n_genes == 0, !d_gene_ptr || !d_p_all, rc)) return rc;
+    if (ends_here(p.n_genes == 0, !csr.gene_ptr || !d_p_all, rc)) return rc;
     if ((rc = use_device(p.device))) return rc;
     const bool small = all_small_tier(p);
     if (!small && p.W > kGenMaxW) {
@@ -985,9 +990,9 @@ int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_a
         return GECCO_CRF_EUNSUPPORTED;
     }
     GenArgs g;
-    if ((rc = fill_gen_args(p, d_gene_ptr, d_attr_id, g))) return rc;
+    if ((rc = fill_gen_args(p, csr, g))) return rc;
     g.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(g, stream, p.valued ? p.d_attr_value : nullptr), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value), "state score launch"))) return rc;
     AllArgs a{};
     a.E = g.E;
     a.exp_trans = g.exp_trans;
@@ -1291,11 +1296,11 @@ namespace {
 // what a caller of run_viterbi_l2 has already left in the plan's workspace
 enum class SeqLeft { nothing, state, dstate };  // ... the state scores (a.state), their differences (a.dstate)
 
-inline void bind_seq_io(const Plan &p, SeqArgs &a, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int8_t *d_y, double *d_score) {
+inline void bind_seq_io(const Plan &p, SeqArgs &a, const DeviceCsr &csr, int8_t *d_y, double *d_score) {
     a.y = d_y;
     a.score = d_score;
-    a.csr_gene_ptr = d_gene_ptr;
-    a.csr_attr_id = d_attr_id;
+    a.csr_gene_ptr = csr.gene_ptr;
+    a.csr_attr_id = csr.attr_id;
     a.csr_wtab01 = p.tables_model->wtab2[1];
     a.csr_n_attrs = p.model->A;
 }
@@ -1335,12 +1340,12 @@ int run_viterbi_l2(Plan &p, const SeqArgs &a, SeqLeft left, bool delta, hipStrea
 }
 }  // namespace
 
-int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, double *d_marg,
+int plan_run_marginals_full(Plan &p, const DeviceCsr &csr, double *d_marg,
                             double *d_lognorm, hipStream_t stream) {
     SeqArgs a;
-    int rc = begin_whole_contig(p, 0, a, stream);
-    if (rc || ends_here(p.n_contigs == 0, p.n_genes > 0 && (!d_gene_ptr || !d_marg), rc)) return rc;
-    if (p.general) return run_gen_whole(p, kGenMarginals, d_gene_ptr, d_attr_id, d_marg, d_lognorm, nullptr, nullptr, stream);
+    int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc || ends_here(p.n_contigs == 0, p.n_genes > 0 && (!csr.gene_ptr || !d_marg), rc)) return rc;
+    if (p.general) return run_gen_whole(p, kGenMarginals, csr, d_marg, d_lognorm, nullptr, nullptr, stream);
     a.marg = d_marg;
     a.lognorm = d_lognorm;
     // 8-byte inputs, alpha in registers: one fused kernel when workgroups own whole contigs, the workgroups' products
@@ -1350,42 +1355,42 @@ int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d
     if (p.seq_short && d_lognorm && p.n_empty_contigs &&
         (rc = check_hip(hipMemsetAsync(d_lognorm, 0, size_t(p.n_contigs) * 8, stream), "memset lognorm")))
         return rc;
-    return check_hip(launch_seq_marginals_short(a, d_gene_ptr, d_attr_id, p.tables_model->wtab2[1], p.model->A, p.d_contig_ptr,
+    return check_hip(launch_seq_marginals_short(a, csr.gene_ptr, csr.attr_id, p.tables_model->wtab2[1], p.model->A, p.d_contig_ptr,
                                                 stream), "marginals launch");
 }
 
-int plan_run_viterbi(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int8_t *d_y, double *d_score,
+int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,
                      hipStream_t stream) {
     SeqArgs a;
-    int rc = begin_whole_contig(p, 0, a, stream);
-    if (rc || ends_here(p.n_contigs == 0, p.n_genes > 0 && (!d_gene_ptr || !d_y), rc)) return rc;
-    if (p.general) return run_gen_whole(p, kGenViterbi, d_gene_ptr, d_attr_id, nullptr, nullptr, d_y, d_score, stream);
-    bind_seq_io(p, a, d_gene_ptr, d_attr_id, d_y, d_score);
+    int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc || ends_here(p.n_contigs == 0, p.n_genes > 0 && (!csr.gene_ptr || !d_y), rc)) return rc;
+    if (p.general) return run_gen_whole(p, kGenViterbi, csr, nullptr, nullptr, d_y, d_score, stream);
+    bind_seq_io(p, a, csr, d_y, d_score);
     return run_viterbi_l2(p, a, SeqLeft::nothing, viterbi_delta_ok(a), stream);
 }
 
-int plan_run_decode(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int plan_run_decode(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                     int8_t *d_y, double *d_score, hipStream_t stream) {
     if (!can_hand_over(p)) {
         // (pipe.pending is only ever set on a plan that can hand over, so it is clear here; plan_run_viterbi clears it all the same)
-        int rc = plan_run_windowed(p, d_gene_ptr, d_attr_id, label, d_p_out, stream);
+        int rc = plan_run_windowed(p, csr, label, d_p_out, stream);
         if (rc) return rc;
-        return plan_run_viterbi(p, d_gene_ptr, d_attr_id, d_y, d_score, stream);
+        return plan_run_viterbi(p, csr, d_y, d_score, stream);
     }
     SeqArgs a;
-    int rc = begin_whole_contig(p, label, a, stream);
-    if (rc || ends_here(p.n_contigs == 0 || p.n_genes == 0, !d_gene_ptr || !d_p_out || !d_y, rc)) return rc;
-    bind_seq_io(p, a, d_gene_ptr, d_attr_id, d_y, d_score);
+    int rc = begin_whole_contig(p, csr, label, a, stream);
+    if (rc || ends_here(p.n_contigs == 0 || p.n_genes == 0, !csr.gene_ptr || !d_p_out || !d_y, rc)) return rc;
+    bind_seq_io(p, a, csr, d_y, d_score);
     // the window tiles leave the state scores, or their differences, where the Viterbi side reads them
     const bool delta = viterbi_delta_ok(a);
     const SeqLeft left = tiles_hand_over(delta, d_score);
-    if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, left == SeqLeft::state ? const_cast<double2 *>(a.state) : nullptr,
+    if ((rc = run_windowed_impl(p, csr, label, d_p_out, left == SeqLeft::state ? const_cast<double2 *>(a.state) : nullptr,
                                 left == SeqLeft::dstate ? const_cast<double *>(a.dstate) : nullptr, stream)))
         return rc;
     return run_viterbi_l2(p, a, left, delta, stream);
 }
 
-int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int plan_run_decode_pipelined(Plan *cur, const DeviceCsr &csr, int32_t label, double *d_p_out,
                               Plan *prev, int8_t *d_prev_y, hipStream_t stream) {
     int rc;
     // ---- the previous batch: labels from the score differences its window tiles left behind (or from its CSR arrays)
@@ -1400,7 +1405,7 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
         if (prev->pipe.pending && !prev->general) {
             if ((rc = fill_seq_args(*prev, pa, stream))) return rc;
             pa.dstate = parity_buffer(*prev, pa, prev->pipe.parity);
-            bind_seq_io(*prev, pa, prev->pipe.gene_ptr, prev->pipe.attr_id, d_prev_y, nullptr);
+            bind_seq_io(*prev, pa, prev->pipe.csr, d_prev_y, nullptr);
             prev_delta = true;
         }
     }
@@ -1408,11 +1413,11 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
         // no score differences left behind (any-L model, contigs outside slot space, or another call used the workspace since):
         // the state scores are summed again from the CSR arrays -- BEFORE this batch's tiles write into the workspace
         const Plan::Pipe keep = prev->pipe;
-        if (!keep.gene_ptr) {
+        if (!keep.csr.gene_ptr) {
             set_error("pipelined decode: the previous plan has not been scored by a pipelined call (or has been rebuilt since)");
             return GECCO_CRF_EINVAL;
         }
-        if ((rc = plan_run_viterbi(*prev, keep.gene_ptr, keep.attr_id, d_prev_y, nullptr, stream))) return rc;
+        if ((rc = plan_run_viterbi(*prev, keep.csr, d_prev_y, nullptr, stream))) return rc;
         prev->pipe = keep;
     }
     // ---- this batch: marginals, and score differences for the next call where the kernels hand them over
@@ -1434,13 +1439,12 @@ int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_
         PipelinedLaunch fl{};
         fl.seq = &pa;
         fl.took = &took;
-        if ((rc = run_windowed_impl(p, d_gene_ptr, d_attr_id, label, d_p_out, nullptr, d_dstate, stream,
+        if ((rc = run_windowed_impl(p, csr, label, d_p_out, nullptr, d_dstate, stream,
                                     (delta && prev_delta) ? &fl : nullptr)))
             return rc;
         p.pipe.pending = delta;
         p.pipe.parity = delta ? parity : p.pipe.parity;
-        p.pipe.gene_ptr = d_gene_ptr;
-        p.pipe.attr_id = d_attr_id;
+        p.pipe.csr = csr;
     }
     if (prev_delta && !took && (rc = run_viterbi_l2(*prev, pa, SeqLeft::dstate, true, stream))) return rc;
     if (prev && prev != cur) prev->pipe.pending = false;

@@ -59,6 +59,15 @@ struct Arena {
     void release();
 };
 
+// One batch's CSR arrays on the device, as every run call takes them: the row pointers and attribute ids, and for a plan laid
+// out with `valued` the value of every attribute entry (parallel to attr_id) with the largest |value| among them, which scales
+// the Viterbi margin's bound on a state score.  The caller keeps the arrays alive until the work is done.
+struct DeviceCsr {
+    const int32_t *gene_ptr = nullptr, *attr_id = nullptr;
+    const double *attr_value = nullptr;
+    double vmax_abs = 1.0;
+};
+
 struct Plan {
     const Model *model = nullptr;
     int device = -1;  // -1: host-only plan (layout queries work, launches return ENODEV)
@@ -118,11 +127,11 @@ struct Plan {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // Pipelined decode (plan_run_decode_pipelined): what the last call left for the next one -- the batch's score differences
-    // in buffer `parity` of the workspace (pending) and the batch's CSR arrays, which the caller keeps alive until then.
+    // in buffer `parity` of the workspace (pending) and the batch's arrays, which the caller keeps alive until then.
     struct Pipe {
         bool pending = false;
         int parity = 0;
-        const int32_t *gene_ptr = nullptr, *attr_id = nullptr;
+        DeviceCsr csr;
     } pipe;
     bool async_tables = false;  // the owner launches everything on ONE stream (batch driver): table uploads are not waited for
     bool tables_by_kernel = false;  // copied tables are fetched from the pinned block by a small launch on the upload stream, not by
@@ -138,12 +147,10 @@ struct Plan {
                                // whole-contig-marginal requests): the environment switch applies to such layouts only
     bool reference_now = false;  // (this layout runs in reference-bits mode: reference_bits, or the environment)
     // Real-valued attributes (the *_valued one-shots).  `valued` is set by the owner before plan_build: the layout
-    // takes the any-L kernels at every label count, 2 included, and reference-bits mode does not apply.  d_attr_value (parallel to
-    // the d_attr_id of the run calls) and vmax_abs (max |value| of the batch, which scales the Viterbi margin's bound on a state
-    // score) are set before a run call.
+    // takes the any-L kernels at every label count, 2 included, and reference-bits mode does not apply.  The values themselves
+    // belong to a batch, not to the layout: they come with every run call (DeviceCsr), which is refused when it brings values
+    // to a layout without `valued`, or none to one with it.
     bool valued = false;
-    const double *d_attr_value = nullptr;
-    double vmax_abs = 1.0;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_windowed_all.hip): the tile table of the lane-per-window tier when the plan's own
@@ -167,24 +174,24 @@ int plan_ensure_seq(Plan &p, hipStream_t stream, bool sync = true);
 int plan_run_segment(Plan &p, const double *d_p, const uint8_t *d_annotated, const SegParams &params, int32_t *d_seg,
                      int32_t max_seg, int32_t *d_seg_off, int32_t *d_total, hipStream_t stream, double *d_gather = nullptr,
                      int32_t gather_cap = 0);
-int plan_run_windowed(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int plan_run_windowed(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                       hipStream_t stream);
 // every label's windowed marginal in one pass: d_p_all [n_genes][L]; d_p_any [n_genes] = the windowed probability of any label
 // but `background`, or null with background == -1 (crf_windowed_all.hip)
-int plan_run_windowed_all(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t background, double *d_p_all,
+int plan_run_windowed_all(Plan &p, const DeviceCsr &csr, int32_t background, double *d_p_all,
                           double *d_p_any, hipStream_t stream);
 const char *plan_all_kernel_name(const Plan &p);
 // windowed marginals + whole-contig Viterbi of the same batch in one pass over the CSR
 // Decode pipelined over batches: enqueue the windowed marginals of `cur`'s batch (cur may be null: flush) and the Viterbi
 // labels of the batch the previous call scored on `prev` (null on the first call; may be the same plan) -- in ONE launch
 // when both sides qualify (2-label model, W = 20, short contigs: crf_decode_pipelined), in separate launches otherwise.
-int plan_run_decode_pipelined(Plan *cur, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int plan_run_decode_pipelined(Plan *cur, const DeviceCsr &csr, int32_t label, double *d_p_out,
                               Plan *prev, int8_t *d_prev_y, hipStream_t stream);
-int plan_run_decode(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label, double *d_p_out,
+int plan_run_decode(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                     int8_t *d_y, double *d_score, hipStream_t stream);
-int plan_run_marginals_full(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, double *d_marg,
+int plan_run_marginals_full(Plan &p, const DeviceCsr &csr, double *d_marg,
                             double *d_lognorm, hipStream_t stream);
-int plan_run_viterbi(Plan &p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int8_t *d_y, double *d_score,
+int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,
                      hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);

@@ -499,7 +499,7 @@ int flush_pending(RunCtx &X, DeviceCtx &D) {
     Lane &pl = *D.pending;
     int rc = check_hip(hipSetDevice(pl.device), "hipSetDevice");
     if (rc) return rc;
-    if ((rc = plan_run_decode_pipelined(nullptr, nullptr, nullptr, X.r.label, nullptr, &pl.plan, pl.y_dst, pl.comp)))
+    if ((rc = plan_run_decode_pipelined(nullptr, {}, X.r.label, nullptr, &pl.plan, pl.y_dst, pl.comp)))
         return rc;
     if ((rc = check_hip(hipEventRecord(pl.ev_comp, pl.comp), "hipEventRecord"))) return rc;
     if ((rc = check_hip(hipStreamWaitEvent(pl.down, pl.ev_comp, 0), "hipStreamWaitEvent"))) return rc;
@@ -757,13 +757,13 @@ int submit_plan(RunCtx &X, Lane &ln, int chunk_index) {
 int run_chunk(RunCtx &X, Lane &ln, const int32_t *d_gp, const int32_t *d_at, double *d_p, int8_t *d_y, double *d_score, bool pair) {
     const int32_t label = X.r.label;
     if (X.windowed && X.viterbi && pair) {
-        int rc = plan_run_decode_pipelined(&ln.plan, d_gp, d_at, label, d_p, nullptr, nullptr, ln.comp);
+        int rc = plan_run_decode_pipelined(&ln.plan, {d_gp, d_at}, label, d_p, nullptr, nullptr, ln.comp);
         if (rc) return rc;
-        return plan_run_decode_pipelined(nullptr, nullptr, nullptr, label, nullptr, &ln.plan, d_y, ln.comp);
+        return plan_run_decode_pipelined(nullptr, {}, label, nullptr, &ln.plan, d_y, ln.comp);
     }
-    if (X.windowed && X.viterbi) return plan_run_decode(ln.plan, d_gp, d_at, label, d_p, d_y, d_score, ln.comp);
-    if (X.windowed) return plan_run_windowed(ln.plan, d_gp, d_at, label, d_p, ln.comp);
-    if (X.viterbi) return plan_run_viterbi(ln.plan, d_gp, d_at, d_y, d_score, ln.comp);
+    if (X.windowed && X.viterbi) return plan_run_decode(ln.plan, {d_gp, d_at}, label, d_p, d_y, d_score, ln.comp);
+    if (X.windowed) return plan_run_windowed(ln.plan, {d_gp, d_at}, label, d_p, ln.comp);
+    if (X.viterbi) return plan_run_viterbi(ln.plan, {d_gp, d_at}, d_y, d_score, ln.comp);
     return GECCO_CRF_OK;
 }
 
@@ -889,7 +889,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     if (piped) {
         // ONE launch per chunk: this chunk's window tiles + the Viterbi workgroups of the chunk this device scored before
         Lane *prev = D.pending;
-        rc = plan_run_decode_pipelined(&ln.plan, d_gp, d_at, r.label, d_p, prev ? &prev->plan : nullptr,
+        rc = plan_run_decode_pipelined(&ln.plan, {d_gp, d_at}, r.label, d_p, prev ? &prev->plan : nullptr,
                                        prev ? prev->y_dst : nullptr, ln.comp);
         if (rc) return rc;
         if ((rc = check_hip(hipEventRecord(ln.ev_comp, ln.comp), "hipEventRecord"))) return rc;
@@ -908,7 +908,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
         d_marg = reinterpret_cast<double *>(ln.d_marg.p);
         if ((rc = ln.d_lognorm.reserve(size_t(nc) * 8, "hipMalloc lognorm"))) return rc;
         d_lognorm = reinterpret_cast<double *>(ln.d_lognorm.p);
-        if ((rc = plan_run_marginals_full(ln.plan, d_gp, d_at, d_marg, d_lognorm, ln.comp))) return rc;
+        if ((rc = plan_run_marginals_full(ln.plan, {d_gp, d_at}, d_marg, d_lognorm, ln.comp))) return rc;
     }
     // (nothing but the rows' few bytes crosses PCIe for a cluster call)
     if (r.want_segments &&
