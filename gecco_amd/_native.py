@@ -225,6 +225,11 @@ SIGNATURES = {
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, _c_i32p, _c_i32p,
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
     ),
+    "gecco_crf_trainer_general_create_partial": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p,
+                       _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
+    ),
     "gecco_crf_trainer_general_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_general_num_problems": (ctypes.c_int32, [_vp]),
     "gecco_crf_trainer_general_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
@@ -240,6 +245,12 @@ SIGNATURES = {
         [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
          ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p,
          ctypes.POINTER(_vp)],
+    ),
+    "gecco_crf_trainer_sequences_create_partial": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+         ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.POINTER(_vp),
+         ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)],
     ),
     "gecco_crf_trainer_sequences_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_sequences_num_problems": (ctypes.c_int32, [_vp]),
@@ -1318,9 +1329,37 @@ class _TrainerHandle:
             keep.append(v if v.size else np.zeros(1, dtype=np.float64))
         return (_vp * len(keep))(*[None if v is None else v.ctypes.data for v in keep]), keep
 
-    def _create_general(self, problems, device, values, whole: bool):
+    @staticmethod
+    def _allowed_table(allowed, item_counts):
+        """``allowed=`` of the general and whole-sequence families: None, or per problem None (a labelled problem) or one
+        uint32 mask per item, bit y set when label y is allowed.  Returns None when no problem has masks (the labelled
+        creates are called), else the table of pointers (NULL for a labelled problem) and the arrays it points to."""
+        if allowed is None or all(a is None for a in allowed):
+            return None, None
+        if len(allowed) != len(item_counts):
+            raise ValueError(f"allowed holds {len(allowed)} entries for {len(item_counts)} problems")
+        keep = []
+        for a, n in zip(allowed, item_counts):
+            if a is None:
+                keep.append(None)
+                continue
+            a = np.asarray(a)
+            if a.dtype.kind not in "ui" or (a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF)):
+                raise ValueError("allowed masks are unsigned 32-bit integers")
+            a = np.ascontiguousarray(a, dtype=np.uint32).ravel()
+            if a.size != n:
+                raise ValueError(f"allowed masks of a problem hold {a.size} entries, the problem {n} items")
+            keep.append(a if a.size else np.zeros(1, dtype=np.uint32))
+        return (_vp * len(keep))(*[None if a is None else a.ctypes.data for a in keep]), keep
+
+    def _create_general(self, problems, device, values, whole: bool, allowed=None):
         """The constructor of the general (``whole=False``: every problem with a window and a step) and the whole-sequence
-        family, on ``create`` or, when a problem has values, on ``create_valued``."""
+        family, on ``create`` or, when a problem has values, on ``create_valued``, or, when a problem has allowed-label
+        masks, on ``create_partial`` (a problem with masks may give None as its labels)."""
+        at, _keep_allowed = self._allowed_table(allowed, [int(np.asarray(p[0])[-1]) for p in problems])
+        if at is not None:  # (the labels of a problem with masks are not read: any array of the right kind will do)
+            problems = [p if a is None or p[3] is not None else (*p[:3], np.zeros(1, dtype=np.int32), *p[4:])
+                        for p, a in zip(problems, allowed)]
         if whole and any(len(p) != 8 for p in problems):
             raise ValueError("a whole-sequence problem has 8 entries: no window and no step")
         arrays, counts = _trainer_sets(problems)
@@ -1330,10 +1369,14 @@ class _TrainerHandle:
         c = {name: _i32_vector(v) for name, v in counts.items()}
         vt, _keep = self._value_table(values, [int(np.asarray(p[2]).size) for p in problems])
         value_table = () if vt is None else (vt,)
+        entry = "create" if vt is None else "create_valued"
+        allowed_table = ()
+        if at is not None:  # (the partial create takes the values' table always: NULL when no problem has values)
+            value_table, allowed_table, entry = (vt,), (at,), "create_partial"
         window_step = () if whole else (c["window"], c["step"])
         self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], *value_table,
-                     t["labels"], c["num_attrs"], c["num_labels"], *window_step, t["state_fid"], t["trans_fid"],
-                     c["num_features"], entry="create" if vt is None else "create_valued")
+                     t["labels"], *allowed_table, c["num_attrs"], c["num_labels"], *window_step, t["state_fid"],
+                     t["trans_fid"], c["num_features"], entry=entry)
         self.num_features = self._features = counts["num_features"]
 
     def __del__(self):
@@ -1468,13 +1511,15 @@ class TrainerGeneral(_TrainerHandle):
     window, step)`` per problem, as ``TrainerGrid`` takes its sets; the label count of a problem is that of its
     ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the active problems; problem k's f and g are bitwise what a
     ``TrainerGeneral`` of problem k alone returns for ``ws[k]``.  ``values=``: per problem None or one float64 per
-    attribute entry, parallel to its ``attr_id`` (``gecco_crf_trainer_general_create_valued``)."""
+    attribute entry, parallel to its ``attr_id`` (``gecco_crf_trainer_general_create_valued``).  ``allowed=``: per problem
+    None (a labelled problem) or one uint32 mask per item, bit y set when label y is allowed: the problem then minimises
+    log Z - log Z_A (``gecco_crf_trainer_general_create_partial``), and its ``labels`` entry is not read and may be None."""
 
     _family = "gecco_crf_trainer_general"
     eval = _TrainerHandle._eval_problems
 
-    def __init__(self, problems, device: int = 0, values=None):
-        self._create_general(problems, device, values, whole=False)
+    def __init__(self, problems, device: int = 0, values=None, allowed=None):
+        self._create_general(problems, device, values, whole=False, allowed=allowed)
 
     def scratch_bytes(self, k: int = -1) -> int:
         """Scratch bytes of problem k; for k = -1 the sum over the problems, which is what is allocated."""
@@ -1488,13 +1533,14 @@ class TrainerSequences(_TrainerHandle):
     ``problems`` holds one tuple ``(seq_ptr, item_ptr, attr_id, labels, num_attrs, state_fid, trans_fid, num_features)``
     per problem; the label count of a problem is that of its ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the
     active problems; problem k's f and g are bitwise what a ``TrainerSequences`` of problem k alone returns for
-    ``ws[k]``.  ``values=``: as ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_valued``)."""
+    ``ws[k]``.  ``values=``: as ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_valued``); ``allowed=``: as
+    ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_partial``)."""
 
     _family = "gecco_crf_trainer_sequences"
     eval = _TrainerHandle._eval_problems
 
-    def __init__(self, problems, device: int = 0, values=None):
-        self._create_general(problems, device, values, whole=True)
+    def __init__(self, problems, device: int = 0, values=None, allowed=None):
+        self._create_general(problems, device, values, whole=True, allowed=allowed)
 
     def num_sequences(self, k: int) -> int:
         return int(self._c("num_sequences")(self._h, int(k)))

@@ -118,7 +118,7 @@ int check_background(const gecco_crf_model *m, int32_t background, const double 
 }  // namespace
 
 GECCO_API const char *gecco_crf_last_error(void) { return last_error(); }
-GECCO_API int gecco_crf_version(void) { return 330; }
+GECCO_API int gecco_crf_version(void) { return 340; }
 
 GECCO_API int gecco_crf_model_load(const uint8_t *lcrf, size_t n_bytes, gecco_crf_model **out) {
     if (!out) return GECCO_CRF_EINVAL;
@@ -1261,26 +1261,30 @@ constexpr GeneralFamily kSequencesFamily{true, "trainer sequences: at least one 
                                          "trainer sequences: null argument"};
 
 // The create of both families, with and without attribute values (`valued`: attr_value is required, ABI 2.13.0; its entry k
-// holds the values of problem k's attribute entries, or NULL for a problem without).
+// holds the values of problem k's attribute entries, or NULL for a problem without), and with allowed-label sets (`partial`:
+// allowed is required, ABI 2.14.0; its entry k holds one mask per item of problem k, or NULL for a labelled problem, and
+// attr_value may then be NULL as a whole: no problem has values).
 template <class Handle>
 int general_open(Handle **out, const GeneralFamily &family, bool valued, int32_t device, int32_t n_problems,
                  const int32_t *const *seq_ptr, const int32_t *n_seqs, const int32_t *const *item_ptr,
                  const int32_t *const *attr_id, const double *const *attr_value, const int32_t *const *labels,
                  const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
-                 const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features) {
+                 const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
+                 bool partial = false, const uint32_t *const *allowed = nullptr) {
     if (!out) return GECCO_CRF_EINVAL;
     *out = nullptr;
     GECCO_GUARD_BEGIN
     if (n_problems < 1) return fail(family.no_problem);
-    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || (valued && !attr_value) || !labels || !num_attrs || !num_labels ||
+    if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || (valued && !attr_value) || (partial && !allowed) || !labels || !num_attrs || !num_labels ||
         (!family.whole && (!window || !step)) || !state_fid || !trans_fid || !num_features)
         return fail(family.null_argument);
     DeviceGuard guard;
     TrainerGeneral *t = nullptr;
     const int rc = family.whole ? trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
-                                                           num_labels, state_fid, trans_fid, num_features, &t, attr_value)
+                                                           num_labels, state_fid, trans_fid, num_features, &t, attr_value, allowed)
                                 : trainer_general_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
-                                                         num_labels, window, step, state_fid, trans_fid, num_features, &t, attr_value);
+                                                         num_labels, window, step, state_fid, trans_fid, num_features, &t, attr_value,
+                                                         allowed);
     *out = reinterpret_cast<Handle *>(t);
     return rc;
     GECCO_GUARD_END
@@ -1306,6 +1310,17 @@ GECCO_API int gecco_crf_trainer_general_create_valued(int32_t device, int32_t n_
                                                       const int32_t *num_features, gecco_crf_trainer_general **out) {
     return general_open(out, kGeneralFamily, true, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
                         num_attrs, num_labels, window, step, state_fid, trans_fid, num_features);
+}
+GECCO_API int gecco_crf_trainer_general_create_partial(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                       const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                       const int32_t *const *attr_id, const double *const *attr_value,
+                                                       const int32_t *const *labels, const uint32_t *const *allowed,
+                                                       const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window,
+                                                       const int32_t *step, const int32_t *const *state_fid,
+                                                       const int32_t *const *trans_fid, const int32_t *num_features,
+                                                       gecco_crf_trainer_general **out) {
+    return general_open(out, kGeneralFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
+                        num_attrs, num_labels, window, step, state_fid, trans_fid, num_features, true, allowed);
 }
 GECCO_API int gecco_crf_trainer_general_eval(gecco_crf_trainer_general *t, const uint8_t *active, const double *const *w,
                                              double *f, double *const *g) {
@@ -1349,6 +1364,16 @@ GECCO_API int gecco_crf_trainer_sequences_create_valued(int32_t device, int32_t 
                                                         gecco_crf_trainer_sequences **out) {
     return general_open(out, kSequencesFamily, true, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
                         num_attrs, num_labels, nullptr, nullptr, state_fid, trans_fid, num_features);
+}
+GECCO_API int gecco_crf_trainer_sequences_create_partial(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                         const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                         const int32_t *const *attr_id, const double *const *attr_value,
+                                                         const int32_t *const *labels, const uint32_t *const *allowed,
+                                                         const int32_t *num_attrs, const int32_t *num_labels,
+                                                         const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                                         const int32_t *num_features, gecco_crf_trainer_sequences **out) {
+    return general_open(out, kSequencesFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
+                        num_attrs, num_labels, nullptr, nullptr, state_fid, trans_fid, num_features, true, allowed);
 }
 GECCO_API int gecco_crf_trainer_sequences_eval(gecco_crf_trainer_sequences *t, const uint8_t *active, const double *const *w,
                                                double *f, double *const *g) {

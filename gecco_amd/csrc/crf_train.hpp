@@ -58,11 +58,15 @@ void trainer_destroy(Trainer *t);
 // The general-label family (gecco_crf_trainer_general_*, crf_train_general.hip): the same objective for 2 to 32 labels,
 // problem k with its own label count, window and step.  Errors carry "trainer general: problem k: ".  attr_value (the
 // *_create_valued entries): null, or per problem the values of its attribute entries, entry k null for a problem without.
+// allowed (the *_create_partial entries): null, or per problem one mask per item, bit y set when label y is allowed, entry k
+// null for a labelled problem.  A problem with masks minimises log Z - log Z_A; its labels[k] is not read,
+// and a mask of 0 or with a bit at or above its label count is refused on the host, naming the problem and the item.
 int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                            const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                            const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                            const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                           TrainerGeneral **out, const double *const *attr_value = nullptr);
+                           TrainerGeneral **out, const double *const *attr_value = nullptr,
+                           const uint32_t *const *allowed = nullptr);
 int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g);
 int32_t trainer_general_num_problems(const TrainerGeneral *t);
 int64_t trainer_general_num_windows(const TrainerGeneral *t, int32_t k);
@@ -77,6 +81,6 @@ int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *
                              const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                              const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
                              const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out,
-                             const double *const *attr_value = nullptr);
+                             const double *const *attr_value = nullptr, const uint32_t *const *allowed = nullptr);
 
 }  // namespace gecco

@@ -19,6 +19,10 @@
 // The whole-sequence family (gecco_crf_trainer_sequences_*) is the same objective with one instance per
 // sequence, of that sequence's own length.  It shares kernels 1, 4, 5 and 6 and replaces 2 and 3 by one kernel,
 // gen_sequences: every item lies in exactly one instance, so that kernel's node marginals are the item marginals.
+//
+// Partially labelled problems (gecco_crf_trainer_{general, sequences}_create_partial) carry a mask of allowed
+// labels per item and minimise log Z - log Z_A.  They replace kernel 2 (or gen_sequences) by gen_partial, which runs the free
+// and the restricted recursion in the same slot and hands on their difference; every other kernel is shared as it is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -341,6 +345,173 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_sequences(GenProb P) {
     if (tid == 0) part[0] = f_sh;
 }
 
+// Partially labelled problems (the *_create_partial problems that carry allowed-label sets): every item
+// has a set of allowed labels, one uint32_t with bit y set when label y is allowed, and the objective is
+//     f(w) = sum over instances of (log Z - log Z_A),   g(w) = E[feature counts] - E_A[feature counts],
+// Z_A and E_A over the paths that stay inside the sets.  This is gen_windows (kWhole: gen_sequences) with a second,
+// restricted recursion run beside the free one in the same slot, position by position: the same work decomposition, the same
+// loops, and what the kernel hands on is the *difference* of the two passes (node marginals free - restricted in the slots
+// the labelled kernels fill, xi free - restricted, f = log Z - log Z_A), so that the item-marginal, attribute-count and
+// block-sum kernels run unchanged and the host's empirical vector is zero.
+// A disallowed label is excluded, not penalised: its restricted log alpha is -inf, and so is what it offers to the backward
+// step.  Every item has an allowed label (create refuses a mask of 0), so every maximum below is taken over at least one
+// finite term: the excluded terms are exp(-inf - finite) = 0 exactly and no -inf - (-inf) can form, however much of the free
+// mass the excluded labels carry.  The restricted log alpha has its own storage, la_a, of the node marginals' shape
+// ([n_win][W][L], whole sequences [n_items][L]).  No barrier and no shuffle beyond the group inside the loops, as before.
+template <int G, bool kWhole>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const uint32_t *allowed, double *la_a) {
+    constexpr int kSlots = kTrainGenThreads / G;  // instances side by side in a workgroup
+    constexpr int kPerBlock = kWhole ? kSlots : kTrainGenWindowsPerBlock;
+    __shared__ double tT[G * G];             // [i][j] = T[i][j]
+    __shared__ double tTt[G * G];            // [j][i] = T[i][j]
+    __shared__ double xi_sh[G * G];          // [j][i]
+    __shared__ double f_sh;
+    const int tid = threadIdx.x;
+    const int L = P.L;
+    const int i = tid % G, slot = tid / G;
+    const bool lab = i < L;
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int a = e / G, b = e % G;
+        const double v = (a < L && b < L) ? P.trans[a * L + b] : 0.0;
+        tT[e] = v;
+        tTt[b * G + a] = v;
+    }
+    __syncthreads();
+
+    double xacc[G];
+#pragma unroll
+    for (int k = 0; k < G; ++k) xacc[k] = 0.0;
+    double facc = 0.0;
+    double v[G];
+    const int64_t w_base = static_cast<int64_t>(blockIdx.x) * kPerBlock;
+    for (int r = 0; r < kPerBlock / kSlots; ++r) {
+        const int64_t w = w_base + r * kSlots + slot;
+        if (w >= P.n_win) continue;  // (a whole group of G lanes: the shuffles below stay inside the group)
+        const int64_t i0 = P.win_start[w];
+        const int n = kWhole ? P.win_len[w] : P.W;
+        const double *sc = P.score + i0 * L;
+        const uint32_t *al = allowed + i0;
+        const int64_t m0 = kWhole ? i0 * L : w * n * L;
+        double *mw = (kWhole ? P.item_marg : P.marg) + m0;  // free log alpha, then the difference of the marginals
+        double *ma = la_a + m0;                              // restricted log alpha
+
+        double la = lab ? sc[i] : 0.0;
+        double lr = (lab && ((al[0] >> i) & 1u)) ? la : -INFINITY;
+        if (lab) mw[i] = la, ma[i] = lr;
+        for (int t = 1; t < n; ++t) {
+            const double s = lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0;
+            double mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = __shfl(la, k, G) + tT[k * G + i];
+                    mx = fmax(mx, v[k]);
+                }
+            double sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) sum += exp(v[k] - mx);
+            la = mx + log(sum) + s;
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = __shfl(lr, k, G) + tT[k * G + i];
+                    mx = fmax(mx, v[k]);
+                }
+            sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) sum += exp(v[k] - mx);
+            lr = (lab && ((al[t] >> i) & 1u)) ? mx + log(sum) + s : -INFINITY;
+            if (lab) mw[static_cast<int64_t>(t) * L + i] = la, ma[static_cast<int64_t>(t) * L + i] = lr;
+        }
+        double mx = -INFINITY, mxr = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            if (k < L) mx = fmax(mx, __shfl(la, k, G)), mxr = fmax(mxr, __shfl(lr, k, G));
+        double sum = 0.0, sumr = 0.0;
+#pragma unroll
+        for (int k = 0; k < G; ++k)
+            if (k < L) sum += exp(__shfl(la, k, G) - mx), sumr += exp(__shfl(lr, k, G) - mxr);
+        const double logz = mx + log(sum), logzr = mxr + log(sumr);
+        if (i == 0) facc += logz - logzr;
+
+        if (lab) mw[static_cast<int64_t>(n - 1) * L + i] = exp(la - logz) - exp(lr - logzr);
+        double lb = 0.0, lbr = 0.0;
+        for (int t = n - 1; t >= 1; --t) {
+            const double s = lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0;
+            const double q = s + lb;                                                // log of exp(s_t[i]) beta_t[i]
+            const double qr = (lab && ((al[t] >> i) & 1u)) ? s + lbr : -INFINITY;  // the same, restricted
+            const double lap = lab ? mw[static_cast<int64_t>(t - 1) * L + i] : 0.0;  // log alpha_{t-1}[i], stored by this lane
+            const double lapr = lab ? ma[static_cast<int64_t>(t - 1) * L + i] : -INFINITY;
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = tTt[k * G + i] + __shfl(q, k, G);
+                    mx = fmax(mx, v[k]);
+                }
+            sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = exp(v[k] - mx);
+                    sum += v[k];
+                }
+            lb = mx + log(sum);
+            const double m = exp(lap + lb - logz);
+            const double c = m / sum;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) xacc[k] += c * v[k];
+            mx = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = tTt[k * G + i] + __shfl(qr, k, G);
+                    mx = fmax(mx, v[k]);
+                }
+            sum = 0.0;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) {
+                    v[k] = exp(v[k] - mx);
+                    sum += v[k];
+                }
+            lbr = mx + log(sum);
+            const double mr = exp(lapr + lbr - logzr);  // (a label excluded at t - 1: exp(-inf) = 0)
+            const double cr = mr / sum;
+#pragma unroll
+            for (int k = 0; k < G; ++k)
+                if (k < L) xacc[k] -= cr * v[k];
+            if (lab) mw[static_cast<int64_t>(t - 1) * L + i] = m - mr;
+        }
+    }
+
+    // every group has left its loops: the slots of a wave by a butterfly, then the waves in wave order (as gen_windows)
+    for (int off = 32; off >= G; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
+        facc += __shfl_xor(facc, off);
+    }
+    const int wave = tid / 64, lane = tid % 64;
+    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
+        if (wave == wv && lane < G) {
+#pragma unroll
+            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
+            if (lane == 0) f_sh = (wv ? f_sh : 0.0) + facc;
+        }
+        __syncthreads();
+    }
+    double *part = P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L);
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int k = e / G, a = e % G;
+        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
+    }
+    if (tid == 0) part[0] = f_sh;
+}
+
 __global__ void __launch_bounds__(kTrainGenThreads) gen_item_marginals(GenProb P) {
     const int64_t idx = static_cast<int64_t>(blockIdx.x) * kTrainGenThreads + threadIdx.x;
     if (idx >= static_cast<int64_t>(P.n_items) * P.L) return;
@@ -443,6 +614,9 @@ struct TrainerGeneral {
         // a problem with values: its slice of d_attr_value (parallel to attr_id); the values in transposed order (parallel to
         // attr_items) are the last nnz doubles of its scratch, written once by create.  val0 < 0: no values
         int64_t val0 = -1, nnz = 0;
+        // a partially labelled problem: its slice of d_allowed (one mask per item), and the doubles of its second log alpha
+        // array, which lies behind the slabs.  allow0 < 0: a labelled problem
+        int64_t allow0 = -1, la_a = 0;
         std::vector<int32_t> state_fid, trans_fid;
         std::vector<double> empirical;
     };
@@ -452,6 +626,7 @@ struct TrainerGeneral {
     int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr, *d_win_len = nullptr;
     int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr, *d_attr_ptr = nullptr, *d_attr_items = nullptr;
     double *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_attr_value = nullptr;
+    uint32_t *d_allowed = nullptr;
 
     ~TrainerGeneral() {
         if (!stream) return;  // refused before the device was checked: nothing to free, and no HIP call
@@ -460,7 +635,7 @@ struct TrainerGeneral {
         (void)hipSetDevice(device);
         for (void *p : {(void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start, (void *)d_win_len,
                         (void *)d_iw_first, (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items,
-                        (void *)d_in, (void *)d_out, (void *)d_scratch, (void *)d_attr_value})
+                        (void *)d_in, (void *)d_out, (void *)d_scratch, (void *)d_attr_value, (void *)d_allowed})
             if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
         if (restore && prev >= 0) (void)hipSetDevice(prev);
@@ -470,12 +645,13 @@ struct TrainerGeneral {
 namespace {
 
 // Both families' create: window == nullptr is the whole-sequence family.  attr_value: null, or per problem the values of its
-// attribute entries (entry k null: problem k has none, and runs the unvalued kernels).
+// attribute entries (entry k null: problem k has none, and runs the unvalued kernels).  allowed: null, or per problem one mask
+// per item (entry k null: problem k is labelled, and runs the labelled kernels); labels[k] of a problem with masks is not read.
 int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                          const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                          const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                          const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                         const double *const *attr_value, TrainerGeneral **out) {
+                         const double *const *attr_value, const uint32_t *const *allowed, TrainerGeneral **out) {
     auto t = std::make_unique<TrainerGeneral>();
     t->device = device;
     const bool whole = t->whole = window == nullptr;
@@ -483,16 +659,33 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
     std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, win_len_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c,
         attr_items_c;
     std::vector<double> attr_value_c;
+    std::vector<uint32_t> allowed_c;
     std::vector<std::vector<double>> transposed(static_cast<size_t>(n_problems));  // (attr_item_value of the valued problems)
     int64_t in_total = 0, out_total = 0, scratch_total = 0;
     for (int32_t k = 0; k < n_problems; ++k) {
         HostProblem hp;
-        int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], labels[k], num_attrs[k], num_labels[k],
+        const uint32_t *masks = allowed ? allowed[k] : nullptr;
+        // (a problem with masks has no gold path: build_problem gets label 0 on every item, and the counts it takes from them
+        // are dropped below)
+        std::vector<int32_t> no_labels;
+        if (masks && seq_ptr[k] && n_seqs[k] >= 0) no_labels.assign(size_t(std::max(seq_ptr[k][n_seqs[k]], 1)), 0);
+        int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], masks ? no_labels.data() : labels[k], num_attrs[k], num_labels[k],
                                whole ? 0 : window[k], whole ? 0 : step[k], state_fid[k], trans_fid[k], num_features[k],
                                kTrainGenMaxL, &hp, whole, attr_value ? attr_value[k] : nullptr);
         if (rc) {
             set_error(family + std::to_string(k) + ": " + last_error());
             return rc;
+        }
+        if (masks) {
+            const uint32_t beyond = num_labels[k] >= 32 ? 0u : ~0u << num_labels[k];  // the bits at or above L
+            for (int32_t i = 0; i < hp.n_items; ++i) {
+                if (masks[i] == 0)
+                    return fail(family + std::to_string(k) + ": item " + std::to_string(i) + " allows no label (a mask of 0)");
+                if (masks[i] & beyond)
+                    return fail(family + std::to_string(k) + ": item " + std::to_string(i) + " allows a label at or above num_labels = " +
+                                std::to_string(num_labels[k]) + " (mask " + std::to_string(masks[i]) + ")");
+            }
+            std::fill(hp.empirical.begin(), hp.empirical.end(), 0.0);  // both passes are expectations: nothing is observed
         }
         TrainerGeneral::Prob p;
         p.A = hp.A, p.n_items = hp.n_items, p.K = hp.K, p.L = num_labels[k];
@@ -510,8 +703,15 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
         p.aptr0 = int64_t(attr_ptr_c.size());
         p.in0 = in_total, p.out0 = out_total, p.sc0 = scratch_total;
         // scratch: item scores and item marginals [n_items][L], node marginals [n_win][W][L] (none for whole sequences:
-        // W = 0), blocks and slabs of (f, xi); with values, one double per attribute entry (the transposed values)
+        // W = 0), blocks and slabs of (f, xi); with masks, a second log alpha array; with values, one double per attribute entry
+        // (the transposed values)
         p.scratch = 2 * int64_t(p.n_items) * p.L + hp.n_win * p.W * p.L + (nb + kTrainGenReduceSlabs) * cols;
+        if (masks) {  // the restricted pass's log alpha, of the node marginals' shape
+            p.allow0 = int64_t(allowed_c.size());
+            p.la_a = whole ? int64_t(p.n_items) * p.L : hp.n_win * p.W * p.L;
+            p.scratch += p.la_a;
+            allowed_c.insert(allowed_c.end(), masks, masks + hp.n_items);
+        }
         if (attr_value && attr_value[k]) {  // a problem with values: the transposed values behind everything else
             p.val0 = int64_t(attr_value_c.size());
             p.nnz = int64_t(hp.attr_value.size());
@@ -569,6 +769,7 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
                         "trainer alloc")))
         return rc;
     if ((rc = dev_upload(&t->d_attr_value, attr_value_c, "trainer upload"))) return rc;
+    if ((rc = dev_upload(&t->d_allowed, allowed_c, "trainer upload"))) return rc;
     for (int32_t k = 0; k < n_problems; ++k) {
         const TrainerGeneral::Prob &p = t->probs[size_t(k)];
         if (p.val0 < 0 || p.nnz == 0) continue;
@@ -587,19 +788,19 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
                            const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                            const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                            const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                           TrainerGeneral **out, const double *const *attr_value) {
+                           TrainerGeneral **out, const double *const *attr_value, const uint32_t *const *allowed) {
     if (!window || !step) return fail("trainer general: null argument");
     return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
-                                step, state_fid, trans_fid, num_features, attr_value, out);
+                                step, state_fid, trans_fid, num_features, attr_value, allowed, out);
 }
 
 int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                              const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                              const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
                              const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out,
-                             const double *const *attr_value) {
+                             const double *const *attr_value, const uint32_t *const *allowed) {
     return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, nullptr,
-                                nullptr, state_fid, trans_fid, num_features, attr_value, out);
+                                nullptr, state_fid, trans_fid, num_features, attr_value, allowed, out);
 }
 
 int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
@@ -666,7 +867,29 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
                 gen_item_scores<true><<<nb_items, kTrainGenThreads, 0, st>>>(a, attr_value);
             else
                 gen_item_scores<false><<<nb_items, kTrainGenThreads, 0, st>>>(a, nullptr);
-            if (t->whole) {
+            if (p.allow0 >= 0) {  // a problem with masks: both passes in one kernel, which hands on their difference
+                const uint32_t *al = t->d_allowed + p.allow0;
+                double *la_a = a.slab + kTrainGenReduceSlabs * cols;
+                const unsigned nb = unsigned(p.n_blocks);
+                if (t->whole) {
+                    switch (G) {
+                        case 2: gen_partial<2, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        case 4: gen_partial<4, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        case 8: gen_partial<8, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        case 16: gen_partial<16, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        default: gen_partial<32, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                    }
+                } else {
+                    switch (G) {
+                        case 2: gen_partial<2, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        case 4: gen_partial<4, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        case 8: gen_partial<8, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        case 16: gen_partial<16, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                        default: gen_partial<32, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
+                    }
+                    gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
+                }
+            } else if (t->whole) {
                 switch (G) {
                     case 2: gen_sequences<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
                     case 4: gen_sequences<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;

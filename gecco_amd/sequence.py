@@ -64,12 +64,16 @@ class SequenceCRF:
     # ---- training
     def fit(self, X: Sequence[Iterable[Iterable[str]]], y: Sequence[Sequence[str]]) -> "SequenceCRF":
         """``X``: sequences of items; an item is an iterable of attribute names, or a dict / a list of ``(name, value)``
-        pairs (``train.item_attributes``), as in every prediction method."""
+        pairs (``train.item_attributes``), as in every prediction method.  An entry of ``y`` is a label, a ``set`` /
+        ``frozenset`` / ``list`` / ``tuple`` of labels (the labels allowed on that item) or None (every label): with any
+        entry that is not one label the fit maximises the marginal likelihood of the allowed paths
+        (``train.build_training_set``)."""
         seqs = []
         for xseq in X:  # (a sequence with values goes to the training set as (name, value) pairs, one without as names)
             names, values = _items(xseq)
             seqs.append(names if values is None else [list(zip(nm, v)) for nm, v in zip(names, values)])
-        labs = [[str(lab) for lab in yseq] for yseq in y]
+        labs = [[None if lab is None else frozenset(str(m) for m in lab) if isinstance(lab, (set, frozenset, list, tuple))
+                 else str(lab) for lab in yseq] for yseq in y]
         if len(seqs) != len(labs):
             raise ValueError(f"X holds {len(seqs)} sequences and y {len(labs)}")
         for k, (items, ls) in enumerate(zip(seqs, labs)):

@@ -88,15 +88,23 @@ def _pseudo_gradient(x: np.ndarray, g: np.ndarray, c1: float) -> np.ndarray:
 def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarray, c1: float = 0.0,
              num_memories: int = 6, epsilon: float = 1e-5, period: int = 10, delta: float = 1e-5,
              max_iterations: Optional[int] = None, max_linesearch: int = 20,
-             callback: Optional[Callable[[int, float, np.ndarray], None]] = None) -> OptimizeResult:
+             callback: Optional[Callable[[int, float, np.ndarray], None]] = None,
+             skip_nonpositive_curvature: bool = False) -> OptimizeResult:
     """Minimise ``fg(x)[0] + c1 * |x|_1`` with L-BFGS (``c1 = 0``) or OWL-QN (``c1 > 0``), libLBFGS's algorithm.
     ``fg`` returns the smooth part of the objective and its gradient.  Stops on the gradient test, the delta test, the
     iteration limit, or a failed line search (status "line search failed": the point before that search is returned, as
     libLBFGS does; near the optimum this is where the objective's rounding hides any further decrease).  A trial point
     whose f or g is not finite fails the sufficient-decrease test, so the step is halved: it is never accepted.  A start
-    ``x0`` whose f or g is not finite raises ``ValueError``.  This drives ``minimize_steps`` with ``fg``."""
+    ``x0`` whose f or g is not finite raises ``ValueError``.  This drives ``minimize_steps`` with ``fg``.
+
+    ``skip_nonpositive_curvature`` (for objectives that are not convex; off by default, and then every iterate is what it
+    always was): a correction pair with y.s <= 0 is not stored, the usual safeguard.  The Wolfe search of ``c1 = 0`` forces
+    y.s > 0 on every accepted step, but OWL-QN's search only backtracks, so on a non-convex objective it can accept a step
+    with y.s <= 0, and the two-loop recursion then divides by it.  The direction after a skipped pair comes from the pairs
+    already stored (steepest descent, with libLBFGS's first step 1 / |d|, when there is none)."""
     steps = minimize_steps(x0, c1=c1, num_memories=num_memories, epsilon=epsilon, period=period, delta=delta,
-                           max_iterations=max_iterations, max_linesearch=max_linesearch, callback=callback)
+                           max_iterations=max_iterations, max_linesearch=max_linesearch, callback=callback,
+                           skip_nonpositive_curvature=skip_nonpositive_curvature)
     try:
         x = next(steps)
         while True:
@@ -107,7 +115,8 @@ def minimize(fg: Callable[[np.ndarray], Tuple[float, np.ndarray]], x0: np.ndarra
 
 def minimize_steps(x0: np.ndarray, c1: float = 0.0, num_memories: int = 6, epsilon: float = 1e-5, period: int = 10,
                    delta: float = 1e-5, max_iterations: Optional[int] = None, max_linesearch: int = 20,
-                   callback: Optional[Callable[[int, float, np.ndarray], None]] = None
+                   callback: Optional[Callable[[int, float, np.ndarray], None]] = None,
+                   skip_nonpositive_curvature: bool = False
                    ) -> Generator[np.ndarray, Tuple[float, np.ndarray], OptimizeResult]:
     """``minimize`` in stepping form, for driving several optimisations in lock-step: a generator that yields every
     point to evaluate, takes ``(f, g)`` of the smooth part there back through ``send``, and returns the
@@ -201,20 +210,29 @@ def minimize_steps(x0: np.ndarray, c1: float = 0.0, num_memories: int = 6, epsil
         # ---- L-BFGS direction (two-loop recursion on the smooth gradient's differences)
         s, y = x - xp, g - gp
         ys, yy = float(np.dot(y, s)), float(np.dot(y, y))
-        mem_s.append(s)
-        mem_y.append(y)
-        mem_ys.append(ys)
-        if len(mem_s) > num_memories:
-            mem_s.pop(0)
-            mem_y.pop(0)
-            mem_ys.pop(0)
+        if not (skip_nonpositive_curvature and not ys > 0):  # (a pair without positive curvature: not stored, on request)
+            mem_s.append(s)
+            mem_y.append(y)
+            mem_ys.append(ys)
+            scale = ys / yy
+            if len(mem_s) > num_memories:
+                mem_s.pop(0)
+                mem_y.pop(0)
+                mem_ys.pop(0)
         d = -pg
+        if not mem_s:  # (only after a skipped first pair: steepest descent again, with the first iteration's step)
+            if c1 > 0:
+                d = np.where(d * pg >= 0, 0.0, d)
+            dnorm = float(np.linalg.norm(d))
+            step = 1.0 / dnorm if dnorm > 0 else 1.0
+            k += 1
+            continue
         alphas = []
         for si, yi, ysi in zip(reversed(mem_s), reversed(mem_y), reversed(mem_ys)):
             a = float(np.dot(si, d)) / ysi
             alphas.append(a)
             d = d - a * yi
-        d = d * (ys / yy)
+        d = d * scale
         for si, yi, ysi, a in zip(mem_s, mem_y, mem_ys, reversed(alphas)):
             b = float(np.dot(yi, d)) / ysi
             d = d + (a - b) * si
@@ -233,9 +251,13 @@ class TrainingSet:
     ``state_label``, ``trans_src``, ``trans_dst``: the generated features (state features first, feature id = position);
     ``state_fid`` [A, L] / ``trans_fid`` [L, L]: feature id of every pair, -1 where there is none.  ``attr_value``: the value
     of every attribute entry (float64, parallel to ``attr_id``), or None when every item was plain names (each entry then
-    weighs 1, and the set trains on the unvalued kernels)."""
+    weighs 1, and the set trains on the unvalued kernels).  ``allowed``: one uint32 mask per item, bit y set when label y is
+    allowed on it, or None when every item has exactly one label (a labelled set, which trains on the labelled kernels); a set
+    with ``allowed`` is partially labelled, trains by marginal likelihood, and its ``labels`` hold every item's lowest allowed
+    id, which nothing reads."""
 
     attr_value = None  # (a set built without the field has no values)
+    allowed = None     # (and is labelled)
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -329,6 +351,18 @@ def item_attributes(item) -> Tuple[List[str], Optional[List[float]]]:
     return [name for name, _ in pairs], [value for _, value in pairs]
 
 
+def _label_entry(entry):
+    """One entry of ``sequence_labels`` as a tuple of label names, in the order their ids are assigned, or None for "every
+    label": a plain label is itself, a set / frozenset / list / tuple of labels is its names sorted (duplicates once)."""
+    if entry is None:
+        return None
+    if isinstance(entry, (set, frozenset, list, tuple)):
+        if len(entry) == 0:
+            raise ValueError("an item's set of allowed labels is empty: every item needs at least one label")
+        return tuple(sorted(set(entry)))
+    return (entry,)
+
+
 def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_labels: Sequence[Sequence[str]],
                        window: Optional[int] = None, step: Optional[int] = None, min_freq: float = 0.0,
                        all_possible_states: bool = False, all_possible_transitions: bool = False,
@@ -342,7 +376,16 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
 
     ``window=None``: the instances are the whole sequences, of any length from one item up (``step`` is not read, and the
     set's ``window`` and ``step`` are None): a state feature's frequency is its plain count, a transition's its count over
-    adjacent pairs.  An empty sequence raises ``ValueError``."""
+    adjacent pairs.  An empty sequence raises ``ValueError``.
+
+    Partial labels: an entry of ``sequence_labels`` may also be a ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels,
+    the labels allowed on that item, or None, every label of the set.  Label ids follow first appearance as ever, the names
+    inside a set scanned in sorted order (None names no label).  A feature is generated when some allowed path of some
+    instance fires it: state (a, y) when a sits on a covered item whose set holds y, transition (i, j) when two adjacent items
+    inside an instance hold i and j; its frequency is the sum over those occurrences of value x coverage (pair coverage
+    for a transition).  The set then has ``allowed`` and trains by marginal likelihood (``fit_training_set``).  A set whose
+    entries all name one label, however written, is the labelled set it always was, without ``allowed``.  An empty set is a
+    ``ValueError``, and so is a None where fewer than 2 labels occur overall."""
     if not 2 <= int(max_labels) <= MAX_LABELS:
         raise ValueError(f"max_labels must lie in 2..{MAX_LABELS}, got {max_labels}")
     whole = window is None
@@ -354,6 +397,10 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
     converted = [[item_attributes(item) for item in items] for items in sequences]
     valued = any(vals is not None for items in converted for _, vals in items)
     sequences = [[names for names, _ in items] for items in converted]
+    entries = [[_label_entry(lab) for lab in labs] for labs in sequence_labels]
+    partial = any(e is None or len(e) != 1 for labs in entries for e in labs)
+    if not partial:  # (every item names one label: the labels as they are given, or the one member of a set)
+        sequence_labels = [[e[0] for e in labs] for labs in entries]
     label_index: Dict[str, int] = {}
     attr_index: Dict[str, int] = {}
     covs = []
@@ -367,8 +414,14 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
             for name in names:
                 if name not in attr_index:
                     attr_index[name] = len(attr_index)
-            if lab not in label_index:
-                label_index[lab] = len(label_index)
+            if not partial:
+                if lab not in label_index:
+                    label_index[lab] = len(label_index)
+        if partial:  # (the same scan, over the names of every covered item's set)
+            for e, c in zip(entries[len(covs) - 1], cov.tolist()):
+                for lab in (e or ()) if c else ():
+                    if lab not in label_index:
+                        label_index[lab] = len(label_index)
     if max_labels == 2 and len(label_index) != 2:
         raise ValueError(f"training needs exactly 2 labels, found {len(label_index)} ({sorted(label_index)}): "
                          "GECCO's protein and domain modes are binary")
@@ -380,15 +433,21 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
     attr_id: List[int] = []
     labels: List[int] = []
     attr_value: List[float] = []
-    for items, labs, conv in zip(sequences, sequence_labels, converted):
-        for names, lab, (_, vals) in zip(items, labs, conv):
+    masks: List[int] = []
+    for items, labs, conv, ents in zip(sequences, sequence_labels, converted, entries):
+        for names, lab, (_, vals), e in zip(items, labs, conv, ents):
             # (names outside the dictionary can only sit on items no window covers: they carry no weight)
             attr_id.extend(attr_index[nm] for nm in names if nm in attr_index)
             if valued:  # (an item of plain names inside a valued set: every value is 1)
                 vals = vals if vals is not None else [1.0] * len(names)
                 attr_value.extend(v for nm, v in zip(names, vals) if nm in attr_index)
             item_ptr.append(len(attr_id))
-            labels.append(label_index.get(lab, 0))
+            if partial:  # (names outside the dictionary sit on items no window covers, whose mask nothing trains on)
+                mask = (1 << L) - 1 if e is None else sum(1 << label_index[nm] for nm in e if nm in label_index)
+                masks.append(mask or 1)
+                labels.append((masks[-1] & -masks[-1]).bit_length() - 1)
+            else:
+                labels.append(label_index.get(lab, 0))
         seq_ptr.append(len(labels))
     seq_ptr_a = np.array(seq_ptr, dtype=np.int32)
     item_ptr_a = np.array(item_ptr, dtype=np.int64)
@@ -415,6 +474,24 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
         pair = lab_a[b:e - 1] * L + lab_a[b + 1:e]
         np.add.at(trans_freq, pair, pc.astype(np.float64))
         trans_seen[pair[pc > 0]] = True
+    if partial:  # one rule for both kinds of feature: some allowed path of some instance fires it (in place of the above)
+        ok = ((np.array(masks, dtype=np.uint64)[:, None] >> np.arange(L, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool)
+        state_freq = np.zeros((A, L), dtype=np.float64)
+        np.add.at(state_freq, attr_a, occ_freq[:, None] * ok[occ_item])
+        state_freq = state_freq.ravel()
+        state_seen = np.zeros((A, L), dtype=bool)
+        covered = cov_a[occ_item] > 0
+        np.logical_or.at(state_seen, attr_a[covered], ok[occ_item[covered]])
+        state_seen = state_seen.ravel()
+        trans_freq = np.zeros((L, L), dtype=np.float64)
+        trans_seen = np.zeros((L, L), dtype=bool)
+        for s in range(len(seq_ptr) - 1):
+            b, e = seq_ptr[s], seq_ptr[s + 1]
+            pc = np.ones(e - b - 1, dtype=np.int64) if whole else _pair_coverage(e - b, window, step)
+            pairs = ok[b:e - 1, :, None] & ok[b + 1:e, None, :]  # [positions, L, L]
+            trans_freq += (pairs * pc[:, None, None].astype(np.float64)).sum(axis=0)
+            trans_seen |= pairs[pc > 0].any(axis=0)
+        trans_freq, trans_seen = trans_freq.ravel(), trans_seen.ravel()
     if all_possible_states:
         state_seen[:] = True
     if all_possible_transitions:
@@ -432,7 +509,7 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
         labels=lab_a.astype(np.int32), labels_=list(label_index), attrs_=list(attr_index),
         state_attr=s_idx // L, state_label=s_idx % L, trans_src=t_idx // L, trans_dst=t_idx % L,
         state_fid=state_fid.reshape(A, L), trans_fid=trans_fid.reshape(L, L), window=window, step=step,
-        attr_value=val_a,
+        attr_value=val_a, allowed=np.array(masks, dtype=np.uint32) if partial else None,
     )
 
 
@@ -441,12 +518,20 @@ def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0
     """Optimise the weights of the generated features on the device: L-BFGS / OWL-QN from w = 0.  A set of whole
     sequences (``window is None``) takes ``_native.TrainerSequences`` at any label count; of the windowed sets, one of two
     labels takes the 2-label trainer, one of more labels ``_native.TrainerGeneral``.  A set with values (``attr_value``)
-    takes ``TrainerGeneral`` at any label count, 2 included, or ``TrainerSequences``, with its values."""
+    takes ``TrainerGeneral`` at any label count, 2 included, or ``TrainerSequences``, with its values.
+
+    A partially labelled set (``allowed``) goes the same two ways with its masks and minimises the marginal likelihood
+    log Z - log Z_A, which is not convex: the optimiser then skips correction pairs without positive curvature
+    (``minimize``'s ``skip_nonpositive_curvature``; labelled fits keep their iterates bit for bit).  It starts at w = 0 like
+    every fit.  There every label scores alike, so an item's restricted marginal is uniform over its set: a set in which no
+    item names a single label has a zero gradient at 0 and the fit returns "converged" at w = 0."""
     from . import _native
 
     args = ts.native_args()
     # (a set with values: the general kernels at any label count; one without: the calls they always were)
     valued = {} if ts.attr_value is None else {"values": [ts.attr_value]}
+    if ts.allowed is not None:
+        valued["allowed"] = [ts.allowed]
     if ts.window is None:
         trainer = _native.TrainerSequences([args], device=device, **valued)
     elif ts.num_labels == 2 and not valued:
@@ -461,13 +546,20 @@ def _valued_entries(ts: TrainingSet) -> int:
     return 0 if ts.attr_value is None else int(len(ts.attr_value))
 
 
+def _general_trainer(ts: TrainingSet) -> bool:
+    """A windowed set that takes ``_native.TrainerGeneral`` at any label count: one with values or with allowed-label masks."""
+    return ts.attr_value is not None or ts.allowed is not None
+
+
 def _general_scratch_bytes(ts: TrainingSet) -> int:
     """The scratch ``_native.TrainerGeneral`` allocates for ``ts`` (``scratch_bytes(k)``; the formula of DESIGN.md §4.9b:
     item scores and marginals, node marginals, and one (f, xi) block per 128 windows plus 32 slabs)."""
     L, W = ts.num_labels, ts.window
     n = np.diff(np.asarray(ts.seq_ptr, dtype=np.int64))
     windows = int(np.sum((n[n >= W] - W) // ts.step + 1))
-    return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L) + _valued_entries(ts))
+    second_pass = windows * W * L if ts.allowed is not None else 0  # (a partial set: the restricted pass's log alpha, §4.9e)
+    return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L) + second_pass
+                + _valued_entries(ts))
 
 
 def _sequences_scratch_bytes(ts: TrainingSet) -> int:
@@ -476,7 +568,8 @@ def _sequences_scratch_bytes(ts: TrainingSet) -> int:
     plus 32 slabs)."""
     L = ts.num_labels
     per_block = 256 // max(2, 1 << (L - 1).bit_length())
-    return 8 * (2 * int(ts.seq_ptr[-1]) * L + (-(-(len(ts.seq_ptr) - 1) // per_block) + 32) * (1 + L * L)
+    second_pass = int(ts.seq_ptr[-1]) * L if ts.allowed is not None else 0  # (a partial set: as above, §4.9e)
+    return 8 * (2 * int(ts.seq_ptr[-1]) * L + (-(-(len(ts.seq_ptr) - 1) // per_block) + 32) * (1 + L * L) + second_pass
                 + _valued_entries(ts))
 
 
@@ -492,9 +585,9 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
     from . import _native
 
     results: List[Optional[OptimizeResult]] = [None] * len(sets)
-    # (a windowed set with values goes with the sets of more labels, at any label count)
-    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and ts.attr_value is None]
-    more = [k for k, ts in enumerate(sets) if ts.window is not None and (ts.num_labels != 2 or ts.attr_value is not None)]
+    # (a windowed set with values or with masks goes with the sets of more labels, at any label count)
+    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and not _general_trainer(ts)]
+    more = [k for k, ts in enumerate(sets) if ts.window is not None and (ts.num_labels != 2 or _general_trainer(ts))]
     whole = [k for k, ts in enumerate(sets) if ts.window is None]
     if two:
         for k, r in zip(two, fit_two(two)):
@@ -514,6 +607,8 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
         for group in groups:
             values = [sets[k].attr_value for k in group]
             valued = {} if all(v is None for v in values) else {"values": values}  # (no values: the call it always was)
+            if any(sets[k].allowed is not None for k in group):  # (partial sets beside labelled ones: None for the latter)
+                valued["allowed"] = [sets[k].allowed for k in group]
             trainer = getattr(_native, family)([sets[k].native_args() for k in group], device=device, **valued)
             for k, r in zip(group, _fit_lockstep(trainer, [sets[k] for k in group], [params(k) for k in group])):
                 results[k] = r
@@ -566,7 +661,7 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
             raise ValueError(f"fit_grid: problem {k} names set {s}, but there are {len(sets)} sets")
 
     def fit_two(idx):
-        used = [s for s, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and ts.attr_value is None]
+        used = [s for s, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and not _general_trainer(ts)]
         grid = _native.TrainerGrid([sets[s].native_args() for s in used], [used.index(int(problems[k][0])) for k in idx],
                                    scratch_budget_bytes, device=device)
         return _fit_lockstep(grid, [sets[int(problems[k][0])] for k in idx], [problems[k][1] for k in idx])
@@ -584,7 +679,9 @@ def _fit_lockstep(trainer, sets: Sequence[TrainingSet], params: Sequence[Dict[st
     n = len(sets)
     steppers = [minimize_steps(np.zeros(ts.num_features), c1=float(p["c1"]), num_memories=int(p["num_memories"]),
                                epsilon=float(p["epsilon"]), period=int(p["period"]), delta=float(p["delta"]),
-                               max_iterations=p["max_iterations"], callback=callback) for ts, p in zip(sets, params)]
+                               max_iterations=p["max_iterations"], callback=callback,
+                               skip_nonpositive_curvature=ts.allowed is not None)  # (a partial set is not convex)
+                for ts, p in zip(sets, params)]
     c2 = [float(p["c2"]) for p in params]
     pending: List[Optional[np.ndarray]] = [next(st) for st in steppers]
     results: List[Optional[OptimizeResult]] = [None] * n

@@ -13,6 +13,12 @@ cluster id are skipped, a repeated id is an error); of several clusters the firs
 composite labels (those with a ``";"``) with the fewest clusters are folded into one label ``"Mixed"``, fewest first,
 ties by name, until 31 remain.
 
+``unknown="any"`` (``--unknown any``): a cluster without a type says that its genes lie in a cluster of *some* type, which is
+a set of allowed labels, not a label.  Its genes then carry the set of every cluster label of the training set (everything but
+the background), ``"Unknown"`` is no label of the model, and the fit maximises the marginal likelihood of the allowed paths
+(``train.build_training_set``'s partial labels).  The set needs at least one cluster with a type.  The default,
+``unknown="label"``, is the labelling above.
+
 Type of a call.  For a type t and a gene g, v[g] = the sum over the labels whose names contain t, in label order, of the
 label's windowed probability; the cluster's probability of t is ``min(1, exact mean of v over its genes)``; its type is
 the set of t with a probability above 0.5 (the rule of ``TypeClassifier.predict_types``), ``Unknown`` when empty.
@@ -80,19 +86,31 @@ def fold_labels(counts: Dict[str, int], limit: int = MAX_CLUSTER_LABELS) -> Dict
     return {label: (MIXED if label in gone else label) for label in names}
 
 
-def gene_labels(n_genes: int, clusters: tables.ClusterTable, join: Any, limit: int = MAX_CLUSTER_LABELS) -> List[str]:
+def gene_labels(n_genes: int, clusters: tables.ClusterTable, join: Any, limit: int = MAX_CLUSTER_LABELS,
+                unknown: str = "label") -> List[Any]:
     """The label of every gene from the overlap join (``train_cli.ClusterJoin``) of the genes with ``clusters``.  The
     clusters are ``train_cli.assigned_clusters``': those with at least one gene, in sorted ``cluster_id`` order; a row with
-    an empty id labels no gene, and a repeated id is a ``ValueError``."""
+    an empty id labels no gene, and a repeated id is a ``ValueError``.  ``unknown="any"``: the genes of a cluster without a
+    type carry the frozenset of every cluster label (after folding, which then counts the clusters with a type only) instead
+    of ``"Unknown"``; a table without any cluster with a type is a ``ValueError``."""
     from .train_cli import assigned_clusters
 
+    if unknown not in ("label", "any"):
+        raise ValueError(f"unknown must be 'label' or 'any', got {unknown!r}")
     row_label = cluster_labels(clusters)
     rows = [i for _, i, _ in assigned_clusters(clusters, join)]
     counts: Dict[str, int] = {}
     for i in rows:
+        if unknown == "any" and row_label[i] == UNKNOWN:
+            continue
         counts[row_label[i]] = counts.get(row_label[i], 0) + 1
-    folded = fold_labels(counts, limit)
-    labels = [BACKGROUND] * n_genes
+    folded: Dict[str, Any] = fold_labels(counts, limit)
+    if unknown == "any":
+        if not counts:
+            raise ValueError("unknown='any' needs at least one cluster with a type: an untyped cluster's genes take the set "
+                             "of the typed clusters' labels")
+        folded[UNKNOWN] = frozenset(folded.values())
+    labels: List[Any] = [BACKGROUND] * n_genes
     for i in rows:
         label = folded[row_label[i]]
         for g in np.asarray(join.members(i)).tolist():
@@ -145,15 +163,20 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
 
 # ---------------------------------------------------------------------------------------------- the model
 class TypedClusterCRF:
-    """``TypedClusterCRF(window_size=5, window_step=1, device=0, **options)``; ``options`` are the trainer's
-    (``train.trainer_params``: ``c1``, ``c2``, ...).  After ``fit`` or ``trained``: ``classes_`` (labels in id order),
+    """``TypedClusterCRF(window_size=5, window_step=1, device=0, unknown="label", **options)``; ``options`` are the
+    trainer's (``train.trainer_params``: ``c1``, ``c2``, ...); ``unknown``: how ``fit`` labels the genes of a cluster without
+    a type, ``"label"`` (the label ``"Unknown"``) or ``"any"`` (the set of every cluster label: module docstring).  After ``fit`` or ``trained``: ``classes_`` (labels in id order),
     ``label_types_`` (per label its type names), ``types_`` (the sorted distinct type names), ``background`` (``"0"``)."""
 
     feature_type = "protein"
 
-    def __init__(self, window_size: int = 5, window_step: int = 1, device: int = 0, **options: Any) -> None:
+    def __init__(self, window_size: int = 5, window_step: int = 1, device: int = 0, unknown: str = "label",
+                 **options: Any) -> None:
         if options.pop("feature_type", "protein") != "protein":
             raise ValueError("typed models use protein features")
+        if unknown not in ("label", "any"):
+            raise ValueError(f"unknown must be 'label' or 'any', got {unknown!r}")
+        self.unknown = unknown
         if window_size <= 0:
             raise ValueError("Window size must be strictly positive")
         if window_step <= 0 or window_step > window_size:
@@ -179,7 +202,7 @@ class TypedClusterCRF:
 
         genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
         join = join_clusters(genes, clusters, device=self.device)
-        labels = gene_labels(len(genes), clusters, join)
+        labels = gene_labels(len(genes), clusters, join, unknown=self.unknown)
         if BACKGROUND not in labels:
             raise ValueError("no gene outside every cluster: the background label '0' must be present")
         helper = ClusterCRF("protein", "lbfgs", self.window_size, self.window_step, **self._options)
@@ -379,6 +402,8 @@ def build_parser() -> argparse.ArgumentParser:
     tr.add_argument("--feature-type", choices=("protein", "domain"), default="protein")
     tr.add_argument("--select", type=float, default=None, help="fraction of domains kept by Fisher selection")
     tr.add_argument("--correction", type=str, default=None, help="multiple-testing correction of the selection p-values")
+    tr.add_argument("--unknown", choices=("label", "any"), default="label",
+                    help="genes of a cluster without a type: the label 'Unknown', or the set of every cluster label")
     tr.add_argument("--device", type=int, default=0)
     tr.add_argument("-o", "--output-dir", default=".", help="the model directory")
     pr = sub.add_parser("predict", help="tables in; genes.tsv, features.tsv and clusters.tsv out")
@@ -408,7 +433,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         np.random.seed(args.seed)
         genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
         clusters = tables.ClusterTable.load(args.clusters)
-        crf = TypedClusterCRF(args.window_size, args.window_step, args.device, c1=args.c1, c2=args.c2)
+        crf = TypedClusterCRF(args.window_size, args.window_step, args.device, unknown=args.unknown, c1=args.c1, c2=args.c2)
         crf.fit(genes, clusters, shuffle=args.shuffle, select=args.select, correction_method=args.correction)
         crf.save(args.output_dir)
         print(f"train: {len(genes)} genes, {len(clusters)} clusters, labels {crf.classes_} -> {args.output_dir}", file=sys.stderr)

@@ -48,7 +48,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330). */
+/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340). */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -642,6 +642,38 @@ int gecco_crf_trainer_sequences_create_valued(int32_t device, int32_t n_problems
                                               const int32_t *const *labels, const int32_t *num_attrs, const int32_t *num_labels,
                                               const int32_t *const *state_fid, const int32_t *const *trans_fid,
                                               const int32_t *num_features, gecco_crf_trainer_sequences **out);
+
+/* ---- partially labelled training sets (ABI 2.14.0, additive) ---------------------------------------------------------
+ * Marginal-likelihood ("partial-label", "constrained-lattice") training: every item of a problem carries a set of allowed
+ * labels A_t, one uint32_t with bit y set when label y is allowed (at 32 labels bit 31 is a label like any other), and
+ *     f(w) = sum over instances of (log Z - log Z_A),    g(w) = E[feature counts] - E_A[feature counts],
+ * Z_A and E_A over the label paths with y_t in A_t for every t; the instances are the family's (windows, or whole sequences).
+ * With every set a singleton this is the labelled objective (to rounding: the operations differ); with every set full f and
+ * g are 0.  The objective is not convex.  Log space throughout, right for any finite weights: a disallowed label is excluded
+ * (an exact 0), not penalised.  No float atomics: an evaluation is bit-reproducible, and a problem's bits do not depend on its
+ * neighbours.
+ * The arguments of the *_create_valued sibling plus `allowed` after labels: allowed[k] holds one mask per item of problem k,
+ * or is NULL, which makes problem k an ordinary labelled problem with the bits it has from the other creates.  For a problem
+ * with masks labels[k] is not read and may be NULL.  attr_value may be NULL as a whole (no problem has values) or per problem;
+ * a problem with masks and values uses the valued kernels like any other.  eval, num_*, scratch_bytes and free are the
+ * family's.  Refused on the host before the device is looked at, GECCO_CRF_EINVAL, naming problem and item: a mask of 0
+ * ("trainer general: problem k: item i allows no label"), a mask with a bit at or above num_labels[k].
+ * Memory: a problem with masks adds the second pass's log alpha to its scratch_bytes: 8 * n_windows * window * L bytes
+ * (whole sequences: 8 * n_items * L), and 4 bytes per item for the masks. */
+int gecco_crf_trainer_general_create_partial(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                             const int32_t *n_seqs, const int32_t *const *item_ptr, const int32_t *const *attr_id,
+                                             const double *const *attr_value, const int32_t *const *labels,
+                                             const uint32_t *const *allowed, const int32_t *num_attrs, const int32_t *num_labels,
+                                             const int32_t *window, const int32_t *step, const int32_t *const *state_fid,
+                                             const int32_t *const *trans_fid, const int32_t *num_features,
+                                             gecco_crf_trainer_general **out);
+int gecco_crf_trainer_sequences_create_partial(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                               const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                               const int32_t *const *attr_id, const double *const *attr_value,
+                                               const int32_t *const *labels, const uint32_t *const *allowed,
+                                               const int32_t *num_attrs, const int32_t *num_labels,
+                                               const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                               const int32_t *num_features, gecco_crf_trainer_sequences **out);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
