@@ -32,6 +32,7 @@
 #include "crf_model.hpp"
 #include "crf_plan.hpp"
 #include "crf_train.hpp"
+#include "crf_train_host.hpp"
 
 namespace gecco {
 
@@ -430,21 +431,8 @@ __global__ void __launch_bounds__(kTrainReduceBlocks) train_reduce_final(const S
 }
 
 template <class T>
-int dev_upload(T **d, const std::vector<T> &h, const char *what) {
-    int rc = check_hip(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(h.size(), 1) * sizeof(T)), what);
-    if (rc) return rc;
-    if (h.empty()) return GECCO_CRF_OK;
-    return check_hip(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), what);
-}
-
-template <class T>
 int dev_alloc(T **d, size_t n, const char *what) {
     return check_hip(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(n, 1) * sizeof(T)), what);
-}
-
-int fail(const std::string &msg) {
-    set_error(msg);
-    return GECCO_CRF_EINVAL;
 }
 
 }  // namespace
@@ -599,11 +587,6 @@ TransArgs trans_args(const std::vector<int32_t> &trans_fid, const double *w) {
     return T;
 }
 
-template <class T>
-void append(std::vector<T> &dst, const std::vector<T> &src) {
-    dst.insert(dst.end(), src.begin(), src.end());
-}
-
 static_assert(sizeof(Slot) % alignof(double) == 0 && sizeof(ItemGroup) % alignof(int32_t) == 0, "upload layout");
 
 }  // namespace
@@ -655,12 +638,6 @@ struct Trainer {
         if (restore && prev >= 0) (void)hipSetDevice(prev);
     }
 };
-
-namespace {
-
-int64_t blocks_of(int64_t n, int per) { return (n + per - 1) / per; }
-
-}  // namespace
 
 // Sets as build_problem takes them.  A set's error names it after what the caller numbers: the set where problems pick
 // their sets (problem_set), the problem where problem k is set k.

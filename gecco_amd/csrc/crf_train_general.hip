@@ -7,7 +7,7 @@
 // Every problem has its own label count L, window W and step, and runs its own launches on the trainer's stream (no
 // kernel ever sees two problems, so a problem's bits cannot depend on its neighbours):
 //   1. item scores     one thread per (item, label): s[i][y] = sum of the state weights of its attributes (CSR order)
-//   2. windows         G = the power of two at or above L lanes per window, lane i owning label i; log-space
+//   2. instances       G = the power of two at or above L lanes per window, lane i owning label i; log-space
 //                      forward-backward.  log alpha_t is stored in the window's node-marginal slots and overwritten by
 //                      the marginals on the way back.  A workgroup runs a fixed 128 windows, keeps the pairwise
 //                      expectations xi[i][.] of all of them in registers, and writes one block (f, xi[L][L])
@@ -16,13 +16,17 @@
 //   5/6. block sums    fixed-geometry two-stage sum over the workgroups' blocks
 // Log space throughout: right for any finite weights, no second path.  No float atomics: every sum has one fixed order.
 //
-// The whole-sequence family (gecco_crf_trainer_sequences_*) is the same objective with one instance per
-// sequence, of that sequence's own length.  It shares kernels 1, 4, 5 and 6 and replaces 2 and 3 by one kernel,
-// gen_sequences: every item lies in exactly one instance, so that kernel's node marginals are the item marginals.
-//
-// Partially labelled problems (gecco_crf_trainer_{general, sequences}_create_partial) carry a mask of allowed
-// labels per item and minimise log Z - log Z_A.  They replace kernel 2 (or gen_sequences) by gen_partial, which runs the free
-// and the restricted recursion in the same slot and hands on their difference; every other kernel is shared as it is.
+// Kernel 2 is two kernels with two parameters each, which share what can be shared at no cost in time: the transition load
+// and the workgroup sum are device functions templated on G that both call, the forward step is one that gen_partial calls
+// for both of its passes.  The other steps stay in the kernels' bodies (see forward_lse below for what was measured):
+//   gen_labelled<G, kWhole>  the labelled problems.  kWhole = false: the windows above.  kWhole = true: the whole-sequence
+//                            family (gecco_crf_trainer_sequences_*), the same objective with one instance
+//                            per sequence, of that sequence's own length.  Every item then lies in exactly one instance, so
+//                            the kernel writes its node marginals straight into the item marginals and kernel 3 does not run.
+//   gen_partial<G, kWhole>   partially labelled problems (gecco_crf_trainer_{general, sequences}_create_partial; DESIGN.md
+//                            §4.9e), which carry a mask of allowed labels per item and minimise log Z - log Z_A: the free and
+//                            the restricted recursion in the same slot; it hands on their difference.
+// Every other kernel is shared by all of them as it is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,12 +34,14 @@
 #include <cmath>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gecco_crf.h"
 #include "crf_model.hpp"
 #include "crf_plan.hpp"
 #include "crf_train.hpp"
+#include "crf_train_host.hpp"
 
 namespace gecco {
 
@@ -81,54 +87,124 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_item_scores(GenProb P, c
     P.score[idx] = s;
 }
 
-// G lanes per window (G a power of two, L <= G), lane i owning label i; 256 / G windows run side by side, and a
-// workgroup runs its kTrainGenWindowsPerBlock windows in rounds of that many.  Everything is in log space:
+// The instance kernels.  G lanes per instance (G a power of two, L <= G), lane i owning label i; 256 / G instances run side by
+// side, one per slot.  Everything is in log space:
 //     forward   la_t[j] = s_t[j] + lse_i(la_{t-1}[i] + T[i][j])
 //     backward  lb_{t-1}[i] = lse_j(T[i][j] + s_t[j] + lb_t[j]),   marginal_t[i] = exp(la_t[i] + lb_t[i] - log Z)
 //     pairwise  xi_t[i][j] = marginal_{t-1}[i] * e_ij / sum_j e_ij,   e_ij = exp(T[i][j] + s_t[j] + lb_t[j] - max_j),
 // so the pairwise term reuses the exponentials of the backward step (e_ij <= 1 and their sum >= 1: nothing overflows, and
 // what underflows is below 1e-308 of a probability).  A lane reads its neighbours' values by shuffles inside its group
 // of G lanes and the transitions from LDS (both orientations, so that either read is conflict-free).  Lanes at or above
-// L compute on zeros and store nothing.  xi[i][.] accumulates in the registers of lane i over the positions and windows
+// L compute on zeros and store nothing.  xi[i][.] accumulates in the registers of lane i over the positions and instances
 // of its slot, in that order; the slots of a wave are then summed by a butterfly, the four waves in wave order.
+// The instances of a wave may differ in length, so none of the steps below that run inside a loop over t has a workgroup
+// barrier or a shuffle that leaves the group's own G lanes (all of which run the same trip count).
+
+// The transitions into LDS: tT[i][j] = T[i][j], tTt[j][i] = T[i][j], zero at or above L.  Ends with the workgroup's barrier.
 template <int G>
-__global__ void __launch_bounds__(kTrainGenThreads) gen_windows(GenProb P) {
-    constexpr int kSlots = kTrainGenThreads / G;  // windows side by side in a workgroup
+__device__ __forceinline__ void load_transitions(const double *trans, int L, double *tT, double *tTt) {
+    for (int e = threadIdx.x; e < G * G; e += kTrainGenThreads) {
+        const int a = e / G, b = e % G;
+        const double v = (a < L && b < L) ? trans[a * L + b] : 0.0;
+        tT[e] = v;
+        tTt[b * G + a] = v;
+    }
+    __syncthreads();
+}
+
+// The forward step: lse over k < L of log alpha_{t-1}[k] (x of the group's lane k) + T[k][i], on the kernel's one array v.
+// gen_partial calls it for both passes.  It is the only step of the recursion that is a function, by measurement on an
+// MI355X (profiles/train_general_layouts.txt): gen_labelled with this step, or with the backward step, as a function ran 32
+// labels on whole sequences 4 to 5 % slower than with both in its body; gen_partial with the backward step as a function
+// ran windows at 2 labels 10 % slower, and with the log partition as one called twice windows at 32 labels 2 % slower.  The
+// arithmetic is the same every time; what moves is the compiler's schedule and register allocation around the inlined
+// code.  So a change to the recursion is made in gen_labelled's body, in gen_partial's (twice) and, for this step, here.
+template <int G>
+__device__ __forceinline__ double forward_lse(double x, const double *tT, int i, int L, double (&v)[G]) {
+    double mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < G; ++k)
+        if (k < L) {
+            v[k] = __shfl(x, k, G) + tT[k * G + i];
+            mx = fmax(mx, v[k]);
+        }
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < G; ++k)
+        if (k < L) sum += exp(v[k] - mx);
+    return mx + log(sum);
+}
+
+// The workgroup's block (f, xi[L][L]) from every lane's sums, after every group has left its loops: the slots of a wave by a
+// butterfly over the lanes that own the same label (both partners form the same sum), then the waves in wave order.
+template <int G>
+__device__ __forceinline__ void write_block(double (&xacc)[G], double facc, int L, double *xi_sh, double *f_sh, double *part) {
+    const int tid = threadIdx.x;
+    for (int off = 32; off >= G; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
+        facc += __shfl_xor(facc, off);
+    }
+    const int wave = tid / 64, lane = tid % 64;
+    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
+        if (wave == wv && lane < G) {
+#pragma unroll
+            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
+            if (lane == 0) *f_sh = (wv ? *f_sh : 0.0) + facc;
+        }
+        __syncthreads();
+    }
+    for (int e = tid; e < G * G; e += kTrainGenThreads) {
+        const int k = e / G, a = e % G;
+        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
+    }
+    if (tid == 0) part[0] = *f_sh;
+}
+
+// The labelled problems.  kWhole = false, windows: a workgroup runs its kTrainGenWindowsPerBlock windows, all of P.W items, in
+// rounds of 256 / G, and the node marginals go to the window's own slots of P.marg.  kWhole = true, whole sequences: the
+// instance's own length, and the node marginals go straight into item_marg (log alpha on the way forward, the marginal on the
+// way back).  A workgroup then owns the 256 / G sequences it runs side by side, one per slot, so that an evaluation is as close
+// to its bound, the longest sequence, as the sequence count allows: instance q of the problem's slot order (longest first, ties
+// by index: computed on the host from the problem alone) runs in workgroup q / kSlots, slot q % kSlots, and the groups running
+// side by side have neighbouring lengths.
+// The windows index their scores and marginals with int, as their kernel always has (t * L + i < W * L <= 32 * window, and a
+// 64-bit index costs the two-label group a wave per SIMD); a sequence has no such bound and indexes with int64_t.
+template <int G, bool kWhole>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
+    using Idx = std::conditional_t<kWhole, int64_t, int>;
+    constexpr int kSlots = kTrainGenThreads / G;
+    constexpr int kPerBlock = kWhole ? kSlots : kTrainGenWindowsPerBlock;
     __shared__ double tT[G * G];             // [i][j] = T[i][j]
     __shared__ double tTt[G * G];            // [j][i] = T[i][j]
     __shared__ double xi_sh[G * G];          // [j][i]
     __shared__ double f_sh;
     const int tid = threadIdx.x;
-    const int L = P.L, W = P.W;
+    const int L = P.L;
     const int i = tid % G, slot = tid / G;
     const bool lab = i < L;
-    for (int e = tid; e < G * G; e += kTrainGenThreads) {
-        const int a = e / G, b = e % G;
-        const double v = (a < L && b < L) ? P.trans[a * L + b] : 0.0;
-        tT[e] = v;
-        tTt[b * G + a] = v;
-    }
-    __syncthreads();
+    load_transitions<G>(P.trans, L, tT, tTt);
 
     double xacc[G];
 #pragma unroll
     for (int k = 0; k < G; ++k) xacc[k] = 0.0;
     double facc = 0.0;
     double v[G];
-    const int64_t w_base = static_cast<int64_t>(blockIdx.x) * kTrainGenWindowsPerBlock;
-    for (int r = 0; r < kTrainGenWindowsPerBlock / kSlots; ++r) {
+    const int64_t w_base = static_cast<int64_t>(blockIdx.x) * kPerBlock;
+    for (int r = 0; r < kPerBlock / kSlots; ++r) {
         const int64_t w = w_base + r * kSlots + slot;
         if (w >= P.n_win) continue;  // (a whole group of G lanes: the shuffles below stay inside the group)
         const int64_t i0 = P.win_start[w];
+        const int n = kWhole ? P.win_len[w] : P.W;
         const double *sc = P.score + i0 * L;
         const int32_t *label = P.label + i0;
-        double *mw = P.marg + w * W * L;
+        double *mw = kWhole ? P.item_marg + i0 * L : P.marg + w * n * L;
 
         double la = lab ? sc[i] : 0.0;
         int yprev = label[0];
         double gold = (lab && yprev == i) ? la : 0.0;  // this label's share of the gold path's score
         if (lab) mw[i] = la;
-        for (int t = 1; t < W; ++t) {
+        for (int t = 1; t < n; ++t) {
             double mx = -INFINITY;
 #pragma unroll
             for (int k = 0; k < G; ++k)
@@ -140,12 +216,12 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_windows(GenProb P) {
 #pragma unroll
             for (int k = 0; k < G; ++k)
                 if (k < L) sum += exp(v[k] - mx);
-            const double s = lab ? sc[t * L + i] : 0.0;
+            const double s = lab ? sc[static_cast<Idx>(t) * L + i] : 0.0;
             la = mx + log(sum) + s;
             const int y = label[t];
             if (lab && y == i) gold += s + tT[yprev * G + i];
             yprev = y;
-            if (lab) mw[t * L + i] = la;
+            if (lab) mw[static_cast<Idx>(t) * L + i] = la;
         }
         double mx = -INFINITY, gold_all = 0.0;
 #pragma unroll
@@ -162,11 +238,11 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_windows(GenProb P) {
         const double logz = mx + log(sum);
         if (i == 0) facc += logz - gold_all;
 
-        if (lab) mw[(W - 1) * L + i] = exp(la - logz);
+        if (lab) mw[static_cast<Idx>(n - 1) * L + i] = exp(la - logz);
         double lb = 0.0;
-        for (int t = W - 1; t >= 1; --t) {
-            const double q = (lab ? sc[t * L + i] : 0.0) + lb;  // log of exp(s_t[i]) beta_t[i]
-            const double lap = lab ? mw[(t - 1) * L + i] : 0.0;  // log alpha_{t-1}[i], stored by this lane
+        for (int t = n - 1; t >= 1; --t) {
+            const double q = (lab ? sc[static_cast<Idx>(t) * L + i] : 0.0) + lb;  // log of exp(s_t[i]) beta_t[i]
+            const double lap = lab ? mw[static_cast<Idx>(t - 1) * L + i] : 0.0;  // log alpha_{t-1}[i], stored by this lane
             mx = -INFINITY;
 #pragma unroll
             for (int k = 0; k < G; ++k)
@@ -187,177 +263,26 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_windows(GenProb P) {
 #pragma unroll
             for (int k = 0; k < G; ++k)
                 if (k < L) xacc[k] += c * v[k];
-            if (lab) mw[(t - 1) * L + i] = m;
+            if (lab) mw[static_cast<Idx>(t - 1) * L + i] = m;
         }
     }
 
-    // the slots of a wave: a butterfly over the lanes that own the same label (both partners form the same sum)
-    for (int off = 32; off >= G; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
-        facc += __shfl_xor(facc, off);
-    }
-    // the waves, in wave order
-    const int wave = tid / 64, lane = tid % 64;
-    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
-        if (wave == wv && lane < G) {
-#pragma unroll
-            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
-            if (lane == 0) f_sh = (wv ? f_sh : 0.0) + facc;
-        }
-        __syncthreads();
-    }
-    double *part = P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L);
-    for (int e = tid; e < G * G; e += kTrainGenThreads) {
-        const int k = e / G, a = e % G;
-        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
-    }
-    if (tid == 0) part[0] = f_sh;
-}
-
-// Whole sequences: gen_windows with the instance's own length n in place of W, and with the node marginals written
-// straight into item_marg (log alpha on the way forward, the marginal on the way back).  A workgroup owns the 256 / G
-// sequences it runs side by side, one per slot, so that an evaluation is as close to its bound, the longest sequence, as
-// the sequence count allows: instance q of the problem's slot order (longest first, ties by index: computed on the host
-// from the problem alone) runs in workgroup q / kSlots, slot q % kSlots, and the groups running side by side have
-// neighbouring lengths.  The lengths still differ inside a wave, so the loops over t have no workgroup barrier and no
-// shuffle that leaves the group's own G lanes (all of which run the same trip count); the butterfly and the barriers
-// come after every group has left its loops.
-template <int G>
-__global__ void __launch_bounds__(kTrainGenThreads) gen_sequences(GenProb P) {
-    constexpr int kSlots = kTrainGenThreads / G;  // sequences of a workgroup, side by side
-    __shared__ double tT[G * G];             // [i][j] = T[i][j]
-    __shared__ double tTt[G * G];            // [j][i] = T[i][j]
-    __shared__ double xi_sh[G * G];          // [j][i]
-    __shared__ double f_sh;
-    const int tid = threadIdx.x;
-    const int L = P.L;
-    const int i = tid % G, slot = tid / G;
-    const bool lab = i < L;
-    for (int e = tid; e < G * G; e += kTrainGenThreads) {
-        const int a = e / G, b = e % G;
-        const double v = (a < L && b < L) ? P.trans[a * L + b] : 0.0;
-        tT[e] = v;
-        tTt[b * G + a] = v;
-    }
-    __syncthreads();
-
-    double xacc[G];
-#pragma unroll
-    for (int k = 0; k < G; ++k) xacc[k] = 0.0;
-    double facc = 0.0;
-    double v[G];
-    const int64_t q = static_cast<int64_t>(blockIdx.x) * kSlots + slot;
-    if (q < P.n_win) {  // (a whole group of G lanes)
-        const int64_t i0 = P.win_start[q];
-        const int n = P.win_len[q];
-        const double *sc = P.score + i0 * L;
-        const int32_t *label = P.label + i0;
-        double *mw = P.item_marg + i0 * L;
-
-        double la = lab ? sc[i] : 0.0;
-        int yprev = label[0];
-        double gold = (lab && yprev == i) ? la : 0.0;  // this label's share of the gold path's score
-        if (lab) mw[i] = la;
-        for (int t = 1; t < n; ++t) {
-            double mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) {
-                    v[k] = __shfl(la, k, G) + tT[k * G + i];
-                    mx = fmax(mx, v[k]);
-                }
-            double sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) sum += exp(v[k] - mx);
-            const double s = lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0;
-            la = mx + log(sum) + s;
-            const int y = label[t];
-            if (lab && y == i) gold += s + tT[yprev * G + i];
-            yprev = y;
-            if (lab) mw[static_cast<int64_t>(t) * L + i] = la;
-        }
-        double mx = -INFINITY, gold_all = 0.0;
-#pragma unroll
-        for (int k = 0; k < G; ++k)
-            if (k < L) {
-                v[k] = __shfl(la, k, G);
-                mx = fmax(mx, v[k]);
-                gold_all += __shfl(gold, k, G);
-            }
-        double sum = 0.0;
-#pragma unroll
-        for (int k = 0; k < G; ++k)
-            if (k < L) sum += exp(v[k] - mx);
-        const double logz = mx + log(sum);
-        if (i == 0) facc += logz - gold_all;
-
-        if (lab) mw[static_cast<int64_t>(n - 1) * L + i] = exp(la - logz);
-        double lb = 0.0;
-        for (int t = n - 1; t >= 1; --t) {
-            const double q_t = (lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0) + lb;  // log of exp(s_t[i]) beta_t[i]
-            const double lap = lab ? mw[static_cast<int64_t>(t - 1) * L + i] : 0.0;      // log alpha_{t-1}[i], stored by this lane
-            mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) {
-                    v[k] = tTt[k * G + i] + __shfl(q_t, k, G);
-                    mx = fmax(mx, v[k]);
-                }
-            sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) {
-                    v[k] = exp(v[k] - mx);
-                    sum += v[k];
-                }
-            lb = mx + log(sum);
-            const double m = exp(lap + lb - logz);
-            const double c = m / sum;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) xacc[k] += c * v[k];
-            if (lab) mw[static_cast<int64_t>(t - 1) * L + i] = m;
-        }
-    }
-
-    // every group has left its loops: the slots of a wave by a butterfly, then the waves in wave order (as gen_windows)
-    for (int off = 32; off >= G; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
-        facc += __shfl_xor(facc, off);
-    }
-    const int wave = tid / 64, lane = tid % 64;
-    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
-        if (wave == wv && lane < G) {
-#pragma unroll
-            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
-            if (lane == 0) f_sh = (wv ? f_sh : 0.0) + facc;
-        }
-        __syncthreads();
-    }
-    double *part = P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L);
-    for (int e = tid; e < G * G; e += kTrainGenThreads) {
-        const int k = e / G, a = e % G;
-        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
-    }
-    if (tid == 0) part[0] = f_sh;
+    write_block<G>(xacc, facc, L, xi_sh, &f_sh, P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L));
 }
 
 // Partially labelled problems (the *_create_partial problems that carry allowed-label sets): every item
 // has a set of allowed labels, one uint32_t with bit y set when label y is allowed, and the objective is
 //     f(w) = sum over instances of (log Z - log Z_A),   g(w) = E[feature counts] - E_A[feature counts],
-// Z_A and E_A over the paths that stay inside the sets.  This is gen_windows (kWhole: gen_sequences) with a second,
-// restricted recursion run beside the free one in the same slot, position by position: the same work decomposition, the same
+// Z_A and E_A over the paths that stay inside the sets.  This is gen_labelled with a second, restricted recursion run beside
+// the free one in the same slot, position by position: the same work decomposition, the same
 // loops, and what the kernel hands on is the *difference* of the two passes (node marginals free - restricted in the slots
 // the labelled kernels fill, xi free - restricted, f = log Z - log Z_A), so that the item-marginal, attribute-count and
 // block-sum kernels run unchanged and the host's empirical vector is zero.
 // A disallowed label is excluded, not penalised: its restricted log alpha is -inf, and so is what it offers to the backward
-// step.  Every item has an allowed label (create refuses a mask of 0), so every maximum below is taken over at least one
-// finite term: the excluded terms are exp(-inf - finite) = 0 exactly and no -inf - (-inf) can form, however much of the free
-// mass the excluded labels carry.  The restricted log alpha has its own storage, la_a, of the node marginals' shape
-// ([n_win][W][L], whole sequences [n_items][L]).  No barrier and no shuffle beyond the group inside the loops, as before.
+// step.  Every item has an allowed label (create refuses a mask of 0), so every maximum is taken over at least one finite
+// term: the excluded terms are exp(-inf - finite) = 0 exactly and no -inf - (-inf) can form, however much of the free mass
+// the excluded labels carry.  The restricted log alpha has its own storage, la_a, of the node marginals' shape
+// ([n_win][W][L], whole sequences [n_items][L]).  Both families index with int64_t here.
 template <int G, bool kWhole>
 __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const uint32_t *allowed, double *la_a) {
     constexpr int kSlots = kTrainGenThreads / G;  // instances side by side in a workgroup
@@ -370,13 +295,7 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
     const int L = P.L;
     const int i = tid % G, slot = tid / G;
     const bool lab = i < L;
-    for (int e = tid; e < G * G; e += kTrainGenThreads) {
-        const int a = e / G, b = e % G;
-        const double v = (a < L && b < L) ? P.trans[a * L + b] : 0.0;
-        tT[e] = v;
-        tTt[b * G + a] = v;
-    }
-    __syncthreads();
+    load_transitions<G>(P.trans, L, tT, tTt);
 
     double xacc[G];
 #pragma unroll
@@ -400,30 +319,10 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
         if (lab) mw[i] = la, ma[i] = lr;
         for (int t = 1; t < n; ++t) {
             const double s = lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0;
-            double mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) {
-                    v[k] = __shfl(la, k, G) + tT[k * G + i];
-                    mx = fmax(mx, v[k]);
-                }
-            double sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) sum += exp(v[k] - mx);
-            la = mx + log(sum) + s;
-            mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) {
-                    v[k] = __shfl(lr, k, G) + tT[k * G + i];
-                    mx = fmax(mx, v[k]);
-                }
-            sum = 0.0;
-#pragma unroll
-            for (int k = 0; k < G; ++k)
-                if (k < L) sum += exp(v[k] - mx);
-            lr = (lab && ((al[t] >> i) & 1u)) ? mx + log(sum) + s : -INFINITY;
+            const double lse = forward_lse<G>(la, tT, i, L, v);
+            la = lse + s;
+            const double lser = forward_lse<G>(lr, tT, i, L, v);
+            lr = (lab && ((al[t] >> i) & 1u)) ? lser + s : -INFINITY;
             if (lab) mw[static_cast<int64_t>(t) * L + i] = la, ma[static_cast<int64_t>(t) * L + i] = lr;
         }
         double mx = -INFINITY, mxr = -INFINITY;
@@ -489,27 +388,7 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
         }
     }
 
-    // every group has left its loops: the slots of a wave by a butterfly, then the waves in wave order (as gen_windows)
-    for (int off = 32; off >= G; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < G; ++k) xacc[k] += __shfl_xor(xacc[k], off);
-        facc += __shfl_xor(facc, off);
-    }
-    const int wave = tid / 64, lane = tid % 64;
-    for (int wv = 0; wv < kTrainGenThreads / 64; ++wv) {
-        if (wave == wv && lane < G) {
-#pragma unroll
-            for (int k = 0; k < G; ++k) xi_sh[k * G + lane] = (wv ? xi_sh[k * G + lane] : 0.0) + xacc[k];
-            if (lane == 0) f_sh = (wv ? f_sh : 0.0) + facc;
-        }
-        __syncthreads();
-    }
-    double *part = P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L);
-    for (int e = tid; e < G * G; e += kTrainGenThreads) {
-        const int k = e / G, a = e % G;
-        if (a < L && k < L) part[1 + a * L + k] = xi_sh[e];
-    }
-    if (tid == 0) part[0] = f_sh;
+    write_block<G>(xacc, facc, L, xi_sh, &f_sh, P.partial + static_cast<int64_t>(blockIdx.x) * (1 + L * L));
 }
 
 __global__ void __launch_bounds__(kTrainGenThreads) gen_item_marginals(GenProb P) {
@@ -573,30 +452,22 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_reduce_final(GenProb P) 
     }
 }
 
-template <class T>
-int dev_upload(T **d, const std::vector<T> &h, const char *what) {
-    int rc = check_hip(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(h.size(), 1) * sizeof(T)), what);
-    if (rc) return rc;
-    if (h.empty()) return GECCO_CRF_OK;
-    return check_hip(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice), what);
-}
-
-int fail(const std::string &msg) {
-    set_error(msg);
-    return GECCO_CRF_EINVAL;
-}
-
-template <class T>
-void append(std::vector<T> &dst, const std::vector<T> &src) {
-    dst.insert(dst.end(), src.begin(), src.end());
-}
-
-int64_t blocks_of(int64_t n, int per) { return (n + per - 1) / per; }
-
 int group_of(int L) {
     int G = 2;
     while (G < L) G *= 2;
     return G;
+}
+
+// Calls fn with G (a group_of value) as a compile-time constant: fn(std::integral_constant<int, G>).
+template <class F>
+void with_group(int G, F &&fn) {
+    switch (G) {
+        case 2: fn(std::integral_constant<int, 2>{}); break;
+        case 4: fn(std::integral_constant<int, 4>{}); break;
+        case 8: fn(std::integral_constant<int, 8>{}); break;
+        case 16: fn(std::integral_constant<int, 16>{}); break;
+        default: fn(std::integral_constant<int, 32>{}); break;
+    }
 }
 
 }  // namespace
@@ -867,46 +738,27 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
                 gen_item_scores<true><<<nb_items, kTrainGenThreads, 0, st>>>(a, attr_value);
             else
                 gen_item_scores<false><<<nb_items, kTrainGenThreads, 0, st>>>(a, nullptr);
-            if (p.allow0 >= 0) {  // a problem with masks: both passes in one kernel, which hands on their difference
-                const uint32_t *al = t->d_allowed + p.allow0;
-                double *la_a = a.slab + kTrainGenReduceSlabs * cols;
-                const unsigned nb = unsigned(p.n_blocks);
-                if (t->whole) {
-                    switch (G) {
-                        case 2: gen_partial<2, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        case 4: gen_partial<4, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        case 8: gen_partial<8, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        case 16: gen_partial<16, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        default: gen_partial<32, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                    }
-                } else {
-                    switch (G) {
-                        case 2: gen_partial<2, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        case 4: gen_partial<4, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        case 8: gen_partial<8, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        case 16: gen_partial<16, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                        default: gen_partial<32, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a); break;
-                    }
-                    gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
-                }
-            } else if (t->whole) {
-                switch (G) {
-                    case 2: gen_sequences<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    case 4: gen_sequences<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    case 8: gen_sequences<8><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    case 16: gen_sequences<16><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    default: gen_sequences<32><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                }
-            } else {
-                switch (G) {
-                    case 2: gen_windows<2><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    case 4: gen_windows<4><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    case 8: gen_windows<8><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    case 16: gen_windows<16><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                    default: gen_windows<32><<<unsigned(p.n_blocks), kTrainGenThreads, 0, st>>>(a); break;
-                }
-                gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
-            }
+            // kernel 2: the instantiation of the problem's group size and family; a problem with masks runs both passes in
+            // one kernel, which hands on their difference
+            const bool masked = p.allow0 >= 0;
+            const uint32_t *al = masked ? t->d_allowed + p.allow0 : nullptr;
+            double *la_a = masked ? a.slab + kTrainGenReduceSlabs * cols : nullptr;
+            const unsigned nb = unsigned(p.n_blocks);
+            with_group(G, [&](auto g) {
+                constexpr int kG = decltype(g)::value;
+                auto launch = [&](auto whole) {
+                    constexpr bool kWhole = decltype(whole)::value;
+                    if (masked)
+                        gen_partial<kG, kWhole><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a);
+                    else
+                        gen_labelled<kG, kWhole><<<nb, kTrainGenThreads, 0, st>>>(a);
+                };
+                if (t->whole)
+                    launch(std::true_type{});
+                else
+                    launch(std::false_type{});
+            });
+            if (!t->whole) gen_item_marginals<<<nb_items, kTrainGenThreads, 0, st>>>(a);
             if (valued)
                 gen_attr_counts<true><<<unsigned(p.A), kTrainGenThreads, 0, st>>>(a, G, attr_item_value);
             else
