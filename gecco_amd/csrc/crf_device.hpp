@@ -264,9 +264,8 @@ hipError_t launch_copy_block(const void *src, void *dst, size_t bytes, hipStream
 hipError_t launch_wire_format(const uint8_t *d_deg, int n, int32_t base, int32_t *d_row_ptr, int32_t *d_scratch,
                               const uint16_t *d_attr16, int64_t nnz, int32_t *d_attr32, hipStream_t stream);
 
-// ---- any number of labels (crf_general.hip) -------------------------------------------------
+// ---- any number of labels: state scores and whole-contig recursions (crf_general.hip) ------------
 constexpr int kGenMaxL = 32;  // labels: a group of next-pow2(L) lanes must fit in half a wave
-constexpr int kGenMaxW = 48;  // window length: alpha-hat of a whole window lives in LDS (<= 3 KB per step)
 struct GenArgs {
     const int32_t *gene_ptr, *attr_id;
     const double *wtab;       // [A*L] state weights
@@ -301,22 +300,10 @@ struct GenArgs {
     double v_wmax, v_tmax;        // max |state weight|, max |transition|: the bound M of the margin
     int32_t wave_tmax;            // gl_viterbi_wave: contigs longer than this are left to the chunked kernels (0: none is)
     int32_t rows_rescale_period;  // gl_chunk_rows_mfma: steps between two power-of-two rescalings of a column (1 or 4; host: 4 max|trans| < 600)
-    // windowed path: slot space of the plan
-    const int32_t *c_slot, *c_gene, *c_n;
-    const uint64_t *start_bits;
-    double *p_out;
-    int32_t K, S, W, label;
 };
 // attr_value (the *_valued entries): the value of every attribute entry, parallel to a.attr_id; null = every value is 1, the
 // kernel as it was.  No other kernel reads the values (a.v_wmax then carries max|v| of the batch: crf_plan.cpp)
 hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr);
-hipError_t launch_gen_windowed(const GenArgs &a, hipStream_t stream);   // p_out must be zeroed first
-// 3 or 4 labels: one lane per window start (the two-label kernel's design); tile geometry gen_small_tile_out(W)
-constexpr int kGenTileThreads = 256;  // window starts per workgroup of every kernel with that geometry (gen_small_tile_out)
-bool gen_small_ok(int L, int W, const double *trans_host);
-int gen_small_tile_out(int W);
-hipError_t launch_gen_windowed_small(const GenArgs &a, const double *trans_host, const int4 *d_tile_desc, int ntiles,
-                                     hipStream_t stream);
 hipError_t launch_gen_marginals(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_viterbi(const GenArgs &a, hipStream_t stream);
 // 9 to 32 labels, batches of many contigs: one wave per contig, CRFsuite's sequential recursion (no chunk tables needed)
@@ -324,25 +311,34 @@ hipError_t launch_gen_viterbi_wave(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_marginals_wave(const GenArgs &a, hipStream_t stream);  // row F likewise (a.E, a.smax, a.alpha, a.scale)
 int gen_chunk_genes();
 
-// ---- every label's windowed marginal in one pass (crf_windowed_all.hip) ------------------------
-// p_all[g][l] = max over the windows covering g of P_w(y_g = l); p_any[g] = max over the same windows of the sum of
-// P_w(y_g = l) over l != background (label-index order, unclipped).  E: gl_state's exp(state - max state).
-struct AllArgs {
-    const double *E;          // [n*L]
-    const double *exp_trans;  // [L*L] exp(trans) (lane-group tier)
-    const int32_t *c_slot, *c_gene, *c_n;
+// ---- any number of labels: windowed marginals, one label or every label (crf_general_windowed.hip) ----
+// label >= 0: p_out[g] = max over the windows covering g of P_w(y_g = label), clipped at 1 by the tile kernels.
+// label < 0: every label in one pass, p_out[g][l] likewise for all l, and p_any[g] = max over the same windows of the sum of
+// P_w(y_g = l) over l != background (label-index order, unclipped).
+constexpr int kGenMaxW = 48;  // window length of the lane-group tier: alpha-hat of a whole window lives in LDS (<= 3 KB per step)
+struct GenWinArgs {
+    const double *E;          // [n*L] gl_state's exp(state - max state)
+    const double *exp_trans;  // [L*L] exp(trans)                  (lane-group tier)
+    const int32_t *c_slot, *c_gene, *c_n;  // slot space of the plan (WinArgs)
     const uint64_t *start_bits;
-    double *p_all;            // [n*L]
-    double *p_any;            // [n] or null (background < 0)
-    int32_t L, K, S, W, background;
+    double *p_out;            // [n], or [n*L] with label < 0
+    double *p_any;            // [n] or null (label >= 0, or no background)
+    int32_t L, K, S, W;
+    int32_t label;            // the queried label, or -1: every label
+    int32_t background;       // label < 0: the label p_any leaves out (-1 without p_any)
+    const double *trans;      // [L*L] raw transition weights      (matrix-core tier)
 };
-// one group of lanes per window start, any L and W <= kGenMaxW: integer atomic maxima, p_all / p_any zeroed first
-hipError_t launch_all_windowed_groups(const AllArgs &a, hipStream_t stream);
-// one lane per window start, 2 to 8 labels under gen_small_ok: tiles of gen_small_tile_out(W) slots, every output stored once
-bool all_small_ok(int L, int W, const double *trans_host);
-hipError_t launch_all_windowed_small(const AllArgs &a, const double *trans_host, const int4 *d_tile_desc, int ntiles,
+// one group of lanes per window start, any L and W <= kGenMaxW: integer atomic maxima, p_out / p_any zeroed first
+hipError_t launch_gen_windowed(const GenWinArgs &a, hipStream_t stream);
+// the tile kernels, under gen_small_ok: one lane per window start (2 to 8 labels) or, for one label, sixteen windows per wave
+// on the matrix cores (9 to 32 labels); tiles of gen_small_tile_out(W) slots, every output stored once
+constexpr int kGenTileThreads = 256;  // window starts per workgroup of every kernel with that geometry (gen_small_tile_out)
+bool gen_small_ok(int L, int W, const double *trans_host);
+bool all_small_ok(int L, int W, const double *trans_host);  // the same for every label: L <= 8
+int gen_small_tile_out(int W);
+hipError_t launch_gen_windowed_small(const GenWinArgs &a, const double *trans_host, const int4 *d_tile_desc, int ntiles,
                                      hipStream_t stream);
-// NaN ("no prediction") in every column and in p_any for the gene ranges of skipped contigs
+// NaN ("no prediction") in the L columns of p_all and in p_any (may be null) for the gene ranges of skipped contigs
 hipError_t launch_all_fill_nan(double *p_all, double *p_any, int L, const int2 *ranges, int n_ranges, hipStream_t stream);
 
 // weighted domain composition of called clusters (crf_composition.hip); d_tmp: one double per domain row

@@ -29,6 +29,7 @@
 //     next wave of the workgroup through an 8-B LDS slot per step.
 //   No MFMA: L = 2 recurrences are 2x2 matrix-vector products on fp64 VALU.
 #include "crf_device.hpp"
+#include "crf_lanes.hpp"  // wave_shr1_zero: lane l <- lane l-1, lane 0 <- +0.0 (DPP wave_shr:1, bound_ctrl:1)
 #include "crf_vd_short.hpp"
 
 namespace gecco {
@@ -37,14 +38,6 @@ namespace {
 // 16-byte LDS/global accesses must stay single b128 instructions: a struct double2 gets
 // scalarised and re-paired by the compiler into bank-conflicting ds_read2_b64.
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-// lane l receives lane l-1's value; lane 0 receives +0.0 (DPP wave_shr:1, bound_ctrl:1).
-__device__ __forceinline__ double wave_shr1_zero(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x138, 0xF, 0xF, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x138, 0xF, 0xF, true);
-    return __hiloint2double(hi, lo);
-}
 
 // fmax() on a value that went through DPP bit moves first "canonicalises" it (v_max_f64 x, x, x: the
 // compiler cannot see that it is not a signalling NaN), i.e. two VALU ops per step of the diagonal

@@ -624,13 +624,6 @@ int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig =
         a.chMap = reinterpret_cast<uint8_t *>(w + o_chMap);
         a.chY = reinterpret_cast<int8_t *>(w + o_chY);
     }
-    a.c_slot = p.d_c_slot;
-    a.c_gene = p.d_c_gene;
-    a.c_n = p.d_c_n;
-    a.start_bits = p.d_start_bits;
-    a.K = p.K;
-    a.S = p.S;
-    a.W = p.W;
     return GECCO_CRF_OK;
 }
 
@@ -821,24 +814,48 @@ int start_p_out(const Plan &p, double *d_p_out, bool zero, hipStream_t stream) {
     return check_hip(launch_fill_nan(d_p_out, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch");
 }
 
-int run_windowed_general(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
-                         hipStream_t stream) {
-    if (p.W > kGenMaxW) {
+// The windowed marginals of an any-L plan (crf_general_windowed.hip), one label (label >= 0: d_p [n]) or every label
+// (label = -1: d_p [n][L], d_p_any [n] or null, `background`): the state scores, the outputs' preparation and the tier, which
+// the caller has chosen -- `small`: the tile kernels on `d_tiles`, else one group of lanes per window start.
+int run_windowed_general(Plan &p, const DeviceCsr &csr, int32_t label, int32_t background, double *d_p, double *d_p_any,
+                         bool small, const int4 *d_tiles, int32_t ntiles, hipStream_t stream) {
+    if (!small && p.W > kGenMaxW) {
         set_error("window too long for the any-L kernel (alpha of a whole window is LDS-resident: W <= 48)");
         return GECCO_CRF_EUNSUPPORTED;
     }
-    GenArgs a;
-    int rc = fill_gen_args(p, csr, a);
+    GenArgs g;
+    int rc = fill_gen_args(p, csr, g);
     if (rc) return rc;
-    a.p_out = d_p_out;
+    g.state = nullptr;  // marginals only need exp(state - max)
+    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value), "state score launch"))) return rc;
+    GenWinArgs a{};
+    a.E = g.E;
+    a.exp_trans = g.exp_trans;
+    a.trans = g.trans;
+    a.c_slot = p.d_c_slot;
+    a.c_gene = p.d_c_gene;
+    a.c_n = p.d_c_n;
+    a.start_bits = p.d_start_bits;
+    a.p_out = d_p;
+    a.p_any = d_p_any;
+    a.L = g.L;
+    a.K = p.K;
+    a.S = p.S;
+    a.W = p.W;
     a.label = label;
-    if ((rc = start_p_out(p, d_p_out, true, stream))) return rc;
-    double *keep_state = a.state;
-    a.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(a, stream, csr.attr_value), "state score launch"))) return rc;
-    a.state = keep_state;
-    if (p.gen_small)
-        return check_hip(launch_gen_windowed_small(a, p.model->trans.data(), p.d_tile_desc, p.ntiles, stream), "windowed launch");
+    a.background = background;
+    // the lane-group tier takes maxima in place: +0.0 everywhere first (numpy.zeros of crf/__init__.py:251); the tile kernels
+    // store every gene of slot space once.  Then "no prediction" for the genes of skipped contigs, which lie outside slot
+    // space and are written by neither
+    const int cols = label < 0 ? a.L : 1;
+    if (!small) {
+        if ((rc = check_hip(hipMemsetAsync(d_p, 0, size_t(p.n_genes) * size_t(cols) * 8, stream), "memset p"))) return rc;
+        if (d_p_any && (rc = check_hip(hipMemsetAsync(d_p_any, 0, size_t(p.n_genes) * 8, stream), "memset p"))) return rc;
+    }
+    if (!p.skipped.empty() &&
+        (rc = check_hip(launch_all_fill_nan(d_p, d_p_any, cols, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch")))
+        return rc;
+    if (small) return check_hip(launch_gen_windowed_small(a, p.model->trans.data(), d_tiles, ntiles, stream), "windowed launch");
     return check_hip(launch_gen_windowed(a, stream), "windowed launch");
 }
 }  // namespace
@@ -863,7 +880,8 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
     if (rc || ends_here(p.n_genes == 0, !csr.gene_ptr || !d_p_out, rc)) return rc;
     if ((rc = use_device(p.device))) return rc;
     const Model &m = *p.model;
-    if (p.general) return run_windowed_general(p, csr, label, d_p_out, stream);
+    // (the tier of the single-label entry was chosen when the plan was built: gen_small, on the plan's own tile table)
+    if (p.general) return run_windowed_general(p, csr, label, -1, d_p_out, nullptr, p.gen_small, p.d_tile_desc, p.ntiles, stream);
     WinArgs a{};
     a.gene_ptr = csr.gene_ptr;
     a.attr_id = csr.attr_id;
@@ -929,7 +947,7 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
     return check_hip(launch_windowed(a, stream), "windowed launch");
 }
 
-// ---- every label's windowed marginals (crf_windowed_all.hip) --------------------------------
+// ---- every label's windowed marginals (crf_general_windowed.hip) --------------------------------
 namespace {
 // the lane-per-window tier serves this plan (GECCO_CRF_GENERAL_GROUPS=1: the lane-group tier, as for the single-label kernels)
 bool all_small_tier(const Plan &p) {
@@ -984,45 +1002,12 @@ int plan_run_windowed_all(Plan &p, const DeviceCsr &csr, int32_t background, dou
     }
     if (ends_here(p.n_genes == 0, !csr.gene_ptr || !d_p_all, rc)) return rc;
     if ((rc = use_device(p.device))) return rc;
+    // (the tier of this entry is chosen per call, on a tile table of that geometry: all_tiles)
     const bool small = all_small_tier(p);
-    if (!small && p.W > kGenMaxW) {
-        set_error("window too long for the any-L kernel (alpha of a whole window is LDS-resident: W <= 48)");
-        return GECCO_CRF_EUNSUPPORTED;
-    }
-    GenArgs g;
-    if ((rc = fill_gen_args(p, csr, g))) return rc;
-    g.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value), "state score launch"))) return rc;
-    AllArgs a{};
-    a.E = g.E;
-    a.exp_trans = g.exp_trans;
-    a.c_slot = p.d_c_slot;
-    a.c_gene = p.d_c_gene;
-    a.c_n = p.d_c_n;
-    a.start_bits = p.d_start_bits;
-    a.p_all = d_p_all;
-    a.p_any = d_p_any;
-    a.L = p.model->L;
-    a.K = p.K;
-    a.S = p.S;
-    a.W = p.W;
-    a.background = background;
-    // the lane-group tier takes maxima in place: +0.0 everywhere first; then "no prediction" for the genes of skipped contigs,
-    // which lie outside slot space and are written by neither tier
-    if (!small) {
-        if ((rc = check_hip(hipMemsetAsync(d_p_all, 0, size_t(p.n_genes) * size_t(a.L) * 8, stream), "memset p"))) return rc;
-        if (d_p_any && (rc = check_hip(hipMemsetAsync(d_p_any, 0, size_t(p.n_genes) * 8, stream), "memset p"))) return rc;
-    }
-    if (!p.skipped.empty() &&
-        (rc = check_hip(launch_all_fill_nan(d_p_all, d_p_any, a.L, p.d_skipped, int(p.skipped.size()), stream), "fill_nan launch")))
-        return rc;
-    if (small) {
-        const int4 *d_tiles = nullptr;
-        int32_t ntiles = 0;
-        if ((rc = all_tiles(p, &d_tiles, &ntiles))) return rc;
-        return check_hip(launch_all_windowed_small(a, p.model->trans.data(), d_tiles, ntiles, stream), "windowed launch");
-    }
-    return check_hip(launch_all_windowed_groups(a, stream), "windowed launch");
+    const int4 *d_tiles = nullptr;
+    int32_t ntiles = 0;
+    if (small && (rc = all_tiles(p, &d_tiles, &ntiles))) return rc;
+    return run_windowed_general(p, csr, -1, background, d_p_all, d_p_any, small, d_tiles, ntiles, stream);
 }
 
 // ---- whole-contig scans (rows F, V) ------------------------------------------------------

@@ -153,7 +153,7 @@ struct Plan {
     bool valued = false;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
-    // every label's windowed marginals (crf_windowed_all.hip): the tile table of the lane-per-window tier when the plan's own
+    // every label's windowed marginals (crf_general_windowed.hip): the tile table of the lane-per-window tier when the plan's own
     // table has another geometry (2-label plans), built on first use
     int4 *d_all_tiles = nullptr;
     size_t all_tiles_cap = 0;
@@ -177,7 +177,7 @@ int plan_run_segment(Plan &p, const double *d_p, const uint8_t *d_annotated, con
 int plan_run_windowed(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_out,
                       hipStream_t stream);
 // every label's windowed marginal in one pass: d_p_all [n_genes][L]; d_p_any [n_genes] = the windowed probability of any label
-// but `background`, or null with background == -1 (crf_windowed_all.hip)
+// but `background`, or null with background == -1 (crf_general_windowed.hip)
 int plan_run_windowed_all(Plan &p, const DeviceCsr &csr, int32_t background, double *d_p_all,
                           double *d_p_any, hipStream_t stream);
 const char *plan_all_kernel_name(const Plan &p);

@@ -2,7 +2,7 @@
 
 ``TypedClusterCRF`` trains a many-label CRF on GECCO's tables (``train.build_training_set`` with up to 32 labels,
 ``train.fit_training_set``), scores genes with ONE device pass that gives every label's windowed probability and the
-probability of lying in any cluster (``_native.Model.windowed_marginals_all``, ``csrc/crf_windowed_all.hip``), calls
+probability of lying in any cluster (``_native.Model.windowed_marginals_all``, ``csrc/crf_general_windowed.hip``), calls
 clusters on the latter with the segment kernel, and gives every call a type and per-type probabilities from the former:
 the ``type`` and ``*_probability`` columns of ``clusters.tsv``, which the random forest fills otherwise.
 

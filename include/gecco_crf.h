@@ -88,7 +88,7 @@ int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t device,
                                  const int32_t *gene_ptr, const int32_t *attr_id,
                                  int32_t window, int32_t step, int32_t label, int32_t pad,
                                  double *p_out /* n_genes */);
-/* Row W for EVERY label in one pass (ABI 2.11, additive; crf_windowed_all.hip): the windows, padding, centring and
+/* Row W for EVERY label in one pass (ABI 2.11, additive; crf_general_windowed.hip): the windows, padding, centring and
  * `step` of gecco_crf_windowed_marginals, one forward-backward per window.
  *   p_all[g][l] = max over the windows covering gene g of P_w(y_g = l)            (row-major [n_genes][L])
  *   p_any[g]    = max over the same windows of sum_{l != background} P_w(y_g = l)  (label-index order, not clipped)

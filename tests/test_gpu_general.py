@@ -1,4 +1,4 @@
-"""GPU parity of the any-number-of-labels kernels (crf_general.hip):
+"""GPU parity of the any-number-of-labels kernels (crf_general.hip, crf_general_windowed.hip):
 windowed marginals, whole-contig marginals and Viterbi for CRFsuite models with L != 2
 labels, and the same kernels forced onto 2-label models as an on-device cross-check of the
 specialised ones.  Checker: the CPU oracle ([EXT] CRFsuite semantics) + brute-force

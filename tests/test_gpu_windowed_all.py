@@ -1,4 +1,4 @@
-"""Every label's windowed marginal in one device pass (csrc/crf_windowed_all.hip: `gl_all_small`, one lane per window
+"""Every label's windowed marginal in one device pass (csrc/crf_general_windowed.hip: `gl_all_small`, one lane per window
 for 2 to 8 labels; `gl_all_groups`, one group of lanes per window for everything else) against the numpy yardstick
 (tests/typed_yardstick.py) and against the single-label entry on the device.  Tolerances: 1e-12 against the yardstick,
 as tests/test_gpu_general.py holds the single-label kernels to; 2e-12 between two device results that are each within

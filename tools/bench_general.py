@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Throughput of the any-label-count kernels (crf_general.hip) on a C2-shaped
+"""Throughput of the any-label-count kernels (crf_general.hip, crf_general_windowed.hip) on a C2-shaped
 batch (1 000 contigs, ~2e5 genes, A = 35 000) for L = 3, 8, 32, and of the same kernels forced
 onto the 2-label model next to the specialised ones.  Run on the GPU box; prints one JSON object."""
 import json
