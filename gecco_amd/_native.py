@@ -20,6 +20,7 @@ _c_i32p = ctypes.POINTER(ctypes.c_int32)
 _c_f64p = ctypes.POINTER(ctypes.c_double)
 _c_u8p = ctypes.POINTER(ctypes.c_uint8)
 _c_i8p = ctypes.POINTER(ctypes.c_int8)
+_c_u32p = ctypes.POINTER(ctypes.c_uint32)
 _vp = ctypes.c_void_p
 
 # name -> (restype, argtypes); every symbol include/gecco_crf.h declares
@@ -66,6 +67,20 @@ SIGNATURES = {
         ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_f64p, _c_f64p]),
     "gecco_crf_viterbi_valued": (
         ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_i8p, _c_f64p]),
+    "gecco_crf_windowed_marginals_constrained": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int32, _c_f64p],
+    ),
+    "gecco_crf_windowed_marginals_all_constrained": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, ctypes.c_int32,
+         ctypes.c_int32, ctypes.c_int32, _c_f64p, _c_f64p],
+    ),
+    "gecco_crf_marginals_full_constrained": (
+        ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_f64p, _c_f64p]),
+    "gecco_crf_viterbi_constrained": (
+        ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i8p, _c_f64p]),
     "gecco_crf_segment": (
         ctypes.c_int,
         [ctypes.c_int32, _c_f64p, _c_u8p, _c_i32p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
@@ -507,10 +522,14 @@ class Model:
     # ``values=``: one float64 per attribute entry, parallel to ``attr_id`` (CRFsuite's name:value items): the state score of
     # a gene is the sum of value * weight, and the call takes the ``*_valued`` entry (the any-L kernels at every label
     # count).  None: the unvalued entry, as ever.
-    def _oneshot(self, name, contig_ptr, gene_ptr, attr_id, values, device):
+    # ``allowed=``: one uint32 per gene, bit y set when the gene may take label y (the trainers' masks): the call is the same
+    # call on the lattice without the disallowed (gene, label) pairs, and takes the ``*_constrained`` entry, with ``values``
+    # or without.  None: today's call, bit for bit.
+    def _oneshot(self, name, contig_ptr, gene_ptr, attr_id, values, device, allowed=None):
         """The CSR arguments of the one-shot entry ``name``, or of ``name + "_valued"`` when ``values`` are given (their
-        pointer goes in behind ``attr_id``'s).  Returns ``(n_genes, n_contigs, run)``; ``run(*tail)`` calls the entry with
-        the arguments that follow the CSR arrays."""
+        pointer goes in behind ``attr_id``'s), or of ``name + "_constrained"`` when ``allowed`` is (the values' pointer, or
+        NULL, then the masks').  Returns ``(n_genes, n_contigs, run)``; ``run(*tail)`` calls the entry with the arguments
+        that follow the CSR arrays."""
         contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
         n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
         if values is not None:
@@ -521,39 +540,50 @@ class Model:
         if attr_id.size == 0:
             attr_id = np.zeros(1, dtype=np.int32)
         head = [self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p)]
+        if allowed is not None:
+            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
+            if allowed.size != n:
+                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
+            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+            head += [None if values is None else _ptr(values, _c_f64p), _ptr(allowed, _c_u32p)]
+            entry = getattr(self._lib, name + "_constrained")
+            return n, nc, lambda *tail: _check(entry(*head, *tail))
         if values is not None:
             head.append(_ptr(values, _c_f64p))
         entry = getattr(self._lib, name if values is None else name + "_valued")
         return n, nc, lambda *tail: _check(entry(*head, *tail))  # (`head` keeps the arrays alive)
 
-    def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0, values=None):
-        n, _, run = self._oneshot("gecco_crf_windowed_marginals", contig_ptr, gene_ptr, attr_id, values, device)
+    def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0, values=None,
+                           allowed=None):
+        n, _, run = self._oneshot("gecco_crf_windowed_marginals", contig_ptr, gene_ptr, attr_id, values, device, allowed)
         out = np.zeros(max(n, 1), dtype=np.float64)
         run(int(window), int(step), int(label), int(bool(pad)), _ptr(out, _c_f64p))
         return out[:n]
 
     def windowed_marginals_all(self, contig_ptr, gene_ptr, attr_id, window, step=1, background=None, pad=True, device=0,
-                               values=None):
+                               values=None, allowed=None):
         """Every label's windowed probability in one device pass: ``(p_all [n, L], p_any [n] or None)``; ``p_any`` is the
         windowed probability of any label but ``background`` (a label id)."""
-        n, _, run = self._oneshot("gecco_crf_windowed_marginals_all", contig_ptr, gene_ptr, attr_id, values, device)
+        n, _, run = self._oneshot("gecco_crf_windowed_marginals_all", contig_ptr, gene_ptr, attr_id, values, device, allowed)
         p_all = np.zeros((max(n, 1), self.num_labels), dtype=np.float64)
         p_any = None if background is None else np.zeros(max(n, 1), dtype=np.float64)
         run(int(window), int(step), -1 if background is None else int(background), int(bool(pad)), _ptr(p_all, _c_f64p),
             None if p_any is None else _ptr(p_any, _c_f64p))
         return p_all[:n], (None if p_any is None else p_any[:n])
 
-    def marginals_full(self, contig_ptr, gene_ptr, attr_id, device=0, values=None):
-        n, nc, run = self._oneshot("gecco_crf_marginals_full", contig_ptr, gene_ptr, attr_id, values, device)
+    def marginals_full(self, contig_ptr, gene_ptr, attr_id, device=0, values=None, allowed=None):
+        """``(marginals [n, L], log Z [n_contigs])``; with ``allowed``, the marginals given that the path lies inside the
+        sets (a disallowed entry is exactly 0.0) and ``log Z_A``."""
+        n, nc, run = self._oneshot("gecco_crf_marginals_full", contig_ptr, gene_ptr, attr_id, values, device, allowed)
         marg = np.zeros((max(n, 1), self.num_labels), dtype=np.float64)
         ln = np.zeros(max(nc, 1), dtype=np.float64)
         run(_ptr(marg, _c_f64p), _ptr(ln, _c_f64p))
         return marg[:n], ln[:nc]
 
-    def viterbi(self, contig_ptr, gene_ptr, attr_id, device=0, want_score=True, values=None):
+    def viterbi(self, contig_ptr, gene_ptr, attr_id, device=0, want_score=True, values=None, allowed=None):
         """Best label path per contig; with `want_score=False` returns (labels, None) and 2-label
-        models take the cheaper score-difference form of the recursion."""
-        n, nc, run = self._oneshot("gecco_crf_viterbi", contig_ptr, gene_ptr, attr_id, values, device)
+        models take the cheaper score-difference form of the recursion.  With ``allowed``: the best path inside the sets."""
+        n, nc, run = self._oneshot("gecco_crf_viterbi", contig_ptr, gene_ptr, attr_id, values, device, allowed)
         y = np.zeros(max(n, 1), dtype=np.int8)
         sc = np.zeros(max(nc, 1), dtype=np.float64) if want_score else None
         run(_ptr(y, _c_i8p), _ptr(sc, _c_f64p) if want_score else None)

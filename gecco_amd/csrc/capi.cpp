@@ -98,6 +98,7 @@ int fail(const char *msg) {
     set_error(msg);
     return GECCO_CRF_EINVAL;
 }
+int fail(const std::string &msg) { return fail(msg.c_str()); }
 
 // The argument checks that the one-shots share, each message written once.  They come before any device work, so that an
 // argument error surfaces even on a box without a GPU.
@@ -674,11 +675,12 @@ GECCO_API int gecco_crf_viterbi(const gecco_crf_model *m, int32_t device, const 
     GECCO_GUARD_END
 }
 
-// ---- one-shots on one plan over the whole batch: every label's windowed marginals (ABI 2.11.0) and the entries with a value
-// per attribute entry (ABI 2.13.0) ---------------------------------------------------------------------------------------
+// ---- one-shots on one plan over the whole batch: every label's windowed marginals (ABI 2.11.0), the entries with a value
+// per attribute entry (ABI 2.13.0) and those with a mask of allowed labels per gene (ABI 2.15.0) ------------------------------
 namespace {
 // A batch resident on the device for one call: one plan over all of it, and one block with the rebased row pointers, the
-// attribute ids, their values (a valued batch: csr.attr_value; null means unvalued) and the outputs.
+// attribute ids, their values (a valued batch: csr.attr_value; null means unvalued), the masks of allowed labels (a masked batch:
+// csr.allowed) and the outputs.
 struct ResidentBatch {
     Plan plan;
     char *d = nullptr;
@@ -701,11 +703,13 @@ int check_output(const int32_t *contig_ptr, int32_t n_contigs, const void *out) 
 
 // The host checks of the CSR arrays (before any device work), the plan, and the upload.  `valued`: the plan takes the any-L
 // kernels at every label count and attr_value holds a finite value per attribute entry; otherwise attr_value is not read.
+// `masked` (the *_constrained entries): `allowed` holds one mask per gene, indexed like the rows of gene_ptr (gene g of the caller's
+// arrays), each with a bit below L and none at or above it; otherwise `allowed` is not read.
 // Output i gets a part of the block, at b.out(i): per_gene[i] bytes for every gene (i = 0, 1), per_contig for every contig
 // (i = 2).  Returns with b.n == 0 for a batch without genes (nothing to run).
 int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
-               const int32_t *attr_id, const double *attr_value, bool valued, int32_t window, int32_t step, int32_t pad,
-               bool windowed, const size_t per_gene[2], size_t per_contig, ResidentBatch &b) {
+               const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int32_t window,
+               int32_t step, int32_t pad, bool windowed, const size_t per_gene[2], size_t per_contig, ResidentBatch &b) {
     if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
     const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
     if (n > 0 && !gene_ptr) return fail("null buffer");
@@ -723,15 +727,29 @@ int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_p
         }
         vmax = std::max(vmax, std::fabs(v));
     }
+    if (masked && n > 0) {
+        if (!allowed) return fail("null allowed with genes (one mask of allowed labels per gene)");
+        const int32_t L = m->m.L;
+        const uint32_t beyond = L >= 32 ? 0u : ~0u << L;  // the bits at or above L
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t g = int64_t(contig_ptr[0]) + i;
+            if (allowed[g] == 0) return fail("constrained: gene " + std::to_string(g) + " allows no label (a mask of 0)");
+            if (allowed[g] & beyond)
+                return fail("constrained: gene " + std::to_string(g) + " allows a label at or above num_labels = " + std::to_string(L) +
+                            " (mask " + std::to_string(allowed[g]) + ")");
+        }
+    }
     int rc = check_device(device);
     if (rc) return rc;
     b.plan.valued = valued;
+    b.plan.masked = masked;
     b.plan.windowed_use = windowed;
     if ((rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, b.plan))) return rc;
     if (b.plan.n_genes == 0) return GECCO_CRF_OK;
     const size_t b_gp = size_t(n + 1) * 4, n_at = size_t(nnz ? nnz : 1);
     Carver blk;
     const size_t o_gp = blk.take(b_gp), o_at = blk.take(n_at * 4), o_val = valued ? blk.take(n_at * 8) : 0;
+    const size_t o_mask = masked ? blk.take(size_t(n) * 4) : 0;
     b.out_off[0] = blk.take(per_gene[0] * size_t(n) + 8);
     b.out_off[1] = blk.take(per_gene[1] * size_t(n) + 8);
     b.out_off[2] = blk.take(per_contig * size_t(n_contigs) + 8);
@@ -744,6 +762,8 @@ int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_p
     if (!rc && nnz) rc = check_hip(hipMemcpy(b.d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
     if (!rc && nnz && valued)
         rc = check_hip(hipMemcpy(b.d + o_val, attr_value + a0, size_t(nnz) * 8, hipMemcpyHostToDevice), "upload attr_value");
+    if (!rc && masked)
+        rc = check_hip(hipMemcpy(b.d + o_mask, allowed + contig_ptr[0], size_t(n) * 4, hipMemcpyHostToDevice), "upload allowed");
     if (rc) return rc;
     b.n = n;
     b.csr.gene_ptr = reinterpret_cast<const int32_t *>(b.d + o_gp);
@@ -752,6 +772,7 @@ int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_p
         b.csr.attr_value = reinterpret_cast<const double *>(b.d + o_val);
         b.csr.vmax_abs = vmax;
     }
+    if (masked) b.csr.allowed = reinterpret_cast<const uint32_t *>(b.d + o_mask);
     return GECCO_CRF_OK;
 }
 
@@ -764,8 +785,8 @@ int batch_fetch(int rc, void *dst, const void *src, size_t bytes, const char *wh
 }
 
 int windowed_all(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
-                 const int32_t *attr_id, const double *attr_value, bool valued, int32_t window, int32_t step, int32_t background,
-                 int32_t pad, double *p_all, double *p_any) {
+                 const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int32_t window,
+                 int32_t step, int32_t background, int32_t pad, double *p_all, double *p_any) {
     if (!m) return GECCO_CRF_EINVAL;
     int rc;
     if ((rc = check_window(window, step)) || (rc = check_background(m, background, p_any))) return rc;
@@ -774,7 +795,8 @@ int windowed_all(const gecco_crf_model *m, int32_t device, const int32_t *contig
     if ((rc = check_output(contig_ptr, n_contigs, p_all))) return rc;
     ResidentBatch b;
     const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 8};
-    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, window, step, pad, true, per_gene, 0, b);
+    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, window, step, pad, true,
+                    per_gene, 0, b);
     if (rc || b.n == 0) return rc;
     rc = plan_run_windowed_all(b.plan, b.csr, background, b.out<double>(0), p_any ? b.out<double>(1) : nullptr, nullptr);
     rc = batch_wait(rc, "windowed marginals");
@@ -788,22 +810,23 @@ GECCO_API int gecco_crf_windowed_marginals_all(const gecco_crf_model *m, int32_t
                                                int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
                                                int32_t window, int32_t step, int32_t background, int32_t pad, double *p_all,
                                                double *p_any) {
-    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, nullptr, false, window, step, background, pad, p_all,
-                        p_any);
+    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, nullptr, false, nullptr, false, window, step, background,
+                        pad, p_all, p_any);
 }
 
 GECCO_API int gecco_crf_windowed_marginals_all_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
                                                       int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
                                                       const double *attr_value, int32_t window, int32_t step,
                                                       int32_t background, int32_t pad, double *p_all, double *p_any) {
-    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, window, step, background, pad, p_all,
-                        p_any);
+    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, nullptr, false, window, step, background,
+                        pad, p_all, p_any);
 }
 
-GECCO_API int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
-                                                  int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
-                                                  const double *attr_value, int32_t window, int32_t step, int32_t label,
-                                                  int32_t pad, double *p_out) {
+namespace {
+// The three other one-shots of the family, with values (`valued`), masks (`masked`) or both.
+int windowed_one(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                 const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int32_t window,
+                 int32_t step, int32_t label, int32_t pad, double *p_out) {
     if (!m) return GECCO_CRF_EINVAL;
     int rc;
     if ((rc = check_window(window, step)) || (rc = check_label(m, label))) return rc;
@@ -812,23 +835,25 @@ GECCO_API int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int3
     if ((rc = check_output(contig_ptr, n_contigs, p_out))) return rc;
     ResidentBatch b;
     const size_t per_gene[2] = {8, 0};
-    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, window, step, pad, true, per_gene, 0, b);
+    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, window, step, pad, true,
+                    per_gene, 0, b);
     if (rc || b.n == 0) return rc;
     rc = batch_wait(plan_run_windowed(b.plan, b.csr, label, b.out<double>(0), nullptr), "windowed marginals");
     return batch_fetch(rc, p_out, b.out<double>(0), size_t(b.n) * 8, "download p");
     GECCO_GUARD_END
 }
 
-GECCO_API int gecco_crf_marginals_full_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
-                                              int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
-                                              const double *attr_value, double *marg, double *lognorm) {
+int marginals_full_one(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                       const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked,
+                       double *marg, double *lognorm) {
     if (!m) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
     if (!marg && !lognorm) return GECCO_CRF_OK;
     ResidentBatch b;
     const size_t L = size_t(m->m.L), per_gene[2] = {L * 8, 0};
-    int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, 1, 1, 1, false, per_gene, 8, b);
+    int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false, per_gene,
+                        8, b);
     if (rc || b.n == 0) {
         for (int32_t c = 0; !rc && lognorm && c < n_contigs; ++c) lognorm[c] = 0.0;  // (contigs without genes: log Z = 0)
         return rc;
@@ -840,16 +865,17 @@ GECCO_API int gecco_crf_marginals_full_valued(const gecco_crf_model *m, int32_t 
     GECCO_GUARD_END
 }
 
-GECCO_API int gecco_crf_viterbi_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
-                                       const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
-                                       int8_t *y_out, double *score) {
+int viterbi_one(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int8_t *y_out,
+                double *score) {
     if (!m) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
     if (!y_out) return check_output(contig_ptr, n_contigs, y_out);  // (no genes: nothing to label)
     ResidentBatch b;
     const size_t per_gene[2] = {1, 0};
-    int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, 1, 1, 1, false, per_gene, 8, b);
+    int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false, per_gene,
+                        8, b);
     if (rc || b.n == 0) {
         for (int32_t c = 0; !rc && score && c < n_contigs; ++c) score[c] = 0.0;
         return rc;
@@ -858,6 +884,61 @@ GECCO_API int gecco_crf_viterbi_valued(const gecco_crf_model *m, int32_t device,
     rc = batch_fetch(rc, y_out, b.out<int8_t>(0), size_t(b.n), "download labels");
     return batch_fetch(rc, score, b.out<double>(2), size_t(n_contigs) * 8, "download score");
     GECCO_GUARD_END
+}
+}  // namespace
+
+GECCO_API int gecco_crf_windowed_marginals_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                  int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                  const double *attr_value, int32_t window, int32_t step, int32_t label,
+                                                  int32_t pad, double *p_out) {
+    return windowed_one(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, nullptr, false, window, step, label, pad,
+                        p_out);
+}
+
+GECCO_API int gecco_crf_marginals_full_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                              int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                              const double *attr_value, double *marg, double *lognorm) {
+    return marginals_full_one(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, nullptr, false, marg, lognorm);
+}
+
+GECCO_API int gecco_crf_viterbi_valued(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                       const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                       int8_t *y_out, double *score) {
+    return viterbi_one(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, true, nullptr, false, y_out, score);
+}
+
+// ---- allowed-label sets at inference (ABI 2.15.0): the *_valued arguments plus one mask per gene; attr_value may be NULL (no
+// values), so one family serves masked calls with and without values
+GECCO_API int gecco_crf_windowed_marginals_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                       int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                       const double *attr_value, const uint32_t *allowed, int32_t window,
+                                                       int32_t step, int32_t label, int32_t pad, double *p_out) {
+    return windowed_one(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, attr_value != nullptr, allowed, true, window,
+                        step, label, pad, p_out);
+}
+
+GECCO_API int gecco_crf_windowed_marginals_all_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                           int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                           const double *attr_value, const uint32_t *allowed, int32_t window,
+                                                           int32_t step, int32_t background, int32_t pad, double *p_all,
+                                                           double *p_any) {
+    return windowed_all(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, attr_value != nullptr, allowed, true, window,
+                        step, background, pad, p_all, p_any);
+}
+
+GECCO_API int gecco_crf_marginals_full_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                   int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                   const double *attr_value, const uint32_t *allowed, double *marg,
+                                                   double *lognorm) {
+    return marginals_full_one(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, attr_value != nullptr, allowed, true, marg,
+                              lognorm);
+}
+
+GECCO_API int gecco_crf_viterbi_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                            const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                            const uint32_t *allowed, int8_t *y_out, double *score) {
+    return viterbi_one(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, attr_value != nullptr, allowed, true, y_out,
+                       score);
 }
 
 namespace {

@@ -303,7 +303,11 @@ struct GenArgs {
 };
 // attr_value (the *_valued entries): the value of every attribute entry, parallel to a.attr_id; null = every value is 1, the
 // kernel as it was.  No other kernel reads the values (a.v_wmax then carries max|v| of the batch: crf_plan.cpp)
-hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr);
+// allowed (the *_constrained entries): one mask of allowed labels per gene; null = every label is allowed, the kernels as they
+// were.  A disallowed label gets state -infinity and E exactly 0, smax is the maximum over the allowed labels; no other kernel
+// reads the masks
+hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr,
+                            const uint32_t *allowed = nullptr);
 hipError_t launch_gen_marginals(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_viterbi(const GenArgs &a, hipStream_t stream);
 // 9 to 32 labels, batches of many contigs: one wave per contig, CRFsuite's sequential recursion (no chunk tables needed)

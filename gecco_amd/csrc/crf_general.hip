@@ -36,13 +36,20 @@ __device__ __forceinline__ int gl_chunk_end(const GenArgs &a, long long ci) {
 // state[g][y] = sum_a w[a][y]; E[g][y] = exp(state - max_y); smax[g] = max_y state.
 // kValued (the *_valued entries): state[g][y] = sum_a v[a] * w[a][y], attr_value parallel to attr_id, every term
 // added as fma(v, w, acc) in CSR order -- the one multiply-add form of every valued kernel, so that v = 1.0 gives the unvalued
-// sum's bits (fma(1, w, acc) rounds acc + w once).  The unvalued instantiation is the kernel as it was (attr_value, last,
-// is not read there).
-template <int LP, bool kValued>
+// sum's bits (fma(1, w, acc) rounds acc + w once).  The unvalued instantiation is the kernel as it was (attr_value is not read
+// there).
+// kMasked (the *_constrained entries): allowed[g] has bit y set when gene g may take label y.  A disallowed
+// (gene, label) pair leaves the lattice: state = -infinity, E = 0.0 exactly, and the maximum m -- smax, and the shift of E -- is
+// taken over the ALLOWED labels only.  (Over all labels, a disallowed label that leads by 750 would flush every allowed
+// emission to zero.)  Every gene then still has an emission equal to 1, which is what the range guards of the sum-product
+// kernels are argued from.  The host has refused a mask without a bit below L.  The unmasked instantiations do not read
+// `allowed` and keep their code.
+template <int LP, bool kValued, bool kMasked>
 __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene_ptr, const int32_t *__restrict__ attr_id,
                                                 const double *__restrict__ wtab, int L, int A, int n_genes,
                                                 double *__restrict__ state, double *__restrict__ E,
-                                                double *__restrict__ smax, const double *__restrict__ attr_value) {
+                                                double *__restrict__ smax, const double *__restrict__ attr_value,
+                                                const uint32_t *__restrict__ allowed) {
     const int j = threadIdx.x & (LP - 1);
     const long long g = (static_cast<long long>(blockIdx.x) * kGT + threadIdx.x) / LP;
     if (g >= n_genes) return;
@@ -58,12 +65,22 @@ __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene
                 acc += wtab[static_cast<size_t>(id) * L + jj];
         }
     }
-    const double m = group_max<LP>(j < L ? acc : -DBL_MAX);
-    if (j < L) {
-        if (state) state[static_cast<size_t>(g) * L + j] = acc;
-        if (E) E[static_cast<size_t>(g) * L + j] = exp(acc - m);
+    if constexpr (kMasked) {
+        const bool ok = j < L && ((allowed[g] >> j) & 1u);
+        const double m = group_max<LP>(ok ? acc : -DBL_MAX);
+        if (j < L) {
+            if (state) state[static_cast<size_t>(g) * L + j] = ok ? acc : -__builtin_huge_val();
+            if (E) E[static_cast<size_t>(g) * L + j] = ok ? exp(acc - m) : 0.0;
+        }
+        if (j == 0 && smax) smax[g] = m;
+    } else {
+        const double m = group_max<LP>(j < L ? acc : -DBL_MAX);
+        if (j < L) {
+            if (state) state[static_cast<size_t>(g) * L + j] = acc;
+            if (E) E[static_cast<size_t>(g) * L + j] = exp(acc - m);
+        }
+        if (j == 0 && smax) smax[g] = m;
     }
-    if (j == 0 && smax) smax[g] = m;
 }
 
 // ---- row F: whole-contig marginals, one group per contig, CRFsuite's own sequential recursion ----
@@ -1190,19 +1207,30 @@ hipError_t launch_chunked(int what, const GenArgs &a, hipStream_t stream) {
     return hipGetLastError();
 }
 
+template <int LP, bool kValued, bool kMasked>
+void launch_state(const GenArgs &a, hipStream_t stream, const double *attr_value, const uint32_t *allowed) {
+    hipLaunchKernelGGL((gl_state<LP, kValued, kMasked>), dim3(unsigned((static_cast<long long>(a.n_genes) + kGT / LP - 1) / (kGT / LP))),
+                       dim3(kGT), 0, stream, a.gene_ptr, a.attr_id, a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value, allowed);
+}
+
 template <int LP>
-hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr) {
+hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr,
+                     const uint32_t *allowed = nullptr) {
     constexpr int G = kGT / LP;
     auto blocks = [](long long items, int per) { return dim3(unsigned((items + per - 1) / per)); };
     switch (what) {
     case 0:  // state scores
-        if (a.n_genes > 0) {  // (attr_value: the same for every gene of the launch)
-            if (attr_value)
-                hipLaunchKernelGGL((gl_state<LP, true>), blocks(a.n_genes, G), dim3(kGT), 0, stream, a.gene_ptr, a.attr_id,
-                                   a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value);
-            else
-                hipLaunchKernelGGL((gl_state<LP, false>), blocks(a.n_genes, G), dim3(kGT), 0, stream, a.gene_ptr, a.attr_id,
-                                   a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value);
+        if (a.n_genes > 0) {  // (attr_value, allowed: the same for every gene of the launch)
+            if (allowed) {
+                if (attr_value)
+                    launch_state<LP, true, true>(a, stream, attr_value, allowed);
+                else
+                    launch_state<LP, false, true>(a, stream, attr_value, allowed);
+            } else if (attr_value) {
+                launch_state<LP, true, false>(a, stream, attr_value, allowed);
+            } else {
+                launch_state<LP, false, false>(a, stream, attr_value, allowed);
+            }
         }
         break;
     case 2:
@@ -1215,7 +1243,8 @@ hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const doubl
     return hipGetLastError();
 }
 
-hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr) {
+hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr,
+                      const uint32_t *allowed = nullptr) {
     if (a.L <= 0 || a.L > kGenMaxL) return hipErrorNotSupported;
     if ((what == 2 || what == 3) && a.n_chunks > 0) {  // long contigs in the batch: chunked recursions
         if (a.L <= 2) return launch_chunked<2>(what, a, stream);
@@ -1224,17 +1253,17 @@ hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream, const doub
         if (a.L <= 16) return launch_chunked<16>(what, a, stream);
         return launch_chunked<32>(what, a, stream);
     }
-    if (a.L <= 2) return launch_lp<2>(what, a, stream, attr_value);
-    if (a.L <= 4) return launch_lp<4>(what, a, stream, attr_value);
-    if (a.L <= 8) return launch_lp<8>(what, a, stream, attr_value);
-    if (a.L <= 16) return launch_lp<16>(what, a, stream, attr_value);
-    return launch_lp<32>(what, a, stream, attr_value);
+    if (a.L <= 2) return launch_lp<2>(what, a, stream, attr_value, allowed);
+    if (a.L <= 4) return launch_lp<4>(what, a, stream, attr_value, allowed);
+    if (a.L <= 8) return launch_lp<8>(what, a, stream, attr_value, allowed);
+    if (a.L <= 16) return launch_lp<16>(what, a, stream, attr_value, allowed);
+    return launch_lp<32>(what, a, stream, attr_value, allowed);
 }
 
 }  // namespace
 
-hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value) {
-    return launch_any(0, a, stream, attr_value);
+hipError_t launch_gen_state(const GenArgs &a, hipStream_t stream, const double *attr_value, const uint32_t *allowed) {
+    return launch_any(0, a, stream, attr_value, allowed);
 }
 hipError_t launch_gen_marginals(const GenArgs &a, hipStream_t stream) { return launch_any(2, a, stream); }
 hipError_t launch_gen_viterbi(const GenArgs &a, hipStream_t stream) { return launch_any(3, a, stream); }

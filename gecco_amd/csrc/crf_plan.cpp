@@ -368,7 +368,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     }
     {
         const char *env = std::getenv("GECCO_CRF_FORCE_GENERAL");
-        p.general = m.L != 2 || (env && env[0] == '1') || p.valued;  // (valued state scores exist in gl_state alone)
+        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked;  // (valued and masked state scores exist in gl_state alone)
     }
     p.fast_ok = (!p.general && W <= kWinMaxW && rescale_mask_for(m, W, &p.rescale_mask));
     {
@@ -378,7 +378,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
         }();
         // (the environment switch is for windowed marginals of 2-label models: a Viterbi-only or whole-contig layout, or another
         // label count, keeps its kernels; an explicit request -- reference_bits -- for an unsupported shape is an error)
-        p.reference_now = !p.valued && (p.reference_bits || (env_reference && p.windowed_use && m.L == 2 && reference_bits_ok(m.L, W)));
+        p.reference_now = !p.valued && !p.masked && (p.reference_bits || (env_reference && p.windowed_use && m.L == 2 && reference_bits_ok(m.L, W)));
         if (p.reference_now) {
             if (!reference_bits_ok(m.L, W)) {
                 set_error("reference-bits mode serves 2-label models and windows of at most 32 genes");
@@ -754,7 +754,7 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *
     g.score = d_score;
     r.clear(g);
     g.wave_tmax = tail_chunked ? wave_tmax : 0;
-    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch"))) return rc;
     if (!wave) return check_hip(r.chunked(g, stream), r.what);
     if (!tail_chunked || g.n_chunks <= 0) return check_hip(r.wave(g, stream), r.what);
     // the long tail (chunked kernels: short in work, long in dependent launches) NEXT TO the waves of the other contigs:
@@ -771,7 +771,8 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *
 int fill_seq_args(Plan &p, SeqArgs &a, hipStream_t stream);
 
 // What every run entry point checks before it launches, in the order the checks have always had: a device behind the plan and
-// the label (entry points without one pass 0), and a batch that brings values exactly when the layout was built for them ...
+// the label (entry points without one pass 0), and a batch that brings values, and masks, exactly when the layout was built for
+// them ...
 int check_plan(const Plan &p, const DeviceCsr &csr, int32_t label) {
     if (p.device < 0) {
         set_error("host-only plan: no HIP device bound (there is no CPU fallback)");
@@ -784,6 +785,11 @@ int check_plan(const Plan &p, const DeviceCsr &csr, int32_t label) {
     if ((csr.attr_value != nullptr) != p.valued) {
         set_error(p.valued ? "the plan was built for attribute values: the batch has none"
                            : "attribute values given to a plan that was not built for them");
+        return GECCO_CRF_EINVAL;
+    }
+    if ((csr.allowed != nullptr) != p.masked) {
+        set_error(p.masked ? "the plan was built for allowed-label masks: the batch has none"
+                           : "allowed-label masks given to a plan that was not built for them");
         return GECCO_CRF_EINVAL;
     }
     return GECCO_CRF_OK;
@@ -827,7 +833,7 @@ int run_windowed_general(Plan &p, const DeviceCsr &csr, int32_t label, int32_t b
     int rc = fill_gen_args(p, csr, g);
     if (rc) return rc;
     g.state = nullptr;  // marginals only need exp(state - max)
-    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value), "state score launch"))) return rc;
+    if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch"))) return rc;
     GenWinArgs a{};
     a.E = g.E;
     a.exp_trans = g.exp_trans;

@@ -61,11 +61,13 @@ struct Arena {
 
 // One batch's CSR arrays on the device, as every run call takes them: the row pointers and attribute ids, and for a plan laid
 // out with `valued` the value of every attribute entry (parallel to attr_id) with the largest |value| among them, which scales
-// the Viterbi margin's bound on a state score.  The caller keeps the arrays alive until the work is done.
+// the Viterbi margin's bound on a state score; for a plan laid out with `masked`, one mask of allowed labels
+// per gene.  The caller keeps the arrays alive until the work is done.
 struct DeviceCsr {
     const int32_t *gene_ptr = nullptr, *attr_id = nullptr;
     const double *attr_value = nullptr;
     double vmax_abs = 1.0;
+    const uint32_t *allowed = nullptr;
 };
 
 struct Plan {
@@ -151,6 +153,10 @@ struct Plan {
     // belong to a batch, not to the layout: they come with every run call (DeviceCsr), which is refused when it brings values
     // to a layout without `valued`, or none to one with it.
     bool valued = false;
+    // Allowed-label sets (the *_constrained one-shots).  `masked` is set by the owner before plan_build, and works
+    // as `valued` does: the any-L kernels at every label count, no reference-bits mode, and the masks come with every run call
+    // (DeviceCsr::allowed), which is refused when it brings masks to a layout without `masked`, or none to one with it.
+    bool masked = false;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_general_windowed.hip): the tile table of the lane-per-window tier when the plan's own

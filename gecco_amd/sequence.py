@@ -154,27 +154,79 @@ class SequenceCRF:
     def _split(values: np.ndarray, seq_ptr: np.ndarray) -> list:
         return [values[a:b] for a, b in zip(seq_ptr[:-1].tolist(), seq_ptr[1:].tolist())]
 
-    def predict(self, X) -> List[List[str]]:
-        """Viterbi labels of every sequence."""
+    # ``allowed=`` of the prediction methods, and ``y`` of ``log_likelihood``: per sequence a list as long as the sequence whose
+    # entries follow ``fit``'s grammar for ``y`` -- a label, a ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels, or None
+    # for every label of the model.  The prediction is then made on the lattice without the other (item, label) pairs: the
+    # best path inside the sets, the marginals given that the path lies inside them (exactly 0.0 outside).
+    def _label_sets(self, sets, seq_ptr: np.ndarray, what: str) -> Tuple[np.ndarray, bool]:
+        """One uint32 mask per item (bit k: ``classes_[k]`` is allowed), and whether every entry names exactly one label."""
+        index = {c: k for k, c in enumerate(self.classes_)}
+        every = (1 << len(self.classes_)) - 1
+        n_seqs = len(seq_ptr) - 1
+        sets = list(sets)
+        if len(sets) != n_seqs:
+            raise ValueError(f"X holds {n_seqs} sequences and {what} {len(sets)}")
+        masks, single = [], True
+        for k, entries in enumerate(sets):
+            entries = list(entries)
+            if len(entries) != seq_ptr[k + 1] - seq_ptr[k]:
+                raise ValueError(f"sequence {k}: {seq_ptr[k + 1] - seq_ptr[k]} items but {len(entries)} labels")
+            for t, entry in enumerate(entries):
+                if entry is None:
+                    masks.append(every)
+                    single = False
+                    continue
+                names = [str(m) for m in entry] if isinstance(entry, (set, frozenset, list, tuple)) else [str(entry)]
+                if not names:
+                    raise ValueError(f"sequence {k}, item {t}: an empty set allows no label")
+                bits = 0
+                for name in names:
+                    if name not in index:
+                        raise ValueError(f"unknown label {name!r} (classes_: {self.classes_})")
+                    bits |= 1 << index[name]
+                masks.append(bits)
+                single = single and bits & (bits - 1) == 0
+        return np.array(masks, dtype=np.uint32), single
+
+    def _allowed(self, allowed, seq_ptr: np.ndarray) -> Optional[np.ndarray]:
+        return None if allowed is None else self._label_sets(allowed, seq_ptr, "allowed")[0]
+
+    def predict(self, X, allowed=None) -> List[List[str]]:
+        """Viterbi labels of every sequence; with ``allowed``, the best path inside the allowed sets."""
         seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
         if seq_ptr[-1] == 0:
             return [[] for _ in X]
-        y, _ = self._model.viterbi(seq_ptr, item_ptr, attr, device=self.device, values=values)
+        y, _ = self._model.viterbi(seq_ptr, item_ptr, attr, device=self.device, values=values, allowed=masks)
         return [[self.classes_[k] for k in ys.tolist()] for ys in self._split(y, seq_ptr)]
 
-    def predict_marginals(self, X) -> List[np.ndarray]:
-        """Whole-sequence marginals: one ``[n_items, L]`` array per sequence, columns in ``classes_`` order."""
+    def predict_marginals(self, X, allowed=None) -> List[np.ndarray]:
+        """Whole-sequence marginals: one ``[n_items, L]`` array per sequence, columns in ``classes_`` order; with
+        ``allowed``, given that the path lies inside the allowed sets (exactly 0.0 outside them)."""
         seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
         if seq_ptr[-1] == 0:
             return [np.zeros((0, len(self.classes_))) for _ in X]
-        marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device, values=values)
+        marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device, values=values, allowed=masks)
         return self._split(marg, seq_ptr)
 
     def log_likelihood(self, X, y: Sequence[Sequence[str]]) -> np.ndarray:
         """``log p(y | x)`` of every sequence under the model (CRFsuite's ``Tagger.probability`` in logs): the gold path's
         score, gathered on the host from the weight tables (value x weight for items with values), minus the log partition function of the whole-sequence
-        marginals.  An unknown label raises ``ValueError``; an empty sequence gives 0.0."""
+        marginals.  An unknown label raises ``ValueError``; an empty sequence gives 0.0.
+
+        An entry of ``y`` may also be a set of labels or None, as in ``fit``: the result is then ``log Z_A - log Z``, the
+        log-probability that the path lies inside the sets -- the negative of the sequence's term in the partial trainer's
+        objective -- from two whole-sequence forward-backward passes, one on the restricted lattice and one on the full one.
+        (Both take the masked state-score kernel, the second with every label allowed, which has the unmasked kernels' bits:
+        with every entry None the result is exactly 0.0 at every label count.)"""
         seq_ptr, item_ptr, attr, values = self._pack(X)
+        y = [list(yseq) for yseq in y]
+        if any(lab is None or isinstance(lab, (set, frozenset, list, tuple)) for yseq in y for lab in yseq):
+            masks, single = self._label_sets(y, seq_ptr, "y")
+            if not single:
+                return self._log_probability_inside(seq_ptr, item_ptr, attr, values, masks)
+            y = [[next(iter(lab)) if isinstance(lab, (set, frozenset, list, tuple)) else lab for lab in yseq] for yseq in y]
         index = {c: k for k, c in enumerate(self.classes_)}
         labs = [[str(lab) for lab in yseq] for yseq in y]
         n_seqs = len(seq_ptr) - 1
@@ -205,32 +257,48 @@ class SequenceCRF:
         out[full] = np.add.reduceat(score, ptr[:-1]) - lognorm
         return out
 
+    def _log_probability_inside(self, seq_ptr, item_ptr, attr, values, masks: np.ndarray) -> np.ndarray:
+        out = np.zeros(len(seq_ptr) - 1)
+        if seq_ptr[-1] == 0:
+            return out
+        lengths = np.diff(seq_ptr)
+        full = np.flatnonzero(lengths > 0)  # (an empty sequence stays at 0.0 and never reaches the device)
+        ptr = np.concatenate([[0], np.cumsum(lengths[full])]).astype(np.int32)
+        every = np.full(len(masks), (1 << len(self.classes_)) - 1, dtype=np.uint32)
+        _, inside = self._model.marginals_full(ptr, item_ptr, attr, device=self.device, values=values, allowed=masks)
+        _, free = self._model.marginals_full(ptr, item_ptr, attr, device=self.device, values=values, allowed=every)
+        out[full] = inside - free
+        return out
+
     def _windowed(self) -> None:
         self._fitted()
         if self.window_size is None:
             raise ValueError("this SequenceCRF has no window (window_size=None): it has no windowed predictions")
 
-    def predict_windowed(self, X, label: str, pad: bool = True) -> List[np.ndarray]:
+    def predict_windowed(self, X, label: str, pad: bool = True, allowed=None) -> List[np.ndarray]:
         """GECCO's windowed probability of ``label``: per item the maximum, over the windows covering it, of the
-        label's marginal inside the window (``pad``: a sequence shorter than the window is one window)."""
+        label's marginal inside the window (``pad``: a sequence shorter than the window is one window).  With ``allowed``
+        every window runs on the lattice restricted to the allowed sets (padding items allow every label)."""
         self._windowed()
         seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
         if str(label) not in self.classes_:
             raise ValueError(f"unknown label {label!r} (classes_: {self.classes_})")
         if seq_ptr[-1] == 0:
             return [np.zeros(0) for _ in X]
         p = self._model.windowed_marginals(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
                                            label=self.classes_.index(str(label)), pad=pad, device=self.device,
-                                           values=values)
+                                           values=values, allowed=masks)
         return self._split(p, seq_ptr)
 
-    def predict_windowed_all(self, X, background: Optional[str] = None, pad: bool = True):
+    def predict_windowed_all(self, X, background: Optional[str] = None, pad: bool = True, allowed=None):
         """GECCO's windowed probability of every label in one device pass: one ``[n_items, L]`` array per sequence, columns
         in ``classes_`` order (per item and label the maximum, over the windows covering the item, of the label's marginal
         inside the window).  With ``background`` also, second, one ``[n_items]`` array per sequence: the maximum over the
-        same windows of the probability of any label but ``background``."""
+        same windows of the probability of any label but ``background``.  ``allowed``: as in ``predict_windowed``."""
         self._windowed()
         seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
         L = len(self.classes_)
         if background is not None and str(background) not in self.classes_:
             raise ValueError(f"unknown label {background!r} (classes_: {self.classes_})")
@@ -240,7 +308,7 @@ class SequenceCRF:
         bg = None if background is None else self.classes_.index(str(background))
         p_all, p_any = self._model.windowed_marginals_all(seq_ptr, item_ptr, attr, self.window_size, self.window_step,
                                                           background=bg, pad=pad, device=self.device,
-                                                          values=values)
+                                                          values=values, allowed=masks)
         if background is None:
             return self._split(p_all, seq_ptr)
         return self._split(p_all, seq_ptr), self._split(p_any, seq_ptr)

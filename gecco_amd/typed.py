@@ -119,6 +119,35 @@ def gene_labels(n_genes: int, clusters: tables.ClusterTable, join: Any, limit: i
     return labels
 
 
+def known_masks(n_genes: int, known: tables.ClusterTable, join: Any, classes: Sequence[str],
+                background: str = BACKGROUND) -> np.ndarray:
+    """The allowed-label mask of every gene (one uint32, bit k: ``classes[k]``) from what is known about some regions: the
+    overlap join (``train_cli.ClusterJoin``) of the sorted genes with the ``known`` table, as ``gene_labels`` reads it.  A gene
+    that overlaps a row may not take the background label: where the row's label (``cluster_labels``) is one of ``classes``
+    that label alone is allowed, otherwise every label but the background.  A gene under several rows takes the first in
+    ``train_cli.assigned_clusters`` order.  Every other gene allows every label."""
+    from .train_cli import assigned_clusters
+
+    classes = list(classes)
+    if background not in classes:
+        raise ValueError(f"the model has no background label {background!r} (labels: {classes})")
+    every = (1 << len(classes)) - 1
+    no_background = every & ~(1 << classes.index(background))
+    if no_background == 0:
+        raise ValueError("the model has no label but the background: nothing is left for a known region")
+    row_label = cluster_labels(known)
+    masks = [every] * n_genes
+    taken = [False] * n_genes
+    for _, i, _ in assigned_clusters(known, join):
+        label = row_label[i]
+        mask = 1 << classes.index(label) if label in classes and label != background else no_background
+        for g in np.asarray(join.members(i)).tolist():
+            if not taken[g]:
+                taken[g] = True
+                masks[g] = mask
+    return np.array(masks, dtype=np.uint32)
+
+
 def label_type_names(label: str) -> Tuple[str, ...]:
     """The type names a label contains: none for the background, ``"Mixed"`` and ``"Unknown"``."""
     if label in (BACKGROUND, MIXED, UNKNOWN):
@@ -285,9 +314,11 @@ class TypedClusterCRF:
         return self
 
     # ---- prediction
-    def _score(self, genes: Iterable[Any], pad: bool):
+    def _score(self, genes: Iterable[Any], pad: bool, known: Optional[tables.ClusterTable] = None):
         """Genes sorted as ``ClusterCRF.predict_probabilities`` sorts them, their contigs, which contigs are scored, and
-        the device pass: ``p_all`` [n, L] and ``p_any`` [n] (NaN on unscored contigs)."""
+        the device pass: ``p_all`` [n, L] and ``p_any`` [n] (NaN on unscored contigs).  ``known``: a clusters table of
+        regions known beforehand (``known_masks``): every window then runs on the lattice in which a gene of a known region
+        cannot be background, and can only take the region's label where the model has it."""
         from . import packing
 
         model = self._fitted()
@@ -311,9 +342,15 @@ class TypedClusterCRF:
         L = len(self.classes_)
         if not genes:
             return genes, contigs, scored, batch, np.zeros((0, L)), np.zeros(0)
+        allowed = None
+        if known is not None:
+            from .train_cli import join_clusters
+
+            allowed = known_masks(len(genes), known, join_clusters(genes, known, device=self.device), self.classes_, self.background)
         p_all, p_any = model.windowed_marginals_all(batch.item_ptr.astype(np.int32), batch.attr_ptr.astype(np.int32),
                                                     batch.attr_id, W, self.window_step,
-                                                    background=self.classes_.index(self.background), pad=pad, device=self.device)
+                                                    background=self.classes_.index(self.background), pad=pad, device=self.device,
+                                                    allowed=allowed)
         return genes, contigs, scored, batch, p_all, p_any
 
     def _annotated(self, contigs, scored, batch, p_any) -> List[Any]:
@@ -338,32 +375,36 @@ class TypedClusterCRF:
                 gc.enable()
         return out
 
-    def predict_probabilities(self, genes: Iterable[Any], *, pad: bool = True) -> List[Any]:
+    def predict_probabilities(self, genes: Iterable[Any], *, pad: bool = True,
+                              known: Optional[tables.ClusterTable] = None) -> List[Any]:
         """New genes, sorted by (sequence, start), carrying as their probability the windowed probability of lying in any
-        cluster: ``ClusterRefiner`` and the table writers work on them unchanged."""
-        _, contigs, scored, batch, _, p_any = self._score(genes, pad)
+        cluster: ``ClusterRefiner`` and the table writers work on them unchanged.  ``known`` (here and in the other
+        prediction methods): a clusters table of regions known beforehand, whose genes cannot be background (``_score``)."""
+        _, contigs, scored, batch, _, p_any = self._score(genes, pad, known)
         return self._annotated(contigs, scored, batch, p_any)
 
-    def predict_label_probabilities(self, genes: Iterable[Any], *, pad: bool = True) -> np.ndarray:
+    def predict_label_probabilities(self, genes: Iterable[Any], *, pad: bool = True,
+                                    known: Optional[tables.ClusterTable] = None) -> np.ndarray:
         """Every label's windowed probability, ``[n, L]`` in the gene order ``predict_probabilities`` returns, columns in
         ``classes_`` order."""
-        return self._score(genes, pad)[4]
+        return self._score(genes, pad, known)[4]
 
     def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
-                         trim: bool = True, pad: bool = True) -> List[Any]:
+                         trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
         per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
-                                               pad=pad)[1]
+                                               pad=pad, known=known)[1]
 
     def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
-                                   trim: bool = True, pad: bool = True) -> Tuple[List[Any], List[Any]]:
+                                   trim: bool = True, pad: bool = True,
+                                   known: Optional[tables.ClusterTable] = None) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass."""
         from . import _native
         from .refine import _cluster_class
         from .types import _cluster_type_factory
 
-        _, contigs, scored, batch, p_all, p_any = self._score(genes, pad)
+        _, contigs, scored, batch, p_all, p_any = self._score(genes, pad, known)
         annotated = self._annotated(contigs, scored, batch, p_any)
         if not annotated:
             return annotated, []
@@ -417,6 +458,8 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("-E", "--edge-distance", type=int, default=0, help="annotated genes separating a cluster from the edge")
     pr.add_argument("--no-trim", dest="trim", action="store_false", help="keep genes without domains on cluster edges")
     pr.add_argument("--no-pad", dest="pad", action="store_false", help="skip sequences shorter than the window")
+    pr.add_argument("--known", default=None, help="cluster table (TSV) of regions known beforehand: their genes cannot be "
+                    "background, and take the region's type where the model has a label for it")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -441,7 +484,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     crf = TypedClusterCRF.trained(args.model, device=args.device)
     genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
     annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
-                                                      edge_distance=args.edge_distance, trim=args.trim, pad=args.pad)
+                                                      edge_distance=args.edge_distance, trim=args.trim, pad=args.pad,
+                                                      known=None if args.known is None else tables.ClusterTable.load(args.known))
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))

@@ -48,7 +48,8 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
-/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340). */
+/* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
+ * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -674,6 +675,44 @@ int gecco_crf_trainer_sequences_create_partial(int32_t device, int32_t n_problem
                                                const int32_t *num_attrs, const int32_t *num_labels,
                                                const int32_t *const *state_fid, const int32_t *const *trans_fid,
                                                const int32_t *num_features, gecco_crf_trainer_sequences **out);
+
+/* ---- allowed-label sets at inference (ABI 2.15.0, additive; gecco_crf_version() stays 340) ----------------------------------
+ * Constrained decoding: every gene carries a set of allowed labels, one uint32_t with bit y set when label y is allowed, as
+ * the *_create_partial trainers define it (at 32 labels bit 31 is a label like any other).  A constrained call is the
+ * unconstrained call on a lattice in which a disallowed (gene, label) pair has state score -infinity: excluded exactly, not
+ * penalised.
+ *   * Viterbi: CRFsuite's recursion (strict `<`, first arg max) on that table; the path never uses a disallowed label and
+ *     score is its score.
+ *   * Whole-sequence marginals: P(y_t = l | x, path inside the sets); a disallowed entry is exactly 0.0; lognorm is log Z_A,
+ *     so lognorm_constrained - lognorm is the log-probability that the path lies inside the sets.
+ *   * Windowed forms: an independent forward-backward per window on the restricted lattice, the per-gene maximum, p_any as
+ *     before; padding items allow every label; a disallowed entry of p_out / p_all is exactly 0.0.
+ * Arguments: the *_valued sibling's plus `allowed` after attr_value, one mask per gene, indexed like the rows of gene_ptr
+ * (gene g of the caller's arrays: a batch with contig_ptr[0] > 0 reads allowed[contig_ptr[0]] first).  attr_value may be NULL
+ * here: no values.  With values the state scores are the valued ones.  One device per call, one plan over the whole batch (no
+ * session, batch-driver or multi-device form).
+ *   * A constrained call takes the any-L kernels at every label count, like a valued one, with its limits (single-label
+ *     windows of up to 48 genes at 2 labels); reference-bits mode does not apply.  With every mask full the results are the
+ *     bytes of the any-L call without masks.  Results are right wherever the unconstrained call is right for the same model:
+ *     the state scores are shifted by their maximum over the ALLOWED labels, so every gene keeps an emission of 1 and no
+ *     range guard narrows.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL: a NULL allowed with at least one gene; a mask of
+ *     0 ("constrained: gene i allows no label (a mask of 0)"); a mask with a bit at or above the model's label count. */
+int gecco_crf_viterbi_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                  const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* or NULL */,
+                                  const uint32_t *allowed, int8_t *y_out /* n_genes */, double *score);
+int gecco_crf_marginals_full_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                         const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* or NULL */,
+                                         const uint32_t *allowed, double *marg, double *lognorm);
+int gecco_crf_windowed_marginals_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                             int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                             const double *attr_value /* or NULL */, const uint32_t *allowed, int32_t window,
+                                             int32_t step, int32_t label, int32_t pad, double *p_out /* n_genes */);
+int gecco_crf_windowed_marginals_all_constrained(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr,
+                                                 int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
+                                                 const double *attr_value /* or NULL */, const uint32_t *allowed, int32_t window,
+                                                 int32_t step, int32_t background /* label id, or -1 */, int32_t pad,
+                                                 double *p_all /* [n_genes][L] */, double *p_any /* [n_genes], NULL iff background == -1 */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
