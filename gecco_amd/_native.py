@@ -40,6 +40,8 @@ SIGNATURES = {
     "gecco_crf_model_map_attrs": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_char_p), ctypes.c_int32, _c_i32p]),
     "gecco_crf_model_state_weights": (ctypes.c_int, [_vp, _c_f64p, _c_u8p]),
     "gecco_crf_model_trans_weights": (ctypes.c_int, [_vp, _c_f64p, _c_u8p]),
+    "gecco_crf_model_slot_table": (ctypes.c_int, [_vp, ctypes.c_int32, _c_f64p, _c_f64p, _c_i32p]),
+    "gecco_crf_slot_prod_max_cnt": (ctypes.c_int32, [ctypes.c_double]),
     "gecco_crf_device_count": (ctypes.c_int, [_c_i32p]),
     "gecco_crf_windowed_marginals": (
         ctypes.c_int,
@@ -388,8 +390,12 @@ def _preload_hip_runtime(lib_path: str) -> Optional[str]:
     return cand
 
 
+# host-only views of what the library builds for its kernels: no inference or training call goes through them
+_INTROSPECTION_ONLY = frozenset({"gecco_crf_model_slot_table", "gecco_crf_slot_prod_max_cnt"})
+
+
 def load_library(path: Optional[str] = None) -> ctypes.CDLL:
-    """dlopen the native library and bind every declared symbol (raises if any is missing)."""
+    """dlopen the native library and bind every declared symbol (raises if one is missing, the introspection-only ones excepted)."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -402,6 +408,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     _preload_hip_runtime(p)
     lib = ctypes.CDLL(p)
     for name, (res, args) in SIGNATURES.items():
+        if name in _INTROSPECTION_ONLY and not hasattr(lib, name):
+            continue  # (a library built before these existed still loads for A/B runs; calling them then raises AttributeError)
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -510,6 +518,17 @@ class Model:
         present = np.zeros((A, L), dtype=np.uint8)
         _check(self._lib.gecco_crf_model_state_weights(self._h, _ptr(w, _c_f64p), _ptr(present, _c_u8p)))
         return w, present.astype(bool)
+
+    def slot_table(self, label: int = 1):
+        """Two-label models: the factor table of the window kernels' slot constants, as the devices get it: an (A + 1, 2) array of
+        (delta_a, exp(delta_a)) with the neutral pair (0, 1) last, max |delta_a| and the attribute count up to which a slot's
+        constant is the running product (`gecco_crf_model_slot_table`)."""
+        pairs = np.zeros((self.num_attrs + 1, 2), dtype=np.float64)
+        dmax = ctypes.c_double(0.0)
+        cnt = ctypes.c_int32(0)
+        _check(self._lib.gecco_crf_model_slot_table(self._h, int(label), _ptr(pairs, _c_f64p),
+                                                    ctypes.cast(ctypes.byref(dmax), _c_f64p), ctypes.cast(ctypes.byref(cnt), _c_i32p)))
+        return pairs, dmax.value, cnt.value
 
     def trans_weights(self):
         L = self.num_labels

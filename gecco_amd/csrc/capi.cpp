@@ -188,6 +188,18 @@ GECCO_API int gecco_crf_model_state_weights(const gecco_crf_model *m, double *w,
     if (present) std::memcpy(present, m->m.state_mask.data(), m->m.state_mask.size());
     return GECCO_CRF_OK;
 }
+GECCO_API int gecco_crf_model_slot_table(const gecco_crf_model *m, int32_t label, double *pairs, double *dmax, int32_t *prod_max_cnt) {
+    if (!m || m->m.L != 2 || label < 0 || label > 1) return GECCO_CRF_EINVAL;
+    GECCO_GUARD_BEGIN
+    gecco::SlotTable st;
+    gecco::build_slot_table(m->m, label, st);
+    if (pairs) std::memcpy(pairs, st.pairs.data(), st.pairs.size() * sizeof(double));
+    if (dmax) *dmax = st.dmax;
+    if (prod_max_cnt) *prod_max_cnt = st.prod_max_cnt;
+    return GECCO_CRF_OK;
+    GECCO_GUARD_END
+}
+GECCO_API int32_t gecco_crf_slot_prod_max_cnt(double dmax) { return gecco::slot_prod_max_cnt(dmax); }
 GECCO_API int gecco_crf_model_trans_weights(const gecco_crf_model *m, double *w, uint8_t *present) {
     if (!m) return GECCO_CRF_EINVAL;
     if (w) std::memcpy(w, m->m.trans.data(), m->m.trans.size() * sizeof(double));

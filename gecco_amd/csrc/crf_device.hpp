@@ -21,7 +21,7 @@ struct WinArgs {
     const int4 *tile_desc;     // [ntiles]     (gene-slot shift, first contig, last contig, flags: 1 = regular)
     const uint64_t *start_bits;// [S/64+2]     bit q: a window may start at slot q; zero words in front (1) and behind (24)
     double *p_out;             // [n_genes]
-    double2 *state_out;        // [n_genes] or null: raw state scores (s[0], s[1]) as a by-product (fast L == 2 kernel)
+    double2 *state_out;        // [n_genes] or null: raw state scores (s[0], s[1]) as a by-product (fast L == 2 kernel, not its ratio form)
     double *dstate_out;        // [n_genes] or null: s[1] - s[0] as a by-product
     int32_t K, S, ntiles, W, step, L, label;
     int32_t n_genes, A;        // CSR extent and weight-table rows (buffer descriptors)
@@ -39,6 +39,8 @@ struct WinArgs {
     const double *exp_trans;   // [L*L] exp(trans) for the generic kernel
     double *scratch;           // generic kernel workspace
     const double *rtab;        // [32] mu01 * 2^(j/32): exp table of the ratio-form slot constants (mu_exp_tab)
+    const double2 *ptab;       // [A+1] (delta_a, exp(delta_a)), entry A = (0, 1): factor table of the product-form slot constants
+    int32_t prod_cnt;          // a slot with more attributes than this takes mu_exp_tab on its sum instead of its running product
     // What the host may know of the CSR arrays (batch driver's direct path: they are its own copies; a caller of the resident
     // API keeps them in device memory, where the kernel has to look: -1).  csr_end = gene_ptr[n_genes], csr_begin = gene_ptr[0]:
     // a batch of ONE regular tile (crf_windowed_small_l2) takes them from here instead of loading them in front of its first
@@ -157,7 +159,7 @@ struct SeqArgs {
         double d_enter;
     };
     VdCand *vCand;              // [lanes + 4 * workgroups]
-    unsigned long long *vBound; // [0]: bit pattern of the largest per-contig bound (vd_fold); [1] low word: number of candidates
+    unsigned long long *vBound; // [0]: bit pattern of the largest per-contig bound (vd_fold); [1] low word: number of candidates, high word: attribute entries of the largest contig
     uint32_t *vd_stats;         // [4] or null, accumulated over launches: coarse candidates, decisions inside the margin,
                                 // contigs decoded again with CRFsuite's recursion, their genes
     // CSR of the batch + weight pairs (w[a][0], w[a][1]): contigs with such a decision are decoded again with
@@ -358,6 +360,9 @@ hipError_t launch_windowed_reference(const WinArgs &w, const double2 *wtab01, co
 const char *windowed_kernel_name(int W, int L, bool fast);
 // tile_out = output slots per workgroup for the kernel that (W, L) dispatches to.
 int windowed_tile_out(int W, int L, int tiles_per_wg);
+// whether launch_windowed takes the ratio-form kernel for (W, rescale_mask) on the fast path: its slot constants come from the
+// factor table (WinArgs::ptab), and the raw state scores (WinArgs::state_out) are not its to deliver
+bool windowed_ratio_form(int W, uint32_t rescale_mask);
 hipError_t launch_windowed(const WinArgs &a, hipStream_t stream);
 hipError_t launch_fill_nan(double *p, const int2 *ranges, int n_ranges, hipStream_t stream);
 

@@ -100,7 +100,8 @@ struct WinSmem {
     // a contig occupies at least W slots (shorter ones are padded or not scored at all)
     static constexpr int CMAX = EXACT ? CAP / WMAX + 3 : CAP + 2;  // contigs a workgroup can overlap
     f64x2 ef[2 * CAP];              // first CAP entries, per slot: (e0, f = mu01*e1) with e = exp(s - max s), "other" first; or,
-                                    // in the ratio form, CAP doubles r = f / e0 = mu01 exp(s[label] - s[other]) in its first quarter.
+                                    // in the ratio form, CAP doubles r = f / e0 = mu01 exp(s[label] - s[other]) in its first quarter
+                                    // (built as mu01 times the product of the attributes' exp(delta_a): windowed_tile).
                                     // Before that, all 2 CAP entries park the weight pairs of the workgroup's attributes (stage 1).
     uint32_t ginfo[CAP];            // per slot: bit 31 = a window may start here; low bits = gene + 1 (0: none)
     f64x2 carry[NT / 64][WMAX];     // running best leaving lane 63 of each wave, per step
@@ -162,8 +163,13 @@ __device__ __forceinline__ void state_scores_l2(const int32_t *__restrict__ attr
 // costs 3 VALU ops per attribute slot (shift, compare, select) + 2 adds, no exec-mask branches.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
+// (`imax`, `none`: the largest table index an id is clamped to and the byte offset an unused slot gathers from -- past the
+// weight-pair table, or the neutral entry of the factor table.  PROD: the pairs are (delta_a, exp(delta_a)); s1 adds up the
+// first halves, s0 multiplies the second ones)
+template <bool PROD = false>
 __device__ __forceinline__ void state_scores_buf(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rw, uint32_t off,
-                                                 uint32_t cnt, double &s0, double &s1) {
+                                                 uint32_t cnt, double &s0, double &s1, uint32_t imax = 0x0FFFFFFFu,
+                                                 uint32_t none = 0xFFFFFFF0u) {
     for (uint32_t base = 0; base < cnt; base += kGatherUnroll) {  // one trip unless a gene has > 8 domains
         int a[kGatherUnroll];
 #pragma unroll
@@ -172,13 +178,18 @@ __device__ __forceinline__ void state_scores_buf(__amdgpu_buffer_rsrc_t ra, __am
         i32x4 w[kGatherUnroll];
 #pragma unroll
         for (int u = 0; u < kGatherUnroll; ++u) {
-            const uint32_t wo = base + u < cnt ? min(uint32_t(a[u]), 0x0FFFFFFFu) << 4 : 0xFFFFFFF0u;
+            const uint32_t wo = base + u < cnt ? min(uint32_t(a[u]), imax) << 4 : none;
             w[u] = __builtin_amdgcn_raw_buffer_load_b128(rw, int(wo), 0, 0);
         }
 #pragma unroll
         for (int u = 0; u < kGatherUnroll; ++u) {
-            s0 += __hiloint2double(w[u].y, w[u].x);
-            s1 += __hiloint2double(w[u].w, w[u].z);
+            if (PROD) {
+                s1 += __hiloint2double(w[u].y, w[u].x);
+                s0 *= __hiloint2double(w[u].w, w[u].z);
+            } else {
+                s0 += __hiloint2double(w[u].y, w[u].x);
+                s1 += __hiloint2double(w[u].w, w[u].z);
+            }
         }
     }
 }
@@ -200,6 +211,12 @@ __device__ __forceinline__ void state_scores_buf(__amdgpu_buffer_rsrc_t ra, __am
 // genes, BASELINE.json configs[0]): nothing is looked up in front of the first attribute load, and a phase without output
 // slots is skipped.  A kernel of its own (crf_windowed_small_l2): the extra scalars would cost the tiles of the big launches
 // a register spill, and occupancy means nothing to one workgroup.
+// RATIO (the W = 20 kernels): the slot constant of a regular tile is the running product
+// r = mu01 * prod exp(delta_a) over the slot's attributes, from the per-attribute factor table (`ptab`), instead of
+// mu01 exp(s[label] - s[other]): no exponential in front of the first barrier.  A slot with more than P.prod_cnt attributes
+// -- whose partial products could leave the range of a double where the sum would not -- takes the exponential of its sum
+// of delta_a.  Irregular tiles multiply in the same (CSR) order under the same rule, so a slot's constant does not depend on
+// how the batch was cut into chunks and tiles.  These kernels never see the raw state scores (no state_out).
 template <int WMAX, bool EXACT, bool RESCALE, int NT, int TT, bool LEAN = false, bool SMALL = false>
 __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT, TT, EXACT> &sm, const int tile) {
     using Smem = WinSmem<WMAX, NT, TT, EXACT>;
@@ -265,21 +282,30 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
     const uint64_t abytes = uint64_t(nnz - lo_tile) << 2;
     const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<int32_t *>(P.attr_id + lo_tile), 0, abytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32_t(abytes), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<double2 *>(P.wtab2), 0, uint32_t(P.A) << 4, 0x00020000);
+    // RATIO: the factor table (delta_a, exp(delta_a)) with its neutral entry (0, 1) at index A, which ids outside the
+    // dictionary are clamped to and unused gather slots read
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<double2 *>(RATIO ? P.ptab : P.wtab2), 0,
+                                                                        (uint32_t(P.A) + (RATIO ? 1u : 0u)) << 4, 0x00020000);
+    const uint32_t imax = RATIO ? uint32_t(P.A) : 0x0FFFFFFFu, none = RATIO ? uint32_t(P.A) << 4 : 0xFFFFFFF0u;
 
     // (no store in front of the wave-uniform loads above: it turns them into vector loads, and every buffer load then
     // grows a readfirstlane ("waterfall") loop for its descriptor)
     // ---- stage 1: state scores of the workgroup's slots -> slot constants in LDS.
-    double sc0[JMAX], sc1[JMAX];  // s[other], s[label] of the lane's slots
+    double sc0[JMAX], sc1[JMAX];  // s[other], s[label] of the lane's slots; RATIO: r (the running product) and the sum of delta_a
 #pragma unroll
-    for (int j = 0; j < JMAX; ++j) sc0[j] = sc1[j] = 0.0;
+    for (int j = 0; j < JMAX; ++j) {
+        sc0[j] = RATIO ? P.mu01 : 0.0;
+        sc1[j] = 0.0;
+    }
+    uint32_t long_run = 0;  // RATIO: bit j = slot j has more than P.prod_cnt attributes
     if (td.w & 1) {
         // Regular workgroup (the normal case): its slots are CONSECUTIVE GENES, so their attribute ids are one
         // contiguous stretch of the CSR.  The stretch is loaded attribute-per-lane -- consecutive lanes take
         // consecutive ids (coalesced), every id gathers its weight pair once -- parked in LDS (over the area the
         // slot constants will occupy afterwards), and each slot then adds up its own run from there, in CSR
-        // order (bit-exact with sequential addition).  The first version of this stage gave every SLOT eight
+        // order (bit-exact with sequential addition).  RATIO: the pairs are (delta_a, exp(delta_a)) from the factor table; a slot
+        // adds up the first halves (d, what the Viterbi decoder is handed) and multiplies the second ones onto mu01 (its
+        // constant r), two fp64 operations per pair either way.  The first version of this stage gave every SLOT eight
         // speculative id loads and eight weight gathers whatever its number of domains (1.4 on average): 36
         // vector memory instructions per lane, of which the 16-byte gathers alone kept the texture path of a CU
         // busy for ~9 us per launch; the stage took 19.6 us on its own (DP alone: 21.2 us, both: 28.3 us).
@@ -313,7 +339,8 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
             for (int a = 0; a < APL; ++a) {
                 // ids past the stretch belong to later genes (or read 0 past the array): their pairs are parked
                 // and never used; ids outside the dictionary land outside the table and read (+0.0, +0.0)
-                const uint32_t wo = min(uint32_t(id[a]), 0x0FFFFFFFu) << 4;
+                // (RATIO: ... are clamped to the table's neutral entry (0, 1))
+                const uint32_t wo = min(uint32_t(id[a]), imax) << 4;
                 w[a] = __builtin_amdgcn_raw_buffer_load_b128(rw, int(wo), 0, 0);
             }
 #pragma unroll
@@ -328,11 +355,20 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
                 const f64x2 *const e = park + (min(hi[j], c1) - c0);  // (k >= e when the run lies outside this round)
                 for (; k < e && hi[j] > c0; ++k) {
                     const f64x2 v = *k;
-                    sc0[j] += v.x;
-                    sc1[j] += v.y;
+                    if (RATIO) {  // (two fp64 operations per parked pair either way)
+                        sc1[j] += v.x;
+                        sc0[j] *= v.y;
+                    } else {
+                        sc0[j] += v.x;
+                        sc1[j] += v.y;
+                    }
                 }
             }
             if (base + SCAP < n_attr) __syncthreads();  // the parking area is reused by the next round
+        }
+        if (RATIO) {
+#pragma unroll
+            for (int j = 0; j < JMAX; ++j) long_run |= hi[j] - lo[j] > uint32_t(P.prod_cnt) ? 1u << j : 0u;
         }
         // kernels without the ratio form write 16-byte slot constants over the whole lower half right away
         if (!RATIO && n_attr > 0) __syncthreads();
@@ -362,23 +398,37 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
 #pragma unroll
         for (int j = 0; j < JMAX; ++j) {
             if (TT > 1 || j == 0 || wave == 0) {
-                double s0 = 0.0, s1 = 0.0;
+                double s0 = RATIO ? P.mu01 : 0.0, s1 = 0.0;
                 i32x4 w[kGatherUnroll];
 #pragma unroll
                 for (int u = 0; u < kGatherUnroll; ++u) {
-                    const uint32_t wo = uint32_t(u) < cnt[j] ? min(uint32_t(ids[j][u]), 0x0FFFFFFFu) << 4 : 0xFFFFFFF0u;
+                    const uint32_t wo = uint32_t(u) < cnt[j] ? min(uint32_t(ids[j][u]), imax) << 4 : none;
                     w[u] = __builtin_amdgcn_raw_buffer_load_b128(rw, int(wo), 0, 0);
                 }
 #pragma unroll
                 for (int u = 0; u < kGatherUnroll; ++u) {
-                    s0 += __hiloint2double(w[u].y, w[u].x);
-                    s1 += __hiloint2double(w[u].w, w[u].z);
+                    if (RATIO) {  // (an unused slot read the neutral pair: + 0.0, * 1.0)
+                        s1 += __hiloint2double(w[u].y, w[u].x);
+                        s0 *= __hiloint2double(w[u].w, w[u].z);
+                    } else {
+                        s0 += __hiloint2double(w[u].y, w[u].x);
+                        s1 += __hiloint2double(w[u].w, w[u].z);
+                    }
                 }
                 if (cnt[j] > uint32_t(kGatherUnroll))  // rare: a gene with more than 8 domains
-                    state_scores_buf(ra, rw, off[j] + kGatherUnroll, cnt[j] - kGatherUnroll, s0, s1);
+                    state_scores_buf<RATIO>(ra, rw, off[j] + kGatherUnroll, cnt[j] - kGatherUnroll, s0, s1, imax, none);
+                if (RATIO && cnt[j] > uint32_t(P.prod_cnt)) long_run |= 1u << j;  // (the regular tiles' rule)
                 sc0[j] = s0;
                 sc1[j] = s1;
             }
+        }
+    }
+    if (RATIO) {
+        // the rare long run: one vote of the wave, then the exponential under the execution mask of the lanes that need it
+        if (__builtin_amdgcn_ballot_w64(long_run != 0) != 0) {
+#pragma unroll
+            for (int j = 0; j < JMAX; ++j)
+                if ((long_run >> j) & 1u) sc0[j] = mu_exp_tab(sc1[j], P.rtab, P.expc);
         }
     }
     double *rr = reinterpret_cast<double *>(sm.ef);  // ratio form: r per slot, in the first half of the (e0, f) array
@@ -390,14 +440,15 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
             // decode = windowed marginals + Viterbi of the same batch: the raw scores of the genes this
             // workgroup owns are handed to the whole-contig kernels instead of being gathered again
             if (sl >= W - 1 && sl < TT * OUT + (W - 1) && gene[j] >= 0) {
-                if (P.state_out) reinterpret_cast<f64x2 *>(P.state_out)[gene[j]] = P.label ? f64x2{s0, s1} : f64x2{s1, s0};
+                if (!RATIO && P.state_out) reinterpret_cast<f64x2 *>(P.state_out)[gene[j]] = P.label ? f64x2{s0, s1} : f64x2{s1, s0};
             }
-            const double d = s1 - s0;
+            const double d = RATIO ? s1 : s1 - s0;
             if (sl < ns) {
                 if (RATIO) {
-                    // r = mu01 exp(d), with "a window may start here" in its sign bit (r > 0: the DP reads |r|).  A regular
+                    // r = mu01 exp(d) -- the running product, or mu_exp_tab(d) of a long run --, with "a window may start here" in
+                    // its sign bit (r > 0: the DP reads |r|).  A regular
                     // tile maps slots to genes by a constant shift, so only irregular ones park their genes.
-                    const double r = mu_exp_tab(d, P.rtab, P.expc);
+                    const double r = s0;
                     rr[sl] = __hiloint2double(__double2hiint(r) | (start[j] ? int(0x80000000u) : 0), __double2loint(r));
                     if (!(td.w & 1)) sm.ginfo[sl] = uint32_t(gene[j] + 1);
                 } else {
@@ -417,7 +468,7 @@ __device__ __forceinline__ void windowed_tile(const WinArgs &P, WinSmem<WMAX, NT
             if (TT > 1 || j == 0 || wave == 0) {
                 const int sl = tid + j * NT;
                 if (sl >= W - 1 && sl < TT * OUT + (W - 1) && gene[j] >= 0) {
-                    const double d = sc1[j] - sc0[j];
+                    const double d = RATIO ? sc1[j] : sc1[j] - sc0[j];
                     // (s[1] - s[0] = d or -d: one XOR on the sign word)
                     const double dd = __hiloint2double(__double2hiint(d) ^ (P.label ? 0 : int(0x80000000u)), __double2loint(d));
                     store_wt(P.dstate_out + gene[j], dd);
@@ -733,13 +784,13 @@ __global__ void __launch_bounds__(kWinThreads, 4) crf_windowed_small_l2(const Wi
 struct PipeArgs {
     // window tiles (batch k)
     const int32_t *gene_ptr, *attr_id;
-    const double2 *wtab2;
+    const double2 *ptab;
     const int32_t *c_slot, *c_gene, *c_n;
     const int4 *tile_desc;
     const uint64_t *start_bits;
     double *p_out, *dstate_out;
     const double *rtab;
-    int32_t S, ntiles, step, label, n_genes, A, all_regular, nvd8;
+    int32_t S, ntiles, step, label, n_genes, A, all_regular, nvd8, prod_cnt;
     double mu01, rho, kappa_over_mu01, inv_kappa, ratio_zmax, expc5[5];
     // Viterbi workgroups (batch k - 1)
     const double *dstate;
@@ -765,7 +816,8 @@ __global__ void __launch_bounds__(kWinThreads, WGS) crf_decode_pipelined(const P
         WinArgs P{};
         P.gene_ptr = K.gene_ptr;
         P.attr_id = K.attr_id;
-        P.wtab2 = K.wtab2;
+        P.ptab = K.ptab;
+        P.prod_cnt = K.prod_cnt;
         P.c_slot = K.c_slot;
         P.c_gene = K.c_gene;
         P.c_n = K.c_n;
@@ -912,6 +964,8 @@ const char *windowed_kernel_name(int W, int L, bool fast) {
     return "unsupported";
 }
 
+bool windowed_ratio_form(int W, uint32_t rescale_mask) { return W == 20 && rescale_mask == 0; }
+
 int windowed_tile_out(int W, int L, int tt) {
     if (L == 2 && W <= kWinMaxW) return tt * (kWinThreads - (W - 1));
     return kWinThreads;
@@ -939,6 +993,8 @@ hipError_t launch_windowed(const WinArgs &a, hipStream_t stream) {
         return hipGetLastError();
     }
     if (a.L != 2 || a.W > kWinMaxW) return hipErrorNotSupported;
+    // the W = 20 kernels build their slot constants from the factor table: they need it and cannot deliver raw state scores
+    if (windowed_ratio_form(a.W, a.rescale_mask) && (a.state_out || !a.ptab)) return hipErrorNotSupported;
     if (a.ntiles == 1 && a.all_regular && a.csr_end >= 0 && a.csr_begin >= 0 && a.W == 20 && a.rescale_mask == 0 && a.tiles_per_wg == 2) {
         hipLaunchKernelGGL(crf_windowed_small_l2, dim3(1), dim3(kWinThreads), 0, stream, a);
         return hipGetLastError();
@@ -952,7 +1008,7 @@ hipError_t launch_windowed(const WinArgs &a, hipStream_t stream) {
 }
 
 bool decode_pipelined_ok(const WinArgs &w, const SeqArgs &s) {
-    return w.ntiles > 0 && w.W == 20 && w.rescale_mask == 0 && (w.tiles_per_wg == 1 || w.tiles_per_wg == 2) && !w.generic && w.L == 2 && !w.state_out &&
+    return w.ntiles > 0 && w.W == 20 && w.rescale_mask == 0 && (w.tiles_per_wg == 1 || w.tiles_per_wg == 2) && !w.generic && w.L == 2 && !w.state_out && w.ptab &&
            s.short_contigs && s.n_cblocks > 0 && s.n_genes > 0;
 }
 
@@ -961,7 +1017,8 @@ hipError_t launch_decode_pipelined(const WinArgs &w, const SeqArgs &s, hipStream
     PipeArgs k{};
     k.gene_ptr = w.gene_ptr;
     k.attr_id = w.attr_id;
-    k.wtab2 = w.wtab2;
+    k.ptab = w.ptab;
+    k.prod_cnt = w.prod_cnt;
     k.c_slot = w.c_slot;
     k.c_gene = w.c_gene;
     k.c_n = w.c_n;

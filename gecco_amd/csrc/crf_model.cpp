@@ -14,6 +14,7 @@
 // trans[i][f.dst] = f.weight), so duplicated state features would accumulate as they do there.
 #include "crf_model.hpp"
 
+#include <cmath>
 #include <cstring>
 
 #include "../../include/gecco_crf.h"
@@ -196,6 +197,26 @@ int model_from_tables(const double *state, const double *trans, int32_t A, int32
         m.attr_index.emplace(m.attrs[i], i);
     }
     return GECCO_CRF_OK;
+}
+
+int32_t slot_prod_max_cnt(double dmax) {
+    if (!(dmax < 700.0)) return 0;  // (also a NaN weight: every slot takes the exp form)
+    if (dmax * 2147483647.0 <= 700.0) return INT32_MAX;
+    return int32_t(std::floor(700.0 / dmax));
+}
+
+void build_slot_table(const Model &m, int label, SlotTable &out) {
+    const size_t A = size_t(m.A);
+    out.pairs.assign(2 * (A + 1), 0.0);
+    out.dmax = 0.0;
+    for (size_t a = 0; a < A; ++a) {
+        const double d = m.state[a * 2 + size_t(label)] - m.state[a * 2 + size_t(1 - label)];
+        out.pairs[2 * a] = d;
+        out.pairs[2 * a + 1] = double(expl((long double)d));
+        out.dmax = std::fabs(d) > out.dmax || d != d ? std::fabs(d) : out.dmax;
+    }
+    out.pairs[2 * A + 1] = 1.0;
+    out.prod_max_cnt = slot_prod_max_cnt(out.dmax);
 }
 
 }  // namespace gecco

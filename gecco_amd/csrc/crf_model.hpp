@@ -38,4 +38,17 @@ struct Model {
 int parse_lcrf(const uint8_t *blob, size_t n, Model &out);
 int model_from_tables(const double *state, const double *trans, int32_t A, int32_t L, Model &out);
 
+// The per-attribute factor table of the window kernels' product-form slot constants (L == 2): A + 1 pairs
+// (delta_a, psi_a), delta_a = w[a][label] - w[a][other] (one rounding; exact for integer weights), psi_a = exp(delta_a)
+// rounded once from extended precision; entry A is the neutral pair (0, 1) that ids outside the dictionary are clamped to.
+// dmax = max |delta_a|; prod_max_cnt = floor(700 / dmax) (0 from dmax >= 700 on, INT32_MAX for dmax == 0): the number of
+// attributes up to which no partial product of a slot can leave the range of a double.
+struct SlotTable {
+    std::vector<double> pairs;  // 2 (A + 1)
+    double dmax = 0.0;
+    int32_t prod_max_cnt = 0;
+};
+int32_t slot_prod_max_cnt(double dmax);
+void build_slot_table(const Model &m, int label, SlotTable &out);
+
 }  // namespace gecco

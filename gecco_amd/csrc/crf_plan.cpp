@@ -45,6 +45,8 @@ Model::~Model() {
             (void)hipFree(t->trans);
             (void)hipFree(t->rtab[0]);
             (void)hipFree(t->rtab[1]);
+            (void)hipFree(t->ptab[0]);
+            (void)hipFree(t->ptab[1]);
             (void)hipSetDevice(prev);
         }
         delete t;  // without a usable device the allocations die with the context
@@ -59,6 +61,8 @@ static void free_device_tables(DeviceTables *t) {
     (void)hipFree(t->trans);
     (void)hipFree(t->rtab[0]);
     (void)hipFree(t->rtab[1]);
+    (void)hipFree(t->ptab[0]);
+    (void)hipFree(t->ptab[1]);
     delete t;
 }
 
@@ -97,6 +101,14 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
             for (int j = 0; j < 32; ++j) tab[j] = double(expl(lmu + (long double)j * 0.693147180559945309417232121458L / 32.0L));
             rc = upload(&t->rtab[label], tab, 32, "upload exp table");
         }
+        // the factor table of the product-form slot constants, in the same precision (build_slot_table)
+        for (int label = 0; label < 2 && !rc; ++label) {
+            SlotTable st;
+            build_slot_table(m, label, st);
+            t->slot_dmax = st.dmax;
+            t->slot_prod_max_cnt = st.prod_max_cnt;
+            rc = upload(&t->ptab[label], reinterpret_cast<const double2 *>(st.pairs.data()), A + 1, "upload slot factor table");
+        }
     }
     if (rc) {
         free_device_tables(t);
@@ -121,6 +133,10 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
             c.g11 = G(label, label);
             fill_exp_coefficients(c.expc);
             c.ratio_zmax = 1.0e250;
+            // the running product starts at mu01: every partial product lies within e^(+-(|ln mu01| + cnt dmax)), which has to
+            // stay within e^+-700 (the normal range of a double ends at e^-708 and e^709)
+            const double room = 700.0 - std::fabs(T(o, label) + T(label, o) - 2.0 * T(o, o));
+            c.prod_cnt = room > 0.0 ? std::min(t->slot_prod_max_cnt, slot_prod_max_cnt(t->slot_dmax * (700.0 / room))) : 0;
         }
         DeviceTables::SeqConsts &q = t->seq;
         q.mx = *std::max_element(m.trans.begin(), m.trans.end());
@@ -895,6 +911,7 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
     a.wtab2 = p.tables_model->wtab2[label];
     a.exp_trans = p.tables_model->exp_trans;
     a.rtab = p.tables_model->rtab[label];
+    a.ptab = p.tables_model->ptab[label];
     a.c_slot = p.d_c_slot;
     a.c_gene = p.d_c_gene;
     a.c_n = p.d_c_n;
@@ -927,6 +944,7 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
         a.g11 = c.g11;
         std::memcpy(a.expc, c.expc, sizeof(a.expc));
         a.ratio_zmax = c.ratio_zmax;
+        a.prod_cnt = c.prod_cnt;
     }
     a.csr_begin = int32_t(p.csr_begin);  // (row pointers are 32-bit)
     a.csr_end = int32_t(p.csr_end);
@@ -1374,7 +1392,9 @@ int plan_run_decode(Plan &p, const DeviceCsr &csr, int32_t label, double *d_p_ou
     bind_seq_io(p, a, csr, d_y, d_score);
     // the window tiles leave the state scores, or their differences, where the Viterbi side reads them
     const bool delta = viterbi_delta_ok(a);
-    const SeqLeft left = tiles_hand_over(delta, d_score);
+    SeqLeft left = tiles_hand_over(delta, d_score);
+    // (the ratio-form tiles add up factors and score differences, not the two scores: those come from run_viterbi_l2's own launch)
+    if (left == SeqLeft::state && p.fast_ok && !p.reference_now && windowed_ratio_form(p.W, p.rescale_mask)) left = SeqLeft::nothing;
     if ((rc = run_windowed_impl(p, csr, label, d_p_out, left == SeqLeft::state ? const_cast<double2 *>(a.state) : nullptr,
                                 left == SeqLeft::dstate ? const_cast<double *>(a.dstate) : nullptr, stream)))
         return rc;

@@ -36,11 +36,17 @@ struct DeviceTables {
     double *trans = nullptr;      // [L*L] raw weights (general-L Viterbi)
     double wmax_abs = 0.0, tmax_abs = 0.0;  // largest |state weight| / |transition weight| (bounds of the Viterbi exactness margin)
     double *rtab[2] = {nullptr, nullptr};  // L == 2: [32] mu01(label) * 2^(j/32), the exp table of the window kernel's slot constants
+    // L == 2: [A + 1] (delta_a, exp(delta_a)) for label = 0 / 1, the factor table of the product-form slot constants
+    // (build_slot_table); slot_dmax / slot_prod_max_cnt: its two model constants
+    double2 *ptab[2] = {nullptr, nullptr};
+    double slot_dmax = 0.0;
+    int32_t slot_prod_max_cnt = 0;
     // Host-side constants of the kernels' argument blocks that depend on the model alone (L == 2), computed ONCE here: a launch
     // used to recompute them (17 exp calls, 36 divisions, three getenv scans per pipelined decode call: ~1 us of a 5 us
     // launch-bound step, tools/host_issue_probe.py).
     struct WinConsts {
         double mu01, rho, kappa_over_mu01, inv_kappa, g00, g01, g10, g11, expc[12], ratio_zmax;
+        int32_t prod_cnt;  // attributes up to which a slot's constant is the running product (slot_prod_max_cnt; 0 when mu01 itself is extreme)
     } win[2];  // by queried label
     struct SeqConsts {
         double mx, m00, m01, m10, m11, v_lo, v_hi, v_k, expc[12];

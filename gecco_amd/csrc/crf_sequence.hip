@@ -596,16 +596,34 @@ __global__ void __launch_bounds__(kT) vd_fold(const SeqArgs A) {
     // the largest bound on CRFsuite's accumulated scores over the batch's contigs (crf_vd_short.hpp: vd_bound), for the
     // margins of vd_replay / vd_refine: a contig per lane, one atomic per wave
     if (A.fix_flag && A.csr_gene_ptr) {
+        // ... and the most attribute entries a contig holds, for the coarse margin's share of the attribute-wise summed score
+        // differences (vd_sum_slack): high word of vBound[1].  (Only the waves that own contigs issue the two atomics.)
         double mx = 0.0;
+        uint32_t nz = 0;
         for (int c = blockIdx.x * kT + threadIdx.x; c < A.n_contigs; c += gridDim.x * kT) {
             const int gs = A.contig_ptr[c], ge = A.contig_ptr[c + 1];
-            if (ge > gs) mx = fmax(mx, vd_bound(A, double(A.csr_gene_ptr[ge] - A.csr_gene_ptr[gs]), double(ge - gs)));
+            if (ge > gs) {
+                const int nnz = A.csr_gene_ptr[ge] - A.csr_gene_ptr[gs];
+                mx = fmax(mx, vd_bound(A, double(nnz), double(ge - gs)));
+                nz = max(nz, uint32_t(nnz));
+            }
         }
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-        if ((threadIdx.x & 63) == 0 && mx > 0.0)
+        for (int o = 32; o >= 1; o >>= 1) {
+            mx = fmax(mx, __shfl_xor(mx, o));
+            nz = max(nz, uint32_t(__shfl_xor(int(nz), o)));
+        }
+        if ((threadIdx.x & 63) == 0 && mx > 0.0) {
             atomicMax(A.vBound, static_cast<unsigned long long>(__double_as_longlong(mx)));  // (non-negative: bit patterns order like values)
+            if (nz > 0u) atomicMax(reinterpret_cast<uint32_t *>(A.vBound + 1) + 1, nz);
+        }
     }
+}
+
+// attribute entries of the genes since a reset, at most: those of the batch's largest contig (a contig's first gene is a reset;
+// vd_fold left the number in the high word of vBound[1])
+__device__ __forceinline__ double vd_coarse_nnz(const SeqArgs &A) {
+    return double(reinterpret_cast<const uint32_t *>(A.vBound + 1)[1]);
 }
 
 __global__ void __launch_bounds__(kT) vd_replay(const SeqArgs A) {
@@ -617,11 +635,12 @@ __global__ void __launch_bounds__(kT) vd_replay(const SeqArgs A) {
     double D = M.L;  // the map entering a lane is constant once a contig has started
     const double d_enter = D;
     uint32_t maps = 0, lane_map = MapOp::identity();
-    // Coarse margin (crf_vd_short.hpp): (4 R + 4) ulp(M) with M the batch's largest per-contig bound (vd_fold) and R = 1023,
+    // Coarse margin (crf_vd_short.hpp): (4 R + 4) ulp(M) + S(nnz) with M the batch's largest per-contig bound (vd_fold), R = 1023
+    // and nnz that of the batch's largest contig (vd_coarse_nnz),
     // which holds as long as every wave (512 genes) contains a reset -- a contig's first gene or a decision that saturates
     // for certain; a wave without one is reported like a candidate.  `sat8`: which of the lane's genes saturate for certain.
     const bool exact = A.v_exact && A.fix_flag && A.csr_gene_ptr;
-    const double margin = exact ? vd_margin(1023.0, __longlong_as_double(static_cast<long long>(A.vBound[0])) * kVdEps)
+    const double margin = exact ? vd_margin(1023.0, __longlong_as_double(static_cast<long long>(A.vBound[0])) * kVdEps) + vd_sum_slack(A, vd_coarse_nnz(A))
                                 : 1e-6 * fmax(1.0, fmax(fabs(A.v_lo), fabs(A.v_hi)));
     bool sensitive = false;  // some decision of this lane lies within the coarse margin of its threshold
     uint32_t sat8 = 0;
@@ -671,7 +690,7 @@ __device__ __forceinline__ void vd_flag_contigs(const SeqArgs &A, int g_lo, int 
 __device__ __forceinline__ void vd_refine_block(const SeqArgs &A, const int blk, const int n_blocks) {
     const uint32_t count = *reinterpret_cast<const uint32_t *>(A.vBound + 1);
     const double ulpM = __longlong_as_double(static_cast<long long>(A.vBound[0])) * kVdEps;
-    const double margin = vd_margin(1023.0, ulpM);
+    const double margin = vd_margin(1023.0, ulpM) + vd_sum_slack(A, vd_coarse_nnz(A));
     for (uint32_t i = blk * kT + threadIdx.x; i < count; i += n_blocks * kT) {
         const SeqArgs::VdCand rec = A.vCand[i];
         const int lane = int(rec.lane & 0x7fffffffu), g0 = lane * kGPL;
@@ -703,7 +722,9 @@ __device__ __forceinline__ void vd_refine_block(const SeqArgs &A, const int blk,
             D = fst ? dk : fmin(fmax(D, A.v_lo), A.v_hi) + (A.v_k + dk);
             const bool lst = (last >> k) & 1u;
             const double thi = lst ? 0.0 : A.v_hi, tlo = lst ? 0.0 : A.v_lo;
-            const double mr = vd_margin(double(r), ulpM);
+            // (the attribute entries of the r + 1 genes whose score differences entered D)
+            const int gt = g0 + k;
+            const double mr = vd_margin(double(r), ulpM) + vd_sum_slack(A, double(A.csr_gene_ptr[gt + 1] - A.csr_gene_ptr[max(gt - r, 0)]));
             flagged |= fabs(D - thi) <= mr || fabs(D - tlo) <= mr;
         }
         if (A.vd_stats) atomicAdd(A.vd_stats + 0, 1u);

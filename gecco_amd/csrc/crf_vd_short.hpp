@@ -86,9 +86,18 @@ struct COp {
 // form saturates -- or up to the contig's first gene, where delta = state exactly: from there on both computed scores are
 // x + (exact terms) + (at most r ulp(M) of rounding each), r = genes since u, with the SAME x.  So its decision at gene t
 // equals the real-arithmetic one -- which the difference form evaluates with an error far below ulp(M) per step -- whenever
-//   |Delta_t - threshold| > (4 r_t + 4) ulp(M)                                                      (vd_margin)
+//   |Delta_t - threshold| > (4 r_t + 4) ulp(M) + S(nnz_t)                                    (vd_margin + vd_sum_slack)
 // (2 r + 1 for CRFsuite's two scores and its two additions, as much again for the difference form's own roundings and
-// the rounded thresholds).  r_t <= n, so a first test against the coarse margin (4 n + 4) ulp(M) -- which also defines
+// the rounded thresholds).  S covers the score differences themselves: the window tiles hand over
+// d = sum over the gene's attributes of delta_a = fl(w[a][1] - w[a][0]), added in CSR order, where CRFsuite forms
+// fl(s[1] - s[0]) from its two CSR-order sums.  For a gene with k attributes each of the three sums rounds k partial sums of
+// magnitude <= k v_wmax2, the k differences round once each and the subtraction once: the two numbers differ by at most
+// (k^2 + 3 k) v_wmax2 2^-53.  Only the d of the genes since the reset enter Delta_t: with nnz_t attribute entries among
+// those r_t + 1 genes, sum (k^2 + 3 k) <= nnz_t^2 + 3 nnz_t, so
+//   S(nnz) = (nnz^2 + 3 nnz + 1) v_wmax2 2^-53                                                       (vd_sum_slack)
+// -- a few genes' worth for a decision close behind its reset, whatever the length of its contig.  With integer-valued
+// weights every delta_a and every sum is exact and S is slack only.
+// r_t <= n, so a first test against the coarse margin -- r = n and the nnz of the whole workgroup --, which also defines
 // "saturates for certain" -- finds the candidates (about one gene in 10^8 on metagenome-sized contigs); a candidate's
 // lane then finds its r_t by walking back to the last certain saturation and tests again.  Only a decision inside THAT
 // margin -- exact ties of integer-valued models; otherwise practically never -- sends its contig to CRFsuite's own
@@ -97,6 +106,11 @@ struct COp {
 __device__ __forceinline__ double vd_bound(const SeqArgs &A, double nnz, double n) { return nnz * A.v_wmax2 + (n + 2.0) * A.v_tmax; }
 constexpr double kVdEps = 2.220446049250313e-16;  // 2^-52: ulp(M) <= M * 2^-52
 __device__ __forceinline__ double vd_margin(double r, double ulpM) { return (4.0 * r + 4.0) * ulpM; }
+// what the attribute-wise summed score differences of genes holding `nnz` attribute entries may be off by, all together
+// (the last factor: the bound's own second-order terms and roundings)
+__device__ __forceinline__ double vd_sum_slack(const SeqArgs &A, double nnz) {
+    return (nnz * nnz + 3.0 * nnz + 1.0) * A.v_wmax2 * (0.5 * kVdEps) * 1.000001;
+}
 
 // ---- CRFsuite's own recursion for the contigs that need it ------------------------------------------------
 // A contig with a decision INSIDE the margin is decoded again here, the way CRFsuite does it: state scores summed attribute by
@@ -440,12 +454,13 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
     // to its contig's first gene) and re-runs the recursion sequentially from there -- a few genes on
     // average -- and the decisions below are those of the strictly sequential difference recursion, bit for
     // bit, independent of lane and workgroup boundaries (oracle_viterbi_delta is that recursion).
-    // coarse margin of the workgroup: (4 n + 4) ulp(M) with n, nnz of all its (whole) contigs together; without the CSR
+    // coarse margin of the workgroup: (4 n + 4) ulp(M) + S(nnz) with n, nnz of all its (whole) contigs together; without the CSR
     // arrays (no exact pass possible) the flat 1e-6 of rounds 2 and 3
     double ulpM = 0.0, margin = 1e-6 * fmax(1.0, fmax(fabs(A.v_lo), fabs(A.v_hi)));
     if (A.csr_gene_ptr) {
-        ulpM = vd_bound(A, double(A.csr_gene_ptr[g0 + n] - A.csr_gene_ptr[g0]), double(n)) * kVdEps;
-        margin = vd_margin(double(n), ulpM);
+        const double nnz = double(A.csr_gene_ptr[g0 + n] - A.csr_gene_ptr[g0]);
+        ulpM = vd_bound(A, nnz, double(n)) * kVdEps;
+        margin = vd_margin(double(n), ulpM) + vd_sum_slack(A, nnz);
     }
     // (the same number in every lane: kept in scalar registers, not in four of the 64 vector registers)
     ulpM = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(ulpM)), __builtin_amdgcn_readfirstlane(__double2loint(ulpM)));
@@ -564,7 +579,10 @@ __device__ __forceinline__ void vd_short_block(const SeqArgs &A, const int blk, 
                 const bool lst = (last >> k) & 1u;
                 const double thi = lst ? 0.0 : A.v_hi, tlo = lst ? 0.0 : A.v_lo;
                 maps |= ((D > thi ? 1u : 0u) | (D > tlo ? 2u : 0u)) << (2 * (kGPL - 1 - k));
-                const double mr = vd_margin(double(r), ulpM);
+                // (the attribute entries of the r + 1 genes whose score differences entered D; gene g0 starts a contig)
+                const int gt = g0 + slot * kGPL + k;
+                const double mr = vd_margin(double(r), ulpM) +
+                                  (A.csr_gene_ptr ? vd_sum_slack(A, double(A.csr_gene_ptr[gt + 1] - A.csr_gene_ptr[max(gt - r, g0)])) : 0.0);
                 lane_flagged |= fabs(D - thi) <= mr || fabs(D - tlo) <= mr;
             }
         }

@@ -74,6 +74,12 @@ int gecco_crf_model_map_attrs(const gecco_crf_model *m, const char *const *names
  * ([EXT] CRF.state_features_ / transition_features_ list only those). */
 int gecco_crf_model_state_weights(const gecco_crf_model *m, double *w /* A*L */, uint8_t *present /* A*L */);
 int gecco_crf_model_trans_weights(const gecco_crf_model *m, double *w /* L*L */, uint8_t *present /* L*L */);
+/* Two-label models: the per-attribute factor table behind the window kernels' slot constants, as the devices get it (host
+ * only, no device needed).  pairs: A + 1 entries (delta_a, exp(delta_a)), delta_a = w[a][label] - w[a][1 - label]; the last
+ * entry is the neutral pair (0, 1) of attribute ids outside the dictionary.  dmax = max |delta_a|; prod_max_cnt = floor(700 /
+ * dmax) (0 from dmax >= 700 on, INT32_MAX for dmax == 0).  Any output may be null.  gecco_crf_slot_prod_max_cnt: the rule alone. */
+int gecco_crf_model_slot_table(const gecco_crf_model *m, int32_t label, double *pairs /* 2*(A+1) */, double *dmax, int32_t *prod_max_cnt);
+int32_t gecco_crf_slot_prod_max_cnt(double dmax);
 
 /* ---- devices ---------------------------------------------------------------------- */
 int gecco_crf_device_count(int32_t *n);

@@ -2,7 +2,9 @@
 # Run on the GPU box (via gpurun): kernel trace + separate PMC passes of bench.py.
 # usage: tools/profile.sh <tag> [extra bench args]
 # Outputs under gpurun_out/<tag>/ ; summary in gpurun_out/<tag>/summary.txt
-set -u
+# every GPU step runs under its own time limit; a step that fails or runs out of time ends the script (nothing more is started
+# on a device that has just faulted or hung)
+set -eu
 TAG=${1:-prof}; shift || true
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$TAG
@@ -32,7 +34,7 @@ timeout 180 rocprofv3 --pmc FETCH_SIZE -d $O/pipe/pmc2 -o pmc2 -- $B $S2 > $O/pi
 timeout 180 rocprofv3 --pmc WRITE_SIZE -d $O/pipe/pmc3 -o pmc3 -- $B $S2 > $O/pipe_pmc3.log 2>&1
 timeout 180 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_SALU SQ_INSTS_VMEM SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM -d $O/pipe/pmc4 -o pmc4 -- $B $S2 > $O/pipe_pmc4.log 2>&1
 python tools/prof_summary.py $O crf_ > $O/summary.txt 2>&1
-mkdir -p $O/win; for k in 1 2 3 4 5 6; do mv $O/pmc$k $O/win/ 2>/dev/null; done
+mkdir -p $O/win; for k in 1 2 3 4 5 6; do mv $O/pmc$k $O/win/ 2>/dev/null || true; done
 python tools/pmc_to_json.py $O/win C3 $TAG crf_windowed_l2 > $O/pmc.json 2>&1
 python tools/pmc_to_json.py $O/pipe C3:pipelined $TAG crf_decode_pipelined >> $O/pmc.json 2>&1
 # the committed begin-to-end durations bench.py quotes as roofline.kernel_us_rocprof (one decode stream: a launch alone on the chip)
