@@ -83,6 +83,11 @@ SIGNATURES = {
         ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_f64p, _c_f64p]),
     "gecco_crf_viterbi_constrained": (
         ctypes.c_int, [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i8p, _c_f64p]),
+    "gecco_crf_span_probabilities": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_i32p, _c_u32p,
+         ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_segment": (
         ctypes.c_int,
         [ctypes.c_int32, _c_f64p, _c_u8p, _c_i32p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
@@ -607,6 +612,49 @@ class Model:
         sc = np.zeros(max(nc, 1), dtype=np.float64) if want_score else None
         run(_ptr(y, _c_i8p), _ptr(sc, _c_f64p) if want_score else None)
         return y[:n], (sc[:nc] if want_score else None)
+
+    def span_log_probabilities(self, contig_ptr, gene_ptr, attr_id, span_contig, span_begin, span_end, span_mask, device=0,
+                               values=None, allowed=None, want_marginals=False):
+        """Region posteriors: ``logp[q] = log P(y_t in set q for span_begin[q] <= t < span_end[q] | x)`` on the whole-contig
+        lattice (``gecco_crf_span_probabilities``), for any number of spans behind one forward-backward pass of the batch.
+        ``span_begin`` / ``span_end`` are offsets from the first gene of contig ``span_contig[q]``, the end exclusive;
+        ``span_mask[q]`` has bit y set when label y is in the set.  ``values`` and ``allowed`` as in ``marginals_full``: with
+        ``allowed`` the lattice is the restricted one.  Returns ``logp`` (float64, <= 0, ``-inf`` for probability zero), or
+        with ``want_marginals`` ``(logp, marginals [n, L], log Z [n_contigs])``, the latter two as ``marginals_full`` gives
+        them."""
+        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
+        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
+        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+            if values.size != attr_id.size:
+                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
+            values = values if values.size else np.zeros(1, dtype=np.float64)
+        if attr_id.size == 0:
+            attr_id = np.zeros(1, dtype=np.int32)
+        if allowed is not None:
+            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
+            if allowed.size != n:
+                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
+            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+        sc, sb, se = _i32(span_contig).ravel(), _i32(span_begin).ravel(), _i32(span_end).ravel()
+        sm = np.ascontiguousarray(span_mask, dtype=np.uint32).ravel()
+        ns = sc.size
+        if not (sb.size == ns and se.size == ns and sm.size == ns):
+            raise ValueError("span_contig, span_begin, span_end and span_mask differ in length")
+        pad_i, pad_u = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.uint32)
+        logp = np.zeros(max(ns, 1), dtype=np.float64)
+        marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_marginals else None
+        _check(self._lib.gecco_crf_span_probabilities(
+            self._h, int(device), _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
+            None if values is None else _ptr(values, _c_f64p), None if allowed is None else _ptr(allowed, _c_u32p),
+            _ptr(sc if ns else pad_i, _c_i32p), _ptr(sb if ns else pad_i, _c_i32p), _ptr(se if ns else pad_i, _c_i32p),
+            _ptr(sm if ns else pad_u, _c_u32p), ns, _ptr(logp, _c_f64p),
+            None if marg is None else _ptr(marg, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
+        if want_marginals:
+            return logp[:ns], marg[:n - n0], ln[:nc]
+        return logp[:ns]
 
 
 def domain_composition(seg, dom_ptr, dom_col, dom_weight, n_cols, normalize=True, device=0) -> np.ndarray:

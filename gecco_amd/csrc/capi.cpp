@@ -953,6 +953,81 @@ GECCO_API int gecco_crf_viterbi_constrained(const gecco_crf_model *m, int32_t de
                        score);
 }
 
+// ---- region posteriors (ABI 2.16.0): log P(every gene of a span carries a label of a set | x) on the whole-contig lattice, any
+// number of spans behind one forward-backward pass of the batch (crf_spans.hip)
+GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                           const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                           const uint32_t *allowed, const int32_t *span_contig, const int32_t *span_begin,
+                                           const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans, double *logp,
+                                           double *marg, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    const bool valued = attr_value != nullptr, masked = allowed != nullptr;
+    const int32_t L = m->m.L;
+    // the checks of the spans, on the host and before any device work
+    if (n_spans < 0) return fail("span_probabilities: negative number of spans");
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    if (n_spans > 0 && (!span_contig || !span_begin || !span_end || !span_mask || !logp)) return fail("null buffer");
+    std::vector<SpanQuery> spans(static_cast<size_t>(n_spans));
+    const uint32_t beyond = L >= 32 ? 0u : ~0u << L;  // the bits at or above L
+    for (int32_t q = 0; q < n_spans; ++q) {
+        const std::string who = "span " + std::to_string(q);
+        const int32_t c = span_contig[q], b = span_begin[q], e = span_end[q];
+        if (c < 0 || c >= n_contigs)
+            return fail(who + ": contig " + std::to_string(c) + " out of range (the batch has " + std::to_string(n_contigs) + ")");
+        const int64_t len = int64_t(contig_ptr[c + 1]) - contig_ptr[c];
+        if (b < 0 || b >= e || e > len)
+            return fail(who + ": [" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
+                        std::to_string(c) + " of " + std::to_string(len) + " genes");
+        if (span_mask[q] == 0) return fail(who + ": the label set is empty (a mask of 0)");
+        if (span_mask[q] & beyond)
+            return fail(who + ": the set holds a label at or above num_labels = " + std::to_string(L) + " (mask " +
+                        std::to_string(span_mask[q]) + ")");
+        spans[size_t(q)] = SpanQuery{c, b, e, span_mask[q]};
+    }
+    // without spans the call is the whole-contig marginals' own
+    if (n_spans == 0) {
+        if (masked) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
+        if (valued) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
+        return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+    }
+    // marg and lognorm are the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one
+    // exception: a 2-label model without values and masks has kernels of its own there, which this call then asks in a second pass
+    const bool own_l2 = L == 2 && !valued && !masked && (marg || lognorm);
+    int rc;
+    {
+        ResidentBatch b;
+        b.plan.spans = true;
+        const size_t per_gene[2] = {size_t(L) * 8, 0};
+        rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false, per_gene,
+                        8, b);
+        if (rc) return rc;  // (b.n == 0 cannot be: a checked span lies inside a contig with genes)
+        DevBuf<char> q;
+        const size_t b_spans = align256(size_t(n_spans) * sizeof(SpanQuery));
+        if ((rc = q.alloc(b_spans + size_t(n_spans) * 8, "hipMalloc spans"))) return rc;
+        if ((rc = check_hip(hipMemcpy(q.p, spans.data(), size_t(n_spans) * sizeof(SpanQuery), hipMemcpyHostToDevice), "upload spans")))
+            return rc;
+        double *d_logp = reinterpret_cast<double *>(q.p + b_spans);
+        rc = batch_wait(plan_run_span_probabilities(b.plan, b.csr, reinterpret_cast<const SpanQuery *>(q.p), n_spans, d_logp,
+                                                    b.out<double>(0), b.out<double>(2), nullptr), "span probabilities");
+        rc = batch_fetch(rc, logp, d_logp, size_t(n_spans) * 8, "download logp");
+        if (!own_l2) {
+            rc = batch_fetch(rc, marg, b.out<double>(0), size_t(b.n) * size_t(L) * 8, "download marginals");
+            rc = batch_fetch(rc, lognorm, b.out<double>(2), size_t(n_contigs) * 8, "download lognorm");
+        }
+        if (rc || !own_l2) return rc;
+    }
+    // (that entry takes batches that start at gene 0: a slice is rebased for it, rows and attribute entries alike)
+    if (contig_ptr[0] == 0) return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+    const int32_t g0 = contig_ptr[0], a0 = gene_ptr[g0];
+    std::vector<int32_t> contigs(size_t(n_contigs) + 1), rows(size_t(contig_ptr[n_contigs] - g0) + 1);
+    for (size_t c = 0; c < contigs.size(); ++c) contigs[c] = contig_ptr[c] - g0;
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = gene_ptr[size_t(g0) + i] - a0;
+    return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
+    GECCO_GUARD_END
+}
+
 namespace {
 // grow-only scratch of the stand-alone segmenter / composition calls, one set per host thread
 struct Scratch {

@@ -317,6 +317,17 @@ hipError_t launch_gen_viterbi_wave(const GenArgs &a, hipStream_t stream);
 hipError_t launch_gen_marginals_wave(const GenArgs &a, hipStream_t stream);  // row F likewise (a.E, a.smax, a.alpha, a.scale)
 int gen_chunk_genes();
 
+// ---- region posteriors (crf_spans.hip) ----
+// One query: genes [begin, end) of contig `contig`, offsets from the contig's first gene, and the label set `mask` (bit y set
+// when label y is inside).  The host has checked the ranges and that mask has a bit, and none at or above L.
+struct SpanQuery {
+    int32_t contig, begin, end;
+    uint32_t mask;
+};
+// logp[q] = log P(y_t in mask for begin <= t < end | x) on the lattice of the whole-contig marginals that ran before it on the
+// same stream with a.state non-null: reads a.state, a.E, a.alpha and a.marg, whatever arrangement filled them
+hipError_t launch_gen_spans(const GenArgs &a, const SpanQuery *spans, int32_t n_spans, double *logp, hipStream_t stream);
+
 // ---- any number of labels: windowed marginals, one label or every label (crf_general_windowed.hip) ----
 // label >= 0: p_out[g] = max over the windows covering g of P_w(y_g = label), clipped at 1 by the tile kernels.
 // label < 0: every label in one pass, p_out[g][l] likewise for all l, and p_any[g] = max over the same windows of the sum of

@@ -384,7 +384,8 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     }
     {
         const char *env = std::getenv("GECCO_CRF_FORCE_GENERAL");
-        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked;  // (valued and masked state scores exist in gl_state alone)
+        // (valued and masked state scores exist in gl_state alone; region posteriors read the any-L workspace)
+        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.spans;
     }
     p.fast_ok = (!p.general && W <= kWinMaxW && rescale_mask_for(m, W, &p.rescale_mask));
     {
@@ -753,9 +754,10 @@ const GenRecursion kGenViterbi = {
 };
 
 // The whole-contig recursion `r` of an any-L plan: state scores, then the chunked kernels, a wave per contig, or both side by
-// side (choose_wave_split).  Outputs the recursion does not write are null.
+// side (choose_wave_split).  Outputs the recursion does not write are null.  `used`: the argument block of the launches, for a
+// kernel that reads the workspace behind them.
 int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *d_marg, double *d_lognorm,
-                  int8_t *d_y, double *d_score, hipStream_t stream) {
+                  int8_t *d_y, double *d_score, hipStream_t stream, GenArgs *used = nullptr) {
     const int L = p.model->L;
     int32_t wave_tmax = -1;  // -1: no wave kernel; 0: every contig; > 0: contigs up to this length
     if (L > 8 && p.n_contigs > 0)
@@ -770,6 +772,7 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *
     g.score = d_score;
     r.clear(g);
     g.wave_tmax = tail_chunked ? wave_tmax : 0;
+    if (used) *used = g;
     if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch"))) return rc;
     if (!wave) return check_hip(r.chunked(g, stream), r.what);
     if (!tail_chunked || g.n_chunks <= 0) return check_hip(r.wave(g, stream), r.what);
@@ -1366,6 +1369,31 @@ int plan_run_marginals_full(Plan &p, const DeviceCsr &csr, double *d_marg,
         return rc;
     return check_hip(launch_seq_marginals_short(a, csr.gene_ptr, csr.attr_id, p.tables_model->wtab2[1], p.model->A, p.d_contig_ptr,
                                                 stream), "marginals launch");
+}
+
+int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *d_spans, int32_t n_spans, double *d_logp,
+                                double *d_marg, double *d_lognorm, hipStream_t stream) {
+    SeqArgs a;
+    int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc) return rc;
+    if (!p.spans || !p.general) {
+        set_error("the plan was not built for region posteriors");
+        return GECCO_CRF_EINVAL;
+    }
+    if (n_spans < 0) {
+        set_error("negative number of spans");
+        return GECCO_CRF_EINVAL;
+    }
+    if (ends_here(p.n_contigs == 0, (p.n_genes > 0 && (!csr.gene_ptr || !d_marg)) || (n_spans > 0 && (!d_spans || !d_logp)), rc))
+        return rc;
+    // the marginals recursion as plan_run_marginals_full runs it, with one difference: gl_state also writes the raw state
+    // scores, which the span kernel shifts by its own maxima (the marginals' launches and bits are the same)
+    GenRecursion with_state = kGenMarginals;
+    with_state.clear = [](GenArgs &) {};
+    GenArgs g;
+    if ((rc = run_gen_whole(p, with_state, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
+    // (a batch's chunked tail has been joined to `stream` by then)
+    return check_hip(launch_gen_spans(g, d_spans, n_spans, d_logp, stream), "span launch");
 }
 
 int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,

@@ -163,6 +163,10 @@ struct Plan {
     // as `valued` does: the any-L kernels at every label count, no reference-bits mode, and the masks come with every run call
     // (DeviceCsr::allowed), which is refused when it brings masks to a layout without `masked`, or none to one with it.
     bool masked = false;
+    // Region posteriors (plan_run_span_probabilities).  `spans` is set by the owner before plan_build: the layout
+    // takes the any-L kernels at every label count, as `valued` and `masked` do -- the span kernel reads the forward vectors of
+    // their workspace, which a 2-label plan does not have otherwise.  Nothing else changes: reference-bits mode is decided as ever.
+    bool spans = false;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_general_windowed.hip): the tile table of the lane-per-window tier when the plan's own
@@ -205,6 +209,11 @@ int plan_run_marginals_full(Plan &p, const DeviceCsr &csr, double *d_marg,
                             double *d_lognorm, hipStream_t stream);
 int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,
                      hipStream_t stream);
+// Region posteriors of a plan laid out with `spans`: the whole-contig marginals of the batch (d_marg [n_genes][L], which the span
+// kernel reads back, and d_lognorm [n_contigs] or null, both as plan_run_marginals_full writes them), then d_logp[q] = log P(every
+// gene of span q carries a label of its set | x) for the n_spans checked queries of d_spans (crf_spans.hip), all on `stream`
+int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *d_spans, int32_t n_spans, double *d_logp,
+                                double *d_marg, double *d_lognorm, hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);
 // returns GECCO_CRF_* ; on HIP failure sets the error text

@@ -5,6 +5,7 @@ points (``_native.Model``).  Training instances are the sliding windows of every
 with ``window_size=None`` the whole sequences, as CRFsuite trains outside GECCO: the objective ``predict`` and
 ``predict_marginals`` decode with.
 """
+import operator
 from collections.abc import Mapping
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -269,6 +270,60 @@ class SequenceCRF:
         _, free = self._model.marginals_full(ptr, item_ptr, attr, device=self.device, values=values, allowed=every)
         out[full] = inside - free
         return out
+
+    def _span_queries(self, spans, seq_ptr: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``spans`` as the native call's four arrays; every refusal is raised here, before any device call."""
+        index = {c: k for k, c in enumerate(self.classes_)}
+        n_seqs = len(seq_ptr) - 1
+        contig, begin, end, mask = [], [], [], []
+        for q, span in enumerate(spans):
+            try:
+                k, start, stop, labels = span
+                k, start, stop = operator.index(k), operator.index(start), operator.index(stop)
+            except (TypeError, ValueError):
+                raise ValueError(f"span {q}: expected (sequence_index, start, stop, labels), got {span!r}") from None
+            if not 0 <= k < n_seqs:
+                raise ValueError(f"span {q}: sequence index {k} out of range (X holds {n_seqs} sequences)")
+            length = int(seq_ptr[k + 1] - seq_ptr[k])
+            if start < 0 or start >= stop:
+                raise ValueError(f"span {q}: [{start}, {stop}) is not a non-empty range of items (start >= stop, or start < 0)")
+            if stop > length:
+                raise ValueError(f"span {q}: stop {stop} lies beyond sequence {k} of {length} items")
+            names = [str(m) for m in labels] if isinstance(labels, (set, frozenset, list, tuple)) else [str(labels)]
+            if not names:
+                raise ValueError(f"span {q}: an empty set holds no label")
+            bits = 0
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"span {q}: unknown label {name!r} (classes_: {self.classes_})")
+                bits |= 1 << index[name]
+            contig.append(k)
+            begin.append(start)
+            end.append(stop)
+            mask.append(bits)
+        return (np.array(contig, dtype=np.int32), np.array(begin, dtype=np.int32), np.array(end, dtype=np.int32),
+                np.array(mask, dtype=np.uint32))
+
+    def span_log_probability(self, X, spans, allowed=None) -> np.ndarray:
+        """Region posteriors: for every ``(sequence_index, start, stop, labels)`` of ``spans`` the log-probability, given the
+        whole sequence, that EVERY item of ``X[sequence_index][start:stop]`` carries a label of ``labels`` -- a label, or a
+        ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels.  One float64 per span, ``<= 0``; ``-inf`` where the
+        probability is zero.  This is a property of the path distribution on the whole-sequence lattice (that of ``predict``
+        and ``predict_marginals``, not a windowed one), not a function of the per-item marginals; with ``allowed`` (as in
+        ``predict_marginals``) the lattice is the restricted one.  All spans take one forward-backward pass over ``X`` and one
+        native call.  Raises ``ValueError`` before any device call for an unknown label, an empty set, a sequence index out
+        of range, ``start >= stop`` or ``start < 0``, and ``stop`` beyond the sequence."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        contig, begin, end, mask = self._span_queries(spans, seq_ptr)
+        if len(contig) == 0:
+            return np.zeros(0)
+        return self._model.span_log_probabilities(seq_ptr, item_ptr, attr, contig, begin, end, mask, device=self.device,
+                                                  values=values, allowed=masks)
+
+    def span_probability(self, X, spans, allowed=None) -> np.ndarray:
+        """``exp`` of ``span_log_probability``."""
+        return np.exp(self.span_log_probability(X, spans, allowed=allowed))
 
     def _windowed(self) -> None:
         self._fitted()

@@ -24,6 +24,16 @@ label's windowed probability; the cluster's probability of t is ``min(1, exact m
 the set of t with a probability above 0.5 (the rule of ``TypeClassifier.predict_types``), ``Unknown`` when empty.
 ``"Mixed"`` and ``"Unknown"`` contain no type.
 
+Region posteriors (opt-in: ``region_posteriors=True``, ``predict --region-posteriors``).  The numbers above are per-gene
+numbers.  With the flag every called cluster also carries ``region_probability``, the posterior probability that EVERY gene
+of the called region carries a cluster label (anything but the background), and ``region_type_probabilities[t]``, the
+posterior probability that every gene's label contains type t -- probabilities of the whole region under the model, which
+are not functions of the per-gene numbers.  They are WHOLE-CONTIG posteriors, on the lattice of ``SequenceCRF.predict`` and
+``predict_marginals`` (``_native.Model.span_log_probabilities``: one forward-backward pass per batch, all regions in one
+native call), not windowed ones: the model's parameters are those fitted on windows, the conditioning is on the whole
+contig.  ``known=`` restricts that lattice as it restricts the windows.  ``clusters.tsv`` then has the columns ``region_p``
+and ``{type}_region_p``; without the flag the tables are unchanged.
+
 Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
 ``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
 """
@@ -178,13 +188,23 @@ def type_of(probabilities: Dict[str, float]) -> frozenset:
 
 def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables.ClusterTable:
     """``ClusterTable.from_clusters`` with one ``{type.lower()}_probability`` column per type between ``type`` and
-    ``proteins``, in ``types.probability_columns`` order."""
+    ``proteins``, in ``types.probability_columns`` order; behind them ``region_p`` and one ``{type.lower()}_region_p`` per type
+    when clusters carry region posteriors (NaN for a cluster of the list that does not)."""
     table = tables.ClusterTable.from_clusters(clusters)
     extra = []
     for name in sorted(types, key=str.casefold):
         col = f"{name.lower()}_probability"
         table.columns[col] = [float(c.type_probabilities.get(name, float("nan"))) for c in clusters]
         extra.append((col, float, None))
+    # region posteriors, behind the per-gene type columns: only when clusters carry them (``region_posteriors=True``)
+    if any(hasattr(c, "region_probability") for c in clusters):
+        nan = float("nan")
+        table.columns["region_p"] = [float(getattr(c, "region_probability", nan)) for c in clusters]
+        extra.append(("region_p", float, None))
+        for name in sorted(types, key=str.casefold):
+            col = f"{name.lower()}_region_p"
+            table.columns[col] = [float(getattr(c, "region_type_probabilities", {}).get(name, nan)) for c in clusters]
+            extra.append((col, float, None))
     at = [n for n, _, _ in tables.ClusterTable.COLUMNS].index("type") + 1
     table.COLUMNS = tables.ClusterTable.COLUMNS[:at] + extra + tables.ClusterTable.COLUMNS[at:]
     return table
@@ -316,7 +336,8 @@ class TypedClusterCRF:
     # ---- prediction
     def _score(self, genes: Iterable[Any], pad: bool, known: Optional[tables.ClusterTable] = None):
         """Genes sorted as ``ClusterCRF.predict_probabilities`` sorts them, their contigs, which contigs are scored, and
-        the device pass: ``p_all`` [n, L] and ``p_any`` [n] (NaN on unscored contigs).  ``known``: a clusters table of
+        the device pass: ``p_all`` [n, L] and ``p_any`` [n] (NaN on unscored contigs), and last the allowed-label masks made
+        from ``known`` (None without).  ``known``: a clusters table of
         regions known beforehand (``known_masks``): every window then runs on the lattice in which a gene of a known region
         cannot be background, and can only take the region's label where the model has it."""
         from . import packing
@@ -341,7 +362,7 @@ class TypedClusterCRF:
                 scored[ci] = False
         L = len(self.classes_)
         if not genes:
-            return genes, contigs, scored, batch, np.zeros((0, L)), np.zeros(0)
+            return genes, contigs, scored, batch, np.zeros((0, L)), np.zeros(0), None
         allowed = None
         if known is not None:
             from .train_cli import join_clusters
@@ -351,7 +372,7 @@ class TypedClusterCRF:
                                                     batch.attr_id, W, self.window_step,
                                                     background=self.classes_.index(self.background), pad=pad, device=self.device,
                                                     allowed=allowed)
-        return genes, contigs, scored, batch, p_all, p_any
+        return genes, contigs, scored, batch, p_all, p_any, allowed
 
     def _annotated(self, contigs, scored, batch, p_any) -> List[Any]:
         """New genes carrying ``p_any``, through ``ClusterCRF``'s annotate path (no label ``'1'``: no cluster weights);
@@ -380,7 +401,7 @@ class TypedClusterCRF:
         """New genes, sorted by (sequence, start), carrying as their probability the windowed probability of lying in any
         cluster: ``ClusterRefiner`` and the table writers work on them unchanged.  ``known`` (here and in the other
         prediction methods): a clusters table of regions known beforehand, whose genes cannot be background (``_score``)."""
-        _, contigs, scored, batch, _, p_any = self._score(genes, pad, known)
+        _, contigs, scored, batch, _, p_any, _ = self._score(genes, pad, known)
         return self._annotated(contigs, scored, batch, p_any)
 
     def predict_label_probabilities(self, genes: Iterable[Any], *, pad: bool = True,
@@ -390,21 +411,44 @@ class TypedClusterCRF:
         return self._score(genes, pad, known)[4]
 
     def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
-                         trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None) -> List[Any]:
+                         trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
+                         region_posteriors: bool = False) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
-        per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities."""
+        per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, and with
+        ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities`` (module docstring)."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
-                                               pad=pad, known=known)[1]
+                                               pad=pad, known=known, region_posteriors=region_posteriors)[1]
+
+    def _region_posteriors(self, batch, allowed, rows: np.ndarray, clusters: List[Any]) -> None:
+        """``region_probability`` and ``region_type_probabilities`` of every called cluster (``rows``: the segment kernel's
+        (contig, number, first gene, last gene + 1)), from ONE native call over the batch: per cluster one span with the set of
+        every label but the background, and one per type with the labels whose names contain it."""
+        L = len(self.classes_)
+        item_ptr = batch.item_ptr.astype(np.int32)
+        not_background = ((1 << L) - 1) & ~(1 << self.classes_.index(self.background))
+        type_masks = [sum(1 << l for l, names in enumerate(self.label_types_) if t in names) for t in self.types_]
+        sets = [not_background] + type_masks
+        contig = np.repeat(rows[:, 0], len(sets)).astype(np.int32)
+        begin = np.repeat(rows[:, 2] - item_ptr[rows[:, 0]], len(sets)).astype(np.int32)
+        end = np.repeat(rows[:, 3] - item_ptr[rows[:, 0]], len(sets)).astype(np.int32)
+        mask = np.tile(np.array(sets, dtype=np.uint32), len(rows))
+        logp = self._fitted().span_log_probabilities(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id, contig, begin, end,
+                                                     mask, device=self.device, allowed=allowed)
+        p = np.exp(logp).reshape(len(rows), len(sets))
+        for cluster, row in zip(clusters, p.tolist()):
+            cluster.region_probability = row[0]
+            cluster.region_type_probabilities = dict(zip(self.types_, row[1:]))
 
     def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
-                                   trim: bool = True, pad: bool = True,
-                                   known: Optional[tables.ClusterTable] = None) -> Tuple[List[Any], List[Any]]:
-        """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass."""
+                                   trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
+                                   region_posteriors: bool = False) -> Tuple[List[Any], List[Any]]:
+        """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
+        second, whole-contig pass gives every cluster its region posteriors (module docstring)."""
         from . import _native
         from .refine import _cluster_class
         from .types import _cluster_type_factory
 
-        _, contigs, scored, batch, p_all, p_any = self._score(genes, pad, known)
+        _, contigs, scored, batch, p_all, p_any, allowed = self._score(genes, pad, known)
         annotated = self._annotated(contigs, scored, batch, p_any)
         if not annotated:
             return annotated, []
@@ -420,6 +464,8 @@ class TypedClusterCRF:
             cluster.type_probabilities = proba
             cluster.type = _cluster_type_factory(cluster)(type_of(proba))
             clusters.append(cluster)
+        if region_posteriors and clusters:
+            self._region_posteriors(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters)
         return annotated, clusters
 
 
@@ -460,6 +506,9 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--no-pad", dest="pad", action="store_false", help="skip sequences shorter than the window")
     pr.add_argument("--known", default=None, help="cluster table (TSV) of regions known beforehand: their genes cannot be "
                     "background, and take the region's type where the model has a label for it")
+    pr.add_argument("--region-posteriors", action="store_true",
+                    help="add region_p and {type}_region_p to clusters.tsv: the whole-contig posterior probability that every gene of "
+                    "a called region lies in a cluster, and in one of the type")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -485,7 +534,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
     annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
                                                       edge_distance=args.edge_distance, trim=args.trim, pad=args.pad,
-                                                      known=None if args.known is None else tables.ClusterTable.load(args.known))
+                                                      known=None if args.known is None else tables.ClusterTable.load(args.known),
+                                                      region_posteriors=args.region_posteriors)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))

@@ -49,7 +49,8 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 /* Thread-local description of the last error returned on this thread. */
 const char *gecco_crf_last_error(void);
 /* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
- * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence. */
+ * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
+ * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -719,6 +720,38 @@ int gecco_crf_windowed_marginals_all_constrained(const gecco_crf_model *m, int32
                                                  const double *attr_value /* or NULL */, const uint32_t *allowed, int32_t window,
                                                  int32_t step, int32_t background /* label id, or -1 */, int32_t pad,
                                                  double *p_all /* [n_genes][L] */, double *p_any /* [n_genes], NULL iff background == -1 */);
+
+/* ---- region posteriors (ABI 2.16.0, additive; gecco_crf_version() stays 340) ------------------------------------------------
+ * logp[q] = log P(y_t in S_q for every t in [begin_q, end_q) | x): the posterior probability, under the model and the whole
+ * contig, that every gene of a span carries a label of a set.  It is a property of the path distribution, not a function of
+ * the per-gene marginals.  The lattice is the whole-contig one of gecco_crf_marginals_full and gecco_crf_viterbi (not a
+ * windowed one); with `allowed` (one mask per gene, as the *_constrained entries take them) it is the lattice restricted by
+ * the masks, and the probability is conditional on the path lying inside them.  attr_value and allowed may each be NULL.
+ *   * Span q is (span_contig[q], span_begin[q], span_end[q], span_mask[q]): a contig of the batch, gene offsets from that
+ *     contig's first gene with the end exclusive, and a mask with bit y set when label y is in the set.  Offsets are relative
+ *     to the contig, so a batch with contig_ptr[0] > 0 works as in the other one-shots.  Spans may overlap and repeat; equal
+ *     queries give equal bits.
+ *   * One forward-backward pass over the batch serves every span; a span then costs a sequential walk of its own genes by one
+ *     group of lanes (a few hundred microseconds per thousand genes: spans are not chunked).  marg [n_genes][L] and lognorm
+ *     [n_contigs], each optional, are the bytes gecco_crf_marginals_full (or its _valued / _constrained sibling, by the
+ *     arguments given) writes for the batch.  (A 2-label model without values and masks has kernels of its own for those:
+ *     asking for marg or lognorm there costs a second pass.)  n_spans == 0 is a valid call that fills marg and lognorm.
+ *   * Results: logp <= 0.0; a set that holds every label gives exactly 0.0; -infinity where the probability is zero (some
+ *     gene of the span allows no label of the set); never NaN.  Inside the span the state scores are shifted by their maximum
+ *     over the SET, so a label outside the set that leads by hundreds costs its exact, finite amount.  The
+ *     two genes bordering a span enter through the whole-contig pass's forward vector and marginals and inherit its range: a
+ *     (gene, label) pair whose forward value underflowed there contributes nothing, as it contributes nothing to marg.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL with a message that names the span ("span q: ..."):
+ *     a contig index outside the batch; begin < 0, begin >= end, or end beyond the contig's length (so a contig without genes
+ *     holds no span); a mask of 0; a mask with a bit at or above the model's label count.  The checks of the *_valued and
+ *     *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                 const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                                 const uint32_t *allowed /* NULL: no masks */, const int32_t *span_contig,
+                                 const int32_t *span_begin, const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans,
+                                 double *logp /* [n_spans] */, double *marg /* [n_genes][L] or NULL */,
+                                 double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
