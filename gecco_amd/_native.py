@@ -6,6 +6,7 @@ call per batch of contigs.  There is no CPU fallback: if the library cannot be l
 import error propagates, and compute calls on a box without a HIP device raise.
 """
 import ctypes
+import operator
 import os
 from typing import Optional, Sequence
 
@@ -87,6 +88,11 @@ SIGNATURES = {
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_i32p, _c_u32p,
          ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p],
+    ),
+    "gecco_crf_sample_paths": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, ctypes.c_uint64,
+         _c_i32p, _c_i32p, _c_u32p, ctypes.c_int32, _c_i8p, _c_i32p, _c_f64p, _c_f64p],
     ),
     "gecco_crf_segment": (
         ctypes.c_int,
@@ -655,6 +661,62 @@ class Model:
         if want_marginals:
             return logp[:ns], marg[:n - n0], ln[:nc]
         return logp[:ns]
+
+    def sample_paths(self, contig_ptr, gene_ptr, attr_id, n_samples, seed=0, device=0, values=None, allowed=None, runs=None,
+                     want_marginals=False, want_paths=True):
+        """Label paths drawn from ``p(y | x)`` on the whole-contig lattice (``gecco_crf_sample_paths``): ``y`` as int8
+        ``[n, n_samples]``, ``y[g, s]`` the label of gene g in sample s, every sample of a contig one draw by forward filtering
+        and backward sampling behind ONE forward-backward pass of the batch.  The uniforms are Philox4x32-10 under ``seed``
+        (0 .. 2**64 - 1) with counters (gene offset, sample, contig): equal arguments give equal bytes, and sample s does not
+        depend on ``n_samples`` (1 .. 2**20).  ``values`` and ``allowed`` as in ``marginals_full``: with ``allowed`` no sample
+        carries a disallowed label.  ``runs=(contig, anchor, mask)``, three arrays of one length: also returns int32
+        ``[n_runs, n_samples, 2]``, per query and sample the maximal run ``(first, last + 1)`` of genes around the anchor (offsets
+        inside contig ``contig[q]``) whose labels all lie in ``mask[q]``, or ``(-1, -1)`` where the anchor's label does not.
+        With ``want_marginals`` also ``marginals [n, L], log Z [n_contigs]`` as ``marginals_full`` gives them.  Returns ``y``,
+        or a tuple ``(y[, runs][, marginals, log Z])``.  ``want_paths=False`` passes ``y = NULL``: the paths stay in device
+        workspace, serve the runs, and ``y`` is left out of what is returned (None when nothing else was asked for)."""
+        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
+        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
+        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
+        n_samples, seed = operator.index(n_samples), operator.index(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed {seed} is outside 0 .. 2**64 - 1")
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+            if values.size != attr_id.size:
+                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
+            values = values if values.size else np.zeros(1, dtype=np.float64)
+        if attr_id.size == 0:
+            attr_id = np.zeros(1, dtype=np.int32)
+        if allowed is not None:
+            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
+            if allowed.size != n:
+                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
+            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+        nr = 0
+        if runs is not None:
+            rc, ra = _i32(runs[0]).ravel(), _i32(runs[1]).ravel()
+            rm = np.ascontiguousarray(runs[2], dtype=np.uint32).ravel()
+            nr = rc.size
+            if not (ra.size == nr and rm.size == nr):
+                raise ValueError("the runs' contig, anchor and mask differ in length")
+        ns = n_samples if 1 <= n_samples <= 1 << 20 else 1  # (the library refuses any other n_samples: the buffers only need a size)
+        y = np.zeros((max(n - n0, 1), ns), dtype=np.int8) if want_paths else None
+        out_runs = np.zeros((max(nr, 1), ns, 2), dtype=np.int32)
+        marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_marginals else None
+        _check(self._lib.gecco_crf_sample_paths(
+            self._h, int(device), _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
+            None if values is None else _ptr(values, _c_f64p), None if allowed is None else _ptr(allowed, _c_u32p), n_samples, seed,
+            _ptr(rc, _c_i32p) if nr else None, _ptr(ra, _c_i32p) if nr else None, _ptr(rm, _c_u32p) if nr else None, nr,
+            None if y is None else _ptr(y, _c_i8p), _ptr(out_runs, _c_i32p) if nr else None,
+            None if marg is None else _ptr(marg, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
+        out = [y[:n - n0]] if want_paths else []
+        if runs is not None:
+            out.append(out_runs[:nr])
+        if want_marginals:
+            out += [marg[:n - n0], ln[:nc]]
+        return None if not out else out[0] if len(out) == 1 else tuple(out)
 
 
 def domain_composition(seg, dom_ptr, dom_col, dom_weight, n_cols, normalize=True, device=0) -> np.ndarray:

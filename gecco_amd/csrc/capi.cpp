@@ -1028,6 +1028,83 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
     GECCO_GUARD_END
 }
 
+// ---- label paths drawn from the posterior (ABI 2.17.0): forward filtering by the whole-contig marginals pass, backward sampling
+// and the run queries behind it (crf_sample.hip)
+GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                     const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                     const uint32_t *allowed, int32_t n_samples, uint64_t seed, const int32_t *run_contig,
+                                     const int32_t *run_anchor, const uint32_t *run_mask, int32_t n_runs, int8_t *y, int32_t *runs,
+                                     double *marg, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    const bool valued = attr_value != nullptr, masked = allowed != nullptr;
+    const int32_t L = m->m.L;
+    // the checks of the call's own arguments, on the host and before any device work
+    if (n_samples < 1 || n_samples > kMaxSamples)
+        return fail("sample_paths: n_samples = " + std::to_string(n_samples) + " is outside 1 .. 1048576");
+    if (n_runs < 0) return fail("sample_paths: negative n_runs");
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    if (n_runs > 0 && (!run_contig || !run_anchor || !run_mask || !runs)) return fail("null buffer");
+    std::vector<RunQuery> queries(static_cast<size_t>(n_runs));
+    const uint32_t beyond = L >= 32 ? 0u : ~0u << L;  // the bits at or above L
+    for (int32_t q = 0; q < n_runs; ++q) {
+        const std::string who = "run " + std::to_string(q);
+        const int32_t c = run_contig[q], t = run_anchor[q];
+        if (c < 0 || c >= n_contigs)
+            return fail(who + ": contig " + std::to_string(c) + " out of range (the batch has " + std::to_string(n_contigs) + ")");
+        const int64_t len = int64_t(contig_ptr[c + 1]) - contig_ptr[c];
+        if (t < 0 || t >= len)
+            return fail(who + ": anchor " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
+                        std::to_string(len) + " genes");
+        if (run_mask[q] == 0) return fail(who + ": the label set is empty (a mask of 0)");
+        if (run_mask[q] & beyond)
+            return fail(who + ": the set holds a label at or above num_labels = " + std::to_string(L) + " (mask " +
+                        std::to_string(run_mask[q]) + ")");
+        queries[size_t(q)] = RunQuery{c, t, run_mask[q]};
+    }
+    // marg and lognorm are the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one
+    // exception: a 2-label model without values and masks has kernels of its own there, which this call then asks in a second pass
+    const bool own_l2 = L == 2 && !valued && !masked && (marg || lognorm);
+    int rc;
+    {
+        ResidentBatch b;
+        b.plan.samples = true;
+        const size_t per_gene[2] = {size_t(L) * 8, size_t(n_samples)};  // marginals; the paths, which need no caller's buffer
+        rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false, per_gene,
+                        8, b);
+        if (rc || b.n == 0) {  // (no genes: no labels, no run -- a checked run lies inside a contig with genes)
+            for (int32_t c = 0; !rc && lognorm && c < n_contigs; ++c) lognorm[c] = 0.0;
+            return rc;
+        }
+        DevBuf<char> q;
+        const size_t b_queries = align256(size_t(n_runs) * sizeof(RunQuery)), b_runs = size_t(n_runs) * size_t(n_samples) * 8;
+        if (n_runs > 0) {
+            if ((rc = q.alloc(b_queries + b_runs, "hipMalloc runs"))) return rc;
+            if ((rc = check_hip(hipMemcpy(q.p, queries.data(), size_t(n_runs) * sizeof(RunQuery), hipMemcpyHostToDevice), "upload runs")))
+                return rc;
+        }
+        int32_t *d_runs = n_runs > 0 ? reinterpret_cast<int32_t *>(q.p + b_queries) : nullptr;
+        rc = batch_wait(plan_run_sample_paths(b.plan, b.csr, n_samples, seed, reinterpret_cast<const RunQuery *>(q.p), n_runs,
+                                              b.out<int8_t>(1), d_runs, b.out<double>(0), b.out<double>(2), nullptr), "sampled paths");
+        rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * size_t(n_samples), "download paths");
+        rc = batch_fetch(rc, runs, d_runs, b_runs, "download runs");
+        if (!own_l2) {
+            rc = batch_fetch(rc, marg, b.out<double>(0), size_t(b.n) * size_t(L) * 8, "download marginals");
+            rc = batch_fetch(rc, lognorm, b.out<double>(2), size_t(n_contigs) * 8, "download lognorm");
+        }
+        if (rc || !own_l2) return rc;
+    }
+    // (that entry takes batches that start at gene 0: a slice is rebased for it, rows and attribute entries alike)
+    if (contig_ptr[0] == 0) return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+    const int32_t g0 = contig_ptr[0], a0 = gene_ptr[g0];
+    std::vector<int32_t> contigs(size_t(n_contigs) + 1), rows(size_t(contig_ptr[n_contigs] - g0) + 1);
+    for (size_t c = 0; c < contigs.size(); ++c) contigs[c] = contig_ptr[c] - g0;
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = gene_ptr[size_t(g0) + i] - a0;
+    return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
+    GECCO_GUARD_END
+}
+
 namespace {
 // grow-only scratch of the stand-alone segmenter / composition calls, one set per host thread
 struct Scratch {

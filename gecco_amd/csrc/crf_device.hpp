@@ -328,6 +328,23 @@ struct SpanQuery {
 // same stream with a.state non-null: reads a.state, a.E, a.alpha and a.marg, whatever arrangement filled them
 hipError_t launch_gen_spans(const GenArgs &a, const SpanQuery *spans, int32_t n_spans, double *logp, hipStream_t stream);
 
+// ---- label paths drawn from the posterior (crf_sample.hip) ----
+constexpr int32_t kMaxSamples = 1 << 20;  // n_samples of one call
+// One run query: the gene at offset `anchor` inside contig `contig`, and the label set `mask`.  The host has checked the ranges
+// and that mask has a bit, and none at or above L.
+struct RunQuery {
+    int32_t contig, anchor;
+    uint32_t mask;
+};
+// y[g * n_samples + s] = the label of gene g in sample s (gene-major), every sample a path drawn from p(y | x) on the lattice of
+// the whole-contig marginals that ran before it on the same stream: reads a.alpha as directions (whatever arrangement filled
+// it), a.exp_trans, and a.marg where a gene's weights sum to nothing (the fallback of crf_sample.hip)
+hipError_t launch_gen_sample_paths(const GenArgs &a, int32_t n_samples, uint64_t seed, int8_t *y, hipStream_t stream);
+// runs[(q * n_samples + s) * 2 + {0, 1}] = (first, last + 1) of the maximal run of genes with labels in the mask around query
+// q's anchor in sample s, offsets inside the contig, or (-1, -1) where the anchor's label is outside the mask
+hipError_t launch_gen_sample_runs(const GenArgs &a, const int8_t *y, const RunQuery *queries, int32_t n_runs, int32_t n_samples,
+                                  int32_t *runs, hipStream_t stream);
+
 // ---- any number of labels: windowed marginals, one label or every label (crf_general_windowed.hip) ----
 // label >= 0: p_out[g] = max over the windows covering g of P_w(y_g = label), clipped at 1 by the tile kernels.
 // label < 0: every label in one pass, p_out[g][l] likewise for all l, and p_any[g] = max over the same windows of the sum of

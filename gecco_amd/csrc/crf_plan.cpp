@@ -384,8 +384,8 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     }
     {
         const char *env = std::getenv("GECCO_CRF_FORCE_GENERAL");
-        // (valued and masked state scores exist in gl_state alone; region posteriors read the any-L workspace)
-        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.spans;
+        // (valued and masked state scores exist in gl_state alone; region posteriors and sampled paths read the any-L workspace)
+        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.spans || p.samples;
     }
     p.fast_ok = (!p.general && W <= kWinMaxW && rescale_mask_for(m, W, &p.rescale_mask));
     {
@@ -1394,6 +1394,29 @@ int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *
     if ((rc = run_gen_whole(p, with_state, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
     // (a batch's chunked tail has been joined to `stream` by then)
     return check_hip(launch_gen_spans(g, d_spans, n_spans, d_logp, stream), "span launch");
+}
+
+int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint64_t seed, const RunQuery *d_queries, int32_t n_runs,
+                          int8_t *d_y, int32_t *d_runs, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    SeqArgs a;
+    int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc) return rc;
+    if (!p.samples || !p.general) {
+        set_error("the plan was not built for sampled paths");
+        return GECCO_CRF_EINVAL;
+    }
+    if (n_samples < 1 || n_samples > kMaxSamples || n_runs < 0) {
+        set_error("n_samples outside 1 .. 2^20, or a negative number of runs");
+        return GECCO_CRF_EINVAL;
+    }
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0, !csr.gene_ptr || !d_marg || !d_y || (n_runs > 0 && (!d_queries || !d_runs)), rc))
+        return rc;
+    // the marginals recursion as plan_run_marginals_full runs it: the same launches, the same bits
+    GenArgs g;
+    if ((rc = run_gen_whole(p, kGenMarginals, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
+    // (a batch's chunked tail has been joined to `stream` by then)
+    if ((rc = check_hip(launch_gen_sample_paths(g, n_samples, seed, d_y, stream), "sample launch"))) return rc;
+    return check_hip(launch_gen_sample_runs(g, d_y, d_queries, n_runs, n_samples, d_runs, stream), "run launch");
 }
 
 int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,

@@ -167,6 +167,9 @@ struct Plan {
     // takes the any-L kernels at every label count, as `valued` and `masked` do -- the span kernel reads the forward vectors of
     // their workspace, which a 2-label plan does not have otherwise.  Nothing else changes: reference-bits mode is decided as ever.
     bool spans = false;
+    // Sampled label paths (plan_run_sample_paths): set by the owner before plan_build, and forces the any-L kernels
+    // the way `spans` does -- the sampling kernel reads the same forward vectors.
+    bool samples = false;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_general_windowed.hip): the tile table of the lane-per-window tier when the plan's own
@@ -214,6 +217,13 @@ int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score
 // gene of span q carries a label of its set | x) for the n_spans checked queries of d_spans (crf_spans.hip), all on `stream`
 int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *d_spans, int32_t n_spans, double *d_logp,
                                 double *d_marg, double *d_lognorm, hipStream_t stream);
+// Label paths drawn from p(y | x), a plan laid out with `samples`: the whole-contig marginals of the batch exactly as
+// plan_run_marginals_full runs them (d_marg [n_genes][L], d_lognorm [n_contigs] or null), then d_y[g * n_samples + s] = the label
+// of gene g in sample s (crf_sample.hip: Philox counters (gene offset, sample, contig, 0) under `seed`), then, for the n_runs
+// checked queries of d_queries, d_runs [n_runs][n_samples][2]: the run of labels of the query's set around its anchor in every
+// sample.  All on `stream`.
+int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint64_t seed, const RunQuery *d_queries, int32_t n_runs,
+                          int8_t *d_y, int32_t *d_runs, double *d_marg, double *d_lognorm, hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);
 // returns GECCO_CRF_* ; on HIP failure sets the error text

@@ -325,6 +325,80 @@ class SequenceCRF:
         """``exp`` of ``span_log_probability``."""
         return np.exp(self.span_log_probability(X, spans, allowed=allowed))
 
+    def _anchor_queries(self, anchors, seq_ptr: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``anchors`` as the native call's three arrays; every refusal is raised here, before any device call."""
+        index = {c: k for k, c in enumerate(self.classes_)}
+        n_seqs = len(seq_ptr) - 1
+        contig, anchor, mask = [], [], []
+        for q, entry in enumerate(anchors):
+            try:
+                k, item, labels = entry
+                k, item = operator.index(k), operator.index(item)
+            except (TypeError, ValueError):
+                raise ValueError(f"anchor {q}: expected (sequence_index, item, labels), got {entry!r}") from None
+            if not 0 <= k < n_seqs:
+                raise ValueError(f"anchor {q}: sequence index {k} out of range (X holds {n_seqs} sequences)")
+            length = int(seq_ptr[k + 1] - seq_ptr[k])
+            if not 0 <= item < length:
+                raise ValueError(f"anchor {q}: item {item} lies outside sequence {k} of {length} items")
+            names = [str(m) for m in labels] if isinstance(labels, (set, frozenset, list, tuple)) else [str(labels)]
+            if not names:
+                raise ValueError(f"anchor {q}: an empty set holds no label")
+            bits = 0
+            for name in names:
+                if name not in index:
+                    raise ValueError(f"anchor {q}: unknown label {name!r} (classes_: {self.classes_})")
+                bits |= 1 << index[name]
+            contig.append(k)
+            anchor.append(item)
+            mask.append(bits)
+        return np.array(contig, dtype=np.int32), np.array(anchor, dtype=np.int32), np.array(mask, dtype=np.uint32)
+
+    @staticmethod
+    def _sample_count(n_samples, seed) -> Tuple[int, int]:
+        try:
+            n_samples, seed = operator.index(n_samples), operator.index(seed)
+        except TypeError:
+            raise ValueError(f"n_samples and seed are integers, got {n_samples!r} and {seed!r}") from None
+        if not 1 <= n_samples <= 1 << 20:
+            raise ValueError(f"n_samples = {n_samples} is outside 1 .. 1048576")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed {seed} is outside 0 .. 2**64 - 1")
+        return n_samples, seed
+
+    def sample(self, X, n_samples, seed=0, allowed=None) -> List[np.ndarray]:
+        """Label paths drawn from the posterior ``p(y | x)`` on the whole-sequence lattice (that of ``predict`` and
+        ``predict_marginals``, not a windowed one): per sequence one int8 ``[n_samples, n_items]`` array of indices into
+        ``classes_``, row s the s-th path (a transposed view of the native call's item-major block; ``[n_samples, 0]`` for a
+        sequence without items).  All samples take one forward-backward pass over ``X`` and one native call.  The draws are a
+        function of ``seed`` and the position alone (Philox counters: item, sample, sequence): the same call gives the same
+        paths, and path s does not depend on ``n_samples``.  With ``allowed`` (as in ``predict_marginals``) the paths are drawn
+        on the restricted lattice and never leave the sets."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        n_samples, seed = self._sample_count(n_samples, seed)
+        if seq_ptr[-1] == 0:
+            return [np.zeros((n_samples, 0), dtype=np.int8) for _ in range(len(seq_ptr) - 1)]
+        y = self._model.sample_paths(seq_ptr, item_ptr, attr, n_samples, seed=seed, device=self.device, values=values,
+                                     allowed=masks)
+        return [rows.T for rows in self._split(y, seq_ptr)]
+
+    def sample_runs(self, X, anchors, n_samples, seed=0, allowed=None) -> np.ndarray:
+        """For every ``(sequence_index, item, labels)`` of ``anchors`` and every one of the ``n_samples`` paths ``sample`` draws
+        with the same ``seed`` and ``allowed``: the maximal run of items around ``X[sequence_index][item]`` whose labels all lie
+        in ``labels`` (a label, or a ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels), as ``(first, last + 1)`` item
+        indices inside the sequence, or ``(-1, -1)`` where the path's label at the anchor is outside ``labels``.  int32
+        ``[n_anchors, n_samples, 2]``; the paths stay on the device.  Raises ``ValueError`` before any device call for an
+        unknown label, an empty set, a sequence index out of range and an item outside its sequence."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        n_samples, seed = self._sample_count(n_samples, seed)
+        contig, anchor, mask = self._anchor_queries(anchors, seq_ptr)
+        if len(contig) == 0:
+            return np.zeros((0, n_samples, 2), dtype=np.int32)
+        return self._model.sample_paths(seq_ptr, item_ptr, attr, n_samples, seed=seed, device=self.device, values=values,
+                                        allowed=masks, runs=(contig, anchor, mask), want_paths=False)
+
     def _windowed(self) -> None:
         self._fitted()
         if self.window_size is None:

@@ -34,6 +34,20 @@ native call), not windowed ones: the model's parameters are those fitted on wind
 contig.  ``known=`` restricts that lattice as it restricts the windows.  ``clusters.tsv`` then has the columns ``region_p``
 and ``{type}_region_p``; without the flag the tables are unchanged.
 
+Boundary intervals (opt-in: ``boundary_samples=N > 0``, ``predict --boundary-samples N [--seed S]``).  "How sure are you about
+where it starts and ends": N label paths per contig are drawn from the path distribution p(y | x)
+(``_native.Model.sample_paths``: forward filtering, backward sampling, one forward-backward pass and one native call per
+batch; the draws are a function of ``seed`` alone).  Every called cluster gets one run query: its anchor is the cluster's gene
+with the greatest any-cluster probability (the first on ties), and in every path whose label at the anchor is not the
+background, the run is the maximal stretch of genes around the anchor without a background label.  With m the number of such
+paths: ``anchor_probability = m / N``; ``exact_probability`` = the share of the N paths whose run is exactly the called gene
+range; ``start_interval`` and ``end_interval`` = (lower, upper), the 5 % and 95 % order statistics over the m runs of the first
+gene's ``start`` and of the last gene's ``end`` -- the sorted values at indices floor(0.05 (m - 1)) and ceil(0.95 (m - 1)); with
+m = 0 the called cluster's own start and end.  Like the region posteriors these are WHOLE-CONTIG posteriors, not windowed
+ones, and ``known=`` restricts the lattice in the same way.  ``clusters.tsv`` then has the columns ``anchor_p``, ``exact_p``,
+``start_lo``, ``start_hi``, ``end_lo`` and ``end_hi`` behind the region columns; with N = 0 the tables and every launch are
+unchanged.
+
 Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
 ``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
 """
@@ -42,6 +56,7 @@ import gc
 import hashlib
 import itertools
 import json
+import math
 import operator
 import os
 import random
@@ -189,7 +204,9 @@ def type_of(probabilities: Dict[str, float]) -> frozenset:
 def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables.ClusterTable:
     """``ClusterTable.from_clusters`` with one ``{type.lower()}_probability`` column per type between ``type`` and
     ``proteins``, in ``types.probability_columns`` order; behind them ``region_p`` and one ``{type.lower()}_region_p`` per type
-    when clusters carry region posteriors (NaN for a cluster of the list that does not)."""
+    when clusters carry region posteriors (NaN for a cluster of the list that does not); behind those ``anchor_p``, ``exact_p``,
+    ``start_lo``, ``start_hi``, ``end_lo`` and ``end_hi`` when clusters carry boundary intervals (``boundary_samples > 0``; a
+    cluster of the list that does not: NaN, and its own start and end)."""
     table = tables.ClusterTable.from_clusters(clusters)
     extra = []
     for name in sorted(types, key=str.casefold):
@@ -205,6 +222,16 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
             col = f"{name.lower()}_region_p"
             table.columns[col] = [float(getattr(c, "region_type_probabilities", {}).get(name, nan)) for c in clusters]
             extra.append((col, float, None))
+    # boundary intervals from sampled paths, behind the region columns: only when clusters carry them (``boundary_samples > 0``)
+    if any(hasattr(c, "anchor_probability") for c in clusters):
+        nan = float("nan")
+        table.columns["anchor_p"] = [float(getattr(c, "anchor_probability", nan)) for c in clusters]
+        table.columns["exact_p"] = [float(getattr(c, "exact_probability", nan)) for c in clusters]
+        extra += [("anchor_p", float, None), ("exact_p", float, None)]
+        for col, attribute, k, own in (("start_lo", "start_interval", 0, "start"), ("start_hi", "start_interval", 1, "start"),
+                                       ("end_lo", "end_interval", 0, "end"), ("end_hi", "end_interval", 1, "end")):
+            table.columns[col] = [int(getattr(c, attribute)[k]) if hasattr(c, attribute) else int(getattr(c, own)) for c in clusters]
+            extra.append((col, int, None))
     at = [n for n, _, _ in tables.ClusterTable.COLUMNS].index("type") + 1
     table.COLUMNS = tables.ClusterTable.COLUMNS[:at] + extra + tables.ClusterTable.COLUMNS[at:]
     return table
@@ -412,12 +439,15 @@ class TypedClusterCRF:
 
     def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                          trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
-                         region_posteriors: bool = False) -> List[Any]:
+                         region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
-        per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, and with
-        ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities`` (module docstring)."""
+        per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, with
+        ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities``, and with
+        ``boundary_samples > 0`` each with ``anchor_probability``, ``exact_probability``, ``start_interval`` and
+        ``end_interval`` (module docstring)."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
-                                               pad=pad, known=known, region_posteriors=region_posteriors)[1]
+                                               pad=pad, known=known, region_posteriors=region_posteriors,
+                                               boundary_samples=boundary_samples, seed=seed)[1]
 
     def _region_posteriors(self, batch, allowed, rows: np.ndarray, clusters: List[Any]) -> None:
         """``region_probability`` and ``region_type_probabilities`` of every called cluster (``rows``: the segment kernel's
@@ -439,12 +469,53 @@ class TypedClusterCRF:
             cluster.region_probability = row[0]
             cluster.region_type_probabilities = dict(zip(self.types_, row[1:]))
 
+    def _boundary_intervals(self, batch, allowed, rows: np.ndarray, clusters: List[Any], annotated: List[Any], p_any: np.ndarray,
+                            n_samples: int, seed: int) -> None:
+        """``anchor_probability``, ``exact_probability``, ``start_interval`` and ``end_interval`` of every called cluster
+        (``rows``: the segment kernel's (contig, number, first gene, last gene + 1)), from ONE native call over the batch:
+        ``n_samples`` label paths per contig drawn from the whole-contig posterior, and per cluster one run query -- the run of
+        genes outside the background around the cluster's gene with the greatest ``p_any`` (the first on ties)."""
+        L = len(self.classes_)
+        item_ptr = batch.item_ptr.astype(np.int32)
+        not_background = ((1 << L) - 1) & ~(1 << self.classes_.index(self.background))
+        base = item_ptr[rows[:, 0]].astype(np.int64)
+        anchor = np.array([first + int(np.argmax(p_any[first:last])) for first, last in rows[:, 2:4].tolist()], dtype=np.int64)
+        runs = self._fitted().sample_paths(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id, n_samples, seed=seed,
+                                           device=self.device, allowed=allowed,
+                                           runs=(rows[:, 0].astype(np.int32), (anchor - base).astype(np.int32),
+                                                 np.full(len(rows), not_background, dtype=np.uint32)), want_paths=False)
+        for cluster, (_, _, first, last), g0, found in zip(clusters, rows.tolist(), base.tolist(), runs):
+            there = found[found[:, 0] >= 0]
+            m = len(there)
+            cluster.anchor_probability = m / n_samples
+            cluster.exact_probability = int(np.count_nonzero((there[:, 0] == first - g0) & (there[:, 1] == last - g0))) / n_samples
+            if m == 0:
+                cluster.start_interval = (int(cluster.start), int(cluster.start))
+                cluster.end_interval = (int(cluster.end), int(cluster.end))
+                continue
+            starts = sorted(annotated[g0 + k].start for k in there[:, 0].tolist())
+            ends = sorted(annotated[g0 + k - 1].end for k in there[:, 1].tolist())
+            lo, hi = int(math.floor(0.05 * (m - 1))), int(math.ceil(0.95 * (m - 1)))
+            cluster.start_interval = (int(starts[lo]), int(starts[hi]))
+            cluster.end_interval = (int(ends[lo]), int(ends[hi]))
+
     def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                                    trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
-                                   region_posteriors: bool = False) -> Tuple[List[Any], List[Any]]:
+                                   region_posteriors: bool = False, boundary_samples: int = 0,
+                                   seed: int = 0) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
-        second, whole-contig pass gives every cluster its region posteriors (module docstring)."""
+        second, whole-contig pass gives every cluster its region posteriors, and with ``boundary_samples = N > 0`` one more
+        draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals (module docstring)."""
         from . import _native
+
+        try:
+            boundary_samples, seed = operator.index(boundary_samples), operator.index(seed)
+        except TypeError:
+            raise ValueError(f"boundary_samples and seed are integers, got {boundary_samples!r} and {seed!r}") from None
+        if not 0 <= boundary_samples <= 1 << 20:
+            raise ValueError(f"boundary_samples = {boundary_samples} is outside 0 .. 1048576")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed {seed} is outside 0 .. 2**64 - 1")
         from .refine import _cluster_class
         from .types import _cluster_type_factory
 
@@ -466,6 +537,9 @@ class TypedClusterCRF:
             clusters.append(cluster)
         if region_posteriors and clusters:
             self._region_posteriors(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters)
+        if boundary_samples > 0 and clusters:
+            self._boundary_intervals(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters, annotated, p_any,
+                                     boundary_samples, seed)
         return annotated, clusters
 
 
@@ -509,6 +583,10 @@ def build_parser() -> argparse.ArgumentParser:
     pr.add_argument("--region-posteriors", action="store_true",
                     help="add region_p and {type}_region_p to clusters.tsv: the whole-contig posterior probability that every gene of "
                     "a called region lies in a cluster, and in one of the type")
+    pr.add_argument("--boundary-samples", type=int, default=0, metavar="N",
+                    help="add anchor_p, exact_p, start_lo, start_hi, end_lo and end_hi to clusters.tsv: 90 %% intervals of every "
+                    "called region's start and end from N label paths drawn from the whole-contig posterior")
+    pr.add_argument("--seed", type=int, default=0, help="seed of the drawn paths (with --boundary-samples)")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -535,7 +613,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
                                                       edge_distance=args.edge_distance, trim=args.trim, pad=args.pad,
                                                       known=None if args.known is None else tables.ClusterTable.load(args.known),
-                                                      region_posteriors=args.region_posteriors)
+                                                      region_posteriors=args.region_posteriors,
+                                                      boundary_samples=args.boundary_samples, seed=args.seed)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))

@@ -50,7 +50,7 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 const char *gecco_crf_last_error(void);
 /* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
- * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way. */
+ * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -752,6 +752,47 @@ int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t device, const
                                  const int32_t *span_begin, const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans,
                                  double *logp /* [n_spans] */, double *marg /* [n_genes][L] or NULL */,
                                  double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- label paths drawn from the posterior (ABI 2.17.0, additive; gecco_crf_version() stays 340) --------------------------------
+ * y[g * n_samples + s] = the label of gene g in sample s: n_samples label paths per contig drawn from p(y | x) on the
+ * whole-contig lattice of gecco_crf_marginals_full and gecco_crf_viterbi (not a windowed one), by forward filtering and backward
+ * sampling.  With `allowed` (one mask per gene, as the *_constrained entries take them) the lattice is the restricted one: no
+ * sample carries a disallowed label.  attr_value and allowed may each be NULL.  One forward-backward pass over the batch serves
+ * every sample; the draws are parallel over samples and contigs and sequential along a contig (contigs are not chunked).
+ *   * The rule.  alpha_t is the pass's forward vector at gene t (used as a direction: its scaling cancels), M = exp(trans).  A
+ *     sample walks from its contig's last gene to its first.  With j the label drawn at gene t + 1, the weights are
+ *     w_i = alpha_t(i) * M(i, j) (w_i = alpha_t(i) at the last gene), their running sums c_i = w_0 + ... + w_i in label order,
+ *     and the label is the smallest i with c_i > u * c_{L-1}.  A label whose weight is exactly 0 is never drawn (a disallowed
+ *     label, a transition with exp(trans) = 0, an underflowed alpha); where rounding leaves no such i, the label is the last i
+ *     with w_i > 0.
+ *   * The uniforms.  u comes from Philox4x32-10 (Salmon et al., Random123) with key (seed & 0xffffffff, seed >> 32) and counter
+ *     (t, s, c, 0): t the gene's offset inside its contig, s the sample, c the contig's index in the batch.  From the output
+ *     words x0, x1: u = double(((uint64_t)x0 << 21) ^ (x1 >> 11)) * 2^-53, in [0, 1).  No state is kept: equal arguments give
+ *     equal bytes, and sample s of a contig does not depend on n_samples.
+ *   * The fallback.  Where c_{L-1} is not > 0 or not finite -- every weight lost to underflow, which is outside the range
+ *     gecco_crf_marginals_full documents -- the label is the first arg max of marg at that gene.  No label >= num_labels is
+ *     ever written.
+ *   * Run query q is (run_contig[q], run_anchor[q], run_mask[q]): a contig of the batch, a gene offset from that contig's first
+ *     gene, and a mask with bit y set when label y is in the set.  runs[(q * n_samples + s) * 2 + {0, 1}] = (first, last + 1),
+ *     offsets inside the contig, of the maximal run of genes around the anchor whose labels in sample s all lie in the set, or
+ *     (-1, -1) where the anchor's own label does not.
+ *   * Outputs.  y is int8 [n_genes][n_samples], gene-major; y == NULL is valid (the paths then live in device workspace only,
+ *     for the runs).  runs is int32 [n_runs][n_samples][2], NULL iff n_runs == 0.  marg [n_genes][L] and lognorm [n_contigs],
+ *     each optional, are the bytes gecco_crf_marginals_full (or its _valued / _constrained sibling, by the arguments given)
+ *     writes for the batch.  (A 2-label model without values and masks has kernels of its own for those: asking for marg or
+ *     lognorm there costs a second pass.)  Sizes are computed in size_t; a failed allocation is GECCO_CRF_ENOMEM.  A batch
+ *     without genes writes nothing but lognorm = 0; contigs without genes and contig_ptr[0] > 0 work as in the other one-shots.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL with a message that names the argument or the run
+ *     ("run q: ..."): n_samples outside 1 .. 2^20; a run's contig outside the batch; an anchor outside its contig (so a contig
+ *     without genes holds no anchor); a mask of 0; a mask with a bit at or above the model's label count.  The checks of the
+ *     *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                           const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                           const uint32_t *allowed /* NULL: no masks */, int32_t n_samples, uint64_t seed,
+                           const int32_t *run_contig, const int32_t *run_anchor, const uint32_t *run_mask, int32_t n_runs,
+                           int8_t *y /* [n_genes][n_samples] or NULL */, int32_t *runs /* [n_runs][n_samples][2], NULL iff n_runs == 0 */,
+                           double *marg /* [n_genes][L] or NULL */, double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
