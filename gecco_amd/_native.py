@@ -94,6 +94,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, ctypes.c_uint64,
          _c_i32p, _c_i32p, _c_u32p, ctypes.c_int32, _c_i8p, _c_i32p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_viterbi_kbest": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, _c_i8p, _c_f64p,
+         _c_i32p, _c_f64p],
+    ),
     "gecco_crf_segment": (
         ctypes.c_int,
         [ctypes.c_int32, _c_f64p, _c_u8p, _c_i32p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
@@ -717,6 +722,42 @@ class Model:
         if want_marginals:
             out += [marg[:n - n0], ln[:nc]]
         return None if not out else out[0] if len(out) == 1 else tuple(out)
+
+    def viterbi_kbest(self, contig_ptr, gene_ptr, attr_id, k, device=0, values=None, allowed=None):
+        """The ``k`` best label paths of every contig on the whole-contig lattice (``gecco_crf_viterbi_kbest``), 1 <= k <= 32.
+        Returns ``(y, score, n_paths, lognorm)``: ``y`` int8 ``[n, k]``, ``y[g, r]`` the label of gene g on its contig's rank-r
+        path (-1 where no path fills the rank); ``score`` float64 ``[n_contigs, k]``, non-increasing along a row, the path's
+        left-to-right score (``-inf`` at an empty rank); ``n_paths`` int32 ``[n_contigs]``; ``lognorm`` ``[n_contigs]`` as
+        ``marginals_full`` gives it, so that ``exp(score - lognorm[:, None])`` are the paths' exact probabilities.  Equal
+        scores are ordered by the reversed path (last gene's label first); rank r does not depend on ``k``; rank 0 is
+        ``viterbi``'s path.  ``values`` and ``allowed`` as in ``marginals_full``: with ``allowed`` no path carries a disallowed
+        label.  A contig without genes has ``n_paths`` 0, scores ``-inf`` and ``lognorm`` 0."""
+        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
+        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
+        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
+        k = operator.index(k)
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+            if values.size != attr_id.size:
+                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
+            values = values if values.size else np.zeros(1, dtype=np.float64)
+        if attr_id.size == 0:
+            attr_id = np.zeros(1, dtype=np.int32)
+        if allowed is not None:
+            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
+            if allowed.size != n:
+                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
+            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+        kk = k if 1 <= k <= 32 else 1  # (the library refuses any other k: the buffers only need a size)
+        y = np.zeros((max(n - n0, 1), kk), dtype=np.int8)
+        score = np.zeros((max(nc, 1), kk), dtype=np.float64)
+        n_paths = np.zeros(max(nc, 1), dtype=np.int32)
+        ln = np.zeros(max(nc, 1), dtype=np.float64)
+        _check(self._lib.gecco_crf_viterbi_kbest(
+            self._h, int(device), _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
+            None if values is None else _ptr(values, _c_f64p), None if allowed is None else _ptr(allowed, _c_u32p), k,
+            _ptr(y, _c_i8p), _ptr(score, _c_f64p), _ptr(n_paths, _c_i32p), _ptr(ln, _c_f64p)))
+        return y[:n - n0], score[:nc], n_paths[:nc], ln[:nc]
 
 
 def domain_composition(seg, dom_ptr, dom_col, dom_weight, n_cols, normalize=True, device=0) -> np.ndarray:

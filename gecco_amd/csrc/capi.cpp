@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <memory>
 #include <new>
 #include <string>
@@ -953,6 +954,20 @@ GECCO_API int gecco_crf_viterbi_constrained(const gecco_crf_model *m, int32_t de
                        score);
 }
 
+namespace {
+// gecco_crf_marginals_full for the one-shots below, whose plain 2-label models ask that entry's own kernels for marg / lognorm in a
+// second pass.  That entry takes batches that start at gene 0: a slice is rebased for it, rows and attribute entries alike.
+int marginals_full_of_slice(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                            const int32_t *gene_ptr, const int32_t *attr_id, double *marg, double *lognorm) {
+    if (contig_ptr[0] == 0) return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+    const int32_t g0 = contig_ptr[0], a0 = gene_ptr[g0];
+    std::vector<int32_t> contigs(size_t(n_contigs) + 1), rows(size_t(contig_ptr[n_contigs] - g0) + 1);
+    for (size_t c = 0; c < contigs.size(); ++c) contigs[c] = contig_ptr[c] - g0;
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = gene_ptr[size_t(g0) + i] - a0;
+    return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
+}
+}  // namespace
+
 // ---- region posteriors (ABI 2.16.0): log P(every gene of a span carries a label of a set | x) on the whole-contig lattice, any
 // number of spans behind one forward-backward pass of the batch (crf_spans.hip)
 GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
@@ -1018,13 +1033,7 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
         }
         if (rc || !own_l2) return rc;
     }
-    // (that entry takes batches that start at gene 0: a slice is rebased for it, rows and attribute entries alike)
-    if (contig_ptr[0] == 0) return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
-    const int32_t g0 = contig_ptr[0], a0 = gene_ptr[g0];
-    std::vector<int32_t> contigs(size_t(n_contigs) + 1), rows(size_t(contig_ptr[n_contigs] - g0) + 1);
-    for (size_t c = 0; c < contigs.size(); ++c) contigs[c] = contig_ptr[c] - g0;
-    for (size_t i = 0; i < rows.size(); ++i) rows[i] = gene_ptr[size_t(g0) + i] - a0;
-    return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
+    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
     GECCO_GUARD_END
 }
 
@@ -1095,13 +1104,61 @@ GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, c
         }
         if (rc || !own_l2) return rc;
     }
-    // (that entry takes batches that start at gene 0: a slice is rebased for it, rows and attribute entries alike)
-    if (contig_ptr[0] == 0) return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
-    const int32_t g0 = contig_ptr[0], a0 = gene_ptr[g0];
-    std::vector<int32_t> contigs(size_t(n_contigs) + 1), rows(size_t(contig_ptr[n_contigs] - g0) + 1);
-    for (size_t c = 0; c < contigs.size(); ++c) contigs[c] = contig_ptr[c] - g0;
-    for (size_t i = 0; i < rows.size(); ++i) rows[i] = gene_ptr[size_t(g0) + i] - a0;
-    return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
+    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+    GECCO_GUARD_END
+}
+
+// ---- the K best label paths with their scores (ABI 2.18.0): the list Viterbi recursion behind gl_state, log Z from the
+// whole-contig marginals pass (crf_kbest.hip)
+GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                      const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                      const uint32_t *allowed, int32_t k, int8_t *y, double *score, int32_t *n_paths,
+                                      double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceGuard guard;
+    GECCO_GUARD_BEGIN
+    const bool valued = attr_value != nullptr, masked = allowed != nullptr;
+    const int32_t L = m->m.L;
+    // the check of the call's own argument, on the host and before any device work
+    if (k < 1 || k > kMaxKBest) return fail("viterbi_kbest: k = " + std::to_string(k) + " is outside 1 .. 32");
+    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    if (n_contigs > 0 && (!score || !n_paths)) return fail("null buffer");
+    int rc;
+    if ((rc = check_output(contig_ptr, n_contigs, y))) return rc;
+    // lognorm is the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one exception: a
+    // 2-label model without values and masks has kernels of its own there, which this call then asks in a second pass
+    const bool own_l2 = L == 2 && !valued && !masked && lognorm;
+    {
+        ResidentBatch b;
+        b.plan.kbest = true;
+        const size_t K = size_t(k), nc = size_t(n_contigs);
+        // per gene: marginals (the pass's own output; not returned), the paths.  Per contig: log Z, k scores, the number of paths
+        const size_t per_gene[2] = {size_t(L) * 8, K};
+        rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false,
+                        per_gene, 8 + K * 8 + 4, b);
+        if (rc || b.n == 0) {  // (no genes: no path anywhere)
+            for (size_t c = 0; !rc && c < nc; ++c) {
+                if (lognorm) lognorm[c] = 0.0;
+                n_paths[c] = 0;
+                for (size_t r = 0; r < K; ++r) score[c * K + r] = -std::numeric_limits<double>::infinity();
+            }
+            return rc;
+        }
+        double *d_lognorm = b.out<double>(2), *d_score = d_lognorm + nc;
+        int32_t *d_n_paths = reinterpret_cast<int32_t *>(d_score + nc * K);
+        DevBuf<char> ws;
+        const size_t b_back = align256(kbest_back_bytes(b.n, L, k)), b_fin = kbest_fin_bytes(n_contigs, k);
+        if ((rc = ws.alloc(b_back + b_fin, "hipMalloc k-best back-pointers"))) return rc;
+        uint16_t *d_back = reinterpret_cast<uint16_t *>(ws.p), *d_fin = reinterpret_cast<uint16_t *>(ws.p + b_back);
+        rc = batch_wait(plan_run_viterbi_kbest(b.plan, b.csr, k, d_back, d_fin, b.out<int8_t>(1), d_score, d_n_paths, b.out<double>(0),
+                                               d_lognorm, nullptr), "k-best paths");
+        rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * K, "download paths");
+        rc = batch_fetch(rc, score, d_score, nc * K * 8, "download scores");
+        rc = batch_fetch(rc, n_paths, d_n_paths, nc * 4, "download n_paths");
+        if (!own_l2) rc = batch_fetch(rc, lognorm, d_lognorm, nc * 8, "download lognorm");
+        if (rc || !own_l2) return rc;
+    }
+    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, nullptr, lognorm);
     GECCO_GUARD_END
 }
 

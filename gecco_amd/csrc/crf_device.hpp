@@ -345,6 +345,17 @@ hipError_t launch_gen_sample_paths(const GenArgs &a, int32_t n_samples, uint64_t
 hipError_t launch_gen_sample_runs(const GenArgs &a, const int8_t *y, const RunQuery *queries, int32_t n_runs, int32_t n_samples,
                                   int32_t *runs, hipStream_t stream);
 
+// ---- the K best label paths (crf_kbest.hip) ----
+constexpr int32_t kMaxKBest = 32;  // K of one call: a rank fits the low byte of a back-pointer, a list row of LDS 33 doubles
+// the kernel's own workspace: back-pointers, uint16 per (gene, label, rank), and the last (label, rank) per (contig, rank)
+size_t kbest_back_bytes(int64_t n_genes, int32_t L, int32_t k);
+size_t kbest_fin_bytes(int32_t n_contigs, int32_t k);
+// y[g * k + r] = the label of gene g on the contig's rank-r path (gene-major; -1 where no path fills the rank), score[c * k + r]
+// its score (-infinity likewise), n_paths[c] the number of ranks filled, on the lattice of the gl_state launch that ran before it
+// on the same stream with a.state non-null: reads a.state, a.trans and a.contig_ptr
+hipError_t launch_gen_kbest(const GenArgs &a, int32_t k, uint16_t *back, uint16_t *fin, int8_t *y, double *score, int32_t *n_paths,
+                            hipStream_t stream);
+
 // ---- any number of labels: windowed marginals, one label or every label (crf_general_windowed.hip) ----
 // label >= 0: p_out[g] = max over the windows covering g of P_w(y_g = label), clipped at 1 by the tile kernels.
 // label < 0: every label in one pass, p_out[g][l] likewise for all l, and p_any[g] = max over the same windows of the sum of

@@ -384,8 +384,9 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     }
     {
         const char *env = std::getenv("GECCO_CRF_FORCE_GENERAL");
-        // (valued and masked state scores exist in gl_state alone; region posteriors and sampled paths read the any-L workspace)
-        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.spans || p.samples;
+        // (valued and masked state scores exist in gl_state alone; region posteriors, sampled paths and the K best paths read the
+        // any-L workspace)
+        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.spans || p.samples || p.kbest;
     }
     p.fast_ok = (!p.general && W <= kWinMaxW && rescale_mask_for(m, W, &p.rescale_mask));
     {
@@ -1417,6 +1418,32 @@ int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint
     // (a batch's chunked tail has been joined to `stream` by then)
     if ((rc = check_hip(launch_gen_sample_paths(g, n_samples, seed, d_y, stream), "sample launch"))) return rc;
     return check_hip(launch_gen_sample_runs(g, d_y, d_queries, n_runs, n_samples, d_runs, stream), "run launch");
+}
+
+int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d_back, uint16_t *d_fin, int8_t *d_y, double *d_score,
+                           int32_t *d_n_paths, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    SeqArgs a;
+    int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc) return rc;
+    if (!p.kbest || !p.general) {
+        set_error("the plan was not built for the K best paths");
+        return GECCO_CRF_EINVAL;
+    }
+    if (k < 1 || k > kMaxKBest) {
+        set_error("k outside 1 .. 32");
+        return GECCO_CRF_EINVAL;
+    }
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !d_marg || !d_back || !d_fin || !d_y || !d_score || !d_n_paths, rc))
+        return rc;
+    // the marginals recursion as plan_run_marginals_full runs it (log Z: the same launches, the same bits), gl_state also
+    // leaving the raw state scores, as for the region posteriors: the list recursion reads those and nothing else
+    GenRecursion with_state = kGenMarginals;
+    with_state.clear = [](GenArgs &) {};
+    GenArgs g;
+    if ((rc = run_gen_whole(p, with_state, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
+    // (a batch's chunked tail has been joined to `stream` by then)
+    return check_hip(launch_gen_kbest(g, k, d_back, d_fin, d_y, d_score, d_n_paths, stream), "k-best launch");
 }
 
 int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,

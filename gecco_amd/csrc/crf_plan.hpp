@@ -170,6 +170,9 @@ struct Plan {
     // Sampled label paths (plan_run_sample_paths): set by the owner before plan_build, and forces the any-L kernels
     // the way `spans` does -- the sampling kernel reads the same forward vectors.
     bool samples = false;
+    // The K best paths (plan_run_viterbi_kbest): set by the owner before plan_build, and forces the any-L kernels
+    // the way `spans` does -- the list recursion reads gl_state's raw state scores.
+    bool kbest = false;
     bool seq_in_host_memory = false;     // small batches (batch driver's direct path): the whole-contig tables AND the contig flags
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_general_windowed.hip): the tile table of the lane-per-window tier when the plan's own
@@ -224,6 +227,13 @@ int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *
 // sample.  All on `stream`.
 int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint64_t seed, const RunQuery *d_queries, int32_t n_runs,
                           int8_t *d_y, int32_t *d_runs, double *d_marg, double *d_lognorm, hipStream_t stream);
+// The K best label paths of every contig, a plan laid out with `kbest`: the whole-contig marginals of the batch exactly as
+// plan_run_marginals_full runs them (d_marg [n_genes][L], d_lognorm [n_contigs] or null; gl_state also keeps the raw state scores),
+// then the list recursion and its backtrack (crf_kbest.hip): d_y [n_genes][k], d_score [n_contigs][k], d_n_paths [n_contigs].
+// d_back (kbest_back_bytes) and d_fin (kbest_fin_bytes) are the kernel's workspace.  A contig is one sequential walk: not
+// chunked, like the spans' and the samples'.  All on `stream`.
+int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d_back, uint16_t *d_fin, int8_t *d_y, double *d_score,
+                           int32_t *d_n_paths, double *d_marg, double *d_lognorm, hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);
 // returns GECCO_CRF_* ; on HIP failure sets the error text

@@ -399,6 +399,43 @@ class SequenceCRF:
         return self._model.sample_paths(seq_ptr, item_ptr, attr, n_samples, seed=seed, device=self.device, values=values,
                                         allowed=masks, runs=(contig, anchor, mask), want_paths=False)
 
+    @staticmethod
+    def _kbest_count(k) -> int:
+        try:
+            k = operator.index(k)
+        except TypeError:
+            raise ValueError(f"k is an integer, got {k!r}") from None
+        if not 1 <= k <= 32:
+            raise ValueError(f"k = {k} is outside 1 .. 32")
+        return k
+
+    def predict_kbest(self, X, k, allowed=None) -> List[Dict[str, object]]:
+        """The ``k`` best label paths of every sequence with their exact probabilities, on the whole-sequence lattice (that of
+        ``predict`` and ``predict_marginals``, not a windowed one).  Per sequence a dict with ``paths``: a list of label lists,
+        best first, holding only the paths that exist (at most ``k``, and at most the number of label paths of the sequence:
+        ``L ** n_items`` without ``allowed``); ``scores``: their scores, float64, non-increasing; ``log_probabilities``:
+        ``score - log Z``, the exact ``log p(y | x)`` of each path -- not a share of draws, so an alternative of probability 1e-3
+        is reported as such.  ``paths[0]`` is ``predict``'s path.  Among paths of equal score the order is that of the reversed
+        path (last item's label first) in ``classes_`` order, and the first ``k'`` entries of a call with ``k`` are the call
+        with ``k'``.  One forward-backward pass (for ``log Z``) and one list-Viterbi walk over ``X``, one native call.  With
+        ``allowed`` (as in ``predict``) the paths are the best inside the sets and the probabilities are given that the path
+        lies inside them.  A sequence without items has no path: three empty entries.  Raises ``ValueError`` before any device
+        call for a ``k`` that is not an integer or lies outside 1 .. 32."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        k = self._kbest_count(k)
+        n_seqs = len(seq_ptr) - 1
+        if seq_ptr[-1] == 0:
+            return [{"paths": [], "scores": np.zeros(0), "log_probabilities": np.zeros(0)} for _ in range(n_seqs)]
+        y, score, n_paths, lognorm = self._model.viterbi_kbest(seq_ptr, item_ptr, attr, k, device=self.device, values=values,
+                                                               allowed=masks)
+        out = []
+        for s, ys in enumerate(self._split(y, seq_ptr)):
+            m = int(n_paths[s])
+            out.append({"paths": [[self.classes_[c] for c in ys[:, r].tolist()] for r in range(m)],
+                        "scores": score[s, :m].copy(), "log_probabilities": score[s, :m] - lognorm[s]})
+        return out
+
     def _windowed(self) -> None:
         self._fitted()
         if self.window_size is None:

@@ -48,6 +48,24 @@ ones, and ``known=`` restricts the lattice in the same way.  ``clusters.tsv`` th
 ``start_lo``, ``start_hi``, ``end_lo`` and ``end_hi`` behind the region columns; with N = 0 the tables and every launch are
 unchanged.
 
+Alternatives (opt-in: ``alternatives=K``, 1 <= K <= 32, ``predict --alternatives K [--alternatives-margin M]``, M = 10 by default).
+"What are the next-best readings of this region, and how much probability does each carry": for every called cluster the K best
+label paths of its neighbourhood, exactly (``_native.Model.viterbi_kbest``: list Viterbi on the device, one native call for all
+clusters), not a share of draws.  The neighbourhood is the contig's genes [first - M - 1, last + M + 1), clipped to the contig,
+as a short sequence of its own; a copied end gene that is not a contig end is pinned, by a singleton mask, to the label the
+contig's Viterbi path gives it, and ``known=`` masks carry over.  Conditioning a chain on both border labels separates the
+inside from the rest of the contig: the K paths are exactly the K best WHOLE-CONTIG paths among those that agree with the
+Viterbi path outside the neighbourhood, and exp(score - log Z) of the short, masked sequence is each path's probability GIVEN
+that agreement (not its unconditional probability).  Every cluster gets ``alternatives``, a list of dicts, best first:
+``rank``; ``window`` = (first, last + 1), the neighbourhood as gene offsets inside the contig, and ``labels``, the path's label
+names over it; ``run`` = (first, last + 1), contig offsets of the maximal stretch of genes without a background label around
+the cluster's anchor (the anchor of the boundary intervals) on the path spliced into the contig's Viterbi path, or None where
+the anchor's label is the background; ``start`` and ``end``, the run's coordinates (None without a run); ``type``, the
+``";"``-joined types of the run's most frequent label (the smaller label id on ties; ``"Unknown"`` for a label without types,
+None without a run); ``log_p``.  Rank 0 is the Viterbi path's reading.  The command line writes ``alternatives.tsv`` (columns
+``cluster_id, rank, start, end, type, log_p, p``; start, end and type empty without a run); ``clusters.tsv`` is unchanged, and
+without the option the tables and every launch are unchanged.
+
 Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
 ``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
 """
@@ -69,7 +87,8 @@ import numpy as np
 from . import tables
 
 __all__ = ["BACKGROUND", "MIXED", "UNKNOWN", "MAX_CLUSTER_LABELS", "TypedClusterCRF", "cluster_labels", "fold_labels",
-           "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "build_parser", "main"]
+           "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "write_alternatives",
+           "build_parser", "main"]
 
 BACKGROUND = "0"
 MIXED = "Mixed"
@@ -439,15 +458,18 @@ class TypedClusterCRF:
 
     def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                          trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
-                         region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0) -> List[Any]:
+                         region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0, alternatives: int = 0,
+                         alternatives_margin: int = 10) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
         per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, with
         ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities``, and with
         ``boundary_samples > 0`` each with ``anchor_probability``, ``exact_probability``, ``start_interval`` and
-        ``end_interval`` (module docstring)."""
+        ``end_interval``, and with ``alternatives = K > 0`` each with ``alternatives``, the K best readings of its
+        neighbourhood with their exact conditional probabilities (module docstring)."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
                                                pad=pad, known=known, region_posteriors=region_posteriors,
-                                               boundary_samples=boundary_samples, seed=seed)[1]
+                                               boundary_samples=boundary_samples, seed=seed, alternatives=alternatives,
+                                               alternatives_margin=alternatives_margin)[1]
 
     def _region_posteriors(self, batch, allowed, rows: np.ndarray, clusters: List[Any]) -> None:
         """``region_probability`` and ``region_type_probabilities`` of every called cluster (``rows``: the segment kernel's
@@ -499,14 +521,84 @@ class TypedClusterCRF:
             cluster.start_interval = (int(starts[lo]), int(starts[hi]))
             cluster.end_interval = (int(ends[lo]), int(ends[hi]))
 
+    def _alternatives(self, batch, allowed, rows: np.ndarray, clusters: List[Any], annotated: List[Any], p_any: np.ndarray,
+                      k: int, margin: int) -> None:
+        """``alternatives`` of every called cluster (``rows``: the segment kernel's (contig, number, first gene, last gene +
+        1)): the contig's Viterbi path from one native call, then ONE ``viterbi_kbest`` call over all clusters' neighbourhoods,
+        each a short sequence whose copied end genes are pinned to the Viterbi path's labels unless they are contig ends.  The
+        k paths of a neighbourhood are exactly the k best whole-contig paths that agree with the Viterbi path outside it, and
+        ``log_p`` is each path's log-probability given that agreement (module docstring)."""
+        model = self._fitted()
+        L = len(self.classes_)
+        bg = self.classes_.index(self.background)
+        item_ptr = batch.item_ptr.astype(np.int64)
+        attr_ptr = batch.attr_ptr.astype(np.int64)
+        best, _ = model.viterbi(item_ptr.astype(np.int32), attr_ptr.astype(np.int32), batch.attr_id, device=self.device,
+                                want_score=False, allowed=allowed)
+        best = np.asarray(best, dtype=np.int64)
+        every = np.uint32((1 << L) - 1)
+        windows, seq_ptr, rows_ptr, ids, masks = [], [0], [0], [], []
+        for contig, _, first, last in rows.tolist():
+            c0, c1 = int(item_ptr[contig]), int(item_ptr[contig + 1])
+            lo, hi = max(c0, first - margin - 1), min(c1, last + margin + 1)
+            windows.append((c0, c1, lo, hi))
+            seq_ptr.append(seq_ptr[-1] + hi - lo)
+            a0, a1 = int(attr_ptr[lo]), int(attr_ptr[hi])
+            ids.append(batch.attr_id[a0:a1])
+            rows_ptr.extend((attr_ptr[lo + 1:hi + 1] - a0 + rows_ptr[-1]).tolist())
+            m = np.full(hi - lo, every, dtype=np.uint32) if allowed is None else np.array(allowed[lo:hi], dtype=np.uint32)
+            if lo > c0:
+                m[0] = np.uint32(1) << np.uint32(best[lo])
+            if hi < c1:
+                m[-1] = np.uint32(1) << np.uint32(best[hi - 1])
+            masks.append(m)
+        y, score, n_paths, lognorm = model.viterbi_kbest(np.array(seq_ptr, dtype=np.int32), np.array(rows_ptr, dtype=np.int32),
+                                                         np.concatenate(ids).astype(np.int32), k, device=self.device,
+                                                         allowed=np.concatenate(masks))
+        for q, (cluster, (_, _, first, last), (c0, c1, lo, hi)) in enumerate(zip(clusters, rows.tolist(), windows)):
+            anchor = first + int(np.argmax(p_any[first:last]))
+            found = []
+            for r in range(int(n_paths[q])):
+                path = y[seq_ptr[q]:seq_ptr[q + 1], r].astype(np.int64)
+                whole = best[c0:c1].copy()
+                whole[lo - c0:hi - c0] = path
+                entry = {"rank": r, "window": (lo - c0, hi - c0), "labels": [self.classes_[l] for l in path.tolist()],
+                         "run": None, "start": None, "end": None, "type": None, "log_p": float(score[q, r] - lognorm[q])}
+                if whole[anchor - c0] != bg:
+                    a = b = anchor - c0
+                    while a > 0 and whole[a - 1] != bg:
+                        a -= 1
+                    while b + 1 < c1 - c0 and whole[b + 1] != bg:
+                        b += 1
+                    counts = np.bincount(whole[a:b + 1], minlength=L)
+                    entry["run"] = (a, b + 1)
+                    entry["start"], entry["end"] = int(annotated[c0 + a].start), int(annotated[c0 + b].end)
+                    entry["type"] = ";".join(self.label_types_[int(np.argmax(counts))]) or UNKNOWN
+                found.append(entry)
+            cluster.alternatives = found
+
     def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                                    trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                                    region_posteriors: bool = False, boundary_samples: int = 0,
-                                   seed: int = 0) -> Tuple[List[Any], List[Any]]:
+                                   seed: int = 0, alternatives: int = 0,
+                                   alternatives_margin: int = 10) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
         second, whole-contig pass gives every cluster its region posteriors, and with ``boundary_samples = N > 0`` one more
-        draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals (module docstring)."""
+        draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals; with ``alternatives = K >
+        0`` (at most 32) a Viterbi pass and one list-Viterbi call give every cluster the K best readings of its neighbourhood of
+        ``alternatives_margin`` genes on either side (module docstring).  ``ValueError`` before any device call for an option
+        that is not an integer or lies outside its range."""
         from . import _native
+
+        try:
+            alternatives, alternatives_margin = operator.index(alternatives), operator.index(alternatives_margin)
+        except TypeError:
+            raise ValueError(f"alternatives and alternatives_margin are integers, got {alternatives!r} and "
+                             f"{alternatives_margin!r}") from None
+        if not 0 <= alternatives <= 32:
+            raise ValueError(f"alternatives = {alternatives} is outside 0 .. 32")
+        if alternatives_margin < 0:
+            raise ValueError(f"alternatives_margin = {alternatives_margin} is negative")
 
         try:
             boundary_samples, seed = operator.index(boundary_samples), operator.index(seed)
@@ -540,7 +632,22 @@ class TypedClusterCRF:
         if boundary_samples > 0 and clusters:
             self._boundary_intervals(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters, annotated, p_any,
                                      boundary_samples, seed)
+        if alternatives > 0 and clusters:
+            self._alternatives(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters, annotated, p_any,
+                               alternatives, alternatives_margin)
         return annotated, clusters
+
+
+def write_alternatives(path, clusters: Sequence[Any]) -> None:
+    """``alternatives.tsv``: one row per called cluster and rank, columns ``cluster_id, rank, start, end, type, log_p, p``
+    (start, end and type empty where the path has no run around the cluster's anchor); floats with ``repr``."""
+    with open(path, "w") as out:
+        out.write("\t".join(("cluster_id", "rank", "start", "end", "type", "log_p", "p")) + "\n")
+        for cluster in clusters:
+            for alt in getattr(cluster, "alternatives", ()):
+                run = alt["run"] is not None
+                where = (str(alt["start"]), str(alt["end"]), alt["type"]) if run else ("", "", "")
+                out.write("\t".join((str(cluster.id), str(alt["rank"]), *where, repr(alt["log_p"]), repr(math.exp(alt["log_p"])))) + "\n")
 
 
 # ---------------------------------------------------------------------------------------------- command line
@@ -587,6 +694,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="add anchor_p, exact_p, start_lo, start_hi, end_lo and end_hi to clusters.tsv: 90 %% intervals of every "
                     "called region's start and end from N label paths drawn from the whole-contig posterior")
     pr.add_argument("--seed", type=int, default=0, help="seed of the drawn paths (with --boundary-samples)")
+    pr.add_argument("--alternatives", type=int, default=0, metavar="K",
+                    help="write alternatives.tsv: for every called region the K (at most 32) best label paths of its neighbourhood, "
+                    "each with its exact probability given that the rest of the contig follows the Viterbi path")
+    pr.add_argument("--alternatives-margin", type=int, default=10, metavar="M",
+                    help="genes on either side of a called region in its neighbourhood (with --alternatives)")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -614,11 +726,15 @@ def main(argv: Optional[List[str]] = None) -> int:
                                                       edge_distance=args.edge_distance, trim=args.trim, pad=args.pad,
                                                       known=None if args.known is None else tables.ClusterTable.load(args.known),
                                                       region_posteriors=args.region_posteriors,
-                                                      boundary_samples=args.boundary_samples, seed=args.seed)
+                                                      boundary_samples=args.boundary_samples, seed=args.seed,
+                                                      alternatives=args.alternatives,
+                                                      alternatives_margin=args.alternatives_margin)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))
     typed_cluster_table(found, crf.types_).dump(os.path.join(args.output_dir, "clusters.tsv"))
+    if args.alternatives > 0:
+        write_alternatives(os.path.join(args.output_dir, "alternatives.tsv"), found)
     print(f"predict: {len(annotated)} genes, {len(found)} clusters -> {args.output_dir}", file=sys.stderr)
     return 0
 

@@ -50,7 +50,8 @@ typedef struct gecco_crf_plan gecco_crf_plan;
 const char *gecco_crf_last_error(void);
 /* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
- * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths. */
+ * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
+ * gecco_crf_viterbi_kbest. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -793,6 +794,43 @@ int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, const int32
                            const int32_t *run_contig, const int32_t *run_anchor, const uint32_t *run_mask, int32_t n_runs,
                            int8_t *y /* [n_genes][n_samples] or NULL */, int32_t *runs /* [n_runs][n_samples][2], NULL iff n_runs == 0 */,
                            double *marg /* [n_genes][L] or NULL */, double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- the K best label paths with exact path scores (ABI 2.18.0, additive; gecco_crf_version() stays 340) ------------------------
+ * y[g * k + r] = the label of gene g on the rank-r path of its contig, score[c * k + r] that path's score, n_paths[c] how many
+ * ranks of contig c a path fills: the k highest-scoring label paths of every contig, in order, on the whole-contig lattice of
+ * gecco_crf_viterbi and gecco_crf_marginals_full (not a windowed one).  exp(score - lognorm[c]) is a path's probability
+ * p(y | x), exactly (not a share of draws).  With `allowed` (one mask per gene, as the *_constrained entries take them) the
+ * lattice is the restricted one: no path carries a disallowed label, and lognorm is the restricted log Z.  attr_value and allowed
+ * may each be NULL.  The walk is parallel over contigs and labels and sequential along a contig (contigs are not chunked).
+ *   * The recursion.  For every (gene t, label j) the k best prefix scores in order, delta_t[j][0 .. k):
+ *     delta_0[j] = [state_0[j]], and delta_t[j] holds the k best of (delta_{t-1}[i][r] + trans[i][j]) + state_t[j] over the
+ *     source label i and the source rank r -- the operation order of gecco_crf_viterbi, so a path's score is the left-to-right
+ *     sum of its terms, every addition rounded on its own.  Every source list is sorted: a step is an L-way merge that stops
+ *     after k outputs.
+ *   * The order is total.  Greater score first; among equal scores the smaller source label i, then the smaller source rank r;
+ *     at the end of the contig the L final lists merge by the same rule (smaller last label, then smaller rank).  In exact
+ *     arithmetic that is "score descending, then the reversed path (y_{T-1}, ..., y_0) ascending lexicographically".  Rank 0 is
+ *     the path gecco_crf_viterbi (or its _valued / _constrained sibling) returns.
+ *   * Empty ranks.  A candidate whose score is -infinity (a disallowed label on it) does not exist and is never emitted.  A rank
+ *     that no path fills -- a contig of T genes has at most the product of its genes' allowed-label counts, L^T without masks --
+ *     has score -infinity and label -1 at every gene of the contig; the filled ranks are 0 .. n_paths[c] - 1.
+ *   * The prefix property.  The order is total and merges preserve it: rank r of a call with k' < k is rank r of the call with
+ *     k, labels and score byte for byte.
+ *   * Outputs.  y is int8 [n_genes][k], gene-major; score is double [n_contigs][k]; n_paths is int32 [n_contigs].  lognorm
+ *     [n_contigs], optional, is the bytes gecco_crf_marginals_full (or its _valued / _constrained sibling, by the arguments
+ *     given) writes for the batch.  (A 2-label model without values and masks has kernels of its own for that: asking for
+ *     lognorm there costs a second pass.)  A contig without genes gets n_paths = 0, scores -infinity and lognorm 0.
+ *     contig_ptr[0] > 0 works as in the other one-shots.  The back-pointers are workspace of n_genes * L * k * 2 bytes; sizes
+ *     are computed in size_t; a failed allocation is GECCO_CRF_ENOMEM.
+ *   * Limits: 1 <= k <= 32 and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL: k outside 1 .. 32 ("viterbi_kbest: k = ... is
+ *     outside 1 .. 32").  The checks of the *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                            const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                            const uint32_t *allowed /* NULL: no masks */, int32_t k, int8_t *y /* [n_genes][k] */,
+                            double *score /* [n_contigs][k] */, int32_t *n_paths /* [n_contigs] */,
+                            double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
