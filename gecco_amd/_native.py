@@ -560,33 +560,43 @@ class Model:
     # ``allowed=``: one uint32 per gene, bit y set when the gene may take label y (the trainers' masks): the call is the same
     # call on the lattice without the disallowed (gene, label) pairs, and takes the ``*_constrained`` entry, with ``values``
     # or without.  None: today's call, bit for bit.
+    def _csr_head(self, contig_ptr, gene_ptr, attr_id, values, allowed, device):
+        """A batch's CSR arrays as every one-shot entry takes them: ``(head, values, allowed, n, n0, nc)``.  ``head`` is the
+        start of the entry's argument list (handle, device, ``contig_ptr``, the number of contigs ``nc``, ``gene_ptr``,
+        ``attr_id``); ``values`` and ``allowed`` are the pointers of the checked arrays, None where the argument is (a pointer
+        keeps its array alive).  The batch's genes are ``n0 .. n - 1``."""
+        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
+        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
+        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
+        if values is not None:
+            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
+            if values.size != attr_id.size:
+                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
+            values = _ptr(values if values.size else np.zeros(1, dtype=np.float64), _c_f64p)
+        if attr_id.size == 0:
+            attr_id = np.zeros(1, dtype=np.int32)
+        if allowed is not None:
+            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
+            if allowed.size != n:
+                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
+            allowed = _ptr(allowed if allowed.size else np.zeros(1, dtype=np.uint32), _c_u32p)
+        head = [self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p)]
+        return head, values, allowed, n, n0, nc
+
     def _oneshot(self, name, contig_ptr, gene_ptr, attr_id, values, device, allowed=None):
         """The CSR arguments of the one-shot entry ``name``, or of ``name + "_valued"`` when ``values`` are given (their
         pointer goes in behind ``attr_id``'s), or of ``name + "_constrained"`` when ``allowed`` is (the values' pointer, or
         NULL, then the masks').  Returns ``(n_genes, n_contigs, run)``; ``run(*tail)`` calls the entry with the arguments
         that follow the CSR arrays."""
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
-        if values is not None:
-            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-            if values.size != attr_id.size:
-                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
-            values = values if values.size else np.zeros(1, dtype=np.float64)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        head = [self._h, device, _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p)]
+        head, values, allowed, n, _, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, device)
         if allowed is not None:
-            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
-            if allowed.size != n:
-                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
-            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
-            head += [None if values is None else _ptr(values, _c_f64p), _ptr(allowed, _c_u32p)]
-            entry = getattr(self._lib, name + "_constrained")
-            return n, nc, lambda *tail: _check(entry(*head, *tail))
-        if values is not None:
-            head.append(_ptr(values, _c_f64p))
-        entry = getattr(self._lib, name if values is None else name + "_valued")
-        return n, nc, lambda *tail: _check(entry(*head, *tail))  # (`head` keeps the arrays alive)
+            head += [values, allowed]
+            name += "_constrained"
+        elif values is not None:
+            head.append(values)
+            name += "_valued"
+        entry = getattr(self._lib, name)
+        return n, nc, lambda *tail: _check(entry(*head, *tail))
 
     def windowed_marginals(self, contig_ptr, gene_ptr, attr_id, window, step=1, label=1, pad=True, device=0, values=None,
                            allowed=None):
@@ -633,21 +643,7 @@ class Model:
         ``allowed`` the lattice is the restricted one.  Returns ``logp`` (float64, <= 0, ``-inf`` for probability zero), or
         with ``want_marginals`` ``(logp, marginals [n, L], log Z [n_contigs])``, the latter two as ``marginals_full`` gives
         them."""
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
-        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
-        if values is not None:
-            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-            if values.size != attr_id.size:
-                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
-            values = values if values.size else np.zeros(1, dtype=np.float64)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        if allowed is not None:
-            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
-            if allowed.size != n:
-                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
-            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
         sc, sb, se = _i32(span_contig).ravel(), _i32(span_begin).ravel(), _i32(span_end).ravel()
         sm = np.ascontiguousarray(span_mask, dtype=np.uint32).ravel()
         ns = sc.size
@@ -658,10 +654,8 @@ class Model:
         marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
         ln = np.zeros(max(nc, 1), dtype=np.float64) if want_marginals else None
         _check(self._lib.gecco_crf_span_probabilities(
-            self._h, int(device), _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
-            None if values is None else _ptr(values, _c_f64p), None if allowed is None else _ptr(allowed, _c_u32p),
-            _ptr(sc if ns else pad_i, _c_i32p), _ptr(sb if ns else pad_i, _c_i32p), _ptr(se if ns else pad_i, _c_i32p),
-            _ptr(sm if ns else pad_u, _c_u32p), ns, _ptr(logp, _c_f64p),
+            *head, values, allowed, _ptr(sc if ns else pad_i, _c_i32p), _ptr(sb if ns else pad_i, _c_i32p),
+            _ptr(se if ns else pad_i, _c_i32p), _ptr(sm if ns else pad_u, _c_u32p), ns, _ptr(logp, _c_f64p),
             None if marg is None else _ptr(marg, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
         if want_marginals:
             return logp[:ns], marg[:n - n0], ln[:nc]
@@ -680,24 +674,10 @@ class Model:
         With ``want_marginals`` also ``marginals [n, L], log Z [n_contigs]`` as ``marginals_full`` gives them.  Returns ``y``,
         or a tuple ``(y[, runs][, marginals, log Z])``.  ``want_paths=False`` passes ``y = NULL``: the paths stay in device
         workspace, serve the runs, and ``y`` is left out of what is returned (None when nothing else was asked for)."""
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
-        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
         n_samples, seed = operator.index(n_samples), operator.index(seed)
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed {seed} is outside 0 .. 2**64 - 1")
-        if values is not None:
-            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-            if values.size != attr_id.size:
-                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
-            values = values if values.size else np.zeros(1, dtype=np.float64)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        if allowed is not None:
-            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
-            if allowed.size != n:
-                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
-            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
         nr = 0
         if runs is not None:
             rc, ra = _i32(runs[0]).ravel(), _i32(runs[1]).ravel()
@@ -711,8 +691,7 @@ class Model:
         marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
         ln = np.zeros(max(nc, 1), dtype=np.float64) if want_marginals else None
         _check(self._lib.gecco_crf_sample_paths(
-            self._h, int(device), _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
-            None if values is None else _ptr(values, _c_f64p), None if allowed is None else _ptr(allowed, _c_u32p), n_samples, seed,
+            *head, values, allowed, n_samples, seed,
             _ptr(rc, _c_i32p) if nr else None, _ptr(ra, _c_i32p) if nr else None, _ptr(rm, _c_u32p) if nr else None, nr,
             None if y is None else _ptr(y, _c_i8p), _ptr(out_runs, _c_i32p) if nr else None,
             None if marg is None else _ptr(marg, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
@@ -732,31 +711,15 @@ class Model:
         scores are ordered by the reversed path (last gene's label first); rank r does not depend on ``k``; rank 0 is
         ``viterbi``'s path.  ``values`` and ``allowed`` as in ``marginals_full``: with ``allowed`` no path carries a disallowed
         label.  A contig without genes has ``n_paths`` 0, scores ``-inf`` and ``lognorm`` 0."""
-        contig_ptr, gene_ptr, attr_id = _i32(contig_ptr), _i32(gene_ptr), _i32(attr_id)
-        n, nc = (int(contig_ptr[-1]) if len(contig_ptr) else 0), max(len(contig_ptr) - 1, 0)
-        n0 = int(contig_ptr[0]) if len(contig_ptr) else 0
         k = operator.index(k)
-        if values is not None:
-            values = np.ascontiguousarray(values, dtype=np.float64).ravel()
-            if values.size != attr_id.size:
-                raise ValueError(f"values holds {values.size} entries, attr_id {attr_id.size}")
-            values = values if values.size else np.zeros(1, dtype=np.float64)
-        if attr_id.size == 0:
-            attr_id = np.zeros(1, dtype=np.int32)
-        if allowed is not None:
-            allowed = np.ascontiguousarray(allowed, dtype=np.uint32).ravel()
-            if allowed.size != n:
-                raise ValueError(f"allowed holds {allowed.size} masks for {n} genes")
-            allowed = allowed if allowed.size else np.zeros(1, dtype=np.uint32)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
         kk = k if 1 <= k <= 32 else 1  # (the library refuses any other k: the buffers only need a size)
         y = np.zeros((max(n - n0, 1), kk), dtype=np.int8)
         score = np.zeros((max(nc, 1), kk), dtype=np.float64)
         n_paths = np.zeros(max(nc, 1), dtype=np.int32)
         ln = np.zeros(max(nc, 1), dtype=np.float64)
         _check(self._lib.gecco_crf_viterbi_kbest(
-            self._h, int(device), _ptr(contig_ptr, _c_i32p), nc, _ptr(gene_ptr, _c_i32p), _ptr(attr_id, _c_i32p),
-            None if values is None else _ptr(values, _c_f64p), None if allowed is None else _ptr(allowed, _c_u32p), k,
-            _ptr(y, _c_i8p), _ptr(score, _c_f64p), _ptr(n_paths, _c_i32p), _ptr(ln, _c_f64p)))
+            *head, values, allowed, k, _ptr(y, _c_i8p), _ptr(score, _c_f64p), _ptr(n_paths, _c_i32p), _ptr(ln, _c_f64p)))
         return y[:n - n0], score[:nc], n_paths[:nc], ln[:nc]
 
 

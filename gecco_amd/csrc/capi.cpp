@@ -714,6 +714,29 @@ int check_output(const int32_t *contig_ptr, int32_t n_contigs, const void *out) 
     return n_contigs > 0 && contig_ptr && contig_ptr[n_contigs] > contig_ptr[0] && !out ? fail("null buffer") : GECCO_CRF_OK;
 }
 
+int check_contig_ptr(const int32_t *contig_ptr, int32_t n_contigs) {
+    return n_contigs < 0 || (n_contigs > 0 && !contig_ptr) ? fail("bad contig_ptr") : GECCO_CRF_OK;
+}
+uint32_t bits_beyond(int32_t L) { return L >= 32 ? 0u : ~0u << L; }  // the mask bits at or above L
+
+// The checks of query q of a lattice call (`kind`: "span", "run"; a message starts with "span 3: "): its contig, whose length comes
+// back for the entry's own range check, and its label set.  A call may bring ten thousand queries: the text is put together for
+// a refusal only.
+std::string query_name(const char *kind, int32_t q) { return std::string(kind) + " " + std::to_string(q) + ": "; }
+int check_query_contig(const char *kind, int32_t q, int32_t c, int32_t n_contigs, const int32_t *contig_ptr, int64_t *len) {
+    if (c < 0 || c >= n_contigs)
+        return fail(query_name(kind, q) + "contig " + std::to_string(c) + " out of range (the batch has " + std::to_string(n_contigs) + ")");
+    *len = int64_t(contig_ptr[c + 1]) - contig_ptr[c];
+    return GECCO_CRF_OK;
+}
+int check_label_set(const char *kind, int32_t q, uint32_t mask, int32_t L) {
+    if (mask == 0) return fail(query_name(kind, q) + "the label set is empty (a mask of 0)");
+    if (mask & bits_beyond(L))
+        return fail(query_name(kind, q) + "the set holds a label at or above num_labels = " + std::to_string(L) + " (mask " +
+                    std::to_string(mask) + ")");
+    return GECCO_CRF_OK;
+}
+
 // The host checks of the CSR arrays (before any device work), the plan, and the upload.  `valued`: the plan takes the any-L
 // kernels at every label count and attr_value holds a finite value per attribute entry; otherwise attr_value is not read.
 // `masked` (the *_constrained entries): `allowed` holds one mask per gene, indexed like the rows of gene_ptr (gene g of the caller's
@@ -723,7 +746,8 @@ int check_output(const int32_t *contig_ptr, int32_t n_contigs, const void *out) 
 int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
                const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int32_t window,
                int32_t step, int32_t pad, bool windowed, const size_t per_gene[2], size_t per_contig, ResidentBatch &b) {
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    int rc = check_contig_ptr(contig_ptr, n_contigs);
+    if (rc) return rc;
     const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
     if (n > 0 && !gene_ptr) return fail("null buffer");
     const int32_t *gp = n > 0 ? gene_ptr + contig_ptr[0] : nullptr;
@@ -743,17 +767,15 @@ int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_p
     if (masked && n > 0) {
         if (!allowed) return fail("null allowed with genes (one mask of allowed labels per gene)");
         const int32_t L = m->m.L;
-        const uint32_t beyond = L >= 32 ? 0u : ~0u << L;  // the bits at or above L
         for (int64_t i = 0; i < n; ++i) {
             const int64_t g = int64_t(contig_ptr[0]) + i;
             if (allowed[g] == 0) return fail("constrained: gene " + std::to_string(g) + " allows no label (a mask of 0)");
-            if (allowed[g] & beyond)
+            if (allowed[g] & bits_beyond(L))
                 return fail("constrained: gene " + std::to_string(g) + " allows a label at or above num_labels = " + std::to_string(L) +
                             " (mask " + std::to_string(allowed[g]) + ")");
         }
     }
-    int rc = check_device(device);
-    if (rc) return rc;
+    if ((rc = check_device(device))) return rc;
     b.plan.valued = valued;
     b.plan.masked = masked;
     b.plan.windowed_use = windowed;
@@ -955,8 +977,8 @@ GECCO_API int gecco_crf_viterbi_constrained(const gecco_crf_model *m, int32_t de
 }
 
 namespace {
-// gecco_crf_marginals_full for the one-shots below, whose plain 2-label models ask that entry's own kernels for marg / lognorm in a
-// second pass.  That entry takes batches that start at gene 0: a slice is rebased for it, rows and attribute entries alike.
+// gecco_crf_marginals_full for LatticeCall::finish.  That entry takes batches that start at gene 0: a slice is rebased for it, rows
+// and attribute entries alike.
 int marginals_full_of_slice(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
                             const int32_t *gene_ptr, const int32_t *attr_id, double *marg, double *lognorm) {
     if (contig_ptr[0] == 0) return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
@@ -965,6 +987,41 @@ int marginals_full_of_slice(const gecco_crf_model *m, int32_t device, const int3
     for (size_t c = 0; c < contigs.size(); ++c) contigs[c] = contig_ptr[c] - g0;
     for (size_t i = 0; i < rows.size(); ++i) rows[i] = gene_ptr[size_t(g0) + i] - a0;
     return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
+}
+
+// One call of a lattice query -- region posteriors, sampled paths, the K best paths.  The batch goes to the device on a plan laid
+// out with `lattice`: the marginals at out(0), per_gene1 bytes a gene at out(1), log Z and then per_contig_more bytes a contig at
+// out(2).  `run(b)` is the entry's part: its plan_run_* call and the fetch of its own outputs; of a batch without genes (b.n == 0:
+// nothing is on the device, and log Z = 0 is written by then) it only fills what else the entry returns.  marg / lognorm (either
+// may be null) are the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one exception:
+// a 2-label model without values and masks has kernels of its own there (own_l2), which are asked in a second pass once the batch
+// has left the device.
+template <class Run>
+int lattice_call(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                 const int32_t *attr_id, const double *attr_value, const uint32_t *allowed, size_t per_gene1, size_t per_contig_more,
+                 double *marg, double *lognorm, Run run) {
+    const size_t L = size_t(m->m.L);
+    const bool own_l2 = L == 2 && !attr_value && !allowed && (marg || lognorm);
+    {
+        ResidentBatch b;
+        b.plan.lattice = true;
+        const size_t per_gene[2] = {L * 8, per_gene1};
+        int rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, attr_value != nullptr, allowed,
+                            allowed != nullptr, 1, 1, 1, false, per_gene, 8 + per_contig_more, b);
+        for (int32_t c = 0; !rc && b.n == 0 && lognorm && c < n_contigs; ++c) lognorm[c] = 0.0;
+        if (!rc) rc = run(b);
+        if (rc || b.n == 0) return rc;
+        if (!own_l2) {
+            rc = batch_fetch(rc, marg, b.out<double>(0), size_t(b.n) * L * 8, "download marginals");
+            return batch_fetch(rc, lognorm, b.out<double>(2), size_t(n_contigs) * 8, "download lognorm");
+        }
+    }
+    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+}
+// the device block of an entry's queries: `total` bytes, the `bytes` of `host` at its head
+int upload_queries(DevBuf<char> &q, const void *host, size_t bytes, size_t total, const char *what_alloc, const char *what_copy) {
+    const int rc = q.alloc(total, what_alloc);
+    return rc ? rc : check_hip(hipMemcpy(q.p, host, bytes, hipMemcpyHostToDevice), what_copy);
 }
 }  // namespace
 
@@ -978,62 +1035,40 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
     if (!m) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    const bool valued = attr_value != nullptr, masked = allowed != nullptr;
-    const int32_t L = m->m.L;
+    int rc;
     // the checks of the spans, on the host and before any device work
     if (n_spans < 0) return fail("span_probabilities: negative number of spans");
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
     if (n_spans > 0 && (!span_contig || !span_begin || !span_end || !span_mask || !logp)) return fail("null buffer");
     std::vector<SpanQuery> spans(static_cast<size_t>(n_spans));
-    const uint32_t beyond = L >= 32 ? 0u : ~0u << L;  // the bits at or above L
     for (int32_t q = 0; q < n_spans; ++q) {
-        const std::string who = "span " + std::to_string(q);
         const int32_t c = span_contig[q], b = span_begin[q], e = span_end[q];
-        if (c < 0 || c >= n_contigs)
-            return fail(who + ": contig " + std::to_string(c) + " out of range (the batch has " + std::to_string(n_contigs) + ")");
-        const int64_t len = int64_t(contig_ptr[c + 1]) - contig_ptr[c];
+        int64_t len;
+        if ((rc = check_query_contig("span", q, c, n_contigs, contig_ptr, &len))) return rc;
         if (b < 0 || b >= e || e > len)
-            return fail(who + ": [" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
+            return fail(query_name("span", q) + "[" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
                         std::to_string(c) + " of " + std::to_string(len) + " genes");
-        if (span_mask[q] == 0) return fail(who + ": the label set is empty (a mask of 0)");
-        if (span_mask[q] & beyond)
-            return fail(who + ": the set holds a label at or above num_labels = " + std::to_string(L) + " (mask " +
-                        std::to_string(span_mask[q]) + ")");
+        if ((rc = check_label_set("span", q, span_mask[q], m->m.L))) return rc;
         spans[size_t(q)] = SpanQuery{c, b, e, span_mask[q]};
     }
     // without spans the call is the whole-contig marginals' own
     if (n_spans == 0) {
-        if (masked) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
-        if (valued) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
+        if (allowed) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
+        if (attr_value) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
         return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
     }
-    // marg and lognorm are the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one
-    // exception: a 2-label model without values and masks has kernels of its own there, which this call then asks in a second pass
-    const bool own_l2 = L == 2 && !valued && !masked && (marg || lognorm);
-    int rc;
-    {
-        ResidentBatch b;
-        b.plan.spans = true;
-        const size_t per_gene[2] = {size_t(L) * 8, 0};
-        rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false, per_gene,
-                        8, b);
-        if (rc) return rc;  // (b.n == 0 cannot be: a checked span lies inside a contig with genes)
+    // (a batch without genes cannot be: a checked span lies inside a contig with genes)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
         DevBuf<char> q;
         const size_t b_spans = align256(size_t(n_spans) * sizeof(SpanQuery));
-        if ((rc = q.alloc(b_spans + size_t(n_spans) * 8, "hipMalloc spans"))) return rc;
-        if ((rc = check_hip(hipMemcpy(q.p, spans.data(), size_t(n_spans) * sizeof(SpanQuery), hipMemcpyHostToDevice), "upload spans")))
-            return rc;
+        int rc = upload_queries(q, spans.data(), size_t(n_spans) * sizeof(SpanQuery), b_spans + size_t(n_spans) * 8, "hipMalloc spans",
+                                "upload spans");
+        if (rc) return rc;
         double *d_logp = reinterpret_cast<double *>(q.p + b_spans);
         rc = batch_wait(plan_run_span_probabilities(b.plan, b.csr, reinterpret_cast<const SpanQuery *>(q.p), n_spans, d_logp,
                                                     b.out<double>(0), b.out<double>(2), nullptr), "span probabilities");
-        rc = batch_fetch(rc, logp, d_logp, size_t(n_spans) * 8, "download logp");
-        if (!own_l2) {
-            rc = batch_fetch(rc, marg, b.out<double>(0), size_t(b.n) * size_t(L) * 8, "download marginals");
-            rc = batch_fetch(rc, lognorm, b.out<double>(2), size_t(n_contigs) * 8, "download lognorm");
-        }
-        if (rc || !own_l2) return rc;
-    }
-    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+        return batch_fetch(rc, logp, d_logp, size_t(n_spans) * 8, "download logp");
+    });
     GECCO_GUARD_END
 }
 
@@ -1047,64 +1082,39 @@ GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, c
     if (!m) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    const bool valued = attr_value != nullptr, masked = allowed != nullptr;
-    const int32_t L = m->m.L;
+    int rc;
     // the checks of the call's own arguments, on the host and before any device work
     if (n_samples < 1 || n_samples > kMaxSamples)
         return fail("sample_paths: n_samples = " + std::to_string(n_samples) + " is outside 1 .. 1048576");
     if (n_runs < 0) return fail("sample_paths: negative n_runs");
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
     if (n_runs > 0 && (!run_contig || !run_anchor || !run_mask || !runs)) return fail("null buffer");
     std::vector<RunQuery> queries(static_cast<size_t>(n_runs));
-    const uint32_t beyond = L >= 32 ? 0u : ~0u << L;  // the bits at or above L
     for (int32_t q = 0; q < n_runs; ++q) {
-        const std::string who = "run " + std::to_string(q);
         const int32_t c = run_contig[q], t = run_anchor[q];
-        if (c < 0 || c >= n_contigs)
-            return fail(who + ": contig " + std::to_string(c) + " out of range (the batch has " + std::to_string(n_contigs) + ")");
-        const int64_t len = int64_t(contig_ptr[c + 1]) - contig_ptr[c];
+        int64_t len;
+        if ((rc = check_query_contig("run", q, c, n_contigs, contig_ptr, &len))) return rc;
         if (t < 0 || t >= len)
-            return fail(who + ": anchor " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
+            return fail(query_name("run", q) + "anchor " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
                         std::to_string(len) + " genes");
-        if (run_mask[q] == 0) return fail(who + ": the label set is empty (a mask of 0)");
-        if (run_mask[q] & beyond)
-            return fail(who + ": the set holds a label at or above num_labels = " + std::to_string(L) + " (mask " +
-                        std::to_string(run_mask[q]) + ")");
+        if ((rc = check_label_set("run", q, run_mask[q], m->m.L))) return rc;
         queries[size_t(q)] = RunQuery{c, t, run_mask[q]};
     }
-    // marg and lognorm are the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one
-    // exception: a 2-label model without values and masks has kernels of its own there, which this call then asks in a second pass
-    const bool own_l2 = L == 2 && !valued && !masked && (marg || lognorm);
-    int rc;
-    {
-        ResidentBatch b;
-        b.plan.samples = true;
-        const size_t per_gene[2] = {size_t(L) * 8, size_t(n_samples)};  // marginals; the paths, which need no caller's buffer
-        rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false, per_gene,
-                        8, b);
-        if (rc || b.n == 0) {  // (no genes: no labels, no run -- a checked run lies inside a contig with genes)
-            for (int32_t c = 0; !rc && lognorm && c < n_contigs; ++c) lognorm[c] = 0.0;
-            return rc;
-        }
+    // per gene: the paths, which need no caller's buffer
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, size_t(n_samples), 0, marg, lognorm,
+                        [&](ResidentBatch &b) {
+        if (b.n == 0) return int(GECCO_CRF_OK);  // (no labels, no run: a checked run lies inside a contig with genes)
         DevBuf<char> q;
         const size_t b_queries = align256(size_t(n_runs) * sizeof(RunQuery)), b_runs = size_t(n_runs) * size_t(n_samples) * 8;
-        if (n_runs > 0) {
-            if ((rc = q.alloc(b_queries + b_runs, "hipMalloc runs"))) return rc;
-            if ((rc = check_hip(hipMemcpy(q.p, queries.data(), size_t(n_runs) * sizeof(RunQuery), hipMemcpyHostToDevice), "upload runs")))
-                return rc;
-        }
+        int rc = n_runs > 0 ? upload_queries(q, queries.data(), size_t(n_runs) * sizeof(RunQuery), b_queries + b_runs, "hipMalloc runs",
+                                             "upload runs") : GECCO_CRF_OK;
+        if (rc) return rc;
         int32_t *d_runs = n_runs > 0 ? reinterpret_cast<int32_t *>(q.p + b_queries) : nullptr;
         rc = batch_wait(plan_run_sample_paths(b.plan, b.csr, n_samples, seed, reinterpret_cast<const RunQuery *>(q.p), n_runs,
                                               b.out<int8_t>(1), d_runs, b.out<double>(0), b.out<double>(2), nullptr), "sampled paths");
         rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * size_t(n_samples), "download paths");
-        rc = batch_fetch(rc, runs, d_runs, b_runs, "download runs");
-        if (!own_l2) {
-            rc = batch_fetch(rc, marg, b.out<double>(0), size_t(b.n) * size_t(L) * 8, "download marginals");
-            rc = batch_fetch(rc, lognorm, b.out<double>(2), size_t(n_contigs) * 8, "download lognorm");
-        }
-        if (rc || !own_l2) return rc;
-    }
-    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+        return batch_fetch(rc, runs, d_runs, b_runs, "download runs");
+    });
     GECCO_GUARD_END
 }
 
@@ -1117,48 +1127,37 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
     if (!m) return GECCO_CRF_EINVAL;
     DeviceGuard guard;
     GECCO_GUARD_BEGIN
-    const bool valued = attr_value != nullptr, masked = allowed != nullptr;
-    const int32_t L = m->m.L;
+    int rc;
     // the check of the call's own argument, on the host and before any device work
     if (k < 1 || k > kMaxKBest) return fail("viterbi_kbest: k = " + std::to_string(k) + " is outside 1 .. 32");
-    if (n_contigs < 0 || (n_contigs > 0 && !contig_ptr)) return fail("bad contig_ptr");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
     if (n_contigs > 0 && (!score || !n_paths)) return fail("null buffer");
-    int rc;
     if ((rc = check_output(contig_ptr, n_contigs, y))) return rc;
-    // lognorm is the bytes of the marginals entry of the same kind.  That entry runs the any-L kernels too, with one exception: a
-    // 2-label model without values and masks has kernels of its own there, which this call then asks in a second pass
-    const bool own_l2 = L == 2 && !valued && !masked && lognorm;
-    {
-        ResidentBatch b;
-        b.plan.kbest = true;
-        const size_t K = size_t(k), nc = size_t(n_contigs);
-        // per gene: marginals (the pass's own output; not returned), the paths.  Per contig: log Z, k scores, the number of paths
-        const size_t per_gene[2] = {size_t(L) * 8, K};
-        rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, valued, allowed, masked, 1, 1, 1, false,
-                        per_gene, 8 + K * 8 + 4, b);
-        if (rc || b.n == 0) {  // (no genes: no path anywhere)
-            for (size_t c = 0; !rc && c < nc; ++c) {
-                if (lognorm) lognorm[c] = 0.0;
+    const size_t K = size_t(k), nc = size_t(n_contigs);
+    // per gene: the paths.  Per contig, behind log Z: k scores, the number of paths.  (The marginals are the pass's own output and
+    // are not returned.)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, K, K * 8 + 4, nullptr, lognorm,
+                        [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: no path anywhere)
+            for (size_t c = 0; c < nc; ++c) {
                 n_paths[c] = 0;
                 for (size_t r = 0; r < K; ++r) score[c * K + r] = -std::numeric_limits<double>::infinity();
             }
-            return rc;
+            return int(GECCO_CRF_OK);
         }
         double *d_lognorm = b.out<double>(2), *d_score = d_lognorm + nc;
         int32_t *d_n_paths = reinterpret_cast<int32_t *>(d_score + nc * K);
         DevBuf<char> ws;
-        const size_t b_back = align256(kbest_back_bytes(b.n, L, k)), b_fin = kbest_fin_bytes(n_contigs, k);
-        if ((rc = ws.alloc(b_back + b_fin, "hipMalloc k-best back-pointers"))) return rc;
+        const size_t b_back = align256(kbest_back_bytes(b.n, m->m.L, k)), b_fin = kbest_fin_bytes(n_contigs, k);
+        int rc = ws.alloc(b_back + b_fin, "hipMalloc k-best back-pointers");
+        if (rc) return rc;
         uint16_t *d_back = reinterpret_cast<uint16_t *>(ws.p), *d_fin = reinterpret_cast<uint16_t *>(ws.p + b_back);
         rc = batch_wait(plan_run_viterbi_kbest(b.plan, b.csr, k, d_back, d_fin, b.out<int8_t>(1), d_score, d_n_paths, b.out<double>(0),
                                                d_lognorm, nullptr), "k-best paths");
         rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * K, "download paths");
         rc = batch_fetch(rc, score, d_score, nc * K * 8, "download scores");
-        rc = batch_fetch(rc, n_paths, d_n_paths, nc * 4, "download n_paths");
-        if (!own_l2) rc = batch_fetch(rc, lognorm, d_lognorm, nc * 8, "download lognorm");
-        if (rc || !own_l2) return rc;
-    }
-    return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, nullptr, lognorm);
+        return batch_fetch(rc, n_paths, d_n_paths, nc * 4, "download n_paths");
+    });
     GECCO_GUARD_END
 }
 

@@ -1246,18 +1246,9 @@ hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const doubl
 hipError_t launch_any(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr,
                       const uint32_t *allowed = nullptr) {
     if (a.L <= 0 || a.L > kGenMaxL) return hipErrorNotSupported;
-    if ((what == 2 || what == 3) && a.n_chunks > 0) {  // long contigs in the batch: chunked recursions
-        if (a.L <= 2) return launch_chunked<2>(what, a, stream);
-        if (a.L <= 4) return launch_chunked<4>(what, a, stream);
-        if (a.L <= 8) return launch_chunked<8>(what, a, stream);
-        if (a.L <= 16) return launch_chunked<16>(what, a, stream);
-        return launch_chunked<32>(what, a, stream);
-    }
-    if (a.L <= 2) return launch_lp<2>(what, a, stream, attr_value, allowed);
-    if (a.L <= 4) return launch_lp<4>(what, a, stream, attr_value, allowed);
-    if (a.L <= 8) return launch_lp<8>(what, a, stream, attr_value, allowed);
-    if (a.L <= 16) return launch_lp<16>(what, a, stream, attr_value, allowed);
-    return launch_lp<32>(what, a, stream, attr_value, allowed);
+    if ((what == 2 || what == 3) && a.n_chunks > 0)  // long contigs in the batch: chunked recursions
+        return dispatch_lp(a.L, [&](auto lp) { return launch_chunked<lp>(what, a, stream); });
+    return dispatch_lp(a.L, [&](auto lp) { return launch_lp<lp>(what, a, stream, attr_value, allowed); });
 }
 
 }  // namespace

@@ -26,6 +26,7 @@
 // y[g * K + k], gene-major like the sampler's output: a step's stores are consecutive bytes.
 // A contig is one sequential walk; it is not chunked (profiles/EXPERIMENTS.md has the parallel-in-T idea).
 #include "crf_device.hpp"
+#include "crf_lanes.hpp"
 
 #include <cmath>
 
@@ -200,16 +201,7 @@ hipError_t launch_gen_kbest(const GenArgs &a, int32_t k, uint16_t *back, uint16_
     if (a.L <= 0 || a.L > kGenMaxL || k < 1 || k > kMaxKBest) return hipErrorNotSupported;
     if (a.n_contigs <= 0) return hipSuccess;
     if (!a.state || !a.trans || !back || !fin || !y || !score || !n_paths) return hipErrorNotSupported;
-    if (a.L <= 2)
-        launch_forward<2>(a, k, back, fin, score, n_paths, stream);
-    else if (a.L <= 4)
-        launch_forward<4>(a, k, back, fin, score, n_paths, stream);
-    else if (a.L <= 8)
-        launch_forward<8>(a, k, back, fin, score, n_paths, stream);
-    else if (a.L <= 16)
-        launch_forward<16>(a, k, back, fin, score, n_paths, stream);
-    else
-        launch_forward<32>(a, k, back, fin, score, n_paths, stream);
+    dispatch_lp(a.L, [&](auto lp) { launch_forward<lp>(a, k, back, fin, score, n_paths, stream); });
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const size_t lanes = static_cast<size_t>(a.n_contigs) * static_cast<size_t>(k);

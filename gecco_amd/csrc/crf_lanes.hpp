@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace gecco {
 namespace {
 
@@ -29,6 +31,17 @@ __device__ __forceinline__ double wave_shr1_zero(double v) {  // lane l <- lane 
 }
 
 typedef double gl_v4d __attribute__((ext_vector_type(4)));  // the four result registers of v_mfma_f64_16x16x4_f64
+
+// Host side: the group width of a model of L labels (1 .. 32) -- the next power of two, 2 at the least -- as a constant:
+// f(std::integral_constant<int, LP>{}).  Every launcher of a kernel templated on LP picks its instance here.
+template <class F>
+auto dispatch_lp(int L, F &&f) {
+    if (L <= 2) return f(std::integral_constant<int, 2>{});
+    if (L <= 4) return f(std::integral_constant<int, 4>{});
+    if (L <= 8) return f(std::integral_constant<int, 8>{});
+    if (L <= 16) return f(std::integral_constant<int, 16>{});
+    return f(std::integral_constant<int, 32>{});
+}
 
 }  // namespace
 }  // namespace gecco

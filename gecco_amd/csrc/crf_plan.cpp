@@ -386,7 +386,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
         const char *env = std::getenv("GECCO_CRF_FORCE_GENERAL");
         // (valued and masked state scores exist in gl_state alone; region posteriors, sampled paths and the K best paths read the
         // any-L workspace)
-        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.spans || p.samples || p.kbest;
+        p.general = m.L != 2 || (env && env[0] == '1') || p.valued || p.masked || p.lattice;
     }
     p.fast_ok = (!p.general && W <= kWinMaxW && rescale_mask_for(m, W, &p.rescale_mask));
     {
@@ -829,6 +829,27 @@ bool ends_here(bool empty, bool null_buffer, int &rc) {
     set_error("null device buffer");
     rc = GECCO_CRF_EINVAL;
     return true;
+}
+
+// The whole-contig marginals of a plan laid out with `lattice`, for a query (`what`) that then reads what the pass left in the
+// workspace: the recursion as plan_run_marginals_full runs it -- the same launches, the same bits -- with one difference under
+// keep_state: gl_state also leaves the raw state scores.  `g`: the argument block of the launches, for the query's kernel (a
+// batch's chunked tail has been joined to `stream` by then).
+const GenRecursion kGenMarginalsKeepState = [] {
+    GenRecursion r = kGenMarginals;
+    r.clear = [](GenArgs &) {};
+    return r;
+}();
+int run_lattice(Plan &p, const DeviceCsr &csr, const char *what, bool keep_state, double *d_marg, double *d_lognorm, hipStream_t stream,
+                GenArgs &g) {
+    SeqArgs a;
+    const int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc) return rc;
+    if (!p.lattice || !p.general) {
+        set_error(std::string("the plan was not built for ") + what);
+        return GECCO_CRF_EINVAL;
+    }
+    return run_gen_whole(p, keep_state ? kGenMarginalsKeepState : kGenMarginals, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g);
 }
 
 // where the window kernels accumulate (atomic maxima: `zero` first, numpy.zeros of crf/__init__.py:251) or store p; the genes of
@@ -1374,75 +1395,45 @@ int plan_run_marginals_full(Plan &p, const DeviceCsr &csr, double *d_marg,
 
 int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *d_spans, int32_t n_spans, double *d_logp,
                                 double *d_marg, double *d_lognorm, hipStream_t stream) {
-    SeqArgs a;
-    int rc = begin_whole_contig(p, csr, 0, a, stream);
-    if (rc) return rc;
-    if (!p.spans || !p.general) {
-        set_error("the plan was not built for region posteriors");
-        return GECCO_CRF_EINVAL;
-    }
     if (n_spans < 0) {
         set_error("negative number of spans");
         return GECCO_CRF_EINVAL;
     }
+    int rc;
     if (ends_here(p.n_contigs == 0, (p.n_genes > 0 && (!csr.gene_ptr || !d_marg)) || (n_spans > 0 && (!d_spans || !d_logp)), rc))
         return rc;
-    // the marginals recursion as plan_run_marginals_full runs it, with one difference: gl_state also writes the raw state
-    // scores, which the span kernel shifts by its own maxima (the marginals' launches and bits are the same)
-    GenRecursion with_state = kGenMarginals;
-    with_state.clear = [](GenArgs &) {};
-    GenArgs g;
-    if ((rc = run_gen_whole(p, with_state, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
-    // (a batch's chunked tail has been joined to `stream` by then)
+    GenArgs g;  // (with the raw state scores, which the span kernel shifts by its own maxima)
+    if ((rc = run_lattice(p, csr, "region posteriors", true, d_marg, d_lognorm, stream, g))) return rc;
     return check_hip(launch_gen_spans(g, d_spans, n_spans, d_logp, stream), "span launch");
 }
 
 int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint64_t seed, const RunQuery *d_queries, int32_t n_runs,
                           int8_t *d_y, int32_t *d_runs, double *d_marg, double *d_lognorm, hipStream_t stream) {
-    SeqArgs a;
-    int rc = begin_whole_contig(p, csr, 0, a, stream);
-    if (rc) return rc;
-    if (!p.samples || !p.general) {
-        set_error("the plan was not built for sampled paths");
-        return GECCO_CRF_EINVAL;
-    }
     if (n_samples < 1 || n_samples > kMaxSamples || n_runs < 0) {
         set_error("n_samples outside 1 .. 2^20, or a negative number of runs");
         return GECCO_CRF_EINVAL;
     }
+    int rc;
     if (ends_here(p.n_contigs == 0 || p.n_genes == 0, !csr.gene_ptr || !d_marg || !d_y || (n_runs > 0 && (!d_queries || !d_runs)), rc))
         return rc;
-    // the marginals recursion as plan_run_marginals_full runs it: the same launches, the same bits
     GenArgs g;
-    if ((rc = run_gen_whole(p, kGenMarginals, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
-    // (a batch's chunked tail has been joined to `stream` by then)
+    if ((rc = run_lattice(p, csr, "sampled paths", false, d_marg, d_lognorm, stream, g))) return rc;
     if ((rc = check_hip(launch_gen_sample_paths(g, n_samples, seed, d_y, stream), "sample launch"))) return rc;
     return check_hip(launch_gen_sample_runs(g, d_y, d_queries, n_runs, n_samples, d_runs, stream), "run launch");
 }
 
 int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d_back, uint16_t *d_fin, int8_t *d_y, double *d_score,
                            int32_t *d_n_paths, double *d_marg, double *d_lognorm, hipStream_t stream) {
-    SeqArgs a;
-    int rc = begin_whole_contig(p, csr, 0, a, stream);
-    if (rc) return rc;
-    if (!p.kbest || !p.general) {
-        set_error("the plan was not built for the K best paths");
-        return GECCO_CRF_EINVAL;
-    }
     if (k < 1 || k > kMaxKBest) {
         set_error("k outside 1 .. 32");
         return GECCO_CRF_EINVAL;
     }
+    int rc;
     if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
                   !csr.gene_ptr || !d_marg || !d_back || !d_fin || !d_y || !d_score || !d_n_paths, rc))
         return rc;
-    // the marginals recursion as plan_run_marginals_full runs it (log Z: the same launches, the same bits), gl_state also
-    // leaving the raw state scores, as for the region posteriors: the list recursion reads those and nothing else
-    GenRecursion with_state = kGenMarginals;
-    with_state.clear = [](GenArgs &) {};
-    GenArgs g;
-    if ((rc = run_gen_whole(p, with_state, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g))) return rc;
-    // (a batch's chunked tail has been joined to `stream` by then)
+    GenArgs g;  // (the pass gives log Z; the list recursion reads the raw state scores and nothing else)
+    if ((rc = run_lattice(p, csr, "the K best paths", true, d_marg, d_lognorm, stream, g))) return rc;
     return check_hip(launch_gen_kbest(g, k, d_back, d_fin, d_y, d_score, d_n_paths, stream), "k-best launch");
 }
 

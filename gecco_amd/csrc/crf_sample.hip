@@ -32,6 +32,7 @@
 // gene-major y).  Where sample s has a label of the mask at the anchor: the maximal run of genes around the anchor whose labels
 // are all in the mask, as offsets (first, last + 1) inside the contig; else (-1, -1).
 #include "crf_device.hpp"
+#include "crf_lanes.hpp"
 
 #include <cfloat>
 
@@ -189,16 +190,7 @@ hipError_t launch_gen_sample_paths(const GenArgs &a, int32_t n_samples, uint64_t
     if (a.L <= 0 || a.L > kGenMaxL || !a.alpha || !a.marg || !y || n_samples <= 0 || n_samples > kMaxSamples)
         return hipErrorNotSupported;
     if (a.n_contigs <= 0 || a.n_genes <= 0) return hipSuccess;
-    if (a.L <= 2)
-        launch_paths<2>(a, n_samples, seed, y, stream);
-    else if (a.L <= 4)
-        launch_paths<4>(a, n_samples, seed, y, stream);
-    else if (a.L <= 8)
-        launch_paths<8>(a, n_samples, seed, y, stream);
-    else if (a.L <= 16)
-        launch_paths<16>(a, n_samples, seed, y, stream);
-    else
-        launch_paths<32>(a, n_samples, seed, y, stream);
+    dispatch_lp(a.L, [&](auto lp) { launch_paths<lp>(a, n_samples, seed, y, stream); });
     return hipGetLastError();
 }
 

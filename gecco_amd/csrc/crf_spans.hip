@@ -138,16 +138,7 @@ void launch_spans(const GenArgs &a, const SpanQuery *spans, int32_t n_spans, dou
 hipError_t launch_gen_spans(const GenArgs &a, const SpanQuery *spans, int32_t n_spans, double *logp, hipStream_t stream) {
     if (a.L <= 0 || a.L > kGenMaxL || !a.state || !a.E || !a.alpha || !a.marg) return hipErrorNotSupported;
     if (n_spans <= 0) return hipSuccess;
-    if (a.L <= 2)
-        launch_spans<2>(a, spans, n_spans, logp, stream);
-    else if (a.L <= 4)
-        launch_spans<4>(a, spans, n_spans, logp, stream);
-    else if (a.L <= 8)
-        launch_spans<8>(a, spans, n_spans, logp, stream);
-    else if (a.L <= 16)
-        launch_spans<16>(a, spans, n_spans, logp, stream);
-    else
-        launch_spans<32>(a, spans, n_spans, logp, stream);
+    dispatch_lp(a.L, [&](auto lp) { launch_spans<lp>(a, spans, n_spans, logp, stream); });
     return hipGetLastError();
 }
 

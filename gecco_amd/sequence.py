@@ -271,10 +271,28 @@ class SequenceCRF:
         out[full] = inside - free
         return out
 
+    @staticmethod
+    def _sequence_length(who: str, k: int, seq_ptr: np.ndarray) -> int:
+        """The number of items of sequence ``k``, the sequence of the query ``who`` ("span 3"), once ``k`` is one of ``X``'s."""
+        n_seqs = len(seq_ptr) - 1
+        if not 0 <= k < n_seqs:
+            raise ValueError(f"{who}: sequence index {k} out of range (X holds {n_seqs} sequences)")
+        return int(seq_ptr[k + 1] - seq_ptr[k])
+
+    def _label_bits(self, who: str, labels) -> int:
+        """The mask of a query's label set: a label, or a ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels."""
+        names = [str(m) for m in labels] if isinstance(labels, (set, frozenset, list, tuple)) else [str(labels)]
+        if not names:
+            raise ValueError(f"{who}: an empty set holds no label")
+        bits = 0
+        for name in names:
+            if name not in self.classes_:
+                raise ValueError(f"{who}: unknown label {name!r} (classes_: {self.classes_})")
+            bits |= 1 << self.classes_.index(name)
+        return bits
+
     def _span_queries(self, spans, seq_ptr: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """``spans`` as the native call's four arrays; every refusal is raised here, before any device call."""
-        index = {c: k for k, c in enumerate(self.classes_)}
-        n_seqs = len(seq_ptr) - 1
         contig, begin, end, mask = [], [], [], []
         for q, span in enumerate(spans):
             try:
@@ -282,25 +300,15 @@ class SequenceCRF:
                 k, start, stop = operator.index(k), operator.index(start), operator.index(stop)
             except (TypeError, ValueError):
                 raise ValueError(f"span {q}: expected (sequence_index, start, stop, labels), got {span!r}") from None
-            if not 0 <= k < n_seqs:
-                raise ValueError(f"span {q}: sequence index {k} out of range (X holds {n_seqs} sequences)")
-            length = int(seq_ptr[k + 1] - seq_ptr[k])
+            length = self._sequence_length(f"span {q}", k, seq_ptr)
             if start < 0 or start >= stop:
                 raise ValueError(f"span {q}: [{start}, {stop}) is not a non-empty range of items (start >= stop, or start < 0)")
             if stop > length:
                 raise ValueError(f"span {q}: stop {stop} lies beyond sequence {k} of {length} items")
-            names = [str(m) for m in labels] if isinstance(labels, (set, frozenset, list, tuple)) else [str(labels)]
-            if not names:
-                raise ValueError(f"span {q}: an empty set holds no label")
-            bits = 0
-            for name in names:
-                if name not in index:
-                    raise ValueError(f"span {q}: unknown label {name!r} (classes_: {self.classes_})")
-                bits |= 1 << index[name]
             contig.append(k)
             begin.append(start)
             end.append(stop)
-            mask.append(bits)
+            mask.append(self._label_bits(f"span {q}", labels))
         return (np.array(contig, dtype=np.int32), np.array(begin, dtype=np.int32), np.array(end, dtype=np.int32),
                 np.array(mask, dtype=np.uint32))
 
@@ -327,8 +335,6 @@ class SequenceCRF:
 
     def _anchor_queries(self, anchors, seq_ptr: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``anchors`` as the native call's three arrays; every refusal is raised here, before any device call."""
-        index = {c: k for k, c in enumerate(self.classes_)}
-        n_seqs = len(seq_ptr) - 1
         contig, anchor, mask = [], [], []
         for q, entry in enumerate(anchors):
             try:
@@ -336,22 +342,12 @@ class SequenceCRF:
                 k, item = operator.index(k), operator.index(item)
             except (TypeError, ValueError):
                 raise ValueError(f"anchor {q}: expected (sequence_index, item, labels), got {entry!r}") from None
-            if not 0 <= k < n_seqs:
-                raise ValueError(f"anchor {q}: sequence index {k} out of range (X holds {n_seqs} sequences)")
-            length = int(seq_ptr[k + 1] - seq_ptr[k])
+            length = self._sequence_length(f"anchor {q}", k, seq_ptr)
             if not 0 <= item < length:
                 raise ValueError(f"anchor {q}: item {item} lies outside sequence {k} of {length} items")
-            names = [str(m) for m in labels] if isinstance(labels, (set, frozenset, list, tuple)) else [str(labels)]
-            if not names:
-                raise ValueError(f"anchor {q}: an empty set holds no label")
-            bits = 0
-            for name in names:
-                if name not in index:
-                    raise ValueError(f"anchor {q}: unknown label {name!r} (classes_: {self.classes_})")
-                bits |= 1 << index[name]
             contig.append(k)
             anchor.append(item)
-            mask.append(bits)
+            mask.append(self._label_bits(f"anchor {q}", labels))
         return np.array(contig, dtype=np.int32), np.array(anchor, dtype=np.int32), np.array(mask, dtype=np.uint32)
 
     @staticmethod

@@ -471,13 +471,11 @@ class TypedClusterCRF:
                                                boundary_samples=boundary_samples, seed=seed, alternatives=alternatives,
                                                alternatives_margin=alternatives_margin)[1]
 
-    def _region_posteriors(self, batch, allowed, rows: np.ndarray, clusters: List[Any]) -> None:
+    def _region_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int,
+                           clusters: List[Any]) -> None:
         """``region_probability`` and ``region_type_probabilities`` of every called cluster (``rows``: the segment kernel's
         (contig, number, first gene, last gene + 1)), from ONE native call over the batch: per cluster one span with the set of
         every label but the background, and one per type with the labels whose names contain it."""
-        L = len(self.classes_)
-        item_ptr = batch.item_ptr.astype(np.int32)
-        not_background = ((1 << L) - 1) & ~(1 << self.classes_.index(self.background))
         type_masks = [sum(1 << l for l, names in enumerate(self.label_types_) if t in names) for t in self.types_]
         sets = [not_background] + type_masks
         contig = np.repeat(rows[:, 0], len(sets)).astype(np.int32)
@@ -491,15 +489,12 @@ class TypedClusterCRF:
             cluster.region_probability = row[0]
             cluster.region_type_probabilities = dict(zip(self.types_, row[1:]))
 
-    def _boundary_intervals(self, batch, allowed, rows: np.ndarray, clusters: List[Any], annotated: List[Any], p_any: np.ndarray,
-                            n_samples: int, seed: int) -> None:
+    def _boundary_intervals(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int, clusters: List[Any],
+                            annotated: List[Any], p_any: np.ndarray, n_samples: int, seed: int) -> None:
         """``anchor_probability``, ``exact_probability``, ``start_interval`` and ``end_interval`` of every called cluster
         (``rows``: the segment kernel's (contig, number, first gene, last gene + 1)), from ONE native call over the batch:
         ``n_samples`` label paths per contig drawn from the whole-contig posterior, and per cluster one run query -- the run of
         genes outside the background around the cluster's gene with the greatest ``p_any`` (the first on ties)."""
-        L = len(self.classes_)
-        item_ptr = batch.item_ptr.astype(np.int32)
-        not_background = ((1 << L) - 1) & ~(1 << self.classes_.index(self.background))
         base = item_ptr[rows[:, 0]].astype(np.int64)
         anchor = np.array([first + int(np.argmax(p_any[first:last])) for first, last in rows[:, 2:4].tolist()], dtype=np.int64)
         runs = self._fitted().sample_paths(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id, n_samples, seed=seed,
@@ -521,8 +516,8 @@ class TypedClusterCRF:
             cluster.start_interval = (int(starts[lo]), int(starts[hi]))
             cluster.end_interval = (int(ends[lo]), int(ends[hi]))
 
-    def _alternatives(self, batch, allowed, rows: np.ndarray, clusters: List[Any], annotated: List[Any], p_any: np.ndarray,
-                      k: int, margin: int) -> None:
+    def _alternatives(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, clusters: List[Any], annotated: List[Any],
+                      p_any: np.ndarray, k: int, margin: int) -> None:
         """``alternatives`` of every called cluster (``rows``: the segment kernel's (contig, number, first gene, last gene +
         1)): the contig's Viterbi path from one native call, then ONE ``viterbi_kbest`` call over all clusters' neighbourhoods,
         each a short sequence whose copied end genes are pinned to the Viterbi path's labels unless they are contig ends.  The
@@ -531,9 +526,8 @@ class TypedClusterCRF:
         model = self._fitted()
         L = len(self.classes_)
         bg = self.classes_.index(self.background)
-        item_ptr = batch.item_ptr.astype(np.int64)
         attr_ptr = batch.attr_ptr.astype(np.int64)
-        best, _ = model.viterbi(item_ptr.astype(np.int32), attr_ptr.astype(np.int32), batch.attr_id, device=self.device,
+        best, _ = model.viterbi(item_ptr, attr_ptr.astype(np.int32), batch.attr_id, device=self.device,
                                 want_score=False, allowed=allowed)
         best = np.asarray(best, dtype=np.int64)
         every = np.uint32((1 << L) - 1)
@@ -616,8 +610,9 @@ class TypedClusterCRF:
         if not annotated:
             return annotated, []
         has_domains = np.fromiter((1 if g.protein.domains else 0 for g in annotated), dtype=np.uint8, count=len(annotated))
-        rows = _native.segment(p_any, has_domains, batch.item_ptr.astype(np.int32), threshold=threshold, n_cds=n_cds,
-                               edge_distance=edge_distance, trim=trim, device=self.device, carry_state=False)
+        item_ptr = batch.item_ptr.astype(np.int32)
+        rows = _native.segment(p_any, has_domains, item_ptr, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance,
+                               trim=trim, device=self.device, carry_state=False)
         Cluster = _cluster_class()
         clusters: List[Any] = []
         for contig, number, first, last in rows.tolist():
@@ -627,14 +622,15 @@ class TypedClusterCRF:
             cluster.type_probabilities = proba
             cluster.type = _cluster_type_factory(cluster)(type_of(proba))
             clusters.append(cluster)
+        # what the whole-contig passes below share: the segment kernel's rows and the set of every label but the background
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+        not_background = ((1 << len(self.classes_)) - 1) & ~(1 << self.classes_.index(self.background))
         if region_posteriors and clusters:
-            self._region_posteriors(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters)
+            self._region_posteriors(batch, allowed, rows, item_ptr, not_background, clusters)
         if boundary_samples > 0 and clusters:
-            self._boundary_intervals(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters, annotated, p_any,
-                                     boundary_samples, seed)
+            self._boundary_intervals(batch, allowed, rows, item_ptr, not_background, clusters, annotated, p_any, boundary_samples, seed)
         if alternatives > 0 and clusters:
-            self._alternatives(batch, allowed, np.asarray(rows, dtype=np.int64).reshape(-1, 4), clusters, annotated, p_any,
-                               alternatives, alternatives_margin)
+            self._alternatives(batch, allowed, rows, item_ptr, clusters, annotated, p_any, alternatives, alternatives_margin)
         return annotated, clusters
 
 
