@@ -59,42 +59,6 @@ struct gecco_crf_session {
 #define GECCO_API extern "C" __attribute__((visibility("default")))
 
 namespace {
-struct DeviceGuard {  // restores the caller's current device
-    int prev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && (hipGetDevice(&cur) != hipSuccess || cur != prev)) (void)hipSetDevice(prev);
-    }
-};
-
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t n, const char *what) {
-        return check_hip(hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)), what);
-    }
-};
-
-int check_device(int32_t device) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        set_error("no HIP device available (this library has no CPU fallback)");
-        return GECCO_CRF_ENODEV;
-    }
-    if (device < 0 || device >= n) {
-        set_error("device index out of range");
-        return GECCO_CRF_ENODEV;
-    }
-    return GECCO_CRF_OK;
-}
-
 int fail(const char *msg) {
     set_error(msg);
     return GECCO_CRF_EINVAL;
@@ -230,7 +194,7 @@ GECCO_API int gecco_crf_plan_create(const gecco_crf_model *m, int32_t device, co
         set_error("contig_ptr[0] must be 0");
         return GECCO_CRF_EINVAL;
     }
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     std::unique_ptr<gecco_crf_plan> h(new gecco_crf_plan());
     int rc = plan_build(m->m, device, contig_ptr, n_contigs, window, step, pad, h->p);
@@ -240,7 +204,7 @@ GECCO_API int gecco_crf_plan_create(const gecco_crf_model *m, int32_t device, co
     GECCO_GUARD_END
 }
 GECCO_API void gecco_crf_plan_free(gecco_crf_plan *p) {
-    DeviceGuard guard;
+    DeviceScope guard;
     delete p;
 }
 GECCO_API int32_t gecco_crf_plan_num_genes(const gecco_crf_plan *p) { return p ? p->p.n_genes : 0; }
@@ -252,7 +216,7 @@ GECCO_API const char *gecco_crf_plan_kernel_name(const gecco_crf_plan *p) { retu
 GECCO_API int gecco_crf_plan_run_windowed(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                           int32_t label, double *d_p_out, void *stream) {
     if (!p) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_windowed(p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
@@ -261,7 +225,7 @@ GECCO_API int gecco_crf_plan_run_windowed(gecco_crf_plan *p, const int32_t *d_ge
 GECCO_API int gecco_crf_plan_run_windowed_all(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                               int32_t background, double *d_p_all, double *d_p_any, void *stream) {
     if (!p) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_windowed_all(p->p, {d_gene_ptr, d_attr_id}, background, d_p_all, d_p_any, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
@@ -293,7 +257,7 @@ GECCO_API int gecco_crf_plan_time_windowed(gecco_crf_plan *p, const int32_t *d_g
                                            int32_t label, double *d_p_out, void *stream, int32_t warmup,
                                            int32_t iters, float *ms_per_launch) {
     if (!p || !ms_per_launch || iters <= 0) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     hipStream_t s = static_cast<hipStream_t>(stream);
     return time_calls(s, warmup, iters, ms_per_launch, [&] { return plan_run_windowed(p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, s); });
@@ -304,7 +268,7 @@ GECCO_API int gecco_crf_plan_time_windowed_all(gecco_crf_plan *p, const int32_t 
                                                int32_t background, double *d_p_all, double *d_p_any, void *stream,
                                                int32_t warmup, int32_t iters, float *ms_per_launch) {
     if (!p || !ms_per_launch || iters <= 0) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     hipStream_t s = static_cast<hipStream_t>(stream);
     return time_calls(s, warmup, iters, ms_per_launch,
@@ -316,7 +280,7 @@ GECCO_API int gecco_crf_plan_time_decode_pipelined(gecco_crf_plan *p, const int3
                                                    int32_t label, double *d_p_out, int8_t *d_y, void *stream, int32_t warmup,
                                                    int32_t iters, float *ms_per_launch) {
     if (!p || !ms_per_launch || iters <= 0) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
@@ -331,7 +295,7 @@ GECCO_API int gecco_crf_plan_time_decode_pipelined(gecco_crf_plan *p, const int3
 
 GECCO_API int gecco_crf_plan_viterbi_stats(gecco_crf_plan *p, int64_t out[4], int32_t reset) {
     if (!p || !out) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_viterbi_stats(p->p, out, reset != 0);
     GECCO_GUARD_END
@@ -340,7 +304,7 @@ GECCO_API int gecco_crf_plan_viterbi_stats(gecco_crf_plan *p, int64_t out[4], in
 GECCO_API int gecco_crf_plan_run_decode(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                         int32_t label, double *d_p_out, int8_t *d_y, double *d_score, void *stream) {
     if (!p) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_decode(p->p, {d_gene_ptr, d_attr_id}, label, d_p_out, d_y, d_score, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
@@ -348,7 +312,7 @@ GECCO_API int gecco_crf_plan_run_decode(gecco_crf_plan *p, const int32_t *d_gene
 GECCO_API int gecco_crf_plan_run_decode_pipelined(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id, int32_t label,
                                                   double *d_p_out, gecco_crf_plan *prev, int8_t *d_prev_y, void *stream) {
     if (!p && !prev) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_decode_pipelined(p ? &p->p : nullptr, {d_gene_ptr, d_attr_id}, label, d_p_out, prev ? &prev->p : nullptr, d_prev_y,
                                      static_cast<hipStream_t>(stream));
@@ -357,7 +321,7 @@ GECCO_API int gecco_crf_plan_run_decode_pipelined(gecco_crf_plan *p, const int32
 GECCO_API int gecco_crf_plan_run_marginals_full(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                                 double *d_marg, double *d_lognorm, void *stream) {
     if (!p) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_marginals_full(p->p, {d_gene_ptr, d_attr_id}, d_marg, d_lognorm, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
@@ -365,7 +329,7 @@ GECCO_API int gecco_crf_plan_run_marginals_full(gecco_crf_plan *p, const int32_t
 GECCO_API int gecco_crf_plan_run_viterbi(gecco_crf_plan *p, const int32_t *d_gene_ptr, const int32_t *d_attr_id,
                                          int8_t *d_y, double *d_score, void *stream) {
     if (!p) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_viterbi(p->p, {d_gene_ptr, d_attr_id}, d_y, d_score, static_cast<hipStream_t>(stream));
     GECCO_GUARD_END
@@ -391,7 +355,7 @@ GECCO_API int gecco_crf_session_create(const gecco_crf_model *m, const int32_t *
                                        gecco_crf_session **out) {
     if (!m || !out) return GECCO_CRF_EINVAL;
     *out = nullptr;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     std::unique_ptr<gecco_crf_session> h(new gecco_crf_session());
     int rc = session_create(m->m, devices, n_devices, &h->s);
@@ -401,7 +365,7 @@ GECCO_API int gecco_crf_session_create(const gecco_crf_model *m, const int32_t *
     GECCO_GUARD_END
 }
 GECCO_API void gecco_crf_session_free(gecco_crf_session *s) {
-    DeviceGuard guard;
+    DeviceScope guard;
     delete s;
 }
 GECCO_API int gecco_crf_session_set_chunk_genes(gecco_crf_session *s, int32_t genes) {
@@ -631,7 +595,7 @@ GECCO_API int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t dev
     if (!m) return GECCO_CRF_EINVAL;
     int rc;
     if ((rc = check_window(window, step)) || (rc = check_label(m, label))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     Session *s = nullptr;
     if ((rc = default_session(m, device, &s))) return rc;
@@ -653,7 +617,7 @@ GECCO_API int gecco_crf_marginals_full(const gecco_crf_model *m, int32_t device,
                                        int32_t n_contigs, const int32_t *gene_ptr, const int32_t *attr_id,
                                        double *marg, double *lognorm) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     Session *s = nullptr;
     int rc = default_session(m, device, &s);
@@ -669,7 +633,7 @@ GECCO_API int gecco_crf_marginals_full(const gecco_crf_model *m, int32_t device,
 GECCO_API int gecco_crf_viterbi(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
                                 const int32_t *gene_ptr, const int32_t *attr_id, int8_t *y_out, double *score) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     Session *s = nullptr;
     int rc = default_session(m, device, &s);
@@ -696,16 +660,13 @@ namespace {
 // csr.allowed) and the outputs.
 struct ResidentBatch {
     Plan plan;
-    char *d = nullptr;
+    DeviceBlock<char> d;  // (after the plan: freed before it, with the plan's device still current)
     int64_t n = 0;  // genes
     DeviceCsr csr;
     size_t out_off[3] = {0, 0, 0};
     template <class T>
     T *out(int i) const {
-        return reinterpret_cast<T *>(d + out_off[i]);
-    }
-    ~ResidentBatch() {
-        if (d) (void)hipFree(d);
+        return d.at<T>(out_off[i]);
     }
 };
 
@@ -788,26 +749,26 @@ int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_p
     b.out_off[0] = blk.take(per_gene[0] * size_t(n) + 8);
     b.out_off[1] = blk.take(per_gene[1] * size_t(n) + 8);
     b.out_off[2] = blk.take(per_contig * size_t(n_contigs) + 8);
-    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&b.d), blk.off), "hipMalloc batch"))) return rc;
+    if ((rc = b.d.alloc(blk.off, "hipMalloc batch"))) return rc;
     // (gene_ptr may carry any base offset: the kernels index attr_id with its values, so the row pointers are rebased on the
     // host, and ids and values go up from that base)
     std::vector<int32_t> rows(size_t(n) + 1);
     for (int64_t i = 0; i <= n; ++i) rows[size_t(i)] = int32_t(gp[i] - a0);
-    rc = check_hip(hipMemcpy(b.d + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
-    if (!rc && nnz) rc = check_hip(hipMemcpy(b.d + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
+    rc = check_hip(hipMemcpy(b.d.get() + o_gp, rows.data(), b_gp, hipMemcpyHostToDevice), "upload gene_ptr");
+    if (!rc && nnz) rc = check_hip(hipMemcpy(b.d.get() + o_at, attr_id + a0, size_t(nnz) * 4, hipMemcpyHostToDevice), "upload attr_id");
     if (!rc && nnz && valued)
-        rc = check_hip(hipMemcpy(b.d + o_val, attr_value + a0, size_t(nnz) * 8, hipMemcpyHostToDevice), "upload attr_value");
+        rc = check_hip(hipMemcpy(b.d.get() + o_val, attr_value + a0, size_t(nnz) * 8, hipMemcpyHostToDevice), "upload attr_value");
     if (!rc && masked)
-        rc = check_hip(hipMemcpy(b.d + o_mask, allowed + contig_ptr[0], size_t(n) * 4, hipMemcpyHostToDevice), "upload allowed");
+        rc = check_hip(hipMemcpy(b.d.get() + o_mask, allowed + contig_ptr[0], size_t(n) * 4, hipMemcpyHostToDevice), "upload allowed");
     if (rc) return rc;
     b.n = n;
-    b.csr.gene_ptr = reinterpret_cast<const int32_t *>(b.d + o_gp);
-    b.csr.attr_id = reinterpret_cast<const int32_t *>(b.d + o_at);
+    b.csr.gene_ptr = reinterpret_cast<const int32_t *>(b.d.get() + o_gp);
+    b.csr.attr_id = reinterpret_cast<const int32_t *>(b.d.get() + o_at);
     if (valued) {
-        b.csr.attr_value = reinterpret_cast<const double *>(b.d + o_val);
+        b.csr.attr_value = reinterpret_cast<const double *>(b.d.get() + o_val);
         b.csr.vmax_abs = vmax;
     }
-    if (masked) b.csr.allowed = reinterpret_cast<const uint32_t *>(b.d + o_mask);
+    if (masked) b.csr.allowed = reinterpret_cast<const uint32_t *>(b.d.get() + o_mask);
     return GECCO_CRF_OK;
 }
 
@@ -825,7 +786,7 @@ int windowed_all(const gecco_crf_model *m, int32_t device, const int32_t *contig
     if (!m) return GECCO_CRF_EINVAL;
     int rc;
     if ((rc = check_window(window, step)) || (rc = check_background(m, background, p_any))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     if ((rc = check_output(contig_ptr, n_contigs, p_all))) return rc;
     ResidentBatch b;
@@ -865,7 +826,7 @@ int windowed_one(const gecco_crf_model *m, int32_t device, const int32_t *contig
     if (!m) return GECCO_CRF_EINVAL;
     int rc;
     if ((rc = check_window(window, step)) || (rc = check_label(m, label))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     if ((rc = check_output(contig_ptr, n_contigs, p_out))) return rc;
     ResidentBatch b;
@@ -882,7 +843,7 @@ int marginals_full_one(const gecco_crf_model *m, int32_t device, const int32_t *
                        const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked,
                        double *marg, double *lognorm) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     if (!marg && !lognorm) return GECCO_CRF_OK;
     ResidentBatch b;
@@ -904,7 +865,7 @@ int viterbi_one(const gecco_crf_model *m, int32_t device, const int32_t *contig_
                 const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int8_t *y_out,
                 double *score) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     if (!y_out) return check_output(contig_ptr, n_contigs, y_out);  // (no genes: nothing to label)
     ResidentBatch b;
@@ -1019,9 +980,9 @@ int lattice_call(const gecco_crf_model *m, int32_t device, const int32_t *contig
     return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
 }
 // the device block of an entry's queries: `total` bytes, the `bytes` of `host` at its head
-int upload_queries(DevBuf<char> &q, const void *host, size_t bytes, size_t total, const char *what_alloc, const char *what_copy) {
+int upload_queries(DeviceBlock<char> &q, const void *host, size_t bytes, size_t total, const char *what_alloc, const char *what_copy) {
     const int rc = q.alloc(total, what_alloc);
-    return rc ? rc : check_hip(hipMemcpy(q.p, host, bytes, hipMemcpyHostToDevice), what_copy);
+    return rc ? rc : check_hip(hipMemcpy(q.get(), host, bytes, hipMemcpyHostToDevice), what_copy);
 }
 }  // namespace
 
@@ -1033,7 +994,7 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
                                            const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans, double *logp,
                                            double *marg, double *lognorm) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     int rc;
     // the checks of the spans, on the host and before any device work
@@ -1059,13 +1020,13 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
     }
     // (a batch without genes cannot be: a checked span lies inside a contig with genes)
     return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
-        DevBuf<char> q;
+        DeviceBlock<char> q;
         const size_t b_spans = align256(size_t(n_spans) * sizeof(SpanQuery));
         int rc = upload_queries(q, spans.data(), size_t(n_spans) * sizeof(SpanQuery), b_spans + size_t(n_spans) * 8, "hipMalloc spans",
                                 "upload spans");
         if (rc) return rc;
-        double *d_logp = reinterpret_cast<double *>(q.p + b_spans);
-        rc = batch_wait(plan_run_span_probabilities(b.plan, b.csr, reinterpret_cast<const SpanQuery *>(q.p), n_spans, d_logp,
+        double *d_logp = reinterpret_cast<double *>(q.get() + b_spans);
+        rc = batch_wait(plan_run_span_probabilities(b.plan, b.csr, reinterpret_cast<const SpanQuery *>(q.get()), n_spans, d_logp,
                                                     b.out<double>(0), b.out<double>(2), nullptr), "span probabilities");
         return batch_fetch(rc, logp, d_logp, size_t(n_spans) * 8, "download logp");
     });
@@ -1080,7 +1041,7 @@ GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, c
                                      const int32_t *run_anchor, const uint32_t *run_mask, int32_t n_runs, int8_t *y, int32_t *runs,
                                      double *marg, double *lognorm) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     int rc;
     // the checks of the call's own arguments, on the host and before any device work
@@ -1104,13 +1065,13 @@ GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, c
     return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, size_t(n_samples), 0, marg, lognorm,
                         [&](ResidentBatch &b) {
         if (b.n == 0) return int(GECCO_CRF_OK);  // (no labels, no run: a checked run lies inside a contig with genes)
-        DevBuf<char> q;
+        DeviceBlock<char> q;
         const size_t b_queries = align256(size_t(n_runs) * sizeof(RunQuery)), b_runs = size_t(n_runs) * size_t(n_samples) * 8;
         int rc = n_runs > 0 ? upload_queries(q, queries.data(), size_t(n_runs) * sizeof(RunQuery), b_queries + b_runs, "hipMalloc runs",
                                              "upload runs") : GECCO_CRF_OK;
         if (rc) return rc;
-        int32_t *d_runs = n_runs > 0 ? reinterpret_cast<int32_t *>(q.p + b_queries) : nullptr;
-        rc = batch_wait(plan_run_sample_paths(b.plan, b.csr, n_samples, seed, reinterpret_cast<const RunQuery *>(q.p), n_runs,
+        int32_t *d_runs = n_runs > 0 ? reinterpret_cast<int32_t *>(q.get() + b_queries) : nullptr;
+        rc = batch_wait(plan_run_sample_paths(b.plan, b.csr, n_samples, seed, reinterpret_cast<const RunQuery *>(q.get()), n_runs,
                                               b.out<int8_t>(1), d_runs, b.out<double>(0), b.out<double>(2), nullptr), "sampled paths");
         rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * size_t(n_samples), "download paths");
         return batch_fetch(rc, runs, d_runs, b_runs, "download runs");
@@ -1125,7 +1086,7 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
                                       const uint32_t *allowed, int32_t k, int8_t *y, double *score, int32_t *n_paths,
                                       double *lognorm) {
     if (!m) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     int rc;
     // the check of the call's own argument, on the host and before any device work
@@ -1147,11 +1108,11 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
         }
         double *d_lognorm = b.out<double>(2), *d_score = d_lognorm + nc;
         int32_t *d_n_paths = reinterpret_cast<int32_t *>(d_score + nc * K);
-        DevBuf<char> ws;
+        DeviceBlock<char> ws;
         const size_t b_back = align256(kbest_back_bytes(b.n, m->m.L, k)), b_fin = kbest_fin_bytes(n_contigs, k);
         int rc = ws.alloc(b_back + b_fin, "hipMalloc k-best back-pointers");
         if (rc) return rc;
-        uint16_t *d_back = reinterpret_cast<uint16_t *>(ws.p), *d_fin = reinterpret_cast<uint16_t *>(ws.p + b_back);
+        uint16_t *d_back = reinterpret_cast<uint16_t *>(ws.get()), *d_fin = reinterpret_cast<uint16_t *>(ws.get() + b_back);
         rc = batch_wait(plan_run_viterbi_kbest(b.plan, b.csr, k, d_back, d_fin, b.out<int8_t>(1), d_score, d_n_paths, b.out<double>(0),
                                                d_lognorm, nullptr), "k-best paths");
         rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * K, "download paths");
@@ -1164,23 +1125,18 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
 namespace {
 // grow-only scratch of the stand-alone segmenter / composition calls, one set per host thread
 struct Scratch {
+    DeviceScope home{DeviceScope::kLater};  // (first member: the block is freed with its device current)
     int device = -1;
-    char *d = nullptr;
-    size_t cap = 0;
-    ~Scratch() {
-        if (d && hipSetDevice(device) == hipSuccess) (void)hipFree(d);
-    }
+    DeviceBlock<char> d;
+    ~Scratch() { home.enter(device); }
     int reserve(int dev, size_t bytes) {
-        if (d && dev == device && bytes <= cap) return GECCO_CRF_OK;
-        if (d && hipSetDevice(device) == hipSuccess) (void)hipFree(d);
-        d = nullptr;
-        cap = 0;
-        int rc = check_hip(hipSetDevice(dev), "hipSetDevice");
-        if (rc) return rc;
-        const size_t want = bytes + bytes / 8 + 256;
-        if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&d), want), "hipMalloc scratch"))) return rc;
+        if (d.get() && dev != device) {  // a block of another device: freed there
+            DeviceScope there(device);
+            d.release();
+        }
+        int rc = d.get() && bytes <= d.capacity() ? GECCO_CRF_OK : set_device(dev);
+        if (rc || (rc = d.reserve(bytes, "hipMalloc scratch"))) return rc;
         device = dev;
-        cap = want;
         return GECCO_CRF_OK;
     }
 };
@@ -1227,14 +1183,14 @@ GECCO_API int gecco_crf_segment_ex(int32_t device, const double *p, const uint8_
             }
         nb = size_t(sp.bio_ptr[n]);
     }
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     static thread_local Scratch scratch;
     const size_t o_p = 0, o_a = o_p + al256(n * 8), o_c = o_a + al256(n + 8), o_seg = o_c + al256((nc + 1) * 4),
                  o_tot = o_seg + al256(size_t(max_seg) * 16 + 16), o_bp = o_tot + 256, o_bi = o_bp + al256((n + 1) * 4),
                  o_ws = o_bi + al256((nb + 4) * 4), bytes = o_ws + segment_workspace_bytes(int(n), n_contigs);
     if ((rc = scratch.reserve(device, bytes))) return rc;
-    char *d = scratch.d;
+    char *d = scratch.d.get();
     if ((rc = check_hip(hipMemcpy(d + o_p, p, n * 8, hipMemcpyHostToDevice), "H2D p"))) return rc;
     if ((rc = check_hip(hipMemcpy(d + o_a, annotated, n, hipMemcpyHostToDevice), "H2D annotated"))) return rc;
     if ((rc = check_hip(hipMemcpy(d + o_c, contig_ptr, (nc + 1) * 4, hipMemcpyHostToDevice), "H2D contig_ptr"))) return rc;
@@ -1274,7 +1230,7 @@ GECCO_API int gecco_crf_plan_run_segment_ex(gecco_crf_plan *p, const double *d_p
                                             const gecco_crf_refine_params *params, int32_t *d_seg, int32_t max_seg,
                                             int32_t *d_n_seg, void *stream) {
     if (!p || !params) return GECCO_CRF_EINVAL;
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
     return plan_run_segment(p->p, d_p, d_annotated, seg_params(*params), d_seg, max_seg, nullptr, d_n_seg,
                             static_cast<hipStream_t>(stream));
@@ -1310,11 +1266,11 @@ GECCO_API int gecco_crf_domain_composition(int32_t device, const int32_t *seg, i
             return GECCO_CRF_EINVAL;
         }
     }
-    DeviceGuard guard;
+    DeviceScope guard;
     GECCO_GUARD_BEGIN
-    if ((rc = check_hip(hipSetDevice(device), "hipSetDevice"))) return rc;
-    DevBuf<int32_t> d_seg, d_ptr, d_col;
-    DevBuf<double> d_w, d_tmp, d_out;
+    if ((rc = set_device(device))) return rc;
+    DeviceBlock<int32_t> d_seg, d_ptr, d_col;
+    DeviceBlock<double> d_w, d_tmp, d_out;
     const size_t out_n = size_t(n_seg) * size_t(n_cols);
     if ((rc = d_seg.alloc(size_t(n_seg) * 4, "hipMalloc segments"))) return rc;
     if ((rc = d_ptr.alloc(size_t(n_genes) + 1, "hipMalloc dom_ptr"))) return rc;
@@ -1322,14 +1278,14 @@ GECCO_API int gecco_crf_domain_composition(int32_t device, const int32_t *seg, i
     if ((rc = d_w.alloc(rows, "hipMalloc dom_weight"))) return rc;
     if ((rc = d_tmp.alloc(rows, "hipMalloc scratch"))) return rc;
     if ((rc = d_out.alloc(out_n, "hipMalloc compositions"))) return rc;
-    if ((rc = check_hip(hipMemcpy(d_seg.p, seg, size_t(n_seg) * 16, hipMemcpyHostToDevice), "H2D segments"))) return rc;
-    if ((rc = check_hip(hipMemcpy(d_ptr.p, dom_ptr, (size_t(n_genes) + 1) * 4, hipMemcpyHostToDevice), "H2D dom_ptr"))) return rc;
-    if (rows && (rc = check_hip(hipMemcpy(d_col.p, dom_col, rows * 4, hipMemcpyHostToDevice), "H2D dom_col"))) return rc;
-    if (rows && (rc = check_hip(hipMemcpy(d_w.p, dom_weight, rows * 8, hipMemcpyHostToDevice), "H2D dom_weight"))) return rc;
-    if ((rc = check_hip(launch_composition(d_seg.p, n_seg, d_ptr.p, d_col.p, d_w.p, d_tmp.p, n_cols, normalize ? 1 : 0,
-                                           d_out.p, nullptr), "composition launch")))
+    if ((rc = check_hip(hipMemcpy(d_seg.get(), seg, size_t(n_seg) * 16, hipMemcpyHostToDevice), "H2D segments"))) return rc;
+    if ((rc = check_hip(hipMemcpy(d_ptr.get(), dom_ptr, (size_t(n_genes) + 1) * 4, hipMemcpyHostToDevice), "H2D dom_ptr"))) return rc;
+    if (rows && (rc = check_hip(hipMemcpy(d_col.get(), dom_col, rows * 4, hipMemcpyHostToDevice), "H2D dom_col"))) return rc;
+    if (rows && (rc = check_hip(hipMemcpy(d_w.get(), dom_weight, rows * 8, hipMemcpyHostToDevice), "H2D dom_weight"))) return rc;
+    if ((rc = check_hip(launch_composition(d_seg.get(), n_seg, d_ptr.get(), d_col.get(), d_w.get(), d_tmp.get(), n_cols, normalize ? 1 : 0,
+                                           d_out.get(), nullptr), "composition launch")))
         return rc;
-    return check_hip(hipMemcpy(comp_out, d_out.p, out_n * 8, hipMemcpyDeviceToHost), "D2H compositions");
+    return check_hip(hipMemcpy(comp_out, d_out.get(), out_n * 8, hipMemcpyDeviceToHost), "D2H compositions");
     GECCO_GUARD_END
 }
 
@@ -1444,7 +1400,7 @@ int trainer_open(Handle **out, const char *family, int32_t device, int32_t n_set
                  const int32_t *const *labels, const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window,
                  const int32_t *step, const int32_t *const *state_fid, const int32_t *const *trans_fid,
                  const int32_t *num_features, int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget_bytes) {
-    DeviceGuard guard;
+    DeviceScope guard;
     Trainer *t = nullptr;
     int rc = trainer_create(device, n_sets, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window, step,
                             state_fid, trans_fid, num_features, n_problems, problem_set, scratch_budget_bytes, family, &t);
@@ -1455,14 +1411,14 @@ int trainer_open(Handle **out, const char *family, int32_t device, int32_t n_set
 int trainer_run(Trainer *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
     if (!t) return GECCO_CRF_EINVAL;
     GECCO_GUARD_BEGIN
-    DeviceGuard guard;
+    DeviceScope guard;
     return trainer_eval(t, active, w, f, g);
     GECCO_GUARD_END
 }
 
 void trainer_close(Trainer *t) {
     if (!t) return;
-    DeviceGuard guard;
+    DeviceScope guard;
     trainer_destroy(t);
 }
 
@@ -1579,7 +1535,7 @@ int general_open(Handle **out, const GeneralFamily &family, bool valued, int32_t
     if (!seq_ptr || !n_seqs || !item_ptr || !attr_id || (valued && !attr_value) || (partial && !allowed) || !labels || !num_attrs || !num_labels ||
         (!family.whole && (!window || !step)) || !state_fid || !trans_fid || !num_features)
         return fail(family.null_argument);
-    DeviceGuard guard;
+    DeviceScope guard;
     TrainerGeneral *t = nullptr;
     const int rc = family.whole ? trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
                                                            num_labels, state_fid, trans_fid, num_features, &t, attr_value, allowed)
@@ -1627,7 +1583,7 @@ GECCO_API int gecco_crf_trainer_general_eval(gecco_crf_trainer_general *t, const
                                              double *f, double *const *g) {
     if (!t) return GECCO_CRF_EINVAL;
     GECCO_GUARD_BEGIN
-    DeviceGuard guard;
+    DeviceScope guard;
     return trainer_general_eval(reinterpret_cast<TrainerGeneral *>(t), active, w, f, g);
     GECCO_GUARD_END
 }
@@ -1642,7 +1598,7 @@ GECCO_API int64_t gecco_crf_trainer_general_scratch_bytes(const gecco_crf_traine
 }
 GECCO_API void gecco_crf_trainer_general_free(gecco_crf_trainer_general *t) {
     if (!t) return;
-    DeviceGuard guard;
+    DeviceScope guard;
     trainer_general_destroy(reinterpret_cast<TrainerGeneral *>(t));
 }
 
@@ -1699,7 +1655,7 @@ GECCO_API int gecco_crf_fisher_exact(int32_t device, const int64_t *tables, int6
     int rc = fisher_check(tables, n, pvalue);
     if (rc || n == 0) return rc;
     if ((rc = check_device(device))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     return fisher_exact(device, tables, n, pvalue);
     GECCO_GUARD_END
 }
@@ -1715,7 +1671,7 @@ GECCO_API int gecco_crf_cluster_overlaps(int32_t device, int32_t n_genes, const 
                             member_ptr_out, max_members, n_members);
     if (rc) return rc;
     if ((rc = check_device(device))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     return cluster_overlaps(device, n_genes, gene_seq, gene_start, gene_end, n_seqs, cluster_ptr, cluster_start, cluster_end,
                             label_out, member_ptr_out, member_gene_out, max_members, n_members);
     GECCO_GUARD_END
@@ -1731,7 +1687,7 @@ GECCO_API int gecco_crf_domain_composition_members(int32_t device, const int32_t
     if (rc) return rc;
     if ((rc = check_device(device))) return rc;
     if (n_clusters == 0 || n_cols == 0) return GECCO_CRF_OK;
-    DeviceGuard guard;
+    DeviceScope guard;
     return composition_members(device, member_ptr, n_clusters, member_gene, dom_ptr, n_genes, dom_col, dom_weight, n_cols,
                                normalize, comp_out);
     GECCO_GUARD_END
@@ -1756,7 +1712,7 @@ GECCO_API int gecco_crf_forest_fit(int32_t device, int32_t n_samples, int32_t n_
                               rand_state, max_features);
     if (rc) return rc;
     if ((rc = check_device(device))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     const ForestProblem p{n_samples, col_ptr, row_idx, values, n_classes, y, sample_counts, rand_state};
     std::vector<std::unique_ptr<Forest>> f;
     if ((rc = forest_fit_batch(device, 1, n_features, n_outputs, n_trees, max_features, &p, /*lone=*/true, &f))) return rc;
@@ -1790,7 +1746,7 @@ GECCO_API int gecco_crf_forest_fit_batch(int32_t device, int32_t n_problems, int
     int rc = forest_fit_batch_check(n_problems, n_features, n_outputs, n_trees, max_features, problems.data());
     if (rc) return rc;
     if ((rc = check_device(device))) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     std::vector<std::unique_ptr<Forest>> f;
     if ((rc = forest_fit_batch(device, n_problems, n_features, n_outputs, n_trees, max_features, problems.data(), /*lone=*/false,
                                &f)))
@@ -1828,7 +1784,7 @@ GECCO_API int gecco_crf_forest_export(const gecco_crf_forest *h, int32_t tree, i
         set_error("gecco_crf_forest_export: null forest");
         return GECCO_CRF_EINVAL;
     }
-    DeviceGuard guard;
+    DeviceScope guard;
     return forest_export(h->f.get(), tree, children_left, children_right, feature, threshold, impurity, n_node_samples,
                          weighted_n_node_samples, value);
     GECCO_GUARD_END
@@ -1849,7 +1805,7 @@ GECCO_API int gecco_crf_forest_predict(const gecco_crf_forest *h, int32_t n_rows
         set_error("forest_predict: null buffer");
         return GECCO_CRF_EINVAL;
     }
-    DeviceGuard guard;
+    DeviceScope guard;
     const Forest *f = h->f.get();
     return forest_predict_batch(&f, 1, &n_rows, &x, &posit);
     GECCO_GUARD_END
@@ -1863,13 +1819,13 @@ GECCO_API int gecco_crf_forest_predict_batch(const gecco_crf_forest *const *h, i
         for (int32_t k = 0; k < n_problems; ++k) f.push_back(h[k] ? h[k]->f.get() : nullptr);
     int rc = forest_predict_batch_check(h ? f.data() : nullptr, n_problems, n_rows, x, posit);
     if (rc) return rc;
-    DeviceGuard guard;
+    DeviceScope guard;
     return forest_predict_batch(f.data(), n_problems, n_rows, x, posit);
     GECCO_GUARD_END
 }
 
 GECCO_API void gecco_crf_forest_free(gecco_crf_forest *h) {
     if (!h) return;
-    DeviceGuard guard;
+    DeviceScope guard;
     delete h;
 }

@@ -156,17 +156,6 @@ int fail(const std::string &msg) {
     return GECCO_CRF_EINVAL;
 }
 
-struct FisherBuffers {
-    int64_t *d_tables = nullptr;
-    double *d_p = nullptr;
-    hipStream_t stream = nullptr;
-    ~FisherBuffers() {
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_p) (void)hipFree(d_p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
 }  // namespace
 
 int fisher_check(const int64_t *tables, int64_t n, const double *pvalue) {
@@ -185,24 +174,25 @@ int fisher_check(const int64_t *tables, int64_t n, const double *pvalue) {
 }
 
 int fisher_exact(int32_t device, const int64_t *tables, int64_t n, double *pvalue) {
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    int rc = set_device(device);
     if (rc) return rc;
-    FisherBuffers B;
-    if ((rc = check_hip(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
-    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&B.d_tables), size_t(n) * 4 * sizeof(int64_t)), "fisher alloc")))
-        return rc;
-    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&B.d_p), size_t(n) * sizeof(double)), "fisher alloc"))) return rc;
-    if ((rc = check_hip(hipMemcpyAsync(B.d_tables, tables, size_t(n) * 4 * sizeof(int64_t), hipMemcpyHostToDevice, B.stream),
+    Stream stream;
+    DeviceBlock<int64_t> d_tables;
+    DeviceBlock<double> d_p;
+    if ((rc = stream.create())) return rc;
+    if ((rc = d_tables.alloc(size_t(n) * 4, "fisher alloc"))) return rc;
+    if ((rc = d_p.alloc(size_t(n), "fisher alloc"))) return rc;
+    if ((rc = check_hip(hipMemcpyAsync(d_tables.get(), tables, size_t(n) * 4 * sizeof(int64_t), hipMemcpyHostToDevice, stream.get()),
                         "fisher upload")))
         return rc;
     const int64_t want = (n + kFisherWavesPerBlock - 1) / kFisherWavesPerBlock;
     const unsigned blocks = unsigned(want < kFisherMaxBlocks ? want : kFisherMaxBlocks);
-    fisher_kernel<<<blocks, kFisherWave * kFisherWavesPerBlock, 0, B.stream>>>(B.d_tables, n, B.d_p);
+    fisher_kernel<<<blocks, kFisherWave * kFisherWavesPerBlock, 0, stream.get()>>>(d_tables.get(), n, d_p.get());
     if ((rc = check_hip(hipGetLastError(), "fisher kernel"))) return rc;
-    if ((rc = check_hip(hipMemcpyAsync(pvalue, B.d_p, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, B.stream),
+    if ((rc = check_hip(hipMemcpyAsync(pvalue, d_p.get(), size_t(n) * sizeof(double), hipMemcpyDeviceToHost, stream.get()),
                         "fisher download")))
         return rc;
-    return check_hip(hipStreamSynchronize(B.stream), "fisher synchronize");
+    return check_hip(hipStreamSynchronize(stream.get()), "fisher synchronize");
 }
 
 }  // namespace gecco

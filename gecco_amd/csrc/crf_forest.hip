@@ -674,18 +674,6 @@ struct Layout {
     }
 };
 
-struct DeviceBuffer {
-    void *p = nullptr;
-    ~DeviceBuffer() {
-        if (p) (void)hipFree(p);
-    }
-    int alloc(size_t bytes, const char *what) { return check_hip(hipMalloc(&p, bytes ? bytes : 1), what); }
-    template <typename T>
-    T *at(size_t off) const {
-        return reinterpret_cast<T *>(static_cast<char *>(p) + off);
-    }
-};
-
 template <typename T>
 void stage(std::vector<unsigned char> &host, size_t off, const T *src, size_t n) {
     if (n) std::memcpy(host.data() + off, src, n * sizeof(T));
@@ -744,10 +732,6 @@ std::string fit_prefix(bool lone, int32_t k) {
 
 }  // namespace
 
-Forest::~Forest() {
-    if (d_slab) (void)hipFree(d_slab);
-}
-
 int forest_fit_check(int32_t n_samples, int32_t n_features, const int32_t *col_ptr, const int32_t *row_idx, const float *values,
                      int32_t n_outputs, const uint8_t *n_classes, const uint8_t *y, int32_t n_trees, const int32_t *sample_counts,
                      const uint32_t *rand_state, int32_t max_features) {
@@ -773,7 +757,7 @@ int forest_fit_batch_check(int32_t n_problems, int32_t n_features, int32_t n_out
 
 int forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int32_t n_outputs, int32_t n_trees,
                      int32_t max_features, const ForestProblem *problems, bool lone, std::vector<std::unique_ptr<Forest>> *out) {
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    int rc = set_device(device);
     if (rc) return rc;
     const int32_t K = n_problems, F = n_features, T = n_trees;
     // host side, per problem: CSR of the nonzero-valued entries, class bits, the output layout
@@ -825,7 +809,7 @@ int forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int
     Layout work = in;  // not uploaded: every problem's stacks, then node_count / max_depth / status of all K x T trees
     for (int32_t k = 0; k < K; ++k) host[size_t(k)].stack = work.add<int32_t>(size_t(T) * (size_t(problems[k].n_samples) + 1) * 6);
     const size_t result_at = work.add<int32_t>(size_t(3) * K * T);
-    DeviceBuffer d;
+    DeviceBlock<char> d;
     if ((rc = d.alloc(work.bytes, "forest alloc"))) return rc;
     std::vector<unsigned char> up(in.bytes);
     std::vector<FitArgs> table(static_cast<size_t>(K));
@@ -847,8 +831,8 @@ int forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int
                      n_node = o.add<int32_t>(slots), threshold = o.add<double>(slots), impurity = o.add<double>(slots),
                      weighted = o.add<double>(slots), value = o.add<double>(slots * n_outputs * h.mc),
                      ncls = o.add<uint8_t>(size_t(n_outputs));
-        if ((rc = check_hip(hipMalloc(&f->d_slab, o.bytes), "forest alloc"))) return rc;
-        char *base = static_cast<char *>(f->d_slab);
+        if ((rc = f->d_slab.alloc(o.bytes, "forest alloc"))) return rc;
+        char *base = f->d_slab.get();
         f->d_left = reinterpret_cast<int32_t *>(base + left);
         f->d_right = reinterpret_cast<int32_t *>(base + right);
         f->d_feature = reinterpret_cast<int32_t *>(base + feature);
@@ -900,7 +884,7 @@ int forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int
         own[size_t(k)] = std::move(f);
     }
     stage(up, table_at, table.data(), table.size());
-    if ((rc = check_hip(hipMemcpy(d.p, up.data(), up.size(), hipMemcpyHostToDevice), "forest upload"))) return rc;
+    if ((rc = check_hip(hipMemcpy(d.get(), up.data(), up.size(), hipMemcpyHostToDevice), "forest upload"))) return rc;
     forest_fit_kernel<<<unsigned(K) * unsigned(T), kThreads>>>(d.at<FitArgs>(table_at), T);
     if ((rc = check_hip(hipGetLastError(), "forest fit kernel"))) return rc;
     if ((rc = check_hip(hipDeviceSynchronize(), "forest fit"))) return rc;
@@ -929,7 +913,7 @@ int forest_fit_batch(int32_t device, int32_t n_problems, int32_t n_features, int
 int forest_export(const Forest *f, int32_t tree, int32_t *left, int32_t *right, int32_t *feature, double *threshold,
                   double *impurity, int32_t *n_node_samples, double *weighted_n_node_samples, double *value) {
     if (!f || tree < 0 || tree >= f->n_trees) return fail("forest_export: no such tree");
-    int rc = check_hip(hipSetDevice(f->device), "hipSetDevice");
+    int rc = set_device(f->device);
     if (rc) return rc;
     const size_t nc = size_t(f->node_count[size_t(tree)]), off = size_t(tree) * f->cap;
     const size_t vs = size_t(f->n_outputs) * f->max_n_classes;
@@ -979,9 +963,9 @@ int forest_predict_batch(const Forest *const *f, int32_t n_problems, const int32
     if (block_problem.empty()) return GECCO_CRF_OK;  // no rows at all: no device is touched
     // the table and the block map go up in one copy of their own, after the rows
     const size_t small_at = in.bytes, table_at = in.add<PredictArgs>(size_t(K)), map_at = in.add<int32_t>(block_problem.size());
-    int rc = check_hip(hipSetDevice(f[0]->device), "hipSetDevice");
+    int rc = set_device(f[0]->device);
     if (rc) return rc;
-    DeviceBuffer d;
+    DeviceBlock<char> d;
     if ((rc = d.alloc(in.bytes + out.bytes, "forest predict alloc"))) return rc;
     std::vector<unsigned char> up(in.bytes - small_at);
     for (int32_t k = 0; k < K; ++k) {

@@ -4,6 +4,8 @@
 #include <memory>
 #include <vector>
 
+#include "crf_hip_own.hpp"
+
 namespace gecco {
 
 // Range of gecco_crf_forest_fit: one workgroup per tree keeps the tree's sample and feature arrays in LDS.
@@ -18,11 +20,10 @@ struct Forest {
     std::vector<uint8_t> n_classes;
     std::vector<int32_t> node_count, max_depth;
     // device, [n_trees][cap] (value: [n_trees][cap][n_outputs][max_n_classes]); all of them lie in the one allocation d_slab
-    void *d_slab = nullptr;
+    DeviceBlock<char> d_slab;
     int32_t *d_left = nullptr, *d_right = nullptr, *d_feature = nullptr, *d_n_node = nullptr;
     double *d_threshold = nullptr, *d_impurity = nullptr, *d_weighted = nullptr, *d_value = nullptr;
     uint8_t *d_ncls = nullptr;
-    ~Forest();
 };
 
 // What differs between the problems of one forest_fit_batch: the per-problem arguments of gecco_crf_forest_fit.

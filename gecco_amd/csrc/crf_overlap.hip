@@ -319,50 +319,44 @@ int fail(const std::string &msg) {
 inline unsigned grid(int64_t n) { return unsigned((n + kOT - 1) / kOT); }
 
 struct JoinBuffers {  // device buffers and the stream of one call, released on every way out
-    hipStream_t stream = nullptr;
-    void *bufs[24] = {};
-    int nbuf = 0;
+    Stream stream;  // (before the blocks: destroyed after them)
+    std::vector<DeviceBlock<char>> bufs;
     ~JoinBuffers() {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (int i = 0; i < nbuf; ++i) (void)hipFree(bufs[i]);
-        if (stream) (void)hipStreamDestroy(stream);
+        if (stream.get()) (void)hipStreamSynchronize(stream.get());
     }
     template <class T>
     int alloc(T **p, int64_t n, const char *what) {
-        if (nbuf == int(sizeof(bufs) / sizeof(bufs[0]))) return fail("internal error: too many buffers");
-        void *q = nullptr;
-        int rc = check_hip(hipMalloc(&q, size_t(n > 0 ? n : 1) * sizeof(T)), what);
-        if (rc) return rc;
-        bufs[nbuf++] = q;
-        *p = static_cast<T *>(q);
-        return GECCO_CRF_OK;
+        bufs.emplace_back();
+        int rc = bufs.back().alloc(size_t(n > 0 ? n : 1) * sizeof(T), what);
+        *p = bufs.back().at<T>(0);
+        return rc;
     }
     template <class T>
     int upload(T **p, const T *src, int64_t n, const char *what) {
         int rc = alloc(p, n, what);
         if (rc || n <= 0) return rc;
-        return check_hip(hipMemcpyAsync(*p, src, size_t(n) * sizeof(T), hipMemcpyHostToDevice, stream), what);
+        return check_hip(hipMemcpyAsync(*p, src, size_t(n) * sizeof(T), hipMemcpyHostToDevice, stream.get()), what);
     }
 };
 
 // exclusive scan of in[0, n) into out[0, n] (out[n] = total) on the arena's stream
 int exclusive_scan(JoinBuffers &A, const int32_t *d_in, int64_t n, int64_t *d_out) {
-    if (n == 0) return check_hip(hipMemsetAsync(d_out, 0, sizeof(int64_t), A.stream), "scan");
+    if (n == 0) return check_hip(hipMemsetAsync(d_out, 0, sizeof(int64_t), A.stream.get()), "scan");
     const int64_t nb = (n + kScanTile - 1) / kScanTile;
     if (nb > INT32_MAX - 1) return fail("scan: too many items");
     int64_t *d_bsum = nullptr;
     int rc = A.alloc(&d_bsum, nb + 1, "scan alloc");
     if (rc) return rc;
-    scan_tile_sums<<<unsigned(nb), kOT, 0, A.stream>>>(d_in, n, d_bsum);
-    scan_block_sums<<<1, kOT, 0, A.stream>>>(d_bsum, int(nb));
-    scan_tiles<<<unsigned(nb), kOT, 0, A.stream>>>(d_in, n, d_bsum, int(nb), d_out);
+    scan_tile_sums<<<unsigned(nb), kOT, 0, A.stream.get()>>>(d_in, n, d_bsum);
+    scan_block_sums<<<1, kOT, 0, A.stream.get()>>>(d_bsum, int(nb));
+    scan_tiles<<<unsigned(nb), kOT, 0, A.stream.get()>>>(d_in, n, d_bsum, int(nb), d_out);
     return check_hip(hipGetLastError(), "scan kernels");
 }
 
 int download_sync(JoinBuffers &A, void *dst, const void *src, size_t bytes, const char *what) {
-    int rc = check_hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, A.stream), what);
+    int rc = check_hip(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, A.stream.get()), what);
     if (rc) return rc;
-    return check_hip(hipStreamSynchronize(A.stream), what);
+    return check_hip(hipStreamSynchronize(A.stream.get()), what);
 }
 
 }  // namespace
@@ -400,10 +394,10 @@ int cluster_overlaps(int32_t device, int32_t n_genes, const int32_t *gene_seq, c
         member_ptr_out[0] = 0;
         return GECCO_CRF_OK;
     }
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    int rc = set_device(device);
     if (rc) return rc;
     JoinBuffers A;
-    if ((rc = check_hip(hipStreamCreateWithFlags(&A.stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+    if ((rc = A.stream.create())) return rc;
     int32_t *d_seq = nullptr, *d_cptr = nullptr, *d_sptr = nullptr, *d_cnt = nullptr, *d_members = nullptr;
     int64_t *d_start = nullptr, *d_end = nullptr, *d_cs = nullptr, *d_ce = nullptr, *d_cmax = nullptr, *d_blk = nullptr,
             *d_check = nullptr, *d_mptr = nullptr;
@@ -421,42 +415,41 @@ int cluster_overlaps(int32_t device, int32_t n_genes, const int32_t *gene_seq, c
     // 1. the genes' order, and the longest gene
     int64_t check[2] = {0, 0};
     if (n > 0) {
-        check_genes<<<unsigned(nbg), kOT, 0, A.stream>>>(n_genes, d_seq, d_start, d_end, n_seqs, d_blk);
-        reduce_check<<<1, kOT, 0, A.stream>>>(d_blk, int(nbg), d_check);
+        check_genes<<<unsigned(nbg), kOT, 0, A.stream.get()>>>(n_genes, d_seq, d_start, d_end, n_seqs, d_blk);
+        reduce_check<<<1, kOT, 0, A.stream.get()>>>(d_blk, int(nbg), d_check);
         if ((rc = check_hip(hipGetLastError(), "check kernels"))) return rc;
         if ((rc = download_sync(A, check, d_check, sizeof(check), "D2H check"))) return rc;
         if (check[0])
             return fail("cluster_overlaps: genes must be grouped by sequence code (0 <= code < n_seqs, non-decreasing), "
                         "sorted by start inside a sequence, with coordinates below 2^60");
-    } else if ((rc = check_hip(hipMemsetAsync(d_check, 0, sizeof(check), A.stream), "memset check"))) {
+    } else if ((rc = check_hip(hipMemsetAsync(d_check, 0, sizeof(check), A.stream.get()), "memset check"))) {
         return rc;
     }
     // 2. labels: one thread per gene over the clusters' running maximum of ends
-    if (n_seqs > 0) cluster_runmax<<<grid(n_seqs), kOT, 0, A.stream>>>(n_seqs, d_cptr, d_ce, d_cmax);
+    if (n_seqs > 0) cluster_runmax<<<grid(n_seqs), kOT, 0, A.stream.get()>>>(n_seqs, d_cptr, d_ce, d_cmax);
     if (n > 0)
-        label_genes<<<grid(n), kOT, 0, A.stream>>>(n_genes, d_seq, d_start, d_end, d_cptr, d_cs, d_ce, d_cmax, d_label);
+        label_genes<<<grid(n), kOT, 0, A.stream.get()>>>(n_genes, d_seq, d_start, d_end, d_cptr, d_cs, d_ce, d_cmax, d_label);
     // 3. members: count -> scan -> fill, one thread per cluster
-    seq_gene_ptr<<<grid(int64_t(n_seqs) + 1), kOT, 0, A.stream>>>(n_genes, d_seq, n_seqs, d_sptr);
+    seq_gene_ptr<<<grid(int64_t(n_seqs) + 1), kOT, 0, A.stream.get()>>>(n_genes, d_seq, n_seqs, d_sptr);
     if (m > 0)
-        count_members<<<grid(m), kOT, 0, A.stream>>>(m, n_seqs, d_cptr, d_cs, d_ce, d_sptr, d_start, d_end, d_check, d_cnt);
+        count_members<<<grid(m), kOT, 0, A.stream.get()>>>(m, n_seqs, d_cptr, d_cs, d_ce, d_sptr, d_start, d_end, d_check, d_cnt);
     if ((rc = check_hip(hipGetLastError(), "join kernels"))) return rc;
     if ((rc = exclusive_scan(A, d_cnt, m, d_mptr))) return rc;
     int64_t total = 0;
     if ((rc = download_sync(A, &total, d_mptr + m, sizeof(total), "D2H member count"))) return rc;
     if (total > INT32_MAX) return fail("cluster_overlaps: more than 2^31 - 1 cluster members");
     *n_members = total;
-    if (n > 0 && (rc = check_hip(hipMemcpyAsync(label_out, d_label, size_t(n), hipMemcpyDeviceToHost, A.stream), "D2H labels")))
+    if (n > 0 && (rc = check_hip(hipMemcpyAsync(label_out, d_label, size_t(n), hipMemcpyDeviceToHost, A.stream.get()), "D2H labels")))
         return rc;
-    int64_t *mptr = new int64_t[size_t(m) + 1];
-    rc = download_sync(A, mptr, d_mptr, (size_t(m) + 1) * sizeof(int64_t), "D2H member_ptr");
+    std::vector<int64_t> mptr(size_t(m) + 1);
+    rc = download_sync(A, mptr.data(), d_mptr, (size_t(m) + 1) * sizeof(int64_t), "D2H member_ptr");
     for (int32_t k = 0; !rc && k <= m; ++k) member_ptr_out[k] = int32_t(mptr[k]);
-    delete[] mptr;
     if (rc) return rc;
     if (total > max_members) return fail("cluster_overlaps: member_gene_out too small (n_members holds the size needed)");
     if (total == 0) return GECCO_CRF_OK;
     if (!member_gene_out) return fail("cluster_overlaps: null member_gene_out");
     if ((rc = A.alloc(&d_members, total, "alloc members"))) return rc;
-    fill_members<<<grid(m), kOT, 0, A.stream>>>(m, n_seqs, d_cptr, d_cs, d_ce, d_sptr, d_start, d_end, d_check, d_mptr,
+    fill_members<<<grid(m), kOT, 0, A.stream.get()>>>(m, n_seqs, d_cptr, d_cs, d_ce, d_sptr, d_start, d_end, d_check, d_mptr,
                                                 d_members);
     if ((rc = check_hip(hipGetLastError(), "fill kernel"))) return rc;
     return download_sync(A, member_gene_out, d_members, size_t(total) * sizeof(int32_t), "D2H members");
@@ -486,10 +479,10 @@ int composition_members_check(const int32_t *member_ptr, int32_t n_clusters, con
 int composition_members(int32_t device, const int32_t *member_ptr, int32_t n_clusters, const int32_t *member_gene,
                         const int32_t *dom_ptr, int32_t n_genes, const int32_t *dom_col, const double *dom_weight,
                         int32_t n_cols, int32_t normalize, double *comp_out) {
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    int rc = set_device(device);
     if (rc) return rc;
     JoinBuffers A;
-    if ((rc = check_hip(hipStreamCreateWithFlags(&A.stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+    if ((rc = A.stream.create())) return rc;
     const int64_t M = member_ptr[n_clusters], rows = dom_ptr[n_genes], m = n_clusters;
     int32_t *d_mptr = nullptr, *d_members = nullptr, *d_dptr = nullptr, *d_dcol = nullptr, *d_deg = nullptr, *d_vptr32 = nullptr,
             *d_gcol = nullptr, *d_seg = nullptr;
@@ -502,7 +495,7 @@ int composition_members(int32_t device, const int32_t *member_ptr, int32_t n_clu
         (rc = A.alloc(&d_vptr32, M + 1, "alloc row offsets")) || (rc = A.alloc(&d_seg, 4 * m, "alloc segments")) ||
         (rc = A.alloc(&d_out, m * int64_t(n_cols), "alloc compositions")))
         return rc;
-    if (M > 0) member_degrees<<<grid(M), kOT, 0, A.stream>>>(M, d_members, d_dptr, d_deg);
+    if (M > 0) member_degrees<<<grid(M), kOT, 0, A.stream.get()>>>(M, d_members, d_dptr, d_deg);
     if ((rc = check_hip(hipGetLastError(), "degree kernel"))) return rc;
     if ((rc = exclusive_scan(A, d_deg, M, d_vptr))) return rc;
     int64_t total = 0;
@@ -513,13 +506,13 @@ int composition_members(int32_t device, const int32_t *member_ptr, int32_t n_clu
         (rc = A.alloc(&d_tmp, total, "alloc composition scratch")))
         return rc;
     if (M > 0)
-        gather_rows<<<grid(M), kOT, 0, A.stream>>>(M, d_members, d_dptr, d_dcol, d_dw, d_vptr, d_vptr32, d_gcol, d_gw);
-    else if ((rc = check_hip(hipMemsetAsync(d_vptr32, 0, sizeof(int32_t), A.stream), "memset row offsets")))
+        gather_rows<<<grid(M), kOT, 0, A.stream.get()>>>(M, d_members, d_dptr, d_dcol, d_dw, d_vptr, d_vptr32, d_gcol, d_gw);
+    else if ((rc = check_hip(hipMemsetAsync(d_vptr32, 0, sizeof(int32_t), A.stream.get()), "memset row offsets")))
         return rc;
-    member_segments<<<grid(m), kOT, 0, A.stream>>>(n_clusters, d_mptr, d_seg);
+    member_segments<<<grid(m), kOT, 0, A.stream.get()>>>(n_clusters, d_mptr, d_seg);
     if ((rc = check_hip(hipGetLastError(), "gather kernels"))) return rc;
     if ((rc = check_hip(launch_composition(d_seg, n_clusters, d_vptr32, d_gcol, d_gw, d_tmp, n_cols, normalize ? 1 : 0, d_out,
-                                           A.stream),
+                                           A.stream.get()),
                         "composition launch")))
         return rc;
     return download_sync(A, comp_out, d_out, size_t(m) * size_t(n_cols) * sizeof(double), "D2H compositions");

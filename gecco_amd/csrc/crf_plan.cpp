@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <memory>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -20,50 +21,13 @@ int check_hip(hipError_t e, const char *what) {
     return GECCO_CRF_EHIP;
 }
 
-namespace {
-template <class T>
-int upload(T **dst, const T *src, size_t n, const char *what) {
-    *dst = nullptr;
-    if (n == 0) n = 1;  // keep pointers valid
-    int rc = check_hip(hipMalloc(reinterpret_cast<void **>(dst), n * sizeof(T)), what);
-    if (rc) return rc;
-    if (src) rc = check_hip(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice), what);
-    return rc;
-}
-}  // namespace
-
 Model::~Model() {
     for (auto &e : sessions) session_destroy(e.second);  // before the tables their plans point at
     for (DeviceTables *t : dev_tables) {
         if (!t) continue;
-        int prev = 0;
-        if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(t->device) == hipSuccess) {
-            (void)hipFree(t->wtab);
-            (void)hipFree(t->wtab2[0]);
-            (void)hipFree(t->wtab2[1]);
-            (void)hipFree(t->exp_trans);
-            (void)hipFree(t->trans);
-            (void)hipFree(t->rtab[0]);
-            (void)hipFree(t->rtab[1]);
-            (void)hipFree(t->ptab[0]);
-            (void)hipFree(t->ptab[1]);
-            (void)hipSetDevice(prev);
-        }
-        delete t;  // without a usable device the allocations die with the context
+        DeviceScope scope(t->device);
+        delete t;  // (the blocks free themselves; without a usable device the allocations die with the context)
     }
-}
-
-static void free_device_tables(DeviceTables *t) {
-    (void)hipFree(t->wtab);
-    (void)hipFree(t->wtab2[0]);
-    (void)hipFree(t->wtab2[1]);
-    (void)hipFree(t->exp_trans);
-    (void)hipFree(t->trans);
-    (void)hipFree(t->rtab[0]);
-    (void)hipFree(t->rtab[1]);
-    (void)hipFree(t->ptab[0]);
-    (void)hipFree(t->ptab[1]);
-    delete t;
 }
 
 int get_device_tables(const Model &m, int device, const DeviceTables **out) {
@@ -73,23 +37,23 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
             *out = t;
             return GECCO_CRF_OK;
         }
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    int rc = set_device(device);
     if (rc) return rc;
-    auto *t = new DeviceTables();
+    auto t = std::make_unique<DeviceTables>();
     t->device = device;
     const size_t A = size_t(m.A), L = size_t(m.L);
     std::vector<double> et(L * L);
     for (size_t i = 0; i < L * L; ++i) et[i] = std::exp(m.trans[i]);
     for (double v : m.state) t->wmax_abs = std::max(t->wmax_abs, std::fabs(v));
     for (double v : m.trans) t->tmax_abs = std::max(t->tmax_abs, std::fabs(v));
-    rc = upload(&t->wtab, m.state.data(), A * L, "upload state weights");
-    if (!rc) rc = upload(&t->exp_trans, et.data(), L * L, "upload transitions");
-    if (!rc) rc = upload(&t->trans, m.trans.data(), L * L, "upload transitions");
+    rc = t->wtab.upload(m.state.data(), A * L, "upload state weights");
+    if (!rc) rc = t->exp_trans.upload(et.data(), L * L, "upload transitions");
+    if (!rc) rc = t->trans.upload(m.trans.data(), L * L, "upload transitions");
     if (!rc && m.L == 2) {
         std::vector<double2> w2(A ? A : 1);
         for (int label = 0; label < 2 && !rc; ++label) {
             for (size_t a = 0; a < A; ++a) w2[a] = make_double2(m.state[a * 2 + (1 - label)], m.state[a * 2 + label]);
-            rc = upload(&t->wtab2[label], w2.data(), A, "upload state weight pairs");
+            rc = t->wtab2[label].upload(w2, "upload state weight pairs");
         }
         // r = mu01 exp(d) in the window kernel (mu_exp_tab): exp(d) = 2^e 2^(j/32) exp(r'), |r'| <= ln2/64; the table holds
         // mu01 2^(j/32), rounded once from extended precision
@@ -99,7 +63,7 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
             const long double lmu = T(o, label) + T(label, o) - 2.0L * T(o, o);
             double tab[32];
             for (int j = 0; j < 32; ++j) tab[j] = double(expl(lmu + (long double)j * 0.693147180559945309417232121458L / 32.0L));
-            rc = upload(&t->rtab[label], tab, 32, "upload exp table");
+            rc = t->rtab[label].upload(tab, 32, "upload exp table");
         }
         // the factor table of the product-form slot constants, in the same precision (build_slot_table)
         for (int label = 0; label < 2 && !rc; ++label) {
@@ -107,13 +71,10 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
             build_slot_table(m, label, st);
             t->slot_dmax = st.dmax;
             t->slot_prod_max_cnt = st.prod_max_cnt;
-            rc = upload(&t->ptab[label], reinterpret_cast<const double2 *>(st.pairs.data()), A + 1, "upload slot factor table");
+            rc = t->ptab[label].upload(reinterpret_cast<const double2 *>(st.pairs.data()), A + 1, "upload slot factor table");
         }
     }
-    if (rc) {
-        free_device_tables(t);
-        return rc;
-    }
+    if (rc) return rc;
     if (m.L == 2) {
         for (int label = 0; label < 2; ++label) {
             DeviceTables::WinConsts &c = t->win[label];
@@ -153,17 +114,9 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
         fill_exp_coefficients(q.expc);
         t->consts_ok = true;
     }
-    m.dev_tables.push_back(t);
-    *out = t;
+    *out = t.get();
+    m.dev_tables.push_back(t.release());
     return GECCO_CRF_OK;
-}
-
-// hipSetDevice only when the calling thread is on another device (the C ABI's guard restores the caller's device afterwards):
-// a launch-bound step used to make four runtime calls for this
-static inline int use_device(int device) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur == device) return GECCO_CRF_OK;
-    return check_hip(hipSetDevice(device), "hipSetDevice");
 }
 
 int Arena::reserve(size_t bytes, const char *what) {
@@ -189,25 +142,15 @@ void Arena::release() {
     cap = 0;
 }
 
+// The blocks and the side stream free themselves after this body, with the plan's device current; `home` then hands the
+// caller's device back.
 Plan::~Plan() {
-    if (device >= 0) {
-        int prev = 0;
-        if (hipGetDevice(&prev) == hipSuccess && hipSetDevice(device) == hipSuccess) {
-            tables.release();
-            seq.release();
-            (void)hipFree(d_seq_ws);
-            (void)hipFree(d_win_scratch);
-            (void)hipFree(d_gen_ws);
-            (void)hipFree(gen_tab[0].d);
-            (void)hipFree(gen_tab[1].d);
-            (void)hipFree(d_seg_ws);
-            (void)hipFree(d_all_tiles);
-            if (side_stream) (void)hipStreamDestroy(side_stream);
-            if (ev_fork) (void)hipEventDestroy(ev_fork);
-            if (ev_join) (void)hipEventDestroy(ev_join);
-            (void)hipSetDevice(prev);
-        }
-    }
+    if (device < 0) return;
+    home.enter(device);
+    tables.release();
+    seq.release();
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (ev_join) (void)hipEventDestroy(ev_join);
 }
 
 // Steps after which the un-normalised DP vectors are rescaled by a power of two.
@@ -256,22 +199,6 @@ static inline void set_bit_range(uint64_t *bits, int64_t lo, int64_t hi) {
     for (int64_t w = w0 + 1; w < w1; ++w) bits[w] = ~0ull;
     bits[w1] |= m1;
 }
-
-namespace {
-// grow-only device workspace (hipFree waits for the launches that may still use the old block)
-template <class T>
-int grow_ws(T *&ptr, size_t &cap, size_t bytes, const char *what) {
-    if (ptr && bytes <= cap) return GECCO_CRF_OK;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    int rc = check_hip(hipMalloc(reinterpret_cast<void **>(&ptr), want), what);
-    if (rc) return rc;
-    cap = want;
-    return GECCO_CRF_OK;
-}
-}  // namespace
 
 // The tile table of a window kernel whose workgroups own `tile_out` output slots each: per tile the contigs in reach and
 // whether its slots map to genes by a constant shift.  irr_prefix[k + 1] - irr_prefix[k] = 1 where contig k is padded or a
@@ -463,7 +390,7 @@ int plan_build(const Model &m, int device, const int32_t *contig_ptr, int32_t n_
     fill_tile_desc(p, irr_prefix, p.tile_out, p.ntiles, p.tile_desc.data());
     if (device < 0) return GECCO_CRF_OK;
 
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
+    int rc = set_device(device);
     if (rc) return rc;
     if ((rc = get_device_tables(m, device, &p.tables_model))) return rc;
     // one pinned block -> one device block, one copy
@@ -539,7 +466,7 @@ int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig =
         }
         std::lock_guard<std::mutex> lock(p.ws_mutex);
         Plan::GenTab &tab = p.gen_tab[chunk_min_len >= 0 ? 1 : 0];
-        if (!tab.d || tab.chunk != C || tab.min_len != chunk_min_len) {
+        if (!tab.d.get() || tab.chunk != C || tab.min_len != chunk_min_len) {
             std::vector<int32_t> ch_g0, ch_contig, cc_ptr;
             cc_ptr.push_back(0);
             for (int32_t c = 0; c < p.n_contigs; ++c) {
@@ -556,16 +483,14 @@ int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig =
             Carver img_at;
             img_at.take(ch_g0.size() * 4);
             const size_t o1 = img_at.take(n_ch * 4 + 4), o2 = img_at.take(cc_ptr.size() * 4), total = img_at.off;
-            if (tab.d) (void)hipFree(tab.d);
-            tab.d = nullptr;
             tab.chunk = 0;
-            int rc = check_hip(hipMalloc(reinterpret_cast<void **>(&tab.d), total), "hipMalloc chunk tables");
+            int rc = tab.d.alloc(total, "hipMalloc chunk tables");
             if (rc) return rc;
             std::vector<char> img(total, 0);
             std::memcpy(img.data(), ch_g0.data(), ch_g0.size() * 4);
             std::memcpy(img.data() + o1, ch_contig.data(), n_ch * 4);
             std::memcpy(img.data() + o2, cc_ptr.data(), cc_ptr.size() * 4);
-            if ((rc = check_hip(hipMemcpy(tab.d, img.data(), total, hipMemcpyHostToDevice), "upload chunk tables"))) return rc;
+            if ((rc = check_hip(hipMemcpy(tab.d.get(), img.data(), total, hipMemcpyHostToDevice), "upload chunk tables"))) return rc;
             tab.chunk = C;
             tab.min_len = chunk_min_len;
             tab.nch = n_ch;
@@ -596,12 +521,12 @@ int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig =
     }
     {
         std::lock_guard<std::mutex> lock(p.ws_mutex);
-        const size_t cap0 = p.gen_ws_cap;
-        int rc = grow_ws(p.d_gen_ws, p.gen_ws_cap, ws.off, "hipMalloc general-L workspace");
+        const size_t cap0 = p.gen_ws.capacity();
+        int rc = p.gen_ws.reserve(ws.off, "hipMalloc general-L workspace");
         if (rc) return rc;
-        if (p.gen_ws_cap != cap0 && (rc = check_hip(hipMemsetAsync(p.d_gen_ws, 0, b_fix, stream), "memset contig flags"))) return rc;
+        if (p.gen_ws.capacity() != cap0 && (rc = check_hip(hipMemsetAsync(p.gen_ws.get(), 0, b_fix, stream), "memset contig flags"))) return rc;
     }
-    char *w = p.d_gen_ws;
+    char *w = p.gen_ws.get();
     a = GenArgs{};
     a.vit_stats = reinterpret_cast<uint32_t *>(w);
     a.fix_flag = reinterpret_cast<uint8_t *>(w + 16);
@@ -613,9 +538,9 @@ int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig =
     a.v_tmax = p.tables_model->tmax_abs;
     a.gene_ptr = csr.gene_ptr;
     a.attr_id = csr.attr_id;
-    a.wtab = p.tables_model->wtab;
-    a.exp_trans = p.tables_model->exp_trans;
-    a.trans = p.tables_model->trans;
+    a.wtab = p.tables_model->wtab.get();
+    a.exp_trans = p.tables_model->exp_trans.get();
+    a.trans = p.tables_model->trans.get();
     a.contig_ptr = p.d_contig_ptr;
     a.L = m.L;
     a.A = m.A;
@@ -630,9 +555,9 @@ int fill_gen_args(Plan &p, const DeviceCsr &csr, GenArgs &a, bool whole_contig =
     a.back = reinterpret_cast<uint8_t *>(w + o_back);
     if (chunked && nch) {
         const Plan::GenTab &tab = p.gen_tab[chunk_min_len >= 0 ? 1 : 0];
-        a.ch_g0 = reinterpret_cast<const int32_t *>(tab.d);
-        a.ch_contig = reinterpret_cast<const int32_t *>(tab.d + tab.off1);
-        a.cc_ptr = reinterpret_cast<const int32_t *>(tab.d + tab.off2);
+        a.ch_g0 = tab.d.at<const int32_t>(0);
+        a.ch_contig = tab.d.at<const int32_t>(tab.off1);
+        a.cc_ptr = tab.d.at<const int32_t>(tab.off2);
         a.n_chunks = int32_t(nch);
         a.chM = reinterpret_cast<double *>(w + o_chM);
         a.chV = reinterpret_cast<double *>(w + o_chV);
@@ -687,16 +612,16 @@ int32_t choose_wave_split(const Plan &p, const char *env, bool automatic, double
 // makes `stream` wait for them
 int fork_tail(Plan &p, hipStream_t stream) {
     int rc;
-    if (!p.side_stream) {
-        if ((rc = check_hip(hipStreamCreateWithFlags(&p.side_stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+    if (!p.side_stream.get()) {
+        if ((rc = p.side_stream.create())) return rc;
         if ((rc = check_hip(hipEventCreateWithFlags(&p.ev_fork, hipEventDisableTiming), "hipEventCreate"))) return rc;
         if ((rc = check_hip(hipEventCreateWithFlags(&p.ev_join, hipEventDisableTiming), "hipEventCreate"))) return rc;
     }
     if ((rc = check_hip(hipEventRecord(p.ev_fork, stream), "hipEventRecord"))) return rc;
-    return check_hip(hipStreamWaitEvent(p.side_stream, p.ev_fork, 0), "hipStreamWaitEvent");
+    return check_hip(hipStreamWaitEvent(p.side_stream.get(), p.ev_fork, 0), "hipStreamWaitEvent");
 }
 int join_tail(Plan &p, hipStream_t stream) {
-    int rc = check_hip(hipEventRecord(p.ev_join, p.side_stream), "hipEventRecord");
+    int rc = check_hip(hipEventRecord(p.ev_join, p.side_stream.get()), "hipEventRecord");
     if (rc) return rc;
     return check_hip(hipStreamWaitEvent(stream, p.ev_join, 0), "hipStreamWaitEvent");
 }
@@ -783,7 +708,7 @@ int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *
     // inside its own T * L bytes (gl_viterbi_wave: quads of rows 1 .. T - 1 from the first dword boundary).  (A chunkless
     // contig's path score is the waves'.)
     if ((rc = fork_tail(p, stream))) return rc;
-    if ((rc = check_hip(r.chunked(g, p.side_stream), r.what))) return rc;
+    if ((rc = check_hip(r.chunked(g, p.side_stream.get()), r.what))) return rc;
     if ((rc = check_hip(r.wave(g, stream), r.what))) return rc;
     return join_tail(p, stream);
 }
@@ -932,11 +857,11 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
     WinArgs a{};
     a.gene_ptr = csr.gene_ptr;
     a.attr_id = csr.attr_id;
-    a.wtab = p.tables_model->wtab;
-    a.wtab2 = p.tables_model->wtab2[label];
-    a.exp_trans = p.tables_model->exp_trans;
-    a.rtab = p.tables_model->rtab[label];
-    a.ptab = p.tables_model->ptab[label];
+    a.wtab = p.tables_model->wtab.get();
+    a.wtab2 = p.tables_model->wtab2[label].get();
+    a.exp_trans = p.tables_model->exp_trans.get();
+    a.rtab = p.tables_model->rtab[label].get();
+    a.ptab = p.tables_model->ptab[label].get();
     a.c_slot = p.d_c_slot;
     a.c_gene = p.d_c_gene;
     a.c_n = p.d_c_n;
@@ -977,7 +902,7 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
     if (p.reference_now || !p.fast_ok) {  // (the reference-bits and the generic kernel work in a scratch block)
         const size_t bytes = p.reference_now ? reference_scratch_bytes(p.n_genes) : size_t(p.S) * size_t(p.W) * 16 + 16;
         std::lock_guard<std::mutex> lock(p.ws_mutex);
-        if ((rc = grow_ws(p.d_win_scratch, p.win_scratch_cap, bytes, p.reference_now ? "hipMalloc reference scratch" : "hipMalloc window scratch")))
+        if ((rc = p.win_scratch.reserve(bytes, p.reference_now ? "hipMalloc reference scratch" : "hipMalloc window scratch")))
             return rc;
     }
     // (the register-resident and the reference-bits kernel store every gene of slot space once, by the tile that owns its slot:
@@ -986,9 +911,9 @@ static int run_windowed_impl(Plan &p, const DeviceCsr &csr, int32_t label, doubl
     if (p.reference_now) {
         double et[4];
         for (int i = 0; i < 4; ++i) et[i] = std::exp(m.trans[size_t(i)]);  // (the host's libm, as the reference's CRFsuite calls it)
-        return check_hip(launch_windowed_reference(a, p.tables_model->wtab2[1], et, p.d_win_scratch, stream), "reference-bits launch");
+        return check_hip(launch_windowed_reference(a, p.tables_model->wtab2[1].get(), et, p.win_scratch.get(), stream), "reference-bits launch");
     }
-    if (a.generic) a.scratch = p.d_win_scratch;
+    if (a.generic) a.scratch = p.win_scratch.get();
     if (piped && !a.generic && decode_pipelined_ok(a, *piped->seq)) {
         *piped->took = true;
         return check_hip(launch_decode_pipelined(a, *piped->seq, stream), "pipelined decode launch");
@@ -1023,13 +948,13 @@ int all_tiles(Plan &p, const int4 **d_tiles, int32_t *ntiles) {
         }
         std::vector<int4> td(size_t(nt) + 1);
         fill_tile_desc(p, irr, tile_out, nt, td.data());
-        int rc = grow_ws(p.d_all_tiles, p.all_tiles_cap, td.size() * sizeof(int4), "hipMalloc tile table");
+        int rc = p.all_tiles.reserve(td.size() * sizeof(int4), "hipMalloc tile table");
         if (rc) return rc;
-        if ((rc = check_hip(hipMemcpy(p.d_all_tiles, td.data(), td.size() * sizeof(int4), hipMemcpyHostToDevice), "upload tile table")))
+        if ((rc = check_hip(hipMemcpy(p.all_tiles.get(), td.data(), td.size() * sizeof(int4), hipMemcpyHostToDevice), "upload tile table")))
             return rc;
         p.all_ntiles = nt;
     }
-    *d_tiles = p.d_all_tiles;
+    *d_tiles = p.all_tiles.get();
     *ntiles = p.all_ntiles;
     return GECCO_CRF_OK;
 }
@@ -1241,15 +1166,15 @@ int ensure_seq(Plan &p, hipStream_t stream) {
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(p.ws_mutex);
     const SeqLayout l = seq_layout(size_t(p.n_genes));
-    const bool fresh = !p.d_seq_ws || l.bytes + align256(size_t(p.n_contigs) + 24) > p.seq_ws_cap;
-    rc = grow_ws(p.d_seq_ws, p.seq_ws_cap, l.bytes + align256(size_t(p.n_contigs) + 24), "hipMalloc scan workspace");
+    const bool fresh = !p.seq_ws.get() || l.bytes + align256(size_t(p.n_contigs) + 24) > p.seq_ws.capacity();
+    rc = p.seq_ws.reserve(l.bytes + align256(size_t(p.n_contigs) + 24), "hipMalloc scan workspace");
     // (the decoder's counters accumulate over launches: they start from zero in a new block)
-    if (!rc && fresh) rc = check_hip(hipMemsetAsync(p.d_seq_ws + l.off_stats, 0, 64, stream), "memset decoder counters");
+    if (!rc && fresh) rc = check_hip(hipMemsetAsync(p.seq_ws.get() + l.off_stats, 0, 64, stream), "memset decoder counters");
     // the exactness test's bound, candidate counter and contig flags (behind the layout): zero before the first decode on
     // this layout; every decode leaves them zero again (vd_exact_fix)
     const size_t sig = l.bytes * 1000003u + size_t(p.n_contigs) + 1;
     if (!rc && (fresh || sig != p.vbound_sig)) {
-        rc = check_hip(hipMemsetAsync(p.d_seq_ws + l.bytes, 0, 16 + size_t(p.n_contigs), stream), "memset contig flags");
+        rc = check_hip(hipMemsetAsync(p.seq_ws.get() + l.bytes, 0, 16 + size_t(p.n_contigs), stream), "memset contig flags");
         if (!rc) p.vbound_sig = sig;
     }
     return rc;
@@ -1263,7 +1188,7 @@ int fill_seq_args(Plan &p, SeqArgs &a, hipStream_t stream) {
     if ((rc = ensure_seq(p, stream))) return rc;
     const Model &m = *p.model;
     const SeqLayout l = seq_layout(size_t(p.n_genes));
-    char *w = p.d_seq_ws;
+    char *w = p.seq_ws.get();
     a = SeqArgs{};
     a.state = reinterpret_cast<double2 *>(w + l.off_state);
     a.alpha = reinterpret_cast<double2 *>(w + l.off_alpha);
@@ -1335,7 +1260,7 @@ inline void bind_seq_io(const Plan &p, SeqArgs &a, const DeviceCsr &csr, int8_t 
     a.score = d_score;
     a.csr_gene_ptr = csr.gene_ptr;
     a.csr_attr_id = csr.attr_id;
-    a.csr_wtab01 = p.tables_model->wtab2[1];
+    a.csr_wtab01 = p.tables_model->wtab2[1].get();
     a.csr_n_attrs = p.model->A;
 }
 
@@ -1389,7 +1314,7 @@ int plan_run_marginals_full(Plan &p, const DeviceCsr &csr, double *d_marg,
     if (p.seq_short && d_lognorm && p.n_empty_contigs &&
         (rc = check_hip(hipMemsetAsync(d_lognorm, 0, size_t(p.n_contigs) * 8, stream), "memset lognorm")))
         return rc;
-    return check_hip(launch_seq_marginals_short(a, csr.gene_ptr, csr.attr_id, p.tables_model->wtab2[1], p.model->A, p.d_contig_ptr,
+    return check_hip(launch_seq_marginals_short(a, csr.gene_ptr, csr.attr_id, p.tables_model->wtab2[1].get(), p.model->A, p.d_contig_ptr,
                                                 stream), "marginals launch");
 }
 
@@ -1535,7 +1460,7 @@ int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset) {
     for (int i = 0; i < 4; ++i) out[i] = 0;
     std::lock_guard<std::mutex> lock(p.ws_mutex);
     // (any-L plans: the counters of the chunked Viterbi, in front of the general-L workspace)
-    char *base = p.general ? p.d_gen_ws : p.d_seq_ws;
+    char *base = p.general ? p.gen_ws.get() : p.seq_ws.get();
     if (p.device < 0 || !base) return GECCO_CRF_OK;  // nothing has been decoded yet
     int rc = use_device(p.device);
     if (rc) return rc;
@@ -1571,11 +1496,11 @@ int plan_run_segment(Plan &p, const double *d_p, const uint8_t *d_annotated, con
     }
     {
         std::lock_guard<std::mutex> lock(p.ws_mutex);
-        if ((rc = grow_ws(p.d_seg_ws, p.seg_ws_cap, segment_workspace_bytes(p.n_genes, p.n_contigs), "hipMalloc segment workspace")))
+        if ((rc = p.seg_ws.reserve(segment_workspace_bytes(p.n_genes, p.n_contigs), "hipMalloc segment workspace")))
             return rc;
     }
     return check_hip(launch_segment(d_p, d_annotated, p.seq_ready ? p.d_seq_flags : nullptr, p.d_contig_ptr, p.n_genes, p.n_contigs, params, d_seg, max_seg,
-                                    d_seg_off, d_total, p.d_seg_ws, stream, d_gather, gather_cap),
+                                    d_seg_off, d_total, p.seg_ws.get(), stream, d_gather, gather_cap),
                      "segment launch");
 }
 

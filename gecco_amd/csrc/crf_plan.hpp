@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "crf_device.hpp"
+#include "crf_hip_own.hpp"
 #include "crf_model.hpp"
 
 namespace gecco {
@@ -30,15 +31,15 @@ struct Carver {
 // Per-device copies of a model's tables (owned by the Model, created on first use).
 struct DeviceTables {
     int device = -1;
-    double *wtab = nullptr;       // [A*L]
-    double2 *wtab2[2] = {nullptr, nullptr};  // L == 2: [A] (other, label) for label = 0 / 1
-    double *exp_trans = nullptr;  // [L*L]
-    double *trans = nullptr;      // [L*L] raw weights (general-L Viterbi)
+    DeviceBlock<double> wtab;     // [A*L]
+    DeviceBlock<double2> wtab2[2];  // L == 2: [A] (other, label) for label = 0 / 1
+    DeviceBlock<double> exp_trans;  // [L*L]
+    DeviceBlock<double> trans;      // [L*L] raw weights (general-L Viterbi)
     double wmax_abs = 0.0, tmax_abs = 0.0;  // largest |state weight| / |transition weight| (bounds of the Viterbi exactness margin)
-    double *rtab[2] = {nullptr, nullptr};  // L == 2: [32] mu01(label) * 2^(j/32), the exp table of the window kernel's slot constants
+    DeviceBlock<double> rtab[2];  // L == 2: [32] mu01(label) * 2^(j/32), the exp table of the window kernel's slot constants
     // L == 2: [A + 1] (delta_a, exp(delta_a)) for label = 0 / 1, the factor table of the product-form slot constants
     // (build_slot_table); slot_dmax / slot_prod_max_cnt: its two model constants
-    double2 *ptab[2] = {nullptr, nullptr};
+    DeviceBlock<double2> ptab[2];
     double slot_dmax = 0.0;
     int32_t slot_prod_max_cnt = 0;
     // Host-side constants of the kernels' argument blocks that depend on the model alone (L == 2), computed ONCE here: a launch
@@ -77,6 +78,7 @@ struct DeviceCsr {
 };
 
 struct Plan {
+    DeviceScope home{DeviceScope::kLater};  // (first member: see ~Plan)
     const Model *model = nullptr;
     int device = -1;  // -1: host-only plan (layout queries work, launches return ENODEV)
     int32_t W = 0, step = 1, pad = 1;
@@ -115,24 +117,23 @@ struct Plan {
     int32_t *d_seq_cblk_rank = nullptr, *d_seq_ne_contig = nullptr;  // non-empty contigs before every workgroup; their indices
     int32_t n_empty_contigs = 0;
     bool seq_short = false;           // no contig longer than one scan block: whole contigs per workgroup, one launch per decoder
-    // workspaces, allocated on first use, grow-only
-    char *d_seq_ws = nullptr, *d_gen_ws = nullptr, *d_seg_ws = nullptr;
+    Stream side_stream;  // (Viterbi of 17-32 labels, below; declared before the work spaces its kernels use)
+    // workspaces, reserved on first use, grow-only
+    DeviceBlock<char> seq_ws, gen_ws, seg_ws;
     size_t vbound_sig = 0;  // layout for which the exactness test's bound / counter / contig flags were last zeroed
-    double *d_win_scratch = nullptr;
-    size_t seq_ws_cap = 0, gen_ws_cap = 0, seg_ws_cap = 0, win_scratch_cap = 0;
+    DeviceBlock<double> win_scratch;
     // chunk tables of the any-L whole-contig kernels (first gene / contig of every chunk, chunks of every contig): they
     // depend on the plan's contigs and the chunk length only, so they are built and uploaded on first use
     // Two sets: every contig (marginals, Viterbi of small models), and the contigs longer than `min_len` only (Viterbi of
     // 17-32 labels: the long tail of a batch whose other contigs take the wave-per-contig kernel).
     struct GenTab {
-        char *d = nullptr;
+        DeviceBlock<char> d;
         int32_t chunk = 0, min_len = -1;  // (chunk == 0: not built)
         size_t nch = 0, off1 = 0, off2 = 0;
     } gen_tab[2];
     // Viterbi of 17-32 labels: the chunked kernels of a batch's long contigs run on a stream of the plan's own next to the
     // wave-per-contig kernel of the others (forked from and joined to the caller's stream by events)
     int32_t gen_wave_tmax = INT32_MIN, gen_wave_tmax_f = INT32_MIN;  // the splits chosen for this layout (Viterbi, marginals; INT32_MIN: not yet)
-    hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // Pipelined decode (plan_run_decode_pipelined): what the last call left for the next one -- the batch's score differences
     // in buffer `parity` of the workspace (pending) and the batch's arrays, which the caller keeps alive until then.
@@ -172,8 +173,7 @@ struct Plan {
                                          // stay in the pinned block, flags built by the host -- no copy, no launch in front of the decoder
     // every label's windowed marginals (crf_general_windowed.hip): the tile table of the lane-per-window tier when the plan's own
     // table has another geometry (2-label plans), built on first use
-    int4 *d_all_tiles = nullptr;
-    size_t all_tiles_cap = 0;
+    DeviceBlock<int4> all_tiles;
     int32_t all_ntiles = -1;  // (-1: not built for this layout)
     std::mutex ws_mutex;  // guards the lazy workspace / table creation: launches of one plan may come from several threads
     ~Plan();
@@ -231,8 +231,6 @@ int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d
                            int32_t *d_n_paths, double *d_marg, double *d_lognorm, hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);
-// returns GECCO_CRF_* ; on HIP failure sets the error text
-int check_hip(hipError_t e, const char *what);
 int get_device_tables(const Model &m, int device, const DeviceTables **out);
 
 }  // namespace gecco

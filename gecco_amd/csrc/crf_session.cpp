@@ -45,26 +45,6 @@ struct TraceMark {
     }
 };
 
-struct DevBuf {  // grow-only device block
-    char *p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t bytes, const char *what) {
-        if (p && bytes <= cap) return GECCO_CRF_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 8 + 256;
-        int rc = check_hip(hipMalloc(reinterpret_cast<void **>(&p), want), what);
-        if (!rc) cap = want;
-        return rc;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 struct HostBuf {  // grow-only pinned, device-visible host block: kernels write the (few) segment rows straight into it
     char *p = nullptr, *dp = nullptr;
     size_t cap = 0;
@@ -117,7 +97,7 @@ struct Lane {
     Plan plan;
     int up_chunk = -1;  // chunk whose arrays were uploaded ahead of its submission (-1: none)
     int64_t up_a0 = 0, up_nnz = 0, up_b0 = 0;
-    DevBuf d_gp, d_at, d_at16, d_p, d_y, d_ann, d_score, d_marg, d_lognorm, d_bp, d_bi, d_seg, d_deg, d_deg_ws, d_segp;
+    DeviceBlock<char> d_gp, d_at, d_at16, d_p, d_y, d_ann, d_score, d_marg, d_lognorm, d_bp, d_bi, d_seg, d_deg, d_deg_ws, d_segp;
     SessionStats *st = nullptr;  // the device's share of the batch's figures (merged when the batch is done)
     int8_t *y_dst = nullptr;     // where the decoder writes the chunk's labels: the lane's device buffer, or the caller's pinned array
     bool y_to_host = false;      // ... the latter: no download of labels
@@ -243,13 +223,12 @@ struct Session {
 
 Session::~Session() {
     workers.stop();
-    int prev = -1;
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    DeviceScope scope;
     for (auto &d : devs) {
-        if (hipSetDevice(d->device) != hipSuccess) continue;
+        if (set_device(d->device)) continue;
         (void)hipDeviceSynchronize();
         for (Lane &ln : d->lanes) {
-            for (DevBuf *b : {&ln.d_gp, &ln.d_at, &ln.d_at16, &ln.d_p, &ln.d_y, &ln.d_ann, &ln.d_score, &ln.d_marg, &ln.d_lognorm, &ln.d_bp, &ln.d_bi, &ln.d_seg, &ln.d_deg, &ln.d_deg_ws, &ln.d_segp}) b->release();
+            for (DeviceBlock<char> *b : {&ln.d_gp, &ln.d_at, &ln.d_at16, &ln.d_p, &ln.d_y, &ln.d_ann, &ln.d_score, &ln.d_marg, &ln.d_lognorm, &ln.d_bp, &ln.d_bi, &ln.d_seg, &ln.d_deg, &ln.d_deg_ws, &ln.d_segp}) b->release();
             ln.h_seg.release();
             ln.h_io.release();
             for (hipEvent_t e : {ln.ev_up, ln.ev_comp, ln.done})
@@ -259,8 +238,7 @@ Session::~Session() {
             for (hipStream_t st : {d->up, d->comp, d->down})
                 if (st) (void)hipStreamDestroy(st);
     }
-    devs.clear();  // plans free their blocks under their own device guard
-    if (prev >= 0) (void)hipSetDevice(prev);
+    devs.clear();  // plans free their blocks under their own device scope
 }
 
 int session_create(const Model &m, const int32_t *devices, int32_t n_devices, Session **out) {
@@ -269,11 +247,6 @@ int session_create(const Model &m, const int32_t *devices, int32_t n_devices, Se
         return GECCO_CRF_EINVAL;
     }
     *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
-        set_error("no HIP device available (this library has no CPU fallback)");
-        return GECCO_CRF_ENODEV;
-    }
     std::unique_ptr<Session> s(new Session());
     s->model = &m;
     if (const char *env = std::getenv("GECCO_CRF_CHUNK_GENES")) {
@@ -282,15 +255,12 @@ int session_create(const Model &m, const int32_t *devices, int32_t n_devices, Se
     }
     if (const char *env = std::getenv("GECCO_CRF_DIRECT_GENES")) s->direct_genes = int32_t(std::max<long>(0, std::min<long>(std::atol(env), 1 << 24)));
     for (int32_t i = 0; i < n_devices; ++i) {
-        if (devices[i] < 0 || devices[i] >= count) {
-            set_error("device index out of range");
-            return GECCO_CRF_ENODEV;
-        }
+        int rc = check_device(devices[i]);
+        if (rc) return rc;
         // a device may be listed more than once: every entry gets its own ring of lanes and its own submitting thread, but a
         // physical device has ONE stream per direction (copies of one direction queue up behind each other anyway; three
         // streams per entry only multiplied the hardware queues the device has to poll)
-        int rc = check_hip(hipSetDevice(devices[i]), "hipSetDevice");
-        if (rc) return rc;
+        if ((rc = set_device(devices[i]))) return rc;
         std::unique_ptr<DeviceCtx> d(new DeviceCtx());
         d->device = devices[i];
         s->devs.push_back(std::move(d));  // from here on the session's destructor cleans up
@@ -487,7 +457,7 @@ int finish_pending(RunCtx &X, DeviceCtx &D) {
     int rc = GECCO_CRF_OK;
     if (!pl.y_to_host) {  // (labels written into the caller's pinned array by the decoder itself need no copy)
         pl.st->d2h_bytes += int64_t(ng);
-        rc = check_hip(hipMemcpyAsync(X.r.y_out + pk.g0, pl.d_y.p, ng, hipMemcpyDeviceToHost, pl.down), "D2H labels");
+        rc = check_hip(hipMemcpyAsync(X.r.y_out + pk.g0, pl.d_y.get(), ng, hipMemcpyDeviceToHost, pl.down), "D2H labels");
         if (rc) return rc;
     }
     return check_hip(hipEventRecord(pl.done, pl.down), "hipEventRecord");
@@ -497,7 +467,7 @@ int finish_pending(RunCtx &X, DeviceCtx &D) {
 int flush_pending(RunCtx &X, DeviceCtx &D) {
     if (!D.pending) return GECCO_CRF_OK;
     Lane &pl = *D.pending;
-    int rc = check_hip(hipSetDevice(pl.device), "hipSetDevice");
+    int rc = set_device(pl.device);
     if (rc) return rc;
     if ((rc = plan_run_decode_pipelined(nullptr, {}, X.r.label, nullptr, &pl.plan, pl.y_dst, pl.comp)))
         return rc;
@@ -527,7 +497,7 @@ int chunk_degrees(const BatchRequest &r, int32_t g0, int32_t g1, int64_t nnz) {
 int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
     const BatchRequest &r = X.r;
     Chunk &ck = X.chunks[chunk_index];
-    int rc = check_hip(hipSetDevice(ln.device), "hipSetDevice");
+    int rc = set_device(ln.device);
     if (rc) return rc;
     const int32_t ng = ck.u1 - ck.u0;
     TraceMark tm;
@@ -542,30 +512,30 @@ int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
             if ((rc = ln.d_gp.reserve((size_t(ng) + 1) * 4, "hipMalloc gene_ptr"))) return rc;
             if ((rc = ln.d_deg.reserve(size_t(ng) + 32, "hipMalloc degrees"))) return rc;
             if ((rc = ln.d_deg_ws.reserve(degree_scratch_bytes(ng), "hipMalloc degree scan"))) return rc;
-            if ((rc = check_hip(hipMemcpyAsync(ln.d_deg.p, r.degree + ck.u0, size_t(ng), hipMemcpyHostToDevice, ln.up), "H2D degrees")))
+            if ((rc = check_hip(hipMemcpyAsync(ln.d_deg.get(), r.degree + ck.u0, size_t(ng), hipMemcpyHostToDevice, ln.up), "H2D degrees")))
                 return rc;
             ln.st->h2d_bytes += int64_t(ng);
         } else {
             if ((rc = ln.d_gp.reserve((size_t(ng) + 1) * 4, "hipMalloc gene_ptr"))) return rc;
-            if ((rc = check_hip(hipMemcpyAsync(ln.d_gp.p, r.gene_ptr + ck.u0, (size_t(ng) + 1) * 4, hipMemcpyHostToDevice, ln.up), "H2D gene_ptr")))
+            if ((rc = check_hip(hipMemcpyAsync(ln.d_gp.get(), r.gene_ptr + ck.u0, (size_t(ng) + 1) * 4, hipMemcpyHostToDevice, ln.up), "H2D gene_ptr")))
                 return rc;
             ln.st->h2d_bytes += int64_t((size_t(ng) + 1) * 4);
         }
         if ((rc = ln.d_at.reserve((nnz + 8) * 4, "hipMalloc attr_id"))) return rc;
         if (r.attr_id16) {  // 16-bit indices cross PCIe; widened on the compute stream (below)
             if ((rc = ln.d_at16.reserve((nnz + 8) * 2, "hipMalloc attr_id16"))) return rc;
-            if (nnz && (rc = check_hip(hipMemcpyAsync(ln.d_at16.p, r.attr_id16 + a0, nnz * 2, hipMemcpyHostToDevice, ln.up), "H2D attr_id16")))
+            if (nnz && (rc = check_hip(hipMemcpyAsync(ln.d_at16.get(), r.attr_id16 + a0, nnz * 2, hipMemcpyHostToDevice, ln.up), "H2D attr_id16")))
                 return rc;
             ln.st->h2d_bytes += int64_t(nnz * 2);
         } else {
-            if (nnz && (rc = check_hip(hipMemcpyAsync(ln.d_at.p, r.attr_id + a0, nnz * 4, hipMemcpyHostToDevice, ln.up), "H2D attr_id")))
+            if (nnz && (rc = check_hip(hipMemcpyAsync(ln.d_at.get(), r.attr_id + a0, nnz * 4, hipMemcpyHostToDevice, ln.up), "H2D attr_id")))
                 return rc;
             ln.st->h2d_bytes += int64_t(nnz * 4);
         }
         if (r.want_segments) {
             if (r.annotated) {  // (null: a gene is annotated iff it has a domain the model knows -- the degree bytes themselves)
                 if ((rc = ln.d_ann.reserve(size_t(ng) + 8, "hipMalloc annotated"))) return rc;
-                if ((rc = check_hip(hipMemcpyAsync(ln.d_ann.p, r.annotated + ck.u0, size_t(ng), hipMemcpyHostToDevice, ln.up), "H2D annotated")))
+                if ((rc = check_hip(hipMemcpyAsync(ln.d_ann.get(), r.annotated + ck.u0, size_t(ng), hipMemcpyHostToDevice, ln.up), "H2D annotated")))
                     return rc;
                 ln.st->h2d_bytes += ng;
             }
@@ -574,9 +544,9 @@ int submit_uploads(RunCtx &X, Lane &ln, int chunk_index) {
                 const size_t nb = size_t(b1 - b0);
                 if ((rc = ln.d_bp.reserve((size_t(ng) + 1) * 4, "hipMalloc marker_ptr"))) return rc;
                 if ((rc = ln.d_bi.reserve((nb + 4) * 4, "hipMalloc marker_id"))) return rc;
-                if ((rc = check_hip(hipMemcpyAsync(ln.d_bp.p, r.seg.bio_ptr + ck.u0, (size_t(ng) + 1) * 4, hipMemcpyHostToDevice, ln.up), "H2D marker_ptr")))
+                if ((rc = check_hip(hipMemcpyAsync(ln.d_bp.get(), r.seg.bio_ptr + ck.u0, (size_t(ng) + 1) * 4, hipMemcpyHostToDevice, ln.up), "H2D marker_ptr")))
                     return rc;
-                if (nb && (rc = check_hip(hipMemcpyAsync(ln.d_bi.p, r.seg.bio_id + b0, nb * 4, hipMemcpyHostToDevice, ln.up), "H2D marker_id")))
+                if (nb && (rc = check_hip(hipMemcpyAsync(ln.d_bi.get(), r.seg.bio_id + b0, nb * 4, hipMemcpyHostToDevice, ln.up), "H2D marker_id")))
                     return rc;
                 ln.st->h2d_bytes += int64_t((size_t(ng) + 1 + nb) * 4);
             }
@@ -612,7 +582,7 @@ T *mapped_or_null(T *host) {
 int submit_direct_arrays(RunCtx &X, Lane &ln, int chunk_index) {
     const BatchRequest &r = X.r;
     Chunk &ck = X.chunks[chunk_index];
-    int rc = check_hip(hipSetDevice(ln.device), "hipSetDevice");
+    int rc = set_device(ln.device);
     if (rc) return rc;
     const size_t ng = size_t(ck.g1 - ck.g0);
     int64_t a0, a1, b0 = 0, b1 = 0;
@@ -631,26 +601,26 @@ int submit_direct_arrays(RunCtx &X, Lane &ln, int chunk_index) {
     const bool c_gp = (ng + 1) * 4 >= kCopy, c_at = nnz * 4 >= kCopy && !r.attr_id16;
     if (c_gp) {
         if ((rc = ln.d_gp.reserve((ng + 1) * 4, "hipMalloc gene_ptr"))) return rc;
-        if ((rc = check_hip(hipMemcpyAsync(ln.d_gp.p, r.gene_ptr + ck.g0, (ng + 1) * 4, hipMemcpyHostToDevice, ln.comp), "H2D gene_ptr"))) return rc;
+        if ((rc = check_hip(hipMemcpyAsync(ln.d_gp.get(), r.gene_ptr + ck.g0, (ng + 1) * 4, hipMemcpyHostToDevice, ln.comp), "H2D gene_ptr"))) return rc;
         ln.st->h2d_bytes += int64_t((ng + 1) * 4);
     }
     if (c_at) {
         if ((rc = ln.d_at.reserve((nnz + 8) * 4, "hipMalloc attr_id"))) return rc;
-        if ((rc = check_hip(hipMemcpyAsync(ln.d_at.p, r.attr_id + a0, nnz * 4, hipMemcpyHostToDevice, ln.comp), "H2D attr_id"))) return rc;
+        if ((rc = check_hip(hipMemcpyAsync(ln.d_at.get(), r.attr_id + a0, nnz * 4, hipMemcpyHostToDevice, ln.comp), "H2D attr_id"))) return rc;
         ln.st->h2d_bytes += int64_t(nnz * 4);
     }
     const bool c_at16 = nnz * 4 >= kCopy && r.attr_id16;  // (16-bit indices: half the bytes cross, a launch widens them)
     if (c_at16) {
         if ((rc = ln.d_at.reserve((nnz + 8) * 4, "hipMalloc attr_id"))) return rc;
         if ((rc = ln.d_at16.reserve((nnz + 8) * 2, "hipMalloc attr_id16"))) return rc;
-        if ((rc = check_hip(hipMemcpyAsync(ln.d_at16.p, r.attr_id16 + a0, nnz * 2, hipMemcpyHostToDevice, ln.comp), "H2D attr_id16"))) return rc;
+        if ((rc = check_hip(hipMemcpyAsync(ln.d_at16.get(), r.attr_id16 + a0, nnz * 2, hipMemcpyHostToDevice, ln.comp), "H2D attr_id16"))) return rc;
         ln.st->h2d_bytes += int64_t(nnz * 2);
-        if ((rc = check_hip(launch_wire_format(nullptr, 0, 0, nullptr, nullptr, reinterpret_cast<const uint16_t *>(ln.d_at16.p), int64_t(nnz),
-                                               reinterpret_cast<int32_t *>(ln.d_at.p), ln.comp), "wire format launch")))
+        if ((rc = check_hip(launch_wire_format(nullptr, 0, 0, nullptr, nullptr, reinterpret_cast<const uint16_t *>(ln.d_at16.get()), int64_t(nnz),
+                                               reinterpret_cast<int32_t *>(ln.d_at.get()), ln.comp), "wire format launch")))
             return rc;
     }
-    const int32_t *m_gp = c_gp ? reinterpret_cast<const int32_t *>(ln.d_gp.p) : nullptr;
-    const int32_t *m_at = (c_at || c_at16) ? reinterpret_cast<const int32_t *>(ln.d_at.p) : nullptr;
+    const int32_t *m_gp = c_gp ? reinterpret_cast<const int32_t *>(ln.d_gp.get()) : nullptr;
+    const int32_t *m_at = (c_at || c_at16) ? reinterpret_cast<const int32_t *>(ln.d_at.get()) : nullptr;
     // the kernels write p / y straight into host memory only where nothing reads them again on the device (no refiner behind
     // them) and the window kernel stores every gene exactly once (the 2-label register kernel: decided in submit)
     double *m_p = (r.p_out && !r.want_segments && ng * 8 >= kAsk) ? mapped_or_null(r.p_out + ck.g0) : nullptr;
@@ -715,7 +685,7 @@ int submit_plan(RunCtx &X, Lane &ln, int chunk_index) {
     const BatchRequest &r = X.r;
     Chunk &ck = X.chunks[chunk_index];
     const Model &m = *S.model;
-    int rc = check_hip(hipSetDevice(ln.device), "hipSetDevice");
+    int rc = set_device(ln.device);
     if (rc) return rc;
     const int32_t nc = ck.c1 - ck.c0;
     TraceMark tm;
@@ -797,7 +767,7 @@ int run_refiner(RunCtx &X, Lane &ln, const Chunk &ck, const double *d_p, const u
     }
     return plan_run_segment(ln.plan, d_p, d_ann, sp, reinterpret_cast<int32_t *>(dp + ln.o_rows), int32_t(cap),
                             reinterpret_cast<int32_t *>(dp + ln.o_off), reinterpret_cast<int32_t *>(dp), ln.comp,
-                            r.seg_p_out ? reinterpret_cast<double *>(ln.d_segp.p) : nullptr, ng);
+                            r.seg_p_out ? reinterpret_cast<double *>(ln.d_segp.get()) : nullptr, ng);
 }
 
 // Direct path: every launch of the (one) chunk on the compute stream, on the addresses submit_direct_arrays chose; the host then
@@ -818,7 +788,7 @@ int submit_direct(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
             d_p = ln.x_p;
         } else {
             if ((rc = ln.d_p.reserve(size_t(ng) * 8, "hipMalloc p"))) return rc;
-            d_p = reinterpret_cast<double *>(ln.d_p.p);
+            d_p = reinterpret_cast<double *>(ln.d_p.get());
         }
     }
     if ((rc = run_chunk(X, ln, d_gp, d_at, d_p, ln.x_y, nullptr, true))) return rc;
@@ -837,7 +807,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     const BatchRequest &r = X.r;
     Chunk &ck = X.chunks[chunk_index];
     const Model &m = *S.model;
-    int rc = check_hip(hipSetDevice(ln.device), "hipSetDevice");
+    int rc = set_device(ln.device);
     if (rc) return rc;
     const int32_t nc = ck.c1 - ck.c0, ng = ck.u1 - ck.u0;  // (ng: the genes the chunk scores -- a piece's halo included)
     TraceMark tm;
@@ -850,14 +820,14 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     if (ng == 0) return check_hip(hipEventRecord(ln.done, ln.comp), "hipEventRecord");
     // the wire format's two launches: degree bytes -> row pointers, 16-bit attribute indices -> 32-bit ones
     if ((r.degree || r.attr_id16) &&
-        (rc = check_hip(launch_wire_format(r.degree ? reinterpret_cast<const uint8_t *>(ln.d_deg.p) : nullptr, int(ng), int32_t(a0),
-                                           reinterpret_cast<int32_t *>(ln.d_gp.p), reinterpret_cast<int32_t *>(ln.d_deg_ws.p),
-                                           r.attr_id16 ? reinterpret_cast<const uint16_t *>(ln.d_at16.p) : nullptr, int64_t(nnz),
-                                           reinterpret_cast<int32_t *>(ln.d_at.p), ln.comp), "wire format launch")))
+        (rc = check_hip(launch_wire_format(r.degree ? reinterpret_cast<const uint8_t *>(ln.d_deg.get()) : nullptr, int(ng), int32_t(a0),
+                                           reinterpret_cast<int32_t *>(ln.d_gp.get()), reinterpret_cast<int32_t *>(ln.d_deg_ws.get()),
+                                           r.attr_id16 ? reinterpret_cast<const uint16_t *>(ln.d_at16.get()) : nullptr, int64_t(nnz),
+                                           reinterpret_cast<int32_t *>(ln.d_at.get()), ln.comp), "wire format launch")))
         return rc;
     // gene_ptr keeps the caller's offsets: the attribute array is addressed from where its element 0 would be
-    const int32_t *d_gp = reinterpret_cast<const int32_t *>(ln.d_gp.p);
-    const int32_t *d_at = reinterpret_cast<const int32_t *>(ln.d_at.p) - a0;
+    const int32_t *d_gp = reinterpret_cast<const int32_t *>(ln.d_gp.get());
+    const int32_t *d_at = reinterpret_cast<const int32_t *>(ln.d_at.get()) - a0;
     double *d_p = nullptr, *d_score = nullptr;
     int8_t *d_y = nullptr;
     // The tiles write p to the lane's device buffer, downloaded by a copy.  (Writing it straight into a pinned caller array was
@@ -865,7 +835,7 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     // tools/ubench/pcie_bw.hip; C3 with pinned buffers 0.619 ms against 0.609 through a copy.)
     if (X.windowed) {
         if ((rc = ln.d_p.reserve(size_t(ng) * 8, "hipMalloc p"))) return rc;
-        d_p = reinterpret_cast<double *>(ln.d_p.p);
+        d_p = reinterpret_cast<double *>(ln.d_p.get());
     }
     if (X.viterbi) {
         // Labels (a byte per gene) go straight into the caller's array when it is pinned: a chunk's 0.5 MB of them cost a copy
@@ -877,12 +847,12 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
             d_y = m_y;
         } else {
             if ((rc = ln.d_y.reserve(size_t(ng) + 8, "hipMalloc labels"))) return rc;
-            d_y = reinterpret_cast<int8_t *>(ln.d_y.p);
+            d_y = reinterpret_cast<int8_t *>(ln.d_y.get());
         }
         ln.y_dst = d_y;
         if (r.score_out) {
             if ((rc = ln.d_score.reserve(size_t(nc) * 8, "hipMalloc scores"))) return rc;
-            d_score = reinterpret_cast<double *>(ln.d_score.p);
+            d_score = reinterpret_cast<double *>(ln.d_score.get());
         }
     }
     const bool piped = X.windowed && X.viterbi && !r.score_out && !X.full && !r.want_segments;
@@ -905,15 +875,15 @@ int submit(RunCtx &X, DeviceCtx &D, Lane &ln, int chunk_index) {
     double *d_marg = nullptr, *d_lognorm = nullptr;
     if (X.full) {
         if ((rc = ln.d_marg.reserve(size_t(ng) * L * 8, "hipMalloc marginals"))) return rc;
-        d_marg = reinterpret_cast<double *>(ln.d_marg.p);
+        d_marg = reinterpret_cast<double *>(ln.d_marg.get());
         if ((rc = ln.d_lognorm.reserve(size_t(nc) * 8, "hipMalloc lognorm"))) return rc;
-        d_lognorm = reinterpret_cast<double *>(ln.d_lognorm.p);
+        d_lognorm = reinterpret_cast<double *>(ln.d_lognorm.get());
         if ((rc = plan_run_marginals_full(ln.plan, {d_gp, d_at}, d_marg, d_lognorm, ln.comp))) return rc;
     }
     // (nothing but the rows' few bytes crosses PCIe for a cluster call)
     if (r.want_segments &&
-        (rc = run_refiner(X, ln, ck, d_p, reinterpret_cast<const uint8_t *>(r.annotated ? ln.d_ann.p : ln.d_deg.p),
-                          reinterpret_cast<const int32_t *>(ln.d_bp.p), reinterpret_cast<const int32_t *>(ln.d_bi.p))))
+        (rc = run_refiner(X, ln, ck, d_p, reinterpret_cast<const uint8_t *>(r.annotated ? ln.d_ann.get() : ln.d_deg.get()),
+                          reinterpret_cast<const int32_t *>(ln.d_bp.get()), reinterpret_cast<const int32_t *>(ln.d_bi.get()))))
         return rc;
     tm.lap("launch", chunk_index);
     const bool c_p = r.p_out, c_y = r.y_out && !ln.y_to_host, c_score = r.score_out, c_marg = r.marg_out, c_ln = r.lognorm_out;
@@ -976,9 +946,9 @@ int retire_begin(RunCtx &X, Lane &ln) {
                 dst = ck.seg_p.data();
             }
             if (ck.seg_p_count) {
-                if ((rc = check_hip(hipSetDevice(ln.device), "hipSetDevice"))) return rc;
+                if ((rc = set_device(ln.device))) return rc;
                 ln.st->d2h_bytes += ck.seg_p_count * 8;
-                if ((rc = check_hip(hipMemcpyAsync(dst, ln.d_segp.p, size_t(ck.seg_p_count) * 8, hipMemcpyDeviceToHost, ln.down), "D2H cluster probabilities")))
+                if ((rc = check_hip(hipMemcpyAsync(dst, ln.d_segp.get(), size_t(ck.seg_p_count) * 8, hipMemcpyDeviceToHost, ln.down), "D2H cluster probabilities")))
                     return rc;
                 if ((rc = check_hip(hipEventRecord(ln.done, ln.down), "hipEventRecord"))) return rc;
                 ln.segp_in_flight = true;
@@ -1157,7 +1127,7 @@ int session_run(Session &S, const BatchRequest &r) {
             for (Lane &ln : D.lanes) {
                 if (rc) {  // the failed submission may have left work behind an unrecorded event
                     const std::string keep = last_error();
-                    if (hipSetDevice(ln.device) == hipSuccess) (void)hipDeviceSynchronize();
+                    if (!set_device(ln.device)) (void)hipDeviceSynchronize();
                     ln.chunk = -1;
                     ln.segp_in_flight = false;
                     set_error(keep);

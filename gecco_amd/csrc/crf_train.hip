@@ -430,11 +430,6 @@ __global__ void __launch_bounds__(kTrainReduceBlocks) train_reduce_final(const S
     if (threadIdx.x < kTrainRowCols) out_all[slots[blockIdx.x].out0 + threadIdx.x] = sh[threadIdx.x][0];
 }
 
-template <class T>
-int dev_alloc(T **d, size_t n, const char *what) {
-    return check_hip(hipMalloc(reinterpret_cast<void **>(d), std::max<size_t>(n, 1) * sizeof(T)), what);
-}
-
 }  // namespace
 
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
@@ -599,7 +594,8 @@ static_assert(sizeof(Slot) % alignof(double) == 0 && sizeof(ItemGroup) % alignof
 // kernels, and one download brings back the row sums and expected counts of the span of problems from the first active
 // one to the last.
 struct Trainer {
-    int device = 0;
+    DeviceScope home{DeviceScope::kLater};  // (first member: see ~Trainer)
+    int device = -1;  // set once the device has been checked
     std::string family;  // "batch" / "grid" in error messages; empty: a lone trainer, which keeps its own messages
     struct Set {
         int32_t A, n_items, K, W;
@@ -617,26 +613,16 @@ struct Trainer {
     int64_t scratch_cap = 0;         // bytes of d_scratch: the most one group may use
     std::vector<unsigned char> h_in;  // host staging of the upload
     std::vector<double> h_out;        // host staging of the download
-    hipStream_t stream = nullptr;
+    Stream stream;
     // device: training sets (uploaded once) and per-evaluation work space
-    SetDev *d_sets = nullptr;
-    int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr;
-    int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr;
-    int32_t *d_attr_ptr = nullptr, *d_attr_items = nullptr;
-    unsigned char *d_in = nullptr, *d_scratch = nullptr;
-    double *d_out = nullptr, *d_partial = nullptr;
+    DeviceBlock<SetDev> d_sets;
+    DeviceBlock<int32_t> d_item_ptr, d_attr_id, d_label, d_win_start, d_iw_first, d_iw_cnt, d_iw_off, d_attr_ptr, d_attr_items;
+    DeviceBlock<unsigned char> d_in, d_scratch;
+    DeviceBlock<double> d_out, d_partial;
 
-    ~Trainer() {
-        int prev = -1;
-        const bool restore = hipGetDevice(&prev) == hipSuccess && prev != device;
-        (void)hipSetDevice(device);
-        for (void *p : {(void *)d_sets, (void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start,
-                        (void *)d_iw_first, (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items,
-                        (void *)d_in, (void *)d_scratch, (void *)d_out, (void *)d_partial})
-            if (p) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (restore && prev >= 0) (void)hipSetDevice(prev);
-    }
+    // The members free themselves, in reverse order, after this body: with the trainer's device current, and `home` hands the
+    // caller's device back at the end.
+    ~Trainer() { home.enter(device); }
 };
 
 // Sets as build_problem takes them.  A set's error names it after what the caller numbers: the set where problems pick
@@ -648,7 +634,6 @@ int trainer_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr
                    int32_t n_problems, const int32_t *problem_set, int64_t scratch_budget, const char *family,
                    Trainer **out) {
     auto t = std::make_unique<Trainer>();
-    t->device = device;
     if (family) t->family = family;
     std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c, attr_items_c;
     std::vector<SetDev> layout;
@@ -708,37 +693,30 @@ int trainer_create(int32_t device, int32_t n_sets, const int32_t *const *seq_ptr
             if (b > INT32_MAX) return fail("trainer batch: the problems need more than 2^31 workgroups in one launch");
     t->scratch_cap = scratch_total;
     if (scratch_budget > 0) t->scratch_cap = std::max(scratch_max, std::min(scratch_budget, scratch_total));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available (this library has no CPU fallback)");
-        return GECCO_CRF_ENODEV;
-    }
-    if (device < 0 || device >= ndev) {
-        set_error("device index out of range");
-        return GECCO_CRF_ENODEV;
-    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    t->device = device;
     t->igs_off = size_t(n_problems) * sizeof(Slot);
     t->ws_off = (t->igs_off + size_t(n_problems) * sizeof(ItemGroup) + 15) / 16 * 16;
     t->h_in.assign(t->ws_off + size_t(ws_total) * sizeof(double), 0);
     t->h_out.assign(size_t(out_total), 0.0);
 
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
-    if (rc) return rc;
-    if ((rc = check_hip(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
-    if ((rc = dev_upload(&t->d_sets, layout, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_item_ptr, item_ptr_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_attr_id, attr_id_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_label, label_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_win_start, win_start_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_iw_first, iw_first_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_iw_cnt, iw_cnt_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_iw_off, iw_off_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_attr_ptr, attr_ptr_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_attr_items, attr_items_c, "trainer upload"))) return rc;
-    if ((rc = dev_alloc(&t->d_in, t->h_in.size(), "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_out, t->h_out.size(), "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_partial, size_t(n_problems) * kTrainReduceBlocks * kTrainRowCols, "trainer alloc"))) return rc;
-    if ((rc = dev_alloc(&t->d_scratch, size_t(t->scratch_cap), "trainer alloc"))) return rc;
+    if ((rc = set_device(device))) return rc;
+    if ((rc = t->stream.create())) return rc;
+    if ((rc = t->d_sets.upload(layout, "trainer upload"))) return rc;
+    if ((rc = t->d_item_ptr.upload(item_ptr_c, "trainer upload"))) return rc;
+    if ((rc = t->d_attr_id.upload(attr_id_c, "trainer upload"))) return rc;
+    if ((rc = t->d_label.upload(label_c, "trainer upload"))) return rc;
+    if ((rc = t->d_win_start.upload(win_start_c, "trainer upload"))) return rc;
+    if ((rc = t->d_iw_first.upload(iw_first_c, "trainer upload"))) return rc;
+    if ((rc = t->d_iw_cnt.upload(iw_cnt_c, "trainer upload"))) return rc;
+    if ((rc = t->d_iw_off.upload(iw_off_c, "trainer upload"))) return rc;
+    if ((rc = t->d_attr_ptr.upload(attr_ptr_c, "trainer upload"))) return rc;
+    if ((rc = t->d_attr_items.upload(attr_items_c, "trainer upload"))) return rc;
+    if ((rc = t->d_in.alloc(t->h_in.size(), "trainer alloc"))) return rc;
+    if ((rc = t->d_out.alloc(t->h_out.size(), "trainer alloc"))) return rc;
+    if ((rc = t->d_partial.alloc(size_t(n_problems) * kTrainReduceBlocks * kTrainRowCols, "trainer alloc"))) return rc;
+    if ((rc = t->d_scratch.alloc(size_t(t->scratch_cap), "trainer alloc"))) return rc;
     *out = t.release();
     return GECCO_CRF_OK;
 }
@@ -757,7 +735,7 @@ template <int NP>
 void launch_item_scores(const Group &gr, const ItemGroup *igs, const Slot *slots, const Trainer *t, const double *wstate,
                         hipStream_t st) {
     train_item_scores<NP><<<dim3(unsigned(gr.blk_items)), kTrainThreads, 0, st>>>(
-        igs, gr.g1 - gr.g0, slots, t->d_sets, t->d_item_ptr, t->d_attr_id, wstate, t->d_scratch);
+        igs, gr.g1 - gr.g0, slots, t->d_sets.get(), t->d_item_ptr.get(), t->d_attr_id.get(), wstate, t->d_scratch.get());
 }
 
 }  // namespace
@@ -842,35 +820,35 @@ int trainer_eval(Trainer *t, const uint8_t *active, const double *const *w, doub
     }
     if (open) close(cur);
 
-    int rc = check_hip(hipSetDevice(t->device), "hipSetDevice");
+    int rc = set_device(t->device);
     if (rc) return rc;
-    hipStream_t st = t->stream;
+    hipStream_t st = t->stream.get();
     if (!groups.empty()) {
-        const double *d_wstate = reinterpret_cast<const double *>(t->d_in + t->ws_off);
-        if ((rc = check_hip(hipMemcpyAsync(t->d_in, t->h_in.data(), in_hi, hipMemcpyHostToDevice, st), "trainer weights upload")))
+        const double *d_wstate = reinterpret_cast<const double *>(t->d_in.get() + t->ws_off);
+        if ((rc = check_hip(hipMemcpyAsync(t->d_in.get(), t->h_in.data(), in_hi, hipMemcpyHostToDevice, st), "trainer weights upload")))
             return rc;
         // groups run one after another on the stream and share the work space
         for (const Group &gr : groups) {
-            const Slot *d_slots = reinterpret_cast<const Slot *>(t->d_in) + gr.s0;
-            const ItemGroup *d_igs = reinterpret_cast<const ItemGroup *>(t->d_in + t->igs_off) + gr.g0;
+            const Slot *d_slots = reinterpret_cast<const Slot *>(t->d_in.get()) + gr.s0;
+            const ItemGroup *d_igs = reinterpret_cast<const ItemGroup *>(t->d_in.get() + t->igs_off) + gr.g0;
             const int ns = gr.s1 - gr.s0, ng = gr.g1 - gr.g0;
             if (gr.np <= 1) launch_item_scores<1>(gr, d_igs, d_slots, t, d_wstate, st);
             else if (gr.np <= 2) launch_item_scores<2>(gr, d_igs, d_slots, t, d_wstate, st);
             else if (gr.np <= 4) launch_item_scores<4>(gr, d_igs, d_slots, t, d_wstate, st);
             else launch_item_scores<kTrainSetProbs>(gr, d_igs, d_slots, t, d_wstate, st);
             const size_t lds = size_t(gr.lds_w) * kTrainWinThreads * 3 * sizeof(double);
-            train_windows<<<dim3(unsigned(gr.blk_win)), kTrainWinThreads, lds, st>>>(d_slots, ns, t->d_sets, t->d_label,
-                                                                                   t->d_win_start, gr.lds_w, t->d_scratch);
+            train_windows<<<dim3(unsigned(gr.blk_win)), kTrainWinThreads, lds, st>>>(d_slots, ns, t->d_sets.get(), t->d_label.get(),
+                                                                                   t->d_win_start.get(), gr.lds_w, t->d_scratch.get());
             train_item_marginals<<<dim3(unsigned(gr.blk_items)), kTrainThreads, 0, st>>>(
-                d_igs, ng, d_slots, t->d_sets, t->d_iw_first, t->d_iw_cnt, t->d_iw_off, t->d_scratch);
-            train_attr_counts<<<dim3(unsigned(gr.blk_attr)), kTrainThreads, 0, st>>>(d_slots, ns, t->d_sets, t->d_attr_ptr,
-                                                                                    t->d_attr_items, t->d_scratch, t->d_out);
-            train_reduce_rows<<<ns * kTrainReduceBlocks, kTrainThreads, 0, st>>>(d_slots, t->d_sets, t->d_scratch,
-                                                                                 t->d_partial);
-            train_reduce_final<<<ns, kTrainReduceBlocks, 0, st>>>(d_slots, t->d_partial, t->d_out);
+                d_igs, ng, d_slots, t->d_sets.get(), t->d_iw_first.get(), t->d_iw_cnt.get(), t->d_iw_off.get(), t->d_scratch.get());
+            train_attr_counts<<<dim3(unsigned(gr.blk_attr)), kTrainThreads, 0, st>>>(d_slots, ns, t->d_sets.get(), t->d_attr_ptr.get(),
+                                                                                    t->d_attr_items.get(), t->d_scratch.get(), t->d_out.get());
+            train_reduce_rows<<<ns * kTrainReduceBlocks, kTrainThreads, 0, st>>>(d_slots, t->d_sets.get(), t->d_scratch.get(),
+                                                                                 t->d_partial.get());
+            train_reduce_final<<<ns, kTrainReduceBlocks, 0, st>>>(d_slots, t->d_partial.get(), t->d_out.get());
         }
         if ((rc = check_hip(hipGetLastError(), "trainer kernels"))) return rc;
-        if ((rc = check_hip(hipMemcpyAsync(t->h_out.data() + out_lo, t->d_out + out_lo,
+        if ((rc = check_hip(hipMemcpyAsync(t->h_out.data() + out_lo, t->d_out.get() + out_lo,
                                            size_t(out_hi - out_lo) * sizeof(double), hipMemcpyDeviceToHost, st),
                             "trainer download")))
             return rc;

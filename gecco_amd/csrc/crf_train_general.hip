@@ -475,7 +475,8 @@ void with_group(int G, F &&fn) {
 // Problems resident on one device: every problem's arrays concatenated into one device array per kind, and one work
 // space with every problem's scratch (so that the active problems of an evaluation run back to back on the stream).
 struct TrainerGeneral {
-    int device = 0;
+    DeviceScope home{DeviceScope::kLater};  // (first member: see ~TrainerGeneral)
+    int device = -1;  // set once the device has been checked
     bool whole = false;  // the whole-sequence family: every problem's instances are its sequences (W = step = 0)
     struct Prob {
         int32_t A, n_items, K, L, W, step, n_blocks;
@@ -493,24 +494,14 @@ struct TrainerGeneral {
     };
     std::vector<Prob> probs;
     std::vector<double> h_in, h_out;
-    hipStream_t stream = nullptr;
-    int32_t *d_item_ptr = nullptr, *d_attr_id = nullptr, *d_label = nullptr, *d_win_start = nullptr, *d_win_len = nullptr;
-    int32_t *d_iw_first = nullptr, *d_iw_cnt = nullptr, *d_iw_off = nullptr, *d_attr_ptr = nullptr, *d_attr_items = nullptr;
-    double *d_in = nullptr, *d_out = nullptr, *d_scratch = nullptr, *d_attr_value = nullptr;
-    uint32_t *d_allowed = nullptr;
+    Stream stream;
+    DeviceBlock<int32_t> d_item_ptr, d_attr_id, d_label, d_win_start, d_win_len, d_iw_first, d_iw_cnt, d_iw_off, d_attr_ptr, d_attr_items;
+    DeviceBlock<double> d_in, d_out, d_scratch, d_attr_value;
+    DeviceBlock<uint32_t> d_allowed;
 
-    ~TrainerGeneral() {
-        if (!stream) return;  // refused before the device was checked: nothing to free, and no HIP call
-        int prev = -1;
-        const bool restore = hipGetDevice(&prev) == hipSuccess && prev != device;
-        (void)hipSetDevice(device);
-        for (void *p : {(void *)d_item_ptr, (void *)d_attr_id, (void *)d_label, (void *)d_win_start, (void *)d_win_len,
-                        (void *)d_iw_first, (void *)d_iw_cnt, (void *)d_iw_off, (void *)d_attr_ptr, (void *)d_attr_items,
-                        (void *)d_in, (void *)d_out, (void *)d_scratch, (void *)d_attr_value, (void *)d_allowed})
-            if (p) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (restore && prev >= 0) (void)hipSetDevice(prev);
-    }
+    // The members free themselves, in reverse order, after this body: with the trainer's device current, and `home` hands the
+    // caller's device back at the end.  Refused before the device was checked (device < 0): nothing to free, and no HIP call.
+    ~TrainerGeneral() { home.enter(device); }
 };
 
 namespace {
@@ -524,7 +515,6 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
                          const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
                          const double *const *attr_value, const uint32_t *const *allowed, TrainerGeneral **out) {
     auto t = std::make_unique<TrainerGeneral>();
-    t->device = device;
     const bool whole = t->whole = window == nullptr;
     const std::string family = whole ? "trainer sequences: problem " : "trainer general: problem ";
     std::vector<int32_t> item_ptr_c, attr_id_c, label_c, win_start_c, win_len_c, iw_first_c, iw_cnt_c, iw_off_c, attr_ptr_c,
@@ -610,41 +600,32 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
         p.empirical = std::move(hp.empirical);
         t->probs.push_back(std::move(p));
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        set_error("no HIP device available (this library has no CPU fallback)");
-        return GECCO_CRF_ENODEV;
-    }
-    if (device < 0 || device >= ndev) {
-        set_error("device index out of range");
-        return GECCO_CRF_ENODEV;
-    }
+    int rc = check_device(device);
+    if (rc) return rc;
+    t->device = device;
     t->h_in.assign(size_t(in_total), 0.0);
     t->h_out.assign(size_t(out_total), 0.0);
-    int rc = check_hip(hipSetDevice(device), "hipSetDevice");
-    if (rc) return rc;
-    if ((rc = check_hip(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
-    if ((rc = dev_upload(&t->d_item_ptr, item_ptr_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_attr_id, attr_id_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_label, label_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_win_start, win_start_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_win_len, win_len_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_iw_first, iw_first_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_iw_cnt, iw_cnt_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_iw_off, iw_off_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_attr_ptr, attr_ptr_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_attr_items, attr_items_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_in, t->h_in, "trainer alloc"))) return rc;
-    if ((rc = dev_upload(&t->d_out, t->h_out, "trainer alloc"))) return rc;
-    if ((rc = check_hip(hipMalloc(reinterpret_cast<void **>(&t->d_scratch), std::max<size_t>(size_t(scratch_total), 1) * sizeof(double)),
-                        "trainer alloc")))
-        return rc;
-    if ((rc = dev_upload(&t->d_attr_value, attr_value_c, "trainer upload"))) return rc;
-    if ((rc = dev_upload(&t->d_allowed, allowed_c, "trainer upload"))) return rc;
+    if ((rc = set_device(device))) return rc;
+    if ((rc = t->stream.create())) return rc;
+    if ((rc = t->d_item_ptr.upload(item_ptr_c, "trainer upload"))) return rc;
+    if ((rc = t->d_attr_id.upload(attr_id_c, "trainer upload"))) return rc;
+    if ((rc = t->d_label.upload(label_c, "trainer upload"))) return rc;
+    if ((rc = t->d_win_start.upload(win_start_c, "trainer upload"))) return rc;
+    if ((rc = t->d_win_len.upload(win_len_c, "trainer upload"))) return rc;
+    if ((rc = t->d_iw_first.upload(iw_first_c, "trainer upload"))) return rc;
+    if ((rc = t->d_iw_cnt.upload(iw_cnt_c, "trainer upload"))) return rc;
+    if ((rc = t->d_iw_off.upload(iw_off_c, "trainer upload"))) return rc;
+    if ((rc = t->d_attr_ptr.upload(attr_ptr_c, "trainer upload"))) return rc;
+    if ((rc = t->d_attr_items.upload(attr_items_c, "trainer upload"))) return rc;
+    if ((rc = t->d_in.upload(t->h_in, "trainer alloc"))) return rc;
+    if ((rc = t->d_out.upload(t->h_out, "trainer alloc"))) return rc;
+    if ((rc = t->d_scratch.alloc(size_t(scratch_total), "trainer alloc"))) return rc;
+    if ((rc = t->d_attr_value.upload(attr_value_c, "trainer upload"))) return rc;
+    if ((rc = t->d_allowed.upload(allowed_c, "trainer upload"))) return rc;
     for (int32_t k = 0; k < n_problems; ++k) {
         const TrainerGeneral::Prob &p = t->probs[size_t(k)];
         if (p.val0 < 0 || p.nnz == 0) continue;
-        if ((rc = check_hip(hipMemcpy(t->d_scratch + p.sc0 + p.scratch - p.nnz, transposed[size_t(k)].data(),
+        if ((rc = check_hip(hipMemcpy(t->d_scratch.get() + p.sc0 + p.scratch - p.nnz, transposed[size_t(k)].data(),
                                       size_t(p.nnz) * sizeof(double), hipMemcpyHostToDevice),
                             "trainer upload")))
             return rc;
@@ -694,11 +675,11 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
         out_lo = std::min(out_lo, p.out0);
         out_hi = std::max(out_hi, p.out0 + cols + int64_t(p.A) * p.L);
     }
-    int rc = check_hip(hipSetDevice(t->device), "hipSetDevice");
+    int rc = set_device(t->device);
     if (rc) return rc;
-    hipStream_t st = t->stream;
+    hipStream_t st = t->stream.get();
     if (in_hi > 0) {
-        if ((rc = check_hip(hipMemcpyAsync(t->d_in + in_lo, t->h_in.data() + in_lo, size_t(in_hi - in_lo) * sizeof(double),
+        if ((rc = check_hip(hipMemcpyAsync(t->d_in.get() + in_lo, t->h_in.data() + in_lo, size_t(in_hi - in_lo) * sizeof(double),
                                            hipMemcpyHostToDevice, st),
                             "trainer weights upload")))
             return rc;
@@ -707,33 +688,33 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             if (!active[k] || p.n_win == 0) continue;
             const int64_t cols = 1 + int64_t(p.L) * p.L, nl = int64_t(p.n_items) * p.L;
             GenProb a;
-            a.item_ptr = t->d_item_ptr + p.iptr0;
-            a.attr_id = t->d_attr_id + p.nnz0;
-            a.label = t->d_label + p.item0;
-            a.win_start = t->d_win_start + p.win0;
-            a.win_len = t->d_win_len + (t->whole ? p.win0 : 0);
+            a.item_ptr = t->d_item_ptr.get() + p.iptr0;
+            a.attr_id = t->d_attr_id.get() + p.nnz0;
+            a.label = t->d_label.get() + p.item0;
+            a.win_start = t->d_win_start.get() + p.win0;
+            a.win_len = t->d_win_len.get() + (t->whole ? p.win0 : 0);
             // (the item coverage is the windowed family's alone: in a whole-sequence trainer the arrays are empty)
-            a.iw_first = t->d_iw_first + (t->whole ? 0 : p.item0);
-            a.iw_cnt = t->d_iw_cnt + (t->whole ? 0 : p.item0);
-            a.iw_off = t->d_iw_off + (t->whole ? 0 : p.item0);
-            a.attr_ptr = t->d_attr_ptr + p.aptr0;
-            a.attr_items = t->d_attr_items + p.nnz0;
-            a.wstate = t->d_in + p.in0;
+            a.iw_first = t->d_iw_first.get() + (t->whole ? 0 : p.item0);
+            a.iw_cnt = t->d_iw_cnt.get() + (t->whole ? 0 : p.item0);
+            a.iw_off = t->d_iw_off.get() + (t->whole ? 0 : p.item0);
+            a.attr_ptr = t->d_attr_ptr.get() + p.aptr0;
+            a.attr_items = t->d_attr_items.get() + p.nnz0;
+            a.wstate = t->d_in.get() + p.in0;
             a.trans = a.wstate + int64_t(p.A) * p.L;
-            a.score = t->d_scratch + p.sc0;
+            a.score = t->d_scratch.get() + p.sc0;
             a.item_marg = a.score + nl;
             a.marg = a.item_marg + nl;
             a.partial = a.marg + p.n_win * p.W * p.L;
             a.slab = a.partial + int64_t(p.n_blocks) * cols;
-            a.out = t->d_out + p.out0;
+            a.out = t->d_out.get() + p.out0;
             a.n_win = p.n_win;
             a.n_items = p.n_items, a.A = p.A, a.L = p.L, a.W = p.W, a.step = p.step, a.n_blocks = p.n_blocks;
             const unsigned nb_items = unsigned(blocks_of(nl, kTrainGenThreads));
             const int G = group_of(p.L);
             // (a problem has values or has none: the branch is the same for every thread of its launches)
             const bool valued = p.val0 >= 0;
-            const double *attr_value = valued ? t->d_attr_value + p.val0 : nullptr;
-            const double *attr_item_value = valued ? t->d_scratch + p.sc0 + p.scratch - p.nnz : nullptr;
+            const double *attr_value = valued ? t->d_attr_value.get() + p.val0 : nullptr;
+            const double *attr_item_value = valued ? t->d_scratch.get() + p.sc0 + p.scratch - p.nnz : nullptr;
             if (valued)
                 gen_item_scores<true><<<nb_items, kTrainGenThreads, 0, st>>>(a, attr_value);
             else
@@ -741,7 +722,7 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             // kernel 2: the instantiation of the problem's group size and family; a problem with masks runs both passes in
             // one kernel, which hands on their difference
             const bool masked = p.allow0 >= 0;
-            const uint32_t *al = masked ? t->d_allowed + p.allow0 : nullptr;
+            const uint32_t *al = masked ? t->d_allowed.get() + p.allow0 : nullptr;
             double *la_a = masked ? a.slab + kTrainGenReduceSlabs * cols : nullptr;
             const unsigned nb = unsigned(p.n_blocks);
             with_group(G, [&](auto g) {
@@ -767,7 +748,7 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             gen_reduce_final<<<1, kTrainGenThreads, 0, st>>>(a);
         }
         if ((rc = check_hip(hipGetLastError(), "trainer kernels"))) return rc;
-        if ((rc = check_hip(hipMemcpyAsync(t->h_out.data() + out_lo, t->d_out + out_lo, size_t(out_hi - out_lo) * sizeof(double),
+        if ((rc = check_hip(hipMemcpyAsync(t->h_out.data() + out_lo, t->d_out.get() + out_lo, size_t(out_hi - out_lo) * sizeof(double),
                                            hipMemcpyDeviceToHost, st),
                             "trainer download")))
             return rc;
