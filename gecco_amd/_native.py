@@ -99,6 +99,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, _c_i8p, _c_f64p,
          _c_i32p, _c_f64p],
     ),
+    "gecco_crf_edge_posteriors": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_u32p, ctypes.c_int32, _c_f64p,
+         _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_segment": (
         ctypes.c_int,
         [ctypes.c_int32, _c_f64p, _c_u8p, _c_i32p, ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32,
@@ -721,6 +726,47 @@ class Model:
         _check(self._lib.gecco_crf_viterbi_kbest(
             *head, values, allowed, k, _ptr(y, _c_i8p), _ptr(score, _c_f64p), _ptr(n_paths, _c_i32p), _ptr(ln, _c_f64p)))
         return y[:n - n0], score[:nc], n_paths[:nc], ln[:nc]
+
+    def edge_posteriors(self, contig_ptr, gene_ptr, attr_id, sets=None, want_pair=False, want_transitions=True, want_entropy=True,
+                        want_marginals=False, device=0, values=None, allowed=None):
+        """Edge posteriors of the whole-contig lattice (``gecco_crf_edge_posteriors``), behind ONE forward-backward pass of the
+        batch.  Returns a dict that holds only what was asked for -- nothing else is allocated, computed or copied:
+        ``"pair"`` (``want_pair``) float64 ``[n, L, L]``, ``pair[g, i, j] = P(y_{g-1} = i, y_g = j | x)``, zeros at a contig's
+        first gene -- 8 L^2 bytes per gene, 8 KB at 32 labels;
+        ``"enter"``, ``"leave"`` (``sets``: 1 to 32 uint32 masks, bit y set when label y is in the set) float64
+        ``[n, n_sets]``: the probability that a run of labels of the set starts / ends at the gene;
+        ``"transitions"`` (``want_transitions``) ``[n_contigs, L, L]``: the expected number of (i, j) transitions of a contig;
+        ``"entropy"`` (``want_entropy``) ``[n_contigs]``: the entropy of the contig's path distribution in nats;
+        ``"marginals"`` ``[n, L]`` and ``"lognorm"`` ``[n_contigs]`` (``want_marginals``) as ``marginals_full`` gives them.
+        ``values`` and ``allowed`` as in ``marginals_full``: with ``allowed`` the lattice is the restricted one."""
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        L = self.num_labels
+        ns = 0
+        if sets is not None:
+            sm = np.ascontiguousarray(sets, dtype=np.uint32).ravel()
+            ns = sm.size
+        rows = max(n - n0, 1)
+        width = ns if 1 <= ns <= 32 else 1  # (the library refuses any other number of sets: the buffers only need a size)
+        out = {}
+        if want_pair:
+            out["pair"] = np.zeros((rows, L, L), dtype=np.float64)
+        if sets is not None:
+            out["enter"] = np.zeros((rows, width), dtype=np.float64)
+            out["leave"] = np.zeros((rows, width), dtype=np.float64)
+        if want_transitions:
+            out["transitions"] = np.zeros((max(nc, 1), L, L), dtype=np.float64)
+        if want_entropy:
+            out["entropy"] = np.zeros(max(nc, 1), dtype=np.float64)
+        if want_marginals:
+            out["marginals"] = np.zeros((rows, L), dtype=np.float64)
+            out["lognorm"] = np.zeros(max(nc, 1), dtype=np.float64)
+        ptr = {k: _ptr(v, _c_f64p) for k, v in out.items()}
+        _check(self._lib.gecco_crf_edge_posteriors(
+            *head, values, allowed, _ptr(sm if ns else np.zeros(1, dtype=np.uint32), _c_u32p) if sets is not None else None, ns,
+            ptr.get("pair"), ptr.get("enter"), ptr.get("leave"), ptr.get("transitions"), ptr.get("entropy"), ptr.get("marginals"),
+            ptr.get("lognorm")))
+        per_gene = ("pair", "enter", "leave", "marginals")
+        return {k: v[:n - n0] if k in per_gene else v[:nc] for k, v in out.items()}
 
 
 def domain_composition(seg, dom_ptr, dom_col, dom_weight, n_cols, normalize=True, device=0) -> np.ndarray:

@@ -950,7 +950,7 @@ int marginals_full_of_slice(const gecco_crf_model *m, int32_t device, const int3
     return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
 }
 
-// One call of a lattice query -- region posteriors, sampled paths, the K best paths.  The batch goes to the device on a plan laid
+// One call of a lattice query -- region posteriors, sampled paths, the K best paths, edge posteriors.  The batch goes to the device on a plan laid
 // out with `lattice`: the marginals at out(0), per_gene1 bytes a gene at out(1), log Z and then per_contig_more bytes a contig at
 // out(2).  `run(b)` is the entry's part: its plan_run_* call and the fetch of its own outputs; of a batch without genes (b.n == 0:
 // nothing is on the device, and log Z = 0 is written by then) it only fills what else the entry returns.  marg / lognorm (either
@@ -1118,6 +1118,78 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
         rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * K, "download paths");
         rc = batch_fetch(rc, score, d_score, nc * K * 8, "download scores");
         return batch_fetch(rc, n_paths, d_n_paths, nc * 4, "download n_paths");
+    });
+    GECCO_GUARD_END
+}
+
+// ---- edge posteriors (ABI 2.19.0): the pairwise marginals of the whole-contig lattice, the probability that a run of labels of a
+// set starts or ends at a gene, a contig's expected transition counts and its path entropy, all behind one forward-backward
+// pass of the batch (crf_edges.hip)
+GECCO_API int gecco_crf_edge_posteriors(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                        const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                        const uint32_t *allowed, const uint32_t *set_mask, int32_t n_sets, double *pair, double *enter,
+                                        double *leave, double *transitions, double *entropy, double *marg, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the sets, on the host and before any device work
+    if (n_sets < 0 || n_sets > kMaxEdgeSets)
+        return fail("edge_posteriors: n_sets = " + std::to_string(n_sets) + " is outside 1 .. 32 (0: no set, without enter and leave)");
+    if (n_sets == 0 && (enter || leave)) return fail("edge_posteriors: enter and leave need a label set (n_sets = 0)");
+    if (n_sets > 0 && !set_mask) return fail("null buffer");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    EdgeQuery eq{};
+    for (int32_t s = 0; s < n_sets; ++s) {
+        if ((rc = check_label_set("set", s, set_mask[s], m->m.L))) return rc;
+        eq.set_mask[s] = set_mask[s];
+    }
+    eq.n_sets = n_sets;
+    const size_t L = size_t(m->m.L), nc = size_t(n_contigs), S = size_t(n_sets);
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: no edge, no run, a path distribution of one empty path)
+            for (size_t k = 0; transitions && k < nc * L * L; ++k) transitions[k] = 0.0;
+            for (size_t c = 0; entropy && c < nc; ++c) entropy[c] = 0.0;
+            return int(GECCO_CRF_OK);
+        }
+        // every contig's runs, counted from its own first gene
+        std::vector<int32_t> run_ptr(nc + 1, 0);
+        for (size_t c = 0; c < nc; ++c) run_ptr[c + 1] = run_ptr[c] + edge_run_count(int64_t(contig_ptr[c + 1]) - contig_ptr[c]);
+        const size_t nr = size_t(run_ptr[nc]), n = size_t(b.n);
+        std::vector<EdgeRun> runs(nr);
+        for (size_t c = 0; c < nc; ++c)
+            for (int32_t k = run_ptr[c]; k < run_ptr[c + 1]; ++k) runs[size_t(k)] = EdgeRun{int32_t(c), (k - run_ptr[c]) * kEdgeRunGenes};
+        // one block: the two tables at its head, then the outputs that were asked for and the partials behind them
+        Carver at;
+        const size_t b_runs = nr * sizeof(EdgeRun), b_ptr = (nc + 1) * 4;
+        const size_t o_runs = at.take(b_runs), o_ptr = at.take(b_ptr);
+        const size_t o_pair = pair ? at.take(n * L * L * 8) : 0, o_enter = enter ? at.take(n * S * 8) : 0,
+                     o_leave = leave ? at.take(n * S * 8) : 0, o_trans = transitions ? at.take(nc * L * L * 8) : 0,
+                     o_npart = transitions ? at.take(nr * L * L * 8) : 0, o_ent = entropy ? at.take(nc * 8) : 0,
+                     o_hpart = entropy ? at.take(nr * 8) : 0;
+        DeviceBlock<char> d;
+        int rc = d.alloc(at.off, "hipMalloc edge posteriors");
+        if (!rc) rc = check_hip(hipMemcpy(d.get() + o_runs, runs.data(), b_runs, hipMemcpyHostToDevice), "upload runs");
+        if (!rc) rc = check_hip(hipMemcpy(d.get() + o_ptr, run_ptr.data(), b_ptr, hipMemcpyHostToDevice), "upload run_ptr");
+        if (rc) return rc;
+        auto out = [&](bool wanted, size_t off) { return wanted ? reinterpret_cast<double *>(d.get() + off) : nullptr; };
+        EdgeQuery q = eq;
+        q.n_runs = int32_t(nr);
+        q.runs = reinterpret_cast<const EdgeRun *>(d.get() + o_runs);
+        q.run_ptr = reinterpret_cast<const int32_t *>(d.get() + o_ptr);
+        q.pair = out(pair, o_pair);
+        q.enter = out(enter, o_enter);
+        q.leave = out(leave, o_leave);
+        q.transitions = out(transitions, o_trans);
+        q.npart = out(transitions, o_npart);
+        q.entropy = out(entropy, o_ent);
+        q.hpart = out(entropy, o_hpart);
+        rc = batch_wait(plan_run_edge_posteriors(b.plan, b.csr, q, b.out<double>(0), b.out<double>(2), nullptr), "edge posteriors");
+        rc = batch_fetch(rc, pair, q.pair, n * L * L * 8, "download pair");
+        rc = batch_fetch(rc, enter, q.enter, n * S * 8, "download enter");
+        rc = batch_fetch(rc, leave, q.leave, n * S * 8, "download leave");
+        rc = batch_fetch(rc, transitions, q.transitions, nc * L * L * 8, "download transitions");
+        return batch_fetch(rc, entropy, q.entropy, nc * 8, "download entropy");
     });
     GECCO_GUARD_END
 }

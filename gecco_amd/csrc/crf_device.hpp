@@ -356,6 +356,32 @@ size_t kbest_fin_bytes(int32_t n_contigs, int32_t k);
 hipError_t launch_gen_kbest(const GenArgs &a, int32_t k, uint16_t *back, uint16_t *fin, int8_t *y, double *score, int32_t *n_paths,
                             hipStream_t stream);
 
+// ---- edge posteriors (crf_edges.hip) ----
+constexpr int32_t kMaxEdgeSets = 32;   // label sets of one call
+constexpr int32_t kEdgeRunGenes = 32;  // genes of a run: what one group of lanes walks, counted from its contig's first gene
+inline int32_t edge_run_count(int64_t contig_genes) { return int32_t((contig_genes + kEdgeRunGenes - 1) / kEdgeRunGenes); }
+// One run: the genes [begin, begin + kEdgeRunGenes) of contig `contig`, clipped to it; `begin` is a multiple of kEdgeRunGenes.
+struct EdgeRun {
+    int32_t contig, begin;
+};
+// What one call asks for.  The host has checked that every mask has a bit, and none at or above L.  runs [n_runs]: every
+// contig's runs, contig after contig, each contig's in gene order (edge_run_count of them); run_ptr [n_contigs + 1]: where a
+// contig's runs start.  Every output is optional, null = not stored: pair [n_genes][L][L]; enter, leave [n_genes][n_sets];
+// transitions [n_contigs][L][L], which needs npart [n_runs][L][L]; entropy [n_contigs], which needs hpart [n_runs].
+struct EdgeQuery {
+    uint32_t set_mask[kMaxEdgeSets];
+    int32_t n_sets, n_runs;
+    const EdgeRun *runs;
+    const int32_t *run_ptr;
+    double *pair, *enter, *leave, *transitions, *entropy;
+    double *npart, *hpart;
+};
+// The edge marginals xi_t(i, j) = P(y_{t-1} = i, y_t = j | x) of the edge entering every gene (zeros at a contig's first gene) and
+// their sums, on the lattice of the whole-contig marginals that ran before it on the same stream: reads a.E, a.alpha (as
+// directions, whatever arrangement filled them), a.marg, a.exp_trans and a.contig_ptr.  Two launches: the runs, then the sums of
+// a contig's partials in run order.
+hipError_t launch_gen_edges(const GenArgs &a, const EdgeQuery &q, hipStream_t stream);
+
 // ---- any number of labels: windowed marginals, one label or every label (crf_general_windowed.hip) ----
 // label >= 0: p_out[g] = max over the windows covering g of P_w(y_g = label), clipped at 1 by the tile kernels.
 // label < 0: every label in one pass, p_out[g][l] likewise for all l, and p_any[g] = max over the same windows of the sum of

@@ -1362,6 +1362,27 @@ int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d
     return check_hip(launch_gen_kbest(g, k, d_back, d_fin, d_y, d_score, d_n_paths, stream), "k-best launch");
 }
 
+int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    if (q.n_sets < 0 || q.n_sets > kMaxEdgeSets || (q.n_sets == 0 && (q.enter || q.leave))) {
+        set_error("the number of label sets is outside 1 .. 32 (0 without enter and leave)");
+        return GECCO_CRF_EINVAL;
+    }
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !d_marg || !q.runs || !q.run_ptr || (q.transitions && !q.npart) || (q.entropy && !q.hpart), rc))
+        return rc;
+    // (the run table is the caller's: it has to be the one of this layout's contigs, or a run would leave its contig)
+    int64_t n_runs = 0;
+    for (int32_t c = 0; c < p.n_contigs; ++c) n_runs += edge_run_count(p.contig_ptr[c + 1] - p.contig_ptr[c]);
+    if (q.n_runs != n_runs) {
+        set_error("edge posteriors: the run table does not belong to the plan's contigs");
+        return GECCO_CRF_EINVAL;
+    }
+    GenArgs g;  // (the raw state scores are not needed: the edges read E, alpha and the marginals)
+    if ((rc = run_lattice(p, csr, "edge posteriors", false, d_marg, d_lognorm, stream, g))) return rc;
+    return check_hip(launch_gen_edges(g, q, stream), "edge launch");
+}
+
 int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score,
                      hipStream_t stream) {
     SeqArgs a;

@@ -48,6 +48,17 @@ ones, and ``known=`` restricts the lattice in the same way.  ``clusters.tsv`` th
 ``start_lo``, ``start_hi``, ``end_lo`` and ``end_hi`` behind the region columns; with N = 0 the tables and every launch are
 unchanged.
 
+Boundary posteriors (opt-in: ``boundary_posteriors=True``, ``predict --boundary-posteriors``).  The exact counterpart of the
+sampled intervals: with S the set of every label but the background, every called cluster carries ``start_probability``, the
+whole-contig posterior probability that a run of cluster labels STARTS at its first gene (that gene is in S and the gene
+before it, if any, is not), and ``end_probability``, that one ENDS at its last gene -- sums of entries of the pairwise
+marginals of the edge entering the first gene, and of the edge leaving the last (``_native.Model.edge_posteriors``: one forward-backward pass and one native call per
+batch, every gene of the batch at once).  ``sequence_posteriors_`` then holds, per contig, ``sequence_id``, ``genes``,
+``log_z``, ``entropy`` (of the contig's path distribution, in nats) and ``expected_clusters`` (the expected number of runs of
+S: the sum over the contig of the start probabilities).  Whole-contig posteriors like the region posteriors, and ``known=``
+restricts the lattice in the same way.  ``clusters.tsv`` then has the columns ``start_p`` and ``end_p`` behind the other
+optional columns, and the command line writes ``sequences.tsv``; without the flag the tables and every launch are unchanged.
+
 Alternatives (opt-in: ``alternatives=K``, 1 <= K <= 32, ``predict --alternatives K [--alternatives-margin M]``, M = 10 by default).
 "What are the next-best readings of this region, and how much probability does each carry": for every called cluster the K best
 label paths of its neighbourhood, exactly (``_native.Model.viterbi_kbest``: list Viterbi on the device, one native call for all
@@ -88,7 +99,7 @@ from . import tables
 
 __all__ = ["BACKGROUND", "MIXED", "UNKNOWN", "MAX_CLUSTER_LABELS", "TypedClusterCRF", "cluster_labels", "fold_labels",
            "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "write_alternatives",
-           "build_parser", "main"]
+           "write_sequences", "build_parser", "main"]
 
 BACKGROUND = "0"
 MIXED = "Mixed"
@@ -225,7 +236,8 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
     ``proteins``, in ``types.probability_columns`` order; behind them ``region_p`` and one ``{type.lower()}_region_p`` per type
     when clusters carry region posteriors (NaN for a cluster of the list that does not); behind those ``anchor_p``, ``exact_p``,
     ``start_lo``, ``start_hi``, ``end_lo`` and ``end_hi`` when clusters carry boundary intervals (``boundary_samples > 0``; a
-    cluster of the list that does not: NaN, and its own start and end)."""
+    cluster of the list that does not: NaN, and its own start and end); last ``start_p`` and ``end_p`` when clusters carry
+    boundary posteriors (``boundary_posteriors=True``)."""
     table = tables.ClusterTable.from_clusters(clusters)
     extra = []
     for name in sorted(types, key=str.casefold):
@@ -251,6 +263,12 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
                                        ("end_lo", "end_interval", 0, "end"), ("end_hi", "end_interval", 1, "end")):
             table.columns[col] = [int(getattr(c, attribute)[k]) if hasattr(c, attribute) else int(getattr(c, own)) for c in clusters]
             extra.append((col, int, None))
+    # boundary posteriors, behind every other optional column: only when clusters carry them (``boundary_posteriors=True``)
+    if any(hasattr(c, "start_probability") for c in clusters):
+        nan = float("nan")
+        table.columns["start_p"] = [float(getattr(c, "start_probability", nan)) for c in clusters]
+        table.columns["end_p"] = [float(getattr(c, "end_probability", nan)) for c in clusters]
+        extra += [("start_p", float, None), ("end_p", float, None)]
     at = [n for n, _, _ in tables.ClusterTable.COLUMNS].index("type") + 1
     table.COLUMNS = tables.ClusterTable.COLUMNS[:at] + extra + tables.ClusterTable.COLUMNS[at:]
     return table
@@ -459,17 +477,19 @@ class TypedClusterCRF:
     def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                          trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                          region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0, alternatives: int = 0,
-                         alternatives_margin: int = 10) -> List[Any]:
+                         alternatives_margin: int = 10, boundary_posteriors: bool = False) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
         per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, with
         ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities``, and with
         ``boundary_samples > 0`` each with ``anchor_probability``, ``exact_probability``, ``start_interval`` and
         ``end_interval``, and with ``alternatives = K > 0`` each with ``alternatives``, the K best readings of its
-        neighbourhood with their exact conditional probabilities (module docstring)."""
+        neighbourhood with their exact conditional probabilities, and with ``boundary_posteriors`` each with
+        ``start_probability`` and ``end_probability`` (module docstring)."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
                                                pad=pad, known=known, region_posteriors=region_posteriors,
                                                boundary_samples=boundary_samples, seed=seed, alternatives=alternatives,
-                                               alternatives_margin=alternatives_margin)[1]
+                                               alternatives_margin=alternatives_margin,
+                                               boundary_posteriors=boundary_posteriors)[1]
 
     def _region_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int,
                            clusters: List[Any]) -> None:
@@ -515,6 +535,28 @@ class TypedClusterCRF:
             lo, hi = int(math.floor(0.05 * (m - 1))), int(math.ceil(0.95 * (m - 1)))
             cluster.start_interval = (int(starts[lo]), int(starts[hi]))
             cluster.end_interval = (int(ends[lo]), int(ends[hi]))
+
+    SEQUENCE_COLUMNS = ("sequence_id", "genes", "log_z", "entropy", "expected_clusters")
+
+    def _boundary_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int, clusters: List[Any],
+                             annotated: List[Any]) -> None:
+        """``start_probability`` and ``end_probability`` of every called cluster (``rows``: the segment kernel's (contig,
+        number, first gene, last gene + 1)) and ``sequence_posteriors_``, from ONE native call over the batch: the probability
+        that a run of labels outside the background starts / ends at every gene, every contig's log Z and path entropy."""
+        out = self._fitted().edge_posteriors(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
+                                             sets=np.array([not_background], dtype=np.uint32), want_transitions=False,
+                                             want_entropy=True, want_marginals=True, device=self.device, allowed=allowed)
+        enter, leave = out["enter"][:, 0], out["leave"][:, 0]
+        for cluster, (_, _, first, last) in zip(clusters, rows.tolist()):
+            cluster.start_probability = float(enter[first])
+            cluster.end_probability = float(leave[last - 1])
+        starts = item_ptr[:-1].astype(np.int64)
+        self.sequence_posteriors_ = {
+            "sequence_id": [annotated[g].source.id for g in starts.tolist()],
+            "genes": np.diff(item_ptr).astype(np.int64).tolist(),
+            "log_z": out["lognorm"].tolist(),
+            "entropy": out["entropy"].tolist(),
+            "expected_clusters": [float(enter[a:b].sum()) for a, b in zip(item_ptr[:-1].tolist(), item_ptr[1:].tolist())]}
 
     def _alternatives(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, clusters: List[Any], annotated: List[Any],
                       p_any: np.ndarray, k: int, margin: int) -> None:
@@ -575,12 +617,15 @@ class TypedClusterCRF:
                                    trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                                    region_posteriors: bool = False, boundary_samples: int = 0,
                                    seed: int = 0, alternatives: int = 0,
-                                   alternatives_margin: int = 10) -> Tuple[List[Any], List[Any]]:
+                                   alternatives_margin: int = 10,
+                                   boundary_posteriors: bool = False) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
         second, whole-contig pass gives every cluster its region posteriors, and with ``boundary_samples = N > 0`` one more
         draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals; with ``alternatives = K >
         0`` (at most 32) a Viterbi pass and one list-Viterbi call give every cluster the K best readings of its neighbourhood of
-        ``alternatives_margin`` genes on either side (module docstring).  ``ValueError`` before any device call for an option
+        ``alternatives_margin`` genes on either side; with ``boundary_posteriors`` one more whole-contig pass gives every
+        cluster ``start_probability`` and ``end_probability`` and the model ``sequence_posteriors_``, the per-contig columns
+        ``SEQUENCE_COLUMNS`` (module docstring).  ``ValueError`` before any device call for an option
         that is not an integer or lies outside its range."""
         from . import _native
 
@@ -607,6 +652,8 @@ class TypedClusterCRF:
 
         _, contigs, scored, batch, p_all, p_any, allowed = self._score(genes, pad, known)
         annotated = self._annotated(contigs, scored, batch, p_any)
+        if boundary_posteriors:
+            self.sequence_posteriors_ = {name: [] for name in self.SEQUENCE_COLUMNS}
         if not annotated:
             return annotated, []
         has_domains = np.fromiter((1 if g.protein.domains else 0 for g in annotated), dtype=np.uint8, count=len(annotated))
@@ -629,6 +676,8 @@ class TypedClusterCRF:
             self._region_posteriors(batch, allowed, rows, item_ptr, not_background, clusters)
         if boundary_samples > 0 and clusters:
             self._boundary_intervals(batch, allowed, rows, item_ptr, not_background, clusters, annotated, p_any, boundary_samples, seed)
+        if boundary_posteriors:  # (the per-contig table does not need a called cluster)
+            self._boundary_posteriors(batch, allowed, rows, item_ptr, not_background, clusters, annotated)
         if alternatives > 0 and clusters:
             self._alternatives(batch, allowed, rows, item_ptr, clusters, annotated, p_any, alternatives, alternatives_margin)
         return annotated, clusters
@@ -644,6 +693,16 @@ def write_alternatives(path, clusters: Sequence[Any]) -> None:
                 run = alt["run"] is not None
                 where = (str(alt["start"]), str(alt["end"]), alt["type"]) if run else ("", "", "")
                 out.write("\t".join((str(cluster.id), str(alt["rank"]), *where, repr(alt["log_p"]), repr(math.exp(alt["log_p"])))) + "\n")
+
+
+def write_sequences(path, columns: Dict[str, Sequence[Any]]) -> None:
+    """``sequences.tsv``: one row per contig, columns ``TypedClusterCRF.SEQUENCE_COLUMNS`` (``sequence_posteriors_``); floats
+    with ``repr``."""
+    names = TypedClusterCRF.SEQUENCE_COLUMNS
+    with open(path, "w") as out:
+        out.write("\t".join(names) + "\n")
+        for row in zip(*(columns[name] for name in names)):
+            out.write("\t".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
 
 
 # ---------------------------------------------------------------------------------------------- command line
@@ -695,6 +754,10 @@ def build_parser() -> argparse.ArgumentParser:
                     "each with its exact probability given that the rest of the contig follows the Viterbi path")
     pr.add_argument("--alternatives-margin", type=int, default=10, metavar="M",
                     help="genes on either side of a called region in its neighbourhood (with --alternatives)")
+    pr.add_argument("--boundary-posteriors", action="store_true",
+                    help="add start_p and end_p to clusters.tsv: the whole-contig posterior probability that a run of cluster labels "
+                    "starts at a called region's first gene, and ends at its last; write sequences.tsv: per contig its log Z, "
+                    "path entropy and expected number of clusters")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -724,13 +787,16 @@ def main(argv: Optional[List[str]] = None) -> int:
                                                       region_posteriors=args.region_posteriors,
                                                       boundary_samples=args.boundary_samples, seed=args.seed,
                                                       alternatives=args.alternatives,
-                                                      alternatives_margin=args.alternatives_margin)
+                                                      alternatives_margin=args.alternatives_margin,
+                                                      boundary_posteriors=args.boundary_posteriors)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))
     typed_cluster_table(found, crf.types_).dump(os.path.join(args.output_dir, "clusters.tsv"))
     if args.alternatives > 0:
         write_alternatives(os.path.join(args.output_dir, "alternatives.tsv"), found)
+    if args.boundary_posteriors:
+        write_sequences(os.path.join(args.output_dir, "sequences.tsv"), crf.sequence_posteriors_)
     print(f"predict: {len(annotated)} genes, {len(found)} clusters -> {args.output_dir}", file=sys.stderr)
     return 0
 

@@ -51,7 +51,7 @@ const char *gecco_crf_last_error(void);
 /* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
- * gecco_crf_viterbi_kbest. */
+ * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -831,6 +831,42 @@ int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, const int3
                             const uint32_t *allowed /* NULL: no masks */, int32_t k, int8_t *y /* [n_genes][k] */,
                             double *score /* [n_contigs][k] */, int32_t *n_paths /* [n_contigs] */,
                             double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- edge posteriors (ABI 2.19.0, additive; gecco_crf_version() stays 340) -----------------------------------------------------
+ * The pairwise (edge) marginals xi_t(i, j) = P(y_{t-1} = i, y_t = j | x) on the whole-contig lattice of gecco_crf_viterbi and
+ * gecco_crf_marginals_full (not a windowed one), and what follows from them, behind ONE forward-backward pass of the batch.  With
+ * `allowed` (one mask per gene, as the *_constrained entries take them) the lattice is the restricted one, and a disallowed
+ * (gene, label) pair contributes exact zeros everywhere.  attr_value and allowed may each be NULL.  Every output may be NULL: it
+ * is then neither computed nor stored.  An edge depends on the two genes it joins only: the query is parallel over genes.
+ *   * pair [n_genes][L][L]: pair[g][i][j] = xi of the edge entering gene g, all zeros for a contig's first gene.  8 L^2 bytes per
+ *     gene (8 KB at 32 labels): ask for it only when the table itself is wanted.
+ *   * enter, leave [n_genes][n_sets], for the label sets set_mask[0 .. n_sets) (bit y set: label y is inside):
+ *     enter[g][s] = P(y_g in S and (g is its contig's first gene or y_{g-1} not in S)): a run of labels of S starts at g;
+ *     leave[g][s] = P(y_g in S and (g is its contig's last gene or y_{g+1} not in S)): a run of labels of S ends at g.
+ *     Sums of entries of xi, formed without storing pair; a set's values do not depend on the other sets or their order.
+ *     The sum of enter over a contig is the expected number of runs of S on it, and equals the sum of leave.
+ *   * transitions [n_contigs][L][L]: N(i, j) = sum over the contig's edges of xi(i, j); zeros for a contig of 0 or 1 genes.
+ *   * entropy [n_contigs]: H(Y | x) of the contig's path distribution in nats, by the chain rule -- the entropy of the first
+ *     gene's marginals plus, per edge, the entropy of every conditional row P(y_t = . | y_{t-1} = i) weighted by the marginal
+ *     of i -- a sum of non-negative terms: never negative, never NaN, and small on a confident contig without cancellation.
+ *     0 for a contig without genes.
+ *   * marg [n_genes][L] and lognorm [n_contigs], optional, are the bytes gecco_crf_marginals_full (or its _valued /
+ *     _constrained sibling, by the arguments given) writes for the batch.  (A 2-label model without values and masks has
+ *     kernels of its own for that: asking for either there costs a second pass.)
+ *   * Determinism: no floating-point atomics; a contig's sums are added in gene order in runs of 32 genes counted from the
+ *     contig's first gene; equal calls give equal bytes.  contig_ptr[0] > 0 works as in the other one-shots.
+ *   * Limits: 1 <= n_sets <= 32 (n_sets = 0 with enter = leave = NULL: no set is asked) and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL: n_sets outside that range, an empty mask, a mask
+ *     with a bit at or above num_labels ("set 3: ..."), enter or leave without a set.  The checks of the *_valued and
+ *     *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_edge_posteriors(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                              const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                              const uint32_t *allowed /* NULL: no masks */, const uint32_t *set_mask /* [n_sets] */, int32_t n_sets,
+                              double *pair /* [n_genes][L][L] or NULL */, double *enter /* [n_genes][n_sets] or NULL */,
+                              double *leave /* [n_genes][n_sets] or NULL */, double *transitions /* [n_contigs][L][L] or NULL */,
+                              double *entropy /* [n_contigs] or NULL */, double *marg /* [n_genes][L] or NULL */,
+                              double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
