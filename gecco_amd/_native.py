@@ -99,6 +99,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, _c_i8p, _c_f64p,
          _c_i32p, _c_f64p],
     ),
+    "gecco_crf_viterbi_min_run": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_i8p,
+         _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_edge_posteriors": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_u32p, ctypes.c_int32, _c_f64p,
@@ -726,6 +731,31 @@ class Model:
         _check(self._lib.gecco_crf_viterbi_kbest(
             *head, values, allowed, k, _ptr(y, _c_i8p), _ptr(score, _c_f64p), _ptr(n_paths, _c_i32p), _ptr(ln, _c_f64p)))
         return y[:n - n0], score[:nc], n_paths[:nc], ln[:nc]
+
+    def viterbi_min_run(self, contig_ptr, gene_ptr, attr_id, set_mask, min_run, device=0, values=None, allowed=None,
+                        want_lognorm=True):
+        """The best label path of every contig among those whose every maximal run of labels of a set has at least ``min_run``
+        genes (``gecco_crf_viterbi_min_run``), 1 <= min_run <= 32; ``set_mask`` has bit y set when label y is in the set.
+        Returns ``(y, score, lognorm_min_run, lognorm)``: ``y`` int8 ``[n]`` (-1 at every gene of a contig without a feasible
+        path); ``score`` float64 ``[n_contigs]``, the path's left-to-right score (``-inf`` likewise); ``lognorm_min_run``
+        ``[n_contigs]``, the log-mass of all feasible paths (``-inf`` where there is none); ``lognorm`` ``[n_contigs]`` as
+        ``marginals_full`` gives it -- so ``exp(lognorm_min_run - lognorm)`` is the probability that no run is shorter than
+        ``min_run`` and ``exp(score - lognorm)`` the path's.  With ``want_lognorm=False`` the last two are None and the
+        sum-semiring launch does not run; ``y`` and ``score`` are the same bytes either way.  Ties go by the kernel's scan
+        order over expanded states (include/gecco_crf.h), which at ``min_run = 1`` is ``viterbi``'s rule.  ``values`` and
+        ``allowed`` as in ``marginals_full``.  A contig without genes has score 0 and 0 for both log Z."""
+        min_run, set_mask = operator.index(min_run), operator.index(set_mask)
+        if not 0 <= set_mask < 1 << 32:
+            raise ValueError(f"viterbi_min_run: set_mask {set_mask} is outside 0 .. 2**32 - 1")
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        y = np.zeros(max(n - n0, 1), dtype=np.int8)
+        score = np.zeros(max(nc, 1), dtype=np.float64)
+        ln_c = np.zeros(max(nc, 1), dtype=np.float64) if want_lognorm else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_lognorm else None
+        _check(self._lib.gecco_crf_viterbi_min_run(
+            *head, values, allowed, set_mask, min_run, _ptr(y, _c_i8p), _ptr(score, _c_f64p),
+            None if ln_c is None else _ptr(ln_c, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
+        return y[:n - n0], score[:nc], (None if ln_c is None else ln_c[:nc]), (None if ln is None else ln[:nc])
 
     def edge_posteriors(self, contig_ptr, gene_ptr, attr_id, sets=None, want_pair=False, want_transitions=True, want_entropy=True,
                         want_marginals=False, device=0, values=None, allowed=None):

@@ -950,7 +950,7 @@ int marginals_full_of_slice(const gecco_crf_model *m, int32_t device, const int3
     return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
 }
 
-// One call of a lattice query -- region posteriors, sampled paths, the K best paths, edge posteriors.  The batch goes to the device on a plan laid
+// One call of a lattice query -- region posteriors, sampled paths, the K best paths, edge posteriors, minimum-run decoding.  The batch goes to the device on a plan laid
 // out with `lattice`: the marginals at out(0), per_gene1 bytes a gene at out(1), log Z and then per_contig_more bytes a contig at
 // out(2).  `run(b)` is the entry's part: its plan_run_* call and the fetch of its own outputs; of a batch without genes (b.n == 0:
 // nothing is on the device, and log Z = 0 is written by then) it only fills what else the entry returns.  marg / lognorm (either
@@ -1118,6 +1118,50 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
         rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * K, "download paths");
         rc = batch_fetch(rc, score, d_score, nc * K * 8, "download scores");
         return batch_fetch(rc, n_paths, d_n_paths, nc * 4, "download n_paths");
+    });
+    GECCO_GUARD_END
+}
+
+// ---- decoding under a minimum run length (ABI 2.20.0): the best path among those whose every run of labels of a set has at
+// least min_run genes, and the log-mass of all such paths, on a lattice expanded by a run counter behind gl_state; log Z from the
+// whole-contig marginals pass (crf_minrun.hip)
+GECCO_API int gecco_crf_viterbi_min_run(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                        const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                        const uint32_t *allowed, uint32_t set_mask, int32_t min_run, int8_t *y, double *score,
+                                        double *lognorm_min_run, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    if (min_run < 1 || min_run > kMaxMinRun)
+        return fail("viterbi_min_run: min_run = " + std::to_string(min_run) + " is outside 1 .. 32");
+    if ((rc = check_label_set("set_mask", 0, set_mask, m->m.L))) return rc;
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    if (n_contigs > 0 && !score) return fail("null buffer");
+    if ((rc = check_output(contig_ptr, n_contigs, y))) return rc;
+    const size_t nc = size_t(n_contigs);
+    // per gene: the path.  Per contig, behind log Z: the score, log Z_C.  (The marginals are the pass's own output and are not
+    // returned.)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 1, 16, nullptr, lognorm,
+                        [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: every contig's one path is the empty one -- gecco_crf_viterbi's score, log Z_C = log Z = 0)
+            for (size_t c = 0; c < nc; ++c) {
+                score[c] = 0.0;
+                if (lognorm_min_run) lognorm_min_run[c] = 0.0;
+            }
+            return int(GECCO_CRF_OK);
+        }
+        double *d_lognorm = b.out<double>(2), *d_score = d_lognorm + nc, *d_lognorm_mr = d_score + nc;
+        DeviceBlock<char> ws;
+        int rc = ws.alloc(minrun_back_bytes(b.n, m->m.L, min_run), "hipMalloc min-run back-pointers");
+        if (rc) return rc;
+        rc = batch_wait(plan_run_viterbi_min_run(b.plan, b.csr, set_mask, min_run, reinterpret_cast<uint8_t *>(ws.get()), b.out<int8_t>(1),
+                                                 d_score, lognorm_min_run ? d_lognorm_mr : nullptr, b.out<double>(0), d_lognorm, nullptr),
+                        "min-run decoding");
+        rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n), "download path");
+        rc = batch_fetch(rc, score, d_score, nc * 8, "download score");
+        return batch_fetch(rc, lognorm_min_run, d_lognorm_mr, nc * 8, "download lognorm_min_run");
     });
     GECCO_GUARD_END
 }

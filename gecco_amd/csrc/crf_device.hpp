@@ -356,6 +356,18 @@ size_t kbest_fin_bytes(int32_t n_contigs, int32_t k);
 hipError_t launch_gen_kbest(const GenArgs &a, int32_t k, uint16_t *back, uint16_t *fin, int8_t *y, double *score, int32_t *n_paths,
                             hipStream_t stream);
 
+// ---- decoding under a minimum run length (crf_minrun.hip) ----
+constexpr int32_t kMaxMinRun = 32;  // m of one call: a column of LDS is 33 doubles at the most
+// the kernel's own workspace: back-pointers, one byte per (gene, label, run counter)
+size_t minrun_back_bytes(int64_t n_genes, int32_t L, int32_t min_run);
+// y[g] = the label of gene g on the contig's best path among those whose every maximal run of labels in set_mask has at least
+// min_run genes (-1 at every gene of a contig without such a path), score[c] its score (-infinity likewise; 0 for a contig without
+// genes), lognorm_min_run[c] (null: not computed, one launch fewer) the log-mass of all such paths, on the lattice of the gl_state
+// launch that ran before it on the same stream with a.state non-null: reads a.state, a.trans and a.contig_ptr.  The caller has
+// checked that set_mask has a bit, and none at or above L.
+hipError_t launch_gen_min_run(const GenArgs &a, uint32_t set_mask, int32_t min_run, uint8_t *back, int8_t *y, double *score,
+                              double *lognorm_min_run, hipStream_t stream);
+
 // ---- edge posteriors (crf_edges.hip) ----
 constexpr int32_t kMaxEdgeSets = 32;   // label sets of one call
 constexpr int32_t kEdgeRunGenes = 32;  // genes of a run: what one group of lanes walks, counted from its contig's first gene

@@ -164,8 +164,8 @@ struct Plan {
     // as `valued` does: the any-L kernels at every label count, no reference-bits mode, and the masks come with every run call
     // (DeviceCsr::allowed), which is refused when it brings masks to a layout without `masked`, or none to one with it.
     bool masked = false;
-    // Lattice queries (plan_run_span_probabilities, plan_run_sample_paths, plan_run_viterbi_kbest, plan_run_edge_posteriors;
-    // DESIGN.md §4.9g-j).  `lattice` is
+    // Lattice queries (plan_run_span_probabilities, plan_run_sample_paths, plan_run_viterbi_kbest, plan_run_edge_posteriors,
+    // plan_run_viterbi_min_run).  `lattice` is
     // set by the owner before plan_build: the layout takes the any-L kernels at every label count, as `valued` and `masked` do --
     // the queries' kernels read the forward vectors and raw state scores of their workspace, which a 2-label plan does not have
     // otherwise.  Nothing else changes: reference-bits mode is decided as ever.
@@ -230,6 +230,13 @@ int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint
 // chunked, like the spans' and the samples'.  All on `stream`.
 int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d_back, uint16_t *d_fin, int8_t *d_y, double *d_score,
                            int32_t *d_n_paths, double *d_marg, double *d_lognorm, hipStream_t stream);
+// Decoding under a minimum run length, a plan laid out with `lattice`: the whole-contig marginals of the batch exactly as
+// plan_run_marginals_full runs them (d_marg [n_genes][L], d_lognorm [n_contigs] or null; gl_state also keeps the raw state scores),
+// then the run-counter recursion and its backtrack (crf_minrun.hip): d_y [n_genes], d_score [n_contigs], and d_lognorm_min_run
+// [n_contigs] or null (not asked for: the sum-semiring launch does not run).  d_back (minrun_back_bytes) is the kernel's
+// workspace.  A contig is one sequential walk: not chunked.  All on `stream`.
+int plan_run_viterbi_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t min_run, uint8_t *d_back, int8_t *d_y,
+                             double *d_score, double *d_lognorm_min_run, double *d_marg, double *d_lognorm, hipStream_t stream);
 // Edge posteriors of a plan laid out with `lattice`: the whole-contig marginals of the batch exactly as plan_run_marginals_full
 // runs them (d_marg [n_genes][L], d_lognorm [n_contigs] or null), then the edge marginals and their sums that `q` asks for
 // (crf_edges.hip; crf_device.hpp: EdgeQuery -- device pointers throughout, the run table that of this layout's contigs), all on

@@ -432,6 +432,48 @@ class SequenceCRF:
                         "scores": score[s, :m].copy(), "log_probabilities": score[s, :m] - lognorm[s]})
         return out
 
+    @staticmethod
+    def _min_run(min_run) -> int:
+        try:
+            min_run = operator.index(min_run)
+        except TypeError:
+            raise ValueError(f"min_run is an integer, got {min_run!r}") from None
+        if not 1 <= min_run <= 32:
+            raise ValueError(f"min_run = {min_run} is outside 1 .. 32")
+        return min_run
+
+    def predict_min_run(self, X, labels, min_run, allowed=None) -> List[Dict[str, object]]:
+        """The best label path of every sequence AMONG THOSE in which every maximal run of consecutive items carrying a label of
+        ``labels`` (a label, or a ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels; the labels inside a run may differ)
+        has at least ``min_run`` items, runs at either end of the sequence included -- on the whole-sequence lattice, that of
+        ``predict`` and ``predict_marginals``.  This is not ``predict``'s path with its short runs deleted: the model may prefer
+        to stretch a run or to merge two.  Per sequence a dict with ``labels``: the path as a list of label names, or None when
+        no path satisfies the constraint (every label in the set and fewer than ``min_run`` items, or ``allowed`` forbids it);
+        ``score``: its score (``-inf`` without a path); ``log_probability``: ``score - log Z``, the exact ``log p(y | x)`` of
+        the path; ``constraint_log_probability``: ``log Z_C - log Z``, the log of the probability that a path drawn from the
+        model satisfies the constraint -- ``<= 0`` up to rounding, reported as computed -- so that ``log_probability -
+        constraint_log_probability`` is the path's log-probability given the constraint.  With ``min_run = 1`` the path is
+        ``predict``'s.  Ties go by the kernel's scan order over run-counter states (include/gecco_crf.h).  One forward-backward
+        pass and two walks over ``X``, one native call.  With ``allowed`` (as in ``predict``) everything is on the restricted
+        lattice.  A sequence without items has the empty path: ``labels`` ``[]`` and zeros.  Raises ``ValueError`` before any
+        device call for an unknown label, an empty set, and a ``min_run`` that is not an integer or lies outside 1 .. 32."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = self._label_bits("predict_min_run", labels)
+        min_run = self._min_run(min_run)
+        n_seqs = len(seq_ptr) - 1
+        if seq_ptr[-1] == 0:
+            return [{"labels": [], "score": 0.0, "log_probability": 0.0, "constraint_log_probability": 0.0} for _ in range(n_seqs)]
+        y, score, lognorm_c, lognorm = self._model.viterbi_min_run(seq_ptr, item_ptr, attr, bits, min_run, device=self.device,
+                                                                   values=values, allowed=masks)
+        out = []
+        for s, ys in enumerate(self._split(y, seq_ptr)):
+            found = score[s] > -np.inf
+            out.append({"labels": [self.classes_[c] for c in ys.tolist()] if found else None, "score": float(score[s]),
+                        "log_probability": float(score[s] - lognorm[s]),
+                        "constraint_log_probability": float(lognorm_c[s] - lognorm[s])})
+        return out
+
     # ---- edge posteriors: the pairwise marginals of the whole-sequence lattice and their sums (``_native.Model.edge_posteriors``)
     def _edges(self, X, allowed, sets=None, **want):
         """One pass over ``X`` for the edge outputs ``want`` names: ``(seq_ptr, masks of sets, the native call's dict)``, the dict

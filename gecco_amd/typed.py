@@ -77,6 +77,19 @@ None without a run); ``log_p``.  Rank 0 is the Viterbi path's reading.  The comm
 ``cluster_id, rank, start, end, type, log_p, p``; start, end and type empty without a run); ``clusters.tsv`` is unchanged, and
 without the option the tables and every launch are unchanged.
 
+Path clusters (``predict_path_clusters(genes, min_run=M)``, ``predict --path-clusters M``, 1 <= M <= 32).  The refiner drops a
+cluster of fewer than ``n_cds`` annotated genes after the fact; a decoded path with its short runs deleted is not the best path
+among those without short runs -- the model may prefer to stretch a run of two genes to three, or to merge two runs across a gap
+of one.  One whole-contig call (``_native.Model.viterbi_min_run``: a Viterbi recursion on the lattice expanded by a run counter)
+gives every contig its best label path among those in which every run of genes with a label other than the background has at
+least M GENES (genes, not annotated genes: ``n_cds`` counts annotated ones), and the clusters are that path's runs: ids
+``{sequence}_cluster_{number}``, ``type`` from the run's most frequent label as the alternatives derive it.
+``path_posteriors_`` then holds one row per contig: ``sequence_id``, ``genes``, ``log_z``, ``score`` and ``log_p`` (the path's
+score and exact log-probability; ``-inf`` where no path satisfies the constraint, a contig shorter than M whose every label is
+a cluster label under ``known=``), ``constraint_log_p`` = log P(no run shorter than M | x), and ``clusters``.  The command line
+writes ``path_clusters.tsv`` (columns ``sequence_id, cluster_id, start, end, genes, type``) and ``paths.tsv`` next to the other
+tables, which stay byte for byte what they are without the flag.
+
 Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
 ``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
 """
@@ -99,7 +112,7 @@ from . import tables
 
 __all__ = ["BACKGROUND", "MIXED", "UNKNOWN", "MAX_CLUSTER_LABELS", "TypedClusterCRF", "cluster_labels", "fold_labels",
            "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "write_alternatives",
-           "write_sequences", "build_parser", "main"]
+           "write_sequences", "write_path_clusters", "write_paths", "build_parser", "main"]
 
 BACKGROUND = "0"
 MIXED = "Mixed"
@@ -613,6 +626,69 @@ class TypedClusterCRF:
                 found.append(entry)
             cluster.alternatives = found
 
+    PATH_COLUMNS = ("sequence_id", "genes", "log_z", "score", "log_p", "constraint_log_p", "clusters")
+
+    def predict_path_clusters(self, genes: Iterable[Any], *, min_run: int = 3,
+                              known: Optional[tables.ClusterTable] = None) -> List[Any]:
+        """Clusters as the runs of the best whole-contig label path AMONG THOSE in which every maximal run of genes with a label
+        other than the background has at least ``min_run`` genes (module docstring): one ``viterbi_min_run`` call over all
+        contigs with the set of every label but the background.  ``min_run`` counts genes, not annotated genes (the refiner's
+        ``n_cds`` counts annotated ones), 1 <= ``min_run`` <= 32.  Every cluster has the id ``{sequence}_cluster_{number}``
+        (numbered from 1 along its contig), its genes (the caller's, sorted by (sequence, start); no probability is computed),
+        ``type`` from the run's most frequent label (the smaller label id on ties) and ``path_type``, its ``";"``-joined names
+        (``"Unknown"`` for a label without types).  Fills ``path_posteriors_``, the
+        per-contig columns ``PATH_COLUMNS``.  ``known`` restricts the lattice as in the other prediction methods.
+        ``ValueError`` before any device call for a ``min_run`` that is not an integer or lies outside its range."""
+        try:
+            min_run = operator.index(min_run)
+        except TypeError:
+            raise ValueError(f"min_run is an integer, got {min_run!r}") from None
+        if not 1 <= min_run <= 32:
+            raise ValueError(f"min_run = {min_run} is outside 1 .. 32")
+        from . import packing
+        from .refine import _cluster_class
+        from .types import _cluster_type_factory
+
+        model = self._fitted()
+        genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
+        for gene in genes:
+            gene.protein.domains.sort(key=operator.attrgetter("start"))
+        contigs = [list(g) for _, g in itertools.groupby(genes, key=operator.attrgetter("source.id"))]
+        self.path_posteriors_ = {name: [] for name in self.PATH_COLUMNS}
+        if not genes:
+            return []
+        batch = packing.pack_contigs(contigs, self._attr_index, "protein")
+        allowed = None
+        if known is not None:
+            from .train_cli import join_clusters
+
+            allowed = known_masks(len(genes), known, join_clusters(genes, known, device=self.device), self.classes_, self.background)
+        L = len(self.classes_)
+        bg = self.classes_.index(self.background)
+        item_ptr = batch.item_ptr.astype(np.int32)
+        y, score, lognorm_c, lognorm = model.viterbi_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
+                                                             ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device, allowed=allowed)
+        Cluster = _cluster_class()
+        clusters: List[Any] = []
+        for ci, contig in enumerate(contigs):
+            c0, c1 = int(item_ptr[ci]), int(item_ptr[ci + 1])
+            path = y[c0:c1].astype(np.int64)
+            found = 0
+            if score[ci] > -np.inf:
+                inside = np.concatenate([[False], path != bg, [False]])
+                edges = np.flatnonzero(inside[1:] != inside[:-1])
+                for a, b in zip(edges[::2].tolist(), edges[1::2].tolist()):
+                    found += 1
+                    cluster = Cluster(f"{contig[0].source.id}_cluster_{found}", list(contig[a:b]))
+                    major = int(np.argmax(np.bincount(path[a:b], minlength=L)))
+                    cluster.type = _cluster_type_factory(cluster)(self.label_types_[major])
+                    cluster.path_type = ";".join(self.label_types_[major]) or UNKNOWN  # (as the alternatives name a run's type)
+                    clusters.append(cluster)
+            for name, value in zip(self.PATH_COLUMNS, (contig[0].source.id, c1 - c0, float(lognorm[ci]), float(score[ci]),
+                                                       float(score[ci] - lognorm[ci]), float(lognorm_c[ci] - lognorm[ci]), found)):
+                self.path_posteriors_[name].append(value)
+        return clusters
+
     def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                                    trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                                    region_posteriors: bool = False, boundary_samples: int = 0,
@@ -695,6 +771,29 @@ def write_alternatives(path, clusters: Sequence[Any]) -> None:
                 out.write("\t".join((str(cluster.id), str(alt["rank"]), *where, repr(alt["log_p"]), repr(math.exp(alt["log_p"])))) + "\n")
 
 
+def write_path_clusters(path, clusters: Sequence[Any]) -> None:
+    """``path_clusters.tsv``: one row per cluster of ``predict_path_clusters``, columns ``sequence_id, cluster_id, start, end,
+    genes, type`` (type: the ``";"``-joined names, ``"Unknown"`` for a label without types)."""
+    with open(path, "w") as out:
+        out.write("\t".join(("sequence_id", "cluster_id", "start", "end", "genes", "type")) + "\n")
+        for cluster in clusters:
+            members = cluster.genes
+            names = getattr(cluster, "path_type", None) or ";".join(sorted(getattr(cluster.type, "names", ()))) or UNKNOWN
+            out.write("\t".join((str(members[0].source.id), str(cluster.id), str(min(g.start for g in members)),
+                                 str(max(g.end for g in members)), str(len(members)), names)) + "\n")
+
+
+def write_paths(path, columns) -> None:
+    """``paths.tsv``: one row per contig, columns ``TypedClusterCRF.PATH_COLUMNS`` (``path_posteriors_``, or a list of row
+    dicts); floats with ``repr``."""
+    names = TypedClusterCRF.PATH_COLUMNS
+    rows = zip(*(columns[name] for name in names)) if isinstance(columns, dict) else ([row[name] for name in names] for row in columns)
+    with open(path, "w") as out:
+        out.write("\t".join(names) + "\n")
+        for row in rows:
+            out.write("\t".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
+
+
 def write_sequences(path, columns: Dict[str, Sequence[Any]]) -> None:
     """``sequences.tsv``: one row per contig, columns ``TypedClusterCRF.SEQUENCE_COLUMNS`` (``sequence_posteriors_``); floats
     with ``repr``."""
@@ -758,6 +857,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="add start_p and end_p to clusters.tsv: the whole-contig posterior probability that a run of cluster labels "
                     "starts at a called region's first gene, and ends at its last; write sequences.tsv: per contig its log Z, "
                     "path entropy and expected number of clusters")
+    pr.add_argument("--path-clusters", type=int, default=None, metavar="M",
+                    help="write path_clusters.tsv and paths.tsv: the regions of the best whole-contig label path among those in "
+                    "which every region has at least M (at most 32) genes, and per contig that path's probability and the "
+                    "probability that no region is shorter")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -779,6 +882,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         crf.save(args.output_dir)
         print(f"train: {len(genes)} genes, {len(clusters)} clusters, labels {crf.classes_} -> {args.output_dir}", file=sys.stderr)
         return 0
+    if args.path_clusters is not None and not 1 <= args.path_clusters <= 32:
+        raise ValueError(f"--path-clusters {args.path_clusters} is outside 1 .. 32")
     crf = TypedClusterCRF.trained(args.model, device=args.device)
     genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
     annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
@@ -797,6 +902,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         write_alternatives(os.path.join(args.output_dir, "alternatives.tsv"), found)
     if args.boundary_posteriors:
         write_sequences(os.path.join(args.output_dir, "sequences.tsv"), crf.sequence_posteriors_)
+    if args.path_clusters is not None:
+        known = None if args.known is None else tables.ClusterTable.load(args.known)
+        write_path_clusters(os.path.join(args.output_dir, "path_clusters.tsv"),
+                            crf.predict_path_clusters(genes, min_run=args.path_clusters, known=known))
+        write_paths(os.path.join(args.output_dir, "paths.tsv"), crf.path_posteriors_)
     print(f"predict: {len(annotated)} genes, {len(found)} clusters -> {args.output_dir}", file=sys.stderr)
     return 0
 

@@ -51,7 +51,7 @@ const char *gecco_crf_last_error(void);
 /* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
- * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors. */
+ * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -867,6 +867,52 @@ int gecco_crf_edge_posteriors(const gecco_crf_model *m, int32_t device, const in
                               double *leave /* [n_genes][n_sets] or NULL */, double *transitions /* [n_contigs][L][L] or NULL */,
                               double *entropy /* [n_contigs] or NULL */, double *marg /* [n_genes][L] or NULL */,
                               double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- decoding under a minimum run length (ABI 2.20.0, additive; gecco_crf_version() stays 340) ----------------------------------
+ * y[g] = the label of gene g on the best label path of its contig AMONG THE FEASIBLE ONES, score[c] that path's score, and
+ * lognorm_min_run[c] = log Z_C, the log-mass of all feasible paths, on the whole-contig lattice of gecco_crf_viterbi and
+ * gecco_crf_marginals_full (not a windowed one).  set_mask names a label set S (bit y set: label y is inside; S may be every
+ * label).  A path is feasible when every maximal run of consecutive genes whose labels lie in S has at least min_run genes; runs
+ * that touch the contig's first or last gene count like any other, and the labels inside a run may differ from gene to gene.
+ * That is not the free Viterbi path with its short runs deleted: the model may prefer to stretch a run, or to merge two across a
+ * gap.  exp(lognorm_min_run - lognorm) = P(no run shorter than min_run | x); exp(score - lognorm) is the path's probability,
+ * exp(score - lognorm_min_run) its probability given the constraint.  With `allowed` (one mask per gene, as the *_constrained
+ * entries take them) a path with a disallowed label does not exist, and lognorm is the restricted log Z.  attr_value and allowed
+ * may each be NULL.  The walk is parallel over contigs and labels and sequential along a contig (contigs are not chunked).
+ *   * The recursion runs on the lattice expanded by a run counter.  A label outside S has one state; a label j in S has the
+ *     states (j, d), d = 1 .. min_run, d = min(run length so far, min_run); states are ordered by label, then by d.  At gene 0
+ *     the states with d <= 1 (the outside states among them) start at state_0[j], the others at -infinity.  The sources of a
+ *     destination at gene t: j outside S -- every label i, its one state if i is outside S, (i, min_run) alone if inside (a run
+ *     may end only once it is long enough); (j, 1) -- the labels i outside S; (j, d) with 1 < d < min_run -- (i, d - 1), i in S;
+ *     (j, min_run) -- (i, min_run - 1) and (i, min_run), i in S.  With min_run = 1 the expanded lattice is the plain one.  At
+ *     the contig's end the outside states and the states (j, min_run) are admissible.
+ *   * Max semiring: value = (delta[source] + trans[i][j]) + state_t[j] -- the operation order of gecco_crf_viterbi, so the score
+ *     is the left-to-right sum of the path's terms, every addition rounded on its own.
+ *   * The tie rule is operational.  A destination scans its sources in ascending (source label, source d) order with a strict
+ *     `>` update; at the end the first arg max over the admissible states, in state order, wins.  This is a rule on expanded
+ *     states and NOT "reversed path ascending" (no local rule can give that here: two expanded states stand for one label).
+ *     With min_run = 1 it is gecco_crf_viterbi's rule: the same labels, and the score bits of gecco_crf_viterbi_kbest's rank 0.
+ *   * Sum semiring: the same sources with a max-shifted log-sum-exp in place of the max, fp64 throughout; a destination all of
+ *     whose sources are -infinity stays -infinity.  It runs only when lognorm_min_run is given, and asking for it changes no
+ *     byte of y or score.
+ *   * No feasible path (S every label and fewer than min_run genes, or masks that forbid it): score -infinity, label -1 at
+ *     every gene of the contig, lognorm_min_run -infinity; never NaN.
+ *   * Outputs.  y is int8 [n_genes]; score, lognorm_min_run (optional) and lognorm (optional) are double [n_contigs].  lognorm
+ *     is the bytes gecco_crf_marginals_full (or its _valued / _constrained sibling, by the arguments given) writes for the
+ *     batch.  (A 2-label model without values and masks has kernels of its own for that: asking for lognorm there costs a
+ *     second pass.)  A contig without genes gets gecco_crf_viterbi's score, 0, and 0 for both log Z.  contig_ptr[0] > 0 works
+ *     as in the other one-shots.  The back-pointers are workspace of n_genes * L * min_run bytes; sizes are computed in size_t;
+ *     a failed allocation is GECCO_CRF_ENOMEM.  Equal calls give equal bytes (no atomics).
+ *   * Limits: 1 <= min_run <= 32 and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL: min_run outside 1 .. 32 ("viterbi_min_run: min_run
+ *     = ... is outside 1 .. 32"), a set_mask of 0, a set_mask with a bit at or above num_labels ("set_mask 0: ...").  The checks
+ *     of the *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_viterbi_min_run(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                              const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                              const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
+                              int8_t *y /* [n_genes] */, double *score /* [n_contigs] */,
+                              double *lognorm_min_run /* [n_contigs] or NULL */, double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
