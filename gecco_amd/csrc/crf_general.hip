@@ -83,6 +83,10 @@ __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene
     }
 }
 
+// alpha beta / c as a stored probability.  Where one label holds all the mass the quotient can round to 1 + a few ulp
+// (1 + 3.5e-15 seen with a label that leads by 800): at most 1 is stored.  A comparison, not fmin: a NaN stays a NaN.
+__device__ __forceinline__ double gl_prob(double x) { return x > 1.0 ? 1.0 : x; }
+
 // ---- row F: whole-contig marginals, one group per contig, CRFsuite's own sequential recursion ----
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
@@ -138,7 +142,7 @@ __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
     // backward; alpha/scale of step t were written by this very lane / this group's lane 0
     double *marg = a.marg + static_cast<size_t>(g0) * L;
     double b = c;
-    if (on) marg[static_cast<size_t>(T - 1) * L + j] = v * b / c;
+    if (on) marg[static_cast<size_t>(T - 1) * L + j] = gl_prob(v * b / c);
     double al_p = (T >= 2 && on) ? alpha[static_cast<size_t>(T - 2) * L + j] : 0.0;
     double c_p = T >= 2 ? __shfl(j == 0 ? scale[T - 2] : 0.0, 0, LP) : 1.0;
     double e1 = (T >= 2 && on) ? E[static_cast<size_t>(T - 1) * L + jj] : 0.0;
@@ -156,7 +160,7 @@ __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
         for (int i = 0; i < LP; ++i) acc = fma(mrow[i], vec[i], acc);
         __builtin_amdgcn_wave_barrier();
         b = acc * ct;
-        if (on) marg[static_cast<size_t>(t) * L + j] = al_t * b / ct;
+        if (on) marg[static_cast<size_t>(t) * L + j] = gl_prob(al_t * b / ct);
     }
 }
 
@@ -438,8 +442,8 @@ __global__ void __launch_bounds__(kGT) gl_viterbi_wave(GenArgs a) {
 // quad permute, the per-step sum over the labels (the scale factor's 1 / sum) is a DPP reduction inside the rows of sixteen
 // lanes and four v_readlane across them, emissions / alpha / scale factors are staged eight or sixteen genes ahead.  A
 // partial sum adds its terms in another order than the sequential loop does: results agree with the oracle to 1e-12, like
-// the matrix-core kernels', not bit for bit.  log Z comes from the product of the scale factors, renormalised by frexp every
-// sixteen genes (one log per contig instead of one per gene).
+// the matrix-core kernels', not bit for bit.  log Z comes from the product of the scale factors, renormalised by frexp at every
+// factor (one log per contig instead of one per gene).
 template <int X>
 __device__ __forceinline__ double gl_row_dpp(double v) {  // X = 0: row_half_mirror, 1: row_mirror
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), X == 0 ? 0x141 : 0x140, 0xF, 0xF, true);
@@ -531,7 +535,12 @@ __global__ void __launch_bounds__(kGT) gl_marginals_wave(GenArgs a) {
             const double s = gl_wave_label_sum<H>(on ? v : 0.0);
             c = s != 0.0 ? 1.0 / s : 1.0;
             v *= c;
-            prod *= c;
+            // the product of the scale factors, renormalised at every factor: one factor is as small as (L e^(max trans))^-period,
+            // e^-600 at period 4 next to its guard, and the two of a block of eight genes already left the range when the frexp
+            // was taken once per block (log Z = +-inf).  frexp is exact: the bits of a log Z that was finite are what they were
+            int ex;
+            prod = frexp(prod * c, &ex);
+            ex_sum += ex;
         } else {
             c = 1.0;
         }
@@ -558,9 +567,6 @@ __global__ void __launch_bounds__(kGT) gl_marginals_wave(GenArgs a) {
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if (tb + k < T) fstep(tb + k, ec[k], sc[k]);
-        int ex;  // (the product of the scale factors since the last renormalisation stays far inside the double range)
-        prod = frexp(prod, &ex);
-        ex_sum += ex;
     }
     if (lane == 0 && a.lognorm) a.lognorm[ci] = sm_sum - (log(prod) + double(ex_sum) * 0.6931471805599453);
     // ---- backward ([EXT] crf1dc_beta_score, marginal_point): beta_t[i] = (sum_k M[i][k] E_{t+1}[k] beta_{t+1}[k]) c_t,
@@ -568,7 +574,7 @@ __global__ void __launch_bounds__(kGT) gl_marginals_wave(GenArgs a) {
     // lanes for a missing label): the fence orders them before the loads below.
     __threadfence();
     double b = c;
-    marg[static_cast<size_t>(T - 1) * L] = v * b / c;
+    marg[static_cast<size_t>(T - 1) * L] = gl_prob(v * b / c);
     if (T == 1) return;
     // step t needs alpha_t, c_t, E_{t+1}; blocks of K steps t = hi, hi - 1, ... fetched one block ahead
     double an[K], cn[K], e1n[K];
@@ -611,10 +617,10 @@ __global__ void __launch_bounds__(kGT) gl_marginals_wave(GenArgs a) {
                 const double ct = cc[k];
                 if (__builtin_amdgcn_readfirstlane(__double2hiint(ct)) == 0x3ff00000 && __builtin_amdgcn_readfirstlane(__double2loint(ct)) == 0) {
                     b = acc;  // (a step without rescaling: c_t = 1)
-                    *mp = ac[k] * b;
+                    *mp = gl_prob(ac[k] * b);
                 } else {
                     b = acc * ct;
-                    *mp = ac[k] * b / ct;
+                    *mp = gl_prob(ac[k] * b / ct);
                 }
                 mp -= stride;
             }
@@ -641,6 +647,11 @@ __global__ void __launch_bounds__(kGT) gl_marginals_wave(GenArgs a) {
 // are normalised by their sum inside the chunk (CRFsuite divides by the scale factor, which is the same
 // number up to rounding).
 constexpr int kChunk = 64;
+// The exponent of a row of a chunk's sum-product matrix that is all zeros (a label whose every exp(trans) is 0: nothing
+// follows it; or a row that underflowed): below every exponent a row with mass can have, so that it never sets the alignment
+// maximum of chunk_walk_fwd.  With the exponent the row happened to have (0), rows of exponents under -1074 next to it were
+// shifted out of the double range and the walk lost every path.  Far from INT_MIN: the walks form differences of exponents.
+constexpr int kZeroRowEx = -(1 << 24);
 
 template <int LP, bool MAXPLUS>
 __global__ void __launch_bounds__(kGT) gl_chunk_rows(GenArgs a) {
@@ -663,6 +674,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows(GenArgs a) {
     const double *src = MAXPLUS ? a.state : a.E;
     double v = MAXPLUS ? (j == i ? 0.0 : ninf) : (j == i ? 1.0 : 0.0);
     int ex = 0;
+    double mx = 1.0;  // (sum-product: the row's maximum after the last gene)
     double e = on ? src[static_cast<size_t>(g0) * L + jj] : (MAXPLUS ? ninf : 0.0);
     for (int t = g0; t < g1; ++t) {
         const double e_next = (t + 1 < g1 && on) ? src[static_cast<size_t>(t + 1) * L + jj] : (MAXPLUS ? ninf : 0.0);
@@ -684,7 +696,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows(GenArgs a) {
             v = MAXPLUS ? acc + e : acc * e;
         }
         if (!MAXPLUS) {  // exact power-of-two scaling of the row, exponent kept
-            const double mx = group_max<LP>(on ? v : 0.0);
+            mx = group_max<LP>(on ? v : 0.0);
             if (mx > 0.0) {
                 int e2;
                 (void)frexp(mx, &e2);
@@ -695,7 +707,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows(GenArgs a) {
         e = e_next;
     }
     if (on) a.chM[(static_cast<size_t>(ci) * L + i) * L + j] = v;
-    if (!MAXPLUS && j == 0) a.chEx[static_cast<size_t>(ci) * L + i] = ex;
+    if (!MAXPLUS && j == 0) a.chEx[static_cast<size_t>(ci) * L + i] = mx > 0.0 ? ex : kZeroRowEx;
 }
 
 // The same transfer matrices for 9 to 32 labels on the fp64 matrix cores.  The L rows of a chunk's matrix are L forward
@@ -735,6 +747,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows_mfma(GenArgs a, const int p
             E[t][r] = label_of(t, r) < L ? a.E[static_cast<size_t>(g0) * L + label_of(t, r)] : 0.0;
         }
     int ex = 0;
+    double mx_last = 1.0;  // the column's maximum at its last rescaling, which the last gene always has
     for (int gi = g0; gi < g1; ++gi) {
         // (the next gene's emissions are requested before this gene's products)
 #pragma unroll
@@ -765,6 +778,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows_mfma(GenArgs a, const int p
                 for (int r = 0; r < 4; ++r) mx = fmax(mx, D[t][r]);
             mx = fmax(mx, __shfl_xor(mx, 16));
             mx = fmax(mx, __shfl_xor(mx, 32));
+            mx_last = mx;
             if (mx > 0.0) {
                 int e2;
                 (void)frexp(mx, &e2);
@@ -784,7 +798,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows_mfma(GenArgs a, const int p
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 if (label_of(t, r) < L) a.chM[(static_cast<size_t>(ci) * L + col) * L + label_of(t, r)] = D[t][r];
-        if (g == 0) a.chEx[static_cast<size_t>(ci) * L + col] = ex;
+        if (g == 0) a.chEx[static_cast<size_t>(ci) * L + col] = mx_last > 0.0 ? ex : kZeroRowEx;
     }
 }
 

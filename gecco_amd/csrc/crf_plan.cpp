@@ -46,6 +46,7 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
     for (size_t i = 0; i < L * L; ++i) et[i] = std::exp(m.trans[i]);
     for (double v : m.state) t->wmax_abs = std::max(t->wmax_abs, std::fabs(v));
     for (double v : m.trans) t->tmax_abs = std::max(t->tmax_abs, std::fabs(v));
+    if (!m.trans.empty()) t->tmax = *std::max_element(m.trans.begin(), m.trans.end());
     rc = t->wtab.upload(m.state.data(), A * L, "upload state weights");
     if (!rc) rc = t->exp_trans.upload(et.data(), L * L, "upload transitions");
     if (!rc) rc = t->trans.upload(m.trans.data(), L * L, "upload transitions");
@@ -608,6 +609,23 @@ int32_t choose_wave_split(const Plan &p, const char *env, bool automatic, double
     return wave_tmax;
 }
 
+// The any-L sum-product kernels take the transitions as exp(trans), uploaded as std::exp gives them (get_device_tables).  A
+// scaled step forms s <= L e^max with L <= 32, finite while max < 709.78 - ln 32 = 706.3; with max < -745 every exp(trans) is
+// 0 and the pass would return zeros, with max > 709.78 infinities and NaN, either with a clean status.  700 is the figure
+// the 2-label route keeps its own products inside (`room`, slot_prod_max_cnt).  A finite model outside it is refused, not
+// shifted: no in-range model changes a bit.  Viterbi reads the raw weights and is not refused.  DESIGN.md §4.9f.
+int check_exp_trans_range(const Plan &p) {
+    const double mx = p.tables_model->tmax;
+    if (!(mx > 700.0) && !(mx < -700.0)) return GECCO_CRF_OK;
+    char msg[320];
+    std::snprintf(msg, sizeof(msg),
+                  "the largest transition weight (%g) is outside [-700, 700], the range in which the any-label sum-product kernels "
+                  "can take exp(transition weight): subtracting a constant from every transition weight leaves the model unchanged",
+                  mx);
+    set_error(msg);
+    return GECCO_CRF_EINVAL;
+}
+
 // fork the chunked kernels of a batch's long tail onto the plan's side stream (behind what `stream` holds so far); join_tail
 // makes `stream` wait for them
 int fork_tail(Plan &p, hipStream_t stream) {
@@ -638,6 +656,7 @@ struct GenRecursion {
     hipError_t (*chunked)(const GenArgs &, hipStream_t), (*wave)(const GenArgs &, hipStream_t);
     void (*clear)(GenArgs &);           // the workspace fields the recursion does not use
     const char *what;
+    bool sum_product;                   // the kernels read exp(trans): check_exp_trans_range
 };
 // 17 to 32 labels: the split of the Viterbi recursion for the forward-backward recursion (gl_marginals_wave; a step of it is
 // ~0.5 us; the chunked kernels -- transfer matrices on the matrix cores -- run at 2.6 / 2.2 ns per gene at L = 32 / 24).
@@ -655,6 +674,7 @@ const GenRecursion kGenMarginals = {
     launch_gen_marginals_wave,
     [](GenArgs &g) { g.state = nullptr; },
     "marginals launch",
+    true,
 };
 // 13 to 32 labels: a wave per contig (gl_viterbi_wave) where the batch has its parallelism in its contigs.  The wave
 // kernel takes as long as the longest contig it is given (~0.36 / 0.25 us per gene above / up to 16 labels: a lone wave
@@ -677,6 +697,7 @@ const GenRecursion kGenViterbi = {
     launch_gen_viterbi_wave,
     [](GenArgs &g) { g.E = g.smax = nullptr; },
     "viterbi launch",
+    false,
 };
 
 // The whole-contig recursion `r` of an any-L plan: state scores, then the chunked kernels, a wave per contig, or both side by
@@ -685,6 +706,8 @@ const GenRecursion kGenViterbi = {
 int run_gen_whole(Plan &p, const GenRecursion &r, const DeviceCsr &csr, double *d_marg, double *d_lognorm,
                   int8_t *d_y, double *d_score, hipStream_t stream, GenArgs *used = nullptr) {
     const int L = p.model->L;
+    if (r.sum_product)
+        if (const int bad = check_exp_trans_range(p)) return bad;
     int32_t wave_tmax = -1;  // -1: no wave kernel; 0: every contig; > 0: contigs up to this length
     if (L > 8 && p.n_contigs > 0)
         wave_tmax = choose_wave_split(p, r.forced(), L > r.auto_above, r.t_step(L), r.t_gene(L), r.t_walk(L), r.t_launches(L), p.*r.cache);
@@ -796,8 +819,8 @@ int run_windowed_general(Plan &p, const DeviceCsr &csr, int32_t label, int32_t b
         return GECCO_CRF_EUNSUPPORTED;
     }
     GenArgs g;
-    int rc = fill_gen_args(p, csr, g);
-    if (rc) return rc;
+    int rc = check_exp_trans_range(p);
+    if (rc || (rc = fill_gen_args(p, csr, g))) return rc;
     g.state = nullptr;  // marginals only need exp(state - max)
     if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch"))) return rc;
     GenWinArgs a{};

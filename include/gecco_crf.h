@@ -116,7 +116,10 @@ int gecco_crf_windowed_marginals_all(const gecco_crf_model *m, int32_t device,
                                      int32_t window, int32_t step, int32_t background /* label id, or -1 */, int32_t pad,
                                      double *p_all /* [n_genes][L] */, double *p_any /* [n_genes], NULL iff background == -1 */);
 /* Row F (extension; [EXT] CRF.predict_marginals_single on a whole contig): marginals of
- * every label, marg[n_genes][L]; lognorm[n_contigs] may be NULL. */
+ * every label, marg[n_genes][L]; lognorm[n_contigs] may be NULL.
+ * With 3 to 32 labels the sum-product kernels (this entry, every lattice query behind it, and the windowed entries) take
+ * exp(transition weight): a model whose largest transition weight is outside [-700, 700] is GECCO_CRF_EINVAL.  Subtracting
+ * a constant from every transition weight leaves the model's distribution unchanged.  Viterbi is not refused. */
 int gecco_crf_marginals_full(const gecco_crf_model *m, int32_t device,
                              const int32_t *contig_ptr, int32_t n_contigs,
                              const int32_t *gene_ptr, const int32_t *attr_id,

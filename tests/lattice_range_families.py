@@ -1,0 +1,166 @@
+"""Planted transition families for the whole-contig sum-product pass at its transition-range guards: the models and batches of
+tests/test_lattice_range_host.py (which shows that the log-space yardstick is right on them) and tests/test_gpu_lattice_range.py
+(which holds every whole-contig arrangement to that yardstick on them).  Builders only: no reference arithmetic lives here.
+
+The guards (crf_plan.cpp) read the transition weights alone:
+
+* ``rows_rescale_period = 4 max|trans| < 600 ? 4 : 1`` -- four un-normalised steps of gl_marginals_wave / gl_chunk_rows_mfma;
+* ``raw_fold = 8 (max trans - min trans) < 600`` -- eight un-renormalised 2 x 2 factors per lane of the 2-label scan;
+* ``exp(trans)`` uploaded raw for the any-L kernels, accepted while -700 <= max trans <= 700.
+
+One base model per label count: state weights N(0, 1) and a transition matrix N(0, 1) rounded to multiples of 2^-20.  On that
+grid ``trans + c`` is exact for every shift c used here (c itself is on the grid and |trans + c| < 2^11, 31 significant bits),
+so a shifted model is the base model's distribution EXACTLY, not up to the rounding of 30 000 sums, and max|trans + c| is the
+planted figure to the bit."""
+import functools
+
+import numpy as np
+
+A = 12                       # attributes; the last two are family d's leaders
+LEAD0, LEAD1 = A - 2, A - 1  # the attribute that makes label 0 / label 1 lead by 800
+GRID = 2.0 ** -20
+LABELS = (2, 3, 8, 9, 17, 32)
+LENGTHS = (0, 1, 2, 3, 4, 7, 8, 9, 31, 32, 33, 63, 64, 65, 127, 129, 300)
+LONG_LENGTHS = (2049, 65, 0, 1)  # one contig past kGenLongContig = 2048: chunks of 64 genes
+
+SHIFTS_A = ("under+", "at+", "under-", "at-", "+600", "-600")
+FAR_B = (74.9, 75.1, 149.0, 151.0, 600.0, 2000.0)
+FORBID_C = ("row", "column", "diagonal", "row-150")
+LEADERS_D = (74.9, 75.1)
+SHIFTS_E = (800.0, -800.0)
+FORBIDDEN = -2000.0
+
+
+@functools.lru_cache(maxsize=None)
+def base(L):
+    """(state weights [A, L], transitions [L, L]) of the base model; the two leader attributes weigh nothing here."""
+    rng = np.random.default_rng(7300 + L)
+    w = rng.normal(0.0, 1.0, size=(A, L))
+    w[LEAD0:] = 0.0
+    trans = np.round(rng.normal(0.0, 1.0, size=(L, L)) / GRID) * GRID
+    w.setflags(write=False)
+    trans.setflags(write=False)
+    return w, trans
+
+
+def shift_of(L, which):
+    """Family a / e: the uniform shift c.  "under+" / "at+": max|trans + c| = 150 - 2^-20 / = 150 with c > 0 (the largest
+    entry lands there); "under-" / "at-" with c < 0 (the smallest entry); "+600" / "-600" / a number: that shift."""
+    _, trans = base(L)
+    if which in ("under+", "at+"):
+        return 150.0 - float(trans.max()) - (GRID if which == "under+" else 0.0)
+    if which in ("under-", "at-"):
+        return -150.0 - float(trans.min()) + (GRID if which == "under-" else 0.0)
+    return float(which)
+
+
+def shifted(L, which):
+    """Family a / e: (trans + c, c); the sum is exact (module docstring)."""
+    c = shift_of(L, which)
+    out = base(L)[1] + c
+    assert np.array_equal(out - c, base(L)[1]), "the shift is exact on the grid"
+    return out, c
+
+
+def far_cell(L):
+    """The off-diagonal entry family b moves: (0, 1), or (1, 0) where (0, 1) holds the base matrix's maximum."""
+    _, trans = base(L)
+    return (1, 0) if np.unravel_index(int(np.argmax(trans)), trans.shape) == (0, 1) else (0, 1)
+
+
+def far_entry(L, s):
+    """Family b: one off-diagonal entry at max - s."""
+    out = base(L)[1].copy()
+    out[far_cell(L)] = out.max() - s
+    return out
+
+
+def forbidden(L, what):
+    """Family c: (trans, dead) with -2000 in a whole row (label L - 1 is followed by nothing: legal at a contig's last item
+    only), a whole column (label 0 follows nothing: legal at the first item only) or the whole diagonal (no self-transition).
+    ``dead(T)`` is the boolean [T, L] table of the (item, label) pairs that no path of a T-item contig goes through.
+    "row-150": the row in the matrix shifted to max|trans| just under 150 on the negative side -- the other rows of a chunk's
+    transfer matrix then carry exponents near -7000 next to the zero row's."""
+    out = (shifted(L, "under-")[0] if what.endswith("-150") else base(L)[1]).copy()
+    what = what.split("-")[0]
+    if what == "row":
+        out[L - 1, :] = FORBIDDEN
+
+        def dead(T):
+            d = np.zeros((T, L), dtype=bool)
+            d[:max(T - 1, 0), L - 1] = True
+            return d
+    elif what == "column":
+        out[:, 0] = FORBIDDEN
+
+        def dead(T):
+            d = np.zeros((T, L), dtype=bool)
+            d[1:, 0] = True
+            return d
+    else:
+        out[np.arange(L), np.arange(L)] = FORBIDDEN
+
+        def dead(T):
+            return np.zeros((T, L), dtype=bool)
+    return out, dead
+
+
+def leader_weights(L):
+    """Family d: the base state weights with the two leader attributes switched on: LEAD0 gives label 0, LEAD1 label 1 a lead of
+    at least 800 over every other label whatever else an item carries (the `special` attribute of
+    tests/test_gpu_spans.py::test_a_label_outside_the_set_that_leads_by_800)."""
+    w = base(L)[0].copy()
+    lead = 800.0 + 2.0 * 4 * np.abs(w).max()  # (an item carries at most 4 other attributes)
+    w[LEAD0, 0] = lead
+    w[LEAD1, 1] = lead
+    return w
+
+
+def leader_runs(T):
+    """Family d: the item ranges [b, e) of a T-item contig whose items carry alternately LEAD0 and LEAD1: the whole contig up
+    to 33 items; beyond, 24 items from item 5 (across the 8-item lane folds at 8, 16 and 24) and the last 16 items."""
+    if T <= 33:
+        return [(0, T)]
+    return [(5, 29), (T - 16, T)]
+
+
+@functools.lru_cache(maxsize=None)
+def batch(L, lengths=LENGTHS, leaders=False):
+    """(contig_ptr, gene_ptr, attr_id) over `lengths`: 0 to 4 of the ten plain attributes per item, and with `leaders` family
+    d's alternating leader attribute on the items of leader_runs."""
+    rng = np.random.default_rng(7400 + L)
+    cptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    rows = [list(rng.integers(0, LEAD0, size=int(d))) for d in rng.integers(0, 5, size=int(cptr[-1]))]
+    if leaders:
+        for g0, T in zip(cptr[:-1].tolist(), lengths):
+            for b, e in leader_runs(T):
+                for t in range(b, e):
+                    rows[g0 + t].append(LEAD0 if (t - b) % 2 == 0 else LEAD1)
+    gptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    attr = np.array([a for r in rows for a in r], dtype=np.int32)
+    for x in (cptr, gptr, attr):
+        x.setflags(write=False)
+    return cptr, gptr, attr
+
+
+def model_of(L, family, key):
+    """(state weights, transitions, leaders) of a planted model: family "base", "a" (key in SHIFTS_A), "b" (s in FAR_B), "c"
+    (key in FORBID_C), "d" (s in LEADERS_D: the leaders and family b's entry at max - s) or "e" (a shift in SHIFTS_E)."""
+    w, trans = base(L)
+    if family == "base":
+        return w, trans, False
+    if family in ("a", "e"):
+        return w, shifted(L, key)[0], False
+    if family == "b":
+        return w, far_entry(L, key), False
+    if family == "c":
+        return w, forbidden(L, key)[0], False
+    assert family == "d"
+    return leader_weights(L), far_entry(L, key), True
+
+
+def figures(trans):
+    """What the guards read: (max|trans|, max trans - min trans, max trans), and the sides they land on."""
+    amax, spread, tmax = float(np.abs(trans).max()), float(trans.max() - trans.min()), float(trans.max())
+    return dict(amax=amax, spread=spread, tmax=tmax, period=4 if 4.0 * amax < 600.0 else 1, raw_fold=1 if spread * 8.0 < 600.0 else 0,
+                in_range=-700.0 <= tmax <= 700.0)
