@@ -83,10 +83,6 @@ __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene
     }
 }
 
-// alpha beta / c as a stored probability.  Where one label holds all the mass the quotient can round to 1 + a few ulp
-// (1 + 3.5e-15 seen with a label that leads by 800): at most 1 is stored.  A comparison, not fmin: a NaN stays a NaN.
-__device__ __forceinline__ double gl_prob(double x) { return x > 1.0 ? 1.0 : x; }
-
 // ---- row F: whole-contig marginals, one group per contig, CRFsuite's own sequential recursion ----
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {

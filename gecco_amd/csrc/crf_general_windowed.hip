@@ -3,8 +3,12 @@
 //   * one label (label >= 0):  p_out[g] = max over the windows covering gene g of P_w(y_g = label);
 //   * every label (label < 0): p_out[g][l] = the same for all L labels at once, and p_any[g] = max over the same windows of
 //     sum_{l != background} P_w(y_g = l) -- the probability that a gene lies in ANY cluster of a type-aware cluster CRF, which
-//     cannot be formed from the L columns (the maximum of a sum is not a sum of maxima).  Nothing is clipped at 1: with L = 2
-//     and background 0, p_any is column 1 bit for bit.
+//     cannot be formed from the L columns (the maximum of a sum is not a sum of maxima).
+// Every stored value lies in [0, 1]: a marginal, or a sum of marginals, that rounds to 1 + a few ulp (a label that leads by
+// 800 holds all the mass; 1 + 6.7e-15 seen in p_any at 32 labels) is stored as 1, by a comparison where it is stored (gl_prob,
+// crf_lanes.hpp: a NaN stays a NaN), in every tier and both outputs.  Values up to 1 keep their bits.  The sum behind p_any
+// adds the stored, clipped marginals in label order and is clipped in turn, so with L = 2 and background 0 p_any is still
+// column 1 bit for bit.
 // Each tier states its recursion ONCE; `kAll` only chooses what is kept of it (one component of alpha and one running
 // maximum, or all L and the non-background sum).  A change to a recursion is made in that one kernel body and reaches both
 // outputs.  The single-label form runs the full L-label recursions and keeps one component, so L labels cost L passes
@@ -152,12 +156,12 @@ __global__ void __launch_bounds__(kGT) gl_windowed(GenWinArgs a) {
         const int gi = off + t;
         if constexpr (!kAll) {
             if (lane_on && j == a.label && gi >= 0 && gi < n) {
-                const double pr = al[t * LP + j] * b / ct;
+                const double pr = gl_prob(al[t * LP + j] * b / ct);
                 atomicMax(out + g0 + gi, static_cast<unsigned long long>(__double_as_longlong(pr)));
             }
         } else {
             const bool gene_on = active && gi >= 0 && gi < n;
-            const double pr = lane_on ? al[t * LP + j] * b / ct : 0.0;
+            const double pr = lane_on ? gl_prob(al[t * LP + j] * b / ct) : 0.0;
             if (lane_on && gene_on)
                 atomicMax(out + static_cast<size_t>(g0 + gi) * L + j, static_cast<unsigned long long>(__double_as_longlong(pr)));
             if (out_any) {
@@ -167,7 +171,7 @@ __global__ void __launch_bounds__(kGT) gl_windowed(GenWinArgs a) {
                     double s = 0.0;  // (+0.0 + x = x for the non-negative x here: a single term keeps its bits)
                     for (int i = 0; i < L; ++i)
                         if (i != bg) s += vec[i];
-                    atomicMax(out_any + g0 + gi, static_cast<unsigned long long>(__double_as_longlong(s)));
+                    atomicMax(out_any + g0 + gi, static_cast<unsigned long long>(__double_as_longlong(gl_prob(s))));
                 }
                 __builtin_amdgcn_wave_barrier();
             }
@@ -186,8 +190,8 @@ __global__ void __launch_bounds__(kGT) gl_windowed(GenWinArgs a) {
 //     Sums: alpha_k[j] over the source label i in index order, beta_{k-1}[i] over the target label j in index order, Z over
 //     the labels in index order, the non-background sum over the labels in index order.
 //   * kAll = false: labels are permuted so that the queried one is component 0, and only alpha_k[0] is kept (W doubles); one
-//     running maximum, clipped at 1 when stored.  kAll = true: labels in their own order, the alpha of EVERY label kept
-//     (L x W doubles), L + 1 running maxima (the L columns and the non-background sum), nothing clipped.
+//     running maximum.  kAll = true: labels in their own order, the alpha of EVERY label kept (L x W doubles), L + 1 running
+//     maxima (the L columns and the non-background sum).  Every maximum is clipped at 1 when it is stored (gl_prob).
 //   * the maxima over the windows that cover a gene are DPP diagonals as in the two-label kernel (the running best moves one
 //     lane up per step, the hand-over between waves goes through LDS): no atomics, every output stored once by the
 //     workgroup that owns its slot.
@@ -305,10 +309,10 @@ __global__ void __launch_bounds__(kTileNT) gl_windowed_small(GenWinArgs a, Small
     if (tid >= W - 1 && my_gene >= 0) {
         if constexpr (kAll) {
 #pragma unroll
-            for (int j = 0; j < L; ++j) a.p_out[size_t(my_gene) * L + j] = R[j];
-            if (a.p_any) a.p_any[my_gene] = R[L];
+            for (int j = 0; j < L; ++j) a.p_out[size_t(my_gene) * L + j] = gl_prob(R[j]);
+            if (a.p_any) a.p_any[my_gene] = gl_prob(R[L]);
         } else {
-            a.p_out[my_gene] = fmin(R[0], 1.0);
+            a.p_out[my_gene] = gl_prob(R[0]);
         }
     }
 }
@@ -451,7 +455,7 @@ __global__ void __launch_bounds__(kTileNT) gl_windowed_mfma(GenWinArgs a, double
     __syncthreads();
     const int my_gene = int(ginfo[tid] & 0x7fffffffu) - 1;
     // genes no window covers (step > 1) keep 0.0 like numpy.zeros (crf/__init__.py:251)
-    if (tid >= W - 1 && my_gene >= 0) a.p_out[my_gene] = fmin(__longlong_as_double(static_cast<long long>(best[tid])), 1.0);
+    if (tid >= W - 1 && my_gene >= 0) a.p_out[my_gene] = gl_prob(__longlong_as_double(static_cast<long long>(best[tid])));
 }
 
 // NaN ("no prediction") in the `cols` columns of p and in p_any (may be null) for the gene ranges of skipped contigs

@@ -1,6 +1,6 @@
 // Lane-level moves and reductions of the any-L kernels (crf_general.hip, crf_general_windowed.hip): a reduction over a
 // group of LP consecutive lanes (LP a power of two, a group never straddles a wave) and the one-lane shift of the DPP
-// diagonals, and the accumulator type of the fp64 matrix-core kernels.  gfx950 only.
+// diagonals, the clip of a stored probability, and the accumulator type of the fp64 matrix-core kernels.  gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +29,11 @@ __device__ __forceinline__ double wave_shr1_zero(double v) {  // lane l <- lane 
     hi = __builtin_amdgcn_update_dpp(0, hi, 0x138, 0xF, 0xF, true);
     return __hiloint2double(hi, lo);
 }
+
+// alpha beta / c (or alpha beta / Z, or a sum of such) as a stored probability.  Where one label holds all the mass the
+// quotient can round to 1 + a few ulp (1 + 3.5e-15 seen on a whole contig, 1 + 6.7e-15 in a window, with a label that leads by
+// 800): at most 1 is stored.  A comparison, not fmin: a NaN stays a NaN.
+__device__ __forceinline__ double gl_prob(double x) { return x > 1.0 ? 1.0 : x; }
 
 typedef double gl_v4d __attribute__((ext_vector_type(4)));  // the four result registers of v_mfma_f64_16x16x4_f64
 

@@ -100,7 +100,8 @@ int gecco_crf_windowed_marginals(const gecco_crf_model *m, int32_t device,
 /* Row W for EVERY label in one pass (ABI 2.11, additive; crf_general_windowed.hip): the windows, padding, centring and
  * `step` of gecco_crf_windowed_marginals, one forward-backward per window.
  *   p_all[g][l] = max over the windows covering gene g of P_w(y_g = l)            (row-major [n_genes][L])
- *   p_any[g]    = max over the same windows of sum_{l != background} P_w(y_g = l)  (label-index order, not clipped)
+ *   p_any[g]    = max over the same windows of sum_{l != background} P_w(y_g = l)  (label-index order)
+ * Every value of both outputs lies in [0, 1], exactly 1 at the most.
  * p_any is what a caller whose label 'background' means "in no cluster" thresholds: the maximum of a sum is not a sum of
  * maxima, so it cannot be formed from the columns.  With 2 labels and background 0 it is column 1 bit for bit.
  * background == -1: no p_any, which must then be NULL; a buffer without a background label, a missing buffer with one,

@@ -11,7 +11,11 @@ The guards (crf_plan.cpp) read the transition weights alone:
 One base model per label count: state weights N(0, 1) and a transition matrix N(0, 1) rounded to multiples of 2^-20.  On that
 grid ``trans + c`` is exact for every shift c used here (c itself is on the grid and |trans + c| < 2^11, 31 significant bits),
 so a shifted model is the base model's distribution EXACTLY, not up to the rounding of 30 000 sums, and max|trans + c| is the
-planted figure to the bit."""
+planted figure to the bit.
+
+The second half of the file plants the window kernels' guard (``gen_small_ok``: spread (W - 1) < 600) for
+tests/test_window_range_host.py and tests/test_gpu_window_range.py: the spread of the base matrix set to the last grid value
+inside the guard or the first beyond it, in four shapes, and batches of contigs around a window of W items."""
 import functools
 
 import numpy as np
@@ -125,15 +129,15 @@ def leader_runs(T):
 
 
 @functools.lru_cache(maxsize=None)
-def batch(L, lengths=LENGTHS, leaders=False):
+def batch(L, lengths=LENGTHS, leaders=False, whole=False):
     """(contig_ptr, gene_ptr, attr_id) over `lengths`: 0 to 4 of the ten plain attributes per item, and with `leaders` family
-    d's alternating leader attribute on the items of leader_runs."""
+    d's alternating leader attribute on the items of leader_runs (`whole`: on every item of every contig)."""
     rng = np.random.default_rng(7400 + L)
     cptr = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
     rows = [list(rng.integers(0, LEAD0, size=int(d))) for d in rng.integers(0, 5, size=int(cptr[-1]))]
     if leaders:
         for g0, T in zip(cptr[:-1].tolist(), lengths):
-            for b, e in leader_runs(T):
+            for b, e in ([(0, T)] if whole else leader_runs(T)):
                 for t in range(b, e):
                     rows[g0 + t].append(LEAD0 if (t - b) % 2 == 0 else LEAD1)
     gptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
@@ -164,3 +168,97 @@ def figures(trans):
     amax, spread, tmax = float(np.abs(trans).max()), float(trans.max() - trans.min()), float(trans.max())
     return dict(amax=amax, spread=spread, tmax=tmax, period=4 if 4.0 * amax < 600.0 else 1, raw_fold=1 if spread * 8.0 < 600.0 else 0,
                 in_range=-700.0 <= tmax <= 700.0)
+
+
+# ---------------------------------------------------------------- the window kernels' guard (tests/test_gpu_window_range.py)
+# gen_small_ok (crf_general_windowed.hip): the un-normalised window tiers run W - 1 steps on exp(trans - max trans) while
+# ``(max trans - min trans) * (W - 1) < 600``; everything else takes the scaled lane-group tier.
+WINDOWS = (2, 5, 20, 32)
+SPREAD_SHAPES = ("one", "sticky", "restless", "column")
+
+
+def guard_spread(W):
+    """The largest grid value s with ``s * (W - 1) < 600.0`` in double arithmetic; s + 2^-20 is the first grid value on the
+    other side."""
+    s = np.floor(600.0 / (W - 1) / GRID) * GRID
+    while not s * float(W - 1) < 600.0:
+        s -= GRID
+    while (s + GRID) * float(W - 1) < 600.0:
+        s += GRID
+    assert s * float(W - 1) < 600.0 and not (s + GRID) * float(W - 1) < 600.0
+    return float(s)
+
+
+def spread_model(L, shape, s):
+    """The base matrix clipped from below at max - s, with max - min at exactly s in one of four shapes: "one", one
+    off-diagonal entry at max - s (family b's cell); "sticky", the diagonal at max and every other entry at max - s (every
+    change of label costs s); "restless", the diagonal at max - s; "column", every transition into label 0 at max - s.  The
+    maximum is planted again at (0, 1) where the shape removed it."""
+    trans = base(L)[1]
+    hi = float(trans.max())
+    out = np.maximum(trans, hi - s)
+    diag = np.arange(L)
+    if shape == "one":
+        out[far_cell(L)] = hi - s
+    elif shape == "sticky":
+        out[:] = hi - s
+        out[diag, diag] = hi
+    elif shape == "restless":
+        out[diag, diag] = hi - s
+    else:
+        assert shape == "column"
+        out[:, 0] = hi - s
+    if out.max() != hi:
+        out[0, 1] = hi
+    assert out.max() == hi and out.min() == hi - s and float(out.max() - out.min()) == s, "the spread is s to the bit"
+    return out
+
+
+def window_lengths(W):
+    """Contigs around a window of W items: padded (or, without padding, skipped) ones, one across a wave's 64 lanes, one
+    across a tile of 256 window starts, empty ones at both ends."""
+    return (0, 1, W - 1, W, W + 1, 2 * W + 3, 65, 300, 0)
+
+
+def window_batch(L, W, leaders=False):
+    """(contig_ptr, gene_ptr, attr_id) over window_lengths(W); `leaders`: family d's alternating leader attribute on every item."""
+    return batch(L, window_lengths(W), leaders, whole=leaders)
+
+
+def leader_of(csr):
+    """Per item the label that a leader attribute makes lead (0 or 1), or -1."""
+    cptr, gptr, attr = csr
+    out = np.full(int(cptr[-1]), -1, dtype=np.int64)
+    for g in range(len(out)):
+        mine = attr[gptr[g]:gptr[g + 1]]
+        if (mine == LEAD0).any():
+            out[g] = 0
+        elif (mine == LEAD1).any():
+            out[g] = 1
+    return out
+
+
+def forbid_the_leader(L, csr):
+    """uint32 masks that allow every label but the one that leads on the item."""
+    lead = leader_of(csr)
+    full = np.full(len(lead), (1 << L) - 1, dtype=np.uint64)
+    full[lead >= 0] &= ~(np.uint64(1) << lead[lead >= 0].astype(np.uint64))
+    return full.astype(np.uint32)
+
+
+def small_tier_ok(L, W, trans, all_labels=False):
+    """What the plan's guard computes: the un-normalised tier takes this (label count, window, matrix)."""
+    wmax = 32 if (L <= 4 or (L > 8 and not all_labels)) else 20
+    if all_labels and L > 8:
+        return False
+    return bool(2 <= L <= 32 and 1 <= W <= wmax and float(trans.max() - trans.min()) * float(W - 1) < 600.0)
+
+
+def window_model(L, key):
+    """(state weights, transitions, leaders) of a model of the window tests: ("edge", shape, W, side, leaders) is the spread
+    shape at guard_spread(W) (side 0) or one grid step beyond (side 1), with or without the leaders; (family, key) with a
+    family of model_of is that model."""
+    if key[0] == "edge":
+        _, shape, W, side, leaders = key
+        return (leader_weights(L) if leaders else base(L)[0]), spread_model(L, shape, guard_spread(W) + side * GRID), leaders
+    return model_of(L, key[0], key[1])

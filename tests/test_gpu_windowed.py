@@ -114,37 +114,11 @@ def test_strong_transitions_need_rescale(nat):
         _cmp(got, exp)
 
 
-def _logspace_windowed(w, trans, cptr, gptr, attr, W):
-    """Independent log-domain windowed marginals (numpy logaddexp): immune to the exp()
-    overflow that CRFsuite's (and hence the oracle's) probability-domain recursion hits."""
-    out = np.zeros(cptr[-1])
-    for c in range(len(cptr) - 1):
-        g0, n = cptr[c], cptr[c + 1] - cptr[c]
-        st = np.zeros((n, 2))
-        for g in range(n):
-            for a in attr[gptr[g0 + g]:gptr[g0 + g + 1]]:
-                st[g] += w[a]
-        assert n >= W
-        prob = np.zeros(n)
-        for s in range(n - W + 1):
-            x = st[s:s + W]
-            la = np.zeros((W, 2)); lb = np.zeros((W, 2))
-            la[0] = x[0]
-            for t in range(1, W):
-                la[t] = x[t] + np.logaddexp(la[t - 1][0] + trans[0], la[t - 1][1] + trans[1])
-            for t in range(W - 2, -1, -1):
-                v = x[t + 1] + lb[t + 1]
-                lb[t] = np.logaddexp(trans[:, 0] + v[0], trans[:, 1] + v[1])
-            lz = np.logaddexp(la[-1][0], la[-1][1])
-            prob[s:s + W] = np.maximum(prob[s:s + W], np.exp(la[:, 1] + lb[:, 1] - lz))
-        out[g0:g0 + n] = prob
-    return out
-
-
 def test_extreme_state_scores(nat):
     """Saturated emissions: |s1-s0| of a few hundred must neither overflow nor NaN.  The
     probability-domain oracle is only usable while exp(s) is finite (sigma=40); beyond that
-    (sigma=150) the HIP path is checked against a log-domain restatement."""
+    (sigma=150) the HIP path is checked against the conditioned log-space yardstick (tests/window_range_reference.py: every
+    vector shifted by its own log-sum-exp, within 1e-13 of its long double run at such scores), at the tolerance of ordinary weights."""
     from oracle import crf_oracle as orc
 
     trans = np.array([[2.67, -2.6], [-2.6, 2.57]])
@@ -163,8 +137,13 @@ def test_extreme_state_scores(nat):
     model = nat.Model.from_tables(w, trans)
     got = model.windowed_marginals(cptr, gptr, attr, 20)
     assert np.isfinite(got).all() and (got >= 0).all() and (got <= 1).all()
-    ref = _logspace_windowed(w, trans, cptr, gptr, attr, 20)
-    assert np.abs(got - ref).max() <= 1e-9  # log-domain reference itself carries ~1e-13*|score| error
+    from tests import constrained_reference as cr, window_range_reference as wr
+    from tests.train_objective_partial import full_masks
+
+    score = cr.masked_scores(gptr, attr, None, w, full_masks(int(cptr[-1]), 2))
+    ref = wr.windowed(cptr, score, trans, 20, 1)[0][:, 1]
+    print(f"saturated emissions: worst |p - yardstick| = {np.abs(got - ref).max():.3g}")
+    assert np.abs(got - ref).max() <= 1e-12
 
 
 @pytest.mark.parametrize("W,step", [(33, 1), (50, 1), (64, 7), (100, 1)])
