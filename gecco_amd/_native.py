@@ -89,6 +89,12 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_i32p, _c_u32p,
          ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_run_posteriors": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_u32p,
+         ctypes.c_int32, ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_i32p, _c_i32p, _c_i32p, _c_u32p,
+         ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_sample_paths": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, ctypes.c_uint64,
@@ -670,6 +676,58 @@ class Model:
         if want_marginals:
             return logp[:ns], marg[:n - n0], ln[:nc]
         return logp[:ns]
+
+    def run_posteriors(self, contig_ptr, gene_ptr, attr_id, anchors=None, reach=64, runs=None, device=0, values=None, allowed=None,
+                       want_marginals=False):
+        """Run posteriors on the whole-contig lattice (``gecco_crf_run_posteriors``), any number of queries behind one
+        forward-backward pass of the batch.  ``anchors=(contig, item, mask)``, three arrays of one length: for the run through
+        gene ``item[q]`` of contig ``contig[q]`` -- the maximal stretch of genes around it whose labels all lie in ``mask[q]`` --
+        ``log_anchor [n]`` (log P(the gene's label is in the set)), ``log_start [n, reach + 1]`` (entry r: log P(the run starts
+        at ``item - r``)), ``log_start_beyond [n]`` (the run starts before the reach), and ``log_end`` / ``log_end_beyond``
+        likewise towards the contig's end (entry r: the run's last gene is ``item + r``).  ``runs=(contig, begin, end, mask)``,
+        four arrays of one length: ``log_run [n]``, log P(a run is exactly ``[begin, end)``).  Natural logs, ``<= 0``, ``-inf``
+        for probability zero.  ``values`` and ``allowed`` as in ``marginals_full``.  Returns a dict with the keys named above
+        (those of a list that was not given are left out), and with ``want_marginals`` also ``marginals`` and ``lognorm`` as
+        ``marginals_full`` gives them."""
+        reach = operator.index(reach)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        na = nr = 0
+        if anchors is not None:
+            ac, ai = _i32(anchors[0]).ravel(), _i32(anchors[1]).ravel()
+            am = np.ascontiguousarray(anchors[2], dtype=np.uint32).ravel()
+            na = ac.size
+            if not (ai.size == na and am.size == na):
+                raise ValueError("the anchors' contig, item and mask differ in length")
+        if runs is not None:
+            rc, rb, re_ = _i32(runs[0]).ravel(), _i32(runs[1]).ravel(), _i32(runs[2]).ravel()
+            rm = np.ascontiguousarray(runs[3], dtype=np.uint32).ravel()
+            nr = rc.size
+            if not (rb.size == nr and re_.size == nr and rm.size == nr):
+                raise ValueError("the runs' contig, begin, end and mask differ in length")
+        # (the library refuses any other reach, or more than 2^31 - 1 entries: the buffers only need a size)
+        row = reach + 1 if 0 <= reach <= 65536 and na * (reach + 1) < 1 << 31 else 1
+        small = [np.zeros(max(na, 1), dtype=np.float64) for _ in range(3)]
+        wide = [np.zeros((max(na, 1), row), dtype=np.float64) for _ in range(2)]
+        log_run = np.zeros(max(nr, 1), dtype=np.float64)
+        marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_marginals else None
+        p = lambda x: _ptr(x, _c_f64p)
+        _check(self._lib.gecco_crf_run_posteriors(
+            *head, values, allowed,
+            _ptr(ac, _c_i32p) if na else None, _ptr(ai, _c_i32p) if na else None, _ptr(am, _c_u32p) if na else None, na, reach,
+            p(small[0]), p(wide[0]), p(small[1]), p(wide[1]), p(small[2]),
+            _ptr(rc, _c_i32p) if nr else None, _ptr(rb, _c_i32p) if nr else None, _ptr(re_, _c_i32p) if nr else None,
+            _ptr(rm, _c_u32p) if nr else None, nr, p(log_run),
+            None if marg is None else p(marg), None if ln is None else p(ln)))
+        out = {}
+        if anchors is not None:
+            out.update(log_anchor=small[0][:na], log_start=wide[0][:na], log_start_beyond=small[1][:na], log_end=wide[1][:na],
+                       log_end_beyond=small[2][:na])
+        if runs is not None:
+            out["log_run"] = log_run[:nr]
+        if want_marginals:
+            out.update(marginals=marg[:n - n0], lognorm=ln[:nc])
+        return out
 
     def sample_paths(self, contig_ptr, gene_ptr, attr_id, n_samples, seed=0, device=0, values=None, allowed=None, runs=None,
                      want_marginals=False, want_paths=True):

@@ -1033,6 +1033,97 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
     GECCO_GUARD_END
 }
 
+// ---- run posteriors (ABI 2.21.0): the exact start and end distributions of the run through an anchor, and the probability that
+// a run is exactly a range, any number of queries behind one forward-backward pass of the batch (crf_runs.hip)
+GECCO_API int gecco_crf_run_posteriors(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                       const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                       const uint32_t *allowed, const int32_t *anchor_contig, const int32_t *anchor_item,
+                                       const uint32_t *anchor_mask, int32_t n_anchors, int32_t reach, double *log_anchor,
+                                       double *log_start, double *log_start_beyond, double *log_end, double *log_end_beyond,
+                                       const int32_t *run_contig, const int32_t *run_begin, const int32_t *run_end,
+                                       const uint32_t *run_mask, int32_t n_runs, double *log_run, double *marg, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the queries, on the host and before any device work
+    if (n_anchors < 0 || n_runs < 0) return fail("run_posteriors: negative number of anchors or runs");
+    if (reach < 0 || reach > kMaxRunReach) return fail("run_posteriors: reach = " + std::to_string(reach) + " is outside 0 .. 65536");
+    if (int64_t(n_anchors) * (int64_t(reach) + 1) >= (int64_t(1) << 31))
+        return fail("run_posteriors: n_anchors * (reach + 1) = " + std::to_string(int64_t(n_anchors) * (int64_t(reach) + 1)) +
+                    " does not stay below 2^31");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    if (n_anchors > 0 && (!anchor_contig || !anchor_item || !anchor_mask || !log_anchor || !log_start || !log_start_beyond || !log_end ||
+                          !log_end_beyond))
+        return fail("null buffer");
+    if (n_runs > 0 && (!run_contig || !run_begin || !run_end || !run_mask || !log_run)) return fail("null buffer");
+    std::vector<RunQuery> anchors(static_cast<size_t>(n_anchors));
+    for (int32_t q = 0; q < n_anchors; ++q) {
+        const int32_t c = anchor_contig[q], t = anchor_item[q];
+        int64_t len;
+        if ((rc = check_query_contig("anchor", q, c, n_contigs, contig_ptr, &len))) return rc;
+        if (t < 0 || t >= len)
+            return fail(query_name("anchor", q) + "item " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
+                        std::to_string(len) + " genes");
+        if ((rc = check_label_set("anchor", q, anchor_mask[q], m->m.L))) return rc;
+        anchors[size_t(q)] = RunQuery{c, t, anchor_mask[q]};
+    }
+    std::vector<SpanQuery> runs(static_cast<size_t>(n_runs));
+    for (int32_t q = 0; q < n_runs; ++q) {
+        const int32_t c = run_contig[q], b = run_begin[q], e = run_end[q];
+        int64_t len;
+        if ((rc = check_query_contig("run", q, c, n_contigs, contig_ptr, &len))) return rc;
+        if (b < 0 || b >= e || e > len)
+            return fail(query_name("run", q) + "[" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
+                        std::to_string(c) + " of " + std::to_string(len) + " genes");
+        if ((rc = check_label_set("run", q, run_mask[q], m->m.L))) return rc;
+        runs[size_t(q)] = SpanQuery{c, b, e, run_mask[q]};
+    }
+    // without queries the call is the whole-contig marginals' own
+    if (n_anchors == 0 && n_runs == 0) {
+        if (allowed) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
+        if (attr_value) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
+        return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+    }
+    // (a batch without genes cannot be: a checked query lies inside a contig with genes)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
+        // one block: the anchors, the runs, then the outputs in the order log_anchor, start_beyond, end_beyond, run, start, end
+        const size_t na = size_t(n_anchors), nr = size_t(n_runs), row = size_t(reach) + 1;
+        const size_t b_anchors = align256(na * sizeof(RunQuery)), b_runs = align256(nr * sizeof(SpanQuery));
+        const size_t n_small = 3 * na + nr, n_out = n_small + 2 * na * row;
+        std::vector<char> host(b_anchors + b_runs);
+        if (na) std::memcpy(host.data(), anchors.data(), na * sizeof(RunQuery));
+        if (nr) std::memcpy(host.data() + b_anchors, runs.data(), nr * sizeof(SpanQuery));
+        DeviceBlock<char> q;
+        int rc = upload_queries(q, host.data(), host.size(), host.size() + n_out * 8, "hipMalloc run queries", "upload run queries");
+        if (rc) return rc;
+        double *d_out = reinterpret_cast<double *>(q.get() + host.size());
+        RunPosteriorArgs a{};
+        a.anchors = reinterpret_cast<const RunQuery *>(q.get());
+        a.runs = reinterpret_cast<const SpanQuery *>(q.get() + b_anchors);
+        a.n_anchors = n_anchors;
+        a.n_runs = n_runs;
+        a.reach = reach;
+        a.log_anchor = d_out;
+        a.log_start_beyond = d_out + na;
+        a.log_end_beyond = d_out + 2 * na;
+        a.log_run = d_out + 3 * na;
+        a.log_start = d_out + n_small;
+        a.log_end = a.log_start + na * row;
+        rc = batch_wait(plan_run_run_posteriors(b.plan, b.csr, a, b.out<double>(0), b.out<double>(2), nullptr), "run posteriors");
+        if (na) {
+            rc = batch_fetch(rc, log_anchor, a.log_anchor, na * 8, "download log_anchor");
+            rc = batch_fetch(rc, log_start_beyond, a.log_start_beyond, na * 8, "download log_start_beyond");
+            rc = batch_fetch(rc, log_end_beyond, a.log_end_beyond, na * 8, "download log_end_beyond");
+            rc = batch_fetch(rc, log_start, a.log_start, na * row * 8, "download log_start");
+            rc = batch_fetch(rc, log_end, a.log_end, na * row * 8, "download log_end");
+        }
+        if (nr) rc = batch_fetch(rc, log_run, a.log_run, nr * 8, "download log_run");
+        return rc;
+    });
+    GECCO_GUARD_END
+}
+
 // ---- label paths drawn from the posterior (ABI 2.17.0): forward filtering by the whole-contig marginals pass, backward sampling
 // and the run queries behind it (crf_sample.hip)
 GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,

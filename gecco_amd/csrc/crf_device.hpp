@@ -345,6 +345,24 @@ hipError_t launch_gen_sample_paths(const GenArgs &a, int32_t n_samples, uint64_t
 hipError_t launch_gen_sample_runs(const GenArgs &a, const int8_t *y, const RunQuery *queries, int32_t n_runs, int32_t n_samples,
                                   int32_t *runs, hipStream_t stream);
 
+// ---- run posteriors (crf_runs.hip) ----
+constexpr int32_t kMaxRunReach = 65536;  // reach of one call: genes a walk goes from its anchor, each side
+// What one call asks for.  Anchor query q is anchors[q] (a RunQuery: the run through gene `anchor` of labels in `mask`), closed
+// run q is runs[q] (a SpanQuery: the run is exactly [begin, end)).  The host has checked the ranges, that every mask has a bit
+// and none at or above L, and n_anchors * (reach + 1) < 2^31.  Natural logs, -infinity for probability zero:
+//   log_anchor [n_anchors] = log P(y_a in S);  log_start [n_anchors][reach + 1]: entry r = log P(the run starts at a - r);
+//   log_start_beyond [n_anchors] = log P(y_{a-reach-1} .. y_a in S);  log_end, log_end_beyond: the same towards the contig's end;
+//   log_run [n_runs] = log P(y_begin .. y_{end-1} in S, begin = 0 or y_{begin-1} not in S, end = T or y_end not in S).
+struct RunPosteriorArgs {
+    const RunQuery *anchors;
+    const SpanQuery *runs;
+    int32_t n_anchors, n_runs, reach;
+    double *log_anchor, *log_start, *log_start_beyond, *log_end, *log_end_beyond, *log_run;
+};
+// on the lattice of the whole-contig marginals that ran before it on the same stream with a.state non-null: reads a.state, a.E,
+// a.alpha, a.marg and a.exp_trans, whatever arrangement filled them.  Two launches at the most: the left walks, the right walks.
+hipError_t launch_gen_runs(const GenArgs &a, const RunPosteriorArgs &p, hipStream_t stream);
+
 // ---- the K best label paths (crf_kbest.hip) ----
 constexpr int32_t kMaxKBest = 32;  // K of one call: a rank fits the low byte of a back-pointer, a list row of LDS 33 doubles
 // the kernel's own workspace: back-pointers, uint16 per (gene, label, rank), and the last (label, rank) per (contig, rank)

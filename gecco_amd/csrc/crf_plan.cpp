@@ -1355,6 +1355,24 @@ int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *
     return check_hip(launch_gen_spans(g, d_spans, n_spans, d_logp, stream), "span launch");
 }
 
+int plan_run_run_posteriors(Plan &p, const DeviceCsr &csr, const RunPosteriorArgs &q, double *d_marg, double *d_lognorm,
+                            hipStream_t stream) {
+    if (q.n_anchors < 0 || q.n_runs < 0 || q.reach < 0 || q.reach > kMaxRunReach) {
+        set_error("a negative number of anchors or runs, or reach outside 0 .. 65536");
+        return GECCO_CRF_EINVAL;
+    }
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !d_marg ||
+                      (q.n_anchors > 0 && (!q.anchors || !q.log_anchor || !q.log_start || !q.log_start_beyond || !q.log_end ||
+                                           !q.log_end_beyond)) ||
+                      (q.n_runs > 0 && (!q.runs || !q.log_run)), rc))
+        return rc;
+    GenArgs g;  // (with the raw state scores, which the walks shift by their own maxima)
+    if ((rc = run_lattice(p, csr, "run posteriors", true, d_marg, d_lognorm, stream, g))) return rc;
+    return check_hip(launch_gen_runs(g, q, stream), "run-posterior launch");
+}
+
 int plan_run_sample_paths(Plan &p, const DeviceCsr &csr, int32_t n_samples, uint64_t seed, const RunQuery *d_queries, int32_t n_runs,
                           int8_t *d_y, int32_t *d_runs, double *d_marg, double *d_lognorm, hipStream_t stream) {
     if (n_samples < 1 || n_samples > kMaxSamples || n_runs < 0) {

@@ -396,6 +396,61 @@ class SequenceCRF:
                                         allowed=masks, runs=(contig, anchor, mask), want_paths=False)
 
     @staticmethod
+    def _reach(reach) -> int:
+        try:
+            reach = operator.index(reach)
+        except TypeError:
+            raise ValueError(f"reach is an integer, got {reach!r}") from None
+        if not 0 <= reach <= 65536:
+            raise ValueError(f"reach = {reach} is outside 0 .. 65536")
+        return reach
+
+    def run_posteriors(self, X, anchors, reach=64, allowed=None) -> List[Dict[str, object]]:
+        """Exact start and end distributions of runs.  For every ``(sequence_index, item, labels)`` of ``anchors`` (what
+        ``sample_runs`` takes), "the run through the anchor" is the maximal stretch of items around ``X[sequence_index][item]``
+        whose labels all lie in ``labels``.  Per anchor one dict of natural logs (``<= 0``, ``-inf`` for probability zero):
+        ``log_anchor``, log P(the anchor's label is in the set); ``log_start``, float64 ``[reach + 1]``, entry r the
+        log-probability that the run starts at ``item - r`` (``-inf`` for ``r > item``); ``log_start_beyond``, that it starts
+        before ``item - reach``; ``log_end`` (entry r: the run's last item is ``item + r``) and ``log_end_beyond`` likewise.
+        The starts and the beyond-mass sum to the anchor's probability, as do the ends.  These are the exact values of what
+        ``sample_runs`` estimates by counting; they are not ``boundary_probability``, which counts the start of ANY run at an
+        item.  The start and the end are not independent: the joint is ``run_log_probability``.  Whole-sequence lattice (that
+        of ``predict`` and ``predict_marginals``); with ``allowed`` the restricted one.  One forward-backward pass and one
+        native call.  Raises ``ValueError`` before any device call for what ``sample_runs`` refuses, for ``reach`` outside
+        0 .. 65536 and for ``n_anchors * (reach + 1) >= 2**31``."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        reach = self._reach(reach)
+        contig, anchor, mask = self._anchor_queries(anchors, seq_ptr)
+        if len(contig) * (reach + 1) >= 1 << 31:
+            raise ValueError(f"{len(contig)} anchors at reach {reach}: n_anchors * (reach + 1) does not stay below 2**31")
+        if len(contig) == 0:
+            return []
+        out = self._model.run_posteriors(seq_ptr, item_ptr, attr, anchors=(contig, anchor, mask), reach=reach, device=self.device,
+                                         values=values, allowed=masks)
+        keys = ("log_anchor", "log_start", "log_start_beyond", "log_end", "log_end_beyond")
+        return [{k: (out[k][q] if out[k].ndim == 2 else float(out[k][q])) for k in keys} for q in range(len(contig))]
+
+    def run_log_probability(self, X, runs, allowed=None) -> np.ndarray:
+        """For every ``(sequence_index, start, stop, labels)`` of ``runs`` (as in ``span_log_probability``) the log-probability
+        that a run is EXACTLY ``X[sequence_index][start:stop]``: every item of the range carries a label of ``labels``, the item
+        before it (if any) does not, and the item after it (if any) does not.  It is one entry of the joint distribution of a
+        run's start and end, which is not the product of ``run_posteriors``' two marginals.  One float64 per run, ``<= 0``,
+        ``-inf`` where the probability is zero.  Raises ``ValueError`` before any device call for what ``span_log_probability``
+        refuses."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        contig, begin, end, mask = self._span_queries(runs, seq_ptr)
+        if len(contig) == 0:
+            return np.zeros(0)
+        return self._model.run_posteriors(seq_ptr, item_ptr, attr, runs=(contig, begin, end, mask), device=self.device,
+                                          values=values, allowed=masks)["log_run"]
+
+    def run_probability(self, X, runs, allowed=None) -> np.ndarray:
+        """``exp`` of ``run_log_probability``."""
+        return np.exp(self.run_log_probability(X, runs, allowed=allowed))
+
+    @staticmethod
     def _kbest_count(k) -> int:
         try:
             k = operator.index(k)

@@ -59,6 +59,28 @@ S: the sum over the contig of the start probabilities).  Whole-contig posteriors
 restricts the lattice in the same way.  ``clusters.tsv`` then has the columns ``start_p`` and ``end_p`` behind the other
 optional columns, and the command line writes ``sequences.tsv``; without the flag the tables and every launch are unchanged.
 
+Run posteriors (opt-in: ``run_posteriors=True``, ``predict --run-posteriors [--run-reach R]``, R = 256 by default).  The three
+boundary features answer three different questions.  The SAMPLED intervals above estimate the distribution of the run through a
+cluster's anchor by counting N drawn paths: an alternative of probability 1e-4 is seen rarely or never, and the numbers move with
+the seed.  The per-gene EDGE posteriors above are exact, but ``start_p`` is the probability that SOME run starts at a gene, a
+neighbouring run's start included.  The per-run posteriors here are the exact distribution of where THE RUN THROUGH THE ANCHOR
+starts and ends (``_native.Model.run_posteriors``: one forward-backward pass and one native call per batch, per cluster a masked
+walk of at most R + 2 genes to either side of the anchor).  With S every label but the background and the anchor of the boundary
+intervals (the gene with the greatest any-cluster probability, the first on ties), every called cluster carries
+``run_anchor_probability`` = P(the anchor's label is in S); ``run_probability`` = P(a run of S is EXACTLY the called gene range:
+every gene inside, the neighbours outside) -- one entry of the joint distribution of start and end, which is NOT the product of
+the two marginal distributions; ``run_start_interval`` and ``run_end_interval`` = (lower, upper) from the distribution GIVEN that
+the anchor is in S: positions in ascending coordinate order, the mass beyond the reach placed outside the farthest gene the walk
+reaches, lower = the first position whose cumulative mass is >= 0.05 and upper = the first with >= 0.95, reported as the gene's
+``start`` (starts) or ``end`` (ends) like the sampled columns, a bound that falls into the mass beyond the reach clamped to the
+gene at the reach, and the cluster's own start and end where the anchor's probability is 0; ``run_start_beyond_probability`` and
+``run_end_beyond_probability``, the conditional mass beyond the reach (0 says the interval was not clamped); and
+``run_boundaries``, the conditional distributions themselves as ``(side, gene, position, p)``.  Whole-contig posteriors like the
+others, and ``known=`` restricts the lattice in the same way.  ``clusters.tsv`` then has the columns ``run_anchor_p``, ``run_p``,
+``run_start_lo``, ``run_start_hi``, ``run_end_lo``, ``run_end_hi``, ``run_start_beyond_p`` and ``run_end_beyond_p`` behind every
+other optional column, and the command line writes ``boundaries.tsv`` (columns ``cluster_id, side, protein_id, position, p``: the
+entries with p >= 1e-6); without the flag the tables and every launch are unchanged.
+
 Alternatives (opt-in: ``alternatives=K``, 1 <= K <= 32, ``predict --alternatives K [--alternatives-margin M]``, M = 10 by default).
 "What are the next-best readings of this region, and how much probability does each carry": for every called cluster the K best
 label paths of its neighbourhood, exactly (``_native.Model.viterbi_kbest``: list Viterbi on the device, one native call for all
@@ -250,7 +272,9 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
     when clusters carry region posteriors (NaN for a cluster of the list that does not); behind those ``anchor_p``, ``exact_p``,
     ``start_lo``, ``start_hi``, ``end_lo`` and ``end_hi`` when clusters carry boundary intervals (``boundary_samples > 0``; a
     cluster of the list that does not: NaN, and its own start and end); last ``start_p`` and ``end_p`` when clusters carry
-    boundary posteriors (``boundary_posteriors=True``)."""
+    boundary posteriors (``boundary_posteriors=True``), then ``run_anchor_p``, ``run_p``, ``run_start_lo``, ``run_start_hi``,
+    ``run_end_lo``, ``run_end_hi``, ``run_start_beyond_p`` and ``run_end_beyond_p`` when clusters carry run posteriors
+    (``run_posteriors=True``)."""
     table = tables.ClusterTable.from_clusters(clusters)
     extra = []
     for name in sorted(types, key=str.casefold):
@@ -282,9 +306,43 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
         table.columns["start_p"] = [float(getattr(c, "start_probability", nan)) for c in clusters]
         table.columns["end_p"] = [float(getattr(c, "end_probability", nan)) for c in clusters]
         extra += [("start_p", float, None), ("end_p", float, None)]
+    # run posteriors, behind every other optional column: only when clusters carry them (``run_posteriors=True``)
+    if any(hasattr(c, "run_anchor_probability") for c in clusters):
+        nan = float("nan")
+        table.columns["run_anchor_p"] = [float(getattr(c, "run_anchor_probability", nan)) for c in clusters]
+        table.columns["run_p"] = [float(getattr(c, "run_probability", nan)) for c in clusters]
+        extra += [("run_anchor_p", float, None), ("run_p", float, None)]
+        for col, attribute, k, own in (("run_start_lo", "run_start_interval", 0, "start"), ("run_start_hi", "run_start_interval", 1, "start"),
+                                       ("run_end_lo", "run_end_interval", 0, "end"), ("run_end_hi", "run_end_interval", 1, "end")):
+            table.columns[col] = [int(getattr(c, attribute)[k]) if hasattr(c, attribute) else int(getattr(c, own)) for c in clusters]
+            extra.append((col, int, None))
+        table.columns["run_start_beyond_p"] = [float(getattr(c, "run_start_beyond_probability", nan)) for c in clusters]
+        table.columns["run_end_beyond_p"] = [float(getattr(c, "run_end_beyond_probability", nan)) for c in clusters]
+        extra += [("run_start_beyond_p", float, None), ("run_end_beyond_p", float, None)]
     at = [n for n, _, _ in tables.ClusterTable.COLUMNS].index("type") + 1
     table.COLUMNS = tables.ClusterTable.COLUMNS[:at] + extra + tables.ClusterTable.COLUMNS[at:]
     return table
+
+
+def run_interval_offsets(p: np.ndarray, beyond: float, side: str) -> Tuple[int, int]:
+    """The interval rule of the run posteriors (module docstring) on one conditional distribution: ``p[r]`` the probability
+    that the run starts ``r`` genes before the anchor (``side="start"``) or ends ``r`` genes after it (``"end"``), ``beyond`` the
+    mass beyond the reach ``len(p) - 1``.  Positions are taken in ascending coordinate order -- for starts the mass beyond the
+    reach first, then r = reach .. 0; for ends r = 0 .. reach, then the mass beyond -- and the bounds are the first positions
+    whose cumulative mass is >= 0.05 and >= 0.95, as offsets r; a bound inside the mass beyond the reach is the reach.  (Should
+    rounding keep the total below 0.95, the upper bound is the last position with mass.)"""
+    reach = len(p) - 1
+    if side == "start":
+        mass = np.concatenate([[beyond], p[::-1]])
+        offset = [reach] + list(range(reach, -1, -1))
+    else:
+        mass = np.concatenate([p, [beyond]])
+        offset = list(range(reach + 1)) + [reach]
+    cum = np.cumsum(mass)
+    with_mass = np.flatnonzero(mass > 0.0)
+    last = int(with_mass[-1]) if len(with_mass) else 0
+    pick = lambda level: offset[int(np.argmax(cum >= level))] if cum[-1] >= level else offset[last]
+    return pick(0.05), pick(0.95)
 
 
 # ---------------------------------------------------------------------------------------------- the model
@@ -490,19 +548,24 @@ class TypedClusterCRF:
     def predict_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                          trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                          region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0, alternatives: int = 0,
-                         alternatives_margin: int = 10, boundary_posteriors: bool = False) -> List[Any]:
+                         alternatives_margin: int = 10, boundary_posteriors: bool = False, run_posteriors: bool = False,
+                         run_reach: int = 256) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
         per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, with
         ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities``, and with
         ``boundary_samples > 0`` each with ``anchor_probability``, ``exact_probability``, ``start_interval`` and
         ``end_interval``, and with ``alternatives = K > 0`` each with ``alternatives``, the K best readings of its
         neighbourhood with their exact conditional probabilities, and with ``boundary_posteriors`` each with
-        ``start_probability`` and ``end_probability`` (module docstring)."""
+        ``start_probability`` and ``end_probability``, and with ``run_posteriors`` each with ``run_anchor_probability``,
+        ``run_probability``, ``run_start_interval``, ``run_end_interval``, ``run_start_beyond_probability``,
+        ``run_end_beyond_probability`` and ``run_boundaries``, exact over ``run_reach`` genes to either side of the anchor
+        (module docstring)."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
                                                pad=pad, known=known, region_posteriors=region_posteriors,
                                                boundary_samples=boundary_samples, seed=seed, alternatives=alternatives,
                                                alternatives_margin=alternatives_margin,
-                                               boundary_posteriors=boundary_posteriors)[1]
+                                               boundary_posteriors=boundary_posteriors, run_posteriors=run_posteriors,
+                                               run_reach=run_reach)[1]
 
     def _region_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int,
                            clusters: List[Any]) -> None:
@@ -570,6 +633,40 @@ class TypedClusterCRF:
             "log_z": out["lognorm"].tolist(),
             "entropy": out["entropy"].tolist(),
             "expected_clusters": [float(enter[a:b].sum()) for a, b in zip(item_ptr[:-1].tolist(), item_ptr[1:].tolist())]}
+
+    def _run_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int, clusters: List[Any],
+                        annotated: List[Any], p_any: np.ndarray, reach: int) -> None:
+        """``run_anchor_probability``, ``run_probability``, ``run_start_interval``, ``run_end_interval``, the two beyond-masses
+        and ``run_boundaries`` of every called cluster (``rows``: the segment kernel's (contig, number, first gene, last gene +
+        1)), from ONE native call over the batch: per cluster one anchor query -- the run of genes outside the background
+        through the cluster's gene with the greatest ``p_any`` (the first on ties) -- and one closed-run query over the called
+        range."""
+        base = item_ptr[rows[:, 0]].astype(np.int64)
+        anchor = np.array([first + int(np.argmax(p_any[first:last])) for first, last in rows[:, 2:4].tolist()], dtype=np.int64)
+        contig, sets = rows[:, 0].astype(np.int32), np.full(len(rows), not_background, dtype=np.uint32)
+        out = self._fitted().run_posteriors(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
+                                            anchors=(contig, (anchor - base).astype(np.int32), sets), reach=reach,
+                                            runs=(contig, (rows[:, 2] - base).astype(np.int32), (rows[:, 3] - base).astype(np.int32), sets),
+                                            device=self.device, allowed=allowed)
+        for q, (cluster, a) in enumerate(zip(clusters, anchor.tolist())):
+            log_anchor = float(out["log_anchor"][q])
+            cluster.run_anchor_probability = math.exp(log_anchor)
+            cluster.run_probability = math.exp(float(out["log_run"][q]))
+            cluster.run_boundaries = []
+            if log_anchor == -math.inf:
+                cluster.run_start_interval = (int(cluster.start), int(cluster.start))
+                cluster.run_end_interval = (int(cluster.end), int(cluster.end))
+                cluster.run_start_beyond_probability = cluster.run_end_beyond_probability = 0.0
+                continue
+            for side, step, coordinate in (("start", -1, "start"), ("end", 1, "end")):
+                p = np.exp(out[f"log_{side}"][q] - log_anchor)
+                beyond = math.exp(float(out[f"log_{side}_beyond"][q]) - log_anchor)
+                lo, hi = run_interval_offsets(p, beyond, side)
+                setattr(cluster, f"run_{side}_interval", (int(getattr(annotated[a + step * lo], coordinate)),
+                                                          int(getattr(annotated[a + step * hi], coordinate))))
+                setattr(cluster, f"run_{side}_beyond_probability", beyond)
+                cluster.run_boundaries += [(side, annotated[a + step * r], int(getattr(annotated[a + step * r], coordinate)), float(p[r]))
+                                           for r in np.flatnonzero(p > 0.0).tolist()]
 
     def _alternatives(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, clusters: List[Any], annotated: List[Any],
                       p_any: np.ndarray, k: int, margin: int) -> None:
@@ -694,14 +791,17 @@ class TypedClusterCRF:
                                    region_posteriors: bool = False, boundary_samples: int = 0,
                                    seed: int = 0, alternatives: int = 0,
                                    alternatives_margin: int = 10,
-                                   boundary_posteriors: bool = False) -> Tuple[List[Any], List[Any]]:
+                                   boundary_posteriors: bool = False, run_posteriors: bool = False,
+                                   run_reach: int = 256) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
         second, whole-contig pass gives every cluster its region posteriors, and with ``boundary_samples = N > 0`` one more
         draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals; with ``alternatives = K >
         0`` (at most 32) a Viterbi pass and one list-Viterbi call give every cluster the K best readings of its neighbourhood of
         ``alternatives_margin`` genes on either side; with ``boundary_posteriors`` one more whole-contig pass gives every
         cluster ``start_probability`` and ``end_probability`` and the model ``sequence_posteriors_``, the per-contig columns
-        ``SEQUENCE_COLUMNS`` (module docstring).  ``ValueError`` before any device call for an option
+        ``SEQUENCE_COLUMNS``; with ``run_posteriors`` one more whole-contig pass and one native call give every cluster
+        the exact start and end distributions of the run through its anchor, over ``run_reach`` (0 .. 65536) genes to either
+        side (module docstring).  ``ValueError`` before any device call for an option
         that is not an integer or lies outside its range."""
         from . import _native
 
@@ -723,6 +823,12 @@ class TypedClusterCRF:
             raise ValueError(f"boundary_samples = {boundary_samples} is outside 0 .. 1048576")
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed {seed} is outside 0 .. 2**64 - 1")
+        try:
+            run_reach = operator.index(run_reach)
+        except TypeError:
+            raise ValueError(f"run_reach is an integer, got {run_reach!r}") from None
+        if not 0 <= run_reach <= 65536:
+            raise ValueError(f"run_reach = {run_reach} is outside 0 .. 65536")
         from .refine import _cluster_class
         from .types import _cluster_type_factory
 
@@ -756,6 +862,8 @@ class TypedClusterCRF:
             self._boundary_posteriors(batch, allowed, rows, item_ptr, not_background, clusters, annotated)
         if alternatives > 0 and clusters:
             self._alternatives(batch, allowed, rows, item_ptr, clusters, annotated, p_any, alternatives, alternatives_margin)
+        if run_posteriors and clusters:
+            self._run_posteriors(batch, allowed, rows, item_ptr, not_background, clusters, annotated, p_any, run_reach)
         return annotated, clusters
 
 
@@ -769,6 +877,19 @@ def write_alternatives(path, clusters: Sequence[Any]) -> None:
                 run = alt["run"] is not None
                 where = (str(alt["start"]), str(alt["end"]), alt["type"]) if run else ("", "", "")
                 out.write("\t".join((str(cluster.id), str(alt["rank"]), *where, repr(alt["log_p"]), repr(math.exp(alt["log_p"])))) + "\n")
+
+
+def write_boundaries(path, clusters: Sequence[Any], floor: float = 1e-6) -> None:
+    """``boundaries.tsv``: the exact start and end distributions of the run through every called cluster's anchor, given that the
+    anchor lies in a cluster: one row per cluster, side (``start`` / ``end``) and gene with conditional probability >= ``floor``,
+    columns ``cluster_id, side, protein_id, position, p`` (position: the gene's start for a start, its end for an end); floats
+    with ``repr``."""
+    with open(path, "w") as out:
+        out.write("\t".join(("cluster_id", "side", "protein_id", "position", "p")) + "\n")
+        for cluster in clusters:
+            for side, gene, position, p in getattr(cluster, "run_boundaries", ()):
+                if p >= floor:
+                    out.write("\t".join((str(cluster.id), side, str(gene.protein.id), str(position), repr(p))) + "\n")
 
 
 def write_path_clusters(path, clusters: Sequence[Any]) -> None:
@@ -857,6 +978,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="add start_p and end_p to clusters.tsv: the whole-contig posterior probability that a run of cluster labels "
                     "starts at a called region's first gene, and ends at its last; write sequences.tsv: per contig its log Z, "
                     "path entropy and expected number of clusters")
+    pr.add_argument("--run-posteriors", action="store_true",
+                    help="add run_anchor_p, run_p, run_start_lo, run_start_hi, run_end_lo, run_end_hi, run_start_beyond_p and "
+                    "run_end_beyond_p to clusters.tsv: the exact whole-contig distribution of where the run of cluster labels through "
+                    "every called region starts and ends; write boundaries.tsv, the distributions themselves")
+    pr.add_argument("--run-reach", type=int, default=256, metavar="R",
+                    help="genes on either side of a called region's anchor that the exact distributions cover (with --run-posteriors)")
     pr.add_argument("--path-clusters", type=int, default=None, metavar="M",
                     help="write path_clusters.tsv and paths.tsv: the regions of the best whole-contig label path among those in "
                     "which every region has at least M (at most 32) genes, and per contig that path's probability and the "
@@ -893,7 +1020,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                                       boundary_samples=args.boundary_samples, seed=args.seed,
                                                       alternatives=args.alternatives,
                                                       alternatives_margin=args.alternatives_margin,
-                                                      boundary_posteriors=args.boundary_posteriors)
+                                                      boundary_posteriors=args.boundary_posteriors,
+                                                      run_posteriors=args.run_posteriors, run_reach=args.run_reach)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))
@@ -902,6 +1030,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         write_alternatives(os.path.join(args.output_dir, "alternatives.tsv"), found)
     if args.boundary_posteriors:
         write_sequences(os.path.join(args.output_dir, "sequences.tsv"), crf.sequence_posteriors_)
+    if args.run_posteriors:
+        write_boundaries(os.path.join(args.output_dir, "boundaries.tsv"), found)
     if args.path_clusters is not None:
         known = None if args.known is None else tables.ClusterTable.load(args.known)
         write_path_clusters(os.path.join(args.output_dir, "path_clusters.tsv"),

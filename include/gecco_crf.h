@@ -51,7 +51,8 @@ const char *gecco_crf_last_error(void);
 /* ABI version: major*100 + minor*10 + patch (2.10.0 = 300, 2.11.0 = 310, 2.12.0 = 320, 2.13.0 = 330, 2.14.0 = 340).
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
- * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run. */
+ * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
+ * gecco_crf_run_posteriors. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -917,6 +918,57 @@ int gecco_crf_viterbi_min_run(const gecco_crf_model *m, int32_t device, const in
                               const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
                               int8_t *y /* [n_genes] */, double *score /* [n_contigs] */,
                               double *lognorm_min_run /* [n_contigs] or NULL */, double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- run posteriors (ABI 2.21.0, additive; gecco_crf_version() stays 340) --------------------------------------------------------
+ * The exact distribution of where a run starts and ends, on the whole-contig lattice of gecco_crf_marginals_full and
+ * gecco_crf_viterbi (not a windowed one).  Fix a gene a and a label set S; "the run through a" is the maximal stretch of genes
+ * around a whose labels all lie in S.  With `allowed` (one mask per gene, as the *_constrained entries take them) the lattice is
+ * the restricted one.  attr_value and allowed may each be NULL.  All outputs are natural logarithms, <= 0.0, -infinity where the
+ * probability is zero, never NaN.  T is the contig's number of genes.
+ *   * Anchor query q is (anchor_contig[q], anchor_item[q], anchor_mask[q]): a contig of the batch, a gene offset a from that
+ *     contig's first gene, and a mask with bit y set when label y is in S.  With the call-wide reach >= 0 it gives
+ *       log_anchor[q]                  = log P(y_a in S | x);
+ *       log_start[q * (reach+1) + r]   = log P(the run through a starts at gene a - r | x)
+ *                                      = log P(y_{a-r} .. y_a in S, and a - r = 0 or y_{a-r-1} not in S | x), -infinity for r > a;
+ *       log_start_beyond[q]            = log P(y_{a-reach-1} .. y_a in S | x), the run starts before the reach; -infinity when
+ *                                        a - reach - 1 < 0;
+ *       log_end[q * (reach+1) + r]     = log P(the run's last gene is a + r | x), -infinity for a + r >= T;
+ *       log_end_beyond[q]              = log P(y_a .. y_{a+reach+1} in S | x); -infinity when a + reach + 1 >= T.
+ *     logsumexp(log_start[q][:]) (+) log_start_beyond[q] = log_anchor[q] up to rounding, and the same for the ends.  S may hold
+ *     every label: every start but gene 0 and every end but gene T - 1 is then -infinity, and log_anchor is exactly 0.0.
+ *   * Closed-run query q is (run_contig[q], run_begin[q], run_end[q], run_mask[q]), the end exclusive:
+ *       log_run[q] = log P(y_begin .. y_{end-1} in S, begin = 0 or y_{begin-1} not in S, end = T or y_end not in S | x),
+ *     the probability that a run is EXACTLY the range: one entry of the joint (start, end) distribution of the run through any
+ *     gene of the range.  The joint is NOT the product of the two marginals above; sum_e P(start = s, end = e) = P(start = s).
+ *   * CRFsuite has no begin or end features: at a contig's first gene the entering vector is the emission alone.
+ *   * One forward-backward pass over the batch serves every query.  An anchor then costs two sequential walks of at most
+ *     reach + 2 genes, a closed run one walk of its genes, each by one group of lanes (crf_runs.hip); walks are not chunked.
+ *     Inside a walk the state scores are shifted by their maximum over S, so a label outside S that leads by hundreds costs its
+ *     exact, finite amount, and the vector is rescaled at every gene: a start hundreds of genes away with probability 1e-250 is
+ *     reported with relative accuracy.  The genes bordering the run enter through the pass's forward vector and marginals and
+ *     inherit its range, as in gecco_crf_span_probabilities.  A walk that loses all mass (a gene that allows no label of S,
+ *     zero transitions, an empty complement) writes -infinity for the rest.
+ *   * Equal calls give equal bytes (no atomics); a query's result depends neither on the other queries nor on reach: entry r
+ *     is the same bits at every reach >= r.
+ *   * marg [n_genes][L] and lognorm [n_contigs], each optional, are the bytes gecco_crf_marginals_full (or its _valued /
+ *     _constrained sibling, by the arguments given) writes for the batch.  (A 2-label model without values and masks has kernels
+ *     of its own for those: asking for marg or lognorm there costs a second pass.)  Either list of queries may be empty; with
+ *     both empty the call fills marg and lognorm.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL with a message: a negative n_anchors or n_runs; reach
+ *     outside 0 .. 65536; n_anchors * (reach + 1) >= 2^31; a NULL array of a non-empty list ("null buffer"); and, naming the
+ *     query ("anchor q: ...", "run q: ..."): a contig index outside the batch, an item outside its contig, begin < 0, begin >=
+ *     end, end beyond the contig's length, a mask of 0, a mask with a bit at or above the model's label count.  The checks of
+ *     the *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_run_posteriors(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                             const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                             const uint32_t *allowed /* NULL: no masks */, const int32_t *anchor_contig, const int32_t *anchor_item,
+                             const uint32_t *anchor_mask, int32_t n_anchors, int32_t reach, double *log_anchor /* [n_anchors] */,
+                             double *log_start /* [n_anchors][reach+1] */, double *log_start_beyond /* [n_anchors] */,
+                             double *log_end /* [n_anchors][reach+1] */, double *log_end_beyond /* [n_anchors] */,
+                             const int32_t *run_contig, const int32_t *run_begin, const int32_t *run_end, const uint32_t *run_mask,
+                             int32_t n_runs, double *log_run /* [n_runs] */, double *marg /* [n_genes][L] or NULL */,
+                             double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- feature selection (ABI 2.4.0): two-sided Fisher exact test over 2x2 tables, in fp64 -------------------------
  * What GECCO's Fisher feature selection (gecco/crf/select.py) asks scipy.stats.fisher_exact(table, "two-sided") for, once
