@@ -110,6 +110,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_i8p,
          _c_f64p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_marginals_min_run": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
+         _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_edge_posteriors": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_u32p, ctypes.c_int32, _c_f64p,
@@ -814,6 +819,30 @@ class Model:
             *head, values, allowed, set_mask, min_run, _ptr(y, _c_i8p), _ptr(score, _c_f64p),
             None if ln_c is None else _ptr(ln_c, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
         return y[:n - n0], score[:nc], (None if ln_c is None else ln_c[:nc]), (None if ln is None else ln[:nc])
+
+    def marginals_min_run(self, contig_ptr, gene_ptr, attr_id, set_mask, min_run, device=0, values=None, allowed=None,
+                          want_marginals=True, want_inside=True):
+        """The marginals of every gene among the paths ``viterbi_min_run`` decodes over: those whose every maximal run of labels
+        of a set has at least ``min_run`` genes (``gecco_crf_marginals_min_run``), 1 <= min_run <= 32; ``set_mask`` has bit y
+        set when label y is in the set.  Returns ``(marg, inside, lognorm_min_run, lognorm)``: ``marg`` float64 ``[n, L]``,
+        P(gene has label | x, the constraint), or None with ``want_marginals=False``; ``inside`` ``[n]``, the sum of ``marg``
+        over the labels of the set, or None with ``want_inside=False`` (the same bytes whether ``marg`` is asked for or not;
+        without it 8 bytes per gene come back); ``lognorm_min_run`` ``[n_contigs]``, ``viterbi_min_run``'s bits; ``lognorm``
+        ``[n_contigs]`` as ``marginals_full`` gives it.  A disallowed (gene, label) pair has exactly 0.0; a contig without a
+        feasible path has 0.0 at every gene and ``lognorm_min_run`` ``-inf``; a contig without genes has 0 for both log Z.
+        ``values`` and ``allowed`` as in ``marginals_full``."""
+        min_run, set_mask = operator.index(min_run), operator.index(set_mask)
+        if not 0 <= set_mask < 1 << 32:
+            raise ValueError(f"marginals_min_run: set_mask {set_mask} is outside 0 .. 2**32 - 1")
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
+        inside = np.zeros(max(n - n0, 1), dtype=np.float64) if want_inside else None
+        ln_c = np.zeros(max(nc, 1), dtype=np.float64)
+        ln = np.zeros(max(nc, 1), dtype=np.float64)
+        _check(self._lib.gecco_crf_marginals_min_run(
+            *head, values, allowed, set_mask, min_run, None if marg is None else _ptr(marg, _c_f64p),
+            None if inside is None else _ptr(inside, _c_f64p), _ptr(ln_c, _c_f64p), _ptr(ln, _c_f64p)))
+        return (None if marg is None else marg[:n - n0]), (None if inside is None else inside[:n - n0]), ln_c[:nc], ln[:nc]
 
     def edge_posteriors(self, contig_ptr, gene_ptr, attr_id, sets=None, want_pair=False, want_transitions=True, want_entropy=True,
                         want_marginals=False, device=0, values=None, allowed=None):

@@ -1257,6 +1257,59 @@ GECCO_API int gecco_crf_viterbi_min_run(const gecco_crf_model *m, int32_t device
     GECCO_GUARD_END
 }
 
+// ---- marginals under a minimum run length (ABI 2.22.0): P(gene g has label j | x, no run of labels of the set is shorter than
+// min_run) and its sum over the set, by a forward-backward on the run-counter lattice behind gl_state; log Z from the whole-contig
+// marginals pass (crf_minrun.hip)
+GECCO_API int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                          const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                          const uint32_t *allowed, uint32_t set_mask, int32_t min_run, double *marg, double *inside,
+                                          double *lognorm_min_run, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    if (min_run < 1 || min_run > kMaxMinRun)
+        return fail("marginals_min_run: min_run = " + std::to_string(min_run) + " is outside 1 .. 32");
+    if ((rc = check_label_set("marginals_min_run: set_mask", 0, set_mask, m->m.L))) return rc;
+    if (!marg && !inside) return fail("marginals_min_run: marg and inside are both NULL");
+    if (!lognorm_min_run) return fail("marginals_min_run: lognorm_min_run is NULL");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    const size_t nc = size_t(n_contigs), L = size_t(m->m.L);
+    {  // a batch whose every contig is empty needs no device: log Z_C = log Z = 0, and nothing else is written
+        bool empty = true;
+        for (size_t c = 0; empty && c < nc; ++c) empty = contig_ptr[c + 1] == contig_ptr[c];
+        if (empty) {
+            for (size_t c = 0; c < nc; ++c) {
+                lognorm_min_run[c] = 0.0;
+                if (lognorm) lognorm[c] = 0.0;
+            }
+            return GECCO_CRF_OK;
+        }
+    }
+    // per gene: inside, then (if asked for) the marginals under the constraint.  Per contig, behind log Z: log Z_C.  (The free
+    // marginals are the pass's own output and are not returned.)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 8 + (marg ? L * 8 : 0), 8, nullptr,
+                        lognorm, [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: log Z_C = log Z = 0, and nothing else is written)
+            for (size_t c = 0; c < nc; ++c) lognorm_min_run[c] = 0.0;
+            return int(GECCO_CRF_OK);
+        }
+        double *d_lognorm = b.out<double>(2), *d_lognorm_mr = d_lognorm + nc;
+        double *d_inside = b.out<double>(1), *d_marg = marg ? d_inside + size_t(b.n) : nullptr;
+        DeviceBlock<char> ws;
+        int rc = ws.alloc(minrun_forward_bytes(b.n, m->m.L, min_run), "hipMalloc min-run forward values");
+        if (rc) return rc;
+        rc = batch_wait(plan_run_marginals_min_run(b.plan, b.csr, set_mask, min_run, reinterpret_cast<double *>(ws.get()), d_marg,
+                                                   inside ? d_inside : nullptr, d_lognorm_mr, b.out<double>(0), d_lognorm, nullptr),
+                        "min-run marginals");
+        rc = batch_fetch(rc, marg, d_marg, size_t(b.n) * L * 8, "download marginals under the constraint");
+        rc = batch_fetch(rc, inside, d_inside, size_t(b.n) * 8, "download inside");
+        return batch_fetch(rc, lognorm_min_run, d_lognorm_mr, nc * 8, "download lognorm_min_run");
+    });
+    GECCO_GUARD_END
+}
+
 // ---- edge posteriors (ABI 2.19.0): the pairwise marginals of the whole-contig lattice, the probability that a run of labels of a
 // set starts or ends at a gene, a contig's expected transition counts and its path entropy, all behind one forward-backward
 // pass of the batch (crf_edges.hip)

@@ -386,6 +386,16 @@ size_t minrun_back_bytes(int64_t n_genes, int32_t L, int32_t min_run);
 hipError_t launch_gen_min_run(const GenArgs &a, uint32_t set_mask, int32_t min_run, uint8_t *back, int8_t *y, double *score,
                               double *lognorm_min_run, hipStream_t stream);
 
+// the workspace of the marginals under the constraint: one double per (gene, label, run counter), the forward values
+size_t minrun_forward_bytes(int64_t n_genes, int32_t L, int32_t min_run);
+// The marginals under the constraint of launch_gen_min_run, two launches: the sum-semiring forward walk, which
+// leaves lognorm_min_run[c] (launch_gen_min_run's bits) and its forward values in fwd (minrun_forward_bytes), and the backward
+// walk, which writes marg[g][j] = P(gene g has label j | x, the constraint) (null: not written) and inside[g] = the sum of marg[g]
+// over the labels of set_mask (null: not computed); at least one of the two.  A contig without a feasible path gets 0.0 at every
+// gene, a contig without genes 0 for log Z_C and nothing else.  Reads a.state, a.trans and a.contig_ptr like launch_gen_min_run.
+hipError_t launch_gen_min_run_marginals(const GenArgs &a, uint32_t set_mask, int32_t min_run, double *fwd, double *marg,
+                                        double *inside, double *lognorm_min_run, hipStream_t stream);
+
 // ---- edge posteriors (crf_edges.hip) ----
 constexpr int32_t kMaxEdgeSets = 32;   // label sets of one call
 constexpr int32_t kEdgeRunGenes = 32;  // genes of a run: what one group of lanes walks, counted from its contig's first gene

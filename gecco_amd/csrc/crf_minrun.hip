@@ -32,7 +32,10 @@
 //   Back-pointers (max only): one byte per (gene, label, slot), the source label in the low five bits and one bit "from d = m"
 // (as against m - 1), which means something at d = m only.  The final arg max runs across the group's lanes by xor-shuffles, the
 // smaller label winning a tie (one admissible state per label), and leaves the last gene's label in y, or -1.
-//   SUM is the second instantiation of the same body: no back-pointers, log Z_C instead of the score.
+//   SUM is the second instantiation of the same body: no back-pointers, log Z_C instead of the score.  <SUM, STORE> is the third:
+// it also writes every (gene, label, slot) forward value it stores in LDS to a workspace of 8 n_genes L m bytes, the slots of a
+// label that exist only (an outside label's one state at slot m - 1), and changes no arithmetic: its log Z_C has SUM's bits.
+// gl_minrun_backward reads them (below, at the kernel).
 // gl_minrun_backtrack: one lane per contig, last gene to first; the previous slot follows from the rule above.
 // A contig is one sequential walk; it is not chunked.
 #include "crf_device.hpp"
@@ -48,11 +51,12 @@ constexpr int kRTile = 8;    // genes of state scores fetched ahead
 constexpr int kRBack = 256;  // lanes per workgroup of the backtrack
 constexpr uint8_t kFromFull = 0x20;  // back-pointer bit: the source was (i, m), not (i, m - 1)
 
-template <int LP, bool SUM>
+template <int LP, bool SUM, bool STORE = false>
 __global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restrict__ state, const double *__restrict__ trans,
                                                          const int32_t *__restrict__ contig_ptr, const int L, const int n_contigs,
                                                          const int m, const uint32_t set_mask, uint8_t *__restrict__ back,
-                                                         int8_t *__restrict__ y, double *__restrict__ out) {
+                                                         int8_t *__restrict__ y, double *__restrict__ out, double *__restrict__ fwd) {
+    static_assert(SUM || !STORE, "the forward values are the sum semiring's");
     extern __shared__ __attribute__((aligned(16))) double cols[];  // [2][kRW][KS]
     constexpr int G = kRW / LP;
     const double ninf = -INFINITY;
@@ -81,6 +85,12 @@ __global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restric
         for (int k = 0; k < KS; ++k) {
             buf0[lane * KS + k] = k == first ? s0 : ninf;
             buf1[lane * KS + k] = ninf;
+        }
+        if constexpr (STORE) {
+            if (on && T > 0) {
+                const size_t b0 = (static_cast<size_t>(g0) * L + jj) * static_cast<size_t>(m);
+                for (int k = inside ? 0 : top; k < m; ++k) fwd[b0 + k] = k == first ? s0 : ninf;
+            }
         }
     }
     __syncthreads();  // (one wave)
@@ -133,6 +143,9 @@ __global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restric
                 mine[d] = value;
                 if constexpr (!SUM) {
                     if (on) back[bk + d] = static_cast<uint8_t>(arg);
+                }
+                if constexpr (STORE) {
+                    if (on) fwd[bk + d] = value;
                 }
             }
         }
@@ -210,13 +223,155 @@ __global__ void __launch_bounds__(kRBack) gl_minrun_backtrack(const uint8_t *__r
     }
 }
 
-template <int LP, bool SUM>
-void launch_forward(const GenArgs &a, uint32_t set_mask, int32_t m, uint8_t *back, int8_t *y, double *out, hipStream_t stream) {
+// The backward walk of the sum semiring and the marginals under the constraint.  The geometry of the forward
+// kernel, transposed: a lane owns a SOURCE label i and keeps its row of trans; its column beta_t(i, d) lies in LDS as the forward
+// column does, and beside it one double per lane, the state score of the gene the column belongs to, so that a source reads
+// state_{t+1}[k] of every successor label from LDS.  The successors of a source at gene t, from the table at the head of the file:
+//   i outside S             every k outside S, and (k, 1) for k in S (slot 0; at m = 1 that is the one state of k)
+//   (i, d), d < m           (k, d + 1), k in S
+//   (i, m)                  (k, m), k in S, and every k outside S -- all of them at slot m - 1
+// beta_{T-1} = 0 at the admissible states (slot m - 1 of every label), -infinity elsewhere;
+// beta_t(s) = LSE over successors s' of (trans[i][k] + state_{t+1}[k]) + beta_{t+1}(s'), max-shifted, -infinity when every
+// term is.  The groups of a wave start at their contigs' last genes, so step u is gene T - 2 - u of each; a group that has reached
+// gene 0 stores nothing more.  State scores come eight steps ahead.  One barrier per step, outside every divergent branch.
+//   As it goes: marg[g][i] = sum over the lane's slots, ascending, of exp((alpha + beta) - log Z_C) with alpha from the forward
+// launch's workspace and log Z_C its output; inside[g] = the group's sum of marg over the labels of S (crf_lanes.hpp's butterfly:
+// one order of additions).  A state that no feasible path visits adds exactly 0.0, and so does every state of a contig without a
+// feasible path.  No atomics.
+template <int LP>
+__global__ void __launch_bounds__(kRW) gl_minrun_backward(const double *__restrict__ state, const double *__restrict__ trans,
+                                                          const int32_t *__restrict__ contig_ptr, const int L, const int n_contigs,
+                                                          const int m, const uint32_t set_mask, const double *__restrict__ fwd,
+                                                          const double *__restrict__ lognorm_c, double *__restrict__ marg,
+                                                          double *__restrict__ inside_out) {
+    extern __shared__ __attribute__((aligned(16))) double cols[];  // [2][kRW][KS] beta, then [2][kRW] state scores
+    constexpr int G = kRW / LP;
+    const double ninf = -INFINITY;
+    const int KS = m | 1, top = m - 1;
+    const int lane = threadIdx.x, i = lane & (LP - 1), row0 = lane - i;
+    const long long c = static_cast<long long>(blockIdx.x) * G + lane / LP;
+    const bool valid = c < n_contigs;
+    int g0 = 0, T = 0;
+    if (valid) {
+        g0 = contig_ptr[c];
+        T = contig_ptr[c + 1] - g0;
+        T = T < 0 ? 0 : T;
+    }
+    const bool on = i < L;
+    const int ii = on ? i : 0;
+    const bool inside = (set_mask >> i) & 1u;
+    const double lz = valid ? lognorm_c[c] : ninf;
+    const bool feasible = lz > ninf;
+    double trow[LP];
+#pragma unroll
+    for (int k = 0; k < LP; ++k) trow[k] = k < L ? trans[ii * L + k] : 0.0;
+    double *const buf0 = cols, *const buf1 = cols + kRW * KS;
+    double *const sb0 = cols + 2 * kRW * KS, *const sb1 = sb0 + kRW;
+    const double *st = state + static_cast<size_t>(g0) * L + ii;
+    // the state score of the gene u steps before the last one
+    const auto fetch = [&](int u) { return u < T ? (on ? st[static_cast<size_t>(T - 1 - u) * L] : ninf) : 0.0; };
+    // one gene's outputs; every lane of the wave comes here
+    const auto emit = [&](const bool act, const int t, const double p) {
+        const size_t g = static_cast<size_t>(g0) + static_cast<size_t>(act ? t : 0);
+        if (marg && act && on) marg[g * L + ii] = p;
+        if (inside_out) {  // (wave-uniform)
+            const double s = group_sum<LP>(inside && on ? p : 0.0);
+            if (act && i == 0) inside_out[g] = s;
+        }
+    };
+    {
+        for (int k = 0; k < KS; ++k) {
+            buf0[lane * KS + k] = (on && k == top) ? 0.0 : ninf;
+            buf1[lane * KS + k] = ninf;
+        }
+        sb0[lane] = fetch(0);
+        sb1[lane] = ninf;
+        double p = 0.0;
+        if (T > 0 && on) {  // the last gene: beta is 0 at the one admissible state of the label
+            const double a = fwd[((static_cast<size_t>(g0) + static_cast<size_t>(T - 1)) * L + ii) * static_cast<size_t>(m) + top];
+            p = (feasible && a > ninf) ? exp(a - lz) : 0.0;
+        }
+        emit(T > 0, T - 1, p);
+    }
+    __syncthreads();  // (one wave)
+    const auto step = [&](const int u, const double s_t) {
+        const int t = T - 2 - u;
+        const bool act = t >= 0;
+        const double *prev = ((u & 1) ? buf1 : buf0) + row0 * KS;
+        const double *sprev = ((u & 1) ? sb1 : sb0) + row0;
+        double *mine = ((u & 1) ? buf0 : buf1) + lane * KS;
+        double ts[LP];  // what every successor label costs on top of its beta
+#pragma unroll
+        for (int k = 0; k < LP; ++k) ts[k] = trow[k] + sprev[k];
+        const size_t ak = ((static_cast<size_t>(g0) + static_cast<size_t>(act ? t : 0)) * L + ii) * static_cast<size_t>(m);
+        double p = 0.0;
+#pragma unroll 1
+        for (int d = 0; d < m; ++d) {
+            const bool last = d == top;  // (wave-uniform)
+            const bool own = inside || last;
+            const double a = (act && on && own) ? fwd[ak + d] : ninf;
+            const int slot_in = last ? top : d + 1;
+            const bool every = !inside || last;  // every label has a successor state; otherwise the labels of S only
+            const auto successors = [&](auto &&f) {
+#pragma unroll
+                for (int k = 0; k < LP; ++k) {
+                    const bool in_k = (set_mask >> k) & 1u;
+                    const int slot = inside ? slot_in : (in_k ? 0 : top);
+                    const double v = prev[k * KS + slot] + ts[k];
+                    f((every || in_k) ? v : ninf);
+                }
+            };
+            double mx = ninf;
+            successors([&](double v) { mx = v > mx ? v : mx; });
+            const double shift = mx > ninf ? mx : 0.0;
+            double sum = 0.0;
+            successors([&](double v) { sum += v > ninf ? exp(v - shift) : 0.0; });
+            const double b = (on && mx > ninf) ? mx + log(sum) : ninf;
+            if (act && own) {
+                mine[d] = b;
+                const double ab = a + b;
+                p += (feasible && ab > ninf) ? exp(ab - lz) : 0.0;
+            }
+        }
+        if (act) (((u & 1) ? sb0 : sb1))[lane] = s_t;
+        emit(act, t, p);
+        __syncthreads();
+    };
+    double nxt[kRTile];
+#pragma unroll
+    for (int k = 0; k < kRTile; ++k) nxt[k] = fetch(1 + k);
+    for (int ub = 0; __any(ub < T - 1); ub += kRTile) {
+        double cur[kRTile];
+#pragma unroll
+        for (int k = 0; k < kRTile; ++k) cur[k] = nxt[k];
+#pragma unroll
+        for (int k = 0; k < kRTile; ++k) nxt[k] = fetch(ub + kRTile + 1 + k);
+#pragma unroll
+        for (int k = 0; k < kRTile; ++k) {
+            if (!__any(ub + k < T - 1)) break;  // (wave-uniform)
+            step(ub + k, cur[k]);
+        }
+    }
+}
+
+template <int LP, bool SUM, bool STORE = false>
+void launch_forward(const GenArgs &a, uint32_t set_mask, int32_t m, uint8_t *back, int8_t *y, double *out, hipStream_t stream,
+                    double *fwd = nullptr) {
     constexpr int G = kRW / LP;
     const unsigned blocks = static_cast<unsigned>((static_cast<long long>(a.n_contigs) + G - 1) / G);
     const size_t lds = size_t(2) * kRW * size_t(m | 1) * sizeof(double);
-    hipLaunchKernelGGL((gl_minrun_forward<LP, SUM>), dim3(blocks), dim3(kRW), lds, stream, a.state, a.trans, a.contig_ptr, a.L,
-                       a.n_contigs, m, set_mask, back, y, out);
+    hipLaunchKernelGGL((gl_minrun_forward<LP, SUM, STORE>), dim3(blocks), dim3(kRW), lds, stream, a.state, a.trans, a.contig_ptr, a.L,
+                       a.n_contigs, m, set_mask, back, y, out, fwd);
+}
+
+template <int LP>
+void launch_backward(const GenArgs &a, uint32_t set_mask, int32_t m, const double *fwd, const double *lognorm_c, double *marg,
+                     double *inside, hipStream_t stream) {
+    constexpr int G = kRW / LP;
+    const unsigned blocks = static_cast<unsigned>((static_cast<long long>(a.n_contigs) + G - 1) / G);
+    const size_t lds = (size_t(2) * kRW * size_t(m | 1) + size_t(2) * kRW) * sizeof(double);
+    hipLaunchKernelGGL((gl_minrun_backward<LP>), dim3(blocks), dim3(kRW), lds, stream, a.state, a.trans, a.contig_ptr, a.L,
+                       a.n_contigs, m, set_mask, fwd, lognorm_c, marg, inside);
 }
 
 }  // namespace
@@ -240,6 +395,24 @@ hipError_t launch_gen_min_run(const GenArgs &a, uint32_t set_mask, int32_t min_r
     e = hipGetLastError();
     if (e != hipSuccess || !lognorm_min_run) return e;
     dispatch_lp(a.L, [&](auto lp) { launch_forward<lp, true>(a, set_mask, min_run, nullptr, nullptr, lognorm_min_run, stream); });
+    return hipGetLastError();
+}
+
+size_t minrun_forward_bytes(int64_t n_genes, int32_t L, int32_t min_run) {
+    return sizeof(double) * static_cast<size_t>(n_genes) * static_cast<size_t>(L) * static_cast<size_t>(min_run);
+}
+
+hipError_t launch_gen_min_run_marginals(const GenArgs &a, uint32_t set_mask, int32_t min_run, double *fwd, double *marg,
+                                        double *inside, double *lognorm_min_run, hipStream_t stream) {
+    const uint32_t beyond = a.L >= 32 ? 0u : ~0u << a.L;
+    if (a.L <= 0 || a.L > kGenMaxL || min_run < 1 || min_run > kMaxMinRun || set_mask == 0 || (set_mask & beyond))
+        return hipErrorNotSupported;
+    if (a.n_contigs <= 0) return hipSuccess;
+    if (!a.state || !a.trans || !fwd || !lognorm_min_run || (!marg && !inside)) return hipErrorNotSupported;
+    dispatch_lp(a.L, [&](auto lp) { launch_forward<lp, true, true>(a, set_mask, min_run, nullptr, nullptr, lognorm_min_run, stream, fwd); });
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    dispatch_lp(a.L, [&](auto lp) { launch_backward<lp>(a, set_mask, min_run, fwd, lognorm_min_run, marg, inside, stream); });
     return hipGetLastError();
 }
 

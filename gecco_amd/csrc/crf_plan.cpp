@@ -1421,6 +1421,27 @@ int plan_run_viterbi_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, i
     return check_hip(launch_gen_min_run(g, set_mask, min_run, d_back, d_y, d_score, d_lognorm_min_run, stream), "min-run launch");
 }
 
+int plan_run_marginals_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t min_run, double *d_fwd, double *d_marg_min_run,
+                               double *d_inside, double *d_lognorm_min_run, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    if (min_run < 1 || min_run > kMaxMinRun) {
+        set_error("min_run outside 1 .. 32");
+        return GECCO_CRF_EINVAL;
+    }
+    const int32_t L = p.model ? p.model->L : 32;  // (a plan that was never built is check_plan's to refuse)
+    if (set_mask == 0 || (L < 32 && (set_mask >> L))) {
+        set_error("set_mask is empty, or holds a label at or above num_labels");
+        return GECCO_CRF_EINVAL;
+    }
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !d_marg || !d_fwd || !d_lognorm_min_run || (!d_marg_min_run && !d_inside), rc))
+        return rc;
+    GenArgs g;  // (the pass gives log Z; the run-counter recursions read the raw state scores and nothing else)
+    if ((rc = run_lattice(p, csr, "minimum-run marginals", true, d_marg, d_lognorm, stream, g))) return rc;
+    return check_hip(launch_gen_min_run_marginals(g, set_mask, min_run, d_fwd, d_marg_min_run, d_inside, d_lognorm_min_run, stream),
+                     "min-run marginals launch");
+}
+
 int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, double *d_marg, double *d_lognorm, hipStream_t stream) {
     if (q.n_sets < 0 || q.n_sets > kMaxEdgeSets || (q.n_sets == 0 && (q.enter || q.leave))) {
         set_error("the number of label sets is outside 1 .. 32 (0 without enter and leave)");

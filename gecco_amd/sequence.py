@@ -529,6 +529,34 @@ class SequenceCRF:
                         "constraint_log_probability": float(lognorm_c[s] - lognorm[s])})
         return out
 
+    def predict_marginals_min_run(self, X, labels, min_run, allowed=None) -> List[Dict[str, object]]:
+        """How sure the model is of every item AMONG THE PATHS ``predict_min_run`` decodes over: those in which every maximal
+        run of consecutive items carrying a label of ``labels`` has at least ``min_run`` items (``labels``, ``min_run`` and
+        ``allowed`` as there).  These are not ``predict_marginals``' numbers, which give mass to paths with short runs: a lone
+        high-scoring item can have a free marginal of 0.9 and a constrained one near 0.  Per sequence a dict with
+        ``marginals``: ``[n_items, L]``, P(item has label | x, the constraint), columns in ``predict_marginals``' order
+        (``classes_``); ``inside``: ``[n_items]``, the probability that the item carries a label of ``labels``, the sum of those
+        columns; ``constraint_log_probability``: ``log Z_C - log Z`` as ``predict_min_run`` reports it.  ``marginals`` and
+        ``inside`` are None when no path satisfies the constraint (``constraint_log_probability`` is then ``-inf``).  One
+        forward-backward pass and two walks over ``X``, one native call.  A sequence without items has empty arrays and 0.0.
+        Raises the ``ValueError`` s of ``predict_min_run``, before any device call."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = self._label_bits("predict_marginals_min_run", labels)
+        min_run = self._min_run(min_run)
+        n_seqs = len(seq_ptr) - 1
+        L = len(self.classes_)
+        if seq_ptr[-1] == 0:
+            return [{"marginals": np.zeros((0, L)), "inside": np.zeros(0), "constraint_log_probability": 0.0} for _ in range(n_seqs)]
+        marg, inside, lognorm_c, lognorm = self._model.marginals_min_run(seq_ptr, item_ptr, attr, bits, min_run, device=self.device,
+                                                                         values=values, allowed=masks)
+        out = []
+        for s, (ms, ins) in enumerate(zip(self._split(marg, seq_ptr), self._split(inside, seq_ptr))):
+            found = lognorm_c[s] > -np.inf
+            out.append({"marginals": ms if found else None, "inside": ins if found else None,
+                        "constraint_log_probability": float(lognorm_c[s] - lognorm[s])})
+        return out
+
     # ---- edge posteriors: the pairwise marginals of the whole-sequence lattice and their sums (``_native.Model.edge_posteriors``)
     def _edges(self, X, allowed, sets=None, **want):
         """One pass over ``X`` for the edge outputs ``want`` names: ``(seq_ptr, masks of sets, the native call's dict)``, the dict

@@ -112,6 +112,15 @@ a cluster label under ``known=``), ``constraint_log_p`` = log P(no run shorter t
 writes ``path_clusters.tsv`` (columns ``sequence_id, cluster_id, start, end, genes, type``) and ``paths.tsv`` next to the other
 tables, which stay byte for byte what they are without the flag.
 
+Path marginals (``predict_path_clusters(..., marginals=True)``, ``predict --path-clusters M --path-marginals``).  The free
+marginals are the wrong numbers to attach to a path cluster: they give mass to paths with runs shorter than M, which the
+constrained decoder rules out.  One more whole-contig call after the decode (``_native.Model.marginals_min_run`` with the same
+set and the same ``known`` masks, 8 bytes per gene back) gives every gene ``inside`` = P(the gene lies in a region | x, no region
+is shorter than M); every path cluster gains ``average_p``, ``max_p`` and ``min_p`` of it over its genes (the mean is
+``numpy.mean``, as the refiner takes a cluster's mean), and ``path_gene_probabilities_`` holds it per gene.  The command line
+appends the three columns to ``path_clusters.tsv`` and writes ``path_genes.tsv`` (columns ``sequence_id, protein_id, path_label,
+p``).  Without the flag every table and every launch is what it is today.
+
 Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
 ``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
 """
@@ -134,7 +143,7 @@ from . import tables
 
 __all__ = ["BACKGROUND", "MIXED", "UNKNOWN", "MAX_CLUSTER_LABELS", "TypedClusterCRF", "cluster_labels", "fold_labels",
            "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "write_alternatives",
-           "write_sequences", "write_path_clusters", "write_paths", "build_parser", "main"]
+           "write_sequences", "write_path_clusters", "write_path_genes", "write_paths", "build_parser", "main"]
 
 BACKGROUND = "0"
 MIXED = "Mixed"
@@ -725,16 +734,24 @@ class TypedClusterCRF:
 
     PATH_COLUMNS = ("sequence_id", "genes", "log_z", "score", "log_p", "constraint_log_p", "clusters")
 
+    PATH_GENE_COLUMNS = ("sequence_id", "protein_id", "path_label", "p")
+
     def predict_path_clusters(self, genes: Iterable[Any], *, min_run: int = 3,
-                              known: Optional[tables.ClusterTable] = None) -> List[Any]:
+                              known: Optional[tables.ClusterTable] = None, marginals: bool = False) -> List[Any]:
         """Clusters as the runs of the best whole-contig label path AMONG THOSE in which every maximal run of genes with a label
         other than the background has at least ``min_run`` genes (module docstring): one ``viterbi_min_run`` call over all
         contigs with the set of every label but the background.  ``min_run`` counts genes, not annotated genes (the refiner's
         ``n_cds`` counts annotated ones), 1 <= ``min_run`` <= 32.  Every cluster has the id ``{sequence}_cluster_{number}``
-        (numbered from 1 along its contig), its genes (the caller's, sorted by (sequence, start); no probability is computed),
+        (numbered from 1 along its contig), its genes (the caller's, sorted by (sequence, start); no probability is computed
+        unless ``marginals`` is set),
         ``type`` from the run's most frequent label (the smaller label id on ties) and ``path_type``, its ``";"``-joined names
         (``"Unknown"`` for a label without types).  Fills ``path_posteriors_``, the
         per-contig columns ``PATH_COLUMNS``.  ``known`` restricts the lattice as in the other prediction methods.
+        With ``marginals=True`` one ``marginals_min_run`` call follows the decode (the same set, the same masks, no marginals
+        table: 8 bytes per gene come back): every cluster gains ``average_p`` (``numpy.mean``), ``max_p`` and ``min_p`` of
+        ``inside`` = P(gene in a region | x, the constraint) over its genes, ``path_gene_probabilities_`` holds ``inside`` per
+        gene in (sequence, start) order and ``path_genes_`` the columns ``PATH_GENE_COLUMNS`` (``path_label``: the gene's label
+        on the path, empty where a contig has no path).  Without it neither attribute is set and no further launch runs.
         ``ValueError`` before any device call for a ``min_run`` that is not an integer or lies outside its range."""
         try:
             min_run = operator.index(min_run)
@@ -752,6 +769,9 @@ class TypedClusterCRF:
             gene.protein.domains.sort(key=operator.attrgetter("start"))
         contigs = [list(g) for _, g in itertools.groupby(genes, key=operator.attrgetter("source.id"))]
         self.path_posteriors_ = {name: [] for name in self.PATH_COLUMNS}
+        if marginals:
+            self.path_gene_probabilities_ = np.zeros(0)
+            self.path_genes_ = {name: [] for name in self.PATH_GENE_COLUMNS}
         if not genes:
             return []
         batch = packing.pack_contigs(contigs, self._attr_index, "protein")
@@ -765,6 +785,12 @@ class TypedClusterCRF:
         item_ptr = batch.item_ptr.astype(np.int32)
         y, score, lognorm_c, lognorm = model.viterbi_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
                                                              ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device, allowed=allowed)
+        inside_p = None
+        if marginals:
+            _, inside_p, _, _ = model.marginals_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
+                                                        ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device, allowed=allowed,
+                                                        want_marginals=False)
+            self.path_gene_probabilities_ = inside_p
         Cluster = _cluster_class()
         clusters: List[Any] = []
         for ci, contig in enumerate(contigs):
@@ -780,7 +806,16 @@ class TypedClusterCRF:
                     major = int(np.argmax(np.bincount(path[a:b], minlength=L)))
                     cluster.type = _cluster_type_factory(cluster)(self.label_types_[major])
                     cluster.path_type = ";".join(self.label_types_[major]) or UNKNOWN  # (as the alternatives name a run's type)
+                    if inside_p is not None:
+                        ps = inside_p[c0 + a:c0 + b]
+                        cluster.average_p, cluster.max_p, cluster.min_p = float(np.mean(ps)), float(ps.max()), float(ps.min())
                     clusters.append(cluster)
+            if inside_p is not None:
+                rows = self.path_genes_
+                rows["sequence_id"].extend(g.source.id for g in contig)
+                rows["protein_id"].extend(g.protein.id for g in contig)
+                rows["path_label"].extend(self.classes_[k] if k >= 0 else "" for k in path.tolist())
+                rows["p"].extend(inside_p[c0:c1].tolist())
             for name, value in zip(self.PATH_COLUMNS, (contig[0].source.id, c1 - c0, float(lognorm[ci]), float(score[ci]),
                                                        float(score[ci] - lognorm[ci]), float(lognorm_c[ci] - lognorm[ci]), found)):
                 self.path_posteriors_[name].append(value)
@@ -892,16 +927,29 @@ def write_boundaries(path, clusters: Sequence[Any], floor: float = 1e-6) -> None
                     out.write("\t".join((str(cluster.id), side, str(gene.protein.id), str(position), repr(p))) + "\n")
 
 
-def write_path_clusters(path, clusters: Sequence[Any]) -> None:
+def write_path_clusters(path, clusters: Sequence[Any], marginals: bool = False) -> None:
     """``path_clusters.tsv``: one row per cluster of ``predict_path_clusters``, columns ``sequence_id, cluster_id, start, end,
-    genes, type`` (type: the ``";"``-joined names, ``"Unknown"`` for a label without types)."""
+    genes, type`` (type: the ``";"``-joined names, ``"Unknown"`` for a label without types); with ``marginals`` (clusters of
+    ``predict_path_clusters(..., marginals=True)``) ``average_p, max_p, min_p`` behind them, floats with ``repr``."""
+    more = ("average_p", "max_p", "min_p") if marginals else ()
     with open(path, "w") as out:
-        out.write("\t".join(("sequence_id", "cluster_id", "start", "end", "genes", "type")) + "\n")
+        out.write("\t".join(("sequence_id", "cluster_id", "start", "end", "genes", "type") + more) + "\n")
         for cluster in clusters:
             members = cluster.genes
             names = getattr(cluster, "path_type", None) or ";".join(sorted(getattr(cluster.type, "names", ()))) or UNKNOWN
             out.write("\t".join((str(members[0].source.id), str(cluster.id), str(min(g.start for g in members)),
-                                 str(max(g.end for g in members)), str(len(members)), names)) + "\n")
+                                 str(max(g.end for g in members)), str(len(members)), names,
+                                 *(repr(float(getattr(cluster, name))) for name in more))) + "\n")
+
+
+def write_path_genes(path, columns) -> None:
+    """``path_genes.tsv``: one row per gene, columns ``TypedClusterCRF.PATH_GENE_COLUMNS`` (``path_genes_``); ``p`` with
+    ``repr``."""
+    names = TypedClusterCRF.PATH_GENE_COLUMNS
+    with open(path, "w") as out:
+        out.write("\t".join(names) + "\n")
+        for row in zip(*(columns[name] for name in names)):
+            out.write("\t".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
 
 
 def write_paths(path, columns) -> None:
@@ -988,6 +1036,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="write path_clusters.tsv and paths.tsv: the regions of the best whole-contig label path among those in "
                     "which every region has at least M (at most 32) genes, and per contig that path's probability and the "
                     "probability that no region is shorter")
+    pr.add_argument("--path-marginals", action="store_true",
+                    help="with --path-clusters M: add average_p, max_p and min_p to path_clusters.tsv, of the probability that a "
+                    "gene lies in a region given that no region has fewer than M genes; write path_genes.tsv, that probability "
+                    "per gene")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -1011,6 +1063,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if args.path_clusters is not None and not 1 <= args.path_clusters <= 32:
         raise ValueError(f"--path-clusters {args.path_clusters} is outside 1 .. 32")
+    if args.path_marginals and args.path_clusters is None:
+        raise ValueError("--path-marginals needs --path-clusters M")
     crf = TypedClusterCRF.trained(args.model, device=args.device)
     genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
     annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
@@ -1035,7 +1089,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.path_clusters is not None:
         known = None if args.known is None else tables.ClusterTable.load(args.known)
         write_path_clusters(os.path.join(args.output_dir, "path_clusters.tsv"),
-                            crf.predict_path_clusters(genes, min_run=args.path_clusters, known=known))
+                            crf.predict_path_clusters(genes, min_run=args.path_clusters, known=known, marginals=args.path_marginals),
+                            marginals=args.path_marginals)
+        if args.path_marginals:
+            write_path_genes(os.path.join(args.output_dir, "path_genes.tsv"), crf.path_genes_)
         write_paths(os.path.join(args.output_dir, "paths.tsv"), crf.path_posteriors_)
     print(f"predict: {len(annotated)} genes, {len(found)} clusters -> {args.output_dir}", file=sys.stderr)
     return 0

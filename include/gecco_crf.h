@@ -52,7 +52,7 @@ const char *gecco_crf_last_error(void);
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
- * gecco_crf_run_posteriors. */
+ * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -918,6 +918,40 @@ int gecco_crf_viterbi_min_run(const gecco_crf_model *m, int32_t device, const in
                               const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
                               int8_t *y /* [n_genes] */, double *score /* [n_contigs] */,
                               double *lognorm_min_run /* [n_contigs] or NULL */, double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- marginals under a minimum run length (ABI 2.22.0, additive; gecco_crf_version() stays 340) ---------------------------------
+ * marg[g][j] = P(gene g has label j | x, every maximal run of labels of S has at least min_run genes) and inside[g] = the sum of
+ * marg[g] over the labels of S: how sure the model is of each gene AMONG THE FEASIBLE PATHS of gecco_crf_viterbi_min_run -- the
+ * same set, the same feasibility, the same whole-contig lattice, `allowed` and attr_value as there.  These are not the free
+ * marginals of gecco_crf_marginals_full, which give mass to paths with short runs: a lone high-scoring gene can have a free
+ * marginal of 0.9 and a constrained one near 0.
+ *   * A forward-backward on the lattice expanded by a run counter (the states, sources and admissible end states of
+ *     gecco_crf_viterbi_min_run above), in log space with a max-shifted log-sum-exp per state, fp64 throughout.  The forward walk
+ *     is the sum-semiring walk of gecco_crf_viterbi_min_run with its values kept: lognorm_min_run has that entry's bits.  The
+ *     backward walk transposes the table: a state outside S is followed by every label outside S and by (k, 1), k in S; (i, d)
+ *     with d < min_run by (k, d + 1), k in S, only; (i, min_run) by (k, min_run), k in S, and every label outside S.  beta is 0
+ *     at the admissible states of the last gene; beta_t(s) = LSE over successors of trans[i][k] + state_{t+1}[k] + beta_{t+1}.
+ *     marg[g][j] = the sum over d, ascending, of exp((alpha + beta) - lognorm_min_run).
+ *   * Outputs.  marg is double [n_genes][num_labels] or NULL, inside double [n_genes] or NULL -- at least one of them; with marg
+ *     NULL only 8 bytes per gene come back, and inside has the bytes it has when both are asked for.  lognorm_min_run
+ *     [n_contigs] is required; lognorm [n_contigs] (optional) is the bytes gecco_crf_marginals_full (or its _valued /
+ *     _constrained sibling, by the arguments given) writes for the batch, so exp(lognorm_min_run - lognorm) = P(no run shorter
+ *     than min_run | x).  A disallowed (gene, label) pair gives exactly 0.0.  A contig without a feasible path gives 0.0 at every
+ *     gene and lognorm_min_run -infinity; never NaN.  A contig without genes gets 0 for both log Z and nothing else.  A marginal
+ *     is stored as computed: a sum over labels may differ from 1 by rounding.  contig_ptr[0] > 0 works as in the other one-shots.
+ *   * The forward values are workspace of 8 * n_genes * num_labels * min_run bytes; sizes are computed in size_t; a failed
+ *     allocation is GECCO_CRF_ENOMEM.  Equal calls give equal bytes (no atomics), and a contig's bytes do not depend on the
+ *     other contigs of the batch.
+ *   * Limits: 1 <= min_run <= 32 and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL, every message prefixed "marginals_min_run:": min_run
+ *     outside 1 .. 32, a set_mask of 0 or with a bit at or above num_labels, marg and inside both NULL, lognorm_min_run NULL.
+ *     The checks of the *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form); contigs are not chunked. */
+int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                                const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
+                                double *marg /* [n_genes][L] or NULL */, double *inside /* [n_genes] or NULL */,
+                                double *lognorm_min_run /* [n_contigs] */, double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- run posteriors (ABI 2.21.0, additive; gecco_crf_version() stays 340) --------------------------------------------------------
  * The exact distribution of where a run starts and ends, on the whole-contig lattice of gecco_crf_marginals_full and

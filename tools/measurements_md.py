@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """profiles/MEASUREMENTS.md from the committed records of the round (profiles/r06_*): every number in that file is read from the
 file it names, so the document cannot drift from the records.   usage: python tools/measurements_md.py > profiles/MEASUREMENTS.md
-(the head of the file, §1 to §7); python tools/measurements_md.py --section 7m prints §7m from profiles/runs_bench.jsonl."""
+(the head of the file, §1 to §7); python tools/measurements_md.py --section 7m prints §7m from profiles/runs_bench.jsonl,
+--section 7n prints §7n from profiles/minrun_marginals_bench.jsonl."""
 import json
 import os
 import re
@@ -100,6 +101,73 @@ def section_7m():
       "longest (the typed front end: a fit, five predictions and two command lines) 5.2 s.")
     A("* Not measured: how the pass, the host checks and the copies divide inside the call; reaches beyond the sequences' length; a batch "
       "with many more anchors than sequences (walks then share the device better); the typed front end's call.\n")
+    print_wrapped(out)
+
+
+def section_7n():
+    """§7n from profiles/minrun_marginals_bench.jsonl and, for the max walk's neighbours, profiles/minrun_bench.jsonl (``python
+    tools/measurements_md.py --section 7n``): appended to MEASUREMENTS.md behind §7m."""
+    rows = [json.loads(ln) for ln in open(os.path.join(P, "minrun_marginals_bench.jsonl")) if ln.strip()]
+    med = lambda t, name: t["kernel_us"][name]["median"]
+    t0 = rows[0]
+    out = []
+    A = out.append
+    A("### 7n. Marginals under a minimum run length: `gecco_crf_marginals_min_run` (`tools/bench_minrun.py --marginals`, "
+      "`minrun_marginals_bench.jsonl`)\n")
+    A(f"`Model.marginals_min_run` (DESIGN.md §4.9m) on §7l's batch: {t0['items']} items as {t0['sequences']} sequences of "
+      f"{t0['items'] // t0['sequences']}; weights N(0, 0.5); the label set is every label but label 0; `marg` and `inside` both asked for.  "
+      "No threshold was set: these are records.  Kernel times are begin-to-end durations from one `rocprofv3 --kernel-trace --stats` run "
+      "of its own (`--trace-pass --marginals`: per label count and minimum one warm-up call and three traced calls of `viterbi_min_run` "
+      "with log Z_C, then as many of `marginals_min_run`, nothing else); medians of the three, µs.  The sum-semiring launch of "
+      "`viterbi_min_run` is the parent commit's code path (the same source with the store compiled out), in the same run.  The pass is "
+      "the sum of the launches of a `marginals_min_run` call before its own two: the whole-contig forward-backward that every lattice "
+      "query runs first (gl_state keeps the raw state scores; its marginals are not brought back).\n")
+    A("| L | m | forward, sum, values kept | `gl_minrun_backward` | the two launches | `viterbi_min_run`'s forward, sum | two launches / "
+      "that | kept forward / plain forward | the pass | forward values |")
+    A("|---|---|---|---|---|---|---|---|---|---|")
+    for t in rows:
+        A(f"| {t['labels']} | {t['min_run']} | {med(t, 'gl_minrun_forward_sum_store'):.0f} | {med(t, 'gl_minrun_backward'):.0f} | "
+          f"{t['two_launches_us']:.0f} | {med(t, 'gl_minrun_forward_sum'):.0f} | {t['two_launches_over_forward_sum']:.2f} | "
+          f"{med(t, 'gl_minrun_forward_sum_store') / med(t, 'gl_minrun_forward_sum'):.2f} | {med(t, 'marginals_pass'):.0f} | "
+          f"{t['forward_value_bytes'] / 1e6:.1f} MB |")
+    A("")
+    lo = min(t["two_launches_over_forward_sum"] for t in rows)
+    hi = max(t["two_launches_over_forward_sum"] for t in rows)
+    big = rows[-1]
+    A("What the figures say, and what they do not:\n")
+    A(f"* **The call's two launches take {lo:.1f} to {hi:.1f} times the sum-semiring launch that exists without it** -- at or below the two "
+      "to three times that a second walk plus a stored and re-read workspace suggested.  The factor falls with the label count and the "
+      "minimum: the forward body reads two slots of every source at d = m, the transposed table of the backward walk has no such state, "
+      "so the backward launch is the cheaper of the two from m = 3 on.")
+    A(f"* **Keeping the forward values costs {100 * (min(med(t, 'gl_minrun_forward_sum_store') / med(t, 'gl_minrun_forward_sum') for t in rows) - 1):.0f} to "
+      f"{100 * (max(med(t, 'gl_minrun_forward_sum_store') / med(t, 'gl_minrun_forward_sum') for t in rows) - 1):.0f} %** of the forward launch; the workspace stream is "
+      f"far from binding: at L = {big['labels']} and m = {big['min_run']} the forward launch writes {big['forward_value_bytes'] / 1e6:.0f} MB in "
+      f"{med(big, 'gl_minrun_forward_sum_store') / 1e3:.1f} ms and the backward launch reads them in {med(big, 'gl_minrun_backward') / 1e3:.1f} ms, "
+      f"{big['forward_value_bytes'] / med(big, 'gl_minrun_forward_sum_store') / 1e3:.0f} and {big['forward_value_bytes'] / med(big, 'gl_minrun_backward') / 1e3:.0f} GB/s.  "
+      "Both walks are bound by the fp64 exponentials issued along a dependent walk (DESIGN.md §4.9m has the count), as §7l found for "
+      "the max walk's instruction issue.")
+    A("* The pass costs what it costs every lattice query and does not depend on the minimum.")
+    A("* Accuracy, from `tests/test_gpu_minrun_marginals.py` on an MI355X (30 cases, 9 s; the longest, the typed front end with a fit, "
+      "three predictions and three command lines, 5.5 s; the largest seam case, 8 labels at a minimum of 32, under a second): against the "
+      "forward-backward over the explicit expanded state list in `numpy.longdouble`, over L = 2, 3, 5, 8, 32 and m = 1, 2, 3, 32, the "
+      "fifteen seam lengths in one batch, three label sets and both weight families (N(0, 1), and N(0, 30) state scores with N(0, 10) "
+      "transitions), **the largest relative error of a marginal / bound was 0.0115** (a seam case at L = 2 and m = 2; 0.0109 against "
+      "enumeration's short sequences, 0.0023 with state scores of ±700 per item), the bound being expm1(3 (T + 1)(2 L + 8) ε max(1, M) + (m + 4) ε).  log Z_C was "
+      "bit-equal to `viterbi_min_run`'s in every case, `inside` with `marg` NULL had the bytes it has with both, and every contig run "
+      "alone had the bytes it has inside its batch.")
+    A("* Not measured: the call as a whole (plan build, upload, the allocation of the workspace, the downloads: 8 bytes a gene for "
+      "`inside`, 8 L more for `marg`), a minimum of 32 (the kernels' time grows about linearly in m, §7l), one long contig (the walks are "
+      "sequential), other label sets, counters of the new kernels, and the typed front end's call.\n")
+    A("Existing paths did not move.  The two instantiations of `gl_minrun_forward` that existed compile to the instruction streams they had "
+      "(the ISA of the parent's file and of this one compared function by function), and calls without the new entry run the launches "
+      "they ran: the whole GPU suite passes (2 178 cases with the 30 new ones, 280 s; 813 without a device).  `bench.py --gpus 1 --steps "
+      "1000 --warmup 100 --no-cpu-baseline --no-latency --no-past-l3 --no-levels --no-8d --no-c4` (the 2-label flagship, whose kernels are "
+      "untouched), the parent's tree and this one alternating on one box: parent 24.02, 24.13, 24.20 µs per step; change 24.02, 24.11, "
+      "24.08.\n")
+    print_wrapped(out)
+
+
+def print_wrapped(out):
     import textwrap
 
     wrapped = []
@@ -117,6 +185,8 @@ def main():
 
     if sys.argv[1:] == ["--section", "7m"]:
         return section_7m()
+    if sys.argv[1:] == ["--section", "7n"]:
+        return section_7n()
     c3, c3d = J("bench_c3_detail"), J("bench_c3_driver_command_detail")
     line = open(os.path.join(P, f"{TAG}_bench_c3_driver_command.json")).read().strip()
     c1, c2, c5, two = J("bench_c1_detail"), J("bench_c2_detail"), J("bench_c5_detail"), J("bench_c3_two_launch_detail")
