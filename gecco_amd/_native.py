@@ -115,6 +115,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
          _c_f64p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_run_counts": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
+         _c_f64p, _c_i8p, _c_f64p],
+    ),
     "gecco_crf_edge_posteriors": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_u32p, ctypes.c_int32, _c_f64p,
@@ -843,6 +848,34 @@ class Model:
             *head, values, allowed, set_mask, min_run, None if marg is None else _ptr(marg, _c_f64p),
             None if inside is None else _ptr(inside, _c_f64p), _ptr(ln_c, _c_f64p), _ptr(ln, _c_f64p)))
         return (None if marg is None else marg[:n - n0]), (None if inside is None else inside[:n - n0]), ln_c[:nc], ln[:nc]
+
+    def run_counts(self, contig_ptr, gene_ptr, attr_id, set_mask, max_runs, device=0, values=None, allowed=None,
+                   want_log_mass=True, want_paths=True, want_lognorm=True):
+        """How many maximal runs of labels of a set every contig holds, and the best path of every count
+        (``gecco_crf_run_counts``), 1 <= max_runs <= 32 = K; ``set_mask`` has bit y set when label y is in the set.  Returns
+        ``(log_mass, score, y, lognorm)``: ``log_mass`` float64 ``[n_contigs, K + 1]``, column k the log-mass of the paths with
+        exactly k runs and the last column that of the paths with at least K (None with ``want_log_mass=False``: the
+        sum-semiring launch does not run); ``score`` ``[n_contigs, K + 1]``, the left-to-right score of the best path of every
+        column, and ``y`` int8 ``[K + 1, n]``, its labels (both None with ``want_paths=False``: the max-semiring launch and the
+        backtrack do not run); ``lognorm`` ``[n_contigs]`` as ``marginals_full`` gives it (None with ``want_lognorm=False``).
+        A count that no path has gives ``-inf`` twice and -1 at every gene of its plane.  ``log_mass - logsumexp(log_mass,
+        axis=1)`` is log P(count | x); ``score - lognorm[:, None]`` a path's log-probability.  Either output has the same bytes
+        whether the other is asked for or not.  ``values`` and ``allowed`` as in ``marginals_full``.  A contig without genes
+        has 0 in column 0 of ``log_mass`` and ``score``, ``-inf`` in the others, and ``lognorm`` 0."""
+        max_runs, set_mask = operator.index(max_runs), operator.index(set_mask)
+        if not 0 <= set_mask < 1 << 32:
+            raise ValueError(f"run_counts: set_mask {set_mask} is outside 0 .. 2**32 - 1")
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        k1 = (max_runs if 1 <= max_runs <= 32 else 1) + 1  # (the library refuses any other max_runs: the buffers only need a size)
+        mass = np.zeros((max(nc, 1), k1), dtype=np.float64) if want_log_mass else None
+        score = np.zeros((max(nc, 1), k1), dtype=np.float64) if want_paths else None
+        y = np.zeros((k1, n - n0), dtype=np.int8) if want_paths else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_lognorm else None
+        _check(self._lib.gecco_crf_run_counts(
+            *head, values, allowed, set_mask, max_runs, None if mass is None else _ptr(mass, _c_f64p),
+            None if score is None else _ptr(score, _c_f64p), None if y is None or y.size == 0 else _ptr(y, _c_i8p),
+            None if ln is None else _ptr(ln, _c_f64p)))
+        return (None if mass is None else mass[:nc]), (None if score is None else score[:nc]), y, (None if ln is None else ln[:nc])
 
     def edge_posteriors(self, contig_ptr, gene_ptr, attr_id, sets=None, want_pair=False, want_transitions=True, want_entropy=True,
                         want_marginals=False, device=0, values=None, allowed=None):

@@ -950,7 +950,7 @@ int marginals_full_of_slice(const gecco_crf_model *m, int32_t device, const int3
     return gecco_crf_marginals_full(m, device, contigs.data(), n_contigs, rows.data(), attr_id ? attr_id + a0 : nullptr, marg, lognorm);
 }
 
-// One call of a lattice query -- region posteriors, sampled paths, the K best paths, edge posteriors, minimum-run decoding.  The batch goes to the device on a plan laid
+// One call of a lattice query -- region posteriors, sampled paths, the K best paths, edge posteriors, minimum-run decoding, run counts.  The batch goes to the device on a plan laid
 // out with `lattice`: the marginals at out(0), per_gene1 bytes a gene at out(1), log Z and then per_contig_more bytes a contig at
 // out(2).  `run(b)` is the entry's part: its plan_run_* call and the fetch of its own outputs; of a batch without genes (b.n == 0:
 // nothing is on the device, and log Z = 0 is written by then) it only fills what else the entry returns.  marg / lognorm (either
@@ -1306,6 +1306,51 @@ GECCO_API int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t devi
         rc = batch_fetch(rc, marg, d_marg, size_t(b.n) * L * 8, "download marginals under the constraint");
         rc = batch_fetch(rc, inside, d_inside, size_t(b.n) * 8, "download inside");
         return batch_fetch(rc, lognorm_min_run, d_lognorm_mr, nc * 8, "download lognorm_min_run");
+    });
+    GECCO_GUARD_END
+}
+
+// ---- run counts (ABI 2.23.0): for k = 0 .. max_runs, the log-mass of the paths with exactly k runs of labels of a set (at
+// k = max_runs: at least that many), and the best such path with its score, on a lattice expanded by a saturating run counter
+// behind gl_state; log Z from the whole-contig marginals pass (crf_counts.hip)
+GECCO_API int gecco_crf_run_counts(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                   const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value, const uint32_t *allowed,
+                                   uint32_t set_mask, int32_t max_runs, double *log_mass, double *score, int8_t *y, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    if (max_runs < 1 || max_runs > kMaxRunCounts)
+        return fail("run_counts: max_runs = " + std::to_string(max_runs) + " is outside 1 .. 32");
+    if ((rc = check_label_set("run_counts: set_mask", 0, set_mask, m->m.L))) return rc;
+    if (y && !score) return fail("run_counts: y is given without score");
+    if (!log_mass && !score) return fail("run_counts: log_mass, score and y are all NULL");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    const size_t nc = size_t(n_contigs), K1 = size_t(max_runs) + 1;
+    const double ninf = -std::numeric_limits<double>::infinity();
+    // per gene: the K + 1 paths, if asked for.  Per contig, behind log Z: K + 1 log-masses, K + 1 scores.  (The marginals are the
+    // pass's own output and are not returned.)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, score ? K1 : 0, 2 * K1 * 8, nullptr,
+                        lognorm, [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: every contig's one path is the empty one, which has no run -- gecco_crf_viterbi's score)
+            for (size_t i = 0; i < nc * K1; ++i) {
+                if (log_mass) log_mass[i] = i % K1 ? ninf : 0.0;
+                if (score) score[i] = i % K1 ? ninf : 0.0;
+            }
+            return int(GECCO_CRF_OK);
+        }
+        double *d_lognorm = b.out<double>(2), *d_mass = d_lognorm + nc, *d_score = d_mass + nc * K1;
+        DeviceBlock<char> ws;
+        int rc = score ? ws.alloc(counts_back_bytes(b.n, m->m.L, max_runs), "hipMalloc run-count back-pointers") : GECCO_CRF_OK;
+        if (rc) return rc;
+        rc = batch_wait(plan_run_run_counts(b.plan, b.csr, set_mask, max_runs, score ? reinterpret_cast<uint8_t *>(ws.get()) : nullptr,
+                                            log_mass ? d_mass : nullptr, score ? d_score : nullptr,
+                                            score ? b.out<int8_t>(1) : nullptr, b.out<double>(0), d_lognorm, nullptr),
+                        "run counts");
+        rc = batch_fetch(rc, log_mass, d_mass, nc * K1 * 8, "download log_mass");
+        rc = batch_fetch(rc, score, d_score, nc * K1 * 8, "download score");
+        return batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n) * K1, "download paths");
     });
     GECCO_GUARD_END
 }

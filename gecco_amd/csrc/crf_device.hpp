@@ -396,6 +396,19 @@ size_t minrun_forward_bytes(int64_t n_genes, int32_t L, int32_t min_run);
 hipError_t launch_gen_min_run_marginals(const GenArgs &a, uint32_t set_mask, int32_t min_run, double *fwd, double *marg,
                                         double *inside, double *lognorm_min_run, hipStream_t stream);
 
+// ---- run counts (crf_counts.hip) ----
+constexpr int32_t kMaxRunCounts = 32;  // K of one call: a column of LDS is 33 doubles
+// the max semiring's own workspace: back-pointers, one byte per (gene, label, slot), K + 1 slots
+size_t counts_back_bytes(int64_t n_genes, int32_t L, int32_t max_runs);
+// For every contig c and k = 0 .. K (K = max_runs): log_mass[c][k] (null: the sum-semiring launch does not run) = the log-mass of
+// the paths with exactly k maximal runs of labels in set_mask, at k = K with at least K; score[c][k] (null: neither the
+// max-semiring launch nor the backtrack runs) the score of the best such path and plane k of y [K + 1][n_genes] its labels.  A
+// class without a path has -infinity twice and -1 at every gene of its plane; a contig without genes 0 at k = 0, -infinity at the
+// other slots.  On the lattice of the gl_state launch that ran before it on the same stream with a.state non-null: reads a.state,
+// a.trans, a.contig_ptr and a.n_genes.  The caller has checked that set_mask has a bit, and none at or above L.
+hipError_t launch_gen_run_counts(const GenArgs &a, uint32_t set_mask, int32_t max_runs, uint8_t *back, double *log_mass,
+                                 double *score, int8_t *y, hipStream_t stream);
+
 // ---- edge posteriors (crf_edges.hip) ----
 constexpr int32_t kMaxEdgeSets = 32;   // label sets of one call
 constexpr int32_t kEdgeRunGenes = 32;  // genes of a run: what one group of lanes walks, counted from its contig's first gene

@@ -1442,6 +1442,26 @@ int plan_run_marginals_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask,
                      "min-run marginals launch");
 }
 
+int plan_run_run_counts(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t max_runs, uint8_t *d_back, double *d_log_mass,
+                        double *d_score, int8_t *d_y, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    if (max_runs < 1 || max_runs > kMaxRunCounts) {
+        set_error("max_runs outside 1 .. 32");
+        return GECCO_CRF_EINVAL;
+    }
+    const int32_t L = p.model ? p.model->L : 32;  // (a plan that was never built is check_plan's to refuse)
+    if (set_mask == 0 || (L < 32 && (set_mask >> L))) {
+        set_error("set_mask is empty, or holds a label at or above num_labels");
+        return GECCO_CRF_EINVAL;
+    }
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !d_marg || (!d_log_mass && !d_score) || (d_score && (!d_back || !d_y)), rc))
+        return rc;
+    GenArgs g;  // (the pass gives log Z; the run-counter recursion reads the raw state scores and nothing else)
+    if ((rc = run_lattice(p, csr, "run counts", true, d_marg, d_lognorm, stream, g))) return rc;
+    return check_hip(launch_gen_run_counts(g, set_mask, max_runs, d_back, d_log_mass, d_score, d_y, stream), "run-count launch");
+}
+
 int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, double *d_marg, double *d_lognorm, hipStream_t stream) {
     if (q.n_sets < 0 || q.n_sets > kMaxEdgeSets || (q.n_sets == 0 && (q.enter || q.leave))) {
         set_error("the number of label sets is outside 1 .. 32 (0 without enter and leave)");

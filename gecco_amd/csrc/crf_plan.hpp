@@ -166,7 +166,7 @@ struct Plan {
     // (DeviceCsr::allowed), which is refused when it brings masks to a layout without `masked`, or none to one with it.
     bool masked = false;
     // Lattice queries (plan_run_span_probabilities, plan_run_sample_paths, plan_run_viterbi_kbest, plan_run_edge_posteriors,
-    // plan_run_viterbi_min_run, plan_run_run_posteriors, plan_run_marginals_min_run).  `lattice` is
+    // plan_run_viterbi_min_run, plan_run_run_posteriors, plan_run_marginals_min_run, plan_run_run_counts).  `lattice` is
     // set by the owner before plan_build: the layout takes the any-L kernels at every label count, as `valued` and `masked` do --
     // the queries' kernels read the forward vectors and raw state scores of their workspace, which a 2-label plan does not have
     // otherwise.  Nothing else changes: reference-bits mode is decided as ever.
@@ -249,6 +249,13 @@ int plan_run_viterbi_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, i
 // d_inside [n_genes] or null, at least one of the two.  Not chunked.  All on `stream`.
 int plan_run_marginals_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t min_run, double *d_fwd, double *d_marg_min_run,
                                double *d_inside, double *d_lognorm_min_run, double *d_marg, double *d_lognorm, hipStream_t stream);
+// Run counts, a plan laid out with `lattice`: the whole-contig marginals of the batch as above (d_marg, d_lognorm), then the
+// recursion on the lattice expanded by a saturating run counter (crf_counts.hip): d_log_mass [n_contigs][K + 1] or
+// null (the sum-semiring launch does not run); d_score [n_contigs][K + 1] or null (the max-semiring launch and the backtrack do
+// not run) with d_y [K + 1][n_genes] and the workspace d_back (counts_back_bytes); at least one of the two.  Not chunked.  All
+// on `stream`.
+int plan_run_run_counts(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t max_runs, uint8_t *d_back, double *d_log_mass,
+                        double *d_score, int8_t *d_y, double *d_marg, double *d_lognorm, hipStream_t stream);
 // Edge posteriors of a plan laid out with `lattice`: the whole-contig marginals of the batch exactly as plan_run_marginals_full
 // runs them (d_marg [n_genes][L], d_lognorm [n_contigs] or null), then the edge marginals and their sums that `q` asks for
 // (crf_edges.hip; crf_device.hpp: EdgeQuery -- device pointers throughout, the run table that of this layout's contigs), all on

@@ -557,6 +557,76 @@ class SequenceCRF:
                         "constraint_log_probability": float(lognorm_c[s] - lognorm[s])})
         return out
 
+    # ---- run counts: how many runs a sequence holds, and the best path of every count (``_native.Model.run_counts``)
+    @staticmethod
+    def _max_runs(max_runs) -> int:
+        try:
+            max_runs = operator.index(max_runs)
+        except TypeError:
+            raise ValueError(f"max_runs is an integer, got {max_runs!r}") from None
+        if not 1 <= max_runs <= 32:
+            raise ValueError(f"max_runs = {max_runs} is outside 1 .. 32")
+        return max_runs
+
+    def run_count_log_probability(self, X, labels, max_runs, allowed=None) -> np.ndarray:
+        """The distribution of the NUMBER of runs: float64 ``[n_seqs, max_runs + 1]``, column k the log-probability that the
+        sequence holds exactly k maximal runs of consecutive items carrying a label of ``labels`` (a label, or a ``set`` /
+        ``frozenset`` / ``list`` / ``tuple`` of labels; the labels inside a run may differ; runs at either end of the sequence
+        count), and the last column log P(at least ``max_runs`` runs).  ``expected_runs`` is the mean of this distribution and
+        says nothing else of it: a mean of 1.0 can be "certainly one" or a coin flip between none and two.  Column 0 is the
+        probability that the sequence holds no such item at all.  Exact, on the whole-sequence lattice (that of ``predict`` and
+        ``predict_marginals``): one forward-backward pass and one walk over ``X`` on the lattice expanded by a run counter,
+        one native call.  A row is normalised by the walk's own total, so its exponentials sum to 1 to rounding; a count that
+        no path has is ``-inf``.  With ``allowed`` (as in ``predict``) everything is on the restricted lattice.  A sequence
+        without items has no run: 0 in column 0.  Raises ``ValueError`` before any device call for an unknown label, an empty
+        set, and a ``max_runs`` that is not an integer or lies outside 1 .. 32."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = self._label_bits("run_count_log_probability", labels)
+        max_runs = self._max_runs(max_runs)
+        n_seqs = len(seq_ptr) - 1
+        if seq_ptr[-1] == 0:
+            out = np.full((n_seqs, max_runs + 1), -np.inf)
+            out[:, 0] = 0.0
+            return out
+        mass, _, _, _ = self._model.run_counts(seq_ptr, item_ptr, attr, bits, max_runs, device=self.device, values=values,
+                                               allowed=masks, want_paths=False, want_lognorm=False)
+        top = mass.max(axis=1, keepdims=True)  # (finite: every sequence has a path)
+        return mass - (top + np.log(np.exp(mass - top).sum(axis=1, keepdims=True)))
+
+    def run_count_probability(self, X, labels, max_runs, allowed=None) -> np.ndarray:
+        """``exp`` of ``run_count_log_probability``: column k is P(exactly k runs), the last column P(at least ``max_runs``)."""
+        return np.exp(self.run_count_log_probability(X, labels, max_runs, allowed=allowed))
+
+    def predict_run_counts(self, X, labels, max_runs, allowed=None) -> List[Dict[str, object]]:
+        """The best label path of every sequence for every number of runs: among the paths with exactly k maximal runs of items
+        carrying a label of ``labels``, k = 0 .. ``max_runs`` - 1, and among those with at least ``max_runs`` (``labels``,
+        ``max_runs`` and ``allowed`` as in ``run_count_log_probability``).  The best path with exactly one run is not
+        ``predict``'s path with its surplus runs deleted or merged by hand.  Per sequence a dict with ``paths``: ``max_runs +
+        1`` entries, each a list of label names, or None where no path has that count (more runs than ``ceil(n_items / 2)``,
+        none when every label is in the set, or ``allowed`` forbids it); ``scores``: float64 ``[max_runs + 1]``, ``-inf`` without
+        a path; ``log_probabilities``: ``score - log Z``, the exact ``log p(y | x)`` of each path.  The best of the ``max_runs +
+        1`` scores is ``predict``'s path's.  Ties go by the kernel's scan order over run-counter states (include/gecco_crf.h).
+        One forward-backward pass and one walk over ``X``, one native call.  A sequence without items has the empty path in
+        entry 0.  Raises the ``ValueError`` s of ``run_count_log_probability``, before any device call."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = self._label_bits("predict_run_counts", labels)
+        max_runs = self._max_runs(max_runs)
+        n_seqs = len(seq_ptr) - 1
+        if seq_ptr[-1] == 0:
+            first = np.full(max_runs + 1, -np.inf)
+            first[0] = 0.0
+            return [{"paths": [[]] + [None] * max_runs, "scores": first.copy(), "log_probabilities": first.copy()} for _ in range(n_seqs)]
+        _, score, y, lognorm = self._model.run_counts(seq_ptr, item_ptr, attr, bits, max_runs, device=self.device, values=values,
+                                                      allowed=masks, want_log_mass=False)
+        out = []
+        for s in range(n_seqs):
+            b, e = int(seq_ptr[s]), int(seq_ptr[s + 1])
+            paths = [[self.classes_[c] for c in y[k, b:e].tolist()] if score[s, k] > -np.inf else None for k in range(max_runs + 1)]
+            out.append({"paths": paths, "scores": score[s].copy(), "log_probabilities": score[s] - lognorm[s]})
+        return out
+
     # ---- edge posteriors: the pairwise marginals of the whole-sequence lattice and their sums (``_native.Model.edge_posteriors``)
     def _edges(self, X, allowed, sets=None, **want):
         """One pass over ``X`` for the edge outputs ``want`` names: ``(seq_ptr, masks of sets, the native call's dict)``, the dict

@@ -121,6 +121,18 @@ is shorter than M); every path cluster gains ``average_p``, ``max_p`` and ``min_
 appends the three columns to ``path_clusters.tsv`` and writes ``path_genes.tsv`` (columns ``sequence_id, protein_id, path_label,
 p``).  Without the flag every table and every launch is what it is today.
 
+Cluster counts (``predict_cluster_counts(genes, max_clusters=K)``, ``predict --cluster-counts K``, 1 <= K <= 32).  How many
+clusters does a contig hold, and how sure is the model of that number?  ``expected_clusters`` of ``sequences.tsv`` is the mean of
+the distribution and nothing else: 1.0 can be "certainly one" or a coin flip between none and two.  One whole-contig call
+(``_native.Model.run_counts``: a sum-product recursion on the lattice expanded by a saturating run counter, with the set of
+every label but the background) gives ``cluster_counts_``, one row per contig: ``sequence_id``, ``genes``, ``p_0 .. p_{K-1}``
+= P(exactly k clusters | x), ``p_ge_K`` = P(at least K), and ``map_clusters``, the arg max over 0 .. K (the smaller on a tie; K
+stands for "K or more").  ``p_0`` is the exact P(no cluster).  ``predict_count_clusters(genes, n_clusters=N)``
+(``predict --exact-clusters N``, 0 <= N <= 31) is the decoding counterpart, for a user who knows how many clusters a record
+holds (a MIBiG-style record holds one): the runs of the best whole-contig label path AMONG THOSE with exactly N runs of cluster
+labels, which is not the free path with surplus runs deleted or merged by hand.  The command line writes ``cluster_counts.tsv``
+and ``count_clusters.tsv`` (``path_clusters.tsv``'s columns); without the flags every table and every launch is what it is today.
+
 Run as ``python -m gecco_amd.typed train --genes G.tsv --features F.tsv --clusters C.tsv -o DIR`` and
 ``python -m gecco_amd.typed predict --model DIR --genes G.tsv --features F.tsv -o OUT``.
 """
@@ -143,7 +155,8 @@ from . import tables
 
 __all__ = ["BACKGROUND", "MIXED", "UNKNOWN", "MAX_CLUSTER_LABELS", "TypedClusterCRF", "cluster_labels", "fold_labels",
            "gene_labels", "label_type_names", "type_probabilities", "type_of", "typed_cluster_table", "write_alternatives",
-           "write_sequences", "write_path_clusters", "write_path_genes", "write_paths", "build_parser", "main"]
+           "write_sequences", "write_path_clusters", "write_path_genes", "write_paths", "count_columns", "write_cluster_counts",
+           "build_parser", "main"]
 
 BACKGROUND = "0"
 MIXED = "Mixed"
@@ -821,6 +834,106 @@ class TypedClusterCRF:
                 self.path_posteriors_[name].append(value)
         return clusters
 
+    def _whole_contigs(self, genes: Iterable[Any], known: Optional[tables.ClusterTable]):
+        """``(contigs, CSR arrays, known masks or None)`` of the caller's genes sorted by (sequence, start), for a whole-contig
+        call; ``(contigs, None, None)`` without genes."""
+        from . import packing
+
+        genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
+        for gene in genes:
+            gene.protein.domains.sort(key=operator.attrgetter("start"))
+        contigs = [list(g) for _, g in itertools.groupby(genes, key=operator.attrgetter("source.id"))]
+        if not genes:
+            return contigs, None, None
+        batch = packing.pack_contigs(contigs, self._attr_index, "protein")
+        allowed = None
+        if known is not None:
+            from .train_cli import join_clusters
+
+            allowed = known_masks(len(genes), known, join_clusters(genes, known, device=self.device), self.classes_, self.background)
+        return contigs, (batch.item_ptr.astype(np.int32), batch.attr_ptr.astype(np.int32), batch.attr_id), allowed
+
+    def _cluster_set(self) -> int:
+        """The mask of every label but the background."""
+        return ((1 << len(self.classes_)) - 1) & ~(1 << self.classes_.index(self.background))
+
+    def predict_cluster_counts(self, genes: Iterable[Any], max_clusters: int = 8,
+                               known: Optional[tables.ClusterTable] = None) -> Dict[str, List[Any]]:
+        """How many clusters every contig holds, as a distribution (module docstring): one ``run_counts`` call over all contigs
+        with the set of every label but the background, sum semiring only.  Fills and returns ``cluster_counts_``, the
+        per-contig columns ``count_columns(max_clusters)``: ``sequence_id``, ``genes``, ``p_0 .. p_{K-1}`` = P(exactly k maximal
+        runs of genes with a cluster label | x), ``p_ge_K`` = P(at least K), K = ``max_clusters``, and ``map_clusters``, the arg
+        max over 0 .. K, the smaller winning a tie.  A row is normalised by the recursion's own total: it sums to 1 to
+        rounding.  A run counts genes of any length, annotated or not; no threshold and no refiner is applied.  ``known``
+        restricts the lattice as in the other prediction methods.  ``ValueError`` before any device call for a
+        ``max_clusters`` that is not an integer or lies outside 1 .. 32."""
+        try:
+            max_clusters = operator.index(max_clusters)
+        except TypeError:
+            raise ValueError(f"max_clusters is an integer, got {max_clusters!r}") from None
+        if not 1 <= max_clusters <= 32:
+            raise ValueError(f"max_clusters = {max_clusters} is outside 1 .. 32")
+        model = self._fitted()
+        names = count_columns(max_clusters)
+        self.cluster_counts_ = {name: [] for name in names}
+        contigs, csr, allowed = self._whole_contigs(genes, known)
+        if csr is None:
+            return self.cluster_counts_
+        mass, _, _, _ = model.run_counts(*csr, self._cluster_set(), max_clusters, device=self.device, allowed=allowed,
+                                         want_paths=False, want_lognorm=False)
+        top = mass.max(axis=1, keepdims=True)
+        p = np.exp(mass - (top + np.log(np.exp(mass - top).sum(axis=1, keepdims=True))))
+        for ci, contig in enumerate(contigs):
+            row = (contig[0].source.id, int(csr[0][ci + 1] - csr[0][ci]), *p[ci].tolist(), int(np.argmax(p[ci])))
+            for name, value in zip(names, row):
+                self.cluster_counts_[name].append(value)
+        return self.cluster_counts_
+
+    def predict_count_clusters(self, genes: Iterable[Any], n_clusters: int = 1,
+                               known: Optional[tables.ClusterTable] = None) -> List[Any]:
+        """Clusters as the runs of the best whole-contig label path AMONG THOSE with exactly ``n_clusters`` maximal runs of genes
+        with a label other than the background (module docstring): plane ``n_clusters`` of one ``run_counts`` call with K =
+        ``n_clusters + 1``, max semiring only.  The clusters are what ``predict_path_clusters`` returns for its path: ids
+        ``{sequence}_cluster_{number}``, the caller's genes, ``type`` from the run's most frequent label (the smaller label id
+        on ties) and ``path_type``.  A contig on which no path has that many runs (fewer than ``2 n_clusters - 1`` genes, or
+        ``known`` forbids it) gives no cluster.  ``count_scores_`` holds per contig the path's score (``-inf`` without a path).
+        ``ValueError`` before any device call for an ``n_clusters`` that is not an integer or lies outside 0 .. 31."""
+        try:
+            n_clusters = operator.index(n_clusters)
+        except TypeError:
+            raise ValueError(f"n_clusters is an integer, got {n_clusters!r}") from None
+        if not 0 <= n_clusters <= 31:
+            raise ValueError(f"n_clusters = {n_clusters} is outside 0 .. 31")
+        from .refine import _cluster_class
+        from .types import _cluster_type_factory
+
+        model = self._fitted()
+        self.count_scores_ = []
+        contigs, csr, allowed = self._whole_contigs(genes, known)
+        if csr is None:
+            return []
+        _, score, y, _ = model.run_counts(*csr, self._cluster_set(), n_clusters + 1, device=self.device, allowed=allowed,
+                                          want_log_mass=False, want_lognorm=False)
+        L = len(self.classes_)
+        bg = self.classes_.index(self.background)
+        Cluster = _cluster_class()
+        clusters: List[Any] = []
+        for ci, contig in enumerate(contigs):
+            c0, c1 = int(csr[0][ci]), int(csr[0][ci + 1])
+            self.count_scores_.append(float(score[ci, n_clusters]))
+            if not score[ci, n_clusters] > -np.inf:
+                continue
+            path = y[n_clusters, c0:c1].astype(np.int64)
+            inside = np.concatenate([[False], path != bg, [False]])
+            edges = np.flatnonzero(inside[1:] != inside[:-1])
+            for found, (a, b) in enumerate(zip(edges[::2].tolist(), edges[1::2].tolist()), 1):
+                cluster = Cluster(f"{contig[0].source.id}_cluster_{found}", list(contig[a:b]))
+                major = int(np.argmax(np.bincount(path[a:b], minlength=L)))
+                cluster.type = _cluster_type_factory(cluster)(self.label_types_[major])
+                cluster.path_type = ";".join(self.label_types_[major]) or UNKNOWN
+                clusters.append(cluster)
+        return clusters
+
     def predict_genes_and_clusters(self, genes: Iterable[Any], *, threshold: float = 0.8, n_cds: int = 3, edge_distance: int = 0,
                                    trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                                    region_posteriors: bool = False, boundary_samples: int = 0,
@@ -963,6 +1076,21 @@ def write_paths(path, columns) -> None:
             out.write("\t".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
 
 
+def count_columns(max_clusters: int) -> Tuple[str, ...]:
+    """The columns of ``cluster_counts_`` / ``cluster_counts.tsv`` at K = ``max_clusters``: ``sequence_id, genes, p_0 .. p_{K-1},
+    p_ge_K, map_clusters``."""
+    return ("sequence_id", "genes", *(f"p_{k}" for k in range(max_clusters)), f"p_ge_{max_clusters}", "map_clusters")
+
+
+def write_cluster_counts(path, columns: Dict[str, Sequence[Any]]) -> None:
+    """``cluster_counts.tsv``: one row per contig, the columns of ``cluster_counts_`` in their order; floats with ``repr``."""
+    names = list(columns)
+    with open(path, "w") as out:
+        out.write("\t".join(names) + "\n")
+        for row in zip(*(columns[name] for name in names)):
+            out.write("\t".join(repr(v) if isinstance(v, float) else str(v) for v in row) + "\n")
+
+
 def write_sequences(path, columns: Dict[str, Sequence[Any]]) -> None:
     """``sequences.tsv``: one row per contig, columns ``TypedClusterCRF.SEQUENCE_COLUMNS`` (``sequence_posteriors_``); floats
     with ``repr``."""
@@ -1040,6 +1168,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --path-clusters M: add average_p, max_p and min_p to path_clusters.tsv, of the probability that a "
                     "gene lies in a region given that no region has fewer than M genes; write path_genes.tsv, that probability "
                     "per gene")
+    pr.add_argument("--cluster-counts", type=int, default=None, metavar="K",
+                    help="write cluster_counts.tsv: per contig the exact whole-contig probability that it holds 0, 1, ... K - 1 "
+                    "clusters and at least K (at most 32), and the most probable number")
+    pr.add_argument("--exact-clusters", type=int, default=None, metavar="N",
+                    help="write count_clusters.tsv: the regions of the best whole-contig label path among those with exactly N (at "
+                    "most 31) regions")
     pr.add_argument("--device", type=int, default=0)
     pr.add_argument("-o", "--output-dir", default=".", help="directory of the output tables")
     return ap
@@ -1065,6 +1199,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise ValueError(f"--path-clusters {args.path_clusters} is outside 1 .. 32")
     if args.path_marginals and args.path_clusters is None:
         raise ValueError("--path-marginals needs --path-clusters M")
+    if args.cluster_counts is not None and not 1 <= args.cluster_counts <= 32:
+        raise ValueError(f"--cluster-counts {args.cluster_counts} is outside 1 .. 32")
+    if args.exact_clusters is not None and not 0 <= args.exact_clusters <= 31:
+        raise ValueError(f"--exact-clusters {args.exact_clusters} is outside 0 .. 31")
     crf = TypedClusterCRF.trained(args.model, device=args.device)
     genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
     annotated, found = crf.predict_genes_and_clusters(genes, threshold=args.threshold, n_cds=args.cds,
@@ -1094,6 +1232,14 @@ def main(argv: Optional[List[str]] = None) -> int:
         if args.path_marginals:
             write_path_genes(os.path.join(args.output_dir, "path_genes.tsv"), crf.path_genes_)
         write_paths(os.path.join(args.output_dir, "paths.tsv"), crf.path_posteriors_)
+    if args.cluster_counts is not None or args.exact_clusters is not None:
+        known = None if args.known is None else tables.ClusterTable.load(args.known)
+        if args.cluster_counts is not None:
+            write_cluster_counts(os.path.join(args.output_dir, "cluster_counts.tsv"),
+                                 crf.predict_cluster_counts(genes, max_clusters=args.cluster_counts, known=known))
+        if args.exact_clusters is not None:
+            write_path_clusters(os.path.join(args.output_dir, "count_clusters.tsv"),
+                                crf.predict_count_clusters(genes, n_clusters=args.exact_clusters, known=known))
     print(f"predict: {len(annotated)} genes, {len(found)} clusters -> {args.output_dir}", file=sys.stderr)
     return 0
 

@@ -52,7 +52,7 @@ const char *gecco_crf_last_error(void);
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
- * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run. */
+ * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -952,6 +952,59 @@ int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t device, const 
                                 const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
                                 double *marg /* [n_genes][L] or NULL */, double *inside /* [n_genes] or NULL */,
                                 double *lognorm_min_run /* [n_contigs] */, double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- run counts (ABI 2.23.0, additive; gecco_crf_version() stays 340) --------------------------------------------------------------
+ * How many runs a contig holds, and the best path with a given number of them, on the whole-contig lattice of gecco_crf_viterbi
+ * and gecco_crf_marginals_full (not a windowed one).  set_mask names a label set S (bit y set: label y is inside; S may be every
+ * label).  N_S(y) is the number of maximal runs of consecutive genes whose labels lie in S; runs that touch the contig's first or
+ * last gene count like any other, and the labels inside a run may differ from gene to gene (gecco_crf_viterbi_min_run's notion
+ * of a run).  With K = max_runs, for every contig c and k = 0 .. K:
+ *     log_mass[c][k] = the log of the summed exp(score) over the paths with N_S = k for k < K, and with N_S >= K for k = K (the
+ *                      saturating tail slot);
+ *     score[c][k]    = the score of the best such path, and plane k of y its labels.
+ * log P(N_S = k | x) = log_mass[c][k] - LSE over k' of log_mass[c][k']: normalised by the recursion's own total the probabilities
+ * sum to 1 to rounding, and that total equals lognorm to rounding.  exp(score[c][k] - lognorm[c]) is the path's probability.
+ * The best path with exactly one run is not the free Viterbi path with its surplus runs deleted, or with two runs merged by
+ * hand.  With `allowed` (one mask per gene, as the *_constrained entries take them) a path with a disallowed label does not exist,
+ * and lognorm is the restricted log Z.  attr_value and allowed may each be NULL.  The walk is parallel over contigs and labels and
+ * sequential along a contig (contigs are not chunked).
+ *   * The recursion runs on the lattice expanded by a run counter c = min(runs begun up to and including this gene, K).  A label
+ *     outside S has the states (j, c), c = 0 .. K; a label inside S has (j, c), c = 1 .. K; states are ordered by label, then by
+ *     c.  At gene 0 (j outside, 0) and (j inside, 1) start at state_0[j], the others at -infinity.  The sources of a destination
+ *     at gene t: (j, c) with j outside S -- (i, c) for every label i; (j, c) with j inside S -- (i, c) for i inside S, (i, c - 1)
+ *     for i outside S, and at c = K also (i, K) for i outside S (the counter saturates).  At the contig's end every state is
+ *     admissible, and slot k collects the states (., k) of every label.
+ *   * Max semiring: value = (delta[source] + trans[i][j]) + state_t[j] -- the operation order of gecco_crf_viterbi and
+ *     gecco_crf_viterbi_min_run, so a score is the left-to-right sum of the path's terms, every addition rounded on its own.
+ *     The largest of a contig's K + 1 scores has the bits of gecco_crf_viterbi_kbest's rank 0.
+ *   * The tie rule is operational.  A destination scans its sources in ascending (source label, source slot) order with a strict
+ *     `>` update; at the end the smaller label wins a tie within a slot.  This is a rule on expanded states and NOT "reversed
+ *     path ascending" (at the tail slot two expanded states stand for one label).
+ *   * Sum semiring: the same sources with a max-shifted log-sum-exp in place of the max, fp64 throughout; a destination all of
+ *     whose sources are -infinity stays -infinity.
+ *   * The sum launch runs only when log_mass is given; the max launch and the backtrack run only when score is given.  Asking
+ *     for one changes no byte of the other.
+ *   * Infeasible counts (k > ceil(T / 2) on a contig of T genes, k = 0 when S is every label, masks that forbid it): log_mass
+ *     -infinity, score -infinity, label -1 at every gene of that plane; never NaN.
+ *   * Outputs.  log_mass and score are double [n_contigs][K + 1], each optional; y is int8 [K + 1][n_genes] (plane k at
+ *     y + k * n_genes), optional with score; lognorm [n_contigs] (optional) is the bytes gecco_crf_marginals_full (or its
+ *     _valued / _constrained sibling, by the arguments given) writes for the batch.  (A 2-label model without values and masks
+ *     has kernels of its own for that: asking for lognorm there costs a second pass.)  A contig without genes gets
+ *     log_mass[c][0] = 0 and score[c][0] = 0, gecco_crf_viterbi's convention, -infinity at every other slot, and 0 for lognorm.
+ *     contig_ptr[0] > 0 works as in the other one-shots.  The back-pointers are workspace of n_genes * L * (K + 1) bytes, one
+ *     byte per (gene, label, slot): the source label and one bit "the source slot was K, not K - 1"; sizes are computed in
+ *     size_t; a failed allocation is GECCO_CRF_ENOMEM.  Equal calls give equal bytes (no atomics).
+ *   * Limits: 1 <= max_runs <= 32 and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL, every message prefixed "run_counts:": max_runs
+ *     outside 1 .. 32 ("run_counts: max_runs = ... is outside 1 .. 32"), a set_mask of 0 or with a bit at or above num_labels,
+ *     y given without score, log_mass, score and y all NULL.  The checks of the *_valued and *_constrained entries apply to
+ *     attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_run_counts(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                         const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                         const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t max_runs,
+                         double *log_mass /* [n_contigs][K + 1] or NULL */, double *score /* [n_contigs][K + 1] or NULL */,
+                         int8_t *y /* [K + 1][n_genes] or NULL */, double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- run posteriors (ABI 2.21.0, additive; gecco_crf_version() stays 340) --------------------------------------------------------
  * The exact distribution of where a run starts and ends, on the whole-contig lattice of gecco_crf_marginals_full and

@@ -2,7 +2,7 @@
 """profiles/MEASUREMENTS.md from the committed records of the round (profiles/r06_*): every number in that file is read from the
 file it names, so the document cannot drift from the records.   usage: python tools/measurements_md.py > profiles/MEASUREMENTS.md
 (the head of the file, §1 to §7); python tools/measurements_md.py --section 7m prints §7m from profiles/runs_bench.jsonl,
---section 7n prints §7n from profiles/minrun_marginals_bench.jsonl."""
+--section 7n prints §7n from profiles/minrun_marginals_bench.jsonl, --section 7o prints §7o from profiles/counts_bench.jsonl."""
 import json
 import os
 import re
@@ -167,6 +167,64 @@ def section_7n():
     print_wrapped(out)
 
 
+def section_7o():
+    """§7o from profiles/counts_bench.jsonl (``python tools/measurements_md.py --section 7o``): appended to MEASUREMENTS.md behind
+    §7n."""
+    rows = [json.loads(ln) for ln in open(os.path.join(P, "counts_bench.jsonl")) if ln.strip()]
+    med = lambda t, name: t["kernel_us"][name]["median"]
+    t0 = rows[0]
+    out = []
+    A = out.append
+    A("### 7o. Run-count posteriors: `gecco_crf_run_counts` (`tools/bench_counts.py`, `counts_bench.jsonl`)\n")
+    A(f"`Model.run_counts` (DESIGN.md §4.9n) on §7l's batch: {t0['items']} items as {t0['sequences']} sequences of "
+      f"{t0['items'] // t0['sequences']}; weights N(0, 0.5); the label set is every label but label 0; `log_mass`, `score` and `y` all asked "
+      "for.  No threshold was set: these are records, and nobody had measured this kernel before.  Kernel times are begin-to-end durations "
+      "from one `rocprofv3 --kernel-trace --stats` run of its own (`--trace-pass`: per label count and K one warm-up call and three traced "
+      "calls of `run_counts`, then as many of `viterbi_min_run` with log Z_C, nothing else); medians of the three, µs.  The comparison is "
+      "`viterbi_min_run` at a minimum of K + 1, which gives its lanes the same K + 1 slots a gene -- except at K = 32, where K + 1 = 33 is "
+      "beyond that entry's range and the minimum is 32: 33 slots against 32.\n")
+    A("| L | K | slots | `gl_counts_forward`, sum | `gl_counts_forward`, max | `gl_counts_backtrack` | min-run m | `gl_minrun_forward`, sum | "
+      "`gl_minrun_forward`, max | `gl_minrun_backtrack` | sum / min-run sum | max / min-run max | back-pointers |")
+    A("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for t in rows:
+        A(f"| {t['labels']} | {t['max_runs']} | {t['slots']} | {med(t, 'gl_counts_forward_sum'):.0f} | {med(t, 'gl_counts_forward_max'):.0f} | "
+          f"{med(t, 'gl_counts_backtrack'):.0f} | {t['min_run']} | {med(t, 'gl_minrun_forward_sum'):.0f} | {med(t, 'gl_minrun_forward_max'):.0f} | "
+          f"{med(t, 'gl_minrun_backtrack'):.0f} | {t['sum_over_min_run_sum']:.2f} | {t['max_over_min_run_max']:.2f} | "
+          f"{t['back_pointer_bytes'] / 1e6:.1f} MB |")
+    A("")
+    ratios = [t[k] for t in rows for k in ("sum_over_min_run_sum", "max_over_min_run_max")]
+    big = rows[-1]
+    A("What the figures say, and what they do not:\n")
+    A(f"* **The counts launches take {min(ratios):.2f} to {max(ratios):.2f} times their min-run siblings at equal slots** -- nowhere near the "
+      "factor of two that would have called for a profile.  A counts destination reads one slot of every source label and a second one at "
+      "the tail slot only, which is what a min-run destination does at d = m; the inside lanes' extra address select (one slot lower for an "
+      "outside source) does not show.  Where the counts launch is the cheaper one (few slots, many labels) the min-run body presumably "
+      "pays for its slot-dependent source masks; that was not looked into.")
+    A("* **The time grows about linearly in the slot count**, as the min-run walks' does in m: the sum launch takes "
+      f"{rows[0]['forward_sum_ns_per_item']:.1f} ns an item at L = {rows[0]['labels']}, K = {rows[0]['max_runs']} and "
+      f"{big['forward_sum_ns_per_item']:.0f} ns at L = {big['labels']}, K = {big['max_runs']}.  The body is §7l's and §7n's: fp64 "
+      "exponentials (sum) and compare-selects (max) issued along a dependent walk, one wave a workgroup, "
+      f"{big['sequences'] * 32 // 64} waves at 32 labels; no profile beyond the trace was taken.  Skipping the slots that cannot be "
+      "reached yet (c > ⌈(t + 1) / 2⌉) would save at most the first 2 K genes of a contig; it was not built.")
+    A(f"* The backtrack, one lane per (sequence, k), takes {min(med(t, 'gl_counts_backtrack') for t in rows):.0f} to "
+      f"{max(med(t, 'gl_counts_backtrack') for t in rows):.0f} µs: K + 1 times the lanes of the min-run backtrack, which keeps more of the "
+      "device busy on a walk that is latency-bound either way.")
+    A("* Accuracy, from `tests/test_gpu_counts.py` on an MI355X (58 cases, 32 s; the largest seam case, 32 labels at K = 32, 3.4 s): against the recursion over the explicit counter table in `numpy.longdouble`, over L = 2, 3, 4, 8, 9, 16, 17, 32 and K = 1, "
+      "2, 3, 5, 16, 32, the thirteen seam lengths in one batch, four label sets and the four kinds of batch, **the largest |log Z_k error| / "
+      "bound was 0.040**, the bound being (T + 1)(2 L + 8) ε max(1, M); −∞ exactly where the yardstick has −∞.  With integer weights every "
+      "plane's labels were the yardstick's and every score bit-equal; the largest of a sequence's scores had the bits of "
+      "`viterbi_kbest`'s rank 0 in both weight families; either output had the bytes it has when the other is not asked for.")
+    A("* Not measured: the call as a whole (plan build, upload, the allocation of the back-pointers, the downloads: 16 (K + 1) bytes a "
+      "sequence and K + 1 bytes a gene), one long contig (the walk is sequential), other label sets, counters of the new kernels, and "
+      "the typed front end's calls.\n")
+    A("Existing paths did not move: no shared kernel, launcher or plan path changed, and calls without the new entry run the launches "
+      "they ran.  The whole GPU suite passes (2 236 cases with the 58 new ones and 1 skipped as before, 310 s; 839 without a device).  "
+      "`bench.py --gpus 1 --steps 1000 --warmup 100 --no-cpu-baseline --no-latency --no-past-l3 --no-levels --no-8d --no-c4` (the 2-label "
+      "flagship, whose kernels are untouched), the parent's tree and this one alternating on one box: parent 24.21, 24.28 µs per step; "
+      "change 24.22, 24.28.\n")
+    print_wrapped(out)
+
+
 def print_wrapped(out):
     import textwrap
 
@@ -187,6 +245,8 @@ def main():
         return section_7m()
     if sys.argv[1:] == ["--section", "7n"]:
         return section_7n()
+    if sys.argv[1:] == ["--section", "7o"]:
+        return section_7o()
     c3, c3d = J("bench_c3_detail"), J("bench_c3_driver_command_detail")
     line = open(os.path.join(P, f"{TAG}_bench_c3_driver_command.json")).read().strip()
     c1, c2, c5, two = J("bench_c1_detail"), J("bench_c2_detail"), J("bench_c5_detail"), J("bench_c3_two_launch_detail")
