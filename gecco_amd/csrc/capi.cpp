@@ -979,6 +979,26 @@ int lattice_call(const gecco_crf_model *m, int32_t device, const int32_t *contig
     }
     return marginals_full_of_slice(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
 }
+// the checks of a query's place in its contig of `len` genes: a half-open range [b, e), or one item t (`word`: what the entry calls it)
+int check_query_range(const char *kind, int32_t q, int32_t c, int32_t b, int32_t e, int64_t len) {
+    if (b < 0 || b >= e || e > len)
+        return fail(query_name(kind, q) + "[" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
+                    std::to_string(c) + " of " + std::to_string(len) + " genes");
+    return GECCO_CRF_OK;
+}
+int check_query_item(const char *kind, const char *word, int32_t q, int32_t c, int32_t t, int64_t len) {
+    if (t < 0 || t >= len)
+        return fail(query_name(kind, q) + word + " " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
+                    std::to_string(len) + " genes");
+    return GECCO_CRF_OK;
+}
+// a lattice entry without queries is the whole-contig marginals' own call, of the batch's kind
+int marginals_full_of_kind(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
+                           const int32_t *attr_id, const double *attr_value, const uint32_t *allowed, double *marg, double *lognorm) {
+    if (allowed) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
+    if (attr_value) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
+    return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
+}
 // the device block of an entry's queries: `total` bytes, the `bytes` of `host` at its head
 int upload_queries(DeviceBlock<char> &q, const void *host, size_t bytes, size_t total, const char *what_alloc, const char *what_copy) {
     const int rc = q.alloc(total, what_alloc);
@@ -1006,18 +1026,12 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
         const int32_t c = span_contig[q], b = span_begin[q], e = span_end[q];
         int64_t len;
         if ((rc = check_query_contig("span", q, c, n_contigs, contig_ptr, &len))) return rc;
-        if (b < 0 || b >= e || e > len)
-            return fail(query_name("span", q) + "[" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
-                        std::to_string(c) + " of " + std::to_string(len) + " genes");
+        if ((rc = check_query_range("span", q, c, b, e, len))) return rc;
         if ((rc = check_label_set("span", q, span_mask[q], m->m.L))) return rc;
         spans[size_t(q)] = SpanQuery{c, b, e, span_mask[q]};
     }
     // without spans the call is the whole-contig marginals' own
-    if (n_spans == 0) {
-        if (allowed) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
-        if (attr_value) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
-        return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
-    }
+    if (n_spans == 0) return marginals_full_of_kind(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
     // (a batch without genes cannot be: a checked span lies inside a contig with genes)
     return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
         DeviceBlock<char> q;
@@ -1062,9 +1076,7 @@ GECCO_API int gecco_crf_run_posteriors(const gecco_crf_model *m, int32_t device,
         const int32_t c = anchor_contig[q], t = anchor_item[q];
         int64_t len;
         if ((rc = check_query_contig("anchor", q, c, n_contigs, contig_ptr, &len))) return rc;
-        if (t < 0 || t >= len)
-            return fail(query_name("anchor", q) + "item " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
-                        std::to_string(len) + " genes");
+        if ((rc = check_query_item("anchor", "item", q, c, t, len))) return rc;
         if ((rc = check_label_set("anchor", q, anchor_mask[q], m->m.L))) return rc;
         anchors[size_t(q)] = RunQuery{c, t, anchor_mask[q]};
     }
@@ -1073,18 +1085,12 @@ GECCO_API int gecco_crf_run_posteriors(const gecco_crf_model *m, int32_t device,
         const int32_t c = run_contig[q], b = run_begin[q], e = run_end[q];
         int64_t len;
         if ((rc = check_query_contig("run", q, c, n_contigs, contig_ptr, &len))) return rc;
-        if (b < 0 || b >= e || e > len)
-            return fail(query_name("run", q) + "[" + std::to_string(b) + ", " + std::to_string(e) + ") is not a non-empty range inside contig " +
-                        std::to_string(c) + " of " + std::to_string(len) + " genes");
+        if ((rc = check_query_range("run", q, c, b, e, len))) return rc;
         if ((rc = check_label_set("run", q, run_mask[q], m->m.L))) return rc;
         runs[size_t(q)] = SpanQuery{c, b, e, run_mask[q]};
     }
     // without queries the call is the whole-contig marginals' own
-    if (n_anchors == 0 && n_runs == 0) {
-        if (allowed) return gecco_crf_marginals_full_constrained(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
-        if (attr_value) return gecco_crf_marginals_full_valued(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, marg, lognorm);
-        return gecco_crf_marginals_full(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, marg, lognorm);
-    }
+    if (n_anchors == 0 && n_runs == 0) return marginals_full_of_kind(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
     // (a batch without genes cannot be: a checked query lies inside a contig with genes)
     return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
         // one block: the anchors, the runs, then the outputs in the order log_anchor, start_beyond, end_beyond, run, start, end
@@ -1146,9 +1152,7 @@ GECCO_API int gecco_crf_sample_paths(const gecco_crf_model *m, int32_t device, c
         const int32_t c = run_contig[q], t = run_anchor[q];
         int64_t len;
         if ((rc = check_query_contig("run", q, c, n_contigs, contig_ptr, &len))) return rc;
-        if (t < 0 || t >= len)
-            return fail(query_name("run", q) + "anchor " + std::to_string(t) + " lies outside contig " + std::to_string(c) + " of " +
-                        std::to_string(len) + " genes");
+        if ((rc = check_query_item("run", "anchor", q, c, t, len))) return rc;
         if ((rc = check_label_set("run", q, run_mask[q], m->m.L))) return rc;
         queries[size_t(q)] = RunQuery{c, t, run_mask[q]};
     }

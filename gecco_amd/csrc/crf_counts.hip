@@ -20,83 +20,56 @@
 //   Sum semiring: the same sources, a max-shifted log-sum-exp in place of the max; a destination all of whose sources are
 // -infinity stays -infinity.
 //
-// gl_counts_forward<LP, SUM>: a group of LP = next-pow2(L) lanes per contig, one lane per destination label, 64 / LP contigs per
-// wave (a workgroup is one wave); lanes of labels that do not exist carry -infinity.  A lane's counter column lies in LDS, two
-// generations, [2][64 rows][(K + 1) | 1] doubles, state (j, c) at slot c (slot 0 of an inside label stays -infinity).  The row
-// length is odd, so that lanes reading different rows at one slot hit different banks.  The lane's column of trans is in
-// registers, indexed by unrolled loops only.  State scores come eight genes ahead, as in gl_minrun_forward.  The groups of a wave
-// end at different genes; a group that has ended keeps its values and stores nothing.  One barrier per gene, outside every
-// divergent branch.
+// gl_counts_forward<LP, SUM>: the frame of crf_contig_walk.hpp (group geometry, columns in LDS, gene loop, the two reducers over
+// sources(f), the end-of-contig reductions), one lane per destination label.  A lane's counter column, [(K + 1) | 1] doubles:
+// state (j, c) at slot c (slot 0 of an inside label stays -infinity).
 //   Back-pointers (max only): one byte per (gene, label, slot), the source label in the low five bits and one bit "the source
 // slot was K" (as against K - 1), which means something only at slot K of an inside label reached from an outside label;
 // everywhere else the source slot follows from the two labels.  The final arg max of every slot runs across the group's lanes by
 // xor-shuffles and leaves the last gene's label in plane k of y, or -1.
 // gl_counts_backtrack: one lane per (contig, k), last gene to first, plane k of y [K + 1][n_genes].
 // A contig is one sequential walk; it is not chunked.  No atomics: equal calls give equal bytes.
-#include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_contig_walk.hpp"
 
 #include <cmath>
 
 namespace gecco {
 namespace {
 
-constexpr int kCW = 64;      // lanes per workgroup of the forward kernel: one wave
-constexpr int kCTile = 8;    // genes of state scores fetched ahead
-constexpr int kCBack = 256;  // lanes per workgroup of the backtrack
-constexpr uint8_t kFromTail = 0x20;  // back-pointer bit: the source was (i, K), not (i, K - 1)
+constexpr int kCBack = kWalkBack;  // lanes per workgroup of the backtrack
 
 template <int LP, bool SUM>
-__global__ void __launch_bounds__(kCW) gl_counts_forward(const double *__restrict__ state, const double *__restrict__ trans,
-                                                         const int32_t *__restrict__ contig_ptr, const int L, const int n_contigs,
-                                                         const long long n_genes, const int K, const uint32_t set_mask,
-                                                         uint8_t *__restrict__ back, int8_t *__restrict__ y,
-                                                         double *__restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) double cols[];  // [2][kCW][KS]
-    constexpr int G = kCW / LP;
-    const double ninf = -INFINITY;
-    const int K1 = K + 1, KS = K1 | 1;
-    const int lane = threadIdx.x, j = lane & (LP - 1), row0 = lane - j;
-    const long long c = static_cast<long long>(blockIdx.x) * G + lane / LP;
-    const bool valid = c < n_contigs;
-    int g0 = 0, T = 0;
-    if (valid) {
-        g0 = contig_ptr[c];
-        T = contig_ptr[c + 1] - g0;
-        T = T < 0 ? 0 : T;
-    }
-    const bool on = j < L;
-    const int jj = on ? j : 0;
+__global__ void __launch_bounds__(kWalkLanes) gl_counts_forward(const double *__restrict__ state, const double *__restrict__ trans,
+                                                                const int32_t *__restrict__ contig_ptr, const int L,
+                                                                const int n_contigs, const long long n_genes, const int K,
+                                                                const uint32_t set_mask, uint8_t *__restrict__ back,
+                                                                int8_t *__restrict__ y, double *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) double cols_lds[];  // [2][kWalkLanes][(K + 1) | 1]
+    const double ninf = kWalkNinf;
+    const int K1 = K + 1;
+    const WalkGroup<LP> g(contig_ptr, n_contigs, L);
+    const int lane = g.lane, j = g.j, T = g.T;
     const bool inside = (set_mask >> j) & 1u;  // (no bit at or above L: a lane without a label is an outside lane at -infinity)
     // the labels whose state one slot below is this lane's source: the outside labels, for an inside lane
     const uint32_t below = inside ? ~set_mask : 0u;
     double tcol[LP];
-#pragma unroll
-    for (int i = 0; i < LP; ++i) tcol[i] = i < L ? trans[i * L + jj] : 0.0;
-    double *const buf0 = cols, *const buf1 = cols + kCW * KS;
-    const double *st = state + static_cast<size_t>(g0) * L + jj;
-    const auto fetch = [&](int t) { return t < T ? (on ? st[static_cast<size_t>(t) * L] : ninf) : 0.0; };
-    {
-        const double s0 = fetch(0);
-        const int first = inside ? 1 : 0;
-        for (int k = 0; k < KS; ++k) {
-            buf0[lane * KS + k] = k == first ? s0 : ninf;
-            buf1[lane * KS + k] = ninf;
-        }
-    }
+    g.load_trans(trans, L, tcol);
+    const double *st = g.column(state, L);
+    const WalkColumns cols(cols_lds, K1);
+    const int KS = cols.KS;
+    cols.fill(lane, inside ? 1 : 0, g.state_at(st, L, 0 < T, 0));
     __syncthreads();  // (one wave)
     // one gene: the lane's states in slot order.  An inside lane has no state at slot 0 and idles there.
     const auto step = [&](const int t, const double s_t) {
         const bool act = t < T;
-        const double *prev = ((t & 1) ? buf0 : buf1) + row0 * KS;
-        double *mine = ((t & 1) ? buf1 : buf0) + lane * KS;
-        const size_t bk = (static_cast<size_t>(g0 + (act ? t : 0)) * L + jj) * static_cast<size_t>(K1);
+        const double *prev = cols.gen(t - 1) + g.row0 * KS;
+        double *mine = cols.gen(t) + lane * KS;
+        const size_t bk = (static_cast<size_t>(g.g0 + (act ? t : 0)) * L + g.jj) * static_cast<size_t>(K1);
 #pragma unroll 1
         for (int k = 0; k < K1; ++k) {
             const bool tail = k == K;          // (wave-uniform)
             const bool own = !inside || k > 0;  // the lane has a state at this slot
             const uint32_t dec = k > 0 ? below : 0u;
-            // f(i, value, from_tail) for every source in ascending (label, slot) order; what is no source gives -infinity
             const auto sources = [&](auto &&f) {
 #pragma unroll
                 for (int i = 0; i < LP; ++i) {
@@ -109,75 +82,35 @@ __global__ void __launch_bounds__(kCW) gl_counts_forward(const double *__restric
                     }
                 }
             };
-            double value;
-            int arg = 0;
-            if constexpr (SUM) {
-                double mx = ninf;
-                sources([&](int, double v, bool) { mx = v > mx ? v : mx; });
-                const double shift = mx > ninf ? mx : 0.0;
-                double sum = 0.0;
-                sources([&](int, double v, bool) { sum += v > ninf ? exp(v - shift) : 0.0; });
-                value = mx > ninf ? (mx + log(sum)) + s_t : ninf;
-            } else {
-                double best = ninf;
-                sources([&](int i, double v, bool from_tail) {
-                    const bool take = v > best;  // strict: the earlier source wins a tie
-                    best = take ? v : best;
-                    arg = take ? (i | (from_tail ? kFromTail : 0)) : arg;
-                });
-                value = best + s_t;
-            }
+            int arg;
+            const double value = walk_value<SUM>(sources, s_t, arg);
             if (act && own) {
                 mine[k] = value;
                 if constexpr (!SUM) {
-                    if (on) back[bk + k] = static_cast<uint8_t>(arg);
+                    if (g.on) back[bk + k] = static_cast<uint8_t>(arg);
                 }
             }
         }
         __syncthreads();
     };
-    double nxt[kCTile];
-#pragma unroll
-    for (int k = 0; k < kCTile; ++k) nxt[k] = fetch(1 + k);
-    for (int tb = 1; __any(tb < T); tb += kCTile) {
-        double cur[kCTile];
-#pragma unroll
-        for (int k = 0; k < kCTile; ++k) cur[k] = nxt[k];
-#pragma unroll
-        for (int k = 0; k < kCTile; ++k) nxt[k] = fetch(tb + kCTile + k);
-#pragma unroll
-        for (int k = 0; k < kCTile; ++k) {
-            if (!__any(tb + k < T)) break;  // (wave-uniform)
-            step(tb + k, cur[k]);
-        }
-    }
+    contig_walk(1, T, [&](int t) { return g.state_at(st, L, t < T, t); }, step);
     // the end of the contig: slot k collects the states (., k) of the group's lanes
-    const double *fl = (((T - 1) & 1) ? buf1 : buf0) + lane * KS;
-    const size_t ob = static_cast<size_t>(valid ? c : 0) * static_cast<size_t>(K1);
+    const double *fl = cols.gen(T - 1) + lane * KS;
+    const size_t ob = static_cast<size_t>(g.valid ? g.c : 0) * static_cast<size_t>(K1);
 #pragma unroll 1
     for (int k = 0; k < K1; ++k) {
         double v = T > 0 ? fl[k] : ninf;
+        const double none = k == 0 ? 0.0 : ninf;  // (a contig without genes: the empty path, which has no run)
         if constexpr (SUM) {
-            const double mx = group_max<LP>(v);
-            const double shift = mx > ninf ? mx : 0.0;
-            const double sum = group_sum<LP>(v > ninf ? exp(v - shift) : 0.0);
-            // (a contig without genes: the empty path, which has no run)
-            if (valid && j == 0) out[ob + k] = T > 0 ? (mx > ninf ? mx + log(sum) : ninf) : (k == 0 ? 0.0 : ninf);
+            const double lse = group_lse<LP>(v);
+            if (g.valid && j == 0) out[ob + k] = T > 0 ? lse : none;
         } else {
             int bj = j;
-#pragma unroll
-            for (int off = LP / 2; off >= 1; off >>= 1) {
-                const double ov = __shfl_xor(v, off);
-                const int oj = __shfl_xor(bj, off);
-                const bool take = ov > v || (ov == v && oj < bj);
-                v = take ? ov : v;
-                bj = take ? oj : bj;
-            }
-            if (valid && j == 0) {
-                // (a contig without genes: the score of gl_viterbi_seq's convention, in the slot of no run)
-                out[ob + k] = T > 0 ? v : (k == 0 ? 0.0 : ninf);
+            group_argmax<LP>(v, bj);
+            if (g.valid && j == 0) {
+                out[ob + k] = T > 0 ? v : none;  // (without genes: the score of gl_viterbi_seq's convention, in the slot of no run)
                 if (T > 0)
-                    y[static_cast<size_t>(k) * static_cast<size_t>(n_genes) + static_cast<size_t>(g0) + static_cast<size_t>(T - 1)] =
+                    y[static_cast<size_t>(k) * static_cast<size_t>(n_genes) + static_cast<size_t>(g.g0) + static_cast<size_t>(T - 1)] =
                         v > ninf ? static_cast<int8_t>(bj) : int8_t(-1);
             }
         }
@@ -210,7 +143,7 @@ __global__ void __launch_bounds__(kCBack) gl_counts_backtrack(const uint8_t *__r
         const int src = b & 0x1f;
         const bool inside = (set_mask >> lab) & 1u, src_inside = (set_mask >> src) & 1u;
         // a run began at this gene: the source is one slot below, or at the tail slot itself when the bit says so
-        if (inside && !src_inside && !(slot == K && (b & kFromTail))) slot -= 1;
+        if (inside && !src_inside && !(slot == K && (b & kWalkSecond))) slot -= 1;
         lab = src;
         col[t - 1] = static_cast<int8_t>(lab);
     }
@@ -218,11 +151,8 @@ __global__ void __launch_bounds__(kCBack) gl_counts_backtrack(const uint8_t *__r
 
 template <int LP, bool SUM>
 void launch_forward(const GenArgs &a, uint32_t set_mask, int32_t K, uint8_t *back, int8_t *y, double *out, hipStream_t stream) {
-    constexpr int G = kCW / LP;
-    const unsigned blocks = static_cast<unsigned>((static_cast<long long>(a.n_contigs) + G - 1) / G);
-    const size_t lds = size_t(2) * kCW * size_t((K + 1) | 1) * sizeof(double);
-    hipLaunchKernelGGL((gl_counts_forward<LP, SUM>), dim3(blocks), dim3(kCW), lds, stream, a.state, a.trans, a.contig_ptr, a.L,
-                       a.n_contigs, static_cast<long long>(a.n_genes), K, set_mask, back, y, out);
+    hipLaunchKernelGGL((gl_counts_forward<LP, SUM>), dim3(walk_blocks<LP>(a.n_contigs)), dim3(kWalkLanes), walk_lds_bytes(K + 1), stream,
+                       a.state, a.trans, a.contig_ptr, a.L, a.n_contigs, static_cast<long long>(a.n_genes), K, set_mask, back, y, out);
 }
 
 }  // namespace
@@ -233,9 +163,7 @@ size_t counts_back_bytes(int64_t n_genes, int32_t L, int32_t max_runs) {
 
 hipError_t launch_gen_run_counts(const GenArgs &a, uint32_t set_mask, int32_t max_runs, uint8_t *back, double *log_mass,
                                  double *score, int8_t *y, hipStream_t stream) {
-    const uint32_t beyond = a.L >= 32 ? 0u : ~0u << a.L;
-    if (a.L <= 0 || a.L > kGenMaxL || max_runs < 1 || max_runs > kMaxRunCounts || set_mask == 0 || (set_mask & beyond))
-        return hipErrorNotSupported;
+    if (!walk_counter_ok(a, set_mask, max_runs, kMaxRunCounts)) return hipErrorNotSupported;
     if (a.n_contigs <= 0) return hipSuccess;
     if (!a.state || !a.trans || (!log_mass && !score) || (score && (!back || !y))) return hipErrorNotSupported;
     if (log_mass) {

@@ -14,67 +14,46 @@
 // fills stays empty (score -infinity, back-pointer 0xffff, labels -1).  The order is total and merges preserve it, so rank k of
 // a call with K' < K is rank k of the call with K: the lists of the smaller call are prefixes of the larger call's.
 //
-// gl_kbest_forward<LP>: a group of LP = next-pow2(L) lanes per contig, one lane per destination label, 64 / LP contigs per wave (a
-// workgroup is one wave).  The two generations of lists lie in LDS, [2][64 rows][K | 1] doubles: a row per lane, padded to an
-// odd number of doubles so that lanes reading different source rows at one rank hit different banks.  Heads, read positions and
-// the lane's column of trans are registers, indexed by unrolled loops only.  State scores come eight genes ahead, as in
-// gl_viterbi_wave.  The groups of a wave end at different genes; a group that has ended keeps its lists and stores nothing.
-// Back-pointers: uint16 per (gene, label, rank), (previous label << 8) | previous rank.  The final merge runs across the
-// group's lanes (every lane the head of its own list, arg max by xor-shuffles) and leaves, per (contig, rank), the last label
-// and its rank in `fin`, the score, and the number of paths.
+// gl_kbest_forward<LP>: the frame of crf_contig_walk.hpp (group geometry, columns in LDS, gene loop, group arg max), one lane per
+// destination label.  The two generations of lists are the frame's columns, [2][64 rows][K | 1] doubles.  Heads and read positions
+// are registers, indexed by unrolled loops only.  Back-pointers: uint16 per (gene, label, rank), (previous label << 8) | previous
+// rank.  The final merge runs across the group's lanes (every lane the head of its own list, the rank as the arg max's payload)
+// and leaves, per (contig, rank), the last label and its rank in `fin`, the score, and the number of paths.
 // gl_kbest_backtrack: one lane per (contig, rank) follows the back-pointers from the last gene to the first and writes
 // y[g * K + k], gene-major like the sampler's output: a step's stores are consecutive bytes.
 // A contig is one sequential walk; it is not chunked (profiles/EXPERIMENTS.md has the parallel-in-T idea).
-#include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_contig_walk.hpp"
 
 #include <cmath>
 
 namespace gecco {
 namespace {
 
-constexpr int kKW = 64;     // lanes per workgroup of the forward kernel: one wave
-constexpr int kKTile = 8;   // genes of state scores fetched ahead
-constexpr int kKBack = 256;  // lanes per workgroup of the backtrack
+constexpr int kKBack = kWalkBack;  // lanes per workgroup of the backtrack
 constexpr uint16_t kNoPath = 0xffffu;
 
 template <int LP>
-__global__ void __launch_bounds__(kKW) gl_kbest_forward(const double *__restrict__ state, const double *__restrict__ trans,
-                                                        const int32_t *__restrict__ contig_ptr, const int L, const int n_contigs,
-                                                        const int K, uint16_t *__restrict__ back, uint16_t *__restrict__ fin,
-                                                        double *__restrict__ score, int32_t *__restrict__ n_paths) {
-    extern __shared__ double lists[];  // [2][kKW][KS]
-    constexpr int G = kKW / LP;
-    const double ninf = -INFINITY;
-    const int KS = K | 1;
-    const int lane = threadIdx.x, j = lane & (LP - 1), row0 = lane - j;
-    const long long c = static_cast<long long>(blockIdx.x) * G + lane / LP;
-    const bool valid = c < n_contigs;
-    int g0 = 0, T = 0;
-    if (valid) {
-        g0 = contig_ptr[c];
-        T = contig_ptr[c + 1] - g0;
-        T = T < 0 ? 0 : T;
-    }
-    // lanes of labels that do not exist carry state -infinity: their lists are empty, and no source reads a finite value there
-    const bool on = j < L;
-    const int jj = on ? j : 0;
+__global__ void __launch_bounds__(kWalkLanes) gl_kbest_forward(const double *__restrict__ state, const double *__restrict__ trans,
+                                                               const int32_t *__restrict__ contig_ptr, const int L,
+                                                               const int n_contigs, const int K, uint16_t *__restrict__ back,
+                                                               uint16_t *__restrict__ fin, double *__restrict__ score,
+                                                               int32_t *__restrict__ n_paths) {
+    extern __shared__ double lists[];  // [2][kWalkLanes][K | 1]
+    const double ninf = kWalkNinf;
+    const WalkGroup<LP> g(contig_ptr, n_contigs, L);
+    const int lane = g.lane, j = g.j, T = g.T;
     double tcol[LP];
-#pragma unroll
-    for (int i = 0; i < LP; ++i) tcol[i] = i < L ? trans[i * L + jj] : 0.0;
-    double *const buf0 = lists, *const buf1 = lists + kKW * KS;
-    const double *st = state + static_cast<size_t>(g0) * L + jj;
-    const auto fetch = [&](int t) { return t < T ? (on ? st[static_cast<size_t>(t) * L] : ninf) : 0.0; };
-    {
-        const double s0 = fetch(0);
-        for (int k = 0; k < K; ++k) buf0[lane * KS + k] = k == 0 ? s0 : ninf;
-    }
+    g.load_trans(trans, L, tcol);
+    const double *st = g.column(state, L);
+    const WalkColumns cols(lists, K);
+    const int KS = cols.KS;
+    cols.fill(lane, 0, g.state_at(st, L, 0 < T, 0));
     __syncthreads();  // (one wave)
     // one gene: the lane's L-way merge of the previous generation's lists, K outputs
     const auto step = [&](const int t, const double s_t) {
         const bool act = t < T;
-        const double *prev = ((t & 1) ? buf0 : buf1) + row0 * KS;
-        double *mine = ((t & 1) ? buf1 : buf0) + lane * KS;
+        const double *prev = cols.gen(t - 1) + g.row0 * KS;
+        double *mine = cols.gen(t) + lane * KS;
         double cand[LP];
         int ptr[LP];
 #pragma unroll
@@ -82,7 +61,7 @@ __global__ void __launch_bounds__(kKW) gl_kbest_forward(const double *__restrict
             cand[i] = prev[i * KS] + tcol[i];
             ptr[i] = 0;
         }
-        uint16_t *bk = back + (static_cast<size_t>(g0 + (act ? t : 0)) * L + jj) * K;
+        uint16_t *bk = back + (static_cast<size_t>(g.g0 + (act ? t : 0)) * L + g.jj) * K;
 #pragma unroll 1
         for (int k = 0; k < K; ++k) {
             double best = cand[0];
@@ -106,51 +85,29 @@ __global__ void __launch_bounds__(kKW) gl_kbest_forward(const double *__restrict
             const double out = best + s_t;
             if (act) {
                 mine[k] = out;
-                if (on) bk[k] = out > ninf ? static_cast<uint16_t>((arg << 8) | r) : kNoPath;
+                if (g.on) bk[k] = out > ninf ? static_cast<uint16_t>((arg << 8) | r) : kNoPath;
             }
         }
         __syncthreads();
     };
-    double nxt[kKTile];
-#pragma unroll
-    for (int k = 0; k < kKTile; ++k) nxt[k] = fetch(1 + k);
-    for (int tb = 1; __any(tb < T); tb += kKTile) {
-        double cur[kKTile];
-#pragma unroll
-        for (int k = 0; k < kKTile; ++k) cur[k] = nxt[k];
-#pragma unroll
-        for (int k = 0; k < kKTile; ++k) nxt[k] = fetch(tb + kKTile + k);
-#pragma unroll
-        for (int k = 0; k < kKTile; ++k) {
-            if (!__any(tb + k < T)) break;  // (wave-uniform)
-            step(tb + k, cur[k]);
-        }
-    }
-    // the final merge: every lane the head of its own label's last list, the group's arg max by xor-shuffles
-    const double *fl = (((T - 1) & 1) ? buf1 : buf0) + lane * KS;
+    contig_walk(1, T, [&](int t) { return g.state_at(st, L, t < T, t); }, step);
+    // the final merge: every lane the head of its own label's last list, the group's arg max
+    const double *fl = cols.gen(T - 1) + lane * KS;
     int p = 0, count = 0;
     for (int k = 0; k < K; ++k) {
         double v = (T > 0 && p < K) ? fl[p < K ? p : 0] : ninf;
         int bj = j, bp = p;
-#pragma unroll
-        for (int off = LP / 2; off >= 1; off >>= 1) {
-            const double ov = __shfl_xor(v, off);
-            const int oj = __shfl_xor(bj, off), op = __shfl_xor(bp, off);
-            const bool take = ov > v || (ov == v && oj < bj);
-            v = take ? ov : v;
-            bj = take ? oj : bj;
-            bp = take ? op : bp;
-        }
+        group_argmax<LP>(v, bj, bp);
         const bool exists = v > ninf;
         p += (exists && bj == j) ? 1 : 0;
         count += exists ? 1 : 0;
-        if (valid && j == 0) {
-            const size_t o = static_cast<size_t>(c) * K + k;
+        if (g.valid && j == 0) {
+            const size_t o = static_cast<size_t>(g.c) * K + k;
             fin[o] = exists ? static_cast<uint16_t>((bj << 8) | bp) : kNoPath;
             score[o] = exists ? v : ninf;
         }
     }
-    if (valid && j == 0) n_paths[c] = count;
+    if (g.valid && j == 0) n_paths[g.c] = count;
 }
 
 __global__ void __launch_bounds__(kKBack) gl_kbest_backtrack(const uint16_t *__restrict__ back, const uint16_t *__restrict__ fin,
@@ -182,11 +139,8 @@ __global__ void __launch_bounds__(kKBack) gl_kbest_backtrack(const uint16_t *__r
 
 template <int LP>
 void launch_forward(const GenArgs &a, int32_t K, uint16_t *back, uint16_t *fin, double *score, int32_t *n_paths, hipStream_t stream) {
-    constexpr int G = kKW / LP;
-    const unsigned blocks = static_cast<unsigned>((static_cast<long long>(a.n_contigs) + G - 1) / G);
-    const size_t lds = size_t(2) * kKW * size_t(K | 1) * sizeof(double);
-    hipLaunchKernelGGL(gl_kbest_forward<LP>, dim3(blocks), dim3(kKW), lds, stream, a.state, a.trans, a.contig_ptr, a.L, a.n_contigs, K,
-                       back, fin, score, n_paths);
+    hipLaunchKernelGGL(gl_kbest_forward<LP>, dim3(walk_blocks<LP>(a.n_contigs)), dim3(kWalkLanes), walk_lds_bytes(K), stream, a.state,
+                       a.trans, a.contig_ptr, a.L, a.n_contigs, K, back, fin, score, n_paths);
 }
 
 }  // namespace

@@ -22,13 +22,10 @@
 //   Sum semiring: the same sources, a max-shifted log-sum-exp in place of the max; a destination all of whose sources are
 // -infinity stays -infinity.
 //
-// gl_minrun_forward<LP, SUM>: a group of LP = next-pow2(L) lanes per contig, one lane per destination label, 64 / LP contigs per
-// wave (a workgroup is one wave); lanes of labels that do not exist carry -infinity.  A lane's d-column lies in LDS, two
-// generations, [2][64 rows][m | 1] doubles: state (j, d) at slot d - 1, an outside label's one state at slot m - 1 -- so every
-// state a run may end in, and every admissible one, is at slot m - 1.  The row length is odd, so that lanes reading different
-// rows at one slot hit different banks.  The lane's column of trans is in registers, indexed by unrolled loops only.  State
-// scores come eight genes ahead, as in gl_viterbi_wave.  The groups of a wave end at different genes; a group that has ended
-// keeps its values and stores nothing.  One barrier per gene, outside every divergent branch.
+// gl_minrun_forward<LP, SUM>: the frame of crf_contig_walk.hpp (group geometry, columns in LDS, gene loop, the two reducers over
+// sources(f), the end-of-contig reductions), one lane per destination label.  A lane's d-column, [m | 1] doubles: state (j, d) at
+// slot d - 1, an outside label's one state at slot m - 1 -- so every state a run may end in, and every admissible one, is at slot
+// m - 1.
 //   Back-pointers (max only): one byte per (gene, label, slot), the source label in the low five bits and one bit "from d = m"
 // (as against m - 1), which means something at d = m only.  The final arg max runs across the group's lanes by xor-shuffles, the
 // smaller label winning a tie (one admissible state per label), and leaves the last gene's label in y, or -1.
@@ -38,58 +35,41 @@
 // gl_minrun_backward reads them (below, at the kernel).
 // gl_minrun_backtrack: one lane per contig, last gene to first; the previous slot follows from the rule above.
 // A contig is one sequential walk; it is not chunked.
-#include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_contig_walk.hpp"
 
 #include <cmath>
 
 namespace gecco {
 namespace {
 
-constexpr int kRW = 64;      // lanes per workgroup of the forward kernel: one wave
-constexpr int kRTile = 8;    // genes of state scores fetched ahead
-constexpr int kRBack = 256;  // lanes per workgroup of the backtrack
-constexpr uint8_t kFromFull = 0x20;  // back-pointer bit: the source was (i, m), not (i, m - 1)
+constexpr int kRBack = kWalkBack;  // lanes per workgroup of the backtrack
 
 template <int LP, bool SUM, bool STORE = false>
-__global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restrict__ state, const double *__restrict__ trans,
-                                                         const int32_t *__restrict__ contig_ptr, const int L, const int n_contigs,
-                                                         const int m, const uint32_t set_mask, uint8_t *__restrict__ back,
-                                                         int8_t *__restrict__ y, double *__restrict__ out, double *__restrict__ fwd) {
+__global__ void __launch_bounds__(kWalkLanes) gl_minrun_forward(const double *__restrict__ state, const double *__restrict__ trans,
+                                                                const int32_t *__restrict__ contig_ptr, const int L,
+                                                                const int n_contigs, const int m, const uint32_t set_mask,
+                                                                uint8_t *__restrict__ back, int8_t *__restrict__ y,
+                                                                double *__restrict__ out, double *__restrict__ fwd) {
     static_assert(SUM || !STORE, "the forward values are the sum semiring's");
-    extern __shared__ __attribute__((aligned(16))) double cols[];  // [2][kRW][KS]
-    constexpr int G = kRW / LP;
-    const double ninf = -INFINITY;
-    const int KS = m | 1, top = m - 1;
-    const int lane = threadIdx.x, j = lane & (LP - 1), row0 = lane - j;
-    const long long c = static_cast<long long>(blockIdx.x) * G + lane / LP;
-    const bool valid = c < n_contigs;
-    int g0 = 0, T = 0;
-    if (valid) {
-        g0 = contig_ptr[c];
-        T = contig_ptr[c + 1] - g0;
-        T = T < 0 ? 0 : T;
-    }
-    const bool on = j < L;
-    const int jj = on ? j : 0;
+    extern __shared__ __attribute__((aligned(16))) double cols_lds[];  // [2][kWalkLanes][m | 1]
+    const double ninf = kWalkNinf;
+    const int top = m - 1;
+    const WalkGroup<LP> g(contig_ptr, n_contigs, L);
+    const int lane = g.lane, j = g.j, T = g.T;
     const bool inside = (set_mask >> j) & 1u;  // (no bit at or above L: a lane without a label is an outside lane at -infinity)
     double tcol[LP];
-#pragma unroll
-    for (int i = 0; i < LP; ++i) tcol[i] = i < L ? trans[i * L + jj] : 0.0;
-    double *const buf0 = cols, *const buf1 = cols + kRW * KS;
-    const double *st = state + static_cast<size_t>(g0) * L + jj;
-    const auto fetch = [&](int t) { return t < T ? (on ? st[static_cast<size_t>(t) * L] : ninf) : 0.0; };
+    g.load_trans(trans, L, tcol);
+    const double *st = g.column(state, L);
+    const WalkColumns cols(cols_lds, m);
+    const int KS = cols.KS;
     {
-        const double s0 = fetch(0);
+        const double s0 = g.state_at(st, L, 0 < T, 0);
         const int first = inside ? 0 : top;
-        for (int k = 0; k < KS; ++k) {
-            buf0[lane * KS + k] = k == first ? s0 : ninf;
-            buf1[lane * KS + k] = ninf;
-        }
+        cols.fill(lane, first, s0);
         if constexpr (STORE) {
-            if (on && T > 0) {
-                const size_t b0 = (static_cast<size_t>(g0) * L + jj) * static_cast<size_t>(m);
-                for (int k = inside ? 0 : top; k < m; ++k) fwd[b0 + k] = k == first ? s0 : ninf;
+            if (g.on && T > 0) {
+                const size_t b0 = (static_cast<size_t>(g.g0) * L + g.jj) * static_cast<size_t>(m);
+                for (int k = first; k < m; ++k) fwd[b0 + k] = k == first ? s0 : ninf;
             }
         }
     }
@@ -97,9 +77,9 @@ __global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restric
     // one gene: the lane's states in slot order.  An outside lane has its one state at the last slot and idles before it.
     const auto step = [&](const int t, const double s_t) {
         const bool act = t < T;
-        const double *prev = ((t & 1) ? buf0 : buf1) + row0 * KS;
-        double *mine = ((t & 1) ? buf1 : buf0) + lane * KS;
-        const size_t bk = (static_cast<size_t>(g0 + (act ? t : 0)) * L + jj) * static_cast<size_t>(m);
+        const double *prev = cols.gen(t - 1) + g.row0 * KS;
+        double *mine = cols.gen(t) + lane * KS;
+        const size_t bk = (static_cast<size_t>(g.g0 + (act ? t : 0)) * L + g.jj) * static_cast<size_t>(m);
 #pragma unroll 1
         for (int d = 0; d < m; ++d) {
             const bool last = d == top;  // (wave-uniform)
@@ -108,7 +88,6 @@ __global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restric
             const uint32_t from = plain ? ~0u : (d == 0 ? ~set_mask : set_mask);
             const bool two = !plain && last;
             const int slot = plain || d == 0 ? top : (two ? top - 1 : d - 1);
-            // f(i, value, from_full) for every source in ascending (label, d) order; a label that is no source gives -infinity
             const auto sources = [&](auto &&f) {
 #pragma unroll
                 for (int i = 0; i < LP; ++i) {
@@ -121,73 +100,33 @@ __global__ void __launch_bounds__(kRW) gl_minrun_forward(const double *__restric
                     }
                 }
             };
-            double value;
-            int arg = 0;
-            if constexpr (SUM) {
-                double mx = ninf;
-                sources([&](int, double v, bool) { mx = v > mx ? v : mx; });
-                const double shift = mx > ninf ? mx : 0.0;
-                double sum = 0.0;
-                sources([&](int, double v, bool) { sum += v > ninf ? exp(v - shift) : 0.0; });
-                value = mx > ninf ? (mx + log(sum)) + s_t : ninf;
-            } else {
-                double best = ninf;
-                sources([&](int i, double v, bool full) {
-                    const bool take = v > best;  // strict: the earlier source wins a tie
-                    best = take ? v : best;
-                    arg = take ? (i | (full ? kFromFull : 0)) : arg;
-                });
-                value = best + s_t;
-            }
+            int arg;
+            const double value = walk_value<SUM>(sources, s_t, arg);
             if (act && (inside || last)) {
                 mine[d] = value;
                 if constexpr (!SUM) {
-                    if (on) back[bk + d] = static_cast<uint8_t>(arg);
+                    if (g.on) back[bk + d] = static_cast<uint8_t>(arg);
                 }
                 if constexpr (STORE) {
-                    if (on) fwd[bk + d] = value;
+                    if (g.on) fwd[bk + d] = value;
                 }
             }
         }
         __syncthreads();
     };
-    double nxt[kRTile];
-#pragma unroll
-    for (int k = 0; k < kRTile; ++k) nxt[k] = fetch(1 + k);
-    for (int tb = 1; __any(tb < T); tb += kRTile) {
-        double cur[kRTile];
-#pragma unroll
-        for (int k = 0; k < kRTile; ++k) cur[k] = nxt[k];
-#pragma unroll
-        for (int k = 0; k < kRTile; ++k) nxt[k] = fetch(tb + kRTile + k);
-#pragma unroll
-        for (int k = 0; k < kRTile; ++k) {
-            if (!__any(tb + k < T)) break;  // (wave-uniform)
-            step(tb + k, cur[k]);
-        }
-    }
+    contig_walk(1, T, [&](int t) { return g.state_at(st, L, t < T, t); }, step);
     // the end of the contig: every lane its label's admissible state, which is the last slot of its column
-    const double *fl = (((T - 1) & 1) ? buf1 : buf0) + lane * KS;
-    double v = T > 0 ? fl[top] : ninf;
+    double v = T > 0 ? cols.gen(T - 1)[lane * KS + top] : ninf;
     if constexpr (SUM) {
-        const double mx = group_max<LP>(v);
-        const double shift = mx > ninf ? mx : 0.0;
-        const double sum = group_sum<LP>(v > ninf ? exp(v - shift) : 0.0);
-        if (valid && j == 0) out[c] = T > 0 ? (mx > ninf ? mx + log(sum) : ninf) : 0.0;
+        const double lse = group_lse<LP>(v);
+        if (g.valid && j == 0) out[g.c] = T > 0 ? lse : 0.0;
     } else {
         int bj = j;
-#pragma unroll
-        for (int off = LP / 2; off >= 1; off >>= 1) {
-            const double ov = __shfl_xor(v, off);
-            const int oj = __shfl_xor(bj, off);
-            const bool take = ov > v || (ov == v && oj < bj);
-            v = take ? ov : v;
-            bj = take ? oj : bj;
-        }
-        if (valid && j == 0) {
+        group_argmax<LP>(v, bj);
+        if (g.valid && j == 0) {
             // (a contig without genes: the score of gl_viterbi_seq's convention)
-            out[c] = T > 0 ? v : 0.0;
-            if (T > 0) y[static_cast<size_t>(g0) + static_cast<size_t>(T - 1)] = v > ninf ? static_cast<int8_t>(bj) : int8_t(-1);
+            out[g.c] = T > 0 ? v : 0.0;
+            if (T > 0) y[static_cast<size_t>(g.g0) + static_cast<size_t>(T - 1)] = v > ninf ? static_cast<int8_t>(bj) : int8_t(-1);
         }
     }
 }
@@ -216,7 +155,7 @@ __global__ void __launch_bounds__(kRBack) gl_minrun_backtrack(const uint8_t *__r
         const uint8_t b = back[(static_cast<size_t>(g0 + t) * L + lab) * M + static_cast<size_t>(slot)];
         const bool inside = (set_mask >> lab) & 1u;
         if (!inside || m == 1 || slot == 0) slot = top;          // from an outside state, or from a run that was long enough
-        else if (slot == top) slot = (b & kFromFull) ? top : top - 1;
+        else if (slot == top) slot = (b & kWalkSecond) ? top : top - 1;
         else slot = slot - 1;
         lab = b & 0x1f;
         col[t - 1] = static_cast<int8_t>(lab);
@@ -239,56 +178,44 @@ __global__ void __launch_bounds__(kRBack) gl_minrun_backtrack(const uint8_t *__r
 // one order of additions).  A state that no feasible path visits adds exactly 0.0, and so does every state of a contig without a
 // feasible path.  No atomics.
 template <int LP>
-__global__ void __launch_bounds__(kRW) gl_minrun_backward(const double *__restrict__ state, const double *__restrict__ trans,
-                                                          const int32_t *__restrict__ contig_ptr, const int L, const int n_contigs,
-                                                          const int m, const uint32_t set_mask, const double *__restrict__ fwd,
-                                                          const double *__restrict__ lognorm_c, double *__restrict__ marg,
-                                                          double *__restrict__ inside_out) {
-    extern __shared__ __attribute__((aligned(16))) double cols[];  // [2][kRW][KS] beta, then [2][kRW] state scores
-    constexpr int G = kRW / LP;
-    const double ninf = -INFINITY;
-    const int KS = m | 1, top = m - 1;
-    const int lane = threadIdx.x, i = lane & (LP - 1), row0 = lane - i;
-    const long long c = static_cast<long long>(blockIdx.x) * G + lane / LP;
-    const bool valid = c < n_contigs;
-    int g0 = 0, T = 0;
-    if (valid) {
-        g0 = contig_ptr[c];
-        T = contig_ptr[c + 1] - g0;
-        T = T < 0 ? 0 : T;
-    }
-    const bool on = i < L;
-    const int ii = on ? i : 0;
+__global__ void __launch_bounds__(kWalkLanes) gl_minrun_backward(const double *__restrict__ state, const double *__restrict__ trans,
+                                                                 const int32_t *__restrict__ contig_ptr, const int L,
+                                                                 const int n_contigs, const int m, const uint32_t set_mask,
+                                                                 const double *__restrict__ fwd, const double *__restrict__ lognorm_c,
+                                                                 double *__restrict__ marg, double *__restrict__ inside_out) {
+    extern __shared__ __attribute__((aligned(16))) double cols_lds[];  // [2][kWalkLanes][m | 1] beta, then [2][kWalkLanes] state scores
+    const double ninf = kWalkNinf;
+    const int top = m - 1;
+    const WalkGroup<LP> g(contig_ptr, n_contigs, L);
+    const int lane = g.lane, i = g.j, ii = g.jj, T = g.T;
+    const bool on = g.on;
     const bool inside = (set_mask >> i) & 1u;
-    const double lz = valid ? lognorm_c[c] : ninf;
+    const double lz = g.valid ? lognorm_c[g.c] : ninf;
     const bool feasible = lz > ninf;
     double trow[LP];
-#pragma unroll
-    for (int k = 0; k < LP; ++k) trow[k] = k < L ? trans[ii * L + k] : 0.0;
-    double *const buf0 = cols, *const buf1 = cols + kRW * KS;
-    double *const sb0 = cols + 2 * kRW * KS, *const sb1 = sb0 + kRW;
-    const double *st = state + static_cast<size_t>(g0) * L + ii;
+    g.template load_trans<true>(trans, L, trow);
+    const double *st = g.column(state, L);
+    const WalkColumns cols(cols_lds, m);
+    const int KS = cols.KS;
+    double *const sb0 = cols_lds + 2 * kWalkLanes * KS, *const sb1 = sb0 + kWalkLanes;
     // the state score of the gene u steps before the last one
-    const auto fetch = [&](int u) { return u < T ? (on ? st[static_cast<size_t>(T - 1 - u) * L] : ninf) : 0.0; };
+    const auto fetch = [&](int u) { return g.state_at(st, L, u < T, T - 1 - u); };
     // one gene's outputs; every lane of the wave comes here
     const auto emit = [&](const bool act, const int t, const double p) {
-        const size_t g = static_cast<size_t>(g0) + static_cast<size_t>(act ? t : 0);
-        if (marg && act && on) marg[g * L + ii] = p;
+        const size_t gene = static_cast<size_t>(g.g0) + static_cast<size_t>(act ? t : 0);
+        if (marg && act && on) marg[gene * L + ii] = p;
         if (inside_out) {  // (wave-uniform)
             const double s = group_sum<LP>(inside && on ? p : 0.0);
-            if (act && i == 0) inside_out[g] = s;
+            if (act && i == 0) inside_out[gene] = s;
         }
     };
     {
-        for (int k = 0; k < KS; ++k) {
-            buf0[lane * KS + k] = (on && k == top) ? 0.0 : ninf;
-            buf1[lane * KS + k] = ninf;
-        }
+        cols.fill(lane, on ? top : -1, 0.0);
         sb0[lane] = fetch(0);
         sb1[lane] = ninf;
         double p = 0.0;
         if (T > 0 && on) {  // the last gene: beta is 0 at the one admissible state of the label
-            const double a = fwd[((static_cast<size_t>(g0) + static_cast<size_t>(T - 1)) * L + ii) * static_cast<size_t>(m) + top];
+            const double a = fwd[((static_cast<size_t>(g.g0) + static_cast<size_t>(T - 1)) * L + ii) * static_cast<size_t>(m) + top];
             p = (feasible && a > ninf) ? exp(a - lz) : 0.0;
         }
         emit(T > 0, T - 1, p);
@@ -297,13 +224,13 @@ __global__ void __launch_bounds__(kRW) gl_minrun_backward(const double *__restri
     const auto step = [&](const int u, const double s_t) {
         const int t = T - 2 - u;
         const bool act = t >= 0;
-        const double *prev = ((u & 1) ? buf1 : buf0) + row0 * KS;
-        const double *sprev = ((u & 1) ? sb1 : sb0) + row0;
-        double *mine = ((u & 1) ? buf0 : buf1) + lane * KS;
+        const double *prev = cols.gen(u) + g.row0 * KS;
+        const double *sprev = ((u & 1) ? sb1 : sb0) + g.row0;
+        double *mine = cols.gen(u + 1) + lane * KS;
         double ts[LP];  // what every successor label costs on top of its beta
 #pragma unroll
         for (int k = 0; k < LP; ++k) ts[k] = trow[k] + sprev[k];
-        const size_t ak = ((static_cast<size_t>(g0) + static_cast<size_t>(act ? t : 0)) * L + ii) * static_cast<size_t>(m);
+        const size_t ak = ((static_cast<size_t>(g.g0) + static_cast<size_t>(act ? t : 0)) * L + ii) * static_cast<size_t>(m);
         double p = 0.0;
 #pragma unroll 1
         for (int d = 0; d < m; ++d) {
@@ -318,15 +245,11 @@ __global__ void __launch_bounds__(kRW) gl_minrun_backward(const double *__restri
                     const bool in_k = (set_mask >> k) & 1u;
                     const int slot = inside ? slot_in : (in_k ? 0 : top);
                     const double v = prev[k * KS + slot] + ts[k];
-                    f((every || in_k) ? v : ninf);
+                    f(k, (every || in_k) ? v : ninf, false);
                 }
             };
-            double mx = ninf;
-            successors([&](double v) { mx = v > mx ? v : mx; });
-            const double shift = mx > ninf ? mx : 0.0;
-            double sum = 0.0;
-            successors([&](double v) { sum += v > ninf ? exp(v - shift) : 0.0; });
-            const double b = (on && mx > ninf) ? mx + log(sum) : ninf;
+            const WalkSum r = walk_sum(successors);
+            const double b = (on && r.finite) ? r.value : ninf;
             if (act && own) {
                 mine[d] = b;
                 const double ab = a + b;
@@ -337,41 +260,22 @@ __global__ void __launch_bounds__(kRW) gl_minrun_backward(const double *__restri
         emit(act, t, p);
         __syncthreads();
     };
-    double nxt[kRTile];
-#pragma unroll
-    for (int k = 0; k < kRTile; ++k) nxt[k] = fetch(1 + k);
-    for (int ub = 0; __any(ub < T - 1); ub += kRTile) {
-        double cur[kRTile];
-#pragma unroll
-        for (int k = 0; k < kRTile; ++k) cur[k] = nxt[k];
-#pragma unroll
-        for (int k = 0; k < kRTile; ++k) nxt[k] = fetch(ub + kRTile + 1 + k);
-#pragma unroll
-        for (int k = 0; k < kRTile; ++k) {
-            if (!__any(ub + k < T - 1)) break;  // (wave-uniform)
-            step(ub + k, cur[k]);
-        }
-    }
+    contig_walk(0, T - 1, [&](int u) { return fetch(u + 1); }, step);
 }
 
 template <int LP, bool SUM, bool STORE = false>
 void launch_forward(const GenArgs &a, uint32_t set_mask, int32_t m, uint8_t *back, int8_t *y, double *out, hipStream_t stream,
                     double *fwd = nullptr) {
-    constexpr int G = kRW / LP;
-    const unsigned blocks = static_cast<unsigned>((static_cast<long long>(a.n_contigs) + G - 1) / G);
-    const size_t lds = size_t(2) * kRW * size_t(m | 1) * sizeof(double);
-    hipLaunchKernelGGL((gl_minrun_forward<LP, SUM, STORE>), dim3(blocks), dim3(kRW), lds, stream, a.state, a.trans, a.contig_ptr, a.L,
-                       a.n_contigs, m, set_mask, back, y, out, fwd);
+    hipLaunchKernelGGL((gl_minrun_forward<LP, SUM, STORE>), dim3(walk_blocks<LP>(a.n_contigs)), dim3(kWalkLanes), walk_lds_bytes(m), stream,
+                       a.state, a.trans, a.contig_ptr, a.L, a.n_contigs, m, set_mask, back, y, out, fwd);
 }
 
 template <int LP>
 void launch_backward(const GenArgs &a, uint32_t set_mask, int32_t m, const double *fwd, const double *lognorm_c, double *marg,
                      double *inside, hipStream_t stream) {
-    constexpr int G = kRW / LP;
-    const unsigned blocks = static_cast<unsigned>((static_cast<long long>(a.n_contigs) + G - 1) / G);
-    const size_t lds = (size_t(2) * kRW * size_t(m | 1) + size_t(2) * kRW) * sizeof(double);
-    hipLaunchKernelGGL((gl_minrun_backward<LP>), dim3(blocks), dim3(kRW), lds, stream, a.state, a.trans, a.contig_ptr, a.L,
-                       a.n_contigs, m, set_mask, fwd, lognorm_c, marg, inside);
+    const size_t lds = walk_lds_bytes(m) + size_t(2) * kWalkLanes * sizeof(double);  // (the columns, then the state scores)
+    hipLaunchKernelGGL((gl_minrun_backward<LP>), dim3(walk_blocks<LP>(a.n_contigs)), dim3(kWalkLanes), lds, stream, a.state, a.trans,
+                       a.contig_ptr, a.L, a.n_contigs, m, set_mask, fwd, lognorm_c, marg, inside);
 }
 
 }  // namespace
@@ -382,9 +286,7 @@ size_t minrun_back_bytes(int64_t n_genes, int32_t L, int32_t min_run) {
 
 hipError_t launch_gen_min_run(const GenArgs &a, uint32_t set_mask, int32_t min_run, uint8_t *back, int8_t *y, double *score,
                               double *lognorm_min_run, hipStream_t stream) {
-    const uint32_t beyond = a.L >= 32 ? 0u : ~0u << a.L;
-    if (a.L <= 0 || a.L > kGenMaxL || min_run < 1 || min_run > kMaxMinRun || set_mask == 0 || (set_mask & beyond))
-        return hipErrorNotSupported;
+    if (!walk_counter_ok(a, set_mask, min_run, kMaxMinRun)) return hipErrorNotSupported;
     if (a.n_contigs <= 0) return hipSuccess;
     if (!a.state || !a.trans || !back || !y || !score) return hipErrorNotSupported;
     dispatch_lp(a.L, [&](auto lp) { launch_forward<lp, false>(a, set_mask, min_run, back, y, score, stream); });
@@ -404,9 +306,7 @@ size_t minrun_forward_bytes(int64_t n_genes, int32_t L, int32_t min_run) {
 
 hipError_t launch_gen_min_run_marginals(const GenArgs &a, uint32_t set_mask, int32_t min_run, double *fwd, double *marg,
                                         double *inside, double *lognorm_min_run, hipStream_t stream) {
-    const uint32_t beyond = a.L >= 32 ? 0u : ~0u << a.L;
-    if (a.L <= 0 || a.L > kGenMaxL || min_run < 1 || min_run > kMaxMinRun || set_mask == 0 || (set_mask & beyond))
-        return hipErrorNotSupported;
+    if (!walk_counter_ok(a, set_mask, min_run, kMaxMinRun)) return hipErrorNotSupported;
     if (a.n_contigs <= 0) return hipSuccess;
     if (!a.state || !a.trans || !fwd || !lognorm_min_run || (!marg && !inside)) return hipErrorNotSupported;
     dispatch_lp(a.L, [&](auto lp) { launch_forward<lp, true, true>(a, set_mask, min_run, nullptr, nullptr, lognorm_min_run, stream, fwd); });

@@ -1403,17 +1403,21 @@ int plan_run_viterbi_kbest(Plan &p, const DeviceCsr &csr, int32_t k, uint16_t *d
     return check_hip(launch_gen_kbest(g, k, d_back, d_fin, d_y, d_score, d_n_paths, stream), "k-best launch");
 }
 
+// the label set of a run-counter query: not empty, and no label at or above the model's
+static bool set_mask_ok(const Plan &p, uint32_t set_mask) {
+    const int32_t L = p.model ? p.model->L : 32;  // (a plan that was never built is check_plan's to refuse)
+    if (set_mask != 0 && (L >= 32 || !(set_mask >> L))) return true;
+    set_error("set_mask is empty, or holds a label at or above num_labels");
+    return false;
+}
+
 int plan_run_viterbi_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t min_run, uint8_t *d_back, int8_t *d_y,
                              double *d_score, double *d_lognorm_min_run, double *d_marg, double *d_lognorm, hipStream_t stream) {
     if (min_run < 1 || min_run > kMaxMinRun) {
         set_error("min_run outside 1 .. 32");
         return GECCO_CRF_EINVAL;
     }
-    const int32_t L = p.model ? p.model->L : 32;  // (a plan that was never built is check_plan's to refuse)
-    if (set_mask == 0 || (L < 32 && (set_mask >> L))) {
-        set_error("set_mask is empty, or holds a label at or above num_labels");
-        return GECCO_CRF_EINVAL;
-    }
+    if (!set_mask_ok(p, set_mask)) return GECCO_CRF_EINVAL;
     int rc;
     if (ends_here(p.n_contigs == 0 || p.n_genes == 0, !csr.gene_ptr || !d_marg || !d_back || !d_y || !d_score, rc)) return rc;
     GenArgs g;  // (the pass gives log Z; the run-counter recursion reads the raw state scores and nothing else)
@@ -1427,11 +1431,7 @@ int plan_run_marginals_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask,
         set_error("min_run outside 1 .. 32");
         return GECCO_CRF_EINVAL;
     }
-    const int32_t L = p.model ? p.model->L : 32;  // (a plan that was never built is check_plan's to refuse)
-    if (set_mask == 0 || (L < 32 && (set_mask >> L))) {
-        set_error("set_mask is empty, or holds a label at or above num_labels");
-        return GECCO_CRF_EINVAL;
-    }
+    if (!set_mask_ok(p, set_mask)) return GECCO_CRF_EINVAL;
     int rc;
     if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
                   !csr.gene_ptr || !d_marg || !d_fwd || !d_lognorm_min_run || (!d_marg_min_run && !d_inside), rc))
@@ -1448,11 +1448,7 @@ int plan_run_run_counts(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_
         set_error("max_runs outside 1 .. 32");
         return GECCO_CRF_EINVAL;
     }
-    const int32_t L = p.model ? p.model->L : 32;  // (a plan that was never built is check_plan's to refuse)
-    if (set_mask == 0 || (L < 32 && (set_mask >> L))) {
-        set_error("set_mask is empty, or holds a label at or above num_labels");
-        return GECCO_CRF_EINVAL;
-    }
+    if (!set_mask_ok(p, set_mask)) return GECCO_CRF_EINVAL;
     int rc;
     if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
                   !csr.gene_ptr || !d_marg || (!d_log_mass && !d_score) || (d_score && (!d_back || !d_y)), rc))

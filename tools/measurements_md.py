@@ -2,7 +2,8 @@
 """profiles/MEASUREMENTS.md from the committed records of the round (profiles/r06_*): every number in that file is read from the
 file it names, so the document cannot drift from the records.   usage: python tools/measurements_md.py > profiles/MEASUREMENTS.md
 (the head of the file, §1 to §7); python tools/measurements_md.py --section 7m prints §7m from profiles/runs_bench.jsonl,
---section 7n prints §7n from profiles/minrun_marginals_bench.jsonl, --section 7o prints §7o from profiles/counts_bench.jsonl."""
+--section 7n prints §7n from profiles/minrun_marginals_bench.jsonl, --section 7o prints §7o from profiles/counts_bench.jsonl,
+--section walk prints the contig-walk refactor's section from profiles/walk_refactor_ab.txt and profiles/walk_bits.txt."""
 import json
 import os
 import re
@@ -225,6 +226,29 @@ def section_7o():
     print_wrapped(out)
 
 
+def section_walk():
+    """The contig-walk refactor's section from profiles/walk_refactor_ab.txt and profiles/walk_bits.txt (``python
+    tools/measurements_md.py --section walk``): appended to MEASUREMENTS.md behind the lattice refactor's."""
+    ab = [ln.rstrip("\n") for ln in open(os.path.join(P, "walk_refactor_ab.txt"))]
+    bits = [ln for ln in open(os.path.join(P, "walk_bits.txt")) if ln.strip()]
+    kernels = [ln for ln in ab if " | parent " in ln and " | change " in ln]
+    tally = [ln for ln in ab if ln.startswith("inside ")][-1]
+    whole = [ln for ln in ab if ln.startswith("figures whose every run")][-1]
+    cases = sum(int(ln.split(" | cases ")[1].split(" ")[0]) for ln in bits)
+    out = []
+    A = out.append
+    A("## One contig-walk frame for the K-best, min-run and run-count kernels, parent commit against the change (`walk_refactor_ab.txt`, "
+      "`walk_bits.txt`)\n")
+    A("`crf_contig_walk.hpp` holds the frame of `gl_kbest_forward`, `gl_minrun_forward`, `gl_minrun_backward` and `gl_counts_forward` once "
+      "(DESIGN.md §4.9i, k, m, n).  **Resources**: `walk_refactor_ab.txt` opens with the `-Rpass-analysis=kernel-resource-usage` table of "
+      f"the {len(kernels)} kernels of the three files in both builds; {[ln for ln in ab if ln.startswith('conditions missed')][-1]} (no scratch "
+      "anywhere, no kernel's occupancy below its parent's).  **Bits**: `tools/walk_bits.py` under `GECCO_CRF_LIBRARY` with the parent's library "
+      f"and the change's in one job gave the same file, {cases} cases in {len(bits)} blocks (`walk_bits.txt` is the short form).  **Time**: "
+      "`tools/bench_kbest.py`, `tools/bench_minrun.py`, `tools/bench_counts.py` at their defaults and `bench.py`, parent and change "
+      f"alternating on one MI355X, three pairs, every run against the parent's own range: {tally}; {whole}.\n")
+    print_wrapped(out)
+
+
 def print_wrapped(out):
     import textwrap
 
@@ -247,6 +271,8 @@ def main():
         return section_7n()
     if sys.argv[1:] == ["--section", "7o"]:
         return section_7o()
+    if sys.argv[1:] == ["--section", "walk"]:
+        return section_walk()
     c3, c3d = J("bench_c3_detail"), J("bench_c3_driver_command_detail")
     line = open(os.path.join(P, f"{TAG}_bench_c3_driver_command.json")).read().strip()
     c1, c2, c5, two = J("bench_c1_detail"), J("bench_c2_detail"), J("bench_c5_detail"), J("bench_c3_two_launch_detail")
