@@ -22,7 +22,7 @@
 // over the group by crf_lanes.hpp's butterflies: one order of operations in every lane.  No atomics anywhere.
 #pragma once
 #include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_lane_group.hpp"
 
 #include <cmath>
 
@@ -173,8 +173,7 @@ __device__ __forceinline__ double group_lse(const double v) {
 // Host side: a launch of one wave per 64 / LP contigs, and the LDS bytes of its columns
 template <int LP>
 unsigned walk_blocks(const int32_t n_contigs) {
-    constexpr int G = kWalkLanes / LP;
-    return static_cast<unsigned>((static_cast<long long>(n_contigs) + G - 1) / G);
+    return group_blocks(n_contigs, kWalkLanes / LP);
 }
 inline size_t walk_lds_bytes(const int32_t slots) { return size_t(2) * kWalkLanes * size_t(slots | 1) * sizeof(double); }
 // what a launcher of a counter lattice takes: a label count and a counter limit inside the kernels' range, and a label set that

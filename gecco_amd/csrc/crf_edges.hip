@@ -5,8 +5,8 @@
 // the marginals in the caller's buffer; an edge reads the two genes it joins and nothing else, so this is the lattice query
 // that is parallel over genes.
 //
-// Layout as in gl_span_logp: LP = L rounded up to a power of two, LP consecutive lanes ("a group", never straddling a wave),
-// lane j holds column j of exp(trans) in registers.  A group walks one RUN: kEdgeRunGenes consecutive genes of one contig,
+// Layout: one group of lanes per run, on the frame of crf_lane_group.hpp (its geometry; the xi product below is the kernel's
+// own).  A group walks one RUN: kEdgeRunGenes consecutive genes of one contig,
 // counted from the contig's first gene (not the batch's), so that what a contig gets does not depend on its place in the
 // batch.  Per gene every lane loads alpha, E and marg of its label once; the previous gene's come along in registers.
 //   directions: alpha_{t-1} and w_t(j) = E_t(j) marg_t(j) / alpha_t(j) (0 where alpha_t(j) is 0; the backward direction of
@@ -26,7 +26,7 @@
 // partials in run order.  No atomics anywhere: equal calls give equal bytes.  (Nothing here is specified as an exact difference
 // of two like recursions: the file is compiled with floating-point contraction left on.)
 #include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_lane_group.hpp"
 
 #include <cfloat>
 
@@ -46,10 +46,10 @@ __global__ void __launch_bounds__(kET) gl_edge_runs(GenArgs a, EdgeQuery q) {
         tt[e] = (i < L && k < L) ? a.trans[i * L + k] : 0.0;
     }
     __syncthreads();
-    constexpr int G = kET / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *va = vecs[0] + grp * LP, *vw = vecs[1] + grp * LP, *vl = vecs[2] + grp * LP;
-    const long long r = static_cast<long long>(blockIdx.x) * G + grp;
+    const LaneGroup<LP, kET> g{};
+    const int j = g.j;
+    double *va = vecs[0] + g.slot, *vw = vecs[1] + g.slot, *vl = vecs[2] + g.slot;
+    const long long r = g.item;
     if (r >= q.n_runs) return;
     const EdgeRun run = q.runs[r];
     const int g0 = a.contig_ptr[run.contig], g1 = a.contig_ptr[run.contig + 1];
@@ -100,7 +100,7 @@ __global__ void __launch_bounds__(kET) gl_edge_runs(GenArgs a, EdgeQuery q) {
             va[j] = ah;
             vw[j] = wh;
             if (q.hpart) vl[j] = wh > 0.0 ? log(wh) : 0.0;
-            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_wave_barrier();  // (the kernel's own exchange: three slots, read until the end of the step)
             double col = 0.0;
 #pragma unroll
             for (int i = 0; i < LP; ++i) {
@@ -193,8 +193,7 @@ __global__ void __launch_bounds__(kET) gl_edge_reduce(EdgeQuery q, const int L, 
 
 template <int LP>
 void launch_runs(const GenArgs &a, const EdgeQuery &q, hipStream_t stream) {
-    constexpr int G = kET / LP;
-    hipLaunchKernelGGL(gl_edge_runs<LP>, dim3(unsigned((static_cast<long long>(q.n_runs) + G - 1) / G)), dim3(kET), 0, stream, a, q);
+    hipLaunchKernelGGL(gl_edge_runs<LP>, dim3(group_blocks(q.n_runs, LaneGroup<LP, kET>::G)), dim3(kET), 0, stream, a, q);
 }
 
 }  // namespace
@@ -210,7 +209,7 @@ hipError_t launch_gen_edges(const GenArgs &a, const EdgeQuery &q, hipStream_t st
     }
     if ((q.transitions || q.entropy) && a.n_contigs > 0) {
         const long long entries = (static_cast<long long>(a.L) * a.L + 1) * a.n_contigs;
-        hipLaunchKernelGGL(gl_edge_reduce, dim3(unsigned((entries + kET - 1) / kET)), dim3(kET), 0, stream, q, a.L, a.n_contigs);
+        hipLaunchKernelGGL(gl_edge_reduce, dim3(group_blocks(entries, kET)), dim3(kET), 0, stream, q, a.L, a.n_contigs);
     }
     return hipGetLastError();
 }

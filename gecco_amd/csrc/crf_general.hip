@@ -4,12 +4,9 @@
 // `GECCO_CRF_FORCE_GENERAL=1` routes 2-label models through these kernels so the tests can cross-check the specialised
 // kernels on the device.
 //
-// Layout: LP = L rounded up to a power of two; LP consecutive lanes ("a group", never straddling
-// a wave) own one contig, lane j holds component j of the alpha / beta / delta
-// vector.  A step is a vector x (L x L) product: the previous vector goes through one LDS slot
-// per lane and comes back as L broadcast reads; the lane's column (forward) and row (backward)
-// of the transition matrix stay in registers.  LDS traffic of one wave is in order and groups
-// live inside a wave, so no barrier is needed and groups may run different trip counts.
+// Layout: a group of LP lanes per contig, chunk or chunk row, lane j holding component j of the alpha / beta / delta vector;
+// crf_lane_group.hpp has the geometry and the products through the group's LDS slot, and describes the registers of the table.  (The
+// wave-per-contig and matrix-core kernels below have layouts and exchanges of their own.)
 //
 // Arithmetic follows [EXT] CRFsuite crf1d_context.c in its own order (alpha: sum over the
 // source label in index order, then * exp(state), then 1/sum scaling; beta: row . (beta o exp(state))
@@ -17,7 +14,7 @@
 // one deliberate difference: exp(state - max_y state) instead of exp(state), which cancels in
 // every marginal and is added back to the log-partition.
 #include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_lane_group.hpp"
 
 #include <cfloat>
 
@@ -50,6 +47,7 @@ __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene
                                                 double *__restrict__ state, double *__restrict__ E,
                                                 double *__restrict__ smax, const double *__restrict__ attr_value,
                                                 const uint32_t *__restrict__ allowed) {
+    // (the gene from the flat lane index: LaneGroup's item is the same number, formed another way, and compiles to other code)
     const int j = threadIdx.x & (LP - 1);
     const long long g = (static_cast<long long>(blockIdx.x) * kGT + threadIdx.x) / LP;
     if (g >= n_genes) return;
@@ -87,10 +85,10 @@ __global__ void __launch_bounds__(kGT) gl_state(const int32_t *__restrict__ gene
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
     __shared__ double vecs[kGT];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vec = vecs + grp * LP;
-    const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    double *vec = vecs + g.slot;
+    const long long ci = g.item;
     if (ci >= a.n_contigs) return;
     const int L = a.L;
     const int g0 = a.contig_ptr[ci], T = a.contig_ptr[ci + 1] - g0;
@@ -118,13 +116,7 @@ __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
         if (t == 0) {
             v = e;
         } else {
-            vec[j] = v;
-            __builtin_amdgcn_wave_barrier();
-            double acc = 0.0;
-#pragma unroll
-            for (int i = 0; i < LP; ++i) acc = fma(vec[i], mcol[i], acc);
-            __builtin_amdgcn_wave_barrier();
-            v = acc * e;
+            v = sum_product(vec, j, v, mcol) * e;
         }
         const double s = group_sum<LP>(v);
         c = s != 0.0 ? 1.0 / s : 1.0;
@@ -149,13 +141,7 @@ __global__ void __launch_bounds__(kGT) gl_marginals_seq(GenArgs a) {
             c_p = __shfl(j == 0 ? scale[t - 1] : 0.0, 0, LP);
             e1 = on ? E[static_cast<size_t>(t) * L + jj] : 0.0;
         }
-        vec[j] = b * et1;
-        __builtin_amdgcn_wave_barrier();
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < LP; ++i) acc = fma(mrow[i], vec[i], acc);
-        __builtin_amdgcn_wave_barrier();
-        b = acc * ct;
+        b = sum_product<true>(vec, j, b * et1, mrow) * ct;
         if (on) marg[static_cast<size_t>(t) * L + j] = gl_prob(al_t * b / ct);
     }
 }
@@ -169,11 +155,11 @@ template <int LP, bool FIX = false>
 __global__ void __launch_bounds__(kGT) gl_viterbi_seq(GenArgs a) {
     __shared__ double vecs[kGT];
     __shared__ uint8_t rows[kGT * kBackRows];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vec = vecs + grp * LP;
-    uint8_t *row = rows + grp * LP * kBackRows;
-    const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    double *vec = vecs + g.slot;
+    uint8_t *row = rows + g.slot * kBackRows;
+    const long long ci = g.item;
     if (ci >= a.n_contigs) return;
     if (FIX && !a.fix_flag[ci]) return;  // (group-uniform)
     const int L = a.L;
@@ -199,25 +185,11 @@ __global__ void __launch_bounds__(kGT) gl_viterbi_seq(GenArgs a) {
     for (int t = 1; t < T; ++t) {
         const double s_t = s_next;
         if (t + 1 < T) s_next = on ? st[static_cast<size_t>(t + 1) * L + jj] : 0.0;
-        vec[j] = d;
-        __builtin_amdgcn_wave_barrier();
-        double best = -DBL_MAX;
-        int arg = -1;
-#pragma unroll
-        for (int i = 0; i < LP; ++i) {
-            if (i < L) {
-                const double s = vec[i] + tcol[i];
-                if (best < s) {
-                    best = s;
-                    arg = i;
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (on) back[static_cast<size_t>(t) * L + j] = static_cast<uint8_t>(arg < 0 ? 0 : arg);
-        d = best + s_t;
+        const MaxPlusArg m = max_plus_arg(vec, j, d, tcol, L);
+        if (on) back[static_cast<size_t>(t) * L + j] = static_cast<uint8_t>(m.arg < 0 ? 0 : m.arg);
+        d = m.best + s_t;
     }
-    // end label = first arg max; back-tracking by lane 0, rows staged through LDS in chunks
+    // end label = first arg max; back-tracking by lane 0, rows staged through LDS in chunks (exchanges of their own: no product)
     vec[j] = d;
     __builtin_amdgcn_wave_barrier();
     int y = 0;
@@ -652,11 +624,11 @@ constexpr int kZeroRowEx = -(1 << 24);
 template <int LP, bool MAXPLUS>
 __global__ void __launch_bounds__(kGT) gl_chunk_rows(GenArgs a) {
     __shared__ double vecs[kGT];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vec = vecs + grp * LP;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    double *vec = vecs + g.slot;
     const int L = a.L;
-    const long long q = static_cast<long long>(blockIdx.x) * G + grp;
+    const long long q = g.item;
     if (q >= static_cast<long long>(a.n_chunks) * L) return;
     const int ci = int(q / L), i = int(q % L);
     const int g0 = a.ch_g0[ci], g1 = gl_chunk_end(a, ci);
@@ -677,19 +649,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_rows(GenArgs a) {
         if (t == cfirst) {
             v = e;  // every row: the first gene forgets what entered
         } else {
-            vec[j] = v;
-            __builtin_amdgcn_wave_barrier();
-            double acc = MAXPLUS ? ninf : 0.0;
-#pragma unroll
-            for (int k = 0; k < LP; ++k) {
-                if (MAXPLUS) {
-                    if (k < L) acc = fmax(acc, vec[k] + mcol[k]);
-                } else {
-                    acc = fma(vec[k], mcol[k], acc);
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            v = MAXPLUS ? acc + e : acc * e;
+            v = MAXPLUS ? max_plus(vec, j, v, mcol, L) + e : sum_product(vec, j, v, mcol) * e;
         }
         if (!MAXPLUS) {  // exact power-of-two scaling of the row, exponent kept
             mx = group_max<LP>(on ? v : 0.0);
@@ -854,13 +814,15 @@ __device__ __forceinline__ void chunk_walk_fwd(const GenArgs &a, long long ct, i
                         const double exm = group_max<LP>((on && v > 0.0) ? double(ex[b]) : -1e300);
                         w = (on && v > 0.0) ? ldexp(v, ex[b] - int(exm)) : 0.0;
                     }
-                    vec[j] = w;
-                    __builtin_amdgcn_wave_barrier();
-                    double acc = MAXPLUS ? ninf : 0.0;
+                    double acc = MAXPLUS ? max_plus(vec, j, w, mc[b], L) : 0.0;
+                    if (!MAXPLUS) {  // (written out: this sum, alone among the forward products, leaves out the labels that do not exist)
+                        vec[j] = w;
+                        __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                    for (int k = 0; k < LP; ++k)
-                        if (k < L) acc = MAXPLUS ? fmax(acc, vec[k] + mc[b][k]) : fma(vec[k], mc[b][k], acc);
-                    __builtin_amdgcn_wave_barrier();
+                        for (int k = 0; k < LP; ++k)
+                            if (k < L) acc = fma(vec[k], mc[b][k], acc);
+                        __builtin_amdgcn_wave_barrier();
+                    }
                     if (MAXPLUS) {
                         v = acc;
                     } else {
@@ -910,6 +872,7 @@ __device__ __forceinline__ void chunk_walk_bwd(const GenArgs &a, long long ct, i
             if (c >= c0) {
                 if (on) a.chB[static_cast<size_t>(c) * L + j] = bt;
                 if (c > c0) {  // beta of the gene before the chunk = M_c beta: lane j takes row j
+                    // (written out: likewise, alone among the backward products)
                     vec[j] = on ? bt : 0.0;
                     __builtin_amdgcn_wave_barrier();
                     double acc = 0.0;
@@ -930,9 +893,9 @@ __device__ __forceinline__ void chunk_walk_bwd(const GenArgs &a, long long ct, i
 template <int LP, bool MAXPLUS>
 __global__ void __launch_bounds__(kGT) gl_chunk_vecs(GenArgs a) {
     __shared__ double vecs[kGT];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    const long long ct = static_cast<long long>(blockIdx.x) * G + grp;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    const long long ct = g.item;
     if (ct >= a.n_contigs) return;
     // a contig without genes has no chunk, so none of the chunk kernels writes its log-partition / path score: 0, as the
     // contig-sequential kernels give it
@@ -941,20 +904,20 @@ __global__ void __launch_bounds__(kGT) gl_chunk_vecs(GenArgs a) {
         if (MAXPLUS && a.score) a.score[ct] = 0.0;
     }
     if (MAXPLUS || blockIdx.y == 0)
-        chunk_walk_fwd<LP, MAXPLUS>(a, ct, j, vecs + grp * LP);
+        chunk_walk_fwd<LP, MAXPLUS>(a, ct, j, vecs + g.slot);
     else
-        chunk_walk_bwd<LP>(a, ct, j, vecs + grp * LP);
+        chunk_walk_bwd<LP>(a, ct, j, vecs + g.slot);
 }
 
 // CRFsuite's forward recursion inside a chunk, from the vector that enters it
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_chunk_fwd(GenArgs a) {
     __shared__ double vecs[kGT];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vec = vecs + grp * LP;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    double *vec = vecs + g.slot;
     const int L = a.L;
-    const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
+    const long long ci = g.item;
     if (ci >= a.n_chunks) return;
     const int g0 = a.ch_g0[ci], g1 = gl_chunk_end(a, ci);
     const int cfirst = a.contig_ptr[a.ch_contig[ci]];
@@ -970,13 +933,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_fwd(GenArgs a) {
         if (t == cfirst) {
             v = e;
         } else {
-            vec[j] = v;
-            __builtin_amdgcn_wave_barrier();
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < LP; ++k) acc = fma(vec[k], mcol[k], acc);
-            __builtin_amdgcn_wave_barrier();
-            v = acc * e;
+            v = sum_product(vec, j, v, mcol) * e;
         }
         const double sm = group_sum<LP>(v);
         const double c = sm != 0.0 ? 1.0 / sm : 1.0;
@@ -993,11 +950,11 @@ __global__ void __launch_bounds__(kGT) gl_chunk_fwd(GenArgs a) {
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_chunk_bwd(GenArgs a) {
     __shared__ double vecs[kGT];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vec = vecs + grp * LP;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    double *vec = vecs + g.slot;
     const int L = a.L;
-    const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
+    const long long ci = g.item;
     if (ci >= a.n_chunks) return;
     const int g0 = a.ch_g0[ci], g1 = gl_chunk_end(a, ci);
     const bool on = j < L;
@@ -1021,13 +978,7 @@ __global__ void __launch_bounds__(kGT) gl_chunk_bwd(GenArgs a) {
         const double sm = group_sum<LP>(x);
         if (on) a.marg[static_cast<size_t>(t) * L + j] = sm != 0.0 ? x / sm : 0.0;
         if (t > g0) {
-            vec[j] = on ? b * a.E[static_cast<size_t>(t) * L + jj] : 0.0;
-            __builtin_amdgcn_wave_barrier();
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < LP; ++k) acc = fma(mrow[k], vec[k], acc);
-            __builtin_amdgcn_wave_barrier();
-            b = acc * a.scale[t - 1];  // CRFsuite's own scaling keeps beta near 1
+            b = sum_product<true>(vec, j, on ? b * a.E[static_cast<size_t>(t) * L + jj] : 0.0, mrow) * a.scale[t - 1];  // (CRFsuite's scaling)
         }
     }
 }
@@ -1036,11 +987,11 @@ __global__ void __launch_bounds__(kGT) gl_chunk_bwd(GenArgs a) {
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_chunk_vit(GenArgs a) {
     __shared__ double vecs[kGT];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vec = vecs + grp * LP;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
+    double *vec = vecs + g.slot;
     const int L = a.L;
-    const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
+    const long long ci = g.item;
     if (ci >= a.n_chunks) return;
     const int g0 = a.ch_g0[ci], g1 = gl_chunk_end(a, ci);
     const int ct = a.ch_contig[ci];
@@ -1065,29 +1016,12 @@ __global__ void __launch_bounds__(kGT) gl_chunk_vit(GenArgs a) {
             d = on ? s_t : -DBL_MAX;
             continue;
         }
-        vec[j] = d;
-        __builtin_amdgcn_wave_barrier();
-        double best = -DBL_MAX, second = -DBL_MAX;
-        int arg = -1;
-#pragma unroll
-        for (int k = 0; k < LP; ++k) {
-            if (k < L) {
-                const double sc = vec[k] + tcol[k];
-                if (best < sc) {
-                    second = best;
-                    best = sc;
-                    arg = k;
-                } else {
-                    second = fmax(second, sc);
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (on) a.back[static_cast<size_t>(t) * L + j] = static_cast<uint8_t>(arg < 0 ? 0 : arg);
-        inside |= on && L > 1 && best - second <= (4.0 * double(t - cfirst) + 8.0) * ulpM;
-        d = best + s_t;
+        const MaxPlusArg m = max_plus_arg<LP, true>(vec, j, d, tcol, L);
+        if (on) a.back[static_cast<size_t>(t) * L + j] = static_cast<uint8_t>(m.arg < 0 ? 0 : m.arg);
+        inside |= on && L > 1 && m.best - m.second <= (4.0 * double(t - cfirst) + 8.0) * ulpM;
+        d = m.best + s_t;
     }
-    if (g1 == cend) {  // first arg max of the final scores
+    if (g1 == cend) {  // first arg max of the final scores (no product: lane 0 alone reads the slot, and nothing is written to it again)
         vec[j] = d;
         __builtin_amdgcn_wave_barrier();
         if (j == 0) {
@@ -1121,10 +1055,10 @@ __global__ void __launch_bounds__(kGT) gl_chunk_vit(GenArgs a) {
 // per chunk: label of its last gene -> label of the gene before the chunk (lane y follows the back-pointers)
 template <int LP>
 __global__ void __launch_bounds__(kGT) gl_chunk_maps(GenArgs a) {
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
+    const LaneGroup<LP> g{};
+    const int j = g.j;
     const int L = a.L;
-    const long long ci = static_cast<long long>(blockIdx.x) * G + grp;
+    const long long ci = g.item;
     if (ci >= a.n_chunks || j >= L) return;
     const int g0 = a.ch_g0[ci], g1 = gl_chunk_end(a, ci);
     if (g0 == a.contig_ptr[a.ch_contig[ci]]) return;  // nothing before a contig's first chunk
@@ -1181,9 +1115,9 @@ __global__ void __launch_bounds__(kGT) gl_chunk_backtrack(GenArgs a) {
 
 template <int LP>
 hipError_t launch_chunked(int what, const GenArgs &a, hipStream_t stream) {
-    constexpr int G = kGT / LP;
+    constexpr int G = LaneGroup<LP>::G;
     const int rows_period = a.rows_rescale_period;
-    auto blocks = [](long long items, int per) { return dim3(unsigned((items + per - 1) / per)); };
+    auto blocks = [](long long items, int per) { return dim3(group_blocks(items, per)); };
     const long long rows = static_cast<long long>(a.n_chunks) * a.L;
     if (a.n_chunks <= 0) return hipSuccess;
     if (what == 2) {
@@ -1219,15 +1153,14 @@ hipError_t launch_chunked(int what, const GenArgs &a, hipStream_t stream) {
 
 template <int LP, bool kValued, bool kMasked>
 void launch_state(const GenArgs &a, hipStream_t stream, const double *attr_value, const uint32_t *allowed) {
-    hipLaunchKernelGGL((gl_state<LP, kValued, kMasked>), dim3(unsigned((static_cast<long long>(a.n_genes) + kGT / LP - 1) / (kGT / LP))),
-                       dim3(kGT), 0, stream, a.gene_ptr, a.attr_id, a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value, allowed);
+    hipLaunchKernelGGL((gl_state<LP, kValued, kMasked>), dim3(group_blocks(a.n_genes, LaneGroup<LP>::G)), dim3(kGT), 0, stream,
+                       a.gene_ptr, a.attr_id, a.wtab, a.L, a.A, a.n_genes, a.state, a.E, a.smax, attr_value, allowed);
 }
 
 template <int LP>
 hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const double *attr_value = nullptr,
                      const uint32_t *allowed = nullptr) {
-    constexpr int G = kGT / LP;
-    auto blocks = [](long long items, int per) { return dim3(unsigned((items + per - 1) / per)); };
+    const dim3 grid(group_blocks(a.n_contigs, LaneGroup<LP>::G));
     switch (what) {
     case 0:  // state scores
         if (a.n_genes > 0) {  // (attr_value, allowed: the same for every gene of the launch)
@@ -1244,10 +1177,10 @@ hipError_t launch_lp(int what, const GenArgs &a, hipStream_t stream, const doubl
         }
         break;
     case 2:
-        if (a.n_contigs > 0) hipLaunchKernelGGL(gl_marginals_seq<LP>, blocks(a.n_contigs, G), dim3(kGT), 0, stream, a);
+        if (a.n_contigs > 0) hipLaunchKernelGGL(gl_marginals_seq<LP>, grid, dim3(kGT), 0, stream, a);
         break;
     case 3:
-        if (a.n_contigs > 0) hipLaunchKernelGGL(gl_viterbi_seq<LP>, blocks(a.n_contigs, G), dim3(kGT), 0, stream, a);
+        if (a.n_contigs > 0) hipLaunchKernelGGL(gl_viterbi_seq<LP>, grid, dim3(kGT), 0, stream, a);
         break;
     }
     return hipGetLastError();
@@ -1271,21 +1204,15 @@ hipError_t launch_gen_viterbi(const GenArgs &a, hipStream_t stream) { return lau
 hipError_t launch_gen_marginals_wave(const GenArgs &a, hipStream_t stream) {
     if (a.L <= 8 || a.L > kGenMaxL) return hipErrorNotSupported;
     if (a.n_contigs <= 0) return hipSuccess;
-    const dim3 grid(unsigned((a.n_contigs + kGT / 64 - 1) / (kGT / 64)));
-    if (a.L <= 16)
-        hipLaunchKernelGGL(gl_marginals_wave<16>, grid, dim3(kGT), 0, stream, a);
-    else
-        hipLaunchKernelGGL(gl_marginals_wave<32>, grid, dim3(kGT), 0, stream, a);
+    const dim3 grid(group_blocks(a.n_contigs, kGT / 64));
+    dispatch_wave_lp(a.L, [&](auto lp) { hipLaunchKernelGGL(gl_marginals_wave<lp>, grid, dim3(kGT), 0, stream, a); });
     return hipGetLastError();
 }
 hipError_t launch_gen_viterbi_wave(const GenArgs &a, hipStream_t stream) {
     if (a.L <= 8 || a.L > kGenMaxL) return hipErrorNotSupported;
     if (a.n_contigs <= 0) return hipSuccess;
-    const dim3 grid(unsigned((a.n_contigs + kGT / 64 - 1) / (kGT / 64)));
-    if (a.L <= 16)
-        hipLaunchKernelGGL(gl_viterbi_wave<16>, grid, dim3(kGT), 0, stream, a);
-    else
-        hipLaunchKernelGGL(gl_viterbi_wave<32>, grid, dim3(kGT), 0, stream, a);
+    const dim3 grid(group_blocks(a.n_contigs, kGT / 64));
+    dispatch_wave_lp(a.L, [&](auto lp) { hipLaunchKernelGGL(gl_viterbi_wave<lp>, grid, dim3(kGT), 0, stream, a); });
     return hipGetLastError();
 }
 int gen_chunk_genes() { return kChunk; }

@@ -31,7 +31,7 @@
 // label in index order, then * exp(state), then 1/sum scaling; beta: row . (beta o exp(state)) then * scale; marginal =
 // alpha * beta / scale).
 #include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_lane_group.hpp"
 
 #include <cfloat>
 
@@ -68,10 +68,8 @@ __device__ __forceinline__ int slot_gene(const GenWinArgs &a, const int4 td, int
 }
 
 // ---- lane-group tier: one group per window start -------------------------------------------------------------------------
-// Layout: LP = L rounded up to a power of two; LP consecutive lanes ("a group", never straddling a wave) own one window,
-// lane j holds component j of the alpha / beta vector.  A step is a vector x (L x L) product: the previous vector goes
-// through LDS and comes back as L broadcast reads; the lane's column (forward) and row (backward) of the transition matrix
-// stay in registers.  LDS traffic of one wave is in order and groups live inside a wave, so no barrier is needed.
+// Layout: one group of lanes per window, on the frame of crf_lane_group.hpp; the forward steps read alpha-hat of the window
+// where it is kept in LDS and have no exchange of their own.
 // Written for up to 32 labels, it spends most of its time on that exchange (1.6 G genes/s at L = 3, 0.34 G at L = 16, 0.10 G
 // at L = 32, single label).
 // Outputs: atomicMax on the 64-bit patterns.  Marginals are non-negative (products and sums of non-negative numbers), and
@@ -83,13 +81,13 @@ __device__ __forceinline__ int slot_gene(const GenWinArgs &a, const int4 td, int
 template <int LP, bool kAll>
 __global__ void __launch_bounds__(kGT) gl_windowed(GenWinArgs a) {
     extern __shared__ double lds[];
-    constexpr int G = kGT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
+    const LaneGroup<LP, kGT> g{};
+    const int j = g.j, grp = g.grp;
     const int W = a.W, L = a.L;
     double *al = lds + static_cast<size_t>(grp) * W * LP;         // alpha-hat of every step
-    double *sc = lds + static_cast<size_t>(G) * W * LP + grp * W;  // scale factors
-    double *vec = lds + static_cast<size_t>(G) * W * (LP + 1) + grp * LP;
-    const long long q = static_cast<long long>(blockIdx.x) * G + grp;
+    double *sc = lds + static_cast<size_t>(g.G) * W * LP + grp * W;  // scale factors
+    double *vec = lds + static_cast<size_t>(g.G) * W * (LP + 1) + grp * LP;
+    const long long q = g.item;
     const bool active = q < a.S && ((a.start_bits[q >> 6] >> (q & 63)) & 1);
     int g0 = 0, n = 0, off = 0;
     if (active) {  // the scored contig owning slot q: its first gene, its number of genes
@@ -145,13 +143,7 @@ __global__ void __launch_bounds__(kGT) gl_windowed(GenWinArgs a) {
     for (int t = W - 1; t >= 0; --t) {
         const double ct = sc[t];
         if (t < W - 1) {
-            vec[j] = b * emis(t + 1);
-            __builtin_amdgcn_wave_barrier();
-            double acc = 0.0;
-#pragma unroll
-            for (int i = 0; i < LP; ++i) acc = fma(mrow[i], vec[i], acc);
-            b = acc * ct;
-            __builtin_amdgcn_wave_barrier();
+            b = sum_product<true>(vec, j, b * emis(t + 1), mrow) * ct;
         }
         const int gi = off + t;
         if constexpr (!kAll) {
@@ -475,14 +467,14 @@ __global__ void __launch_bounds__(256) gl_all_fill_nan(double *__restrict__ p_al
 
 template <int LP, bool kAll>
 hipError_t launch_groups(const GenWinArgs &a, hipStream_t stream) {
-    constexpr int G = kGT / LP;
+    constexpr int G = LaneGroup<LP, kGT>::G;
     const size_t lds = (size_t(G) * a.W * (LP + 1) + kGT) * sizeof(double);
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gl_windowed<LP, kAll>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
         if (e != hipSuccess) return e;
     }
-    const unsigned blocks = unsigned((static_cast<long long>(a.S) + G - 1) / G);
+    const unsigned blocks = group_blocks(a.S, G);
     hipLaunchKernelGGL((gl_windowed<LP, kAll>), dim3(blocks), dim3(kGT), lds, stream, a);
     return hipGetLastError();
 }

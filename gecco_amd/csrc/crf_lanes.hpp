@@ -47,6 +47,12 @@ auto dispatch_lp(int L, F &&f) {
     if (L <= 16) return f(std::integral_constant<int, 16>{});
     return f(std::integral_constant<int, 32>{});
 }
+// the same for the wave-per-contig kernels (gl_marginals_wave, gl_viterbi_wave: 9 to 32 labels), which have two instances
+template <class F>
+auto dispatch_wave_lp(int L, F &&f) {
+    if (L <= 16) return f(std::integral_constant<int, 16>{});
+    return f(std::integral_constant<int, 32>{});
+}
 
 }  // namespace
 }  // namespace gecco

@@ -6,10 +6,7 @@
 // Any number of queries behind ONE forward-backward pass of the batch (gl_state + any arrangement of the marginals recursion,
 // crf_general.hip), which leaves the raw state scores, E, alpha and the marginals; a query walks away from its anchor only.
 //
-// Layout as in gl_span_logp (crf_spans.hip): LP = L rounded up to a power of two, LP consecutive lanes ("a group", never
-// straddling a wave) own one walk, lane j holds component j.  A step is one matrix-vector product: the vector goes through one
-// LDS slot per lane and comes back as L broadcast reads.  LDS traffic of one wave is in order and groups live inside a wave, so
-// a scheduling barrier is all a step needs and groups may run different trip counts.  A LEFT walk multiplies by the rows of
+// Layout: one group of lanes per walk, on the frame of crf_lane_group.hpp.  A LEFT walk multiplies by the rows of
 // exp(trans) (d(k) = sum_j M(k, j) c(j)), a RIGHT walk by its columns: the kernel is templated on the direction and a lane
 // holds the one it needs, LP register pairs.  An anchor is two walks in two launches; a closed run is one right walk.
 //
@@ -31,7 +28,7 @@
 // no label of S, zero transitions, underflow -- writes -infinity for the rest and stops; never NaN.  Results are clipped at 0.
 // A walk is one fixed operation sequence: entry r does not depend on reach, nor on the other queries.  No atomics.
 #include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_lane_group.hpp"
 
 #include <cfloat>
 
@@ -73,10 +70,10 @@ struct Neighbour {
 template <int LP, bool RIGHT>
 __global__ void __launch_bounds__(kRT) gl_run_walk(GenArgs a, RunPosteriorArgs p) {
     __shared__ double vecs[2][kRT];
-    constexpr int G = kRT / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vf = vecs[0] + grp * LP, *vm = vecs[1] + grp * LP;
-    const long long q = static_cast<long long>(blockIdx.x) * G + grp;
+    const LaneGroup<LP, kRT> g{};
+    const int j = g.j;
+    double *vf = vecs[0] + g.slot, *vm = vecs[1] + g.slot;
+    const long long q = g.item;
     const int n_walks = RIGHT ? p.n_anchors + p.n_runs : p.n_anchors;
     if (q >= n_walks) return;
     const bool closed = RIGHT && q >= p.n_anchors;
@@ -123,6 +120,7 @@ __global__ void __launch_bounds__(kRT) gl_run_walk(GenArgs a, RunPosteriorArgs p
         Neighbour<!RIGHT> other;  // (a left walk starts from psi beta of gene a + 1, a right walk from alpha of gene a - 1)
         if (on) other.load(a, at);
         const double w = on ? other.value() : 0.0;
+        // (the pair of sums is written out, here and in the walk: with a helper for it the right walks compile to another schedule)
         vf[j] = w;
         vm[j] = (closed && in) ? 0.0 : w;
         __builtin_amdgcn_wave_barrier();
@@ -214,10 +212,9 @@ __global__ void __launch_bounds__(kRT) gl_run_walk(GenArgs a, RunPosteriorArgs p
 
 template <int LP, bool RIGHT>
 void launch_walks(const GenArgs &a, const RunPosteriorArgs &p, hipStream_t stream) {
-    constexpr int G = kRT / LP;
     const long long n = RIGHT ? static_cast<long long>(p.n_anchors) + p.n_runs : p.n_anchors;
     if (n <= 0) return;
-    hipLaunchKernelGGL((gl_run_walk<LP, RIGHT>), dim3(unsigned((n + G - 1) / G)), dim3(kRT), 0, stream, a, p);
+    hipLaunchKernelGGL((gl_run_walk<LP, RIGHT>), dim3(group_blocks(n, LaneGroup<LP, kRT>::G)), dim3(kRT), 0, stream, a, p);
 }
 
 }  // namespace

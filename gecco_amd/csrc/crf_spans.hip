@@ -3,11 +3,7 @@
 // recursion, crf_general.hip) leaves in the plan's workspace the raw state scores, E, alpha, and in the caller's buffer the
 // marginals; a query walks its own span only.
 //
-// Layout as in gl_marginals_seq: LP = L rounded up to a power of two, LP consecutive lanes ("a group", never straddling a
-// wave) own one query, lane j holds component j.  A step is a vector x (L x L) product: the previous vector goes through one
-// LDS slot per lane and comes back as L broadcast reads, the lane's column of exp(trans) stays in registers.  LDS traffic of
-// one wave is in order and groups live inside a wave, so a scheduling barrier is all a step needs and groups may run
-// different trip counts.
+// Layout: one group of lanes per query, on the frame of crf_lane_group.hpp.
 //
 // Two recursions run side by side in the same lanes over the span, one over every label ("free"), one over the labels of
 // the set ("masked").  Both take the RAW state scores: at every item the free one is shifted by the maximum over all labels,
@@ -27,7 +23,7 @@
 //     mass; never NaN.
 // A span of thousands of genes is one group's sequential walk (a few hundred us per thousand genes); it is not chunked.
 #include "crf_device.hpp"
-#include "crf_lanes.hpp"
+#include "crf_lane_group.hpp"
 
 #include <cfloat>
 
@@ -40,10 +36,10 @@ template <int LP>
 __global__ void __launch_bounds__(kST) gl_span_logp(GenArgs a, const SpanQuery *__restrict__ spans, const int n_spans,
                                                      double *__restrict__ logp) {
     __shared__ double vecs[2][kST];
-    constexpr int G = kST / LP;
-    const int j = threadIdx.x & (LP - 1), grp = threadIdx.x / LP;
-    double *vf = vecs[0] + grp * LP, *vm = vecs[1] + grp * LP;
-    const long long q = static_cast<long long>(blockIdx.x) * G + grp;
+    const LaneGroup<LP, kST> g{};
+    const int j = g.j;
+    double *vf = vecs[0] + g.slot, *vm = vecs[1] + g.slot;
+    const long long q = g.item;
     if (q >= n_spans) return;
     const SpanQuery s = spans[q];
     const int L = a.L;
@@ -58,13 +54,7 @@ __global__ void __launch_bounds__(kST) gl_span_logp(GenArgs a, const SpanQuery *
     // what enters the span, before its first emission (the same for both recursions)
     double pf = 1.0, pm = 1.0;
     if (gb > g0) {
-        vf[j] = on ? a.alpha[static_cast<size_t>(gb - 1) * L + jj] : 0.0;
-        __builtin_amdgcn_wave_barrier();
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < LP; ++i) acc = fma(vf[i], mcol[i], acc);
-        __builtin_amdgcn_wave_barrier();
-        pf = pm = acc;
+        pf = pm = sum_product(vf, j, on ? a.alpha[static_cast<size_t>(gb - 1) * L + jj] : 0.0, mcol);
     }
     const double *state = a.state + static_cast<size_t>(gb) * L + jj;
     double xf = 0.0, xm = 0.0, d = 0.0;
@@ -79,6 +69,7 @@ __global__ void __launch_bounds__(kST) gl_span_logp(GenArgs a, const SpanQuery *
         }
         const double ef = on ? exp(st - mf) : 0.0, em = in ? exp(st - mm) : 0.0;
         if (t > gb) {
+            // (the pair of sums is written out, as in gl_run_walk: crf_runs.hip)
             vf[j] = xf;
             vm[j] = xm;
             __builtin_amdgcn_wave_barrier();
@@ -113,6 +104,7 @@ __global__ void __launch_bounds__(kST) gl_span_logp(GenArgs a, const SpanQuery *
             const double al = a.alpha[at];
             w = al != 0.0 ? a.E[at] * a.marg[at] / al : 0.0;
         }
+        // (written out: one product per query, its row read from memory and not kept in LP registers)
         vf[j] = w;
         __builtin_amdgcn_wave_barrier();
         double acc = 0.0;
@@ -128,9 +120,8 @@ __global__ void __launch_bounds__(kST) gl_span_logp(GenArgs a, const SpanQuery *
 
 template <int LP>
 void launch_spans(const GenArgs &a, const SpanQuery *spans, int32_t n_spans, double *logp, hipStream_t stream) {
-    constexpr int G = kST / LP;
-    hipLaunchKernelGGL(gl_span_logp<LP>, dim3(unsigned((static_cast<long long>(n_spans) + G - 1) / G)), dim3(kST), 0, stream, a,
-                       spans, n_spans, logp);
+    hipLaunchKernelGGL(gl_span_logp<LP>, dim3(group_blocks(n_spans, LaneGroup<LP, kST>::G)), dim3(kST), 0, stream, a, spans, n_spans,
+                       logp);
 }
 
 }  // namespace
