@@ -89,6 +89,12 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_i32p, _c_u32p,
          ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_span_conditionals": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_i32p, _c_u32p,
+         ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_f64p, _c_f64p, _c_f64p,
+         _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_run_posteriors": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i32p, _c_i32p, _c_u32p,
@@ -686,6 +692,66 @@ class Model:
         if want_marginals:
             return logp[:ns], marg[:n - n0], ln[:nc]
         return logp[:ns]
+
+    def span_conditionals(self, contig_ptr, gene_ptr, attr_id, span_contig, span_begin, span_end, span_mask, reach=0, device=0,
+                          values=None, allowed=None, want_contributions=True, want_marginals=False, row_ptr=None, occ_ptr=None):
+        """Marginals given a region, and exact knock-out attributions (``gecco_crf_span_conditionals``): for every span of
+        ``span_log_probabilities`` and the event E "every gene of the span carries a label of its set", the rows of the genes
+        ``max(begin - reach, 0) .. min(end + reach, T)`` of its contig.  Returns a dict: ``logp [n_spans]``
+        (``span_log_probabilities``' bytes), ``first [n_spans]`` (the offset of a query's first row inside its contig),
+        ``row_ptr [n_spans + 1]`` (a query's rows are ``row_ptr[q] .. row_ptr[q + 1]``), ``cond [n_rows, L]`` = P(y_t = l | E, x),
+        and with ``want_contributions`` ``occ_ptr [n_rows + 1]``, ``item [n_rows]`` and ``attr [n_occ]``: log P(E | x) minus
+        log P(E | x without the row's gene's scores / without one attribute occurrence of it), the occurrences of row r at
+        ``occ_ptr[r] .. occ_ptr[r + 1]`` in CSR order.  With ``want_marginals`` also ``marginals`` and ``lognorm`` as
+        ``marginals_full`` gives them.  Where ``logp[q]`` is ``-inf`` the query's rows and contributions are 0.0.
+        ``row_ptr`` / ``occ_ptr``: the tables are computed here and checked by the library; given, they are passed on as they
+        are (tests of that check)."""
+        reach = operator.index(reach)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        cptr, gptr = _i32(contig_ptr).astype(np.int64), _i32(gene_ptr).astype(np.int64)
+        sc, sb, se = _i32(span_contig).ravel(), _i32(span_begin).ravel(), _i32(span_end).ravel()
+        sm = np.ascontiguousarray(span_mask, dtype=np.uint32).ravel()
+        ns = sc.size
+        if not (sb.size == ns and se.size == ns and sm.size == ns):
+            raise ValueError("span_contig, span_begin, span_end and span_mask differ in length")
+        # the rows of every query (the library refuses a bad span or reach before it looks at the tables: they only need a size)
+        c64, b64, e64 = sc.astype(np.int64), sb.astype(np.int64), se.astype(np.int64)
+        known = (c64 >= 0) & (c64 < nc)
+        length = np.where(known, cptr[np.where(known, c64 + 1, 0)] - cptr[np.where(known, c64, 0)], 0) if nc else np.zeros(ns, np.int64)
+        good = bool(reach >= 0 and np.all(known & (b64 >= 0) & (b64 < e64) & (e64 <= length)))
+        first = np.maximum(b64 - reach, 0) if good else np.zeros(ns, dtype=np.int64)
+        count = np.minimum(e64 + reach, length) - first if good else np.zeros(ns, dtype=np.int64)
+        rows = np.concatenate([[0], np.cumsum(count)]).astype(np.int64)
+        n_rows = int(rows[-1])
+        occ = None
+        if want_contributions:
+            gene = np.repeat(cptr[c64] + first - rows[:-1], count) + np.arange(n_rows) if n_rows else np.zeros(0, dtype=np.int64)
+            occ = np.concatenate([[0], np.cumsum(gptr[gene + 1] - gptr[gene])]).astype(np.int64)
+        if row_ptr is not None:
+            rows = np.ascontiguousarray(row_ptr, dtype=np.int64).ravel()
+        if occ_ptr is not None:
+            occ = np.ascontiguousarray(occ_ptr, dtype=np.int64).ravel()
+        n_occ = int(occ[-1]) if occ is not None and occ.size else 0
+        L = self.num_labels
+        pad_i, pad_u = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.uint32)
+        logp = np.zeros(max(ns, 1), dtype=np.float64)
+        cond = np.zeros((max(n_rows, 1), L), dtype=np.float64)
+        item = np.zeros(max(n_rows, 1), dtype=np.float64) if want_contributions else None
+        attr = np.zeros(max(n_occ, 1), dtype=np.float64) if want_contributions else None
+        marg = np.zeros((max(n - n0, 1), L), dtype=np.float64) if want_marginals else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_marginals else None
+        p = lambda x: None if x is None else _ptr(x, _c_f64p)
+        i64 = lambda x: None if x is None else _ptr(x, ctypes.POINTER(ctypes.c_int64))
+        _check(self._lib.gecco_crf_span_conditionals(
+            *head, values, allowed, _ptr(sc if ns else pad_i, _c_i32p), _ptr(sb if ns else pad_i, _c_i32p),
+            _ptr(se if ns else pad_i, _c_i32p), _ptr(sm if ns else pad_u, _c_u32p), ns, reach, i64(rows), i64(occ), p(logp), p(cond),
+            p(item), p(attr), p(marg), p(ln)))
+        out = dict(logp=logp[:ns], first=first.astype(np.int64), row_ptr=rows, cond=cond[:n_rows])
+        if want_contributions:
+            out.update(occ_ptr=occ, item=item[:n_rows], attr=attr[:n_occ])
+        if want_marginals:
+            out.update(marginals=marg[:n - n0], lognorm=ln[:nc])
+        return out
 
     def run_posteriors(self, contig_ptr, gene_ptr, attr_id, anchors=None, reach=64, runs=None, device=0, values=None, allowed=None,
                        want_marginals=False):

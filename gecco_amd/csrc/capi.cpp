@@ -1004,6 +1004,62 @@ int upload_queries(DeviceBlock<char> &q, const void *host, size_t bytes, size_t 
     const int rc = q.alloc(total, what_alloc);
     return rc ? rc : check_hip(hipMemcpy(q.get(), host, bytes, hipMemcpyHostToDevice), what_copy);
 }
+// the n_spans queries of the span entries, each checked ("span 3: ..."), as the kernels take them
+int checked_spans(const gecco_crf_model *m, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *span_contig,
+                  const int32_t *span_begin, const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans,
+                  std::vector<SpanQuery> &spans) {
+    spans.resize(static_cast<size_t>(n_spans));
+    for (int32_t q = 0; q < n_spans; ++q) {
+        const int32_t c = span_contig[q], b = span_begin[q], e = span_end[q];
+        int64_t len;
+        int rc;
+        if ((rc = check_query_contig("span", q, c, n_contigs, contig_ptr, &len))) return rc;
+        if ((rc = check_query_range("span", q, c, b, e, len))) return rc;
+        if ((rc = check_label_set("span", q, span_mask[q], m->m.L))) return rc;
+        spans[size_t(q)] = SpanQuery{c, b, e, span_mask[q]};
+    }
+    return GECCO_CRF_OK;
+}
+// The rows of the conditionals entry: query q's are the genes max(begin - reach, 0) .. min(end + reach, T) of its contig.  Fills
+// the library's own row_ptr [n_spans + 1], fwd_ptr [n_spans + 1] (cumulative span lengths) and, with the caller's occ_ptr,
+// occ [n_rows + 1] (cumulative attribute-occurrence counts of the rows' genes), and holds the caller's two arrays to them
+// ("span 3: ..."): a caller whose buffers were sized from other numbers is refused before anything is written.
+int check_conditional_rows(const std::vector<SpanQuery> &spans, int32_t reach, const int32_t *contig_ptr, const int32_t *gene_ptr,
+                           const int64_t *row_ptr, const int64_t *occ_ptr, std::vector<int64_t> &rows, std::vector<int64_t> &fwd,
+                           std::vector<int64_t> &occ) {
+    const size_t n = spans.size();
+    rows.assign(n + 1, 0);
+    fwd.assign(n + 1, 0);
+    if (row_ptr[0] != 0) return fail(query_name("span", 0) + "row_ptr[0] = " + std::to_string(row_ptr[0]) + ", expected 0");
+    for (size_t q = 0; q < n; ++q) {
+        const SpanQuery &s = spans[q];
+        const int64_t len = int64_t(contig_ptr[s.contig + 1]) - contig_ptr[s.contig];
+        const int64_t lo = std::max<int64_t>(int64_t(s.begin) - reach, 0), hi = std::min<int64_t>(int64_t(s.end) + reach, len);
+        rows[q + 1] = rows[q] + (hi - lo);
+        fwd[q + 1] = fwd[q] + (s.end - s.begin);
+        if (row_ptr[q + 1] != rows[q + 1])
+            return fail(query_name("span", int32_t(q)) + "row_ptr[" + std::to_string(q + 1) + "] = " + std::to_string(row_ptr[q + 1]) +
+                        ", expected " + std::to_string(rows[q + 1]) + " (the span's rows are the genes " + std::to_string(lo) + " .. " +
+                        std::to_string(hi) + " of contig " + std::to_string(s.contig) + " at reach " + std::to_string(reach) + ")");
+    }
+    occ.clear();
+    if (!occ_ptr) return GECCO_CRF_OK;
+    occ.assign(size_t(rows[n]) + 1, 0);
+    if (occ_ptr[0] != 0) return fail(query_name("span", 0) + "occ_ptr[0] = " + std::to_string(occ_ptr[0]) + ", expected 0");
+    for (size_t q = 0; q < n; ++q) {
+        const SpanQuery &s = spans[q];
+        const int64_t g_lo = int64_t(contig_ptr[s.contig]) + std::max<int64_t>(int64_t(s.begin) - reach, 0);
+        for (int64_t r = rows[q]; r < rows[q + 1]; ++r) {
+            const int64_t g = g_lo + (r - rows[q]);
+            occ[size_t(r) + 1] = occ[size_t(r)] + (int64_t(gene_ptr[g + 1]) - gene_ptr[g]);
+            if (occ_ptr[r + 1] != occ[size_t(r) + 1])
+                return fail(query_name("span", int32_t(q)) + "occ_ptr[" + std::to_string(r + 1) + "] = " + std::to_string(occ_ptr[r + 1]) +
+                            ", expected " + std::to_string(occ[size_t(r) + 1]) + " (gene " + std::to_string(g) + " carries " +
+                            std::to_string(int64_t(gene_ptr[g + 1]) - gene_ptr[g]) + " attribute occurrences)");
+        }
+    }
+    return GECCO_CRF_OK;
+}
 }  // namespace
 
 // ---- region posteriors (ABI 2.16.0): log P(every gene of a span carries a label of a set | x) on the whole-contig lattice, any
@@ -1021,15 +1077,8 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
     if (n_spans < 0) return fail("span_probabilities: negative number of spans");
     if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
     if (n_spans > 0 && (!span_contig || !span_begin || !span_end || !span_mask || !logp)) return fail("null buffer");
-    std::vector<SpanQuery> spans(static_cast<size_t>(n_spans));
-    for (int32_t q = 0; q < n_spans; ++q) {
-        const int32_t c = span_contig[q], b = span_begin[q], e = span_end[q];
-        int64_t len;
-        if ((rc = check_query_contig("span", q, c, n_contigs, contig_ptr, &len))) return rc;
-        if ((rc = check_query_range("span", q, c, b, e, len))) return rc;
-        if ((rc = check_label_set("span", q, span_mask[q], m->m.L))) return rc;
-        spans[size_t(q)] = SpanQuery{c, b, e, span_mask[q]};
-    }
+    std::vector<SpanQuery> spans;
+    if ((rc = checked_spans(m, contig_ptr, n_contigs, span_contig, span_begin, span_end, span_mask, n_spans, spans))) return rc;
     // without spans the call is the whole-contig marginals' own
     if (n_spans == 0) return marginals_full_of_kind(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
     // (a batch without genes cannot be: a checked span lies inside a contig with genes)
@@ -1043,6 +1092,77 @@ GECCO_API int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t dev
         rc = batch_wait(plan_run_span_probabilities(b.plan, b.csr, reinterpret_cast<const SpanQuery *>(q.get()), n_spans, d_logp,
                                                     b.out<double>(0), b.out<double>(2), nullptr), "span probabilities");
         return batch_fetch(rc, logp, d_logp, size_t(n_spans) * 8, "download logp");
+    });
+    GECCO_GUARD_END
+}
+
+// ---- marginals given a region and knock-out attributions (ABI 2.24.0): c_t(l) = P(y_t = l | every gene of the span carries a
+// label of the set, x) for the genes of a span and `reach` genes on either side, and from them the exact change of the span's
+// log-probability when a gene, or one attribute occurrence of it, is taken out; any number of spans behind one forward-backward
+// pass of the batch (crf_conditionals.hip)
+GECCO_API int gecco_crf_span_conditionals(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                          const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                          const uint32_t *allowed, const int32_t *span_contig, const int32_t *span_begin,
+                                          const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans, int32_t reach,
+                                          const int64_t *row_ptr, const int64_t *occ_ptr, double *logp, double *cond,
+                                          double *item_contribution, double *attr_contribution, double *marg, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the spans and of the caller's row tables, on the host and before any device work
+    if (n_spans < 0) return fail("span_conditionals: negative number of spans");
+    if (reach < 0) return fail("span_conditionals: reach = " + std::to_string(reach) + " is negative");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    if (n_spans > 0 && (!span_contig || !span_begin || !span_end || !span_mask || !logp || !row_ptr || !cond)) return fail("null buffer");
+    if (n_spans > 0 && attr_contribution && !occ_ptr) return fail("span_conditionals: attr_contribution without occ_ptr");
+    std::vector<SpanQuery> spans;
+    if ((rc = checked_spans(m, contig_ptr, n_contigs, span_contig, span_begin, span_end, span_mask, n_spans, spans))) return rc;
+    // without spans the call is the whole-contig marginals' own
+    if (n_spans == 0) return marginals_full_of_kind(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, marg, lognorm);
+    if (!gene_ptr) return fail("null buffer");  // (a checked span lies inside a contig with genes)
+    std::vector<int64_t> rows, fwd, occ;
+    if ((rc = check_conditional_rows(spans, reach, contig_ptr, gene_ptr, row_ptr, occ_ptr, rows, fwd, occ))) return rc;
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 0, 0, marg, lognorm, [&](ResidentBatch &b) {
+        // one block: the spans, the three row tables, then logp, the walks' two workspaces, cond, and the two contributions
+        const size_t ns = size_t(n_spans), L = size_t(m->m.L), n_rows = size_t(rows[ns]), n_fwd = size_t(fwd[ns]);
+        const size_t n_occ = occ.empty() ? 0 : size_t(occ[n_rows]);
+        Carver at;
+        at.take(ns * sizeof(SpanQuery));
+        const size_t o_rows = at.take((ns + 1) * 8), o_fwd = at.take((ns + 1) * 8), o_occ = at.take(occ.size() * 8 + 8);
+        const size_t b_host = at.off;
+        const size_t o_logp = at.take(ns * 8), o_vec = at.take(n_fwd * L * 8), o_walk = at.take(n_rows * L * 8 + 8),
+                     o_cond = at.take(n_rows * L * 8 + 8), o_item = at.take(n_rows * 8 + 8), o_attr = at.take(n_occ * 8 + 8);
+        std::vector<char> host(b_host, 0);
+        std::memcpy(host.data(), spans.data(), ns * sizeof(SpanQuery));
+        std::memcpy(host.data() + o_rows, rows.data(), (ns + 1) * 8);
+        std::memcpy(host.data() + o_fwd, fwd.data(), (ns + 1) * 8);
+        if (!occ.empty()) std::memcpy(host.data() + o_occ, occ.data(), occ.size() * 8);
+        DeviceBlock<char> q;
+        int rc = upload_queries(q, host.data(), b_host, at.off, "hipMalloc span conditionals", "upload spans");
+        if (rc) return rc;
+        ConditionalArgs a{};
+        a.spans = reinterpret_cast<const SpanQuery *>(q.get());
+        a.n_spans = n_spans;
+        a.reach = reach;
+        a.n_rows = int64_t(n_rows);
+        a.n_fwd = int64_t(n_fwd);
+        a.n_occ = int64_t(n_occ);
+        a.row_ptr = reinterpret_cast<const int64_t *>(q.get() + o_rows);
+        a.fwd_ptr = reinterpret_cast<const int64_t *>(q.get() + o_fwd);
+        a.occ_ptr = occ.empty() ? nullptr : reinterpret_cast<const int64_t *>(q.get() + o_occ);
+        a.fwd = reinterpret_cast<double *>(q.get() + o_vec);
+        a.walk = reinterpret_cast<double *>(q.get() + o_walk);
+        a.cond = reinterpret_cast<double *>(q.get() + o_cond);
+        a.item = reinterpret_cast<double *>(q.get() + o_item);
+        a.attr = reinterpret_cast<double *>(q.get() + o_attr);
+        double *d_logp = reinterpret_cast<double *>(q.get() + o_logp);
+        rc = batch_wait(plan_run_span_conditionals(b.plan, b.csr, a, d_logp, b.out<double>(0), b.out<double>(2), nullptr),
+                        "span conditionals");
+        rc = batch_fetch(rc, logp, d_logp, ns * 8, "download logp");
+        rc = batch_fetch(rc, cond, a.cond, n_rows * L * 8, "download cond");
+        rc = batch_fetch(rc, item_contribution, a.item, n_rows * 8, "download item_contribution");
+        return batch_fetch(rc, a.occ_ptr ? attr_contribution : nullptr, a.attr, n_occ * 8, "download attr_contribution");
     });
     GECCO_GUARD_END
 }

@@ -328,6 +328,28 @@ struct SpanQuery {
 // same stream with a.state non-null: reads a.state, a.E, a.alpha and a.marg, whatever arrangement filled them
 hipError_t launch_gen_spans(const GenArgs &a, const SpanQuery *spans, int32_t n_spans, double *logp, hipStream_t stream);
 
+// ---- marginals given a region and knock-out attributions (crf_conditionals.hip) ----
+// What one call asks for: the checked queries `spans` and, for each, the rows of the genes max(begin - reach, 0) ..
+// min(end + reach, T) of its contig.  The host has computed row_ptr [n_spans + 1] (cumulative row counts), fwd_ptr [n_spans + 1]
+// (cumulative span lengths: where a query's stored forward vectors start in fwd [n_fwd][L]) and occ_ptr [n_rows + 1] (cumulative
+// attribute-occurrence counts of the rows' genes; null: attr is not written).  fwd and walk [n_rows][L] are the walks' workspace.
+// logp [n_spans] is what launch_gen_spans wrote for the same queries on the same stream.  cond [n_rows][L]: the conditional
+// marginals; item [n_rows]: log P(E | x) - log P(E | x without the gene's state scores); attr [n_occ]: the same for each attribute
+// occurrence of the rows' genes in CSR order (attr_value: the batch's values, parallel to attr_id, or null).  All zeros for a
+// query whose logp is -infinity.
+struct ConditionalArgs {
+    const SpanQuery *spans;
+    int32_t n_spans, reach;
+    int64_t n_rows, n_fwd, n_occ;
+    const int64_t *row_ptr, *fwd_ptr, *occ_ptr;
+    const double *logp, *attr_value;
+    double *fwd, *walk, *cond, *item, *attr;
+};
+// on the lattice of the whole-contig marginals that ran before it on the same stream with a.state non-null: reads a.state, a.E,
+// a.alpha, a.marg, a.exp_trans, and for the attributions a.gene_ptr, a.attr_id and a.wtab.  Memsets of the outputs and the
+// workspace, the right walks, the left walks, the epilogue over the rows.
+hipError_t launch_gen_conditionals(const GenArgs &a, const ConditionalArgs &p, hipStream_t stream);
+
 // ---- label paths drawn from the posterior (crf_sample.hip) ----
 constexpr int32_t kMaxSamples = 1 << 20;  // n_samples of one call
 // One run query: the gene at offset `anchor` inside contig `contig`, and the label set `mask`.  The host has checked the ranges

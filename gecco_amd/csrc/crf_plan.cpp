@@ -1355,6 +1355,27 @@ int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *
     return check_hip(launch_gen_spans(g, d_spans, n_spans, d_logp, stream), "span launch");
 }
 
+int plan_run_span_conditionals(Plan &p, const DeviceCsr &csr, const ConditionalArgs &q, double *d_logp, double *d_marg,
+                               double *d_lognorm, hipStream_t stream) {
+    if (q.n_spans < 0 || q.reach < 0 || q.n_rows < 0 || q.n_fwd < 0 || q.n_occ < 0) {
+        set_error("a negative number of spans or rows, or a negative reach");
+        return GECCO_CRF_EINVAL;
+    }
+    int rc;
+    if (ends_here(p.n_contigs == 0,
+                  (p.n_genes > 0 && (!csr.gene_ptr || !d_marg)) ||
+                      (q.n_spans > 0 && (!q.spans || !d_logp || !q.row_ptr || !q.fwd_ptr || !q.fwd || !q.walk || !q.cond || !q.item ||
+                                         (q.occ_ptr && !q.attr))), rc))
+        return rc;
+    GenArgs g;  // (with the raw state scores, which the span kernel and the walks shift by their own maxima)
+    if ((rc = run_lattice(p, csr, "conditional marginals", true, d_marg, d_lognorm, stream, g))) return rc;
+    if ((rc = check_hip(launch_gen_spans(g, q.spans, q.n_spans, d_logp, stream), "span launch"))) return rc;
+    ConditionalArgs a = q;
+    a.logp = d_logp;
+    a.attr_value = csr.attr_value;
+    return check_hip(launch_gen_conditionals(g, a, stream), "conditionals launch");
+}
+
 int plan_run_run_posteriors(Plan &p, const DeviceCsr &csr, const RunPosteriorArgs &q, double *d_marg, double *d_lognorm,
                             hipStream_t stream) {
     if (q.n_anchors < 0 || q.n_runs < 0 || q.reach < 0 || q.reach > kMaxRunReach) {

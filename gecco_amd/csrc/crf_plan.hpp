@@ -165,7 +165,7 @@ struct Plan {
     // as `valued` does: the any-L kernels at every label count, no reference-bits mode, and the masks come with every run call
     // (DeviceCsr::allowed), which is refused when it brings masks to a layout without `masked`, or none to one with it.
     bool masked = false;
-    // Lattice queries (plan_run_span_probabilities, plan_run_sample_paths, plan_run_viterbi_kbest, plan_run_edge_posteriors,
+    // Lattice queries (plan_run_span_probabilities, plan_run_span_conditionals, plan_run_sample_paths, plan_run_viterbi_kbest, plan_run_edge_posteriors,
     // plan_run_viterbi_min_run, plan_run_run_posteriors, plan_run_marginals_min_run, plan_run_run_counts).  `lattice` is
     // set by the owner before plan_build: the layout takes the any-L kernels at every label count, as `valued` and `masked` do --
     // the queries' kernels read the forward vectors and raw state scores of their workspace, which a 2-label plan does not have
@@ -217,6 +217,11 @@ int plan_run_viterbi(Plan &p, const DeviceCsr &csr, int8_t *d_y, double *d_score
 // gene of span q carries a label of its set | x) for the n_spans checked queries of d_spans (crf_spans.hip), all on `stream`
 int plan_run_span_probabilities(Plan &p, const DeviceCsr &csr, const SpanQuery *d_spans, int32_t n_spans, double *d_logp,
                                 double *d_marg, double *d_lognorm, hipStream_t stream);
+// Marginals given a region and knock-out attributions of a plan laid out with `lattice`: the whole-contig marginals of the batch
+// and the region posteriors d_logp [n_spans], both exactly as plan_run_span_probabilities runs them, then what `q` asks for (device
+// pointers; crf_device.hpp: its logp and attr_value are set here) for its checked queries (crf_conditionals.hip), all on `stream`
+int plan_run_span_conditionals(Plan &p, const DeviceCsr &csr, const ConditionalArgs &q, double *d_logp, double *d_marg,
+                               double *d_lognorm, hipStream_t stream);
 // Run posteriors of a plan laid out with `lattice`: the whole-contig marginals of the batch (d_marg [n_genes][L], which the walks
 // read back, and d_lognorm [n_contigs] or null, both as plan_run_marginals_full writes them), then what `q` asks for (device
 // pointers; crf_device.hpp) for its checked anchors and closed runs (crf_runs.hip), all on `stream`

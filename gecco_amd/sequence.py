@@ -329,6 +329,66 @@ class SequenceCRF:
         return self._model.span_log_probabilities(seq_ptr, item_ptr, attr, contig, begin, end, mask, device=self.device,
                                                   values=values, allowed=masks)
 
+    def _span_conditionals(self, X, spans, reach, allowed, want_contributions: bool):
+        """The native call behind ``predict_marginals_given_span`` and ``span_attributions``: ``(result or None, attr, values)``."""
+        try:
+            reach = operator.index(reach)
+        except TypeError:
+            raise ValueError(f"reach = {reach!r} is not an integer") from None
+        if reach < 0:
+            raise ValueError(f"reach = {reach} is negative")
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        contig, begin, end, mask = self._span_queries(spans, seq_ptr)
+        if len(contig) == 0:
+            return None, attr, values
+        res = self._model.span_conditionals(seq_ptr, item_ptr, attr, contig, begin, end, mask, reach=reach, device=self.device,
+                                            values=values, allowed=masks, want_contributions=want_contributions)
+        # (the attribute occurrences of row r, as the packer kept them: item_ptr of the row's item)
+        res["item_index"] = np.repeat(seq_ptr[contig].astype(np.int64) + res["first"] - res["row_ptr"][:-1],
+                                      np.diff(res["row_ptr"])) + np.arange(int(res["row_ptr"][-1]))
+        res["item_ptr"] = item_ptr
+        return res, attr, values
+
+    def predict_marginals_given_span(self, X, spans, reach=0, allowed=None) -> List[dict]:
+        """Marginals given a region: for every ``(sequence_index, start, stop, labels)`` of ``spans`` (as in
+        ``span_log_probability``) a dict with ``first`` (the index of the first row's item in its sequence: ``max(start - reach,
+        0)``), ``log_probability`` (``span_log_probability``'s value) and ``marginals [rows, L]``: P(item t has label l | every
+        item of the span carries a label of ``labels``, the whole sequence), for the items ``first .. min(stop + reach, T) - 1``,
+        columns in ``classes_`` order.  Inside the span a label outside the set has exactly 0.0; a row sums to 1; where the span
+        is impossible (``-inf``) the rows are 0.0.  One forward-backward pass over ``X`` and one native call for all spans.
+        Raises ``ValueError`` before any device call for what ``span_log_probability`` refuses, and for a negative ``reach``."""
+        res, _, _ = self._span_conditionals(X, spans, reach, allowed, False)
+        if res is None:
+            return []
+        rows = res["row_ptr"]
+        return [dict(first=int(res["first"][q]), log_probability=float(res["logp"][q]), marginals=res["cond"][rows[q]:rows[q + 1]])
+                for q in range(len(res["logp"]))]
+
+    def span_attributions(self, X, spans, reach=0, allowed=None) -> List[dict]:
+        """Exact knock-out attributions of a region: for every span (as in ``predict_marginals_given_span``, whose rows these
+        are) a dict with ``first``, ``log_probability``, ``items [rows]`` and ``attributes``.  ``items[r]`` is log P(region | x)
+        minus log P(region | x with everything row r's item carries removed); ``attributes[r]`` lists, for every attribute
+        occurrence the packer kept of that item and in its order, ``(name, value, contribution)``: the same difference with that
+        one occurrence removed (value 1.0 for an attribute without one).  Positive where the region's probability leans on
+        it.  Exact: the values ``span_log_probability`` would give on the changed input, from one pass and one native call.
+        Where the span is impossible everything is 0.0.  Refusals as in ``predict_marginals_given_span``."""
+        res, attr, values = self._span_conditionals(X, spans, reach, allowed, True)
+        if res is None:
+            return []
+        rows, occ, item_ptr = res["row_ptr"], res["occ_ptr"], res["item_ptr"]
+        contribution = res["attr"].tolist()
+        out = []
+        for q in range(len(res["logp"])):
+            attributes = []
+            for r in range(int(rows[q]), int(rows[q + 1])):
+                k0 = int(item_ptr[res["item_index"][r]])
+                attributes.append([(self.attributes_[int(attr[k0 + i])], 1.0 if values is None else float(values[k0 + i]),
+                                    contribution[int(occ[r]) + i]) for i in range(int(occ[r + 1] - occ[r]))])
+            out.append(dict(first=int(res["first"][q]), log_probability=float(res["logp"][q]), items=res["item"][rows[q]:rows[q + 1]],
+                            attributes=attributes))
+        return out
+
     def span_probability(self, X, spans, allowed=None) -> np.ndarray:
         """``exp`` of ``span_log_probability``."""
         return np.exp(self.span_log_probability(X, spans, allowed=allowed))

@@ -34,6 +34,15 @@ native call), not windowed ones: the model's parameters are those fitted on wind
 contig.  ``known=`` restricts that lattice as it restricts the windows.  ``clusters.tsv`` then has the columns ``region_p``
 and ``{type}_region_p``; without the flag the tables are unchanged.
 
+Attributions (opt-in: ``attributions=True``, ``predict --attributions [--attribution-reach R]``).  "Which genes and domains
+does this call rest on": with E the event that every gene of the called region carries a cluster label, every gene in the
+region and R genes on either side gets ``contribution`` = log P(E | x) - log P(E | x without anything the gene carries), and
+every domain of such a gene the same with that one domain taken out -- exact, the values a second run on the edited input
+would give, from the marginals conditioned on E (``_native.Model.span_conditionals``: one forward-backward pass per batch,
+every cluster in one native call).  Positive where the call leans on the gene or domain, negative where it speaks against
+it.  WHOLE-CONTIG posteriors like the region posteriors, and ``known=`` restricts the lattice in the same way.  The command
+line writes ``attributions.tsv``; without the flag the tables and every launch are unchanged.
+
 Boundary intervals (opt-in: ``boundary_samples=N > 0``, ``predict --boundary-samples N [--seed S]``).  "How sure are you about
 where it starts and ends": N label paths per contig are drawn from the path distribution p(y | x)
 (``_native.Model.sample_paths``: forward filtering, backward sampling, one forward-backward pass and one native call per
@@ -571,7 +580,7 @@ class TypedClusterCRF:
                          trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                          region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0, alternatives: int = 0,
                          alternatives_margin: int = 10, boundary_posteriors: bool = False, run_posteriors: bool = False,
-                         run_reach: int = 256) -> List[Any]:
+                         run_reach: int = 256, attributions: bool = False, attribution_reach: int = 10) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
         per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, with
         ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities``, and with
@@ -581,13 +590,19 @@ class TypedClusterCRF:
         ``start_probability`` and ``end_probability``, and with ``run_posteriors`` each with ``run_anchor_probability``,
         ``run_probability``, ``run_start_interval``, ``run_end_interval``, ``run_start_beyond_probability``,
         ``run_end_beyond_probability`` and ``run_boundaries``, exact over ``run_reach`` genes to either side of the anchor
-        (module docstring)."""
+        (module docstring), and with ``attributions`` each with ``attributions``: for every gene of the call and of
+        ``attribution_reach`` genes on either side a dict with its ``protein_id``, its ``offset`` (0 = the cluster's first gene,
+        negative before it), its ``contribution`` -- log P(every gene of the call lies in a cluster | x) minus the same without
+        anything the gene carries, exact, positive where the call leans on the gene -- and ``domains``, the ``(name,
+        contribution)`` of each of its domains the model knows; the cluster's ``attribution_log_probability`` is the
+        log-probability they are differences of."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
                                                pad=pad, known=known, region_posteriors=region_posteriors,
                                                boundary_samples=boundary_samples, seed=seed, alternatives=alternatives,
                                                alternatives_margin=alternatives_margin,
                                                boundary_posteriors=boundary_posteriors, run_posteriors=run_posteriors,
-                                               run_reach=run_reach)[1]
+                                               run_reach=run_reach, attributions=attributions,
+                                               attribution_reach=attribution_reach)[1]
 
     def _region_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int,
                            clusters: List[Any]) -> None:
@@ -606,6 +621,30 @@ class TypedClusterCRF:
         for cluster, row in zip(clusters, p.tolist()):
             cluster.region_probability = row[0]
             cluster.region_type_probabilities = dict(zip(self.types_, row[1:]))
+
+    def _attributions(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int, clusters: List[Any],
+                      annotated: List[Any], reach: int) -> None:
+        """``attributions`` and ``attribution_log_probability`` of every called cluster (``rows``: the segment kernel's (contig,
+        number, first gene, last gene + 1)), from ONE native call over the batch: per cluster one query with the set of every
+        label but the background; the call's rows are the cluster's genes and ``reach`` genes on either side."""
+        base = item_ptr[rows[:, 0]].astype(np.int64)
+        attr_ptr = batch.attr_ptr.astype(np.int32)
+        out = self._fitted().span_conditionals(item_ptr, attr_ptr, batch.attr_id, rows[:, 0].astype(np.int32),
+                                               (rows[:, 2] - base).astype(np.int32), (rows[:, 3] - base).astype(np.int32),
+                                               np.full(len(rows), not_background, dtype=np.uint32), reach=reach, device=self.device,
+                                               allowed=allowed)
+        names = self._fitted().attrs()
+        row_ptr, occ_ptr, item, attr = out["row_ptr"].tolist(), out["occ_ptr"].tolist(), out["item"].tolist(), out["attr"].tolist()
+        for q, (cluster, (_, _, first, _), g0) in enumerate(zip(clusters, rows.tolist(), base.tolist())):
+            cluster.attribution_log_probability = float(out["logp"][q])
+            cluster.attributions = []
+            gene0 = g0 + int(out["first"][q])  # (the gene of the query's first row)
+            for r in range(row_ptr[q], row_ptr[q + 1]):
+                g = gene0 + r - row_ptr[q]
+                k0 = int(attr_ptr[g])
+                cluster.attributions.append({
+                    "protein_id": annotated[g].protein.id, "offset": g - first, "contribution": item[r],
+                    "domains": [(names[int(batch.attr_id[k0 + i])], attr[occ_ptr[r] + i]) for i in range(occ_ptr[r + 1] - occ_ptr[r])]})
 
     def _boundary_intervals(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int, clusters: List[Any],
                             annotated: List[Any], p_any: np.ndarray, n_samples: int, seed: int) -> None:
@@ -940,7 +979,8 @@ class TypedClusterCRF:
                                    seed: int = 0, alternatives: int = 0,
                                    alternatives_margin: int = 10,
                                    boundary_posteriors: bool = False, run_posteriors: bool = False,
-                                   run_reach: int = 256) -> Tuple[List[Any], List[Any]]:
+                                   run_reach: int = 256, attributions: bool = False,
+                                   attribution_reach: int = 10) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
         second, whole-contig pass gives every cluster its region posteriors, and with ``boundary_samples = N > 0`` one more
         draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals; with ``alternatives = K >
@@ -949,7 +989,9 @@ class TypedClusterCRF:
         cluster ``start_probability`` and ``end_probability`` and the model ``sequence_posteriors_``, the per-contig columns
         ``SEQUENCE_COLUMNS``; with ``run_posteriors`` one more whole-contig pass and one native call give every cluster
         the exact start and end distributions of the run through its anchor, over ``run_reach`` (0 .. 65536) genes to either
-        side (module docstring).  ``ValueError`` before any device call for an option
+        side (module docstring); with ``attributions`` one more whole-contig pass and one native call give every cluster the
+        exact knock-out contribution of every gene and domain in it and ``attribution_reach`` genes around it
+        (``predict_clusters``).  ``ValueError`` before any device call for an option
         that is not an integer or lies outside its range."""
         from . import _native
 
@@ -977,6 +1019,12 @@ class TypedClusterCRF:
             raise ValueError(f"run_reach is an integer, got {run_reach!r}") from None
         if not 0 <= run_reach <= 65536:
             raise ValueError(f"run_reach = {run_reach} is outside 0 .. 65536")
+        try:
+            attribution_reach = operator.index(attribution_reach)
+        except TypeError:
+            raise ValueError(f"attribution_reach is an integer, got {attribution_reach!r}") from None
+        if attribution_reach < 0:
+            raise ValueError(f"attribution_reach = {attribution_reach} is negative")
         from .refine import _cluster_class
         from .types import _cluster_type_factory
 
@@ -1012,7 +1060,25 @@ class TypedClusterCRF:
             self._alternatives(batch, allowed, rows, item_ptr, clusters, annotated, p_any, alternatives, alternatives_margin)
         if run_posteriors and clusters:
             self._run_posteriors(batch, allowed, rows, item_ptr, not_background, clusters, annotated, p_any, run_reach)
+        if attributions and clusters:
+            self._attributions(batch, allowed, rows, item_ptr, not_background, clusters, annotated, attribution_reach)
         return annotated, clusters
+
+
+def write_attributions(path, clusters: Sequence[Any]) -> None:
+    """``attributions.tsv``: what every called cluster rests on, one row per gene of the call and its neighbourhood (``domain``
+    empty) and per domain of such a gene, columns ``cluster_id, sequence_id, protein_id, offset, domain, contribution,
+    p_without``: ``contribution`` = log P(region | x) - log P(region | x without it), positive when the call leans on it, and
+    ``p_without`` = exp(log P(region | x) - contribution), the region's probability without it; floats with ``repr``."""
+    with open(path, "w") as out:
+        out.write("\t".join(("cluster_id", "sequence_id", "protein_id", "offset", "domain", "contribution", "p_without")) + "\n")
+        for cluster in clusters:
+            logp = getattr(cluster, "attribution_log_probability", -math.inf)
+            for row in getattr(cluster, "attributions", ()):
+                for domain, contribution in [("", row["contribution"])] + list(row["domains"]):
+                    without = math.exp(logp - contribution) if logp > -math.inf else 0.0
+                    out.write("\t".join((str(cluster.id), str(cluster.source.id), str(row["protein_id"]), str(row["offset"]), domain,
+                                         repr(contribution), repr(without))) + "\n")
 
 
 def write_alternatives(path, clusters: Sequence[Any]) -> None:
@@ -1160,6 +1226,11 @@ def build_parser() -> argparse.ArgumentParser:
                     "every called region starts and ends; write boundaries.tsv, the distributions themselves")
     pr.add_argument("--run-reach", type=int, default=256, metavar="R",
                     help="genes on either side of a called region's anchor that the exact distributions cover (with --run-posteriors)")
+    pr.add_argument("--attributions", action="store_true",
+                    help="write attributions.tsv: for every called region the exact change of its whole-contig log-probability when "
+                    "one gene, or one domain of a gene, is taken out of the input, for the genes in and around it")
+    pr.add_argument("--attribution-reach", type=int, default=10, metavar="R",
+                    help="genes on either side of a called region that attributions.tsv covers (with --attributions)")
     pr.add_argument("--path-clusters", type=int, default=None, metavar="M",
                     help="write path_clusters.tsv and paths.tsv: the regions of the best whole-contig label path among those in "
                     "which every region has at least M (at most 32) genes, and per contig that path's probability and the "
@@ -1213,7 +1284,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                                       alternatives=args.alternatives,
                                                       alternatives_margin=args.alternatives_margin,
                                                       boundary_posteriors=args.boundary_posteriors,
-                                                      run_posteriors=args.run_posteriors, run_reach=args.run_reach)
+                                                      run_posteriors=args.run_posteriors, run_reach=args.run_reach,
+                                                      attributions=args.attributions, attribution_reach=args.attribution_reach)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))
@@ -1224,6 +1296,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         write_sequences(os.path.join(args.output_dir, "sequences.tsv"), crf.sequence_posteriors_)
     if args.run_posteriors:
         write_boundaries(os.path.join(args.output_dir, "boundaries.tsv"), found)
+    if args.attributions:
+        write_attributions(os.path.join(args.output_dir, "attributions.tsv"), found)
     if args.path_clusters is not None:
         known = None if args.known is None else tables.ClusterTable.load(args.known)
         write_path_clusters(os.path.join(args.output_dir, "path_clusters.tsv"),

@@ -52,7 +52,8 @@ const char *gecco_crf_last_error(void);
  * ABI 2.15.0 adds the *_constrained one-shots and keeps 340: the new entries are detected by symbol presence.
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
- * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts. */
+ * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts, ABI 2.24.0
+ * gecco_crf_span_conditionals. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -758,6 +759,46 @@ int gecco_crf_span_probabilities(const gecco_crf_model *m, int32_t device, const
                                  const int32_t *span_begin, const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans,
                                  double *logp /* [n_spans] */, double *marg /* [n_genes][L] or NULL */,
                                  double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- marginals given a region, and knock-out attributions (ABI 2.24.0, additive; gecco_crf_version() stays 340) ----------------
+ * cond[r][l] = P(y_t = l | E, x), E the event "every gene of span q carries a label of its set": the marginals conditioned on a
+ * region, for the genes of the span and `reach` genes on either side, on the lattice of gecco_crf_span_probabilities (whose
+ * arguments, checks and refusals this entry shares, in the same words).  From them, exactly, what the region's log-probability
+ * rests on: changing the state scores of ONE gene t by delta_l multiplies Z by sum_l marg_t(l) e^{delta_l} and Z_E by
+ * sum_l cond_t(l) e^{delta_l}, so
+ *     log P(E | x) - log P(E | x with the change) = log sum_l marg_t(l) e^{delta_l} - log sum_l cond_t(l) e^{delta_l}.
+ *   * Rows.  Query q's rows are the genes max(begin - reach, 0) .. min(end + reach, T) of its contig of T genes, in gene order;
+ *     the queries' rows follow each other in query order.  row_ptr [n_spans + 1] holds the cumulative row counts (row_ptr[0] = 0),
+ *     occ_ptr [n_rows + 1] (optional) the cumulative numbers of attribute occurrences of the rows' genes, gene_ptr[g + 1] -
+ *     gene_ptr[g] each.  The caller computes both -- they size its buffers -- and the library holds them to its own: a mismatch
+ *     is GECCO_CRF_EINVAL, "span q: ...", before any device work.  So is reach < 0.
+ *   * cond [n_rows][L].  A row sums to 1; inside the span an entry outside the set is exactly 0.0, and so is a disallowed (gene,
+ *     label) pair anywhere.  A row is one fixed operation sequence: its bytes depend neither on reach, nor on the other queries,
+ *     nor on the query's place in the batch; equal queries give equal bits.
+ *   * item_contribution [n_rows] (optional): the change above for delta_l = -s_t(l), the gene without anything it carries (to
+ *     the model a gene without domain hits).  attr_contribution [n_occ] (optional, needs occ_ptr): for delta_l = -v w[a][l], one
+ *     occurrence of attribute a with value v taken out, for every occurrence of the row's gene in CSR order, valued or not (an
+ *     id outside the model's dictionary has no weight: 0.0).  Positive when the region leans on it.  Each sum is shifted by its
+ *     own largest delta: a |delta| of 1 000 does not overflow.  Labels without mass take no part.
+ *   * logp [n_spans] has the bytes of gecco_crf_span_probabilities for the same queries (that kernel runs as it is); marg and
+ *     lognorm, each optional, are as there.  Where logp[q] is -infinity the query's rows and contributions are all 0.0.  Never
+ *     NaN.  n_spans == 0 is a valid call that fills marg and lognorm.
+ *   * Range.  Inside the span the state scores are shifted by their maximum over the SET, and a row's own gene enters with its
+ *     raw scores, so a label that leads by hundreds at the gene is knocked out exactly.  The other genes enter
+ *     through the whole-contig pass's forward vector and marginals and inherit its range: a (gene, label) pair whose forward
+ *     value underflowed there contributes nothing, as it contributes nothing to marg.
+ *   * Cost: one forward-backward pass, the span kernel, two sequential walks per query (its span plus its reach on one side
+ *     each) by one group of lanes, and one group of lanes per row; 8 (end - begin + rows) L bytes of device workspace per query.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_span_conditionals(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                                const uint32_t *allowed /* NULL: no masks */, const int32_t *span_contig,
+                                const int32_t *span_begin, const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans,
+                                int32_t reach, const int64_t *row_ptr /* [n_spans + 1] */,
+                                const int64_t *occ_ptr /* [n_rows + 1] or NULL */, double *logp /* [n_spans] */,
+                                double *cond /* [n_rows][L] */, double *item_contribution /* [n_rows] or NULL */,
+                                double *attr_contribution /* [n_occ] or NULL */, double *marg /* [n_genes][L] or NULL */,
+                                double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- label paths drawn from the posterior (ABI 2.17.0, additive; gecco_crf_version() stays 340) --------------------------------
  * y[g * n_samples + s] = the label of gene g in sample s: n_samples label paths per contig drawn from p(y | x) on the
