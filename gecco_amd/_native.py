@@ -764,7 +764,8 @@ class Model:
         four arrays of one length: ``log_run [n]``, log P(a run is exactly ``[begin, end)``).  Natural logs, ``<= 0``, ``-inf``
         for probability zero.  ``values`` and ``allowed`` as in ``marginals_full``.  Returns a dict with the keys named above
         (those of a list that was not given are left out), and with ``want_marginals`` also ``marginals`` and ``lognorm`` as
-        ``marginals_full`` gives them."""
+        ``marginals_full`` gives them.  A model whose largest |transition weight| (among those whose exp is not 0) exceeds 150 is
+        refused with ``ValueError``: subtract a constant from every transition weight."""
         reach = operator.index(reach)
         head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
         na = nr = 0

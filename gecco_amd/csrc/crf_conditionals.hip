@@ -61,6 +61,25 @@ __device__ __forceinline__ bool unit_sum(double &x) {
     x = to_unit_sum(x, sum);
     return true;
 }
+// The lane's row or column m of exp(trans), times one power of two for the whole group: 2^-k, k the binary exponent of the
+// table's largest entry rounded towards zero to a multiple of 256.  A model whose largest transition weight is +-600 has its
+// table around 2^+-866, a walk keeps the vector that LEFT the product with it, and gl_cond_rows multiplies two of those: the
+// product left the doubles' range and every row of such a model came out 0.  A factor common to the whole table multiplies
+// every vector of both walks alike and cancels in a row, which is a ratio, and a power of two is exact.
+// k = 0, and not one bit changes, while the largest weight stays inside +-177 = +-256 ln 2.
+template <int LP>
+__device__ __forceinline__ void table_to_range(double (&m)[LP]) {
+    double top = 0.0;
+#pragma unroll
+    for (int i = 0; i < LP; ++i) top = fmax(top, m[i]);
+    top = group_max<LP>(top);
+    int e;
+    (void)__builtin_frexp(top, &e);
+    const int k = e / 256 * 256;  // (towards zero)
+    if (k == 0) return;
+#pragma unroll
+    for (int i = 0; i < LP; ++i) m[i] = ldexp(m[i], -k);
+}
 // the direction of psi beta at a gene: E marg / alpha, 0 where alpha is 0
 __device__ __forceinline__ double psi_beta(const GenArgs &a, size_t at) {
     const double al = a.alpha[at];
@@ -89,6 +108,7 @@ __global__ void __launch_bounds__(kCT) gl_cond_walk(GenArgs a, ConditionalArgs p
     double mvec[LP];
 #pragma unroll
     for (int i = 0; i < LP; ++i) mvec[i] = (i < L && on) ? (RIGHT ? a.exp_trans[i * L + j] : a.exp_trans[j * L + i]) : 0.0;
+    table_to_range(mvec);  // (every vector of both walks carries the factor: it cancels in a row)
     double *fwd = p.fwd + static_cast<size_t>(p.fwd_ptr[q]) * L;    // the restricted forward vector entering gene t at fwd[(t - gb) L + j]
     double *rows = p.walk + static_cast<size_t>(p.row_ptr[q]) * L;  // the walk's vector at gene t at rows[(t - lo) L + j]
 

@@ -47,6 +47,8 @@ int get_device_tables(const Model &m, int device, const DeviceTables **out) {
     for (double v : m.state) t->wmax_abs = std::max(t->wmax_abs, std::fabs(v));
     for (double v : m.trans) t->tmax_abs = std::max(t->tmax_abs, std::fabs(v));
     if (!m.trans.empty()) t->tmax = *std::max_element(m.trans.begin(), m.trans.end());
+    for (size_t i = 0; i < L * L; ++i)
+        if (et[i] != 0.0) t->tmax_abs_live = std::max(t->tmax_abs_live, std::fabs(m.trans[i]));
     rc = t->wtab.upload(m.state.data(), A * L, "upload state weights");
     if (!rc) rc = t->exp_trans.upload(et.data(), L * L, "upload transitions");
     if (!rc) rc = t->trans.upload(m.trans.data(), L * L, "upload transitions");
@@ -614,6 +616,7 @@ int32_t choose_wave_split(const Plan &p, const char *env, bool automatic, double
 // 0 and the pass would return zeros, with max > 709.78 infinities and NaN, either with a clean status.  700 is the figure
 // the 2-label route keeps its own products inside (`room`, slot_prod_max_cnt).  A finite model outside it is refused, not
 // shifted: no in-range model changes a bit.  Viterbi reads the raw weights and is not refused.  DESIGN.md §4.9f.
+constexpr double kRunsMaxTrans = 150.0;  // plan_run_run_posteriors
 int check_exp_trans_range(const Plan &p) {
     const double mx = p.tables_model->tmax;
     if (!(mx > 700.0) && !(mx < -700.0)) return GECCO_CRF_OK;
@@ -1389,6 +1392,21 @@ int plan_run_run_posteriors(Plan &p, const DeviceCsr &csr, const RunPosteriorArg
                                            !q.log_end_beyond)) ||
                       (q.n_runs > 0 && (!q.runs || !q.log_run)), rc))
         return rc;
+    // The walks read the pass's stored alpha, and E marg / alpha, of single labels.  The pass forms (alpha . M) E before it
+    // normalises, and a wave pass keeps alpha with the step's factor: with max|trans| = s a label B nats behind at a gene is
+    // flushed to an exact 0 there once s + B passes 708, and the runs that need it came back -infinity instead of about -B
+    // (at s = 600: every label more than 108 behind).  150 is rows_rescale_period's figure; under it a label is kept down
+    // to 550 nats behind.  A transition whose exp is 0 does not exist for the pass and does not count.  DESIGN.md 4.9f.
+    if ((rc = check_exp_trans_range(p))) return rc;
+    if (p.tables_model->tmax_abs_live > kRunsMaxTrans) {
+        char msg[320];
+        std::snprintf(msg, sizeof(msg),
+                      "run posteriors: the largest |transition weight| (%g) is above %g, the range in which the stored forward vectors "
+                      "keep the labels the walks read: subtracting a constant from every transition weight leaves the model unchanged",
+                      p.tables_model->tmax_abs_live, kRunsMaxTrans);
+        set_error(msg);
+        return GECCO_CRF_EINVAL;
+    }
     GenArgs g;  // (with the raw state scores, which the walks shift by their own maxima)
     if ((rc = run_lattice(p, csr, "run posteriors", true, d_marg, d_lognorm, stream, g))) return rc;
     return check_hip(launch_gen_runs(g, q, stream), "run-posterior launch");

@@ -37,6 +37,7 @@ struct DeviceTables {
     DeviceBlock<double> trans;      // [L*L] raw weights (general-L Viterbi)
     double wmax_abs = 0.0, tmax_abs = 0.0;  // largest |state weight| / |transition weight| (bounds of the Viterbi exactness margin)
     double tmax = 0.0;              // largest transition weight: what exp_trans has to keep inside the range (check_exp_trans_range)
+    double tmax_abs_live = 0.0;     // largest |transition weight| among those whose exp is not 0 (the range run posteriors take)
     DeviceBlock<double> rtab[2];  // L == 2: [32] mu01(label) * 2^(j/32), the exp table of the window kernel's slot constants
     // L == 2: [A + 1] (delta_a, exp(delta_a)) for label = 0 / 1, the factor table of the product-form slot constants
     // (build_slot_table); slot_dmax / slot_prod_max_cnt: its two model constants

@@ -1087,6 +1087,10 @@ int gecco_crf_run_counts(const gecco_crf_model *m, int32_t device, const int32_t
  *     query ("anchor q: ...", "run q: ..."): a contig index outside the batch, an item outside its contig, begin < 0, begin >=
  *     end, end beyond the contig's length, a mask of 0, a mask with a bit at or above the model's label count.  The checks of
  *     the *_valued and *_constrained entries apply to attr_value and allowed.
+ *   * Refused with GECCO_CRF_EINVAL when there are queries and the largest |transition weight| among those whose exp is not 0
+ *     exceeds 150 (the whole-contig pass itself takes -700 <= max <= 700): beyond it the stored forward vectors no longer hold
+ *     the labels the walks read, and runs that need them came back -infinity.  Subtracting a constant from every transition
+ *     weight leaves the model unchanged.
  * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
 int gecco_crf_run_posteriors(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
                              const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,

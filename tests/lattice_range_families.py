@@ -15,7 +15,11 @@ planted figure to the bit.
 
 The second half of the file plants the window kernels' guard (``gen_small_ok``: spread (W - 1) < 600) for
 tests/test_window_range_host.py and tests/test_gpu_window_range.py: the spread of the base matrix set to the last grid value
-inside the guard or the first beyond it, in four shapes, and batches of contigs around a window of W items."""
+inside the guard or the first beyond it, in four shapes, and batches of contigs around a window of W items.
+
+The third part plants the models of the lattice queries (tests/test_query_range_host.py, tests/test_gpu_query_range.py): family g,
+the guard's own figures (max trans at exactly +700 and -700, and one grid step beyond either); family m, one mid leader of 150;
+family d', the alternating 800-leaders on the base and the +-600 transitions; and ``exp_zero``, the matrix the device uploads."""
 import functools
 
 import numpy as np
@@ -262,3 +266,116 @@ def window_model(L, key):
         _, shape, W, side, leaders = key
         return (leader_weights(L) if leaders else base(L)[0]), spread_model(L, shape, guard_spread(W) + side * GRID), leaders
     return model_of(L, key[0], key[1])
+
+
+# ---------------------------------------------------------------- the lattice queries (tests/test_gpu_query_range.py)
+# The nine entries behind run_lattice (crf_plan.cpp) are held to every family the pass accepts.  QUERY_LENGTHS: an empty contig,
+# contigs shorter than any run, both sides of the 8-item lane fold and of a 64-lane wave, one contig across two waves.
+QUERY_LENGTHS = (0, 1, 2, 3, 7, 8, 9, 33, 65, 129)
+QUERY_LABELS = (2, 3, 8, 9, 17, 32)
+GUARD_G = ("at+700", "at-700")           # accepted: check_exp_trans_range takes -700 <= max trans <= 700
+BEYOND_G = ("beyond+700", "beyond-700")  # refused: one grid step further out
+FAR_QUERY_B = (74.9, 151.0, 2000.0)
+LEADERS_DP = ("base", "+600", "-600")
+MID_M = ("base", "+600", "-600", "at+700", "at-700", "at+", "at-")  # (the last two: max|trans| = 150, the side run_posteriors takes)
+QUERY_FAMILIES = {"a": SHIFTS_A, "g": GUARD_G, "b": FAR_QUERY_B, "c": FORBID_C, "d'": LEADERS_DP, "m": MID_M}
+MID_LEAD = 150.0
+
+
+def guard_shift(L, which):
+    """Family g: the uniform shift that puts max trans at exactly +700 / -700 ("at+700" / "at-700"), or one grid step beyond."""
+    tmax = float(base(L)[1].max())
+    side = 1.0 if "+" in which else -1.0
+    return side * 700.0 - tmax + (side * GRID if which.startswith("beyond") else 0.0)
+
+
+def shift_any(L, which):
+    """(trans + c, c) for a key of family a, of family g or "base" (c = 0); the sum is exact on the grid."""
+    c = 0.0 if which == "base" else guard_shift(L, which) if which in GUARD_G + BEYOND_G else shift_of(L, which)
+    out = base(L)[1] + c
+    assert np.array_equal(out - c, base(L)[1]), "the shift is exact on the grid"
+    return out, c
+
+
+def mid_weights(L):
+    """Family m: the base state weights with LEAD0 giving label 0 a lead of at least 150 over every other label whatever else
+    the item carries (leader_weights' construction: the lead plus 8 max|w|)."""
+    w = base(L)[0].copy()
+    w[LEAD0, 0] = MID_LEAD + 2.0 * 4 * np.abs(w).max()
+    return w
+
+
+def mid_item(T):
+    """Family m: the one interior item of a contig of 7 or more items that carries the leader, or -1."""
+    return T // 2 if T >= 7 else -1
+
+
+@functools.lru_cache(maxsize=None)
+def mid_batch(L, lengths=QUERY_LENGTHS):
+    """batch(L, lengths) with LEAD0 appended to mid_item(T) of every contig, and to no other item."""
+    cptr, gptr, attr = batch(L, lengths)
+    rows = [list(attr[gptr[g]:gptr[g + 1]]) for g in range(int(cptr[-1]))]
+    for g0, T in zip(cptr[:-1].tolist(), lengths):
+        if mid_item(T) >= 0:
+            rows[g0 + mid_item(T)].append(LEAD0)
+    gptr2 = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    attr2 = np.array([a for r in rows for a in r], dtype=np.int32)
+    for x in (gptr2, attr2):
+        x.setflags(write=False)
+    return cptr, gptr2, attr2
+
+
+def query_model(L, family, key):
+    """(state weights, transitions, leaders) of a model of the query tests; leaders is None, "d" (the alternating 800-leaders
+    of leader_runs) or "m" (the mid leader).  Families a, b, c as model_of; g, d' and m move the base transitions by a uniform
+    shift.  d' is never combined with family b's far entry."""
+    if family in ("a", "g"):
+        return base(L)[0], shift_any(L, key)[0], None
+    if family in ("b", "c"):
+        return model_of(L, family, key)[:2] + (None,)
+    if family == "d'":
+        return leader_weights(L), shift_any(L, key)[0], "d"
+    assert family == "m"
+    return mid_weights(L), shift_any(L, key)[0], "m"
+
+
+def query_batch(L, leaders, lengths=QUERY_LENGTHS):
+    """The CSR batch of a query model over `lengths`."""
+    if leaders == "m":
+        return mid_batch(L, lengths)
+    return batch(L, lengths, leaders == "d")
+
+
+def distinct_items(L, csr, w):
+    """(csr, state weights) with one more attribute per item that no other item carries, first in its row, weights N(0, 1):
+    items without attributes, or with equal ones, have equal score rows, and whole families of paths then tie exactly -- which a
+    test that compares ranked paths (tests/test_gpu_kbest.py::accept) cannot take."""
+    cptr, gptr, attr = csr
+    n = int(cptr[-1])
+    rows = [[A + g] + list(attr[gptr[g]:gptr[g + 1]]) for g in range(n)]
+    gptr2 = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    attr2 = np.array([a for r in rows for a in r], dtype=np.int32)
+    w2 = np.concatenate([w, np.random.default_rng(7900 + L).normal(0.0, 1.0, size=(n, L))], axis=0)
+    return (cptr, gptr2, attr2), w2
+
+
+def query_shift(L, family, key):
+    """The uniform shift c by which a query model's transitions differ from its family's unshifted model (0 for b and c)."""
+    return shift_any(L, key)[1] if family in ("a", "g", "d'", "m") else 0.0
+
+
+RUNS_MAX_TRANS = 150.0
+
+
+def runs_in_range(trans):
+    """What plan_run_run_posteriors reads: the largest |transition weight| among those whose exp is not 0 is at most 150."""
+    with np.errstate(under="ignore"):
+        live = np.exp(trans) != 0.0
+    return bool(np.abs(trans[live]).max(initial=0.0) <= RUNS_MAX_TRANS)
+
+
+def exp_zero(trans):
+    """The matrix with -inf wherever numpy.exp(trans) == 0.0: what the device uploads as exp(trans), back in log space."""
+    with np.errstate(under="ignore"):
+        dead = np.exp(trans) == 0.0
+    return np.where(dead, -np.inf, trans)

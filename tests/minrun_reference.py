@@ -60,7 +60,26 @@ def _logsumexp(c, axis):
         return np.where(mx == -np.inf, -np.inf, shift + np.log(np.exp(c - np.expand_dims(shift, axis)).sum(axis=axis))).astype(c.dtype)
 
 
+REACH = 11000.0  # what one shift holds in longdouble: exp(-11356) is its smallest normal number
+
+
 def _sum_step(out, run, ins, T, m):
+    """_sum_step_once on the states within one shift's reach of the item's largest, and again on their own on those further
+    below, whose exp under that shift is 0 or subnormal; the two parts are disjoint sets of sources and add up (log-add-exp).
+    A sequence whose only feasible paths cross six transitions of weight -2000, next to infeasible states of ordinary size,
+    has log Z_C = -12000, not -inf.  Without states that far below, this is _sum_step_once and its bits."""
+    top = max(out.max(), run.max())
+    reach = max(REACH - float(T.max() - T[np.isfinite(T)].min()), 1000.0)  # (a product with the smallest exp(T - max T) has to fit as well)
+    low_o, low_r = out < top - reach, run < top - reach
+    if top == -np.inf or not ((low_o & (out > -np.inf)).any() or (low_r & (run > -np.inf)).any()):
+        return _sum_step_once(out, run, ins, T, m)
+    ninf = out.dtype.type(-np.inf)
+    near = _sum_step_once(np.where(low_o, ninf, out), np.where(low_r, ninf, run), ins, T, m)
+    far = _sum_step(np.where(low_o, out, ninf), np.where(low_r, run, ninf), ins, T, m)
+    return np.logaddexp(near[0], far[0]), np.logaddexp(near[1], far[1])
+
+
+def _sum_step_once(out, run, ins, T, m):
     """One item of the sum semiring without the item score: log-sum-exp over every destination's sources, as sums of products
     in the linear domain under one shift for the item (the largest finite forward value) and one for T -- in longdouble, whose
     exponent range holds exp of differences of ten thousand, the log-sum-exp itself to rounding."""
