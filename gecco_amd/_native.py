@@ -111,6 +111,11 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_int32, _c_i8p, _c_f64p,
          _c_i32p, _c_f64p],
     ),
+    "gecco_crf_max_marginals": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_u32p, ctypes.c_int32, _c_i32p,
+         _c_i32p, _c_i32p, _c_u32p, ctypes.c_int32, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_viterbi_min_run": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_i8p,
@@ -866,6 +871,64 @@ class Model:
         _check(self._lib.gecco_crf_viterbi_kbest(
             *head, values, allowed, k, _ptr(y, _c_i8p), _ptr(score, _c_f64p), _ptr(n_paths, _c_i32p), _ptr(ln, _c_f64p)))
         return y[:n - n0], score[:nc], n_paths[:nc], ln[:nc]
+
+    def max_marginals(self, contig_ptr, gene_ptr, attr_id, sets=None, spans=None, device=0, values=None, allowed=None,
+                      want_through=True, want_inside=True, want_outside=True, want_span_best=True, want_span_broken=True,
+                      want_lognorm=False):
+        """Max-marginals of the whole-contig lattice (``gecco_crf_max_marginals``): scores of best paths under a restriction,
+        from one max-plus forward and one backward walk of the batch.  Returns a dict that holds only what was asked for:
+        ``"best"`` float64 ``[n_contigs]``, the score of the contig's best path (``viterbi_kbest``'s rank-0 bits; 0 for a
+        contig without genes);
+        ``"through"`` (``want_through``) ``[n, L]``: the score of the best path of the gene's contig that gives the gene that
+        label -- ``-inf`` where no such path exists, never NaN, and not clamped to ``best``;
+        ``"inside"``, ``"outside"`` (``sets``: 1 to 32 uint32 masks, bit y set when label y is in the set) ``[n, n_sets]``:
+        the maximum of ``through`` over the labels in / not in the set (``-inf`` for an empty or wholly disallowed side);
+        ``"span_best"``, ``"span_broken"`` (``spans``: ``(contig, begin, end, mask)`` arrays as ``span_log_probabilities``
+        takes them) ``[n_spans]``: the score of the best path whose labels on the span all lie in the set, and of the best
+        path with a label outside it somewhere on the span;
+        ``"lognorm"`` (``want_lognorm``) ``[n_contigs]`` as ``marginals_full`` gives it -- the only output that runs the
+        sum-product pass.
+        The numbers are path scores: a difference of two is the log of the ratio of two single paths' probabilities, not a
+        posterior.  ``values`` and ``allowed`` as in ``marginals_full``: with ``allowed`` the lattice is the restricted one."""
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        L = self.num_labels
+        ns = nq = 0
+        sm = None
+        if sets is not None:
+            sm = np.ascontiguousarray(sets, dtype=np.uint32).ravel()
+            ns = sm.size
+        if spans is not None:
+            sc, sb, se = (_i32(x).ravel() for x in spans[:3])
+            sq = np.ascontiguousarray(spans[3], dtype=np.uint32).ravel()
+            nq = sc.size
+            if not (sb.size == nq and se.size == nq and sq.size == nq):
+                raise ValueError("max_marginals: the span arrays differ in length")
+        rows = max(n - n0, 1)
+        width = ns if 1 <= ns <= 32 else 1  # (the library refuses any other number of sets: the buffers only need a size)
+        out = {"best": np.zeros(max(nc, 1), dtype=np.float64)}
+        if want_through:
+            out["through"] = np.zeros((rows, L), dtype=np.float64)
+        if sets is not None and want_inside:
+            out["inside"] = np.zeros((rows, width), dtype=np.float64)
+        if sets is not None and want_outside:
+            out["outside"] = np.zeros((rows, width), dtype=np.float64)
+        if spans is not None and want_span_best:
+            out["span_best"] = np.zeros(max(nq, 1), dtype=np.float64)
+        if spans is not None and want_span_broken:
+            out["span_broken"] = np.zeros(max(nq, 1), dtype=np.float64)
+        if want_lognorm:
+            out["lognorm"] = np.zeros(max(nc, 1), dtype=np.float64)
+        ptr = {k: _ptr(v, _c_f64p) for k, v in out.items()}
+        pad_i, pad_u = np.zeros(1, dtype=np.int32), np.zeros(1, dtype=np.uint32)
+        span_args = [None, None, None, None] if spans is None else [
+            _ptr(sc if nq else pad_i, _c_i32p), _ptr(sb if nq else pad_i, _c_i32p), _ptr(se if nq else pad_i, _c_i32p),
+            _ptr(sq if nq else pad_u, _c_u32p)]
+        _check(self._lib.gecco_crf_max_marginals(
+            *head, values, allowed, None if sm is None else _ptr(sm if ns else pad_u, _c_u32p), ns, *span_args, nq,
+            ptr.get("through"), ptr.get("inside"), ptr.get("outside"), ptr.get("span_best"), ptr.get("span_broken"), ptr["best"],
+            ptr.get("lognorm")))
+        size = {"through": n - n0, "inside": n - n0, "outside": n - n0, "span_best": nq, "span_broken": nq, "best": nc, "lognorm": nc}
+        return {k: v[:size[k]] for k, v in out.items()}
 
     def viterbi_min_run(self, contig_ptr, gene_ptr, attr_id, set_mask, min_run, device=0, values=None, allowed=None,
                         want_lognorm=True):

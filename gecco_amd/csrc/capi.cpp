@@ -1337,6 +1337,92 @@ GECCO_API int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, 
     GECCO_GUARD_END
 }
 
+// ---- max-marginals (ABI 2.25.0): the score of the best whole-contig path through every (gene, label) pair, its maxima inside and
+// outside label sets, and per span the best path that stays inside a set and the best one that leaves it, from a max-plus
+// forward and backward walk behind gl_state; log Z, when asked for, from the whole-contig marginals pass (crf_maxmarg.hip,
+// DESIGN.md §4.9p)
+GECCO_API int gecco_crf_max_marginals(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                      const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                      const uint32_t *allowed, const uint32_t *set_mask, int32_t n_sets, const int32_t *span_contig,
+                                      const int32_t *span_begin, const int32_t *span_end, const uint32_t *span_mask, int32_t n_spans,
+                                      double *through, double *inside, double *outside, double *span_best, double *span_broken,
+                                      double *best, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    if (n_sets < 0 || n_sets > kMaxMargSets) return fail("max_marginals: n_sets = " + std::to_string(n_sets) + " is outside 0 .. 32");
+    if (n_sets > 0 && !set_mask) return fail("max_marginals: null buffer (set_mask)");
+    for (int32_t s = 0; s < n_sets; ++s)
+        if ((rc = check_label_set("max_marginals: set", s, set_mask[s], m->m.L))) return rc;
+    if (n_sets == 0 && (inside || outside)) return fail("max_marginals: inside or outside given without a label set");
+    if (n_spans < 0) return fail("max_marginals: negative number of spans");
+    if (n_spans == 0 && (span_best || span_broken)) return fail("max_marginals: span_best or span_broken given without spans");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    if (n_contigs > 0 && !best) return fail("max_marginals: null buffer (best)");
+    if (n_spans > 0 && (!span_contig || !span_begin || !span_end || !span_mask)) return fail("max_marginals: null buffer (spans)");
+    std::vector<SpanQuery> spans(static_cast<size_t>(n_spans));
+    for (int32_t q = 0; q < n_spans; ++q) {
+        const int32_t c = span_contig[q], b = span_begin[q], e = span_end[q];
+        int64_t len;
+        if ((rc = check_query_contig("max_marginals: span", q, c, n_contigs, contig_ptr, &len))) return rc;
+        if ((rc = check_query_range("max_marginals: span", q, c, b, e, len))) return rc;
+        if ((rc = check_label_set("max_marginals: span", q, span_mask[q], m->m.L))) return rc;
+        spans[size_t(q)] = SpanQuery{c, b, e, span_mask[q]};
+    }
+    const size_t nc = size_t(n_contigs), L = size_t(m->m.L), ns = size_t(n_sets);
+    const size_t nq = (span_best || span_broken) ? size_t(n_spans) : 0;  // (spans without an output: nothing to walk)
+    // per gene: through, inside, outside, each only when asked for.  Per contig, behind log Z: best.  (The marginals are the
+    // pass's own output and are not returned; the pass runs only when lognorm is asked for.)
+    const size_t per_gene = (through ? L * 8 : 0) + (inside ? ns * 8 : 0) + (outside ? ns * 8 : 0);
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, per_gene, 8, nullptr, lognorm,
+                        [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: every contig's one path is the empty one -- gecco_crf_viterbi's score)
+            for (size_t c = 0; c < nc; ++c) best[c] = 0.0;
+            return int(GECCO_CRF_OK);
+        }
+        const size_t n = size_t(b.n);
+        double *d_lognorm = b.out<double>(2), *d_best = d_lognorm + nc;
+        MaxMargArgs a{};
+        for (size_t s = 0; s < ns; ++s) a.set_mask[s] = set_mask[s];
+        a.n_sets = n_sets;
+        a.n_spans = int32_t(nq);
+        double *at = b.out<double>(1);
+        if (through) a.through = at, at += n * L;
+        if (inside) a.inside = at, at += n * ns;
+        if (outside) a.outside = at;
+        a.best = d_best;
+        // the walks' workspace, a block of its own (folded into the batch's block, a 32-label call with spans took 30 ms for 1.6:
+        // profiles/MEASUREMENTS.md 7q)
+        DeviceBlock<char> ws, q;
+        const size_t b_half = align256(maxmarg_workspace_bytes(b.n, m->m.L) / 2);
+        int rc = ws.alloc(2 * b_half, "hipMalloc max-marginal workspace");
+        if (rc) return rc;
+        a.fwd = reinterpret_cast<double *>(ws.get());
+        a.bwd = reinterpret_cast<double *>(ws.get() + b_half);
+        double *d_span_best = nullptr, *d_span_broken = nullptr;
+        if (nq) {
+            const size_t b_spans = align256(nq * sizeof(SpanQuery));
+            if ((rc = upload_queries(q, spans.data(), nq * sizeof(SpanQuery), b_spans + 2 * nq * 8, "hipMalloc spans", "upload spans")))
+                return rc;
+            a.spans = reinterpret_cast<const SpanQuery *>(q.get());
+            d_span_best = reinterpret_cast<double *>(q.get() + b_spans);
+            d_span_broken = d_span_best + nq;
+            a.span_best = span_best ? d_span_best : nullptr;
+            a.span_broken = span_broken ? d_span_broken : nullptr;
+        }
+        rc = batch_wait(plan_run_max_marginals(b.plan, b.csr, a, b.out<double>(0), lognorm ? d_lognorm : nullptr, nullptr), "max-marginals");
+        rc = batch_fetch(rc, through, a.through, n * L * 8, "download through");
+        rc = batch_fetch(rc, inside, a.inside, n * ns * 8, "download inside");
+        rc = batch_fetch(rc, outside, a.outside, n * ns * 8, "download outside");
+        rc = batch_fetch(rc, span_best, d_span_best, nq * 8, "download span_best");
+        rc = batch_fetch(rc, span_broken, d_span_broken, nq * 8, "download span_broken");
+        return batch_fetch(rc, best, d_best, nc * 8, "download best");
+    });
+    GECCO_GUARD_END
+}
+
 // ---- decoding under a minimum run length (ABI 2.20.0): the best path among those whose every run of labels of a set has at
 // least min_run genes, and the log-mass of all such paths, on a lattice expanded by a run counter behind gl_state; log Z from the
 // whole-contig marginals pass (crf_minrun.hip)

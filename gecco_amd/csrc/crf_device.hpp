@@ -431,6 +431,29 @@ size_t counts_back_bytes(int64_t n_genes, int32_t L, int32_t max_runs);
 hipError_t launch_gen_run_counts(const GenArgs &a, uint32_t set_mask, int32_t max_runs, uint8_t *back, double *log_mass,
                                  double *score, int8_t *y, hipStream_t stream);
 
+// ---- max-marginals (crf_maxmarg.hip) ----
+constexpr int32_t kMaxMargSets = 32;  // label sets of one call
+// the kernels' own workspace: the max-plus forward and backward vectors, two doubles per (gene, label)
+size_t maxmarg_workspace_bytes(int64_t n_genes, int32_t L);
+// What one call asks for.  fwd and bwd [n_genes][L] are the two halves of the workspace; best [n_contigs] is always written.
+// Every other output is optional, null = not formed: through [n_genes][L]; inside, outside [n_genes][n_sets] (they need a set);
+// span_best, span_broken [n_spans] for the checked queries `spans`.  The host has checked that every mask has a bit, and none
+// at or above L.
+struct MaxMargArgs {
+    uint32_t set_mask[kMaxMargSets];
+    int32_t n_sets, n_spans;
+    const SpanQuery *spans;
+    double *fwd, *bwd;
+    double *through, *inside, *outside, *span_best, *span_broken, *best;
+};
+// best[c] = the score of contig c's best label path (gl_kbest_forward's rank-0 bits; 0 for a contig without genes), through[g][l] =
+// the score of the best path of g's contig with label l at g (-infinity without one, never NaN), inside / outside[g][s] its
+// maximum over the labels in / not in set s, span_best[q] the score of the best path whose labels on the span all lie in the
+// query's set, span_broken[q] that of the best path with a label outside the set somewhere on the span.  On the lattice of the
+// gl_state launch that ran before it on the same stream with a.state non-null: reads a.state, a.trans, a.contig_ptr and
+// a.n_genes.  Four launches at the most: the forward walk, the backward walk, the epilogue over the genes, the span walks.
+hipError_t launch_gen_max_marginals(const GenArgs &a, const MaxMargArgs &p, hipStream_t stream);
+
 // ---- edge posteriors (crf_edges.hip) ----
 constexpr int32_t kMaxEdgeSets = 32;   // label sets of one call
 constexpr int32_t kEdgeRunGenes = 32;  // genes of a run: what one group of lanes walks, counted from its contig's first gene

@@ -1497,6 +1497,35 @@ int plan_run_run_counts(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_
     return check_hip(launch_gen_run_counts(g, set_mask, max_runs, d_back, d_log_mass, d_score, d_y, stream), "run-count launch");
 }
 
+int plan_run_max_marginals(Plan &p, const DeviceCsr &csr, const MaxMargArgs &q, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    if (q.n_sets < 0 || q.n_sets > kMaxMargSets || q.n_spans < 0 || (q.n_sets == 0 && (q.inside || q.outside))) {
+        set_error("the number of label sets is outside 0 .. 32 (1 .. 32 with inside or outside), or a negative number of spans");
+        return GECCO_CRF_EINVAL;
+    }
+    for (int32_t s = 0; s < q.n_sets; ++s)
+        if (!set_mask_ok(p, q.set_mask[s])) return GECCO_CRF_EINVAL;
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !q.fwd || !q.bwd || !q.best || (d_lognorm && !d_marg) ||
+                      (q.n_spans > 0 && (!q.spans || (!q.span_best && !q.span_broken))), rc))
+        return rc;
+    GenArgs g;
+    if (d_lognorm) {  // (the pass gives log Z; the max walks read the raw state scores and nothing else)
+        if ((rc = run_lattice(p, csr, "max-marginals", true, d_marg, d_lognorm, stream, g))) return rc;
+    } else {  // the state scores alone: no exp(trans) is read, and no transition range applies
+        SeqArgs a;
+        if ((rc = begin_whole_contig(p, csr, 0, a, stream))) return rc;
+        if (!p.lattice || !p.general) {
+            set_error("the plan was not built for max-marginals");
+            return GECCO_CRF_EINVAL;
+        }
+        if ((rc = fill_gen_args(p, csr, g, false, stream))) return rc;
+        g.E = g.smax = nullptr;
+        if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch"))) return rc;
+    }
+    return check_hip(launch_gen_max_marginals(g, q, stream), "max-marginal launch");
+}
+
 int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, double *d_marg, double *d_lognorm, hipStream_t stream) {
     if (q.n_sets < 0 || q.n_sets > kMaxEdgeSets || (q.n_sets == 0 && (q.enter || q.leave))) {
         set_error("the number of label sets is outside 1 .. 32 (0 without enter and leave)");

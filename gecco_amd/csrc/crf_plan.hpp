@@ -167,7 +167,7 @@ struct Plan {
     // (DeviceCsr::allowed), which is refused when it brings masks to a layout without `masked`, or none to one with it.
     bool masked = false;
     // Lattice queries (plan_run_span_probabilities, plan_run_span_conditionals, plan_run_sample_paths, plan_run_viterbi_kbest, plan_run_edge_posteriors,
-    // plan_run_viterbi_min_run, plan_run_run_posteriors, plan_run_marginals_min_run, plan_run_run_counts).  `lattice` is
+    // plan_run_viterbi_min_run, plan_run_run_posteriors, plan_run_marginals_min_run, plan_run_run_counts, plan_run_max_marginals).  `lattice` is
     // set by the owner before plan_build: the layout takes the any-L kernels at every label count, as `valued` and `masked` do --
     // the queries' kernels read the forward vectors and raw state scores of their workspace, which a 2-label plan does not have
     // otherwise.  Nothing else changes: reference-bits mode is decided as ever.
@@ -267,6 +267,13 @@ int plan_run_run_counts(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_
 // (crf_edges.hip; crf_device.hpp: EdgeQuery -- device pointers throughout, the run table that of this layout's contigs), all on
 // `stream`.  An edge is independent of every other: the query is parallel over genes, a contig of any length included.
 int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, double *d_marg, double *d_lognorm, hipStream_t stream);
+// Max-marginals, a plan laid out with `lattice`: gl_state with the raw state scores kept, then the max-plus forward and backward
+// walks, the epilogue over the genes and the span walks that `q` asks for (crf_maxmarg.hip; crf_device.hpp: MaxMargArgs -- device
+// pointers throughout, its workspace of maxmarg_workspace_bytes included).  The max walks read the state scores alone: the
+// whole-contig marginals of the batch run (exactly as plan_run_marginals_full runs them, into d_marg [n_genes][L] and d_lognorm
+// [n_contigs]) only when d_lognorm is given, and a call without it takes models whose transitions lie outside the sum-product
+// kernels' range.  Not chunked.  All on `stream`.
+int plan_run_max_marginals(Plan &p, const DeviceCsr &csr, const MaxMargArgs &q, double *d_marg, double *d_lognorm, hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);
 int get_device_tables(const Model &m, int device, const DeviceTables **out);

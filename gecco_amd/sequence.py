@@ -547,6 +547,82 @@ class SequenceCRF:
                         "scores": score[s, :m].copy(), "log_probabilities": score[s, :m] - lognorm[s]})
         return out
 
+    # ---- max-marginals: scores of best paths under a restriction (``_native.Model.max_marginals``).  Every number is a path score
+    # or a difference of two: the log of the ratio of the probabilities of two single paths, NOT a posterior (a margin of 3 says the
+    # best competing reading is e^3 times less probable than the best one, not that the call holds with probability 0.95), on the
+    # whole-sequence lattice of ``predict``, not a windowed one.
+    def predict_max_marginals(self, X, sets=None, allowed=None) -> List[Dict[str, object]]:
+        """Max-marginals: per sequence a dict with ``through``, float64 ``[n_items, L]``, ``through[t, l]`` the score of the best
+        whole-sequence label path that gives item t the label ``classes_[l]`` (``-inf`` where ``allowed`` leaves no such path);
+        ``best``, the score of ``predict``'s path; ``margins`` = ``through - best``, ``<= 0`` up to a few ulps: how much worse the
+        best reading becomes when the item is labelled that way; and, with ``sets`` (a list of label sets, each a label or a
+        ``set`` / ``frozenset`` / ``list`` / ``tuple`` of labels), ``inside`` and ``outside``, ``[n_items, n_sets]``: the best
+        score with the item's label in / not in the set (``-inf`` for a side that is empty or wholly disallowed).
+
+        These are score differences -- the log of the ratio of the probabilities of two single paths --, not posteriors:
+        ``predict_marginals`` sums over all paths, this takes the best one.  They live on the whole-sequence lattice (that of
+        ``predict``), not a windowed one.  One max-plus forward and one backward walk over ``X``, one native call per 32 sets;
+        no forward-backward pass runs.  A sequence without items gets empty arrays and ``best`` 0.0.  Raises ``ValueError``
+        before any device call for an unknown label or an empty set."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = None
+        if sets is not None:
+            try:
+                sets = list(sets)
+            except TypeError:
+                raise ValueError(f"sets is a list of label sets, got {sets!r}") from None
+            bits = np.array([self._label_bits(f"set {q}", labels) for q, labels in enumerate(sets)], dtype=np.uint32)
+        n_seqs, L = len(seq_ptr) - 1, len(self.classes_)
+        n_sets = 0 if bits is None else len(bits)
+        if seq_ptr[-1] == 0:
+            out = [{"through": np.zeros((0, L)), "margins": np.zeros((0, L)), "best": 0.0} for _ in range(n_seqs)]
+            if bits is not None:
+                for o in out:
+                    o["inside"], o["outside"] = np.zeros((0, n_sets)), np.zeros((0, n_sets))
+            return out
+        first = self._model.max_marginals(seq_ptr, item_ptr, attr, sets=bits[:32] if n_sets else None, device=self.device,
+                                          values=values, allowed=masks)
+        inside, outside = [first.get("inside")], [first.get("outside")]
+        for k in range(32, n_sets, 32):
+            part = self._model.max_marginals(seq_ptr, item_ptr, attr, sets=bits[k:k + 32], device=self.device, values=values,
+                                             allowed=masks, want_through=False)
+            inside.append(part["inside"])
+            outside.append(part["outside"])
+        out = []
+        for s, th in enumerate(self._split(first["through"], seq_ptr)):
+            best = float(first["best"][s])
+            out.append({"through": th, "margins": th - best if len(th) else th.copy(), "best": best})
+        if bits is not None:
+            rows = int(seq_ptr[-1])
+            ins = np.concatenate(inside, axis=1) if n_sets else np.zeros((rows, 0))
+            outs = np.concatenate(outside, axis=1) if n_sets else np.zeros((rows, 0))
+            for o, a, b in zip(out, self._split(ins, seq_ptr), self._split(outs, seq_ptr)):
+                o["inside"], o["outside"] = a, b
+        return out
+
+    def span_best_scores(self, X, spans, allowed=None) -> Dict[str, np.ndarray]:
+        """For every ``(sequence_index, start, stop, labels)`` of ``spans`` (written as ``span_log_probability`` takes them) the
+        scores of three best whole-sequence paths, each float64 ``[n_spans]``: ``best``, the sequence's best path (``predict``'s);
+        ``inside``, the best path that gives EVERY item of ``X[sequence_index][start:stop]`` a label of ``labels`` -- the score
+        ``predict(X, allowed=...)`` reaches with the span pinned to the set --; ``broken``, the best path that gives at least
+        one item of the span a label outside ``labels``.  ``-inf`` where no such path exists (``broken`` when ``labels`` holds
+        every label).  ``max(inside, broken) = best`` up to rounding.
+
+        ``best - inside`` and ``best - broken`` are score differences -- the log of the ratio of the probabilities of two single
+        paths --, not posteriors (``span_log_probability`` gives those).  They live on the whole-sequence lattice, not a windowed
+        one; with ``allowed`` (as in ``predict``) on the restricted one.  All spans take two walks over ``X`` and a walk over
+        each span, in one native call.  Raises ``ValueError`` before any device call for an unknown label, an empty set, a
+        sequence index out of range, ``start >= stop`` or ``start < 0``, and ``stop`` beyond the sequence."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        contig, begin, end, mask = self._span_queries(spans, seq_ptr)
+        if len(contig) == 0:
+            return {"best": np.zeros(0), "inside": np.zeros(0), "broken": np.zeros(0)}
+        got = self._model.max_marginals(seq_ptr, item_ptr, attr, spans=(contig, begin, end, mask), device=self.device, values=values,
+                                        allowed=masks, want_through=False)
+        return {"best": got["best"][contig], "inside": got["span_best"], "broken": got["span_broken"]}
+
     @staticmethod
     def _min_run(min_run) -> int:
         try:

@@ -108,6 +108,15 @@ None without a run); ``log_p``.  Rank 0 is the Viterbi path's reading.  The comm
 ``cluster_id, rank, start, end, type, log_p, p``; start, end and type empty without a run); ``clusters.tsv`` is unchanged, and
 without the option the tables and every launch are unchanged.
 
+Margins (opt-in: ``margins=True``, ``predict --margins``).  "How much worse is the best reading without this cluster, or one that
+breaks it somewhere": differences of best-path scores from the max-marginals of the whole-contig lattice
+(``_native.Model.max_marginals``: one max-plus forward and one backward walk of the batch and a short walk per call, one native
+call for all clusters, no forward-backward pass).  Every cluster gets ``margin_present``, ``margin_absent``, ``margin_broken`` and
+``type_margins`` (``TypedClusterCRF._margins`` defines them).  They are score differences -- the log of the ratio of the
+probabilities of two single label paths -- and not posteriors; they live on the whole-contig lattice (that of the path clusters),
+not the windowed one the calls come from.  ``clusters.tsv`` then has the columns ``margin_present``, ``margin_absent`` and
+``margin_broken`` behind every other optional column; without the flag the tables and every launch are unchanged.
+
 Path clusters (``predict_path_clusters(genes, min_run=M)``, ``predict --path-clusters M``, 1 <= M <= 32).  The refiner drops a
 cluster of fewer than ``n_cds`` annotated genes after the fact; a decoded path with its short runs deleted is not the best path
 among those without short runs -- the model may prefer to stretch a run of two genes to three, or to merge two runs across a gap
@@ -305,7 +314,8 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
     cluster of the list that does not: NaN, and its own start and end); last ``start_p`` and ``end_p`` when clusters carry
     boundary posteriors (``boundary_posteriors=True``), then ``run_anchor_p``, ``run_p``, ``run_start_lo``, ``run_start_hi``,
     ``run_end_lo``, ``run_end_hi``, ``run_start_beyond_p`` and ``run_end_beyond_p`` when clusters carry run posteriors
-    (``run_posteriors=True``)."""
+    (``run_posteriors=True``), then ``margin_present``, ``margin_absent`` and ``margin_broken`` when clusters carry margins
+    (``margins=True``)."""
     table = tables.ClusterTable.from_clusters(clusters)
     extra = []
     for name in sorted(types, key=str.casefold):
@@ -350,6 +360,12 @@ def typed_cluster_table(clusters: Sequence[Any], types: Sequence[str]) -> tables
         table.columns["run_start_beyond_p"] = [float(getattr(c, "run_start_beyond_probability", nan)) for c in clusters]
         table.columns["run_end_beyond_p"] = [float(getattr(c, "run_end_beyond_probability", nan)) for c in clusters]
         extra += [("run_start_beyond_p", float, None), ("run_end_beyond_p", float, None)]
+    # best-path score margins, behind every other optional column: only when clusters carry them (``margins=True``)
+    if any(hasattr(c, "margin_present") for c in clusters):
+        nan = float("nan")
+        for col in ("margin_present", "margin_absent", "margin_broken"):
+            table.columns[col] = [float(getattr(c, col, nan)) for c in clusters]
+            extra.append((col, float, None))
     at = [n for n, _, _ in tables.ClusterTable.COLUMNS].index("type") + 1
     table.COLUMNS = tables.ClusterTable.COLUMNS[:at] + extra + tables.ClusterTable.COLUMNS[at:]
     return table
@@ -580,7 +596,8 @@ class TypedClusterCRF:
                          trim: bool = True, pad: bool = True, known: Optional[tables.ClusterTable] = None,
                          region_posteriors: bool = False, boundary_samples: int = 0, seed: int = 0, alternatives: int = 0,
                          alternatives_margin: int = 10, boundary_posteriors: bool = False, run_posteriors: bool = False,
-                         run_reach: int = 256, attributions: bool = False, attribution_reach: int = 10) -> List[Any]:
+                         run_reach: int = 256, attributions: bool = False, attribution_reach: int = 10,
+                         margins: bool = False) -> List[Any]:
         """Clusters by the refiner's ``gecco`` criterion on the any-cluster probability (the segment kernel, one grouper
         per contig as the CLI runs it), each with ``type`` and ``type_probabilities`` from the labels' probabilities, with
         ``region_posteriors`` each with ``region_probability`` and ``region_type_probabilities``, and with
@@ -595,14 +612,51 @@ class TypedClusterCRF:
         negative before it), its ``contribution`` -- log P(every gene of the call lies in a cluster | x) minus the same without
         anything the gene carries, exact, positive where the call leans on the gene -- and ``domains``, the ``(name,
         contribution)`` of each of its domains the model knows; the cluster's ``attribution_log_probability`` is the
-        log-probability they are differences of."""
+        log-probability they are differences of, and with ``margins`` each with ``margin_present``, ``margin_absent``,
+        ``margin_broken`` and ``type_margins`` (``_margins``): differences of best-path scores on the whole-contig lattice, not
+        posteriors."""
         return self.predict_genes_and_clusters(genes, threshold=threshold, n_cds=n_cds, edge_distance=edge_distance, trim=trim,
                                                pad=pad, known=known, region_posteriors=region_posteriors,
                                                boundary_samples=boundary_samples, seed=seed, alternatives=alternatives,
                                                alternatives_margin=alternatives_margin,
                                                boundary_posteriors=boundary_posteriors, run_posteriors=run_posteriors,
                                                run_reach=run_reach, attributions=attributions,
-                                               attribution_reach=attribution_reach)[1]
+                                               attribution_reach=attribution_reach, margins=margins)[1]
+
+    def _margins(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int, clusters: List[Any]) -> None:
+        """The margins of every called cluster (``rows``: the segment kernel's (contig, number, first gene, last gene + 1)),
+        from ONE native call over the batch (``_native.Model.max_marginals``): per cluster one span with the set of every label
+        but the background, one with the background alone, and one per type with the labels whose names contain it.  With
+        ``best`` the score of the contig's Viterbi path (read off the max-marginals at the call's last gene: the same number up
+        to a few ulps, in the summation order a span's score ends in, so that an exact 0.0 is an exact 0.0):
+        ``margin_present`` = best - (the best path that gives every gene of the call a cluster label): 0.0 when the Viterbi path
+        keeps the whole call inside a cluster;
+        ``margin_absent`` = best - (the best path that gives every gene of the call the background): the score the best reading
+        loses when the call is removed altogether;
+        ``margin_broken`` = best - (the best path that gives at least one gene of the call the background);
+        ``type_margins`` = {type: best - (the best path that gives every gene of the call a label of that type)}.
+        Each is a difference of two path scores, that is, the log of the ratio of the probabilities of two single label paths
+        (``inf`` where no path qualifies) -- not a posterior: ``region_posteriors`` sums over all paths, a margin compares the
+        two best.  The paths are those of the whole-contig lattice (``predict_path_clusters``'s), not of the windowed one the
+        calls themselves come from, so a call the windowed marginals make may have a positive ``margin_present``."""
+        type_masks = [sum(1 << l for l, names in enumerate(self.label_types_) if t in names) for t in self.types_]
+        full = (1 << len(self.classes_)) - 1
+        sets = [not_background, full & ~not_background] + type_masks
+        contig = np.repeat(rows[:, 0], len(sets)).astype(np.int32)
+        begin = np.repeat(rows[:, 2] - item_ptr[rows[:, 0]], len(sets)).astype(np.int32)
+        end = np.repeat(rows[:, 3] - item_ptr[rows[:, 0]], len(sets)).astype(np.int32)
+        mask = np.tile(np.array(sets, dtype=np.uint32), len(rows))
+        got = self._fitted().max_marginals(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id, spans=(contig, begin, end, mask),
+                                           device=self.device, allowed=allowed)
+        # ``best`` as the forward and backward vectors give it at the call's last gene: the contig's best score up to a few ulps
+        # (a max-marginal is a sum in another order than the Viterbi score), and the very sum a span's score ends in -- so a call
+        # the Viterbi path contains gets exactly 0.0, not a rounding residue of either sign
+        best = np.repeat(got["through"][rows[:, 3] - 1].max(axis=1), len(sets)).reshape(len(rows), len(sets))
+        inside = best - got["span_best"].reshape(len(rows), len(sets))
+        broken = best - got["span_broken"].reshape(len(rows), len(sets))
+        for cluster, row, brk in zip(clusters, inside.tolist(), broken[:, 0].tolist()):
+            cluster.margin_present, cluster.margin_absent, cluster.margin_broken = row[0], row[1], brk
+            cluster.type_margins = dict(zip(self.types_, row[2:]))
 
     def _region_posteriors(self, batch, allowed, rows: np.ndarray, item_ptr: np.ndarray, not_background: int,
                            clusters: List[Any]) -> None:
@@ -980,7 +1034,7 @@ class TypedClusterCRF:
                                    alternatives_margin: int = 10,
                                    boundary_posteriors: bool = False, run_posteriors: bool = False,
                                    run_reach: int = 256, attributions: bool = False,
-                                   attribution_reach: int = 10) -> Tuple[List[Any], List[Any]]:
+                                   attribution_reach: int = 10, margins: bool = False) -> Tuple[List[Any], List[Any]]:
         """``(predict_probabilities(genes), predict_clusters(genes))`` from one device pass; with ``region_posteriors`` a
         second, whole-contig pass gives every cluster its region posteriors, and with ``boundary_samples = N > 0`` one more
         draws N label paths per contig under ``seed`` and gives every cluster its boundary intervals; with ``alternatives = K >
@@ -991,7 +1045,8 @@ class TypedClusterCRF:
         the exact start and end distributions of the run through its anchor, over ``run_reach`` (0 .. 65536) genes to either
         side (module docstring); with ``attributions`` one more whole-contig pass and one native call give every cluster the
         exact knock-out contribution of every gene and domain in it and ``attribution_reach`` genes around it
-        (``predict_clusters``).  ``ValueError`` before any device call for an option
+        (``predict_clusters``); with ``margins`` one native call (two max-plus walks of the contigs, no forward-backward pass)
+        gives every cluster its best-path score margins (``_margins``).  ``ValueError`` before any device call for an option
         that is not an integer or lies outside its range."""
         from . import _native
 
@@ -1062,6 +1117,8 @@ class TypedClusterCRF:
             self._run_posteriors(batch, allowed, rows, item_ptr, not_background, clusters, annotated, p_any, run_reach)
         if attributions and clusters:
             self._attributions(batch, allowed, rows, item_ptr, not_background, clusters, annotated, attribution_reach)
+        if margins and clusters:
+            self._margins(batch, allowed, rows, item_ptr, not_background, clusters)
         return annotated, clusters
 
 
@@ -1231,6 +1288,10 @@ def build_parser() -> argparse.ArgumentParser:
                     "one gene, or one domain of a gene, is taken out of the input, for the genes in and around it")
     pr.add_argument("--attribution-reach", type=int, default=10, metavar="R",
                     help="genes on either side of a called region that attributions.tsv covers (with --attributions)")
+    pr.add_argument("--margins", action="store_true",
+                    help="add margin_present, margin_absent and margin_broken to clusters.tsv: how much the score of the best "
+                    "whole-contig label path drops when every gene of a called region must lie in a cluster, must not, or when one "
+                    "must not (log-ratios of two paths' probabilities, not posteriors)")
     pr.add_argument("--path-clusters", type=int, default=None, metavar="M",
                     help="write path_clusters.tsv and paths.tsv: the regions of the best whole-contig label path among those in "
                     "which every region has at least M (at most 32) genes, and per contig that path's probability and the "
@@ -1285,7 +1346,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                                                       alternatives_margin=args.alternatives_margin,
                                                       boundary_posteriors=args.boundary_posteriors,
                                                       run_posteriors=args.run_posteriors, run_reach=args.run_reach,
-                                                      attributions=args.attributions, attribution_reach=args.attribution_reach)
+                                                      attributions=args.attributions, attribution_reach=args.attribution_reach,
+                                                      margins=args.margins)
     os.makedirs(args.output_dir, exist_ok=True)
     tables.GeneTable.from_genes(annotated).dump(os.path.join(args.output_dir, "genes.tsv"))
     tables.FeatureTable.from_genes(annotated).dump(os.path.join(args.output_dir, "features.tsv"))

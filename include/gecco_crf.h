@@ -53,7 +53,7 @@ const char *gecco_crf_last_error(void);
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
  * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts, ABI 2.24.0
- * gecco_crf_span_conditionals. */
+ * gecco_crf_span_conditionals, ABI 2.25.0 gecco_crf_max_marginals. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -877,6 +877,60 @@ int gecco_crf_viterbi_kbest(const gecco_crf_model *m, int32_t device, const int3
                             const uint32_t *allowed /* NULL: no masks */, int32_t k, int8_t *y /* [n_genes][k] */,
                             double *score /* [n_contigs][k] */, int32_t *n_paths /* [n_contigs] */,
                             double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- max-marginals (ABI 2.25.0, additive; gecco_crf_version() stays 340) ----------------------------------------------------------
+ * through[g * L + l] = the score of the best label path of gene g's contig that gives gene g the label l, on the whole-contig
+ * lattice of gecco_crf_viterbi and gecco_crf_viterbi_kbest (not a windowed one): to gecco_crf_viterbi what
+ * gecco_crf_marginals_full is to the sum-product pass.  best[c] - through is how much worse the best reading becomes when a gene is
+ * labelled differently.  These are score differences -- the log of the ratio of two single paths' probabilities --, not
+ * posteriors.  With `allowed` (one mask per gene, as the *_constrained entries take them) the lattice is the restricted one.
+ * attr_value and allowed may each be NULL.  The walks are parallel over contigs and labels and sequential along a contig
+ * (contigs are not chunked); one more walk than gecco_crf_viterbi.
+ *   * Definitions, for a contig of T genes with raw state scores s_t(l) (-infinity where `allowed` forbids) and raw transition
+ *     weights A; every addition is rounded on its own, in the order written:
+ *       forward    a_0(j) = s_0(j),   a_t(j) = max_i (a_{t-1}(i) + A(i, j)) + s_t(j)      (gecco_crf_viterbi's order)
+ *       best[c]    = max_j a_{T-1}(j): the score bits of gecco_crf_viterbi_kbest's rank 0
+ *       backward   b_{T-1}(i) = 0,    b_t(i) = max_j ((b_{t+1}(j) + s_{t+1}(j)) + A(i, j))
+ *       through    = a_t(l) + b_t(l).  It is not clamped: under rounding it may differ from best[c] by a few ulps on the Viterbi
+ *                  path; with weights whose sums are exact, max_l through_t(l) == best[c] at every gene.
+ *   * Label sets.  set_mask[s], s < n_sets, has bit y set when label y is inside set s.  inside[g * n_sets + s] = the maximum of
+ *     through[g][l] over the labels inside, outside[g * n_sets + s] over the labels not inside -- -infinity when that side is
+ *     empty (a full set) or wholly disallowed.  A set's values do not depend on the other sets of the call.
+ *   * Span queries.  Query q is (span_contig[q], span_begin[q], span_end[q], span_mask[q]) as gecco_crf_span_probabilities takes
+ *     it: gene offsets from the contig's first gene, the end exclusive, bit y of the mask set when label y is in the set S.
+ *       span_best[q]   = the best score of a path of the contig whose labels on [begin, end) all lie in S: v_begin(j) = a_begin(j)
+ *                        for j in S and -infinity elsewhere, v_t(j) = max_i (v_{t-1}(i) + A(i, j)) + s_t(j) for j in S and
+ *                        -infinity elsewhere, and the result max_j (v_{end-1}(j) + b_{end-1}(j));
+ *       span_broken[q] = the best score of a path with at least one gene of the span outside S: the maximum of through[t][l] over
+ *                        the genes t of the span and the labels l not in S.
+ *     max(span_best, span_broken) is best[c] up to rounding.  A query's results depend on no other query.
+ *   * -infinity and NaN.  A value is -infinity exactly where no such path exists (a disallowed label, a span gene that allows no
+ *     label of S, a full S for span_broken), and never NaN.
+ *   * Outputs.  through [n_genes][L], inside and outside [n_genes][n_sets], span_best and span_broken [n_spans] are each optional
+ *     (NULL: not formed, and the others keep their bytes); best [n_contigs] is always written.  lognorm [n_contigs], optional, is
+ *     the bytes gecco_crf_marginals_full (or its _valued / _constrained sibling, by the arguments given) writes for the batch, so
+ *     that best[c] - lognorm[c] is the Viterbi path's log-probability.  The max walks need the state scores alone: the
+ *     sum-product pass runs only when lognorm is asked for, and costs about as much as the two walks again; without it a model
+ *     whose transitions lie outside that pass's range is taken.  (A 2-label model without values and masks has kernels of its own
+ *     for lognorm: asking for it there costs a second pass.)  A contig without genes gets best = 0 (gecco_crf_viterbi's score),
+ *     lognorm 0 and nothing else.  contig_ptr[0] > 0 works as in the other one-shots.  The two vectors are workspace of
+ *     16 * n_genes * L bytes; sizes are computed in size_t; a failed allocation is GECCO_CRF_ENOMEM.  Equal calls give equal bytes
+ *     (no atomics).
+ *   * Limits: num_labels <= 32, 0 <= n_sets <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL with a message that starts "max_marginals:": n_sets
+ *     outside 0 .. 32; a set mask of 0 or with a bit at or above num_labels ("max_marginals: set s: ..."); inside or outside given
+ *     without a set; span_best or span_broken given without spans; a negative n_spans; a NULL array of a non-empty list; and,
+ *     naming the query ("max_marginals: span q: ..."), the span checks of gecco_crf_span_probabilities.  The checks of the
+ *     *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_max_marginals(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                            const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                            const uint32_t *allowed /* NULL: no masks */, const uint32_t *set_mask /* [n_sets] */, int32_t n_sets,
+                            const int32_t *span_contig, const int32_t *span_begin, const int32_t *span_end,
+                            const uint32_t *span_mask, int32_t n_spans, double *through /* [n_genes][L] or NULL */,
+                            double *inside /* [n_genes][n_sets] or NULL */, double *outside /* [n_genes][n_sets] or NULL */,
+                            double *span_best /* [n_spans] or NULL */, double *span_broken /* [n_spans] or NULL */,
+                            double *best /* [n_contigs] */, double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- edge posteriors (ABI 2.19.0, additive; gecco_crf_version() stays 340) -----------------------------------------------------
  * The pairwise (edge) marginals xi_t(i, j) = P(y_{t-1} = i, y_t = j | x) on the whole-contig lattice of gecco_crf_viterbi and
