@@ -300,6 +300,12 @@ SIGNATURES = {
                        ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p,
                        _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)]
     ),
+    "gecco_crf_trainer_general_create_weighted": (
+        ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                       ctypes.POINTER(_vp), _c_i32p, _c_i32p, _c_i32p, _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                       _c_i32p, ctypes.POINTER(_vp)]
+    ),
     "gecco_crf_trainer_general_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_general_num_problems": (ctypes.c_int32, [_vp]),
     "gecco_crf_trainer_general_num_windows": (ctypes.c_int64, [_vp, ctypes.c_int32]),
@@ -321,6 +327,12 @@ SIGNATURES = {
         [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
          ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, _c_i32p, ctypes.POINTER(_vp),
          ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)],
+    ),
+    "gecco_crf_trainer_sequences_create_weighted": (
+        ctypes.c_int,
+        [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+         ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p,
+         _c_i32p, ctypes.POINTER(_vp), ctypes.POINTER(_vp), _c_i32p, ctypes.POINTER(_vp)],
     ),
     "gecco_crf_trainer_sequences_eval": (ctypes.c_int, [_vp, _c_u8p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp)]),
     "gecco_crf_trainer_sequences_num_problems": (ctypes.c_int32, [_vp]),
@@ -1841,10 +1853,34 @@ class _TrainerHandle:
             keep.append(a if a.size else np.zeros(1, dtype=np.uint32))
         return (_vp * len(keep))(*[None if a is None else a.ctypes.data for a in keep]), keep
 
-    def _create_general(self, problems, device, values, whole: bool, allowed=None):
+    @staticmethod
+    def _double_table(name, arrays, sizes):
+        """``weights=`` / ``costs=`` of the general and whole-sequence families: None, or per problem None or a float64
+        array of the size given (one weight per sequence; the cost matrix [L, L], row = gold).  Returns None when no
+        problem has any, else the table of pointers (NULL for a problem without) and the arrays it points to.  The
+        values themselves are checked by the library, which names the problem and the index."""
+        if arrays is None or all(a is None for a in arrays):
+            return None, None
+        if len(arrays) != len(sizes):
+            raise ValueError(f"{name} holds {len(arrays)} entries for {len(sizes)} problems")
+        keep = []
+        for a, n in zip(arrays, sizes):
+            if a is None:
+                keep.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+            if a.size != n:
+                raise ValueError(f"{name} of a problem hold {a.size} entries, the problem needs {n}")
+            keep.append(a if a.size else np.zeros(1, dtype=np.float64))
+        return (_vp * len(keep))(*[None if a is None else a.ctypes.data for a in keep]), keep
+
+    def _create_general(self, problems, device, values, whole: bool, allowed=None, weights=None, costs=None):
         """The constructor of the general (``whole=False``: every problem with a window and a step) and the whole-sequence
         family, on ``create`` or, when a problem has values, on ``create_valued``, or, when a problem has allowed-label
-        masks, on ``create_partial`` (a problem with masks may give None as its labels)."""
+        masks, on ``create_partial`` (a problem with masks may give None as its labels), or, when a problem has sequence
+        weights or label costs, on ``create_weighted``."""
+        wt, _keep_weights = self._double_table("weights", weights, [int(np.asarray(p[0]).size) - 1 for p in problems])
+        ct, _keep_costs = self._double_table("costs", costs, [int(np.asarray(p[6]).size) for p in problems])  # (trans_fid's L * L)
         at, _keep_allowed = self._allowed_table(allowed, [int(np.asarray(p[0])[-1]) for p in problems])
         if at is not None:  # (the labels of a problem with masks are not read: any array of the right kind will do)
             problems = [p if a is None or p[3] is not None else (*p[:3], np.zeros(1, dtype=np.int32), *p[4:])
@@ -1862,6 +1898,8 @@ class _TrainerHandle:
         allowed_table = ()
         if at is not None:  # (the partial create takes the values' table always: NULL when no problem has values)
             value_table, allowed_table, entry = (vt,), (at,), "create_partial"
+        if wt is not None or ct is not None:  # (the weighted create takes every table: NULL where no problem has one)
+            value_table, allowed_table, entry = (vt,), (at, wt, ct), "create_weighted"
         window_step = () if whole else (c["window"], c["step"])
         self._create(int(device), len(problems), t["seq_ptr"], c["n_seqs"], t["item_ptr"], t["attr_id"], *value_table,
                      t["labels"], *allowed_table, c["num_attrs"], c["num_labels"], *window_step, t["state_fid"],
@@ -2002,13 +2040,17 @@ class TrainerGeneral(_TrainerHandle):
     ``TrainerGeneral`` of problem k alone returns for ``ws[k]``.  ``values=``: per problem None or one float64 per
     attribute entry, parallel to its ``attr_id`` (``gecco_crf_trainer_general_create_valued``).  ``allowed=``: per problem
     None (a labelled problem) or one uint32 mask per item, bit y set when label y is allowed: the problem then minimises
-    log Z - log Z_A (``gecco_crf_trainer_general_create_partial``), and its ``labels`` entry is not read and may be None."""
+    log Z - log Z_A (``gecco_crf_trainer_general_create_partial``), and its ``labels`` entry is not read and may be None.
+    ``weights=``: per problem None or one float64 >= 0 per sequence, the weight of every window cut from it; ``costs=``:
+    per problem None or the label-cost matrix [L, L], row = gold, >= 0 with a zero diagonal
+    (``gecco_crf_trainer_general_create_weighted``): the problem then minimises the weighted cost-augmented objective.  A
+    problem with neither is the problem the other creates build, with their kernels and their bits."""
 
     _family = "gecco_crf_trainer_general"
     eval = _TrainerHandle._eval_problems
 
-    def __init__(self, problems, device: int = 0, values=None, allowed=None):
-        self._create_general(problems, device, values, whole=False, allowed=allowed)
+    def __init__(self, problems, device: int = 0, values=None, allowed=None, weights=None, costs=None):
+        self._create_general(problems, device, values, whole=False, allowed=allowed, weights=weights, costs=costs)
 
     def scratch_bytes(self, k: int = -1) -> int:
         """Scratch bytes of problem k; for k = -1 the sum over the problems, which is what is allocated."""
@@ -2023,13 +2065,14 @@ class TrainerSequences(_TrainerHandle):
     per problem; the label count of a problem is that of its ``state_fid`` [A, L].  ``eval(ws, active)`` evaluates the
     active problems; problem k's f and g are bitwise what a ``TrainerSequences`` of problem k alone returns for
     ``ws[k]``.  ``values=``: as ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_valued``); ``allowed=``: as
-    ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_partial``)."""
+    ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_partial``); ``weights=`` and ``costs=``: as
+    ``TrainerGeneral``'s (``gecco_crf_trainer_sequences_create_weighted``)."""
 
     _family = "gecco_crf_trainer_sequences"
     eval = _TrainerHandle._eval_problems
 
-    def __init__(self, problems, device: int = 0, values=None, allowed=None):
-        self._create_general(problems, device, values, whole=True, allowed=allowed)
+    def __init__(self, problems, device: int = 0, values=None, allowed=None, weights=None, costs=None):
+        self._create_general(problems, device, values, whole=True, allowed=allowed, weights=weights, costs=costs)
 
     def num_sequences(self, k: int) -> int:
         return int(self._c("num_sequences")(self._h, int(k)))

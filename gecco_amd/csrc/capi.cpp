@@ -2042,7 +2042,8 @@ int general_open(Handle **out, const GeneralFamily &family, bool valued, int32_t
                  const int32_t *const *attr_id, const double *const *attr_value, const int32_t *const *labels,
                  const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                  const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                 bool partial = false, const uint32_t *const *allowed = nullptr) {
+                 bool partial = false, const uint32_t *const *allowed = nullptr, const double *const *seq_weight = nullptr,
+                 const double *const *label_cost = nullptr) {
     if (!out) return GECCO_CRF_EINVAL;
     *out = nullptr;
     GECCO_GUARD_BEGIN
@@ -2053,10 +2054,11 @@ int general_open(Handle **out, const GeneralFamily &family, bool valued, int32_t
     DeviceScope guard;
     TrainerGeneral *t = nullptr;
     const int rc = family.whole ? trainer_sequences_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
-                                                           num_labels, state_fid, trans_fid, num_features, &t, attr_value, allowed)
+                                                           num_labels, state_fid, trans_fid, num_features, &t, attr_value, allowed,
+                                                           seq_weight, label_cost)
                                 : trainer_general_create(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs,
                                                          num_labels, window, step, state_fid, trans_fid, num_features, &t, attr_value,
-                                                         allowed);
+                                                         allowed, seq_weight, label_cost);
     *out = reinterpret_cast<Handle *>(t);
     return rc;
     GECCO_GUARD_END
@@ -2093,6 +2095,20 @@ GECCO_API int gecco_crf_trainer_general_create_partial(int32_t device, int32_t n
                                                        gecco_crf_trainer_general **out) {
     return general_open(out, kGeneralFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
                         num_attrs, num_labels, window, step, state_fid, trans_fid, num_features, true, allowed);
+}
+// (attr_value, allowed, seq_weight and label_cost may each be NULL as a whole: no problem has them)
+GECCO_API int gecco_crf_trainer_general_create_weighted(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                        const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                        const int32_t *const *attr_id, const double *const *attr_value,
+                                                        const int32_t *const *labels, const uint32_t *const *allowed,
+                                                        const double *const *seq_weight, const double *const *label_cost,
+                                                        const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window,
+                                                        const int32_t *step, const int32_t *const *state_fid,
+                                                        const int32_t *const *trans_fid, const int32_t *num_features,
+                                                        gecco_crf_trainer_general **out) {
+    return general_open(out, kGeneralFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
+                        num_attrs, num_labels, window, step, state_fid, trans_fid, num_features, false, allowed, seq_weight,
+                        label_cost);
 }
 GECCO_API int gecco_crf_trainer_general_eval(gecco_crf_trainer_general *t, const uint8_t *active, const double *const *w,
                                              double *f, double *const *g) {
@@ -2146,6 +2162,18 @@ GECCO_API int gecco_crf_trainer_sequences_create_partial(int32_t device, int32_t
                                                          const int32_t *num_features, gecco_crf_trainer_sequences **out) {
     return general_open(out, kSequencesFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
                         num_attrs, num_labels, nullptr, nullptr, state_fid, trans_fid, num_features, true, allowed);
+}
+GECCO_API int gecco_crf_trainer_sequences_create_weighted(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                          const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                          const int32_t *const *attr_id, const double *const *attr_value,
+                                                          const int32_t *const *labels, const uint32_t *const *allowed,
+                                                          const double *const *seq_weight, const double *const *label_cost,
+                                                          const int32_t *num_attrs, const int32_t *num_labels,
+                                                          const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                                          const int32_t *num_features, gecco_crf_trainer_sequences **out) {
+    return general_open(out, kSequencesFamily, false, device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, attr_value, labels,
+                        num_attrs, num_labels, nullptr, nullptr, state_fid, trans_fid, num_features, false, allowed, seq_weight,
+                        label_cost);
 }
 GECCO_API int gecco_crf_trainer_sequences_eval(gecco_crf_trainer_sequences *t, const uint8_t *active, const double *const *w,
                                                double *f, double *const *g) {

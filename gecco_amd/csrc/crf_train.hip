@@ -435,7 +435,7 @@ __global__ void __launch_bounds__(kTrainReduceBlocks) train_reduce_final(const S
 int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_ptr, const int32_t *attr_id,
                   const int32_t *labels, int32_t num_attrs, int32_t num_labels, int32_t window, int32_t step,
                   const int32_t *state_fid, const int32_t *trans_fid, int32_t num_features, int32_t max_labels,
-                  HostProblem *hp, bool whole_sequences, const double *attr_value) {
+                  HostProblem *hp, bool whole_sequences, const double *attr_value, const double *seq_weight) {
     if (!seq_ptr || n_seqs < 0 || !state_fid || !trans_fid) return fail("trainer: null argument");
     if (max_labels == 2 && num_labels != 2) {
         set_error("trainer: only 2-label models can be trained (GECCO's protein and domain modes are binary)");
@@ -505,6 +505,7 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
         for (int32_t s : order) {
             win_start.push_back(seq_ptr[s]);
             hp->win_len.push_back(seq_ptr[s + 1] - seq_ptr[s]);
+            if (seq_weight) hp->inst_weight.push_back(seq_weight[s]);  // (the weight follows its sequence into the slot order)
         }
         iw_cnt.assign(n_items, 1);
     }
@@ -513,6 +514,7 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
         const int64_t w0 = int64_t(win_start.size());
         const int32_t nw = (n - window) / step + 1;
         for (int32_t k = 0; k < nw; ++k) win_start.push_back(base + k * step);
+        if (seq_weight) hp->inst_weight.insert(hp->inst_weight.end(), size_t(nw), seq_weight[s]);
         for (int32_t p = 0; p < n; ++p) {
             const int32_t klo = p < window ? 0 : (p - window + step) / step;  // smallest k with k*step + W > p
             const int32_t khi = std::min(nw - 1, p / step);
@@ -527,16 +529,21 @@ int build_problem(const int32_t *seq_ptr, int32_t n_seqs, const int32_t *item_pt
 
     // empirical counts, exact (integers in doubles): state (a, y_i) once per window covering item i, transitions per window
     hp->empirical.assign(size_t(num_features), 0.0);
-    for (int32_t i = 0; i < n_items; ++i)
+    for (int32_t i = 0, s = 0; i < n_items; ++i) {
+        while (seq_weight && i >= seq_ptr[s + 1]) ++s;  // (the sequence of item i: only a weighted problem asks)
         for (int32_t k = item_ptr[i]; k < item_ptr[i + 1]; ++k) {
             const int32_t fid = hp->state_fid[size_t(attr_id[k]) * L + labels[i]];
-            // (with values: value x coverage, in this one order; a value of 1 adds the integer it always added)
-            if (fid >= 0) hp->empirical[fid] += attr_value ? attr_value[k] * iw_cnt[i] : iw_cnt[i];
+            if (fid < 0) continue;
+            // (with values: value x coverage, in this one order; a value of 1 adds the integer it always added.  With sequence
+            // weights: that term times the weight of the item's sequence)
+            const double term = attr_value ? attr_value[k] * iw_cnt[i] : iw_cnt[i];
+            hp->empirical[fid] += seq_weight ? term * seq_weight[s] : term;
         }
+    }
     for (size_t q = 0; q < win_start.size(); ++q)
         for (int32_t i0 = win_start[q], j = 1; j < (whole_sequences ? hp->win_len[q] : window); ++j) {
             const int32_t fid = hp->trans_fid[labels[i0 + j - 1] * L + labels[i0 + j]];
-            if (fid >= 0) hp->empirical[fid] += 1.0;
+            if (fid >= 0) hp->empirical[fid] += seq_weight ? hp->inst_weight[q] : 1.0;
         }
 
     // attribute -> items transpose (items ascending within every attribute)

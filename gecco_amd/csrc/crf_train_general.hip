@@ -26,6 +26,8 @@
 //   gen_partial<G, kWhole>   partially labelled problems (gecco_crf_trainer_{general, sequences}_create_partial; DESIGN.md
 //                            §4.9e), which carry a mask of allowed labels per item and minimise log Z - log Z_A: the free and
 //                            the restricted recursion in the same slot; it hands on their difference.
+// Each has a third parameter, kWeighted (the *_create_weighted problems with sequence weights or a label-cost matrix; DESIGN.md
+// §4.9q): the weighted instantiation hands on its sums already weighted.
 // Every other kernel is shared by all of them as it is.
 #include <hip/hip_runtime.h>
 
@@ -170,8 +172,18 @@ __device__ __forceinline__ void write_block(double (&xacc)[G], double facc, int 
 // side by side have neighbouring lengths.
 // The windows index their scores and marginals with int, as their kernel always has (t * L + i < W * L <= 32 * window, and a
 // 64-bit index costs the two-label group a wave per SIMD); a sequence has no such bound and indexes with int64_t.
-template <int G, bool kWhole>
-__global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
+//
+// kWeighted (the *_create_weighted problems that carry sequence weights or a label-cost matrix): the instance's
+// term of the objective is omega * (log Z_C - score(gold)), omega = inst_weight[w] the weight of the sequence it was cut from and
+// Z_C the partition function of the lattice whose state scores are s_t[i] + C[gold_t][i].  C[gold][.] lies in LDS beside the
+// transitions, [G][G] with zeros at or above L, and is added wherever the recursion reads a state score: the first item, the
+// forward step and the backward step's q.  Its diagonal is exactly 0, so the gold path's score needs nothing.  omega multiplies
+// what the instance hands on and nothing it keeps: its term of f, every node marginal at the store on the way back (never the
+// log alpha the slot holds on the way forward) and, through the marginal m, the pairwise expectations.  cost == nullptr: weights
+// only, a table of zeros.  inst_weight holds one weight per instance in the order of win_start, so a sequence's weight follows it
+// through the slot order.  The unweighted instantiation reads neither argument and is the kernel as it was.
+template <int G, bool kWhole, bool kWeighted>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P, const double *inst_weight, const double *cost) {
     using Idx = std::conditional_t<kWhole, int64_t, int>;
     constexpr int kSlots = kTrainGenThreads / G;
     constexpr int kPerBlock = kWhole ? kSlots : kTrainGenWindowsPerBlock;
@@ -179,10 +191,13 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
     __shared__ double tTt[G * G];            // [j][i] = T[i][j]
     __shared__ double xi_sh[G * G];          // [j][i]
     __shared__ double f_sh;
+    __shared__ double tC[kWeighted ? G * G : 1];  // [y][i] = C[y][i]: what predicting i costs at an item whose gold label is y
     const int tid = threadIdx.x;
     const int L = P.L;
     const int i = tid % G, slot = tid / G;
     const bool lab = i < L;
+    if constexpr (kWeighted)  // (load_transitions ends with the barrier that covers these stores too)
+        for (int e = tid; e < G * G; e += kTrainGenThreads) tC[e] = (cost && e / G < L && e % G < L) ? cost[(e / G) * L + e % G] : 0.0;
     load_transitions<G>(P.trans, L, tT, tTt);
 
     double xacc[G];
@@ -200,8 +215,11 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
         const int32_t *label = P.label + i0;
         double *mw = kWhole ? P.item_marg + i0 * L : P.marg + w * n * L;
 
+        double om = 1.0;
+        if constexpr (kWeighted) om = inst_weight[w];
         double la = lab ? sc[i] : 0.0;
         int yprev = label[0];
+        if constexpr (kWeighted) la += tC[yprev * G + i];
         double gold = (lab && yprev == i) ? la : 0.0;  // this label's share of the gold path's score
         if (lab) mw[i] = la;
         for (int t = 1; t < n; ++t) {
@@ -216,7 +234,8 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
 #pragma unroll
             for (int k = 0; k < G; ++k)
                 if (k < L) sum += exp(v[k] - mx);
-            const double s = lab ? sc[static_cast<Idx>(t) * L + i] : 0.0;
+            const double s = kWeighted ? (lab ? sc[static_cast<Idx>(t) * L + i] : 0.0) + tC[label[t] * G + i]
+                                       : (lab ? sc[static_cast<Idx>(t) * L + i] : 0.0);
             la = mx + log(sum) + s;
             const int y = label[t];
             if (lab && y == i) gold += s + tT[yprev * G + i];
@@ -236,12 +255,19 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
         for (int k = 0; k < G; ++k)
             if (k < L) sum += exp(v[k] - mx);
         const double logz = mx + log(sum);
-        if (i == 0) facc += logz - gold_all;
+        if constexpr (kWeighted) {
+            if (i == 0) facc += om * (logz - gold_all);
+            if (lab) mw[static_cast<Idx>(n - 1) * L + i] = om * exp(la - logz);
+        } else {
+            if (i == 0) facc += logz - gold_all;
 
-        if (lab) mw[static_cast<Idx>(n - 1) * L + i] = exp(la - logz);
+            if (lab) mw[static_cast<Idx>(n - 1) * L + i] = exp(la - logz);
+        }
         double lb = 0.0;
         for (int t = n - 1; t >= 1; --t) {
-            const double q = (lab ? sc[static_cast<Idx>(t) * L + i] : 0.0) + lb;  // log of exp(s_t[i]) beta_t[i]
+            // log of exp(s_t[i]) beta_t[i]
+            const double q = kWeighted ? (lab ? sc[static_cast<Idx>(t) * L + i] : 0.0) + tC[label[t] * G + i] + lb
+                                       : (lab ? sc[static_cast<Idx>(t) * L + i] : 0.0) + lb;
             const double lap = lab ? mw[static_cast<Idx>(t - 1) * L + i] : 0.0;  // log alpha_{t-1}[i], stored by this lane
             mx = -INFINITY;
 #pragma unroll
@@ -258,7 +284,7 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
                     sum += v[k];
                 }
             lb = mx + log(sum);
-            const double m = exp(lap + lb - logz);
+            const double m = kWeighted ? om * exp(lap + lb - logz) : exp(lap + lb - logz);
             const double c = m / sum;
 #pragma unroll
             for (int k = 0; k < G; ++k)
@@ -283,8 +309,11 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_labelled(GenProb P) {
 // term: the excluded terms are exp(-inf - finite) = 0 exactly and no -inf - (-inf) can form, however much of the free mass
 // the excluded labels carry.  The restricted log alpha has its own storage, la_a, of the node marginals' shape
 // ([n_win][W][L], whole sequences [n_items][L]).  Both families index with int64_t here.
-template <int G, bool kWhole>
-__global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const uint32_t *allowed, double *la_a) {
+// kWeighted: the instance's term is omega * (log Z - log Z_A), omega = inst_weight[w] as in gen_labelled: it multiplies the
+// term of f, the difference of the node marginals at its store and both passes' marginals m and mr, and so the pairwise terms.
+// There are no costs here: an item with a set of allowed labels has no single gold label to index C with.
+template <int G, bool kWhole, bool kWeighted>
+__global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const uint32_t *allowed, double *la_a, const double *inst_weight) {
     constexpr int kSlots = kTrainGenThreads / G;  // instances side by side in a workgroup
     constexpr int kPerBlock = kWhole ? kSlots : kTrainGenWindowsPerBlock;
     __shared__ double tT[G * G];             // [i][j] = T[i][j]
@@ -314,6 +343,8 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
         double *mw = (kWhole ? P.item_marg : P.marg) + m0;  // free log alpha, then the difference of the marginals
         double *ma = la_a + m0;                              // restricted log alpha
 
+        double om = 1.0;
+        if constexpr (kWeighted) om = inst_weight[w];
         double la = lab ? sc[i] : 0.0;
         double lr = (lab && ((al[0] >> i) & 1u)) ? la : -INFINITY;
         if (lab) mw[i] = la, ma[i] = lr;
@@ -334,9 +365,14 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
         for (int k = 0; k < G; ++k)
             if (k < L) sum += exp(__shfl(la, k, G) - mx), sumr += exp(__shfl(lr, k, G) - mxr);
         const double logz = mx + log(sum), logzr = mxr + log(sumr);
-        if (i == 0) facc += logz - logzr;
+        if constexpr (kWeighted) {
+            if (i == 0) facc += om * (logz - logzr);
+            if (lab) mw[static_cast<int64_t>(n - 1) * L + i] = om * (exp(la - logz) - exp(lr - logzr));
+        } else {
+            if (i == 0) facc += logz - logzr;
 
-        if (lab) mw[static_cast<int64_t>(n - 1) * L + i] = exp(la - logz) - exp(lr - logzr);
+            if (lab) mw[static_cast<int64_t>(n - 1) * L + i] = exp(la - logz) - exp(lr - logzr);
+        }
         double lb = 0.0, lbr = 0.0;
         for (int t = n - 1; t >= 1; --t) {
             const double s = lab ? sc[static_cast<int64_t>(t) * L + i] : 0.0;
@@ -359,7 +395,7 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
                     sum += v[k];
                 }
             lb = mx + log(sum);
-            const double m = exp(lap + lb - logz);
+            const double m = kWeighted ? om * exp(lap + lb - logz) : exp(lap + lb - logz);
             const double c = m / sum;
 #pragma unroll
             for (int k = 0; k < G; ++k)
@@ -379,7 +415,8 @@ __global__ void __launch_bounds__(kTrainGenThreads) gen_partial(GenProb P, const
                     sum += v[k];
                 }
             lbr = mx + log(sum);
-            const double mr = exp(lapr + lbr - logzr);  // (a label excluded at t - 1: exp(-inf) = 0)
+            // (a label excluded at t - 1: exp(-inf) = 0)
+            const double mr = kWeighted ? om * exp(lapr + lbr - logzr) : exp(lapr + lbr - logzr);
             const double cr = mr / sum;
 #pragma unroll
             for (int k = 0; k < G; ++k)
@@ -489,6 +526,9 @@ struct TrainerGeneral {
         // a partially labelled problem: its slice of d_allowed (one mask per item), and the doubles of its second log alpha
         // array, which lies behind the slabs.  allow0 < 0: a labelled problem
         int64_t allow0 = -1, la_a = 0;
+        // a weighted problem (sequence weights or label costs): one weight per instance at wt0 of its scratch, in the order of
+        // win_start, and the cost matrix [L][L] at cost0 (cost0 < 0: weights only), both written once by create.  wt0 < 0: none
+        int64_t wt0 = -1, cost0 = -1;
         std::vector<int32_t> state_fid, trans_fid;
         std::vector<double> empirical;
     };
@@ -509,11 +549,14 @@ namespace {
 // Both families' create: window == nullptr is the whole-sequence family.  attr_value: null, or per problem the values of its
 // attribute entries (entry k null: problem k has none, and runs the unvalued kernels).  allowed: null, or per problem one mask
 // per item (entry k null: problem k is labelled, and runs the labelled kernels); labels[k] of a problem with masks is not read.
+// seq_weight / label_cost: null, or per problem one weight per sequence / the cost matrix [L][L], row = gold (entry k null:
+// weights of 1 / no costs); a problem with either runs the weighted kernels, a problem with neither is built as it always was.
 int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                          const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                          const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                          const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                         const double *const *attr_value, const uint32_t *const *allowed, TrainerGeneral **out) {
+                         const double *const *attr_value, const uint32_t *const *allowed, const double *const *seq_weight,
+                         const double *const *label_cost, TrainerGeneral **out) {
     auto t = std::make_unique<TrainerGeneral>();
     const bool whole = t->whole = window == nullptr;
     const std::string family = whole ? "trainer sequences: problem " : "trainer general: problem ";
@@ -522,17 +565,36 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
     std::vector<double> attr_value_c;
     std::vector<uint32_t> allowed_c;
     std::vector<std::vector<double>> transposed(static_cast<size_t>(n_problems));  // (attr_item_value of the valued problems)
+    std::vector<std::vector<double>> weighting(static_cast<size_t>(n_problems));   // (instance weights, then costs, of the weighted)
     int64_t in_total = 0, out_total = 0, scratch_total = 0;
     for (int32_t k = 0; k < n_problems; ++k) {
         HostProblem hp;
         const uint32_t *masks = allowed ? allowed[k] : nullptr;
+        const double *omega = seq_weight ? seq_weight[k] : nullptr, *cost = label_cost ? label_cost[k] : nullptr;
+        if (omega && n_seqs[k] > 0)
+            for (int32_t s = 0; s < n_seqs[k]; ++s)
+                if (!(omega[s] >= 0.0) || std::isinf(omega[s]))
+                    return fail(family + std::to_string(k) + ": weight of sequence " + std::to_string(s) +
+                                " is negative or not finite (" + std::to_string(omega[s]) + ")");
+        if (cost && num_labels[k] >= 2 && num_labels[k] <= kTrainGenMaxL) {
+            const int32_t L = num_labels[k];
+            if (masks)
+                return fail(family + std::to_string(k) + ": label costs on a problem with allowed-label masks (no gold label to cost against)");
+            for (int32_t e = 0; e < L * L; ++e) {
+                const std::string at = "cost [" + std::to_string(e / L) + "][" + std::to_string(e % L) + "]";
+                if (!(cost[e] >= 0.0) || std::isinf(cost[e]))
+                    return fail(family + std::to_string(k) + ": " + at + " is negative or not finite (" + std::to_string(cost[e]) + ")");
+                if (e / L == e % L && cost[e] != 0.0)
+                    return fail(family + std::to_string(k) + ": " + at + " is on the diagonal and not 0 (" + std::to_string(cost[e]) + ")");
+            }
+        }
         // (a problem with masks has no gold path: build_problem gets label 0 on every item, and the counts it takes from them
         // are dropped below)
         std::vector<int32_t> no_labels;
         if (masks && seq_ptr[k] && n_seqs[k] >= 0) no_labels.assign(size_t(std::max(seq_ptr[k][n_seqs[k]], 1)), 0);
         int rc = build_problem(seq_ptr[k], n_seqs[k], item_ptr[k], attr_id[k], masks ? no_labels.data() : labels[k], num_attrs[k], num_labels[k],
                                whole ? 0 : window[k], whole ? 0 : step[k], state_fid[k], trans_fid[k], num_features[k],
-                               kTrainGenMaxL, &hp, whole, attr_value ? attr_value[k] : nullptr);
+                               kTrainGenMaxL, &hp, whole, attr_value ? attr_value[k] : nullptr, omega);
         if (rc) {
             set_error(family + std::to_string(k) + ": " + last_error());
             return rc;
@@ -565,13 +627,25 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
         p.in0 = in_total, p.out0 = out_total, p.sc0 = scratch_total;
         // scratch: item scores and item marginals [n_items][L], node marginals [n_win][W][L] (none for whole sequences:
         // W = 0), blocks and slabs of (f, xi); with masks, a second log alpha array; with values, one double per attribute entry
-        // (the transposed values)
+        // (the transposed values); a weighted problem, one double per instance and, with costs, L * L more
         p.scratch = 2 * int64_t(p.n_items) * p.L + hp.n_win * p.W * p.L + (nb + kTrainGenReduceSlabs) * cols;
         if (masks) {  // the restricted pass's log alpha, of the node marginals' shape
             p.allow0 = int64_t(allowed_c.size());
             p.la_a = whole ? int64_t(p.n_items) * p.L : hp.n_win * p.W * p.L;
             p.scratch += p.la_a;
             allowed_c.insert(allowed_c.end(), masks, masks + hp.n_items);
+        }
+        if (omega || cost) {  // a weighted problem: the instance weights (1 without sequence weights), then the costs
+            p.wt0 = p.scratch;
+            p.scratch += hp.n_win;
+            std::vector<double> &up = weighting[size_t(k)];
+            up = std::move(hp.inst_weight);
+            if (!omega) up.assign(size_t(hp.n_win), 1.0);
+            if (cost) {
+                p.cost0 = p.scratch;
+                p.scratch += int64_t(p.L) * p.L;
+                up.insert(up.end(), cost, cost + int64_t(p.L) * p.L);
+            }
         }
         if (attr_value && attr_value[k]) {  // a problem with values: the transposed values behind everything else
             p.val0 = int64_t(attr_value_c.size());
@@ -624,6 +698,14 @@ int trainer_general_open(int32_t device, int32_t n_problems, const int32_t *cons
     if ((rc = t->d_allowed.upload(allowed_c, "trainer upload"))) return rc;
     for (int32_t k = 0; k < n_problems; ++k) {
         const TrainerGeneral::Prob &p = t->probs[size_t(k)];
+        if (p.wt0 < 0 || weighting[size_t(k)].empty()) continue;
+        if ((rc = check_hip(hipMemcpy(t->d_scratch.get() + p.sc0 + p.wt0, weighting[size_t(k)].data(),
+                                      weighting[size_t(k)].size() * sizeof(double), hipMemcpyHostToDevice),
+                            "trainer upload")))
+            return rc;
+    }
+    for (int32_t k = 0; k < n_problems; ++k) {
+        const TrainerGeneral::Prob &p = t->probs[size_t(k)];
         if (p.val0 < 0 || p.nnz == 0) continue;
         if ((rc = check_hip(hipMemcpy(t->d_scratch.get() + p.sc0 + p.scratch - p.nnz, transposed[size_t(k)].data(),
                                       size_t(p.nnz) * sizeof(double), hipMemcpyHostToDevice),
@@ -640,19 +722,21 @@ int trainer_general_create(int32_t device, int32_t n_problems, const int32_t *co
                            const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                            const int32_t *num_attrs, const int32_t *num_labels, const int32_t *window, const int32_t *step,
                            const int32_t *const *state_fid, const int32_t *const *trans_fid, const int32_t *num_features,
-                           TrainerGeneral **out, const double *const *attr_value, const uint32_t *const *allowed) {
+                           TrainerGeneral **out, const double *const *attr_value, const uint32_t *const *allowed,
+                           const double *const *seq_weight, const double *const *label_cost) {
     if (!window || !step) return fail("trainer general: null argument");
     return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, window,
-                                step, state_fid, trans_fid, num_features, attr_value, allowed, out);
+                                step, state_fid, trans_fid, num_features, attr_value, allowed, seq_weight, label_cost, out);
 }
 
 int trainer_sequences_create(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr, const int32_t *n_seqs,
                              const int32_t *const *item_ptr, const int32_t *const *attr_id, const int32_t *const *labels,
                              const int32_t *num_attrs, const int32_t *num_labels, const int32_t *const *state_fid,
                              const int32_t *const *trans_fid, const int32_t *num_features, TrainerGeneral **out,
-                             const double *const *attr_value, const uint32_t *const *allowed) {
+                             const double *const *attr_value, const uint32_t *const *allowed,
+                             const double *const *seq_weight, const double *const *label_cost) {
     return trainer_general_open(device, n_problems, seq_ptr, n_seqs, item_ptr, attr_id, labels, num_attrs, num_labels, nullptr,
-                                nullptr, state_fid, trans_fid, num_features, attr_value, allowed, out);
+                                nullptr, state_fid, trans_fid, num_features, attr_value, allowed, seq_weight, label_cost, out);
 }
 
 int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double *const *w, double *f, double *const *g) {
@@ -724,15 +808,22 @@ int trainer_general_eval(TrainerGeneral *t, const uint8_t *active, const double 
             const bool masked = p.allow0 >= 0;
             const uint32_t *al = masked ? t->d_allowed.get() + p.allow0 : nullptr;
             double *la_a = masked ? a.slab + kTrainGenReduceSlabs * cols : nullptr;
+            // (a weighted problem: its instance weights and, with costs, its cost matrix, where create put them)
+            const double *inst_weight = p.wt0 >= 0 ? t->d_scratch.get() + p.sc0 + p.wt0 : nullptr;
+            const double *cost = p.cost0 >= 0 ? t->d_scratch.get() + p.sc0 + p.cost0 : nullptr;
             const unsigned nb = unsigned(p.n_blocks);
             with_group(G, [&](auto g) {
                 constexpr int kG = decltype(g)::value;
                 auto launch = [&](auto whole) {
                     constexpr bool kWhole = decltype(whole)::value;
-                    if (masked)
-                        gen_partial<kG, kWhole><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a);
+                    if (masked && inst_weight)
+                        gen_partial<kG, kWhole, true><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a, inst_weight);
+                    else if (masked)
+                        gen_partial<kG, kWhole, false><<<nb, kTrainGenThreads, 0, st>>>(a, al, la_a, nullptr);
+                    else if (inst_weight)
+                        gen_labelled<kG, kWhole, true><<<nb, kTrainGenThreads, 0, st>>>(a, inst_weight, cost);
                     else
-                        gen_labelled<kG, kWhole><<<nb, kTrainGenThreads, 0, st>>>(a);
+                        gen_labelled<kG, kWhole, false><<<nb, kTrainGenThreads, 0, st>>>(a, nullptr, nullptr);
                 };
                 if (t->whole)
                     launch(std::true_type{});

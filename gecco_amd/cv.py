@@ -281,6 +281,13 @@ def _fold_truth(seqs: List[List[Any]], test_idx: Any) -> Tuple[List[Any], Dict[T
     return truth_genes, truth
 
 
+def cost_options(miss_cost: float, false_cost: float) -> Dict[str, Any]:
+    """The ``label_costs`` option of the binary models from the command lines' ``--miss-cost`` (gold '1', predicted '0') and
+    ``--false-cost`` (the reverse): no option at all when both are 0."""
+    costs = {pair: float(c) for pair, c in ((("1", "0"), miss_cost), (("0", "1"), false_cost)) if c}
+    return {"label_costs": costs} if costs else {}
+
+
 def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle: bool = True,
                    select: Optional[float] = None, correction_method: Optional[str] = None) -> CrossValidation:
     """Cross-validate the unfitted ``ClusterCRF`` template ``crf`` (its feature type, window, trainer options, ``devices``
@@ -321,14 +328,20 @@ def cross_validate(crf: Any, genes: Iterable[Any], splits: SplitSpec, *, shuffle
 
 # ---------------------------------------------------------------------------------------------- hyperparameter search
 GRID_KEYS = ("c1", "c2", "window_size")
+#: an axis a grid may have: the cost of a missed cluster gene, ``label_costs[('1', '0')]`` of the point's fits
+COST_KEY = "miss_cost"
 METRICS = ("aupr", "auroc")
 
 
 def grid_points(grid: Dict[str, Sequence[Any]], crf: Any = None) -> List[Dict[str, Any]]:
     """The points of a ``{"c1": [...], "c2": [...], "window_size": [...]}`` grid, in grid order: c1 outermost, then c2,
     then the window size.  A key left out takes the template ``crf``'s value.  ``ValueError`` for an unknown key, an
-    empty list, a regularisation strength that is negative or not finite, or a window size outside 1 .. 32."""
-    unknown = sorted(set(grid) - set(GRID_KEYS))
+    empty list, a regularisation strength that is negative or not finite, or a window size outside 1 .. 32.
+
+    A grid may also have a ``"miss_cost"`` axis, in the form of the ``c1`` / ``c2`` axes: the points then carry the key
+    (innermost), and a point's fits take ``label_costs[('1', '0')]`` from it (0: no cost).  Without it the points are
+    what they always were."""
+    unknown = sorted(set(grid) - set(GRID_KEYS) - {COST_KEY})
     if unknown:
         raise ValueError(f"grid: unknown parameter(s) {', '.join(map(repr, unknown))} (expected {', '.join(GRID_KEYS)})")
     values: Dict[str, List[Any]] = {}
@@ -353,8 +366,17 @@ def grid_points(grid: Dict[str, Sequence[Any]], crf: Any = None) -> List[Dict[st
                     raise ValueError(f"grid: {key} {v!r} is not a finite value >= 0")
                 out.append(v)
         values[key] = out
-    return [{"c1": c1, "c2": c2, "window_size": w}
-            for c1, c2, w in itertools.product(values["c1"], values["c2"], values["window_size"])]
+    points = [{"c1": c1, "c2": c2, "window_size": w}
+              for c1, c2, w in itertools.product(values["c1"], values["c2"], values["window_size"])]
+    if COST_KEY not in grid:
+        return points
+    costs = list(grid[COST_KEY])
+    if not costs:
+        raise ValueError(f"grid: empty list of values for {COST_KEY!r}")
+    for v in costs:
+        if isinstance(v, bool) or not math.isfinite(float(v)) or float(v) < 0:
+            raise ValueError(f"grid: {COST_KEY} {v!r} is not a finite value >= 0")
+    return [{**pt, COST_KEY: v} for pt in points for v in costs]
 
 
 def rank_points(auroc: Sequence[float], aupr: Sequence[float], metric: str = "aupr") -> List[int]:
@@ -419,11 +441,12 @@ class GridSearch:
     def table(self) -> bytes:
         """One row per (point, fold), points in grid order: ``point`` (1-based), ``c1``, ``c2``, ``window_size``,
         ``fold``, ``n_train`` / ``n_test`` (sequences), ``auroc``, ``aupr``."""
-        rows = ["point\tc1\tc2\twindow_size\tfold\tn_train\tn_test\tauroc\taupr"]
+        cost = any(COST_KEY in pt for pt in self.points)  # (a grid with the axis: one more column, after window_size)
+        rows = ["point\tc1\tc2\twindow_size\t" + (COST_KEY + "\t" if cost else "") + "fold\tn_train\tn_test\tauroc\taupr"]
         for p, (pt, fs) in enumerate(zip(self.points, self.folds)):
             for f in fs:
                 rows.append("\t".join([str(p + 1), _fmt_float(pt["c1"]), _fmt_float(pt["c2"]), str(pt["window_size"]),
-                                       str(f.index), str(len(f.train)), str(len(f.test)), _fmt_float(f.auroc),
+                                       *([_fmt_float(pt[COST_KEY])] if cost else []), str(f.index), str(len(f.train)), str(len(f.test)), _fmt_float(f.auroc),
                                        _fmt_float(f.aupr)]))
         return ("\n".join(rows) + "\n").encode("utf-8")
 
@@ -431,9 +454,11 @@ class GridSearch:
         """One row per point, in grid order: ``point``, ``c1``, ``c2``, ``window_size``, ``mean_auroc``, ``mean_aupr``,
         the pooled ``auroc`` / ``aupr``, and ``rank`` (1 = best)."""
         rank = {p: r + 1 for r, p in enumerate(self.ranking)}
-        rows = ["point\tc1\tc2\twindow_size\tmean_auroc\tmean_aupr\tauroc\taupr\trank"]
+        cost = any(COST_KEY in pt for pt in self.points)
+        rows = ["point\tc1\tc2\twindow_size\t" + (COST_KEY + "\t" if cost else "") + "mean_auroc\tmean_aupr\tauroc\taupr\trank"]
         for p, pt in enumerate(self.points):
             rows.append("\t".join([str(p + 1), _fmt_float(pt["c1"]), _fmt_float(pt["c2"]), str(pt["window_size"]),
+                                   *([_fmt_float(pt[COST_KEY])] if cost else []),
                                    _fmt_float(self.mean_auroc[p]), _fmt_float(self.mean_aupr[p]),
                                    _fmt_float(self.auroc[p]), _fmt_float(self.aupr[p]), str(rank[p])]))
         return ("\n".join(rows) + "\n").encode("utf-8")
@@ -524,6 +549,8 @@ def grid_search(crf: Any, genes: Iterable[Any], splits: SplitSpec, grid: Dict[st
         # (the template's options with the point's values, as the point's own template would hold them)
         options = dict(template_options)
         options.update({k: pt[k] for k in ("c1", "c2") if k in grid or k in options})
+        if COST_KEY in pt:  # (the template's costs with the point's cost of a miss; a point without one keeps TrainerGrid)
+            options["label_costs"] = {**(options.get("label_costs") or {}), ("1", "0"): pt[COST_KEY]}
         return _clone(crf, pt["window_size"], options)
 
     windows = list(dict.fromkeys(pt["window_size"] for pt in points))
@@ -639,6 +666,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--window-step", type=int, default=1)
     ap.add_argument("--c1", type=float, default=0.15)
     ap.add_argument("--c2", type=float, default=0.15)
+    ap.add_argument("--miss-cost", type=float, default=0.0, help="training cost of a missed cluster gene (every fold)")
+    ap.add_argument("--false-cost", type=float, default=0.0, help="training cost of a false cluster gene (every fold)")
     ap.add_argument("--select", type=float, default=None, help="fraction of domains kept by Fisher selection")
     ap.add_argument("--correction", default=None, help="multiple-testing correction of the selection p-values")
     ap.add_argument("--loto", action="store_true", help="leave-one-type-out instead of K-fold cross-validation")
@@ -655,7 +684,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     genes = label_genes(genes, clusters)
 
     crf = ClusterCRF(args.feature_type, algorithm="lbfgs", window_size=args.window_size, window_step=args.window_step,
-                     c1=args.c1, c2=args.c2)
+                     c1=args.c1, c2=args.c2, **cost_options(args.miss_cost, args.false_cost))
     if args.loto:
         def splits(seqs):
             return list(LeaveOneGroupOut().split(seqs, groups=loto_groups(seqs, clusters)))

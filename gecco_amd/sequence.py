@@ -40,7 +40,8 @@ def _items(xseq) -> Tuple[List[List[str]], Optional[List[List[float]]]]:
 class SequenceCRF:
     """``SequenceCRF(window_size=5, window_step=1, device=0, **options)``: ``options`` are the trainer's
     (``train.trainer_params``: ``c1``, ``c2``, ``min_freq``, ``all_possible_states``, ``all_possible_transitions`` and the
-    libLBFGS parameters).  ``window_size=None``: the training instances are the whole sequences, of any length from one
+    libLBFGS parameters, and ``label_costs``, a mapping ``{(gold, predicted): cost}`` that makes the fit cost-sensitive;
+    costs exist in training only).  ``window_size=None``: the training instances are the whole sequences, of any length from one
     item up; ``window_step`` is then ignored and stored as 1, and the model has no windowed predictions.
 
     After ``fit(X, y)``: ``classes_`` (labels in order of first appearance), ``attributes_`` (the attributes the model
@@ -63,12 +64,13 @@ class SequenceCRF:
         self._model = None
 
     # ---- training
-    def fit(self, X: Sequence[Iterable[Iterable[str]]], y: Sequence[Sequence[str]]) -> "SequenceCRF":
+    def fit(self, X: Sequence[Iterable[Iterable[str]]], y: Sequence[Sequence[str]], sample_weight=None) -> "SequenceCRF":
         """``X``: sequences of items; an item is an iterable of attribute names, or a dict / a list of ``(name, value)``
         pairs (``train.item_attributes``), as in every prediction method.  An entry of ``y`` is a label, a ``set`` /
         ``frozenset`` / ``list`` / ``tuple`` of labels (the labels allowed on that item) or None (every label): with any
         entry that is not one label the fit maximises the marginal likelihood of the allowed paths
-        (``train.build_training_set``)."""
+        (``train.build_training_set``), and ``label_costs`` are then a ``ValueError``.  ``sample_weight``: None, or one finite
+        weight >= 0 per sequence, which every training instance cut from that sequence carries in the objective."""
         seqs = []
         for xseq in X:  # (a sequence with values goes to the training set as (name, value) pairs, one without as names)
             names, values = _items(xseq)
@@ -86,7 +88,8 @@ class SequenceCRF:
         step = None if self.window_size is None else self.window_step
         ts = train.build_training_set(seqs, labs, self.window_size, step, min_freq=p["min_freq"],
                                       all_possible_states=p["all_possible_states"],
-                                      all_possible_transitions=p["all_possible_transitions"], max_labels=train.MAX_LABELS)
+                                      all_possible_transitions=p["all_possible_transitions"], max_labels=train.MAX_LABELS,
+                                      sample_weight=sample_weight)
         self.training_result_ = train.fit_training_set(ts, p, device=self.device)
         self._set_blob(train.model_blob(ts, self.training_result_.x))
         return self

@@ -41,9 +41,14 @@ _SILENT_OPTIONS = ("verbose",)
 
 def trainer_params(options: Dict[str, object]) -> Dict[str, object]:
     """Check ``sklearn_crfsuite.CRF``-style options (what ``ClusterCRF(**kwargs)`` stores) and return the complete set:
-    ``c1``, ``c2``, the feature-generation options and the five libLBFGS parameters, defaults filled in."""
+    ``c1``, ``c2``, the feature-generation options and the five libLBFGS parameters, defaults filled in.
+
+    ``label_costs`` (not a CRFsuite option): a mapping ``{(gold, predicted): cost}`` of label names, the softmax-margin
+    cost matrix of the training objective (``fit_training_set``); missing pairs cost 0.  A cost that is negative, NaN or
+    infinite, or a non-zero cost on the diagonal, is a ``ValueError`` here; a label the training set does not have is one
+    at fit time.  Returned as a dict of the non-zero entries, or None (the default, and what an empty mapping gives)."""
     out: Dict[str, object] = {"c1": 0.0, "c2": 1.0, "min_freq": 0.0, "all_possible_states": False,
-                              "all_possible_transitions": False, **TRAINER_DEFAULTS}
+                              "all_possible_transitions": False, "label_costs": None, **TRAINER_DEFAULTS}
     for key, value in options.items():
         if key == "algorithm":
             if value != "lbfgs":
@@ -61,10 +66,31 @@ def trainer_params(options: Dict[str, object]) -> Dict[str, object]:
                 raise ValueError(f"invalid value for {key}: {value}")
         elif key in ("all_possible_states", "all_possible_transitions"):
             value = bool(value)
+        elif key == "label_costs":
+            value = _checked_label_costs(value)
         else:
             raise ValueError(f"unsupported trainer option {key!r}")
         out[key] = value
     return out
+
+
+def _checked_label_costs(costs) -> Optional[Dict[Tuple[object, object], float]]:
+    """``label_costs`` as ``trainer_params`` keeps it: the non-zero entries, or None when there is none."""
+    if not isinstance(costs, Mapping):
+        raise ValueError(f"label_costs is a mapping {{(gold, predicted): cost}}, got {type(costs).__name__}")
+    out = {}
+    for pair, cost in costs.items():
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError(f"label_costs: a key is a (gold, predicted) pair of labels, got {pair!r}")
+        gold, predicted = pair
+        cost = float(cost)
+        if cost < 0 or not math.isfinite(cost):
+            raise ValueError(f"label_costs: the cost of {(gold, predicted)!r} is {cost}: costs are finite and not negative")
+        if gold == predicted and cost != 0:
+            raise ValueError(f"label_costs: the cost of {(gold, predicted)!r} is {cost}: predicting the gold label costs 0")
+        if cost != 0:
+            out[(gold, predicted)] = cost
+    return out or None
 
 
 # ---------------------------------------------------------------------------------------------- optimiser
@@ -254,10 +280,12 @@ class TrainingSet:
     weighs 1, and the set trains on the unvalued kernels).  ``allowed``: one uint32 mask per item, bit y set when label y is
     allowed on it, or None when every item has exactly one label (a labelled set, which trains on the labelled kernels); a set
     with ``allowed`` is partially labelled, trains by marginal likelihood, and its ``labels`` hold every item's lowest allowed
-    id, which nothing reads."""
+    id, which nothing reads.  ``seq_weight``: one float64 weight >= 0 per sequence, which every instance cut from it carries
+    in the objective, or None (every sequence weighs 1, and the set trains on the kernels it always did)."""
 
     attr_value = None  # (a set built without the field has no values)
     allowed = None     # (and is labelled)
+    seq_weight = None  # (and every sequence weighs 1)
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -366,7 +394,7 @@ def _label_entry(entry):
 def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_labels: Sequence[Sequence[str]],
                        window: Optional[int] = None, step: Optional[int] = None, min_freq: float = 0.0,
                        all_possible_states: bool = False, all_possible_transitions: bool = False,
-                       max_labels: int = 2) -> TrainingSet:
+                       max_labels: int = 2, sample_weight=None) -> TrainingSet:
     """Encode sequences (per item the attribute names, per item a label) and generate CRFsuite's features over the
     sliding-window instances.  An item may also be a list of ``(name, value)`` pairs or a mapping (``item_attributes``):
     the set then has ``attr_value``, a state feature (a, y) exists if the pair is observed on a covered item whatever the
@@ -385,9 +413,20 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
     inside an instance hold i and j; its frequency is the sum over those occurrences of value x coverage (pair coverage
     for a transition).  The set then has ``allowed`` and trains by marginal likelihood (``fit_training_set``).  A set whose
     entries all name one label, however written, is the labelled set it always was, without ``allowed``.  An empty set is a
-    ``ValueError``, and so is a None where fewer than 2 labels occur overall."""
+    ``ValueError``, and so is a None where fewer than 2 labels occur overall.
+
+    ``sample_weight``: None, or one finite number >= 0 per sequence (anything else is a ``ValueError``), kept as the set's
+    ``seq_weight``.  Feature generation, the frequencies ``min_freq`` compares and the windows do not depend on it."""
     if not 2 <= int(max_labels) <= MAX_LABELS:
         raise ValueError(f"max_labels must lie in 2..{MAX_LABELS}, got {max_labels}")
+    seq_weight = None
+    if sample_weight is not None:
+        seq_weight = np.array(sample_weight, dtype=np.float64)
+        if seq_weight.shape != (len(sequences),):
+            raise ValueError(f"sample_weight holds one weight per sequence: expected {len(sequences)}, got shape {seq_weight.shape}")
+        bad = np.flatnonzero(~(np.isfinite(seq_weight) & (seq_weight >= 0)))
+        if bad.size:
+            raise ValueError(f"sample_weight[{int(bad[0])}] is {seq_weight[bad[0]]}: weights are finite and not negative")
     whole = window is None
     if whole:
         step = None
@@ -509,8 +548,37 @@ def build_training_set(sequences: Sequence[Sequence[Sequence[str]]], sequence_la
         labels=lab_a.astype(np.int32), labels_=list(label_index), attrs_=list(attr_index),
         state_attr=s_idx // L, state_label=s_idx % L, trans_src=t_idx // L, trans_dst=t_idx % L,
         state_fid=state_fid.reshape(A, L), trans_fid=trans_fid.reshape(L, L), window=window, step=step,
-        attr_value=val_a, allowed=np.array(masks, dtype=np.uint32) if partial else None,
+        attr_value=val_a, allowed=np.array(masks, dtype=np.uint32) if partial else None, seq_weight=seq_weight,
     )
+
+
+def _cost_matrix(ts: TrainingSet, params: Optional[Dict[str, object]]) -> Optional[np.ndarray]:
+    """``params['label_costs']`` as the matrix [L, L] (row = gold) over the label ids of ``ts``, or None without costs.  A
+    label the set does not have, and costs on a partially labelled set, raise ``ValueError``."""
+    costs = (params or {}).get("label_costs")
+    if not costs:
+        return None
+    if ts.allowed is not None:
+        raise ValueError("label_costs need a gold label on every item: the training set is partially labelled")
+    index = {name: k for k, name in enumerate(ts.labels_)}
+    C = np.zeros((len(index), len(index)), dtype=np.float64)
+    for (gold, predicted), cost in costs.items():
+        for name in (gold, predicted):
+            if name not in index:
+                raise ValueError(f"label_costs names the label {name!r}, which the training set does not have "
+                                 f"(its labels: {list(ts.labels_)})")
+        C[index[gold], index[predicted]] = cost
+    return C
+
+
+def _weighting(sets: Sequence[TrainingSet], params: Sequence[Optional[Dict[str, object]]]) -> Dict[str, list]:
+    """The ``weights=`` / ``costs=`` keywords of a ``_native`` trainer of these problems: none at all when no problem has
+    sequence weights or label costs (the call it always was), else both lists, None for a problem without."""
+    weights = [ts.seq_weight for ts in sets]
+    costs = [_cost_matrix(ts, p) for ts, p in zip(sets, params)]
+    if all(w is None for w in weights) and all(c is None for c in costs):
+        return {}
+    return {"weights": weights, "costs": costs}
 
 
 def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0,
@@ -524,7 +592,13 @@ def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0
     log Z - log Z_A, which is not convex: the optimiser then skips correction pairs without positive curvature
     (``minimize``'s ``skip_nonpositive_curvature``; labelled fits keep their iterates bit for bit).  It starts at w = 0 like
     every fit.  There every label scores alike, so an item's restricted marginal is uniform over its set: a set in which no
-    item names a single label has a zero gradient at 0 and the fit returns "converged" at w = 0."""
+    item names a single label has a zero gradient at 0 and the fit returns "converged" at w = 0.
+
+    Cost-sensitive fits: a set with sequence weights (``seq_weight``) or ``params`` with ``label_costs`` minimises
+    ``sum over instances of seq_weight * (log sum_y' exp(score(y') + sum_t C[y_t][y'_t]) - score(y))`` and takes
+    ``TrainerGeneral`` (windowed, 2 labels included) or ``TrainerSequences``.  With every weight 1 and no non-zero cost
+    such a 2-label windowed fit agrees with the 2-label trainer's to rounding; it is not bit-equal to it (the kernels
+    differ).  Costs exist in training only: the model and every prediction are what they always were."""
     from . import _native
 
     args = ts.native_args()
@@ -532,6 +606,7 @@ def fit_training_set(ts: TrainingSet, params: Dict[str, object], device: int = 0
     valued = {} if ts.attr_value is None else {"values": [ts.attr_value]}
     if ts.allowed is not None:
         valued["allowed"] = [ts.allowed]
+    valued.update(_weighting([ts], [params]))
     if ts.window is None:
         trainer = _native.TrainerSequences([args], device=device, **valued)
     elif ts.num_labels == 2 and not valued:
@@ -546,31 +621,43 @@ def _valued_entries(ts: TrainingSet) -> int:
     return 0 if ts.attr_value is None else int(len(ts.attr_value))
 
 
-def _general_trainer(ts: TrainingSet) -> bool:
-    """A windowed set that takes ``_native.TrainerGeneral`` at any label count: one with values or with allowed-label masks."""
-    return ts.attr_value is not None or ts.allowed is not None
+def _weighted_entries(ts: TrainingSet, params: Optional[Dict[str, object]], instances: int) -> int:
+    """What sequence weights or label costs add to a problem's scratch, in doubles: exactly what is uploaded for them, one
+    weight per instance and, with costs, the matrix [L, L]."""
+    costs = bool((params or {}).get("label_costs"))
+    if ts.seq_weight is None and not costs:
+        return 0
+    return instances + (ts.num_labels ** 2 if costs else 0)
 
 
-def _general_scratch_bytes(ts: TrainingSet) -> int:
+def _general_trainer(ts: TrainingSet, params: Optional[Dict[str, object]] = None) -> bool:
+    """A windowed set that takes ``_native.TrainerGeneral`` at any label count: one with values, with allowed-label masks or
+    with sequence weights, or any set when the fit's ``params`` carry label costs."""
+    return (ts.attr_value is not None or ts.allowed is not None or ts.seq_weight is not None
+            or bool((params or {}).get("label_costs")))
+
+
+def _general_scratch_bytes(ts: TrainingSet, params: Optional[Dict[str, object]] = None) -> int:
     """The scratch ``_native.TrainerGeneral`` allocates for ``ts`` (``scratch_bytes(k)``; the formula of DESIGN.md §4.9b:
-    item scores and marginals, node marginals, and one (f, xi) block per 128 windows plus 32 slabs)."""
+    item scores and marginals, node marginals, and one (f, xi) block per 128 windows plus 32 slabs), fitted with ``params``
+    (whose label costs, like the set's sequence weights, add what ``_weighted_entries`` says)."""
     L, W = ts.num_labels, ts.window
     n = np.diff(np.asarray(ts.seq_ptr, dtype=np.int64))
     windows = int(np.sum((n[n >= W] - W) // ts.step + 1))
     second_pass = windows * W * L if ts.allowed is not None else 0  # (a partial set: the restricted pass's log alpha, §4.9e)
     return 8 * (2 * int(ts.seq_ptr[-1]) * L + windows * W * L + (-(-windows // 128) + 32) * (1 + L * L) + second_pass
-                + _valued_entries(ts))
+                + _valued_entries(ts) + _weighted_entries(ts, params, windows))
 
 
-def _sequences_scratch_bytes(ts: TrainingSet) -> int:
+def _sequences_scratch_bytes(ts: TrainingSet, params: Optional[Dict[str, object]] = None) -> int:
     """The scratch ``_native.TrainerSequences`` allocates for ``ts`` (``scratch_bytes(k)``; the formula of DESIGN.md
     §4.9c: item scores and marginals, and one (f, xi) block per 256 / G sequences, G the power of two at or above L,
-    plus 32 slabs)."""
+    plus 32 slabs), fitted with ``params`` (as above)."""
     L = ts.num_labels
     per_block = 256 // max(2, 1 << (L - 1).bit_length())
     second_pass = int(ts.seq_ptr[-1]) * L if ts.allowed is not None else 0  # (a partial set: as above, §4.9e)
     return 8 * (2 * int(ts.seq_ptr[-1]) * L + (-(-(len(ts.seq_ptr) - 1) // per_block) + 32) * (1 + L * L) + second_pass
-                + _valued_entries(ts))
+                + _valued_entries(ts) + _weighted_entries(ts, params, len(ts.seq_ptr) - 1))
 
 
 def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], List[OptimizeResult]],
@@ -581,13 +668,14 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
     None``, any label count) in ``_native.TrainerSequences``; fit k trains ``sets[k]`` with ``params(k)``.  Without a
     budget the fits of such a family share one trainer; with one they run, in their order, in groups whose scratch fits the
     budget (a group holds at least one fit), one trainer after another, so that only one group is resident at a time.  A
-    fit's result does not depend on its group: problem k of a trainer has the bits of a lone trainer of it."""
+    fit's result does not depend on its group: problem k of a trainer has the bits of a lone trainer of it.  A windowed
+    2-label fit with sequence weights or label costs goes with the sets of more labels (``_general_trainer``)."""
     from . import _native
 
     results: List[Optional[OptimizeResult]] = [None] * len(sets)
     # (a windowed set with values or with masks goes with the sets of more labels, at any label count)
-    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and not _general_trainer(ts)]
-    more = [k for k, ts in enumerate(sets) if ts.window is not None and (ts.num_labels != 2 or _general_trainer(ts))]
+    two = [k for k, ts in enumerate(sets) if ts.window is not None and ts.num_labels == 2 and not _general_trainer(ts, params(k))]
+    more = [k for k, ts in enumerate(sets) if ts.window is not None and (ts.num_labels != 2 or _general_trainer(ts, params(k)))]
     whole = [k for k, ts in enumerate(sets) if ts.window is None]
     if two:
         for k, r in zip(two, fit_two(two)):
@@ -598,7 +686,7 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
         groups: List[List[int]] = []
         used = 0
         for k in members:
-            need = scratch(sets[k]) if budget is not None else 0
+            need = scratch(sets[k], params(k)) if budget is not None else 0
             if not groups or (budget is not None and used + need > budget):
                 groups.append([])
                 used = 0
@@ -609,6 +697,7 @@ def _by_label_count(sets: Sequence[TrainingSet], fit_two: Callable[[List[int]], 
             valued = {} if all(v is None for v in values) else {"values": values}  # (no values: the call it always was)
             if any(sets[k].allowed is not None for k in group):  # (partial sets beside labelled ones: None for the latter)
                 valued["allowed"] = [sets[k].allowed for k in group]
+            valued.update(_weighting([sets[k] for k in group], [params(k) for k in group]))  # (none: no keyword)
             trainer = getattr(_native, family)([sets[k].native_args() for k in group], device=device, **valued)
             for k, r in zip(group, _fit_lockstep(trainer, [sets[k] for k in group], [params(k) for k in group])):
                 results[k] = r
@@ -651,7 +740,9 @@ def fit_grid(sets: Sequence[TrainingSet], problems: Sequence[Tuple[int, Dict[str
     problems in one batched pass (in groups whose scratch fits ``scratch_budget_bytes``).  Result k is exactly
     ``fit_training_set(sets[set_k], params_k, device)``.  Problems on sets of more than two labels run in
     ``_native.TrainerGeneral`` (one copy of the set per problem), also in groups whose scratch fits the budget, one
-    group resident at a time; so do problems on sets of whole sequences, in ``_native.TrainerSequences``."""
+    group resident at a time; so do problems on sets of whole sequences, in ``_native.TrainerSequences``.  ``label_costs``
+    are a trainer parameter like ``c1`` / ``c2`` and may differ from problem to problem: a problem with costs, or on a set
+    with sequence weights, runs in ``TrainerGeneral`` at 2 labels too, the others keep ``TrainerGrid`` and their bits."""
     from . import _native
 
     if not problems:

@@ -236,6 +236,11 @@ def build_parser() -> argparse.ArgumentParser:
     group.add_argument("--window-step", type=int, default=1)
     group.add_argument("--c1", type=float, default=0.15, help="strength of the L1 regularisation")
     group.add_argument("--c2", type=float, default=0.15, help="strength of the L2 regularisation")
+    # (not gecco train's: the options exist on the parsed arguments only when they are given)
+    group.add_argument("--miss-cost", type=float, default=argparse.SUPPRESS,
+                       help="training cost of a missed cluster gene (label_costs[('1', '0')]; default: none)")
+    group.add_argument("--false-cost", type=float, default=argparse.SUPPRESS,
+                       help="training cost of a false cluster gene (label_costs[('0', '1')]; default: none)")
     group.add_argument("--feature-type", choices=("protein", "domain"), default="protein")
     group.add_argument("--select", type=float, default=None, help="fraction of domains kept by Fisher selection")
     group.add_argument("--correction", type=str, default=None,
@@ -259,7 +264,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     clusters = tables.ClusterTable.load(args.clusters)
     t1 = time.perf_counter()
     times["load"] = t1 - t0
-    crf = ClusterCRF(args.feature_type, "lbfgs", args.window_size, args.window_step, c1=args.c1, c2=args.c2)
+    from .cv import cost_options
+
+    crf = ClusterCRF(args.feature_type, "lbfgs", args.window_size, args.window_step, c1=args.c1, c2=args.c2,
+                     **cost_options(getattr(args, "miss_cost", 0.0), getattr(args, "false_cost", 0.0)))
     device = int((crf.devices or [0])[0])
     join = join_clusters(genes, clusters, device=device)
     t2 = time.perf_counter()

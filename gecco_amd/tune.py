@@ -45,6 +45,8 @@ def parser() -> argparse.ArgumentParser:
     ap.add_argument("--c1", type=_values(float), nargs="+", default=[[0.15]], help="values of c1 (L1 strength)")
     ap.add_argument("--c2", type=_values(float), nargs="+", default=[[0.15]], help="values of c2 (L2 strength)")
     ap.add_argument("--window-size", type=_values(int), nargs="+", default=[[5]], help="window sizes (1 to 32)")
+    ap.add_argument("--miss-cost", type=_values(float), nargs="+", default=None,
+                    help="values of the training cost of a missed cluster gene (an axis of the grid; 0: no cost)")
     ap.add_argument("--select", type=float, default=None, help="fraction of domains kept by Fisher selection")
     ap.add_argument("--correction", default=None, help="multiple-testing correction of the selection p-values")
     ap.add_argument("--loto", action="store_true", help="leave-one-type-out instead of K-fold cross-validation")
@@ -61,6 +63,8 @@ def parse_args(argv: Optional[List[str]] = None):
     args = ap.parse_args(argv)
     grid = {"c1": [v for vs in args.c1 for v in vs], "c2": [v for vs in args.c2 for v in vs],
             "window_size": [v for vs in args.window_size for v in vs]}
+    if args.miss_cost is not None:
+        grid[cv.COST_KEY] = [v for vs in args.miss_cost for v in vs]
     try:
         points = cv.grid_points(grid)
     except ValueError as err:
@@ -76,6 +80,8 @@ def train_command(args, point) -> str:
     """The winning options as ``python -m gecco_amd.train`` takes them."""
     words = ["python -m gecco_amd.train", "--feature-type", args.feature_type, "--window-size", str(point["window_size"]),
              "--window-step", str(args.window_step), "--c1", repr(float(point["c1"])), "--c2", repr(float(point["c2"]))]
+    if point.get(cv.COST_KEY):
+        words += ["--miss-cost", repr(float(point[cv.COST_KEY]))]
     if args.select is not None:
         words += ["--select", repr(args.select)]
     if args.correction is not None:
@@ -107,7 +113,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     result = cv.grid_search(crf, genes, splits, grid, shuffle=args.shuffle, select=args.select,
                             correction_method=args.correction, metric=args.metric)
     for p, pt in enumerate(result.points):
-        print(f"c1={pt['c1']} c2={pt['c2']} window_size={pt['window_size']}: mean AUROC={result.mean_auroc[p]:.3f} "
+        print(f"c1={pt['c1']} c2={pt['c2']} window_size={pt['window_size']}"
+              f"{' miss_cost=%s' % pt[cv.COST_KEY] if cv.COST_KEY in pt else ''}: mean AUROC={result.mean_auroc[p]:.3f} "
               f"mean AUPR={result.mean_aupr[p]:.3f}", file=sys.stderr)
     with open(args.output, "wb") as out:
         out.write(result.table())

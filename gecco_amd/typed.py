@@ -249,6 +249,44 @@ def gene_labels(n_genes: int, clusters: tables.ClusterTable, join: Any, limit: i
     return labels
 
 
+def balanced_class_weight(counts: Dict[str, int]) -> Dict[str, float]:
+    """sklearn's ``class_weight="balanced"`` over clusters: label l weighs n / (k * count_l), n the number of clusters, k
+    the number of labels present and count_l the clusters of label l."""
+    n, k = sum(counts.values()), len(counts)
+    return {label: n / (k * c) for label, c in counts.items()}
+
+
+def sequence_weights(genes: Sequence[Any], clusters: tables.ClusterTable, join: Any, labels: Sequence[Any],
+                     class_weight: Any) -> Tuple[Dict[str, float], Dict[str, float]]:
+    """``(class_weight_, weight of every sequence that holds a cluster)`` for ``TypedClusterCRF(class_weight=...)``.  The
+    clusters are ``gene_labels``' (``train_cli.assigned_clusters``), a cluster's label is the one ``labels`` (that
+    function's result) gives its first gene; a cluster whose genes carry a set of labels (``unknown="any"``) has no label
+    and weighs 1.  ``class_weight``: ``"balanced"`` (``balanced_class_weight`` over the clusters with a label) or a mapping
+    ``{label: weight}`` of finite weights >= 0 (a label it does not name weighs 1).  A sequence's weight is the mean of the
+    weights of the clusters on it, keyed by its source id; a sequence without a cluster is not listed and weighs 1."""
+    from .train_cli import assigned_clusters
+
+    on_sequence: Dict[str, List[Any]] = {}
+    counts: Dict[str, int] = {}
+    for _, i, _ in assigned_clusters(clusters, join):
+        members = np.asarray(join.members(i)).tolist()
+        label = labels[members[0]]
+        on_sequence.setdefault(genes[members[0]].source.id, []).append(label)
+        if isinstance(label, str) and label != BACKGROUND:
+            counts[label] = counts.get(label, 0) + 1
+    if class_weight == "balanced":
+        weights = balanced_class_weight(counts)
+    elif isinstance(class_weight, dict):
+        weights = {label: float(class_weight.get(label, 1.0)) for label in counts}
+        for label, w in class_weight.items():
+            if not (float(w) >= 0 and np.isfinite(float(w))):
+                raise ValueError(f"class_weight[{label!r}] is {w}: weights are finite and not negative")
+    else:
+        raise ValueError(f"class_weight is None, 'balanced' or a mapping {{label: weight}}, got {class_weight!r}")
+    return weights, {sid: float(np.mean([weights.get(lab, 1.0) if isinstance(lab, str) else 1.0 for lab in labs]))
+                     for sid, labs in on_sequence.items()}
+
+
 def known_masks(n_genes: int, known: tables.ClusterTable, join: Any, classes: Sequence[str],
                 background: str = BACKGROUND) -> np.ndarray:
     """The allowed-label mask of every gene (one uint32, bit k: ``classes[k]``) from what is known about some regions: the
@@ -395,19 +433,31 @@ def run_interval_offsets(p: np.ndarray, beyond: float, side: str) -> Tuple[int, 
 # ---------------------------------------------------------------------------------------------- the model
 class TypedClusterCRF:
     """``TypedClusterCRF(window_size=5, window_step=1, device=0, unknown="label", **options)``; ``options`` are the
-    trainer's (``train.trainer_params``: ``c1``, ``c2``, ...); ``unknown``: how ``fit`` labels the genes of a cluster without
+    trainer's (``train.trainer_params``: ``c1``, ``c2``, ``label_costs``, ...); ``class_weight``: None, ``"balanced"`` or
+    ``{label: weight}``: every training sequence then weighs the mean of the label weights of the clusters on it
+    (``sequence_weights``; the weights used are kept as ``class_weight_``); ``miss_cost`` / ``false_cost``: the training cost
+    of predicting the background on a gene of any cluster label / a cluster label on a background gene, added to the options'
+    ``label_costs`` for the pairs they do not name; ``unknown``: how ``fit`` labels the genes of a cluster without
     a type, ``"label"`` (the label ``"Unknown"``) or ``"any"`` (the set of every cluster label: module docstring).  After ``fit`` or ``trained``: ``classes_`` (labels in id order),
     ``label_types_`` (per label its type names), ``types_`` (the sorted distinct type names), ``background`` (``"0"``)."""
 
     feature_type = "protein"
 
     def __init__(self, window_size: int = 5, window_step: int = 1, device: int = 0, unknown: str = "label",
-                 **options: Any) -> None:
+                 class_weight: Any = None, miss_cost: float = 0.0, false_cost: float = 0.0, **options: Any) -> None:
         if options.pop("feature_type", "protein") != "protein":
             raise ValueError("typed models use protein features")
         if unknown not in ("label", "any"):
             raise ValueError(f"unknown must be 'label' or 'any', got {unknown!r}")
         self.unknown = unknown
+        if not (class_weight is None or class_weight == "balanced" or isinstance(class_weight, dict)):
+            raise ValueError(f"class_weight is None, 'balanced' or a mapping {{label: weight}}, got {class_weight!r}")
+        self.class_weight = class_weight
+        for name, cost in (("miss_cost", miss_cost), ("false_cost", false_cost)):
+            if not (float(cost) >= 0 and math.isfinite(float(cost))):
+                raise ValueError(f"{name} is {cost}: costs are finite and not negative")
+        self.miss_cost, self.false_cost = float(miss_cost), float(false_cost)
+        self.class_weight_: Optional[Dict[str, float]] = None
         if window_size <= 0:
             raise ValueError("Window size must be strictly positive")
         if window_step <= 0 or window_step > window_size:
@@ -448,17 +498,29 @@ class TypedClusterCRF:
         order = [[i for i, _ in group] for _, group in
                  itertools.groupby(enumerate(binary), key=lambda ig: ig[1].source.id)]
         typed = [[labels[i] for i in seq] for seq in order]
+        seq_weight = None
+        if self.class_weight is not None:  # (a sequence weighs the mean of its clusters' label weights, 1 without a cluster)
+            self.class_weight_, by_source = sequence_weights(genes, clusters, join, labels, self.class_weight)
+            seq_weight = [by_source.get(binary[seq[0]].source.id, 1.0) for seq in order]
         if [[lab != BACKGROUND for lab in seq] for seq in typed] != [[lab == "1" for lab in seq] for seq in binary_labels]:
             raise ValueError("different features and labels found, something is wrong")
         if shuffle:
-            pairs = list(zip(feats, typed))
+            pairs = list(zip(feats, typed, seq_weight or [1.0] * len(feats)))
             random.shuffle(pairs)
-            feats, typed = [f for f, _ in pairs], [t for _, t in pairs]
-        params = train.trainer_params(self._options)
+            feats, typed = [f for f, _, _ in pairs], [t for _, t, _ in pairs]
+            seq_weight = [w for _, _, w in pairs] if seq_weight is not None else None
+        options = dict(self._options)
+        if self.miss_cost or self.false_cost:  # (on top of the options' label_costs: every cluster label against the background)
+            costs = dict(options.get("label_costs") or {})
+            for label in dict.fromkeys(lab for seq in typed for lab in seq if isinstance(lab, str) and lab != BACKGROUND):
+                costs.setdefault((label, BACKGROUND), self.miss_cost)
+                costs.setdefault((BACKGROUND, label), self.false_cost)
+            options["label_costs"] = costs
+        params = train.trainer_params(options)
         ts = train.build_training_set(feats, typed, self.window_size, self.window_step, min_freq=float(params["min_freq"]),
                                       all_possible_states=bool(params["all_possible_states"]),
                                       all_possible_transitions=bool(params["all_possible_transitions"]),
-                                      max_labels=train.MAX_LABELS)
+                                      max_labels=train.MAX_LABELS, sample_weight=seq_weight)
         self.training_result_ = train.fit_training_set(ts, params, device=self.device)
         self._set_blob(train.model_blob(ts, self.training_result_.x))
         return self
@@ -1241,6 +1303,10 @@ def build_parser() -> argparse.ArgumentParser:
     tr.add_argument("--window-step", type=int, default=1)
     tr.add_argument("--c1", type=float, default=0.15, help="strength of the L1 regularisation")
     tr.add_argument("--c2", type=float, default=0.15, help="strength of the L2 regularisation")
+    tr.add_argument("--class-weight", choices=("balanced",), default=None,
+                    help="weigh every training sequence by its clusters' types: 'balanced' is n / (k * count) per type")
+    tr.add_argument("--miss-cost", type=float, default=0.0, help="training cost of calling a cluster gene background")
+    tr.add_argument("--false-cost", type=float, default=0.0, help="training cost of calling a background gene a cluster gene")
     tr.add_argument("--feature-type", choices=("protein", "domain"), default="protein")
     tr.add_argument("--select", type=float, default=None, help="fraction of domains kept by Fisher selection")
     tr.add_argument("--correction", type=str, default=None, help="multiple-testing correction of the selection p-values")
@@ -1322,7 +1388,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         np.random.seed(args.seed)
         genes = load_training_genes(args.genes, args.features, args.e_filter, args.p_filter)
         clusters = tables.ClusterTable.load(args.clusters)
-        crf = TypedClusterCRF(args.window_size, args.window_step, args.device, unknown=args.unknown, c1=args.c1, c2=args.c2)
+        crf = TypedClusterCRF(args.window_size, args.window_step, args.device, unknown=args.unknown, c1=args.c1, c2=args.c2,
+                              class_weight=args.class_weight, miss_cost=args.miss_cost, false_cost=args.false_cost)
         crf.fit(genes, clusters, shuffle=args.shuffle, select=args.select, correction_method=args.correction)
         crf.save(args.output_dir)
         print(f"train: {len(genes)} genes, {len(clusters)} clusters, labels {crf.classes_} -> {args.output_dir}", file=sys.stderr)

@@ -53,7 +53,7 @@ const char *gecco_crf_last_error(void);
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
  * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts, ABI 2.24.0
- * gecco_crf_span_conditionals, ABI 2.25.0 gecco_crf_max_marginals. */
+ * gecco_crf_span_conditionals, ABI 2.25.0 gecco_crf_max_marginals, ABI 2.26.0 the *_create_weighted trainers. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -689,6 +689,47 @@ int gecco_crf_trainer_sequences_create_partial(int32_t device, int32_t n_problem
                                                const int32_t *num_attrs, const int32_t *num_labels,
                                                const int32_t *const *state_fid, const int32_t *const *trans_fid,
                                                const int32_t *num_features, gecco_crf_trainer_sequences **out);
+
+/* ---- cost-sensitive training: sequence weights and a label-cost matrix (ABI 2.26.0, additive; gecco_crf_version() stays 340) ----
+ * Every sequence q of a problem carries a weight omega(q) >= 0, and the problem a cost matrix C[gold][predicted] >= 0 with a
+ * zero diagonal ("softmax-margin"):
+ *     f(w) = sum over instances of omega * (log sum over y' of exp(score(y') + sum_t C[y_t][y'_t]) - score(y)),
+ *     g(w) = sum over instances of omega * (E_cost-augmented[feature counts] - empirical counts),
+ * omega the weight of the sequence the instance was cut from (every window of it, or the whole sequence).  Both keep the
+ * objective convex.  The partition function sees a wrong label y' at an item whose gold label is y as C[y][y'] better than it
+ * is, so the optimum separates the gold path from costly mistakes by a margin.  Costs exist in training only: the model file
+ * and every prediction path are unchanged.  Log space throughout; no float atomics: an evaluation is bit-reproducible, and a
+ * problem's bits do not depend on its neighbours.
+ * The arguments of the *_create_partial sibling plus, after `allowed`:
+ *     seq_weight  const double *const *: per problem n_seqs[k] doubles.  NULL as a whole or per problem: weights of 1.
+ *     label_cost  const double *const *: per problem L * L doubles, row = gold.  NULL as a whole or per problem: no costs.
+ * attr_value and allowed may be NULL as a whole or per problem, as there.  A problem with neither weights nor costs is the
+ * problem the other creates build, with their kernels and their bits.  A problem with masks takes weights only:
+ * f = sum of omega * (log Z - log Z_A).  A weight of 0 is legal: the sequence contributes exact zeros.  eval, num_*,
+ * scratch_bytes and free are the family's.  The empirical counts are weighted on the host in one fixed order (state feature:
+ * value x coverage x omega; transition: omega per covered pair).
+ * Refused on the host before the device is looked at, GECCO_CRF_EINVAL, naming problem and index: a weight that is negative,
+ * NaN or infinite ("trainer general: problem k: weight of sequence s is negative or not finite"), a cost that is negative, NaN
+ * or infinite ("... cost [a][b] is negative or not finite"), a non-zero diagonal cost ("... cost [a][a] is on the diagonal and
+ * not 0"), costs on a problem with masks ("... label costs on a problem with allowed-label masks").
+ * Memory: a problem with weights or costs adds 8 bytes per instance (window, or sequence) to its scratch_bytes, and with costs
+ * 8 * L * L more; that is exactly what create uploads for it. */
+int gecco_crf_trainer_general_create_weighted(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                              const int32_t *n_seqs, const int32_t *const *item_ptr, const int32_t *const *attr_id,
+                                              const double *const *attr_value, const int32_t *const *labels,
+                                              const uint32_t *const *allowed, const double *const *seq_weight,
+                                              const double *const *label_cost, const int32_t *num_attrs,
+                                              const int32_t *num_labels, const int32_t *window, const int32_t *step,
+                                              const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                              const int32_t *num_features, gecco_crf_trainer_general **out);
+int gecco_crf_trainer_sequences_create_weighted(int32_t device, int32_t n_problems, const int32_t *const *seq_ptr,
+                                                const int32_t *n_seqs, const int32_t *const *item_ptr,
+                                                const int32_t *const *attr_id, const double *const *attr_value,
+                                                const int32_t *const *labels, const uint32_t *const *allowed,
+                                                const double *const *seq_weight, const double *const *label_cost,
+                                                const int32_t *num_attrs, const int32_t *num_labels,
+                                                const int32_t *const *state_fid, const int32_t *const *trans_fid,
+                                                const int32_t *num_features, gecco_crf_trainer_sequences **out);
 
 /* ---- allowed-label sets at inference (ABI 2.15.0, additive; gecco_crf_version() stays 340) ----------------------------------
  * Constrained decoding: every gene carries a set of allowed labels, one uint32_t with bit y set when label y is allowed, as

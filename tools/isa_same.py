@@ -1,6 +1,6 @@
 """Do two source trees compile to the same gfx950 machine code?  For a refactor that is meant to leave the kernels as they are.
 
-    python tools/isa_same.py PARENT_TREE [CHANGE_TREE] [--files a.hip b.hip ...] [--out FILE] [--keep DIR]
+    python tools/isa_same.py PARENT_TREE [CHANGE_TREE] [--files a.hip b.hip ...] [--out FILE] [--keep DIR] [--alias REGEX=REPL ...]
 
 Each named file of gecco_amd/csrc (default: the any-label lane-group files and the three contig-walk files) is compiled from both
 trees with the flags gecco_amd/build.py of the CHANGE tree gives that file, plus `--cuda-device-only -S`.  The assembly is split by
@@ -8,7 +8,11 @@ kernel symbol (the .amdhsa_kernel directives name them); of a kernel's body the 
 local labels are dropped, and what is left is compared as text, for equality only.  Printed: one line per kernel instance, "same" or
 "differs" with the two instruction counts, then the summary, which `--out` keeps: per file the number of instances and how many are
 the same, and every instance that differs by name.  Exit status 1 when an instance differs or exists in one tree only.  No device
-is needed."""
+is needed.
+
+`--alias REGEX=REPL` is for a change that gives a kernel template a further parameter, which renames every instance: a kernel of
+the CHANGE tree whose demangled name matches REGEX as a whole is compared under the name REPL gives (re.sub), the parent's name of
+the instantiation that is meant to stay the same.  E.g. --alias 'gen_labelled<(\d+), (\w+), false>=gen_labelled<\1, \2>'."""
 import argparse
 import importlib.util
 import os
@@ -69,6 +73,21 @@ def demangled(symbols):
         return {s: s for s in symbols}
 
 
+def aliased(change, parent, aliases):
+    """`change` ({symbol: lines}) with every kernel whose demangled name an alias maps onto a parent kernel's under that symbol."""
+    if not aliases:
+        return change
+    by_name = {name: sym for sym, name in demangled(sorted(parent)).items()}
+    names, out = demangled(sorted(change)), {}
+    for sym, body in change.items():
+        for pattern, repl in aliases:
+            if re.fullmatch(pattern, names[sym]):
+                sym = by_name.get(re.sub(pattern, repl, names[sym]), sym)
+                break
+        out[sym] = body
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("parent", help="the parent commit, checked out")
@@ -76,6 +95,8 @@ def main():
     ap.add_argument("--files", nargs="+", default=list(FILES))
     ap.add_argument("--out", default=None, help="also write the summary to this file")
     ap.add_argument("--keep", default=None, help="keep the assembly files in this directory")
+    ap.add_argument("--alias", nargs="+", default=[], metavar="REGEX=REPL",
+                    help="compare a kernel of the change whose demangled name matches REGEX under the name REPL gives")
     args = ap.parse_args()
     build = build_module(args.change)
     keep = args.keep or tempfile.mkdtemp(prefix="isa_same_")
@@ -90,7 +111,8 @@ def main():
              "file | flags of build.py | instances | same | differ"]
     exceptions, instances = [], []
     for name in args.files:
-        p, c = asm[("parent", name)], asm[("change", name)]
+        p = asm[("parent", name)]
+        c = aliased(asm[("change", name)], p, [tuple(a.split("=", 1)) for a in args.alias])
         names = demangled(sorted(set(p) | set(c)))
         same = 0
         for sym in sorted(set(p) | set(c)):
