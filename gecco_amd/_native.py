@@ -126,6 +126,16 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
          _c_f64p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_viterbi_run_length": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
+         ctypes.c_double, _c_i8p, _c_f64p, _c_f64p, _c_f64p],
+    ),
+    "gecco_crf_marginals_run_length": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
+         ctypes.c_double, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_run_counts": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
@@ -990,6 +1000,67 @@ class Model:
             *head, values, allowed, set_mask, min_run, None if marg is None else _ptr(marg, _c_f64p),
             None if inside is None else _ptr(inside, _c_f64p), _ptr(ln_c, _c_f64p), _ptr(ln, _c_f64p)))
         return (None if marg is None else marg[:n - n0]), (None if inside is None else inside[:n - n0]), ln_c[:nc], ln[:nc]
+
+    @staticmethod
+    def _length_model(who, set_mask, length_scores, tail):
+        """(set_mask, M, the table as a contiguous float64 array, tail): the shapes only -- the library checks the values."""
+        set_mask = operator.index(set_mask)
+        if not 0 <= set_mask < 1 << 32:
+            raise ValueError(f"{who}: set_mask {set_mask} is outside 0 .. 2**32 - 1")
+        g = np.ascontiguousarray(length_scores, dtype=np.float64)
+        if g.ndim != 1:
+            raise ValueError(f"{who}: length_scores is a one-dimensional table, got shape {g.shape}")
+        M = int(g.size)
+        if M == 0:  # (the library names the range; the pointer only has to be valid)
+            g = np.zeros(1, dtype=np.float64)
+        return set_mask, M, g, float(tail)
+
+    def viterbi_run_length(self, contig_ptr, gene_ptr, attr_id, set_mask, length_scores, tail=0.0, device=0, values=None,
+                           allowed=None, want_lognorm=True):
+        """The best label path of every contig under run-length potentials (``gecco_crf_viterbi_run_length``): every maximal
+        run of n genes with labels of the set (``set_mask`` has bit y set when label y is in it) adds ``length_scores[min(n, M)
+        - 1] + tail * max(n - M, 0)`` to the path's score, M = ``len(length_scores)``, 1 <= M <= 32; an entry is finite or
+        ``-inf``, and ``-inf`` forbids what it scores.  Returns ``(y, score, lognorm_run_length, lognorm)``: ``y`` int8 ``[n]``
+        (-1 at every gene of a contig without a feasible path); ``score`` float64 ``[n_contigs]``, the path's score with its
+        length terms (``-inf`` likewise); ``lognorm_run_length`` ``[n_contigs]``, the log-mass of all paths under that score;
+        ``lognorm`` as ``marginals_full`` gives it.  With ``want_lognorm=False`` the last two are None and the sum-semiring
+        launch does not run; ``y`` and ``score`` are the same bytes either way.  Zeros decode the plain lattice; ``(-inf, ...,
+        -inf, 0)`` is ``viterbi_min_run``; ``tail=-inf`` is a maximum run length.  Ties go by the kernel's scan order over
+        expanded states (include/gecco_crf.h).  ``values`` and ``allowed`` as in ``marginals_full``."""
+        set_mask, M, g, tail = self._length_model("viterbi_run_length", set_mask, length_scores, tail)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        y = np.zeros(max(n - n0, 1), dtype=np.int8)
+        score = np.zeros(max(nc, 1), dtype=np.float64)
+        ln_g = np.zeros(max(nc, 1), dtype=np.float64) if want_lognorm else None
+        ln = np.zeros(max(nc, 1), dtype=np.float64) if want_lognorm else None
+        _check(self._lib.gecco_crf_viterbi_run_length(
+            *head, values, allowed, set_mask, M, _ptr(g, _c_f64p), tail, _ptr(y, _c_i8p), _ptr(score, _c_f64p),
+            None if ln_g is None else _ptr(ln_g, _c_f64p), None if ln is None else _ptr(ln, _c_f64p)))
+        return y[:n - n0], score[:nc], (None if ln_g is None else ln_g[:nc]), (None if ln is None else ln[:nc])
+
+    def marginals_run_length(self, contig_ptr, gene_ptr, attr_id, set_mask, length_scores, tail=0.0, device=0, values=None,
+                             allowed=None, want_marginals=True, want_inside=True, want_counts=True):
+        """The marginals and the expected run-length counts under the length model of ``viterbi_run_length``
+        (``gecco_crf_marginals_run_length``; the same model arguments).  Returns ``(marg, inside, counts, lognorm_run_length,
+        lognorm)``: ``marg`` float64 ``[n, L]``; ``inside`` ``[n]``, its sum over the labels of the set; ``counts``
+        ``[n_contigs, M + 1]``, column d - 1 the expected number of runs with min(length, M) = d and column M the expected
+        number of genes beyond the M-th of their runs -- the derivatives of ``lognorm_run_length`` by the table and the tail;
+        each is None when not asked for, and asking for one changes no byte of another.  ``lognorm_run_length``
+        ``[n_contigs]`` has ``viterbi_run_length``'s bits.  A contig without a feasible path has 0.0 everywhere and ``-inf``;
+        a contig without genes 0 for both log Z and zeros in ``counts``."""
+        set_mask, M, g, tail = self._length_model("marginals_run_length", set_mask, length_scores, tail)
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        marg = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64) if want_marginals else None
+        inside = np.zeros(max(n - n0, 1), dtype=np.float64) if want_inside else None
+        counts = np.zeros((max(nc, 1), M + 1), dtype=np.float64) if want_counts else None
+        ln_g = np.zeros(max(nc, 1), dtype=np.float64)
+        ln = np.zeros(max(nc, 1), dtype=np.float64)
+        opt = lambda a: None if a is None else _ptr(a, _c_f64p)  # noqa: E731
+        _check(self._lib.gecco_crf_marginals_run_length(
+            *head, values, allowed, set_mask, M, _ptr(g, _c_f64p), tail, opt(marg), opt(inside), opt(counts), _ptr(ln_g, _c_f64p),
+            _ptr(ln, _c_f64p)))
+        return (None if marg is None else marg[:n - n0]), (None if inside is None else inside[:n - n0]), \
+            (None if counts is None else counts[:nc]), ln_g[:nc], ln[:nc]
 
     def run_counts(self, contig_ptr, gene_ptr, attr_id, set_mask, max_runs, device=0, values=None, allowed=None,
                    want_log_mass=True, want_paths=True, want_lognorm=True):

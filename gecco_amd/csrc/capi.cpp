@@ -1520,6 +1520,125 @@ GECCO_API int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t devi
     GECCO_GUARD_END
 }
 
+// ---- run-length potentials (ABI 2.27.0): a score g[min(n, M)] + tau max(n - M, 0) on every run of n genes with labels of a set,
+// on the run-counter lattice behind gl_state: the best path and the log-mass under it, the marginals and the expected run-length
+// counts; log Z from the whole-contig marginals pass (crf_runlength.hip)
+namespace {
+// the model arguments of the two entries, checked on the host: `who` is the entry's name
+int check_run_length_model(const char *who, const gecco_crf_model *m, uint32_t set_mask, int32_t max_length, const double *length_score,
+                           double tail, RunLengthScores &sc) {
+    const std::string name(who);
+    if (max_length < 1 || max_length > kMaxRunLength)
+        return fail(name + ": max_length = " + std::to_string(max_length) + " is outside 1 .. 32");
+    if (!length_score) return fail(name + ": length_score is NULL");
+    sc = RunLengthScores{};
+    for (int32_t d = 0; d < max_length; ++d) {
+        if (!(length_score[d] < std::numeric_limits<double>::infinity()))
+            return fail(name + ": length_score[" + std::to_string(d) + "] is NaN or +infinity (a score is finite or -infinity)");
+        sc.g[d] = length_score[d];
+    }
+    if (!(tail < std::numeric_limits<double>::infinity())) return fail(name + ": tail is NaN or +infinity (a score is finite or -infinity)");
+    sc.tau = tail;
+    sc.M = max_length;
+    return check_label_set((name + ": set_mask").c_str(), 0, set_mask, m->m.L);
+}
+}  // namespace
+
+GECCO_API int gecco_crf_viterbi_run_length(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                           const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                           const uint32_t *allowed, uint32_t set_mask, int32_t max_length, const double *length_score,
+                                           double tail, int8_t *y, double *score, double *lognorm_run_length, double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    RunLengthScores sc;
+    if ((rc = check_run_length_model("viterbi_run_length", m, set_mask, max_length, length_score, tail, sc))) return rc;
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    if (n_contigs > 0 && !score) return fail("viterbi_run_length: score is NULL");
+    if (n_contigs > 0 && contig_ptr[n_contigs] > contig_ptr[0] && !y) return fail("viterbi_run_length: y is NULL");
+    const size_t nc = size_t(n_contigs);
+    // per gene: the path.  Per contig, behind log Z: the score, log Z_g.  (The marginals are the pass's own output and are not
+    // returned.)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 1, 16, nullptr, lognorm,
+                        [&](ResidentBatch &b) {
+        if (b.n == 0) {  // (no genes: every contig's one path is the empty one, which has no run -- log Z_g = log Z = 0)
+            for (size_t c = 0; c < nc; ++c) {
+                score[c] = 0.0;
+                if (lognorm_run_length) lognorm_run_length[c] = 0.0;
+            }
+            return int(GECCO_CRF_OK);
+        }
+        double *d_lognorm = b.out<double>(2), *d_score = d_lognorm + nc, *d_lognorm_rl = d_score + nc;
+        DeviceBlock<char> ws;
+        int rc = ws.alloc(runlen_back_bytes(b.n, m->m.L, max_length), "hipMalloc run-length back-pointers");
+        if (rc) return rc;
+        rc = batch_wait(plan_run_viterbi_run_length(b.plan, b.csr, set_mask, sc, reinterpret_cast<uint8_t *>(ws.get()), b.out<int8_t>(1),
+                                                    d_score, lognorm_run_length ? d_lognorm_rl : nullptr, b.out<double>(0), d_lognorm,
+                                                    nullptr),
+                        "run-length decoding");
+        rc = batch_fetch(rc, y, b.out<int8_t>(1), size_t(b.n), "download path");
+        rc = batch_fetch(rc, score, d_score, nc * 8, "download score");
+        return batch_fetch(rc, lognorm_run_length, d_lognorm_rl, nc * 8, "download lognorm_run_length");
+    });
+    GECCO_GUARD_END
+}
+
+GECCO_API int gecco_crf_marginals_run_length(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                             const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value,
+                                             const uint32_t *allowed, uint32_t set_mask, int32_t max_length, const double *length_score,
+                                             double tail, double *marg, double *inside, double *counts, double *lognorm_run_length,
+                                             double *lognorm) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    RunLengthScores sc;
+    if ((rc = check_run_length_model("marginals_run_length", m, set_mask, max_length, length_score, tail, sc))) return rc;
+    if (!marg && !inside && !counts) return fail("marginals_run_length: marg, inside and counts are all NULL");
+    if (!lognorm_run_length) return fail("marginals_run_length: lognorm_run_length is NULL");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    const size_t nc = size_t(n_contigs), L = size_t(m->m.L), M1 = size_t(max_length) + 1;
+    const auto no_genes = [&] {  // log Z_g = log Z = 0, no run anywhere, and nothing else is written
+        for (size_t c = 0; c < nc; ++c) lognorm_run_length[c] = 0.0;
+        for (size_t k = 0; counts && k < nc * M1; ++k) counts[k] = 0.0;
+    };
+    {  // a batch whose every contig is empty needs no device
+        bool empty = true;
+        for (size_t c = 0; empty && c < nc; ++c) empty = contig_ptr[c + 1] == contig_ptr[c];
+        if (empty) {
+            no_genes();
+            for (size_t c = 0; lognorm && c < nc; ++c) lognorm[c] = 0.0;
+            return GECCO_CRF_OK;
+        }
+    }
+    // per gene: inside, then (if asked for) the marginals under the length model.  Per contig, behind log Z: log Z_g, the counts.
+    // (The free marginals are the pass's own output and are not returned.)
+    return lattice_call(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, allowed, 8 + (marg ? L * 8 : 0), 8 + M1 * 8,
+                        nullptr, lognorm, [&](ResidentBatch &b) {
+        if (b.n == 0) {
+            no_genes();
+            return int(GECCO_CRF_OK);
+        }
+        double *d_lognorm = b.out<double>(2), *d_lognorm_rl = d_lognorm + nc, *d_counts = d_lognorm_rl + nc;
+        double *d_inside = b.out<double>(1), *d_marg = marg ? d_inside + size_t(b.n) : nullptr;
+        DeviceBlock<char> ws;
+        int rc = ws.alloc(runlen_forward_bytes(b.n, m->m.L, max_length), "hipMalloc run-length forward values");
+        if (rc) return rc;
+        rc = batch_wait(plan_run_marginals_run_length(b.plan, b.csr, set_mask, sc, reinterpret_cast<double *>(ws.get()), d_marg,
+                                                      inside ? d_inside : nullptr, counts ? d_counts : nullptr, d_lognorm_rl,
+                                                      b.out<double>(0), d_lognorm, nullptr),
+                        "run-length marginals");
+        rc = batch_fetch(rc, marg, d_marg, size_t(b.n) * L * 8, "download marginals under the length model");
+        rc = batch_fetch(rc, inside, d_inside, size_t(b.n) * 8, "download inside");
+        rc = batch_fetch(rc, counts, d_counts, nc * M1 * 8, "download counts");
+        return batch_fetch(rc, lognorm_run_length, d_lognorm_rl, nc * 8, "download lognorm_run_length");
+    });
+    GECCO_GUARD_END
+}
+
 // ---- run counts (ABI 2.23.0): for k = 0 .. max_runs, the log-mass of the paths with exactly k runs of labels of a set (at
 // k = max_runs: at least that many), and the best such path with its score, on a lattice expanded by a saturating run counter
 // behind gl_state; log Z from the whole-contig marginals pass (crf_counts.hip)

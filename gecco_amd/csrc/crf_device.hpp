@@ -454,6 +454,36 @@ struct MaxMargArgs {
 // a.n_genes.  Four launches at the most: the forward walk, the backward walk, the epilogue over the genes, the span walks.
 hipError_t launch_gen_max_marginals(const GenArgs &a, const MaxMargArgs &p, hipStream_t stream);
 
+// ---- run-length potentials (crf_runlength.hip) ----
+constexpr int32_t kMaxRunLength = 32;  // M of one call: a column of LDS is 33 doubles, and a slot fits a back-pointer's five bits
+// The length model of one call, passed to the kernels by value: g[d - 1] is the score of a run of min(length, M) = d genes, tau
+// the score of every gene of a run beyond its M-th.  Every entry is finite or -infinity (the host has checked: no NaN, no
+// +infinity); the entries at and above M are not read.
+struct RunLengthScores {
+    double g[kMaxRunLength];
+    double tau;
+    int32_t M;
+};
+// the max semiring's own workspace: one byte per (gene, label, run counter), and behind them one per (gene, label)
+size_t runlen_back_bytes(int64_t n_genes, int32_t L, int32_t max_length);
+// y[g] = the label of gene g on the contig's best path under score_g = score + the length scores of its runs of labels in set_mask
+// (-1 at every gene of a contig without a feasible path), score[c] its score_g (-infinity likewise; 0 for a contig without genes),
+// lognorm_run_length[c] (null: not computed, one launch fewer) the log-mass of all paths under score_g, on the lattice of the
+// gl_state launch that ran before it on the same stream with a.state non-null: reads a.state, a.trans, a.contig_ptr and a.n_genes.
+// The caller has checked that set_mask has a bit, and none at or above L.
+hipError_t launch_gen_run_length(const GenArgs &a, uint32_t set_mask, const RunLengthScores &sc, uint8_t *back, int8_t *y, double *score,
+                                 double *lognorm_run_length, hipStream_t stream);
+// the workspace of the marginals under the length model: one double per (gene, label, run counter), the forward values
+size_t runlen_forward_bytes(int64_t n_genes, int32_t L, int32_t max_length);
+// The marginals and the expected run-length counts under the length model, two launches: the sum-semiring forward walk, which
+// leaves lognorm_run_length[c] (launch_gen_run_length's bits) and its forward values in fwd, and the backward walk, which writes
+// marg[g][j] (null: not written), inside[g] = the sum of marg[g] over the labels of set_mask (null: not computed) and
+// counts[c][0 .. M] (null: not written): column d - 1 the expected number of runs with min(length, M) = d, column M the expected
+// number of genes beyond the M-th of their runs; at least one of the three.  A contig without a feasible path gets 0.0
+// everywhere, a contig without genes 0 for log Z_g, zeros in counts and nothing else.
+hipError_t launch_gen_run_length_marginals(const GenArgs &a, uint32_t set_mask, const RunLengthScores &sc, double *fwd, double *marg,
+                                           double *inside, double *counts, double *lognorm_run_length, hipStream_t stream);
+
 // ---- edge posteriors (crf_edges.hip) ----
 constexpr int32_t kMaxEdgeSets = 32;   // label sets of one call
 constexpr int32_t kEdgeRunGenes = 32;  // genes of a run: what one group of lanes walks, counted from its contig's first gene

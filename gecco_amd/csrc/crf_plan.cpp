@@ -1481,6 +1481,39 @@ int plan_run_marginals_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask,
                      "min-run marginals launch");
 }
 
+// the length model of a run-length query: M inside the kernels' range, no NaN and no +infinity among its scores
+static bool run_length_scores_ok(const RunLengthScores &sc) {
+    bool ok = sc.M >= 1 && sc.M <= kMaxRunLength && sc.tau < INFINITY;
+    for (int32_t d = 0; ok && d < sc.M; ++d) ok = sc.g[d] < INFINITY;
+    if (!ok) set_error("max_length outside 1 .. 32, or a length score that is NaN or +infinity");
+    return ok;
+}
+
+int plan_run_viterbi_run_length(Plan &p, const DeviceCsr &csr, uint32_t set_mask, const RunLengthScores &sc, uint8_t *d_back, int8_t *d_y,
+                                double *d_score, double *d_lognorm_run_length, double *d_marg, double *d_lognorm, hipStream_t stream) {
+    if (!run_length_scores_ok(sc) || !set_mask_ok(p, set_mask)) return GECCO_CRF_EINVAL;
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0, !csr.gene_ptr || !d_marg || !d_back || !d_y || !d_score, rc)) return rc;
+    GenArgs g;  // (the pass gives log Z; the run-counter recursion reads the raw state scores and nothing else)
+    if ((rc = run_lattice(p, csr, "run-length decoding", true, d_marg, d_lognorm, stream, g))) return rc;
+    return check_hip(launch_gen_run_length(g, set_mask, sc, d_back, d_y, d_score, d_lognorm_run_length, stream), "run-length launch");
+}
+
+int plan_run_marginals_run_length(Plan &p, const DeviceCsr &csr, uint32_t set_mask, const RunLengthScores &sc, double *d_fwd,
+                                  double *d_marg_run_length, double *d_inside, double *d_counts, double *d_lognorm_run_length,
+                                  double *d_marg, double *d_lognorm, hipStream_t stream) {
+    if (!run_length_scores_ok(sc) || !set_mask_ok(p, set_mask)) return GECCO_CRF_EINVAL;
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !d_marg || !d_fwd || !d_lognorm_run_length || (!d_marg_run_length && !d_inside && !d_counts), rc))
+        return rc;
+    GenArgs g;  // (the pass gives log Z; the run-counter recursions read the raw state scores and nothing else)
+    if ((rc = run_lattice(p, csr, "run-length marginals", true, d_marg, d_lognorm, stream, g))) return rc;
+    return check_hip(launch_gen_run_length_marginals(g, set_mask, sc, d_fwd, d_marg_run_length, d_inside, d_counts,
+                                                     d_lognorm_run_length, stream),
+                     "run-length marginals launch");
+}
+
 int plan_run_run_counts(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t max_runs, uint8_t *d_back, double *d_log_mass,
                         double *d_score, int8_t *d_y, double *d_marg, double *d_lognorm, hipStream_t stream) {
     if (max_runs < 1 || max_runs > kMaxRunCounts) {

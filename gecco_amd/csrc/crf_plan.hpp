@@ -255,6 +255,19 @@ int plan_run_viterbi_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, i
 // d_inside [n_genes] or null, at least one of the two.  Not chunked.  All on `stream`.
 int plan_run_marginals_min_run(Plan &p, const DeviceCsr &csr, uint32_t set_mask, int32_t min_run, double *d_fwd, double *d_marg_min_run,
                                double *d_inside, double *d_lognorm_min_run, double *d_marg, double *d_lognorm, hipStream_t stream);
+// Decoding under run-length potentials, a plan laid out with `lattice`: the whole-contig marginals of the batch as above (d_marg,
+// d_lognorm), then the run-counter recursion with the length scores `sc` and its backtrack (crf_runlength.hip):
+// d_y [n_genes], d_score [n_contigs], and d_lognorm_run_length [n_contigs] or null (the sum-semiring launch does not run).  d_back
+// (runlen_back_bytes) is the kernel's workspace.  Not chunked.  All on `stream`.
+int plan_run_viterbi_run_length(Plan &p, const DeviceCsr &csr, uint32_t set_mask, const RunLengthScores &sc, uint8_t *d_back, int8_t *d_y,
+                                double *d_score, double *d_lognorm_run_length, double *d_marg, double *d_lognorm, hipStream_t stream);
+// Marginals and expected run-length counts under run-length potentials, a plan laid out with `lattice`: the whole-contig marginals as
+// above, then the sum-semiring forward walk with its values kept in d_fwd (runlen_forward_bytes) and the backward walk
+// (crf_runlength.hip): d_lognorm_run_length [n_contigs], d_marg_run_length [n_genes][L] or null, d_inside [n_genes] or null,
+// d_counts [n_contigs][M + 1] or null, at least one of the three.  Not chunked.  All on `stream`.
+int plan_run_marginals_run_length(Plan &p, const DeviceCsr &csr, uint32_t set_mask, const RunLengthScores &sc, double *d_fwd,
+                                  double *d_marg_run_length, double *d_inside, double *d_counts, double *d_lognorm_run_length,
+                                  double *d_marg, double *d_lognorm, hipStream_t stream);
 // Run counts, a plan laid out with `lattice`: the whole-contig marginals of the batch as above (d_marg, d_lognorm), then the
 // recursion on the lattice expanded by a saturating run counter (crf_counts.hip): d_log_mass [n_contigs][K + 1] or
 // null (the sum-semiring launch does not run); d_score [n_contigs][K + 1] or null (the max-semiring launch and the backtrack do

@@ -696,6 +696,169 @@ class SequenceCRF:
                         "constraint_log_probability": float(lognorm_c[s] - lognorm[s])})
         return out
 
+    # ---- run-length potentials: a score on the length of a run (``_native.Model.viterbi_run_length`` / ``marginals_run_length``)
+    @staticmethod
+    def _length_model(length_scores, tail) -> Tuple[np.ndarray, float]:
+        """The table and the tail of a length model, checked before any device call: 1 .. 32 entries, each finite or ``-inf``."""
+        try:
+            g = np.array(length_scores, dtype=np.float64)
+            tail = float(tail)
+        except (TypeError, ValueError):
+            raise ValueError(f"length_scores is a list of numbers and tail a number, got {length_scores!r} and {tail!r}") from None
+        if g.ndim != 1 or not 1 <= g.size <= 32:
+            raise ValueError(f"length_scores holds 1 .. 32 scores, got shape {g.shape}")
+        if np.isnan(g).any() or (g == np.inf).any():
+            raise ValueError("length_scores: a score is finite or -inf, not NaN or +inf")
+        if np.isnan(tail) or tail == np.inf:
+            raise ValueError(f"tail = {tail} is not finite or -inf")
+        return g, tail
+
+    def predict_run_length(self, X, labels, length_scores, tail=0.0, allowed=None) -> List[Dict[str, object]]:
+        """The best label path of every sequence under a score on the LENGTH of its runs.  A run is ``predict_min_run``'s: a
+        maximal stretch of consecutive items carrying a label of ``labels`` (the labels inside it may differ; runs at either
+        end of the sequence count).  With M = ``len(length_scores)`` (1 .. 32), a run of n items adds ``length_scores[min(n, M)
+        - 1] + tail * max(n - M, 0)`` to the path's score; every entry is finite or ``-inf``, and ``-inf`` forbids what it
+        scores.  Zeros are ``predict``; ``[-inf] * (m - 1) + [0]`` is ``predict_min_run(m)``; ``tail=-inf`` is a maximum run
+        length M; anything else is a soft duration model (``fit_run_length_scores`` learns one).  Per sequence a dict with
+        ``labels``: the path, or None when no path is feasible; ``score``: its score with the length terms (``-inf`` without a
+        path); ``log_probability_given_model``: ``score - log Z_g``, the path's log-probability under the extended model;
+        ``log_mass_ratio``: ``log Z_g - log Z``, the log of the expected ``exp`` of the length terms under the plain model.
+        On the whole-sequence lattice, not a windowed one; with ``allowed`` (as in ``predict``) on the restricted one.  One
+        forward-backward pass and two walks over ``X``, one native call.  A sequence without items has the empty path and zeros.
+        Raises ``ValueError`` before any device call for an unknown label, an empty set, a table that does not hold 1 .. 32
+        scores, and a NaN or ``+inf`` among the scores."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = self._label_bits("predict_run_length", labels)
+        g, tail = self._length_model(length_scores, tail)
+        n_seqs = len(seq_ptr) - 1
+        if seq_ptr[-1] == 0:
+            return [{"labels": [], "score": 0.0, "log_probability_given_model": 0.0, "log_mass_ratio": 0.0} for _ in range(n_seqs)]
+        y, score, lognorm_g, lognorm = self._model.viterbi_run_length(seq_ptr, item_ptr, attr, bits, g, tail, device=self.device,
+                                                                      values=values, allowed=masks)
+        out = []
+        for s, ys in enumerate(self._split(y, seq_ptr)):
+            found = score[s] > -np.inf
+            out.append({"labels": [self.classes_[c] for c in ys.tolist()] if found else None, "score": float(score[s]),
+                        "log_probability_given_model": float(score[s] - lognorm_g[s]) if found else -np.inf,
+                        "log_mass_ratio": float(lognorm_g[s] - lognorm[s])})
+        return out
+
+    def predict_marginals_run_length(self, X, labels, length_scores, tail=0.0, allowed=None) -> List[Dict[str, object]]:
+        """How sure the model is of every item under the length model of ``predict_run_length`` (the same arguments).  Per
+        sequence a dict with ``marginals``: ``[n_items, L]``, columns in ``predict_marginals``' order; ``inside``: ``[n_items]``,
+        the probability that the item carries a label of ``labels``; ``counts``: ``[M + 1]``, entry d - 1 the expected number of
+        runs with min(length, M) = d and the last entry the expected number of items beyond the M-th of their runs;
+        ``log_mass_ratio``: ``log Z_g - log Z``.  ``marginals`` and ``inside`` are None when no path is feasible
+        (``log_mass_ratio`` is then ``-inf`` and ``counts`` zeros).  One forward-backward pass and two walks over ``X``, one
+        native call.  A sequence without items has empty arrays, zero counts and 0.0.  Raises the ``ValueError`` s of
+        ``predict_run_length``, before any device call."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        bits = self._label_bits("predict_marginals_run_length", labels)
+        g, tail = self._length_model(length_scores, tail)
+        n_seqs, L = len(seq_ptr) - 1, len(self.classes_)
+        if seq_ptr[-1] == 0:
+            return [{"marginals": np.zeros((0, L)), "inside": np.zeros(0), "counts": np.zeros(g.size + 1), "log_mass_ratio": 0.0}
+                    for _ in range(n_seqs)]
+        marg, inside, counts, lognorm_g, lognorm = self._model.marginals_run_length(seq_ptr, item_ptr, attr, bits, g, tail,
+                                                                                    device=self.device, values=values, allowed=masks)
+        out = []
+        for s, (ms, ins) in enumerate(zip(self._split(marg, seq_ptr), self._split(inside, seq_ptr))):
+            found = lognorm_g[s] > -np.inf
+            out.append({"marginals": ms if found else None, "inside": ins if found else None, "counts": counts[s].copy(),
+                        "log_mass_ratio": float(lognorm_g[s] - lognorm[s])})
+        return out
+
+    def run_length_counts(self, X, labels, length_scores, tail=0.0) -> np.ndarray:
+        """The expected run-length counts of every sequence under the length model of ``predict_run_length``: float64 ``[n_seqs,
+        M + 1]``, column d - 1 the expected number of runs with min(length, M) = d, the last column the expected number of
+        items beyond the M-th of their runs.  With zeros for the scores these are the plain model's expectations (their first M
+        columns sum to ``expected_runs``).  One native call; a sequence without items, or without a feasible path, has zeros."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        bits = self._label_bits("run_length_counts", labels)
+        g, tail = self._length_model(length_scores, tail)
+        if seq_ptr[-1] == 0:
+            return np.zeros((len(seq_ptr) - 1, g.size + 1))
+        return self._model.marginals_run_length(seq_ptr, item_ptr, attr, bits, g, tail, device=self.device, values=values,
+                                                want_marginals=False, want_inside=False)[2]
+
+    @staticmethod
+    def observed_run_lengths(paths, inside, max_length: int) -> np.ndarray:
+        """The run-length counts of label paths: ``[len(paths), max_length + 1]`` in ``run_length_counts``' columns; ``inside``
+        says of a label whether it belongs to the set."""
+        out = np.zeros((len(paths), max_length + 1))
+        for q, path in enumerate(paths):
+            run = 0
+            for lab in list(path) + [None]:
+                if lab is not None and inside(lab):
+                    run += 1
+                    continue
+                if run:
+                    out[q, min(run, max_length) - 1] += 1.0
+                    out[q, max_length] += max(run - max_length, 0)
+                run = 0
+        return out
+
+    def fit_run_length_scores(self, X, y, labels, max_length, c2=1.0, **lbfgs) -> Tuple[np.ndarray, float]:
+        """Learn the length model of ``predict_run_length`` from labelled sequences, the CRF's own weights held fixed:
+        ``(length_scores [max_length], tail)`` that minimise
+
+            F(g, tau) = sum over the sequences of (log Z_g(x) - score_g(y)) + c2 / 2 * (|g|^2 + tau^2),
+
+        the penalised negative log-likelihood of ``y`` under the extended model.  The length scores are log-linear features
+        ("the number of runs of length d"), so F is convex -- strongly, with modulus ``c2`` -- and its gradient is the expected
+        minus the observed run-length counts plus ``c2`` times the parameters.  L-BFGS (``train.minimize`` with ``c1 = 0``) from
+        zeros; one evaluation is one ``marginals_run_length`` call over all of ``X`` (``lbfgs`` passes ``epsilon``, ``delta``,
+        ``max_iterations`` ... on).  The observed counts are taken from ``y`` on the host.  ``fit_run_length_result_`` keeps the
+        optimiser's result (its ``n_eval`` counts the native calls).  Raises ``ValueError`` before any device call for an
+        unknown label, an empty set, ``max_length`` outside 1 .. 32, ``c2 <= 0``, a ``y`` that does not match ``X``, and an entry
+        of ``y`` that is a set of labels or None (partial labels carry no run lengths)."""
+        from . import train
+
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        bits = self._label_bits("fit_run_length_scores", labels)
+        try:
+            M = operator.index(max_length)
+        except TypeError:
+            raise ValueError(f"max_length is an integer, got {max_length!r}") from None
+        if not 1 <= M <= 32:
+            raise ValueError(f"max_length = {M} is outside 1 .. 32")
+        c2 = float(c2)
+        if not c2 > 0.0 or not np.isfinite(c2):
+            raise ValueError(f"c2 = {c2} is not a positive number (it is what makes the fit strongly convex)")
+        y = [list(yseq) for yseq in y]
+        n_seqs = len(seq_ptr) - 1
+        if len(y) != n_seqs:
+            raise ValueError(f"X holds {n_seqs} sequences and y {len(y)}")
+        index = {c: k for k, c in enumerate(self.classes_)}
+        for k, ls in enumerate(y):
+            if len(ls) != seq_ptr[k + 1] - seq_ptr[k]:
+                raise ValueError(f"sequence {k}: {seq_ptr[k + 1] - seq_ptr[k]} items but {len(ls)} labels")
+            for lab in ls:
+                if lab is None or isinstance(lab, (set, frozenset, list, tuple)):
+                    raise ValueError(f"sequence {k}: fit_run_length_scores takes one label per item, got {lab!r} (a partially labelled "
+                                     f"sequence has no run lengths to count)")
+                if str(lab) not in index:
+                    raise ValueError(f"unknown label {str(lab)!r} (classes_: {self.classes_})")
+        observed = self.observed_run_lengths([[index[str(lab)] for lab in ls] for ls in y], lambda k: (bits >> k) & 1, M).sum(axis=0)
+        if seq_ptr[-1] == 0:
+            self.fit_run_length_result_ = None
+            return np.zeros(M), 0.0
+        gold = -float(self.log_likelihood(X, y).sum())  # sum of log Z - score(y): the part of F that the length model does not move
+
+        def fg(theta):
+            _, _, counts, lognorm_g, lognorm = self._model.marginals_run_length(
+                seq_ptr, item_ptr, attr, bits, theta[:M], theta[M], device=self.device, values=values, want_marginals=False,
+                want_inside=False)
+            f = gold + float((lognorm_g - lognorm).sum()) - float(observed @ theta) + 0.5 * c2 * float(theta @ theta)
+            return f, counts.sum(axis=0) - observed + c2 * theta
+
+        result = train.minimize(fg, np.zeros(M + 1), c1=0.0, **lbfgs)
+        self.fit_run_length_result_ = result
+        theta = np.asarray(result.x, dtype=np.float64)
+        return theta[:M].copy(), float(theta[M])
+
     # ---- run counts: how many runs a sequence holds, and the best path of every count (``_native.Model.run_counts``)
     @staticmethod
     def _max_runs(max_runs) -> int:

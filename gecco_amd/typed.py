@@ -139,6 +139,16 @@ is shorter than M); every path cluster gains ``average_p``, ``max_p`` and ``min_
 appends the three columns to ``path_clusters.tsv`` and writes ``path_genes.tsv`` (columns ``sequence_id, protein_id, path_label,
 p``).  Without the flag every table and every launch is what it is today.
 
+A length model (``fit_length_model(genes, clusters, max_length=M)``, ``train --length-model M``; ``predict_path_clusters(...,
+length_model=True)``, ``predict --path-clusters --length-model``).  A minimum of M genes is one hand-picked point of what a
+region's length can say: real regions have almost none under three genes and most between ten and forty.  The length model is a
+table of M scores (entry d - 1: a region of min(genes, M) = d genes) and a tail score per gene beyond the M-th, learnt from the
+training tables with the CRF's weights held fixed (``SequenceCRF.fit_run_length_scores``: convex, one whole-contig call per
+evaluation), saved as ``typed_length_model.tsv`` next to the model and loaded with it; a directory without the table has no
+length model.  With ``length_model=True`` the path clusters are the runs of the best whole-contig path under those scores
+(``_native.Model.viterbi_run_length``), ``marginals=True`` takes its probabilities under them
+(``_native.Model.marginals_run_length``), and ``min_run`` is not used: giving both is an error.
+
 Cluster counts (``predict_cluster_counts(genes, max_clusters=K)``, ``predict --cluster-counts K``, 1 <= K <= 32).  How many
 clusters does a contig hold, and how sure is the model of that number?  ``expected_clusters`` of ``sequences.tsv`` is the mean of
 the distribution and nothing else: 1.0 can be "certainly one" or a coin flip between none and two.  One whole-contig call
@@ -183,6 +193,14 @@ MAX_CLUSTER_LABELS = 31  # the trainer's 32 labels less the background
 
 MODEL_FILE = "typed_model.crfsuite"
 META_FILE = "typed_model.json"
+LENGTH_FILE = "typed_length_model.tsv"  # the length model, if the classifier has one: a settings table, "length<TAB>score"
+
+
+class _DefaultMinRun(int):
+    """The default ``min_run`` of ``predict_path_clusters``: 3, and told apart from a 3 the caller wrote."""
+
+
+_DEFAULT_MIN_RUN = _DefaultMinRun(3)
 
 
 # ---------------------------------------------------------------------------------------------- labels
@@ -468,6 +486,8 @@ class TypedClusterCRF:
         self.significance: Optional[Dict[str, float]] = None
         self.significant_features = None
         self.training_result_ = None
+        self.length_scores_: Optional[np.ndarray] = None  # (fit_length_model, or the model directory)
+        self.length_tail_: Optional[float] = None
         self._blob: Optional[bytes] = None
         self._model = None
 
@@ -560,6 +580,16 @@ class TypedClusterCRF:
         with open(os.path.join(model_dir, META_FILE), "w") as fh:
             json.dump(meta, fh, indent=1)
             fh.write("\n")
+        length_file = os.path.join(model_dir, LENGTH_FILE)
+        if self.length_scores_ is None:
+            if os.path.exists(length_file):  # (a directory written before by a classifier that had one)
+                os.remove(length_file)
+            return
+        with open(length_file, "w") as fh:  # floats with repr: they load as the same bits
+            fh.write("length\tscore\n")
+            for d, value in enumerate(np.asarray(self.length_scores_, dtype=np.float64).tolist(), 1):
+                fh.write(f"{d}\t{value!r}\n")
+            fh.write(f"tail\t{float(self.length_tail_)!r}\n")
 
     @classmethod
     def trained(cls, model_dir, device: int = 0) -> "TypedClusterCRF":
@@ -575,6 +605,15 @@ class TypedClusterCRF:
         self = cls(int(meta["window_size"]), int(meta["window_step"]), device)
         self.background = str(meta["background"])
         self._set_blob(blob, {entry["name"]: tuple(entry["types"]) for entry in meta["labels"]})
+        length_file = os.path.join(model_dir, LENGTH_FILE)
+        if os.path.exists(length_file):  # (a directory without the table has no length model)
+            with open(length_file) as fh:
+                rows = [line.rstrip("\n").split("\t") for line in fh if line.strip()]
+            if rows[:1] != [["length", "score"]] or len(rows) < 3 or rows[-1][0] != "tail" or \
+                    [r[0] for r in rows[1:-1]] != [str(d) for d in range(1, len(rows) - 1)]:
+                raise ValueError(f"{LENGTH_FILE}: expected the columns length, score, the rows 1 .. M and a row 'tail'")
+            self.length_scores_ = np.array([float(r[1]) for r in rows[1:-1]], dtype=np.float64)
+            self.length_tail_ = float(rows[-1][1])
         return self
 
     # ---- prediction
@@ -904,8 +943,38 @@ class TypedClusterCRF:
 
     PATH_GENE_COLUMNS = ("sequence_id", "protein_id", "path_label", "p")
 
-    def predict_path_clusters(self, genes: Iterable[Any], *, min_run: int = 3,
-                              known: Optional[tables.ClusterTable] = None, marginals: bool = False) -> List[Any]:
+    def fit_length_model(self, genes: Iterable[Any], clusters: tables.ClusterTable, max_length: int = 32,
+                         c2: float = 1.0) -> "TypedClusterCRF":
+        """Learn a score on the LENGTH of a region from labelled contigs, the CRF's weights held fixed, and keep it as
+        ``length_scores_`` (``[max_length]``; entry d - 1 scores a region of min(genes, max_length) = d genes) and
+        ``length_tail_`` (the score of every gene beyond the ``max_length``-th).  A region is a maximal run of genes with a
+        label other than the background, as ``predict_path_clusters`` calls them; the genes are labelled from ``clusters`` as
+        ``fit`` labels them.  The fit is ``SequenceCRF.fit_run_length_scores`` over the whole contigs: convex, L-BFGS from
+        zeros, one whole-contig native call per evaluation, ``c2`` its L2 penalty.  ``predict_path_clusters(...,
+        length_model=True)`` decodes with the result, and ``save`` writes it next to the model."""
+        from .sequence import SequenceCRF
+        from .train_cli import join_clusters
+
+        model = self._fitted()
+        genes = sorted(genes, key=operator.attrgetter("source.id", "start"))
+        labels = gene_labels(len(genes), clusters, join_clusters(genes, clusters, device=self.device), unknown=self.unknown)
+        contigs, csr, _ = self._whole_contigs(genes, None)
+        if csr is None:
+            raise ValueError("fit_length_model: no genes")
+        item_ptr, attr_ptr, attr_id = csr
+        names = model.attrs()
+        X = [[[names[a] for a in attr_id[attr_ptr[i]:attr_ptr[i + 1]].tolist()] for i in range(int(item_ptr[c]), int(item_ptr[c + 1]))]
+             for c in range(len(contigs))]
+        y = [labels[int(item_ptr[c]):int(item_ptr[c + 1])] for c in range(len(contigs))]
+        seq = SequenceCRF.from_bytes(self._blob, window_size=None, device=self.device)
+        g, tau = seq.fit_run_length_scores(X, y, [c for c in self.classes_ if c != self.background], max_length, c2=c2)
+        self.length_scores_, self.length_tail_ = g, tau
+        self.length_fit_result_ = seq.fit_run_length_result_
+        return self
+
+    def predict_path_clusters(self, genes: Iterable[Any], *, min_run: int = _DEFAULT_MIN_RUN,
+                              known: Optional[tables.ClusterTable] = None, marginals: bool = False,
+                              length_model: bool = False) -> List[Any]:
         """Clusters as the runs of the best whole-contig label path AMONG THOSE in which every maximal run of genes with a label
         other than the background has at least ``min_run`` genes (module docstring): one ``viterbi_min_run`` call over all
         contigs with the set of every label but the background.  ``min_run`` counts genes, not annotated genes (the refiner's
@@ -920,7 +989,16 @@ class TypedClusterCRF:
         ``inside`` = P(gene in a region | x, the constraint) over its genes, ``path_gene_probabilities_`` holds ``inside`` per
         gene in (sequence, start) order and ``path_genes_`` the columns ``PATH_GENE_COLUMNS`` (``path_label``: the gene's label
         on the path, empty where a contig has no path).  Without it neither attribute is set and no further launch runs.
-        ``ValueError`` before any device call for a ``min_run`` that is not an integer or lies outside its range."""
+        ``ValueError`` before any device call for a ``min_run`` that is not an integer or lies outside its range.
+        With ``length_model=True`` the path is the best one under the length scores of ``fit_length_model`` (or of the model
+        directory) instead: one ``viterbi_run_length`` call, and with ``marginals`` one ``marginals_run_length`` call, in place
+        of the min-run ones; ``constraint_log_p`` is then ``log Z_g - log Z``.  ``min_run`` is ignored then, and giving both
+        explicitly is a ``ValueError``, as is asking for a length model the classifier does not have."""
+        if length_model:
+            if min_run is not _DEFAULT_MIN_RUN:
+                raise ValueError("predict_path_clusters: min_run and length_model=True are two ways to say how long a region is: give one")
+            if getattr(self, "length_scores_", None) is None:
+                raise ValueError("predict_path_clusters: this classifier has no length model: call fit_length_model first")
         try:
             min_run = operator.index(min_run)
         except TypeError:
@@ -951,13 +1029,23 @@ class TypedClusterCRF:
         L = len(self.classes_)
         bg = self.classes_.index(self.background)
         item_ptr = batch.item_ptr.astype(np.int32)
-        y, score, lognorm_c, lognorm = model.viterbi_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
-                                                             ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device, allowed=allowed)
         inside_p = None
+        if length_model:
+            head = (item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id, ((1 << L) - 1) & ~(1 << bg), self.length_scores_,
+                    self.length_tail_)
+            y, score, lognorm_c, lognorm = model.viterbi_run_length(*head, device=self.device, allowed=allowed)
+            if marginals:
+                inside_p = model.marginals_run_length(*head, device=self.device, allowed=allowed, want_marginals=False,
+                                                      want_counts=False)[1]
+        else:
+            y, score, lognorm_c, lognorm = model.viterbi_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
+                                                                 ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device,
+                                                                 allowed=allowed)
+            if marginals:
+                _, inside_p, _, _ = model.marginals_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
+                                                            ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device, allowed=allowed,
+                                                            want_marginals=False)
         if marginals:
-            _, inside_p, _, _ = model.marginals_min_run(item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id,
-                                                        ((1 << L) - 1) & ~(1 << bg), min_run, device=self.device, allowed=allowed,
-                                                        want_marginals=False)
             self.path_gene_probabilities_ = inside_p
         Cluster = _cluster_class()
         clusters: List[Any] = []
@@ -1312,6 +1400,11 @@ def build_parser() -> argparse.ArgumentParser:
     tr.add_argument("--correction", type=str, default=None, help="multiple-testing correction of the selection p-values")
     tr.add_argument("--unknown", choices=("label", "any"), default="label",
                     help="genes of a cluster without a type: the label 'Unknown', or the set of every cluster label")
+    tr.add_argument("--length-model", type=int, default=None, metavar="M",
+                    help="after the fit, learn a score on the length of a region from the same tables (a table of M scores, at "
+                    "most 32, and a tail score) and write it next to the model: predict --path-clusters --length-model decodes "
+                    "with it")
+    tr.add_argument("--length-c2", type=float, default=1.0, metavar="C", help="the L2 penalty of the length model's fit")
     tr.add_argument("--device", type=int, default=0)
     tr.add_argument("-o", "--output-dir", default=".", help="the model directory")
     pr = sub.add_parser("predict", help="tables in; genes.tsv, features.tsv and clusters.tsv out")
@@ -1358,10 +1451,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="add margin_present, margin_absent and margin_broken to clusters.tsv: how much the score of the best "
                     "whole-contig label path drops when every gene of a called region must lie in a cluster, must not, or when one "
                     "must not (log-ratios of two paths' probabilities, not posteriors)")
-    pr.add_argument("--path-clusters", type=int, default=None, metavar="M",
+    pr.add_argument("--path-clusters", type=int, default=None, nargs="?", const=0, metavar="M",
                     help="write path_clusters.tsv and paths.tsv: the regions of the best whole-contig label path among those in "
                     "which every region has at least M (at most 32) genes, and per contig that path's probability and the "
-                    "probability that no region is shorter")
+                    "probability that no region is shorter; without M and with --length-model: the best path under the "
+                    "model directory's length scores")
+    pr.add_argument("--length-model", action="store_true",
+                    help="with --path-clusters (and no M): decode under the length scores that train --length-model wrote, in "
+                    "place of a minimum length")
     pr.add_argument("--path-marginals", action="store_true",
                     help="with --path-clusters M: add average_p, max_p and min_p to path_clusters.tsv, of the probability that a "
                     "gene lies in a region given that no region has fewer than M genes; write path_genes.tsv, that probability "
@@ -1390,11 +1487,22 @@ def main(argv: Optional[List[str]] = None) -> int:
         clusters = tables.ClusterTable.load(args.clusters)
         crf = TypedClusterCRF(args.window_size, args.window_step, args.device, unknown=args.unknown, c1=args.c1, c2=args.c2,
                               class_weight=args.class_weight, miss_cost=args.miss_cost, false_cost=args.false_cost)
+        if args.length_model is not None and not 1 <= args.length_model <= 32:
+            raise ValueError(f"--length-model {args.length_model} is outside 1 .. 32")
         crf.fit(genes, clusters, shuffle=args.shuffle, select=args.select, correction_method=args.correction)
+        if args.length_model is not None:
+            crf.fit_length_model(genes, clusters, max_length=args.length_model, c2=args.length_c2)
         crf.save(args.output_dir)
         print(f"train: {len(genes)} genes, {len(clusters)} clusters, labels {crf.classes_} -> {args.output_dir}", file=sys.stderr)
         return 0
-    if args.path_clusters is not None and not 1 <= args.path_clusters <= 32:
+    if args.length_model:
+        if args.path_clusters is None:
+            raise ValueError("--length-model needs --path-clusters")
+        if args.path_clusters != 0:
+            raise ValueError("--path-clusters M and --length-model are two ways to say how long a region is: give one")
+    elif args.path_clusters == 0:
+        raise ValueError("--path-clusters needs M, or --length-model")
+    if args.path_clusters is not None and not args.length_model and not 1 <= args.path_clusters <= 32:
         raise ValueError(f"--path-clusters {args.path_clusters} is outside 1 .. 32")
     if args.path_marginals and args.path_clusters is None:
         raise ValueError("--path-marginals needs --path-clusters M")
@@ -1430,7 +1538,8 @@ def main(argv: Optional[List[str]] = None) -> int:
     if args.path_clusters is not None:
         known = None if args.known is None else tables.ClusterTable.load(args.known)
         write_path_clusters(os.path.join(args.output_dir, "path_clusters.tsv"),
-                            crf.predict_path_clusters(genes, min_run=args.path_clusters, known=known, marginals=args.path_marginals),
+                            crf.predict_path_clusters(genes, known=known, marginals=args.path_marginals,
+                                                      **({"length_model": True} if args.length_model else {"min_run": args.path_clusters})),
                             marginals=args.path_marginals)
         if args.path_marginals:
             write_path_genes(os.path.join(args.output_dir, "path_genes.tsv"), crf.path_genes_)

@@ -53,7 +53,8 @@ const char *gecco_crf_last_error(void);
  * ABI 2.16.0 adds gecco_crf_span_probabilities in the same way, ABI 2.17.0 gecco_crf_sample_paths, ABI 2.18.0
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
  * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts, ABI 2.24.0
- * gecco_crf_span_conditionals, ABI 2.25.0 gecco_crf_max_marginals, ABI 2.26.0 the *_create_weighted trainers. */
+ * gecco_crf_span_conditionals, ABI 2.25.0 gecco_crf_max_marginals, ABI 2.26.0 the *_create_weighted trainers, ABI 2.27.0
+ * gecco_crf_viterbi_run_length and gecco_crf_marginals_run_length. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -1088,6 +1089,86 @@ int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t device, const 
                                 const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
                                 double *marg /* [n_genes][L] or NULL */, double *inside /* [n_genes] or NULL */,
                                 double *lognorm_min_run /* [n_contigs] */, double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- run-length potentials: decoding (ABI 2.27.0, additive; gecco_crf_version() stays 340) ---------------------------------------
+ * A score on the LENGTH of a run, on the whole-contig lattice of gecco_crf_viterbi and gecco_crf_marginals_full (not a windowed
+ * one).  set_mask names a label set S as in gecco_crf_viterbi_min_run, and a run is that entry's: a maximal stretch of genes
+ * whose labels lie in S; runs that touch the contig's first or last gene count like any other, and the labels inside a run may
+ * differ.  length_score[0 .. max_length - 1] = g[1 .. M] and tail = tau are each finite or -infinity.  For a path y whose runs
+ * have n_r genes,
+ *     score_g(y) = score(y) + sum over runs of ( g[min(n_r, M)] + tau * max(n_r - M, 0) ),
+ * and a term of -infinity makes the path infeasible.
+ *     g = 0, tau = 0                                 the plain lattice
+ *     M = m, g = (-inf, ..., -inf, 0), tau = 0       gecco_crf_viterbi_min_run with min_run = m
+ *     tau = -inf                                     a maximum run length M
+ *     anything else                                  a soft duration model
+ * y[g] = the label of gene g on the path of its contig with the largest score_g, score[c] = that score_g, lognorm_run_length[c]
+ * = log Z_g, the log-mass of all paths under score_g.  exp(score - lognorm_run_length) is the path's probability under the
+ * extended model; lognorm_run_length - lognorm compares the two models' masses.  attr_value and allowed as in
+ * gecco_crf_viterbi_min_run.  The walk is parallel over contigs and labels and sequential along a contig (not chunked).
+ *   * States: gecco_crf_viterbi_min_run's, with M for min_run.  The exit aggregate of a source label scores a run where it ends:
+ *     A_t(i) = (+)_d (alpha_t(i, d) + g[d]) for i in S, alpha_t(i) for i outside.  The sources of a destination at gene t: j
+ *     outside S -- A_{t-1}(i) + trans[i][j], every label i; (j, 1) -- alpha_{t-1}(i) + trans[i][j], i outside S, and at M = 1
+ *     also (alpha_{t-1}(i, 1) + tau) + trans[i][j], i in S; (j, d), 1 < d < M -- alpha_{t-1}(i, d - 1) + trans[i][j], i in S;
+ *     (j, M), M > 1 -- (i, M - 1) likewise and (alpha_{t-1}(i, M) + tau) + trans[i][j], i in S; then + state_t[j].  The total is
+ *     (+)_i A_{T-1}(i): a run that reaches the last gene is scored like any other.
+ *   * Max semiring: ((delta + g or tau) + trans) + state, every addition rounded on its own.  With integer weights and scores
+ *     every output equals enumeration bit for bit; with g = 0, tau = 0 the score is gecco_crf_viterbi_kbest's rank 0; with the
+ *     min-run table the score and the labels are gecco_crf_viterbi_min_run's.
+ *   * The tie rule is operational, as in gecco_crf_viterbi_min_run: a destination scans its sources in ascending label order, a
+ *     label's tau source directly behind its other one, with a strict `>` update; the aggregate scans d ascending with a strict
+ *     `>`; at the end the smaller label wins among equal aggregates.  A rule on expanded states, not an order on paths.
+ *   * Sum semiring: the same sources and aggregates with a max-shifted log-sum-exp, fp64 throughout; a destination all of whose
+ *     sources are -infinity stays -infinity.  It runs only when lognorm_run_length is given, and changes no byte of y or score.
+ *   * No feasible path: score -infinity, label -1 at every gene of the contig, lognorm_run_length -infinity; never NaN.
+ *   * Outputs.  y is int8 [n_genes]; score, lognorm_run_length (optional) and lognorm (optional) are double [n_contigs], lognorm
+ *     the bytes of gecco_crf_marginals_full (or its sibling by the arguments given).  A contig without genes gets score 0 and 0
+ *     for both log Z.  The back-pointers are workspace of n_genes * L * (M + 1) bytes: gecco_crf_viterbi_min_run's byte per
+ *     (gene, label, d) and one per (gene, label), the arg max d of the aggregate.  Equal calls give equal bytes (no atomics).
+ *   * Limits: 1 <= max_length <= 32 and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL, every message prefixed "viterbi_run_length:":
+ *     max_length outside 1 .. 32, a NaN or +infinity in length_score or tail, a set_mask of 0 or with a bit at or above
+ *     num_labels, score NULL.  The checks of the *_valued and *_constrained entries apply to attr_value and allowed.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form). */
+int gecco_crf_viterbi_run_length(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                 const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                                 const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t max_length,
+                                 const double *length_score /* [max_length] */, double tail, int8_t *y /* [n_genes] */,
+                                 double *score /* [n_contigs] */, double *lognorm_run_length /* [n_contigs] or NULL */,
+                                 double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- run-length potentials: marginals and expected length counts (ABI 2.27.0, additive; gecco_crf_version() stays 340) ----------
+ * marg[g][j] = P_g(gene g has label j | x), inside[g] = the sum of marg[g] over the labels of S, under the extended model of
+ * gecco_crf_viterbi_run_length (the same arguments, the same lattice), and counts[c][0 .. M]: counts[c][d - 1] = the expected
+ * number of runs with min(length, M) = d, d = 1 .. M, and counts[c][M] = the expected number of tail steps, sum of max(length - M,
+ * 0).  These are the derivatives of log Z_g by g[d] and by tau: with observed counts they are the gradient of a convex fit of
+ * the length scores.
+ *   * A forward-backward on the run-counter lattice in log space, fp64 throughout.  The forward walk is the sum-semiring walk of
+ *     gecco_crf_viterbi_run_length with its values kept: lognorm_run_length has that entry's bits.  Backward, per source i in S:
+ *     the exit continuation E_t(i) = LSE over k outside S of (trans[i][k] + state_{t+1}[k]) + beta_{t+1}(k), 0 at the last gene;
+ *     the stay continuation C_t(i, d) = LSE over k in S of (trans[i][k] + state_{t+1}[k]) + beta_{t+1}(k, min(d + 1, M));
+ *     beta_t(i, d) = LSE(g[d] + E, C), at d = M LSE(g[M] + E, tau + C).  marg[g][j] = the sum over d, ascending, of exp((alpha +
+ *     beta) - lognorm_run_length).  counts[d] adds exp(((alpha_t(i, d) + g[d]) + E_t(i)) - log Z_g), counts[M + 1] adds
+ *     exp((alpha_t(i, M) + (tau + C_t(i, M))) - log Z_g), per lane in walk order, reduced across the labels once per contig.
+ *   * Outputs.  marg double [n_genes][num_labels], inside double [n_genes], counts double [n_contigs][max_length + 1], each or
+ *     NULL, at least one of them; asking for one changes no byte of another.  lognorm_run_length [n_contigs] is required;
+ *     lognorm [n_contigs] is optional.  A disallowed (gene, label) pair gives exactly 0.0.  A contig without a feasible path
+ *     gives 0.0 everywhere and lognorm_run_length -infinity; never NaN.  A contig without genes gets 0 for both log Z and zeros
+ *     in counts.  With tau = -infinity counts[c][M] is exactly 0.0.
+ *   * The forward values are workspace of 8 * n_genes * num_labels * max_length bytes.  Equal calls give equal bytes (no
+ *     atomics), and a contig's bytes do not depend on the other contigs of the batch.
+ *   * Limits: 1 <= max_length <= 32 and num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL, every message prefixed "marginals_run_length:":
+ *     max_length outside 1 .. 32, a NaN or +infinity in length_score or tail, a set_mask of 0 or with a bit at or above
+ *     num_labels, marg, inside and counts all NULL, lognorm_run_length NULL.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form); contigs are not chunked. */
+int gecco_crf_marginals_run_length(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                                   const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                                   const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t max_length,
+                                   const double *length_score /* [max_length] */, double tail,
+                                   double *marg /* [n_genes][L] or NULL */, double *inside /* [n_genes] or NULL */,
+                                   double *counts /* [n_contigs][max_length + 1] or NULL */,
+                                   double *lognorm_run_length /* [n_contigs] */, double *lognorm /* [n_contigs] or NULL */);
 
 /* ---- run counts (ABI 2.23.0, additive; gecco_crf_version() stays 340) --------------------------------------------------------------
  * How many runs a contig holds, and the best path with a given number of them, on the whole-contig lattice of gecco_crf_viterbi
