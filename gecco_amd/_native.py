@@ -136,6 +136,10 @@ SIGNATURES = {
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
          ctypes.c_double, _c_f64p, _c_f64p, _c_f64p, _c_f64p, _c_f64p],
     ),
+    "gecco_crf_ring": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, _c_i8p, _c_f64p, _c_f64p, _c_f64p],
+    ),
     "gecco_crf_run_counts": (
         ctypes.c_int,
         [_vp, ctypes.c_int32, _c_i32p, ctypes.c_int32, _c_i32p, _c_i32p, _c_f64p, _c_u32p, ctypes.c_uint32, ctypes.c_int32, _c_f64p,
@@ -1000,6 +1004,29 @@ class Model:
             *head, values, allowed, set_mask, min_run, None if marg is None else _ptr(marg, _c_f64p),
             None if inside is None else _ptr(inside, _c_f64p), _ptr(ln_c, _c_f64p), _ptr(ln, _c_f64p)))
         return (None if marg is None else marg[:n - n0]), (None if inside is None else inside[:n - n0]), ln_c[:nc], ln[:nc]
+
+    def ring(self, contig_ptr, gene_ptr, attr_id, device=0, values=None, allowed=None, want_path=True, want_marginals=True):
+        """Every contig of the batch as a RING, whose last gene has a transition into its first (``gecco_crf_ring``).  Returns a
+        dict that holds only what was asked for: ``"lognorm"`` float64 ``[n_contigs]``, log Z of the ring (always);
+        ``"labels"`` int8 ``[n]`` and ``"score"`` float64 ``[n_contigs]`` (``want_path``), the ring's best path and its score,
+        closing edge included -- -1 at every gene and ``-inf`` for a ring without a feasible path; ``"marginals"`` float64
+        ``[n, L]`` (``want_marginals``), P(gene has label | x) on the ring, exactly 0.0 at a disallowed pair.  What is not asked
+        for is neither computed nor stored on the device, and changes no byte of the rest.  Ties: the smaller start label, then
+        ``viterbi``'s rule.  ``values`` and ``allowed`` as in ``marginals_full``.  A ring without genes has log Z 0 and score
+        0."""
+        head, values, allowed, n, n0, nc = self._csr_head(contig_ptr, gene_ptr, attr_id, values, allowed, int(device))
+        out = {"lognorm": np.zeros(max(nc, 1), dtype=np.float64)}
+        y = score = marg = None
+        if want_path:
+            y = out["labels"] = np.zeros(max(n - n0, 1), dtype=np.int8)
+            score = out["score"] = np.zeros(max(nc, 1), dtype=np.float64)
+        if want_marginals:
+            marg = out["marginals"] = np.zeros((max(n - n0, 1), self.num_labels), dtype=np.float64)
+        _check(self._lib.gecco_crf_ring(
+            *head, values, allowed, None if y is None else _ptr(y, _c_i8p), None if score is None else _ptr(score, _c_f64p),
+            None if marg is None else _ptr(marg, _c_f64p), _ptr(out["lognorm"], _c_f64p)))
+        size = {"lognorm": nc, "labels": n - n0, "score": nc, "marginals": n - n0}
+        return {k: v[:size[k]] for k, v in out.items()}
 
     @staticmethod
     def _length_model(who, set_mask, length_scores, tail):

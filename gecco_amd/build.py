@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgecco_crf.so")
-SOURCES = ["crf_model.cpp", "crf_plan.cpp", "crf_session.cpp", "crf_tables.cpp", "capi.cpp", "crf_kernels.hip", "crf_sequence.hip", "crf_segment.hip", "crf_general.hip", "crf_general_windowed.hip", "crf_spans.hip", "crf_conditionals.hip", "crf_runs.hip", "crf_sample.hip", "crf_kbest.hip", "crf_minrun.hip", "crf_counts.hip", "crf_maxmarg.hip", "crf_runlength.hip", "crf_edges.hip", "crf_composition.hip", "crf_exact.hip", "crf_train.hip", "crf_train_general.hip", "crf_fisher.hip", "crf_overlap.hip", "crf_forest.hip"]
+SOURCES = ["crf_model.cpp", "crf_plan.cpp", "crf_session.cpp", "crf_tables.cpp", "capi.cpp", "crf_kernels.hip", "crf_sequence.hip", "crf_segment.hip", "crf_general.hip", "crf_general_windowed.hip", "crf_spans.hip", "crf_conditionals.hip", "crf_runs.hip", "crf_sample.hip", "crf_kbest.hip", "crf_minrun.hip", "crf_counts.hip", "crf_maxmarg.hip", "crf_runlength.hip", "crf_ring.hip", "crf_edges.hip", "crf_composition.hip", "crf_exact.hip", "crf_train.hip", "crf_train_general.hip", "crf_fisher.hip", "crf_overlap.hip", "crf_forest.hip"]
 HEADERS = ["crf_model.hpp", "crf_plan.hpp", "crf_device.hpp", "crf_scan.hpp", "crf_lanes.hpp", "crf_lane_group.hpp", "crf_contig_walk.hpp", "crf_vd_short.hpp", "crf_session.hpp", "crf_tables.hpp", "crf_exact_exp.hpp", "crf_npsum.hpp", "crf_train.hpp", "crf_train_host.hpp", "crf_hip_own.hpp", "crf_fisher.hpp", "crf_overlap.hpp", "crf_forest.hpp", os.path.join("..", "..", "include", "gecco_crf.h")]
 # reference-bits mode and the correctly rounded exp rely on every multiply and add being rounded on its own: no fused multiply-add
 # where the source has none
@@ -32,7 +32,10 @@ EXTRA_FLAGS = {"crf_exact.hip": ["-ffp-contract=off"], "capi.cpp": ["-ffp-contra
                # (a max-marginal is the rounded sum of two such sums, and with integer weights every output is exact)
                "crf_maxmarg.hip": ["-ffp-contract=off"],
                # (a score under the length model is ((delta + g or tau) + trans) + state, every addition rounded on its own)
-               "crf_runlength.hip": ["-ffp-contract=off"]}
+               "crf_runlength.hip": ["-ffp-contract=off"],
+               # (a ring's score is the left-to-right sum of its terms and then the closing edge, and the conditioned walk repeats
+               # one slot of the max walk operation for operation)
+               "crf_ring.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"
 
 

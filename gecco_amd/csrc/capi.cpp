@@ -703,10 +703,12 @@ int check_label_set(const char *kind, int32_t q, uint32_t mask, int32_t L) {
 // `masked` (the *_constrained entries): `allowed` holds one mask per gene, indexed like the rows of gene_ptr (gene g of the caller's
 // arrays), each with a bit below L and none at or above it; otherwise `allowed` is not read.
 // Output i gets a part of the block, at b.out(i): per_gene[i] bytes for every gene (i = 0, 1), per_contig for every contig
-// (i = 2).  Returns with b.n == 0 for a batch without genes (nothing to run).
+// (i = 2).  Returns with b.n == 0 for a batch without genes (nothing to run).  empty_masks_ok: a mask of 0 is taken (the entry's
+// kernels read the state scores alone, where such a gene is -infinity at every label: its contig has no path).
 int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs, const int32_t *gene_ptr,
                const int32_t *attr_id, const double *attr_value, bool valued, const uint32_t *allowed, bool masked, int32_t window,
-               int32_t step, int32_t pad, bool windowed, const size_t per_gene[2], size_t per_contig, ResidentBatch &b) {
+               int32_t step, int32_t pad, bool windowed, const size_t per_gene[2], size_t per_contig, ResidentBatch &b,
+               bool empty_masks_ok = false) {
     int rc = check_contig_ptr(contig_ptr, n_contigs);
     if (rc) return rc;
     const int64_t n = n_contigs > 0 ? int64_t(contig_ptr[n_contigs]) - contig_ptr[0] : 0;
@@ -730,7 +732,7 @@ int batch_open(const gecco_crf_model *m, int32_t device, const int32_t *contig_p
         const int32_t L = m->m.L;
         for (int64_t i = 0; i < n; ++i) {
             const int64_t g = int64_t(contig_ptr[0]) + i;
-            if (allowed[g] == 0) return fail("constrained: gene " + std::to_string(g) + " allows no label (a mask of 0)");
+            if (allowed[g] == 0 && !empty_masks_ok) return fail("constrained: gene " + std::to_string(g) + " allows no label (a mask of 0)");
             if (allowed[g] & bits_beyond(L))
                 return fail("constrained: gene " + std::to_string(g) + " allows a label at or above num_labels = " + std::to_string(L) +
                             " (mask " + std::to_string(allowed[g]) + ")");
@@ -1517,6 +1519,58 @@ GECCO_API int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t devi
         rc = batch_fetch(rc, inside, d_inside, size_t(b.n) * 8, "download inside");
         return batch_fetch(rc, lognorm_min_run, d_lognorm_mr, nc * 8, "download lognorm_min_run");
     });
+    GECCO_GUARD_END
+}
+
+// ---- circular contigs (ABI 2.28.0): every contig of the call is a ring whose last gene has a transition into its first; exact
+// log Z, marginals and best path on the lattice expanded by the start label, behind gl_state (crf_ring.hip)
+GECCO_API int gecco_crf_ring(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                             const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value, const uint32_t *allowed,
+                             int8_t *y, double *score, double *marg, double *lognorm_ring) {
+    if (!m) return GECCO_CRF_EINVAL;
+    DeviceScope guard;
+    GECCO_GUARD_BEGIN
+    int rc;
+    // the checks of the call's own arguments, on the host and before any device work
+    if (!lognorm_ring) return fail("ring: lognorm_ring is NULL");
+    if (y && !score) return fail("ring: y given without score");
+    if (score && !y) return fail("ring: score given without y");
+    if (m->m.L > kGenMaxL) return fail("ring: num_labels = " + std::to_string(m->m.L) + " is above 32");
+    if ((rc = check_contig_ptr(contig_ptr, n_contigs))) return rc;
+    const size_t nc = size_t(n_contigs), L = size_t(m->m.L);
+    ResidentBatch b;
+    b.plan.lattice = true;
+    // per gene: the marginals and the path, each only when asked for.  Per contig: log Z of the ring, the score, the best start label.
+    const size_t per_gene[2] = {marg ? L * 8 : 0, y ? size_t(1) : 0};
+    rc = batch_open(m, device, contig_ptr, n_contigs, gene_ptr, attr_id, attr_value, attr_value != nullptr, allowed, allowed != nullptr, 1,
+                    1, 1, false, per_gene, 24, b, true);  // (a mask of 0 is taken: that ring has no path)
+    if (rc) return rc;
+    if (b.n == 0) {  // (no genes: every ring's one path is the empty one -- log Z = 0 and gecco_crf_viterbi's score)
+        for (size_t c = 0; c < nc; ++c) {
+            lognorm_ring[c] = 0.0;
+            if (score) score[c] = 0.0;
+        }
+        return GECCO_CRF_OK;
+    }
+    RingArgs q{};
+    q.lognorm_ring = b.out<double>(2);
+    q.marg = marg ? b.out<double>(0) : nullptr;
+    // the walks' workspace, a block of its own: the forward values for the marginals, the back-pointers for the path
+    DeviceBlock<char> ws;
+    const size_t b_fwd = marg ? align256(ring_forward_bytes(b.n, m->m.L, n_contigs)) : 0, b_back = y ? ring_back_bytes(b.n, m->m.L) : 0;
+    if (b_fwd + b_back && (rc = ws.alloc(b_fwd + b_back, "hipMalloc ring workspace"))) return rc;
+    if (marg) q.fwd = reinterpret_cast<double *>(ws.get());
+    if (y) {
+        q.y = b.out<int8_t>(1);
+        q.score = q.lognorm_ring + nc;
+        q.start = reinterpret_cast<int32_t *>(q.score + nc);
+        q.back = reinterpret_cast<uint8_t *>(ws.get() + b_fwd);
+    }
+    rc = batch_wait(plan_run_ring(b.plan, b.csr, q, nullptr), "ring");
+    rc = batch_fetch(rc, marg, q.marg, size_t(b.n) * L * 8, "download ring marginals");
+    rc = batch_fetch(rc, y, q.y, size_t(b.n), "download ring path");
+    rc = batch_fetch(rc, score, q.score, nc * 8, "download ring score");
+    return batch_fetch(rc, lognorm_ring, q.lognorm_ring, nc * 8, "download lognorm_ring");
     GECCO_GUARD_END
 }
 

@@ -454,6 +454,28 @@ struct MaxMargArgs {
 // a.n_genes.  Four launches at the most: the forward walk, the backward walk, the epilogue over the genes, the span walks.
 hipError_t launch_gen_max_marginals(const GenArgs &a, const MaxMargArgs &p, hipStream_t stream);
 
+// ---- circular contigs (crf_ring.hip) ----
+// the workspaces: the forward values, one double per (gene, label, start label), with one shift per gene and one shifted log Z
+// per contig behind them, needed for the marginals only; the conditioned Viterbi walk's back-pointers, one byte per (gene, label)
+size_t ring_forward_bytes(int64_t n_genes, int32_t L, int32_t n_contigs);
+size_t ring_back_bytes(int64_t n_genes, int32_t L);
+// What one call asks for.  lognorm_ring [n_contigs] is always written.  marg [n_genes][L] (null: neither the workspace is
+// written nor the backward walk run) needs fwd (ring_forward_bytes).  y [n_genes] and score [n_contigs] go together (null: the
+// two max-plus walks and the backtrack do not run) and need back (ring_back_bytes) and start [n_contigs], the best start label.
+struct RingArgs {
+    double *fwd, *marg;
+    uint8_t *back;
+    int32_t *start;
+    int8_t *y;
+    double *score, *lognorm_ring;
+};
+// Every contig of the batch as a ring, whose last gene has a transition into its first: lognorm_ring[c] = log Z of the ring,
+// marg[g][l] = P(gene g has label l | x) on it, y the ring's best path (-1 at every gene of a ring without a feasible path) and
+// score[c] its score, closing edge included (-infinity likewise).  A ring without genes gets 0 twice and nothing else.  On the
+// lattice of the gl_state launch that ran before it on the same stream with a.state non-null: reads a.state, a.trans and
+// a.contig_ptr.  Five launches at the most: the forward walk, the backward walk, the max walk, the conditioned walk, the backtrack.
+hipError_t launch_gen_ring(const GenArgs &a, const RingArgs &q, hipStream_t stream);
+
 // ---- run-length potentials (crf_runlength.hip) ----
 constexpr int32_t kMaxRunLength = 32;  // M of one call: a column of LDS is 33 doubles, and a slot fits a back-pointer's five bits
 // The length model of one call, passed to the kernels by value: g[d - 1] is the score of a run of min(length, M) = d genes, tau

@@ -803,6 +803,21 @@ int run_lattice(Plan &p, const DeviceCsr &csr, const char *what, bool keep_state
     return run_gen_whole(p, keep_state ? kGenMarginalsKeepState : kGenMarginals, csr, d_marg, d_lognorm, nullptr, nullptr, stream, &g);
 }
 
+// The state scores alone, for a query on a plan laid out with `lattice` whose kernels read nothing else: gl_state with the raw
+// scores kept and neither E nor smax.  No exp(trans) is read, and no transition range applies.  `g`: the launch's argument block.
+int run_state_only(Plan &p, const DeviceCsr &csr, const char *what, hipStream_t stream, GenArgs &g) {
+    SeqArgs a;
+    int rc = begin_whole_contig(p, csr, 0, a, stream);
+    if (rc) return rc;
+    if (!p.lattice || !p.general) {
+        set_error(std::string("the plan was not built for ") + what);
+        return GECCO_CRF_EINVAL;
+    }
+    if ((rc = fill_gen_args(p, csr, g, false, stream))) return rc;
+    g.E = g.smax = nullptr;
+    return check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch");
+}
+
 // where the window kernels accumulate (atomic maxima: `zero` first, numpy.zeros of crf/__init__.py:251) or store p; the genes of
 // skipped contigs keep "no prediction"
 int start_p_out(const Plan &p, double *d_p_out, bool zero, hipStream_t stream) {
@@ -1545,18 +1560,20 @@ int plan_run_max_marginals(Plan &p, const DeviceCsr &csr, const MaxMargArgs &q, 
     GenArgs g;
     if (d_lognorm) {  // (the pass gives log Z; the max walks read the raw state scores and nothing else)
         if ((rc = run_lattice(p, csr, "max-marginals", true, d_marg, d_lognorm, stream, g))) return rc;
-    } else {  // the state scores alone: no exp(trans) is read, and no transition range applies
-        SeqArgs a;
-        if ((rc = begin_whole_contig(p, csr, 0, a, stream))) return rc;
-        if (!p.lattice || !p.general) {
-            set_error("the plan was not built for max-marginals");
-            return GECCO_CRF_EINVAL;
-        }
-        if ((rc = fill_gen_args(p, csr, g, false, stream))) return rc;
-        g.E = g.smax = nullptr;
-        if ((rc = check_hip(launch_gen_state(g, stream, csr.attr_value, csr.allowed), "state score launch"))) return rc;
+    } else if ((rc = run_state_only(p, csr, "max-marginals", stream, g))) {  // (no exp(trans) is read: no transition range applies)
+        return rc;
     }
     return check_hip(launch_gen_max_marginals(g, q, stream), "max-marginal launch");
+}
+
+int plan_run_ring(Plan &p, const DeviceCsr &csr, const RingArgs &q, hipStream_t stream) {
+    int rc;
+    if (ends_here(p.n_contigs == 0 || p.n_genes == 0,
+                  !csr.gene_ptr || !q.lognorm_ring || (q.marg && !q.fwd) || (!q.y != !q.score) || (q.y && (!q.back || !q.start)), rc))
+        return rc;
+    GenArgs g;
+    if ((rc = run_state_only(p, csr, "circular contigs", stream, g))) return rc;
+    return check_hip(launch_gen_ring(g, q, stream), "ring launch");
 }
 
 int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, double *d_marg, double *d_lognorm, hipStream_t stream) {

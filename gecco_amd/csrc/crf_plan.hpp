@@ -287,6 +287,12 @@ int plan_run_edge_posteriors(Plan &p, const DeviceCsr &csr, const EdgeQuery &q, 
 // [n_contigs]) only when d_lognorm is given, and a call without it takes models whose transitions lie outside the sum-product
 // kernels' range.  Not chunked.  All on `stream`.
 int plan_run_max_marginals(Plan &p, const DeviceCsr &csr, const MaxMargArgs &q, double *d_marg, double *d_lognorm, hipStream_t stream);
+// Circular contigs, a plan laid out with `lattice`: gl_state with the raw state scores kept, then the walks of the lattice expanded
+// by the start label that `q` asks for (crf_ring.hip; crf_device.hpp: RingArgs -- device pointers throughout, its workspaces
+// included).  Every contig of the plan is a ring.  The walks run in log space on the state scores alone: no
+// exp(trans) is read, the whole-contig marginals of the chain do not run, and no transition range applies.  Not chunked.  All on
+// `stream`.
+int plan_run_ring(Plan &p, const DeviceCsr &csr, const RingArgs &q, hipStream_t stream);
 // counters of the 2-label Viterbi decoder (crf_device.hpp: SeqArgs::vd_stats); waits for the device
 int plan_viterbi_stats(Plan &p, int64_t out[4], bool reset);
 int get_device_tables(const Model &m, int device, const DeviceTables **out);

@@ -195,8 +195,68 @@ class SequenceCRF:
     def _allowed(self, allowed, seq_ptr: np.ndarray) -> Optional[np.ndarray]:
         return None if allowed is None else self._label_sets(allowed, seq_ptr, "allowed")[0]
 
-    def predict(self, X, allowed=None) -> List[List[str]]:
-        """Viterbi labels of every sequence; with ``allowed``, the best path inside the allowed sets."""
+    # ``circular=`` of ``predict``, ``predict_marginals`` and ``log_likelihood``: None (every sequence is a chain with two free
+    # ends: the calls and the bytes there have always been), True (every sequence is a RING, whose last item has a transition
+    # into its first: a complete chromosome or plasmid) or one boolean per sequence.  The circular sequences go to the ring entry
+    # in one call, the others to the chain entry in one call, and the results come back in the caller's order.
+    @staticmethod
+    def _ring_flags(circular, n_seqs: int) -> np.ndarray:
+        if isinstance(circular, (bool, np.bool_)):
+            return np.full(n_seqs, bool(circular))
+        flags = [bool(c) for c in circular]
+        if len(flags) != n_seqs:
+            raise ValueError(f"X holds {n_seqs} sequences and circular {len(flags)} flags")
+        return np.array(flags, dtype=bool)
+
+    def _by_topology(self, X, circular, per_sequence, chain, ring) -> list:
+        """``chain(X', extras')`` of the linear sequences and ``ring(X', extras')`` of the circular ones, each a list with one
+        result per sequence, merged in the caller's order; ``per_sequence`` holds the arguments that go sequence by sequence
+        (``allowed``, ``y``; None stays None)."""
+        X = list(X)
+        flags = self._ring_flags(circular, len(X))
+        per_sequence = [None if arg is None else list(arg) for arg in per_sequence]
+        for arg, what in zip(per_sequence, ("allowed", "y")):
+            if arg is not None and len(arg) != len(X):
+                raise ValueError(f"X holds {len(X)} sequences and {what} {len(arg)}")
+        out: list = [None] * len(X)
+        for keep, call in ((np.flatnonzero(~flags), chain), (np.flatnonzero(flags), ring)):
+            if len(keep):
+                part = call([X[k] for k in keep], *[None if arg is None else [arg[k] for k in keep] for arg in per_sequence])
+                for k, result in zip(keep.tolist(), part):
+                    out[k] = result
+        return out
+
+    def _ring(self, X, allowed, want_path: bool, want_marginals: bool):
+        """The ring entry's outputs for X, every sequence a ring, and the packed batch: ``(out, seq_ptr, item_ptr, attr, values)``.
+        A batch without items never reaches the device."""
+        seq_ptr, item_ptr, attr, values = self._pack(X)
+        masks = self._allowed(allowed, seq_ptr)
+        n_seqs, L = len(seq_ptr) - 1, len(self.classes_)
+        if seq_ptr[-1] == 0:
+            out = {"lognorm": np.zeros(n_seqs)}
+            if want_path:
+                out.update(labels=np.zeros(0, dtype=np.int8), score=np.zeros(n_seqs))
+            if want_marginals:
+                out["marginals"] = np.zeros((0, L))
+        else:
+            out = self._model.ring(seq_ptr, item_ptr, attr, device=self.device, values=values, allowed=masks, want_path=want_path,
+                                   want_marginals=want_marginals)
+        return out, seq_ptr, item_ptr, attr, values
+
+    def _ring_labels(self, X, allowed) -> List[List[str]]:
+        out, seq_ptr = self._ring(X, allowed, True, False)[:2]
+        return [[self.classes_[k] for k in ys.tolist()] for ys in self._split(out["labels"], seq_ptr)]
+
+    def _ring_marginals(self, X, allowed) -> List[np.ndarray]:
+        out, seq_ptr = self._ring(X, allowed, False, True)[:2]
+        return self._split(out["marginals"], seq_ptr)
+
+    def predict(self, X, allowed=None, circular=None) -> List[List[str]]:
+        """Viterbi labels of every sequence; with ``allowed``, the best path inside the allowed sets.  ``circular``: the
+        sequences that are rings get the ring's best path, closing edge included (ties: the smaller first label, then the
+        chain's rule)."""
+        if circular is not None:
+            return self._by_topology(X, circular, [allowed], self.predict, self._ring_labels)
         seq_ptr, item_ptr, attr, values = self._pack(X)
         masks = self._allowed(allowed, seq_ptr)
         if seq_ptr[-1] == 0:
@@ -204,9 +264,12 @@ class SequenceCRF:
         y, _ = self._model.viterbi(seq_ptr, item_ptr, attr, device=self.device, values=values, allowed=masks)
         return [[self.classes_[k] for k in ys.tolist()] for ys in self._split(y, seq_ptr)]
 
-    def predict_marginals(self, X, allowed=None) -> List[np.ndarray]:
+    def predict_marginals(self, X, allowed=None, circular=None) -> List[np.ndarray]:
         """Whole-sequence marginals: one ``[n_items, L]`` array per sequence, columns in ``classes_`` order; with
-        ``allowed``, given that the path lies inside the allowed sets (exactly 0.0 outside them)."""
+        ``allowed``, given that the path lies inside the allowed sets (exactly 0.0 outside them).  ``circular``: the
+        sequences that are rings get the ring's marginals, which do not depend on where the ring was cut."""
+        if circular is not None:
+            return self._by_topology(X, circular, [allowed], self.predict_marginals, self._ring_marginals)
         seq_ptr, item_ptr, attr, values = self._pack(X)
         masks = self._allowed(allowed, seq_ptr)
         if seq_ptr[-1] == 0:
@@ -214,7 +277,44 @@ class SequenceCRF:
         marg, _ = self._model.marginals_full(seq_ptr, item_ptr, attr, device=self.device, values=values, allowed=masks)
         return self._split(marg, seq_ptr)
 
-    def log_likelihood(self, X, y: Sequence[Sequence[str]]) -> np.ndarray:
+    def predict_ring(self, X, allowed=None) -> List[Dict[str, object]]:
+        """Every sequence as a ring, in one device call: per sequence ``labels`` (the ring's best path), ``score`` (its score:
+        the state scores, the transitions and the closing edge from the last item into the first), ``log_probability`` (=
+        ``score - lognorm``), ``lognorm`` (log Z of the ring) and ``marginals`` ``[n_items, L]``.  Rotating a ring rotates
+        ``labels`` and ``marginals`` and keeps the rest.  A sequence without items has no labels, score 0 and log Z 0."""
+        out, seq_ptr = self._ring(X, allowed, True, True)[:2]
+        labels, marginals = self._split(out["labels"], seq_ptr), self._split(out["marginals"], seq_ptr)
+        return [{"labels": [self.classes_[k] for k in labels[s].tolist()], "score": float(out["score"][s]),
+                 "log_probability": float(out["score"][s] - out["lognorm"][s]), "lognorm": float(out["lognorm"][s]),
+                 "marginals": marginals[s]} for s in range(len(seq_ptr) - 1)]
+
+    def _ring_log_likelihood(self, X, y) -> List[float]:
+        """``log_likelihood`` of rings: the path's ring score minus log Z of the ring, or with sets log Z_A,ring - log Z_ring."""
+        y = [list(yseq) for yseq in y]
+        out, seq_ptr, item_ptr, attr, values = self._ring(X, None, False, False)
+        masks, single = self._label_sets(y, seq_ptr, "y")
+        if len(masks) == 0:
+            return [0.0] * (len(seq_ptr) - 1)
+        if not single:
+            inside = self._model.ring(seq_ptr, item_ptr, attr, device=self.device, values=values, allowed=masks, want_path=False,
+                                      want_marginals=False)["lognorm"]
+            return (inside - out["lognorm"]).tolist()
+        yy = np.log2(masks.astype(np.float64)).astype(np.int64)  # (one bit per mask)
+        state, _ = self._model.state_weights()
+        trans, _ = self._model.trans_weights()
+        owner = np.repeat(np.arange(len(yy)), np.diff(item_ptr))
+        score = np.zeros(len(yy))  # per item: its state score under its label, and the transition into it -- the closing edge at the first
+        np.add.at(score, owner, state[attr, yy[owner]] if values is None else values * state[attr, yy[owner]])
+        lengths = np.diff(seq_ptr)
+        full = np.flatnonzero(lengths > 0)
+        first = np.repeat(seq_ptr[:-1][full], lengths[full])
+        before = first + (np.arange(len(yy)) - first - 1) % np.repeat(lengths[full], lengths[full])
+        score += trans[yy[before], yy]
+        result = np.zeros(len(seq_ptr) - 1)
+        result[full] = np.add.reduceat(score, seq_ptr[:-1][full]) - out["lognorm"][full]
+        return result.tolist()
+
+    def log_likelihood(self, X, y: Sequence[Sequence[str]], circular=None) -> np.ndarray:
         """``log p(y | x)`` of every sequence under the model (CRFsuite's ``Tagger.probability`` in logs): the gold path's
         score, gathered on the host from the weight tables (value x weight for items with values), minus the log partition function of the whole-sequence
         marginals.  An unknown label raises ``ValueError``; an empty sequence gives 0.0.
@@ -223,7 +323,13 @@ class SequenceCRF:
         log-probability that the path lies inside the sets -- the negative of the sequence's term in the partial trainer's
         objective -- from two whole-sequence forward-backward passes, one on the restricted lattice and one on the full one.
         (Both take the masked state-score kernel, the second with every label allowed, which has the unmasked kernels' bits:
-        with every entry None the result is exactly 0.0 at every label count.)"""
+        with every entry None the result is exactly 0.0 at every label count.)
+
+        ``circular``: for the sequences that are rings the path's score has the closing edge from the last item into the first
+        (added on the host) and the partition function is the ring's; with sets the result is ``log Z_A,ring - log Z_ring``."""
+        if circular is not None:
+            return np.array(self._by_topology(X, circular, [None, y], lambda Xs, _, ys: self.log_likelihood(Xs, ys).tolist(),
+                                              lambda Xs, _, ys: self._ring_log_likelihood(Xs, ys)), dtype=np.float64)
         seq_ptr, item_ptr, attr, values = self._pack(X)
         y = [list(yseq) for yseq in y]
         if any(lab is None or isinstance(lab, (set, frozenset, list, tuple)) for yseq in y for lab in yseq):

@@ -974,7 +974,7 @@ class TypedClusterCRF:
 
     def predict_path_clusters(self, genes: Iterable[Any], *, min_run: int = _DEFAULT_MIN_RUN,
                               known: Optional[tables.ClusterTable] = None, marginals: bool = False,
-                              length_model: bool = False) -> List[Any]:
+                              length_model: bool = False, circular=None) -> List[Any]:
         """Clusters as the runs of the best whole-contig label path AMONG THOSE in which every maximal run of genes with a label
         other than the background has at least ``min_run`` genes (module docstring): one ``viterbi_min_run`` call over all
         contigs with the set of every label but the background.  ``min_run`` counts genes, not annotated genes (the refiner's
@@ -993,7 +993,26 @@ class TypedClusterCRF:
         With ``length_model=True`` the path is the best one under the length scores of ``fit_length_model`` (or of the model
         directory) instead: one ``viterbi_run_length`` call, and with ``marginals`` one ``marginals_run_length`` call, in place
         of the min-run ones; ``constraint_log_p`` is then ``log Z_g - log Z``.  ``min_run`` is ignored then, and giving both
-        explicitly is a ``ValueError``, as is asking for a length model the classifier does not have."""
+        explicitly is a ``ValueError``, as is asking for a length model the classifier does not have.
+        ``circular`` names the contigs that are RINGS -- a collection of sequence ids (a single string is one id), or True for every contig; None or an
+        empty collection: every contig is a chain, and the call is the one it has always been.  On a circular contig the path
+        is the ring's best path (one ``ring`` call over all of them; the last gene has a transition into the first), and a run
+        that crosses the cut is ONE cluster: its genes are ``contig[a:] + contig[:b]``, ``wraps_origin`` is True and it is
+        numbered by where it starts.  A ring labelled non-background throughout is one cluster of all genes in contig order
+        with ``wraps_origin`` False.  Every cluster of such a call has ``wraps_origin``.  With ``marginals`` the per-gene
+        ``inside`` of a ring comes from the ring's marginals; ``path_posteriors_`` gets its columns from the ring's quantities,
+        and ``constraint_log_p`` is 0 there.  On a circular contig only ``min_run=1`` is defined: ``min_run`` > 1 (the default
+        included) or ``length_model=True`` together with a non-empty ``circular`` is a ``ValueError`` before any device call.
+        The linear contigs of the same call behave as ever."""
+        rings_all = circular is True
+        if isinstance(circular, (str, bytes)):  # (one sequence id, not its characters)
+            circular = [circular.decode() if isinstance(circular, bytes) else circular]
+        ring_ids = frozenset() if circular is None or isinstance(circular, (bool, np.bool_)) else frozenset(str(c) for c in circular)
+        with_rings = rings_all or bool(ring_ids)
+        if with_rings and (length_model or min_run is _DEFAULT_MIN_RUN or min_run != 1):
+            raise ValueError("predict_path_clusters: on a circular contig only min_run=1 is defined: a minimum run length across the "
+                             "cut needs the head run's length as a second counter (L * m**2 slots) and is left out, so min_run > 1 "
+                             "(the default included) or length_model=True cannot go with a non-empty circular")
         if length_model:
             if min_run is not _DEFAULT_MIN_RUN:
                 raise ValueError("predict_path_clusters: min_run and length_model=True are two ways to say how long a region is: give one")
@@ -1030,7 +1049,10 @@ class TypedClusterCRF:
         bg = self.classes_.index(self.background)
         item_ptr = batch.item_ptr.astype(np.int32)
         inside_p = None
-        if length_model:
+        is_ring = [with_rings and (rings_all or str(contig[0].source.id) in ring_ids) for contig in contigs]
+        if any(is_ring):
+            y, score, lognorm_c, lognorm, inside_p = self._paths_with_rings(model, contigs, is_ring, item_ptr, allowed, marginals)
+        elif length_model:
             head = (item_ptr, batch.attr_ptr.astype(np.int32), batch.attr_id, ((1 << L) - 1) & ~(1 << bg), self.length_scores_,
                     self.length_tail_)
             y, score, lognorm_c, lognorm = model.viterbi_run_length(*head, device=self.device, allowed=allowed)
@@ -1056,14 +1078,20 @@ class TypedClusterCRF:
             if score[ci] > -np.inf:
                 inside = np.concatenate([[False], path != bg, [False]])
                 edges = np.flatnonzero(inside[1:] != inside[:-1])
-                for a, b in zip(edges[::2].tolist(), edges[1::2].tolist()):
+                runs = [np.arange(a, b) for a, b in zip(edges[::2].tolist(), edges[1::2].tolist())]
+                wraps = is_ring[ci] and len(runs) >= 2 and runs[0][0] == 0 and runs[-1][-1] == c1 - c0 - 1
+                if wraps:  # the run across the cut is one cluster, numbered by where it starts: after the others
+                    runs = runs[1:-1] + [np.concatenate([runs[-1], runs[0]])]
+                for k, members in enumerate(runs):
                     found += 1
-                    cluster = Cluster(f"{contig[0].source.id}_cluster_{found}", list(contig[a:b]))
-                    major = int(np.argmax(np.bincount(path[a:b], minlength=L)))
+                    cluster = Cluster(f"{contig[0].source.id}_cluster_{found}", [contig[t] for t in members.tolist()])
+                    major = int(np.argmax(np.bincount(path[members], minlength=L)))
                     cluster.type = _cluster_type_factory(cluster)(self.label_types_[major])
                     cluster.path_type = ";".join(self.label_types_[major]) or UNKNOWN  # (as the alternatives name a run's type)
+                    if with_rings:
+                        cluster.wraps_origin = bool(wraps and k == len(runs) - 1)
                     if inside_p is not None:
-                        ps = inside_p[c0 + a:c0 + b]
+                        ps = inside_p[c0 + members]
                         cluster.average_p, cluster.max_p, cluster.min_p = float(np.mean(ps)), float(ps.max()), float(ps.min())
                     clusters.append(cluster)
             if inside_p is not None:
@@ -1076,6 +1104,38 @@ class TypedClusterCRF:
                                                        float(score[ci] - lognorm[ci]), float(lognorm_c[ci] - lognorm[ci]), found)):
                 self.path_posteriors_[name].append(value)
         return clusters
+
+    def _paths_with_rings(self, model, contigs, is_ring, item_ptr: np.ndarray, allowed, marginals: bool):
+        """``predict_path_clusters``'s ``(y, score, lognorm_c, lognorm, inside_p)`` at ``min_run = 1`` for a batch with circular
+        contigs: the linear contigs through the calls they always take, in one batch of their own, the circular ones through
+        one ``ring`` call -- there log Z of the ring stands for both ``lognorm`` columns, and ``inside_p`` is the sum of the
+        ring's marginals over the cluster labels.  The results are in the caller's contig order."""
+        from . import packing
+
+        n, nc = int(item_ptr[-1]), len(contigs)
+        bg = self.classes_.index(self.background)
+        y, score, lognorm_c, lognorm = np.zeros(n, dtype=np.int8), np.zeros(nc), np.zeros(nc), np.zeros(nc)
+        inside_p = np.zeros(n) if marginals else None
+        for ring in (False, True):
+            keep = [ci for ci in range(nc) if bool(is_ring[ci]) == ring]
+            if not keep:
+                continue
+            at = np.concatenate([np.arange(item_ptr[ci], item_ptr[ci + 1]) for ci in keep])
+            sub = packing.pack_contigs([contigs[ci] for ci in keep], self._attr_index, "protein")
+            csr = (sub.item_ptr.astype(np.int32), sub.attr_ptr.astype(np.int32), sub.attr_id)
+            masks = None if allowed is None else np.ascontiguousarray(np.asarray(allowed)[at])
+            if ring:
+                out = model.ring(*csr, device=self.device, allowed=masks, want_path=True, want_marginals=marginals)
+                y[at], score[keep], lognorm_c[keep], lognorm[keep] = out["labels"], out["score"], out["lognorm"], out["lognorm"]
+                if marginals:
+                    inside_p[at] = np.delete(out["marginals"], bg, axis=1).sum(axis=1)
+            else:
+                y[at], score[keep], lognorm_c[keep], lognorm[keep] = model.viterbi_min_run(*csr, self._cluster_set(), 1,
+                                                                                            device=self.device, allowed=masks)
+                if marginals:
+                    inside_p[at] = model.marginals_min_run(*csr, self._cluster_set(), 1, device=self.device, allowed=masks,
+                                                           want_marginals=False)[1]
+        return y, score, lognorm_c, lognorm, inside_p
 
     def _whole_contigs(self, genes: Iterable[Any], known: Optional[tables.ClusterTable]):
         """``(contigs, CSR arrays, known masks or None)`` of the caller's genes sorted by (sequence, start), for a whole-contig
@@ -1313,19 +1373,24 @@ def write_boundaries(path, clusters: Sequence[Any], floor: float = 1e-6) -> None
                     out.write("\t".join((str(cluster.id), side, str(gene.protein.id), str(position), repr(p))) + "\n")
 
 
-def write_path_clusters(path, clusters: Sequence[Any], marginals: bool = False) -> None:
+def write_path_clusters(path, clusters: Sequence[Any], marginals: bool = False, wraps: bool = False) -> None:
     """``path_clusters.tsv``: one row per cluster of ``predict_path_clusters``, columns ``sequence_id, cluster_id, start, end,
     genes, type`` (type: the ``";"``-joined names, ``"Unknown"`` for a label without types); with ``marginals`` (clusters of
-    ``predict_path_clusters(..., marginals=True)``) ``average_p, max_p, min_p`` behind them, floats with ``repr``."""
+    ``predict_path_clusters(..., marginals=True)``) ``average_p, max_p, min_p`` behind them, floats with ``repr``; with ``wraps``
+    (clusters of ``predict_path_clusters(..., circular=...)``) a last column ``wraps``, 1 for a cluster that crosses the cut of
+    its circular contig and 0 otherwise.  Such a cluster's row has ``start`` > ``end``: it runs from the start of its first
+    gene, near the contig's end, across the origin to the end of its last gene."""
     more = ("average_p", "max_p", "min_p") if marginals else ()
     with open(path, "w") as out:
-        out.write("\t".join(("sequence_id", "cluster_id", "start", "end", "genes", "type") + more) + "\n")
+        out.write("\t".join(("sequence_id", "cluster_id", "start", "end", "genes", "type") + more + (("wraps",) if wraps else ())) + "\n")
         for cluster in clusters:
             members = cluster.genes
             names = getattr(cluster, "path_type", None) or ";".join(sorted(getattr(cluster.type, "names", ()))) or UNKNOWN
-            out.write("\t".join((str(members[0].source.id), str(cluster.id), str(min(g.start for g in members)),
-                                 str(max(g.end for g in members)), str(len(members)), names,
-                                 *(repr(float(getattr(cluster, name))) for name in more))) + "\n")
+            across = bool(getattr(cluster, "wraps_origin", False))
+            start, end = (members[0].start, members[-1].end) if across else (min(g.start for g in members), max(g.end for g in members))
+            out.write("\t".join((str(members[0].source.id), str(cluster.id), str(start), str(end), str(len(members)), names,
+                                 *(repr(float(getattr(cluster, name))) for name in more),
+                                 *((str(int(across)),) if wraps else ()))) + "\n")
 
 
 def write_path_genes(path, columns) -> None:
@@ -1463,6 +1528,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --path-clusters M: add average_p, max_p and min_p to path_clusters.tsv, of the probability that a "
                     "gene lies in a region given that no region has fewer than M genes; write path_genes.tsv, that probability "
                     "per gene")
+    pr.add_argument("--circular", default=None, metavar="FILE|all",
+                    help="with --path-clusters 1: the contigs that are rings (complete chromosomes, plasmids) -- a file with one "
+                    "sequence id per line, or `all`; a region across the cut of such a contig is one cluster, and "
+                    "path_clusters.tsv gains the column wraps")
     pr.add_argument("--cluster-counts", type=int, default=None, metavar="K",
                     help="write cluster_counts.tsv: per contig the exact whole-contig probability that it holds 0, 1, ... K - 1 "
                     "clusters and at least K (at most 32), and the most probable number")
@@ -1506,6 +1575,15 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise ValueError(f"--path-clusters {args.path_clusters} is outside 1 .. 32")
     if args.path_marginals and args.path_clusters is None:
         raise ValueError("--path-marginals needs --path-clusters M")
+    circular = None
+    if args.circular is not None:
+        if args.path_clusters is None:
+            raise ValueError("--circular needs --path-clusters 1")
+        if args.circular == "all":
+            circular = True
+        else:
+            with open(args.circular) as fh:
+                circular = [line.strip() for line in fh if line.strip()]
     if args.cluster_counts is not None and not 1 <= args.cluster_counts <= 32:
         raise ValueError(f"--cluster-counts {args.cluster_counts} is outside 1 .. 32")
     if args.exact_clusters is not None and not 0 <= args.exact_clusters <= 31:
@@ -1539,8 +1617,9 @@ def main(argv: Optional[List[str]] = None) -> int:
         known = None if args.known is None else tables.ClusterTable.load(args.known)
         write_path_clusters(os.path.join(args.output_dir, "path_clusters.tsv"),
                             crf.predict_path_clusters(genes, known=known, marginals=args.path_marginals,
-                                                      **({"length_model": True} if args.length_model else {"min_run": args.path_clusters})),
-                            marginals=args.path_marginals)
+                                                      **({"length_model": True} if args.length_model else {"min_run": args.path_clusters}),
+                                                      **({} if args.circular is None else {"circular": circular})),
+                            marginals=args.path_marginals, **({} if args.circular is None else {"wraps": True}))
         if args.path_marginals:
             write_path_genes(os.path.join(args.output_dir, "path_genes.tsv"), crf.path_genes_)
         write_paths(os.path.join(args.output_dir, "paths.tsv"), crf.path_posteriors_)

@@ -54,7 +54,7 @@ const char *gecco_crf_last_error(void);
  * gecco_crf_viterbi_kbest, ABI 2.19.0 gecco_crf_edge_posteriors, ABI 2.20.0 gecco_crf_viterbi_min_run, ABI 2.21.0
  * gecco_crf_run_posteriors, ABI 2.22.0 gecco_crf_marginals_min_run, ABI 2.23.0 gecco_crf_run_counts, ABI 2.24.0
  * gecco_crf_span_conditionals, ABI 2.25.0 gecco_crf_max_marginals, ABI 2.26.0 the *_create_weighted trainers, ABI 2.27.0
- * gecco_crf_viterbi_run_length and gecco_crf_marginals_run_length. */
+ * gecco_crf_viterbi_run_length and gecco_crf_marginals_run_length, ABI 2.28.0 gecco_crf_ring. */
 int gecco_crf_version(void);
 
 /* ---- model (replaces [EXT] pycrfsuite.Tagger.open / labels() / info(); the blob is the
@@ -1089,6 +1089,54 @@ int gecco_crf_marginals_min_run(const gecco_crf_model *m, int32_t device, const 
                                 const uint32_t *allowed /* NULL: no masks */, uint32_t set_mask, int32_t min_run,
                                 double *marg /* [n_genes][L] or NULL */, double *inside /* [n_genes] or NULL */,
                                 double *lognorm_min_run /* [n_contigs] */, double *lognorm /* [n_contigs] or NULL */);
+
+/* ---- circular contigs (ABI 2.28.0, additive; gecco_crf_version() stays 340) ----------------------------------------------------------
+ * EVERY contig of the call is a RING: a complete chromosome or plasmid, whose last gene has a transition into its first.  (The
+ * caller splits a mixed batch: the linear contigs go to the other entries.)  A ring of n >= 1 genes has n edges, t -> (t + 1) mod n,
+ * all scored by the model's one transition table:
+ *     score(y) = sum_t state_t[y_t] + sum_{t = 0 .. n-1} trans[y_t][y_{(t+1) mod n}]
+ * so a ring of one gene has the self-edge trans[y_0][y_0] and a ring of two genes both trans[y_0][y_1] and trans[y_1][y_0].
+ * lognorm_ring[c] = log Z_ring, the log-mass of all label paths of ring c; marg[g][j] = P(gene g has label j | x) on the ring; y the
+ * ring's best path and score[c] its score, closing edge included.  None of them depends on where the ring was cut: rotating the
+ * genes of a ring rotates marg and y and keeps lognorm_ring and score (up to rounding; exactly with integer weights and a unique
+ * best path).  The chain entries do not have that property.  With `allowed` (one mask per gene, as the *_constrained entries take
+ * them) a path with a disallowed label does not exist, and lognorm_ring is the restricted log Z.  attr_value and allowed may each
+ * be NULL.  The walks are parallel over rings and labels and sequential along a ring (rings are not chunked).
+ *   * Recursions.  Exact inference conditions on the start label a = y_0; the lattice is the whole-contig one expanded by a, and
+ *     the L conditioned chains meet at the closing edge only.  With R the max-shifted log-sum-exp (sum semiring) or the max:
+ *       F_0[a][j] = state_0[a] if j = a, else -infinity;   F_t[a][j] = R_i(F_{t-1}[a][i] + trans[i][j]) + state_t[j];
+ *       closed[a] = R_j(F_{n-1}[a][j] + trans[j][a]);       log Z_ring = LSE_a closed[a];
+ *       B_{n-1}[a][i] = trans[i][a];   B_t[a][i] = LSE_k((trans[i][k] + state_{t+1}[k]) + B_{t+1}[a][k]);
+ *       marg[g][i] = the sum over a, ascending, of exp((F_t[a][i] + B_t[a][i]) - log Z_ring), at most 1.
+ *     fp64 and log space throughout: any finite weights are right, and no transition range applies.  The whole-contig marginals
+ *     of the chain do not run.
+ *   * Decoding needs no L * L back-pointer table.  Pass one is a max-plus walk over all start labels without back-pointers; it
+ *     leaves closed[a] = max_j(V_{n-1}[a][j] + trans[j][a]) and a* = its arg max.  Pass two is the Viterbi walk conditioned on
+ *     y_0 = a*, with one byte of back-pointer per (gene, label); then the backtrack.  score has the bits of closed[a*]; values are
+ *     (previous + trans) + state, every addition rounded on its own.
+ *   * Tie rule.  Equal closed[a]: the smaller a.  Inside the conditioned walk: gecco_crf_viterbi's rule, sources in ascending label
+ *     order with a strict `>` (the earlier source wins).  The last label is the first arg max of V_{n-1}[a*][j] + trans[j][a*].
+ *   * Outputs that are not asked for are neither computed nor stored: the two max-plus passes run only for y (int8 [n_genes])
+ *     and score (double [n_contigs]), which go together; the forward workspace and the backward walk only for marg (double
+ *     [n_genes][num_labels]).  lognorm_ring (double [n_contigs]) is required, and asking for the others changes no byte of it,
+ *     nor do they change each other's.  A disallowed (gene, label) pair gives exactly 0.0 in marg.  A ring without a feasible
+ *     path gives lognorm_ring and score -infinity, 0.0 at every gene of marg and label -1 at every gene; never NaN.  A ring
+ *     without genes gets 0 for lognorm_ring and score and nothing else.  contig_ptr[0] > 0 works as in the other one-shots.
+ *   * Workspace: the forward values, 8 * n_genes * L * L bytes (and 8 bytes per gene and per ring behind them: the sum walks
+ *     keep their values small by a shift per gene, which never enters a marginal), for marg only; the back-pointers,
+ *     n_genes * L bytes, for y only.
+ *     Sizes are computed in size_t; a failed allocation is GECCO_CRF_ENOMEM.
+ *   * Determinism: no atomics.  Equal calls give equal bytes, and a ring's bytes do not depend on the other rings of the batch.
+ *   * Limits: num_labels <= 32.
+ *   * Refused on the host before the device is looked at, GECCO_CRF_EINVAL, every message prefixed "ring:": lognorm_ring NULL,
+ *     y without score or score without y, more than 32 labels.  The checks of the *_valued and *_constrained entries apply to
+ *     attr_value and allowed, with one exception: a mask of 0 is taken here, and the ring of such a gene has no feasible path.
+ * One device per call, one plan over the whole batch (no session, batch-driver or multi-device form); rings are not chunked. */
+int gecco_crf_ring(const gecco_crf_model *m, int32_t device, const int32_t *contig_ptr, int32_t n_contigs,
+                   const int32_t *gene_ptr, const int32_t *attr_id, const double *attr_value /* NULL: no values */,
+                   const uint32_t *allowed /* NULL: no masks */, int8_t *y /* [n_genes] or NULL */,
+                   double *score /* [n_contigs] or NULL */, double *marg /* [n_genes][L] or NULL */,
+                   double *lognorm_ring /* [n_contigs] */);
 
 /* ---- run-length potentials: decoding (ABI 2.27.0, additive; gecco_crf_version() stays 340) ---------------------------------------
  * A score on the LENGTH of a run, on the whole-contig lattice of gecco_crf_viterbi and gecco_crf_marginals_full (not a windowed
